@@ -2,6 +2,8 @@
 """Nef-Net train-step benchmark (BASELINE.json metric: ECG-samples/sec of one train step).
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full            (+ breakdown, roofline, secondary, CPU baseline)
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR (+ the last timed step's results as DIR/*.npy)
     python bench.py --gpus 8 --steps 10 --warmup 3        (re-executes itself under torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -9,12 +11,13 @@
 One process per GPU; each rank trains on its own shard of the synthetic batch (weak scaling: per-GPU batch
 fixed), gradients are summed with ONE RCCL all-reduce of the flat gradient buffer per step.  A step is
 forward + losswrapper + backward + fused momentum-SGD on inputs already resident in HBM.  Rank 0 prints one
-JSON line.  At N=1 the line also carries the CPU baseline (the torch-CPU oracle timed on this box's host cores on
-a bounded sample of the same workload), the roofline of the dominant kernel (the k=7 grouped-conv MFMA kernel: EXECUTED
-matrix-core flops over its HIP-event time on the launch stream, against the fp32 MFMA peak; `roofline.whole_step`: the
-executed matrix work of the WHOLE step over ms_per_step against the same peak) and `secondary`: the reference's own training
-shape (batch 32, 3 leads, len 512) eager and graph-replayed, and the two inference configs of BASELINE.json (configs[3] panorama
-sweep, configs[4] per-GPU share of gen_ecg), all timed after the train step.
+JSON line.  A plain run sets up, warms up, times the --steps steps and prints the headline; everything else is measured only
+with --full.  With --full, the line also carries the per-kernel breakdown of extra single-stream steps and, at N=1, the CPU
+baseline (the torch-CPU oracle timed on this box's host cores on a bounded sample of the same workload), the roofline of the
+dominant kernel (the k=7 grouped-conv MFMA kernel: EXECUTED matrix-core flops over its HIP-event time on the launch stream,
+against the fp32 MFMA peak; `roofline.whole_step`: the executed matrix work of the WHOLE step over ms_per_step against the same
+peak) and `secondary`: the reference's own training shape (batch 32, 3 leads, len 512) eager and graph-replayed, and the two
+inference configs of BASELINE.json (configs[3] panorama sweep, configs[4] per-GPU share of gen_ecg), all timed after the train step.
 """
 import argparse
 import json
@@ -48,20 +51,48 @@ def parse():
     ap.add_argument("--cpu-threads", type=str, default="16,1",
                     help="thread pools to time the CPU baseline with ('all' = os.cpu_count(): 5 MINUTES PER STEP on the "
                          "256-core GPU box, profiles/r02_cpu_thread_sweep.md); the best one is headlined")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-dropout", action="store_true")
     ap.add_argument("--no-kernel-events", action="store_true",
-                    help="do not bracket launches with HIP events (roofline / hbm_bound are then null): at launch-bound "
-                         "shapes the ~250 event pairs per step cost more host time than the launches themselves")
+                    help="--full without the breakdown steps: do not bracket launches with HIP events (roofline / hbm_bound are then "
+                         "null): at launch-bound shapes the ~250 event pairs per step cost more host time than the launches themselves")
     ap.add_argument("--graph", action="store_true", help="(default) the timed steps replay the captured hipGraph of the step")
     ap.add_argument("--no-graph", action="store_true",
                     help="issue every launch of the timed steps from Python instead (what the per-kernel breakdown steps always do)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the configs[3] / configs[4] inference timings")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the secondary workloads (configs[3] / configs[4] ...)")
     ap.add_argument("--dry-collective", type=int, default=0, metavar="N",
                     help="ONE-GPU run of the N-rank data-parallel graphed step with the gradient all-reduces replaced by device-side "
                          "stand-ins of their modelled xGMI duration (parallel.DryCollective): reports allreduce_ms_exposed for the "
                          "two-graph and the one-graph schedule next to the collective-free step; prints its own JSON line")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the per-kernel breakdown / roofline, the secondary workloads and the "
+                         "CPU baseline (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (losses, updated parameters, BatchNorm buffers) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
+    return args
+
+
+DUMP_BYTES = 63 * 10 ** 6       # --dump-outputs writes at most 64 MB, .npy headers included
+
+
+def dump_outputs(out_dir, losses, model):
+    """The results a caller of the timed step receives from its last call: the loss vector [loss, f0*l1, f1*l2, f2*l3], the
+    parameters it updated (flat, model.named_parameters() order) and the BatchNorm buffers it updated (flat,
+    model.named_buffers() order).  The parameters are written whole while everything fits in DUMP_BYTES; beyond that, a fixed
+    seeded sample of them (the same indices for the same model size)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"losses": losses.detach().float().cpu().numpy(),
+              "bn_buffers": torch.cat([b.detach().double().reshape(-1).cpu() for _, b in model.named_buffers()]).numpy()}
+    params = torch.cat([p.detach().float().reshape(-1).cpu() for _, p in model.named_parameters()]).numpy()
+    room = (DUMP_BYTES - sum(a.nbytes for a in arrays.values())) // params.itemsize
+    if params.size > room:
+        params = params[np.sort(np.random.default_rng(0).choice(params.size, room, replace=False))]
+    arrays["parameters"] = params
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def make_cfg(V):
@@ -374,6 +405,8 @@ def main():
     dev = torch.device("cuda", local)
     torch.cuda.set_device(dev)
     if args.dry_collective > 1:
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs writes the results of the headline step, which --dry-collective does not run")
         if world != 1:
             raise SystemExit("--dry-collective models the collectives of an N-rank job on ONE GPU: run it with --gpus 1")
         return dry_collective(args, dev)
@@ -401,14 +434,15 @@ def main():
         graphed = GraphedTrainStep(model, cfg, optimizer=optim)
 
     def step(eager=False):
+        """One train step; returns its losses [loss, f0*l1, f1*l2, f2*l3] (a device vector, or a tuple of 0-dim tensors)."""
         if graphed is not None and not eager:
-            return graphed(data, in_theta, tgt_theta, rois, tgt_view)[0]
+            return graphed(data, in_theta, tgt_theta, rois, tgt_view)
         out, sp, sl = model(data, in_theta, tgt_theta, rois, phase="train")
         losses = lossf(out, sp, sl, tgt_view, cfg)
         losses[0].backward()
         optim.step()
         optim.zero_grad()
-        return losses[0]
+        return losses
 
     def fence():
         torch.cuda.synchronize(dev)
@@ -426,7 +460,8 @@ def main():
     T_lat = L // 4
     dom = {("conv_fwd", 7, V, 128, 128, B, T_lat), ("conv_bwd_data", 7, V, 128, 128, B, T_lat),
            ("conv_bwd_weight", 7, V, 128, 128, B, T_lat)}
-    timing = rank == 0 and not args.no_kernel_events and not args.graph
+    kernel_events = args.full and not args.no_kernel_events
+    timing = rank == 0 and kernel_events and not args.graph
     ops.PROFILE, ops.PROFILE_ONLY = ([] if timing else None), (lambda tag: tag in dom)
     parallel.TIMING = [] if (world > 1 and rank == 0) else None      # events around the exposed part of the gradient all-reduce
     t0 = time.perf_counter()
@@ -436,9 +471,11 @@ def main():
     dt = time.perf_counter() - t0
     prof, ops.PROFILE, ops.PROFILE_ONLY = ops.PROFILE or [], None, None
     ar_events, parallel.TIMING = parallel.TIMING or [], None
-    final_loss_t = loss.detach().clone()      # (the graphed step returns a view of its static loss buffer)
+    final_loss_t = loss[0].detach().clone()      # (the graphed step returns its static loss buffer)
+    if args.dump_outputs and rank == 0:           # before anything else steps the model
+        dump_outputs(args.dump_outputs, torch.stack([v.detach() for v in loss[:4]]), model)
     prof_all, extra_steps = [], 2
-    if not args.no_kernel_events:       # every rank takes the extra steps (they contain the all-reduce); always issued eagerly
+    if kernel_events:       # every rank takes the extra steps (they contain the all-reduce); always issued eagerly
         # Per-kernel breakdown: untimed extra steps with EVERY launch bracketed, on ONE stream (NEF_SIDE_STREAM=0 is read per
         # step by engine._side), so each kernel has the chip to itself and its event time is its own duration -- in the
         # default two-stream schedule a chain kernel that shares the chip with a side-stream weight-gradient kernel reads
@@ -624,7 +661,7 @@ def main():
                 "ms_per_step": round(sum(v) / max(extra_steps, 1), 3), "floor_ms": pr["floor_ms"], "bound": pr["bound"],
                 "mfma_floor_ms": pr["mfma_floor_ms"], "hbm_floor_ms": pr["hbm_floor_ms"], "frac": pr["frac"]}
         sec = None
-        if world == 1 and not args.no_secondary:
+        if world == 1 and args.full and not args.no_secondary:
             del model, optim, data, loss, final_loss_t
             torch.cuda.empty_cache()
             try:
@@ -632,7 +669,7 @@ def main():
             except Exception as exc:  # the headline stays valid; the failure is visible in the line
                 sec = {"error": f"{type(exc).__name__}: {exc}"}
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cpu = cpu_baseline(V, L, args.cpu_batch, args.cpu_steps, args.cpu_threads.split(","))
         line = {
             "metric": "ECG-samples/sec (train step)", "value": round(world * B * args.steps / dt, 2),

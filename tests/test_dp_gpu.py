@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 import torch
 
-from util import rel
+from util import free_port, rel
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,7 +29,8 @@ def _env(port):
 def dp_run(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("dp2"))
     script = os.path.join(ROOT, "tests", "dp2_worker.py")
-    procs = [subprocess.Popen([sys.executable, script, out], env=dict(_env(29681), RANK=str(r), LOCAL_RANK=str(r)),
+    env = _env(free_port())
+    procs = [subprocess.Popen([sys.executable, script, out], env=dict(env, RANK=str(r), LOCAL_RANK=str(r)),
                               stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for r in range(2)]
     logs = [p.communicate(timeout=900)[0] for p in procs]
     assert all(p.returncode == 0 for p in procs), "\n".join(lg[-3000:] for lg in logs)
@@ -130,7 +131,7 @@ def test_world2_rccl_on_two_devices(tmp_path):
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two HIP devices (RCCL between two ranks)")
     out = str(tmp_path)
-    env = _env(29685)
+    env = _env(free_port())
     env.pop("NEF_DIST_BACKEND")
     env.pop("NEF_SHARE_GPU")
     script = os.path.join(ROOT, "tests", "dp2_worker.py")
@@ -188,10 +189,11 @@ def test_world2_clamp_on_one_rank_skips_the_step_on_both(dp_run):
 
 def test_bench_two_ranks_prints_one_json_line():
     """bench.py's torchrun branch (barrier, max-over-ranks timing, whole-job value) with world_size 2."""
+    port = free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", "29683", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
+           "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
            "--warmup", "1", "--batch", "8", "--len", "1000", "--leads", "8"]
-    env = _env(29683)
+    env = _env(port)
     env.pop("WORLD_SIZE")
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]

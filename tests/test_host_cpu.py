@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from util import free_port
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -100,7 +102,7 @@ def test_data_parallel_plumbing_gloo_world2(tmp_path):
     """Two CPU ranks over gloo: batch sharding covers the global batch exactly once, and the flat-gradient
     all-reduce + 1/world averaging that FusedSGD performs matches a single-process run on the full batch."""
     script = os.path.join(ROOT, "tests", "dp_worker.py")
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29671", PYTHONPATH=ROOT)
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()), PYTHONPATH=ROOT)
     procs = [subprocess.Popen([sys.executable, script, str(r), "2", str(tmp_path)], env=env) for r in range(2)]
     assert all(p.wait(timeout=300) == 0 for p in procs)
     a, b = (np.load(os.path.join(tmp_path, f"rank{r}.npz")) for r in range(2))

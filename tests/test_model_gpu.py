@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from decisions import FLAT_TOL, TENSOR_TOL, assert_flips_are_ties, assert_grad_parity, gpu_decisions
-from util import FWD_TOL, maxabs, rel, stats, sub
+from util import FWD_TOL, free_port, maxabs, rel, stats, sub
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -290,7 +290,7 @@ def test_train_vs_oracle_live():
 
 
 @pytest.mark.parametrize("graph", [False, True], ids=["eager", "graphed"])
-def test_sgd_steps_golden(golden_dir, graph):
+def test_sgd_steps_golden(golden_dir, graph, tmp_path):
     """Three iterations of Solver.run_one_epoch(phase='train') vs the reference Solver's trajectory -- eagerly, and through
     the captured hipGraph the Solver uses at launch-bound shapes (cfg.SOLVER.graph; FusedSGD's flat buffers stepped)."""
     from electrocardio_panorama_amd import synth
@@ -324,7 +324,7 @@ def test_sgd_steps_golden(golden_dir, graph):
     import conftest
     conftest.report(f"3-step SGD trajectory vs the reference Solver ({'graphed' if graph else 'eager'}): worst parameter "
                     f"{worst[1]} rel-L2 {worst[0]:.2e} (bar 2e-4)")
-    with open(os.path.join(os.environ.get("NEF_TEST_LOG_DIR", "/tmp"), "sgd_trajectory.txt"), "w") as fh:
+    with open(os.path.join(os.environ.get("NEF_TEST_LOG_DIR", str(tmp_path)), "sgd_trajectory.txt"), "w") as fh:
         fh.write(f"3-step SGD trajectory vs the reference Solver: worst parameter {worst[1]} rel-L2 {worst[0]:.2e} (bar 2e-4)\n")
     for k in orc.buffer_shapes():
         if "running" in k:
@@ -476,7 +476,7 @@ def test_config3_shard_full_size_is_deterministic_and_fits():
 
 
 @pytest.mark.parametrize("B", [256], ids=["B256"])
-def test_full_size_train_gradients_vs_oracle(record_property, B):
+def test_full_size_train_gradients_vs_oracle(record_property, B, tmp_path):
     """BASELINE configs[1] at FULL size in TRAIN mode (256 x 3 x 5000, dropout masks replayed, batch-statistics
     BatchNorm over 3.84 M elements per channel, split-K weight gradients over 320 k columns): outputs, losses, BN running
     statistics and EVERY gradient tensor against the CPU oracle on the same batch, at the tie-free bars.  The oracle
@@ -523,7 +523,7 @@ def test_full_size_train_gradients_vs_oracle(record_property, B):
            f"replayed ties {dec.total_flips()}")
     print(msg)
     conftest.report(msg)
-    with open(os.path.join(os.environ.get("NEF_TEST_LOG_DIR", "/tmp"), "full_size_parity.txt"), "w") as fh:
+    with open(os.path.join(os.environ.get("NEF_TEST_LOG_DIR", str(tmp_path)), "full_size_parity.txt"), "w") as fh:
         fh.write(msg + "\n")
     m.last_saved = None
 
@@ -922,7 +922,7 @@ def test_rccl_single_rank():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
-           "127.0.0.1", "--master-port", "29533", os.path.join(root, "tests", "rccl_worker.py")]
+           "127.0.0.1", "--master-port", str(free_port()), os.path.join(root, "tests", "rccl_worker.py")]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "RCCL_OK" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
 

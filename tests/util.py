@@ -1,5 +1,15 @@
+import socket
+
 import numpy as np
 import torch
+
+
+def free_port():
+    """A TCP port on 127.0.0.1 that nothing listens on now: the rendezvous port of a multi-process test (a fixed number
+    collides with another run of the suite on the same host)."""
+    with socket.socket() as sk:
+        sk.bind(("127.0.0.1", 0))
+        return sk.getsockname()[1]
 
 
 def rel(a, b):

@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r6a; rm -rf $O; mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -q -x > $O/pytest.log 2>&1; tail -n 5 $O/pytest.log | cut -c1-300
-timeout 600 python bench.py > $O/bench.log 2>&1; tail -n 1 $O/bench.log > $O/bench_line.json
+timeout 600 python bench.py --full > $O/bench.log 2>&1; tail -n 1 $O/bench.log > $O/bench_line.json
 python - <<'PY'
 import json
 d=json.load(open('gpurun_out/r6a/bench_line.json'))

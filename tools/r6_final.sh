@@ -12,8 +12,8 @@ rm -rf $O/graph
 timeout 600 rocprofv3 --kernel-trace --stats -d $O/small -o t -- python bench.py --batch 32 --len 512 --steps 9 --warmup 1 --no-cpu-baseline --no-kernel-events --no-secondary > $O/small.log 2>&1
 python tools/rocprof_summary.py $(find $O/small -name "*results.db" | head -1) $O/r06_small32_graph_kernel_stats.md 11 2 > /dev/null
 rm -rf $O/small
-timeout 900 python bench.py > $O/bench.log 2>&1; tail -n 1 $O/bench.log > $O/r06_bench_line.json
-timeout 600 python bench.py --leads 8 --no-cpu-baseline --no-secondary > $O/bench8.log 2>&1; tail -n 1 $O/bench8.log > $O/r06_bench_line_8lead_shard.json
+timeout 900 python bench.py --full > $O/bench.log 2>&1; tail -n 1 $O/bench.log > $O/r06_bench_line.json
+timeout 600 python bench.py --full --leads 8 --no-cpu-baseline --no-secondary > $O/bench8.log 2>&1; tail -n 1 $O/bench8.log > $O/r06_bench_line_8lead_shard.json
 timeout 600 python bench.py --leads 8 --dry-collective 8 --steps 10 --warmup 3 > $O/dry8.log 2>&1; tail -n 1 $O/dry8.log > $O/r06_dry_collective_8lead.json
 timeout 600 python bench.py --dry-collective 8 --steps 20 --warmup 5 > $O/dry3.log 2>&1; tail -n 1 $O/dry3.log > $O/r06_dry_collective_3lead.json
 python - <<'PY'
