@@ -7,13 +7,11 @@ import ctypes as C
 import os
 
 import torch  # noqa: F401  (first: the library must bind to the HIP runtime PyTorch-ROCm has already loaded)
-from . import _env
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = _env.get("NEF_LIB") or os.path.join(_HERE, "csrc", "libnefnet_hip.so")   # NEF_LIB: A/B builds
+LIB_PATH = os.path.join(_HERE, "csrc", "libnefnet_hip.so")
 
 NEF_OK = 0
-OPT_H2_FORM, OPT_H2P_WGS = 1, 2      # nef_set_option keys (include/nefnet_hip.h)
 _ERR = {-1: "NEF_E_SHAPE", -2: "NEF_E_NULL", -3: "NEF_E_WORKSPACE", -4: "NEF_E_UNSUPPORTED"}
 
 p = C.c_void_p
@@ -49,8 +47,7 @@ class PackDesc(C.Structure):
 # name -> (restype, argtypes); every symbol include/nefnet_hip.h declares
 SIGNATURES = {
     "nef_abi_version": (i32, []),
-    "nef_set_option": (i32, [i32, i32]),
-    "nef_get_option": (i32, [i32]),
+    "nef_debug_spin_us": (i32, [f32, i32, p]),
     "nef_stem_fwd": (i32, [p, p, p, i32, i32, i32, p]),
     "nef_stem_bwd_ws_bytes": (sz, [i32]),
     "nef_stem_bwd_weight": (i32, [p, p, p, p, p, sz, i32, i32, i32, p]),
@@ -107,7 +104,6 @@ SIGNATURES = {
     "nef_mix_bwd_up": (i32, [p, p, p, p, p, p, p, p, i32, i32, i32, i32, i32, p, i32, p]),
     "nef_upsample2_fwd": (i32, [p, p, i64, i32, p]),
     "nef_upsample2_bwd": (i32, [p, p, i64, i32, p]),
-    "nef_upsample2_aff_fwd": (i32, [p, p, p, p, i32, i32, i32, i32, p]),
     "nef_bn_ws_bytes": (sz, [i32, i32]),
     "nef_bn_train_stats": (i32, [p, p, p, p, p, p, p, p, p, p, sz, i32, i32, i32, i32, f32, f32, p, p]),
     "nef_conv_stats_slots": (i32, [i32, i32]),
@@ -175,7 +171,6 @@ def load():
         fn = getattr(lib, name)        # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
-    lib.nef_debug_spin_us.restype, lib.nef_debug_spin_us.argtypes = i32, [f32, i32, p]      # diagnostics, not in the header
     if lib.nef_conv_args_bytes() != C.sizeof(ConvArgs):      # a stale .so next to a newer binding (or the reverse)
         raise NefLibraryError(f"{LIB_PATH}: nef_conv_args is {lib.nef_conv_args_bytes()} bytes, the binding mirrors "
                               f"{C.sizeof(ConvArgs)}; rebuild with `python -m electrocardio_panorama_amd.csrc.build`")

@@ -29,20 +29,10 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-#ifndef NEF_GL_ABL
-#define NEF_GL_ABL 0      // timing-only builds (results wrong): 1 = no DMA inside the loop, 2 = fragments read once per tile
-#endif
-
-#ifndef NEF_GL_OCC
-#define NEF_GL_OCC 3      // workgroups per CU the register allocation aims at (168 VGPRs)
-#endif
-
 namespace {
 
-#ifndef NEF_GL_TW
-#define NEF_GL_TW 32
-#endif
-constexpr int TW = NEF_GL_TW;          // reduction columns per staged tile
+constexpr int GL_OCC = 3;              // workgroups per CU the register allocation aims at (168 VGPRs)
+constexpr int TW = 32;                 // reduction columns per staged tile
 constexpr int ROWS = 64;               // gY rows (co) and X rows (ci) of a workgroup
 constexpr int GCH = (TW / 4) | 1;      // 16-byte chunks per gY image row (TW / 4 fetched + 1 so that the pitch is odd)
 
@@ -58,7 +48,7 @@ __device__ __forceinline__ void wait_vm() {
 // (nn.Upsample(scale_factor=2, mode='linear', align_corners=False): pro_mode 2) -- the X image then holds the T/2-resolution
 // samples x[t0/2 - 1 .. t0/2 + 18), and a quad's six inputs are interpolated from four of them.
 template <int K, bool AFF, int WINO, int NBUF, bool UP = false>
-__global__ __launch_bounds__(256, NEF_GL_OCC) void conv_bww_glds_kernel(
+__global__ __launch_bounds__(256, GL_OCC) void conv_bww_glds_kernel(
     const float* __restrict__ x, int64_t x_bs, int64_t x_gs, const float* __restrict__ gy, int64_t gy_bs, int64_t gy_gs,
     float* __restrict__ ws, int B, int T, int G, int Cig, int Cog, int tps, int n_tiles, int m_tiles, int ci_chunks, int S,
     const float* __restrict__ pro_a, const float* __restrict__ pro_b, int pro_Bp, int n_pass, int64_t x_extent,
@@ -184,9 +174,7 @@ __global__ __launch_bounds__(256, NEF_GL_OCC) void conv_bww_glds_kernel(
         // tile k has landed once at most the pieces of the tiles issued after it are outstanding
         {
             const int after = n_k - 1 - k;
-            if (NEF_GL_ABL & 1) {
-                wait_vm<0>();
-            } else if (after >= NBUF - 2) {
+            if (after >= NBUF - 2) {
                 if (full_w) wait_vm<(NBUF - 2) * NPW>(); else wait_vm<(NBUF - 2) * (NPW - 1)>();
             } else if (NBUF > 3 && after == NBUF - 3) {
                 if (full_w) wait_vm<(NBUF - 3) * NPW>(); else wait_vm<(NBUF - 3) * (NPW - 1)>();
@@ -195,7 +183,7 @@ __global__ __launch_bounds__(256, NEF_GL_OCC) void conv_bww_glds_kernel(
             }
         }
         __builtin_amdgcn_s_barrier();       // every wave's pieces of tile k are in LDS; every wave is done with tile k - 1
-        if (!(NEF_GL_ABL & 1) && k + NBUF - 1 < n_k) {
+        if (k + NBUF - 1 < n_k) {
             const int nb = buf == 0 ? NBUF - 1 : buf - 1;          // the buffer tile k - 1 was read from
             NEF_GL_ISSUE(nb)
         }
@@ -258,7 +246,7 @@ __global__ __launch_bounds__(256, NEF_GL_OCC) void conv_bww_glds_kernel(
             pa = tab[pass * 128 + wci * 32 + lo];
             pb = tab[pass * 128 + 64 + wci * 32 + lo];
         }
-        constexpr int NSTEP = (NEF_GL_ABL & 4) ? 0 : TW / 8;      // ABL 4: no fragment reads, transforms, MFMAs at all
+        constexpr int NSTEP = TW / 8;
         if constexpr (WINO == 4) {
             // taps 0..3: quad j = 2s + hi, gy[4j .. 4j+3] against d_m = x[4j-3+m], m = 0..6 (image positions 4j + m)
             f32x4 fg[2], fa[2], fb[2];
@@ -271,7 +259,7 @@ __global__ __launch_bounds__(256, NEF_GL_OCC) void conv_bww_glds_kernel(
             if (NSTEP) NEF_GL_LOAD(0, 0)
 #pragma unroll
             for (int s_ = 0; s_ < NSTEP; ++s_) {
-                if (!(NEF_GL_ABL & 2) && s_ + 1 < NSTEP) NEF_GL_LOAD(s_ + 1, (s_ + 1) & 1)
+                if (s_ + 1 < NSTEP) NEF_GL_LOAD(s_ + 1, (s_ + 1) & 1)
                 const float g0 = fg[s_ & 1][0], g1 = fg[s_ & 1][1], g2 = fg[s_ & 1][2], g3 = fg[s_ & 1][3];
                 const float d0 = fa[s_ & 1][0], d1 = fa[s_ & 1][1], d2 = fa[s_ & 1][2], d3 = fa[s_ & 1][3];
                 const float d4 = fb[s_ & 1][0], d5 = fb[s_ & 1][1], d6 = fb[s_ & 1][2];
@@ -328,7 +316,7 @@ __global__ __launch_bounds__(256, NEF_GL_OCC) void conv_bww_glds_kernel(
             if (NSTEP) NEF_GL_LOAD(0, 0)
 #pragma unroll
             for (int s_ = 0; s_ < NSTEP; ++s_) {
-                if (!(NEF_GL_ABL & 2) && s_ + 1 < NSTEP) NEF_GL_LOAD(s_ + 1, (s_ + 1) & 1)
+                if (s_ + 1 < NSTEP) NEF_GL_LOAD(s_ + 1, (s_ + 1) & 1)
                 const float g0 = fg[s_ & 1][0], g1 = fg[s_ & 1][1], g2 = fg[s_ & 1][2], g3 = fg[s_ & 1][3];
                 float d0 = fa[s_ & 1][0], d1 = fa[s_ & 1][1], d2 = fa[s_ & 1][2], d3 = fa[s_ & 1][3];
                 float d4 = fb[s_ & 1][0], d5 = fb[s_ & 1][1];
@@ -485,19 +473,13 @@ int launch(const float* x, int64_t x_bs, int64_t x_gs, const float* gy, int64_t 
 // Ring depth.  Measured (tools/bench_conv.py, all eight weight-gradient shapes of the step): 2, 3 and 4 buffers, 32- and
 // 64-column tiles, two and three workgroups per CU all land within 3 % of each other -- with the tiles' HBM traffic at the
 // algorithmic bytes the fetch is no longer a latency problem.  Two buffers at three workgroups per CU is the smallest.
-#ifndef NEF_GLDS_NBUF
-#define NEF_GLDS_NBUF 2
-#endif
+constexpr int GL_NBUF = 2;
 
 // Shapes the LDS-DMA kernel takes (everything else stays on conv_bwd_weight_kernel): whole 64-channel slabs, at least two
 // tiles per sample, no in_scale, T % 4 == 0 with the upsampling prologue; at most 8 BatchNorm passes in the prologue table.
 extern "C" __attribute__((visibility("hidden"))) bool nef_bww_glds_ok(int B, int T, int Cig, int Cog, int K, int pro_mode, int pro_Bp,
                                                                       bool in_scale) {
-    static const int on = [] {
-        const char* e = nef_diag_env("NEF_BWW_GLDS");
-        return (e && e[0] == '0') ? 0 : 1;
-    }();
-    if (!on || in_scale || (K != 3 && K != 7) || (K == 7 && pro_mode != 0)) return false;
+    if (in_scale || (K != 3 && K != 7) || (K == 7 && pro_mode != 0)) return false;
     if ((pro_mode & 2) && T % 4 != 0) return false;
     if (Cig % ROWS != 0 || Cog % ROWS != 0 || T < 2 * TW || T % 2 != 0) return false;
     if ((int64_t)(ROWS - 1) * T * 4 + 4 * 11 * 4 >= 0x7FFFFFFCll) return false;      // per-lane offsets are 32-bit
@@ -514,20 +496,20 @@ extern "C" __attribute__((visibility("hidden"))) int nef_bww_glds_launch(
     const int n_pass = (pro_mode & 1) ? (B + pro_Bp - 1) / pro_Bp : 0;
     if (K == 3) {
         if (pro_mode == 3)
-            return launch<3, true, 2, NEF_GLDS_NBUF, true>(x, x_bs, x_gs, gy, gy_bs, gy_gs, ws, B, T, G, Cig, Cog, pro_a, pro_b, pro_Bp,
-                                                           n_pass, S_max, fixed_S, S_used, st);
-        if (pro_mode & 2)
-            return launch<3, false, 2, NEF_GLDS_NBUF, true>(x, x_bs, x_gs, gy, gy_bs, gy_gs, ws, B, T, G, Cig, Cog, nullptr, nullptr, 1,
-                                                            0, S_max, fixed_S, S_used, st);
-        if (pro_mode & 1)
-            return launch<3, true, 2, NEF_GLDS_NBUF>(x, x_bs, x_gs, gy, gy_bs, gy_gs, ws, B, T, G, Cig, Cog, pro_a, pro_b, pro_Bp,
+            return launch<3, true, 2, GL_NBUF, true>(x, x_bs, x_gs, gy, gy_bs, gy_gs, ws, B, T, G, Cig, Cog, pro_a, pro_b, pro_Bp,
                                                      n_pass, S_max, fixed_S, S_used, st);
-        return launch<3, false, 2, NEF_GLDS_NBUF>(x, x_bs, x_gs, gy, gy_bs, gy_gs, ws, B, T, G, Cig, Cog, nullptr, nullptr, 1, 0,
-                                                  S_max, fixed_S, S_used, st);
+        if (pro_mode & 2)
+            return launch<3, false, 2, GL_NBUF, true>(x, x_bs, x_gs, gy, gy_bs, gy_gs, ws, B, T, G, Cig, Cog, nullptr, nullptr, 1,
+                                                      0, S_max, fixed_S, S_used, st);
+        if (pro_mode & 1)
+            return launch<3, true, 2, GL_NBUF>(x, x_bs, x_gs, gy, gy_bs, gy_gs, ws, B, T, G, Cig, Cog, pro_a, pro_b, pro_Bp,
+                                               n_pass, S_max, fixed_S, S_used, st);
+        return launch<3, false, 2, GL_NBUF>(x, x_bs, x_gs, gy, gy_bs, gy_gs, ws, B, T, G, Cig, Cog, nullptr, nullptr, 1, 0,
+                                            S_max, fixed_S, S_used, st);
     }
     if (half == 4)
-        return launch<7, false, 4, NEF_GLDS_NBUF>(x, x_bs, x_gs, gy, gy_bs, gy_gs, ws, B, T, G, Cig, Cog, nullptr, nullptr, 1, 0,
-                                                  S_max, fixed_S, S_used, st);
-    return launch<7, false, 5, NEF_GLDS_NBUF>(x, x_bs, x_gs, gy, gy_bs, gy_gs, ws, B, T, G, Cig, Cog, nullptr, nullptr, 1, 0, S_max,
-                                              fixed_S, S_used, st);
+        return launch<7, false, 4, GL_NBUF>(x, x_bs, x_gs, gy, gy_bs, gy_gs, ws, B, T, G, Cig, Cog, nullptr, nullptr, 1, 0,
+                                            S_max, fixed_S, S_used, st);
+    return launch<7, false, 5, GL_NBUF>(x, x_bs, x_gs, gy, gy_bs, gy_gs, ws, B, T, G, Cig, Cog, nullptr, nullptr, 1, 0, S_max,
+                                        fixed_S, S_used, st);
 }

@@ -40,9 +40,6 @@
 #include "nefnet_hip.h"
 #include "nef_common.h"
 
-#ifndef NEF_H2_CLAMP
-#define NEF_H2_CLAMP 0      // 1: clamp operands at fp16's range before the split (round 4; the range rescue makes it unnecessary)
-#endif
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -71,33 +68,15 @@ __device__ __forceinline__ void split2(float x0, float x1, unsigned& h, unsigned
     asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(l) : "v"(r0), "v"(r1));
 }
 
-#ifndef NEF_H2_SPLIT
-#define NEF_H2_SPLIT 1      // 1 (round 5): the scale rides on the staging's channel-scale multiply, split by full-rate instructions
-#endif
 // split of an already scaled pair, no clamp (range rescue): h = (fp16(x0), fp16(x1)), l = (fp16(x0 - h0), fp16(x1 - h1)).  Four
-// full-rate instructions (2.2 ns of SIMD time each, profiles/r05_valu_rates.md) where split2s spends four half-rate ones (3.75 ns).
+// full-rate instructions (2.2 ns of SIMD time each, profiles/r05_valu_rates.md) where the scale folded into four half-rate
+// mixed-precision conversions (round 4) spent 3.75 ns each.
 __device__ __forceinline__ void split2n(float x0, float x1, unsigned& h, unsigned& l) {
     float r0, r1;
     asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h) : "v"(x0), "v"(x1));
     asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(h), "v"(x0));
     asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(h), "v"(x1));
     asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(l) : "v"(r0), "v"(r1));
-}
-
-// the same split with the power-of-two scale s folded into the conversions: hi = fp16(x s), lo = fp16(x s - hi), each ONE
-// mixed-precision FMA per element (x s is exact, x s - hi is exact in fp32: bit-identical to split2(x0 * s, x1 * s));
-// |x| is clamped at lim = 65000 / s first
-__device__ __forceinline__ void split2s(float x0, float x1, float s, float lim, unsigned& h, unsigned& l) {
-#if NEF_H2_CLAMP
-    x0 = __builtin_amdgcn_fmed3f(x0, -lim, lim);
-    x1 = __builtin_amdgcn_fmed3f(x1, -lim, lim);
-#else
-    (void)lim;      // no clamp: a tile whose data does not fit is redone with its own scale (range rescue), its first pass is discarded
-#endif
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "=v"(h) : "v"(x0), "v"(s));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "+v"(h) : "v"(x1), "v"(s));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(l) : "v"(x0), "v"(s), "v"(h));
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(l) : "v"(x1), "v"(s), "v"(h));
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -186,55 +165,19 @@ __global__ __launch_bounds__(256) void pack_h2_kernel(H2PackTable tab) {
 // PRO as in conv_fwd_kernel (bit0: BatchNorm affine + ReLU of the producing layer, bit1: x2 linear upsampling of a
 // half-resolution input), applied to the fp32 values before the split.
 // ------------------------------------------------------------------------------------------------------------------
-// A/B switches of the range rescue (tools/h2_rescue_ab.sh): RESCUE 0 = one pass, no second copy of the tile's work; AMAX 0 = the
-// staging does not track the operand magnitude either (x_amax_next is then not written: timing only); EPI_ALWAYS 1 = the first
-// pass runs its epilogue even when the tile has to be redone (the second pass overwrites it).
-#ifndef NEF_H2_RESCUE
-#define NEF_H2_RESCUE 1
-#endif
-#ifndef NEF_H2_AMAX
-#define NEF_H2_AMAX 1
-#endif
-#ifndef NEF_H2_EPI_ALWAYS
-#define NEF_H2_EPI_ALWAYS 0
-#endif
-// NEF_H2_SPLIT 1: the staging multiplies by (channel scale x launch scale) -- one product it does anyway, exact because the launch
-// scale is a power of two -- and splits the scaled value; the magnitude it tracks is the scaled one (divided out once per tile).
-// Bit-identical to the 0 form (scale folded into v_fma_mixlo/hi_f16).
-#if NEF_H2_SPLIT
-#define NEF_H2_SPLIT2(V0, V1, H, L) split2n(V0, V1, H, L)
-#define NEF_H2_STAGE_SCALE xs_
-#else
-#define NEF_H2_SPLIT2(V0, V1, H, L) split2s(V0, V1, xs_, xlim_, H, L)
-#define NEF_H2_STAGE_SCALE 1.f
-#endif
-#if NEF_H2_AMAX
+// The staging multiplies by (channel scale x launch scale) -- one product it does anyway, exact because the launch scale is a power
+// of two -- and splits the scaled value; the magnitude it tracks is the scaled one (divided out once per tile).  Bit-identical to
+// folding the scale into v_fma_mixlo/hi_f16 (round 4).
 #define NEF_H2_TRACK1(V) amax_ = fmaxf(amax_, fabsf(V));
 #define NEF_H2_TRACK2(V, W) amax_ = fmaxf(amax_, fmaxf(fabsf(V), fabsf(W)));
-#else
-#define NEF_H2_TRACK1(V)
-#define NEF_H2_TRACK2(V, W)
-#endif
-#ifndef NEF_H2_LAYOUT
-#define NEF_H2_LAYOUT 1
-#endif
-#ifndef NEF_H2_T
-#define NEF_H2_T 0      // timing-only builds: 1 = no activation loads in the loop, 2 = no matrix instructions, 4 = no epilogue
-#endif
-#ifndef NEF_H2_XORDER
-#define NEF_H2_XORDER 1     // 1 (round 6): tap 1's A fragments are issued in front of the next stage's activation rows (see the stage loop)
-#endif
-#ifndef NEF_H2_UP_OCC3
-#define NEF_H2_UP_OCC3 0      // 1: the x2-upsampling forms of the 64-channel tile at three workgroups per CU too
-#endif
-#ifndef NEF_H2_OCC1
-#define NEF_H2_OCC1 3      // workgroups per CU the 64-channel tile is compiled for (168 VGPRs); the x2-upsampling prologue needs 2
-#endif
+// workgroups per CU the 64-channel tile is compiled for (168 VGPRs); the x2-upsampling prologue needs 2 (at three it spills 8
+// registers and is 2 % slower)
+constexpr int H2_OCC1 = 3;
 // PACK (short rows, 8 <= T <= 64, T % 4 == 0): a tile is `tps` SAMPLES laid end to end at a pitch of T + 4 positions -- the four
 // positions between two samples are staged as zeros (the zero padding of both neighbours) and their outputs are dropped; a lane's
 // four adjacent outputs lie inside one sample or inside one gap.  No prologue, channel scale or statistics in this mode.
 template <int K, int PRO, int TM, bool PACK = false>
-__global__ __launch_bounds__(256, (TM == 1 && ((PRO & 2) == 0 || NEF_H2_UP_OCC3)) ? NEF_H2_OCC1 : 2) void conv_h2_kernel(nef_conv_args a_, int tps_, int n_tiles_, int m_tiles_) {
+__global__ __launch_bounds__(256, (TM == 1 && (PRO & 2) == 0) ? H2_OCC1 : 2) void conv_h2_kernel(nef_conv_args a_, int tps_, int n_tiles_, int m_tiles_) {
     constexpr int MT = 64 * TM;                    // output channels per workgroup: 2 (co) x 2 (t) waves of TM x 4 tiles
     constexpr bool UP = (PRO & 2) != 0, AFF = (PRO & 1) != 0;
     // PH (pro_mode 4, polyphase backward-data through a x2 upsampling): the input is a FULL-resolution tensor [Cin_g / 2][2 T] read as
@@ -253,18 +196,13 @@ __global__ __launch_bounds__(256, (TM == 1 && ((PRO & 2) == 0 || NEF_H2_UP_OCC3)
     constexpr int XROW = NTO + K - 1;              // staged positions per channel: t0 - PAD .. t0 + NTO + PAD - 1
     constexpr int P4 = (XROW + 3) / 4 + 1;         // positions per (t mod 4) class
     constexpr int PLANE = 4 * P4 * 32;             // bytes of one fp16 plane of a stage
-    // LDS image of a plane.  NEF_H2_LAYOUT 1 (round 5): [channel half][t mod 4][P4][8 channels] -- a 16-byte chunk per (position, half)
+    // LDS image of a plane (round 5): [channel half][t mod 4][P4][8 channels] -- a 16-byte chunk per (position, half)
     // at a pitch of 16 bytes, so a fragment read (lane = position, ds_read_b128) covers 256 contiguous bytes per 16-lane group:
-    // conflict-free.  0 (round 4): [t mod 4][P4][16 channels] -- 32 bytes per position, of which a lane reads one half: every
+    // conflict-free.  Round 4 used [t mod 4][P4][16 channels] -- 32 bytes per position, of which a lane reads one half: every
     // 16-lane group of a fragment read spans 512 bytes for 256 of data (2-way bank conflict), stores 4-way.
     constexpr int HALF = 4 * P4 * 16;
-#if NEF_H2_LAYOUT
 #define NEF_H2_WADDR(R, W) (((W) >> 1) * HALF + (((R) & 3) * P4 + ((R) >> 2)) * 16 + ((W) & 1) * 8)
 #define NEF_H2_RPOS(S) ((((S) & 3) * P4 + ((S) >> 2)) * 16)
-#else
-#define NEF_H2_WADDR(R, W) ((((R) & 3) * P4 + ((R) >> 2)) * 32 + 8 * (W))
-#define NEF_H2_RPOS(S) ((((S) & 3) * P4 + ((S) >> 2)) * 32)
-#endif
     constexpr int NIT = (XROW + 63) / 64;
     constexpr int NSF = K + 3;                     // distinct B fragments per stage (s = tap + t-tile)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_h2[];
@@ -402,11 +340,7 @@ __global__ __launch_bounds__(256, (TM == 1 && ((PRO & 2) == 0 || NEF_H2_UP_OCC3)
             }
         }
     }
-    const float xlim_ = 65000.f / xs_;
-    (void)xlim_;
     float amax_ = 0.f;
-    float over_ret = -1.f;
-    (void)over_ret;
     f32x16 acc[TM][4];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -443,7 +377,7 @@ __global__ __launch_bounds__(256, (TM == 1 && ((PRO & 2) == 0 || NEF_H2_UP_OCC3)
     {                                                                                                               \
         float sa_[4], pa_[4], pb_[4];                                                                               \
         _Pragma("unroll") for (int rr = 0; rr < 4; ++rr) {                                                          \
-            sa_[rr] = (a.in_scale ? a.in_scale[soff + (C0) + 4 * wave + rr] : 1.f) * NEF_H2_STAGE_SCALE;            \
+            sa_[rr] = (a.in_scale ? a.in_scale[soff + (C0) + 4 * wave + rr] : 1.f) * xs_;                           \
             pa_[rr] = 1.f, pb_[rr] = 0.f;                                                                           \
             if constexpr (AFF) {                                                                                    \
                 pa_[rr] = Pl[(C0) + 4 * wave_u + rr];                                                               \
@@ -466,10 +400,10 @@ __global__ __launch_bounds__(256, (TM == 1 && ((PRO & 2) == 0 || NEF_H2_UP_OCC3)
                 }                                                                                                   \
                 const int r = 2 * (lane + 64 * it);                                                                 \
                 unsigned h0_, l0_, h1_, l1_, h2_, l2_, h3_, l3_;                                                    \
-                NEF_H2_SPLIT2(v0_[0], v0_[1], h0_, l0_);                                                      \
-                NEF_H2_SPLIT2(v0_[2], v0_[3], h1_, l1_);                                                      \
-                NEF_H2_SPLIT2(v1_[0], v1_[1], h2_, l2_);                                                      \
-                NEF_H2_SPLIT2(v1_[2], v1_[3], h3_, l3_);                                                      \
+                split2n(v0_[0], v0_[1], h0_, l0_);                                                                  \
+                split2n(v0_[2], v0_[3], h1_, l1_);                                                                  \
+                split2n(v1_[0], v1_[1], h2_, l2_);                                                                  \
+                split2n(v1_[2], v1_[3], h3_, l3_);                                                                  \
                 unsigned char* p0_ = (BUFP) + NEF_H2_WADDR(r, wave);                                                \
                 unsigned char* p1_ = (BUFP) + NEF_H2_WADDR(r + 1, wave);                                            \
                 *reinterpret_cast<u32x2*>(p0_) = u32x2{h0_, h1_};                                                   \
@@ -483,14 +417,14 @@ __global__ __launch_bounds__(256, (TM == 1 && ((PRO & 2) == 0 || NEF_H2_UP_OCC3)
                     const float pa = Pl[(C0) + 4 * wave_u + lane], pb = Pl[Cig + (C0) + 4 * wave_u + lane];         \
                     sa = fmaxf(fmaf(sa, pa, pb), 0.f), sb = fmaxf(fmaf(sb, pa, pb), 0.f);                           \
                 }                                                                                                   \
-                const float sc = (a.in_scale ? a.in_scale[soff + (C0) + 4 * wave + lane] : 1.f) * NEF_H2_STAGE_SCALE; \
+                const float sc = (a.in_scale ? a.in_scale[soff + (C0) + 4 * wave + lane] : 1.f) * xs_;              \
                 float o0 = (1.f - 0.25f) * sa + 0.25f * sb;                                                         \
                 float o1 = (1.f - 0.75f) * sa + 0.75f * sb;                                                         \
                 o0 = mok[0] ? o0 * sc : 0.f;                                                                        \
                 o1 = mok[1] ? o1 * sc : 0.f;                                                                        \
                 NEF_H2_TRACK2(o0, o1)                                                  \
                 unsigned h_, l_;                                                                                    \
-                NEF_H2_SPLIT2(o0, o1, h_, l_);                                                                \
+                split2n(o0, o1, h_, l_);                                                                            \
                 unsigned char* p0_ = (BUFP) + NEF_H2_WADDR(256, wave) + 2 * lane;                                   \
                 unsigned char* p1_ = (BUFP) + NEF_H2_WADDR(257, wave) + 2 * lane;                                   \
                 *reinterpret_cast<unsigned short*>(p0_) = (unsigned short)(h_ & 0xffffu);                           \
@@ -511,8 +445,8 @@ __global__ __launch_bounds__(256, (TM == 1 && ((PRO & 2) == 0 || NEF_H2_UP_OCC3)
             }                                                                                                       \
             const int r = lane + 64 * it;                                                                           \
             unsigned h0_, l0_, h1_, l1_;                                                                            \
-            NEF_H2_SPLIT2(v_[0], v_[1], h0_, l0_);                                                            \
-            NEF_H2_SPLIT2(v_[2], v_[3], h1_, l1_);                                                            \
+            split2n(v_[0], v_[1], h0_, l0_);                                                                        \
+            split2n(v_[2], v_[3], h1_, l1_);                                                                        \
             const u32x2 hv = {h0_, h1_}, lv = {l0_, l1_};                                                           \
             if (r < XROW) {                                                                                         \
                 unsigned char* p_ = (BUFP) + NEF_H2_WADDR(r, wave);                                                 \
@@ -560,19 +494,16 @@ __global__ __launch_bounds__(256, (TM == 1 && ((PRO & 2) == 0 || NEF_H2_UP_OCC3)
 
     const int nst = Cig / KC;
     // this lane's fragment address inside a plane: position wn * 32 + lo (+ the s-dependent constant), channels 8 hi ..
-    const unsigned fb_lane = NEF_H2_LAYOUT ? (unsigned)(hi * HALF + (wn * 32 + lo) * 16) : (unsigned)((wn * 32 + lo) * 32 + hi * 16);
+    const unsigned fb_lane = (unsigned)(hi * HALF + (wn * 32 + lo) * 16);
     for (int st = 0; st < nst; ++st) {
         const unsigned char* const xb = Xl + (st & 1) * (2 * PLANE) + fb_lane;
         const bool more = st + 1 < nst;
         const __amdgpu_buffer_rsrc_t xrs_n = nef_rsrc_n(xbase, more ? 0x7FFFFFFCu : 0u);      // branch-free: see conv_wino4_kernel
-        // Issue order of the stage's vector-memory loads (round 6, NEF_H2_XORDER 1).  Loads return IN ORDER, so the wait for an A
+        // Issue order of the stage's vector-memory loads (round 6).  Loads return IN ORDER, so the wait for an A
         // fragment also waits for every load issued before it.  Rounds 4-5 issued the next stage's activation rows first and tap 1's A
         // fragments behind them: the wait in front of tap 1 then covered the activation rows -- they had ONE tap (768 cycles at K = 3,
         // 128-row tile) to arrive from HBM, whatever the length of the stage.  Now tap 1's A fragments go out first: the first wait that
         // covers the activation rows is the one in front of tap 2, two taps after their issue.
-#if !(NEF_H2_T & 1) && !NEF_H2_XORDER
-        NEF_H2X_ISSUE((st + 1) * KC, xrs_n)
-#endif
         h16x8 fb[5][2];              // ring over s: [slot][plane]
 #define NEF_H2B_LOAD(S)                                                                                              \
     {                                                                                                               \
@@ -589,17 +520,14 @@ __global__ __launch_bounds__(256, (TM == 1 && ((PRO & 2) == 0 || NEF_H2_UP_OCC3)
             // next tap's A fragments (the next stage's first tap behind the last one; past the end: a repeat, harmless)
             if (kk + 1 < K) NEF_H2A_ISSUE(st, kk + 1, (kk + 1) & 1)
             else NEF_H2A_ISSUE(more ? st + 1 : st, 0, (kk + 1) & 1)
-#if !(NEF_H2_T & 1) && NEF_H2_XORDER
             if (kk == 0) {
                 __builtin_amdgcn_sched_barrier(0);      // keep the A issue in front of the activation rows
                 NEF_H2X_ISSUE((st + 1) * KC, xrs_n)
             }
-#endif
             if (kk + 4 < NSF) NEF_H2B_LOAD(kk + 4)
             __builtin_amdgcn_s_setprio(1);      // scheduling fence (see conv_wino_kernel)
             // product-major order: the three MFMAs that accumulate into one tile are 4 TM instructions apart (never back to
             // back on the same accumulator)
-#if !(NEF_H2_T & 2)
             const int s_ = kk & 1;
 #pragma unroll
             for (int j = 0; j < 4; ++j)
@@ -616,7 +544,6 @@ __global__ __launch_bounds__(256, (TM == 1 && ((PRO & 2) == 0 || NEF_H2_UP_OCC3)
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[s_][2 * i + 1], fb[(kk + j) % 5][0], acc[i][j], 0, 0, 0);
-#endif
         }
 #undef NEF_H2B_LOAD
         // K odd: the set toggles K times per stage, so stage st + 1 finds its tap 0 in set (K & 1) ^ ... -- keep it simple:
@@ -631,22 +558,16 @@ __global__ __launch_bounds__(256, (TM == 1 && ((PRO & 2) == 0 || NEF_H2_UP_OCC3)
         else {      // every element of the tile has been staged: publish this wave's magnitude with the loop's last barrier
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) amax_ = fmaxf(amax_, __shfl_xor(amax_, o, 64));
-#if NEF_H2_SPLIT
             amax_ *= 1.f / xs_;      // tracked on the scaled values (exact: a power of two)
-#endif
             if (lane == 0) Al[wave_u] = amax_;
         }
         __syncthreads();
     }
     {
         const float wg_ = fmaxf(fmaxf(Al[0], Al[1]), fmaxf(Al[2], Al[3]));      // workgroup-uniform
-        if (NEF_H2_RESCUE && !last && !(wg_ * xs_ < 65000.f) && wg_ < 3e38f) {
-#if NEF_H2_EPI_ALWAYS
-            over_ret = wg_;
-#else
+        if (!last && !(wg_ * xs_ < 65000.f) && wg_ < 3e38f) {
             __syncthreads();      // (Al is rewritten by the second pass)
             return wg_;
-#endif
         }
     }
 #undef NEF_H2X_ISSUE
@@ -664,14 +585,6 @@ __global__ __launch_bounds__(256, (TM == 1 && ((PRO & 2) == 0 || NEF_H2_UP_OCC3)
             if (b_ > __atomic_load_n(p_, __ATOMIC_RELAXED)) atomicMax(p_, b_);
         }
     }
-#if NEF_H2_T & 4
-    {
-        float z_ = 0.f;
-        for (int i = 0; i < TM; ++i) for (int j = 0; j < 4; ++j) for (int r = 0; r < 16; ++r) z_ += acc[i][j][r];
-        if (z_ == 12345.678f) a.y[0] = z_;
-        return -1.f;
-    }
-#endif
     if constexpr (PF) {
         // ---- polyphase epilogue: the lane's four adjacent half-resolution columns m .. m + 3 of both phases = outputs 2 m .. 2 m + 7
         const int t = t0 + wn * 128 + 4 * lo;
@@ -727,12 +640,7 @@ __global__ __launch_bounds__(256, (TM == 1 && ((PRO & 2) == 0 || NEF_H2_UP_OCC3)
             const int64_t slot = (int64_t)b0 * nslot + (int64_t)(t0 / NTO) * 2 + wn;
             if (inb) slot_out[((int64_t)ch * a.B * nslot + slot) * 2 + (lo & 1)] = sv[0];
         }
-#if NEF_H2_EPI_ALWAYS
-        __syncthreads();
-        return over_ret;
-#else
         return -1.f;
-#endif
     }
     // ---- epilogue: descale, then bias / residual / ReLU / dropout / gate on the four adjacent outputs a lane owns per row
     const int64_t ctot = (int64_t)a.G * Cog;
@@ -763,15 +671,8 @@ __global__ __launch_bounds__(256, (TM == 1 && ((PRO & 2) == 0 || NEF_H2_UP_OCC3)
             float y[8][4];
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
-#if defined(NEF_H2_DBG) && NEF_H2_DBG == 1
-                const float ds = reinterpret_cast<const float*>(wph + (int64_t)a.G * K * Cog * Cig * 2)[g * Cog + cobase + NEF_ROW(q)] / xs_;
-                const float bv = a.bias ? a.bias[g * Cog + cobase + NEF_ROW(q)] : 0.f;
-#elif defined(NEF_H2_DBG) && NEF_H2_DBG == 2
-                const float ds = 1.f, bv = 1000.f;
-#else
                 const float ds = El[5 * MT + erow0 + NEF_ROW(q)];
                 const float bv = El[erow0 + NEF_ROW(q)];
-#endif
 #pragma unroll
                 for (int e = 0; e < 4; ++e) y[q][e] = fmaf(acc[i][e][q + 8 * h], ds, bv);
             }
@@ -963,18 +864,12 @@ __global__ __launch_bounds__(256, (TM == 1 && ((PRO & 2) == 0 || NEF_H2_UP_OCC3)
             if (inb) slot_out[((int64_t)ch * a.B * nslot + slot) * 2 + (lo & 1)] = sv[0];
         }
     }
-#if NEF_H2_EPI_ALWAYS
-    __syncthreads();
-    return over_ret;
-#else
     return -1.f;
-#endif
 #undef a
     };      // tile_pass
     kargs_t* ap_ = (kargs_t*)__builtin_amdgcn_kernarg_segment_ptr();      // (a_ is the segment's first member)
     (void)a_;
     const float over_ = tile_pass(ap_, (int)blockIdx.x, (int)threadIdx.x, tps_, n_tiles_, m_tiles_, 0.f, false);
-#if NEF_H2_RESCUE
     if (over_ > 0.f) {
         int e_;
         (void)frexpf(over_, &e_);
@@ -983,7 +878,6 @@ __global__ __launch_bounds__(256, (TM == 1 && ((PRO & 2) == 0 || NEF_H2_UP_OCC3)
         asm volatile("" : "+v"(tid_));
         (void)tile_pass(ap_, bid_, tid_, tps2_, nt2_, mt2_, ldexpf(1.f, 9 - e_ < 100 ? 9 - e_ : 100), true);
     }
-#endif
 }
 
 template <int K, int PRO, int TM, bool PACK = false>
@@ -1030,47 +924,10 @@ __attribute__((visibility("hidden"))) bool nef_h2_ok(const nef_conv_args* a) {
            (!(a->pro_mode & 1) || a->Cin_g <= PRO_MAX_CIN);
 }
 
-// Kernel-form options of the process (nef_set_option / nef_get_option; under NEF_DIAG=1 the environment gives the initial values:
-// NEF_H2P, NEF_H2P_WGS).  The producer / consumer form they select (tools/experiments/conv_h2p.hip: bit-identical, measured slower,
-// DESIGN.md 3.0a) is only linked into builds made with `csrc/build.py --with-experiments`: the two hooks below are weak, and a
-// library without them keeps every launch on conv_h2_kernel whatever the option says.
-static int g_opt[4] = {0, -1, -1, 0};
-static void opt_init() {
-    if (__atomic_load_n(&g_opt[0], __ATOMIC_ACQUIRE)) return;
-    const char* e1 = nef_diag_env("NEF_H2P");
-    const char* e2 = nef_diag_env("NEF_H2P_WGS");
-    int v1 = e1 ? atoi(e1) : 0, v2 = e2 ? atoi(e2) : 1;
-    int neg = -1;
-    __atomic_compare_exchange_n(&g_opt[NEF_OPT_H2_FORM], &neg, v1, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED);
-    neg = -1;
-    __atomic_compare_exchange_n(&g_opt[NEF_OPT_H2P_WGS], &neg, v2, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED);
-    __atomic_store_n(&g_opt[0], 1, __ATOMIC_RELEASE);
-}
-__attribute__((visibility("hidden"))) int nef_opt_get(int key) {
-    opt_init();
-    return __atomic_load_n(&g_opt[key], __ATOMIC_RELAXED);
-}
-extern "C" {
-int nef_set_option(int key, int value) {
-    if (key != NEF_OPT_H2_FORM && key != NEF_OPT_H2P_WGS) return NEF_E_SHAPE;
-    opt_init();
-    return __atomic_exchange_n(&g_opt[key], value, __ATOMIC_RELAXED);
-}
-int nef_get_option(int key) {
-    if (key != NEF_OPT_H2_FORM && key != NEF_OPT_H2P_WGS) return NEF_E_SHAPE;
-    return nef_opt_get(key);
-}
-}
-__attribute__((weak, visibility("hidden"))) bool nef_h2p_ok(const nef_conv_args* a);
-__attribute__((weak, visibility("hidden"))) int nef_h2p_launch(const nef_conv_args* a, hipStream_t st);
-
 __attribute__((visibility("hidden"))) int nef_h2_launch(const nef_conv_args* a, hipStream_t st) {
     if (!nef_h2_ok(a)) return NEF_E_SHAPE;
     if ((a->pro_mode & 1) && !(a->pro_a && a->pro_b && a->pro_Bp > 0)) return NEF_E_NULL;
-    if (&nef_h2p_launch && &nef_h2p_ok && nef_opt_get(NEF_OPT_H2_FORM) && a->pro_mode <= 3 && !a->res_scale && !a->gate_rowscale && a->stats_mode == 0 && nef_h2p_ok(a))
-        return nef_h2p_launch(a, st);
-    static const bool force_tm1 = nef_diag_env("NEF_H2_TM1") && atoi(nef_diag_env("NEF_H2_TM1")) == 1;      // A/B: 64-channel tile everywhere
-    const bool wide = a->Cout_g % 128 == 0 && !force_tm1;
+    const bool wide = a->Cout_g % 128 == 0;
     // the x2-upsampling prologue keeps two source samples per staged position in registers: next to the 128 accumulator
     // registers of the 128-channel tile that spills (250..330 bytes per lane; 34.1 vs 31.1 ms/step in round 4), so those launches
     // always take the 64-channel tile (the 128-channel instantiations <3, 2, 2> / <3, 3, 2> are no longer built)

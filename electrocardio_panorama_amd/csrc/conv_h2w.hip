@@ -18,8 +18,7 @@
 //   conv_h2w_kernel ("first form"; the 64-output-channel layers): 64 x 64 channels, 256 threads, every wave stages, splits and
 //           multiplies in turn, two workgroups per CU.  A lane reads the 16-column window X[ci][t0 + 8 hi - 4 .. + 11] once per 16
 //           columns and cuts each tap's fragment out of it in registers (even shifts: register renames, odd shifts: four
-//           v_alignbit_b32).  (NEF_H2W_MCO=2 builds its 128 x 64 variant with the taps / chunks divided between two wave groups:
-//           measured a wash, kept for A/B.)
+//           v_alignbit_b32).
 //
 // Both operands are scaled by exact powers of two derived from the magnitudes their call site measured before (x_amax,
 // gy_amax; ops.py keeps them per site as for the forward launches); the product of the two scales is divided out of the
@@ -33,9 +32,6 @@
 #include "nefnet_hip.h"
 #include "nef_common.h"
 
-#ifndef NEF_H2_CLAMP
-#define NEF_H2_CLAMP 0      // 1: clamp operands at fp16's range before the split (round 4; the range rescue makes it unnecessary)
-#endif
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -74,26 +70,16 @@ struct H2WArgs {
 };
 
 
-// (x0, x1) * s -> fp16 pair h, residual pair l; |x| is clamped at lim = 65000 / s first
-__device__ __forceinline__ void split_pair_s(float x0, float x1, float s, float lim, unsigned& h, unsigned& l) {
-#if NEF_H2_CLAMP
-    x0 = __builtin_amdgcn_fmed3f(x0, -lim, lim);
-    x1 = __builtin_amdgcn_fmed3f(x1, -lim, lim);
-#else
-    (void)lim;      // no clamp: a tile whose data does not fit is redone with its own scale (range rescue), its first pass is discarded
-#endif
+// (x0, x1) * s -> fp16 pair h, residual pair l.  No clamp: a tile whose data does not fit is redone with its own scale (range
+// rescue), its first pass is discarded
+__device__ __forceinline__ void split_pair_s(float x0, float x1, float s, unsigned& h, unsigned& l) {
     asm("v_fma_mixlo_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "=v"(h) : "v"(x0), "v"(s));
     asm("v_fma_mixhi_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "+v"(h) : "v"(x1), "v"(s));
     asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(l) : "v"(x0), "v"(s), "v"(h));
     asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(l) : "v"(x1), "v"(s), "v"(h));
 }
 // one value: the low halves of h and l (the high halves are not defined)
-__device__ __forceinline__ void split_one_s(float x0, float s, float lim, unsigned& h, unsigned& l) {
-#if NEF_H2_CLAMP
-    x0 = __builtin_amdgcn_fmed3f(x0, -lim, lim);
-#else
-    (void)lim;
-#endif
+__device__ __forceinline__ void split_one_s(float x0, float s, unsigned& h, unsigned& l) {
     asm("v_fma_mixlo_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "=v"(h) : "v"(x0), "v"(s));
     asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(l) : "v"(x0), "v"(s), "v"(h));
 }
@@ -214,7 +200,6 @@ __global__ __launch_bounds__(SPLIT ? 512 : 256, SPLIT ? 1 : 2) void conv_h2w_ker
     float* const Wl = reinterpret_cast<float*>(smem_w);      // [2][8] wave magnitudes, written behind the last tile (the stages are free then)
     float rx_ = 0.f, rg_ = 0.f;                              // the share's magnitudes, left by a pass that did not fit
     auto share_pass = [&](const float sx, const float sg, const bool last) __attribute__((always_inline)) -> bool {
-    const float limx = 65000.f / sx, limg = 65000.f / sg;
     float amax_x = 0.f, amax_g = 0.f;
 
     f32x16 acc[MCO][KA];
@@ -268,7 +253,7 @@ __global__ __launch_bounds__(SPLIT ? 512 : 256, SPLIT ? 1 : 2) void conv_h2w_ker
             const int row = p >> 5, c2 = p & 31;                                                                    \
             amax_g = fmaxf(amax_g, fmaxf(fabsf(gq[q][0]), fabsf(gq[q][1])));                                        \
             unsigned h_, l_;                                                                                        \
-            split_pair_s(gq[q][0], gq[q][1], sg, limg, h_, l_);                                                           \
+            split_pair_s(gq[q][0], gq[q][1], sg, h_, l_);                                                           \
             unsigned char* p_ = (BUFP) + row * GP + c2 * 4;                                                         \
             *reinterpret_cast<unsigned*>(p_) = h_;                                                                  \
             *reinterpret_cast<unsigned*>(p_ + GY_PLANE) = l_;                                                       \
@@ -304,7 +289,7 @@ __global__ __launch_bounds__(SPLIT ? 512 : 256, SPLIT ? 1 : 2) void conv_h2w_ker
                 if (t < 0 || t >= T) v0 = v1 = 0.f;      /* zero padding comes after the prologue */                \
                 amax_x = fmaxf(amax_x, fmaxf(fabsf(v0), fabsf(v1)));                                                \
                 unsigned h_, l_;                                                                                    \
-                split_pair_s(v0, v1, sx, limx, h_, l_);                                                                   \
+                split_pair_s(v0, v1, sx, h_, l_);                                                                   \
                 unsigned char* p_ = (BUFP) + 2 * GY_PLANE + row * XP + c2 * 4;                                      \
                 *reinterpret_cast<unsigned*>(p_) = h_;                                                              \
                 *reinterpret_cast<unsigned*>(p_ + X_PLANE) = l_;                                                    \
@@ -423,7 +408,7 @@ H2WForm h2w_form(int Cog, int K) {
 // =====================================================================================================================
 // Second form (Cout_g % 128 == 0): producer and consumer waves.
 //
-// Timing-only builds of the first form (NEF_W2_DBG, K = 7 encoder shape, random data) showed three costs that ADD: the matrix
+// Timing-only builds of the first form (round 5, K = 7 encoder shape, random data) showed three costs that ADD: the matrix
 // stream alone 0.50 ms (= the rate this chip sustains for dense fp16 MFMA on random data, 1.3 PFLOP/s), staging (split + LDS
 // stores) 0.13 ms, exposed global-load time 0.17 ms -- whatever the tile form, as long as every wave does all three in turn.
 // Here the roles are separate waves of one workgroup (128 output x 64 input channels, 64-column tiles, two LDS stages, ONE
@@ -443,12 +428,9 @@ H2WForm h2w_form(int Cog, int K) {
 // stream 3.0 - 3.6 TB/s (7 - 8 B/clk/CU of 256-byte row pieces that straddle cache lines); the 64-channel layers are at that
 // rate with the first form already (64 -> 64, T = 5000: 1.97 GB in 0.50 ms) and stay on it.
 // =====================================================================================================================
-#ifndef NEF_W2_DBG
-#define NEF_W2_DBG 0      // timing-only builds: 1 = no split / LDS stores, 2 = no global loads, 4 = no matrix work
-#endif
-#ifndef NEF_H2W_64_DEFAULT
-#define NEF_H2W_64_DEFAULT 12     // the x2-upsampling prologues (modes 2, 3): 1.12 -> 0.92 ms for the 128 -> 64 decoder layer; plain and affine-only 64-channel layers are at the load rate with either form
-#endif
+// the x2-upsampling prologues (modes 2, 3): 1.12 -> 0.92 ms for the 128 -> 64 decoder layer; plain and affine-only 64-channel
+// layers are at the load rate with either form
+constexpr int H2W2_64_MODES = 12;
 typedef u32x4 u32x4_a4 __attribute__((aligned(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -555,7 +537,6 @@ __global__ __launch_bounds__(64 * (WM / WR * WN + NP), 1) void conv_h2w2_kernel(
     float* const Wl = reinterpret_cast<float*>(smem_w);      // [2][16] wave magnitudes
     float rx_ = 0.f, rg_ = 0.f;
     auto share_pass = [&](const float sx, const float sg, const bool last) __attribute__((always_inline)) -> bool {
-    const float limx = 65000.f / sx, limg = 65000.f / sg;
     float amax_x = 0.f, amax_g = 0.f;
 
     f32x16 acc[WR][K];
@@ -663,8 +644,8 @@ __global__ __launch_bounds__(64 * (WM / WR * WN + NP), 1) void conv_h2w2_kernel(
             amax_g = fmaxf(amax_g, fmaxf(fabsf(v[0]), fabsf(v[1])));
             amax_g = fmaxf(amax_g, fmaxf(fabsf(v[2]), fabsf(v[3])));
             unsigned h0, l0, h1, l1;
-            split_pair_s(v[0], v[1], sg, limg, h0, l0);
-            split_pair_s(v[2], v[3], sg, limg, h1, l1);
+            split_pair_s(v[0], v[1], sg, h0, l0);
+            split_pair_s(v[2], v[3], sg, h1, l1);
             unsigned char* p_ = bufp + g_lds + q * GROWS * GP;
             *reinterpret_cast<u32x2*>(p_) = u32x2{h0, h1};
             *reinterpret_cast<u32x2*>(p_ + G_PLANE) = u32x2{l0, l1};
@@ -710,9 +691,9 @@ __global__ __launch_bounds__(64 * (WM / WR * WN + NP), 1) void conv_h2w2_kernel(
                 amax_x = fmaxf(amax_x, fmaxf(fabsf(v[0]), fabsf(v[1])));
                 amax_x = fmaxf(amax_x, fmaxf(fabsf(v[2]), fabsf(v[3])));
                 unsigned h0, l0, h1, l1, h2, l2;
-                split_pair_s(v[0], v[1], sx, limx, h0, l0);
-                split_pair_s(v[2], v[3], sx, limx, h1, l1);
-                split_one_s(v[4], sx, limx, h2, l2);
+                split_pair_s(v[0], v[1], sx, h0, l0);
+                split_pair_s(v[2], v[3], sx, h1, l1);
+                split_one_s(v[4], sx, h2, l2);
                 unsigned char* p_ = bufp + 2 * G_PLANE + x_lds[q];
                 *reinterpret_cast<u32x2*>(p_) = u32x2{h0, h1};
                 *reinterpret_cast<u32x2*>(p_ + X_PLANE) = u32x2{l0, l1};
@@ -744,18 +725,10 @@ __global__ __launch_bounds__(64 * (WM / WR * WN + NP), 1) void conv_h2w2_kernel(
             // while tile n is multiplied: X of tile n + 1 goes into the other stage and the X loads of tile n + 2 go out, then the
             // same for gy -- every load is in flight over the other half's stores and the wait for the consumers
             for (int n = n_lo; n < n_hi; ++n) {
-#if !(NEF_W2_DBG & 1)
                 store_t(st0, n + 1, 2);
-#endif
-#if !(NEF_W2_DBG & 2)
                 issue_t(st0, n + 2, 2);
-#endif
-#if !(NEF_W2_DBG & 1)
                 store_t(st0, n + 1, 1);
-#endif
-#if !(NEF_W2_DBG & 2)
                 issue_t(st0, n + 2, 1);
-#endif
                 __syncthreads();
             }
         } else {
@@ -766,20 +739,12 @@ __global__ __launch_bounds__(64 * (WM / WR * WN + NP), 1) void conv_h2w2_kernel(
             issue_t(st0, n_lo + 2, 3);
             __syncthreads();
             for (int n = n_lo; n < n_hi; n += 2) {
-#if !(NEF_W2_DBG & 1)
                 store_t(st1, n + 1, 3);
-#endif
-#if !(NEF_W2_DBG & 2)
                 issue_t(st1, n + 3, 3);
-#endif
                 __syncthreads();
                 if (n + 1 < n_hi) {
-#if !(NEF_W2_DBG & 1)
                     store_t(st0, n + 2, 3);
-#endif
-#if !(NEF_W2_DBG & 2)
                     issue_t(st0, n + 4, 3);
-#endif
                     __syncthreads();
                 }
             }
@@ -790,10 +755,8 @@ __global__ __launch_bounds__(64 * (WM / WR * WN + NP), 1) void conv_h2w2_kernel(
             const unsigned char* const bufp = smem_w + ((n - n_lo) & 1) * BUF;
             const unsigned char* const ga = bufp + (wm * 32 + lo) * GP + hi * 16;
             const unsigned char* const xa = bufp + 2 * G_PLANE + (wn * 32 + lo) * XP + hi * 16;
-#if !(NEF_W2_DBG & 4)
 #pragma unroll
             for (int c = 0; c < NCH; ++c) h2w2_chunk<K, WR, GP, XP, G_PLANE, X_PLANE>(ga, xa, c, acc);
-#endif
             __syncthreads();
         }
     }
@@ -860,15 +823,11 @@ int launch_h2w2(const H2WArgs& a, hipStream_t st) {
     return nef_launch_status();
 }
 
-// the second kernel takes the shapes with Cout_g % 128 == 0 (form 1: 128 x 64 channels per workgroup); NEF_H2W_V=1: the first kernel
-// everywhere; NEF_H2W_64=<mask of prologue modes + 1>: form 2 (64 x 64 channels, 4 consumer + 8 producer waves) for the 64-channel
-// layers with those prologues (bit p + 1 set: pro_mode p)
+// the second kernel takes the shapes with Cout_g % 128 == 0 (form 1: 128 x 64 channels per workgroup) and the 64-channel layers
+// whose prologue mode p has bit p set in H2W2_64_MODES (form 2: 64 x 64 channels, 4 consumer + 8 producer waves)
 int h2w2_form(int Cog, int pro_mode) {
-    static const bool v1 = nef_diag_env("NEF_H2W_V") && atoi(nef_diag_env("NEF_H2W_V")) == 1;
-    static const int m64 = nef_diag_env("NEF_H2W_64") ? atoi(nef_diag_env("NEF_H2W_64")) : NEF_H2W_64_DEFAULT;
-    if (v1) return 0;
     if (Cog % 128 == 0) return 1;
-    return ((m64 >> pro_mode) & 1) ? 2 : 0;
+    return ((H2W2_64_MODES >> pro_mode) & 1) ? 2 : 0;
 }
 
 }  // namespace
@@ -890,9 +849,8 @@ __attribute__((visibility("hidden"))) int nef_h2w_splits(int B, int T, int G, in
     const int64_t n_tiles = (int64_t)B * tps;
     const int units = v2 ? G * (Cog / (v2 == 1 ? 128 : 64)) * (Cig / 64) : G * (Cog / (64 * f.mco)) * (Cig / 64);
     const int resident = v2 ? 1 : (f.split ? 1 : 2);      // workgroups per CU
-    static const int rounds = nef_diag_env("NEF_H2W_ROUNDS") ? atoi(nef_diag_env("NEF_H2W_ROUNDS")) : 1;
-    const int slots = rounds * resident * nef_cu_count();
-    int S = slots / units;                 // `rounds` rounds of resident workgroups and never a workgroup more: one extra costs a whole round
+    const int slots = resident * nef_cu_count();
+    int S = slots / units;                 // one round of resident workgroups and never a workgroup more: one extra costs a whole round
     if (S > n_tiles) S = (int)n_tiles;
     if (S < 1) S = 1;
     if (partials) *partials = S * (!v2 && f.split == 2 ? 2 : 1);
@@ -944,12 +902,8 @@ __attribute__((visibility("hidden"))) int nef_h2w_launch(const float* x, int64_t
     }
     if (K == 7) return launch_h2w<7, 0, 1, 0>(a, st);
     if (K == 1) return launch_h2w<1, 0, 1, 0>(a, st);
-    switch (pro_mode) {
-        case 0: return launch_h2w<3, 0, 1, 0>(a, st);
-        case 1: return launch_h2w<3, 1, 1, 0>(a, st);
-        case 2: return launch_h2w<3, 2, 1, 0>(a, st);
-        default: return launch_h2w<3, 3, 1, 0>(a, st);
-    }
+    // (the upsampling prologues of the 64-channel layers took form 2 above)
+    return pro_mode == 0 ? launch_h2w<3, 0, 1, 0>(a, st) : launch_h2w<3, 1, 1, 0>(a, st);
 }
 
 }  // extern "C"

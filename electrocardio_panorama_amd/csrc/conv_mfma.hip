@@ -28,21 +28,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
-// NEF_ABL: timing-only ablation builds (tools/ablate_k7.py; results are WRONG by construction, never shipped): bit0 = no
-// weight (A) fetches inside the main loop, bit1 = no activation fetches / LDS staging stores inside the loop, bit2 = no LDS
-// fragment reads and no transform arithmetic inside the loop (operands are loop-invariant registers of random data),
-// bit3 = no epilogue (the accumulators stay live behind a run-time-false branch).  15 = the MFMA stream and its barriers.
-#ifndef NEF_ABL
-#define NEF_ABL 0
-#endif
-// NEF_TRACE: measurement builds only (tools/trace_conv.py).  Wave 0 of every 16th workgroup of conv_wino4_kernel keeps
-// s_memtime stamps of its phases (entry, first tile staged, every stage's barrier, epilogue done) and writes them out at exit.
-#ifdef NEF_TRACE
-__device__ unsigned long long* nef_trace_ptr = nullptr;
-#define NEF_TR(I) if (tr_on) tr_t[(I)] = __builtin_readcyclecounter();
-#else
-#define NEF_TR(I)
-#endif
 constexpr int NT = 128;   // forward: columns per workgroup
 constexpr int WT = 64;    // bwd-weight: reduction columns per staged tile
 
@@ -52,14 +37,8 @@ template <> struct StageK<7> { static constexpr int KC = 16; };
 // workgroups on a CU instead of 2, so one more workgroup's MFMA stream covers the others' barriers and epilogues:
 // 126.7 -> 133.1 TFLOP/s on the encoder convs (80.5 -> 84.6 % of the fp32 matrix peak).  The 64-row variants cannot
 // split an 8-channel weight tile evenly over 256 threads and keep 16.  The 128-row K=3 kernels take 8 as well (-0.4 ms).
-#ifndef NEF_K7_KC
-#define NEF_K7_KC 8
-#endif
-#ifndef NEF_K3_KC2
-#define NEF_K3_KC2 8
-#endif
 template <int K, int TM> struct FwdStage {
-    static constexpr int KC = (K == 7 && TM == 2) ? NEF_K7_KC : (K == 3 && TM == 2) ? NEF_K3_KC2 : StageK<K>::KC;
+    static constexpr int KC = ((K == 7 || K == 3) && TM == 2) ? 8 : StageK<K>::KC;
 };
 // K=3: 16-channel stages keep the kernel at <= 168 VGPRs and 34 KB of LDS -> 3 workgroups per CU (the per-tile fixed
 // costs of these short-K convs then overlap across workgroups): -2.3 % step time against 32-channel stages.
@@ -258,10 +237,7 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_kernel(nef_conv_args a, int s
         // MFMA loop, software-pipelined in registers: the LDS fragments of k-step group gi+1 are read while the
         // MFMAs of group gi issue (fully unrolled, so every register index is static), one ds_read per MFMA slot.
         {
-#ifndef NEF_GS
-#define NEF_GS 2
-#endif
-            constexpr int GS = NEF_GS;                  // k-steps (of 2 channels) per group
+            constexpr int GS = 2;                       // k-steps (of 2 channels) per group
             constexpr int SPK = KC / 2;                 // k-steps per tap
             constexpr int NG = K * SPK / GS;
             static_assert((K * SPK) % GS == 0, "k-steps must split into whole groups");
@@ -401,10 +377,7 @@ static int launch_conv_fwd(const nef_conv_args& a, hipStream_t st) {
 // the result differs from the direct form by the rounding of the three transforms (transform entries are 0, +-1,
 // 1/2: a few ulp, measured in tests/test_ops_gpu.py::test_conv_winograd).  Sequences shorter than a tile keep the
 // direct kernel.  NEF_WINOGRAD=0 in the environment disables this path (ops.py).
-#ifndef NEF_WKC
-#define NEF_WKC 16
-#endif
-constexpr int WKC = NEF_WKC;   // channels per activation stage: 64 MFMAs per wave between barriers
+constexpr int WKC = 16;        // channels per activation stage: 64 MFMAs per wave between barriers
 constexpr int PRO_MAX_CIN = 512; // input channels per group the LDS table of the affine prologue holds
 
 // Operand paths.  B (activations): raw tile through LDS, DOUBLE-buffered -- the registers holding stage s+1 (fetched
@@ -585,7 +558,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(nef_conv_args a, int 
     }
     NEF_WX_ISSUE(0, xrs)
 #pragma unroll
-    for (int s_ = 0; s_ < ((NEF_ABL & 1) ? NSET : AHEAD); ++s_) NEF_WA_ISSUE(s_, s_)
+    for (int s_ = 0; s_ < AHEAD; ++s_) NEF_WA_ISSUE(s_, s_)
     if constexpr (AFF) {     // the producing BatchNorm's (a, b) of this tile's pass: one table in LDS instead of a global load per
                              // staged row (each of those was waited for with the queue drained)
         for (int i = threadIdx.x; i < Cig; i += 256) {
@@ -604,27 +577,22 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(nef_conv_args a, int 
         const f32x2* xp_ = reinterpret_cast<const f32x2*>(xb + 2 * (S) * XRS);                                      \
         _Pragma("unroll") for (int q_ = 0; q_ < NXV; ++q_) fx[BUF][q_] = xp_[q_];                                   \
     }
-    if constexpr ((NEF_ABL & 4) != 0) {
-        const float* xb = Xl + hi * XRS + 2 * (wn * 32 + lo);
-        NEF_WX_LOAD(0, 0)
-        NEF_WX_LOAD(1, 1)
-    }
     for (int c0 = 0; c0 < Cig; c0 += KC, ++st) {
-        const float* xb = Xl + ((NEF_ABL & 2) ? 0 : (st & 1)) * (KC * XRS) + hi * XRS + 2 * (wn * 32 + lo);
+        const float* xb = Xl + (st & 1) * (KC * XRS) + hi * XRS + 2 * (wn * 32 + lo);
         const bool more = c0 + KC < Cig;
         const __amdgpu_buffer_rsrc_t xrs_n = nef_rsrc_n(xbase, more ? 0x7FFFFFFCu : 0u);
-        if constexpr (!(NEF_ABL & 4)) NEF_WX_LOAD(0, 0)
+        NEF_WX_LOAD(0, 0)
 #pragma unroll
         for (int s_ = 0; s_ < SPK; ++s_) {
-            if constexpr (!(NEF_ABL & 1)) NEF_WA_ISSUE(st * SPK + s_ + AHEAD, (s_ + AHEAD) % NSET)
+            NEF_WA_ISSUE(st * SPK + s_ + AHEAD, (s_ + AHEAD) % NSET)
             // the activation rows of the next stage are requested once per stage, right behind an A request: the first
             // A fragment that is YOUNGER than them is consumed later in the stage, by when they have long arrived
             // (vector-memory results return in order)
             // (branch-free on purpose: past the last stage the burst goes through an empty descriptor.  With `if (more)`
             // around it the compiler's s_waitcnt bookkeeping took the smaller count of the two paths and made every wave sit
             // on the burst within the first k-step of the stage)
-            if constexpr (!(NEF_ABL & 2)) if (s_ == 0) NEF_WX_ISSUE(c0 + KC, xrs_n)
-            if constexpr (!(NEF_ABL & 4)) if (s_ + 1 < SPK) NEF_WX_LOAD(s_ + 1, (s_ + 1) & 1)
+            if (s_ == 0) NEF_WX_ISSUE(c0 + KC, xrs_n)
+            if (s_ + 1 < SPK) NEF_WX_LOAD(s_ + 1, (s_ + 1) & 1)
             const f32x2* d = fx[s_ & 1];
 #define w_(I, TM) NEF_FA(s_ % NSET, I, TM)
             // One s_setprio per k-step.  Measured -3..5 % on the K = 3 shapes and -1 % on K = 7 (tools/bench_conv.py); a
@@ -676,7 +644,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(nef_conv_args a, int 
             }
         }
 #undef w_
-        if constexpr (!(NEF_ABL & 2)) if (more) NEF_WX_STORE(c0 + KC, Xl + ((st + 1) & 1) * (KC * XRS))
+        if (more) NEF_WX_STORE(c0 + KC, Xl + ((st + 1) & 1) * (KC * XRS))
         __syncthreads();
     }
 #undef NEF_WX_LOAD
@@ -684,7 +652,6 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(nef_conv_args a, int 
 #undef NEF_FA
 #undef NEF_WX_ISSUE
 #undef NEF_WX_STORE
-    if constexpr ((NEF_ABL & 8) != 0) if (a.T >= 0) return;      // run-time true: the epilogue below is dead at run time only
 
     // epilogue: output transform, then bias / residual / ReLU / dropout / gate exactly as conv_fwd_kernel, on the two
     // adjacent outputs (2j, 2j+1) a lane owns per channel row: 8-byte loads and stores, 256 contiguous bytes per row.
@@ -822,23 +789,8 @@ static int launch_conv_wino(const nef_conv_args& a, hipStream_t st) {
 // A fragments straight from L2 ahead of use, one barrier per 16-channel stage); a wave owns 32 output channels x 32 quads
 // (128 outputs) = 6 accumulator tiles; a workgroup is 4 x 1 waves (128 channels x 128 outputs) or 2 x 2 (64 x 256).
 // K = 3, 128 channels, no upsampling prologue: 168 VGPRs -> three workgroups per CU (-3..5 % against two)
-#ifndef NEF_W4_MINB3
-#define NEF_W4_MINB3 1
-#endif
-#ifndef NEF_W4_AHEAD3_W2
-#define NEF_W4_AHEAD3_W2 3
-#endif
-#ifndef NEF_W4_AHEAD3_W4
-#define NEF_W4_AHEAD3_W4 3
-#endif
-#ifndef NEF_W4_AHEAD7
-#define NEF_W4_AHEAD7 1
-#endif
-#ifndef NEF_W4_MINB3_W2
-#define NEF_W4_MINB3_W2 0
-#endif
 constexpr int w4_wgs_per_cu(int K, int WMC, int PRO) {
-    return (K == 3 && (PRO & 2) == 0 && ((WMC == 4 && NEF_W4_MINB3) || (WMC == 2 && NEF_W4_MINB3_W2))) ? 3 : 2;
+    return (K == 3 && (PRO & 2) == 0 && WMC == 4) ? 3 : 2;
 }
 template <int K, int WMC, int PRO>
 __global__ __launch_bounds__(256, w4_wgs_per_cu(K, WMC, PRO)) void conv_wino4_kernel(nef_conv_args a, int tps, int n_tiles, int m_tiles) {
@@ -861,16 +813,6 @@ __global__ __launch_bounds__(256, w4_wgs_per_cu(K, WMC, PRO)) void conv_wino4_ke
     // fetched while the first tile is in flight -- in the epilogue each of these was a dependent global load with the
     // memory latency of a loaded chip in front of the output stores
     float* El = Pl + (AFF ? 2 * PRO_MAX_CIN : 0);
-#ifdef NEF_TRACE
-    const bool tr_on = nef_trace_ptr != nullptr && (blockIdx.x & 15) == 0;
-    unsigned long long tr_t[24];
-#pragma unroll
-    for (int i = 0; i < 24; ++i) tr_t[i] = 0;
-#endif
-    NEF_TR(0)
-#ifdef NEF_TRACE
-    if (tr_on) tr_t[22] = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11));
-#endif
 
     const int tile = blockIdx.x % n_tiles;
     const int gm = blockIdx.x / n_tiles;
@@ -946,7 +888,7 @@ __global__ __launch_bounds__(256, w4_wgs_per_cu(K, WMC, PRO)) void conv_wino4_ke
     // activation rows of the next stage also waits for those rows: the ring depth is the cover (in k-steps) the activation
     // fetch gets before the wave is made to sit on it -- and with it the share of a stage during which a workgroup has
     // bytes in flight at all (the 64-channel layers are bound by exactly that: ~17 KB per workgroup, 40 % of the time).
-    constexpr int AHEAD = K == 3 ? (WMC == 2 ? NEF_W4_AHEAD3_W2 : NEF_W4_AHEAD3_W4) : NEF_W4_AHEAD7;
+    constexpr int AHEAD = K == 3 ? 3 : 1;
     constexpr int NSET = AHEAD + 1;
     static_assert(SPK % NSET == 0, "the A sets must line up across stages");
     const int nsteps = Cig / 2;
@@ -1009,7 +951,7 @@ __global__ __launch_bounds__(256, w4_wgs_per_cu(K, WMC, PRO)) void conv_wino4_ke
     }
     NEF_W4X_ISSUE(0, xrs)
 #pragma unroll
-    for (int s_ = 0; s_ < ((NEF_ABL & 1) ? NSET : AHEAD); ++s_) NEF_W4A_ISSUE(s_, s_)
+    for (int s_ = 0; s_ < AHEAD; ++s_) NEF_W4A_ISSUE(s_, s_)
     if (threadIdx.x < MT) {     // published by the barrier behind the first tile's LDS stores
         const int ch_ = g * Cog + m0 + (int)threadIdx.x;
         El[threadIdx.x] = a.bias ? a.bias[ch_] : 0.f;
@@ -1028,10 +970,8 @@ __global__ __launch_bounds__(256, w4_wgs_per_cu(K, WMC, PRO)) void conv_wino4_ke
         }
         __syncthreads();
     }
-    NEF_TR(1)
     NEF_W4X_STORE(0, Xl)
     __syncthreads();
-    NEF_TR(2)
     int st = 0;
     f32x2 fx[2][NXV];
 #define NEF_W4X_LOAD(S, BUF)                                                                                         \
@@ -1039,21 +979,16 @@ __global__ __launch_bounds__(256, w4_wgs_per_cu(K, WMC, PRO)) void conv_wino4_ke
         const f32x2* xp_ = reinterpret_cast<const f32x2*>(xb + 2 * (S) * XRS);                                      \
         _Pragma("unroll") for (int q_ = 0; q_ < NXV; ++q_) fx[BUF][q_] = xp_[q_];                                   \
     }
-    if constexpr ((NEF_ABL & 4) != 0) {
-        const float* xb = Xl + hi * XRS + 4 * (wn * 32 + lo);
-        NEF_W4X_LOAD(0, 0)
-        NEF_W4X_LOAD(1, 1)
-    }
     for (int c0 = 0; c0 < Cig; c0 += KC, ++st) {
-        const float* xb = Xl + ((NEF_ABL & 2) ? 0 : (st & 1)) * (KC * XRS) + hi * XRS + 4 * (wn * 32 + lo);
+        const float* xb = Xl + (st & 1) * (KC * XRS) + hi * XRS + 4 * (wn * 32 + lo);
         const bool more = c0 + KC < Cig;
         const __amdgpu_buffer_rsrc_t xrs_n = nef_rsrc_n(xbase, more ? 0x7FFFFFFCu : 0u);     // see conv_wino_kernel
-        if constexpr (!(NEF_ABL & 4)) NEF_W4X_LOAD(0, 0)
+        NEF_W4X_LOAD(0, 0)
 #pragma unroll
         for (int s_ = 0; s_ < SPK; ++s_) {
-            if constexpr (!(NEF_ABL & 1)) NEF_W4A_ISSUE(st * SPK + s_ + AHEAD, (s_ + AHEAD) % NSET)
-            if constexpr (!(NEF_ABL & 2)) if (s_ == 0) NEF_W4X_ISSUE(c0 + KC, xrs_n)
-            if constexpr (!(NEF_ABL & 4)) if (s_ + 1 < SPK) NEF_W4X_LOAD(s_ + 1, (s_ + 1) & 1)
+            NEF_W4A_ISSUE(st * SPK + s_ + AHEAD, (s_ + AHEAD) % NSET)
+            if (s_ == 0) NEF_W4X_ISSUE(c0 + KC, xrs_n)
+            if (s_ + 1 < SPK) NEF_W4X_LOAD(s_ + 1, (s_ + 1) & 1)
             __builtin_amdgcn_s_setprio(1);      // scheduling fence, see conv_wino_kernel
             float x_[2 * NXV];
 #pragma unroll
@@ -1096,37 +1031,14 @@ __global__ __launch_bounds__(256, w4_wgs_per_cu(K, WMC, PRO)) void conv_wino4_ke
                     acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(NEF_FA4(s_ % NSET, P0 + i), v[i], acc[i], 0, 0, 0);
             }
         }
-#ifdef NEF_TRACE
-        if (tr_on) {      // stage st: [3 + 2*st] = MFMA loop done, [4 + 2*st] = next tile stored + barrier passed
-#pragma unroll
-            for (int q_ = 0; q_ < 8; ++q_) if (q_ == st) tr_t[3 + 2 * q_] = __builtin_readcyclecounter();
-        }
-#endif
-        if constexpr (!(NEF_ABL & 2)) if (more) NEF_W4X_STORE(c0 + KC, Xl + ((st + 1) & 1) * (KC * XRS))
+        if (more) NEF_W4X_STORE(c0 + KC, Xl + ((st + 1) & 1) * (KC * XRS))
         __syncthreads();
-#ifdef NEF_TRACE
-        if (tr_on) {
-#pragma unroll
-            for (int q_ = 0; q_ < 8; ++q_) if (q_ == st) tr_t[4 + 2 * q_] = __builtin_readcyclecounter();
-        }
-#endif
     }
 #undef NEF_W4X_LOAD
 #undef NEF_W4A_ISSUE
 #undef NEF_FA4
 #undef NEF_W4X_ISSUE
 #undef NEF_W4X_STORE
-#ifdef NEF_TRACE
-    if constexpr ((NEF_ABL & 8) != 0) {
-        if (tr_on && threadIdx.x == 0) {
-            unsigned long long* o = nef_trace_ptr + (size_t)(blockIdx.x >> 4) * 24;
-            tr_t[20] = tr_t[21] = __builtin_readcyclecounter();
-#pragma unroll
-            for (int i = 0; i < 24; ++i) o[i] = tr_t[i];
-        }
-    }
-#endif
-    if constexpr ((NEF_ABL & 8) != 0) if (a.T >= 0) return;      // run-time true: the epilogue below is dead at run time only
 
     // epilogue: output transform, then the usual bias / residual / ReLU / dropout / gate on the four adjacent outputs a
     // lane owns per channel row (two 8-byte accesses; T is even, so each pair is inside or outside the row as a whole)
@@ -1347,18 +1259,6 @@ __global__ __launch_bounds__(256, w4_wgs_per_cu(K, WMC, PRO)) void conv_wino4_ke
 #undef NEF_ROW4
         if (inb) slot_out[((int64_t)ch * a.B * nslot + slot) * 2 + (lo & 1)] = sv[0];
     }
-#ifdef NEF_TRACE
-    NEF_TR(20)
-    if (tr_on) {
-        __builtin_amdgcn_s_waitcnt(0);      // vmcnt(0): the output stores have left the wave's queue
-        tr_t[21] = __builtin_readcyclecounter();
-        if (threadIdx.x == 0) {
-            unsigned long long* o = nef_trace_ptr + (size_t)(blockIdx.x >> 4) * 24;
-#pragma unroll
-            for (int i = 0; i < 24; ++i) o[i] = tr_t[i];
-        }
-    }
-#endif
 }
 
 template <int K, int WMC, int PRO = 0>
@@ -1368,20 +1268,13 @@ static int launch_conv_wino4(const nef_conv_args& a, hipStream_t st) {
     constexpr size_t lds = (size_t)(2 * WKC * (NTO + 16) + ((PRO & 1) ? 2 * PRO_MAX_CIN : 0) + 5 * MT) * sizeof(float);
     if ((PRO & 1) && a.Cin_g > PRO_MAX_CIN) return NEF_E_SHAPE;
     static unsigned long long lds_set = 0;      // per-device bits, see nef_ensure_dyn_lds
-#ifdef NEF_TRACE
-    size_t lds_launch = lds;       // NEF_DEBUG_LDS=<bytes>: inflate the LDS request to force fewer workgroups per CU
-    if (const char* e_ = nef_diag_env("NEF_DEBUG_LDS")) lds_launch = (size_t)atol(e_);
-    if (int e = nef_ensure_dyn_lds(reinterpret_cast<const void*>(&conv_wino4_kernel<K, WMC, PRO>), 160 * 1024, &lds_set)) return e;
-#else
-    constexpr size_t lds_launch = lds;
     if (int e = nef_ensure_dyn_lds(reinterpret_cast<const void*>(&conv_wino4_kernel<K, WMC, PRO>), lds, &lds_set)) return e;
-#endif
     const int tps = (a.T + NTO - 1) / NTO;
     const int n_tiles = a.B * tps;
     const int m_tiles = a.Cout_g / MT;
     const int64_t blocks = (int64_t)a.G * m_tiles * n_tiles;
     if (blocks <= 0 || blocks > 0x7fffffff) return NEF_E_SHAPE;
-    hipLaunchKernelGGL((conv_wino4_kernel<K, WMC, PRO>), dim3((unsigned)blocks), dim3(256), lds_launch, st, a, tps, n_tiles, m_tiles);
+    hipLaunchKernelGGL((conv_wino4_kernel<K, WMC, PRO>), dim3((unsigned)blocks), dim3(256), lds, st, a, tps, n_tiles, m_tiles);
     return nef_launch_status();
 }
 
@@ -1732,12 +1625,8 @@ __global__ __launch_bounds__(256, 2) void conv_bwd_weight_kernel(
     if (split < n_tiles) {
         if constexpr (FASTW) NEF_BW_ISSUE_W() else NEF_BW_ISSUE(split)
     }
-#ifdef NEF_BW_SETPRIO
-    __builtin_amdgcn_s_setprio(1);
-#endif
     for (int tile = split; tile < n_tiles; tile += S) {
         __syncthreads();
-        if (!(NEF_ABL & 2) || tile == split) {
         if (FASTW && g_vec) {
             float* gp = GYl + (wave * GR + (lane >> 4)) * GYS + 4 * (lane & 15);
 #pragma unroll
@@ -1799,9 +1688,8 @@ __global__ __launch_bounds__(256, 2) void conv_bwd_weight_kernel(
                 if (nh > 0 && row < CIT) Xl[row * XS + 64 + idx - row * nh] = v;
             }
         }
-        }
         __syncthreads();
-        if constexpr (!(NEF_ABL & 1)) if (tile + S < n_tiles) {
+        if (tile + S < n_tiles) {
             if constexpr (FASTW) NEF_BW_ISSUE_W() else NEF_BW_ISSUE(tile + S)
         }
         if constexpr (WINO == 4 || WINO == 5) {
@@ -1821,7 +1709,7 @@ __global__ __launch_bounds__(256, 2) void conv_bwd_weight_kernel(
                 NEF_BW7A_LOAD(0, 0)
 #pragma unroll
                 for (int s_ = 0; s_ < NSTEP; ++s_) {
-                    if ((NEF_ABL & 4) ? s_ == 0 : s_ + 1 < NSTEP) NEF_BW7A_LOAD(s_ + 1, (s_ + 1) & 1)
+                    if (s_ + 1 < NSTEP) NEF_BW7A_LOAD(s_ + 1, (s_ + 1) & 1)
                     const float g0 = fg[s_ & 1][0][0], g1 = fg[s_ & 1][0][1], g2 = fg[s_ & 1][1][0], g3 = fg[s_ & 1][1][1];
                     const f32x2* d = fx[s_ & 1];
                     const float d0 = d[0][0], d1 = d[0][1], d2 = d[1][0], d3 = d[1][1], d4 = d[2][0], d5 = d[2][1], d6 = d[3][0];
@@ -1868,7 +1756,7 @@ __global__ __launch_bounds__(256, 2) void conv_bwd_weight_kernel(
                 NEF_BW7B_LOAD(0, 0)
 #pragma unroll
                 for (int s_ = 0; s_ < NSTEP; ++s_) {
-                    if ((NEF_ABL & 4) ? s_ == 0 : s_ + 1 < NSTEP) NEF_BW7B_LOAD(s_ + 1, (s_ + 1) & 1)
+                    if (s_ + 1 < NSTEP) NEF_BW7B_LOAD(s_ + 1, (s_ + 1) & 1)
                     const float g0 = fg[s_ & 1][0][0], g1 = fg[s_ & 1][0][1], g2 = fg[s_ & 1][1][0], g3 = fg[s_ & 1][1][1];
                     float u[6];
                     {
@@ -1917,7 +1805,7 @@ __global__ __launch_bounds__(256, 2) void conv_bwd_weight_kernel(
             NEF_BW4_LOAD(0, 0)
 #pragma unroll
             for (int s_ = 0; s_ < NSTEP; ++s_) {
-                if ((NEF_ABL & 4) ? s_ == 0 : s_ + 1 < NSTEP) NEF_BW4_LOAD(s_ + 1, (s_ + 1) & 1)
+                if (s_ + 1 < NSTEP) NEF_BW4_LOAD(s_ + 1, (s_ + 1) & 1)
                 const float g0 = fg[s_ & 1][0][0], g1 = fg[s_ & 1][0][1], g2 = fg[s_ & 1][1][0], g3 = fg[s_ & 1][1][1];
                 float u[6];
                 {
@@ -1967,7 +1855,7 @@ __global__ __launch_bounds__(256, 2) void conv_bwd_weight_kernel(
             NEF_BWW_LOAD(0, 0)
 #pragma unroll
             for (int s_ = 0; s_ < NSTEP; ++s_) {
-                if ((NEF_ABL & 4) ? s_ == 0 : s_ + 1 < NSTEP) NEF_BWW_LOAD(s_ + 1, (s_ + 1) & 1)
+                if (s_ + 1 < NSTEP) NEF_BWW_LOAD(s_ + 1, (s_ + 1) & 1)
                 const float g0 = fg[s_ & 1][0], g1 = fg[s_ & 1][1];
                 float u[4];
                 u[0] = g0;
@@ -2069,7 +1957,6 @@ __global__ __launch_bounds__(256, 2) void conv_bwd_weight_kernel(
 #undef NEF_BW_ISSUE
 #undef NEF_BW_ISSUE_W
 #undef NEF_BW_TAPS
-    if constexpr ((NEF_ABL & 8) != 0) if (T >= 0) return;      // run-time true: the stores below are dead at run time only
     // partials: ws[split][g][k][co][ci]
 #pragma unroll
     for (int i = 0; i < TCI; ++i) {
@@ -2161,6 +2048,8 @@ struct BwdWeightPlan {
     int wco, tci, m_tiles, ci_chunks, S;
     ColTiling ct;
 };
+// workgroups the split count is first sized for (the workspace bound); launches trim it to one round of resident workgroups
+constexpr int BW_TARGET_WGS = 768;
 
 static bool plan_bwd_weight(int B, int T, int G, int Cig, int Cog, int K, BwdWeightPlan* p, int pro_mode = 0,
                             int wino = 0) {
@@ -2180,10 +2069,7 @@ static bool plan_bwd_weight(int B, int T, int G, int Cig, int Cog, int K, BwdWei
     p->ci_chunks = Cig / cit;
     p->ct = make_tiling(B, T, WT);
     const int base = G * p->m_tiles * p->ci_chunks;
-#ifndef NEF_BW_TARGET
-#define NEF_BW_TARGET 768
-#endif
-    int S = (NEF_BW_TARGET + base - 1) / base;
+    int S = (BW_TARGET_WGS + base - 1) / base;
     if (S > p->ct.n_tiles) S = p->ct.n_tiles;
     if (S < 1) S = 1;
     p->S = S;
@@ -2343,7 +2229,7 @@ __attribute__((visibility("hidden"))) int nef_mfma_bww_wino4(const float* x, int
 #if NEF_PART(1)
 extern "C" {
 
-int nef_abi_version(void) { return 18; }
+int nef_abi_version(void) { return 19; }
 
 int nef_pack_weight(const float* w, float* wp, int G, int Cog, int Cig, int K, int transpose_flip,
                     nef_stream_t stream) {
@@ -2438,12 +2324,6 @@ int nef_pack_weights(const nef_pack_desc* descs, int n, nef_stream_t stream) {
 
 size_t nef_conv_args_bytes(void) { return sizeof(nef_conv_args); }
 
-#ifdef NEF_TRACE
-int nef_debug_set_trace(void* p) {
-    unsigned long long* v = (unsigned long long*)p;
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(nef_trace_ptr), &v, sizeof(v));
-}
-#endif
 
 int nef_conv_fwd(const nef_conv_args* a, nef_stream_t stream) {
     NEF_ENTER();

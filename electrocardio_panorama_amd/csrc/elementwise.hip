@@ -475,30 +475,6 @@ __device__ __forceinline__ float up2_at(const float* __restrict__ xr, int Tin, i
     return l0 * xr[i0] + l1 * xr[i1];
 }
 
-// y = upsample2(relu(x*a[p][c] + b[p][c])): the BatchNorm affine + ReLU of the producing layer folded into the resample
-__global__ void upsample2_aff_fwd_kernel(const float* __restrict__ x, const float* __restrict__ a,
-                                         const float* __restrict__ b, float* __restrict__ y, int64_t rows, int C, int Tin,
-                                         int Bp) {
-    const int To = 2 * Tin;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += (int64_t)gridDim.x * 4) {
-        const int c = (int)(row % C);
-        const int p = (int)((row / C) / Bp);
-        const float af = a[p * C + c], bf = b[p * C + c];
-        const float* xr = x + row * Tin;
-        float* yr = y + row * To;
-        for (int i = lane; i < To; i += 64) {
-            float src = 0.5f * ((float)i + 0.5f) - 0.5f;
-            if (src < 0.f) src = 0.f;
-            int i0 = (int)src;
-            if (i0 > Tin - 1) i0 = Tin - 1;
-            const int i1 = i0 + (i0 < Tin - 1 ? 1 : 0);
-            const float l1 = src - (float)i0;
-            yr[i] = (1.f - l1) * fmaxf(fmaf(xr[i0], af, bf), 0.f) + l1 * fmaxf(fmaf(xr[i1], af, bf), 0.f);
-        }
-    }
-}
-
 __global__ void upsample2_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t N, int Tin) {
     const int To = 2 * Tin;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -512,33 +488,6 @@ __global__ void upsample2_fwd_kernel(const float* __restrict__ x, float* __restr
 // transpose of the above.  x[m] is read by outputs 2m-1 (weight .25), 2m (.75), 2m+1 (.75), 2m+2 (.25); the first and
 // the last sample of a row also collect the clamped edge taps.  Lane m loads the pair (g[2m], g[2m+1]) as one 8-byte
 // access (fully coalesced) and takes g[2m-1] / g[2m+2] from its neighbours with wave shuffles.
-// One workgroup per row, four outputs per thread (Tin even): y[4q..4q+3] from x[2q-1..2q+2], same operation order as above.
-__global__ __launch_bounds__(256) void upsample2_aff_fwd_rows(const float* __restrict__ x, const float* __restrict__ a,
-                                                              const float* __restrict__ b, float* __restrict__ y, int C,
-                                                              int Tin, int Bp) {
-    const int64_t row = blockIdx.x;
-    const int c = (int)(row % C);
-    const int p = (int)((row / C) / Bp);
-    const float af = a[p * C + c], bf = b[p * C + c];
-    const float* xr = x + row * Tin;
-    nef_f32x4* yr = (nef_f32x4*)(y + row * 2 * Tin);
-    const int Q = Tin >> 1;
-    for (int q = threadIdx.x; q < Q; q += 256) {
-        const float2 m = *reinterpret_cast<const float2*>(xr + 2 * q);
-        const float xl = xr[q > 0 ? 2 * q - 1 : 0], xh = xr[2 * q + 2 < Tin ? 2 * q + 2 : Tin - 1];
-        const float r0 = fmaxf(fmaf(xl, af, bf), 0.f), r1 = fmaxf(fmaf(m.x, af, bf), 0.f);
-        const float r2 = fmaxf(fmaf(m.y, af, bf), 0.f), r3 = fmaxf(fmaf(xh, af, bf), 0.f);
-        nef_f32x4 o;
-        // i = 4q: src = 2q - .25 (clamped to 0 at q = 0: l1 = 0, both taps are x[0])
-        o[0] = q > 0 ? 0.25f * r0 + 0.75f * r1 : 1.f * r1 + 0.f * r2;
-        o[1] = 0.75f * r1 + 0.25f * r2;
-        o[2] = 0.25f * r1 + 0.75f * r2;
-        o[3] = 0.75f * r2 + 0.25f * r3;
-        yr[q] = o;
-    }
-}
-
-
 __global__ void upsample2_bwd_kernel(const float* __restrict__ gy, float* __restrict__ gx, int64_t N, int Tin) {
     const int To = 2 * Tin;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1993,21 +1942,6 @@ int nef_upsample2_fwd(const float* x, float* y, int64_t N, int Tin, nef_stream_t
     return nef_launch_status();
 }
 
-int nef_upsample2_aff_fwd(const float* x, const float* a, const float* b, float* y, int N, int C, int Tin, int Bp,
-                          nef_stream_t stream) {
-    NEF_ENTER();
-    NEF_REQUIRE(x && a && b && y, NEF_E_NULL);
-    NEF_REQUIRE(N > 0 && C > 0 && Tin > 0 && Bp > 0, NEF_E_SHAPE);
-    const int64_t rows = (int64_t)N * C;
-    if ((Tin & 1) == 0 && Tin >= 4 && rows <= 0x7FFFFFFF) {
-        hipLaunchKernelGGL(upsample2_aff_fwd_rows, dim3((unsigned)rows), dim3(256), 0, NEF_ST, x, a, b, y, C, Tin, Bp);
-        return nef_launch_status();
-    }
-    hipLaunchKernelGGL(upsample2_aff_fwd_kernel, dim3(nef_stream_grid(rows, 4)), dim3(256), 0, NEF_ST, x, a, b, y, rows, C,
-                       Tin, Bp);
-    return nef_launch_status();
-}
-
 int nef_upsample2_bwd(const float* gy, float* gx, int64_t N, int Tin, nef_stream_t stream) {
     NEF_ENTER();
     NEF_REQUIRE(gy && gx, NEF_E_NULL);
@@ -2463,7 +2397,7 @@ int nef_regroup_halves(const float* src, float* dst, int Co, int Cih, int K, int
     return nef_launch_status();
 }
 
-// diagnostics (not in the header): `wgs` workgroups busy for `us` microseconds on `stream` (bench.py --dry-collective)
+// diagnostics: `wgs` workgroups busy for `us` microseconds on `stream` (bench.py --dry-collective)
 int nef_debug_spin_us(float us, int wgs, nef_stream_t stream) {
     NEF_ENTER();
     NEF_REQUIRE(us >= 0.f && us <= 50000.f && wgs >= 1 && wgs <= 64, NEF_E_SHAPE);

@@ -657,10 +657,7 @@ __global__ __launch_bounds__(512, 1) void hconv_pair_kernel(const _Float16* __re
     constexpr int CIN = 256, COUT = 128, NT = 256, NI = 4;
     constexpr int XROWS = NT + 2;
     constexpr int XBYTES = XROWS * PH_XRS;
-#ifndef NEF_PHP_AD
-#define NEF_PHP_AD 6
-#endif
-    constexpr int AD = NEF_PHP_AD;           // A ring: fragments of AD - 1 k-steps in flight (a divisor of 12)
+    constexpr int AD = 6;                    // A ring: fragments of AD - 1 k-steps in flight (a divisor of 12)
     static_assert(12 % AD == 0, "the ring position of a k-step must not depend on the chunk");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const C1 = smem + 2 * XBYTES;      // [258][PHP_CRS]: row r = time r - 1
@@ -903,13 +900,7 @@ __global__ __launch_bounds__(512, 1) void hconv_tail_kernel(const _Float16* __re
     constexpr int CIN = 128, NT = 512, NI = 4;
     constexpr int XROWS = NT + 2;
     constexpr int XBYTES = XROWS * PH_XRS;
-#ifndef NEF_PHT_AD
-#define NEF_PHT_AD 6
-#endif
-#ifndef NEF_PHT_EARLY
-#define NEF_PHT_EARLY 1  // the input rows of a staging pass are fetched one phase ahead, just before the preceding epilogue (see the main loop)
-#endif
-    constexpr int AD = NEF_PHT_AD;          // A ring: fragments of AD - 1 k-steps in flight (a divisor of 12; one 1 KB fragment per k-step and wave: 6 = 24 registers)
+    constexpr int AD = 6;                   // A ring: fragments of AD - 1 k-steps in flight (a divisor of 12; one 1 KB fragment per k-step and wave: 6 = 24 registers)
     static_assert(12 % AD == 0, "the ring position of a k-step must not depend on the chunk");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const XA = smem;
@@ -1014,9 +1005,9 @@ __global__ __launch_bounds__(512, 1) void hconv_tail_kernel(const _Float16* __re
 #define PHT_A(wd_, slot_, stage_)                                                                             \
     a[slot_] = __builtin_bit_cast(nef_h8, __builtin_amdgcn_raw_buffer_load_b128(wd_, avoff, (stage_) * 2048, 0));
     // 12 k-steps (3 taps x 4 x 16 channels) of one 64-channel chunk, B fragments at Bp_ + (ni * 32 + tap) * PH_XRS + kq * 32;
-    // A of k-step s + AD - 1 from (WDC_, SC_ + .) or, past the chunk, from (WDN_, SN_ + .); FE_: fetch (pair FN_, chunk FC_) at
-    // k-step 1; ST_: stage the fetched rows into XN_, one row per k-step, during k-steps 4 .. 11
-#define PHT_STEPS(Bp_, WDC_, SC_, WDN_, SN_, FE_, FN_, FC_, ST_, XN_)                                         \
+    // A of k-step s + AD - 1 from (WDC_, SC_ + .) or, past the chunk, from (WDN_, SN_ + .); ST_: stage the rows fetched ahead of
+    // this phase (PHT_FETCH) into XN_, one row per k-step, during k-steps 4 .. 11
+#define PHT_STEPS(Bp_, WDC_, SC_, WDN_, SN_, ST_, XN_)                                                        \
     {                                                                                                         \
         nef_h8 b[2][NI];                                                                                      \
         _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) b[0][ni] = *(const nef_h8*)((Bp_) + ni * 32 * PH_XRS); \
@@ -1031,7 +1022,6 @@ __global__ __launch_bounds__(512, 1) void hconv_tail_kernel(const _Float16* __re
             if (s + 1 < 12)                                                                                   \
                 _Pragma("unroll") for (int ni = 0; ni < NI; ++ni)                                             \
                     b[(s + 1) & 1][ni] = *(const nef_h8*)((Bp_) + (ni * 32 + (s + 1) / 4) * PH_XRS + ((s + 1) % 4) * 32); \
-            if ((FE_) && !NEF_PHT_EARLY && s == 1) PHT_FETCH(FN_, FC_)                                        \
             __builtin_amdgcn_sched_barrier(0);                                                                \
             if ((ST_) && s >= 4) PHT_STAGE(XN_, s - 4, s - 3)                                                 \
             if ((ST_) && TILED && s == 11) PHT_STAGE(XN_, 8, 9)                                               \
@@ -1088,7 +1078,7 @@ __global__ __launch_bounds__(512, 1) void hconv_tail_kernel(const _Float16* __re
         PHT_FETCH(w, 0)
         PHT_STAGE(XA, 0, 9)
         PHT_PAD_ROWS(XA, fbase)
-        if (NEF_PHT_EARLY) PHT_FETCH(w, 1)
+        PHT_FETCH(w, 1)
     }
     __syncthreads();
     const float b0 = bout[0];
@@ -1101,22 +1091,22 @@ __global__ __launch_bounds__(512, 1) void hconv_tail_kernel(const _Float16* __re
         const char* const BA = XA + (wn * 128 + lo) * PH_XRS + 16 * hi;
         const char* const BB = XB + (wn * 128 + lo) * PH_XRS + 16 * hi;
         // ---- layer 3: chunk 0 from buffer A while chunk 1 is fetched and staged into buffer B, then chunk 1
-        PHT_STEPS(BA, wd3, 0, wd3, 12, true, w, 1, true, XB)
+        PHT_STEPS(BA, wd3, 0, wd3, 12, true, XB)
         PHT_PAD_ROWS(XB, base)
         __syncthreads();
-        PHT_STEPS(BB, wd3, 12, wd4, 0, false, w, 0, false, XB)
+        PHT_STEPS(BB, wd3, 12, wd4, 0, false, XB)
         // Memory returns in issue order: a weight fragment issued behind these rows cannot be consumed before they have arrived.  Issued
         // here the rows have the epilogue and AD - 1 k-steps to come from HBM; issued at k-step 1 of the staging phase (rounds 2-5)
         // they had AD k-steps, and the matrix pipes waited for them.
-        if (NEF_PHT_EARLY) PHT_FETCH(n_next, 0)
+        PHT_FETCH(n_next, 0)
         __syncthreads();                     // every wave is done reading buffer B as an input chunk
         PHT_TO_LDS(bv3)
         PHT_ZERO_SLOTS()
         __syncthreads();                     // c3 complete
         // ---- layer 4: straight from the c3 rows; the next pair's first chunk rides along into buffer A
-        PHT_STEPS(BB, wd4, 0, wd3, 0, true, n_next, 0, true, XA)
+        PHT_STEPS(BB, wd4, 0, wd3, 0, true, XA)
         PHT_PAD_ROWS(XA, fbase)              // (fbase: the next item's tile)
-        if (NEF_PHT_EARLY) PHT_FETCH(n_next, 1)      // for the next item's first phase
+        PHT_FETCH(n_next, 1)      // for the next item's first phase
         __syncthreads();                     // every wave is done reading c3; buffer A holds the next pair's chunk 0
         PHT_TO_LDS(bv4)
         PHT_ZERO_SLOTS()                     // (rows outside the sequence zero: their share of the last conv is zero)
@@ -1356,13 +1346,6 @@ static int launch_hconv_tail(const void* x, const void* wp3, const float* b3, co
     return nef_launch_status();
 }
 
-static bool ph_l4_old() {
-    // the 64 -> 64 layer (+ fused last conv) on hconv_wide_kernel<64, 64, 0, OUT> measured SLOWER than the round-1 kernel (sweep 52.1 vs
-    // 50.7 ms, gen_ecg share 9.98 vs 9.68: one 64-channel chunk per tile leaves the double buffer nothing to hide): opt-in, A/B only
-    static const bool v = !(nef_diag_env("NEF_PANO_L4_WIDE") && atoi(nef_diag_env("NEF_PANO_L4_WIDE")) == 1);
-    return v;
-}
-
 extern "C" {
 
 int nef_pano_h_from_f32(const float* x, void* y, int B, int C, int T, nef_stream_t stream) {
@@ -1403,7 +1386,6 @@ int nef_pano_h_conv(const void* x, const void* wp, const float* bias, const floa
     PHW_CASE(128, 128, 0);
     PHW_CASE(128, 64, 2);
     PHW_CASE(128, 64, 0);
-    if (!ph_l4_old()) PHW_CASE(64, 64, 0);      // round 5, opt-in (NEF_DIAG=1 NEF_PANO_L4_WIDE=1): measured slower, see ph_l4_old()
 #undef PHW_CASE
     PH_CASE(64, 64, 0);
 #undef PH_CASE
@@ -1440,10 +1422,9 @@ int nef_pano_h_conv_outconv(const void* x, const void* wp, const float* bias, co
                        T, NT, tiles, nq, (long)out_bs, (long)out_is);
     int rc = nef_launch_status();
     if (rc != NEF_OK) return rc;
-    rc = ph_l4_old() ? launch_hconv<64, 64, 0, 1>(x, wp, bias, nullptr, nullptr, N, T, 1, nq, 0, 0, st, wout, out, (long)out_bs,
-                                                  (long)out_is)
-                     : launch_hconv_wide<64, 64, 0, 1>(x, wp, bias, nullptr, nullptr, N, T, 1, nq, 0, 0, st, wout, out,
-                                                       (long)out_bs, (long)out_is);
+    // the 64 -> 64 layer (+ fused last conv) stays on the round-1 kernel: hconv_wide_kernel<64, 64, 0, 1> measured SLOWER (sweep 52.1
+    // vs 50.7 ms, gen_ecg share 9.98 vs 9.68: one 64-channel chunk per tile leaves the double buffer nothing to hide)
+    rc = launch_hconv<64, 64, 0, 1>(x, wp, bias, nullptr, nullptr, N, T, 1, nq, 0, 0, st, wout, out, (long)out_bs, (long)out_is);
     if (rc != NEF_OK) return rc;
     hipLaunchKernelGGL(ph_sigmoid3_kernel, dim3(nef_stream_grid((int64_t)N * T, 256)), dim3(256), 0, st, out, bout, N, T,
                        nq, (long)out_bs, (long)out_is);

@@ -124,12 +124,8 @@ __global__ __launch_bounds__(256) void stem_bwd_weight_kernel(const float* __res
         const unsigned go_ = (tp_ >= 0 && tp_ < T) ? (unsigned)(tp_ * 4) : NEF_OOB;                                   \
         _Pragma("unroll") for (int c = 0; c < BW_CPW; ++c) gn[c] = nef_buf_f32(grs_, go_, (unsigned)(c * T * 4));     \
     }
-#ifndef NEF_STEM_PREFETCH
-#define NEF_STEM_PREFETCH 1
-#endif
-    if (NEF_STEM_PREFETCH && split < n_units) NEF_STEM_FETCH(split)
+    if (split < n_units) NEF_STEM_FETCH(split)
     for (int unit = split; unit < n_units; unit += BW_SPLIT) {
-        if (!NEF_STEM_PREFETCH) NEF_STEM_FETCH(unit)
         const int b = unit / tiles_per_row;
         const int tp = (unit - b * tiles_per_row) * BW_TP + lane - 1;
         float xw[19], gc[BW_CPW];
@@ -137,7 +133,7 @@ __global__ __launch_bounds__(256) void stem_bwd_weight_kernel(const float* __res
         for (int i = 0; i < 19; ++i) xw[i] = xn[i];
 #pragma unroll
         for (int c = 0; c < BW_CPW; ++c) gc[c] = gn[c];
-        if (NEF_STEM_PREFETCH && unit + BW_SPLIT < n_units) NEF_STEM_FETCH(unit + BW_SPLIT)
+        if (unit + BW_SPLIT < n_units) NEF_STEM_FETCH(unit + BW_SPLIT)
         const bool valid = tp >= 0 && tp < T;
         const bool owns = valid && lane > 0 && lane < 63;
         const bool has_l = (2 * tp - 1) >= 0;
@@ -364,11 +360,8 @@ int nef_stem_bwd_weight(const float* x, const float* w, const float* gy, float* 
     const int T = L / 4;
     hipStream_t st = (hipStream_t)stream;
     const int n = V * CPL * KW;
-#ifndef NEF_STEM_MFMA
-#define NEF_STEM_MFMA 1
-#endif
     const size_t lds = (size_t)(MB_HALO + L + MB_TAIL) * sizeof(float);
-    if (NEF_STEM_MFMA && T % 2 == 0 && lds <= 64 * 1024) {       // a whole input row in LDS; gy rows 8-byte aligned
+    if (T % 2 == 0 && lds <= 64 * 1024) {       // a whole input row in LDS; gy rows 8-byte aligned
         const int slots = B < MB_SPLIT ? B : MB_SPLIT;
         hipLaunchKernelGGL(stem_bwd_weight_mfma_kernel, dim3((unsigned)(slots * V)), dim3(256), lds, st, x, w, gy, (float*)ws, B,
                            V, L, T);

@@ -18,24 +18,12 @@ N_SEG, ROI_BINS = 7, 16
 DROP_P = 0.2           # every nn.Dropout on the path (model_nefnet.py:46, encoder/resnet_1d.py:37)
 BN_EPS, BN_MOM = 1e-5, 0.1
 
-# NEF_FUSE_L2=0: third decoder conv on a materialised u2 = up2(relu(bn(c2))) instead of the (affine + ReLU, x2) prologue on c2.
+# The third decoder conv takes u2 = up2(relu(bn(c2))) through its (affine + ReLU, x2) prologue on c2 instead of a materialised u2.
 # Round 2 measured the prologue form slower (60.2 against 58.8 ms/step: the register-staged weight gradient paid for the
 # prologue per staged element); since the LDS-DMA weight gradient interpolates while it forms its fragments it is the
 # faster one: 47.85 -> 47.36 ms/step, and the 1.97 GB tensor is never written.  On the split-fp16 kernels of round 4 the two
 # forms are equal within the run-to-run noise (three alternating runs on one box: 31.2 - 31.7 against 31.5 - 31.9 ms/step,
 # bit-identical loss): the prologue stays.
-_FUSE_L2 = _env.get("NEF_FUSE_L2", "1") == "1"
-
-# NEF_FUSE_STATS=0: BatchNorm statistics by a pass over the conv output (nef_bn_train_stats) instead of the conv epilogue
-_FUSE_STATS = _env.get("NEF_FUSE_STATS", "1") == "1"
-# NEF_BNB_UP=0: the BatchNorm-backward sums behind a x2 upsampling by the pass (bn_relu_bwd_up reduces them itself) instead of the
-# backward-data conv's epilogue
-_BNB_UP = _env.get("NEF_BNB_UP", "1") == "1"
-# NEF_FOLD_CHSCALE=0: the theta scaling in front of w_conv as a pass of its own (chscale_fwd) instead of in_scale / res_scale on the block's convs
-_FOLD_CHSCALE = _env.get("NEF_FOLD_CHSCALE", "1") == "1"
-_FOLD_CHSCALE_BWD = _env.get("NEF_FOLD_CHSCALE_BWD", "1") == "1"      # ... and its backward in the epilogue of the block's last backward-data launch
-
-_BWD_F4 = _env.get("NEF_BWD_F4", "1")
 
 DROPOUT_SITES = ("W_encoder.layer1.0", "W_encoder.layer1.1", "W_encoder.layer1.2", "w_conv.0", "z1_conv.0",
                  "z2_conv1.0", "z2_conv2.0", "z2_conv2.2")
@@ -99,9 +87,8 @@ def block_scale_ok(P, prefix, G, T):
 def _bwd_f4(K):
     """Backward-data launches of the encoder-side blocks take F(4,3) (K=3) resp. F(4,4) + F(4,3) (K=7): no ReLU decision is ever taken
     on a gradient, so the exact-zero / decision-flip argument that keeps their FORWARD convs on F(2,3) does not apply.
-    Measured on the reference's 3-step SGD trajectory: worst parameter 1.4e-5 (bar 2e-4), stem weight 1.8e-6.
-    NEF_BWD_F4=0: F(2,3) there too; =3: K=3 only."""
-    return _BWD_F4 != "0" and (K == 3 or (K == 7 and _BWD_F4 != "3"))
+    Measured on the reference's 3-step SGD trajectory: worst parameter 1.4e-5 (bar 2e-4), stem weight 1.8e-6."""
+    return K in (3, 7)
 
 
 def _block_pack_requests(P, prefix, G, T, flip):
@@ -174,8 +161,6 @@ def _side(device, work=None):
     if mode == "0" or (mode == "auto" and work is not None and work < _SIDE_MIN_WORK
                        and not torch.cuda.is_current_stream_capturing()):
         return ops._Inline()
-    if torch.cuda.is_current_stream_capturing() and _env.get("NEF_GRAPH_SIDE", "1") == "0":
-        return ops._Inline()          # NEF_GRAPH_SIDE=0: a captured step stays on the capturing stream
     return ops.SideStream.get(device)
 
 
@@ -292,17 +277,11 @@ def decoder_fwd(D, P, Bf, passes, training, save, shared_B=None):
     N = D.shape[0] if shared_B is None else 3 * shared_B
     for li, (blk, cv, bn, cout) in enumerate(_DEC):
         wname, bname, pre = f"{blk}.double_conv.{cv}.weight", f"{blk}.double_conv.{cv}.bias", f"{blk}.double_conv.{bn}"
-        if li == 2 and not _FUSE_L2:
-            # NEF_FUSE_L2=0 (the round-2 form): this layer materialises u2 = up(relu(bn(c2))) and runs the plain conv
-            x_in = ops.upsample2_aff_fwd(x, pro_in[0], pro_in[1], pro_in[2])
-            pro = (0, None, None, 1)
-            up_after = True
-        else:
-            x_in = x
-            mode = (2 if li in (0, 2) else 0) | (1 if pro_in is not None else 0)
-            pro = (mode, pro_in[0], pro_in[1], pro_in[2]) if pro_in is not None else (mode, None, None, 1)
-            up_after = bool(mode & 2)
-        T_out = x_in.shape[2] * (2 if up_after and pro[0] & 2 else 1)
+        x_in = x
+        mode = (2 if li in (0, 2) else 0) | (1 if pro_in is not None else 0)
+        pro = (mode, pro_in[0], pro_in[1], pro_in[2]) if pro_in is not None else (mode, None, None, 1)
+        up_after = bool(mode & 2)
+        T_out = x_in.shape[2] * (2 if up_after else 1)
         stats = xedge = None
         # the two convs behind a x2 upsampling run in polyphase form where the shape allows: a conv over the half-resolution input
         # whose rows are the two output phases (ops.conv_poly_fwd) -- half the staged elements, no interpolation arithmetic
@@ -322,7 +301,7 @@ def decoder_fwd(D, P, Bf, passes, training, save, shared_B=None):
                 c = ops.pass_combine_fwd(p2, P[bname], shared_B)
         elif poly:
             slots = None
-            if training and _FUSE_STATS:
+            if training:
                 c, slots = ops.conv_poly_fwd(GV.dense(x_in, 1), P[wname], cout, bias=P[bname], pro=pro, stats=True, save_edge=save)
             else:
                 c = ops.conv_poly_fwd(GV.dense(x_in, 1), P[wname], cout, bias=P[bname], pro=pro, save_edge=save)
@@ -334,7 +313,7 @@ def decoder_fwd(D, P, Bf, passes, training, save, shared_B=None):
         else:
             wp = ops.pack_weight(P[wname], 1, T=T_out, f4=True)
             # train mode: the F(4,3) epilogue leaves the BatchNorm slot sums of c -- no statistics pass over c
-            slots = ops.conv_stats_buffer(wp, N, 1, cout, T_out, D.device) if (training and _FUSE_STATS) else None
+            slots = ops.conv_stats_buffer(wp, N, 1, cout, T_out, D.device) if training else None
             c = ops.conv(GV.dense(x_in, 1), wp, cout, 3, bias=P[bname], pro=pro, stats=slots)
             if slots is not None:
                 stats = ops.bn_stats_from_slots(slots, P[pre + ".weight"], P[pre + ".bias"], Bf[pre + ".running_mean"],
@@ -423,7 +402,7 @@ def decoder_bwd(dsaved, g_out, P, grads, side=None):
                 # x2 upsampling in front of this conv: the polyphase pass leaves the gradient wrt the half-resolution input (= what the
                 # BatchNorm below produced) directly, with that BatchNorm's backward sums in its epilogue
                 bnb = None
-                if li > 0 and _FUSE_STATS and saved[li - 1][2] is not None:
+                if li > 0 and saved[li - 1][2] is not None:
                     cb, mb, ib, ab, bb = saved[li - 1][1:6]
                     bnb = (cb, mb, ib, ab, bb, cb.shape[0] // passes)
                 g = ops.conv_bwd_data_poly(gcv, P[wname], x.shape[1], bnb=bnb, phase_major=pm)
@@ -437,11 +416,11 @@ def decoder_bwd(dsaved, g_out, P, grads, side=None):
             # reduction sums of that BatchNorm's backward (it reads c_below's tile for the ReLU decision and xhat)
             # (with the x2 upsampling in between, the sums are those of its adjoint -- what bn_relu_bwd_up reduces)
             g_slots = bnb = None
-            if li > 0 and _FUSE_STATS:
+            if li > 0:
                 cb, mb, ib, ab, bb = saved[li - 1][1:6]
                 Tg = gc.shape[2]
                 plain = not up_after and cb.shape[2] == Tg
-                upv = _BNB_UP and bool(up_after) and 2 * cb.shape[2] == Tg and Tg % 8 == 0 and Tg >= 16     # the g_is_up case below
+                upv = bool(up_after) and 2 * cb.shape[2] == Tg and Tg % 8 == 0 and Tg >= 16     # the g_is_up case below
                 if (plain or upv) and mb is not None:
                     g_slots = ops.conv_stats_buffer(wpf, cb.shape[0], 1, x.shape[1], Tg, gc.device)
                     if g_slots is not None:
@@ -477,7 +456,7 @@ def _latents(P, x, in_theta, rois, drop, save, pack_side=None):
         a, s = block_fwd(GV.dense(a, V), P, f"W_encoder.layer1.{i}", 7, 128, drop)
         sv["blk_enc"].append(s)
     e = ops.theta_mlp_fwd(in_theta, P["mlp1.weight"], P["mlp1.bias"])           # [B, V, 128]
-    if _FOLD_CHSCALE and block_scale_ok(P, "w_conv.0", V, T):
+    if block_scale_ok(P, "w_conv.0", V, T):
         # a * e is never written: w_conv's first conv scales while it stages, its last conv scales the residual (round 5)
         enc, sv["blk_w_conv"] = block_fwd(GV.dense(a, V), P, "w_conv.0", 3, 128, drop, in_scale=(e, V * 128, 128))
     else:
@@ -647,10 +626,6 @@ def sweep_eval(P, Bf, latent, query_thetas, chunk=8):
     return rest
 
 
-PANO_FUSE_PAIR = _env.get("NEF_PANO_FUSE_PAIR", "1") != "0"   # measurement switch: 0 = two launches
-PANO_FUSE_TAIL = _env.get("NEF_PANO_FUSE_TAIL", "1") != "0"   # round 6: layers 3 + 4 + last conv in one launch (L <= 512); 0 = two launches
-
-
 def sweep_eval_h(P, Bf, latent, query_thetas, pair_budget=16384):
     """The eval-mode sweep on the fp16 matrix cores (pano_h.hip; SURVEY 8-f2, BASELINE configs 4/5).  Same folding as
     sweep_eval; activations are fp16 [pair][time][channel] with pair = (sample, angle) sample-major, so the result
@@ -670,28 +645,17 @@ def sweep_eval_h(P, Bf, latent, query_thetas, pair_budget=16384):
         bias.append(bf_)
     rest = torch.empty(B, Q, 4 * T, device=dev, dtype=torch.float32)
     nq = max(1, min(Q, pair_budget // max(B, 1)))      # angles per chunk: bounds the fp16 intermediates
-    bufs = None
+    c2buf = None      # the only fp16 intermediate: layer 2's output
     for q0 in range(0, Q, nq):
         n = min(nq, Q - q0)
         N = B * n
-        if bufs is None or bufs[0].shape[0] != N:
-            bufs = (torch.empty(N, 2 * T, 128, device=dev, dtype=torch.float16),
-                    torch.empty(N, 2 * T, 128, device=dev, dtype=torch.float16),
-                    torch.empty(N, 4 * T, 64, device=dev, dtype=torch.float16))
-        if PANO_FUSE_PAIR:      # layers 1 + 2 in one pass (one tile per pair up to 256 rows, tiles of 252 rows beyond)
-            c2 = ops.pano_h_conv_pair(lat_h, wp[0], bias[0], (rq[:, q0:], Q * 256, 256), wp[1], bias[1], N, n, n,
-                                      out=bufs[1])
-        else:
-            c1 = ops.pano_h_conv(lat_h, wp[0], bias[0], 128, N=N, upsample=True, scale=(rq[:, q0:], Q * 256, 256),
-                                 x_div=n, nq=n, out=bufs[0])
-            c2 = ops.pano_h_conv(c1, wp[1], bias[1], 128, out=bufs[1])
-        if PANO_FUSE_TAIL:      # layers 3 + 4 + last conv + sigmoid in one pass (one tile per pair up to 512 rows, tiles of 508 beyond)
-            ops.pano_h_conv_tail(c2, wp[2], bias[2], wp[3], bias[3], P["decoder.4.weight"], P["decoder.4.bias"], rest[:, q0:], n,
-                                 Q * 4 * T, 4 * T)
-            continue
-        c3 = ops.pano_h_conv(c2, wp[2], bias[2], 64, upsample=True, out=bufs[2])
-        ops.pano_h_conv_outconv(c3, wp[3], bias[3], P["decoder.4.weight"], P["decoder.4.bias"], rest[:, q0:], n,
-                                Q * 4 * T, 4 * T)
+        if c2buf is None or c2buf.shape[0] != N:
+            c2buf = torch.empty(N, 2 * T, 128, device=dev, dtype=torch.float16)
+        # layers 1 + 2 in one pass (one tile per pair up to 256 rows, tiles of 252 rows beyond)
+        c2 = ops.pano_h_conv_pair(lat_h, wp[0], bias[0], (rq[:, q0:], Q * 256, 256), wp[1], bias[1], N, n, n, out=c2buf)
+        # layers 3 + 4 + last conv + sigmoid in one pass (one tile per pair up to 512 rows, tiles of 508 beyond)
+        ops.pano_h_conv_tail(c2, wp[2], bias[2], wp[3], bias[3], P["decoder.4.weight"], P["decoder.4.bias"], rest[:, q0:], n,
+                             Q * 4 * T, 4 * T)
     return rest
 
 
@@ -754,7 +718,7 @@ def _latents_bwd(P, sv, gz1, gz2r, grads, side, z1_pre_gated=False, early=False)
     else:
         gz2c = ops.roi_align_bwd(gh0.view(B, 128 * V, N_SEG, ROI_BINS), sv["rois"], T)
         block_bwd(sv["blk_z2c"], gz2c, P, grads, out=GV.half(genc, V, 1), side=side, gate_input=True)
-    gew = block_bwd(sv["blk_w_conv"], genc, P, grads, side=side, pre_gated=True, scale_bwd=_FOLD_CHSCALE_BWD)
+    gew = block_bwd(sv["blk_w_conv"], genc, P, grads, side=side, pre_gated=True, scale_bwd=True)
     if isinstance(gew, tuple):      # the scaling's backward came out of the block's last launch (block_fwd(..., in_scale=...) + scale_bwd)
         g, ge = gew
     else:

@@ -215,9 +215,9 @@ WINOGRAD = _WV != "0"
 # was no faster than F(2,3) (1.31 vs 1.33 ms on the K=7 conv).
 WINO_FWD = 1 if _WV in ("1", "2") else 2
 # Winograd weight gradients (nef_conv_bwd_weight_wino4): K=3 through the transposed F(3,4), K=7 with the taps split 4 + 3 over
-# two launches (transposed F(4,4) + F(3,4)).  NEF_BW_WINO4=0 / NEF_BW7_F42=0 put K=3 / K=7 back on the direct kernel.
-WINO_BW4 = _env.get("NEF_BW_WINO4", "1") == "1" and _WV not in ("1", "2")
-WINO_BW7 = _env.get("NEF_BW7_F42", "1") == "1" and _WV not in ("1", "2")
+# two launches (transposed F(4,4) + F(3,4)).
+WINO_BW4 = _WV not in ("1", "2")
+WINO_BW7 = _WV not in ("1", "2")
 _WINO_PLANES = {(1, 3): 4, (1, 7): 10, (2, 3): 6, (2, 7): 13}
 
 
@@ -226,13 +226,6 @@ _WINO_PLANES = {(1, 3): 4, (1, 7): 10, (2, 3): 6, (2, 7): 13}
 # instructions' pipe time.  NEF_H2=0 keeps the fp32 Winograd forms; NEF_H2=1 takes it wherever the shape allows
 # (128-channel output tiles, 16-channel input chunks, T even and >= 128; K = 7 without an input prologue).
 H2 = _env.get("NEF_H2", "1") == "1"
-_H2_DIR = {False: _env.get("NEF_H2_FWD", "1") == "1", True: _env.get("NEF_H2_BWD", "1") == "1"}     # diagnostics
-_H2_K = _env.get("NEF_H2_K", "1,3,7").split(",")
-_H2_64 = _env.get("NEF_H2_64", "1") == "1"
-_H2_MIN_T = int(_env.get("NEF_H2_MIN_T", "0"))      # shortest sequence the split-fp16 kernels take (256-column tiles)
-_H2_W = _env.get("NEF_H2_W", "1") == "1"          # weight gradients on the split-fp16 kernel too (csrc/conv_h2w.hip)
-_H2_WK = _env.get("NEF_H2_WK", "1,3,7").split(",")
-_H2_AMAX = _env.get("NEF_H2_AMAX", "sticky")      # diagnostics: "anon" = every launch measures first, "follow" = no stickiness
 
 
 # Small problems stay on the fp32 kernels: the split-fp16 kernels tile a sample in 256 outputs x 128 (64) channels, and below
@@ -240,14 +233,13 @@ _H2_AMAX = _env.get("NEF_H2_AMAX", "sticky")      # diagnostics: "anon" = every 
 # batch 32 x L 512: 3.11 ms per captured step with them, 2.72 without).  The engine announces the batch of the pass it is about
 # to run (BATCH_HINT); without a hint (bare ops calls) the shape rules alone decide.
 BATCH_HINT = None
-_H2_PACK = _env.get("NEF_H2_PACK", "1") == "1"
-_H2_MIN_WGS = int(_env.get("NEF_H2_MIN_WGS", "256"))
+_H2_MIN_WGS = 256       # fewest workgroups a split-fp16 launch must fill
 
 
 def _h2_packed(K, T_out, pro=0):
     """Short rows (8 <= T <= 64, T % 4 == 0) of plain K = 1 / K = 3 launches: several samples per tile of conv_h2_kernel
-    (csrc/conv_h2.hip, PACK).  NEF_H2_PACK=0: they stay on the fp32 kernels."""
-    return _H2_PACK and K in (1, 3) and not pro and 8 <= T_out <= 64 and T_out % 4 == 0
+    (csrc/conv_h2.hip, PACK)."""
+    return K in (1, 3) and not pro and 8 <= T_out <= 64 and T_out % 4 == 0
 
 
 def _h2_fills(G, Cout_g, T_out, tile_t, tile_c):
@@ -260,10 +252,8 @@ def _h2_fills(G, Cout_g, T_out, tile_t, tile_c):
 
 
 def h2_ok(K, Cin_g, Cout_g, T_out, pro=0):
-    # NEF_H2_64=0 leaves the 64-channel output tiles (conv_h2_kernel<., ., 1>) to the F(4,3) kernels
     return (H2 and (K == 3 or (K in (1, 7) and not pro)) and T_out % 2 == 0 and
-            (T_out >= max(128, _H2_MIN_T) or (_h2_packed(K, T_out, pro) and _H2_64)) and Cin_g % 16 == 0 and
-            Cout_g % (64 if _H2_64 else 128) == 0)
+            (T_out >= 128 or _h2_packed(K, T_out, pro)) and Cin_g % 16 == 0 and Cout_g % 64 == 0)
 
 
 # Input magnitudes of the split-fp16 launches, per call site (= per weight tensor and direction): `cur` is what a launch derives
@@ -486,8 +476,8 @@ def amax_roll():
         if st["used"]:
             # one launch over the slots handed out so far (rounds 4-5: ~10 torch elementwise launches per pass)
             with torch.cuda.device(st["cur"].device):
-                _lib.check(_lib.load().nef_amax_roll(_p(st["cur"]), _p(st["nxt"]), int(st["n"]), H2_FOLLOW_UP, H2_FOLLOW_DOWN,
-                                                     int(_H2_AMAX == "follow"), _stream()), "nef_amax_roll")
+                _lib.check(_lib.load().nef_amax_roll(_p(st["cur"]), _p(st["nxt"]), int(st["n"]), H2_FOLLOW_UP, H2_FOLLOW_DOWN, 0,
+                                                     _stream()), "nef_amax_roll")
             st["used"] = False
 
 
@@ -553,7 +543,7 @@ def _pack_shape(w, G, flip, T, f4=False, plain=True, src=None):
     Cog, Cig, K = shp[0] // G, shp[1], shp[2]
     cin_g, cout_g = (Cog, Cig) if flip else (Cig, Cog)          # roles in the launch that consumes the operand
     wino = (WINO_FWD if f4 else 1) if (T is not None and wino_ok(K, cin_g, cout_g, T)) else 0
-    if (T is not None and (T >= 128 or plain) and h2_ok(K, cin_g, cout_g, T) and _H2_DIR[bool(flip)] and str(K) in _H2_K and
+    if (T is not None and (T >= 128 or plain) and h2_ok(K, cin_g, cout_g, T) and
             _h2_fills(G, cout_g, T, 256, 128 if cout_g % 128 == 0 else 64)):
         wino = 3
     return Cog, Cig, K, wino
@@ -728,7 +718,7 @@ def conv(xv, wp, Cog, K, out=None, bias=None, in_scale=None, res=None, gate=None
         st = _amax_state(xv.t.device)
         ws = getattr(wp, "nef_site", None)
         site = None
-        if AMAX_SCOPE is not None and ws is not None and _H2_AMAX != "anon":
+        if AMAX_SCOPE is not None and ws is not None:
             # + the occurrence within the pass: the k-th launch through one weight keeps its own history, so a step repeated on
             # the same data finds the scales it left (bit-identical results)
             occ = st["occ"]
@@ -765,11 +755,6 @@ def conv(xv, wp, Cog, K, out=None, bias=None, in_scale=None, res=None, gate=None
 
 
 # ------------------------------------------------------------------ polyphase form of conv1d(upsample2(x)), K = 3
-POLY = _env.get("NEF_POLY", "1") == "1"
-_POLY_FWD = _env.get("NEF_POLY_FWD", "1") == "1"
-_POLY_W = _env.get("NEF_POLY_W", "1") == "1"
-
-
 def poly_weights(w, tile_Cr=0):
     """w [R, Cig, 3] -> [2R, Cig, 3]: row 2r + p = the phase-p weights of row r (csrc/elementwise.hip poly_weights_kernel): output
     2m + p of conv1d(upsample2(x), w) is the K = 3 conv of the half-resolution x with them.  `tile_Cr` (channels per group): rows in
@@ -784,8 +769,8 @@ def poly_fwd_ok(G, Cog, Cig, T):
     """Can y = conv1d(upsample2(x [.., G*Cig, T/2]), w [G*Cog, Cig, 3]) run in polyphase form?  (a split-fp16 conv with Cig reduction
     channels, 2 Cog output rows in 128-row tiles, T / 2 columns)"""
     Th = T // 2
-    return (POLY and _POLY_FWD and H2 and T % 2 == 0 and Th >= 128 and Cog % 64 == 0 and Cig % 16 == 0 and h2_ok(3, Cig, 2 * Cog, Th, 1) and
-            _H2_DIR[False] and "3" in _H2_K and _h2_fills(G, 2 * Cog, Th, 256, 128))
+    return (H2 and T % 2 == 0 and Th >= 128 and Cog % 64 == 0 and Cig % 16 == 0 and h2_ok(3, Cig, 2 * Cog, Th, 1) and
+            _h2_fills(G, 2 * Cog, Th, 256, 128))
 
 
 def conv_poly_fwd(xv, w, Cog, bias=None, pro=None, stats=False, site=None, save_edge=False):
@@ -821,8 +806,8 @@ def poly_bwd_ok(G, Cog, Cig, T):
     """Can the backward-data pass of conv1d(upsample2(x) [.., G*Cig, T], w [G*Cog, Cig, 3]) run in polyphase form?  (the launch is a
     split-fp16 conv with 2 Cog reduction channels, Cig outputs, T / 2 columns)"""
     Th = T // 2
-    return (POLY and H2 and T % 2 == 0 and Th >= 128 and Cig % 64 == 0 and (2 * Cog) % 16 == 0 and h2_ok(3, 2 * Cog, Cig, Th) and
-            _H2_DIR[True] and "3" in _H2_K and _h2_fills(G, Cig, Th, 256, 128 if Cig % 128 == 0 else 64))
+    return (H2 and T % 2 == 0 and Th >= 128 and Cig % 64 == 0 and (2 * Cog) % 16 == 0 and h2_ok(3, 2 * Cog, Cig, Th) and
+            _h2_fills(G, Cig, Th, 256, 128 if Cig % 128 == 0 else 64))
 
 
 def conv_bwd_data_poly(gyv, w, Cig, bnb=None, site=None, phase_major=False):
@@ -859,7 +844,7 @@ def poly_w_ok(B, G, Cog, Cig, T):
     """Weight gradient of conv1d(upsample2(x), w) in polyphase form: a split-fp16 weight gradient over the half-resolution x and
     the phase-major gradient (2 Cog rows), producer / consumer form (2 Cog % 128 == 0), then nef_poly_wgrad_fold."""
     Th = T // 2
-    return (POLY and _POLY_W and T % 4 == 0 and Cog % 64 == 0 and h2w_ok(3, Cig, 2 * Cog, Th, 1) and
+    return (T % 4 == 0 and Cog % 64 == 0 and h2w_ok(3, Cig, 2 * Cog, Th, 1) and
             (BATCH_HINT is None or B * ((Th + 63) // 64) >= 8 * _H2_MIN_WGS))
 
 
@@ -882,7 +867,7 @@ def conv_bwd_weight_poly(xv, gy_pm, Cog, pro, xedge, site=None):
 
 
 def h2w_ok(K, Cig, Cog, T, pro_mode=0, in_scale=False):
-    return (H2 and _H2_W and str(K) in _H2_WK and T % 2 == 0 and T >= max(64, _H2_MIN_T) and Cig % 64 == 0 and Cog % 64 == 0 and
+    return (H2 and T % 2 == 0 and T >= 64 and Cig % 64 == 0 and Cog % 64 == 0 and
             (K == 3 or not pro_mode) and not (pro_mode and in_scale))
 
 
@@ -923,7 +908,7 @@ def conv_bwd_weight(xv, gyv, K, in_scale=None, pro=None, wino=None, site=None, h
         else:
             st = _amax_state(xv.t.device)
             key = None
-            if AMAX_SCOPE is not None and site is not None and _H2_AMAX != "anon":
+            if AMAX_SCOPE is not None and site is not None:
                 occ = st["occ"]
                 base = (AMAX_SCOPE, (site, "w"), "conv_bwd_weight", B, T)
                 k = occ[base] = occ.get(base, 0) + 1
@@ -1373,18 +1358,6 @@ def upsample2_fwd(x):
     N, Ct, T = x.shape
     y = torch.empty(N, Ct, 2 * T, device=x.device, dtype=torch.float32)
     _lib.check(L.nef_upsample2_fwd(_p(x), _p(y), N * Ct, T, _stream()), "nef_upsample2_fwd")
-    return y
-
-
-def upsample2_aff_fwd(x, a, b, Bp):
-    """upsample2(relu(x*a[p,c] + b[p,c])), p = sample // Bp."""
-    L = _lib.load()
-    _chk(x)
-    N, Ct, T = x.shape
-    y = torch.empty(N, Ct, 2 * T, device=x.device, dtype=torch.float32)
-    ev = _hbm("upsample2_aff_fwd", x, y)
-    _lib.check(L.nef_upsample2_aff_fwd(_p(x), _p(a), _p(b), _p(y), N, Ct, T, Bp, _stream()), "nef_upsample2_aff_fwd")
-    _done(ev)
     return y
 
 

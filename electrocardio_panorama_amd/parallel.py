@@ -9,7 +9,6 @@ from . import _env
 import torch.distributed as dist
 
 
-_HOOK_VARS = ("NEF_SHARE_GPU", "NEF_DIST_BACKEND", "NEF_DIST_FORCE")
 _warned = []
 
 
@@ -17,6 +16,7 @@ def _hook(name):
     """Test hooks (two ranks on one GPU, gradients over gloo, a one-rank RCCL group) are honoured ONLY under
     NEF_TEST_HOOKS=1, so that a stray variable cannot put a production run on gloo; without the guard they are ignored
     with one warning."""
+    assert name in _env.TEST_HOOKS, name
     v = os.environ.get(name)
     if v is None:
         return None

@@ -34,19 +34,11 @@ extern "C" {
 typedef void* nef_stream_t;
 
 /* ABI version of this header; bumped on any signature change. */
-int nef_abi_version(void);   /* 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + nef_set_option / nef_get_option); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + nef_conv_bwd_weight_h2); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, nef_conv_bwd_weight_wino4 covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
+int nef_abi_version(void);   /* 19 (the kernel-form option entry points of 16 and nef_upsample2_aff_fwd are gone; + nef_debug_spin_us); 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + kernel-form option entry points); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + nef_conv_bwd_weight_h2); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, nef_conv_bwd_weight_wino4 covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
 
-/* Kernel-form options of the process (tuning / A-B hooks; every value computes the same results).  Not part of any reference
- * interface: the reference's nn.Conv1d has one form (codes/network/model_nefnet.py:18-21).  Returns the previous value, or
- * NEF_E_SHAPE for an unknown key.  Read by the launches that follow; not meant to be flipped while a hipGraph capture is open. */
-#define NEF_OPT_H2_FORM 1       /* split-fp16 forward / backward-data convolutions (conv args wino = 3): 0 (default) = every wave
-                                   stages, multiplies and stores in turn (csrc/conv_h2.hip); 1 = producer and consumer waves in a
-                                   persistent twelve-wave workgroup (tools/experiments/conv_h2p.hip; only in libraries built with
-                                   `csrc/build.py --with-experiments`, ignored otherwise) wherever its shape rules hold -- bit-identical
-                                   results, measured slower in round 5, kept as the A/B reference */
-#define NEF_OPT_H2P_WGS 2       /* persistent workgroups per CU of that form (default 1: twelve waves fill a CU at 168 registers) */
-int nef_set_option(int key, int value);
-int nef_get_option(int key);
+/* Diagnostics: `wgs` workgroups busy for `us` microseconds on `stream` (a stand-in for a collective's time on the chip:
+ * parallel.DryCollective, bench.py --dry-collective).  0 <= us <= 50000, 1 <= wgs <= 64. */
+int nef_debug_spin_us(float us, int wgs, nef_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Stem: Conv1d(1->128 per lead, k15, s2, p7, no bias) + ReLU + MaxPool1d(3,2,1), fused.
@@ -187,9 +179,7 @@ typedef struct nef_conv_args {
     int32_t* x_clamped;    /* wino == 3: NULL, or a device counter the launch adds 1 to (per wave) when an element of its operand is
                               still out of fp16's range AFTER the range rescue -- i.e. is not finite.  (A tile whose finite data does
                               not fit under the launch's scale -- the operand grew more than ~64x since x_amax was measured -- is
-                              redone inside the launch with the scale its own data asks for; round 4 clamped it and counted it.)
-                              The producer / consumer form (nef_set_option(NEF_OPT_H2_FORM, 1)) has no rescue: it clamps at
-                              65000 / scale and counts */
+                              redone inside the launch with the scale its own data asks for; round 4 clamped it and counted it.) */
     const float* res_scale;   /* wino == 3, res != NULL: NULL, or a per-(sample, channel) factor on the residual,
                               y = conv + bias + res * res_scale[b*rs_bs + g*rs_gs + c] -- the residual of a block whose input is a
                               channel-scaled tensor (w_conv behind the theta scaling, codes/network/model_nefnet.py:122-124) read
@@ -382,9 +372,6 @@ int nef_pass_combine_bwd(const float* gc1, float* gP2, int B, int C, int L, nef_
  * Upsample(scale 2, linear, align_corners=False): x [N][Tin] rows -> y [N][2Tin]. */
 int nef_upsample2_fwd(const float* x, float* y, int64_t N, int Tin, nef_stream_t stream);
 int nef_upsample2_bwd(const float* gy, float* gx, int64_t N, int Tin, nef_stream_t stream);
-/* y [N][C][2Tin] = upsample2(max(0, x*a[p][c] + b[p][c])), p = n / Bp: BN affine + ReLU folded into the resample. */
-int nef_upsample2_aff_fwd(const float* x, const float* a, const float* b, float* y, int N, int C, int Tin, int Bp,
-                          nef_stream_t stream);
 
 /* BatchNorm1d, training mode, P independent passes stacked along batch (x [P*Bp][C][L]).
  * nef_bn_train_stats: per (pass, channel) batch mean / biased var -> mean, invstd [P][C], the affine

@@ -14,7 +14,7 @@ from util import free_port
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_header_symbols_exported():
+def test_header_symbols_exported_abi_19():
     """The shared library loads and exports every function include/nefnet_hip.h declares (no compute calls)."""
     from electrocardio_panorama_amd import _lib
     from electrocardio_panorama_amd.csrc import build
@@ -25,7 +25,7 @@ def test_header_symbols_exported():
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name), name
-    assert _lib.load().nef_abi_version() == 18
+    assert _lib.load().nef_abi_version() == 19
     assert ctypes.sizeof(_lib.ConvArgs) == 384 == _lib.load().nef_conv_args_bytes()
 
 
@@ -381,19 +381,12 @@ def test_dropin_shim_resolves_reference_import_lines():
     assert r.returncode == 0 and "DROPIN_OK" in r.stdout, r.stderr[-2000:]
 
 
-def test_env_switch_groups(monkeypatch, capsys):
-    """Product switches are always honoured; diagnostics switches only under NEF_DIAG=1 (ignored with one warning otherwise);
-    anything else is a programming error.  The C side gates its own diagnostics reads the same way (nef_common.h: nef_diag_env)."""
+def test_env_switches_are_product_or_test_hooks(monkeypatch):
+    """Product switches are always honoured; anything else is a programming error.  Every switch the sources read is registered
+    as a product switch or a test hook; the HIP library reads none."""
     from electrocardio_panorama_amd import _env
-    monkeypatch.delenv("NEF_DIAG", raising=False)
     monkeypatch.setenv("NEF_H2", "0")
     assert _env.get("NEF_H2", "1") == "0"
-    monkeypatch.setenv("NEF_FUSE_STATS", "0")
-    _env._warned.discard("NEF_FUSE_STATS")
-    assert _env.get("NEF_FUSE_STATS", "1") == "1" and _env.get("NEF_FUSE_STATS", "1") == "1"
-    assert capsys.readouterr().err.count("NEF_FUSE_STATS=0 ignored") == 1
-    monkeypatch.setenv("NEF_DIAG", "1")
-    assert _env.get("NEF_FUSE_STATS", "1") == "0"
     monkeypatch.setenv("NEF_NOT_A_SWITCH", "1")
     with pytest.raises(KeyError):
         _env.get("NEF_NOT_A_SWITCH")
@@ -405,9 +398,11 @@ def test_env_switch_groups(monkeypatch, capsys):
         for f in files:
             if f.endswith((".py", ".hip", ".h")):
                 txt = open(os.path.join(dirpath, f), errors="ignore").read()
-                seen |= set(re.findall(r'(?:_env\.get|nef_diag_env|getenv)\(["\'](NEF_[A-Z0-9_]+)', txt))
-    hooks = {"NEF_SHARE_GPU", "NEF_DIST_BACKEND", "NEF_DIST_FORCE"}
-    assert seen - set(_env.PRODUCT) - _env.DIAGNOSTICS - hooks == set(), seen - set(_env.PRODUCT) - _env.DIAGNOSTICS - hooks
+                seen |= set(re.findall(r'(?:_env\.get|_hook|getenv)\(["\'](NEF_[A-Z0-9_]+)', txt))
+                if f.endswith((".hip", ".h")):
+                    assert "getenv" not in txt, f
+    assert "NEF_H2" in seen and "NEF_SHARE_GPU" in seen
+    assert seen - set(_env.PRODUCT) - _env.TEST_HOOKS == set(), seen - set(_env.PRODUCT) - _env.TEST_HOOKS
 
 
 def test_polyphase_form_of_conv_behind_upsampling_is_exact_algebra():

@@ -1,6 +1,6 @@
 """Decoder forward + backward alone at the configs[1] shapes (three Standin passes of B=256, T=1250 latents), every launch
 bracketed with HIP events on one stream: per-tag mean ms over ITERS rounds after WARM rounds.  The launches carry their real
-prologues / epilogues (BatchNorm slot sums, bnb sums, upsampling), unlike tools/bench_conv.py.  A/B: NEF_LIB=<variant .so>."""
+prologues / epilogues (BatchNorm slot sums, bnb sums, upsampling), unlike tools/bench_conv.py."""
 import json
 import os
 import sys

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Arbitrary PMC group on the conv micro-benchmark.  usage: tools/pmc_any.sh "<shape filter>" <out dir under gpurun_out> COUNTER...
-# env passes through (NEF_LIB, F4, ONLY_WHAT).  One --pmc group per call: counters of one pass must fit the hardware.
+# env passes through (F4, ONLY_WHAT).  One --pmc group per call: counters of one pass must fit the hardware.
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 SH="$1"; O=gpurun_out/$2; shift 2

@@ -1,5 +1,5 @@
 """Per-step gradient check on the tests' hashed-weight model: the same model stepped with the split-fp16 convs (and whatever
-NEF_* switches the environment sets, e.g. NEF_DIAG=1 NEF_POLY=0) against a clone that computes the same step on the fp32 kernels.
+product switches the environment sets, e.g. NEF_WINOGRAD=2) against a clone that computes the same step on the fp32 kernels.
 Shows how far a few nearly cancelling gradient sums move when activations differ in the last bit (a ReLU decision that flips):
 usage: [SHAPES="[(2,512)]*4"] python tools/step_grad_check.py"""
 import sys, copy, random, numpy as np, torch, os
