@@ -1263,6 +1263,68 @@ __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, f
 }
 
 // ------------------------------------------------------------------------------------------------
+// torch.optim.Adam (amsgrad=False, maximize=False, L2 weight_decay)    (codes/solver/optim_scheduler.py:8)
+// ------------------------------------------------------------------------------------------------
+// One element in torch's operation order (_single_tensor_adam): grad.add(param, alpha=wd); exp_avg.lerp_(grad, 1 - b1);
+// exp_avg_sq.mul_(b2).addcmul_(grad, grad, value=1 - b2); denom = exp_avg_sq.sqrt() / sqrt(bc2) + eps (a division by a scalar is a
+// multiplication by its reciprocal on the device); param.addcdiv_(exp_avg, denom, value=-lr / bc1).  The build contracts nothing.
+__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float gscale, float wd, float w1, float b2,
+                                          float w2, float inv_bc2s, float eps, float step_size) {
+    float gv = g * gscale;
+    if (wd != 0.f) gv = gv + wd * p;
+    m = m + w1 * (gv - m);                       // lerp with a weight below 0.5
+    v = v * b2 + w2 * gv * gv;
+    const float den = sqrtf(v) * inv_bc2s + eps;
+    p = p + -step_size * (m / den);
+}
+
+// `step`: the number of completed updates (torch's state["step"]); every block reads it before anything changes it -- the increment is
+// the one-lane launch behind this one (adam_step_kernel), so no block can see t + 1
+template <bool VEC>
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, int64_t n, float lr, double b1, double b2, float eps, float wd,
+                                                   float gscale, const float* __restrict__ step, const float* __restrict__ skip,
+                                                   int32_t* skipped, const float* __restrict__ lr_dev) {
+    if (lr_dev) lr = lr_dev[0];      // a captured launch freezes its scalar arguments: the learning rate of a replayed step lives in memory
+    if (skip && skip[0] > 0.f) {      // a tainted step (nef_h2_taint): parameters, moments and the step word stay as they are
+        if (skipped && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(skipped, 1);
+        return;
+    }
+    // the bias corrections in fp64, as torch computes them on the host (1 - beta ** step with Python floats)
+    const double t = (double)step[0] + 1.0;
+    const double bc1 = 1.0 - pow(b1, t), bc2 = 1.0 - pow(b2, t);
+    const float step_size = (float)((double)lr / bc1);
+    const float inv_bc2s = 1.f / (float)sqrt(bc2);
+    const float w1 = (float)(1.0 - b1), w2 = (float)(1.0 - b2), b2f = (float)b2;      // torch: 1 - beta of Python floats
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t n4 = VEC ? (n >> 2) : 0;
+    if (VEC) {      // 16-byte body: seven fp32 streams, one dwordx4 load / store per stream and lane
+        for (int64_t i = gid; i < n4; i += stride) {
+            nef_f32x4 pv = ((const nef_f32x4*)p)[i], mv = ((const nef_f32x4*)m)[i], vv = ((const nef_f32x4*)v)[i];
+            const nef_f32x4 gv = ((const nef_f32x4*)g)[i];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float pe = pv[e], me = mv[e], ve = vv[e];
+                adam_elem(pe, gv[e], me, ve, gscale, wd, w1, b2f, w2, inv_bc2s, eps, step_size);
+                pv[e] = pe, mv[e] = me, vv[e] = ve;
+            }
+            ((nef_f32x4*)p)[i] = pv;
+            ((nef_f32x4*)m)[i] = mv;
+            ((nef_f32x4*)v)[i] = vv;
+        }
+    }
+    for (int64_t i = 4 * n4 + gid; i < n; i += stride) {       // the n % 4 tail (VEC), or everything
+        float pe = p[i], me = m[i], ve = v[i];
+        adam_elem(pe, g[i], me, ve, gscale, wd, w1, b2f, w2, inv_bc2s, eps, step_size);
+        p[i] = pe, m[i] = me, v[i] = ve;
+    }
+}
+
+__global__ void adam_step_kernel(float* step, const float* __restrict__ skip) {
+    if (!(skip && skip[0] > 0.f)) step[0] += 1.f;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Round 6: the last torch elementwise kernels of the train step, as one launch each.
 // amax_roll: ops.amax_roll's follow-up rule on the split-fp16 site table (was ~10 ATen launches: compares, ors, where, fill).
 __global__ __launch_bounds__(256) void amax_roll_kernel(float* __restrict__ cur, float* __restrict__ nxt, int n, float up, float down,
@@ -2284,6 +2346,24 @@ int nef_sgd_momentum(float* p, const float* g, float* buf, int64_t n, float lr, 
     NEF_REQUIRE(n > 0, NEF_E_SHAPE);
     hipLaunchKernelGGL(sgd_kernel, dim3(nef_stream_grid(n, 256)), dim3(256), 0, NEF_ST, p, g, buf, n, lr, mu, gscale,
                        first_step, skip_if_positive, skipped, lr_dev);
+    return nef_launch_status();
+}
+
+int nef_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2, float eps,
+             float weight_decay, float gscale, float* step, const float* skip_if_positive, int32_t* skipped, const float* lr_dev,
+             nef_stream_t stream) {
+    NEF_ENTER();
+    NEF_REQUIRE(p && g && m && v && step, NEF_E_NULL);
+    NEF_REQUIRE(n > 0, NEF_E_SHAPE);
+    const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
+    if (vec && n >= 4)
+        hipLaunchKernelGGL(adam_kernel<true>, dim3(nef_stream_grid(n >> 2, 256)), dim3(256), 0, NEF_ST, p, g, m, v, n, lr, beta1,
+                           beta2, eps, weight_decay, gscale, step, skip_if_positive, skipped, lr_dev);
+    else
+        hipLaunchKernelGGL(adam_kernel<false>, dim3(nef_stream_grid(n, 256)), dim3(256), 0, NEF_ST, p, g, m, v, n, lr, beta1, beta2,
+                           eps, weight_decay, gscale, step, skip_if_positive, skipped, lr_dev);
+    // stream order: every block of the update has read the step word before this launch advances it
+    hipLaunchKernelGGL(adam_step_kernel, dim3(1), dim3(1), 0, NEF_ST, step, skip_if_positive);
     return nef_launch_status();
 }
 

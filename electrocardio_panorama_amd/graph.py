@@ -2,15 +2,16 @@
 
 At the reference's own training shape (batch 32, 512-sample beats, `train_net.py:27`) a step is ~250 short launches
 and the host cannot issue them as fast as the GPU retires them.  `GraphedTrainStep` captures forward + losswrapper +
-backward + momentum-SGD once per input shape (torch.cuda.CUDAGraph on the stream the C ABI launches into) and replays
+backward + the optimiser update once per input shape (torch.cuda.CUDAGraph on the stream the C ABI launches into) and replays
 it: inputs are copied into static buffers, and the only per-step host decisions -- the two Standin lead choices
 (reference model_nefnet.py:154,156, drawn from Python's `random` in the reference's order) and the dropout seed --
 travel through device words that the kernels read at run time.  Same arithmetic as the eager path.
 
 One graph (with its own static input buffers) is kept per input shape, so a final partial batch or alternating shapes
 replay instead of re-capturing; the flat parameter / gradient / momentum buffers are shared by all of them and survive
-every re-capture (shape change); the learning rate lives in a device word the captured SGD launch reads, so a scheduler step costs
-one small copy and no re-capture.  `state_dict()` / `load_state_dict()` carry the momentum buffer
+every re-capture (shape change); the learning rate lives in a device word the captured update launch reads, so a scheduler step costs
+one small copy and no re-capture.  With a fused optimiser (solver.optim_scheduler: FusedSGD, FusedAdam) the graph steps that
+optimiser's own flat buffers through its `_device_update`.  `state_dict()` / `load_state_dict()` carry the momentum buffer
 for checkpoints.
 
 Data parallel (world > 1): the step is captured as TWO graphs cut at the early-bucket point of the backward pass; the all-reduce
@@ -28,17 +29,20 @@ from . import engine, ops
 
 class GraphedTrainStep:
     def __init__(self, model, cfg, lr=None, momentum=0.9, optimizer=None):
-        """`optimizer`: a solver.optim_scheduler.FusedSGD over model.parameters() -- the graph then steps THAT optimiser's flat
-        parameter / momentum buffers (so checkpoints, a learning-rate scheduler and eager steps in between see one state) and
-        takes lr / momentum from its parameter group; without it the stepper owns its buffers (lr / momentum arguments)."""
+        """`optimizer`: a fused optimiser of solver.optim_scheduler (FusedSGD, FusedAdam) over model.parameters() -- the graph then
+        steps THAT optimiser's flat parameter / state buffers through its `_device_update` (so checkpoints, a learning-rate scheduler
+        and eager steps in between see one state) and takes its scalars from its parameter group; without it the stepper owns its
+        buffers and runs momentum SGD (lr / momentum arguments)."""
         if cfg.DATA.noise:
             raise NotImplementedError("cfg.DATA.noise adds a host-side tensor op between model and loss")
         self.model, self.cfg = model, cfg
         self.optimizer = optimizer
         if optimizer is not None:
-            if len(optimizer.param_groups) != 1 or not hasattr(optimizer, "_flat"):
-                raise NotImplementedError("the graphed step drives FusedSGD with one parameter group")
-            lr, momentum = optimizer.param_groups[0]["lr"], optimizer.param_groups[0]["momentum"]
+            if len(optimizer.param_groups) != 1 or not hasattr(optimizer, "_device_update"):
+                raise NotImplementedError("the graphed step drives a fused optimiser (FusedSGD, FusedAdam) with one parameter group")
+            g0 = optimizer.param_groups[0]
+            lr, momentum = g0["lr"], g0.get("momentum", momentum)
+            self._captured = optimizer._captured_scalars(g0)     # frozen into the captured update launch: a change re-captures
         self.lr = float(cfg.SOLVER.lr if lr is None else lr)
         self.mu = float(momentum)
         self.factors = tuple(float(f) for f in cfg.SOLVER.loss_factor)
@@ -47,6 +51,7 @@ class GraphedTrainStep:
         self.use_mask = (1 if 1 in u else 0) | (2 if 2 in u else 0) | (4 if 3 in u else 0)
         self.slots = {}          # input shape -> static input buffers + captured graph
         self.flat_p = self.flat_g = self.flat_buf = None
+        self.opt_flat = None     # the optimiser's flat buffers (optimizer mode)
         self.live = None
         self.choice_dev = None
         self.lr_dev = None
@@ -72,17 +77,12 @@ class GraphedTrainStep:
         shape, so later captures reuse the buffers -- and with them the momentum."""
         named = dict(self.model.named_parameters())
         if self.optimizer is not None:
-            # the optimiser's own flat buffers (FusedSGD._build: parameters become views of fl["p"], the momentum views of
-            # fl["buf"] live in optimizer.state): nothing to copy, nothing to keep in sync
-            opt, params = self.optimizer, [named[k] for k in live]
-            fl = opt._flat.get(0)
-            if fl is None or fl["ids"] != [id(p) for p in params] or any(
-                    p.data.data_ptr() < fl["p"].data_ptr() or
-                    p.data.data_ptr() >= fl["p"].data_ptr() + fl["p"].numel() * 4 for p in params):
-                opt._build(0, params)
-                fl = opt._flat[0]
+            # the optimiser's own flat buffers (its _build: parameters become views of fl["p"], the views of its state buffers -- FusedSGD's
+            # momentum fl["buf"], FusedAdam's moments fl["m"] / fl["v"] -- live in optimizer.state): nothing to copy, nothing to keep in sync
+            fl = self.optimizer._current(0, [named[k] for k in live])
             self.live = live
-            self.flat_p, self.flat_g, self.flat_buf, self.flat_g_all = fl["p"], fl["g"], fl["buf"], fl["g_all"]
+            self.opt_flat = fl
+            self.flat_p, self.flat_g, self.flat_buf, self.flat_g_all = fl["p"], fl["g"], fl.get("buf"), fl["g_all"]
             return
         if self.live == live and self.flat_p is not None and all(
                 named[k].data.data_ptr() >= self.flat_p.data_ptr() and
@@ -122,9 +122,13 @@ class GraphedTrainStep:
             g3 = ops.loss_bwd(o, p_, l_, self.target, None, self.factors, self.reg_l2, self.use_mask)
             return engine.backward(P, sv, g3)
 
-    def _sgd(self):
+    def _update(self):
         # the learning rate travels through a device word (a captured launch freezes its scalars): a scheduler step updates the word,
         # nothing is re-captured
+        if self.optimizer is not None:
+            self.optimizer._device_update(self.opt_flat, self.optimizer.param_groups[0], 1.0 / self.world, skip=self.flat_g_all[:1],
+                                          lr_dev=self.lr_dev)
+            return
         ops.sgd_momentum(self.flat_p, self.flat_g, self.flat_buf, self.lr, self.mu, 1.0 / self.world, False,
                          skip=self.flat_g_all[:1], lr_dev=self.lr_dev)
 
@@ -133,7 +137,7 @@ class GraphedTrainStep:
         ops.flatten_into([grads[k] for k in self.live], self.flat_g)
         ops.h2_taint(self.flat_g_all[:1])      # this step's clamped split-fp16 launches: the update is skipped (on every rank)
         if not self.dp:
-            self._sgd()
+            self._update()
 
     def _capture_split(self):
         """Data parallel: the step as TWO graphs, cut where engine.backward would start the early gradient bucket (everything
@@ -179,6 +183,12 @@ class GraphedTrainStep:
         self._comm = getattr(self, "_comm", None) or torch.cuda.Stream()
         return (gA, gB, info["split"])
 
+    def _state_tensors(self):
+        """Everything the update writes: the parameters and the optimiser state (momentum; Adam's moments and step word)."""
+        if self.opt_flat is None:
+            return [self.flat_p, self.flat_buf]
+        return [self.flat_p] + [v for k, v in self.opt_flat.items() if k not in ("ids", "params", "p", "g", "g_all")]
+
     def _use(self, slot):
         self.data, self.in_theta, self.q_theta, self.rois, self.target = (slot[k] for k in
                                                                           ("data", "in_theta", "q_theta", "rois", "target"))
@@ -222,7 +232,8 @@ class GraphedTrainStep:
         torch.cuda.synchronize(dev)
         graph = torch.cuda.CUDAGraph()
         saved = {k: v.clone() for k, v in self.model.named_buffers()}
-        p0, b0 = self.flat_p.clone(), self.flat_buf.clone()
+        state = self._state_tensors()
+        saved_state = [t.clone() for t in state]
         if self.dp and self.split_capture:
             graph = self._capture_split()
         else:
@@ -231,8 +242,8 @@ class GraphedTrainStep:
         # capture does not execute, but keep state exactly as before the capture regardless
         for k, v in self.model.named_buffers():
             v.copy_(saved[k])
-        self.flat_p.copy_(p0)
-        self.flat_buf.copy_(b0)
+        for t, t0 in zip(state, saved_state):
+            t.copy_(t0)
         slot["graph"] = graph
         # The graph bakes in the pointers of every scratch buffer its launches used (ops.workspace, incl. the side
         # stream's, which the eager probe allocated from the general pool).  ops.workspace() REPLACES a buffer when a later
@@ -303,8 +314,10 @@ class GraphedTrainStep:
         self.model._check_inputs(data, rois)       # what Model_nefnet.forward rejects (float rois, L % 4, CPU tensors) is rejected here too
         if self.optimizer is not None:
             g = self.optimizer.param_groups[0]
-            if float(g["momentum"]) != self.mu:                # (momentum is a captured scalar: re-capture)
-                self.mu = float(g["momentum"])
+            cap = self.optimizer._captured_scalars(g)
+            if cap != self._captured:                          # (momentum; Adam's betas / eps / weight_decay are captured scalars: re-capture)
+                self._captured = cap
+                self.mu = float(g.get("momentum", self.mu))
                 self.slots.clear()
             self.set_lr(g["lr"])                               # a scheduler stepped: the device word follows, nothing is re-captured
             fl = self.optimizer._flat.get(0)
@@ -352,5 +365,5 @@ class GraphedTrainStep:
         if ev is not None:
             ev[1].record()
             parallel.TIMING.append(ev)
-        self._sgd()
+        self._update()
         return self.losses

@@ -1636,6 +1636,21 @@ def sgd_momentum(p, g, buf, lr, mu, gscale, first_step, skip=None, lr_dev=None):
     _done(ev)
 
 
+def adam(p, g, m, v, step, lr, beta1, beta2, eps, weight_decay, gscale, skip=None, lr_dev=None):
+    """torch.optim.Adam's update (amsgrad=False, L2 weight_decay) over flat fp32 buffers, in place on p / m / v.  `step`: a one-element
+    fp32 device tensor holding the completed updates (torch's state["step"]); the launch reads it and advances it on the device, so a
+    captured update stays right on every replay.  `skip` / `lr_dev`: as for sgd_momentum (a skipped step leaves `step` as it is)."""
+    L = _lib.load()
+    _chk(p), _chk(m), _chk(v), _chk(step)
+    assert g.is_cuda and g.dtype == torch.float32 and g.is_contiguous()
+    assert g.numel() == p.numel() == m.numel() == v.numel() and step.numel() == 1
+    ev = _hbm("adam", p, p, g, m, m, v, v)
+    sk = _p(_amax_state(p.device)["skipped"]) if skip is not None else None
+    _lib.check(L.nef_adam(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, weight_decay, gscale, _p(step), _p(skip), sk,
+                          _p(lr_dev), _stream()), "nef_adam")
+    _done(ev)
+
+
 # ------------------------------------------------------------------ half-precision panorama decoder (pano_h.hip)
 def pano_h_from_f32(x):
     """fp32 [B,C,T] -> fp16 [B,T,C] (time-major)."""

@@ -2,7 +2,9 @@
 
 'sgd' returns FusedSGD: torch.optim.SGD(lr, momentum=0.9) semantics, but one HIP launch over a flat
 parameter buffer, and -- when torch.distributed is initialised -- one RCCL all-reduce of the flat
-gradient buffer per step (data-parallel training, one process per GPU)."""
+gradient buffer per step (data-parallel training, one process per GPU).
+'adam' returns FusedAdam: torch.optim.Adam(lr) semantics on the same flat-buffer machinery (one nef_adam launch).
+DataParallelAdam (torch Adam behind a separate all-reduce) is kept as the unfused comparison."""
 import torch
 import torch.distributed as dist
 from torch.optim import Adam
@@ -17,20 +19,26 @@ from ..parallel import reduce_flat_grads
 GRAD_HDR = 4
 
 
-class FusedSGD(torch.optim.Optimizer):
-    """A tainted step (a split-fp16 launch met non-finite data, on any rank) leaves parameters and momentum untouched; the
-    BatchNorm running statistics its forward pass already updated are NOT rolled back (DESIGN.md 3.0 "Range")."""
+class _FusedFlat(torch.optim.Optimizer):
+    """Flat-buffer machinery of the fused optimisers: the live parameters of a group become views of one flat fp32 buffer, the
+    per-element state (`_SLOTS`: flat key -> torch state key) views of flat buffers of the same layout, and a step is ONE
+    device-update launch (`_device_update`) over them -- behind, in data-parallel runs, the flat gradient all-reduce that consumes
+    engine.backward's early bucket (`_reduce`).  The same `_device_update` is what GraphedTrainStep captures.
 
-    def __init__(self, params, lr, momentum=0.9):
-        super().__init__(params, dict(lr=lr, momentum=momentum))
-        self._flat = {}      # group index -> dict(params, p, g, buf)
+    A tainted step (a split-fp16 launch met non-finite data, on any rank) leaves parameters and optimiser state untouched; the
+    BatchNorm running statistics its forward pass already updated are NOT rolled back (DESIGN.md 3.0 "Range")."""
+    _SLOTS = ()
+
+    def __init__(self, params, defaults):
+        super().__init__(params, defaults)
+        self._flat = {}      # group index -> dict(ids, params, p, g_all, g, one flat buffer per _SLOTS key)
         parallel.enable_early_reduce()      # this optimiser consumes engine.backward's early gradient bucket (see _reduce)
 
     def _build(self, gi, live):
         n = sum(p.numel() for p in live)
         dev = live[0].device
         flat_p = torch.empty(n, device=dev, dtype=torch.float32)
-        flat_b = torch.zeros(n, device=dev, dtype=torch.float32)
+        slots = {fk: torch.zeros(n, device=dev, dtype=torch.float32) for fk, _ in self._SLOTS}
         off = 0
         for p in live:
             k = p.numel()
@@ -39,19 +47,38 @@ class FusedSGD(torch.optim.Optimizer):
             p.data = flat_p[off:off + k].view_as(p.data)          # parameters become views of the flat buffer
             ops.amax_move(old_ptr, p.data.data_ptr())
             st = self.state[p]
-            if "momentum_buffer" in st and st["momentum_buffer"] is not None:
-                flat_b[off:off + k].copy_(st["momentum_buffer"].reshape(-1))
-            st["momentum_buffer"] = flat_b[off:off + k].view_as(p.data)
+            for fk, sk in self._SLOTS:
+                if sk in st and st[sk] is not None:
+                    slots[fk][off:off + k].copy_(st[sk].reshape(-1))
+                st[sk] = slots[fk][off:off + k].view_as(p.data)
             off += k
         # gradients: [header (taint word, 3 zero words) | n gradients] -- the word in front (ops.h2_taint: clamps of this step's
         # split-fp16 launches) is summed by the same all-reduce as the gradients, so a clamp on any rank makes every rank skip the update
         g_all = torch.zeros(n + GRAD_HDR, device=dev, dtype=torch.float32)
-        self._flat[gi] = dict(ids=[id(p) for p in live], params=live, p=flat_p, buf=flat_b, g_all=g_all, g=g_all[GRAD_HDR:])
+        self._flat[gi] = dict(ids=[id(p) for p in live], params=live, p=flat_p, g_all=g_all, g=g_all[GRAD_HDR:], **slots)
+
+    def _current(self, gi, live):
+        """The flat buffers of group `gi` for these live parameters, (re)built when the set changed or a parameter was re-pointed."""
+        fl = self._flat.get(gi)
+        if fl is None or fl["ids"] != [id(p) for p in live] or any(
+                p.data.data_ptr() < fl["p"].data_ptr() or
+                p.data.data_ptr() >= fl["p"].data_ptr() + fl["p"].numel() * 4 for p in live):
+            self._build(gi, live)
+            fl = self._flat[gi]
+        return fl
 
     def load_state_dict(self, state_dict):
-        """The loaded momentum buffers replace the flat one: drop the flat views so the next step() re-imports them."""
+        """The loaded state replaces the flat buffers: drop the flat views so the next step() re-imports them."""
         super().load_state_dict(state_dict)
         self._flat = {}
+
+    def _captured_scalars(self, group):
+        """The scalar arguments of `_device_update` that a captured launch freezes (a change re-captures); lr travels in a device word."""
+        raise NotImplementedError
+
+    def _device_update(self, fl, group, gscale, skip=None, lr_dev=None):
+        """One update launch over the flat buffers `fl` of `group` (gradients already summed over the ranks: scaled by `gscale`)."""
+        raise NotImplementedError
 
     @staticmethod
     def _reduce(live, flat, world, flat_all=None):
@@ -107,15 +134,10 @@ class FusedSGD(torch.optim.Optimizer):
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         taint = None           # ONE taint word per step: h2_taint advances its mark, so later groups reuse the first group's (summed) word
         for gi, group in enumerate(self.param_groups):
-            live = [p for p in group["params"] if p.grad is not None]      # torch SGD skips grad=None
+            live = [p for p in group["params"] if p.grad is not None]      # torch skips grad=None
             if not live:
                 continue
-            fl = self._flat.get(gi)
-            if fl is None or fl["ids"] != [id(p) for p in live] or any(
-                    p.data.data_ptr() < fl["p"].data_ptr() or
-                    p.data.data_ptr() >= fl["p"].data_ptr() + fl["p"].numel() * 4 for p in live):
-                self._build(gi, live)
-                fl = self._flat[gi]
+            fl = self._current(gi, live)
             if taint is None:
                 ops.h2_taint(fl["g_all"][:1])      # clamps of this step's split-fp16 launches -> the word in front of the gradients
             else:
@@ -125,10 +147,98 @@ class FusedSGD(torch.optim.Optimizer):
                 taint = fl["g_all"][:1]
             else:
                 fl["g_all"][:1].copy_(taint)       # (already summed over the ranks)
-            # buf starts at zero, so mu*buf + g reproduces torch's first-step "buf = g" exactly; a tainted step is skipped
-            ops.sgd_momentum(fl["p"], fl["g"], fl["buf"], float(group["lr"]), float(group["momentum"]), 1.0 / world,
-                             False, skip=fl["g_all"][:1])
+            self._device_update(fl, group, 1.0 / world, skip=fl["g_all"][:1])      # a tainted step is skipped on the device
+        # the update wrote the parameters through raw pointers (no version bump): an operand pre-packed from the old weights by a forward
+        # pass that no backward consumed (ops.pack_many) must not be served to the next one
+        ops._PREPACKED.clear()
         return None
+
+
+class FusedSGD(_FusedFlat):
+    """torch.optim.SGD(lr, momentum) semantics, one nef_sgd_momentum launch per parameter group."""
+    _SLOTS = (("buf", "momentum_buffer"),)
+
+    def __init__(self, params, lr, momentum=0.9):
+        super().__init__(params, dict(lr=lr, momentum=momentum))
+
+    def _captured_scalars(self, group):
+        return (float(group["momentum"]),)
+
+    def _device_update(self, fl, group, gscale, skip=None, lr_dev=None):
+        # buf starts at zero, so mu*buf + g reproduces torch's first-step "buf = g" exactly
+        ops.sgd_momentum(fl["p"], fl["g"], fl["buf"], float(group["lr"]), float(group["momentum"]), gscale, False, skip=skip,
+                         lr_dev=lr_dev)
+
+
+class FusedAdam(_FusedFlat):
+    """torch.optim.Adam semantics (amsgrad=False, maximize=False, L2 weight_decay folded into the gradient), one nef_adam launch per
+    parameter group.  The state is torch's: state[p] = {"step", "exp_avg", "exp_avg_sq"} with the moments as views of the flat
+    buffers, so checkpoints go both ways between this optimiser and torch.optim.Adam / DataParallelAdam.  The step count of a group
+    lives in ONE device word (the kernel reads it for the bias corrections and advances it: a captured update stays right on every
+    replay); it is imported from the parameters' state["step"] when the flat buffers are built, and state_dict() writes it back into
+    each parameter's state["step"] -- one synchronisation, at checkpoint time only.  Between two state_dict() calls state["step"] is
+    not kept current."""
+    _SLOTS = (("m", "exp_avg"), ("v", "exp_avg_sq"))
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, maximize=False):
+        if amsgrad or maximize:
+            raise NotImplementedError("FusedAdam implements amsgrad=False, maximize=False")
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"Invalid beta parameters: {betas}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        super().__init__(params, dict(lr=lr, betas=(float(betas[0]), float(betas[1])), eps=eps, weight_decay=weight_decay,
+                                      amsgrad=False, maximize=False))
+
+    @staticmethod
+    def _check_group(group):
+        if group.get("amsgrad") or group.get("maximize") or group.get("decoupled_weight_decay"):
+            raise NotImplementedError("FusedAdam implements amsgrad=False, maximize=False, L2 weight_decay")
+
+    def _export_steps(self):
+        """The device step words -> state["step"] of every parameter (torch's float32 scalar tensor)."""
+        for fl in self._flat.values():
+            s = float(fl["step"].item())
+            for p in fl["params"]:
+                self.state[p]["step"] = torch.tensor(s, dtype=torch.float32)
+
+    def _build(self, gi, live):
+        old = self._flat.get(gi)
+        if old is not None:         # the old buffers' step word is the current count of their parameters
+            s = float(old["step"].item())
+            for p in old["params"]:
+                self.state[p]["step"] = torch.tensor(s, dtype=torch.float32)
+        steps = {}
+        for i, p in enumerate(live):
+            v = self.state[p].get("step", 0.0)
+            steps.setdefault(float(v), []).append(getattr(p, "_nef_name", None) or f"param {i}")
+        if len(steps) > 1:
+            raise ValueError("FusedAdam keeps one step count per parameter group; the live parameters carry different ones: " +
+                             "; ".join(f"step {s:g}: {', '.join(names)}" for s, names in sorted(steps.items())))
+        super()._build(gi, live)
+        self._flat[gi]["step"] = torch.full((1,), next(iter(steps)), device=live[0].device, dtype=torch.float32)
+
+    def state_dict(self):
+        self._export_steps()
+        return super().state_dict()
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        for group in self.param_groups:
+            self._check_group(group)
+
+    def _captured_scalars(self, group):
+        b1, b2 = group["betas"]
+        return (float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]))
+
+    def _device_update(self, fl, group, gscale, skip=None, lr_dev=None):
+        self._check_group(group)
+        b1, b2, eps, wd = self._captured_scalars(group)
+        ops.adam(fl["p"], fl["g"], fl["m"], fl["v"], fl["step"], float(group["lr"]), b1, b2, eps, wd, gscale, skip=skip, lr_dev=lr_dev)
 
 
 class DataParallelAdam(Adam):
@@ -158,7 +268,7 @@ class DataParallelAdam(Adam):
 def get_optimizer(cfg, model_params):
     optim_name = cfg.SOLVER.optim
     if optim_name == 'adam':
-        return DataParallelAdam(model_params, lr=cfg.SOLVER.lr)
+        return FusedAdam(model_params, lr=cfg.SOLVER.lr)
     elif optim_name == 'sgd':
         return FusedSGD(model_params, lr=cfg.SOLVER.lr, momentum=0.9)
 

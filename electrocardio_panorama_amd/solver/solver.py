@@ -225,7 +225,8 @@ class Solver:
 
     def _graphed_step(self, optim, data, keep):
         """The hipGraph stepper for this batch, or None when the step runs eagerly: `cfg.SOLVER.graph` False, the per-view host lists are wanted (the graph returns losses only), the
-        model is not the plain Model_nefnet train path, DATA.noise, or the optimiser is not FusedSGD."""
+        model is not the plain Model_nefnet train path, DATA.noise, or the optimiser is not a fused one (FusedSGD, FusedAdam) with one
+        parameter group."""
         mode = self.cfg.SOLVER.get('graph', None)
         mode = 'auto' if mode is None or mode == 'auto' else bool(mode)
         if mode is False or keep or self.cfg.DATA.noise:
@@ -248,7 +249,7 @@ class Solver:
         data (finite operands beyond ops.H2_HEADROOM x of growth are redone with their own scale inside the launch), or any
         clamp of the opt-in producer / consumer kernel form (fp16 ends at 65504; the reference's fp32 nn.Conv1d,
         model_nefnet.py:18-21, has no such limit).  A train step that contained such a launch was SKIPPED on the device when the
-        optimiser is FusedSGD (ops.h2_taint): that is reported; counts nothing protected against -- a test-phase forward,
+        optimiser is a fused one, FusedSGD or FusedAdam (ops.h2_taint): that is reported; counts nothing protected against -- a test-phase forward,
         another optimiser -- mean wrong results were used: raise, unless NEF_H2_ALLOW_CLAMP=1 (then warn).  NEF_H2=0 runs the
         fp32 kernels instead.  Data parallel: the counters are per rank, so they are SUMMED over the process group before anything
         is decided -- every rank raises (or warns) together; a rank that alone saw the bad operand must not leave the others

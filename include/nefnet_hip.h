@@ -34,7 +34,7 @@ extern "C" {
 typedef void* nef_stream_t;
 
 /* ABI version of this header; bumped on any signature change. */
-int nef_abi_version(void);   /* 19 (the kernel-form option entry points of 16 and nef_upsample2_aff_fwd are gone; + nef_debug_spin_us); 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + kernel-form option entry points); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + nef_conv_bwd_weight_h2); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, nef_conv_bwd_weight_wino4 covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
+int nef_abi_version(void);   /* 19 (+ nef_adam, an addition only; the kernel-form option entry points of 16 and nef_upsample2_aff_fwd are gone; + nef_debug_spin_us); 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + kernel-form option entry points); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + nef_conv_bwd_weight_h2); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, nef_conv_bwd_weight_wino4 covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
 
 /* Diagnostics: `wgs` workgroups busy for `us` microseconds on `stream` (a stand-in for a collective's time on the chip:
  * parallel.DryCollective, bench.py --dry-collective).  0 <= us <= 50000, 1 <= wgs <= 64. */
@@ -470,6 +470,16 @@ int nef_sgd_momentum(float* p, const float* g, float* buf, int64_t n, float lr, 
                      (a step whose gradients are tainted, see nef_h2_taint) */, int32_t* skipped /* NULL, or a device counter of
                      skipped steps */, const float* lr_dev /* NULL, or a device word that replaces `lr` at run time (hipGraph replay: a scheduler's
                      new learning rate without a re-capture) */, nef_stream_t stream);
+/* Adam over a flat buffer.  codes/solver/optim_scheduler.py:8 (torch.optim.Adam semantics with amsgrad=False, maximize=False and L2
+ * weight_decay folded into the gradient): g' = g*gscale + weight_decay*p; m = lerp(m, g', 1-beta1); v = beta2*v + (1-beta2)*g'^2;
+ * with t = *step + 1 and the bias corrections bc1 = 1-beta1^t, bc2 = 1-beta2^t in fp64: p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps).
+ * `step` is a device word (torch's state["step"]: completed updates) that a second, one-lane launch advances behind the update, so
+ * a captured launch steps the right t on every replay.  skip_if_positive / skipped / lr_dev: as for nef_sgd_momentum; a skipped step
+ * leaves p, m, v and *step as they are.  16-byte aligned p, g, m, v take the vector path.  The betas are doubles because torch forms
+ * 1 - beta and the bias corrections from Python floats: 1 - (double)0.999f is 1.3e-5 away from 1 - 0.999. */
+int nef_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2, float eps,
+             float weight_decay, float gscale, float* step /* device word: completed updates */, const float* skip_if_positive,
+             int32_t* skipped, const float* lr_dev, nef_stream_t stream);
 /* The split-fp16 convolutions (conv args wino = 3, nef_conv_bwd_weight_h2) count the waves that had to clamp an operand at fp16's
  * range in a device counter (x_clamped); such a launch's results are wrong.  nef_h2_taint writes out[0] = (float)(*clamped_total -
  * *mark) -- the clamps since the previous call -- and sets *mark = *clamped_total: called once per train step behind the backward

@@ -1,0 +1,151 @@
+"""Adam against SGD on the train step of BASELINE config 2 (B=256, 3 leads, L=5000), one GPU; prints one JSON line.
+
+    python tools/bench_adam.py [--steps 10] [--warmup 3] [--reps 3] [--out profiles/adam_bench_line.json]
+
+Each measurement runs in a child process of its own under `timeout` (nothing more is started once one fails), `--reps` rounds of
+the three children; every figure is reported as [min, median, max] over the rounds:
+  sgd-graph   the graphed step (GraphedTrainStep) with FusedSGD -- what bench.py times;
+  adam-graph  the graphed step with FusedAdam, then the nef_adam launch alone on the same flat buffers, COLD: before every timed
+              launch a 512 MiB scratch buffer (twice the 256 MiB Infinity Cache) is written, as the backward pass in front of the
+              update does in the train step; HIP events around each launch, median of 30 (seven fp32 streams per parameter = the
+              algorithmic bytes).  The warm figure (50 back-to-back launches, the 115 MB working set cache-resident) is listed too;
+  adam-eager  the eager step with DataParallelAdam (torch.optim.Adam: ATen kernels, no graph) -- the path 'adam' took before.
+Every child warms up before it times."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+MODES = {"sgd-graph": 900, "adam-graph": 900, "adam-eager": 1200}      # child -> its time limit (s)
+
+
+def child(mode, steps, warmup, V=3, B=256, L=5000):
+    import numpy as np
+    import torch
+    from electrocardio_panorama_amd import ops, synth
+    from electrocardio_panorama_amd.config import get_defaults, resolve_config_path
+    from electrocardio_panorama_amd.network import build_loss, build_model
+    from electrocardio_panorama_amd.solver.optim_scheduler import DataParallelAdam, FusedAdam, FusedSGD
+    from electrocardio_panorama_amd.utils import seed_torch
+    cfg = get_defaults()
+    cfg.merge_from_file(resolve_config_path("config/nef_net.yml"))
+    cfg.DATA.lead_num = V
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    seed_torch(cfg.seed)
+    model = build_model(cfg).float().to(dev).train()
+    lossf = build_loss(cfg)
+    if mode == "sgd-graph":
+        optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9)
+    elif mode == "adam-graph":
+        optim = FusedAdam(model.parameters(), lr=1e-3)
+    else:
+        optim = DataParallelAdam(model.parameters(), lr=1e-3)
+    meta = synth.make_batch(B, V, L, seed=123)
+    data, rois, in_theta, tgt_view, tgt_theta = (torch.from_numpy(np.ascontiguousarray(meta[k])).to(dev) for k in
+                                                 ("data", "rois", "input_theta", "target_view", "target_theta"))
+    tgt_view = tgt_view.unsqueeze(1)
+    graphed = None
+    if mode.endswith("-graph"):
+        from electrocardio_panorama_amd.graph import GraphedTrainStep
+        graphed = GraphedTrainStep(model, cfg, optimizer=optim)
+
+    def step():
+        if graphed is not None:
+            return graphed(data, in_theta, tgt_theta, rois, tgt_view)
+        out, sp, sl = model(data, in_theta, tgt_theta, rois, phase="train")
+        losses = lossf(out, sp, sl, tgt_view, cfg)
+        losses[0].backward()
+        optim.step()
+        optim.zero_grad()
+        return losses
+
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        step()
+    torch.cuda.synchronize(dev)
+    res = {"mode": mode, "ms_per_step": round((time.perf_counter() - t0) * 1e3 / steps, 3), "steps": steps, "warmup": warmup}
+    if mode == "adam-graph":
+        fl = optim._flat[0]
+        p, g, m, v, s = (fl[k].clone() for k in ("p", "g", "m", "v", "step"))
+        n = p.numel()
+        for _ in range(5):
+            ops.adam(p, g, m, v, s, 1e-3, 0.9, 0.999, 1e-8, 0.0, 1.0)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        reps = 50
+        e0.record()
+        for _ in range(reps):
+            ops.adam(p, g, m, v, s, 1e-3, 0.9, 0.999, 1e-8, 0.0, 1.0)
+        e1.record()
+        e1.synchronize()
+        warm = e0.elapsed_time(e1) / reps
+        flush = torch.empty(512 << 18, device=dev, dtype=torch.float32)        # 512 MiB
+        cold = []
+        for i in range(30):
+            flush.fill_(float(i))
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            ops.adam(p, g, m, v, s, 1e-3, 0.9, 0.999, 1e-8, 0.0, 1.0)
+            b.record()
+            cold.append((a, b))
+        torch.cuda.synchronize(dev)
+        ms = float(np.median([a.elapsed_time(b) for a, b in cold]))
+        res.update(nef_adam_cold_ms=round(ms, 4), nef_adam_warm_ms=round(warm, 4), nef_adam_params=n,
+                   nef_adam_cold_GBps=round(7 * 4 * n / (ms * 1e-3) / 1e9, 1))
+    print("RESULT " + json.dumps(res), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=3, help="rounds of the three children")
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    ap.add_argument("--child", choices=sorted(MODES), default=None)
+    args = ap.parse_args()
+    if args.child:
+        return child(args.child, args.steps if args.child != "adam-eager" else max(3, args.steps // 2), args.warmup)
+    results = {mode: [] for mode in MODES}
+    for rnd in range(args.reps):
+        order = list(MODES) if rnd % 2 == 0 else list(reversed(MODES))       # no mode always runs first on a fresh box
+        for mode in order:
+            cmd = ["timeout", "-k", "10", str(MODES[mode]), sys.executable, os.path.abspath(__file__), "--child", mode,
+                   "--steps", str(args.steps), "--warmup", str(args.warmup)]
+            r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+            line = [x for x in r.stdout.splitlines() if x.startswith("RESULT ")]
+            if r.returncode != 0 or not line:
+                sys.stderr.write(r.stdout[-3000:])
+                raise SystemExit(f"{mode}: exit status {r.returncode}; nothing more is started")
+            results[mode].append(json.loads(line[0][len("RESULT "):]))
+
+    def spread(mode, key):
+        v = sorted(x[key] for x in results[mode])
+        return [v[0], v[len(v) // 2], v[-1]]
+
+    ag = results["adam-graph"]
+    out = {"metric": "ms per train step, Adam vs SGD ([min, median, max] over rounds)",
+           "config": "BASELINE config 2: B=256, 3 leads, L=5000, one GPU, dropout on", "rounds": args.reps,
+           "sgd_graphed_ms": spread("sgd-graph", "ms_per_step"), "adam_graphed_ms": spread("adam-graph", "ms_per_step"),
+           "data_parallel_adam_eager_ms": spread("adam-eager", "ms_per_step"),
+           "nef_adam_cold_ms": spread("adam-graph", "nef_adam_cold_ms"), "nef_adam_cold_GBps": spread("adam-graph", "nef_adam_cold_GBps"),
+           "nef_adam_warm_ms": spread("adam-graph", "nef_adam_warm_ms"), "nef_adam_params": ag[0]["nef_adam_params"],
+           "nef_adam_note": "cold = a 512 MiB buffer written before each launch (the 115 MB working set is evicted, as behind the "
+                            "backward pass); warm = back-to-back launches, working set in the 256 MiB Infinity Cache",
+           "steps": args.steps, "warmup": args.warmup, "eager_steps": results["adam-eager"][0]["steps"]}
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
