@@ -10,6 +10,8 @@ import os
 PRODUCT = {
     "NEF_H2": "1 (default): K = 1 / 3 / 7 convolutions on the split-fp16 kernels; 0: the fp32 Winograd / direct kernels (strict fp32, "
               "required for data whose dynamic range exceeds ops.H2_HEADROOM per step)",
+    "NEF_H2_TAIL": "warn (default): split-fp16 call sites whose operand is heavy-tailed (ops.H2_TAIL_FRAC) are counted and reported; "
+                   "fp32: such WEIGHT-GRADIENT sites run on the fp32 kernels for their lifetime (per site, per rank)",
     "NEF_H2_ALLOW_CLAMP": "1: Solver warns instead of raising when a split-fp16 launch clamped outside a protected train step",
     "NEF_WINOGRAD": "fp32 path: 4 (default) F(4,.) forms where allowed, 2 / 1: F(2,.) only, 0: direct kernels only",
     "NEF_SIDE_STREAM": "auto (default) / 1 / 0: weight gradients on a second HIP stream",

@@ -89,13 +89,22 @@ class Model_nefnet(nn.Module):
         return super().load_state_dict(*args, **kw)
 
     def h2_state(self):
-        """The operand magnitudes of this model's split-fp16 call sites (ops.h2_export) -- not part of the reference's state_dict
-        (codes/utils/checkpointer.py:24-36 saves model / optimizer / scheduler); CheckPointer stores it next to them so that a
-        resumed run continues bit for bit."""
+        """The operand magnitudes of this model's split-fp16 call sites and the weight-gradient sites' routes (ops.h2_export,
+        version 2) -- not part of the reference's state_dict (codes/utils/checkpointer.py:24-36 saves model / optimizer /
+        scheduler); CheckPointer stores it next to them so that a resumed run continues bit for bit."""
         return ops.h2_export(self._nef_scope, {p.data_ptr(): n for n, p in self.named_parameters()})
 
     def load_h2_state(self, blob):
-        """After load_state_dict: the call sites take up the magnitudes the checkpointed run had reached."""
+        """After load_state_dict: the call sites take up the magnitudes the checkpointed run had reached.  A version-2 blob also
+        carries the routes of its weight-gradient sites: they are taken up when THIS process runs ops.H2_TAIL_MODE = "fp32" (and
+        counted in h2_fallback_sites()); in "warn" mode those sites stay on the split kernels and are counted in h2_tail_sites().
+        A version-1 blob has no routes: every site keeps the split kernels.
+        Data parallel: CheckPointer saves rank 0's blob only, and every rank loads it.  Magnitudes and routes are per rank (shards
+        differ: each rank measures and decides its own sites, with no collective), and imported sites never measure again.  So a
+        resumed rank other than 0 splits with rank 0's scales (fp32-class on the norm) and takes rank 0's routes: a site that
+        rank 0 had left on the split kernels stays there for good on that rank even where its own shard is heavy-tailed -- its
+        weight gradient's small half then carries the ~5e-3 the route exists to remove, and the site is not counted in
+        h2_tail_sites().  The gradients are still all-reduced, so the parameters stay identical on every rank."""
         dev = next(self.parameters()).device
         if dev.type != "cuda":
             return 0

@@ -280,9 +280,19 @@ H2_HEADROOM = 64
 # full-size gradient parity 3.3e-5 on the flat norm, every tensor <= 1e-3).  An amax / rms ratio (the review's suggestion) fires on
 # neither: the rms of a heavy-tailed sample is dominated by its largest elements (log-normal: 100-500, not > 2048).  Checked ONCE per
 # site, where it measures its operand (its first launch; never inside a captured step); bench.py and Solver report the count
-# (h2_tail_sites) -- a model that counts here wants NEF_H2=0.
+# (h2_tail_sites) -- a model that counts here wants NEF_H2=0, or NEF_H2_TAIL=fp32 below.
+# The measurement is a HIP census of the operand as the launch splits it (csrc/h2_tail.hip: the view, the affine + ReLU prologue,
+# the channel scale), not of the tensor behind the view.
 H2_TAIL_WINDOW = 2.0 ** -11
 H2_TAIL_FRAC = 0.9
+# What a flagged WEIGHT-GRADIENT site does (NEF_H2_TAIL; tests set the attribute): "warn" (default) only counts it; "fp32" reads its
+# census flag on the host once, at its measuring launch (eager, never captured), and routes the site to the direct fp32
+# weight-gradient kernel, conv_bwd_weight(h2=False, wino=False) for the same operands, for the site's lifetime (h2_fallback_sites).  Forward and
+# backward-data sites keep the split kernels either way.
+H2_TAIL_MODES = ("warn", "fp32")
+H2_TAIL_MODE = _env.get("NEF_H2_TAIL", "warn")
+if H2_TAIL_MODE not in H2_TAIL_MODES:
+    raise ValueError(f"NEF_H2_TAIL={H2_TAIL_MODE!r}: expected one of {H2_TAIL_MODES}")
 AMAX_SITES = 16384
 _AMAX = {}
 # A call site = (scope, weight address, direction, role, batch, length).  The scope is the owning model's token
@@ -316,7 +326,8 @@ def _amax_state(dev):
                                skipped=torch.zeros(1, device=dev, dtype=torch.int32),       # train steps skipped because of a clamp
                                tail=torch.zeros(1, device=dev, dtype=torch.int32),          # call sites whose operand is heavy-tailed (H2_TAIL_*)
                                tail_stat=torch.zeros(2, device=dev, dtype=torch.float32),   # diagnostics: largest (count, energy) fraction below the window seen at a site
-                               seen=0, seen_skipped=0, seen_tail=0)                                       # ... as of the host's last h2_clamped() / h2_skipped()
+                               fp32=set(),                                                  # slots of weight-gradient sites routed to the fp32 kernels (H2_TAIL_MODE)
+                               seen=0, seen_skipped=0, seen_tail=0, fallback=0, seen_fallback=0)          # ... as of the host's last h2_clamped() / h2_skipped()
     return st
 
 
@@ -358,26 +369,57 @@ def h2_tail_sites(reset=True):
     return n
 
 
-def _note_tail(st, i, n, *tensors):
-    """At a site's measuring launch (eager, once per site): slots i .. i + n - 1 of `nxt` hold the operands' amax; count the site if
-    an operand has more than H2_TAIL_FRAC of its nonzero elements below H2_TAIL_WINDOW x that amax (the energy fraction there is kept
-    for the diagnostics, h2_tail_stats).  A handful of torch passes per SITE LIFETIME (the tensor as stored: prologues and channel scales are not applied), nothing per
-    step, nothing read by the host."""
-    hit = None
-    for k, t in enumerate(tensors[:n]):
-        if t is None or t.numel() == 0:
+def h2_fallback_sites(reset=True):
+    """Split-fp16 weight-gradient call sites routed to the fp32 kernels (H2_TAIL_MODE = "fp32": their census flagged an operand)
+    since the last call.  A host count: nothing synchronises."""
+    n = 0
+    for st in _AMAX.values():
+        n += st["fallback"] - st["seen_fallback"]
+        if reset:
+            st["seen_fallback"] = st["fallback"]
+    return n
+
+
+def tail_census(xv, amax, in_scale=None, pro=None, site_flag=None, tail_stat=None):
+    """nef_h2_tail_census of the operand a split-fp16 launch splits: the GV `xv`, `in_scale` = (tensor, batch stride, group stride)
+    and `pro` = (mode, a, b, Bp) as conv() / conv_bwd_weight() get them; `amax` a one-element device tensor (the slot).  Returns the
+    record as a 12-word int32 device tensor (census_record() reads it); `site_flag` / `tail_stat`: device words the launch also
+    updates.  Two stream-ordered launches, nothing read by the host."""
+    L = _lib.load()
+    dev = xv.t.device
+    rec = torch.zeros(12, device=dev, dtype=torch.int32)
+    n = L.nef_h2_tail_census_ws_bytes(xv.B, xv.G, xv.Cg)
+    ws = torch.empty(max(n, 8) // 8, device=dev, dtype=torch.float64)
+    sc, sc_bs, sc_gs = (None, 0, 0) if in_scale is None else (_p(in_scale[0]), in_scale[1], in_scale[2])
+    pm = pro[0] if pro is not None else 0
+    pa, pb, pbp = (_p(pro[1]), _p(pro[2]), pro[3]) if pm & 1 else (None, None, 1)
+    _lib.check(L.nef_h2_tail_census(xv.ptr, xv.bs, xv.gs, xv.B, xv.G, xv.Cg, xv.T, sc, sc_bs, sc_gs, pa, pb, int(pm), int(pbp),
+                                    amax.data_ptr(), H2_TAIL_WINDOW, H2_TAIL_FRAC, _p(ws), ws.numel() * 8, _p(rec), _p(site_flag),
+                                    _p(tail_stat), _stream()), "nef_h2_tail_census")
+    return rec
+
+
+def census_record(rec):
+    """The host's view of a tail_census() record (synchronises)."""
+    r = rec.cpu()
+    n = r[0:4].view(torch.int64).tolist()
+    e = r[4:8].view(torch.float64).tolist()
+    f = r[8:10].view(torch.float32).tolist()
+    return dict(n_nonzero=n[0], n_small=n[1], e_small=e[0], e_total=e[1], frac_count=f[0], frac_energy=f[1], flag=int(r[10]))
+
+
+def _note_tail(st, i, operands):
+    """At a site's measuring launch (eager, once per site): slots i, i + 1, .. of `nxt` hold the amax of `operands` -- (GV,
+    in_scale, pro) each, as the launch reads them; the census (tail_census) counts the site in `tail` if an operand has more than
+    H2_TAIL_FRAC of its nonzero elements below H2_TAIL_WINDOW x that amax, and keeps the largest fractions in `tail_stat`.  Returns
+    the site's device flag word; nothing read by the host."""
+    flag = torch.zeros(1, device=st["nxt"].device, dtype=torch.int32)
+    for k, (xv, in_scale, pro) in enumerate(operands):
+        if xv is None or xv.B * xv.G * xv.Cg * xv.T == 0:
             continue
-        a = t.detach().abs()
-        small = (a > 0) & (a < st["nxt"][i + k] * H2_TAIL_WINDOW)
-        cf = small.sum().to(torch.float32) / (a > 0).sum().clamp_min(1).to(torch.float32)
-        a2 = a.double() * a.double()
-        ef = ((a2 * small).sum() / a2.sum().clamp_min(1e-300)).to(torch.float32)
-        h = cf > H2_TAIL_FRAC
-        hit = h if hit is None else (hit | h)
-        st["tail_stat"][0] = torch.maximum(st["tail_stat"][0], cf)
-        st["tail_stat"][1] = torch.maximum(st["tail_stat"][1], ef)
-    if hit is not None:
-        st["tail"] += hit.to(torch.int32)
+        tail_census(xv, st["nxt"][i + k:i + k + 1], in_scale, pro, site_flag=flag, tail_stat=st["tail_stat"])
+    st["tail"] += flag
+    return flag
 
 
 def h2_tail_stats():
@@ -411,7 +453,7 @@ def _amax_index(st, site, n):
     if i is None:
         if st["n"] + n > AMAX_SITES:       # models come and go (tests): start over
             assert not torch.cuda.is_current_stream_capturing()
-            st["index"].clear(), st["ready"].clear(), st["cur"].zero_(), st["nxt"].zero_()
+            st["index"].clear(), st["ready"].clear(), st["fp32"].clear(), st["cur"].zero_(), st["nxt"].zero_()
             st["n"] = 0
             st["gen"] = st.get("gen", 0) + 1       # captured graphs hold the old slots: GraphedTrainStep re-captures (amax_generation)
         i = st["index"][site] = st["n"]
@@ -425,8 +467,10 @@ def h2_export(scope_id, ptr_names):
     {data_ptr: name}).  With it a restored run splits its operands with the scales the uninterrupted run would have used, i.e.
     continues bit for bit (h2_import); without it a restored model measures again (equal arithmetic, a different power-of-two operand
     scale wherever a magnitude sits near a binade edge).  Sites through tensors that are not parameters (BatchNorm-folded
-    panorama weights) are left out: they measure again.  Reads the device (synchronises)."""
-    keys, cur, nxt = [], [], []
+    panorama weights) are left out: they measure again.  Version 2 also carries each site's route (`fp32`: a weight-gradient site
+    on the fp32 kernels, H2_TAIL_MODE); a blob without a routed site stays version 1 (same meaning: every site on the split
+    kernels, and readable by releases before routes).  Reads the device (synchronises)."""
+    keys, cur, nxt, fp32 = [], [], [], []
     for st in _AMAX.values():
         c_, n_ = st["cur"].cpu(), st["nxt"].cpu()
         for key, i in st["index"].items():
@@ -439,17 +483,25 @@ def h2_export(scope_id, ptr_names):
             keys.append((bool(key[0][1]), (name, key[1][1]), key[2], int(key[3]), int(key[4]), int(key[5])))
             cur.append([float(c_[i + j]) for j in range(n)])
             nxt.append([float(n_[i + j]) for j in range(n)])
-    return {"version": 1, "keys": keys, "cur": cur, "nxt": nxt}
+            fp32.append(i in st["fp32"])
+    if not any(fp32):
+        return {"version": 1, "keys": keys, "cur": cur, "nxt": nxt}
+    return {"version": 2, "keys": keys, "cur": cur, "nxt": nxt, "fp32": fp32}
 
 
 def h2_import(scope_id, name_ptrs, blob, device):
     """Hands the slots of h2_export back to the call sites of the model that now owns `scope_id` (`name_ptrs`: {name: data_ptr});
-    entries whose parameter is gone are skipped (they measure)."""
-    if not blob or blob.get("version") != 1:
+    entries whose parameter is gone are skipped (they measure).  Routes (version 2) follow THIS process's H2_TAIL_MODE: in "fp32"
+    mode a site the checkpointed run had routed is routed again and counted in h2_fallback_sites(); in "warn" mode it stays on the
+    split kernels.  Either way it counts in h2_tail_sites() (its census flagged it; imported sites do not measure again).  A
+    version-1 blob (no routes) leaves every site on the split kernels."""
+    if not blob or blob.get("version") not in (1, 2):
         return 0
     st = _amax_state(torch.device(device))
     done = 0
-    for key, c_, n_ in zip(blob["keys"], blob["cur"], blob["nxt"]):
+    routes = blob["fp32"] if blob["version"] == 2 else [False] * len(blob["keys"])
+    fp32, flagged = _tail_mode() == "fp32", 0
+    for key, c_, n_, r_ in zip(blob["keys"], blob["cur"], blob["nxt"], routes):
         ptr = name_ptrs.get(key[1][0])
         if ptr is None:
             continue
@@ -458,9 +510,17 @@ def h2_import(scope_id, name_ptrs, blob, device):
         st["cur"][i:i + len(c_)] = torch.tensor(c_, dtype=torch.float32)
         st["nxt"][i:i + len(n_)] = torch.tensor(n_, dtype=torch.float32)
         st["ready"].add(i)
+        st["fp32"].discard(i)
+        if r_:
+            flagged += 1
+            if fp32:
+                st["fp32"].add(i)
+                st["fallback"] += 1
         done += 1
     if done:
         st["used"] = True
+    if flagged:
+        st["tail"] += flagged
     return done
 
 
@@ -734,7 +794,7 @@ def conv(xv, wp, Cog, K, out=None, bias=None, in_scale=None, res=None, gate=None
             _lib.check(L.nef_conv_fwd(C.byref(a), _stream()), "nef_conv_fwd")
             st["cur"][i] = st["nxt"][i]
             if site is not None:
-                _note_tail(st, i, 1, xv.t)
+                _note_tail(st, i, [(xv, in_scale, pro)])
             st["ready"].add(i)
         a.x_amax = st["cur"].data_ptr() + 4 * i
         a.x_clamped = st["clamped"].data_ptr()
@@ -857,7 +917,7 @@ def conv_bwd_weight_poly(xv, gy_pm, Cog, pro, xedge, site=None):
     aff = pro is not None and bool(pro[0] & 1)
     gyv = GV.dense(gy_pm, G)
     gw2 = conv_bwd_weight(xv, gyv, 3, pro=(4 | int(aff), pro[1] if aff else None, pro[2] if aff else None, pro[3] if aff else 1),
-                          site=site, h2=True)
+                          site=site, h2=True, xedge=xedge)
     gw = torch.empty(G * Cog, Cig, 3, device=gy_pm.device, dtype=torch.float32)
     n = L.nef_poly_wgrad_fold_ws_bytes(xv.B, G, Cog, Cig)
     ws = torch.empty(n // 4, device=gy_pm.device, dtype=torch.float32)
@@ -871,17 +931,19 @@ def h2w_ok(K, Cig, Cog, T, pro_mode=0, in_scale=False):
             (K == 3 or not pro_mode) and not (pro_mode and in_scale))
 
 
-def conv_bwd_weight(xv, gyv, K, in_scale=None, pro=None, wino=None, site=None, h2=None, x_scale=0.0, gy_scale=0.0):
+def conv_bwd_weight(xv, gyv, K, in_scale=None, pro=None, wino=None, site=None, h2=None, x_scale=0.0, gy_scale=0.0, xedge=None):
     """gw [G*Cog, Cig, K] for y = conv(prologue(x) * in_scale, w); `pro` as in conv().  Default path: the split-fp16 kernel
     (csrc/conv_h2w.hip) wherever its shape rules hold (h2w_ok; `h2=False` forbids it, giving `wino` forbids it too); `site`: the
     identity of the call site for its operand-magnitude slots (the engine passes the weight's address; None = measure at every
     call), `x_scale` / `gy_scale`: explicit powers of two instead.  `wino`: force (True / 4) or forbid
     (False) the transposed-Winograd form -- F(3,4) for K == 3, the 4 + 3 split through F(4,4) + F(3,4) for K == 7; default:
-    wherever it applies (see WINOGRAD, WINO_BW4, WINO_BW7)."""
+    wherever it applies (see WINOGRAD, WINO_BW4, WINO_BW7).  `xedge` [B, G*Cig, 2]: the prologue's output at both row ends, which
+    pro_mode bit 2 needs on the fp32 kernels (conv_bwd_weight_poly passes it)."""
     L = _lib.load()
     B, T, G, Cig, Cog = xv.B, gyv.T, xv.G, xv.Cg, gyv.Cg
     gw = torch.empty(G * Cog, Cig, K, device=xv.t.device, dtype=torch.float32)
     pm0 = pro[0] if pro is not None else 0
+    routed = False
     if h2 is None:
         h2 = (wino is None and h2w_ok(K, Cig, Cog, T, pm0, in_scale is not None) and
               (BATCH_HINT is None or B * ((T + 63) // 64) >= 8 * _H2_MIN_WGS))      # enough (sample, tile) steps to split
@@ -898,14 +960,8 @@ def conv_bwd_weight(xv, gyv, K, in_scale=None, pro=None, wino=None, site=None, h
                                                 _p(gw), _p(ws), n, B, T, G, Cig, Cog, K, float(x_scale), float(gy_scale),
                                                 amax, None if amax is None else amax + 4, nxt, None if nxt is None else nxt + 4,
                                                 clamped, _stream()), "nef_conv_bwd_weight_h2")
-        tag = ("conv_bwd_weight", K, G, Cig, Cog, B, T) + (("up",) if pm0 & 2 else (("pw",) if pm0 & 4 else ()))
-        ev = _timed(tag)
-        if ev is not None:
-            EXEC_FRAC[tag] = 0.0
-            EXEC_FP16[tag] = 3.0
-        if x_scale and gy_scale:
-            launch(None, None)
-        else:
+        amax = nxt = clamped = None
+        if not (x_scale and gy_scale):
             st = _amax_state(xv.t.device)
             key = None
             if AMAX_SCOPE is not None and site is not None:
@@ -922,19 +978,45 @@ def conv_bwd_weight(xv, gyv, K, in_scale=None, pro=None, wino=None, site=None, h
                 launch(None, nxt)
                 st["cur"][i:i + 2] = st["nxt"][i:i + 2]
                 if key is not None:
-                    _note_tail(st, i, 2, xv.t, gyv.t)
+                    flag = _note_tail(st, i, [(xv, in_scale, pro), (gyv, None, None)])
+                    if _tail_mode() == "fp32" and int(flag.item()):      # (the measuring launch is eager: one host read per site lifetime)
+                        st["fp32"].add(i)
+                        st["fallback"] += 1
                 st["ready"].add(i)
-            st["used"] = True
-            launch(st["cur"].data_ptr() + 4 * i, nxt, st["clamped"].data_ptr())
-        if ev is not None:
-            ev.record()
-        return gw
+            routed = i in st["fp32"]
+            if not routed:
+                st["used"] = True
+                amax, clamped = st["cur"].data_ptr() + 4 * i, st["clamped"].data_ptr()
+        if not routed:
+            tag = ("conv_bwd_weight", K, G, Cig, Cog, B, T) + (("up",) if pm0 & 2 else (("pw",) if pm0 & 4 else ()))
+            ev = _timed(tag)
+            if ev is not None:
+                EXEC_FRAC[tag] = 0.0
+                EXEC_FP16[tag] = 3.0
+            launch(amax, nxt, clamped)
+            _done(ev)
+            return gw
+    # fp32 kernels.  A routed split-fp16 site (H2_TAIL_MODE) takes the DIRECT form: the transposed-Winograd transforms add and
+    # subtract neighbouring products before the reduction, which on two heavy-tailed operands costs the small half of the gradient
+    # what the split format does (log-normal K = 3: 2.3e-4 small-half rel-L2 through nef_conv_bwd_weight_wino4, 7.8e-7 for torch's
+    # fp32); bench.py sees its launches under their own tag ("f32" in the extra element).  pro_mode bit 2 (the polyphase weight
+    # gradient's window continued with x'[0] / x'[T-1]): the zero-padded fp32 gradient + the row-end products of `xedge`
+    # (nef_bwd_weight_clamp_ends).
+    extra = ("up" if pm0 & 2 else "") + (("pw" if pm0 & 4 else "") + "f32" if routed else "")
+    if routed:
+        wino = False
+    clamp = bool(pm0 & 4)
+    if clamp:
+        if xedge is None:
+            raise _lib.NefLibraryError("conv_bwd_weight: pro_mode bit 2 on the fp32 kernels needs `xedge`")
+        pro = (pm0 & 3, pro[1], pro[2], pro[3]) if pm0 & 3 else None
+        pm0 = pm0 & 3
     n = L.nef_conv_bwd_weight_ws_bytes(B, T, G, Cig, Cog, K)
     if n == 0:
         raise _lib.NefLibraryError(f"conv_bwd_weight: unsupported shape Cig={Cig} Cog={Cog} K={K}")
     ws = workspace(n, xv.t.device)
     sc, sc_bs, sc_gs = (None, 0, 0) if in_scale is None else (_p(in_scale[0]), in_scale[1], in_scale[2])
-    tag = ("conv_bwd_weight", K, G, Cig, Cog, B, T) + (("up",) if pm0 & 2 else ())
+    tag = ("conv_bwd_weight", K, G, Cig, Cog, B, T) + ((extra,) if extra else ())
     ev = _timed(tag)
     if wino is None:
         wino = (WINOGRAD and ((K == 3 and WINO_BW4) or (K == 7 and WINO_BW7)) and T % 2 == 0 and T >= 64
@@ -956,9 +1038,19 @@ def conv_bwd_weight(xv, gyv, K, in_scale=None, pro=None, wino=None, site=None, h
     else:
         _lib.check(L.nef_conv_bwd_weight(xv.ptr, xv.bs, xv.gs, sc, sc_bs, sc_gs, gyv.ptr, gyv.bs, gyv.gs, _p(gw), _p(ws),
                                          n, B, T, G, Cig, Cog, K, _stream()), "nef_conv_bwd_weight")
+    if clamp:
+        assert K == 3 and in_scale is None and tuple(xedge.shape) == (B, G * Cig, 2)
+        _lib.check(L.nef_bwd_weight_clamp_ends(_p(xedge), gyv.ptr, gyv.bs, gyv.gs, _p(gw), B, T, G, Cig, Cog, _stream()),
+                   "nef_bwd_weight_clamp_ends")
     if ev is not None:
         ev.record()
     return gw
+
+
+def _tail_mode():
+    if H2_TAIL_MODE not in H2_TAIL_MODES:
+        raise ValueError(f"ops.H2_TAIL_MODE={H2_TAIL_MODE!r}: expected one of {H2_TAIL_MODES}")
+    return H2_TAIL_MODE
 
 
 def chan_sum(x):

@@ -256,11 +256,15 @@ class Solver:
         blocking in their next collective."""
         clamped, skipped = parallel.sum_counts([ops.h2_clamped(), ops.h2_skipped()], self.device)
         ops.h2_rebase(self.device)       # clamps of this (test / val) phase are not charged to the next train step's taint word
-        tails = ops.h2_tail_sites()
-        if tails:      # (per rank: a warning only)
+        tails, moved = ops.h2_tail_sites(), ops.h2_fallback_sites()
+        if tails and ops.H2_TAIL_MODE == 'fp32':      # (per rank: a report only)
+            print('NOTE: {} split-fp16 call site(s) measured a heavy-tailed operand (more than {:.0%} of its nonzero elements below 2^-11 of '
+                  'its largest); {} weight-gradient site(s) of them now run on the fp32 kernels (NEF_H2_TAIL=fp32), the forward / '
+                  'backward-data ones keep the split kernels'.format(tails, ops.H2_TAIL_FRAC, moved))
+        elif tails:
             print('WARNING: {} split-fp16 call site(s) measured an operand with more than {:.0%} of its nonzero elements below 2^-11 of its '
-                  'largest: practically the whole tensor is outside the format\'s full-precision window (DESIGN.md 3.0); NEF_H2=0 runs the '
-                  'fp32 kernels'.format(tails, ops.H2_TAIL_FRAC))
+                  'largest: practically the whole tensor is outside the format\'s full-precision window (DESIGN.md 3.0); NEF_H2_TAIL=fp32 '
+                  'runs those weight-gradient sites on the fp32 kernels, NEF_H2=0 every conv'.format(tails, ops.H2_TAIL_FRAC))
         if not clamped and not skipped:
             return
         msg = ('{} waves of split-fp16 conv launches met an operand outside fp16\'s range in this {} phase (non-finite data; finite '

@@ -24,8 +24,9 @@ class CheckPointer:
             data['scheduler'] = self.scheduler.state_dict()
         core = getattr(self.model, 'module', self.model)
         if hasattr(core, 'h2_state'):
-            # beyond the reference's file (checkpointer.py:24-36): the operand magnitudes of the split-fp16 call sites, so that a resumed
-            # run is bit-identical to the uninterrupted one (a reference-side loader ignores the extra key)
+            # beyond the reference's file (checkpointer.py:24-36): the operand magnitudes of the split-fp16 call sites and the routes of
+            # the weight-gradient sites (blob version 2; load also takes version 1), so that a resumed run is bit-identical to the
+            # uninterrupted one (a reference-side loader ignores the extra key)
             data['h2_state'] = core.h2_state()
         data.update(kwargs)
         save_file = os.path.join(self.save_dir, '{}.pkl'.format(name))

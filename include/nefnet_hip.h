@@ -34,7 +34,7 @@ extern "C" {
 typedef void* nef_stream_t;
 
 /* ABI version of this header; bumped on any signature change. */
-int nef_abi_version(void);   /* 19 (+ nef_adam, an addition only; the kernel-form option entry points of 16 and nef_upsample2_aff_fwd are gone; + nef_debug_spin_us); 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + kernel-form option entry points); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + nef_conv_bwd_weight_h2); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, nef_conv_bwd_weight_wino4 covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
+int nef_abi_version(void);   /* 19 (+ nef_adam, nef_h2_tail_census, nef_bwd_weight_clamp_ends: additions only; the kernel-form option entry points of 16 and nef_upsample2_aff_fwd are gone; + nef_debug_spin_us); 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + kernel-form option entry points); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + nef_conv_bwd_weight_h2); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, nef_conv_bwd_weight_wino4 covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
 
 /* Diagnostics: `wgs` workgroups busy for `us` microseconds on `stream` (a stand-in for a collective's time on the chip:
  * parallel.DryCollective, bench.py --dry-collective).  0 <= us <= 50000, 1 <= wgs <= 64. */
@@ -246,6 +246,37 @@ int nef_conv_bwd_weight_h2(const float* x, int64_t x_bs, int64_t x_gs, const flo
                            int64_t gy_gs, float* gw, void* ws, size_t ws_bytes, int B, int T, int G, int Cin_g, int Cout_g, int K,
                            float x_scale, float gy_scale, const float* x_amax, const float* gy_amax, float* x_amax_next,
                            float* gy_amax_next, int32_t* clamped, nef_stream_t stream);
+
+/* Heavy-tail census of one split-fp16 operand (ops._note_tail, once per call site, at its measuring launch; no counterpart in the
+ * reference, whose fp32 convs keep every element's bits).  The operand is described as the launch reads it: the view
+ * x[b][g][c][t] at x + b x_bs + g x_gs + c T + t; pro_mode bit 0 applies the affine + ReLU prologue max(fma(x, a, b), 0), a / b
+ * [pass = b / pro_Bp][g Cg + c]; in_scale (NULL or [b sc_bs + g sc_gs + c]) multiplies after it.  With the x2 upsampling bit (2)
+ * the view is the half-resolution input and its values are counted (the interpolated ones are blends of them), while `amax` is the
+ * interpolated operand's, which can be smaller than the largest half-resolution value (v / amax may exceed 1: no count changes);
+ * bits 2 / 3 add no values.  `amax`: device word with the operand's largest magnitude (the measuring launch's slot).  Counted: nonzero elements, and
+ * those below window x amax; energies: the sums of (v / amax)^2 over both sets (fp32 per wave and row, fp64 across rows).  flag =
+ * (n_small / n_nonzero > frac).  Two launches (block partials in ws, one fixed-order combine): nothing synchronises, results are
+ * bitwise reproducible.  site_flag: NULL, or a device word set to 1 when flag is; tail_stat: NULL, or two device words that keep
+ * the largest count / energy fraction seen.  ws: nef_h2_tail_census_ws_bytes(B, G, Cg) bytes. */
+typedef struct nef_h2_tail_census_out {
+    uint64_t n_nonzero, n_small;
+    double e_small, e_total;
+    float frac_count, frac_energy;
+    int32_t flag, reserved;
+} nef_h2_tail_census_out;
+size_t nef_h2_tail_census_ws_bytes(int B, int G, int Cg);
+int nef_h2_tail_census(const float* x, int64_t x_bs, int64_t x_gs, int B, int G, int Cg, int T, const float* in_scale, int64_t sc_bs,
+                       int64_t sc_gs, const float* pro_a, const float* pro_b, int pro_mode, int pro_Bp, const float* amax, float window,
+                       float frac, void* ws, size_t ws_bytes, nef_h2_tail_census_out* out, int32_t* site_flag, float* tail_stat,
+                       nef_stream_t stream);
+/* gw [G Cout_g][Cin_g][3] += the row-end terms by which a K = 3 weight gradient over a window continued with x'[0] / x'[T-1] at both
+ * row ends (nef_conv_bwd_weight_h2 pro_mode bit 2) differs from the zero-padded one: gw[r][ci][0] += sum_b gy[b][r][0] xedge[b][ci][0],
+ * gw[r][ci][2] += sum_b gy[b][r][T-1] xedge[b][ci][1]; xedge [B][G Cin_g][2] = x' (the prologue's output) at both row ends, as
+ * nef_poly_fwd_edge writes it.  After an fp32 weight gradient (nef_conv_bwd_weight / _pro) with pro_mode & 1 this gives the polyphase
+ * phase-weight gradient that nef_poly_wgrad_fold takes (the fp32 route of a heavy-tailed site).  Cout_g % 16 == 0; samples summed
+ * in order, no atomics. */
+int nef_bwd_weight_clamp_ends(const float* xedge, const float* gy, int64_t gy_bs, int64_t gy_gs, float* gw, int B, int T, int G,
+                              int Cin_g, int Cout_g, nef_stream_t stream);
 
 /* out[c] = sum_{b,t} x[b][c][t] (bias gradients).  ws: nef_chan_sum_ws_bytes(C). */
 size_t nef_chan_sum_ws_bytes(int C);
