@@ -133,6 +133,8 @@ SIGNATURES = {
     "nef_loss_bwd": (i32, [p, p, p, p, p, p, p, p, i64, f32, f32, f32, i32, i32, p]),
     "nef_sgd_momentum": (i32, [p, p, p, i64, f32, f32, f32, i32, p, p, p, p]),
     "nef_adam": (i32, [p, p, p, p, i64, f32, C.c_double, C.c_double, f32, f32, f32, p, p, p, p, p]),
+    "nef_grad_clip_ws_bytes": (sz, []),
+    "nef_grad_clip": (i32, [p, i64, f32, f32, p, p, p, sz, p]),
     "nef_h2_taint": (i32, [p, p, p, p]),
     "nef_amax_roll": (i32, [p, p, i32, f32, f32, i32, p]),
     "nef_step_words": (i32, [p, p, i32, i32, i64, p]),

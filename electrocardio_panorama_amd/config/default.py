@@ -46,6 +46,10 @@ _DEFAULTS = {
         # qualifies (plain Model_nefnet train path, FusedSGD with one parameter group, no DATA.noise, per-view host lists not
         # wanted: Solver._graphed_step; rounds 1-3 replayed launch-bound shapes only); False = always issue eagerly; True = as auto
         "graph": None,
+        # global gradient-norm clipping on the device (ops.grad_clip: torch.nn.utils.clip_grad_norm_ semantics on the mean gradient,
+        # in the eager and the graphed step): 0 = off (no launch, no allocation); inf = measure and report the norm, never scale;
+        # a step whose norm is not finite is skipped
+        "clip_grad_norm": 0.0,
     },
 }
 

@@ -1325,6 +1325,74 @@ __global__ void adam_step_kernel(float* step, const float* __restrict__ skip) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// torch.nn.utils.clip_grad_norm_(norm_type=2) over the flat gradient buffer            (no counterpart in the reference)
+// ------------------------------------------------------------------------------------------------
+// Three launches: partial sums of g^2 (fp64, a grid that depends on n alone, so the same buffer gives the same bits eagerly, under
+// replay and on every rank), a one-block finish (norm, coefficient, stats, taint), and the scale pass.  Both passes over g split it
+// the same way: `head` scalar elements up to the first 16-byte boundary, n4 dwordx4 elements, the scalar rest.
+constexpr int CLIP_BLOCKS = 2048;      // 256 CUs x 8 blocks: the cap of a memory-bound grid; 16 KiB of partials
+
+static inline int clip_head(const float* g, int64_t n) {
+    const int head = (int)((4 - (((uintptr_t)g >> 2) & 3)) & 3);
+    return (int64_t)head < n ? head : (int)n;
+}
+static inline int clip_grid(int64_t n) {
+    const int64_t b = nef_cdiv(nef_cdiv(n, 4), 256);
+    return (int)(b < 1 ? 1 : (b > CLIP_BLOCKS ? CLIP_BLOCKS : b));
+}
+
+__global__ __launch_bounds__(256) void clip_partial(const float* __restrict__ g, int64_t n, int head, double* __restrict__ part) {
+    __shared__ double sm[4];
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+    const int64_t n4 = (n - head) >> 2, rest = head + 4 * n4;
+    const nef_f32x4* __restrict__ g4 = (const nef_f32x4*)(g + head);
+    double s = 0.0;
+    for (int64_t i = gid; i < n4; i += stride) {
+        const nef_f32x4 v = g4[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s += (double)v[e] * (double)v[e];
+    }
+    if (gid < head) s += (double)g[gid] * (double)g[gid];
+    if (rest + gid < n) s += (double)g[rest + gid] * (double)g[rest + gid];
+    s = nef_block_sum_d(s, sm);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(256) void clip_final(const double* __restrict__ part, int nblk, float max_norm, float gscale,
+                                                  float* __restrict__ taint, float* __restrict__ stats) {
+    __shared__ double sm[4];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nblk; i += 256) s += part[i];
+    s = nef_block_sum_d(s, sm);
+    if (threadIdx.x != 0) return;
+    const float total = (float)((double)gscale * sqrt(s));
+    const bool finite = isfinite(total);
+    const bool tainted = taint && taint[0] > 0.f;        // the update behind this call skips the step anyway
+    // torch's order: max_norm / (total + 1e-6), clamped at 1.  stats[1] is what the scale pass applies: 1 when g is left as it is.
+    float coef = 1.f;
+    if (finite && !tainted) coef = fminf(1.f, max_norm / (total + 1e-6f));
+    stats[0] = total;
+    stats[1] = coef;
+    if (tainted) return;
+    if (coef < 1.f) stats[2] += 1.f;
+    if (!finite) {
+        stats[3] += 1.f;
+        if (taint) taint[0] += 1.f;
+    }
+}
+
+__global__ __launch_bounds__(256) void clip_scale(float* __restrict__ g, int64_t n, int head, const float* __restrict__ stats) {
+    const float coef = stats[1];
+    if (coef == 1.f) return;
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+    const int64_t n4 = (n - head) >> 2, rest = head + 4 * n4;
+    nef_f32x4* __restrict__ g4 = (nef_f32x4*)(g + head);
+    for (int64_t i = gid; i < n4; i += stride) g4[i] = g4[i] * coef;
+    if (gid < head) g[gid] *= coef;
+    if (rest + gid < n) g[rest + gid] *= coef;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Round 6: the last torch elementwise kernels of the train step, as one launch each.
 // amax_roll: ops.amax_roll's follow-up rule on the split-fp16 site table (was ~10 ATen launches: compares, ors, where, fill).
 __global__ __launch_bounds__(256) void amax_roll_kernel(float* __restrict__ cur, float* __restrict__ nxt, int n, float up, float down,
@@ -2364,6 +2432,21 @@ int nef_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, 
                            eps, weight_decay, gscale, step, skip_if_positive, skipped, lr_dev);
     // stream order: every block of the update has read the step word before this launch advances it
     hipLaunchKernelGGL(adam_step_kernel, dim3(1), dim3(1), 0, NEF_ST, step, skip_if_positive);
+    return nef_launch_status();
+}
+
+size_t nef_grad_clip_ws_bytes(void) { return (size_t)CLIP_BLOCKS * sizeof(double); }
+
+int nef_grad_clip(float* g, int64_t n, float max_norm, float gscale, float* taint, float* stats, void* ws, size_t ws_bytes,
+                  nef_stream_t stream) {
+    NEF_ENTER();
+    NEF_REQUIRE(g && stats && ws, NEF_E_NULL);
+    NEF_REQUIRE(n > 0 && max_norm > 0.f, NEF_E_SHAPE);       // (a NaN max_norm fails the comparison too; +inf passes)
+    NEF_REQUIRE(ws_bytes >= nef_grad_clip_ws_bytes(), NEF_E_WORKSPACE);
+    const int head = clip_head(g, n), nblk = clip_grid(n);
+    hipLaunchKernelGGL(clip_partial, dim3(nblk), dim3(256), 0, NEF_ST, g, n, head, (double*)ws);
+    hipLaunchKernelGGL(clip_final, dim3(1), dim3(256), 0, NEF_ST, (const double*)ws, nblk, max_norm, gscale, taint, stats);
+    hipLaunchKernelGGL(clip_scale, dim3(nblk), dim3(256), 0, NEF_ST, g, n, head, (const float*)stats);
     return nef_launch_status();
 }
 

@@ -42,7 +42,6 @@ class GraphedTrainStep:
                 raise NotImplementedError("the graphed step drives a fused optimiser (FusedSGD, FusedAdam) with one parameter group")
             g0 = optimizer.param_groups[0]
             lr, momentum = g0["lr"], g0.get("momentum", momentum)
-            self._captured = optimizer._captured_scalars(g0)     # frozen into the captured update launch: a change re-captures
         self.lr = float(cfg.SOLVER.lr if lr is None else lr)
         self.mu = float(momentum)
         self.factors = tuple(float(f) for f in cfg.SOLVER.loss_factor)
@@ -63,6 +62,8 @@ class GraphedTrainStep:
         self.dp = self.world > 1 or (dist.is_available() and dist.is_initialized() and _par._hook("NEF_DIST_FORCE") == "1")
         # data parallel: capture the step as two graphs with the early gradient bucket's all-reduce between them (_capture_split)
         self.split_capture = _env.get("NEF_GRAPH_SPLIT", "1") != "0"
+        if optimizer is not None:
+            self._captured = self._frozen()     # frozen into the captured launches: a change re-captures
         # bench.py --dry-collective: a parallel.DryCollective standing in for dist.all_reduce on a one-GPU box (set `dp` with it)
         self.dry = None
 
@@ -122,6 +123,18 @@ class GraphedTrainStep:
             g3 = ops.loss_bwd(o, p_, l_, self.target, None, self.factors, self.reg_l2, self.use_mask)
             return engine.backward(P, sv, g3)
 
+    def _frozen(self):
+        """The optimiser's scalars that the captured launches freeze: those of its update and -- single process, where the clip launches
+        sit inside the graph -- its max_grad_norm (data parallel they are issued behind the all-reduces, outside the graphs)."""
+        opt = self.optimizer
+        return opt._captured_scalars(opt.param_groups[0]) + (() if self.dp else (float(opt.max_grad_norm),))
+
+    def _clip(self):
+        """The optimiser's global gradient-norm clipping (its own clip_stats), between the summed gradients and the update; the stepper
+        with private buffers does not clip."""
+        if self.optimizer is not None and self.optimizer.max_grad_norm > 0:
+            self.optimizer._clip(self.opt_flat, 1.0 / self.world)
+
     def _update(self):
         # the learning rate travels through a device word (a captured launch freezes its scalars): a scheduler step updates the word,
         # nothing is re-captured
@@ -137,6 +150,7 @@ class GraphedTrainStep:
         ops.flatten_into([grads[k] for k in self.live], self.flat_g)
         ops.h2_taint(self.flat_g_all[:1])      # this step's clamped split-fp16 launches: the update is skipped (on every rank)
         if not self.dp:
+            self._clip()
             self._update()
 
     def _capture_split(self):
@@ -229,6 +243,8 @@ class GraphedTrainStep:
         self._flatten([k for k, _ in self.model.named_parameters() if grads.get(k) is not None])
         for k, v in self.model.named_buffers():
             v.copy_(saved[k])
+        if self.optimizer is not None and self.optimizer.max_grad_norm > 0:
+            self.optimizer._clip_ready(dev)      # the stats words exist before the capture: a tensor made inside it would belong to the graph
         torch.cuda.synchronize(dev)
         graph = torch.cuda.CUDAGraph()
         saved = {k: v.clone() for k, v in self.model.named_buffers()}
@@ -314,8 +330,8 @@ class GraphedTrainStep:
         self.model._check_inputs(data, rois)       # what Model_nefnet.forward rejects (float rois, L % 4, CPU tensors) is rejected here too
         if self.optimizer is not None:
             g = self.optimizer.param_groups[0]
-            cap = self.optimizer._captured_scalars(g)
-            if cap != self._captured:                          # (momentum; Adam's betas / eps / weight_decay are captured scalars: re-capture)
+            cap = self._frozen()
+            if cap != self._captured:                          # (momentum; Adam's betas / eps / weight_decay; max_grad_norm: re-capture)
                 self._captured = cap
                 self.mu = float(g.get("momentum", self.mu))
                 self.slots.clear()
@@ -365,5 +381,6 @@ class GraphedTrainStep:
         if ev is not None:
             ev[1].record()
             parallel.TIMING.append(ev)
+        self._clip()
         self._update()
         return self.losses

@@ -1743,6 +1743,25 @@ def adam(p, g, m, v, step, lr, beta1, beta2, eps, weight_decay, gscale, skip=Non
     _done(ev)
 
 
+def grad_clip(g, max_norm, gscale, stats, taint=None):
+    """torch.nn.utils.clip_grad_norm_(max_norm, norm_type=2) on the averaged flat gradient gscale * g, in place on `g` (which stays the
+    un-averaged sum: the update behind it applies gscale).  `stats`: 4 fp32 device words -- [0] the norm and [1] the coefficient of this
+    call, [2] += 1 when it clipped, [3] += 1 when the norm was not finite.  A non-finite norm leaves g alone and adds 1 to `taint` (the
+    word h2_taint wrote: sgd_momentum / adam(skip=taint) then skip the step, h2_skipped() counts it).  Three stream-ordered launches,
+    capturable, nothing read by the host."""
+    L = _lib.load()
+    _chk(stats)
+    assert g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and stats.numel() == 4
+    if taint is not None:
+        _chk(taint)
+    n = L.nef_grad_clip_ws_bytes()
+    ws = workspace(n, g.device)
+    ev = _hbm("grad_clip", g, g, g)
+    _lib.check(L.nef_grad_clip(_p(g), g.numel(), float(max_norm), float(gscale), _p(taint), _p(stats), _p(ws), n, _stream()),
+               "nef_grad_clip")
+    _done(ev)
+
+
 # ------------------------------------------------------------------ half-precision panorama decoder (pano_h.hip)
 def pano_h_from_f32(x):
     """fp32 [B,C,T] -> fp16 [B,T,C] (time-major)."""

@@ -29,9 +29,15 @@ class _FusedFlat(torch.optim.Optimizer):
     BatchNorm running statistics its forward pass already updated are NOT rolled back (DESIGN.md 3.0 "Range")."""
     _SLOTS = ()
 
-    def __init__(self, params, defaults):
+    def __init__(self, params, defaults, max_grad_norm=0.0):
         super().__init__(params, defaults)
         self._flat = {}      # group index -> dict(ids, params, p, g_all, g, one flat buffer per _SLOTS key)
+        # global gradient-norm clipping (ops.grad_clip on the mean gradient; 0 = off, inf = measure only).  An attribute, NOT a
+        # param_groups key: the state dict stays in torch's format
+        if not float(max_grad_norm) >= 0.0:      # (NaN fails the comparison too)
+            raise ValueError(f"Invalid max_grad_norm value: {max_grad_norm}")
+        self.max_grad_norm = float(max_grad_norm)
+        self._clip_stats = None      # 4 device words [norm, coefficient, steps clipped, steps with a non-finite norm]: made at first use
         parallel.enable_early_reduce()      # this optimiser consumes engine.backward's early gradient bucket (see _reduce)
 
     def _build(self, gi, live):
@@ -66,6 +72,21 @@ class _FusedFlat(torch.optim.Optimizer):
             self._build(gi, live)
             fl = self._flat[gi]
         return fl
+
+    @property
+    def clip_stats(self):
+        """The 4 device words ops.grad_clip writes for this optimiser; None until a step has clipped (clipping off: never made)."""
+        return self._clip_stats
+
+    def _clip_ready(self, device):
+        if self._clip_stats is None:
+            self._clip_stats = torch.zeros(4, device=device, dtype=torch.float32)
+
+    def _clip(self, fl, gscale):
+        """Clip the global norm of the flat gradients `fl["g"]` (summed over the ranks: the norm is that of the mean, the same on every
+        rank) in front of `_device_update`; a non-finite norm taints the step."""
+        self._clip_ready(fl["g"].device)
+        ops.grad_clip(fl["g"], self.max_grad_norm, gscale, self._clip_stats, taint=fl["g_all"][:1])
 
     def load_state_dict(self, state_dict):
         """The loaded state replaces the flat buffers: drop the flat views so the next step() re-imports them."""
@@ -133,6 +154,9 @@ class _FusedFlat(torch.optim.Optimizer):
     def step(self, closure=None):
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         taint = None           # ONE taint word per step: h2_taint advances its mark, so later groups reuse the first group's (summed) word
+        clip = self.max_grad_norm > 0
+        if clip and sum(any(p.grad is not None for p in g["params"]) for g in self.param_groups) > 1:
+            raise NotImplementedError("max_grad_norm clips the global norm of ONE parameter group")
         for gi, group in enumerate(self.param_groups):
             live = [p for p in group["params"] if p.grad is not None]      # torch skips grad=None
             if not live:
@@ -147,6 +171,8 @@ class _FusedFlat(torch.optim.Optimizer):
                 taint = fl["g_all"][:1]
             else:
                 fl["g_all"][:1].copy_(taint)       # (already summed over the ranks)
+            if clip:
+                self._clip(fl, 1.0 / world)
             self._device_update(fl, group, 1.0 / world, skip=fl["g_all"][:1])      # a tainted step is skipped on the device
         # the update wrote the parameters through raw pointers (no version bump): an operand pre-packed from the old weights by a forward
         # pass that no backward consumed (ops.pack_many) must not be served to the next one
@@ -158,8 +184,8 @@ class FusedSGD(_FusedFlat):
     """torch.optim.SGD(lr, momentum) semantics, one nef_sgd_momentum launch per parameter group."""
     _SLOTS = (("buf", "momentum_buffer"),)
 
-    def __init__(self, params, lr, momentum=0.9):
-        super().__init__(params, dict(lr=lr, momentum=momentum))
+    def __init__(self, params, lr, momentum=0.9, max_grad_norm=0.0):
+        super().__init__(params, dict(lr=lr, momentum=momentum), max_grad_norm=max_grad_norm)
 
     def _captured_scalars(self, group):
         return (float(group["momentum"]),)
@@ -180,7 +206,8 @@ class FusedAdam(_FusedFlat):
     not kept current."""
     _SLOTS = (("m", "exp_avg"), ("v", "exp_avg_sq"))
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, maximize=False):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, maximize=False,
+                 max_grad_norm=0.0):
         if amsgrad or maximize:
             raise NotImplementedError("FusedAdam implements amsgrad=False, maximize=False")
         if not 0.0 <= lr:
@@ -192,7 +219,7 @@ class FusedAdam(_FusedFlat):
         if not 0.0 <= weight_decay:
             raise ValueError(f"Invalid weight_decay value: {weight_decay}")
         super().__init__(params, dict(lr=lr, betas=(float(betas[0]), float(betas[1])), eps=eps, weight_decay=weight_decay,
-                                      amsgrad=False, maximize=False))
+                                      amsgrad=False, maximize=False), max_grad_norm=max_grad_norm)
 
     @staticmethod
     def _check_group(group):
@@ -267,10 +294,11 @@ class DataParallelAdam(Adam):
 
 def get_optimizer(cfg, model_params):
     optim_name = cfg.SOLVER.optim
+    clip = float(cfg.SOLVER.get('clip_grad_norm', 0.0))      # (.get: configs written before the key existed)
     if optim_name == 'adam':
-        return FusedAdam(model_params, lr=cfg.SOLVER.lr)
+        return FusedAdam(model_params, lr=cfg.SOLVER.lr, max_grad_norm=clip)
     elif optim_name == 'sgd':
-        return FusedSGD(model_params, lr=cfg.SOLVER.lr, momentum=0.9)
+        return FusedSGD(model_params, lr=cfg.SOLVER.lr, momentum=0.9, max_grad_norm=clip)
 
 
 def get_lr_scheduler(cfg, optim=None):

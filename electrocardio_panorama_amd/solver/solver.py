@@ -170,6 +170,12 @@ class Solver:
                         scalars += [float(np.mean(single[:, i, 0])), float(np.mean(single[:, i, 1]))]
                 msg += ', test_loss: {}'.format(float(te[0]))
                 msg += '\npsnr_gen: {}, psnr_reg: {}, ssim_gen:{}, ssim_reg:{}'.format(psnr_gen, psnr_reg, ssim_gen, ssim_reg)
+            if self.last_grad_norms:              # SOLVER.clip_grad_norm is on
+                norms = [t for t, _ in self.last_grad_norms if np.isfinite(t)]
+                scalars.append(float(np.mean(norms)) if norms else float('nan'))
+                names.append('train_grad_norm')
+                msg += '\ngrad_norm: {} (max_norm {}): {} of {} steps clipped, {} skipped for a non-finite norm'.format(
+                    scalars[-1], optimizer.max_grad_norm, self.last_clip_counts[0], len(self.last_grad_norms), self.last_clip_counts[1])
             if self.summary_writer is not None:
                 self.write_tensorboardx(scalars, names, epoch)
             print(msg)
@@ -288,6 +294,10 @@ class Solver:
         keep = self.collect_views if collect_views is None else bool(collect_views)
         losses_s, pred_s, gt_s, in_s, rest_s, rois_s, psnr_s, ssim_s = (_HostSink() for _ in range(8))
         gen_num, whole = self._gen_num() if phase == 'test' else (0, True)
+        # gradient-norm clipping (SOLVER.clip_grad_norm): [norm, coefficient] of every train step travel like the losses
+        clip_s = _HostSink() if phase == 'train' and getattr(optim, 'max_grad_norm', 0.0) > 0 else None
+        # the optimiser's counters (steps clipped, steps with a non-finite norm) before this epoch: nothing is in flight here
+        clip_0 = optim.clip_stats[2:].tolist() if clip_s is not None and optim.clip_stats is not None else [0.0, 0.0]
         for meta in dl:
             source_data, rois, input_theta, target_view, target_theta, noise = self._to_device(meta)
             rest_theta = torch.as_tensor(meta['rest_theta']).to(self.device) if 'rest_theta' in meta else None
@@ -322,6 +332,8 @@ class Solver:
                 if keep:
                     pred_s.add(rest_out)                           # solver.py:182
                     rest_s.add(rest_view)
+            if clip_s is not None and optim.clip_stats is not None:
+                clip_s.add(optim.clip_stats[:2])
             if keep:
                 gt_s.add(target_view.squeeze(1))
                 in_s.add(source_data)
@@ -329,6 +341,12 @@ class Solver:
         losses = [a.tolist() for a in losses_s.arrays()]
         self._check_h2_range(phase, optim)       # same cadence as the loss read-back above: the device has been waited for anyway
         if phase == 'train':
+            # [norm, coefficient] of every step and this epoch's (steps clipped, steps skipped for a non-finite norm); clipping off: empty
+            self.last_grad_norms, self.last_clip_counts = [], (0, 0)
+            if clip_s is not None and optim.clip_stats is not None:
+                self.last_grad_norms = [a.tolist() for a in clip_s.arrays()]
+                clip_1 = optim.clip_stats[2:].tolist()
+                self.last_clip_counts = (int(clip_1[0] - clip_0[0]), int(clip_1[1] - clip_0[1]))
             return losses, gt_s.rows(), pred_s.rows(), in_s.rows(), [], rois_s.rows()
         mertics_all, mertics_gen_singlelead = [], []
         for ps, ss in zip(psnr_s.arrays(), ssim_s.arrays()):

@@ -511,6 +511,23 @@ int nef_sgd_momentum(float* p, const float* g, float* buf, int64_t n, float lr, 
 int nef_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2, float eps,
              float weight_decay, float gscale, float* step /* device word: completed updates */, const float* skip_if_positive,
              int32_t* skipped, const float* lr_dev, nef_stream_t stream);
+/* Global gradient-norm clipping over a flat buffer: torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2) on the averaged
+ * gradient gscale * g (no counterpart in the reference).  total = gscale * sqrt(sum g[i]^2), coef = min(1, max_norm / (total + 1e-6)),
+ * g[i] *= coef; g stays the un-averaged sum, so the update launch behind this call still applies gscale.  The sum is deterministic:
+ * fp64 partial sums over a grid that depends on n alone and a one-block finish, no atomics -- the same buffer gives the same bits
+ * eagerly, under hipGraph replay and on every rank.  Three launches; the scale pass takes 16-byte accesses from the first 16-byte
+ * boundary of g on and returns without touching g when coef == 1.
+ *   stats[0] = total of this call; stats[1] = the coefficient applied by this call (1 when g is left as it is);
+ *   stats[2] += 1 when coef < 1; stats[3] += 1 when total is not finite.
+ * A non-finite total leaves g as it is and, if `taint` is given, adds 1 to taint[0]: nef_sgd_momentum / nef_adam behind this call
+ * (skip_if_positive = taint) then skip the step as they do for a tainted split-fp16 step.  This is a deliberate difference from
+ * torch, whose clip_grad_norm_ multiplies by a NaN coefficient and so writes NaN into every parameter.  taint[0] > 0 on entry (the
+ * step is skipped anyway): g, stats[2] and stats[3] stay as they are.  max_norm = +inf is legal (the norm is measured, nothing is ever
+ * scaled); max_norm <= 0 or NaN returns NEF_E_SHAPE.  Capturable: nothing is read by the host, nothing is allocated. */
+size_t nef_grad_clip_ws_bytes(void);
+int nef_grad_clip(float* g, int64_t n, float max_norm, float gscale,
+                  float* taint /* NULL, or the device word in front of the flat gradients (nef_h2_taint's output) */,
+                  float* stats /* 4 device floats */, void* ws, size_t ws_bytes, nef_stream_t stream);
 /* The split-fp16 convolutions (conv args wino = 3, nef_conv_bwd_weight_h2) count the waves that had to clamp an operand at fp16's
  * range in a device counter (x_clamped); such a launch's results are wrong.  nef_h2_taint writes out[0] = (float)(*clamped_total -
  * *mark) -- the clamps since the previous call -- and sets *mark = *clamped_total: called once per train step behind the backward

@@ -1,6 +1,7 @@
 """Adam against SGD on the train step of BASELINE config 2 (B=256, 3 leads, L=5000), one GPU; prints one JSON line.
 
     python tools/bench_adam.py [--steps 10] [--warmup 3] [--reps 3] [--out profiles/adam_bench_line.json]
+    python tools/bench_adam.py --clip MAX_NORM [--parent-tree DIR] [--out profiles/clip_bench_line.json]
 
 Each measurement runs in a child process of its own under `timeout` (nothing more is started once one fails), `--reps` rounds of
 the three children; every figure is reported as [min, median, max] over the rounds:
@@ -10,7 +11,13 @@ the three children; every figure is reported as [min, median, max] over the roun
               update does in the train step; HIP events around each launch, median of 30 (seven fp32 streams per parameter = the
               algorithmic bytes).  The warm figure (50 back-to-back launches, the 115 MB working set cache-resident) is listed too;
   adam-eager  the eager step with DataParallelAdam (torch.optim.Adam: ATen kernels, no graph) -- the path 'adam' took before.
-Every child warms up before it times."""
+Every child warms up before it times.
+
+--clip MAX_NORM measures gradient-norm clipping instead: per round the graphed FusedSGD step with clipping off (sgd-graph) and with
+max_grad_norm = MAX_NORM (sgd-graph-clip: also the three nef_grad_clip launches alone on the flat gradient buffer, cold as above, with
+a max_norm that clips), and -- with --parent-tree DIR -- the sgd-graph child of DIR/tools/bench_adam.py, in the same rounds on the same
+device.  DIR is a checkout of the commit to compare against; its library must already be built (nothing is built here) and its
+tools/bench_adam.py must accept `--child sgd-graph --steps N --warmup W`."""
 import argparse
 import json
 import os
@@ -22,9 +29,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 MODES = {"sgd-graph": 900, "adam-graph": 900, "adam-eager": 1200}      # child -> its time limit (s)
+CLIP_MODES = {"sgd-graph": 900, "sgd-graph-clip": 900}
 
 
-def child(mode, steps, warmup, V=3, B=256, L=5000):
+def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0):
     import numpy as np
     import torch
     from electrocardio_panorama_amd import ops, synth
@@ -42,6 +50,8 @@ def child(mode, steps, warmup, V=3, B=256, L=5000):
     lossf = build_loss(cfg)
     if mode == "sgd-graph":
         optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9)
+    elif mode == "sgd-graph-clip":
+        optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9, max_grad_norm=clip)
     elif mode == "adam-graph":
         optim = FusedAdam(model.parameters(), lr=1e-3)
     else:
@@ -51,7 +61,7 @@ def child(mode, steps, warmup, V=3, B=256, L=5000):
                                                  ("data", "rois", "input_theta", "target_view", "target_theta"))
     tgt_view = tgt_view.unsqueeze(1)
     graphed = None
-    if mode.endswith("-graph"):
+    if "-graph" in mode:
         from electrocardio_panorama_amd.graph import GraphedTrainStep
         graphed = GraphedTrainStep(model, cfg, optimizer=optim)
 
@@ -100,6 +110,28 @@ def child(mode, steps, warmup, V=3, B=256, L=5000):
         ms = float(np.median([a.elapsed_time(b) for a, b in cold]))
         res.update(nef_adam_cold_ms=round(ms, 4), nef_adam_warm_ms=round(warm, 4), nef_adam_params=n,
                    nef_adam_cold_GBps=round(7 * 4 * n / (ms * 1e-3) / 1e9, 1))
+    if mode == "sgd-graph-clip":
+        total, coef, clipped, bad = optim.clip_stats.tolist()
+        g = optim._flat[0]["g"].clone()
+        g0, n = g.clone(), g.numel()
+        quarter = 0.25 * float(g0.double().norm().item())     # a quarter of this buffer's norm: the scale pass runs
+        assert quarter > 0 and quarter == quarter and quarter != float("inf"), quarter
+        stats = torch.zeros(4, device=dev)
+        flush = torch.empty(512 << 18, device=dev, dtype=torch.float32)        # 512 MiB
+        cold = []
+        for i in range(30):
+            g.copy_(g0)
+            flush.fill_(float(i))
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            ops.grad_clip(g, quarter, 1.0, stats)
+            b.record()
+            cold.append((a, b))
+        torch.cuda.synchronize(dev)
+        ms = float(np.median([a.elapsed_time(b) for a, b in cold]))
+        res.update(max_grad_norm=clip, last_norm=total, last_coef=coef, steps_clipped=int(clipped), steps_non_finite=int(bad),
+                   steps_run=steps + warmup, nef_grad_clip_cold_ms=round(ms, 4), nef_grad_clip_params=n,
+                   nef_grad_clip_launches_clipped=int(stats[2].item()))
     print("RESULT " + json.dumps(res), flush=True)
 
 
@@ -109,17 +141,30 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=3, help="rounds of the three children")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
-    ap.add_argument("--child", choices=sorted(MODES), default=None)
+    ap.add_argument("--clip", type=float, default=None, metavar="MAX_NORM", help="measure gradient-norm clipping (see above)")
+    ap.add_argument("--parent-tree", default=None, help="with --clip: a built checkout whose own sgd-graph child runs in every round")
+    ap.add_argument("--child", choices=sorted({**MODES, **CLIP_MODES}), default=None)
     args = ap.parse_args()
+    if args.child == "sgd-graph-clip" and not (args.clip is not None and args.clip > 0):
+        ap.error("--child sgd-graph-clip needs --clip MAX_NORM > 0")
+    if args.parent_tree and args.clip is None:
+        ap.error("--parent-tree goes with --clip")
     if args.child:
-        return child(args.child, args.steps if args.child != "adam-eager" else max(3, args.steps // 2), args.warmup)
-    results = {mode: [] for mode in MODES}
+        return child(args.child, args.steps if args.child != "adam-eager" else max(3, args.steps // 2), args.warmup,
+                     clip=args.clip or 0.0)
+    modes = dict(MODES)
+    if args.clip is not None:
+        modes = dict(CLIP_MODES, **({"parent": 900} if args.parent_tree else {}))
+    results = {mode: [] for mode in modes}
     for rnd in range(args.reps):
-        order = list(MODES) if rnd % 2 == 0 else list(reversed(MODES))       # no mode always runs first on a fresh box
+        order = list(modes) if rnd % 2 == 0 else list(reversed(modes))       # no mode always runs first on a fresh box
         for mode in order:
-            cmd = ["timeout", "-k", "10", str(MODES[mode]), sys.executable, os.path.abspath(__file__), "--child", mode,
-                   "--steps", str(args.steps), "--warmup", str(args.warmup)]
-            r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+            tree = os.path.abspath(args.parent_tree) if mode == "parent" else ROOT
+            cmd = ["timeout", "-k", "10", str(modes[mode]), sys.executable, os.path.join(tree, "tools", "bench_adam.py"), "--child",
+                   "sgd-graph" if mode == "parent" else mode, "--steps", str(args.steps), "--warmup", str(args.warmup)]
+            if mode == "sgd-graph-clip":
+                cmd += ["--clip", str(args.clip)]
+            r = subprocess.run(cmd, cwd=tree, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
             line = [x for x in r.stdout.splitlines() if x.startswith("RESULT ")]
             if r.returncode != 0 or not line:
                 sys.stderr.write(r.stdout[-3000:])
@@ -130,6 +175,26 @@ def main():
         v = sorted(x[key] for x in results[mode])
         return [v[0], v[len(v) // 2], v[-1]]
 
+    if args.clip is not None:
+        cg = results["sgd-graph-clip"]
+        out = {"metric": "ms per train step, graphed FusedSGD with and without gradient-norm clipping ([min, median, max] over rounds)",
+               "config": "BASELINE config 2: B=256, 3 leads, L=5000, one GPU, dropout on", "rounds": args.reps,
+               "max_grad_norm": args.clip, "sgd_graphed_clip_off_ms": spread("sgd-graph", "ms_per_step"),
+               "sgd_graphed_clip_on_ms": spread("sgd-graph-clip", "ms_per_step"),
+               "steps_clipped_of_run": [[x["steps_clipped"], x["steps_run"]] for x in cg],
+               "nef_grad_clip_cold_ms": spread("sgd-graph-clip", "nef_grad_clip_cold_ms"),
+               "nef_grad_clip_params": cg[0]["nef_grad_clip_params"],
+               "nef_grad_clip_note": "the three launches alone on the flat gradient buffer, every launch clipping (read, read + write); "
+                                     "cold = a 512 MiB buffer written before each call",
+               "steps": args.steps, "warmup": args.warmup}
+        if args.parent_tree:
+            out["parent_sgd_graphed_ms"] = spread("parent", "ms_per_step")
+        line = json.dumps(out)
+        print(line)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        return
     ag = results["adam-graph"]
     out = {"metric": "ms per train step, Adam vs SGD ([min, median, max] over rounds)",
            "config": "BASELINE config 2: B=256, 3 leads, L=5000, one GPU, dropout on", "rounds": args.reps,
