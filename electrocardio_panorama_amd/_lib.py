@@ -38,6 +38,17 @@ class ConvArgs(C.Structure):
     ]
 
 
+class BwwArgs(C.Structure):
+    """Mirror of `nef_bww_args` (include/nefnet_hip.h)."""
+    _fields_ = [
+        ("x", p), ("gy", p), ("gw", p), ("ws", p), ("in_scale", p), ("pro_a", p), ("pro_b", p),
+        ("x_amax", p), ("gy_amax", p), ("x_amax_next", p), ("gy_amax_next", p), ("clamped", p), ("ws_bytes", sz),
+        ("x_bs", i64), ("x_gs", i64), ("gy_bs", i64), ("gy_gs", i64), ("sc_bs", i64), ("sc_gs", i64),
+        ("B", i32), ("T", i32), ("G", i32), ("Cin_g", i32), ("Cout_g", i32), ("K", i32),
+        ("pro_mode", i32), ("pro_Bp", i32), ("form", i32), ("x_scale", f32), ("gy_scale", f32), ("reserved0", i32),
+    ]
+
+
 class PackDesc(C.Structure):
     """Mirror of `nef_pack_desc` (include/nefnet_hip.h)."""
     _fields_ = [("w", p), ("wp", p), ("G", i32), ("Cog", i32), ("Cig", i32), ("K", i32), ("transpose_flip", i32),
@@ -59,14 +70,9 @@ SIGNATURES = {
     "nef_pack_weight_h2_bytes": (sz, [i32, i32, i32, i32, i32]),
     "nef_conv_fwd": (i32, [C.POINTER(ConvArgs), p]),
     "nef_conv_args_bytes": (sz, []),
-    "nef_conv_bwd_weight_ws_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
-    "nef_conv_bwd_weight": (i32, [p, i64, i64, p, i64, i64, p, i64, i64, p, p, sz, i32, i32, i32, i32, i32, i32, p]),
-    "nef_conv_bwd_weight_pro": (i32, [p, i64, i64, p, p, i32, i32, p, i64, i64, p, p, sz, i32, i32, i32, i32, i32, i32, p]),
-    "nef_conv_bwd_weight_wino4": (i32, [p, i64, i64, p, i64, i64, p, p, i32, i32, p, i64, i64, p, p, sz, i32, i32, i32, i32, i32,
-                                        i32, p]),
-    "nef_conv_bwd_weight_h2_ws_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
-    "nef_conv_bwd_weight_h2": (i32, [p, i64, i64, p, i64, i64, p, p, i32, i32, p, i64, i64, p, p, sz, i32, i32, i32, i32, i32, i32,
-                               f32, f32, p, p, p, p, p, p]),
+    "nef_conv_bwd_weight_ws_bytes": (sz, [C.POINTER(BwwArgs)]),
+    "nef_conv_bwd_weight": (i32, [C.POINTER(BwwArgs), p]),
+    "nef_bww_args_bytes": (sz, []),
     "nef_h2_tail_census_ws_bytes": (sz, [i32, i32, i32]),
     "nef_h2_tail_census": (i32, [p, i64, i64, i32, i32, i32, i32, p, i64, i64, p, p, i32, i32, p, f32, f32, p, sz, p, p, p, p]),
     "nef_bwd_weight_clamp_ends": (i32, [p, p, i64, i64, p, i32, i32, i32, i32, i32, p]),
@@ -177,9 +183,12 @@ def load():
         fn = getattr(lib, name)        # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
-    if lib.nef_conv_args_bytes() != C.sizeof(ConvArgs):      # a stale .so next to a newer binding (or the reverse)
-        raise NefLibraryError(f"{LIB_PATH}: nef_conv_args is {lib.nef_conv_args_bytes()} bytes, the binding mirrors "
-                              f"{C.sizeof(ConvArgs)}; rebuild with `python -m electrocardio_panorama_amd.csrc.build`")
+    # a stale .so next to a newer binding (or the reverse)
+    for name, size, mirror in (("nef_conv_args", lib.nef_conv_args_bytes(), ConvArgs),
+                               ("nef_bww_args", lib.nef_bww_args_bytes(), BwwArgs)):
+        if size != C.sizeof(mirror):
+            raise NefLibraryError(f"{LIB_PATH}: {name} is {size} bytes, the binding mirrors {C.sizeof(mirror)}; rebuild with "
+                                  "`python -m electrocardio_panorama_amd.csrc.build`")
     _lib = lib
     return lib
 

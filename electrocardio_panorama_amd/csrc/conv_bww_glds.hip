@@ -425,9 +425,13 @@ __global__ __launch_bounds__(256, GL_OCC) void conv_bww_glds_kernel(
 }
 
 template <int K, bool AFF, int WINO, int NBUF, bool UP = false>
-int launch(const float* x, int64_t x_bs, int64_t x_gs, const float* gy, int64_t gy_bs, int64_t gy_gs, float* ws, int B, int T,
-           int G, int Cig, int Cog, const float* pro_a, const float* pro_b, int pro_Bp, int n_pass, int S_max, int fixed_S,
-           int* S_used, hipStream_t st) {
+int launch(const nef_bww_args& a, int S_max, int fixed_S, int* S_used, hipStream_t st) {
+    const int B = a.B, T = a.T, G = a.G, Cig = a.Cin_g, Cog = a.Cout_g;
+    // the prologue table (and its arguments) only with the affine bit
+    const float* pro_a = AFF ? a.pro_a : nullptr;
+    const float* pro_b = AFF ? a.pro_b : nullptr;
+    const int pro_Bp = AFF ? a.pro_Bp : 1;
+    const int n_pass = AFF ? (B + pro_Bp - 1) / pro_Bp : 0;
     constexpr int XCH = (((UP ? TW / 2 + 2 : TW + K - 1) + 3) / 4) | 1;
     constexpr size_t lds_tiles = (size_t)NBUF * (ROWS * GCH + ROWS * XCH) * 16;
     const size_t lds = lds_tiles + (AFF ? (size_t)n_pass * 128 * sizeof(float) : 0);
@@ -459,12 +463,12 @@ int launch(const float* x, int64_t x_bs, int64_t x_gs, const float* gy, int64_t 
         if (S < 1) S = 1;
     }
     *S_used = S;
-    const int64_t x_extent = (int64_t)(B - 1) * x_bs + (int64_t)(G - 1) * x_gs + (int64_t)Cig * (UP ? T / 2 : T);
-    const int64_t gy_extent = (int64_t)(B - 1) * gy_bs + (int64_t)(G - 1) * gy_gs + (int64_t)Cog * T;
+    const int64_t x_extent = (int64_t)(B - 1) * a.x_bs + (int64_t)(G - 1) * a.x_gs + (int64_t)Cig * (UP ? T / 2 : T);
+    const int64_t gy_extent = (int64_t)(B - 1) * a.gy_bs + (int64_t)(G - 1) * a.gy_gs + (int64_t)Cog * T;
     const int64_t blocks = (int64_t)S * G * m_tiles * ci_chunks;
-    hipLaunchKernelGGL((conv_bww_glds_kernel<K, AFF, WINO, NBUF, UP>), dim3((unsigned)blocks), dim3(256), lds, st, x, x_bs, x_gs, gy,
-                       gy_bs, gy_gs, ws, B, T, G, Cig, Cog, tps, n_tiles, m_tiles, ci_chunks, S, pro_a, pro_b, pro_Bp, n_pass,
-                       x_extent, gy_extent);
+    hipLaunchKernelGGL((conv_bww_glds_kernel<K, AFF, WINO, NBUF, UP>), dim3((unsigned)blocks), dim3(256), lds, st, a.x, a.x_bs, a.x_gs,
+                       a.gy, a.gy_bs, a.gy_gs, (float*)a.ws, B, T, G, Cig, Cog, tps, n_tiles, m_tiles, ci_chunks, S, pro_a, pro_b,
+                       pro_Bp, n_pass, x_extent, gy_extent);
     return nef_launch_status();
 }
 
@@ -477,9 +481,9 @@ constexpr int GL_NBUF = 2;
 
 // Shapes the LDS-DMA kernel takes (everything else stays on conv_bwd_weight_kernel): whole 64-channel slabs, at least two
 // tiles per sample, no in_scale, T % 4 == 0 with the upsampling prologue; at most 8 BatchNorm passes in the prologue table.
-extern "C" __attribute__((visibility("hidden"))) bool nef_bww_glds_ok(int B, int T, int Cig, int Cog, int K, int pro_mode, int pro_Bp,
-                                                                      bool in_scale) {
-    if (in_scale || (K != 3 && K != 7) || (K == 7 && pro_mode != 0)) return false;
+extern "C" __attribute__((visibility("hidden"))) bool nef_bww_glds_ok(const nef_bww_args& a) {
+    const int B = a.B, T = a.T, Cig = a.Cin_g, Cog = a.Cout_g, K = a.K, pro_mode = a.pro_mode, pro_Bp = a.pro_Bp;
+    if (a.in_scale || (K != 3 && K != 7) || (K == 7 && pro_mode != 0)) return false;
     if ((pro_mode & 2) && T % 4 != 0) return false;
     if (Cig % ROWS != 0 || Cog % ROWS != 0 || T < 2 * TW || T % 2 != 0) return false;
     if ((int64_t)(ROWS - 1) * T * 4 + 4 * 11 * 4 >= 0x7FFFFFFCll) return false;      // per-lane offsets are 32-bit
@@ -489,27 +493,14 @@ extern "C" __attribute__((visibility("hidden"))) bool nef_bww_glds_ok(int B, int
 
 // `half`: 0 for K = 3; 4 / 5 for the two launches of K = 7.  S_max: the split count the workspace was sized for; fixed_S > 0:
 // use exactly this many (second launch of K = 7).  Partials go to ws[S][G][K][Cog][Cig] like conv_bwd_weight_kernel's.
-extern "C" __attribute__((visibility("hidden"))) int nef_bww_glds_launch(
-    const float* x, int64_t x_bs, int64_t x_gs, const float* gy, int64_t gy_bs, int64_t gy_gs, float* ws, int B, int T, int G,
-    int Cig, int Cog, int K, int half, const float* pro_a, const float* pro_b, int pro_mode, int pro_Bp, int S_max, int fixed_S,
-    int* S_used, hipStream_t st) {
-    const int n_pass = (pro_mode & 1) ? (B + pro_Bp - 1) / pro_Bp : 0;
-    if (K == 3) {
-        if (pro_mode == 3)
-            return launch<3, true, 2, GL_NBUF, true>(x, x_bs, x_gs, gy, gy_bs, gy_gs, ws, B, T, G, Cig, Cog, pro_a, pro_b, pro_Bp,
-                                                     n_pass, S_max, fixed_S, S_used, st);
-        if (pro_mode & 2)
-            return launch<3, false, 2, GL_NBUF, true>(x, x_bs, x_gs, gy, gy_bs, gy_gs, ws, B, T, G, Cig, Cog, nullptr, nullptr, 1,
-                                                      0, S_max, fixed_S, S_used, st);
-        if (pro_mode & 1)
-            return launch<3, true, 2, GL_NBUF>(x, x_bs, x_gs, gy, gy_bs, gy_gs, ws, B, T, G, Cig, Cog, pro_a, pro_b, pro_Bp,
-                                               n_pass, S_max, fixed_S, S_used, st);
-        return launch<3, false, 2, GL_NBUF>(x, x_bs, x_gs, gy, gy_bs, gy_gs, ws, B, T, G, Cig, Cog, nullptr, nullptr, 1, 0,
-                                            S_max, fixed_S, S_used, st);
+extern "C" __attribute__((visibility("hidden"))) int nef_bww_glds_launch(const nef_bww_args& a, int half, int S_max, int fixed_S,
+                                                                         int* S_used, hipStream_t st) {
+    if (a.K == 3) {
+        if (a.pro_mode == 3) return launch<3, true, 2, GL_NBUF, true>(a, S_max, fixed_S, S_used, st);
+        if (a.pro_mode & 2) return launch<3, false, 2, GL_NBUF, true>(a, S_max, fixed_S, S_used, st);
+        if (a.pro_mode & 1) return launch<3, true, 2, GL_NBUF>(a, S_max, fixed_S, S_used, st);
+        return launch<3, false, 2, GL_NBUF>(a, S_max, fixed_S, S_used, st);
     }
-    if (half == 4)
-        return launch<7, false, 4, GL_NBUF>(x, x_bs, x_gs, gy, gy_bs, gy_gs, ws, B, T, G, Cig, Cog, nullptr, nullptr, 1, 0,
-                                            S_max, fixed_S, S_used, st);
-    return launch<7, false, 5, GL_NBUF>(x, x_bs, x_gs, gy, gy_bs, gy_gs, ws, B, T, G, Cig, Cog, nullptr, nullptr, 1, 0, S_max,
-                                        fixed_S, S_used, st);
+    if (half == 4) return launch<7, false, 4, GL_NBUF>(a, S_max, fixed_S, S_used, st);
+    return launch<7, false, 5, GL_NBUF>(a, S_max, fixed_S, S_used, st);
 }

@@ -857,31 +857,28 @@ __attribute__((visibility("hidden"))) int nef_h2w_splits(int B, int T, int G, in
     return S;
 }
 
-__attribute__((visibility("hidden"))) int nef_h2w_launch(const float* x, int64_t x_bs, int64_t x_gs, const float* in_scale, int64_t sc_bs,
-                                                         int64_t sc_gs, const float* pro_a, const float* pro_b, int pro_mode, int pro_Bp,
-                                                         const float* gy, int64_t gy_bs, int64_t gy_gs, float* ws, int B, int T, int G,
-                                                         int Cig, int Cog, int K, int S, float x_scale, float gy_scale,
-                                                         const float* x_amax, const float* gy_amax, float* x_amax_next,
-                                                         float* gy_amax_next, int* clamped, hipStream_t st) {
+// `b`: the call as nef_conv_bwd_weight validated it (x_scale / gy_scale of 0 mean 1: scale_from); S from nef_h2w_splits
+__attribute__((visibility("hidden"))) int nef_h2w_launch(const nef_bww_args& b, int S, hipStream_t st) {
+    const int B = b.B, T = b.T, G = b.G, Cig = b.Cin_g, Cog = b.Cout_g, K = b.K;
+    int pro_mode = b.pro_mode;
     if (!nef_h2w_ok(B, T, Cig, Cog, K, pro_mode)) return NEF_E_SHAPE;
-    if ((pro_mode & 1) && !(pro_a && pro_b && pro_Bp > 0)) return NEF_E_NULL;
-    if ((x_amax_next == nullptr) != (gy_amax_next == nullptr)) return NEF_E_NULL;
+    if ((b.x_amax_next == nullptr) != (b.gy_amax_next == nullptr)) return NEF_E_NULL;
     const H2WForm f = h2w_form(Cog, K);
     H2WArgs a;
-    a.x = x, a.gy = gy, a.in_scale = in_scale, a.pro_a = pro_a, a.pro_b = pro_b, a.ws = ws;
-    a.x_amax = x_amax, a.gy_amax = gy_amax, a.x_amax_next = x_amax_next, a.gy_amax_next = gy_amax_next, a.clamped = clamped;
-    a.x_bs = x_bs, a.x_gs = x_gs, a.gy_bs = gy_bs, a.gy_gs = gy_gs, a.sc_bs = sc_bs, a.sc_gs = sc_gs;
-    a.B = B, a.T = T, a.G = G, a.Cig = Cig, a.Cog = Cog, a.pro_Bp = pro_Bp > 0 ? pro_Bp : 1, a.S = S;
+    a.x = b.x, a.gy = b.gy, a.in_scale = b.in_scale, a.pro_a = b.pro_a, a.pro_b = b.pro_b, a.ws = (float*)b.ws;
+    a.x_amax = b.x_amax, a.gy_amax = b.gy_amax, a.x_amax_next = b.x_amax_next, a.gy_amax_next = b.gy_amax_next, a.clamped = b.clamped;
+    a.x_bs = b.x_bs, a.x_gs = b.x_gs, a.gy_bs = b.gy_bs, a.gy_gs = b.gy_gs, a.sc_bs = b.sc_bs, a.sc_gs = b.sc_gs;
+    a.B = B, a.T = T, a.G = G, a.Cig = Cig, a.Cog = Cog, a.pro_Bp = b.pro_Bp, a.S = S;
     a.tps = (T + TT - 1) / TT;
     a.n_tiles = B * a.tps;
     a.m_tiles = Cog / (64 * f.mco), a.c_tiles = Cig / 64;
     a.teams = G * S;
-    a.x_scale = x_scale, a.gy_scale = gy_scale;
+    a.x_scale = b.x_scale, a.gy_scale = b.gy_scale;
     a.xclamp = (pro_mode >> 2) & 1;
     pro_mode &= 3;
     const int Tin = (pro_mode & 2) ? T / 2 : T;
-    a.x_end = ((int64_t)(B - 1) * x_bs + (int64_t)(G - 1) * x_gs + (int64_t)Cig * Tin) * 4;
-    a.gy_end = ((int64_t)(B - 1) * gy_bs + (int64_t)(G - 1) * gy_gs + (int64_t)Cog * T) * 4;
+    a.x_end = ((int64_t)(B - 1) * b.x_bs + (int64_t)(G - 1) * b.x_gs + (int64_t)Cig * Tin) * 4;
+    a.gy_end = ((int64_t)(B - 1) * b.gy_bs + (int64_t)(G - 1) * b.gy_gs + (int64_t)Cog * T) * 4;
     if (a.xclamp && !h2w2_form(Cog, pro_mode)) return NEF_E_UNSUPPORTED;      // (only the producer / consumer form continues the window)
     if (const int v2 = h2w2_form(Cog, pro_mode)) {
         a.m_tiles = Cog / (v2 == 1 ? 128 : 64), a.c_tiles = Cig / 64;

@@ -2077,10 +2077,7 @@ static bool plan_bwd_weight(int B, int T, int G, int Cig, int Cog, int K, BwdWei
 }
 
 template <int K, int WCO, int TCI, int PRO = 0, int WINO = 0>
-static int launch_bwd_weight(BwdWeightPlan& p, const float* x, int64_t x_bs, int64_t x_gs, const float* in_scale,
-                             int64_t sc_bs, int64_t sc_gs, const float* gy, int64_t gy_bs, int64_t gy_gs, float* ws,
-                             int B, int T, int G, int Cig, int Cog, hipStream_t st, const float* pro_a = nullptr,
-                             const float* pro_b = nullptr, int pro_Bp = 1, int fixed_S = 0) {
+static int launch_bwd_weight(BwdWeightPlan& p, const nef_bww_args& a, hipStream_t st, int fixed_S = 0) {
     constexpr int WCI = 4 / WCO;
     constexpr int MT = 32 * WCO;
     constexpr int CIT = 32 * TCI * WCI;
@@ -2109,16 +2106,16 @@ static int launch_bwd_weight(BwdWeightPlan& p, const float* x, int64_t x_bs, int
             resident = per_cu * nef_cu_count();
             __atomic_store_n(&resident_dev[dev & 63], resident, __ATOMIC_RELEASE);
         }
-        const int base = G * p.m_tiles * p.ci_chunks;
+        const int base = a.G * p.m_tiles * p.ci_chunks;
         int S = resident / base;
         if (S > p.S) S = p.S;
         if (S < 1) S = 1;
         p.S = S;
     }
-    const int64_t blocks = (int64_t)p.S * G * p.m_tiles * p.ci_chunks;
-    hipLaunchKernelGGL((conv_bwd_weight_kernel<K, WCO, TCI, PRO, WINO>), dim3((unsigned)blocks), dim3(256), lds, st, x, x_bs,
-                       x_gs, in_scale, sc_bs, sc_gs, gy, gy_bs, gy_gs, ws, B, T, G, Cig, Cog, p.ct.seg_shift, p.ct.nseg,
-                       p.ct.tps, p.ct.n_tiles, p.m_tiles, p.ci_chunks, p.S, pro_a, pro_b, pro_Bp);
+    const int64_t blocks = (int64_t)p.S * a.G * p.m_tiles * p.ci_chunks;
+    hipLaunchKernelGGL((conv_bwd_weight_kernel<K, WCO, TCI, PRO, WINO>), dim3((unsigned)blocks), dim3(256), lds, st, a.x, a.x_bs,
+                       a.x_gs, a.in_scale, a.sc_bs, a.sc_gs, a.gy, a.gy_bs, a.gy_gs, (float*)a.ws, a.B, a.T, a.G, a.Cin_g, a.Cout_g,
+                       p.ct.seg_shift, p.ct.nseg, p.ct.tps, p.ct.n_tiles, p.m_tiles, p.ci_chunks, p.S, a.pro_a, a.pro_b, a.pro_Bp);
     return nef_launch_status();
 }
 
@@ -2221,15 +2218,11 @@ __attribute__((visibility("hidden"))) int nef_h2_pack(const nef_pack_desc* descs
 
 __attribute__((visibility("hidden"))) int nef_mfma_wino4_fwd(const nef_conv_args* a, hipStream_t st);
 __attribute__((visibility("hidden"))) int nef_mfma_wino_fwd(const nef_conv_args* a, hipStream_t st);
-__attribute__((visibility("hidden"))) int nef_mfma_bww_wino4(const float* x, int64_t x_bs, int64_t x_gs, const float* in_scale, int64_t sc_bs,
-                              int64_t sc_gs, const float* pro_a, const float* pro_b, int pro_mode, int pro_Bp,
-                              const float* gy, int64_t gy_bs, int64_t gy_gs, float* gw, void* ws, size_t ws_bytes, int B,
-                              int T, int G, int Cin_g, int Cout_g, int K, nef_stream_t stream);
 
 #if NEF_PART(1)
 extern "C" {
 
-int nef_abi_version(void) { return 19; }
+int nef_abi_version(void) { return 20; }
 
 int nef_pack_weight(const float* w, float* wp, int G, int Cog, int Cig, int K, int transpose_flip,
                     nef_stream_t stream) {
@@ -2386,133 +2379,92 @@ int nef_conv_stats_slots(int T, int Cout_g) {
     return ((T + nto - 1) / nto) * (nto / 128);
 }
 
-size_t nef_conv_bwd_weight_ws_bytes(int B, int T, int G, int Cin_g, int Cout_g, int K) {
-    BwdWeightPlan p;
-    if (!plan_bwd_weight(B, T, G, Cin_g, Cout_g, K, &p)) return 0;
-    return (size_t)p.S * G * K * Cout_g * Cin_g * sizeof(float);
-}
+size_t nef_bww_args_bytes(void) { return sizeof(nef_bww_args); }
 
-int nef_conv_bwd_weight(const float* x, int64_t x_bs, int64_t x_gs, const float* in_scale, int64_t sc_bs,
-                        int64_t sc_gs, const float* gy, int64_t gy_bs, int64_t gy_gs, float* gw, void* ws,
-                        size_t ws_bytes, int B, int T, int G, int Cin_g, int Cout_g, int K, nef_stream_t stream) {
-    NEF_ENTER();
-    NEF_REQUIRE(x && gy && gw && ws, NEF_E_NULL);
-    NEF_REQUIRE(B > 0 && T > 0 && G > 0, NEF_E_SHAPE);
-    BwdWeightPlan p;
-    NEF_REQUIRE(plan_bwd_weight(B, T, G, Cin_g, Cout_g, K, &p), NEF_E_SHAPE);
-    const size_t need = (size_t)p.S * G * K * Cout_g * Cin_g * sizeof(float);
-    NEF_REQUIRE(ws_bytes >= need, NEF_E_WORKSPACE);
-    hipStream_t st = (hipStream_t)stream;
-    float* wsf = (float*)ws;
-    int rc;
-#define NEF_BW(KK, WCO, TCI)                                                                                          \
-    rc = launch_bwd_weight<KK, WCO, TCI>(p, x, x_bs, x_gs, in_scale, sc_bs, sc_gs, gy, gy_bs, gy_gs, wsf, B, T, G,    \
-                                         Cin_g, Cout_g, st)
-    if (K == 7) {
-        if (p.wco == 4) NEF_BW(7, 4, 1); else NEF_BW(7, 2, 1);
-    } else if (K == 3) {
-        if (p.wco == 4) { if (p.tci == 2) NEF_BW(3, 4, 2); else NEF_BW(3, 4, 1); }
-        else { if (p.tci == 2) NEF_BW(3, 2, 2); else NEF_BW(3, 2, 1); }
-    } else {
-        if (p.wco == 4) { if (p.tci == 2) NEF_BW(1, 4, 2); else NEF_BW(1, 4, 1); }
-        else { if (p.tci == 2) NEF_BW(1, 2, 2); else NEF_BW(1, 2, 1); }
-    }
-#undef NEF_BW
-    if (rc != NEF_OK) return rc;
-    const int64_t n = (int64_t)G * K * Cout_g * Cin_g;
-    hipLaunchKernelGGL(conv_bwd_weight_reduce, dim3(nef_stream_grid(n, 256)), dim3(256), 0, st, wsf, gw, G, Cout_g,
-                       Cin_g, K, p.S);
-    return nef_launch_status();
-}
-
-int nef_conv_bwd_weight_pro(const float* x, int64_t x_bs, int64_t x_gs, const float* pro_a, const float* pro_b,
-                            int pro_mode, int pro_Bp, const float* gy, int64_t gy_bs, int64_t gy_gs, float* gw, void* ws,
-                            size_t ws_bytes, int B, int T, int G, int Cin_g, int Cout_g, int K, nef_stream_t stream) {
-    NEF_ENTER();
-    if (pro_mode == 0)
-        return nef_conv_bwd_weight(x, x_bs, x_gs, nullptr, 0, 0, gy, gy_bs, gy_gs, gw, ws, ws_bytes, B, T, G, Cin_g, Cout_g, K,
-                                   stream);
-    NEF_REQUIRE(x && gy && gw && ws, NEF_E_NULL);
-    NEF_REQUIRE(B > 0 && T > 0 && G > 0, NEF_E_SHAPE);
-    NEF_REQUIRE(K == 3 && pro_mode >= 1 && pro_mode <= 3, NEF_E_UNSUPPORTED);
-    NEF_REQUIRE(!(pro_mode & 1) || (pro_a && pro_b && pro_Bp > 0), NEF_E_NULL);
-    NEF_REQUIRE(!(pro_mode & 2) || (T % 2 == 0), NEF_E_SHAPE);
-    BwdWeightPlan p;
-    NEF_REQUIRE(plan_bwd_weight(B, T, G, Cin_g, Cout_g, K, &p, pro_mode), NEF_E_SHAPE);
-    NEF_REQUIRE(!(pro_mode & 1) || p.ct.nseg == 1 || pro_Bp % p.ct.nseg == 0, NEF_E_SHAPE);
-    const size_t need = (size_t)p.S * G * K * Cout_g * Cin_g * sizeof(float);
-    NEF_REQUIRE(ws_bytes >= need, NEF_E_WORKSPACE);
-    hipStream_t st = (hipStream_t)stream;
-    float* wsf = (float*)ws;
-    int rc = NEF_E_UNSUPPORTED;
-#define NEF_BWP(WCO, TCI, PRO)                                                                                          \
-    rc = launch_bwd_weight<3, WCO, TCI, PRO>(p, x, x_bs, x_gs, nullptr, 0, 0, gy, gy_bs, gy_gs, wsf, B, T, G, Cin_g,    \
-                                             Cout_g, st, pro_a, pro_b, pro_Bp)
-#define NEF_BWP_MODE(WCO, TCI)                                                                                          \
-    {                                                                                                                 \
-        if (pro_mode == 1) NEF_BWP(WCO, TCI, 1);                                                                      \
-        else if (pro_mode == 2) NEF_BWP(WCO, TCI, 2);                                                                 \
-        else NEF_BWP(WCO, TCI, 3);                                                                                    \
-    }
-    if (p.wco == 4) { if (p.tci == 2) NEF_BWP_MODE(4, 2) else NEF_BWP_MODE(4, 1) }
-    else NEF_BWP_MODE(2, 1)
-#undef NEF_BWP_MODE
-#undef NEF_BWP
-    if (rc != NEF_OK) return rc;
-    const int64_t n = (int64_t)G * K * Cout_g * Cin_g;
-    hipLaunchKernelGGL(conv_bwd_weight_reduce, dim3(nef_stream_grid(n, 256)), dim3(256), 0, st, wsf, gw, G, Cout_g,
-                       Cin_g, K, p.S);
-    return nef_launch_status();
-}
-
-// conv_h2w.hip: the weight gradient on exact fp16 splits of both operands
-__attribute__((visibility("hidden"))) bool nef_h2w_ok(int B, int T, int Cig, int Cog, int K, int pro_mode);
-__attribute__((visibility("hidden"))) int nef_h2w_splits(int B, int T, int G, int Cig, int Cog, int K, int pro_mode, int* partials);
-__attribute__((visibility("hidden"))) int nef_h2w_launch(const float* x, int64_t x_bs, int64_t x_gs, const float* in_scale, int64_t sc_bs,
-                                                         int64_t sc_gs, const float* pro_a, const float* pro_b, int pro_mode, int pro_Bp,
-                                                         const float* gy, int64_t gy_bs, int64_t gy_gs, float* ws, int B, int T, int G,
-                                                         int Cig, int Cog, int K, int S, float x_scale, float gy_scale,
-                                                         const float* x_amax, const float* gy_amax, float* x_amax_next,
-                                                         float* gy_amax_next, int* clamped, hipStream_t st);
-
-size_t nef_conv_bwd_weight_h2_ws_bytes(int B, int T, int G, int Cin_g, int Cout_g, int K) {
-    if (G <= 0 || !nef_h2w_ok(B, T, Cin_g, Cout_g, K, 0)) return 0;
-    int partials = 0;      // the tile form (and with it the split count) may depend on the prologue: size for the largest
-    for (int pm = 0; pm < (K == 3 ? 4 : 1); ++pm) {
-        int p_ = 0;
-        (void)nef_h2w_splits(B, T, G, Cin_g, Cout_g, K, pm, &p_);
-        if (p_ > partials) partials = p_;
+size_t nef_conv_bwd_weight_ws_bytes(const nef_bww_args* a) {
+    if (!a) return 0;
+    const int B = a->B, T = a->T, G = a->G, Cin_g = a->Cin_g, Cout_g = a->Cout_g, K = a->K;
+    int partials = 0;
+    if (a->form == 0 || a->form == 4) {      // the prologue-free direct plan: no other plan of these forms has more splits
+        BwdWeightPlan p;
+        if (!plan_bwd_weight(B, T, G, Cin_g, Cout_g, K, &p)) return 0;
+        partials = p.S;
+    } else if (a->form == 3) {
+        if (G <= 0 || !nef_h2w_ok(B, T, Cin_g, Cout_g, K, 0)) return 0;
+        // the tile form (and with it the split count) may depend on the prologue: size for the largest
+        for (int pm = 0; pm < (K == 3 ? 4 : 1); ++pm) {
+            int p_ = 0;
+            (void)nef_h2w_splits(B, T, G, Cin_g, Cout_g, K, pm, &p_);
+            if (p_ > partials) partials = p_;
+        }
     }
     return (size_t)partials * G * K * Cout_g * Cin_g * sizeof(float);
 }
 
-int nef_conv_bwd_weight_h2(const float* x, int64_t x_bs, int64_t x_gs, const float* in_scale, int64_t sc_bs, int64_t sc_gs,
-                           const float* pro_a, const float* pro_b, int pro_mode, int pro_Bp, const float* gy, int64_t gy_bs,
-                           int64_t gy_gs, float* gw, void* ws, size_t ws_bytes, int B, int T, int G, int Cin_g, int Cout_g, int K,
-                           float x_scale, float gy_scale, const float* x_amax, const float* gy_amax, float* x_amax_next,
-                           float* gy_amax_next, int32_t* clamped, nef_stream_t stream) {
-    NEF_ENTER();
-    NEF_REQUIRE(x && gy && gw && ws, NEF_E_NULL);
-    NEF_REQUIRE(G > 0 && nef_h2w_ok(B, T, Cin_g, Cout_g, K, pro_mode), NEF_E_SHAPE);
-    NEF_REQUIRE(!(pro_mode && in_scale), NEF_E_UNSUPPORTED);
-    int partials = 0;
-    const int S = nef_h2w_splits(B, T, G, Cin_g, Cout_g, K, pro_mode, &partials);
-    NEF_REQUIRE(ws_bytes >= (size_t)partials * G * K * Cout_g * Cin_g * sizeof(float), NEF_E_WORKSPACE);
-    hipStream_t st = (hipStream_t)stream;
-    if (int rc = nef_h2w_launch(x, x_bs, x_gs, in_scale, sc_bs, sc_gs, pro_a, pro_b, pro_mode, pro_Bp, gy, gy_bs, gy_gs, (float*)ws, B,
-                                T, G, Cin_g, Cout_g, K, S, x_scale, gy_scale, x_amax, gy_amax, x_amax_next, gy_amax_next, clamped, st))
-        return rc;
-    const int64_t n = (int64_t)G * K * Cout_g * Cin_g;
-    hipLaunchKernelGGL(conv_bwd_weight_reduce, dim3(nef_stream_grid(n, 256)), dim3(256), 0, st, (const float*)ws, gw, G, Cout_g,
-                       Cin_g, K, partials);
-    return nef_launch_status();
+// form 0: the direct kernel, with or without the input prologue.  *S_used = partial sums left in a.ws
+static int bww_direct(const nef_bww_args& a, hipStream_t st, int* S_used) {
+    const int K = a.K, pro_mode = a.pro_mode;
+    NEF_REQUIRE(a.B > 0 && a.T > 0 && a.G > 0, NEF_E_SHAPE);
+    NEF_REQUIRE(pro_mode == 0 || (K == 3 && pro_mode >= 1 && pro_mode <= 3 && !a.in_scale), NEF_E_UNSUPPORTED);
+    NEF_REQUIRE(!(pro_mode & 2) || (a.T % 2 == 0), NEF_E_SHAPE);
+    BwdWeightPlan p;
+    NEF_REQUIRE(plan_bwd_weight(a.B, a.T, a.G, a.Cin_g, a.Cout_g, K, &p, pro_mode), NEF_E_SHAPE);
+    NEF_REQUIRE(!(pro_mode & 1) || p.ct.nseg == 1 || a.pro_Bp % p.ct.nseg == 0, NEF_E_SHAPE);
+    const size_t need = (size_t)p.S * a.G * K * a.Cout_g * a.Cin_g * sizeof(float);
+    NEF_REQUIRE(a.ws_bytes >= need, NEF_E_WORKSPACE);
+    int rc = NEF_E_UNSUPPORTED;
+#define NEF_BW(KK, WCO, TCI) rc = launch_bwd_weight<KK, WCO, TCI>(p, a, st)
+#define NEF_BWP(WCO, TCI)                                                                                              \
+    {                                                                                                                 \
+        if (pro_mode == 0) NEF_BW(3, WCO, TCI);                                                                       \
+        else if (pro_mode == 1) rc = launch_bwd_weight<3, WCO, TCI, 1>(p, a, st);                                     \
+        else if (pro_mode == 2) rc = launch_bwd_weight<3, WCO, TCI, 2>(p, a, st);                                     \
+        else rc = launch_bwd_weight<3, WCO, TCI, 3>(p, a, st);                                                        \
+    }
+    if (K == 7) {
+        if (p.wco == 4) NEF_BW(7, 4, 1); else NEF_BW(7, 2, 1);
+    } else if (K == 3) {
+        if (p.wco == 4) { if (p.tci == 2) NEF_BWP(4, 2) else NEF_BWP(4, 1) }
+        else if (p.tci == 2) NEF_BW(3, 2, 2);      // (a prologue keeps the 64-channel form at tci = 1: plan_bwd_weight)
+        else NEF_BWP(2, 1)
+    } else {
+        if (p.wco == 4) { if (p.tci == 2) NEF_BW(1, 4, 2); else NEF_BW(1, 4, 1); }
+        else { if (p.tci == 2) NEF_BW(1, 2, 2); else NEF_BW(1, 2, 1); }
+    }
+#undef NEF_BWP
+#undef NEF_BW
+    *S_used = p.S;
+    return rc;
 }
 
-int nef_conv_bwd_weight_wino4(const float* x, int64_t x_bs, int64_t x_gs, const float* in_scale, int64_t sc_bs,
-                              int64_t sc_gs, const float* pro_a, const float* pro_b, int pro_mode, int pro_Bp,
-                              const float* gy, int64_t gy_bs, int64_t gy_gs, float* gw, void* ws, size_t ws_bytes, int B,
-                              int T, int G, int Cin_g, int Cout_g, int K, nef_stream_t stream) {
-    return nef_mfma_bww_wino4(x, x_bs, x_gs, in_scale, sc_bs, sc_gs, pro_a, pro_b, pro_mode, pro_Bp, gy, gy_bs, gy_gs, gw, ws, ws_bytes, B, T, G, Cin_g, Cout_g, K, stream);
+// form 3: exact fp16 splits of both operands (conv_h2w.hip)
+static int bww_h2(const nef_bww_args& a, hipStream_t st, int* S_used) {
+    NEF_REQUIRE(a.G > 0 && nef_h2w_ok(a.B, a.T, a.Cin_g, a.Cout_g, a.K, a.pro_mode), NEF_E_SHAPE);
+    NEF_REQUIRE(!(a.pro_mode && a.in_scale), NEF_E_UNSUPPORTED);
+    const int S = nef_h2w_splits(a.B, a.T, a.G, a.Cin_g, a.Cout_g, a.K, a.pro_mode, S_used);
+    NEF_REQUIRE(a.ws_bytes >= (size_t)*S_used * a.G * a.K * a.Cout_g * a.Cin_g * sizeof(float), NEF_E_WORKSPACE);
+    return nef_h2w_launch(a, S, st);
+}
+
+int nef_conv_bwd_weight(const nef_bww_args* args, nef_stream_t stream) {
+    NEF_ENTER();
+    NEF_REQUIRE(args && args->x && args->gy && args->gw && args->ws, NEF_E_NULL);
+    nef_bww_args a = *args;
+    if (!(a.pro_mode & 1) && a.pro_Bp <= 0) a.pro_Bp = 1;
+    NEF_REQUIRE(!(a.pro_mode & 1) || (a.pro_a && a.pro_b && a.pro_Bp > 0), NEF_E_NULL);
+    hipStream_t st = (hipStream_t)stream;
+    int S = 0, rc;
+    switch (a.form) {
+        case 0: rc = bww_direct(a, st, &S); break;
+        case 4: rc = nef_mfma_bww_wino4(a, st, &S); break;
+        case 3: rc = bww_h2(a, st, &S); break;
+        default: return NEF_E_UNSUPPORTED;
+    }
+    if (rc != NEF_OK) return rc;
+    const int64_t n = (int64_t)a.G * a.K * a.Cout_g * a.Cin_g;
+    hipLaunchKernelGGL(conv_bwd_weight_reduce, dim3(nef_stream_grid(n, 256)), dim3(256), 0, st, (const float*)a.ws, a.gw, a.G,
+                       a.Cout_g, a.Cin_g, a.K, S);
+    return nef_launch_status();
 }
 
 size_t nef_chan_sum_ws_bytes(int C) { return (size_t)CHAN_SUM_SPLIT * C * sizeof(double); }
@@ -2572,74 +2524,45 @@ __attribute__((visibility("hidden"))) int nef_mfma_wino_fwd(const nef_conv_args*
 #endif
 
 #if NEF_PART(4)
-extern "C" {
-// conv_bww_glds.hip: the same forms with the tiles streamed by LDS-DMA through a ring of LDS buffers
-__attribute__((visibility("hidden"))) bool nef_bww_glds_ok(int B, int T, int Cig, int Cog, int K, int pro_mode, int pro_Bp, bool in_scale);
-__attribute__((visibility("hidden"))) int nef_bww_glds_launch(const float* x, int64_t x_bs, int64_t x_gs, const float* gy, int64_t gy_bs, int64_t gy_gs, float* ws,
-                        int B, int T, int G, int Cig, int Cog, int K, int half, const float* pro_a, const float* pro_b,
-                        int pro_mode, int pro_Bp, int S_max, int fixed_S, int* S_used, hipStream_t st);
-}
-__attribute__((visibility("hidden"))) int nef_mfma_bww_wino4(const float* x, int64_t x_bs, int64_t x_gs, const float* in_scale, int64_t sc_bs,
-                              int64_t sc_gs, const float* pro_a, const float* pro_b, int pro_mode, int pro_Bp,
-                              const float* gy, int64_t gy_bs, int64_t gy_gs, float* gw, void* ws, size_t ws_bytes, int B,
-                              int T, int G, int Cin_g, int Cout_g, int K, nef_stream_t stream) {
-    NEF_ENTER();
-    NEF_REQUIRE(x && gy && gw && ws, NEF_E_NULL);
-    NEF_REQUIRE(B > 0 && T >= WT && T % 2 == 0 && G > 0 && (K == 3 || K == 7), NEF_E_SHAPE);
-    NEF_REQUIRE(pro_mode >= 0 && pro_mode <= 3 && (K == 3 || pro_mode == 0) && !(pro_mode && in_scale), NEF_E_UNSUPPORTED);
-    NEF_REQUIRE(!(pro_mode & 1) || (pro_a && pro_b && pro_Bp > 0), NEF_E_NULL);
+// Form 4.  The LDS-DMA kernel of conv_bww_glds.hip (the same forms with the tiles streamed through a ring of LDS buffers) where
+// it takes the shape, otherwise conv_bwd_weight_kernel.  *S_used = partial sums left in a.ws
+__attribute__((visibility("hidden"))) int nef_mfma_bww_wino4(const nef_bww_args& a, hipStream_t st, int* S_used) {
+    const int K = a.K, pro_mode = a.pro_mode;
+    NEF_REQUIRE(a.B > 0 && a.T >= WT && a.T % 2 == 0 && a.G > 0 && (K == 3 || K == 7), NEF_E_SHAPE);
+    NEF_REQUIRE(pro_mode >= 0 && pro_mode <= 3 && (K == 3 || pro_mode == 0) && !(pro_mode && a.in_scale), NEF_E_UNSUPPORTED);
     BwdWeightPlan p;
-    NEF_REQUIRE(plan_bwd_weight(B, T, G, Cin_g, Cout_g, K, &p, pro_mode, K == 7 ? 4 : 2), NEF_E_SHAPE);
+    NEF_REQUIRE(plan_bwd_weight(a.B, a.T, a.G, a.Cin_g, a.Cout_g, K, &p, pro_mode, K == 7 ? 4 : 2), NEF_E_SHAPE);
     NEF_REQUIRE(p.ct.nseg == 1, NEF_E_SHAPE);
-    const size_t need = (size_t)p.S * G * K * Cout_g * Cin_g * sizeof(float);
-    NEF_REQUIRE(ws_bytes >= need, NEF_E_WORKSPACE);
-    hipStream_t st = (hipStream_t)stream;
-    float* wsf = (float*)ws;
+    const size_t need = (size_t)p.S * a.G * K * a.Cout_g * a.Cin_g * sizeof(float);
+    NEF_REQUIRE(a.ws_bytes >= need, NEF_E_WORKSPACE);
     int rc = NEF_E_UNSUPPORTED;
-#define NEF_BW4(WCO, PRO)                                                                                              \
-    rc = launch_bwd_weight<3, WCO, 1, PRO, 2>(p, x, x_bs, x_gs, in_scale, sc_bs, sc_gs, gy, gy_bs, gy_gs, wsf, B, T, G,  \
-                                              Cin_g, Cout_g, st, pro_a, pro_b, pro_Bp)
 #define NEF_BW4_MODE(WCO)                                                                                              \
     {                                                                                                                 \
-        if (pro_mode == 0) NEF_BW4(WCO, 0);                                                                           \
-        else if (pro_mode == 1) NEF_BW4(WCO, 1);                                                                      \
-        else if (pro_mode == 2) NEF_BW4(WCO, 2);                                                                      \
-        else NEF_BW4(WCO, 3);                                                                                         \
+        if (pro_mode == 0) rc = launch_bwd_weight<3, WCO, 1, 0, 2>(p, a, st);                                         \
+        else if (pro_mode == 1) rc = launch_bwd_weight<3, WCO, 1, 1, 2>(p, a, st);                                    \
+        else if (pro_mode == 2) rc = launch_bwd_weight<3, WCO, 1, 2, 2>(p, a, st);                                    \
+        else rc = launch_bwd_weight<3, WCO, 1, 3, 2>(p, a, st);                                                       \
     }
-    if (nef_bww_glds_ok(B, T, Cin_g, Cout_g, K, pro_mode, pro_Bp, in_scale != nullptr)) {
-        int S_used = 0;
+    if (nef_bww_glds_ok(a)) {
+        int S = 0;
         if (K == 3) {
-            rc = nef_bww_glds_launch(x, x_bs, x_gs, gy, gy_bs, gy_gs, wsf, B, T, G, Cin_g, Cout_g, 3, 0, pro_a, pro_b, pro_mode,
-                                     pro_Bp, p.S, 0, &S_used, st);
-        } else {
-            rc = nef_bww_glds_launch(x, x_bs, x_gs, gy, gy_bs, gy_gs, wsf, B, T, G, Cin_g, Cout_g, 7, 4, nullptr, nullptr, 0, 1, p.S,
-                                     0, &S_used, st);
-            if (rc == NEF_OK)
-                rc = nef_bww_glds_launch(x, x_bs, x_gs, gy, gy_bs, gy_gs, wsf, B, T, G, Cin_g, Cout_g, 7, 5, nullptr, nullptr, 0, 1,
-                                         p.S, S_used, &S_used, st);
+            rc = nef_bww_glds_launch(a, 0, p.S, 0, &S, st);
+        } else {      // taps split 4 + 3 across two launches, the second with the first one's split count
+            rc = nef_bww_glds_launch(a, 4, p.S, 0, &S, st);
+            if (rc == NEF_OK) rc = nef_bww_glds_launch(a, 5, p.S, S, &S, st);
         }
-        p.S = S_used;
+        p.S = S;
     } else if (K == 7) {      // taps split 4 + 3 across two launches: transposed F(4,4), then transposed F(3,4)
         if (p.wco == 4) {
-            rc = launch_bwd_weight<7, 4, 1, 0, 4>(p, x, x_bs, x_gs, in_scale, sc_bs, sc_gs, gy, gy_bs, gy_gs, wsf, B, T, G, Cin_g,
-                                                  Cout_g, st);
-            if (rc == NEF_OK)
-                rc = launch_bwd_weight<7, 4, 1, 0, 5>(p, x, x_bs, x_gs, in_scale, sc_bs, sc_gs, gy, gy_bs, gy_gs, wsf, B, T, G,
-                                                      Cin_g, Cout_g, st, nullptr, nullptr, 1, p.S);
+            rc = launch_bwd_weight<7, 4, 1, 0, 4>(p, a, st);
+            if (rc == NEF_OK) rc = launch_bwd_weight<7, 4, 1, 0, 5>(p, a, st, p.S);
         } else {
-            rc = launch_bwd_weight<7, 2, 1, 0, 4>(p, x, x_bs, x_gs, in_scale, sc_bs, sc_gs, gy, gy_bs, gy_gs, wsf, B, T, G, Cin_g,
-                                                  Cout_g, st);
-            if (rc == NEF_OK)
-                rc = launch_bwd_weight<7, 2, 1, 0, 5>(p, x, x_bs, x_gs, in_scale, sc_bs, sc_gs, gy, gy_bs, gy_gs, wsf, B, T, G,
-                                                      Cin_g, Cout_g, st, nullptr, nullptr, 1, p.S);
+            rc = launch_bwd_weight<7, 2, 1, 0, 4>(p, a, st);
+            if (rc == NEF_OK) rc = launch_bwd_weight<7, 2, 1, 0, 5>(p, a, st, p.S);
         }
     } else if (p.wco == 4) NEF_BW4_MODE(4) else NEF_BW4_MODE(2)
 #undef NEF_BW4_MODE
-#undef NEF_BW4
-    if (rc != NEF_OK) return rc;
-    const int64_t n = (int64_t)G * K * Cout_g * Cin_g;
-    hipLaunchKernelGGL(conv_bwd_weight_reduce, dim3(nef_stream_grid(n, 256)), dim3(256), 0, st, wsf, gw, G, Cout_g,
-                       Cin_g, K, p.S);
-    return nef_launch_status();
+    *S_used = p.S;
+    return rc;
 }
 #endif

@@ -133,3 +133,21 @@ __device__ __forceinline__ void nef_buf_store_f32x4(nef_f32x4 v, __amdgpu_buffer
 __device__ __forceinline__ nef_f32x4 nef_buf_f32x4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
     return __builtin_bit_cast(nef_f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
 }
+
+// ------------------------------------------------------------------------------------------------------------
+// Weight-gradient launchers that cross translation units.  One call = one nef_bww_args (nefnet_hip.h), with pro_Bp already
+// normalised by nef_conv_bwd_weight; each launcher leaves its partial sums in a.ws and says how many there are, the entry reduces.
+// ------------------------------------------------------------------------------------------------------------
+#define NEF_HIDDEN __attribute__((visibility("hidden")))
+extern "C" {
+// conv_h2w.hip (form 3): shape rule, split count S (and partial sums per element), launch with that S
+NEF_HIDDEN bool nef_h2w_ok(int B, int T, int Cig, int Cog, int K, int pro_mode);
+NEF_HIDDEN int nef_h2w_splits(int B, int T, int G, int Cig, int Cog, int K, int pro_mode, int* partials);
+NEF_HIDDEN int nef_h2w_launch(const nef_bww_args& a, int S, hipStream_t st);
+// conv_bww_glds.hip (form 4 by LDS-DMA): `half` 0 for K = 3, 4 / 5 for the two launches of K = 7; S_max: the split count the
+// workspace was sized for; fixed_S > 0: use exactly this many (second launch of K = 7)
+NEF_HIDDEN bool nef_bww_glds_ok(const nef_bww_args& a);
+NEF_HIDDEN int nef_bww_glds_launch(const nef_bww_args& a, int half, int S_max, int fixed_S, int* S_used, hipStream_t st);
+}
+// conv_mfma.hip, part 4 (form 4): validates, picks the LDS-DMA or the register-staged kernel, S_used = partial sums left in a.ws
+NEF_HIDDEN int nef_mfma_bww_wino4(const nef_bww_args& a, hipStream_t st, int* S_used);

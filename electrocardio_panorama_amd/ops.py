@@ -214,7 +214,7 @@ WINOGRAD = _WV != "0"
 # a heavily cancelling gradient -- by 3.7e-4 over the 3-step reference trajectory (bar 2e-4), and the fixed-up kernel
 # was no faster than F(2,3) (1.31 vs 1.33 ms on the K=7 conv).
 WINO_FWD = 1 if _WV in ("1", "2") else 2
-# Winograd weight gradients (nef_conv_bwd_weight_wino4): K=3 through the transposed F(3,4), K=7 with the taps split 4 + 3 over
+# Winograd weight gradients (nef_bww_args form 4): K=3 through the transposed F(3,4), K=7 with the taps split 4 + 3 over
 # two launches (transposed F(4,4) + F(3,4)).
 WINO_BW4 = _WV not in ("1", "2")
 WINO_BW7 = _WV not in ("1", "2")
@@ -725,6 +725,15 @@ def bn_stats_from_slots(stats, gamma, beta, running_mean, running_var, P, N, Ln,
     return mean, invstd, a, b
 
 
+def _operand(a, xv, in_scale, pro):
+    """The input operand of a ConvArgs / BwwArgs (same field names): the view, the channel scale and the input prologue."""
+    a.x, a.x_bs, a.x_gs = xv.ptr, xv.bs, xv.gs
+    if in_scale is not None:
+        a.in_scale, a.sc_bs, a.sc_gs = _p(in_scale[0]), in_scale[1], in_scale[2]
+    if pro is not None and pro[0]:
+        a.pro_mode, a.pro_a, a.pro_b, a.pro_Bp = pro[0], _p(pro[1]), _p(pro[2]), pro[3]
+
+
 def conv(xv, wp, Cog, K, out=None, bias=None, in_scale=None, res=None, gate=None, gate_scale=1.0, relu=False,
          mask=None, drop_p=0.0, drop_scale=1.0, seed=0, role="conv_fwd", pro=None, seed_dev=None, stats=None, bnb=None,
          x_scale=0.0, tag_extra="", res_scale=None, gate_rowscale=None, stats_mode=0):
@@ -741,15 +750,12 @@ def conv(xv, wp, Cog, K, out=None, bias=None, in_scale=None, res=None, gate=None
         y = torch.empty(xv.B, xv.G * Cog, T_out, device=xv.t.device, dtype=torch.float32)
         out = GV.dense(y, xv.G)
     a = _lib.ConvArgs()
-    a.x, a.wp, a.y = xv.ptr, _p(wp), out.ptr
+    _operand(a, xv, in_scale, pro)
+    a.wp, a.y, a.y_bs, a.y_gs = _p(wp), out.ptr, out.bs, out.gs
     a.bias = _p(bias)
-    a.in_scale = None
-    if in_scale is not None:
-        a.in_scale, a.sc_bs, a.sc_gs = _p(in_scale[0]), in_scale[1], in_scale[2]
     a.res = res.ptr if res is not None else None
     a.gate = gate.ptr if gate is not None else None
     a.mask = _p(mask)
-    a.x_bs, a.x_gs, a.y_bs, a.y_gs = xv.bs, xv.gs, out.bs, out.gs
     if res is not None:
         a.res_bs, a.res_gs = res.bs, res.gs
     if gate_rowscale is not None:      # y = gate > 0 ? y * gate_scale * gate_rowscale[b, g, c] : 0 (split-fp16 launches only)
@@ -762,8 +768,6 @@ def conv(xv, wp, Cog, K, out=None, bias=None, in_scale=None, res=None, gate=None
     if gate is not None:
         a.gate_bs, a.gate_gs = gate.bs, gate.gs
     a.B, a.T, a.G, a.Cin_g, a.Cout_g, a.K = xv.B, T_out, xv.G, xv.Cg, Cog, K
-    if pro is not None and pro[0]:
-        a.pro_mode, a.pro_a, a.pro_b, a.pro_Bp = pro[0], _p(pro[1]), _p(pro[2]), pro[3]
     a.relu = int(relu)
     a.gate_scale, a.drop_scale, a.drop_p, a.rng_seed = gate_scale, drop_scale, drop_p, seed
     a.rng_seed_dev = _p(seed_dev)
@@ -941,28 +945,22 @@ def conv_bwd_weight(xv, gyv, K, in_scale=None, pro=None, wino=None, site=None, h
     pro_mode bit 2 needs on the fp32 kernels (conv_bwd_weight_poly passes it)."""
     L = _lib.load()
     B, T, G, Cig, Cog = xv.B, gyv.T, xv.G, xv.Cg, gyv.Cg
-    gw = torch.empty(G * Cog, Cig, K, device=xv.t.device, dtype=torch.float32)
+    dev = xv.t.device
+    gw = torch.empty(G * Cog, Cig, K, device=dev, dtype=torch.float32)
     pm0 = pro[0] if pro is not None else 0
+    a = _lib.BwwArgs()
+    _operand(a, xv, in_scale, pro)
+    a.gy, a.gy_bs, a.gy_gs, a.gw = gyv.ptr, gyv.bs, gyv.gs, _p(gw)
+    a.B, a.T, a.G, a.Cin_g, a.Cout_g, a.K = B, T, G, Cig, Cog, K
+    a.x_scale, a.gy_scale = float(x_scale), float(gy_scale)
     routed = False
     if h2 is None:
         h2 = (wino is None and h2w_ok(K, Cig, Cog, T, pm0, in_scale is not None) and
               (BATCH_HINT is None or B * ((T + 63) // 64) >= 8 * _H2_MIN_WGS))      # enough (sample, tile) steps to split
     if h2:
-        n = L.nef_conv_bwd_weight_h2_ws_bytes(B, T, G, Cig, Cog, K)
-        if n == 0:
-            raise _lib.NefLibraryError(f"conv_bwd_weight (split-fp16): unsupported shape Cig={Cig} Cog={Cog} K={K} T={T}")
-        ws = workspace(n, xv.t.device)
-        sc, sc_bs, sc_gs = (None, 0, 0) if in_scale is None else (_p(in_scale[0]), in_scale[1], in_scale[2])
-        pm, pa, pb, pbp = (pro[0], _p(pro[1]), _p(pro[2]), pro[3]) if pm0 else (0, None, None, 1)
-
-        def launch(amax, nxt, clamped=None):
-            _lib.check(L.nef_conv_bwd_weight_h2(xv.ptr, xv.bs, xv.gs, sc, sc_bs, sc_gs, pa, pb, pm, pbp, gyv.ptr, gyv.bs, gyv.gs,
-                                                _p(gw), _p(ws), n, B, T, G, Cig, Cog, K, float(x_scale), float(gy_scale),
-                                                amax, None if amax is None else amax + 4, nxt, None if nxt is None else nxt + 4,
-                                                clamped, _stream()), "nef_conv_bwd_weight_h2")
-        amax = nxt = clamped = None
+        _bww_form(L, a, 3, dev, f"conv_bwd_weight (split-fp16): unsupported shape Cig={Cig} Cog={Cog} K={K} T={T}")
         if not (x_scale and gy_scale):
-            st = _amax_state(xv.t.device)
+            st = _amax_state(dev)
             key = None
             if AMAX_SCOPE is not None and site is not None:
                 occ = st["occ"]
@@ -971,11 +969,12 @@ def conv_bwd_weight(xv, gyv, K, in_scale=None, pro=None, wino=None, site=None, h
                 key = base + (k,)
             i = _amax_index(st, key if key is not None else (None, "bww"), 2)          # slots i (x) and i + 1 (gy); unscoped launches: a pair of their own
             nxt = st["nxt"].data_ptr() + 4 * i
+            a.x_amax_next, a.gy_amax_next = nxt, nxt + 4
             if i not in st["ready"] or key is None:
                 if torch.cuda.is_current_stream_capturing():
                     raise RuntimeError("split-fp16 weight gradient: a call site's first launch cannot be captured")
                 st["nxt"][i:i + 2] = 0.0
-                launch(None, nxt)
+                _bww(L, a)      # (x_amax, gy_amax and clamped still NULL: it measures)
                 st["cur"][i:i + 2] = st["nxt"][i:i + 2]
                 if key is not None:
                     flag = _note_tail(st, i, [(xv, in_scale, pro), (gyv, None, None)])
@@ -986,22 +985,23 @@ def conv_bwd_weight(xv, gyv, K, in_scale=None, pro=None, wino=None, site=None, h
             routed = i in st["fp32"]
             if not routed:
                 st["used"] = True
-                amax, clamped = st["cur"].data_ptr() + 4 * i, st["clamped"].data_ptr()
+                cur = st["cur"].data_ptr() + 4 * i
+                a.x_amax, a.gy_amax, a.clamped = cur, cur + 4, st["clamped"].data_ptr()
         if not routed:
             tag = ("conv_bwd_weight", K, G, Cig, Cog, B, T) + (("up",) if pm0 & 2 else (("pw",) if pm0 & 4 else ()))
             ev = _timed(tag)
             if ev is not None:
                 EXEC_FRAC[tag] = 0.0
                 EXEC_FP16[tag] = 3.0
-            launch(amax, nxt, clamped)
+            _bww(L, a)
             _done(ev)
             return gw
     # fp32 kernels.  A routed split-fp16 site (H2_TAIL_MODE) takes the DIRECT form: the transposed-Winograd transforms add and
     # subtract neighbouring products before the reduction, which on two heavy-tailed operands costs the small half of the gradient
-    # what the split format does (log-normal K = 3: 2.3e-4 small-half rel-L2 through nef_conv_bwd_weight_wino4, 7.8e-7 for torch's
+    # what the split format does (log-normal K = 3: 2.3e-4 small-half rel-L2 through form 4, 7.8e-7 for torch's
     # fp32); bench.py sees its launches under their own tag ("f32" in the extra element).  pro_mode bit 2 (the polyphase weight
     # gradient's window continued with x'[0] / x'[T-1]): the zero-padded fp32 gradient + the row-end products of `xedge`
-    # (nef_bwd_weight_clamp_ends).
+    # (nef_bwd_weight_clamp_ends).  The struct is the split-fp16 call's: these forms ignore its scale and magnitude fields.
     extra = ("up" if pm0 & 2 else "") + (("pw" if pm0 & 4 else "") + "f32" if routed else "")
     if routed:
         wino = False
@@ -1009,35 +1009,19 @@ def conv_bwd_weight(xv, gyv, K, in_scale=None, pro=None, wino=None, site=None, h
     if clamp:
         if xedge is None:
             raise _lib.NefLibraryError("conv_bwd_weight: pro_mode bit 2 on the fp32 kernels needs `xedge`")
-        pro = (pm0 & 3, pro[1], pro[2], pro[3]) if pm0 & 3 else None
-        pm0 = pm0 & 3
-    n = L.nef_conv_bwd_weight_ws_bytes(B, T, G, Cig, Cog, K)
-    if n == 0:
-        raise _lib.NefLibraryError(f"conv_bwd_weight: unsupported shape Cig={Cig} Cog={Cog} K={K}")
-    ws = workspace(n, xv.t.device)
-    sc, sc_bs, sc_gs = (None, 0, 0) if in_scale is None else (_p(in_scale[0]), in_scale[1], in_scale[2])
-    tag = ("conv_bwd_weight", K, G, Cig, Cog, B, T) + ((extra,) if extra else ())
-    ev = _timed(tag)
+        pm0 = a.pro_mode = pm0 & 3
     if wino is None:
         wino = (WINOGRAD and ((K == 3 and WINO_BW4) or (K == 7 and WINO_BW7)) and T % 2 == 0 and T >= 64
-                and not (K == 7 and pro is not None and pro[0]))
+                and not (K == 7 and pm0))
     wino = 4 if wino else False
+    assert wino or not pm0 or in_scale is None      # (the direct kernel's prologue forms take no in_scale)
+    _bww_form(L, a, wino or 0, dev, f"conv_bwd_weight: unsupported shape Cig={Cig} Cog={Cog} K={K}")
+    tag = ("conv_bwd_weight", K, G, Cig, Cog, B, T) + ((extra,) if extra else ())
+    ev = _timed(tag)
     if ev is not None:
         EXEC_FRAC[tag] = _exec_frac(K, 2) if wino else 1.0
         EXEC_FP16[tag] = 0.0
-    if wino:
-        pm, pa, pb, pbp = (pro[0], _p(pro[1]), _p(pro[2]), pro[3]) if (pro is not None and pro[0]) else (0, None, None, 1)
-        _lib.check(L.nef_conv_bwd_weight_wino4(xv.ptr, xv.bs, xv.gs, sc, sc_bs, sc_gs, pa, pb, pm, pbp, gyv.ptr, gyv.bs,
-                                              gyv.gs, _p(gw), _p(ws), n, B, T, G, Cig, Cog, K, _stream()),
-                   "nef_conv_bwd_weight_wino4")
-    elif pro is not None and pro[0]:
-        assert in_scale is None
-        _lib.check(L.nef_conv_bwd_weight_pro(xv.ptr, xv.bs, xv.gs, _p(pro[1]), _p(pro[2]), pro[0], pro[3], gyv.ptr, gyv.bs,
-                                             gyv.gs, _p(gw), _p(ws), n, B, T, G, Cig, Cog, K, _stream()),
-                   "nef_conv_bwd_weight_pro")
-    else:
-        _lib.check(L.nef_conv_bwd_weight(xv.ptr, xv.bs, xv.gs, sc, sc_bs, sc_gs, gyv.ptr, gyv.bs, gyv.gs, _p(gw), _p(ws),
-                                         n, B, T, G, Cig, Cog, K, _stream()), "nef_conv_bwd_weight")
+    _bww(L, a)
     if clamp:
         assert K == 3 and in_scale is None and tuple(xedge.shape) == (B, G * Cig, 2)
         _lib.check(L.nef_bwd_weight_clamp_ends(_p(xedge), gyv.ptr, gyv.bs, gyv.gs, _p(gw), B, T, G, Cig, Cog, _stream()),
@@ -1045,6 +1029,19 @@ def conv_bwd_weight(xv, gyv, K, in_scale=None, pro=None, wino=None, site=None, h
     if ev is not None:
         ev.record()
     return gw
+
+
+def _bww_form(L, a, form, device, unsupported):
+    """Points the BwwArgs `a` at kernel family `form` and at a workspace of the size the library asks for."""
+    a.form = form
+    a.ws_bytes = L.nef_conv_bwd_weight_ws_bytes(C.byref(a))
+    if a.ws_bytes == 0:
+        raise _lib.NefLibraryError(unsupported)
+    a.ws = _p(workspace(a.ws_bytes, device))
+
+
+def _bww(L, a):
+    _lib.check(L.nef_conv_bwd_weight(C.byref(a), _stream()), "nef_conv_bwd_weight")
 
 
 def _tail_mode():

@@ -34,7 +34,7 @@ extern "C" {
 typedef void* nef_stream_t;
 
 /* ABI version of this header; bumped on any signature change. */
-int nef_abi_version(void);   /* 19 (+ nef_adam, nef_h2_tail_census, nef_bwd_weight_clamp_ends: additions only; the kernel-form option entry points of 16 and nef_upsample2_aff_fwd are gone; + nef_debug_spin_us); 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + kernel-form option entry points); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + nef_conv_bwd_weight_h2); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, nef_conv_bwd_weight_wino4 covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
+int nef_abi_version(void);   /* 20 (the weight gradient is ONE entry, nef_conv_bwd_weight(nef_bww_args*), + nef_bww_args_bytes; its _pro, _wino4, _h2 and _h2_ws_bytes variants are gone); 19 (+ nef_adam, nef_h2_tail_census, nef_bwd_weight_clamp_ends: additions only; the kernel-form option entry points of 16 and nef_upsample2_aff_fwd are gone; + nef_debug_spin_us); 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + kernel-form option entry points); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + the split-fp16 weight gradient, now form 3); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, the transposed F(3,4) / F(4,4) entry, now form 4, covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
 
 /* Diagnostics: `wgs` workgroups busy for `us` microseconds on `stream` (a stand-in for a collective's time on the chip:
  * parallel.DryCollective, bench.py --dry-collective).  0 <= us <= 50000, 1 <= wgs <= 64. */
@@ -201,51 +201,70 @@ int nef_conv_fwd(const nef_conv_args* a, nef_stream_t stream);
 /* sizeof(nef_conv_args) as the library was built: a binding checks its mirror of the struct against it. */
 size_t nef_conv_args_bytes(void);
 
-/* gw[g*Cog+co][ci][k] = sum_{b,t} gy[b][g][co][t] * (x*in_scale)[b][g][ci][t+k-pad].  gw is overwritten.
- * ws: nef_conv_bwd_weight_ws_bytes(...) bytes of scratch (split-K partials, reduced deterministically). */
-size_t nef_conv_bwd_weight_ws_bytes(int B, int T, int G, int Cin_g, int Cout_g, int K);
-int nef_conv_bwd_weight(const float* x, int64_t x_bs, int64_t x_gs, const float* in_scale, int64_t sc_bs,
-                        int64_t sc_gs, const float* gy, int64_t gy_bs, int64_t gy_gs, float* gw, void* ws,
-                        size_t ws_bytes, int B, int T, int G, int Cin_g, int Cout_g, int K, nef_stream_t stream);
-/* Same with the input prologue of nef_conv_args (pro_mode / pro_a / pro_b / pro_Bp) recomputed while staging x. */
-int nef_conv_bwd_weight_pro(const float* x, int64_t x_bs, int64_t x_gs, const float* pro_a, const float* pro_b,
-                            int pro_mode, int pro_Bp, const float* gy, int64_t gy_bs, int64_t gy_gs, float* gw, void* ws,
-                            size_t ws_bytes, int B, int T, int G, int Cin_g, int Cout_g, int K, nef_stream_t stream);
+/* gw[g*Cog+co][ci][k] = sum_{b,t} gy[b][g][co][t] * x'[b][g][ci][t+k-pad], x' = prologue(x) * in_scale.  gw is overwritten.
+ * One struct describes the call, as nef_conv_args does for the forward / backward-data convolutions (same names, same meaning).
+ * Fields a form does not use are ignored (forms 0 and 4: x_scale, gy_scale, the amax words and `clamped`), so one struct can be
+ * handed from form 3 to form 0 as it is. */
+typedef struct nef_bww_args {
+    const float* x;        /* input; element (b, g, ci, t) at x + b*x_bs + g*x_gs + ci*T + t (half resolution, T/2, with pro_mode bit1) */
+    const float* gy;       /* output gradient; element (b, g, co, t) at gy + b*gy_bs + g*gy_gs + co*T + t */
+    float* gw;             /* [G*Cout_g][Cin_g][K], torch layout */
+    void* ws;              /* ws_bytes >= nef_conv_bwd_weight_ws_bytes(args) bytes of scratch: the split partial sums, added up in a
+                              fixed order (deterministic) */
+    const float* in_scale; /* NULL, or per (sample, input channel) factor at in_scale + b*sc_bs + g*sc_gs + ci; only with pro_mode 0 */
+    const float* pro_a;    /* the input prologue of nef_conv_args (pro_mode / pro_a / pro_b / pro_Bp), recomputed while staging x: */
+    const float* pro_b;    /* bit0 needs pro_a, pro_b and pro_Bp > 0; without bit0 pro_Bp <= 0 means 1 */
+    /* Form 3 only.  x_amax / gy_amax: NULL, or device words with the largest |operand| the call site saw before -- when positive and
+     * finite the scales are derived from them instead of x_scale / gy_scale; x_amax_next / gy_amax_next: both NULL, or device words
+     * this launch max-accumulates its operands' magnitudes into; clamped: NULL, or a device counter incremented when a scaled
+     * operand element had to be clamped at fp16's range (see nef_conv_args.x_clamped). */
+    const float* x_amax;
+    const float* gy_amax;
+    float* x_amax_next;
+    float* gy_amax_next;
+    int32_t* clamped;
+    size_t ws_bytes;
+    int64_t x_bs, x_gs, gy_bs, gy_gs, sc_bs, sc_gs;
+    int32_t B, T, G, Cin_g, Cout_g, K;
+    int32_t pro_mode;      /* 0..3 as in nef_conv_args (K == 3 only); form 3 also takes bit 2 (4 / 5, no upsampling bit, Cout_g % 128
+                              == 0: the producer / consumer form): the window's columns -1 and T hold x'[0] and x'[T-1] instead of
+                              zeros (the polyphase weight gradient) */
+    int32_t pro_Bp;
+    int32_t form;          /* which kernel family; anything else: NEF_E_UNSUPPORTED.
+                            * 0: the direct fp32 kernel.  K == 1, 3 or 7; a prologue (pro_mode 1..3) only with K == 3 and in_scale ==
+                            *    NULL, T even with the upsampling bit.
+                            * 4: the TRANSPOSED Winograd algorithm (in_scale or the input prologue); fp32 multiplies and adds on the
+                            *    matrix cores, results differ from the direct form by the rounding of the transforms.  Needs T even and
+                            *    T >= 64; K == 7: pro_mode 0.
+                            *      K == 3: transposed F(3,4), 6 multiplies per four columns -- 1/2 of the direct form's; transform entries
+                            *              up to 8 and 1/24 (the F(4,3) matrices of the forward kernels, roles exchanged): measured
+                            *              rounding 1..6x the direct form's.
+                            *      K == 7: the taps split 4 + 3 across TWO launches, transposed F(4,4) + transposed F(3,4): 13 multiplies
+                            *              per 8 columns (direct: 28).
+                            *    Which kernel runs: the (gy, x) tiles are streamed by LDS-DMA through a ring of LDS buffers
+                            *    (csrc/conv_bww_glds.hip) when in_scale == NULL, both channel counts are multiples of 64, T >= 64, T % 4
+                            *    == 0 if pro_mode has the upsampling bit, not both prologue bits at once, and at most 8 BatchNorm
+                            *    passes (B / pro_Bp); otherwise the register-staged kernel of csrc/conv_mfma.hip.  Same arithmetic and
+                            *    partial-sum layout; the two differ only by the summation order across splits.  The kernel never reads
+                            *    outside [x, x + (B-1)*x_bs + (G-1)*x_gs + Cin_g*T) resp. the same extent of gy.  (ABI <= 11 also had
+                            *    nef_conv_bwd_weight_wino, the transposed F(3,2): removed, this form covers every shape it took.)
+                            * 3: exact fp16 splits of BOTH operands (csrc/conv_h2w.hip; the arithmetic of nef_pack_weight_h2 / conv
+                            *    args wino = 3, the same family: gy = gh + gl, X = xh + xl, three fp16 matrix instructions per product,
+                            *    fp32 accumulation): fp32-class results (closer to fp64 than the transposed-Winograd forms) at 3/16 of
+                            *    the fp32 matrix instructions' pipe time.  K == 3 (any pro_mode) or K == 7 (pro_mode 0), T even and
+                            *    >= 64, both channel counts multiples of 64; in_scale only with pro_mode 0. */
+    float x_scale;         /* form 3: 0 (= 1) or the exact powers of two the operands are multiplied by before they are split (their */
+    float gy_scale;        /* product is divided out) */
+    int32_t reserved0;
+} nef_bww_args;
 
-/* The same weight gradient (either form above: in_scale or the input prologue) through the TRANSPOSED Winograd algorithm;
- * fp32 multiplies and adds on the matrix cores, results differ from the direct form by the rounding of the transforms.
- * Needs T even and T >= 64; K == 7: pro_mode 0.  Workspace as for nef_conv_bwd_weight.
- *   K == 3: transposed F(3,4), 6 multiplies per four columns -- 1/2 of the direct form's; transform entries up to 8 and 1/24
- *           (the F(4,3) matrices of the forward kernels, roles exchanged): measured rounding 1..6x the direct form's.
- *   K == 7: the taps split 4 + 3 across TWO launches, transposed F(4,4) + transposed F(3,4): 13 multiplies per 8 columns
- *           (direct: 28).
- * Which kernel runs: the (gy, x) tiles are streamed by LDS-DMA through a ring of LDS buffers (csrc/conv_bww_glds.hip) when
- * in_scale == NULL, both channel counts are multiples of 64, T >= 64, T % 4 == 0 if pro_mode has the upsampling bit, not
- * both prologue bits at once, and at most 8 BatchNorm passes (B / pro_Bp); otherwise the register-staged kernel of
- * csrc/conv_mfma.hip.  Same arithmetic and partial-sum layout; the two differ only by the summation order across splits.
- * The kernel never reads outside [x, x + (B-1)*x_bs + (G-1)*x_gs + Cin_g*T) resp. the same extent of gy.
- * (ABI <= 11 also had nef_conv_bwd_weight_wino, the transposed F(3,2): removed, this entry covers every shape it took.) */
-int nef_conv_bwd_weight_wino4(const float* x, int64_t x_bs, int64_t x_gs, const float* in_scale, int64_t sc_bs,
-                              int64_t sc_gs, const float* pro_a, const float* pro_b, int pro_mode, int pro_Bp,
-                              const float* gy, int64_t gy_bs, int64_t gy_gs, float* gw, void* ws, size_t ws_bytes, int B, int T,
-                              int G, int Cin_g, int Cout_g, int K, nef_stream_t stream);
-
-/* The same weight gradient on exact fp16 splits of BOTH operands (csrc/conv_h2w.hip; the arithmetic of nef_pack_weight_h2 /
- * conv args wino = 3: gy = gh + gl, X = xh + xl, three fp16 matrix instructions per product, fp32 accumulation): fp32-class
- * results (closer to fp64 than the transposed-Winograd forms) at 3/16 of the fp32 matrix instructions' pipe time.  K == 3 (any
- * pro_mode) or K == 7 (pro_mode 0), T even and >= 64, both channel counts multiples of 64; in_scale only with pro_mode 0.
- * x_scale / gy_scale: 0 (= 1) or the exact powers of two the operands are multiplied by before they are split (their product is
- * divided out); x_amax / gy_amax: NULL, or device words with the largest |operand| the call site saw before -- when positive and
- * finite the scales are derived from them instead; x_amax_next / gy_amax_next: both NULL, or device words this launch
- * max-accumulates its operands' magnitudes into; clamped: NULL, or a device counter incremented when a scaled operand element
- * had to be clamped at fp16's range (see nef_conv_args.x_clamped).  ws: nef_conv_bwd_weight_h2_ws_bytes(...) bytes (split partial sums, added up in a
- * fixed order). */
-size_t nef_conv_bwd_weight_h2_ws_bytes(int B, int T, int G, int Cin_g, int Cout_g, int K);
-int nef_conv_bwd_weight_h2(const float* x, int64_t x_bs, int64_t x_gs, const float* in_scale, int64_t sc_bs, int64_t sc_gs,
-                           const float* pro_a, const float* pro_b, int pro_mode, int pro_Bp, const float* gy, int64_t gy_bs,
-                           int64_t gy_gs, float* gw, void* ws, size_t ws_bytes, int B, int T, int G, int Cin_g, int Cout_g, int K,
-                           float x_scale, float gy_scale, const float* x_amax, const float* gy_amax, float* x_amax_next,
-                           float* gy_amax_next, int32_t* clamped, nef_stream_t stream);
+int nef_conv_bwd_weight(const nef_bww_args* a, nef_stream_t stream);
+/* Reads form, B, T, G, Cin_g, Cout_g, K only; 0: unsupported shape or form.  Forms 0 and 4: the split bound of the prologue-free
+ * direct plan (no plan with a prologue or a Winograd form has more splits); form 3: sized for whichever tile form the launch's
+ * prologue mode takes (the largest over the modes). */
+size_t nef_conv_bwd_weight_ws_bytes(const nef_bww_args* a);
+/* sizeof(nef_bww_args) as the library was built: a binding checks its mirror of the struct against it. */
+size_t nef_bww_args_bytes(void);
 
 /* Heavy-tail census of one split-fp16 operand (ops._note_tail, once per call site, at its measuring launch; no counterpart in the
  * reference, whose fp32 convs keep every element's bits).  The operand is described as the launch reads it: the view
@@ -270,9 +289,9 @@ int nef_h2_tail_census(const float* x, int64_t x_bs, int64_t x_gs, int B, int G,
                        float frac, void* ws, size_t ws_bytes, nef_h2_tail_census_out* out, int32_t* site_flag, float* tail_stat,
                        nef_stream_t stream);
 /* gw [G Cout_g][Cin_g][3] += the row-end terms by which a K = 3 weight gradient over a window continued with x'[0] / x'[T-1] at both
- * row ends (nef_conv_bwd_weight_h2 pro_mode bit 2) differs from the zero-padded one: gw[r][ci][0] += sum_b gy[b][r][0] xedge[b][ci][0],
+ * row ends (nef_bww_args form 3, pro_mode bit 2) differs from the zero-padded one: gw[r][ci][0] += sum_b gy[b][r][0] xedge[b][ci][0],
  * gw[r][ci][2] += sum_b gy[b][r][T-1] xedge[b][ci][1]; xedge [B][G Cin_g][2] = x' (the prologue's output) at both row ends, as
- * nef_poly_fwd_edge writes it.  After an fp32 weight gradient (nef_conv_bwd_weight / _pro) with pro_mode & 1 this gives the polyphase
+ * nef_poly_fwd_edge writes it.  After an fp32 weight gradient (nef_bww_args form 0) with pro_mode & 1 this gives the polyphase
  * phase-weight gradient that nef_poly_wgrad_fold takes (the fp32 route of a heavy-tailed site).  Cout_g % 16 == 0; samples summed
  * in order, no atomics. */
 int nef_bwd_weight_clamp_ends(const float* xedge, const float* gy, int64_t gy_bs, int64_t gy_gs, float* gw, int B, int T, int G,
@@ -528,7 +547,7 @@ size_t nef_grad_clip_ws_bytes(void);
 int nef_grad_clip(float* g, int64_t n, float max_norm, float gscale,
                   float* taint /* NULL, or the device word in front of the flat gradients (nef_h2_taint's output) */,
                   float* stats /* 4 device floats */, void* ws, size_t ws_bytes, nef_stream_t stream);
-/* The split-fp16 convolutions (conv args wino = 3, nef_conv_bwd_weight_h2) count the waves that had to clamp an operand at fp16's
+/* The split-fp16 convolutions (conv args wino = 3, nef_bww_args form 3) count the waves that had to clamp an operand at fp16's
  * range in a device counter (x_clamped); such a launch's results are wrong.  nef_h2_taint writes out[0] = (float)(*clamped_total -
  * *mark) -- the clamps since the previous call -- and sets *mark = *clamped_total: called once per train step behind the backward
  * pass, its output word travels with the gradients (summed by the data-parallel all-reduce, so every rank sees a clamp on any rank)
@@ -579,7 +598,7 @@ int nef_poly_bwd_edge(const float* gy, const float* w /* [G Cog][Cig][3], the co
  * nef_bn_relu_bwd_combine3 writing row r of their output as the two half-length rows 2 r (even positions) and 2 r + 1 (odd
  * positions) of a [.., 2 C, L / 2] tensor (L % 4 == 0 resp. L % 2 == 0).  That is the operand the polyphase backward passes of the
  * conv behind the upsampling want: backward-data = a PLAIN nef_conv_fwd over it (weights nef_poly_weights, transposed / flipped)
- * + nef_poly_bwd_edge(gy_phase_major = 1); weight gradient = nef_conv_bwd_weight_h2 with pro_mode 4 (| 1: affine prologue; bit 2 =
+ * + nef_poly_bwd_edge(gy_phase_major = 1); weight gradient = nef_conv_bwd_weight, form 3, with pro_mode 4 (| 1: affine prologue; bit 2 =
  * the half-resolution x window is continued with x[0] / x[T-1] at the row ends) giving gw2 [G 2 Cog][Cig][3], then
  * nef_poly_wgrad_fold: gw2 folded back onto the conv's own taps minus the row-end terms (xedge [B][G Cig][2] = the prologue's
  * output at the first / last position, written by nef_poly_fwd_edge). */

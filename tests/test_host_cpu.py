@@ -14,7 +14,7 @@ from util import free_port
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_header_symbols_exported_abi_19():
+def test_header_symbols_exported_abi_20():
     """The shared library loads and exports every function include/nefnet_hip.h declares (no compute calls)."""
     from electrocardio_panorama_amd import _lib
     from electrocardio_panorama_amd.csrc import build
@@ -25,18 +25,30 @@ def test_header_symbols_exported_abi_19():
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name), name
-    assert _lib.load().nef_abi_version() == 19
+    assert _lib.load().nef_abi_version() == 20
     assert ctypes.sizeof(_lib.ConvArgs) == 384 == _lib.load().nef_conv_args_bytes()
+    assert ctypes.sizeof(_lib.BwwArgs) == 200 == _lib.load().nef_bww_args_bytes()
 
 
 def test_rejects_bad_calls_without_touching_the_gpu():
     from electrocardio_panorama_amd import _lib
     L = _lib.load()
     assert L.nef_stem_fwd(None, None, None, 1, 1, 512, None) == -2            # NEF_E_NULL
-    assert L.nef_conv_bwd_weight_ws_bytes(2, 100, 3, 100, 128, 3) == 0        # unsupported channel count
-    assert L.nef_conv_bwd_weight_ws_bytes(2, 100, 3, 128, 128, 7) > 0
+    def bww(form=0, Cin_g=128, K=7, **kw):      # the weight gradient's struct; dummy non-null pointers: nothing is launched
+        w = _lib.BwwArgs(x=8, gy=8, gw=8, ws=8, ws_bytes=1 << 40, B=2, T=100, G=3, Cin_g=Cin_g, Cout_g=128, K=K, form=form)
+        for k, v in kw.items():
+            setattr(w, k, v)
+        return ctypes.byref(w)
+    assert L.nef_conv_bwd_weight_ws_bytes(bww(Cin_g=100, K=3)) == 0           # unsupported channel count
+    assert L.nef_conv_bwd_weight_ws_bytes(bww()) > 0
     a = _lib.ConvArgs()
     assert L.nef_conv_fwd(ctypes.byref(a), None) == -2
+    assert L.nef_conv_bwd_weight(ctypes.byref(_lib.BwwArgs()), None) == -2
+    assert L.nef_conv_bwd_weight(bww(form=9), None) == -4                     # NEF_E_UNSUPPORTED: no such kernel family
+    assert L.nef_conv_bwd_weight(bww(K=3, pro_mode=1, pro_a=8, pro_b=8, pro_Bp=1, in_scale=8), None) == -4      # prologue + in_scale
+    assert L.nef_conv_bwd_weight(bww(ws_bytes=0), None) == -3                 # NEF_E_WORKSPACE
+    assert L.nef_conv_bwd_weight(bww(form=3, x_amax_next=8), None) == -2      # the two *_amax_next words go together
+    assert L.nef_conv_bwd_weight(bww(form=3, gy_amax_next=8), None) == -2
 
 
 def test_config_surface():

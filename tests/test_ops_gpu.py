@@ -1116,8 +1116,10 @@ def test_conv_bwd_weight_winograd(K, G, Cig, Cog, T, B, form):
     assert torch.equal(gw, o.conv_bwd_weight(GV.dense(xd, G), GV.dense(gyd, G), K, wino=form))      # deterministic
 
 
-@pytest.mark.parametrize("form", [4])
+@pytest.mark.parametrize("form", [4, False])
 def test_conv_bwd_weight_winograd_views_scale_and_prologues(form):
+    """Strided half views + in_scale, and the three decoder prologues, through the transposed Winograd form (4) and the direct
+    fp32 kernel (False: the one body behind nef_bww_args form 0, with and without a prologue)."""
     o = ops()
     from electrocardio_panorama_amd.ops import GV
     B, V, T, K = 2, 3, 250, 3
