@@ -49,6 +49,15 @@ class BwwArgs(C.Structure):
     ]
 
 
+class BnBwdArgs(C.Structure):
+    """Mirror of `nef_bn_bwd_args` (include/nefnet_hip.h)."""
+    _fields_ = [
+        ("g", p), ("gout", p), ("out", p), ("wout", p), ("x", p), ("mean", p), ("invstd", p), ("a", p), ("b", p),
+        ("gx", p), ("ggamma", p), ("gbeta", p), ("gx_chan_sum", p), ("slots", p), ("ws", p), ("ws_bytes", sz),
+        ("P", i32), ("Bp", i32), ("C", i32), ("L", i32), ("nslot", i32), ("form", i32), ("phase_major", i32), ("reserved0", i32),
+    ]
+
+
 class PackDesc(C.Structure):
     """Mirror of `nef_pack_desc` (include/nefnet_hip.h)."""
     _fields_ = [("w", p), ("wp", p), ("G", i32), ("Cog", i32), ("Cig", i32), ("K", i32), ("transpose_flip", i32),
@@ -101,16 +110,13 @@ SIGNATURES = {
     "nef_roi_segment_table": (i32, [p, p, p, i32, p]),
     "nef_lead_mean": (i32, [p, p, p, i32, i32, i32, p]),
     "nef_mix_fwd": (i32, [p, p, p, p, p, i32, i32, i32, i32, i32, p, p]),
-    "nef_mix_bwd": (i32, [p, p, p, p, p, p, p, p, i32, i32, i32, i32, i32, p, i32, p]),
+    "nef_mix_bwd": (i32, [p, p, p, p, p, p, p, p, i32, i32, i32, i32, i32, p, i32, i32, i32, p]),
     "nef_mix_fwd_shared": (i32, [p, p, p, p, p, i32, i32, i32, i32, i32, p, p]),
     "nef_lead_mean_mix_shared": (i32, [p, p, p, p, p, i32, i32, i32, i32, i32, p, p]),
-    "nef_mix_bwd_shared_up": (i32, [p, p, p, p, p, p, p, p, i32, i32, i32, i32, i32, p, i32, p]),
-    "nef_mix_bwd_shared": (i32, [p, p, p, p, p, p, p, p, i32, i32, i32, i32, i32, p, i32, p]),
     "nef_pass_combine_fwd": (i32, [p, p, p, i32, i32, i32, p]),
     "nef_pass_combine_bwd": (i32, [p, p, i32, i32, i32, p]),
     "nef_pass_combine_stats_ws_bytes": (sz, [i32, i32]),
     "nef_pass_combine_fwd_stats": (i32, [p, p, p, p, p, p, p, p, p, p, p, p, sz, i32, i32, i32, f32, f32, p, p]),
-    "nef_mix_bwd_up": (i32, [p, p, p, p, p, p, p, p, i32, i32, i32, i32, i32, p, i32, p]),
     "nef_upsample2_fwd": (i32, [p, p, i64, i32, p]),
     "nef_upsample2_bwd": (i32, [p, p, i64, i32, p]),
     "nef_bn_ws_bytes": (sz, [i32, i32]),
@@ -120,20 +126,13 @@ SIGNATURES = {
     "nef_bn_eval_affine": (i32, [p, p, p, p, p, p, i32, f32, p]),
     "nef_fold_bn": (i32, [p, p, p, p, p, p, i32, i32, p]),
     "nef_affine_relu_fwd": (i32, [p, p, p, p, i32, i32, i32, i32, p]),
-    "nef_bn_bwd_ws_bytes": (sz, [i32, i32, i32]),
-    "nef_bn_relu_bwd": (i32, [p, p, p, p, p, p, p, p, p, p, p, p, sz, i32, i32, i32, i32, p, i32, p]),
-    "nef_bn_relu_bwd_phase_major": (i32, [p, p, p, p, p, p, p, p, p, p, p, p, sz, i32, i32, i32, i32, p, i32, p]),
-    "nef_bn_relu_bwd_up": (i32, [p, p, p, p, p, p, p, p, p, p, p, sz, i32, i32, i32, i32, p, i32, p]),
-    "nef_bn_relu_bwd_combine3": (i32, [p, p, p, p, p, p, p, p, p, p, p, sz, i32, i32, i32, p, i32, p]),
-    "nef_bn_relu_bwd_combine3_phase_major": (i32, [p, p, p, p, p, p, p, p, p, p, p, sz, i32, i32, i32, p, i32, p]),
-    "nef_bn_bwd_outconv_ws_bytes": (sz, [i32, i32, i32, i32]),
-    "nef_bn_relu_bwd_outconv": (i32, [p, p, p, p, p, p, p, p, p, p, p, p, p, sz, i32, i32, i32, i32, p]),
-    "nef_outconv_fwd": (i32, [p, p, p, p, i32, i32, i32, p]),
-    "nef_outconv_fwd_pro": (i32, [p, p, p, i32, p, p, p, i32, i32, i32, p]),
-    "nef_outconv_bwd_weight_pro": (i32, [p, p, p, p, p, i32, p, p, p, sz, i32, i32, i32, p]),
+    "nef_bn_bwd_ws_bytes": (sz, [C.POINTER(BnBwdArgs)]),
+    "nef_bn_relu_bwd": (i32, [C.POINTER(BnBwdArgs), p]),
+    "nef_bn_bwd_args_bytes": (sz, []),
+    "nef_outconv_fwd": (i32, [p, p, p, i32, p, p, p, i32, i32, i32, p]),
+    "nef_outconv_bwd_weight": (i32, [p, p, p, p, p, i32, p, p, p, sz, i32, i32, i32, p]),
     "nef_outconv_bwd_data": (i32, [p, p, p, p, i32, i32, i32, p]),
     "nef_outconv_bwd_weight_ws_bytes": (sz, [i32]),
-    "nef_outconv_bwd_weight": (i32, [p, p, p, p, p, p, sz, i32, i32, i32, p]),
     "nef_loss_ws_bytes": (sz, []),
     "nef_loss_fwd": (i32, [p, p, p, p, p, p, sz, i64, f32, f32, f32, i32, i32, p]),
     "nef_loss_bwd": (i32, [p, p, p, p, p, p, p, p, i64, f32, f32, f32, i32, i32, p]),
@@ -185,7 +184,8 @@ def load():
         fn.argtypes = args
     # a stale .so next to a newer binding (or the reverse)
     for name, size, mirror in (("nef_conv_args", lib.nef_conv_args_bytes(), ConvArgs),
-                               ("nef_bww_args", lib.nef_bww_args_bytes(), BwwArgs)):
+                               ("nef_bww_args", lib.nef_bww_args_bytes(), BwwArgs),
+                               ("nef_bn_bwd_args", lib.nef_bn_bwd_args_bytes(), BnBwdArgs)):
         if size != C.sizeof(mirror):
             raise NefLibraryError(f"{LIB_PATH}: {name} is {size} bytes, the binding mirrors {C.sizeof(mirror)}; rebuild with "
                                   "`python -m electrocardio_panorama_amd.csrc.build`")

@@ -2222,7 +2222,7 @@ __attribute__((visibility("hidden"))) int nef_mfma_wino_fwd(const nef_conv_args*
 #if NEF_PART(1)
 extern "C" {
 
-int nef_abi_version(void) { return 20; }
+int nef_abi_version(void) { return 21; }
 
 int nef_pack_weight(const float* w, float* wp, int G, int Cog, int Cig, int K, int transpose_flip,
                     nef_stream_t stream) {

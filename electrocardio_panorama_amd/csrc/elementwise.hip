@@ -1672,33 +1672,6 @@ __global__ void h2_taint_kernel(const int32_t* __restrict__ total, int32_t* __re
 
 extern "C" {
 
-int nef_mix_bwd_shared(const float* gD2, const float* latent, const float* z1, const float* z2r, const float* q,
-                       float* gz1, float* gz2r, float* gq, int B, int V, int T, int c1, int c2,
-                       const int32_t* choice_dev, int relu_z1, nef_stream_t stream) {
-    NEF_ENTER();
-    NEF_REQUIRE(gD2 && latent && z1 && z2r && q && gz1 && gz2r && gq, NEF_E_NULL);
-    NEF_REQUIRE(B > 0 && V > 0 && T > 1 && c1 >= 0 && c1 < V && c2 >= 0 && c2 < V, NEF_E_SHAPE);
-    const bool al16 = (((uintptr_t)gD2 | (uintptr_t)latent | (uintptr_t)z1 | (uintptr_t)z2r | (uintptr_t)gz1 | (uintptr_t)gz2r) & 15) == 0;
-    if (T % 4 == 2 && T >= 8 && al16)
-        hipLaunchKernelGGL(mix_bwd_shared_pair_kernel, dim3(nef_stream_grid((int64_t)B * 128, 4)), dim3(256), 0, NEF_ST, gD2, latent, z1,
-                           z2r, q, gz1, gz2r, gq, B, V, T, c1, c2, choice_dev, relu_z1);
-    else
-        hipLaunchKernelGGL((mix_bwd_kernel<false, true>), dim3(nef_stream_grid((int64_t)B * 256, 4)), dim3(256), 0, NEF_ST, gD2,
-                           latent, z1, z2r, q, gz1, gz2r, gq, B, V, T, c1, c2, choice_dev, relu_z1);
-    return nef_launch_status();
-}
-
-int nef_mix_bwd_shared_up(const float* gU2, const float* latent, const float* z1, const float* z2r, const float* q,
-                          float* gz1, float* gz2r, float* gq, int B, int V, int T, int c1, int c2,
-                          const int32_t* choice_dev, int relu_z1, nef_stream_t stream) {
-    NEF_ENTER();
-    NEF_REQUIRE(gU2 && latent && z1 && z2r && q && gz1 && gz2r && gq, NEF_E_NULL);
-    NEF_REQUIRE(B > 0 && V > 0 && T > 1 && c1 >= 0 && c1 < V && c2 >= 0 && c2 < V, NEF_E_SHAPE);
-    hipLaunchKernelGGL((mix_bwd_kernel<true, true>), dim3(nef_stream_grid((int64_t)B * 256, 4)), dim3(256), 0, NEF_ST, gU2,
-                       latent, z1, z2r, q, gz1, gz2r, gq, B, V, T, c1, c2, choice_dev, relu_z1);
-    return nef_launch_status();
-}
-
 // ------------------------------------------------------------------------------------------------
 // First decoder conv shared between the three Standin passes: P2 [2B][2C][L] holds, per sample n, the half-conv of
 // the z1-type half (channels 0..C) and of the z2-type half (C..2C) of input n (n < B: the lead means, n >= B: the picked
@@ -2043,24 +2016,23 @@ int nef_lead_mean_mix_shared(const float* z1, const float* z2r, const float* q, 
 }
 
 int nef_mix_bwd(const float* gD, const float* latent, const float* z1, const float* z2r, const float* q, float* gz1,
-                float* gz2r, float* gq, int B, int V, int T, int c1, int c2, const int32_t* choice_dev, int relu_z1,
-                nef_stream_t stream) {
+                float* gz2r, float* gq, int B, int V, int T, int c1, int c2, const int32_t* choice_dev, int relu_z1, int up,
+                int shared, nef_stream_t stream) {
     NEF_ENTER();
     NEF_REQUIRE(gD && latent && z1 && z2r && q && gz1 && gz2r && gq, NEF_E_NULL);
-    NEF_REQUIRE(B > 0 && V > 0 && T > 0 && c1 >= 0 && c1 < V && c2 >= 0 && c2 < V, NEF_E_SHAPE);
-    hipLaunchKernelGGL((mix_bwd_kernel<false, false>), dim3(nef_stream_grid((int64_t)B * 256, 4)), dim3(256), 0, NEF_ST, gD, latent,
-                       z1, z2r, q, gz1, gz2r, gq, B, V, T, c1, c2, choice_dev, relu_z1);
-    return nef_launch_status();
-}
-
-int nef_mix_bwd_up(const float* gU, const float* latent, const float* z1, const float* z2r, const float* q, float* gz1,
-                   float* gz2r, float* gq, int B, int V, int T, int c1, int c2, const int32_t* choice_dev, int relu_z1,
-                   nef_stream_t stream) {
-    NEF_ENTER();
-    NEF_REQUIRE(gU && latent && z1 && z2r && q && gz1 && gz2r && gq, NEF_E_NULL);
-    NEF_REQUIRE(B > 0 && V > 0 && T > 1 && c1 >= 0 && c1 < V && c2 >= 0 && c2 < V, NEF_E_SHAPE);
-    hipLaunchKernelGGL((mix_bwd_kernel<true, false>), dim3(nef_stream_grid((int64_t)B * 256, 4)), dim3(256), 0, NEF_ST, gU, latent,
-                       z1, z2r, q, gz1, gz2r, gq, B, V, T, c1, c2, choice_dev, relu_z1);
+    NEF_REQUIRE(B > 0 && V > 0 && T > (up || shared ? 1 : 0) && c1 >= 0 && c1 < V && c2 >= 0 && c2 < V, NEF_E_SHAPE);
+    const bool al16 = (((uintptr_t)gD | (uintptr_t)latent | (uintptr_t)z1 | (uintptr_t)z2r | (uintptr_t)gz1 | (uintptr_t)gz2r) & 15) == 0;
+#define NEF_MIX_BWD(UP, SHARED)                                                                                                \
+    hipLaunchKernelGGL((mix_bwd_kernel<UP, SHARED>), dim3(nef_stream_grid((int64_t)B * 256, 4)), dim3(256), 0, NEF_ST, gD, latent, \
+                       z1, z2r, q, gz1, gz2r, gq, B, V, T, c1, c2, choice_dev, relu_z1)
+    if (shared && !up && T % 4 == 2 && T >= 8 && al16)
+        hipLaunchKernelGGL(mix_bwd_shared_pair_kernel, dim3(nef_stream_grid((int64_t)B * 128, 4)), dim3(256), 0, NEF_ST, gD, latent, z1,
+                           z2r, q, gz1, gz2r, gq, B, V, T, c1, c2, choice_dev, relu_z1);
+    else if (shared && up) NEF_MIX_BWD(true, true);
+    else if (shared) NEF_MIX_BWD(false, true);
+    else if (up) NEF_MIX_BWD(true, false);
+    else NEF_MIX_BWD(false, false);
+#undef NEF_MIX_BWD
     return nef_launch_status();
 }
 
@@ -2165,165 +2137,90 @@ int nef_affine_relu_fwd(const float* x, const float* a, const float* b, float* y
     return nef_launch_status();
 }
 
-size_t nef_bn_bwd_ws_bytes(int P, int Bp, int C) { return nef_bn_ws_bytes(P, C) + (size_t)P * Bp * C * sizeof(double); }
+size_t nef_bn_bwd_args_bytes(void) { return sizeof(nef_bn_bwd_args); }
 
-static int bn_relu_bwd_impl(const float* gy, const float* x, const float* gamma, const float* mean, const float* invstd,
-                            const float* a, const float* b, float* gx, float* ggamma, float* gbeta, float* gx_chan_sum, void* ws,
-                            size_t ws_bytes, int P, int Bp, int C, int L, const float* slots, int nslot, int deint,
-                            nef_stream_t stream) {
+size_t nef_bn_bwd_ws_bytes(const nef_bn_bwd_args* a) {
+    if (!a || a->form < 0 || a->form > 3 || a->P <= 0 || a->Bp <= 0 || a->C <= 0 || a->L <= 0) return 0;
+    const size_t go = a->form == 1 ? (size_t)a->P * a->Bp * a->L * sizeof(float) : 0;      // form 1: go [P*Bp][L] behind the rest
+    return nef_bn_ws_bytes(a->P, a->C) + (size_t)a->P * a->Bp * a->C * sizeof(double) + go;
+}
+
+int nef_bn_relu_bwd(const nef_bn_bwd_args* args, nef_stream_t stream) {
     NEF_ENTER();
-    (void)gamma;
-    NEF_REQUIRE(gy && x && mean && invstd && a && b && gx && ggamma && gbeta && ws, NEF_E_NULL);
+    NEF_REQUIRE(args, NEF_E_NULL);
+    const nef_bn_bwd_args& a = *args;
+    const int P = a.P, Bp = a.Bp, C = a.C, L = a.L, form = a.form, deint = a.phase_major;
+    NEF_REQUIRE(a.x && a.mean && a.invstd && a.a && a.b && a.gx && a.ggamma && a.gbeta && a.ws, NEF_E_NULL);
+    NEF_REQUIRE(form >= 0 && form <= 3, NEF_E_UNSUPPORTED);
+    if (form == 1) {
+        NEF_REQUIRE(a.gout && a.out && a.wout, NEF_E_NULL);
+        NEF_REQUIRE(!a.g && !a.slots && !deint, NEF_E_UNSUPPORTED);
+    } else {
+        NEF_REQUIRE(a.g, NEF_E_NULL);
+        NEF_REQUIRE(!a.gout && !a.out && !a.wout && !(form == 2 && deint), NEF_E_UNSUPPORTED);
+    }
     NEF_REQUIRE(P > 0 && Bp > 0 && C > 0 && L > 0, NEF_E_SHAPE);
-    NEF_REQUIRE(!deint || ((L & 3) == 0 && (int64_t)P * Bp * C <= 0x7FFFFFFF), NEF_E_SHAPE);
-    NEF_REQUIRE(!slots || (nslot > 0 && (int64_t)Bp * nslot <= 0x7FFFFFFF), NEF_E_SHAPE);
-    NEF_REQUIRE(ws_bytes >= nef_bn_bwd_ws_bytes(P, Bp, C), NEF_E_WORKSPACE);
-    double* part = (double*)ws;
-    float* coef = (float*)((char*)ws + (size_t)P * C * BN_SPLIT * 2 * sizeof(double));
-    double* rowsum = gx_chan_sum ? (double*)((char*)ws + nef_bn_ws_bytes(P, C)) : nullptr;
-    if (slots) {        // the producing conv left the sums per slot: add them up in fp64, fixed order
-        hipLaunchKernelGGL(bn_slots_bwd_fused, dim3((unsigned)C), dim3(BNF_THREADS), 0, NEF_ST, slots, coef, ggamma, gbeta, P, Bp, C, L, Bp * nslot);
-    } else {
-        hipLaunchKernelGGL(bn_bwd_partial<0>, dim3(P * C * BN_SPLIT), dim3(256), 0, NEF_ST, gy, x, mean, invstd, a, b, part,
-                           P, Bp, C, L, (const float*)nullptr);
-        hipLaunchKernelGGL(bn_bwd_final, dim3((C + 63) / 64), dim3(64), 0, NEF_ST, (const double*)part, coef, ggamma,
-                           gbeta, P, Bp, C, L, BN_SPLIT);
-    }
+    NEF_REQUIRE(form != 3 || P == 3, NEF_E_UNSUPPORTED);
     const int64_t rows = (int64_t)P * Bp * C;
-    if ((L & 3) == 0 && rows <= 0x7FFFFFFF)
-        hipLaunchKernelGGL(bn_bwd_apply_rows<0>, dim3((unsigned)rows), dim3(256), 0, NEF_ST, gy, x, mean, invstd, a, b,
-                           (const float*)coef, gx, rowsum, Bp, C, L >> 2, (const float*)nullptr, deint);
+    const bool by_rows = (L & 3) == 0 && rows <= 0x7FFFFFFF;        // what bn_bwd_apply_rows takes
+    switch (form) {
+    case 0: NEF_REQUIRE(!deint || by_rows, NEF_E_SHAPE); break;     // without phase_major, bn_bwd_apply takes the rest
+    case 1: NEF_REQUIRE(by_rows, NEF_E_SHAPE); break;
+    case 2: NEF_REQUIRE(by_rows && L >= 8, NEF_E_SHAPE); break;
+    case 3: NEF_REQUIRE((int64_t)Bp * C <= 0x7FFFFFFF && (!deint || (L & 1) == 0), NEF_E_SHAPE); break;
+    }
+    NEF_REQUIRE(!a.slots || (a.nslot > 0 && (int64_t)Bp * a.nslot <= 0x7FFFFFFF), NEF_E_SHAPE);
+    NEF_REQUIRE(a.ws_bytes >= nef_bn_bwd_ws_bytes(args), NEF_E_WORKSPACE);
+    double* part = (double*)a.ws;
+    float* coef = (float*)((char*)a.ws + (size_t)P * C * BN_SPLIT * 2 * sizeof(double));
+    double* rowsum = a.gx_chan_sum ? (double*)((char*)a.ws + nef_bn_ws_bytes(P, C)) : nullptr;
+    const float* g = a.g;
+    if (form == 1) {        // go = gout*out*(1-out)/3 [P*Bp][L]: the kernels rebuild the last conv's input gradient from it while reading
+        float* go = (float*)((char*)a.ws + nef_bn_ws_bytes(P, C) + (size_t)rows * sizeof(double));
+        const int64_t n = (int64_t)P * Bp * L;
+        hipLaunchKernelGGL(outconv_go_kernel, dim3(nef_stream_grid(n, 256)), dim3(256), 0, NEF_ST, a.gout, a.out, go, n);
+        g = go;
+    }
+    if (a.slots) {          // the producing conv left the sums per slot: add them up in fp64, fixed order
+        hipLaunchKernelGGL(bn_slots_bwd_fused, dim3((unsigned)C), dim3(BNF_THREADS), 0, NEF_ST, a.slots, coef, a.ggamma, a.gbeta, P, Bp, C,
+                           L, Bp * a.nslot);
+    } else {
+        const dim3 grid(P * C * BN_SPLIT);
+        if (form == 1)
+            hipLaunchKernelGGL(bn_bwd_partial<1>, grid, dim3(256), 0, NEF_ST, g, a.x, a.mean, a.invstd, a.a, a.b, part, P, Bp, C, L,
+                               a.wout);
+        else if (form == 2)
+            hipLaunchKernelGGL(bn_bwd_partial<2>, grid, dim3(256), 0, NEF_ST, g, a.x, a.mean, a.invstd, a.a, a.b, part, P, Bp, C, L,
+                               (const float*)nullptr);
+        else
+            hipLaunchKernelGGL(bn_bwd_partial<0>, grid, dim3(256), 0, NEF_ST, g, a.x, a.mean, a.invstd, a.a, a.b, part, P, Bp, C, L,
+                               (const float*)nullptr);
+        hipLaunchKernelGGL(bn_bwd_final, dim3((C + 63) / 64), dim3(64), 0, NEF_ST, (const double*)part, coef, a.ggamma, a.gbeta, P, Bp, C,
+                           L, BN_SPLIT);
+    }
+    const dim3 grid((unsigned)rows);
+    if (form == 3)
+        hipLaunchKernelGGL(bn_bwd_apply_combine3, dim3((unsigned)(Bp * C)), dim3(256), 0, NEF_ST, g, a.x, a.mean, a.invstd, a.a, a.b,
+                           (const float*)coef, a.gx, rowsum, Bp, C, L, deint);
+    else if (form == 2)
+        hipLaunchKernelGGL(bn_bwd_apply_rows<2>, grid, dim3(256), 0, NEF_ST, g, a.x, a.mean, a.invstd, a.a, a.b, (const float*)coef, a.gx,
+                           rowsum, Bp, C, L >> 2, (const float*)nullptr);
+    else if (form == 1)
+        hipLaunchKernelGGL(bn_bwd_apply_rows<1>, grid, dim3(256), 0, NEF_ST, g, a.x, a.mean, a.invstd, a.a, a.b, (const float*)coef, a.gx,
+                           rowsum, Bp, C, L >> 2, a.wout);
+    else if (by_rows)
+        hipLaunchKernelGGL(bn_bwd_apply_rows<0>, grid, dim3(256), 0, NEF_ST, g, a.x, a.mean, a.invstd, a.a, a.b, (const float*)coef, a.gx,
+                           rowsum, Bp, C, L >> 2, (const float*)nullptr, deint);
     else
-        hipLaunchKernelGGL(bn_bwd_apply, dim3(nef_stream_grid(rows, 4)), dim3(256), 0, NEF_ST, gy, x, mean, invstd, a, b,
-                           (const float*)coef, gx, rowsum, P, Bp, C, L);
-    if (gx_chan_sum)
-        hipLaunchKernelGGL(rowsum_to_channel, dim3(C), dim3(256), 0, NEF_ST, (const double*)rowsum, gx_chan_sum,
-                           P * Bp, C);
+        hipLaunchKernelGGL(bn_bwd_apply, dim3(nef_stream_grid(rows, 4)), dim3(256), 0, NEF_ST, g, a.x, a.mean, a.invstd, a.a, a.b,
+                           (const float*)coef, a.gx, rowsum, P, Bp, C, L);
+    if (a.gx_chan_sum)
+        hipLaunchKernelGGL(rowsum_to_channel, dim3(C), dim3(256), 0, NEF_ST, (const double*)rowsum, a.gx_chan_sum, P * Bp, C);
     return nef_launch_status();
 }
 
-int nef_bn_relu_bwd(const float* gy, const float* x, const float* gamma, const float* mean, const float* invstd,
-                    const float* a, const float* b, float* gx, float* ggamma, float* gbeta, float* gx_chan_sum, void* ws,
-                    size_t ws_bytes, int P, int Bp, int C, int L, const float* slots, int nslot, nef_stream_t stream) {
-    return bn_relu_bwd_impl(gy, x, gamma, mean, invstd, a, b, gx, ggamma, gbeta, gx_chan_sum, ws, ws_bytes, P, Bp, C, L, slots, nslot, 0,
-                            stream);
-}
-
-int nef_bn_relu_bwd_phase_major(const float* gy, const float* x, const float* gamma, const float* mean, const float* invstd,
-                                const float* a, const float* b, float* gx, float* ggamma, float* gbeta, float* gx_chan_sum,
-                                void* ws, size_t ws_bytes, int P, int Bp, int C, int L, const float* slots, int nslot,
-                                nef_stream_t stream) {
-    return bn_relu_bwd_impl(gy, x, gamma, mean, invstd, a, b, gx, ggamma, gbeta, gx_chan_sum, ws, ws_bytes, P, Bp, C, L, slots, nslot, 1,
-                            stream);
-}
-
-int nef_bn_relu_bwd_up(const float* gu, const float* x, const float* mean, const float* invstd, const float* a,
-                       const float* b, float* gx, float* ggamma, float* gbeta, float* gx_chan_sum, void* ws,
-                       size_t ws_bytes, int P, int Bp, int C, int L, const float* slots, int nslot, nef_stream_t stream) {
-    NEF_ENTER();
-    NEF_REQUIRE(gu && x && mean && invstd && a && b && gx && ggamma && gbeta && ws, NEF_E_NULL);
-    NEF_REQUIRE(P > 0 && Bp > 0 && C > 0 && L >= 8 && (L & 3) == 0, NEF_E_SHAPE);
-    NEF_REQUIRE(!slots || (nslot > 0 && (int64_t)Bp * nslot <= 0x7FFFFFFF), NEF_E_SHAPE);
-    const int64_t rows = (int64_t)P * Bp * C;
-    NEF_REQUIRE(rows <= 0x7FFFFFFF, NEF_E_SHAPE);
-    NEF_REQUIRE(ws_bytes >= nef_bn_bwd_ws_bytes(P, Bp, C), NEF_E_WORKSPACE);
-    double* part = (double*)ws;
-    float* coef = (float*)((char*)ws + (size_t)P * C * BN_SPLIT * 2 * sizeof(double));
-    double* rowsum = gx_chan_sum ? (double*)((char*)ws + nef_bn_ws_bytes(P, C)) : nullptr;
-    if (slots) {
-        hipLaunchKernelGGL(bn_slots_bwd_fused, dim3((unsigned)C), dim3(BNF_THREADS), 0, NEF_ST, slots, coef, ggamma, gbeta, P, Bp, C, L, Bp * nslot);
-    } else {
-        hipLaunchKernelGGL(bn_bwd_partial<2>, dim3(P * C * BN_SPLIT), dim3(256), 0, NEF_ST, gu, x, mean, invstd, a, b, part,
-                           P, Bp, C, L, (const float*)nullptr);
-        hipLaunchKernelGGL(bn_bwd_final, dim3((C + 63) / 64), dim3(64), 0, NEF_ST, (const double*)part, coef, ggamma,
-                           gbeta, P, Bp, C, L, BN_SPLIT);
-    }
-    hipLaunchKernelGGL(bn_bwd_apply_rows<2>, dim3((unsigned)rows), dim3(256), 0, NEF_ST, gu, x, mean, invstd, a, b,
-                       (const float*)coef, gx, rowsum, Bp, C, L >> 2, (const float*)nullptr);
-    if (gx_chan_sum)
-        hipLaunchKernelGGL(rowsum_to_channel, dim3(C), dim3(256), 0, NEF_ST, (const double*)rowsum, gx_chan_sum,
-                           P * Bp, C);
-    return nef_launch_status();
-}
-
-static int bn_relu_bwd_combine3_impl(const float* gy, const float* x, const float* mean, const float* invstd, const float* a,
-                                     const float* b, float* gP2, float* ggamma, float* gbeta, float* gx_chan_sum, void* ws,
-                                     size_t ws_bytes, int Bp, int C, int L, const float* slots, int nslot, int deint,
-                                     nef_stream_t stream) {
-    NEF_ENTER();
-    NEF_REQUIRE(!deint || (L & 1) == 0, NEF_E_SHAPE);
-    NEF_REQUIRE(gy && x && mean && invstd && a && b && gP2 && ggamma && gbeta && ws, NEF_E_NULL);
-    NEF_REQUIRE(Bp > 0 && C > 0 && L > 0 && (int64_t)Bp * C <= 0x7FFFFFFF, NEF_E_SHAPE);
-    NEF_REQUIRE(!slots || (nslot > 0 && (int64_t)Bp * nslot <= 0x7FFFFFFF), NEF_E_SHAPE);
-    NEF_REQUIRE(ws_bytes >= nef_bn_bwd_ws_bytes(3, Bp, C), NEF_E_WORKSPACE);
-    double* part = (double*)ws;
-    float* coef = (float*)((char*)ws + (size_t)3 * C * BN_SPLIT * 2 * sizeof(double));
-    double* rowsum = gx_chan_sum ? (double*)((char*)ws + nef_bn_ws_bytes(3, C)) : nullptr;
-    if (slots) {
-        hipLaunchKernelGGL(bn_slots_bwd_fused, dim3((unsigned)C), dim3(BNF_THREADS), 0, NEF_ST, slots, coef, ggamma, gbeta, 3, Bp, C, L, Bp * nslot);
-    } else {
-        hipLaunchKernelGGL(bn_bwd_partial<0>, dim3(3 * C * BN_SPLIT), dim3(256), 0, NEF_ST, gy, x, mean, invstd, a, b, part,
-                           3, Bp, C, L, (const float*)nullptr);
-        hipLaunchKernelGGL(bn_bwd_final, dim3((C + 63) / 64), dim3(64), 0, NEF_ST, (const double*)part, coef, ggamma,
-                           gbeta, 3, Bp, C, L, BN_SPLIT);
-    }
-    hipLaunchKernelGGL(bn_bwd_apply_combine3, dim3((unsigned)(Bp * C)), dim3(256), 0, NEF_ST, gy, x, mean, invstd, a, b,
-                       (const float*)coef, gP2, rowsum, Bp, C, L, deint);
-    if (gx_chan_sum)
-        hipLaunchKernelGGL(rowsum_to_channel, dim3(C), dim3(256), 0, NEF_ST, (const double*)rowsum, gx_chan_sum, 3 * Bp,
-                           C);
-    return nef_launch_status();
-}
-
-int nef_bn_relu_bwd_combine3(const float* gy, const float* x, const float* mean, const float* invstd, const float* a,
-                             const float* b, float* gP2, float* ggamma, float* gbeta, float* gx_chan_sum, void* ws,
-                             size_t ws_bytes, int Bp, int C, int L, const float* slots, int nslot, nef_stream_t stream) {
-    return bn_relu_bwd_combine3_impl(gy, x, mean, invstd, a, b, gP2, ggamma, gbeta, gx_chan_sum, ws, ws_bytes, Bp, C, L, slots, nslot, 0,
-                                     stream);
-}
-
-int nef_bn_relu_bwd_combine3_phase_major(const float* gy, const float* x, const float* mean, const float* invstd, const float* a,
-                                         const float* b, float* gP2, float* ggamma, float* gbeta, float* gx_chan_sum, void* ws,
-                                         size_t ws_bytes, int Bp, int C, int L, const float* slots, int nslot,
-                                         nef_stream_t stream) {
-    return bn_relu_bwd_combine3_impl(gy, x, mean, invstd, a, b, gP2, ggamma, gbeta, gx_chan_sum, ws, ws_bytes, Bp, C, L, slots, nslot, 1,
-                                     stream);
-}
-
-size_t nef_bn_bwd_outconv_ws_bytes(int P, int Bp, int C, int L) {
-    return nef_bn_bwd_ws_bytes(P, Bp, C) + (size_t)P * Bp * L * sizeof(float);
-}
-
-int nef_bn_relu_bwd_outconv(const float* gout, const float* out, const float* wout, const float* x, const float* mean,
-                            const float* invstd, const float* a, const float* b, float* gx, float* ggamma, float* gbeta,
-                            float* gx_chan_sum, void* ws, size_t ws_bytes, int P, int Bp, int C, int L,
-                            nef_stream_t stream) {
-    NEF_ENTER();
-    NEF_REQUIRE(gout && out && wout && x && mean && invstd && a && b && gx && ggamma && gbeta && ws, NEF_E_NULL);
-    NEF_REQUIRE(P > 0 && Bp > 0 && C > 0 && L > 0 && (L & 3) == 0, NEF_E_SHAPE);
-    const int64_t rows = (int64_t)P * Bp * C;
-    NEF_REQUIRE(rows <= 0x7FFFFFFF, NEF_E_SHAPE);
-    NEF_REQUIRE(ws_bytes >= nef_bn_bwd_outconv_ws_bytes(P, Bp, C, L), NEF_E_WORKSPACE);
-    double* part = (double*)ws;
-    float* coef = (float*)((char*)ws + (size_t)P * C * BN_SPLIT * 2 * sizeof(double));
-    double* rowsum = gx_chan_sum ? (double*)((char*)ws + nef_bn_ws_bytes(P, C)) : nullptr;
-    float* go = (float*)((char*)ws + nef_bn_bwd_ws_bytes(P, Bp, C));
-    const int64_t n = (int64_t)P * Bp * L;
-    hipLaunchKernelGGL(outconv_go_kernel, dim3(nef_stream_grid(n, 256)), dim3(256), 0, NEF_ST, gout, out, go, n);
-    hipLaunchKernelGGL(bn_bwd_partial<1>, dim3(P * C * BN_SPLIT), dim3(256), 0, NEF_ST, (const float*)go, x, mean, invstd,
-                       a, b, part, P, Bp, C, L, wout);
-    hipLaunchKernelGGL(bn_bwd_final, dim3((C + 63) / 64), dim3(64), 0, NEF_ST, (const double*)part, coef, ggamma, gbeta,
-                       P, Bp, C, L);
-    hipLaunchKernelGGL(bn_bwd_apply_rows<1>, dim3((unsigned)rows), dim3(256), 0, NEF_ST, (const float*)go, x, mean,
-                       invstd, a, b, (const float*)coef, gx, rowsum, Bp, C, L >> 2, wout);
-    if (gx_chan_sum)
-        hipLaunchKernelGGL(rowsum_to_channel, dim3(C), dim3(256), 0, NEF_ST, (const double*)rowsum, gx_chan_sum,
-                           P * Bp, C);
-    return nef_launch_status();
-}
-
-int nef_outconv_fwd_pro(const float* x, const float* a, const float* b, int Bp, const float* w, const float* bias,
-                        float* out, int N, int C, int L, nef_stream_t stream) {
+int nef_outconv_fwd(const float* x, const float* a, const float* b, int Bp, const float* w, const float* bias,
+                    float* out, int N, int C, int L, nef_stream_t stream) {
     NEF_ENTER();
     NEF_REQUIRE(x && w && bias && out, NEF_E_NULL);
     NEF_REQUIRE((a == nullptr) == (b == nullptr), NEF_E_NULL);
@@ -2340,11 +2237,6 @@ int nef_outconv_fwd_pro(const float* x, const float* a, const float* b, int Bp, 
     return nef_launch_status();
 }
 
-int nef_outconv_fwd(const float* x, const float* w, const float* bias, float* out, int N, int C, int L,
-                    nef_stream_t stream) {
-    return nef_outconv_fwd_pro(x, nullptr, nullptr, 1, w, bias, out, N, C, L, stream);
-}
-
 int nef_outconv_bwd_data(const float* gout, const float* out, const float* w, float* gx, int N, int C, int L,
                          nef_stream_t stream) {
     NEF_ENTER();
@@ -2358,8 +2250,8 @@ int nef_outconv_bwd_data(const float* gout, const float* out, const float* w, fl
 
 size_t nef_outconv_bwd_weight_ws_bytes(int C) { return (size_t)OC_BLOCKS * (C + 1) * 3 * sizeof(double); }
 
-int nef_outconv_bwd_weight_pro(const float* gout, const float* out, const float* x, const float* a, const float* b, int Bp,
-                               float* gw, float* gb, void* ws, size_t ws_bytes, int N, int C, int L, nef_stream_t stream) {
+int nef_outconv_bwd_weight(const float* gout, const float* out, const float* x, const float* a, const float* b, int Bp,
+                           float* gw, float* gb, void* ws, size_t ws_bytes, int N, int C, int L, nef_stream_t stream) {
     NEF_ENTER();
     NEF_REQUIRE(gout && out && x && gw && gb && ws, NEF_E_NULL);
     NEF_REQUIRE((a == nullptr) == (b == nullptr), NEF_E_NULL);
@@ -2373,11 +2265,6 @@ int nef_outconv_bwd_weight_pro(const float* gout, const float* out, const float*
     hipLaunchKernelGGL(outconv_bwd_weight_final, dim3((C + 1) * 3), dim3(256), 0, NEF_ST, (const double*)ws, gw, gb, C,
                        nblk);
     return nef_launch_status();
-}
-
-int nef_outconv_bwd_weight(const float* gout, const float* out, const float* x, float* gw, float* gb, void* ws,
-                           size_t ws_bytes, int N, int C, int L, nef_stream_t stream) {
-    return nef_outconv_bwd_weight_pro(gout, out, x, nullptr, nullptr, 1, gw, gb, ws, ws_bytes, N, C, L, stream);
 }
 
 size_t nef_loss_ws_bytes(void) { return (size_t)LOSS_BLOCKS * 3 * sizeof(double); }

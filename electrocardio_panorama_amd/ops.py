@@ -1377,9 +1377,8 @@ def mix_bwd_shared_up(gU2, latent, z1, z2r, q, V, c1, c2=None, relu_z1=False):
     gq = torch.empty(B, 256, device=latent.device, dtype=torch.float32)
     name = "mix_bwd_shared_up" if up else "mix_bwd_shared"
     ev = _hbm(name, gU2, z1, z2r, gz1, gz2r)
-    fn = L.nef_mix_bwd_shared_up if up else L.nef_mix_bwd_shared
-    _lib.check(fn(_p(gU2), _p(latent), _p(z1), _p(z2r), _p(q), _p(gz1), _p(gz2r), _p(gq), B, V, T, c1, c2, cdev, int(relu_z1),
-                  _stream()), "nef_" + name)
+    _lib.check(L.nef_mix_bwd(_p(gU2), _p(latent), _p(z1), _p(z2r), _p(q), _p(gz1), _p(gz2r), _p(gq), B, V, T, c1, c2, cdev,
+                             int(relu_z1), int(up), 1, _stream()), "nef_mix_bwd (shared)")
     _done(ev)
     return gz1, gz2r, gq
 
@@ -1432,11 +1431,9 @@ def mix_bwd(gD, latent, z1, z2r, q, V, c1, c2=None, upsampled=False, relu_z1=Fal
     assert gD.shape[2] == (2 * T if upsampled else T)
     gz1, gz2r = torch.empty_like(z1), torch.empty_like(z2r)
     gq = torch.empty(B, 256, device=latent.device, dtype=torch.float32)
-    fn = L.nef_mix_bwd_up if upsampled else L.nef_mix_bwd
     # relu_z1: z1 is a ReLU output; gz1 also carries that ReLU's backward mask
-    _lib.check(fn(_p(gD), _p(latent), _p(z1), _p(z2r), _p(q), _p(gz1), _p(gz2r), _p(gq), B, V, T, c1, c2, cdev,
-                  int(relu_z1), _stream()),
-               "nef_mix_bwd")
+    _lib.check(L.nef_mix_bwd(_p(gD), _p(latent), _p(z1), _p(z2r), _p(q), _p(gz1), _p(gz2r), _p(gq), B, V, T, c1, c2, cdev,
+                             int(relu_z1), int(upsampled), 0, _stream()), "nef_mix_bwd")
     return gz1, gz2r, gq
 
 
@@ -1504,91 +1501,67 @@ def affine_relu_fwd(x, a, b, P):
     return y
 
 
+def _bn_bwd(form, tag, hbm, x, mean, invstd, a, b, P, gx, chan_sum=True, slots=None, phase_major=False, **grad):
+    """One nef_bn_relu_bwd call of kernel family `form` (nef_bn_bwd_args) writing into `gx`.  `grad`: g=..., or gout= / out= / wout=
+    for form 1; `hbm`: the tensors the `tag` launch is priced by.  Returns (gx, ggamma, gbeta, sum_{b,t} gx per channel or None)."""
+    L = _lib.load()
+    N, Ct, Ln = x.shape
+    gg = torch.empty(Ct, device=x.device, dtype=torch.float32)
+    gb = torch.empty(Ct, device=x.device, dtype=torch.float32)
+    gs = torch.empty(Ct, device=x.device, dtype=torch.float32) if chan_sum else None
+    A = _lib.BnBwdArgs(x=_p(x), mean=_p(mean), invstd=_p(invstd), a=_p(a), b=_p(b), gx=_p(gx), ggamma=_p(gg), gbeta=_p(gb),
+                       gx_chan_sum=_p(gs), slots=_p(slots[0]) if slots else None, nslot=slots[1] if slots else 0, P=P, Bp=N // P,
+                       C=Ct, L=Ln, form=form, phase_major=int(phase_major), **{k: _p(t) for k, t in grad.items()})
+    A.ws_bytes = L.nef_bn_bwd_ws_bytes(C.byref(A))
+    A.ws = _p(workspace(A.ws_bytes, x.device))
+    ev = _hbm(tag, *hbm)
+    _lib.check(L.nef_bn_relu_bwd(C.byref(A), _stream()), f"nef_bn_relu_bwd form {form}")
+    _done(ev)
+    return gx, gg, gb, gs
+
+
 def bn_relu_bwd(gy, x, gamma, mean, invstd, a, b, P, with_chan_sum=False, slots=None, phase_major=False):
     """Returns (gx, ggamma, gbeta[, sum_{b,t} gx per channel]).  `slots`: the conv_stats_buffer() the conv that produced
     `gy` filled (conv(..., bnb=...)) -- the reduction pass over (gy, x) is then skipped.  `phase_major`: gx comes back as
-    [N, 2C, L/2], row 2c + p = positions p, p + 2, ... of channel c (the operand of the polyphase backward passes)."""
-    L = _lib.load()
+    [N, 2C, L/2], row 2c + p = positions p, p + 2, ... of channel c (the operand of the polyphase backward passes).
+    `gamma` is not used: a = gamma * invstd carries it."""
     _chk(gy), _chk(x)
     N, Ct, Ln = x.shape
     gx = torch.empty(N, 2 * Ct, Ln // 2, device=x.device, dtype=torch.float32) if phase_major else torch.empty_like(x)
-    gg = torch.empty(Ct, device=x.device, dtype=torch.float32)
-    gb = torch.empty(Ct, device=x.device, dtype=torch.float32)
-    gs = torch.empty(Ct, device=x.device, dtype=torch.float32) if with_chan_sum else None
-    n = L.nef_bn_bwd_ws_bytes(P, N // P, Ct)
-    ws = workspace(n, x.device)
-    ev = _hbm("bn_relu_bwd", gy, x, gx)
-    fn = L.nef_bn_relu_bwd_phase_major if phase_major else L.nef_bn_relu_bwd
-    _lib.check(fn(_p(gy), _p(x), _p(gamma), _p(mean), _p(invstd), _p(a), _p(b), _p(gx), _p(gg), _p(gb),
-                  _p(gs), _p(ws), n, P, N // P, Ct, Ln, _p(slots[0]) if slots else None,
-                  slots[1] if slots else 0, _stream()), "nef_bn_relu_bwd")
-    _done(ev)
-    return (gx, gg, gb, gs) if with_chan_sum else (gx, gg, gb)
+    r = _bn_bwd(0, "bn_relu_bwd", (gy, x, gx), x, mean, invstd, a, b, P, gx, with_chan_sum, slots, phase_major, g=gy)
+    return r if with_chan_sum else r[:3]
 
 
 def bn_relu_bwd_combine3(gy, x, mean, invstd, a, b, slots=None, phase_major=False):
     """pass_combine_bwd(bn_relu_bwd(gy, x, ..., P=3)) in one pass: returns (gP2 [2B,2C,L], ggamma, gbeta, chan sum of gx);
     `phase_major`: gP2 as [2B, 4C, L/2] (see bn_relu_bwd)."""
-    L = _lib.load()
     _chk(gy), _chk(x)
     N, Ct, Ln = x.shape
     Bp = N // 3
     gP2 = torch.empty((2 * Bp, 4 * Ct, Ln // 2) if phase_major else (2 * Bp, 2 * Ct, Ln), device=x.device, dtype=torch.float32)
-    gg = torch.empty(Ct, device=x.device, dtype=torch.float32)
-    gb = torch.empty(Ct, device=x.device, dtype=torch.float32)
-    gs = torch.empty(Ct, device=x.device, dtype=torch.float32)
-    n = L.nef_bn_bwd_ws_bytes(3, Bp, Ct)
-    ws = workspace(n, x.device)
-    ev = _hbm("bn_relu_bwd_combine3", gy, x, gP2)
-    fn = L.nef_bn_relu_bwd_combine3_phase_major if phase_major else L.nef_bn_relu_bwd_combine3
-    _lib.check(fn(_p(gy), _p(x), _p(mean), _p(invstd), _p(a), _p(b), _p(gP2), _p(gg), _p(gb),
-                  _p(gs), _p(ws), n, Bp, Ct, Ln, _p(slots[0]) if slots else None,
-                  slots[1] if slots else 0, _stream()), "nef_bn_relu_bwd_combine3")
-    _done(ev)
-    return gP2, gg, gb, gs
+    return _bn_bwd(3, "bn_relu_bwd_combine3", (gy, x, gP2), x, mean, invstd, a, b, 3, gP2, slots=slots, phase_major=phase_major,
+                   g=gy)
 
 
 def bn_relu_bwd_up(gu, x, mean, invstd, a, b, P, slots=None):
     """bn_relu_bwd(upsample2_bwd(gu), x, ...) with the upsampling adjoint taken on the fly; gu [N,C,2L].
     Returns (gx, ggamma, gbeta, sum_{b,t} gx per channel)."""
-    L = _lib.load()
     _chk(gu), _chk(x)
     N, Ct, Ln = x.shape
     assert gu.shape == (N, Ct, 2 * Ln)
     gx = torch.empty_like(x)
-    gg = torch.empty(Ct, device=x.device, dtype=torch.float32)
-    gb = torch.empty(Ct, device=x.device, dtype=torch.float32)
-    gs = torch.empty(Ct, device=x.device, dtype=torch.float32)
-    n = L.nef_bn_bwd_ws_bytes(P, N // P, Ct)
-    ws = workspace(n, x.device)
-    ev = _hbm("bn_relu_bwd_up", gu, x, gx)
-    _lib.check(L.nef_bn_relu_bwd_up(_p(gu), _p(x), _p(mean), _p(invstd), _p(a), _p(b), _p(gx), _p(gg), _p(gb), _p(gs),
-                                    _p(ws), n, P, N // P, Ct, Ln, _p(slots[0]) if slots else None,
-                                    slots[1] if slots else 0, _stream()), "nef_bn_relu_bwd_up")
-    _done(ev)
-    return gx, gg, gb, gs
+    return _bn_bwd(2, "bn_relu_bwd_up", (gu, x, gx), x, mean, invstd, a, b, P, gx, slots=slots, g=gu)
 
 
 def bn_relu_bwd_outconv(gout, out, wout, x, mean, invstd, a, b, P):
     """bn_relu_bwd(outconv_bwd_data(gout, out, wout), x, ...) without materialising the [N,C,L] gradient in between.
     Returns (gx, ggamma, gbeta, sum_{b,t} gx per channel)."""
-    L = _lib.load()
     _chk(gout), _chk(out), _chk(x)
-    N, Ct, Ln = x.shape
     gx = torch.empty_like(x)
-    gg = torch.empty(Ct, device=x.device, dtype=torch.float32)
-    gb = torch.empty(Ct, device=x.device, dtype=torch.float32)
-    gs = torch.empty(Ct, device=x.device, dtype=torch.float32)
-    n = L.nef_bn_bwd_outconv_ws_bytes(P, N // P, Ct, Ln)
-    ws = workspace(n, x.device)
     # a two-pass pair by construction (the reduction pass reads x, the apply pass reads it again and writes gx): priced by
     # what the pair has to move -- 2 reads + 1 write of the [N, C, L] tensor (+ the small gout / out rows twice)
-    ev = _hbm("bn_relu_bwd_outconv", gout, out, x, gout, out, x, gx)
-    _lib.check(L.nef_bn_relu_bwd_outconv(_p(gout), _p(out), _p(wout), _p(x), _p(mean), _p(invstd), _p(a), _p(b), _p(gx),
-                                         _p(gg), _p(gb), _p(gs), _p(ws), n, P, N // P, Ct, Ln, _stream()),
-               "nef_bn_relu_bwd_outconv")
-    _done(ev)
-    return gx, gg, gb, gs
+    return _bn_bwd(1, "bn_relu_bwd_outconv", (gout, out, x, gout, out, x, gx), x, mean, invstd, a, b, P, gx, gout=gout, out=out,
+                   wout=wout)
 
 
 def outconv_fwd(x, w, bias, pro=None):
@@ -1599,8 +1572,7 @@ def outconv_fwd(x, w, bias, pro=None):
     out = torch.empty(N, 1, Ln, device=x.device, dtype=torch.float32)
     a, b, Bp = pro if pro is not None else (None, None, 1)
     ev = _hbm("outconv_fwd", x, out)
-    _lib.check(L.nef_outconv_fwd_pro(_p(x), _p(a), _p(b), Bp, _p(w), _p(bias), _p(out), N, Ct, Ln, _stream()),
-               "nef_outconv_fwd")
+    _lib.check(L.nef_outconv_fwd(_p(x), _p(a), _p(b), Bp, _p(w), _p(bias), _p(out), N, Ct, Ln, _stream()), "nef_outconv_fwd")
     _done(ev)
     return out
 
@@ -1624,8 +1596,8 @@ def outconv_bwd_weight(gout, out, x, pro=None):
     ws = workspace(n, x.device)
     a, b, Bp = pro if pro is not None else (None, None, 1)
     ev = _hbm("outconv_bwd_weight", gout, out, x)
-    _lib.check(L.nef_outconv_bwd_weight_pro(_p(gout), _p(out), _p(x), _p(a), _p(b), Bp, _p(gw), _p(gb), _p(ws), n, N, Ct,
-                                            Ln, _stream()), "nef_outconv_bwd_weight")
+    _lib.check(L.nef_outconv_bwd_weight(_p(gout), _p(out), _p(x), _p(a), _p(b), Bp, _p(gw), _p(gb), _p(ws), n, N, Ct, Ln,
+                                        _stream()), "nef_outconv_bwd_weight")
     _done(ev)
     return gw, gb
 

@@ -34,7 +34,7 @@ extern "C" {
 typedef void* nef_stream_t;
 
 /* ABI version of this header; bumped on any signature change. */
-int nef_abi_version(void);   /* 20 (the weight gradient is ONE entry, nef_conv_bwd_weight(nef_bww_args*), + nef_bww_args_bytes; its _pro, _wino4, _h2 and _h2_ws_bytes variants are gone); 19 (+ nef_adam, nef_h2_tail_census, nef_bwd_weight_clamp_ends: additions only; the kernel-form option entry points of 16 and nef_upsample2_aff_fwd are gone; + nef_debug_spin_us); 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + kernel-form option entry points); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + the split-fp16 weight gradient, now form 3); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, the transposed F(3,4) / F(4,4) entry, now form 4, covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
+int nef_abi_version(void);   /* 21 (BatchNorm backward is ONE entry on a nef_bn_bwd_args struct, + nef_bn_bwd_args_bytes; nef_mix_bwd takes `up` / `shared` flags; nef_outconv_fwd / nef_outconv_bwd_weight take the prologue arguments.  ABI <= 20 had nef_bn_relu_bwd_phase_major, nef_bn_relu_bwd_up, nef_bn_relu_bwd_combine3, nef_bn_relu_bwd_combine3_phase_major, nef_bn_relu_bwd_outconv, nef_bn_bwd_outconv_ws_bytes, nef_mix_bwd_up, nef_mix_bwd_shared, nef_mix_bwd_shared_up, nef_outconv_fwd_pro and nef_outconv_bwd_weight_pro); 20 (the weight gradient is ONE entry, nef_conv_bwd_weight(nef_bww_args*), + nef_bww_args_bytes; its _pro, _wino4, _h2 and _h2_ws_bytes variants are gone); 19 (+ nef_adam, nef_h2_tail_census, nef_bwd_weight_clamp_ends: additions only; the kernel-form option entry points of 16 and nef_upsample2_aff_fwd are gone; + nef_debug_spin_us); 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + kernel-form option entry points); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + the split-fp16 weight gradient, now form 3); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, the transposed F(3,4) / F(4,4) entry, now form 4, covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
 
 /* Diagnostics: `wgs` workgroups busy for `us` microseconds on `stream` (a stand-in for a collective's time on the chip:
  * parallel.DryCollective, bench.py --dry-collective).  0 <= us <= 50000, 1 <= wgs <= 64. */
@@ -165,7 +165,7 @@ typedef struct nef_conv_args {
     int32_t bnb_Bp;
     int32_t bnb_up;        /* 1: a x2 linear upsampling (nn.Upsample, align_corners=False) sits between that BatchNorm's ReLU
                               and this launch's output: bnb_x is [B][G*Cout_g][T/2] and the sums are those of the
-                              upsampling's adjoint (what nef_bn_relu_bwd_up reduces); T % 4 == 0 */
+                              upsampling's adjoint (what nef_bn_relu_bwd form 2 reduces); T % 4 == 0 */
     float x_scale;         /* wino == 3 only: 0 (= 1) or an exact power of two the input is multiplied by before it is split into
                               fp16 terms and the accumulators are divided by again -- brings operands far from magnitude 1
                               (gradients) into fp16's range; the result is unchanged up to the split's rounding */
@@ -376,14 +376,13 @@ int nef_lead_mean(const float* z1, const float* z2r, float* latent, int B, int V
 int nef_mix_fwd(const float* latent, const float* z1, const float* z2r, const float* q, float* D, int B, int V,
                 int T, int c1, int c2, const int32_t* choice_dev, nef_stream_t stream);
 int nef_mix_bwd(const float* gD, const float* latent, const float* z1, const float* z2r, const float* q, float* gz1,
-                float* gz2r, float* gq, int B, int V, int T, int c1, int c2, const int32_t* choice_dev, int relu_z1,
-                nef_stream_t stream);
-/* relu_z1 != 0 (both): z1 is a ReLU output; gz1 is additionally masked with z1 > 0.
- * nef_mix_bwd_up: same, but gU is the gradient wrt the x2-UPSAMPLED decoder input [3B][256][2T] (what the first decoder
- * conv's backward-data writes); the upsampling adjoint (nef_upsample2_bwd) is taken while reading it. */
-int nef_mix_bwd_up(const float* gU, const float* latent, const float* z1, const float* z2r, const float* q, float* gz1,
-                float* gz2r, float* gq, int B, int V, int T, int c1, int c2, const int32_t* choice_dev, int relu_z1,
-                nef_stream_t stream);
+                float* gz2r, float* gq, int B, int V, int T, int c1, int c2, const int32_t* choice_dev, int relu_z1, int up,
+                int shared, nef_stream_t stream);
+/* relu_z1 != 0: z1 is a ReLU output; gz1 is additionally masked with z1 > 0.
+ * up != 0: gD is the gradient wrt the x2-UPSAMPLED decoder input, [..][256][2T] (what the first decoder conv's backward-data
+ *   writes); the upsampling adjoint (nef_upsample2_bwd) is taken while reading it.  T > 1.
+ * shared != 0: gD is the two-pass gradient wrt D2 of nef_mix_fwd_shared (below), [2B][256][T] or, with `up`, [2B][256][2T],
+ *   instead of the three-pass [3B][256][..].  T > 1. */
 
 /* Shared first decoder conv (train step): the three decoder inputs of model_nefnet.py:159-176 are
  * q*cat(z1m|z2m), q*cat(z1[c1]|z2m), q*cat(z1m|z2r[c2]) and decoder.1.double_conv.0 is linear in the two channel halves,
@@ -392,20 +391,14 @@ int nef_mix_bwd_up(const float* gU, const float* latent, const float* z1, const 
  *   (grouped conv, G = 2, on D2 with the weight regrouped to [2*Cout][Cin/2][3] -> P2 [2B][2C][L])
  *   nef_pass_combine_fwd : c1[p][b][c] = P2 A-half[ia(p)] + P2 B-half[ib(p)] + bias[c],  (ia,ib) = (m,m),(pick,m),(m,pick)
  *   nef_pass_combine_bwd : its adjoint, gc1 [3B][C][L] -> gP2 [2B][2C][L]
- *   nef_mix_bwd_shared_up: nef_mix_bwd_up for the two-pass gradient gU2 [2B][256][2T] (wrt the upsampled D2);
- *   nef_mix_bwd_shared: the same for the gradient wrt D2 itself, gD2 [2B][256][T] (what the polyphase backward-data pass leaves). */
+ *   nef_mix_bwd, shared = 1: the adjoint of nef_mix_fwd_shared, from the two-pass gradient wrt the upsampled D2 (up = 1) or wrt
+ *                          D2 itself (up = 0: what the polyphase backward-data pass leaves). */
 int nef_mix_fwd_shared(const float* latent, const float* z1, const float* z2r, const float* q, float* D2, int B, int V,
                        int T, int c1, int c2, const int32_t* choice_dev, nef_stream_t stream);
 /* nef_lead_mean + nef_mix_fwd_shared in one pass over z1 / z2r (the picked lead is one of the rows being averaged):
  * bit-identical latent and D2, 0.65 GB less traffic per step at config 2. */
 int nef_lead_mean_mix_shared(const float* z1, const float* z2r, const float* q, float* latent, float* D2, int B, int V,
                              int T, int c1, int c2, const int32_t* choice_dev, nef_stream_t stream);
-int nef_mix_bwd_shared(const float* gD2, const float* latent, const float* z1, const float* z2r, const float* q,
-                       float* gz1, float* gz2r, float* gq, int B, int V, int T, int c1, int c2,
-                       const int32_t* choice_dev, int relu_z1, nef_stream_t stream);
-int nef_mix_bwd_shared_up(const float* gU2, const float* latent, const float* z1, const float* z2r, const float* q,
-                          float* gz1, float* gz2r, float* gq, int B, int V, int T, int c1, int c2,
-                          const int32_t* choice_dev, int relu_z1, nef_stream_t stream);
 int nef_pass_combine_fwd(const float* P2, const float* bias, float* c1, int B, int C, int L, nef_stream_t stream);
 /* nef_pass_combine_fwd that also leaves the train-mode BatchNorm statistics of its output (3 passes of B samples; same
  * outputs as nef_bn_train_stats(c1, ..., P = 3, Bp = B, ...), running statistics updated pass by pass): saves the separate
@@ -429,9 +422,7 @@ int nef_upsample2_bwd(const float* gy, float* gx, int64_t N, int Tin, nef_stream
  *   momentum (unbiased var), exactly as P successive module calls would.
  * nef_bn_eval_affine: a = gamma/sqrt(rv+eps), b = beta - rm*a  [C].
  * nef_affine_relu_fwd: y = max(0, x*a[p][c] + b[p][c]).
- * nef_bn_relu_bwd: given gy (grad wrt the ReLU output), x (pre-BN), writes gx, ggamma[C], gbeta[C] and, when
- *   gx_chan_sum != NULL, gx_chan_sum[c] = sum_{b,t} gx (the bias gradient of the conv that feeds this BN), fused into
- *   the same pass.  ws: nef_bn_bwd_ws_bytes(P, Bp, C). */
+ * nef_bn_relu_bwd: the backward of BatchNorm + ReLU, one nef_bn_bwd_args struct per call (below). */
 size_t nef_bn_ws_bytes(int P, int C);
 /* Slots per sample of nef_conv_args.stats (0: the F(4,3) kernel does not take this shape), and the statistics pass that
  * replaces nef_bn_train_stats when the producing conv left them: same outputs (fp64 from the slot sums on, fixed
@@ -456,47 +447,61 @@ int nef_fold_bn(const float* w, const float* bias, const float* a, const float* 
                 int Cout, int inner, nef_stream_t stream);
 int nef_affine_relu_fwd(const float* x, const float* a, const float* b, float* y, int P, int Bp, int C, int L,
                         nef_stream_t stream);
-size_t nef_bn_bwd_ws_bytes(int P, int Bp, int C);
-int nef_bn_relu_bwd(const float* gy, const float* x, const float* gamma, const float* mean, const float* invstd,
-                    const float* a, const float* b, float* gx, float* ggamma, float* gbeta, float* gx_chan_sum, void* ws,
-                    size_t ws_bytes, int P, int Bp, int C, int L, const float* slots, int nslot, nef_stream_t stream);
-/* `slots` (here and in nef_bn_relu_bwd_combine3): NULL, or the sums the conv that produced gy left in its epilogue
- * (nef_conv_args.bnb_slots, nslot = nef_conv_stats_slots): the reduction pass over (gy, x) is then skipped. */
+/* BatchNorm + ReLU backward.  Given the gradient wrt the ReLU output and x (pre-BN), writes gx, ggamma[C], gbeta[C] and, when asked,
+ * the per-channel sum of gx, all from one reduction and one apply pass.  One struct describes the call; `form` picks the kernel
+ * family.  A combination no kernel serves (an unknown form, phase_major on forms 1 or 2, slots on form 1, P != 3 on form 3, a
+ * gradient pointer the form does not read) is NEF_E_UNSUPPORTED, never ignored. */
+typedef struct nef_bn_bwd_args {
+    const float* g;        /* the incoming gradient.  Forms 0 and 3: gy [P*Bp][C][L], wrt the ReLU output.  Form 2: gu [P*Bp][C][2L], wrt
+                              nn.Upsample(x2)(ReLU(BN(x))) (model_nefnet.py:104).  Form 1: NULL */
+    const float* gout;     /* form 1 only (NULL otherwise): the gradient wrt the network output [P*Bp][L], */
+    const float* out;      /* that output (the sigmoid's), [P*Bp][L], */
+    const float* wout;     /* and the last conv's weight [1][C][3] */
+    const float* x;        /* the BatchNorm input [P*Bp][C][L] */
+    const float* mean;     /* [P][C], as nef_bn_train_stats left them */
+    const float* invstd;
+    const float* a;
+    const float* b;
+    float* gx;             /* [P*Bp][C][L]; with phase_major [P*Bp][2C][L/2].  Form 3 writes gP2 [2Bp][2C][L] here instead, with
+                              phase_major [2Bp][4C][L/2] (only gx's per-channel sum is kept) */
+    float* ggamma;         /* [C] */
+    float* gbeta;          /* [C] */
+    float* gx_chan_sum;    /* NULL, or [C]: sum_{b,t} gx, the bias gradient of the conv that feeds this BatchNorm */
+    const float* slots;    /* NULL, or the sums the conv that produced g left in its epilogue (nef_conv_args.bnb_slots): the
+                              reduction pass over (g, x) is then skipped.  Not with form 1 */
+    void* ws;              /* ws_bytes >= nef_bn_bwd_ws_bytes(args) bytes of scratch */
+    size_t ws_bytes;
+    int32_t P, Bp, C, L;   /* P independent passes of Bp samples stacked along batch */
+    int32_t nslot;         /* with slots: nef_conv_stats_slots of the producing launch; > 0, Bp*nslot <= INT_MAX */
+    int32_t form;          /* 0: plain.  Any L; the row kernel when L % 4 == 0 and P*Bp*C <= INT_MAX, else the element kernel.
+                            * 1: fed straight from the last conv's output gradient: the [N][C][L] input gradient of Conv1d(C->1) (what
+                            *    nef_outconv_bwd_data would write) is rebuilt on the fly from go = gout*out*(1-out)/3, so it is never
+                            *    materialised.  Same results as nef_outconv_bwd_data + form 0.  L % 4 == 0, P*Bp*C <= INT_MAX.
+                            * 2: g at TWICE the length; the upsampling adjoint (nef_upsample2_bwd) is taken while reading.  L % 4 == 0,
+                            *    L >= 8, P*Bp*C <= INT_MAX.
+                            * 3: form 0 with P == 3 followed by nef_pass_combine_bwd in one pass.  Bp*C <= INT_MAX. */
+    int32_t phase_major;   /* forms 0 and 3: row r of the output is written as the two half-length rows 2 r (even positions) and
+                              2 r + 1 (odd positions) -- the operand of the polyphase backward passes (below).  Form 0: L % 4 == 0
+                              and P*Bp*C <= INT_MAX; form 3: L % 2 == 0 */
+    int32_t reserved0;
+} nef_bn_bwd_args;
+
+int nef_bn_relu_bwd(const nef_bn_bwd_args* a, nef_stream_t stream);
+/* Reads form, P, Bp, C, L only; 0: an unknown form or a non-positive size. */
+size_t nef_bn_bwd_ws_bytes(const nef_bn_bwd_args* a);
+/* sizeof(nef_bn_bwd_args) as the library was built: a binding checks its mirror of the struct against it. */
+size_t nef_bn_bwd_args_bytes(void);
 
 /* Final Conv1d(64->1,k3,p1,bias) + sigmoid(x/3).  model_nefnet.py:106,168.
- *   x [N][C][L], w [1][C][3], bias [1], out [N][L]. */
-/* BatchNorm+ReLU backward of the LAST decoder BatchNorm fed straight from the last conv's output gradient: the
- * [N][C][L] input gradient of Conv1d(C->1) (what nef_outconv_bwd_data would write) is rebuilt on the fly from
- * go = gout*out*(1-out)/3, so it is never materialised.  Same results as nef_outconv_bwd_data + nef_bn_relu_bwd.
- * L % 4 == 0.  wout [1][C][3].  ws: nef_bn_bwd_outconv_ws_bytes(P, Bp, C, L). */
-/* nef_bn_relu_bwd_up: nef_bn_relu_bwd whose incoming gradient is given at TWICE the length, gu [N][C][2L] = the
- * gradient wrt nn.Upsample(x2)(ReLU(BN(x))) (model_nefnet.py:104); the upsampling adjoint (nef_upsample2_bwd) is taken
- * while reading.  L % 4 == 0, L >= 8.  ws: nef_bn_bwd_ws_bytes. */
-int nef_bn_relu_bwd_up(const float* gu, const float* x, const float* mean, const float* invstd, const float* a,
-                       const float* b, float* gx, float* ggamma, float* gbeta, float* gx_chan_sum, void* ws,
-                       size_t ws_bytes, int P, int Bp, int C, int L, const float* slots, int nslot, nef_stream_t stream);
-/* nef_bn_relu_bwd_combine3: nef_bn_relu_bwd (P = 3) followed by nef_pass_combine_bwd in one pass: writes gP2 [2Bp][2C][L]
- * instead of gx (only gx's per-channel sum is kept).  ws: nef_bn_bwd_ws_bytes(3, Bp, C). */
-int nef_bn_relu_bwd_combine3(const float* gy, const float* x, const float* mean, const float* invstd, const float* a,
-                             const float* b, float* gP2, float* ggamma, float* gbeta, float* gx_chan_sum, void* ws,
-                             size_t ws_bytes, int Bp, int C, int L, const float* slots, int nslot, nef_stream_t stream);
-size_t nef_bn_bwd_outconv_ws_bytes(int P, int Bp, int C, int L);
-int nef_bn_relu_bwd_outconv(const float* gout, const float* out, const float* wout, const float* x, const float* mean,
-                            const float* invstd, const float* a, const float* b, float* gx, float* ggamma, float* gbeta,
-                            float* gx_chan_sum, void* ws, size_t ws_bytes, int P, int Bp, int C, int L,
-                            nef_stream_t stream);
-int nef_outconv_fwd(const float* x, const float* w, const float* bias, float* out, int N, int C, int L,
-                    nef_stream_t stream);
-/* Variants that take the pre-BatchNorm tensor and apply x' = max(0, x*a[p][c] + b[p][c]), p = n / Bp, on the fly. */
-int nef_outconv_fwd_pro(const float* x, const float* a, const float* b, int Bp, const float* w, const float* bias,
-                        float* out, int N, int C, int L, nef_stream_t stream);
-int nef_outconv_bwd_weight_pro(const float* gout, const float* out, const float* x, const float* a, const float* b, int Bp,
-                               float* gw, float* gb, void* ws, size_t ws_bytes, int N, int C, int L, nef_stream_t stream);
+ *   x [N][C][L], w [1][C][3], bias [1], out [N][L].
+ * a, b: both NULL, or x is the pre-BatchNorm tensor and x' = max(0, x*a[p][c] + b[p][c]), p = n / Bp, is applied on the fly. */
+int nef_outconv_fwd(const float* x, const float* a, const float* b, int Bp, const float* w, const float* bias,
+                    float* out, int N, int C, int L, nef_stream_t stream);
+int nef_outconv_bwd_weight(const float* gout, const float* out, const float* x, const float* a, const float* b, int Bp,
+                           float* gw, float* gb, void* ws, size_t ws_bytes, int N, int C, int L, nef_stream_t stream);
 int nef_outconv_bwd_data(const float* gout, const float* out, const float* w, float* gx, int N, int C, int L,
                          nef_stream_t stream);
 size_t nef_outconv_bwd_weight_ws_bytes(int C);
-int nef_outconv_bwd_weight(const float* gout, const float* out, const float* x, float* gw, float* gb, void* ws,
-                           size_t ws_bytes, int N, int C, int L, nef_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Loss.  codes/network/loss/losses.py:21-50 (+ solver.py:185-186 noise):
@@ -593,23 +598,14 @@ int nef_poly_fwd_edge(const float* x, const float* w, float* y, int B, int G, in
 int nef_poly_bwd_edge(const float* gy, const float* w /* [G Cog][Cig][3], the conv's own weight */, float* gx, int B, int G, int Cog,
                       int Cig, int T /* length of gy = 2 x length of gx */, const float* bnb_x, const float* bnb_mean,
                       const float* bnb_invstd, const float* bnb_a, const float* bnb_b, int bnb_Bp, float* bnb_slots, int nslot,
-                      int gy_phase_major /* gy stored [B][G 2 Cog][T / 2] (nef_bn_relu_bwd_phase_major) */, nef_stream_t stream);
-/* PHASE-MAJOR gradients: nef_bn_relu_bwd_phase_major / nef_bn_relu_bwd_combine3_phase_major are nef_bn_relu_bwd /
- * nef_bn_relu_bwd_combine3 writing row r of their output as the two half-length rows 2 r (even positions) and 2 r + 1 (odd
- * positions) of a [.., 2 C, L / 2] tensor (L % 4 == 0 resp. L % 2 == 0).  That is the operand the polyphase backward passes of the
+                      int gy_phase_major /* gy stored [B][G 2 Cog][T / 2] (nef_bn_bwd_args.phase_major) */, nef_stream_t stream);
+/* PHASE-MAJOR gradients: nef_bn_relu_bwd with nef_bn_bwd_args.phase_major (forms 0 and 3) writes row r of its output as the two
+ * half-length rows 2 r (even positions) and 2 r + 1 (odd positions) of a [.., 2 C, L / 2] tensor.  That is the operand the polyphase backward passes of the
  * conv behind the upsampling want: backward-data = a PLAIN nef_conv_fwd over it (weights nef_poly_weights, transposed / flipped)
  * + nef_poly_bwd_edge(gy_phase_major = 1); weight gradient = nef_conv_bwd_weight, form 3, with pro_mode 4 (| 1: affine prologue; bit 2 =
  * the half-resolution x window is continued with x[0] / x[T-1] at the row ends) giving gw2 [G 2 Cog][Cig][3], then
  * nef_poly_wgrad_fold: gw2 folded back onto the conv's own taps minus the row-end terms (xedge [B][G Cig][2] = the prologue's
  * output at the first / last position, written by nef_poly_fwd_edge). */
-int nef_bn_relu_bwd_phase_major(const float* gy, const float* x, const float* gamma, const float* mean, const float* invstd,
-                                const float* a, const float* b, float* gx, float* ggamma, float* gbeta, float* gx_chan_sum,
-                                void* ws, size_t ws_bytes, int P, int Bp, int C, int L, const float* slots, int nslot,
-                                nef_stream_t stream);
-int nef_bn_relu_bwd_combine3_phase_major(const float* gy, const float* x, const float* mean, const float* invstd, const float* a,
-                                         const float* b, float* gP2, float* ggamma, float* gbeta, float* gx_chan_sum, void* ws,
-                                         size_t ws_bytes, int Bp, int C, int L, const float* slots, int nslot,
-                                         nef_stream_t stream);
 size_t nef_poly_wgrad_fold_ws_bytes(int B, int G, int Cog, int Cig);
 int nef_poly_wgrad_fold(const float* gw2, const float* gy_pm, const float* xedge, float* gw, void* ws, size_t ws_bytes, int B, int G,
                         int Cog, int Cig, int T /* full-resolution length = 2 x the rows of gy_pm */, nef_stream_t stream);

@@ -14,7 +14,7 @@ from util import free_port
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_header_symbols_exported_abi_20():
+def test_header_symbols_exported_abi_21():
     """The shared library loads and exports every function include/nefnet_hip.h declares (no compute calls)."""
     from electrocardio_panorama_amd import _lib
     from electrocardio_panorama_amd.csrc import build
@@ -25,9 +25,10 @@ def test_header_symbols_exported_abi_20():
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name), name
-    assert _lib.load().nef_abi_version() == 20
+    assert _lib.load().nef_abi_version() == 21
     assert ctypes.sizeof(_lib.ConvArgs) == 384 == _lib.load().nef_conv_args_bytes()
     assert ctypes.sizeof(_lib.BwwArgs) == 200 == _lib.load().nef_bww_args_bytes()
+    assert ctypes.sizeof(_lib.BnBwdArgs) == 160 == _lib.load().nef_bn_bwd_args_bytes()
 
 
 def test_rejects_bad_calls_without_touching_the_gpu():
@@ -49,6 +50,30 @@ def test_rejects_bad_calls_without_touching_the_gpu():
     assert L.nef_conv_bwd_weight(bww(ws_bytes=0), None) == -3                 # NEF_E_WORKSPACE
     assert L.nef_conv_bwd_weight(bww(form=3, x_amax_next=8), None) == -2      # the two *_amax_next words go together
     assert L.nef_conv_bwd_weight(bww(form=3, gy_amax_next=8), None) == -2
+    def bnb(form=0, **kw):                      # BatchNorm backward's struct, dummy pointers again; form 1 reads gout / out / wout, not g
+        grad = dict(gout=8, out=8, wout=8) if form == 1 else dict(g=8)
+        w = _lib.BnBwdArgs(x=8, mean=8, invstd=8, a=8, b=8, gx=8, ggamma=8, gbeta=8, ws=8, ws_bytes=1 << 40, P=3, Bp=2, C=8, L=16,
+                           form=form, **grad)
+        for k, v in kw.items():
+            setattr(w, k, v)
+        return ctypes.byref(w)
+    assert L.nef_bn_relu_bwd(ctypes.byref(_lib.BnBwdArgs()), None) == -2
+    assert L.nef_bn_relu_bwd(bnb(ws_bytes=0), None) == -3
+    assert L.nef_bn_relu_bwd(bnb(form=9), None) == -4                         # combinations no kernel serves are refused, not ignored
+    assert L.nef_bn_relu_bwd(bnb(form=2, phase_major=1), None) == -4
+    assert L.nef_bn_relu_bwd(bnb(form=1, slots=8, nslot=1), None) == -4
+    assert L.nef_bn_relu_bwd(bnb(form=3, P=2), None) == -4
+    assert L.nef_bn_relu_bwd(bnb(form=1, g=8), None) == -4
+    assert L.nef_bn_relu_bwd(bnb(form=0, gout=8), None) == -4
+    assert L.nef_bn_relu_bwd(bnb(form=2, L=6), None) == -1                    # NEF_E_SHAPE
+    assert L.nef_bn_relu_bwd(bnb(form=1, L=10), None) == -1
+    assert L.nef_bn_relu_bwd(bnb(form=0, phase_major=1, L=6), None) == -1
+    assert L.nef_bn_relu_bwd(bnb(slots=8, nslot=0), None) == -1
+    assert L.nef_bn_bwd_ws_bytes(bnb(form=9)) == 0
+    assert L.nef_bn_bwd_ws_bytes(bnb(form=1)) == L.nef_bn_bwd_ws_bytes(bnb(form=0)) + 3 * 2 * 16 * 4 > 3 * 2 * 16 * 4
+    assert L.nef_mix_bwd(None, None, None, None, None, None, None, None, 1, 1, 8, 0, 0, None, 0, 0, 0, None) == -2
+    assert L.nef_mix_bwd(8, 8, 8, 8, 8, 8, 8, 8, 1, 1, 1, 0, 0, None, 0, 1, 0, None) == -1        # up: T > 1
+    assert L.nef_mix_bwd(8, 8, 8, 8, 8, 8, 8, 8, 1, 1, 1, 0, 0, None, 0, 0, 1, None) == -1        # shared: T > 1
 
 
 def test_config_surface():

@@ -428,8 +428,8 @@ def test_outconv():
 
 @pytest.mark.parametrize("L", [500, 2048, 12])
 def test_bn_relu_bwd_through_last_conv_equals_two_calls(L):
-    """nef_bn_relu_bwd_outconv rebuilds the last conv's input gradient from go on the fly: it must give exactly what
-    nef_outconv_bwd_data followed by nef_bn_relu_bwd gives (same expressions, same summation order)."""
+    """nef_bn_relu_bwd form 1 rebuilds the last conv's input gradient from go on the fly: it must give exactly what
+    nef_outconv_bwd_data followed by form 0 gives (same expressions, same summation order)."""
     o = ops()
     P, Bp, C = 3, 2, 64
     N = P * Bp
@@ -463,7 +463,7 @@ def test_mix_bwd_takes_the_upsampling_adjoint_on_the_fly():
 
 @pytest.mark.parametrize("L", [500, 16, 2048])
 def test_bn_relu_bwd_takes_the_upsampling_adjoint_on_the_fly(L):
-    """nef_bn_relu_bwd_up on the gradient wrt the x2-upsampled activation == upsample2_bwd + bn_relu_bwd, bit for bit."""
+    """nef_bn_relu_bwd form 2 on the gradient wrt the x2-upsampled activation == upsample2_bwd + bn_relu_bwd, bit for bit."""
     o = ops()
     P, Bp, C = 3, 2, 128
     N = P * Bp
