@@ -136,6 +136,8 @@ SIGNATURES = {
     "nef_loss_ws_bytes": (sz, []),
     "nef_loss_fwd": (i32, [p, p, p, p, p, p, sz, i64, f32, f32, f32, i32, i32, p]),
     "nef_loss_bwd": (i32, [p, p, p, p, p, p, p, p, i64, f32, f32, f32, i32, i32, p]),
+    "nef_loss_noise_fwd": (i32, [p, p, p, p, p, p, p, sz, i64, f32, f32, f32, i32, i32, p]),
+    "nef_loss_noise_bwd": (i32, [p, p, p, p, p, p, p, p, p, i64, f32, f32, f32, i32, i32, p]),
     "nef_sgd_momentum": (i32, [p, p, p, i64, f32, f32, f32, i32, p, p, p, p]),
     "nef_adam": (i32, [p, p, p, p, i64, f32, C.c_double, C.c_double, f32, f32, f32, p, p, p, p, p]),
     "nef_grad_clip_ws_bytes": (sz, []),

@@ -43,8 +43,9 @@ _DEFAULTS = {
         "part_loss_no_grad": False,
         "loss_factor": [1, 1, 1],
         # train step as one captured hipGraph (graph.GraphedTrainStep): None / 'auto' = replay at EVERY batch size wherever the step
-        # qualifies (plain Model_nefnet train path, FusedSGD with one parameter group, no DATA.noise, per-view host lists not
-        # wanted: Solver._graphed_step; rounds 1-3 replayed launch-bound shapes only); False = always issue eagerly; True = as auto
+        # qualifies (plain Model_nefnet train path, a fused optimiser -- FusedSGD, FusedAdam -- with one parameter group, per-view host
+        # lists not wanted: Solver._graphed_step; DATA.noise replays too, its row is an addend of the loss kernels; rounds 1-3 replayed
+        # launch-bound shapes only); False = always issue eagerly; True = as auto
         "graph": None,
         # global gradient-norm clipping on the device (ops.grad_clip: torch.nn.utils.clip_grad_norm_ semantics on the mean gradient,
         # in the eager and the graphed step): 0 = off (no launch, no allocation); inf = measure and report the norm, never scale;

@@ -1178,13 +1178,16 @@ __global__ __launch_bounds__(256) void outconv_bwd_weight_final(const double* __
 // ------------------------------------------------------------------------------------------------
 constexpr int LOSS_BLOCKS = 256;
 
+// noise: NULL, or the per-sample noise row in pred's layout (cfg.DATA.noise, codes/solver/solver.py:185-186 `out = out + noise`): one
+// plain fp32 add in front of all three terms -- the Standin terms compare against the noisy prediction too (losses.py:34-38)
 __global__ __launch_bounds__(256) void loss_partial(const float* __restrict__ pred, const float* __restrict__ pp,
                                                     const float* __restrict__ pl, const float* __restrict__ tgt,
-                                                    double* __restrict__ part, int64_t n, int reg_l2) {
+                                                    const float* __restrict__ noise, double* __restrict__ part, int64_t n,
+                                                    int reg_l2) {
     __shared__ double sm[4];
     double s1 = 0.0, s2 = 0.0, s3 = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const float o = pred[i];
+        const float o = noise ? pred[i] + noise[i] : pred[i];
         s1 += (double)fabsf(o - pp[i]);
         s2 += (double)fabsf(o - pl[i]);
         const float d = o - tgt[i];
@@ -1227,13 +1230,13 @@ __device__ __forceinline__ float sgnf(float v) { return v > 0.f ? 1.f : (v < 0.f
 
 __global__ void loss_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ pp,
                                 const float* __restrict__ pl, const float* __restrict__ tgt,
-                                const float* __restrict__ gscale, float* __restrict__ g_pred, float* __restrict__ g_p,
-                                float* __restrict__ g_l, int64_t n, float f0, float f1, float f2, int reg_l2,
-                                int use_mask) {
+                                const float* __restrict__ noise, const float* __restrict__ gscale,
+                                float* __restrict__ g_pred, float* __restrict__ g_p, float* __restrict__ g_l, int64_t n,
+                                float f0, float f1, float f2, int reg_l2, int use_mask) {
     const float gs = gscale ? gscale[0] : 1.f;
     const float inv_n = 1.0f / (float)n;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float o = pred[i];
+        const float o = noise ? pred[i] + noise[i] : pred[i];      // the same add as loss_partial's: the gradients keep their formulas
         // d|sg(o) - p| / dp = sign(p - o)
         g_p[i] = (use_mask & 1) ? gs * f0 * inv_n * sgnf(pp[i] - o) : 0.f;
         g_l[i] = (use_mask & 2) ? gs * f1 * inv_n * sgnf(pl[i] - o) : 0.f;
@@ -2269,29 +2272,43 @@ int nef_outconv_bwd_weight(const float* gout, const float* out, const float* x, 
 
 size_t nef_loss_ws_bytes(void) { return (size_t)LOSS_BLOCKS * 3 * sizeof(double); }
 
-int nef_loss_fwd(const float* pred, const float* pred_p, const float* pred_l, const float* target, float* losses,
-                 void* ws, size_t ws_bytes, int64_t n, float f0, float f1, float f2, int reg_l2, int use_mask,
-                 nef_stream_t stream) {
+int nef_loss_noise_fwd(const float* pred, const float* pred_p, const float* pred_l, const float* target,
+                       const float* noise, float* losses, void* ws, size_t ws_bytes, int64_t n, float f0, float f1, float f2,
+                       int reg_l2, int use_mask, nef_stream_t stream) {
     NEF_ENTER();
     NEF_REQUIRE(pred && pred_p && pred_l && target && losses && ws, NEF_E_NULL);
     NEF_REQUIRE(n > 0, NEF_E_SHAPE);
     NEF_REQUIRE(ws_bytes >= nef_loss_ws_bytes(), NEF_E_WORKSPACE);
-    hipLaunchKernelGGL(loss_partial, dim3(LOSS_BLOCKS), dim3(256), 0, NEF_ST, pred, pred_p, pred_l, target, (double*)ws,
-                       n, reg_l2);
+    hipLaunchKernelGGL(loss_partial, dim3(LOSS_BLOCKS), dim3(256), 0, NEF_ST, pred, pred_p, pred_l, target, noise,
+                       (double*)ws, n, reg_l2);
     hipLaunchKernelGGL(loss_final, dim3(1), dim3(256), 0, NEF_ST, (const double*)ws, losses, LOSS_BLOCKS, n, f0, f1, f2,
                        use_mask);
+    return nef_launch_status();
+}
+
+int nef_loss_fwd(const float* pred, const float* pred_p, const float* pred_l, const float* target, float* losses,
+                 void* ws, size_t ws_bytes, int64_t n, float f0, float f1, float f2, int reg_l2, int use_mask,
+                 nef_stream_t stream) {
+    return nef_loss_noise_fwd(pred, pred_p, pred_l, target, nullptr, losses, ws, ws_bytes, n, f0, f1, f2, reg_l2, use_mask,
+                              stream);
+}
+
+int nef_loss_noise_bwd(const float* pred, const float* pred_p, const float* pred_l, const float* target,
+                       const float* noise, const float* gscale, float* g_pred, float* g_p, float* g_l, int64_t n, float f0,
+                       float f1, float f2, int reg_l2, int use_mask, nef_stream_t stream) {
+    NEF_ENTER();
+    NEF_REQUIRE(pred && pred_p && pred_l && target && g_pred && g_p && g_l, NEF_E_NULL);
+    NEF_REQUIRE(n > 0, NEF_E_SHAPE);
+    hipLaunchKernelGGL(loss_bwd_kernel, dim3(nef_stream_grid(n, 256)), dim3(256), 0, NEF_ST, pred, pred_p, pred_l,
+                       target, noise, gscale, g_pred, g_p, g_l, n, f0, f1, f2, reg_l2, use_mask);
     return nef_launch_status();
 }
 
 int nef_loss_bwd(const float* pred, const float* pred_p, const float* pred_l, const float* target, const float* gscale,
                  float* g_pred, float* g_p, float* g_l, int64_t n, float f0, float f1, float f2, int reg_l2,
                  int use_mask, nef_stream_t stream) {
-    NEF_ENTER();
-    NEF_REQUIRE(pred && pred_p && pred_l && target && g_pred && g_p && g_l, NEF_E_NULL);
-    NEF_REQUIRE(n > 0, NEF_E_SHAPE);
-    hipLaunchKernelGGL(loss_bwd_kernel, dim3(nef_stream_grid(n, 256)), dim3(256), 0, NEF_ST, pred, pred_p, pred_l,
-                       target, gscale, g_pred, g_p, g_l, n, f0, f1, f2, reg_l2, use_mask);
-    return nef_launch_status();
+    return nef_loss_noise_bwd(pred, pred_p, pred_l, target, nullptr, gscale, g_pred, g_p, g_l, n, f0, f1, f2, reg_l2,
+                              use_mask, stream);
 }
 
 int nef_sgd_momentum(float* p, const float* g, float* buf, int64_t n, float lr, float mu, float gscale, int first_step,

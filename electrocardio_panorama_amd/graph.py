@@ -5,7 +5,8 @@ and the host cannot issue them as fast as the GPU retires them.  `GraphedTrainSt
 backward + the optimiser update once per input shape (torch.cuda.CUDAGraph on the stream the C ABI launches into) and replays
 it: inputs are copied into static buffers, and the only per-step host decisions -- the two Standin lead choices
 (reference model_nefnet.py:154,156, drawn from Python's `random` in the reference's order) and the dropout seed --
-travel through device words that the kernels read at run time.  Same arithmetic as the eager path.
+travel through device words that the kernels read at run time.  Same arithmetic as the eager path.  `cfg.DATA.noise`: the
+per-sample noise row is one more static input, added to the prediction inside the loss kernels (ops.loss_fwd / loss_bwd, noise=).
 
 One graph (with its own static input buffers) is kept per input shape, so a final partial batch or alternating shapes
 replay instead of re-capturing; the flat parameter / gradient / momentum buffers are shared by all of them and survive
@@ -33,9 +34,11 @@ class GraphedTrainStep:
         steps THAT optimiser's flat parameter / state buffers through its `_device_update` (so checkpoints, a learning-rate scheduler
         and eager steps in between see one state) and takes its scalars from its parameter group; without it the stepper owns its
         buffers and runs momentum SGD (lr / momentum arguments)."""
-        if cfg.DATA.noise:
-            raise NotImplementedError("cfg.DATA.noise adds a host-side tensor op between model and loss")
         self.model, self.cfg = model, cfg
+        # cfg.DATA.noise (reference solver.py:185-186): every shape slot owns a static [B, 1, L] noise buffer, staged with the other inputs
+        # and added inside the loss kernels; off: no buffer, no copy
+        self.use_noise = bool(cfg.DATA.noise)
+        self.noise = None
         self.optimizer = optimizer
         if optimizer is not None:
             if len(optimizer.param_groups) != 1 or not hasattr(optimizer, "_device_update"):
@@ -119,8 +122,8 @@ class GraphedTrainStep:
                                       phase="train", training=True, drop=drop, lead_choice=self.choice_dev, save=True,
                                       status=self.status)
             o, p_, l_ = (t.contiguous() for t in outs)
-            ops.loss_fwd(o, p_, l_, self.target, self.factors, self.reg_l2, self.use_mask, out=self.losses)
-            g3 = ops.loss_bwd(o, p_, l_, self.target, None, self.factors, self.reg_l2, self.use_mask)
+            ops.loss_fwd(o, p_, l_, self.target, self.factors, self.reg_l2, self.use_mask, out=self.losses, noise=self.noise)
+            g3 = ops.loss_bwd(o, p_, l_, self.target, None, self.factors, self.reg_l2, self.use_mask, noise=self.noise)
             return engine.backward(P, sv, g3)
 
     def _frozen(self):
@@ -206,8 +209,9 @@ class GraphedTrainStep:
     def _use(self, slot):
         self.data, self.in_theta, self.q_theta, self.rois, self.target = (slot[k] for k in
                                                                           ("data", "in_theta", "q_theta", "rois", "target"))
+        self.noise = slot.get("noise")
 
-    def _build(self, data, in_theta, q_theta, rois, target):
+    def _build(self, data, in_theta, q_theta, rois, target, noise=None):
         dev = data.device
         # static input buffers: contiguous whatever the caller's strides are (a sharded loader hands out slices)
         slot = dict(data=torch.empty(data.shape, device=dev, dtype=torch.float32),
@@ -215,6 +219,8 @@ class GraphedTrainStep:
                     q_theta=torch.empty(q_theta.shape, device=dev, dtype=torch.float32),
                     rois=torch.empty(rois.shape, device=dev, dtype=torch.int64),
                     target=torch.empty(data.shape[0], 1, data.shape[2], device=dev, dtype=torch.float32))
+        if self.use_noise:
+            slot["noise"] = torch.empty(data.shape[0], 1, data.shape[2], device=dev, dtype=torch.float32)
         self._use(slot)
         if self.choice_dev is None:
             self.choice_dev = torch.zeros(2, device=dev, dtype=torch.int32)
@@ -224,7 +230,7 @@ class GraphedTrainStep:
             self.lr_dev = torch.full((1,), self.lr, device=dev, dtype=torch.float32)
         # the probe runs THIS step's inputs, Standin choices and dropout seed (drawn by __call__ before it builds): the split-fp16
         # convs measure their operands in it, and what they measure must be what the eager path measures on the same step
-        self._stage(data, in_theta, q_theta, rois, target, draw=False)
+        self._stage(data, in_theta, q_theta, rois, target, noise, draw=False)
         self.model.train()
         # eager probe (no update): which parameters are live, and every kernel variant gets its one-time setup
         saved = {k: v.clone() for k, v in self.model.named_buffers()}
@@ -274,12 +280,14 @@ class GraphedTrainStep:
         self.calls += 1
         self._draws = (random.randint(0, V - 1), random.randint(0, V - 1))
 
-    def _stage(self, data, in_theta, q_theta, rois, target, draw=True):
+    def _stage(self, data, in_theta, q_theta, rois, target, noise=None, draw=True):
         self.data.copy_(data, non_blocking=True)
         self.in_theta.copy_(in_theta, non_blocking=True)
         self.q_theta.copy_(q_theta, non_blocking=True)
         self.rois.copy_(rois, non_blocking=True)
         self.target.copy_(target.reshape(self.target.shape), non_blocking=True)
+        if self.noise is not None:
+            self.noise.copy_(noise.reshape(self.noise.shape), non_blocking=True)
         if draw:
             self._draw()
         rank = dist.get_rank() if self.world > 1 else 0
@@ -325,9 +333,13 @@ class GraphedTrainStep:
         self.flat_buf.copy_(buf.to(self.flat_buf.device))
         self._pending_momentum = None
 
-    def __call__(self, data, in_theta, q_theta, rois, target):
-        """One train step; returns the device tensor [loss, f0*l1, f1*l2, f2*l3] (valid in stream order)."""
+    def __call__(self, data, in_theta, q_theta, rois, target, noise=None):
+        """One train step; returns the device tensor [loss, f0*l1, f1*l2, f2*l3] (valid in stream order).  `noise`: the batch's
+        [B, L] or [B, 1, L] noise rows, required when cfg.DATA.noise is set and ignored when it is not (as the reference ignores
+        meta['noise'] then)."""
         self.model._check_inputs(data, rois)       # what Model_nefnet.forward rejects (float rois, L % 4, CPU tensors) is rejected here too
+        if self.use_noise and noise is None:
+            raise ValueError("cfg.DATA.noise is set: the step needs this batch's noise")
         if self.optimizer is not None:
             g = self.optimizer.param_groups[0]
             cap = self._frozen()
@@ -350,10 +362,10 @@ class GraphedTrainStep:
         shape = (tuple(data.shape), tuple(in_theta.shape))
         slot = self.slots.get(shape)
         if slot is None:
-            slot = self.slots[shape] = self._build(data, in_theta, q_theta, rois, target)
+            slot = self.slots[shape] = self._build(data, in_theta, q_theta, rois, target, noise)
             self._restore_momentum()
         self._use(slot)
-        self._stage(data, in_theta, q_theta, rois, target, draw=False)
+        self._stage(data, in_theta, q_theta, rois, target, noise, draw=False)
         if not self.dp:
             slot["graph"].replay()
             return self.losses

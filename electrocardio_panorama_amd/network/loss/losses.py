@@ -6,24 +6,27 @@ from ... import ops
 
 class _LossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pred, pred_p, pred_l, target, factors, reg_l2, use_mask):
+    def forward(ctx, pred, pred_p, pred_l, target, factors, reg_l2, use_mask, noise=None):
         pred, pred_p, pred_l, target = (t.contiguous() for t in (pred, pred_p, pred_l, target))
-        ctx.save_for_backward(pred, pred_p, pred_l, target)
+        ctx.save_for_backward(pred, pred_p, pred_l, target, noise)
         ctx.cfg = (factors, reg_l2, use_mask)
-        return ops.loss_fwd(pred, pred_p, pred_l, target, factors, reg_l2, use_mask)
+        return ops.loss_fwd(pred, pred_p, pred_l, target, factors, reg_l2, use_mask, noise=noise)
 
     @staticmethod
     def backward(ctx, g):
-        pred, pred_p, pred_l, target = ctx.saved_tensors
+        pred, pred_p, pred_l, target, noise = ctx.saved_tensors
         factors, reg_l2, use_mask = ctx.cfg
-        g_pred, g_p, g_l = ops.loss_bwd(pred, pred_p, pred_l, target, g.contiguous(), factors, reg_l2, use_mask)
-        return g_pred, g_p, g_l, None, None, None, None
+        g_pred, g_p, g_l = ops.loss_bwd(pred, pred_p, pred_l, target, g.contiguous(), factors, reg_l2, use_mask, noise=noise)
+        return g_pred, g_p, g_l, None, None, None, None, None
 
 
 def losswrapper(predict, predict_shuffle_p, predict_shuffle_l, target, cfg, rest_out=None, rest_view=None,
-                loss1_gt=None, loss2_gt=None):
+                loss1_gt=None, loss2_gt=None, noise=None):
     """Returns (loss, f0*loss1, f1*loss2, f2*loss3[, loss_unsperv]) as 0-dim tensors; `loss` supports .backward().
-    The Standin terms compare against the detached prediction (OurLoss1, losses.py:5-18)."""
+    The Standin terms compare against the detached prediction (OurLoss1, losses.py:5-18).
+    `noise` (behind the reference's signature): cfg.DATA.noise's per-sample row, [B, 1, L] or anything that expands to the prediction's
+    shape.  The three terms are taken at predict + noise inside the loss kernels -- the reference's `out = out + noise` between model
+    and loss (solver.py:185-186), bit for bit, without a kernel of its own; the rest_out / rest_view term never sees it."""
     if cfg.SOLVER.reg_loss == 'l2_loss':
         reg_l2 = True
     elif cfg.SOLVER.reg_loss == 'l1_loss':
@@ -36,7 +39,9 @@ def losswrapper(predict, predict_shuffle_p, predict_shuffle_l, target, cfg, rest
     use_mask = (1 if 1 in using else 0) | (2 if 2 in using else 0) | (4 if 3 in using else 0)
     factors = tuple(float(f) for f in cfg.SOLVER.loss_factor)
     target = target.to(torch.float32).expand_as(predict)
-    L4 = _LossFn.apply(predict, predict_shuffle_p, predict_shuffle_l, target, factors, reg_l2, use_mask)
+    if noise is not None:
+        noise = noise.detach().to(torch.float32).expand_as(predict).contiguous()
+    L4 = _LossFn.apply(predict, predict_shuffle_p, predict_shuffle_l, target, factors, reg_l2, use_mask, noise)
     result = (L4[0], L4[1].detach(), L4[2].detach(), L4[3].detach())
     if rest_out is not None and rest_view is not None:
         ro = rest_out.detach().to(torch.float32).contiguous()
@@ -54,4 +59,4 @@ class MSELead(torch.nn.Module):
         target = target.to(torch.float32).expand_as(input)
         # element [0] (the total) is the one _LossFn back-propagates through; with factors (0, 0, 1) and only the
         # reconstruction term enabled it IS the MSE (element [3] carries the same number but no gradient)
-        return _LossFn.apply(input, input, input, target, (0.0, 0.0, 1.0), True, 4)[0]
+        return _LossFn.apply(input, input, input, target, (0.0, 0.0, 1.0), True, 4, None)[0]

@@ -1603,26 +1603,32 @@ def outconv_bwd_weight(gout, out, x, pro=None):
 
 
 # ------------------------------------------------------------------ loss / optimiser
-def loss_fwd(pred, pred_p, pred_l, target, factors, reg_l2, use_mask, out=None):
+def loss_fwd(pred, pred_p, pred_l, target, factors, reg_l2, use_mask, out=None, noise=None):
+    """`noise`: None, or cfg.DATA.noise's addend in pred's layout -- every term is taken at pred + noise (reference solver.py:185-186).
+    None is nef_loss_fwd: the same launches with a null pointer."""
     L = _lib.load()
     for t in (pred, pred_p, pred_l, target):
         _chk(t)
+    if noise is not None and _chk(noise).numel() != pred.numel():
+        raise ValueError(f"noise {tuple(noise.shape)} does not have the prediction's {tuple(pred.shape)} elements")
     losses = torch.empty(4, device=pred.device, dtype=torch.float32) if out is None else out
     n = L.nef_loss_ws_bytes()
     ws = workspace(n, pred.device)
-    _lib.check(L.nef_loss_fwd(_p(pred), _p(pred_p), _p(pred_l), _p(target), _p(losses), _p(ws), n, pred.numel(),
-                              factors[0], factors[1], factors[2], int(reg_l2), use_mask, _stream()), "nef_loss_fwd")
+    _lib.check(L.nef_loss_noise_fwd(_p(pred), _p(pred_p), _p(pred_l), _p(target), _p(noise), _p(losses), _p(ws), n, pred.numel(),
+                                    factors[0], factors[1], factors[2], int(reg_l2), use_mask, _stream()), "nef_loss_noise_fwd")
     return losses
 
 
-def loss_bwd(pred, pred_p, pred_l, target, gscale, factors, reg_l2, use_mask):
+def loss_bwd(pred, pred_p, pred_l, target, gscale, factors, reg_l2, use_mask, noise=None):
     L = _lib.load()
+    if noise is not None and _chk(noise).numel() != pred.numel():
+        raise ValueError(f"noise {tuple(noise.shape)} does not have the prediction's {tuple(pred.shape)} elements")
     # the three gradients as ONE [3B, 1, L] buffer (views): engine._head_bwd takes it as the stacked decoder-output gradient as is
     g3 = torch.empty((3 * pred.shape[0],) + tuple(pred.shape[1:]), device=pred.device, dtype=torch.float32)
     g_pred, g_p, g_l = g3[0:pred.shape[0]], g3[pred.shape[0]:2 * pred.shape[0]], g3[2 * pred.shape[0]:]
-    _lib.check(L.nef_loss_bwd(_p(pred), _p(pred_p), _p(pred_l), _p(target), _p(gscale), _p(g_pred), _p(g_p), _p(g_l),
-                              pred.numel(), factors[0], factors[1], factors[2], int(reg_l2), use_mask, _stream()),
-               "nef_loss_bwd")
+    _lib.check(L.nef_loss_noise_bwd(_p(pred), _p(pred_p), _p(pred_l), _p(target), _p(noise), _p(gscale), _p(g_pred), _p(g_p),
+                                    _p(g_l), pred.numel(), factors[0], factors[1], factors[2], int(reg_l2), use_mask, _stream()),
+               "nef_loss_noise_bwd")
     return g_pred, g_p, g_l
 
 

@@ -231,11 +231,11 @@ class Solver:
 
     def _graphed_step(self, optim, data, keep):
         """The hipGraph stepper for this batch, or None when the step runs eagerly: `cfg.SOLVER.graph` False, the per-view host lists are wanted (the graph returns losses only), the
-        model is not the plain Model_nefnet train path, DATA.noise, or the optimiser is not a fused one (FusedSGD, FusedAdam) with one
+        model is not the plain Model_nefnet train path, or the optimiser is not a fused one (FusedSGD, FusedAdam) with one
         parameter group."""
         mode = self.cfg.SOLVER.get('graph', None)
         mode = 'auto' if mode is None or mode == 'auto' else bool(mode)
-        if mode is False or keep or self.cfg.DATA.noise:
+        if mode is False or keep:
             return None
         if not hasattr(optim, '_flat') or len(optim.param_groups) != 1:
             return None
@@ -306,15 +306,15 @@ class Solver:
                 # forward + losswrapper + backward + SGD as ONE replayed hipGraph (one graph per batch shape: the final partial
                 # batch has its own; a learning-rate change re-captures); data parallel: the flat gradient travels as one
                 # all-reduce behind the replay (no early bucket under capture)
-                losses_s.add(stepper(source_data, input_theta, target_theta, rois, target_view))
+                losses_s.add(stepper(source_data, input_theta, target_theta, rois, target_view,
+                                     noise=noise if self.cfg.DATA.noise else None))
             elif phase == 'train':
                 out, shuf_p, shuf_l = self.model(source_data, input_theta, target_theta, rois, rest_theta=rest_theta,
                                                  phase='train')
                 if keep:
                     pred_s.add(out.squeeze(1))                     # solver.py:179 (before the optional noise)
-                if self.cfg.DATA.noise:
-                    out = out + noise
-                losses = self.loss(out, shuf_p, shuf_l, target_view, self.cfg)
+                # DATA.noise (solver.py:185-186): the loss kernels add the row to the prediction, no launch of its own
+                losses = self.loss(out, shuf_p, shuf_l, target_view, self.cfg, noise=noise if self.cfg.DATA.noise else None)
                 losses_s.add(torch.stack([l_.detach() for l_ in losses]))
                 losses[0].backward()
                 optim.step()

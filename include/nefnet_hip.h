@@ -515,6 +515,15 @@ int nef_loss_fwd(const float* pred, const float* pred_p, const float* pred_l, co
 int nef_loss_bwd(const float* pred, const float* pred_p, const float* pred_l, const float* target,
                  const float* gscale /* device scalar */, float* g_pred, float* g_p, float* g_l, int64_t n, float f0,
                  float f1, float f2, int reg_l2, int use_mask, nef_stream_t stream);
+/* The same two with cfg.DATA.noise (codes/solver/solver.py:185-186, `out = out + noise`): noise is NULL or n floats in pred's layout,
+ * and every term and gradient is taken at pred[i] + noise[i] (one fp32 add; the Standin terms compare against the noisy prediction
+ * as well, losses.py:34-38).  NULL noise: the entries above, bit for bit -- those are these with noise = NULL. */
+int nef_loss_noise_fwd(const float* pred, const float* pred_p, const float* pred_l, const float* target,
+                       const float* noise, float* losses, void* ws, size_t ws_bytes, int64_t n, float f0, float f1, float f2,
+                       int reg_l2, int use_mask, nef_stream_t stream);
+int nef_loss_noise_bwd(const float* pred, const float* pred_p, const float* pred_l, const float* target,
+                       const float* noise, const float* gscale /* device scalar */, float* g_pred, float* g_p, float* g_l,
+                       int64_t n, float f0, float f1, float f2, int reg_l2, int use_mask, nef_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * SGD with momentum over a flat buffer.  codes/solver/optim_scheduler.py:10 (torch.optim.SGD semantics:
