@@ -58,6 +58,16 @@ class BnBwdArgs(C.Structure):
     ]
 
 
+class UpdateArgs(C.Structure):
+    """Mirror of `nef_update_args` (include/nefnet_hip.h)."""
+    _fields_ = [
+        ("p", p), ("g", p), ("buf", p), ("m", p), ("v", p), ("step", p), ("skip_if_positive", p), ("skipped", p), ("lr_dev", p),
+        ("run_end", p), ("run_mul", p), ("n", i64), ("beta1", C.c_double), ("beta2", C.c_double),
+        ("lr", f32), ("gscale", f32), ("mu", f32), ("eps", f32), ("weight_decay", f32),
+        ("rule", i32), ("nesterov", i32), ("n_runs", i32),
+    ]
+
+
 class PackDesc(C.Structure):
     """Mirror of `nef_pack_desc` (include/nefnet_hip.h)."""
     _fields_ = [("w", p), ("wp", p), ("G", i32), ("Cog", i32), ("Cig", i32), ("K", i32), ("transpose_flip", i32),
@@ -140,6 +150,8 @@ SIGNATURES = {
     "nef_loss_noise_bwd": (i32, [p, p, p, p, p, p, p, p, p, i64, f32, f32, f32, i32, i32, p]),
     "nef_sgd_momentum": (i32, [p, p, p, i64, f32, f32, f32, i32, p, p, p, p]),
     "nef_adam": (i32, [p, p, p, p, i64, f32, C.c_double, C.c_double, f32, f32, f32, p, p, p, p, p]),
+    "nef_update": (i32, [C.POINTER(UpdateArgs), p]),
+    "nef_update_args_bytes": (sz, []),
     "nef_grad_clip_ws_bytes": (sz, []),
     "nef_grad_clip": (i32, [p, i64, f32, f32, p, p, p, sz, p]),
     "nef_h2_taint": (i32, [p, p, p, p]),
@@ -187,7 +199,8 @@ def load():
     # a stale .so next to a newer binding (or the reverse)
     for name, size, mirror in (("nef_conv_args", lib.nef_conv_args_bytes(), ConvArgs),
                                ("nef_bww_args", lib.nef_bww_args_bytes(), BwwArgs),
-                               ("nef_bn_bwd_args", lib.nef_bn_bwd_args_bytes(), BnBwdArgs)):
+                               ("nef_bn_bwd_args", lib.nef_bn_bwd_args_bytes(), BnBwdArgs),
+                               ("nef_update_args", lib.nef_update_args_bytes(), UpdateArgs)):
         if size != C.sizeof(mirror):
             raise NefLibraryError(f"{LIB_PATH}: {name} is {size} bytes, the binding mirrors {C.sizeof(mirror)}; rebuild with "
                                   "`python -m electrocardio_panorama_amd.csrc.build`")

@@ -32,6 +32,7 @@ _DEFAULTS = {
         "theta_L": 1,
     },
     "SOLVER": {
+        # 'sgd' (FusedSGD: torch.optim.SGD, momentum 0.9), 'adam' (FusedAdam: torch.optim.Adam) or 'adamw' (FusedAdamW: torch.optim.AdamW)
         "optim": "sgd",
         "scheduler": "steplr",
         "lr_step": [150, 350],
@@ -51,6 +52,16 @@ _DEFAULTS = {
         # in the eager and the graphed step): 0 = off (no launch, no allocation); inf = measure and report the norm, never scale;
         # a step whose norm is not finite is skipped
         "clip_grad_norm": 0.0,
+        # weight decay inside the one update launch (nef_update), with torch's semantics per optimiser: 'sgd' and 'adam' give L2 decay
+        # (weight_decay * p is added to the gradient, behind the clipping), 'adamw' gives decoupled decay (p *= 1 - lr * weight_decay in
+        # front of Adam's update).  0 = off: the optimisers issue the launches they issued before the key existed
+        "weight_decay": 0.0,
+        # 'sgd' only: Nesterov momentum (torch.optim.SGD(nesterov=True))
+        "nesterov": False,
+        # fnmatch patterns on the state_dict keys of the parameters that are EXEMPT from weight_decay, e.g. ['*.bias', '*.double_conv.[14].*']
+        # for the biases and the BatchNorm affine parameters; the exemption is a per-run multiplier inside the one flat launch, not a
+        # second parameter group (the graphed step and the clipping take one group)
+        "no_decay": [],
     },
 }
 

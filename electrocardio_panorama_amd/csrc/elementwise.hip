@@ -1328,6 +1328,130 @@ __global__ void adam_step_kernel(float* step, const float* __restrict__ skip) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// nef_update: SGD (L2 decay, Nesterov), Adam (L2 decay) and AdamW (decoupled decay) with a per-run decay multiplier
+// ------------------------------------------------------------------------------------------------
+// torch's operation order again.  SGD (_single_tensor_sgd, dampening 0): grad.add(param, alpha=wd); buf.mul_(mu).add_(grad);
+// grad = nesterov ? grad.add(buf, alpha=mu) : buf; param.add_(grad, alpha=-lr) -- a zero initial buf gives torch's first step
+// ("buf = grad") in both forms.  Adam: adam_elem.  AdamW (_single_tensor_adam, decoupled_weight_decay): param.mul_(1 - lr * wd) with
+// the factor formed from Python floats, then Adam's update on the undecayed gradient.
+// A zero decay adds and multiplies nothing, so wd = 0 (or a zero multiplier) gives the bits of sgd_kernel / adam_kernel.
+template <int RULE>
+struct upd_consts {
+    float lr, gscale, mu, wd;
+    int nesterov;
+    float w1, b2, w2, inv_bc2s, eps, step_size;      // RULE 1, 2
+};
+
+template <int RULE>
+__device__ __forceinline__ void upd_elem(const upd_consts<RULE>& c, float mul, float& p, float g, float& s0, float& s1) {
+    if (RULE == 0) {
+        float gv = g * c.gscale;
+        const float wd = c.wd * mul;
+        if (wd != 0.f) gv = gv + wd * p;
+        const float bv = fmaf(c.mu, s0, gv);
+        s0 = bv;
+        const float d = c.nesterov ? gv + c.mu * bv : bv;
+        p = p - c.lr * d;
+    } else if (RULE == 1) {
+        adam_elem(p, g, s0, s1, c.gscale, c.wd * mul, c.w1, c.b2, c.w2, c.inv_bc2s, c.eps, c.step_size);
+    } else {
+        const double wd = (double)c.wd * (double)mul;
+        if (wd != 0.0) p = p * (float)(1.0 - (double)c.lr * wd);
+        adam_elem(p, g, s0, s1, c.gscale, 0.f, c.w1, c.b2, c.w2, c.inv_bc2s, c.eps, c.step_size);
+    }
+}
+
+// The decay run table in LDS: the first run r >= lo whose exclusive end lies behind element i (ends ascending, the last one = n; the
+// result never leaves the table whatever the ends hold)
+__device__ __forceinline__ int upd_find_run(const int64_t* s_end, int n_runs, int lo, int64_t i) {
+    int hi = n_runs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (s_end[mid] > i) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+
+// s0 / s1: RULE 0 the momentum buffer / unused; RULES 1, 2 exp_avg / exp_avg_sq.  TABLE: every block stages the run table once; a lane
+// finds the run of its first element by binary search (from the run of its previous pass on: its indices only grow), takes that run's
+// multiplier for the whole vector when the run covers it, and walks the ends only where one falls inside the vector.
+template <int RULE, bool VEC, bool TABLE>
+__global__ __launch_bounds__(256) void update_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s0,
+                                                     float* __restrict__ s1, int64_t n, float lr, float mu, int nesterov, double b1,
+                                                     double b2, float eps, float wd, float gscale, const float* __restrict__ step,
+                                                     const float* __restrict__ skip, int32_t* skipped,
+                                                     const float* __restrict__ lr_dev, const int64_t* __restrict__ run_end,
+                                                     const float* __restrict__ run_mul, int n_runs) {
+    __shared__ int64_t s_end[TABLE ? NEF_UPDATE_MAX_RUNS : 1];
+    __shared__ float s_mul[TABLE ? NEF_UPDATE_MAX_RUNS : 1];
+    if (lr_dev) lr = lr_dev[0];
+    if (skip && skip[0] > 0.f) {      // a tainted step: parameters, state and the step word stay as they are -- the decay included
+        if (skipped && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(skipped, 1);
+        return;
+    }
+    if (TABLE) {
+        for (int r = threadIdx.x; r < n_runs; r += blockDim.x) s_end[r] = run_end[r], s_mul[r] = run_mul[r];
+        __syncthreads();
+    }
+    upd_consts<RULE> c;
+    c.lr = lr, c.gscale = gscale, c.mu = mu, c.wd = wd, c.nesterov = nesterov;
+    if (RULE != 0) {      // the bias corrections in fp64, as in adam_kernel
+        const double t = (double)step[0] + 1.0;
+        const double bc1 = 1.0 - pow(b1, t), bc2 = 1.0 - pow(b2, t);
+        c.step_size = (float)((double)lr / bc1);
+        c.inv_bc2s = 1.f / (float)sqrt(bc2);
+        c.w1 = (float)(1.0 - b1), c.w2 = (float)(1.0 - b2), c.b2 = (float)b2, c.eps = eps;
+    }
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t n4 = VEC ? (n >> 2) : 0;
+    int run = 0;
+    if (VEC) {      // 16-byte body: one dwordx4 load / store per stream and lane
+        for (int64_t i = gid; i < n4; i += stride) {
+            nef_f32x4 pv = ((const nef_f32x4*)p)[i], av = ((const nef_f32x4*)s0)[i], bv = {0.f, 0.f, 0.f, 0.f};
+            if (RULE != 0) bv = ((const nef_f32x4*)s1)[i];
+            const nef_f32x4 gv = ((const nef_f32x4*)g)[i];
+            float mul[4] = {1.f, 1.f, 1.f, 1.f};
+            if (TABLE) {
+                run = upd_find_run(s_end, n_runs, run, 4 * i);
+                int r = run;
+                mul[0] = s_mul[r];
+                if (s_end[r] >= 4 * i + 4) {
+                    mul[1] = mul[2] = mul[3] = mul[0];
+                } else {
+#pragma unroll
+                    for (int e = 1; e < 4; ++e) {
+                        while (r < n_runs - 1 && s_end[r] <= 4 * i + e) ++r;
+                        mul[e] = s_mul[r];
+                    }
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float pe = pv[e], ae = av[e], be = bv[e];
+                upd_elem<RULE>(c, mul[e], pe, gv[e], ae, be);
+                pv[e] = pe, av[e] = ae, bv[e] = be;
+            }
+            ((nef_f32x4*)p)[i] = pv;
+            ((nef_f32x4*)s0)[i] = av;
+            if (RULE != 0) ((nef_f32x4*)s1)[i] = bv;
+        }
+    }
+    run = 0;
+    for (int64_t i = 4 * n4 + gid; i < n; i += stride) {       // the n % 4 tail (VEC), or everything
+        float mul = 1.f;
+        if (TABLE) {
+            run = upd_find_run(s_end, n_runs, run, i);
+            mul = s_mul[run];
+        }
+        float pe = p[i], ae = s0[i], be = RULE != 0 ? s1[i] : 0.f;
+        upd_elem<RULE>(c, mul, pe, g[i], ae, be);
+        p[i] = pe, s0[i] = ae;
+        if (RULE != 0) s1[i] = be;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // torch.nn.utils.clip_grad_norm_(norm_type=2) over the flat gradient buffer            (no counterpart in the reference)
 // ------------------------------------------------------------------------------------------------
 // Three launches: partial sums of g^2 (fp64, a grid that depends on n alone, so the same buffer gives the same bits eagerly, under
@@ -1672,6 +1796,21 @@ __global__ void h2_taint_kernel(const int32_t* __restrict__ total, int32_t* __re
 }  // namespace
 
 #define NEF_ST ((hipStream_t)stream)
+
+template <int RULE, bool TABLE>
+static void update_launch(const nef_update_args& a, float* s0, float* s1, hipStream_t stream) {
+    const bool vec = (((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)s0 | (uintptr_t)s1) & 15) == 0 && a.n >= 4;      // (s1 NULL: aligned)
+#define NEF_UPDATE_ARGS                                                                                                            \
+    a.p, a.g, s0, s1, a.n, a.lr, a.mu, a.nesterov, a.beta1, a.beta2, a.eps, a.weight_decay, a.gscale, a.step, a.skip_if_positive, \
+        a.skipped, a.lr_dev, a.run_end, a.run_mul, a.n_runs
+    if (vec)
+        hipLaunchKernelGGL((update_kernel<RULE, true, TABLE>), dim3(nef_stream_grid(a.n >> 2, 256)), dim3(256), 0, NEF_ST,
+                           NEF_UPDATE_ARGS);
+    else
+        hipLaunchKernelGGL((update_kernel<RULE, false, TABLE>), dim3(nef_stream_grid(a.n, 256)), dim3(256), 0, NEF_ST,
+                           NEF_UPDATE_ARGS);
+#undef NEF_UPDATE_ARGS
+}
 
 extern "C" {
 
@@ -2336,6 +2475,35 @@ int nef_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, 
                            eps, weight_decay, gscale, step, skip_if_positive, skipped, lr_dev);
     // stream order: every block of the update has read the step word before this launch advances it
     hipLaunchKernelGGL(adam_step_kernel, dim3(1), dim3(1), 0, NEF_ST, step, skip_if_positive);
+    return nef_launch_status();
+}
+
+size_t nef_update_args_bytes(void) { return sizeof(nef_update_args); }
+
+int nef_update(const nef_update_args* args, nef_stream_t stream) {
+    NEF_ENTER();
+    NEF_REQUIRE(args, NEF_E_NULL);
+    const nef_update_args& a = *args;
+    NEF_REQUIRE(a.p && a.g, NEF_E_NULL);
+    NEF_REQUIRE(a.rule >= 0 && a.rule <= 2, NEF_E_UNSUPPORTED);
+    NEF_REQUIRE(a.rule == 0 ? a.buf != nullptr : (a.m && a.v && a.step), NEF_E_NULL);
+    NEF_REQUIRE(a.n > 0 && a.n_runs >= 0 && a.n_runs <= NEF_UPDATE_MAX_RUNS, NEF_E_SHAPE);
+    NEF_REQUIRE(a.n_runs == 0 || (a.run_end && a.run_mul), NEF_E_NULL);
+    NEF_REQUIRE(a.weight_decay >= 0.f, NEF_E_SHAPE);      // (a NaN fails the comparison too)
+    const bool table = a.n_runs > 0;
+    hipStream_t st = NEF_ST;
+    if (a.rule == 0) {
+        if (table) update_launch<0, true>(a, a.buf, nullptr, st);
+        else update_launch<0, false>(a, a.buf, nullptr, st);
+    } else if (a.rule == 1) {
+        if (table) update_launch<1, true>(a, a.m, a.v, st);
+        else update_launch<1, false>(a, a.m, a.v, st);
+    } else {
+        if (table) update_launch<2, true>(a, a.m, a.v, st);
+        else update_launch<2, false>(a, a.m, a.v, st);
+    }
+    // stream order: every block of the update has read the step word before this launch advances it
+    if (a.rule != 0) hipLaunchKernelGGL(adam_step_kernel, dim3(1), dim3(1), 0, NEF_ST, a.step, a.skip_if_positive);
     return nef_launch_status();
 }
 

@@ -1718,6 +1718,45 @@ def adam(p, g, m, v, step, lr, beta1, beta2, eps, weight_decay, gscale, skip=Non
     _done(ev)
 
 
+def _update(tag, hbm, rule, p, g, lr, gscale, weight_decay, runs, skip, lr_dev, **fields):
+    """One nef_update call (include/nefnet_hip.h).  `runs`: None, or the decay run table (run_end int64 [R], run_mul fp32 [R]) on p's
+    device -- exclusive ends in flat order, ascending, the last one = p.numel(); the library cannot check it."""
+    L = _lib.load()
+    _chk(p)
+    assert g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.numel() == p.numel()
+    run_end = run_mul = None
+    if runs is not None:
+        run_end, run_mul = runs
+        _chk(run_end, torch.int64), _chk(run_mul)
+        assert run_end.numel() == run_mul.numel() > 0
+    ev = _hbm(tag, *hbm)
+    sk = _p(_amax_state(p.device)["skipped"]) if skip is not None else None
+    A = _lib.UpdateArgs(p=_p(p), g=_p(g), n=p.numel(), lr=lr, gscale=gscale, weight_decay=weight_decay, rule=rule,
+                        skip_if_positive=_p(skip), skipped=sk, lr_dev=_p(lr_dev), run_end=_p(run_end), run_mul=_p(run_mul),
+                        n_runs=0 if run_end is None else run_end.numel(), **fields)
+    _lib.check(L.nef_update(C.byref(A), _stream()), "nef_update")
+    _done(ev)
+
+
+def update_sgd(p, g, buf, lr, mu, gscale, weight_decay=0.0, nesterov=False, runs=None, skip=None, lr_dev=None):
+    """torch.optim.SGD's update (momentum mu, dampening 0, L2 weight_decay, Nesterov) over flat fp32 buffers, in place on p / buf; `buf`
+    starts at zero.  `runs`: the decay run table (element i of run r decays with weight_decay * run_mul[r]); None = 1 everywhere.
+    `skip` / `lr_dev`: as for sgd_momentum -- a skipped step does not decay either."""
+    _chk(buf)
+    assert buf.numel() == p.numel()
+    _update("update_sgd", (p, p, g, buf, buf), 0, p, g, lr, gscale, weight_decay, runs, skip, lr_dev, buf=_p(buf), mu=mu,
+            nesterov=int(bool(nesterov)))
+
+
+def update_adam(p, g, m, v, step, lr, beta1, beta2, eps, weight_decay, gscale, decoupled=False, runs=None, skip=None, lr_dev=None):
+    """torch.optim.Adam's update with L2 weight_decay, or (`decoupled`) torch.optim.AdamW's, over flat fp32 buffers; `step`, `skip`,
+    `lr_dev`: as for adam.  `runs`: the decay run table, as for update_sgd."""
+    _chk(m), _chk(v), _chk(step)
+    assert p.numel() == m.numel() == v.numel() and step.numel() == 1
+    _update("update_adamw" if decoupled else "update_adam", (p, p, g, m, m, v, v), 2 if decoupled else 1, p, g, lr, gscale,
+            weight_decay, runs, skip, lr_dev, m=_p(m), v=_p(v), step=_p(step), beta1=beta1, beta2=beta2, eps=eps)
+
+
 def grad_clip(g, max_norm, gscale, stats, taint=None):
     """torch.nn.utils.clip_grad_norm_(max_norm, norm_type=2) on the averaged flat gradient gscale * g, in place on `g` (which stays the
     un-averaged sum: the update behind it applies gscale).  `stats`: 4 fp32 device words -- [0] the norm and [1] the coefficient of this

@@ -4,7 +4,11 @@
 parameter buffer, and -- when torch.distributed is initialised -- one RCCL all-reduce of the flat
 gradient buffer per step (data-parallel training, one process per GPU).
 'adam' returns FusedAdam: torch.optim.Adam(lr) semantics on the same flat-buffer machinery (one nef_adam launch).
+'adamw' returns FusedAdamW: torch.optim.AdamW.  SOLVER.weight_decay reaches all three (sgd, adam: L2, added to the gradient; adamw:
+decoupled), SOLVER.nesterov the first, and SOLVER.no_decay exempts tensors by name inside the one flat launch (decay_runs).
 DataParallelAdam (torch Adam behind a separate all-reduce) is kept as the unfused comparison."""
+import fnmatch
+
 import torch
 import torch.distributed as dist
 from torch.optim import Adam
@@ -17,6 +21,28 @@ from ..parallel import reduce_flat_grads
 # The flat gradient buffer starts with a 4-word header (16 bytes: word 0 = the taint word of ops.h2_taint, words 1..3 zero) so that
 # the gradients behind it, the encoder bucket's all-reduce (header + bucket) and the SGD kernel's reads stay 16-byte aligned.
 GRAD_HDR = 4
+MAX_RUNS = 256      # NEF_UPDATE_MAX_RUNS (include/nefnet_hip.h): runs of one nef_update launch
+
+
+def decay_runs(names, sizes, patterns):
+    """The decay run table of nef_update for tensors laid out one behind the other: `names[i]` (None: unnamed, never exempt) holds
+    `sizes[i]` elements and is exempt from weight decay -- multiplier 0 -- when it matches one of the fnmatch `patterns`, else it decays
+    in full (multiplier 1).  Neighbours with equal multipliers merge into one run.  Returns (ends, muls): the exclusive end of every run
+    in flat order and its multiplier; two empty lists when nothing is exempt (no table: multiplier 1 everywhere)."""
+    ends, muls, off = [], [], 0
+    for name, k in zip(names, sizes):
+        if k <= 0:
+            continue
+        mul = 0.0 if name is not None and any(fnmatch.fnmatchcase(name, pat) for pat in patterns) else 1.0
+        off += int(k)
+        if muls and muls[-1] == mul:
+            ends[-1] = off
+        else:
+            ends.append(off)
+            muls.append(mul)
+    if all(m == 1.0 for m in muls):
+        return [], []
+    return ends, muls
 
 
 class _FusedFlat(torch.optim.Optimizer):
@@ -29,8 +55,13 @@ class _FusedFlat(torch.optim.Optimizer):
     BatchNorm running statistics its forward pass already updated are NOT rolled back (DESIGN.md 3.0 "Range")."""
     _SLOTS = ()
 
-    def __init__(self, params, defaults, max_grad_norm=0.0):
+    def __init__(self, params, defaults, max_grad_norm=0.0, no_decay=()):
         super().__init__(params, defaults)
+        # fnmatch patterns on a parameter's `_nef_name` (Model_nefnet: its state_dict key): a match is exempt from weight decay.  An
+        # attribute like max_grad_norm, NOT a param_groups key; read when the flat buffers are built
+        if isinstance(no_decay, str):
+            no_decay = (no_decay,)
+        self.no_decay = tuple(str(pat) for pat in no_decay)
         self._flat = {}      # group index -> dict(ids, params, p, g_all, g, one flat buffer per _SLOTS key)
         # global gradient-norm clipping (ops.grad_clip on the mean gradient; 0 = off, inf = measure only).  An attribute, NOT a
         # param_groups key: the state dict stays in torch's format
@@ -62,6 +93,31 @@ class _FusedFlat(torch.optim.Optimizer):
         # split-fp16 launches) is summed by the same all-reduce as the gradients, so a clamp on any rank makes every rank skip the update
         g_all = torch.zeros(n + GRAD_HDR, device=dev, dtype=torch.float32)
         self._flat[gi] = dict(ids=[id(p) for p in live], params=live, p=flat_p, g_all=g_all, g=g_all[GRAD_HDR:], **slots)
+        # the decay run table over this layout (device tensors: the update launch reads them); nothing exempt: no table, no key
+        ends, muls = decay_runs([getattr(p, "_nef_name", None) for p in live], [p.numel() for p in live], self.no_decay)
+        if len(ends) > MAX_RUNS:
+            raise ValueError(f"no_decay splits the flat parameters into {len(ends)} runs; one update launch takes {MAX_RUNS}")
+        if ends:
+            self._flat[gi]["run_end"] = torch.tensor(ends, device=dev, dtype=torch.int64)
+            self._flat[gi]["run_mul"] = torch.tensor(muls, device=dev, dtype=torch.float32)
+
+    @staticmethod
+    def _runs(fl):
+        return (fl["run_end"], fl["run_mul"]) if "run_end" in fl else None
+
+    def decay_summary(self):
+        """One line per built parameter group: the exempt live tensors and how many elements decay; None before the first step."""
+        out = []
+        for gi, fl in sorted(self._flat.items()):
+            wd = float(self.param_groups[gi].get("weight_decay", 0.0))
+            names = [getattr(p, "_nef_name", None) for p in fl["params"]]
+            ends, muls = decay_runs(names, [p.numel() for p in fl["params"]], self.no_decay)
+            n = fl["p"].numel()
+            decayed = n if not ends else sum(e - b for b, e, m in zip([0] + ends[:-1], ends, muls) if m)
+            exempt = [k for k in names if k is not None and any(fnmatch.fnmatchcase(k, pat) for pat in self.no_decay)]
+            out.append("weight_decay {:g} on {} of {} elements ({} run(s)); exempt: {}".format(
+                wd, decayed if wd else 0, n, max(len(ends), 1), ", ".join(exempt) if exempt else "none"))
+        return "\n".join(out) if out else None
 
     def _current(self, gi, live):
         """The flat buffers of group `gi` for these live parameters, (re)built when the set changed or a parameter was re-pointed."""
@@ -181,19 +237,49 @@ class _FusedFlat(torch.optim.Optimizer):
 
 
 class FusedSGD(_FusedFlat):
-    """torch.optim.SGD(lr, momentum) semantics, one nef_sgd_momentum launch per parameter group."""
+    """torch.optim.SGD semantics (momentum > 0, dampening 0, L2 weight_decay, Nesterov), one launch per parameter group: nef_sgd_momentum
+    while the group uses neither decay nor Nesterov nor a no_decay table, nef_update (rule 0) otherwise.  The group carries torch's keys,
+    so state_dict() goes both ways with torch.optim.SGD."""
     _SLOTS = (("buf", "momentum_buffer"),)
 
-    def __init__(self, params, lr, momentum=0.9, max_grad_norm=0.0):
-        super().__init__(params, dict(lr=lr, momentum=momentum), max_grad_norm=max_grad_norm)
+    def __init__(self, params, lr, momentum=0.9, dampening=0, weight_decay=0, nesterov=False, *, no_decay=(), max_grad_norm=0.0):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= momentum:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        if dampening != 0:      # torch's first step takes buf = grad undamped: that needs a device step word
+            raise NotImplementedError("FusedSGD implements dampening=0")
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=bool(nesterov),
+                                      maximize=False, foreach=None, differentiable=False, fused=None),
+                         max_grad_norm=max_grad_norm, no_decay=no_decay)
 
-    def _captured_scalars(self, group):
-        return (float(group["momentum"]),)
+    @staticmethod
+    def _check_group(group):
+        if group.get("dampening", 0) != 0 or group.get("maximize"):
+            raise NotImplementedError("FusedSGD implements dampening=0, maximize=False")
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        for group in self.param_groups:
+            self._check_group(group)
+
+    def _captured_scalars(self, group):      # (.get: a group loaded from a checkpoint written before the keys existed)
+        return (float(group["momentum"]), float(group.get("weight_decay", 0.0)), bool(group.get("nesterov", False)))
 
     def _device_update(self, fl, group, gscale, skip=None, lr_dev=None):
         # buf starts at zero, so mu*buf + g reproduces torch's first-step "buf = g" exactly
-        ops.sgd_momentum(fl["p"], fl["g"], fl["buf"], float(group["lr"]), float(group["momentum"]), gscale, False, skip=skip,
-                         lr_dev=lr_dev)
+        self._check_group(group)
+        mu, wd, nesterov = self._captured_scalars(group)
+        runs = self._runs(fl)
+        if wd == 0.0 and not nesterov and runs is None:
+            ops.sgd_momentum(fl["p"], fl["g"], fl["buf"], float(group["lr"]), mu, gscale, False, skip=skip, lr_dev=lr_dev)
+        else:
+            ops.update_sgd(fl["p"], fl["g"], fl["buf"], float(group["lr"]), mu, gscale, wd, nesterov, runs=runs, skip=skip,
+                           lr_dev=lr_dev)
 
 
 class FusedAdam(_FusedFlat):
@@ -206,10 +292,12 @@ class FusedAdam(_FusedFlat):
     not kept current."""
     _SLOTS = (("m", "exp_avg"), ("v", "exp_avg_sq"))
 
+    _DECOUPLED = False
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, maximize=False,
-                 max_grad_norm=0.0):
+                 no_decay=(), max_grad_norm=0.0):
         if amsgrad or maximize:
-            raise NotImplementedError("FusedAdam implements amsgrad=False, maximize=False")
+            raise NotImplementedError(f"{type(self).__name__} implements amsgrad=False, maximize=False")
         if not 0.0 <= lr:
             raise ValueError(f"Invalid learning rate: {lr}")
         if not 0.0 <= eps:
@@ -218,8 +306,12 @@ class FusedAdam(_FusedFlat):
             raise ValueError(f"Invalid beta parameters: {betas}")
         if not 0.0 <= weight_decay:
             raise ValueError(f"Invalid weight_decay value: {weight_decay}")
-        super().__init__(params, dict(lr=lr, betas=(float(betas[0]), float(betas[1])), eps=eps, weight_decay=weight_decay,
-                                      amsgrad=False, maximize=False), max_grad_norm=max_grad_norm)
+        super().__init__(params, self._defaults(lr, (float(betas[0]), float(betas[1])), eps, weight_decay),
+                         max_grad_norm=max_grad_norm, no_decay=no_decay)
+
+    @staticmethod
+    def _defaults(lr, betas, eps, weight_decay):
+        return dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False)
 
     @staticmethod
     def _check_group(group):
@@ -265,7 +357,34 @@ class FusedAdam(_FusedFlat):
     def _device_update(self, fl, group, gscale, skip=None, lr_dev=None):
         self._check_group(group)
         b1, b2, eps, wd = self._captured_scalars(group)
-        ops.adam(fl["p"], fl["g"], fl["m"], fl["v"], fl["step"], float(group["lr"]), b1, b2, eps, wd, gscale, skip=skip, lr_dev=lr_dev)
+        runs = self._runs(fl)
+        if not self._DECOUPLED and runs is None:
+            ops.adam(fl["p"], fl["g"], fl["m"], fl["v"], fl["step"], float(group["lr"]), b1, b2, eps, wd, gscale, skip=skip, lr_dev=lr_dev)
+        else:
+            ops.update_adam(fl["p"], fl["g"], fl["m"], fl["v"], fl["step"], float(group["lr"]), b1, b2, eps, wd, gscale,
+                            decoupled=self._DECOUPLED, runs=runs, skip=skip, lr_dev=lr_dev)
+
+
+class FusedAdamW(FusedAdam):
+    """torch.optim.AdamW semantics on FusedAdam's machinery: the decay is decoupled -- p *= 1 - lr * weight_decay in front of Adam's
+    update on the undecayed gradient -- and defaults to 1e-2; one nef_update launch (rule 2) per parameter group.  The group carries
+    torch's keys (decoupled_weight_decay = True), so state_dict() goes both ways with torch.optim.AdamW."""
+    _DECOUPLED = True
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False,
+                 no_decay=(), max_grad_norm=0.0):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
+                         no_decay=no_decay, max_grad_norm=max_grad_norm)
+
+    @staticmethod
+    def _defaults(lr, betas, eps, weight_decay):
+        return dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, foreach=None,
+                    capturable=False, differentiable=False, fused=None, decoupled_weight_decay=True)
+
+    @staticmethod
+    def _check_group(group):
+        if group.get("amsgrad") or group.get("maximize") or not group.get("decoupled_weight_decay", True):
+            raise NotImplementedError("FusedAdamW implements amsgrad=False, maximize=False, decoupled weight_decay")
 
 
 class DataParallelAdam(Adam):
@@ -295,10 +414,15 @@ class DataParallelAdam(Adam):
 def get_optimizer(cfg, model_params):
     optim_name = cfg.SOLVER.optim
     clip = float(cfg.SOLVER.get('clip_grad_norm', 0.0))      # (.get: configs written before the key existed)
+    wd = float(cfg.SOLVER.get('weight_decay', 0.0))          # sgd, adam: L2 (added to the gradient); adamw: decoupled
+    no_decay = tuple(cfg.SOLVER.get('no_decay', None) or ())
     if optim_name == 'adam':
-        return FusedAdam(model_params, lr=cfg.SOLVER.lr, max_grad_norm=clip)
+        return FusedAdam(model_params, lr=cfg.SOLVER.lr, weight_decay=wd, no_decay=no_decay, max_grad_norm=clip)
+    elif optim_name == 'adamw':
+        return FusedAdamW(model_params, lr=cfg.SOLVER.lr, weight_decay=wd, no_decay=no_decay, max_grad_norm=clip)
     elif optim_name == 'sgd':
-        return FusedSGD(model_params, lr=cfg.SOLVER.lr, momentum=0.9, max_grad_norm=clip)
+        return FusedSGD(model_params, lr=cfg.SOLVER.lr, momentum=0.9, weight_decay=wd, nesterov=bool(cfg.SOLVER.get('nesterov', False)),
+                        no_decay=no_decay, max_grad_norm=clip)
 
 
 def get_lr_scheduler(cfg, optim=None):

@@ -146,6 +146,10 @@ class Solver:
                 dl_train.sampler.set_epoch(epoch)         # DistributedSampler: a new shuffle per epoch
             self.model.dropout_epoch = epoch
             train_losses = self.run_one_epoch(dl_train, phase='train', optim=optimizer, collect_views=False)[0]
+            if epoch == start_epoch and hasattr(optimizer, 'decay_summary') and (
+                    optimizer.no_decay or any(g.get('weight_decay', 0) for g in optimizer.param_groups)):
+                # once: which live tensors SOLVER.no_decay exempts and how many elements decay (known after the first step)
+                print(optimizer.decay_summary())
             scheduler.step()
             parallel.broadcast_buffers(self.model)        # rank 0's BatchNorm running statistics are the model's
             tl = np.mean(train_losses, axis=0)

@@ -544,6 +544,50 @@ int nef_sgd_momentum(float* p, const float* g, float* buf, int64_t n, float lr, 
 int nef_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2, float eps,
              float weight_decay, float gscale, float* step /* device word: completed updates */, const float* skip_if_positive,
              int32_t* skipped, const float* lr_dev, nef_stream_t stream);
+/* The update with weight decay: SGD with L2 decay and Nesterov momentum, Adam with L2 decay, AdamW, over a flat buffer in ONE launch
+ * (rules 1 and 2: plus the one-lane launch that advances *step), with a decay multiplier per RUN of elements -- so that biases and
+ * BatchNorm affine parameters can be exempt without a second parameter group, a mask buffer or a second launch (no counterpart in the
+ * reference, which never decays).  Element i of run r is decayed with wd_i = weight_decay * run_mul[r]; torch's operation order:
+ *   rule 0, torch.optim.SGD (dampening 0): g' = g*gscale + wd_i*p; buf = mu*buf + g'; d = nesterov ? g' + mu*buf : buf; p -= lr*d.
+ *           buf starts at zero (torch's first step "buf = g'" in both forms; dampening != 0 would need a device step word).
+ *   rule 1, torch.optim.Adam: the arithmetic of nef_adam with wd_i in place of weight_decay.
+ *   rule 2, torch.optim.AdamW: p *= (float)(1.0 - (double)lr * (double)wd_i), the factor formed in fp64 like the bias corrections
+ *           (lr: *lr_dev when given), then rule 1's update on the UNDECAYED gradient g*gscale.
+ * A positive skip word leaves p, every state buffer and *step as they are -- the decay included -- and counts the step; lr_dev
+ * replaces lr: both as for nef_sgd_momentum.  16-byte aligned p, g and state buffers take the vector path, anything else (and the
+ * n % 4 tail) the scalar one.  With weight_decay = 0, nesterov = 0 and no table the results are those of nef_sgd_momentum
+ * (first_step = 0) / nef_adam bit for bit; so are those of an all-zero table with weight_decay > 0.
+ * THE RUN TABLE IS THE CALLER'S DUTY: this entry cannot read device memory, so nothing checks that run_end is ascending, that its
+ * last element equals n or that run_mul is non-negative.  (A table that breaks this decays elements with another run's multiplier;
+ * the lookup itself never leaves the n_runs entries.)  Capturable: nothing is read by the host, nothing is allocated. */
+#define NEF_UPDATE_MAX_RUNS 256 /* runs of one launch (the table is staged in LDS); the model's 53 parameter tensors merge into fewer */
+typedef struct nef_update_args {
+    float* p;                      /* [n] parameters, updated in place */
+    const float* g;                /* [n] gradients (the un-averaged sum: multiplied by gscale first) */
+    float* buf;                    /* rule 0: [n] momentum buffer.  Rules 1, 2: unused */
+    float* m;                      /* rules 1, 2: [n] exp_avg */
+    float* v;                      /* rules 1, 2: [n] exp_avg_sq */
+    float* step;                   /* rules 1, 2: device word, completed updates (nef_adam's) */
+    const float* skip_if_positive; /* NULL, or a device word: > 0 = touch nothing */
+    int32_t* skipped;              /* NULL, or a device counter of skipped steps */
+    const float* lr_dev;           /* NULL, or a device word that replaces lr at run time */
+    const int64_t* run_end;        /* NULL (n_runs = 0: multiplier 1 everywhere), or [n_runs] device int64: the exclusive end of each run in
+                                      flat order, ascending, the last one = n */
+    const float* run_mul;          /* NULL, or [n_runs] device floats >= 0 */
+    int64_t n;
+    double beta1, beta2;           /* rules 1, 2 (doubles: see nef_adam) */
+    float lr, gscale;
+    float mu;                      /* rule 0: momentum */
+    float eps;                     /* rules 1, 2 */
+    float weight_decay;            /* >= 0 */
+    int32_t rule;                  /* 0 SGD, 1 Adam (L2 decay), 2 AdamW (decoupled decay); anything else: NEF_E_UNSUPPORTED */
+    int32_t nesterov;              /* rule 0 */
+    int32_t n_runs;                /* 0 .. NEF_UPDATE_MAX_RUNS; more: NEF_E_SHAPE */
+} nef_update_args;
+
+int nef_update(const nef_update_args* a, nef_stream_t stream);
+/* sizeof(nef_update_args) as the library was built: a binding checks its mirror of the struct against it. */
+size_t nef_update_args_bytes(void);
 /* Global gradient-norm clipping over a flat buffer: torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2) on the averaged
  * gradient gscale * g (no counterpart in the reference).  total = gscale * sqrt(sum g[i]^2), coef = min(1, max_norm / (total + 1e-6)),
  * g[i] *= coef; g stays the un-averaged sum, so the update launch behind this call still applies gscale.  The sum is deterministic:

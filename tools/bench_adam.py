@@ -2,6 +2,7 @@
 
     python tools/bench_adam.py [--steps 10] [--warmup 3] [--reps 3] [--out profiles/adam_bench_line.json]
     python tools/bench_adam.py --clip MAX_NORM [--parent-tree DIR] [--out profiles/clip_bench_line.json]
+    python tools/bench_adam.py --weight-decay X [--no-decay PATTERN...] [--parent-tree DIR] [--out profiles/wd_bench_line.json]
 
 Each measurement runs in a child process of its own under `timeout` (nothing more is started once one fails), `--reps` rounds of
 the three children; every figure is reported as [min, median, max] over the rounds:
@@ -17,7 +18,13 @@ Every child warms up before it times.
 max_grad_norm = MAX_NORM (sgd-graph-clip: also the three nef_grad_clip launches alone on the flat gradient buffer, cold as above, with
 a max_norm that clips), and -- with --parent-tree DIR -- the sgd-graph child of DIR/tools/bench_adam.py, in the same rounds on the same
 device.  DIR is a checkout of the commit to compare against; its library must already be built (nothing is built here) and its
-tools/bench_adam.py must accept `--child sgd-graph --steps N --warmup W`."""
+tools/bench_adam.py must accept `--child sgd-graph --steps N --warmup W`.
+
+--weight-decay X measures weight decay inside the update launch (nef_update): per round the graphed step with FusedSGD and FusedAdam as
+they are without decay (sgd-graph, adam-graph), with FusedSGD(weight_decay=X, no_decay=PATTERNS) (sgd-graph-wd) and with
+FusedAdamW(weight_decay=X, no_decay=PATTERNS) (adamw-graph), and -- with --parent-tree DIR -- DIR's own sgd-graph child.  The two decay
+children also time their update launch alone on the flat buffers with the model's real run table, cold as above and alternating with
+the entry it stands beside (nef_sgd_momentum, nef_adam) in the same process: same bytes, the table lookup on top."""
 import argparse
 import json
 import os
@@ -30,15 +37,38 @@ sys.path.insert(0, ROOT)
 
 MODES = {"sgd-graph": 900, "adam-graph": 900, "adam-eager": 1200}      # child -> its time limit (s)
 CLIP_MODES = {"sgd-graph": 900, "sgd-graph-clip": 900}
+WD_MODES = {"sgd-graph": 900, "sgd-graph-wd": 900, "adam-graph": 900, "adamw-graph": 900}
 
 
-def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0):
+def cold_ms(launches, dev, reps=30):
+    """Median device time (ms) of each callable in `launches`, cold: a 512 MiB buffer is written before every timed call, and the
+    callables take turns so that none of them always meets the same cache state."""
+    import numpy as np
+    import torch
+    flush = torch.empty(512 << 18, device=dev, dtype=torch.float32)        # 512 MiB
+    for fn in launches:
+        fn()
+    evs = [[] for _ in launches]
+    for i in range(reps):
+        for k, fn in enumerate(launches):
+            flush.fill_(float(i))
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            evs[k].append((a, b))
+    torch.cuda.synchronize(dev)
+    return [float(np.median([a.elapsed_time(b) for a, b in ev])) for ev in evs]
+
+
+def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()):
     import numpy as np
     import torch
     from electrocardio_panorama_amd import ops, synth
     from electrocardio_panorama_amd.config import get_defaults, resolve_config_path
     from electrocardio_panorama_amd.network import build_loss, build_model
     from electrocardio_panorama_amd.solver.optim_scheduler import DataParallelAdam, FusedAdam, FusedSGD
+    from electrocardio_panorama_amd.solver import optim_scheduler
     from electrocardio_panorama_amd.utils import seed_torch
     cfg = get_defaults()
     cfg.merge_from_file(resolve_config_path("config/nef_net.yml"))
@@ -52,8 +82,12 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0):
         optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9)
     elif mode == "sgd-graph-clip":
         optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9, max_grad_norm=clip)
+    elif mode == "sgd-graph-wd":
+        optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9, weight_decay=wd, no_decay=no_decay)
     elif mode == "adam-graph":
         optim = FusedAdam(model.parameters(), lr=1e-3)
+    elif mode == "adamw-graph":
+        optim = optim_scheduler.FusedAdamW(model.parameters(), lr=1e-3, weight_decay=wd, no_decay=no_decay)
     else:
         optim = DataParallelAdam(model.parameters(), lr=1e-3)
     meta = synth.make_batch(B, V, L, seed=123)
@@ -110,6 +144,23 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0):
         ms = float(np.median([a.elapsed_time(b) for a, b in cold]))
         res.update(nef_adam_cold_ms=round(ms, 4), nef_adam_warm_ms=round(warm, 4), nef_adam_params=n,
                    nef_adam_cold_GBps=round(7 * 4 * n / (ms * 1e-3) / 1e9, 1))
+    if mode in ("sgd-graph-wd", "adamw-graph"):
+        fl = optim._flat[0]
+        runs = optim._runs(fl)
+        n = fl["p"].numel()
+        if mode == "sgd-graph-wd":
+            p, g, buf = (fl[k].clone() for k in ("p", "g", "buf"))
+            old_ms, new_ms = cold_ms([lambda: ops.sgd_momentum(p, g, buf, 0.1, 0.9, 1.0, False),
+                                      lambda: ops.update_sgd(p, g, buf, 0.1, 0.9, 1.0, wd, False, runs=runs)], dev)
+            streams, old = 5, "nef_sgd_momentum"
+        else:
+            p, g, m, v, s = (fl[k].clone() for k in ("p", "g", "m", "v", "step"))
+            old_ms, new_ms = cold_ms([lambda: ops.adam(p, g, m, v, s, 1e-3, 0.9, 0.999, 1e-8, 0.0, 1.0),
+                                      lambda: ops.update_adam(p, g, m, v, s, 1e-3, 0.9, 0.999, 1e-8, wd, 1.0, decoupled=True, runs=runs)], dev)
+            streams, old = 7, "nef_adam"
+        res.update(weight_decay=wd, no_decay=list(no_decay), runs=0 if runs is None else int(runs[0].numel()), update_params=n,
+                   old_entry=old, old_entry_cold_ms=round(old_ms, 4), nef_update_cold_ms=round(new_ms, 4),
+                   nef_update_cold_GBps=round(streams * 4 * n / (new_ms * 1e-3) / 1e9, 1))
     if mode == "sgd-graph-clip":
         total, coef, clipped, bad = optim.clip_stats.tolist()
         g = optim._flat[0]["g"].clone()
@@ -142,19 +193,28 @@ def main():
     ap.add_argument("--reps", type=int, default=3, help="rounds of the three children")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     ap.add_argument("--clip", type=float, default=None, metavar="MAX_NORM", help="measure gradient-norm clipping (see above)")
-    ap.add_argument("--parent-tree", default=None, help="with --clip: a built checkout whose own sgd-graph child runs in every round")
-    ap.add_argument("--child", choices=sorted({**MODES, **CLIP_MODES}), default=None)
+    ap.add_argument("--weight-decay", type=float, default=None, metavar="X", help="measure weight decay in the update launch (see above)")
+    ap.add_argument("--no-decay", nargs="*", default=[], metavar="PATTERN", help="with --weight-decay: fnmatch patterns of exempt tensors")
+    ap.add_argument("--parent-tree", default=None,
+                    help="with --clip / --weight-decay: a built checkout whose own sgd-graph child runs in every round")
+    ap.add_argument("--child", choices=sorted({**MODES, **CLIP_MODES, **WD_MODES}), default=None)
     args = ap.parse_args()
     if args.child == "sgd-graph-clip" and not (args.clip is not None and args.clip > 0):
         ap.error("--child sgd-graph-clip needs --clip MAX_NORM > 0")
-    if args.parent_tree and args.clip is None:
-        ap.error("--parent-tree goes with --clip")
+    if args.child in ("sgd-graph-wd", "adamw-graph") and args.weight_decay is None:
+        ap.error(f"--child {args.child} needs --weight-decay X")
+    if args.clip is not None and args.weight_decay is not None:
+        ap.error("--clip and --weight-decay are two measurements")
+    if args.parent_tree and args.clip is None and args.weight_decay is None:
+        ap.error("--parent-tree goes with --clip or --weight-decay")
     if args.child:
         return child(args.child, args.steps if args.child != "adam-eager" else max(3, args.steps // 2), args.warmup,
-                     clip=args.clip or 0.0)
+                     clip=args.clip or 0.0, wd=args.weight_decay or 0.0, no_decay=tuple(args.no_decay))
     modes = dict(MODES)
     if args.clip is not None:
         modes = dict(CLIP_MODES, **({"parent": 900} if args.parent_tree else {}))
+    if args.weight_decay is not None:
+        modes = dict(WD_MODES, **({"parent": 900} if args.parent_tree else {}))
     results = {mode: [] for mode in modes}
     for rnd in range(args.reps):
         order = list(modes) if rnd % 2 == 0 else list(reversed(modes))       # no mode always runs first on a fresh box
@@ -164,17 +224,46 @@ def main():
                    "sgd-graph" if mode == "parent" else mode, "--steps", str(args.steps), "--warmup", str(args.warmup)]
             if mode == "sgd-graph-clip":
                 cmd += ["--clip", str(args.clip)]
+            if mode in ("sgd-graph-wd", "adamw-graph"):
+                cmd += ["--weight-decay", str(args.weight_decay), "--no-decay"] + list(args.no_decay)
             r = subprocess.run(cmd, cwd=tree, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
             line = [x for x in r.stdout.splitlines() if x.startswith("RESULT ")]
             if r.returncode != 0 or not line:
                 sys.stderr.write(r.stdout[-3000:])
                 raise SystemExit(f"{mode}: exit status {r.returncode}; nothing more is started")
             results[mode].append(json.loads(line[0][len("RESULT "):]))
+            sys.stderr.write(f"round {rnd + 1}/{args.reps} {mode}: {results[mode][-1]['ms_per_step']} ms/step\n")
+            sys.stderr.flush()
 
     def spread(mode, key):
         v = sorted(x[key] for x in results[mode])
         return [v[0], v[len(v) // 2], v[-1]]
 
+    if args.weight_decay is not None:
+        sw, aw = results["sgd-graph-wd"][0], results["adamw-graph"][0]
+        out = {"metric": "ms per train step, graphed, with and without weight decay in the update launch ([min, median, max] over rounds)",
+               "config": "BASELINE config 2: B=256, 3 leads, L=5000, one GPU, dropout on", "rounds": args.reps,
+               "weight_decay": args.weight_decay, "no_decay": list(args.no_decay), "runs": aw["runs"],
+               "sgd_graphed_decay_off_ms": spread("sgd-graph", "ms_per_step"), "sgd_graphed_decay_on_ms": spread("sgd-graph-wd", "ms_per_step"),
+               "adam_graphed_decay_off_ms": spread("adam-graph", "ms_per_step"), "adamw_graphed_decay_on_ms": spread("adamw-graph", "ms_per_step"),
+               "update_params": aw["update_params"],
+               "nef_adam_cold_ms": spread("adamw-graph", "old_entry_cold_ms"),
+               "nef_update_adamw_cold_ms": spread("adamw-graph", "nef_update_cold_ms"),
+               "nef_update_adamw_cold_GBps": spread("adamw-graph", "nef_update_cold_GBps"),
+               "nef_sgd_momentum_cold_ms": spread("sgd-graph-wd", "old_entry_cold_ms"),
+               "nef_update_sgd_cold_ms": spread("sgd-graph-wd", "nef_update_cold_ms"),
+               "nef_update_sgd_cold_GBps": spread("sgd-graph-wd", "nef_update_cold_GBps"),
+               "update_note": "the update launch alone on the flat buffers with the model's real run table (%d runs), alternating with the entry "
+                              "beside it in one process; cold = a 512 MiB buffer written before each launch" % sw["runs"],
+               "steps": args.steps, "warmup": args.warmup}
+        if args.parent_tree:
+            out["parent_sgd_graphed_ms"] = spread("parent", "ms_per_step")
+        line = json.dumps(out)
+        print(line)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        return
     if args.clip is not None:
         cg = results["sgd-graph-clip"]
         out = {"metric": "ms per train step, graphed FusedSGD with and without gradient-norm clipping ([min, median, max] over rounds)",
