@@ -68,6 +68,11 @@ class UpdateArgs(C.Structure):
     ]
 
 
+class EmaArgs(C.Structure):
+    """Mirror of `nef_ema_args` (include/nefnet_hip.h)."""
+    _fields_ = [("ema", p), ("n_averaged", p), ("decay", C.c_double), ("warmup", i32), ("reserved0", i32)]
+
+
 class PackDesc(C.Structure):
     """Mirror of `nef_pack_desc` (include/nefnet_hip.h)."""
     _fields_ = [("w", p), ("wp", p), ("G", i32), ("Cog", i32), ("Cig", i32), ("K", i32), ("transpose_flip", i32),
@@ -152,6 +157,8 @@ SIGNATURES = {
     "nef_adam": (i32, [p, p, p, p, i64, f32, C.c_double, C.c_double, f32, f32, f32, p, p, p, p, p]),
     "nef_update": (i32, [C.POINTER(UpdateArgs), p]),
     "nef_update_args_bytes": (sz, []),
+    "nef_update_ema": (i32, [C.POINTER(UpdateArgs), C.POINTER(EmaArgs), p]),
+    "nef_ema_args_bytes": (sz, []),
     "nef_grad_clip_ws_bytes": (sz, []),
     "nef_grad_clip": (i32, [p, i64, f32, f32, p, p, p, sz, p]),
     "nef_h2_taint": (i32, [p, p, p, p]),
@@ -200,7 +207,8 @@ def load():
     for name, size, mirror in (("nef_conv_args", lib.nef_conv_args_bytes(), ConvArgs),
                                ("nef_bww_args", lib.nef_bww_args_bytes(), BwwArgs),
                                ("nef_bn_bwd_args", lib.nef_bn_bwd_args_bytes(), BnBwdArgs),
-                               ("nef_update_args", lib.nef_update_args_bytes(), UpdateArgs)):
+                               ("nef_update_args", lib.nef_update_args_bytes(), UpdateArgs),
+                               ("nef_ema_args", lib.nef_ema_args_bytes(), EmaArgs)):
         if size != C.sizeof(mirror):
             raise NefLibraryError(f"{LIB_PATH}: {name} is {size} bytes, the binding mirrors {C.sizeof(mirror)}; rebuild with "
                                   "`python -m electrocardio_panorama_amd.csrc.build`")

@@ -62,6 +62,14 @@ _DEFAULTS = {
         # for the biases and the BatchNorm affine parameters; the exemption is a per-run multiplier inside the one flat launch, not a
         # second parameter group (the graphed step and the clipping take one group)
         "no_decay": [],
+        # an exponential moving average (EMA) of the weights, kept inside the one update launch (nef_update_ema) of the eager and the
+        # graphed step: e += (1 - ema_decay) * (p - e) after every update that is not skipped, e starting as a copy of the weights;
+        # BatchNorm statistics stay the live ones.  0 = off: no buffer, no 'ema' checkpoint entry, the launches issued before the key existed
+        "ema_decay": 0.0,
+        # the decay of EMA update t (counted from 0) is min(ema_decay, (1 + t) / (10 + t)): the average forgets its start quickly
+        "ema_warmup": False,
+        # with ema_decay > 0: the per-epoch test phase (psnr_gen, best_valid) and Solver.val run on the averaged weights
+        "ema_eval": True,
     },
 }
 

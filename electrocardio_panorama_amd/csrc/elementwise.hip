@@ -1327,6 +1327,13 @@ __global__ void adam_step_kernel(float* step, const float* __restrict__ skip) {
     if (!(skip && skip[0] > 0.f)) step[0] += 1.f;
 }
 
+// nef_update_ema's one-lane launch: the count of EMA updates and (rules 1, 2; NULL for rule 0) the step word advance together
+__global__ void ema_step_kernel(float* step, float* n_averaged, const float* __restrict__ skip) {
+    if (skip && skip[0] > 0.f) return;
+    if (step) step[0] += 1.f;
+    n_averaged[0] += 1.f;
+}
+
 // ------------------------------------------------------------------------------------------------
 // nef_update: SGD (L2 decay, Nesterov), Adam (L2 decay) and AdamW (decoupled decay) with a per-run decay multiplier
 // ------------------------------------------------------------------------------------------------
@@ -1376,13 +1383,17 @@ __device__ __forceinline__ int upd_find_run(const int64_t* s_end, int n_runs, in
 // s0 / s1: RULE 0 the momentum buffer / unused; RULES 1, 2 exp_avg / exp_avg_sq.  TABLE: every block stages the run table once; a lane
 // finds the run of its first element by binary search (from the run of its previous pass on: its indices only grow), takes that run's
 // multiplier for the whole vector when the run covers it, and walks the ends only where one falls inside the vector.
-template <int RULE, bool VEC, bool TABLE>
+// EMA (nef_update_ema): one more in/out stream next to p -- e = fmaf(w, p_new - e, e) on the freshly updated p, still in registers; the
+// weight comes from the count of completed EMA updates, a device word every block reads before the one-lane launch behind this one
+// (ema_step_kernel) advances it.  Without the flag the four arguments are dead and the kernel is the one it was.
+template <int RULE, bool VEC, bool TABLE, bool EMA>
 __global__ __launch_bounds__(256) void update_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s0,
                                                      float* __restrict__ s1, int64_t n, float lr, float mu, int nesterov, double b1,
                                                      double b2, float eps, float wd, float gscale, const float* __restrict__ step,
                                                      const float* __restrict__ skip, int32_t* skipped,
                                                      const float* __restrict__ lr_dev, const int64_t* __restrict__ run_end,
-                                                     const float* __restrict__ run_mul, int n_runs) {
+                                                     const float* __restrict__ run_mul, int n_runs, float* __restrict__ ema,
+                                                     const float* __restrict__ ema_n, double ema_decay, int ema_warmup) {
     __shared__ int64_t s_end[TABLE ? NEF_UPDATE_MAX_RUNS : 1];
     __shared__ float s_mul[TABLE ? NEF_UPDATE_MAX_RUNS : 1];
     if (lr_dev) lr = lr_dev[0];
@@ -1403,6 +1414,15 @@ __global__ __launch_bounds__(256) void update_kernel(float* __restrict__ p, cons
         c.inv_bc2s = 1.f / (float)sqrt(bc2);
         c.w1 = (float)(1.0 - b1), c.w2 = (float)(1.0 - b2), c.b2 = (float)b2, c.eps = eps;
     }
+    float ew = 0.f;
+    if (EMA) {      // w = 1 - d_t in fp64; warm-up: d_t = min(decay, (1 + t) / (10 + t)) over the completed EMA updates t
+        double d = ema_decay;
+        if (ema_warmup) {
+            const double t = (double)ema_n[0];
+            d = fmin(d, (1.0 + t) / (10.0 + t));
+        }
+        ew = (float)(1.0 - d);
+    }
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
     const int64_t n4 = VEC ? (n >> 2) : 0;
     int run = 0;
@@ -1411,6 +1431,8 @@ __global__ __launch_bounds__(256) void update_kernel(float* __restrict__ p, cons
             nef_f32x4 pv = ((const nef_f32x4*)p)[i], av = ((const nef_f32x4*)s0)[i], bv = {0.f, 0.f, 0.f, 0.f};
             if (RULE != 0) bv = ((const nef_f32x4*)s1)[i];
             const nef_f32x4 gv = ((const nef_f32x4*)g)[i];
+            nef_f32x4 ev = {0.f, 0.f, 0.f, 0.f};
+            if (EMA) ev = ((const nef_f32x4*)ema)[i];
             float mul[4] = {1.f, 1.f, 1.f, 1.f};
             if (TABLE) {
                 run = upd_find_run(s_end, n_runs, run, 4 * i);
@@ -1431,10 +1453,12 @@ __global__ __launch_bounds__(256) void update_kernel(float* __restrict__ p, cons
                 float pe = pv[e], ae = av[e], be = bv[e];
                 upd_elem<RULE>(c, mul[e], pe, gv[e], ae, be);
                 pv[e] = pe, av[e] = ae, bv[e] = be;
+                if (EMA) ev[e] = fmaf(ew, pe - ev[e], ev[e]);
             }
             ((nef_f32x4*)p)[i] = pv;
             ((nef_f32x4*)s0)[i] = av;
             if (RULE != 0) ((nef_f32x4*)s1)[i] = bv;
+            if (EMA) ((nef_f32x4*)ema)[i] = ev;
         }
     }
     run = 0;
@@ -1448,6 +1472,10 @@ __global__ __launch_bounds__(256) void update_kernel(float* __restrict__ p, cons
         upd_elem<RULE>(c, mul, pe, g[i], ae, be);
         p[i] = pe, s0[i] = ae;
         if (RULE != 0) s1[i] = be;
+        if (EMA) {
+            const float ee = ema[i];
+            ema[i] = fmaf(ew, pe - ee, ee);
+        }
     }
 }
 
@@ -1797,19 +1825,50 @@ __global__ void h2_taint_kernel(const int32_t* __restrict__ total, int32_t* __re
 
 #define NEF_ST ((hipStream_t)stream)
 
-template <int RULE, bool TABLE>
-static void update_launch(const nef_update_args& a, float* s0, float* s1, hipStream_t stream) {
-    const bool vec = (((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)s0 | (uintptr_t)s1) & 15) == 0 && a.n >= 4;      // (s1 NULL: aligned)
+template <int RULE, bool TABLE, bool EMA>
+static void update_launch(const nef_update_args& a, float* s0, float* s1, const nef_ema_args* e, hipStream_t stream) {
+    float* ema = EMA ? e->ema : nullptr;
+    // (s1, ema NULL: aligned)
+    const bool vec = (((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)s0 | (uintptr_t)s1 | (uintptr_t)ema) & 15) == 0 && a.n >= 4;
 #define NEF_UPDATE_ARGS                                                                                                            \
     a.p, a.g, s0, s1, a.n, a.lr, a.mu, a.nesterov, a.beta1, a.beta2, a.eps, a.weight_decay, a.gscale, a.step, a.skip_if_positive, \
-        a.skipped, a.lr_dev, a.run_end, a.run_mul, a.n_runs
+        a.skipped, a.lr_dev, a.run_end, a.run_mul, a.n_runs, ema, EMA ? (const float*)e->n_averaged : nullptr, EMA ? e->decay : 0.0, \
+        EMA ? (int)(e->warmup != 0) : 0
     if (vec)
-        hipLaunchKernelGGL((update_kernel<RULE, true, TABLE>), dim3(nef_stream_grid(a.n >> 2, 256)), dim3(256), 0, NEF_ST,
+        hipLaunchKernelGGL((update_kernel<RULE, true, TABLE, EMA>), dim3(nef_stream_grid(a.n >> 2, 256)), dim3(256), 0, NEF_ST,
                            NEF_UPDATE_ARGS);
     else
-        hipLaunchKernelGGL((update_kernel<RULE, false, TABLE>), dim3(nef_stream_grid(a.n, 256)), dim3(256), 0, NEF_ST,
+        hipLaunchKernelGGL((update_kernel<RULE, false, TABLE, EMA>), dim3(nef_stream_grid(a.n, 256)), dim3(256), 0, NEF_ST,
                            NEF_UPDATE_ARGS);
 #undef NEF_UPDATE_ARGS
+}
+
+// What nef_update and nef_update_ema check alike, in front of the first launch (nothing here touches the device)
+static int update_check(const nef_update_args* args) {
+    NEF_REQUIRE(args, NEF_E_NULL);
+    const nef_update_args& a = *args;
+    NEF_REQUIRE(a.p && a.g, NEF_E_NULL);
+    NEF_REQUIRE(a.rule >= 0 && a.rule <= 2, NEF_E_UNSUPPORTED);
+    NEF_REQUIRE(a.rule == 0 ? a.buf != nullptr : (a.m && a.v && a.step), NEF_E_NULL);
+    NEF_REQUIRE(a.n > 0 && a.n_runs >= 0 && a.n_runs <= NEF_UPDATE_MAX_RUNS, NEF_E_SHAPE);
+    NEF_REQUIRE(a.n_runs == 0 || (a.run_end && a.run_mul), NEF_E_NULL);
+    NEF_REQUIRE(a.weight_decay >= 0.f, NEF_E_SHAPE);      // (a NaN fails the comparison too)
+    return NEF_OK;
+}
+
+template <bool EMA>
+static void update_dispatch(const nef_update_args& a, const nef_ema_args* e, hipStream_t st) {
+    const bool table = a.n_runs > 0;
+    if (a.rule == 0) {
+        if (table) update_launch<0, true, EMA>(a, a.buf, nullptr, e, st);
+        else update_launch<0, false, EMA>(a, a.buf, nullptr, e, st);
+    } else if (a.rule == 1) {
+        if (table) update_launch<1, true, EMA>(a, a.m, a.v, e, st);
+        else update_launch<1, false, EMA>(a, a.m, a.v, e, st);
+    } else {
+        if (table) update_launch<2, true, EMA>(a, a.m, a.v, e, st);
+        else update_launch<2, false, EMA>(a, a.m, a.v, e, st);
+    }
 }
 
 extern "C" {
@@ -2482,28 +2541,27 @@ size_t nef_update_args_bytes(void) { return sizeof(nef_update_args); }
 
 int nef_update(const nef_update_args* args, nef_stream_t stream) {
     NEF_ENTER();
-    NEF_REQUIRE(args, NEF_E_NULL);
+    const int rc = update_check(args);
+    if (rc != NEF_OK) return rc;
     const nef_update_args& a = *args;
-    NEF_REQUIRE(a.p && a.g, NEF_E_NULL);
-    NEF_REQUIRE(a.rule >= 0 && a.rule <= 2, NEF_E_UNSUPPORTED);
-    NEF_REQUIRE(a.rule == 0 ? a.buf != nullptr : (a.m && a.v && a.step), NEF_E_NULL);
-    NEF_REQUIRE(a.n > 0 && a.n_runs >= 0 && a.n_runs <= NEF_UPDATE_MAX_RUNS, NEF_E_SHAPE);
-    NEF_REQUIRE(a.n_runs == 0 || (a.run_end && a.run_mul), NEF_E_NULL);
-    NEF_REQUIRE(a.weight_decay >= 0.f, NEF_E_SHAPE);      // (a NaN fails the comparison too)
-    const bool table = a.n_runs > 0;
-    hipStream_t st = NEF_ST;
-    if (a.rule == 0) {
-        if (table) update_launch<0, true>(a, a.buf, nullptr, st);
-        else update_launch<0, false>(a, a.buf, nullptr, st);
-    } else if (a.rule == 1) {
-        if (table) update_launch<1, true>(a, a.m, a.v, st);
-        else update_launch<1, false>(a, a.m, a.v, st);
-    } else {
-        if (table) update_launch<2, true>(a, a.m, a.v, st);
-        else update_launch<2, false>(a, a.m, a.v, st);
-    }
+    update_dispatch<false>(a, nullptr, NEF_ST);
     // stream order: every block of the update has read the step word before this launch advances it
     if (a.rule != 0) hipLaunchKernelGGL(adam_step_kernel, dim3(1), dim3(1), 0, NEF_ST, a.step, a.skip_if_positive);
+    return nef_launch_status();
+}
+
+size_t nef_ema_args_bytes(void) { return sizeof(nef_ema_args); }
+
+int nef_update_ema(const nef_update_args* args, const nef_ema_args* e, nef_stream_t stream) {
+    NEF_ENTER();
+    const int rc = update_check(args);
+    if (rc != NEF_OK) return rc;
+    NEF_REQUIRE(e && e->ema && e->n_averaged, NEF_E_NULL);
+    NEF_REQUIRE(e->decay >= 0.0 && e->decay < 1.0, NEF_E_SHAPE);      // (a NaN fails the comparison too)
+    const nef_update_args& a = *args;
+    update_dispatch<true>(a, e, NEF_ST);
+    // stream order: every block of the update has read the step word and the EMA count before this ONE launch advances both
+    hipLaunchKernelGGL(ema_step_kernel, dim3(1), dim3(1), 0, NEF_ST, a.rule != 0 ? a.step : nullptr, e->n_averaged, a.skip_if_positive);
     return nef_launch_status();
 }
 

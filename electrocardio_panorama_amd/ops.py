@@ -1718,11 +1718,21 @@ def adam(p, g, m, v, step, lr, beta1, beta2, eps, weight_decay, gscale, skip=Non
     _done(ev)
 
 
-def _update(tag, hbm, rule, p, g, lr, gscale, weight_decay, runs, skip, lr_dev, **fields):
+def _update(tag, hbm, rule, p, g, lr, gscale, weight_decay, runs, skip, lr_dev, ema=None, **fields):
     """One nef_update call (include/nefnet_hip.h).  `runs`: None, or the decay run table (run_end int64 [R], run_mul fp32 [R]) on p's
-    device -- exclusive ends in flat order, ascending, the last one = p.numel(); the library cannot check it."""
+    device -- exclusive ends in flat order, ascending, the last one = p.numel(); the library cannot check it.  `ema`: None, or
+    (ema, n_averaged, decay, warmup) -- the call is then nef_update_ema, its tag `tag` + "_ema" and its bytes two streams more."""
     L = _lib.load()
     _chk(p)
+    E = None
+    if ema is not None:
+        e_buf, e_n, decay, warmup = ema
+        _chk(e_buf), _chk(e_n)
+        assert e_buf.numel() == p.numel() and e_n.numel() == 1
+        if not 0.0 <= float(decay) < 1.0:
+            raise ValueError(f"Invalid ema decay: {decay}")
+        E = _lib.EmaArgs(ema=_p(e_buf), n_averaged=_p(e_n), decay=float(decay), warmup=int(bool(warmup)))
+        tag, hbm = tag + "_ema", tuple(hbm) + (e_buf, e_buf)
     assert g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.numel() == p.numel()
     run_end = run_mul = None
     if runs is not None:
@@ -1734,27 +1744,33 @@ def _update(tag, hbm, rule, p, g, lr, gscale, weight_decay, runs, skip, lr_dev, 
     A = _lib.UpdateArgs(p=_p(p), g=_p(g), n=p.numel(), lr=lr, gscale=gscale, weight_decay=weight_decay, rule=rule,
                         skip_if_positive=_p(skip), skipped=sk, lr_dev=_p(lr_dev), run_end=_p(run_end), run_mul=_p(run_mul),
                         n_runs=0 if run_end is None else run_end.numel(), **fields)
-    _lib.check(L.nef_update(C.byref(A), _stream()), "nef_update")
+    if E is None:
+        _lib.check(L.nef_update(C.byref(A), _stream()), "nef_update")
+    else:
+        _lib.check(L.nef_update_ema(C.byref(A), C.byref(E), _stream()), "nef_update_ema")
     _done(ev)
 
 
-def update_sgd(p, g, buf, lr, mu, gscale, weight_decay=0.0, nesterov=False, runs=None, skip=None, lr_dev=None):
+def update_sgd(p, g, buf, lr, mu, gscale, weight_decay=0.0, nesterov=False, runs=None, skip=None, lr_dev=None, ema=None):
     """torch.optim.SGD's update (momentum mu, dampening 0, L2 weight_decay, Nesterov) over flat fp32 buffers, in place on p / buf; `buf`
     starts at zero.  `runs`: the decay run table (element i of run r decays with weight_decay * run_mul[r]); None = 1 everywhere.
-    `skip` / `lr_dev`: as for sgd_momentum -- a skipped step does not decay either."""
+    `skip` / `lr_dev`: as for sgd_momentum -- a skipped step does not decay either.  `ema`: None, or (ema, n_averaged, decay, warmup):
+    the same launch also moves the flat fp32 average `ema` towards the new p by 1 - decay (warmup: 1 - min(decay, (1 + t) / (10 + t)))
+    and the one-word device count `n_averaged` = t advances behind it; a skipped step leaves both."""
     _chk(buf)
     assert buf.numel() == p.numel()
-    _update("update_sgd", (p, p, g, buf, buf), 0, p, g, lr, gscale, weight_decay, runs, skip, lr_dev, buf=_p(buf), mu=mu,
+    _update("update_sgd", (p, p, g, buf, buf), 0, p, g, lr, gscale, weight_decay, runs, skip, lr_dev, ema=ema, buf=_p(buf), mu=mu,
             nesterov=int(bool(nesterov)))
 
 
-def update_adam(p, g, m, v, step, lr, beta1, beta2, eps, weight_decay, gscale, decoupled=False, runs=None, skip=None, lr_dev=None):
+def update_adam(p, g, m, v, step, lr, beta1, beta2, eps, weight_decay, gscale, decoupled=False, runs=None, skip=None, lr_dev=None,
+                ema=None):
     """torch.optim.Adam's update with L2 weight_decay, or (`decoupled`) torch.optim.AdamW's, over flat fp32 buffers; `step`, `skip`,
-    `lr_dev`: as for adam.  `runs`: the decay run table, as for update_sgd."""
+    `lr_dev`: as for adam.  `runs`: the decay run table, `ema`: the weight average, both as for update_sgd."""
     _chk(m), _chk(v), _chk(step)
     assert p.numel() == m.numel() == v.numel() and step.numel() == 1
     _update("update_adamw" if decoupled else "update_adam", (p, p, g, m, m, v, v), 2 if decoupled else 1, p, g, lr, gscale,
-            weight_decay, runs, skip, lr_dev, m=_p(m), v=_p(v), step=_p(step), beta1=beta1, beta2=beta2, eps=eps)
+            weight_decay, runs, skip, lr_dev, ema=ema, m=_p(m), v=_p(v), step=_p(step), beta1=beta1, beta2=beta2, eps=eps)
 
 
 def grad_clip(g, max_norm, gscale, stats, taint=None):

@@ -6,8 +6,12 @@ gradient buffer per step (data-parallel training, one process per GPU; SURVEY.md
 'adam' returns FusedAdam: torch.optim.Adam(lr) semantics on the same flat-buffer machinery (one nef_adam launch).
 'adamw' returns FusedAdamW: torch.optim.AdamW.  SOLVER.weight_decay reaches all three (sgd, adam: L2, added to the gradient; adamw:
 decoupled), SOLVER.nesterov the first, and SOLVER.no_decay exempts tensors by name inside the one flat launch (decay_runs).
+SOLVER.ema_decay keeps an exponential moving average of the flat parameters inside that same launch (nef_update_ema): ema_state_dict,
+load_ema_state_dict and the ema_weights() context are its surface.
 DataParallelAdam (torch Adam behind a separate all-reduce) is kept as the unfused comparison."""
+import contextlib
 import fnmatch
+from collections import OrderedDict
 
 import torch
 import torch.distributed as dist
@@ -55,8 +59,16 @@ class _FusedFlat(torch.optim.Optimizer):
     BatchNorm running statistics its forward pass already updated are NOT rolled back (DESIGN.md 3.0 "Range")."""
     _SLOTS = ()
 
-    def __init__(self, params, defaults, max_grad_norm=0.0, no_decay=()):
+    def __init__(self, params, defaults, max_grad_norm=0.0, no_decay=(), ema_decay=0.0, ema_warmup=False):
         super().__init__(params, defaults)
+        # an exponential moving average of the parameters, kept by the update launch itself (ops.update_*(ema=)): e += (1 - d_t) * (p - e)
+        # after every update that is not skipped, d_t = ema_decay or (ema_warmup) min(ema_decay, (1 + t) / (10 + t)) over the t completed
+        # EMA updates.  0 = off: no buffer, no other launch.  Attributes like max_grad_norm, NOT param_groups keys
+        if not 0.0 <= float(ema_decay) < 1.0:      # (NaN fails the comparison too)
+            raise ValueError(f"Invalid ema_decay value: {ema_decay}")
+        self.ema_decay = float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self._ema_pending = None     # load_ema_state_dict: {"model": name -> tensor, "n_averaged"} until the flat buffers are built
         # fnmatch patterns on a parameter's `_nef_name` (Model_nefnet: its state_dict key): a match is exempt from weight decay.  An
         # attribute like max_grad_norm, NOT a param_groups key; read when the flat buffers are built
         if isinstance(no_decay, str):
@@ -74,6 +86,12 @@ class _FusedFlat(torch.optim.Optimizer):
     def _build(self, gi, live):
         n = sum(p.numel() for p in live)
         dev = live[0].device
+        old = self._flat.get(gi)
+        # the averages of the parameters that survive a rebuild, cut out of the old flat buffer (as the state slots are carried in state[p])
+        old_ema, off = {}, 0
+        for p in (old["params"] if old is not None and "ema" in old else ()):
+            old_ema[id(p)] = old["ema"][off:off + p.numel()]
+            off += p.numel()
         flat_p = torch.empty(n, device=dev, dtype=torch.float32)
         slots = {fk: torch.zeros(n, device=dev, dtype=torch.float32) for fk, _ in self._SLOTS}
         off = 0
@@ -100,10 +118,104 @@ class _FusedFlat(torch.optim.Optimizer):
         if ends:
             self._flat[gi]["run_end"] = torch.tensor(ends, device=dev, dtype=torch.int64)
             self._flat[gi]["run_mul"] = torch.tensor(muls, device=dev, dtype=torch.float32)
+        if self.ema_decay > 0:
+            # the average starts as a copy of the parameters (timm's ModelEmaV2); what a rebuild or a checkpoint carries replaces it
+            ema = flat_p.clone()
+            ema_n = old["ema_n"].clone() if old_ema else torch.zeros(1, device=dev, dtype=torch.float32)
+            off = 0
+            for p in live:
+                if id(p) in old_ema:
+                    ema[off:off + p.numel()].copy_(old_ema[id(p)])
+                off += p.numel()
+            self._flat[gi]["ema"], self._flat[gi]["ema_n"] = ema, ema_n
+            if self._ema_pending is not None:
+                self._import_ema(self._flat[gi], self._ema_pending, skip=old_ema)
+                if len(self.param_groups) == 1:      # (more groups: step() drops it behind the last one)
+                    self._ema_pending = None
 
     @staticmethod
     def _runs(fl):
         return (fl["run_end"], fl["run_mul"]) if "run_end" in fl else None
+
+    @staticmethod
+    def _import_ema(fl, pend, skip=()):
+        """The loaded average `pend` (load_ema_state_dict) into the flat buffers `fl`, by parameter name; parameters in `skip` (ids:
+        they carried their average over a rebuild) keep theirs, and so does the count when there are any."""
+        off = 0
+        for p in fl["params"]:
+            k, name = p.numel(), getattr(p, "_nef_name", None)
+            if id(p) not in skip and name in pend["model"]:
+                src = pend["model"][name]
+                if src.numel() != k:
+                    raise ValueError(f"the loaded EMA of {name} has {src.numel()} elements, the parameter {k}")
+                fl["ema"][off:off + k].copy_(src.reshape(-1))
+            off += k
+        if not skip:
+            fl["ema_n"].fill_(float(pend["n_averaged"]))
+
+    def _ema(self, fl):
+        """The `ema=` argument of ops.update_* for these flat buffers; None when the average is off."""
+        return (fl["ema"], fl["ema_n"], self.ema_decay, self.ema_warmup) if self.ema_decay > 0 else None
+
+    def _ema_scalars(self):
+        """The part of `_captured_scalars` every fused optimiser shares: a captured update freezes the decay and the warm-up flag (the
+        count of EMA updates lives on the device: a replay needs nothing)."""
+        return (float(self.ema_decay), bool(self.ema_warmup))
+
+    def ema_state_dict(self, model):
+        """The averaged model for a checkpoint: {"decay", "warmup", "n_averaged", "model"}; "model" has exactly the keys of
+        `model.state_dict()` -- the parameters the flat buffers cover hold their average, every other entry (parameters that never had a
+        gradient, BatchNorm statistics and the other buffers) the live tensor -- so `model.load_state_dict(sd["model"])` gives the
+        averaged model anywhere.  One synchronisation (the count), at checkpoint time only."""
+        avg, n_avg = {}, 0.0
+        if self._ema_pending is not None:          # loaded, not yet imported (no step since)
+            n_avg = float(self._ema_pending["n_averaged"])
+        for fl in self._flat.values():
+            if "ema" not in fl:
+                continue
+            n_avg, off = float(fl["ema_n"].item()), 0
+            for p in fl["params"]:
+                avg[id(p)] = fl["ema"][off:off + p.numel()].view_as(p.data)
+                off += p.numel()
+        out = OrderedDict(model.state_dict())
+        for name, p in model.named_parameters():
+            if id(p) in avg:
+                out[name] = avg[id(p)].detach().clone()
+            elif self._ema_pending is not None and getattr(p, "_nef_name", None) in self._ema_pending["model"]:
+                out[name] = self._ema_pending["model"][p._nef_name].detach().clone().view_as(p.data)
+        return {"decay": self.ema_decay, "warmup": self.ema_warmup, "n_averaged": n_avg, "model": out}
+
+    def load_ema_state_dict(self, sd):
+        """What ema_state_dict() returned.  The tensors are kept per parameter name (the parameters' `_nef_name`) and imported when the
+        flat buffers are built -- the next step: `load_state_dict` drops them -- or, where they exist, at once.  The decay and the
+        warm-up flag stay this optimiser's own; with the average off nothing is kept."""
+        if not self.ema_decay > 0:
+            return
+        pend = {"model": {(k[7:] if k.startswith("module.") else k): v.detach() for k, v in sd["model"].items()},
+                "n_averaged": float(sd.get("n_averaged", 0.0))}
+        built = [fl for fl in self._flat.values() if "ema" in fl]
+        for fl in built:
+            self._import_ema(fl, pend)
+        self._ema_pending = None if built else pend
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside, the model's parameters ARE the averaged ones (evaluation, export): the CONTENTS of fl["p"] and fl["ema"] are
+        exchanged and exchanged back on exit -- contents, not pointers, because captured graphs and the split-fp16 call sites are keyed
+        by address.  Plain torch copies through a temporary (this is outside the step).  Nothing happens before the first step or with
+        the average off."""
+        def swap():
+            for fl in self._flat.values():
+                if "ema" in fl:
+                    tmp = fl["p"].clone()
+                    fl["p"].copy_(fl["ema"])
+                    fl["ema"].copy_(tmp)
+            ops._PREPACKED.clear()      # an operand packed from the weights of the other side must not be served
+        swap()
+        try:
+            yield self
+        finally:
+            swap()
 
     def decay_summary(self):
         """One line per built parameter group: the exempt live tensors and how many elements decay; None before the first step."""
@@ -122,7 +234,7 @@ class _FusedFlat(torch.optim.Optimizer):
     def _current(self, gi, live):
         """The flat buffers of group `gi` for these live parameters, (re)built when the set changed or a parameter was re-pointed."""
         fl = self._flat.get(gi)
-        if fl is None or fl["ids"] != [id(p) for p in live] or any(
+        if fl is None or fl["ids"] != [id(p) for p in live] or ("ema" in fl) != (self.ema_decay > 0) or any(
                 p.data.data_ptr() < fl["p"].data_ptr() or
                 p.data.data_ptr() >= fl["p"].data_ptr() + fl["p"].numel() * 4 for p in live):
             self._build(gi, live)
@@ -233,6 +345,7 @@ class _FusedFlat(torch.optim.Optimizer):
         # the update wrote the parameters through raw pointers (no version bump): an operand pre-packed from the old weights by a forward
         # pass that no backward consumed (ops.pack_many) must not be served to the next one
         ops._PREPACKED.clear()
+        self._ema_pending = None      # a loaded average has been imported by every group that was built
         return None
 
 
@@ -242,7 +355,8 @@ class FusedSGD(_FusedFlat):
     so state_dict() goes both ways with torch.optim.SGD."""
     _SLOTS = (("buf", "momentum_buffer"),)
 
-    def __init__(self, params, lr, momentum=0.9, dampening=0, weight_decay=0, nesterov=False, *, no_decay=(), max_grad_norm=0.0):
+    def __init__(self, params, lr, momentum=0.9, dampening=0, weight_decay=0, nesterov=False, *, no_decay=(), max_grad_norm=0.0,
+                 ema_decay=0.0, ema_warmup=False):
         if not 0.0 <= lr:
             raise ValueError(f"Invalid learning rate: {lr}")
         if not 0.0 <= momentum:
@@ -255,7 +369,7 @@ class FusedSGD(_FusedFlat):
             raise NotImplementedError("FusedSGD implements dampening=0")
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=bool(nesterov),
                                       maximize=False, foreach=None, differentiable=False, fused=None),
-                         max_grad_norm=max_grad_norm, no_decay=no_decay)
+                         max_grad_norm=max_grad_norm, no_decay=no_decay, ema_decay=ema_decay, ema_warmup=ema_warmup)
 
     @staticmethod
     def _check_group(group):
@@ -268,18 +382,18 @@ class FusedSGD(_FusedFlat):
             self._check_group(group)
 
     def _captured_scalars(self, group):      # (.get: a group loaded from a checkpoint written before the keys existed)
-        return (float(group["momentum"]), float(group.get("weight_decay", 0.0)), bool(group.get("nesterov", False)))
+        return (float(group["momentum"]), float(group.get("weight_decay", 0.0)), bool(group.get("nesterov", False))) + self._ema_scalars()
 
     def _device_update(self, fl, group, gscale, skip=None, lr_dev=None):
         # buf starts at zero, so mu*buf + g reproduces torch's first-step "buf = g" exactly
         self._check_group(group)
-        mu, wd, nesterov = self._captured_scalars(group)
-        runs = self._runs(fl)
-        if wd == 0.0 and not nesterov and runs is None:
+        mu, wd, nesterov = self._captured_scalars(group)[:3]
+        runs, ema = self._runs(fl), self._ema(fl)
+        if wd == 0.0 and not nesterov and runs is None and ema is None:
             ops.sgd_momentum(fl["p"], fl["g"], fl["buf"], float(group["lr"]), mu, gscale, False, skip=skip, lr_dev=lr_dev)
         else:
             ops.update_sgd(fl["p"], fl["g"], fl["buf"], float(group["lr"]), mu, gscale, wd, nesterov, runs=runs, skip=skip,
-                           lr_dev=lr_dev)
+                           lr_dev=lr_dev, ema=ema)
 
 
 class FusedAdam(_FusedFlat):
@@ -295,7 +409,7 @@ class FusedAdam(_FusedFlat):
     _DECOUPLED = False
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, maximize=False,
-                 no_decay=(), max_grad_norm=0.0):
+                 no_decay=(), max_grad_norm=0.0, ema_decay=0.0, ema_warmup=False):
         if amsgrad or maximize:
             raise NotImplementedError(f"{type(self).__name__} implements amsgrad=False, maximize=False")
         if not 0.0 <= lr:
@@ -307,7 +421,7 @@ class FusedAdam(_FusedFlat):
         if not 0.0 <= weight_decay:
             raise ValueError(f"Invalid weight_decay value: {weight_decay}")
         super().__init__(params, self._defaults(lr, (float(betas[0]), float(betas[1])), eps, weight_decay),
-                         max_grad_norm=max_grad_norm, no_decay=no_decay)
+                         max_grad_norm=max_grad_norm, no_decay=no_decay, ema_decay=ema_decay, ema_warmup=ema_warmup)
 
     @staticmethod
     def _defaults(lr, betas, eps, weight_decay):
@@ -352,17 +466,17 @@ class FusedAdam(_FusedFlat):
 
     def _captured_scalars(self, group):
         b1, b2 = group["betas"]
-        return (float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]))
+        return (float(b1), float(b2), float(group["eps"]), float(group["weight_decay"])) + self._ema_scalars()
 
     def _device_update(self, fl, group, gscale, skip=None, lr_dev=None):
         self._check_group(group)
-        b1, b2, eps, wd = self._captured_scalars(group)
-        runs = self._runs(fl)
-        if not self._DECOUPLED and runs is None:
+        b1, b2, eps, wd = self._captured_scalars(group)[:4]
+        runs, ema = self._runs(fl), self._ema(fl)
+        if not self._DECOUPLED and runs is None and ema is None:
             ops.adam(fl["p"], fl["g"], fl["m"], fl["v"], fl["step"], float(group["lr"]), b1, b2, eps, wd, gscale, skip=skip, lr_dev=lr_dev)
         else:
             ops.update_adam(fl["p"], fl["g"], fl["m"], fl["v"], fl["step"], float(group["lr"]), b1, b2, eps, wd, gscale,
-                            decoupled=self._DECOUPLED, runs=runs, skip=skip, lr_dev=lr_dev)
+                            decoupled=self._DECOUPLED, runs=runs, skip=skip, lr_dev=lr_dev, ema=ema)
 
 
 class FusedAdamW(FusedAdam):
@@ -372,9 +486,9 @@ class FusedAdamW(FusedAdam):
     _DECOUPLED = True
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False,
-                 no_decay=(), max_grad_norm=0.0):
+                 no_decay=(), max_grad_norm=0.0, ema_decay=0.0, ema_warmup=False):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
-                         no_decay=no_decay, max_grad_norm=max_grad_norm)
+                         no_decay=no_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup)
 
     @staticmethod
     def _defaults(lr, betas, eps, weight_decay):
@@ -416,13 +530,14 @@ def get_optimizer(cfg, model_params):
     clip = float(cfg.SOLVER.get('clip_grad_norm', 0.0))      # (.get: configs written before the key existed)
     wd = float(cfg.SOLVER.get('weight_decay', 0.0))          # sgd, adam: L2 (added to the gradient); adamw: decoupled
     no_decay = tuple(cfg.SOLVER.get('no_decay', None) or ())
+    ema = dict(ema_decay=float(cfg.SOLVER.get('ema_decay', 0.0)), ema_warmup=bool(cfg.SOLVER.get('ema_warmup', False)))
     if optim_name == 'adam':
-        return FusedAdam(model_params, lr=cfg.SOLVER.lr, weight_decay=wd, no_decay=no_decay, max_grad_norm=clip)
+        return FusedAdam(model_params, lr=cfg.SOLVER.lr, weight_decay=wd, no_decay=no_decay, max_grad_norm=clip, **ema)
     elif optim_name == 'adamw':
-        return FusedAdamW(model_params, lr=cfg.SOLVER.lr, weight_decay=wd, no_decay=no_decay, max_grad_norm=clip)
+        return FusedAdamW(model_params, lr=cfg.SOLVER.lr, weight_decay=wd, no_decay=no_decay, max_grad_norm=clip, **ema)
     elif optim_name == 'sgd':
         return FusedSGD(model_params, lr=cfg.SOLVER.lr, momentum=0.9, weight_decay=wd, nesterov=bool(cfg.SOLVER.get('nesterov', False)),
-                        no_decay=no_decay, max_grad_norm=clip)
+                        no_decay=no_decay, max_grad_norm=clip, **ema)
 
 
 def get_lr_scheduler(cfg, optim=None):

@@ -13,6 +13,7 @@ device by `nef_view_metrics`, one launch per batch.
 Data parallelism replaces `nn.DataParallel` (solver.py:32-34) with one process per GPU (`parallel.py`): the loaders
 hand every rank its shard, FusedSGD all-reduces the flat gradient, rank 0 owns the BatchNorm running statistics,
 the scalar log and the checkpoints."""
+import contextlib
 import json
 import os
 
@@ -159,7 +160,9 @@ class Solver:
             psnr_gen = psnr_reg = 0.
             msg = 'Epoch {}: train_loss: {}'.format(epoch, train_loss_all)
             if dl_test is not None:
-                test_losses, _, _, _, mertics_all, _, single = self.run_one_epoch(dl_test, phase='test', collect_views=False)
+                # SOLVER.ema_decay with ema_eval: the test phase -- and with it psnr_gen and best_valid -- sees the averaged weights
+                with optimizer.ema_weights() if self._ema_eval(optimizer) else contextlib.nullcontext():
+                    test_losses, _, _, _, mertics_all, _, single = self.run_one_epoch(dl_test, phase='test', collect_views=False)
                 te = np.mean(test_losses, axis=0)
                 psnr_gen, psnr_reg, ssim_gen, ssim_reg = (float(v) for v in np.mean(mertics_all, axis=0))
                 # the reference's scalar set and names (solver.py:82-100)
@@ -194,6 +197,12 @@ class Solver:
                     save_arguments['epoch'] = epoch
                     checkpointer.save('best_valid', **save_arguments)
 
+    def _ema_eval(self, optimizer=None):
+        """Whether evaluation runs on the averaged weights: SOLVER.ema_decay > 0 and SOLVER.ema_eval (and, when an optimiser is given,
+        that optimiser keeps the average)."""
+        on = float(self.cfg.SOLVER.get('ema_decay', 0.0)) > 0 and bool(self.cfg.SOLVER.get('ema_eval', True))
+        return on and (optimizer is None or getattr(optimizer, 'ema_decay', 0.0) > 0)
+
     def val(self, dl_test, epoch=-1):
         """solver.py:118-137: load `best_valid.pkl` (epoch == -1) or `epoch_<n>.pkl`, run the test phase, print and
         return (psnr_gen, psnr_reg, ssim_gen, ssim_reg)."""
@@ -202,9 +211,9 @@ class Solver:
         scheduler = get_lr_scheduler(self.cfg, optimizer)
         checkpointer = CheckPointer(self.model, optimizer, scheduler, self.output_dir)
         if epoch == -1:
-            extra = checkpointer.load(best_valid=True)
+            extra = checkpointer.load(best_valid=True, ema=self._ema_eval())
         else:
-            extra = checkpointer.load(os.path.join(self.output_dir, 'epoch_{}.pkl'.format(epoch)))
+            extra = checkpointer.load(os.path.join(self.output_dir, 'epoch_{}.pkl'.format(epoch)), ema=self._ema_eval())
         print('the latest best_test_psnr_gen is {:06f} of epoch {}'.format(extra.get('best_test_psnr_gen', 0.),
                                                                            extra.get('epoch', 0)))
         with torch.no_grad():

@@ -588,6 +588,26 @@ typedef struct nef_update_args {
 int nef_update(const nef_update_args* a, nef_stream_t stream);
 /* sizeof(nef_update_args) as the library was built: a binding checks its mirror of the struct against it. */
 size_t nef_update_args_bytes(void);
+/* nef_update with one more in/out stream: an exponential moving average (EMA) of the parameters, kept inside the same launch (no
+ * counterpart in the reference).  After the update of element i -- its new p still in registers -- ema[i] = fmaf(w, p[i] - ema[i],
+ * ema[i]) in fp32, with w = (float)(1.0 - d_t) formed in fp64; d_t = decay, or with warmup min(decay, (1 + t) / (10 + t)) where
+ * t = *n_averaged, the number of completed EMA updates (a device word like *step: every block reads it before anything changes it).
+ * The one-lane launch behind the update advances *n_averaged -- for rules 1 and 2 it is the launch that advances *step, still one.
+ * p, the state buffers and *step get the bits nef_update gives them for the same nef_update_args.  A positive skip word leaves ema
+ * and *n_averaged as they are too; lr_dev and skipped: as for nef_update.  The vector path needs ema 16-byte aligned as well.
+ * Returns what nef_update returns for `a`; e, e->ema or e->n_averaged NULL: NEF_E_NULL; decay outside [0, 1) or NaN: NEF_E_SHAPE.
+ * Capturable: nothing is read by the host, nothing is allocated. */
+typedef struct nef_ema_args {
+    float* ema;                    /* [n] the averaged parameters, updated in place */
+    float* n_averaged;             /* device word: completed EMA updates */
+    double decay;                  /* in [0, 1) */
+    int32_t warmup;                /* != 0: d_t = min(decay, (1 + t) / (10 + t)) */
+    int32_t reserved0;             /* 0 */
+} nef_ema_args;
+
+int nef_update_ema(const nef_update_args* a, const nef_ema_args* e, nef_stream_t stream);
+/* sizeof(nef_ema_args) as the library was built. */
+size_t nef_ema_args_bytes(void);
 /* Global gradient-norm clipping over a flat buffer: torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2) on the averaged
  * gradient gscale * g (no counterpart in the reference).  total = gscale * sqrt(sum g[i]^2), coef = min(1, max_norm / (total + 1e-6)),
  * g[i] *= coef; g stays the un-averaged sum, so the update launch behind this call still applies gscale.  The sum is deterministic:

@@ -3,6 +3,7 @@
     python tools/bench_adam.py [--steps 10] [--warmup 3] [--reps 3] [--out profiles/adam_bench_line.json]
     python tools/bench_adam.py --clip MAX_NORM [--parent-tree DIR] [--out profiles/clip_bench_line.json]
     python tools/bench_adam.py --weight-decay X [--no-decay PATTERN...] [--parent-tree DIR] [--out profiles/wd_bench_line.json]
+    python tools/bench_adam.py --ema D [--parent-tree DIR] [--out profiles/ema_bench_line.json]
 
 Each measurement runs in a child process of its own under `timeout` (nothing more is started once one fails), `--reps` rounds of
 the three children; every figure is reported as [min, median, max] over the rounds:
@@ -24,7 +25,13 @@ tools/bench_adam.py must accept `--child sgd-graph --steps N --warmup W`.
 they are without decay (sgd-graph, adam-graph), with FusedSGD(weight_decay=X, no_decay=PATTERNS) (sgd-graph-wd) and with
 FusedAdamW(weight_decay=X, no_decay=PATTERNS) (adamw-graph), and -- with --parent-tree DIR -- DIR's own sgd-graph child.  The two decay
 children also time their update launch alone on the flat buffers with the model's real run table, cold as above and alternating with
-the entry it stands beside (nef_sgd_momentum, nef_adam) in the same process: same bytes, the table lookup on top."""
+the entry it stands beside (nef_sgd_momentum, nef_adam) in the same process: same bytes, the table lookup on top.
+
+--ema D measures the EMA of the weights inside the update launch (nef_update_ema), at config 2 AND at the reference's own training shape
+(B=32, L=512): per round and shape the graphed FusedSGD step with the average off (sgd-graph) and with ema_decay = D (sgd-graph-ema), and
+-- with --parent-tree DIR -- DIR's own sgd-graph step at that shape (DIR/tools/bench_adam.py's `child` function, called in a fresh
+process).  The config-2 EMA child also times the update launch alone on the flat buffers, cold as above: nef_update_ema beside nef_update
+in one process (rule 0, no table: five fp32 streams per parameter against seven)."""
 import argparse
 import json
 import os
@@ -38,6 +45,8 @@ sys.path.insert(0, ROOT)
 MODES = {"sgd-graph": 900, "adam-graph": 900, "adam-eager": 1200}      # child -> its time limit (s)
 CLIP_MODES = {"sgd-graph": 900, "sgd-graph-clip": 900}
 WD_MODES = {"sgd-graph": 900, "sgd-graph-wd": 900, "adam-graph": 900, "adamw-graph": 900}
+EMA_MODES = {"sgd-graph": 900, "sgd-graph-ema": 900}
+EMA_SHAPES = {"config2": (256, 5000), "reference": (32, 512)}      # (B, L) at 3 leads
 
 
 def cold_ms(launches, dev, reps=30):
@@ -61,7 +70,7 @@ def cold_ms(launches, dev, reps=30):
     return [float(np.median([a.elapsed_time(b) for a, b in ev])) for ev in evs]
 
 
-def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()):
+def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=(), ema=0.0):
     import numpy as np
     import torch
     from electrocardio_panorama_amd import ops, synth
@@ -84,6 +93,8 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
         optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9, max_grad_norm=clip)
     elif mode == "sgd-graph-wd":
         optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9, weight_decay=wd, no_decay=no_decay)
+    elif mode == "sgd-graph-ema":
+        optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9, ema_decay=ema)
     elif mode == "adam-graph":
         optim = FusedAdam(model.parameters(), lr=1e-3)
     elif mode == "adamw-graph":
@@ -116,7 +127,16 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
     for _ in range(steps):
         step()
     torch.cuda.synchronize(dev)
-    res = {"mode": mode, "ms_per_step": round((time.perf_counter() - t0) * 1e3 / steps, 3), "steps": steps, "warmup": warmup}
+    res = {"mode": mode, "ms_per_step": round((time.perf_counter() - t0) * 1e3 / steps, 3), "steps": steps, "warmup": warmup, "B": B, "L": L}
+    if mode == "sgd-graph-ema":
+        fl = optim._flat[0]
+        p, g, buf, e, e_n = (fl[k].clone() for k in ("p", "g", "buf", "ema", "ema_n"))
+        n = p.numel()
+        old_ms, new_ms = cold_ms([lambda: ops.update_sgd(p, g, buf, 0.1, 0.9, 1.0),
+                                  lambda: ops.update_sgd(p, g, buf, 0.1, 0.9, 1.0, ema=(e, e_n, ema, False))], dev)
+        res.update(ema_decay=ema, ema_updates=float(fl["ema_n"].item()), update_params=n, nef_update_cold_ms=round(old_ms, 4),
+                   nef_update_ema_cold_ms=round(new_ms, 4), nef_update_cold_GBps=round(5 * 4 * n / (old_ms * 1e-3) / 1e9, 1),
+                   nef_update_ema_cold_GBps=round(7 * 4 * n / (new_ms * 1e-3) / 1e9, 1))
     if mode == "adam-graph":
         fl = optim._flat[0]
         p, g, m, v, s = (fl[k].clone() for k in ("p", "g", "m", "v", "step"))
@@ -186,6 +206,71 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
     print("RESULT " + json.dumps(res), flush=True)
 
 
+def run_child(cmd, tree, mode):
+    """One measurement in a fresh process; its RESULT line.  A failure ends the whole run: nothing more is started."""
+    r = subprocess.run(cmd, cwd=tree, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    line = [x for x in r.stdout.splitlines() if x.startswith("RESULT ")]
+    if r.returncode != 0 or not line:
+        sys.stderr.write(r.stdout[-3000:])
+        raise SystemExit(f"{mode}: exit status {r.returncode}; nothing more is started")
+    return json.loads(line[0][len("RESULT "):])
+
+
+def ema_rounds(args):
+    """--ema D: `--reps` alternating rounds of fresh children per shape (see the module docstring); prints and writes one JSON line."""
+    modes = dict(EMA_MODES, **({"parent": 900} if args.parent_tree else {}))
+    results = {(shape, mode): [] for shape in EMA_SHAPES for mode in modes}
+    for rnd in range(args.reps):
+        order = list(modes) if rnd % 2 == 0 else list(reversed(modes))
+        for shape, (B, L) in EMA_SHAPES.items():
+            for mode in order:
+                if mode == "parent":
+                    # the parent's tool has no --shape: its `child` function is called directly, in a fresh process of its own tree
+                    tree = os.path.abspath(args.parent_tree)
+                    code = ("import importlib.util as u; s = u.spec_from_file_location('parent_bench', %r); m = u.module_from_spec(s); "
+                            "s.loader.exec_module(m); m.child('sgd-graph', %d, %d, B=%d, L=%d)"
+                            % (os.path.join(tree, "tools", "bench_adam.py"), args.steps, args.warmup, B, L))
+                    cmd = ["timeout", "-k", "10", str(modes[mode]), sys.executable, "-c", code]
+                else:
+                    tree = ROOT
+                    cmd = ["timeout", "-k", "10", str(modes[mode]), sys.executable, os.path.join(ROOT, "tools", "bench_adam.py"), "--child", mode,
+                           "--steps", str(args.steps), "--warmup", str(args.warmup), "--shape", str(B), str(L)]
+                    if mode == "sgd-graph-ema":
+                        cmd += ["--ema", str(args.ema)]
+                results[(shape, mode)].append(run_child(cmd, tree, mode))
+                sys.stderr.write(f"round {rnd + 1}/{args.reps} {shape} {mode}: {results[(shape, mode)][-1]['ms_per_step']} ms/step\n")
+                sys.stderr.flush()
+
+    def spread(shape, mode, key):
+        v = sorted(x[key] for x in results[(shape, mode)])
+        return [v[0], v[len(v) // 2], v[-1]]
+
+    e2 = results[("config2", "sgd-graph-ema")][0]
+    out = {"metric": "ms per train step, graphed FusedSGD with and without the EMA of the weights in the update launch "
+                     "([min, median, max] over rounds)", "rounds": args.reps, "ema_decay": args.ema,
+           "shapes": {k: "B=%d, 3 leads, L=%d, one GPU, dropout on" % v for k, v in EMA_SHAPES.items()}}
+    for shape in EMA_SHAPES:
+        out[shape + "_ema_off_ms"] = spread(shape, "sgd-graph", "ms_per_step")
+        out[shape + "_ema_on_ms"] = spread(shape, "sgd-graph-ema", "ms_per_step")
+        if args.parent_tree:
+            out[shape + "_parent_ms"] = par = spread(shape, "parent", "ms_per_step")
+            # the two conditions: the EMA-off median inside the parent's own min-max spread; the EMA-on median <= parent median + 0.3 ms
+            out[shape + "_ema_off_median_inside_parent_spread"] = par[0] <= out[shape + "_ema_off_ms"][1] <= par[2]
+            out[shape + "_ema_on_median_minus_parent_median_ms"] = round(out[shape + "_ema_on_ms"][1] - par[1], 3)
+    out.update(update_params=e2["update_params"], nef_update_cold_ms=spread("config2", "sgd-graph-ema", "nef_update_cold_ms"),
+               nef_update_ema_cold_ms=spread("config2", "sgd-graph-ema", "nef_update_ema_cold_ms"),
+               nef_update_cold_GBps=spread("config2", "sgd-graph-ema", "nef_update_cold_GBps"),
+               nef_update_ema_cold_GBps=spread("config2", "sgd-graph-ema", "nef_update_ema_cold_GBps"),
+               update_note="the update launch alone on the flat buffers (rule 0, no table), nef_update_ema alternating with nef_update in one "
+                           "process; cold = a 512 MiB buffer written before each launch; 5 and 7 fp32 streams per parameter",
+               steps=args.steps, warmup=args.warmup)
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
@@ -195,21 +280,30 @@ def main():
     ap.add_argument("--clip", type=float, default=None, metavar="MAX_NORM", help="measure gradient-norm clipping (see above)")
     ap.add_argument("--weight-decay", type=float, default=None, metavar="X", help="measure weight decay in the update launch (see above)")
     ap.add_argument("--no-decay", nargs="*", default=[], metavar="PATTERN", help="with --weight-decay: fnmatch patterns of exempt tensors")
+    ap.add_argument("--ema", type=float, default=None, metavar="D", help="measure the EMA of the weights in the update launch (see above)")
+    ap.add_argument("--shape", type=int, nargs=2, default=(256, 5000), metavar=("B", "L"), help="with --child: batch size and length")
     ap.add_argument("--parent-tree", default=None,
-                    help="with --clip / --weight-decay: a built checkout whose own sgd-graph child runs in every round")
-    ap.add_argument("--child", choices=sorted({**MODES, **CLIP_MODES, **WD_MODES}), default=None)
+                    help="with --clip / --weight-decay / --ema: a built checkout whose own sgd-graph child runs in every round")
+    ap.add_argument("--child", choices=sorted({**MODES, **CLIP_MODES, **WD_MODES, **EMA_MODES}), default=None)
     args = ap.parse_args()
+    if args.child == "sgd-graph-ema" and not (args.ema is not None and 0.0 < args.ema < 1.0):
+        ap.error("--child sgd-graph-ema needs --ema D in (0, 1)")
+    if args.ema is not None and (args.clip is not None or args.weight_decay is not None):
+        ap.error("--ema is a measurement of its own")
     if args.child == "sgd-graph-clip" and not (args.clip is not None and args.clip > 0):
         ap.error("--child sgd-graph-clip needs --clip MAX_NORM > 0")
     if args.child in ("sgd-graph-wd", "adamw-graph") and args.weight_decay is None:
         ap.error(f"--child {args.child} needs --weight-decay X")
     if args.clip is not None and args.weight_decay is not None:
         ap.error("--clip and --weight-decay are two measurements")
-    if args.parent_tree and args.clip is None and args.weight_decay is None:
-        ap.error("--parent-tree goes with --clip or --weight-decay")
+    if args.parent_tree and args.clip is None and args.weight_decay is None and args.ema is None:
+        ap.error("--parent-tree goes with --clip, --weight-decay or --ema")
     if args.child:
         return child(args.child, args.steps if args.child != "adam-eager" else max(3, args.steps // 2), args.warmup,
-                     clip=args.clip or 0.0, wd=args.weight_decay or 0.0, no_decay=tuple(args.no_decay))
+                     B=args.shape[0], L=args.shape[1], clip=args.clip or 0.0, wd=args.weight_decay or 0.0,
+                     no_decay=tuple(args.no_decay), ema=args.ema or 0.0)
+    if args.ema is not None:
+        return ema_rounds(args)
     modes = dict(MODES)
     if args.clip is not None:
         modes = dict(CLIP_MODES, **({"parent": 900} if args.parent_tree else {}))
