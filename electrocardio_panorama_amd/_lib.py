@@ -86,12 +86,8 @@ SIGNATURES = {
     "nef_stem_fwd": (i32, [p, p, p, i32, i32, i32, p]),
     "nef_stem_bwd_ws_bytes": (sz, [i32]),
     "nef_stem_bwd_weight": (i32, [p, p, p, p, p, sz, i32, i32, i32, p]),
-    "nef_pack_weight": (i32, [p, p, i32, i32, i32, i32, i32, p]),
-    "nef_pack_weight_wino": (i32, [p, p, i32, i32, i32, i32, i32, p]),
-    "nef_pack_weight_wino4": (i32, [p, p, i32, i32, i32, i32, i32, p]),
     "nef_pack_weights": (i32, [C.POINTER(PackDesc), i32, p]),
-    "nef_pack_weight_h2": (i32, [p, p, i32, i32, i32, i32, i32, p]),
-    "nef_pack_weight_h2_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "nef_pack_bytes": (sz, [C.POINTER(PackDesc)]),
     "nef_conv_fwd": (i32, [C.POINTER(ConvArgs), p]),
     "nef_conv_args_bytes": (sz, []),
     "nef_conv_bwd_weight_ws_bytes": (sz, [C.POINTER(BwwArgs)]),

@@ -30,7 +30,7 @@
 // on s = kk + j only: a stage reads K + 3 fragment pairs from LDS instead of 4 K (K = 7: 10 instead of 28).
 // B (activations): raw fp32 rows fetched through buffer descriptors a stage (16 channels) ahead, split in registers, stored to
 // LDS as fp16 [plane][position][16 channels] with the positions de-interleaved by t mod 4 (fragment reads = 1 KB contiguous,
-// conflict-free), double-buffered: one barrier per stage.  A (weights): never in LDS -- nef_pack_weight_h2 lays the fragments
+// conflict-free), double-buffered: one barrier per stage.  A (weights): never in LDS -- pack_h2_kernel lays the fragments
 // out in lane order, so a wave's four fragments of a (tap, 16-channel chunk) are one contiguous 4 KB read from L2, fetched a
 // tap ahead.
 #include <hip/hip_runtime.h>
@@ -901,7 +901,7 @@ int launch_h2(const nef_conv_args& a, hipStream_t st) {
 
 }  // namespace
 
-// ---- entry points of this file (hidden: reached through nef_conv_fwd / nef_pack_weights / nef_pack_weight_h2)
+// ---- entry points of this file (hidden: reached through nef_conv_fwd / nef_pack_weights / nef_pack_bytes)
 // short rows (PACK): several samples per tile; plain launches only (no prologue, channel scale, statistics or BatchNorm-backward sums)
 static bool h2_pack_shape(const nef_conv_args* a) {
     if (!(a->T >= 8 && a->T <= 64 && a->T % 4 == 0 && (a->K == 1 || a->K == 3))) return false;
@@ -946,6 +946,16 @@ __attribute__((visibility("hidden"))) int nef_h2_launch(const nef_conv_args* a, 
     }
 }
 
+// shape rules of a split-fp16 pack descriptor (the pointers are not looked at)
+__attribute__((visibility("hidden"))) int nef_h2_pack_status(const nef_pack_desc* dp) {
+    const nef_pack_desc& d = *dp;
+    const int co_n = d.transpose_flip ? d.Cig : d.Cog, ci_n = d.transpose_flip ? d.Cog : d.Cig;
+    if (d.G <= 0 || co_n % 32 != 0 || ci_n % 16 != 0 || (d.K != 1 && d.K != 3 && d.K != 7)) return NEF_E_SHAPE;
+    if (d.src_mode != 0 && !(d.src_mode == 1 && d.K == 3 && d.Cog % 2 == 0 && d.src_Cr >= 0 &&
+                             (d.src_Cr == 0 || (d.src_Cr % 64 == 0 && d.Cog == 2 * d.src_Cr)))) return NEF_E_SHAPE;
+    return NEF_OK;
+}
+
 __attribute__((visibility("hidden"))) int nef_h2_pack(const nef_pack_desc* descs, int n, hipStream_t st) {
     for (int i0 = 0; i0 < n; i0 += H2_PACK_MAX) {
         H2PackTable tab;
@@ -954,10 +964,8 @@ __attribute__((visibility("hidden"))) int nef_h2_pack(const nef_pack_desc* descs
         for (int i = 0; i < m; ++i) {
             const nef_pack_desc& d = descs[i0 + i];
             if (!d.w || !d.wp) return NEF_E_NULL;
-            const int co_n = d.transpose_flip ? d.Cig : d.Cog, ci_n = d.transpose_flip ? d.Cog : d.Cig;
-            if (d.G <= 0 || co_n % 32 != 0 || ci_n % 16 != 0 || (d.K != 1 && d.K != 3 && d.K != 7)) return NEF_E_SHAPE;
-            if (d.src_mode != 0 && !(d.src_mode == 1 && d.K == 3 && d.Cog % 2 == 0 && d.src_Cr >= 0 &&
-                                     (d.src_Cr == 0 || (d.src_Cr % 64 == 0 && d.Cog == 2 * d.src_Cr)))) return NEF_E_SHAPE;
+            if (int e = nef_h2_pack_status(&d)) return e;
+            const int co_n = d.transpose_flip ? d.Cig : d.Cog;
             tab.d[i] = H2PackDesc{d.w, reinterpret_cast<_Float16*>(d.wp), d.G, d.Cog, d.Cig, d.K, d.transpose_flip, d.src_mode, d.src_Cr};
             if (d.G * co_n > rows_max) rows_max = d.G * co_n;
         }

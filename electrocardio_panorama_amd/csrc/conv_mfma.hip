@@ -366,7 +366,7 @@ static int launch_conv_fwd(const nef_conv_args& a, hipStream_t st) {
 // ------------------------------------------------------------------------------------------------
 // For output pair j of a row (outputs 2j, 2j+1; inputs d_m = x[2j-1+m], m = 0..3, zero padded) and taps g0..g2:
 //     v0 = d0-d2   v1 = d1+d2   v2 = d2-d1   v3 = d1-d3              (input transform)
-//     u0 = g0   u1 = (g0+g1+g2)/2   u2 = (g0-g1+g2)/2   u3 = g2      (weight transform, nef_pack_weight_wino)
+//     u0 = g0   u1 = (g0+g1+g2)/2   u2 = (g0-g1+g2)/2   u3 = g2      (weight transform, pack_wino_elem)
 //     M_i[co][j] = sum_ci u_i[ci][co] * v_i[ci][j]                   (4 GEMMs over ci on the matrix cores)
 //     y[2j] = M0+M1+M2   y[2j+1] = M1-M2-M3                          (output transform, in the epilogue)
 // The activation tile is staged RAW exactly as in conv_fwd_kernel (so in_scale and both input prologues work
@@ -493,7 +493,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(nef_conv_args a, int 
     constexpr int NSET = AHEAD + 1;
     static_assert(SPK % NSET == 0, "the A sets must line up across stages");
     const int nsteps = Cig / 2;
-    // A operand: nef_pack_weight_wino lays the 2*NPL values a lane needs per k-step (plane i, co tile tm) out as NQ 16-byte
+    // A operand: pack_wino_elem lays the 2*NPL values a lane needs per k-step (plane i, co tile tm) out as NQ 16-byte
     // vectors, [g][q][ci][64-wide co block][lo][4] with value 2*i + tm = 4*q + e: one buffer_load_dwordx4 per four MFMAs
     // (5 instead of 20 vector-memory instructions per K = 7 k-step; 512 contiguous bytes per half-wave).  q is the
     // OUTER index on purpose: the NQ loads of a k-step then go to addresses >= 64 KB apart, i.e. to different L2
@@ -892,7 +892,7 @@ __global__ __launch_bounds__(256, w4_wgs_per_cu(K, WMC, PRO)) void conv_wino4_ke
     constexpr int NSET = AHEAD + 1;
     static_assert(SPK % NSET == 0, "the A sets must line up across stages");
     const int nsteps = Cig / 2;
-    // A operand: nef_pack_weight_wino4 lays the NPL values a lane needs per k-step out as NQ4 slabs [ci][32-wide co
+    // A operand: pack_wino4_elem lays the NPL values a lane needs per k-step out as NQ4 slabs [ci][32-wide co
     // block][lo][4] of full 16-byte vectors (plane 4*q + e) followed by one tail slab [ci][block][lo][REM]: K = 3: one
     // 16-byte + one 8-byte load instead of 6 dwords, K = 7: four 16-byte loads + one dword instead of 17 (slabs outermost:
     // see conv_wino_kernel)
@@ -1334,13 +1334,6 @@ __device__ __forceinline__ void pack_wino4_elem(const float* __restrict__ w, flo
 #undef NEF_PUT4
 }
 
-__global__ void pack_weight_wino4_kernel(const float* __restrict__ w, float* __restrict__ wp, int G, int Cog, int Cig,
-                                         int K, int flip) {
-    const int64_t n = (int64_t)G * Cog * Cig;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        pack_wino4_elem(w, wp, G, Cog, Cig, K, flip, i);
-}
-
 // Operand of conv_wino_kernel.  K = 3: [g][plane][r][c].  K = 7: [g][q][r][64-wide block of c][lo][4], inside a block
 // c = 32*tm + lo and value 2*plane + tm = 4*q + e.  (r, c) = (ci, co) forward, (co, ci) with the taps reversed for the
 // backward-data operand.
@@ -1390,13 +1383,6 @@ __device__ __forceinline__ void pack_wino_elem(const float* __restrict__ w, floa
     }
 #undef NEF_TAP
 #undef NEF_PUT
-}
-
-__global__ void pack_weight_wino_kernel(const float* __restrict__ w, float* __restrict__ wp, int G, int Cog, int Cig,
-                                        int K, int flip) {
-    const int64_t n = (int64_t)G * Cog * Cig;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        pack_wino_elem(w, wp, G, Cog, Cig, K, flip, i);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2137,15 +2123,8 @@ __device__ __forceinline__ void pack_plain_elem(const float* __restrict__ w, flo
     wp[i] = w[(((int64_t)g * Cog + co) * Cig + ci) * K + ks];
 }
 
-__global__ void pack_weight_kernel(const float* __restrict__ w, float* __restrict__ wp, int G, int Cog, int Cig, int K,
-                                   int flip) {
-    const int64_t n = (int64_t)G * Cog * Cig * K;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        pack_plain_elem(w, wp, G, Cog, Cig, K, flip, i);
-}
-
-// Every operand of a forward (or backward) pass in ONE launch: blockIdx.y selects the descriptor, which travels by value
-// in the kernel arguments (no device-side table to keep in sync).
+// Every operand of a call in ONE launch: blockIdx.y selects the descriptor, which travels by value in the kernel arguments
+// (no device-side table to keep in sync).
 constexpr int PACK_MULTI_MAX = 48;
 struct PackTable { nef_pack_desc d[PACK_MULTI_MAX]; };
 
@@ -2215,6 +2194,7 @@ constexpr int CHAN_SUM_SPLIT = 16;
 __attribute__((visibility("hidden"))) bool nef_h2_ok(const nef_conv_args* a);
 __attribute__((visibility("hidden"))) int nef_h2_launch(const nef_conv_args* a, hipStream_t st);
 __attribute__((visibility("hidden"))) int nef_h2_pack(const nef_pack_desc* descs, int n, hipStream_t st);
+__attribute__((visibility("hidden"))) int nef_h2_pack_status(const nef_pack_desc* d);
 
 __attribute__((visibility("hidden"))) int nef_mfma_wino4_fwd(const nef_conv_args* a, hipStream_t st);
 __attribute__((visibility("hidden"))) int nef_mfma_wino_fwd(const nef_conv_args* a, hipStream_t st);
@@ -2222,54 +2202,22 @@ __attribute__((visibility("hidden"))) int nef_mfma_wino_fwd(const nef_conv_args*
 #if NEF_PART(1)
 extern "C" {
 
-int nef_abi_version(void) { return 21; }
+int nef_abi_version(void) { return 22; }
 
-int nef_pack_weight(const float* w, float* wp, int G, int Cog, int Cig, int K, int transpose_flip,
-                    nef_stream_t stream) {
-    NEF_ENTER();
-    NEF_REQUIRE(w && wp, NEF_E_NULL);
-    NEF_REQUIRE(G > 0 && Cog > 0 && Cig > 0 && K > 0, NEF_E_SHAPE);
-    const int64_t n = (int64_t)G * Cog * Cig * K;
-    hipLaunchKernelGGL(pack_weight_kernel, dim3(nef_stream_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, w, wp, G,
-                       Cog, Cig, K, transpose_flip);
-    return nef_launch_status();
+// Shape and form of one descriptor; the pointers are not looked at
+static int pack_desc_status(const nef_pack_desc& d) {
+    NEF_REQUIRE(d.G > 0 && d.Cog > 0 && d.Cig > 0 && d.K > 0 && d.wino >= 0 && d.wino <= 3 &&
+                    (!d.wino || d.K == 3 || d.K == 7 || (d.wino == 3 && d.K == 1)), NEF_E_SHAPE);
+    NEF_REQUIRE(d.src_mode == 0 || d.wino == 3, NEF_E_UNSUPPORTED);      // synthesized sources: split-fp16 operands only
+    return NEF_OK;
 }
 
-int nef_pack_weight_wino(const float* w, float* wp, int G, int Cog, int Cig, int K, int transpose_flip,
-                         nef_stream_t stream) {
-    NEF_ENTER();
-    NEF_REQUIRE(w && wp, NEF_E_NULL);
-    NEF_REQUIRE(G > 0 && Cog > 0 && Cig > 0 && (K == 3 || K == 7), NEF_E_SHAPE);
-    const int64_t n = (int64_t)G * Cog * Cig;
-    hipLaunchKernelGGL(pack_weight_wino_kernel, dim3(nef_stream_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, w, wp,
-                       G, Cog, Cig, K, transpose_flip);
-    return nef_launch_status();
-}
-
-int nef_pack_weight_wino4(const float* w, float* wp, int G, int Cog, int Cig, int K, int transpose_flip,
-                          nef_stream_t stream) {
-    NEF_ENTER();
-    NEF_REQUIRE(w && wp, NEF_E_NULL);
-    NEF_REQUIRE(G > 0 && Cog > 0 && Cig > 0 && (K == 3 || K == 7), NEF_E_SHAPE);
-    const int64_t n = (int64_t)G * Cog * Cig;
-    hipLaunchKernelGGL(pack_weight_wino4_kernel, dim3(nef_stream_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, w, wp,
-                       G, Cog, Cig, K, transpose_flip);
-    return nef_launch_status();
-}
-
-int nef_pack_weight_h2(const float* w, void* wp, int G, int Cog, int Cig, int K, int transpose_flip, nef_stream_t stream) {
-    NEF_ENTER();
-    nef_pack_desc d;
-    d.w = w;
-    d.wp = (float*)wp;
-    d.G = G, d.Cog = Cog, d.Cig = Cig, d.K = K, d.transpose_flip = transpose_flip, d.wino = 3;
-    d.src_mode = 0, d.src_Cr = 0;
-    return nef_h2_pack(&d, 1, (hipStream_t)stream);
-}
-
-size_t nef_pack_weight_h2_bytes(int G, int Cog, int Cig, int K, int transpose_flip) {
-    if (G <= 0 || Cog <= 0 || Cig <= 0 || K <= 0) return 0;
-    return ((size_t)G * K * Cog * Cig + (size_t)G * (transpose_flip ? Cig : Cog)) * sizeof(float);
+size_t nef_pack_bytes(const nef_pack_desc* d) {
+    if (!d || pack_desc_status(*d) || (d->wino == 3 && nef_h2_pack_status(d))) return 0;
+    static const int planes[3][2] = {{0, 0}, {4, 10}, {6, 13}};      // F(2,.) / F(4,.) planes for K = 3 / K = 7
+    const size_t e = (size_t)d->G * d->Cog * d->Cig;
+    if (d->wino == 3) return (e * d->K + (size_t)d->G * (d->transpose_flip ? d->Cig : d->Cog)) * sizeof(float);
+    return e * (d->wino ? planes[d->wino][d->K == 7] : d->K) * sizeof(float);
 }
 
 int nef_pack_weights(const nef_pack_desc* descs, int n, nef_stream_t stream) {
@@ -2277,19 +2225,19 @@ int nef_pack_weights(const nef_pack_desc* descs, int n, nef_stream_t stream) {
     NEF_REQUIRE(descs || n == 0, NEF_E_NULL);
     NEF_REQUIRE(n >= 0, NEF_E_SHAPE);
     nef_pack_desc h2[PACK_MULTI_MAX];      // split-fp16 operands (wino == 3) are packed by conv_h2.hip
-    int n_h2 = 0;
+    int n_h2 = 0, n_f32 = 0;
     for (int i = 0; i < n; ++i) {
         const nef_pack_desc& d = descs[i];
         NEF_REQUIRE(d.w && d.wp, NEF_E_NULL);
-        NEF_REQUIRE(d.G > 0 && d.Cog > 0 && d.Cig > 0 && d.K > 0 && d.wino >= 0 && d.wino <= 3 &&
-                        (!d.wino || d.K == 3 || d.K == 7 || (d.wino == 3 && d.K == 1)), NEF_E_SHAPE);
-        NEF_REQUIRE(d.src_mode == 0 || d.wino == 3, NEF_E_UNSUPPORTED);      // synthesized sources: split-fp16 operands only
+        if (int e = pack_desc_status(d)) return e;
         if (d.wino == 3) {
             if (n_h2 == PACK_MULTI_MAX) {
                 if (int e = nef_h2_pack(h2, n_h2, (hipStream_t)stream)) return e;
                 n_h2 = 0;
             }
             h2[n_h2++] = d;
+        } else {
+            ++n_f32;
         }
     }
     if (n_h2) {
@@ -2308,8 +2256,11 @@ int nef_pack_weights(const nef_pack_desc* descs, int n, nef_stream_t stream) {
             const int64_t e = (int64_t)t.d[i].G * t.d[i].Cog * t.d[i].Cig * (t.d[i].wino ? 1 : t.d[i].K);
             if (e > biggest) biggest = e;
         }
+        // a pass's operands: at most 64 blocks each, one descriptor per blockIdx.y.  A single operand packed on demand: the
+        // grid of a streaming kernel.  (Every element is written by whichever thread the stride loop gives it: same bits.)
         int gx = (int)nef_cdiv(biggest, 256);
-        if (gx > 64) gx = 64;
+        if (n_f32 == 1) gx = nef_stream_grid(biggest, 256);
+        else if (gx > 64) gx = 64;
         hipLaunchKernelGGL(pack_weights_multi_kernel, dim3((unsigned)gx, (unsigned)m), dim3(256), 0, (hipStream_t)stream, t);
     }
     return nef_launch_status();
@@ -2332,7 +2283,7 @@ int nef_conv_fwd(const nef_conv_args* a, nef_stream_t stream) {
     NEF_REQUIRE(!a->bnb_slots || a->bnb_Bp > 0, NEF_E_SHAPE);
     NEF_REQUIRE(!a->bnb_slots || !a->bnb_up || a->T % 4 == 0, NEF_E_SHAPE);
     NEF_REQUIRE((!a->res_scale && !a->gate_rowscale && a->stats_mode == 0) || a->wino == 3, NEF_E_UNSUPPORTED);
-    if (a->wino == 3) {      // operand packed by nef_pack_weight_h2: direct conv on exact fp16 splits (conv_h2.hip)
+    if (a->wino == 3) {      // split-fp16 operand (nef_pack_desc.wino 3): direct conv on exact fp16 splits (conv_h2.hip)
         NEF_REQUIRE(nef_h2_ok(a), NEF_E_SHAPE);
         return nef_h2_launch(a, st);
     }

@@ -95,9 +95,9 @@ def _block_pack_requests(P, prefix, G, T, flip):
     """The operands block_fwd / block_bwd will ask ops.pack_weight for, for ops.pack_many (one launch per pass)."""
     w1 = P[prefix + ".conv1.weight"]
     f4 = bool(flip) and _bwd_f4(w1.shape[2])
-    reqs = [(P[prefix + ".conv1.weight"], G, flip, T, f4), (P[prefix + ".conv2.weight"], G, flip, T, f4)]
+    reqs = [ops.PackReq(w1, G, flip, T, f4=f4), ops.PackReq(P[prefix + ".conv2.weight"], G, flip, T, f4=f4)]
     if w1.shape[2] == 3 and w1.shape[0] // G != w1.shape[1]:          # block_fwd's res_conv condition
-        reqs.append((P[prefix + ".residual_conv.weight"], G, flip, T))
+        reqs.append(ops.PackReq(P[prefix + ".residual_conv.weight"], G, flip, T))
     return reqs
 
 
@@ -118,8 +118,9 @@ def _decoder_pack_requests(P, T_lat, flip):
     behind the second upsampling packs its own (phase) weights when it runs in polyphase form."""
     w3 = P["decoder.3.double_conv.0.weight"]
     poly = (ops.poly_bwd_ok if flip else ops.poly_fwd_ok)(1, w3.shape[0], w3.shape[1], 4 * T_lat)
-    return ([(P["decoder.1.double_conv.3.weight"], 1, flip, 2 * T_lat, True)] +
-            ([] if poly else [(w3, 1, flip, 4 * T_lat, True)]) + [(P["decoder.3.double_conv.3.weight"], 1, flip, 4 * T_lat, True)])
+    return ([ops.PackReq(P["decoder.1.double_conv.3.weight"], 1, flip, 2 * T_lat, f4=True)] +
+            ([] if poly else [ops.PackReq(w3, 1, flip, 4 * T_lat, f4=True)]) +
+            [ops.PackReq(P["decoder.3.double_conv.3.weight"], 1, flip, 4 * T_lat, f4=True)])
 
 
 def _step_pack_requests(P, V, T):
@@ -137,17 +138,17 @@ def _step_pack_requests(P, V, T):
     co0, co3 = w0.shape[0], w3.shape[0]
     # first decoder conv (shared halves: 2 groups) and the conv behind the second upsampling: polyphase operands where the shape allows
     if ops.poly_fwd_ok(2, co0, w0.shape[1] // 2, 2 * T):
-        reqs.append((wg, 2, False, T, False, ("poly", co0), False, site0))
+        reqs.append(ops.PackReq(wg, 2, False, T, src=("poly", co0), plain=False, site=site0))
     else:
-        reqs.append((wg, 2, False, 2 * T, True, None, True, site0))
+        reqs.append(ops.PackReq(wg, 2, False, 2 * T, f4=True, site=site0))
     if ops.poly_bwd_ok(2, co0, w0.shape[1] // 2, 2 * T):
-        reqs.append((wg, 2, True, T, False, ("poly", 0), True, site0))
+        reqs.append(ops.PackReq(wg, 2, True, T, src=("poly", 0), site=site0))
     else:
-        reqs.append((wg, 2, True, 2 * T, True, None, True, site0))
+        reqs.append(ops.PackReq(wg, 2, True, 2 * T, f4=True, site=site0))
     if ops.poly_fwd_ok(1, co3, w3.shape[1], 4 * T):
-        reqs.append((w3, 1, False, 2 * T, False, ("poly", co3), False, None))
+        reqs.append(ops.PackReq(w3, 1, False, 2 * T, src=("poly", co3), plain=False))
     if ops.poly_bwd_ok(1, co3, w3.shape[1], 4 * T):
-        reqs.append((w3, 1, True, 2 * T, False, ("poly", 0), True, None))
+        reqs.append(ops.PackReq(w3, 1, True, 2 * T, src=("poly", 0)))
     return reqs
 
 

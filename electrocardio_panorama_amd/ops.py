@@ -8,6 +8,7 @@ import ctypes as C
 import contextlib
 import itertools
 import os
+from typing import NamedTuple, Optional
 
 import torch
 from . import _env
@@ -218,7 +219,6 @@ WINO_FWD = 1 if _WV in ("1", "2") else 2
 # two launches (transposed F(4,4) + F(3,4)).
 WINO_BW4 = _WV not in ("1", "2")
 WINO_BW7 = _WV not in ("1", "2")
-_WINO_PLANES = {(1, 3): 4, (1, 7): 10, (2, 3): 6, (2, 7): 13}
 
 
 # Split-fp16 direct convolution (csrc/conv_h2.hip, conv args wino = 3): both fp32 operands split into two fp16 terms each (22-23 bits kept),
@@ -571,12 +571,17 @@ def amax_move(old_ptr, new_ptr):
             st["index"][(site[0], (new_ptr, site[1][1])) + site[2:]] = st["index"].pop(site)
 
 
+def _pack_desc(wino, K, G, Cog, Cig, flip, src=None):
+    """The nef_pack_desc of one operand, pointers left NULL."""
+    d = _lib.PackDesc(G=G, Cog=Cog, Cig=Cig, K=K, transpose_flip=int(flip), wino=int(wino))
+    if src is not None:
+        d.src_mode, d.src_Cr = 1, int(src[1])
+    return d
+
+
 def _packed_floats(wino, K, G, Cog, Cig, flip):
-    """fp32 words of a packed operand: plain K per (co, ci); Winograd: planes per (co, ci); split-fp16: two halves per weight
-    = K words, + one descale word per output row of the launch."""
-    if wino == 3:
-        return G * Cog * Cig * K + G * (Cig if flip else Cog)
-    return G * Cog * Cig * (_WINO_PLANES[(wino, K)] if wino else K)
+    """fp32 words of a packed operand (nef_pack_bytes: include/nefnet_hip.h has the formulas)."""
+    return _lib.load().nef_pack_bytes(C.byref(_pack_desc(wino, K, G, Cog, Cig, flip))) // 4
 
 
 def wino_ok(K, Cin_g, Cout_g, T_out, pro=0):
@@ -609,52 +614,69 @@ def _pack_shape(w, G, flip, T, f4=False, plain=True, src=None):
     return Cog, Cig, K, wino
 
 
-def _req(r):
-    """(w, G, flip, T[, f4[, src[, plain[, site]]]]) -> the full tuple."""
-    w, G, flip, T, *rest = r
-    rest = list(rest) + [False, None, True, None][len(rest):]
-    return (w, G, bool(flip), T, bool(rest[0]), rest[1], bool(rest[2]), rest[3])
+class PackReq(NamedTuple):
+    """One operand for pack_many(): the arguments of the pack_weight(w, G, flip=, T=, f4=, src=, plain=, site=) call that will ask for it."""
+    w: torch.Tensor
+    G: int
+    flip: bool
+    T: Optional[int]
+    f4: bool = False
+    src: Optional[tuple] = None
+    plain: bool = True
+    site: object = None
+
+
+def _pack(reqs, who, align=1):
+    """`reqs`: [(w, G, Cog, Cig, K, flip, wino, src, site)], forms resolved -> their packed operands, written by ONE
+    nef_pack_weights call.  The operands are slices of one allocation, each starting at a multiple of `align` words; a Winograd or
+    split-fp16 operand carries its form (`nef_wino`) and the identity of its call site for the split-fp16 input-magnitude slots
+    (`nef_site`; `site` stands in for w's address when `w` is a temporary)."""
+    L = _lib.load()
+    descs = (_lib.PackDesc * len(reqs))()
+    offs, off = [], 0
+    for i, (w, G, Cog, Cig, K, flip, wino, src, site) in enumerate(reqs):
+        if src is not None and wino != 3:
+            raise _lib.NefLibraryError(who + ": a synthesized (polyphase) operand outside the split-fp16 kernel")
+        descs[i] = _pack_desc(wino, K, G, Cog, Cig, flip, src)
+        offs.append((off, L.nef_pack_bytes(C.byref(descs[i])) // 4))
+        off += (offs[-1][1] + align - 1) // align * align
+    arena = torch.empty(off, device=reqs[0][0].device, dtype=torch.float32)
+    out = []
+    for d, (o, n), (w, G, Cog, Cig, K, flip, wino, src, site) in zip(descs, offs, reqs):
+        wp = arena[o:o + n]
+        if wino:
+            wp.nef_wino = wino
+            wp.nef_site = (w.data_ptr() if site is None else site, flip)
+        d.w, d.wp = w.data_ptr(), wp.data_ptr()
+        out.append(wp)
+    _lib.check(L.nef_pack_weights(descs, len(reqs), _stream()), "nef_pack_weights")
+    return out
 
 
 def pack_many(requests):
     """All operands of a pass -- or, from engine.forward(save=True), of a whole train step: forward AND backward-data operands,
-    the polyphase ones included -- in ONE launch.  `requests`: iterable of (w, G, flip, T[, f4[, src[, plain[, site]]]]) exactly as
+    the polyphase ones included -- in ONE launch.  `requests`: iterable of PackReq (or its fields as a plain tuple), exactly as
     the later pack_weight(w, G, flip=flip, T=T, f4=f4, src=src, plain=plain, site=site) calls will ask for them; those calls then
     return the pre-packed operand instead of launching.  Anything not pre-packed still packs on demand, so a missing or surplus
     request costs time, never correctness.  A call whose requests are ALL still waiting in the table (a pass-level call inside a
     step whose step-level call has already packed everything) does nothing; any other call resets the table first."""
-    L = _lib.load()
     reqs, keys = [], []
     for r in requests:
-        w, G, flip, T, f4, src, plain, site = _req(r)
-        _chk(w)
-        Cog, Cig, K, wino = _pack_shape(w, G, flip, T, f4, plain, src)
-        key = (w.data_ptr(), G, flip, wino, src)
+        r = PackReq(*r)
+        w, flip = _chk(r.w), bool(r.flip)
+        Cog, Cig, K, wino = _pack_shape(w, r.G, flip, r.T, bool(r.f4), bool(r.plain), r.src)
+        key = (w.data_ptr(), r.G, flip, wino, r.src)
         if key not in keys:
             keys.append(key)
-            reqs.append((key, w, G, Cog, Cig, K, flip, wino, src, site))
-    if keys and all(_PREPACKED.get(k) is not None and _PREPACKED[k][1] is r_[1] and _PREPACKED[k][2] == r_[1]._version
+            reqs.append((w, r.G, Cog, Cig, K, flip, wino, r.src, r.site))
+    if keys and all(_PREPACKED.get(k) is not None and _PREPACKED[k][1] is r_[0] and _PREPACKED[k][2] == r_[0]._version
                     for k, r_ in zip(keys, reqs)):
         return
     _PREPACKED.clear()
     if not reqs:
         return
-    sizes = [(_packed_floats(wino, K, G, Cog, Cig, flip) + 3) // 4 * 4 for _, _, G, Cog, Cig, K, flip, wino, _, _ in reqs]      # 16-byte aligned operands
-    arena = torch.empty(sum(sizes), device=reqs[0][1].device, dtype=torch.float32)
-    descs = (_lib.PackDesc * len(reqs))()
-    off = 0
-    for d, n, (key, w, G, Cog, Cig, K, flip, wino, src, site) in zip(descs, sizes, reqs):
-        if src is not None and wino != 3:
-            raise _lib.NefLibraryError("pack_many: a synthesized (polyphase) operand outside the split-fp16 kernel")
-        wp = arena[off:off + n]
-        off += n
-        if wino:
-            wp.nef_wino = wino
-            wp.nef_site = (w.data_ptr() if site is None else site, flip)
-        d.w, d.wp, d.G, d.Cog, d.Cig, d.K, d.transpose_flip, d.wino = w.data_ptr(), wp.data_ptr(), G, Cog, Cig, K, int(flip), int(wino)
-        d.src_mode, d.src_Cr = (1, int(src[1])) if src is not None else (0, 0)
-        _PREPACKED[key] = (wp, w, w._version)          # keep the source alive while its pointer is the key
-    _lib.check(L.nef_pack_weights(descs, len(reqs), _stream()), "nef_pack_weights")
+    for key, r_, wp in zip(keys, reqs, _pack(reqs, "pack_many", align=4)):      # 16-byte aligned operands
+        _PREPACKED[key] = (wp, r_[0], r_[0]._version)          # keep the source alive while its pointer is the key
 
 
 def pack_weight(w, G, flip=False, T=None, f4=False, site=None, shared=False, plain=True, src=None):
@@ -662,38 +684,16 @@ def pack_weight(w, G, flip=False, T=None, f4=False, site=None, shared=False, pla
     `T`: output length of the conv launch this operand is for; when the Winograd F(2,3) path applies to that launch
     the operand is packed for it (marked with `.nef_wino`) and `conv()` takes that path; `f4` allows the F(4,3) form.
     `src` = ("poly", Cr): pack the phase weights of conv1d(upsample2(x), w) instead of w itself (split-fp16 operands only)."""
-    L = _lib.load()
     _chk(w)
     Cog, Cig, K, wino = _pack_shape(w, G, flip, T, f4, plain, src)
     hit = _PREPACKED.pop((w.data_ptr(), G, bool(flip), wino, src), None)
     if hit is not None and hit[1] is w and hit[2] == w._version:
         return hit[0]
-    # `site`: identity of the call site for the split-fp16 input-magnitude slots when `w` is a temporary (default: w's address)
-    if wino == 3:
-        wp = torch.empty(_packed_floats(3, K, G, Cog, Cig, flip), device=w.device, dtype=torch.float32)
-        if src is None:
-            _lib.check(L.nef_pack_weight_h2(_p(w), _p(wp), G, Cog, Cig, K, int(flip), _stream()), "nef_pack_weight_h2")
-        else:
-            d = (_lib.PackDesc * 1)()
-            d[0].w, d[0].wp, d[0].G, d[0].Cog, d[0].Cig, d[0].K, d[0].transpose_flip, d[0].wino = w.data_ptr(), wp.data_ptr(), G, Cog, Cig, K, int(flip), 3
-            d[0].src_mode, d[0].src_Cr = 1, int(src[1])
-            _lib.check(L.nef_pack_weights(d, 1, _stream()), "nef_pack_weights")
-        wp.nef_wino = 3
-        wp.nef_site = (w.data_ptr() if site is None else site, bool(flip))
-        # shared: every launch of a pass through this operand is ONE call site (a loop over chunks of one tensor family, e.g.
+    wp, = _pack([(w, G, Cog, Cig, K, bool(flip), wino, src, site)], "pack_weight")
+    if shared:
+        # every launch of a pass through this operand is ONE call site (a loop over chunks of one tensor family, e.g.
         # the panorama sweep's angle chunks) instead of one site per occurrence
-        wp.nef_shared = bool(shared)
-        return wp
-    if src is not None:
-        raise _lib.NefLibraryError("pack_weight: a synthesized (polyphase) operand outside the split-fp16 kernel")
-    if wino:
-        wp = torch.empty(G * _WINO_PLANES[(wino, K)] * Cog * Cig, device=w.device, dtype=torch.float32)
-        fn = L.nef_pack_weight_wino if wino == 1 else L.nef_pack_weight_wino4
-        _lib.check(fn(_p(w), _p(wp), G, Cog, Cig, K, int(flip), _stream()), "nef_pack_weight_wino")
-        wp.nef_wino = wino
-        return wp
-    wp = torch.empty(w.numel(), device=w.device, dtype=torch.float32)
-    _lib.check(L.nef_pack_weight(_p(w), _p(wp), G, Cog, Cig, K, int(flip), _stream()), "nef_pack_weight")
+        wp.nef_shared = True
     return wp
 
 

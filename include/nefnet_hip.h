@@ -34,7 +34,7 @@ extern "C" {
 typedef void* nef_stream_t;
 
 /* ABI version of this header; bumped on any signature change. */
-int nef_abi_version(void);   /* 21 (BatchNorm backward is ONE entry on a nef_bn_bwd_args struct, + nef_bn_bwd_args_bytes; nef_mix_bwd takes `up` / `shared` flags; nef_outconv_fwd / nef_outconv_bwd_weight take the prologue arguments.  ABI <= 20 had nef_bn_relu_bwd_phase_major, nef_bn_relu_bwd_up, nef_bn_relu_bwd_combine3, nef_bn_relu_bwd_combine3_phase_major, nef_bn_relu_bwd_outconv, nef_bn_bwd_outconv_ws_bytes, nef_mix_bwd_up, nef_mix_bwd_shared, nef_mix_bwd_shared_up, nef_outconv_fwd_pro and nef_outconv_bwd_weight_pro); 20 (the weight gradient is ONE entry, nef_conv_bwd_weight(nef_bww_args*), + nef_bww_args_bytes; its _pro, _wino4, _h2 and _h2_ws_bytes variants are gone); 19 (+ nef_adam, nef_h2_tail_census, nef_bwd_weight_clamp_ends: additions only; the kernel-form option entry points of 16 and nef_upsample2_aff_fwd are gone; + nef_debug_spin_us); 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + kernel-form option entry points); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + the split-fp16 weight gradient, now form 3); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, the transposed F(3,4) / F(4,4) entry, now form 4, covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
+int nef_abi_version(void);   /* 22 (weight packing is ONE entry, nef_pack_weights(nef_pack_desc*, n), + nef_pack_bytes(nef_pack_desc*) for the size of any operand.  ABI <= 21 had nef_pack_weight, nef_pack_weight_wino, nef_pack_weight_wino4, nef_pack_weight_h2 and nef_pack_weight_h2_bytes: each is one descriptor with wino = 0 / 1 / 2 / 3); 21 (BatchNorm backward is ONE entry on a nef_bn_bwd_args struct, + nef_bn_bwd_args_bytes; nef_mix_bwd takes `up` / `shared` flags; nef_outconv_fwd / nef_outconv_bwd_weight take the prologue arguments.  ABI <= 20 had nef_bn_relu_bwd_phase_major, nef_bn_relu_bwd_up, nef_bn_relu_bwd_combine3, nef_bn_relu_bwd_combine3_phase_major, nef_bn_relu_bwd_outconv, nef_bn_bwd_outconv_ws_bytes, nef_mix_bwd_up, nef_mix_bwd_shared, nef_mix_bwd_shared_up, nef_outconv_fwd_pro and nef_outconv_bwd_weight_pro); 20 (the weight gradient is ONE entry, nef_conv_bwd_weight(nef_bww_args*), + nef_bww_args_bytes; its _pro, _wino4, _h2 and _h2_ws_bytes variants are gone); 19 (+ nef_adam, nef_h2_tail_census, nef_bwd_weight_clamp_ends: additions only; the kernel-form option entry points of 16 and nef_upsample2_aff_fwd are gone; + nef_debug_spin_us); 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + kernel-form option entry points); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + the split-fp16 weight gradient, now form 3); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, the transposed F(3,4) / F(4,4) entry, now form 4, covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
 
 /* Diagnostics: `wgs` workgroups busy for `us` microseconds on `stream` (a stand-in for a collective's time on the chip:
  * parallel.DryCollective, bench.py --dry-collective).  0 <= us <= 50000, 1 <= wgs <= 64. */
@@ -55,42 +55,36 @@ int nef_stem_bwd_weight(const float* x, const float* w, const float* gy, float* 
  * Grouped Conv1d (stride 1, odd K in {1,3,7}, pad (K-1)/2) as an implicit GEMM on fp32 MFMA.
  * Replaces nn.Conv1d at codes/network/model_nefnet.py:18,21,32,44 and encoder/resnet_1d.py:23.
  *
- * nef_pack_weight: w [G*Cog][Cig][K] (torch layout) -> wp.
+ * nef_pack_weights packs the operands of nef_conv_fwd: any number in one call (a whole train step packs ~50), one
+ * descriptor each; `descs` is a HOST array.  w [G*Cog][Cig][K] (torch layout) -> wp, nef_pack_bytes(desc) bytes, in the
+ * form `wino` names -- the value the conv launch then passes as nef_conv_args.wino.  transpose_flip = 1 packs the
+ * backward-data operand: (ci, co) exchanged and the taps reversed.
+ *
+ * wino = 0, the direct kernels: G*Cog*Cig*K floats.
  *   transpose_flip = 0: forward operand   wp[g][k][ci][co] = w[g*Cog+co][ci][k]
  *   transpose_flip = 1: bwd-data operand  wp[g][k][co][ci] = w[g*Cog+co][ci][K-1-k]
- */
-int nef_pack_weight(const float* w, float* wp, int G, int Cog, int Cig, int K, int transpose_flip,
-                    nef_stream_t stream);
-
-/* Winograd F(2,3) operand (transpose_flip = 1: the backward-data operand, (ci, co) exchanged and the taps reversed).
+ *
+ * wino = 1, Winograd F(2,3), K == 3 or 7.
  * K == 3: wp[g][plane][ci][co], 4 planes (g0, (g0+g1+g2)/2, (g0-g1+g2)/2, g2) of the taps w[g*Cog+co][ci][0..2].
  * K == 7 (taps split 4 + 3): 10 planes = the F(2,4) transform of taps 0..3 (g0/2, -(g0+g1+g2+g3)/2, (-g0+g1-g2+g3)/6,
  * (g0+2g1+4g2+8g3)/6, g3), the F(2,3) transform of taps 4..6 with its last plane negated, one plane of padding, laid out for
  * 16-byte fragment loads: wp[g][q][ci][co / 64][co % 32][4] with value 2*plane + (co % 64) / 32 = 4*q + e (conv_mfma.hip).
- * The layout is private to nef_conv_fwd; the size is planes * G * Cog * Cig floats either way. */
-int nef_pack_weight_wino(const float* w, float* wp, int G, int Cog, int Cig, int K, int transpose_flip,
-                         nef_stream_t stream);
-
-/* The F(4,3) operand (conv args wino = 2): 6 planes for K == 3 -- (g0/4, -(g0+g1+g2)/6, -(g0-g1+g2)/6, g0/24+g1/12+g2/6,
+ * The layout is private to nef_conv_fwd; the size is planes * G * Cog * Cig floats either way.
+ *
+ * wino = 2, the F(4,3) operand, K == 3 or 7: 6 planes for K == 3 -- (g0/4, -(g0+g1+g2)/6, -(g0-g1+g2)/6, g0/24+g1/12+g2/6,
  * g0/24-g1/12+g2/6, g2) -- and 13 for K == 7: taps split 4 + 3, the F(4,4) transform of taps 0..3 (7 planes, points 0, +-1,
  * +-2, inf, 1/2) followed by the F(4,3) transform of taps 4..6.  Stored as slabs of 16-byte vectors,
  * wp[g][plane / 4][ci][co / 32][co % 32][4] plus a tail slab for the planes % 4 last planes (conv_mfma.hip); planes * G *
- * Cog * Cig floats. */
-int nef_pack_weight_wino4(const float* w, float* wp, int G, int Cog, int Cig, int K, int transpose_flip,
-                          nef_stream_t stream);
-
-/* The split-fp16 operand (conv args wino = 3): each weight, scaled by a power of two per output row of the launch (row
+ * Cog * Cig floats.
+ *
+ * wino = 3, the split-fp16 operand: each weight, scaled by a power of two per output row of the launch (row
  * maximum -> [2^14, 2^15)), is split exactly into two fp16 terms w = wh + wl (+ < 2^-22 |w|) and stored as matrix-core
- * fragments wp[g][ci/16][k][co/32][wh | wl][lane][8] (fp16), followed by the per-row descale factors [g][co] (fp32).
+ * fragments wp[g][ci/16][k][co/32][wh | wl][lane][8] (fp16), followed by the per-row descale factors [g][co] (fp32):
+ * G*K*Cog*Cig floats plus one word per output row of the launch.
  * nef_conv_fwd then runs the DIRECT convolution as three v_mfma_f32_32x32x16_f16 per 16 channels and tap -- xh*wh + xh*wl +
  * xl*wh, exact fp16 products, fp32 accumulation (csrc/conv_h2.hip): fp32-class results (1.1e-7 rel-L2 on a 128-channel K = 7
- * layer against fp64; an fp32 direct conv: 1.3e-7) at 3/16 of the fp32 matrix instructions' pipe time.  K == 3 or 7, Cig % 16 == 0,
- * Cog % 32 == 0 (both as the LAUNCH sees them: exchanged under transpose_flip).  wp: nef_pack_weight_h2_bytes(...) bytes. */
-int nef_pack_weight_h2(const float* w, void* wp, int G, int Cog, int Cig, int K, int transpose_flip, nef_stream_t stream);
-size_t nef_pack_weight_h2_bytes(int G, int Cog, int Cig, int K, int transpose_flip);
-
-/* Any number of operands in one launch (a whole forward or backward pass packs ~25): each descriptor is one
- * nef_pack_weight (wino = 0), nef_pack_weight_wino (wino = 1), nef_pack_weight_wino4 (wino = 2) or nef_pack_weight_h2 (wino = 3) call.  `descs` is a HOST array. */
+ * layer against fp64; an fp32 direct conv: 1.3e-7) at 3/16 of the fp32 matrix instructions' pipe time.  K == 1, 3 or 7, Cig % 16 == 0,
+ * Cog % 32 == 0 (both as the LAUNCH sees them: exchanged under transpose_flip). */
 typedef struct nef_pack_desc {
     const float* w;
     float* wp;
@@ -101,11 +95,13 @@ typedef struct nef_pack_desc {
      * phase tensor is never materialised); src_Cr = 0: row 2 r + p, src_Cr = Cog/2 > 0: the tile order of the polyphase forward launch. */
     int32_t src_mode, src_Cr;
 } nef_pack_desc;
+/* Bytes of the operand `d` packs (w and wp are not looked at); 0 for a descriptor nef_pack_weights rejects by shape or form. */
+size_t nef_pack_bytes(const nef_pack_desc* d);
 int nef_pack_weights(const nef_pack_desc* descs, int n, nef_stream_t stream);
 
 typedef struct nef_conv_args {
     const float* x;        /* input  [B][..][T]; element (b, g, ci, t) at x + b*x_bs + g*x_gs + ci*T + t */
-    const float* wp;       /* packed weights [G][K][Cin_g][Cout_g] (nef_pack_weight) */
+    const float* wp;       /* packed weights (nef_pack_weights; wino 0: [G][K][Cin_g][Cout_g]) */
     float* y;              /* output; element (b, g, co, t) at y + b*y_bs + g*y_gs + co*T + t */
     const float* bias;     /* [G*Cout_g] or NULL */
     const float* in_scale; /* NULL, or per (sample, input channel) factor at in_scale + b*sc_bs + g*sc_gs + ci */
@@ -137,12 +133,12 @@ typedef struct nef_conv_args {
     int32_t pro_Bp;
     const uint64_t* rng_seed_dev;  /* NULL, or a device word added to rng_seed at run time (hipGraph replay: a captured
                                       launch freezes its arguments, the per-step seed must live in device memory) */
-    int32_t wino;          /* 1: wp was packed by nef_pack_weight_wino -- K == 3 through Winograd F(2,3), K == 7 through
+    int32_t wino;          /* 1: wp was packed with nef_pack_desc.wino 1 -- K == 3 through Winograd F(2,3), K == 7 through
                               F(2,4) + F(2,3) (2/3 resp. 9/14 of the multiplies; still fp32 multiplies and adds on the matrix cores, results differ
-                              from the direct form by the rounding of the transforms).  2: packed by
-                              nef_pack_weight_wino4 -- Winograd F(4,3) resp. F(4,4) + F(4,3): 1/2 resp. 13/28 of the multiplies.  Needs T even, T >= 128
+                              from the direct form by the rounding of the transforms).  2: packed with
+                              wino 2 -- Winograd F(4,3) resp. F(4,4) + F(4,3): 1/2 resp. 13/28 of the multiplies.  Needs T even, T >= 128
                               (Cout_g % 128 == 0) or T >= 256 (Cout_g % 64 == 0), Cin_g % 16 == 0; K == 7: pro_mode 0.
-                              3: packed by nef_pack_weight_h2 -- the direct convolution on exact fp16 splits of both operands
+                              3: packed with wino 3 -- the direct convolution on exact fp16 splits of both operands
                               (K == 1, 3 or 7, Cout_g % 64 == 0, Cin_g % 16 == 0, T even and >= 128; every epilogue option
                               incl. stats / bnb_slots; K == 7: pro_mode 0).  Short rows, 8 <= T <= 64 with T % 4 == 0
                               (K == 1 or 3): several samples per tile; then no prologue, in_scale, stats or bnb_slots. */
@@ -248,7 +244,7 @@ typedef struct nef_bww_args {
                             *    partial-sum layout; the two differ only by the summation order across splits.  The kernel never reads
                             *    outside [x, x + (B-1)*x_bs + (G-1)*x_gs + Cin_g*T) resp. the same extent of gy.  (ABI <= 11 also had
                             *    nef_conv_bwd_weight_wino, the transposed F(3,2): removed, this form covers every shape it took.)
-                            * 3: exact fp16 splits of BOTH operands (csrc/conv_h2w.hip; the arithmetic of nef_pack_weight_h2 / conv
+                            * 3: exact fp16 splits of BOTH operands (csrc/conv_h2w.hip; the arithmetic of the wino = 3 pack / conv
                             *    args wino = 3, the same family: gy = gh + gl, X = xh + xl, three fp16 matrix instructions per product,
                             *    fp32 accumulation): fp32-class results (closer to fp64 than the transposed-Winograd forms) at 3/16 of
                             *    the fp32 matrix instructions' pipe time.  K == 3 (any pro_mode) or K == 7 (pro_mode 0), T even and

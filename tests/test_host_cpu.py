@@ -14,8 +14,9 @@ from util import free_port
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_header_symbols_exported_abi_21():
-    """The shared library loads and exports every function include/nefnet_hip.h declares (no compute calls)."""
+def test_header_symbols_exported_abi_22():
+    """The shared library loads and exports every function include/nefnet_hip.h declares (no compute calls); the single-operand
+    packing entries of ABI <= 21 are gone from the header, the binding table and the library."""
     from electrocardio_panorama_amd import _lib
     from electrocardio_panorama_amd.csrc import build
     build.build(verbose=False)
@@ -25,10 +26,44 @@ def test_header_symbols_exported_abi_21():
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name), name
-    assert _lib.load().nef_abi_version() == 21
+    for name in ("nef_pack_weight", "nef_pack_weight_wino", "nef_pack_weight_wino4", "nef_pack_weight_h2", "nef_pack_weight_h2_bytes"):
+        assert name not in declared and name not in _lib.SIGNATURES and not hasattr(lib, name), name
+    assert {"nef_pack_weights", "nef_pack_bytes"} <= declared
+    assert _lib.load().nef_abi_version() == 22
     assert ctypes.sizeof(_lib.ConvArgs) == 384 == _lib.load().nef_conv_args_bytes()
     assert ctypes.sizeof(_lib.BwwArgs) == 200 == _lib.load().nef_bww_args_bytes()
     assert ctypes.sizeof(_lib.BnBwdArgs) == 160 == _lib.load().nef_bn_bwd_args_bytes()
+
+
+def test_pack_entry_rejections_and_operand_sizes():
+    """nef_pack_weights refuses malformed calls before anything is launched (dummy non-null pointers), and nef_pack_bytes states the size
+    of every operand form -- the plane counts are the header's numbers."""
+    from electrocardio_panorama_amd import _lib
+    L = _lib.load()
+    G, Cog, Cig = 3, 128, 64
+
+    def desc(wino=0, K=3, flip=0, w=8, wp=8, **kw):
+        return _lib.PackDesc(w=w, wp=wp, G=G, Cog=Cog, Cig=Cig, K=K, transpose_flip=flip, wino=wino, **kw)
+
+    def pack(d, n=1):
+        return L.nef_pack_weights((_lib.PackDesc * 1)(d), n, None)
+    assert L.nef_pack_weights(None, 1, None) == -2                            # NEF_E_NULL
+    assert pack(desc(), n=-1) == -1                                           # NEF_E_SHAPE
+    assert pack(desc(w=None)) == -2
+    assert pack(desc(wino=4)) == -1
+    assert pack(desc(wino=1, K=5)) == -1
+    assert pack(desc(wino=1, src_mode=1)) == -4                               # NEF_E_UNSUPPORTED: synthesized sources are split-fp16 only
+
+    def nbytes(**kw):
+        return L.nef_pack_bytes(ctypes.byref(desc(w=None, wp=None, **kw)))    # the pointers are not looked at
+    e = G * Cog * Cig
+    assert nbytes(wino=0, K=3) == e * 3 * 4 and nbytes(wino=0, K=1) == e * 1 * 4
+    assert nbytes(wino=1, K=3) == e * 4 * 4 and nbytes(wino=1, K=7) == e * 10 * 4
+    assert nbytes(wino=2, K=3) == e * 6 * 4 and nbytes(wino=2, K=7) == e * 13 * 4
+    assert nbytes(wino=3, K=7, flip=0) == (G * 7 * Cog * Cig + G * Cog) * 4
+    assert nbytes(wino=3, K=7, flip=1) == (G * 7 * Cog * Cig + G * Cig) * 4
+    assert nbytes(wino=4) == 0 and nbytes(wino=1, K=5) == 0
+    assert L.nef_pack_bytes(None) == 0
 
 
 def test_rejects_bad_calls_without_touching_the_gpu():

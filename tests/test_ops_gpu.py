@@ -71,8 +71,9 @@ def test_pack_weight():
 
 
 def test_pack_many_equals_single_packs():
-    """One launch for a whole pass's operands (nef_pack_weights): every pre-packed operand equals the single-call pack,
-    is handed out exactly once, and anything that was not requested still packs on demand."""
+    """One launch for a whole pass's operands (nef_pack_weights): every pre-packed operand equals the one pack_weight packs on demand
+    (the same entry with one descriptor, on its own grid), is handed out exactly once, and anything that was not requested still
+    packs on demand."""
     o = ops()
     ws = [(g(rnd(3 * 128, 128, 7, seed=40)), 3, False, 1250), (g(rnd(3 * 128, 64, 3, seed=41)), 3, True, 1250),
           (g(rnd(3 * 128, 64, 1, seed=42)), 3, False, None), (g(rnd(21 * 128, 128, 3, seed=43)), 21, True, 16),
@@ -87,6 +88,44 @@ def test_pack_many_equals_single_packs():
     other = g(rnd(128, 128, 3, seed=46))
     assert torch.equal(o.pack_weight(other, 1, T=256), o.pack_weight(other, 1, T=256))
     o.pack_many([])
+
+
+# (2, 40, 24): no power of two, every dimension different (a swapped index shows), 1920 elements = more than one block.
+# (2, 136, 72): 19584 elements -- past the 64 x 256 a many-descriptor launch covers in one sweep, so the two grids differ in x too.
+@pytest.mark.parametrize("G,Cog,Cig", [(2, 40, 24), (2, 136, 72)])
+def test_pack_f23_operand_exact(G, Cog, Cig):
+    """The F(2,3) K = 3 operand [g][plane][r][c], packed through a raw one-element nef_pack_desc, against the four planes formed on
+    the CPU in fp32 in the kernel's own operation order (two additions and a multiplication by 0.5: nothing to contract, so the
+    comparison is exact) -- an anchor for the Winograd pack that does not go through a conv.  The same descriptor as the middle
+    one of three in one call (the many-descriptor grid) writes the same bytes."""
+    from electrocardio_panorama_amd import _lib
+    o = ops()
+    L = _lib.load()
+    w = rnd(G * Cog, Cig, 3, seed=47)
+    wd = g(w)
+    w1 = [g(rnd(G * Cog, Cig, 1, seed=48 + i)) for i in range(2)]
+
+    def desc(src, wino, K, flip):
+        d = _lib.PackDesc(G=G, Cog=Cog, Cig=Cig, K=K, transpose_flip=flip, wino=wino)
+        wp = torch.full((L.nef_pack_bytes(d) // 4,), float("nan"), device=DEV)
+        d.w, d.wp = src.data_ptr(), wp.data_ptr()
+        return d, wp
+
+    for flip in (0, 1):
+        taps = w.view(G, Cog, Cig, 3).flip(3) if flip else w.view(G, Cog, Cig, 3)
+        g0, g1, g2 = taps[..., 0], taps[..., 1], taps[..., 2]
+        planes = torch.stack([g0, ((g0 + g1) + g2) * 0.5, ((g0 - g1) + g2) * 0.5, g2], 1)      # [G, 4, co, ci]
+        exp = (planes if flip else planes.transpose(2, 3)).contiguous()                      # (r, c) = (co, ci) under flip
+        d, wp = desc(wd, 1, 3, flip)
+        assert wp.numel() == G * 4 * Cog * Cig
+        _lib.check(L.nef_pack_weights((_lib.PackDesc * 1)(d), 1, o._stream()), "nef_pack_weights")
+        assert torch.equal(wp.cpu().view(exp.shape), exp), flip
+        (da, wpa), (dm, wpm), (db, wpb) = desc(w1[0], 0, 1, flip), desc(wd, 1, 3, flip), desc(w1[1], 0, 1, flip)
+        _lib.check(L.nef_pack_weights((_lib.PackDesc * 3)(da, dm, db), 3, o._stream()), "nef_pack_weights")
+        assert torch.equal(wpm, wp), flip
+        for src, got in ((w1[0], wpa), (w1[1], wpb)):
+            e1 = src.view(G, Cog, Cig) if flip else src.view(G, Cog, Cig).transpose(1, 2)
+            assert torch.equal(got.view(e1.shape), e1), flip
 
 
 CONV_CASES = [  # K, G, Cig, Cog, T, B
