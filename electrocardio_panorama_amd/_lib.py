@@ -124,6 +124,8 @@ SIGNATURES = {
     "nef_mix_bwd": (i32, [p, p, p, p, p, p, p, p, i32, i32, i32, i32, i32, p, i32, i32, i32, p]),
     "nef_mix_fwd_shared": (i32, [p, p, p, p, p, i32, i32, i32, i32, i32, p, p]),
     "nef_lead_mean_mix_shared": (i32, [p, p, p, p, p, i32, i32, i32, i32, i32, p, p]),
+    "nef_lead_mean_mix_unpool": (i32, [p, p, p, p, p, p, p, i32, i32, i32, i32, i32, p, p]),
+    "nef_mix_bwd_unpool": (i32, [p, p, p, p, p, p, p, p, p, i32, i32, i32, i32, i32, p, i32, p]),
     "nef_pass_combine_fwd": (i32, [p, p, p, i32, i32, i32, p]),
     "nef_pass_combine_bwd": (i32, [p, p, i32, i32, i32, p]),
     "nef_pass_combine_stats_ws_bytes": (sz, [i32, i32]),

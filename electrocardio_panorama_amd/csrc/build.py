@@ -42,7 +42,7 @@ def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(HERE, s) for s in SOURCES] + [os.path.join(HERE, "nef_common.h"), os.path.join(ROOT, "include", "nefnet_hip.h")]
+    deps = [os.path.join(HERE, s) for s in SOURCES] + [os.path.join(HERE, "nef_common.h"), os.path.join(HERE, "roi_unpool.h"), os.path.join(ROOT, "include", "nefnet_hip.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -4,6 +4,7 @@
 // `codes/network/model_nefnet.py` unless stated.  One lane = consecutive time samples, so every global access is
 // a coalesced 256-byte wave transaction along the time axis; reductions use wavefront shuffles.
 #include "nef_common.h"
+#include "roi_unpool.h"
 
 namespace {
 
@@ -161,15 +162,17 @@ __global__ __launch_bounds__(256) void lead_mean_mix_shared_kernel(const float* 
                                                                    const float* __restrict__ q,
                                                                    float* __restrict__ latent, float* __restrict__ D2,
                                                                    int B, int V, int T, int c1, int c2,
-                                                                   const int32_t* __restrict__ choice_dev) {
+                                                                   const int32_t* __restrict__ choice_dev, int cshift) {
     typedef float vec __attribute__((ext_vector_type(W)));
     if (choice_dev) { c1 = choice_dev[0]; c2 = choice_dev[1]; }
-    const int64_t rows = (int64_t)B * 256;
+    // cshift: 8 = every channel row, 7 = only the z1 half (rows c < 128; the z2 half is left to the un-pooling kernel)
+    const int64_t nidx = (int64_t)B << cshift;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const float fv = (float)V;
     const int TW = T / W;
-    const int64_t pass = rows * TW;
-    for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += (int64_t)gridDim.x * 4) {
+    const int64_t pass = (int64_t)B * 256 * TW;
+    for (int64_t idx = (int64_t)blockIdx.x * 4 + wave; idx < nidx; idx += (int64_t)gridDim.x * 4) {
+        const int64_t row = ((idx >> cshift) << 8) | (idx & ((1 << cshift) - 1));
         const int b = (int)(row >> 8), c = (int)(row & 255);
         const vec* src = (const vec*)((c < 128 ? z1 : z2r) + ((int64_t)b * V * 128 + (c & 127)) * T);
         const int cp = c < 128 ? c1 : c2;
@@ -220,17 +223,20 @@ __global__ __launch_bounds__(256) void lead_mean_mix_shared_kernel(const float* 
 __global__ __launch_bounds__(256) void lead_mean_mix_shared_pair_kernel(const float* __restrict__ z1, const float* __restrict__ z2r,
                                                                         const float* __restrict__ q, float* __restrict__ latent,
                                                                         float* __restrict__ D2, int B, int V, int T, int c1, int c2,
-                                                                        const int32_t* __restrict__ choice_dev) {
+                                                                        const int32_t* __restrict__ choice_dev, int cshift) {
     typedef float vec __attribute__((ext_vector_type(4)));
     if (choice_dev) { c1 = choice_dev[0]; c2 = choice_dev[1]; }
     const int64_t pairs = (int64_t)B * 128;
+    const int pshift = cshift - 1;            // row pairs per sample: all 128, or the 64 of the z1 half
+    const int64_t nidx = (int64_t)B << pshift;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const float fv = (float)V;
     const int TW = T / 2;                     // vectors per row pair
     const int mid = T / 4;                    // the vector with two elements of either row
     const int64_t pass = pairs * TW;
     const int64_t lead = (int64_t)128 * T / 4;
-    for (int64_t pr = (int64_t)blockIdx.x * 4 + wave; pr < pairs; pr += (int64_t)gridDim.x * 4) {
+    for (int64_t idx = (int64_t)blockIdx.x * 4 + wave; idx < nidx; idx += (int64_t)gridDim.x * 4) {
+        const int64_t pr = ((idx >> pshift) << 7) | (idx & ((1 << pshift) - 1));
         const int64_t row = 2 * pr;
         const int b = (int)(row >> 8), c = (int)(row & 255);
         const vec* src = (const vec*)((c < 128 ? z1 : z2r) + ((int64_t)b * V * 128 + (c & 127)) * T);
@@ -310,13 +316,14 @@ __global__ void mix_bwd_kernel(const float* __restrict__ gD, const float* __rest
                                const float* __restrict__ z1, const float* __restrict__ z2r,
                                const float* __restrict__ q, float* __restrict__ gz1, float* __restrict__ gz2r,
                                float* __restrict__ gq, int B, int V, int T, int c1, int c2,
-                               const int32_t* __restrict__ choice_dev, int relu_z1) {
+                               const int32_t* __restrict__ choice_dev, int relu_z1, int cshift) {
     if (choice_dev) { c1 = choice_dev[0]; c2 = choice_dev[1]; }
-    const int64_t rows = (int64_t)B * 256;
+    const int64_t nidx = (int64_t)B << cshift;      // cshift: see lead_mean_mix_shared_kernel
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t pass = rows * T;
+    const int64_t pass = (int64_t)B * 256 * T;
     const float fv = (float)V;
-    for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += (int64_t)gridDim.x * 4) {
+    for (int64_t idx = (int64_t)blockIdx.x * 4 + wave; idx < nidx; idx += (int64_t)gridDim.x * 4) {
+        const int64_t row = ((idx >> cshift) << 8) | (idx & ((1 << cshift) - 1));
         const int b = (int)(row >> 8), c = (int)(row & 255);
         const bool first = c < 128;
         const int cc = c & 127;
@@ -410,16 +417,20 @@ __global__ __launch_bounds__(256) void mix_bwd_shared_pair_kernel(const float* _
                                                                   const float* __restrict__ z1, const float* __restrict__ z2r,
                                                                   const float* __restrict__ q, float* __restrict__ gz1,
                                                                   float* __restrict__ gz2r, float* __restrict__ gq, int B, int V, int T,
-                                                                  int c1, int c2, const int32_t* __restrict__ choice_dev, int relu_z1) {
+                                                                  int c1, int c2, const int32_t* __restrict__ choice_dev, int relu_z1,
+                                                                  int cshift) {
     typedef float vec __attribute__((ext_vector_type(4)));
     if (choice_dev) { c1 = choice_dev[0]; c2 = choice_dev[1]; }
     const int64_t pairs = (int64_t)B * 128;
+    const int pshift = cshift - 1;
+    const int64_t nidx = (int64_t)B << pshift;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const float fv = (float)V;
     const int TW = T / 2, mid = T / 4;
     const int64_t gpass = pairs * TW;
     const int64_t lead = (int64_t)128 * T / 4;
-    for (int64_t pr = (int64_t)blockIdx.x * 4 + wave; pr < pairs; pr += (int64_t)gridDim.x * 4) {
+    for (int64_t idx = (int64_t)blockIdx.x * 4 + wave; idx < nidx; idx += (int64_t)gridDim.x * 4) {
+        const int64_t pr = ((idx >> pshift) << 7) | (idx & ((1 << pshift) - 1));
         const int64_t row = 2 * pr;
         const int b = (int)(row >> 8), c = (int)(row & 255);
         const bool first = c < 128;
@@ -2197,22 +2208,38 @@ int nef_mix_fwd_shared(const float* latent, const float* z1, const float* z2r, c
     return nef_launch_status();
 }
 
+// cshift = 8: every channel row; 7: the z1 half only (z2r is then not read)
+static void lead_mean_mix_shared_launch(const float* z1, const float* z2r, const float* q, float* latent, float* D2, int B, int V, int T,
+                                        int c1, int c2, const int32_t* choice_dev, int cshift, hipStream_t st) {
+    const dim3 grid(nef_stream_grid((int64_t)B << cshift, 4));
+    const bool al16 = (((uintptr_t)z1 | (uintptr_t)z2r | (uintptr_t)latent | (uintptr_t)D2) & 15) == 0;
+    if (T % 4 == 2 && al16)
+        hipLaunchKernelGGL(lead_mean_mix_shared_pair_kernel, dim3(nef_stream_grid((int64_t)B << (cshift - 1), 4)), dim3(256), 0, st, z1, z2r,
+                           q, latent, D2, B, V, T, c1, c2, choice_dev, cshift);
+    else if (T % 2 == 0)
+        hipLaunchKernelGGL(lead_mean_mix_shared_kernel<2>, grid, dim3(256), 0, st, z1, z2r, q, latent, D2, B, V, T, c1, c2, choice_dev,
+                           cshift);
+    else
+        hipLaunchKernelGGL(lead_mean_mix_shared_kernel<1>, grid, dim3(256), 0, st, z1, z2r, q, latent, D2, B, V, T, c1, c2, choice_dev,
+                           cshift);
+}
+
 int nef_lead_mean_mix_shared(const float* z1, const float* z2r, const float* q, float* latent, float* D2, int B, int V,
                              int T, int c1, int c2, const int32_t* choice_dev, nef_stream_t stream) {
     NEF_ENTER();
     NEF_REQUIRE(z1 && z2r && q && latent && D2, NEF_E_NULL);
     NEF_REQUIRE(B > 0 && V > 0 && T > 0 && c1 >= 0 && c1 < V && c2 >= 0 && c2 < V, NEF_E_SHAPE);
-    const dim3 grid(nef_stream_grid((int64_t)B * 256, 4));
-    const bool al16 = (((uintptr_t)z1 | (uintptr_t)z2r | (uintptr_t)latent | (uintptr_t)D2) & 15) == 0;
-    if (T % 4 == 2 && al16)
-        hipLaunchKernelGGL(lead_mean_mix_shared_pair_kernel, dim3(nef_stream_grid((int64_t)B * 128, 4)), dim3(256), 0, NEF_ST, z1, z2r, q,
-                           latent, D2, B, V, T, c1, c2, choice_dev);
-    else if (T % 2 == 0)
-        hipLaunchKernelGGL(lead_mean_mix_shared_kernel<2>, grid, dim3(256), 0, NEF_ST, z1, z2r, q, latent, D2, B, V, T, c1,
-                           c2, choice_dev);
-    else
-        hipLaunchKernelGGL(lead_mean_mix_shared_kernel<1>, grid, dim3(256), 0, NEF_ST, z1, z2r, q, latent, D2, B, V, T, c1,
-                           c2, choice_dev);
+    lead_mean_mix_shared_launch(z1, z2r, q, latent, D2, B, V, T, c1, c2, choice_dev, 8, NEF_ST);
+    return nef_launch_status();
+}
+
+int nef_lead_mean_mix_unpool(const float* z1, const float* z2b, const int64_t* rois, const float* q, float* latent, float* D2,
+                             int32_t* status, int B, int V, int T, int c1, int c2, const int32_t* choice_dev, nef_stream_t stream) {
+    NEF_ENTER();
+    NEF_REQUIRE(z1 && z2b && rois && q && latent && D2, NEF_E_NULL);
+    NEF_REQUIRE(B > 0 && V > 0 && V <= NEF_UNPOOL_MIX_MAX_V && T > 0 && c1 >= 0 && c1 < V && c2 >= 0 && c2 < V, NEF_E_SHAPE);
+    lead_mean_mix_shared_launch(z1, nullptr, q, latent, D2, B, V, T, c1, c2, choice_dev, 7, NEF_ST);
+    nef_unpool_mix_fwd_z2(z2b, rois, q, latent, D2, status, B, V, T, c2, choice_dev, NEF_ST);
     return nef_launch_status();
 }
 
@@ -2225,15 +2252,35 @@ int nef_mix_bwd(const float* gD, const float* latent, const float* z1, const flo
     const bool al16 = (((uintptr_t)gD | (uintptr_t)latent | (uintptr_t)z1 | (uintptr_t)z2r | (uintptr_t)gz1 | (uintptr_t)gz2r) & 15) == 0;
 #define NEF_MIX_BWD(UP, SHARED)                                                                                                \
     hipLaunchKernelGGL((mix_bwd_kernel<UP, SHARED>), dim3(nef_stream_grid((int64_t)B * 256, 4)), dim3(256), 0, NEF_ST, gD, latent, \
-                       z1, z2r, q, gz1, gz2r, gq, B, V, T, c1, c2, choice_dev, relu_z1)
+                       z1, z2r, q, gz1, gz2r, gq, B, V, T, c1, c2, choice_dev, relu_z1, 8)
     if (shared && !up && T % 4 == 2 && T >= 8 && al16)
         hipLaunchKernelGGL(mix_bwd_shared_pair_kernel, dim3(nef_stream_grid((int64_t)B * 128, 4)), dim3(256), 0, NEF_ST, gD, latent, z1,
-                           z2r, q, gz1, gz2r, gq, B, V, T, c1, c2, choice_dev, relu_z1);
+                           z2r, q, gz1, gz2r, gq, B, V, T, c1, c2, choice_dev, relu_z1, 8);
     else if (shared && up) NEF_MIX_BWD(true, true);
     else if (shared) NEF_MIX_BWD(false, true);
     else if (up) NEF_MIX_BWD(true, false);
     else NEF_MIX_BWD(false, false);
 #undef NEF_MIX_BWD
+    return nef_launch_status();
+}
+
+int nef_mix_bwd_unpool(const float* gD, const float* latent, const float* z1, const float* z2b, const int64_t* rois, const float* q,
+                       float* gz1, float* gz2b, float* gq, int B, int V, int T, int c1, int c2, const int32_t* choice_dev, int relu_z1,
+                       nef_stream_t stream) {
+    NEF_ENTER();
+    NEF_REQUIRE(gD && latent && z1 && z2b && rois && q && gz1 && gz2b && gq, NEF_E_NULL);
+    NEF_REQUIRE(B > 0 && V > 0 && T > 1 && T <= NEF_UNPOOL_MIX_MAX_T && c1 >= 0 && c1 < V && c2 >= 0 && c2 < V, NEF_E_SHAPE);
+    // z1 half: nef_mix_bwd's shared, not-upsampled launch on the rows c < 128 (z2r / gz2r are not touched)
+    const bool al16 = (((uintptr_t)gD | (uintptr_t)latent | (uintptr_t)z1 | (uintptr_t)gz1) & 15) == 0;
+    const bool pair = T % 4 == 2 && T >= 8 && al16;
+    if (pair)
+        hipLaunchKernelGGL(mix_bwd_shared_pair_kernel, dim3(nef_stream_grid((int64_t)B * 64, 4)), dim3(256), 0, NEF_ST, gD, latent, z1,
+                           (const float*)nullptr, q, gz1, (float*)nullptr, gq, B, V, T, c1, c2, choice_dev, relu_z1, 7);
+    else
+        hipLaunchKernelGGL((mix_bwd_kernel<false, true>), dim3(nef_stream_grid((int64_t)B * 128, 4)), dim3(256), 0, NEF_ST, gD, latent, z1,
+                           (const float*)nullptr, q, gz1, (float*)nullptr, gq, B, V, T, c1, c2, choice_dev, relu_z1, 7);
+    // the z2 half deals positions to lanes as the kernel above does (pair kernel / its vector path / its scalar path): same gq bits
+    nef_unpool_mix_bwd_z2(gD, latent, z2b, rois, q, gz2b, gq, B, V, T, c2, choice_dev, pair ? 4 : ((T & 1) == 0 && T >= 8 ? 2 : 1), NEF_ST);
     return nef_launch_status();
 }
 

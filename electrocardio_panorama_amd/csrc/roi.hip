@@ -8,16 +8,11 @@
 //               (long)(float(roi) * 0.25f), bit-exact with the reference.
 // rois stay int64 on the device; no host loop, no per-segment launches.
 #include "nef_common.h"
+#include "roi_unpool.h"
 
 namespace {
 
-constexpr int NSEG = NEF_N_SEG;
-constexpr int BINS = NEF_ROI_BINS;
-constexpr int SEGW = 2 * NEF_ROI_BINS;   // 32 samples per decoded segment
-
-__device__ __forceinline__ int64_t latent_index(int64_t roi) {
-    return (int64_t)((float)roi * 0.25f);   // rois.float().mul_(0.25).long()  (:82-85)
-}
+using namespace nef_unpool;      // NSEG / BINS / SEGW, latent_index, SegTable, load_segments, lerp_src, unpool_lerp, the gather transpose
 
 // grid x for (segment j, bin s): torch.linspace(r0, r1, 16) on fp32, r = roi*0.25*(2/T) - 1   (:50-58)
 __device__ __forceinline__ float grid_x(const int64_t* __restrict__ roi_b, int j, int s, int T) {
@@ -100,41 +95,6 @@ __global__ void roi_align_bwd_kernel(const float* __restrict__ gout, const int64
     }
 }
 
-struct SegTable { int start[NSEG]; int len[NSEG]; int off[NSEG]; float scale[NSEG]; };
-
-__device__ __forceinline__ bool load_segments(const int64_t* __restrict__ roi_b, int T, SegTable& st) {
-    int run = 0;
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < NSEG; ++j) {
-        const int64_t a = latent_index(roi_b[2 * j]);
-        const int64_t e = latent_index(roi_b[2 * j + 1]);
-        int64_t len = e - a;
-        if (len < 0) { ok = false; len = 0; }
-        if (run + len > T) { ok = false; len = T - run; }
-        st.start[j] = (int)a;
-        st.len[j] = (int)len;
-        st.off[j] = run;
-        st.scale[j] = len > 0 ? (float)SEGW / (float)(int)len : 0.f;      // F.interpolate's input/output ratio
-        run += (int)len;
-    }
-    if (run != T) ok = false;
-    return ok;
-}
-
-// F.interpolate(mode='linear', align_corners=False) source index for output i of a len-long segment
-__device__ __forceinline__ void lerp_src(int i, float scale, int& i0, int& i1, float& l0, float& l1) {
-    float src = scale * ((float)i + 0.5f) - 0.5f;
-    if (src < 0.f) src = 0.f;
-    i0 = (int)src;
-    if (i0 > SEGW - 1) i0 = SEGW - 1;
-    i1 = i0 + (i0 < SEGW - 1 ? 1 : 0);
-    l1 = src - (float)i0;
-    if (l1 < 0.f) l1 = 0.f;
-    if (l1 > 1.f) l1 = 1.f;
-    l0 = 1.f - l1;
-}
-
 // one wave per (b, c) row of the output; zseg [B][C][7][32] -> out [B][C][T].
 // The pass is VALU-bound, not HBM-bound (PMC: 1.7e8 vector instructions for 1.2e8 outputs in the first version, which
 // searched the segment of every output with a 7-way select chain): the wave therefore walks the row SEGMENT BY SEGMENT --
@@ -178,7 +138,7 @@ __global__ void roi_unpool_fwd_kernel(const float* __restrict__ zseg, const int6
                 float l0, l1;
                 lerp_src(i, sc, i0, i1, l0, l1);
                 const float v0 = __shfl(reg, base + i0), v1 = __shfl(reg, base + i1);
-                if (i < len) orow[off + i] = l0 * v0 + l1 * v1;
+                if (i < len) orow[off + i] = unpool_lerp(l0, v0, l1, v1);
             }
             covered = off + len;
         }
@@ -186,39 +146,7 @@ __global__ void roi_unpool_fwd_kernel(const float* __restrict__ zseg, const int6
     }
 }
 
-// first output i in [0, len] of a segment whose source index i0(i) reaches s (i0 is non-decreasing in i): the closed form
-// of lerp_src's `scale*(i+0.5)-0.5 >= s`, then corrected by evaluating lerp_src itself around the guess, so that the
-// transpose partitions the outputs exactly as the forward assigned them whatever the rounding of the closed form.
-// lerp_src's left tap alone (its clamp to 31 does not matter against s <= 31)
-__device__ __forceinline__ int unpool_left_tap(int i, float scale) {
-    float src = scale * ((float)i + 0.5f) - 0.5f;
-    if (src < 0.f) src = 0.f;
-    return (int)src;
-}
-
-__device__ __forceinline__ int unpool_first_reaching(int s, int len, float scale, float inv_scale) {
-    if (s <= 0) return 0;
-    int i = (int)ceilf(((float)s + 0.5f) * inv_scale - 0.5f);
-    if (i < 0) i = 0;
-    if (i > len) i = len;
-    // the closed form and the forward's rounded expression can disagree by one position when the boundary falls within
-    // rounding of an integer: one verified step either way ...
-    if (i > 0 && unpool_left_tap(i - 1, scale) >= s) --i;
-    else if (i < len && unpool_left_tap(i, scale) < s) ++i;
-    // ... and, should that ever not be enough, the plain search (never taken in practice; keeps the partition exact)
-    if ((i > 0 && unpool_left_tap(i - 1, scale) >= s) || (i < len && unpool_left_tap(i, scale) < s)) {
-#pragma nounroll
-        while (i > 0 && unpool_left_tap(i - 1, scale) >= s) --i;
-#pragma nounroll
-        while (i < len && unpool_left_tap(i, scale) < s) ++i;
-    }
-    return i;
-}
-
-// gather form of the transpose: lane s of segment j collects the outputs that read sample s:
-//   gz[j][s] = sum_{i: i0(i)=s} l0(i) g[i] + sum_{i: i1(i)=s} l1(i) g[i],  {i0 = s} = [first(s), first(s+1)),
-//   {i1 = s} = {i0 = s-1} (plus {i0 = 31} for s = 31, where i1 is clamped) -- two short contiguous ranges instead of a
-//   widened candidate window with a test per candidate (VALU-bound before: 985 vector instructions per element).
+// the transpose of the above, in its gather form (unpool_gather_row).
 // STAGED = true: the wave first streams its gradient row into a private LDS strip (coalesced, all loads in flight at
 // once), then gathers from LDS -- the strided global gathers of the direct form are latency-bound (PMC: 60 % of wave
 // cycles parked).  STAGED = false reads the row in place and serves rows too long for the strip (T > 4096).
@@ -261,41 +189,219 @@ __global__ __launch_bounds__(256) void roi_unpool_bwd_kernel(const float* __rest
             gr = strip;
         }
         float* gz = gzseg + row * NSEG * SEGW;
+        float acc[(NSEG + 1) / 2] = {0.f, 0.f, 0.f, 0.f};
+        unpool_gather_row(gr, st, lane, acc);
 #pragma unroll
-        for (int jj = 0; jj < NSEG + 1; jj += 2) {
-            const int j = jj + half;
-            if (j >= NSEG) continue;
-            const int len = half ? st.len[jj + 1 < NSEG ? jj + 1 : jj] : st.len[jj];
-            const int off = half ? st.off[jj + 1 < NSEG ? jj + 1 : jj] : st.off[jj];
-            const float sc = half ? st.scale[jj + 1 < NSEG ? jj + 1 : jj] : st.scale[jj];
-            float acc = 0.f;
-            if (len > 0) {
-                const int b0 = unpool_first_reaching(s, len, sc, (float)len * (1.f / SEGW));
-                const int nb = __shfl_down(b0, 1), pb = __shfl_up(b0, 1);   // neighbours lie in the same 32-lane half
-                const int b1 = s + 1 < SEGW ? nb : len;
-                const int a0 = s > 0 ? pb : b0;
-                // outputs in [a0, b0) read s as their RIGHT tap: weight l1 = src - (s - 1), in [0, 1) without a clamp because
-                // their left tap is s - 1; outputs in [b0, b1) read it as their LEFT tap: weight l0 = 1 - (src - s) -- and at
-                // s = 31 the right tap is clamped onto the left one, the two weights add up to 1.  src is lerp_src's
-                // expression term for term ((float)i + 0.5f is exact, so the running fi below is too).
-                const float* gp = gr + off;
-                float fi = (float)a0 + 0.5f;
-                const float sm1 = (float)(s - 1);
-                for (int i = a0; i < b0; ++i, fi += 1.f) {
-                    float src = sc * fi - 0.5f;
-                    src = src < 0.f ? 0.f : src;
-                    acc += (src - sm1) * gp[i];
+        for (int k = 0; k < (NSEG + 1) / 2; ++k)
+            if (2 * k + half < NSEG) gz[(2 * k + half) * SEGW + s] = acc[k];
+        if constexpr (STAGED) __builtin_amdgcn_wave_barrier();     // the strip is rewritten by the next row
+    }
+}
+
+// The segment an output position t falls into (the forward's partition of [0, T): segment j owns [off_j, off_j + len_j), empty
+// segments own nothing): i = position inside it, sc = its scale, jb = index of its first sample in a lead's 7 x 32 samples.
+// Returns false for positions the segments do not reach.  The table is wave-uniform, a lane pays six compares.
+__device__ __forceinline__ bool segment_of(const SegTable& st, int t, int& i, float& sc, int& jb) {
+    int off = st.off[0];
+    sc = st.scale[0];
+    jb = 0;
+#pragma unroll
+    for (int j = 1; j < NSEG; ++j)
+        if (t >= st.off[j]) { off = st.off[j]; sc = st.scale[j]; jb = j * SEGW; }
+    i = t - off;
+    return t < st.off[NSEG - 1] + st.len[NSEG - 1];
+}
+
+// z2 half of nef_lead_mean_mix_unpool = roi_unpool_fwd_kernel + the rows c >= 128 of lead_mean_mix_shared_kernel without the
+// un-pooled tensor between them.  One wave per (b, c): the V leads' 7 x 32 segment samples sit in a per-wave LDS strip
+// (V * 896 bytes), the wave streams over the output row, W positions per lane; lerp_src runs once per position (the segment table
+// belongs to the sample, not to the lead) and every lead's value is unpool_lerp of its own two taps -- the expressions and the
+// order of roi_unpool_fwd_kernel and lead_mean_mix_shared_kernel (s = v0; s += v_v; m = s / fv), so latent and D2 come out bit
+// for bit; positions the segments do not reach carry the zeros the two kernels would have passed on.
+template <int W>
+__global__ __launch_bounds__(256) void unpool_mix_fwd_z2_kernel(const float* __restrict__ z2b, const int64_t* __restrict__ rois,
+                                                                const float* __restrict__ q, float* __restrict__ latent,
+                                                                float* __restrict__ D2, int32_t* __restrict__ status, int B, int V,
+                                                                int T, int c2, const int32_t* __restrict__ choice_dev) {
+    typedef float vec __attribute__((ext_vector_type(W)));
+    extern __shared__ float strip_lds[];
+    constexpr int ROW = NSEG * SEGW;
+    if (choice_dev) c2 = choice_dev[1];
+    const int64_t rows = (int64_t)B * 128;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int64_t per_wave = (rows + (int64_t)gridDim.x * 4 - 1) / ((int64_t)gridDim.x * 4);     // see roi_unpool_fwd_kernel
+    const int64_t row_lo = ((int64_t)blockIdx.x * 4 + wave) * per_wave;
+    const int64_t row_hi = row_lo + per_wave < rows ? row_lo + per_wave : rows;
+    float* strip = strip_lds + wave * V * ROW;
+    const int n = V * ROW;
+    const float fv = (float)V;
+    const int64_t pass = (int64_t)B * 256 * T;
+    int b_cur = -1;
+    SegTable st;
+    for (int64_t row = row_lo; row < row_hi; ++row) {
+        const int b = (int)(row >> 7), c = (int)(row & 127);
+        if (b != b_cur) {
+            b_cur = b;
+            const bool ok = load_segments(rois + (int64_t)b * NSEG * 2, T, st);
+            if (!ok && status && lane == 0) status[0] = 1;
+        }
+        // lead v's samples of this (b, c): z2b row (b*V + v)*128 + c; NU loads per lane in flight per trip
+        const float* zr = z2b + ((int64_t)b * V * 128 + c) * ROW;
+        constexpr int NU = 8;
+        for (int e0 = 0; e0 < n; e0 += 64 * NU) {
+            float r[NU];
+#pragma unroll
+            for (int u = 0; u < NU; ++u) {
+                const int e = e0 + u * 64 + lane, v = e / ROW;
+                r[u] = e < n ? zr[(int64_t)v * 128 * ROW + (e - v * ROW)] : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < NU; ++u)
+                if (e0 + u * 64 + lane < n) strip[e0 + u * 64 + lane] = r[u];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const int64_t orow = ((int64_t)b * 256 + 128 + c) * T;
+        const float f = q[b * 256 + 128 + c];
+        for (int p = lane; p < T / W; p += 64) {
+            vec m, dm, dp;
+#pragma unroll
+            for (int w = 0; w < W; ++w) {
+                int i, jb;
+                float sc;
+                const bool in = segment_of(st, W * p + w, i, sc, jb);
+                int i0 = 0, i1 = 0;
+                float l0 = 0.f, l1 = 0.f;
+                if (in) lerp_src(i, sc, i0, i1, l0, l1);
+                float sum = 0.f, pk = 0.f;
+                for (int v = 0; v < V; ++v) {
+                    const float val = in ? unpool_lerp(l0, strip[v * ROW + jb + i0], l1, strip[v * ROW + jb + i1]) : 0.f;
+                    sum = v == 0 ? val : sum + val;
+                    if (v == 0 || v == c2) pk = val;
                 }
-                const float c0 = s == SEGW - 1 ? 1.f : (float)(s + 1), k = s == SEGW - 1 ? 0.f : 1.f;
-                for (int i = b0; i < b1; ++i, fi += 1.f) {
-                    float src = sc * fi - 0.5f;
-                    src = src < 0.f ? 0.f : src;
-                    acc += (c0 - k * src) * gp[i];
+                const float mean = sum / fv;
+                m[w] = mean;
+                dm[w] = f * mean;
+                dp[w] = f * pk;
+            }
+            *(vec*)(latent + orow + W * p) = m;
+            *(vec*)(D2 + orow + W * p) = dm;
+            *(vec*)(D2 + pass + orow + W * p) = dp;
+        }
+        __builtin_amdgcn_wave_barrier();     // the strip is rewritten by the next row
+    }
+}
+
+// z2 half of nef_mix_bwd_unpool = the rows c >= 128 of mix_bwd_kernel<false, true> + roi_unpool_bwd_kernel<true> without the
+// gradient gz2r between them.  One wave per (b, c).  Per wave in LDS: two T-long strips and the picked lead's 7 x 32 samples.
+//   1. stream the rows ga, gb of gD and the latent row (coalesced, NU of each in flight); per position form mix_bwd's two DISTINCT
+//      output rows in the strips: everyone's f*ga/fv + 0 and the picked lead's f*ga/fv + f*gb (mix_bwd writes the first to V - 1
+//      leads), and the row's gq term ga*lat + gb*pk, pk = the picked lead's un-pooled value rebuilt by the forward's functions;
+//   2. unpool_gather_row once per strip; the picked lead's segment row takes the second result, every other lead's the first.
+// G: how step 1 deals the row's positions to the lanes -- exactly as the nef_mix_bwd kernel that would have taken this row does, so
+// that gq adds the same terms in the same order and comes out bit for bit as well: G = 4 mix_bwd_shared_pair_kernel (the row is half
+// of an aligned span of four-float groups, an odd channel's row starts T floats into it, lane = group % 64), G = 2
+// mix_bwd_kernel<false, true>'s vector path (position pairs), G = 1 its scalar path.  A lane adds its groups in ascending order.
+template <int G>
+__global__ __launch_bounds__(256) void unpool_mix_bwd_z2_kernel(const float* __restrict__ gD, const float* __restrict__ latent,
+                                                                const float* __restrict__ z2b, const int64_t* __restrict__ rois,
+                                                                const float* __restrict__ q, float* __restrict__ gz2b,
+                                                                float* __restrict__ gq, int B, int V, int T, int c2,
+                                                                const int32_t* __restrict__ choice_dev) {
+    extern __shared__ float strip_lds[];
+    constexpr int ROW = NSEG * SEGW;
+    if (choice_dev) c2 = choice_dev[1];
+    const int64_t rows = (int64_t)B * 128;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int s = lane & (SEGW - 1), half = lane >> 5;
+    const int64_t per_wave = (rows + (int64_t)gridDim.x * 4 - 1) / ((int64_t)gridDim.x * 4);
+    const int64_t row_lo = ((int64_t)blockIdx.x * 4 + wave) * per_wave;
+    const int64_t row_hi = row_lo + per_wave < rows ? row_lo + per_wave : rows;
+    float* sa = strip_lds + wave * (2 * T + ROW);
+    float* sb = sa + T;
+    float* pick = sb + T;
+    const float fv = (float)V;
+    const int64_t pass = (int64_t)B * 256 * T;
+    int b_cur = -1;
+    SegTable st;
+    for (int64_t row = row_lo; row < row_hi; ++row) {
+        const int b = (int)(row >> 7), c = (int)(row & 127);
+        if (b != b_cur) {
+            b_cur = b;
+            load_segments(rois + (int64_t)b * NSEG * 2, T, st);
+        }
+        const float* zr = z2b + (((int64_t)b * V + c2) * 128 + c) * ROW;
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (u * 64 + lane < ROW) pick[u * 64 + lane] = zr[u * 64 + lane];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const int64_t grow = ((int64_t)b * 256 + 128 + c) * T;
+        const float f = q[b * 256 + 128 + c];
+        float acc = 0.f;
+        constexpr int NU = G == 4 ? 6 : (G == 2 ? 10 : 20);      // a T = 1250 row is one trip
+        const int shift = G == 4 ? (c & 1) * T : 0;              // where the row starts in its span of groups
+        const int kb = shift / G, ke = (shift + T + G - 1) / G;   // the groups that hold positions of this row
+        for (int k0 = (kb & ~63) + lane; k0 < ke; k0 += 64 * NU) {
+            float ga[NU][G], gb[NU][G], la[NU][G];
+#pragma unroll
+            for (int u = 0; u < NU; ++u) {
+                const int k = k0 + 64 * u;
+                if constexpr (G == 1) {
+                    const bool in = k >= kb && k < ke;
+                    ga[u][0] = in ? gD[grow + k] : 0.f;
+                    gb[u][0] = in ? gD[pass + grow + k] : 0.f;
+                    la[u][0] = in ? latent[grow + k] : 0.f;
+                } else {
+#pragma unroll
+                    for (int e = 0; e < G; e += 2) {      // (T is even: a pair of positions is inside the row or outside it)
+                        const int t = G * k + e - shift;
+                        const bool in = k >= kb && k < ke && t >= 0 && t < T;
+                        const nef_f32x2 z = {0.f, 0.f};
+                        const nef_f32x2 a2 = in ? *(const nef_f32x2*)(gD + grow + t) : z;
+                        const nef_f32x2 b2 = in ? *(const nef_f32x2*)(gD + pass + grow + t) : z;
+                        const nef_f32x2 l2 = in ? *(const nef_f32x2*)(latent + grow + t) : z;
+                        ga[u][e] = a2[0], ga[u][e + 1] = a2[1];
+                        gb[u][e] = b2[0], gb[u][e + 1] = b2[1];
+                        la[u][e] = l2[0], la[u][e + 1] = l2[1];
+                    }
                 }
             }
-            gz[j * SEGW + s] = acc;
+#pragma unroll
+            for (int u = 0; u < NU; ++u) {
+                const int k = k0 + 64 * u;
+#pragma unroll
+                for (int e = 0; e < G; ++e) {
+                    const int t = G * k + e - shift;
+                    if (k >= kb && k < ke && t >= 0 && t < T) {
+                        int i, jb, i0, i1;
+                        float sc, l0, l1, pk = 0.f;
+                        if (segment_of(st, t, i, sc, jb)) {
+                            lerp_src(i, sc, i0, i1, l0, l1);
+                            pk = unpool_lerp(l0, pick[jb + i0], l1, pick[jb + i1]);
+                        }
+                        acc += ga[u][e] * la[u][e] + gb[u][e] * pk;
+                        const float gm = f * ga[u][e] / fv;
+                        sa[t] = gm + 0.f;
+                        sb[t] = gm + f * gb[u][e];
+                    }
+                }
+            }
         }
-        if constexpr (STAGED) __builtin_amdgcn_wave_barrier();     // the strip is rewritten by the next row
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        float ra[(NSEG + 1) / 2] = {0.f, 0.f, 0.f, 0.f}, rb[(NSEG + 1) / 2] = {0.f, 0.f, 0.f, 0.f};
+        unpool_gather_row(sa, st, lane, ra);
+        unpool_gather_row(sb, st, lane, rb);
+        for (int v = 0; v < V; ++v) {
+            float* gz = gz2b + (((int64_t)b * V + v) * 128 + c) * ROW;
+#pragma unroll
+            for (int k = 0; k < (NSEG + 1) / 2; ++k)
+                if (2 * k + half < NSEG) gz[(2 * k + half) * SEGW + s] = v == c2 ? rb[k] : ra[k];
+        }
+        acc = nef_wave_sum(acc);
+        if (lane == 0) gq[b * 256 + 128 + c] = acc;
+        __builtin_amdgcn_wave_barrier();     // the strips are rewritten by the next row
     }
 }
 
@@ -310,6 +416,33 @@ __global__ void roi_segment_table_kernel(const int64_t* __restrict__ rois, int64
 }
 
 }  // namespace
+
+// the callers (elementwise.hip) have validated the arguments: 1 <= V <= NEF_UNPOOL_MIX_MAX_V, 2 <= T <= NEF_UNPOOL_MIX_MAX_T (backward)
+void nef_unpool_mix_fwd_z2(const float* z2b, const int64_t* rois, const float* q, float* latent, float* D2, int32_t* status, int B,
+                           int V, int T, int c2, const int32_t* choice_dev, hipStream_t st) {
+    const dim3 grid(nef_stream_grid((int64_t)B * 128, 4));
+    const size_t lds = (size_t)4 * V * NSEG * SEGW * sizeof(float);
+    const bool al8 = (((uintptr_t)latent | (uintptr_t)D2) & 7) == 0;
+    if (T % 2 == 0 && al8)
+        hipLaunchKernelGGL(unpool_mix_fwd_z2_kernel<2>, grid, dim3(256), lds, st, z2b, rois, q, latent, D2, status, B, V, T, c2,
+                           choice_dev);
+    else
+        hipLaunchKernelGGL(unpool_mix_fwd_z2_kernel<1>, grid, dim3(256), lds, st, z2b, rois, q, latent, D2, status, B, V, T, c2,
+                           choice_dev);
+}
+
+void nef_unpool_mix_bwd_z2(const float* gD, const float* latent, const float* z2b, const int64_t* rois, const float* q, float* gz2b,
+                           float* gq, int B, int V, int T, int c2, const int32_t* choice_dev, int group, hipStream_t st) {
+    static_assert((size_t)4 * (2 * NEF_UNPOOL_MIX_MAX_T + NSEG * SEGW) * sizeof(float) <= 65536, "four waves' strips fit the default LDS limit");
+    const size_t lds = (size_t)4 * (2 * T + NSEG * SEGW) * sizeof(float);
+    const dim3 grid(nef_stream_grid((int64_t)B * 128, 4));
+    if (group == 4)
+        hipLaunchKernelGGL(unpool_mix_bwd_z2_kernel<4>, grid, dim3(256), lds, st, gD, latent, z2b, rois, q, gz2b, gq, B, V, T, c2, choice_dev);
+    else if (group == 2)
+        hipLaunchKernelGGL(unpool_mix_bwd_z2_kernel<2>, grid, dim3(256), lds, st, gD, latent, z2b, rois, q, gz2b, gq, B, V, T, c2, choice_dev);
+    else
+        hipLaunchKernelGGL(unpool_mix_bwd_z2_kernel<1>, grid, dim3(256), lds, st, gD, latent, z2b, rois, q, gz2b, gq, B, V, T, c2, choice_dev);
+}
 
 #define NEF_ST ((hipStream_t)stream)
 

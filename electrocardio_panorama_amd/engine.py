@@ -485,12 +485,24 @@ def _latents(P, x, in_theta, rois, drop, save, pack_side=None):
     return z1, z2b, (sv if save else None)
 
 
-def _head_fwd(P, Bf, z1, z2r, q_theta, V, rest_theta, phase, training, lead_choice, sv, rest_chunk, half_sweep):
-    """model_nefnet.py:146-190: lead means, Standin mixes, query scaling, the three decoder passes (+ the sweep)."""
+def _head_shared(T):
+    """(_fusable) the first decoder conv sees each distinct channel half once."""
+    return 2 * T >= 128
+
+
+def _head_fwd(P, Bf, z1, z2r, q_theta, V, rest_theta, phase, training, lead_choice, sv, rest_chunk, half_sweep, unpool=None):
+    """model_nefnet.py:146-190: lead means, Standin mixes, query scaling, the three decoder passes (+ the sweep).
+    `unpool` = (z2b, rois, status) instead of z2r (None): the shared path un-pools the segments while it mixes."""
     B = z1.shape[0]
     save = sv is not None
     q = ops.theta_mlp_fwd(q_theta, P["mlp2.weight"], P["mlp2.bias"])             # [B, 256]
-    if 2 * z1.shape[2] >= 128:         # (_fusable) the first decoder conv sees each distinct channel half once
+    z2b = None
+    if unpool is not None:
+        assert _head_shared(z1.shape[2])
+        z2b, rois, status = unpool
+        latent, D2 = ops.lead_mean_mix_unpool(z1, z2b, rois, q, V, lead_choice, z1.shape[2], status)
+        out3, dsv = decoder_fwd(D2, P, Bf, 3, training, save, shared_B=B)
+    elif _head_shared(z1.shape[2]):
         latent, D2 = ops.lead_mean_mix_shared(z1, z2r, q, V, lead_choice)         # [B, 256, T], [2B, 256, T]
         out3, dsv = decoder_fwd(D2, P, Bf, 3, training, save, shared_B=B)
     else:
@@ -499,7 +511,7 @@ def _head_fwd(P, Bf, z1, z2r, q_theta, V, rest_theta, phase, training, lead_choi
         out3, dsv = decoder_fwd(D, P, Bf, 3, training, save)
     outs = (out3[0:B], out3[B:2 * B], out3[2 * B:3 * B])
     if save:
-        sv.update(z1=z1, z2r=z2r, latent=latent, q=q, q_theta=q_theta, choice=lead_choice, dec=dsv, hB=B, hV=V)
+        sv.update(z1=z1, z2r=z2r, z2b=z2b, latent=latent, q=q, q_theta=q_theta, choice=lead_choice, dec=dsv, hB=B, hV=V)
     if phase == "train":
         return outs, sv
     if phase in ("val", "test"):
@@ -526,6 +538,10 @@ def forward(P, Bf, x, in_theta, q_theta, rois, rest_theta=None, phase="train", t
     z1, z2b, sv = _latents(P, x, in_theta, rois, drop, save, pack_side)
     if phase == "gen":
         return (z1, z2b), None
+    if _head_shared(T) and V <= ops.UNPOOL_MIX_MAX_V:
+        # z2r [B, 128V, T] is never written: the mix reads the segments (and the backward hands their gradient straight back)
+        return _head_fwd(P, Bf, z1, None, q_theta, V, rest_theta, phase, training, lead_choice, sv, rest_chunk, half_sweep,
+                         unpool=(z2b, rois, status))
     z2r = ops.roi_unpool_fwd(z2b, rois, T, status)
     return _head_fwd(P, Bf, z1, z2r, q_theta, V, rest_theta, phase, training, lead_choice, sv, rest_chunk, half_sweep)
 
@@ -673,7 +689,8 @@ def gen_ecg(P, Bf, z1, z2b, query_thetas, rois, chunk=8, half=False):
 
 
 def _head_bwd(P, sv, g_outs, grads, side, relu_z1=False):
-    """Back through decoder passes, Standin mixes and mlp2: returns the gradients wrt the lead-blocked z1 and z2r."""
+    """Back through decoder passes, Standin mixes and mlp2: returns the gradients wrt the lead-blocked z1 and z2r -- or, where the
+    forward mixed straight from the segment tensor z2b, wrt z1 and z2b: (gz1, gz2r, None) or (gz1, None, gz2b)."""
     B, V = sv["hB"], sv["hV"]
     like = sv["dec"][2]        # stacked decoder output [3B, 1, L]
     g_out = ops.stacked3(g_outs) if all(g is not None for g in g_outs) else None      # ops.loss_bwd's three views of one buffer: no copy
@@ -682,25 +699,35 @@ def _head_bwd(P, sv, g_outs, grads, side, relu_z1=False):
         g_out = torch.cat([p_.contiguous() for p_ in parts], dim=0)
     gD, up, shared = decoder_bwd(sv["dec"], g_out, P, grads, side)
     # relu_z1: z1 is the ReLU output of z1_conv's block, whose backward would start by masking gz1 -- done here
-    if shared:
-        gz1, gz2r, gq = ops.mix_bwd_shared_up(gD, sv["latent"], sv["z1"], sv["z2r"], sv["q"], V, sv["choice"],
+    gz2r = gz2b = None
+    z2r, T = sv["z2r"], sv["latent"].shape[2]
+    fused = z2r is None and gD.shape[2] == T and T <= ops.UNPOOL_MIX_MAX_T
+    if z2r is None and not fused:      # the gradient arrives upsampled, or its rows are too long for the strips: the two-pass form
+        z2r = ops.roi_unpool_fwd(sv["z2b"], sv["rois"], T)
+    if fused:                          # forward mixed straight from the segments: (gz1, gz2b), no gz2r, no un-pooling backward
+        gz1, gz2b, gq = ops.mix_bwd_shared_unpool(gD, sv["latent"], sv["z1"], sv["z2b"], sv["rois"], sv["q"], V, sv["choice"],
+                                                  relu_z1=relu_z1)
+    elif shared:
+        gz1, gz2r, gq = ops.mix_bwd_shared_up(gD, sv["latent"], sv["z1"], z2r, sv["q"], V, sv["choice"],
                                               relu_z1=relu_z1)
     else:
-        gz1, gz2r, gq = ops.mix_bwd(gD, sv["latent"], sv["z1"], sv["z2r"], sv["q"], V, sv["choice"], upsampled=up,
+        gz1, gz2r, gq = ops.mix_bwd(gD, sv["latent"], sv["z1"], z2r, sv["q"], V, sv["choice"], upsampled=up,
                                     relu_z1=relu_z1)
     gW2, gb2 = side.run(lambda: ops.theta_mlp_bwd(sv["q_theta"], gq, 256), gq)
     grads["mlp2.weight"], grads["mlp2.bias"] = gW2, gb2
-    return gz1, gz2r
+    return gz1, gz2r, gz2b
 
 
 EARLY_HOOK = None      # callable(P, grads, side) invoked instead of parallel.early_reduce at the early-bucket point of backward()
 
 
-def _latents_bwd(P, sv, gz1, gz2r, grads, side, z1_pre_gated=False, early=False):
-    """Back through `_latents` (+ the segment un-pooling that follows it): encoder-side parameter gradients."""
+def _latents_bwd(P, sv, gz1, gz2r, grads, side, z1_pre_gated=False, early=False, gz2b=None):
+    """Back through `_latents` (+ the segment un-pooling that follows it, unless the caller already holds `gz2b`, the gradient
+    wrt the segment tensor): encoder-side parameter gradients."""
     B, V, T = sv["B"], sv["V"], sv["T"]
     ops.pack_many(_latent_pack_requests(P, V, T, sv["z2_win"], True))
-    gz2b = ops.roi_unpool_bwd(gz2r, sv["rois"])                                  # [B, 128V, 7, 32]
+    if gz2b is None:
+        gz2b = ops.roi_unpool_bwd(gz2r, sv["rois"])                              # [B, 128V, 7, 32]
     gh3 = gz2b.view(B, 128 * V * N_SEG, 2 * ROI_BINS)
     gh2 = block_bwd(sv["blk_c22"], gh3, P, grads, side=side)
     gh2q = ops.convt2_deinterleave(gh2)                  # shared by the data and the weight gradient
@@ -741,8 +768,8 @@ def backward(P, sv, g_outs):
     """g_outs: gradients wrt (out, shuffle_p, shuffle_l), each [B,1,L] or None.  Returns {param name: grad}."""
     grads = {}
     side = _side(sv["z1"].device, sv["z1"].numel())
-    gz1, gz2r = _head_bwd(P, sv, g_outs, grads, side, relu_z1=True)
-    _latents_bwd(P, sv, gz1, gz2r, grads, side, z1_pre_gated=True, early=True)
+    gz1, gz2r, gz2b = _head_bwd(P, sv, g_outs, grads, side, relu_z1=True)
+    _latents_bwd(P, sv, gz1, gz2r, grads, side, z1_pre_gated=True, early=True, gz2b=gz2b)
     side.join()
     return grads
 
@@ -752,7 +779,7 @@ def backward2(P, sv, g_outs):
     gradients summed over the leads in lead order), then the folded-batch encoder."""
     grads = {}
     side = _side(sv["z1"].device, sv["z1"].numel())
-    gZ1, gZ2 = _head_bwd(P, sv, g_outs, grads, side)                              # [B, 128V, T]
+    gZ1, gZ2, _ = _head_bwd(P, sv, g_outs, grads, side)                           # [B, 128V, T]
     B, V = sv["fold"]
     T = gZ1.shape[2]
     gz1f = torch.empty(V * B, 128, T, device=gZ1.device, dtype=torch.float32)

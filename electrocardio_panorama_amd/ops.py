@@ -1364,6 +1364,44 @@ def lead_mean_mix_shared(z1, z2r, q, V, c1, c2=None):
     return latent, D2
 
 
+UNPOOL_MIX_MAX_V = 12        # NEF_UNPOOL_MIX_MAX_V: the leads' segment samples of a row in one wave's LDS strip
+UNPOOL_MIX_MAX_T = 1936      # NEF_UNPOOL_MIX_MAX_T: two gradient rows per wave, four waves, in 64 KiB of LDS
+
+
+def lead_mean_mix_unpool(z1, z2b, rois, q, V, choice, T, status=None):
+    """roi_unpool_fwd + lead_mean_mix_shared without the un-pooled tensor between them: (latent [B,256,T], D2 [2B,256,T]) straight
+    from the segment tensor z2b [B,128V,7,32], bit-identical to the two calls.  V <= UNPOOL_MIX_MAX_V."""
+    L = _lib.load()
+    c1, c2, cdev = _choice(choice)
+    _chk(z1), _chk(z2b), _chk(q), _chk(rois, torch.int64)
+    B = z1.shape[0]
+    assert z1.shape == (B, 128 * V, T) and z2b.shape == (B, 128 * V, N_SEG, 2 * ROI_BINS) and V <= UNPOOL_MIX_MAX_V
+    latent = torch.empty(B, 256, T, device=z1.device, dtype=torch.float32)
+    D2 = torch.empty(2 * B, 256, T, device=z1.device, dtype=torch.float32)
+    ev = _hbm("lead_mean_mix_unpool", z1, z2b, latent, D2)
+    _lib.check(L.nef_lead_mean_mix_unpool(_p(z1), _p(z2b), _p(rois), _p(q), _p(latent), _p(D2), _p(status), B, V, T, c1, c2, cdev,
+                                          _stream()), "nef_lead_mean_mix_unpool")
+    _done(ev)
+    return latent, D2
+
+
+def mix_bwd_shared_unpool(gD, latent, z1, z2b, rois, q, V, choice, relu_z1=False):
+    """mix_bwd_shared_up (on the gradient wrt D2 itself, [2B,256,T]) + roi_unpool_bwd without gz2r between them:
+    (gz1 [B,128V,T], gz2b [B,128V,7,32], gq [B,256]), bit-identical to the two calls.  T <= UNPOOL_MIX_MAX_T."""
+    L = _lib.load()
+    c1, c2, cdev = _choice(choice)
+    _chk(gD), _chk(latent), _chk(z1), _chk(z2b), _chk(q), _chk(rois, torch.int64)
+    B, _, T = latent.shape
+    assert gD.shape == (2 * B, 256, T) and z2b.shape == (B, 128 * V, N_SEG, 2 * ROI_BINS) and 2 <= T <= UNPOOL_MIX_MAX_T
+    gz1, gz2b = torch.empty_like(z1), torch.empty_like(z2b)
+    gq = torch.empty(B, 256, device=latent.device, dtype=torch.float32)
+    ev = _hbm("mix_bwd_shared_unpool", gD, latent, z1, z2b, gz1, gz2b)
+    _lib.check(L.nef_mix_bwd_unpool(_p(gD), _p(latent), _p(z1), _p(z2b), _p(rois), _p(q), _p(gz1), _p(gz2b), _p(gq), B, V, T, c1, c2,
+                                    cdev, int(relu_z1), _stream()), "nef_mix_bwd_unpool")
+    _done(ev)
+    return gz1, gz2b, gq
+
+
 def mix_bwd_shared_up(gU2, latent, z1, z2r, q, V, c1, c2=None, relu_z1=False):
     """mix_bwd for the two-pass gradient wrt the shared input: gU2 [2B,256,2T] wrt its x2-upsampled form (the adjoint is taken on
     the fly), or [2B,256,T] wrt the input itself (what the polyphase backward-data pass leaves)."""

@@ -395,6 +395,23 @@ int nef_mix_fwd_shared(const float* latent, const float* z1, const float* z2r, c
  * bit-identical latent and D2, 0.65 GB less traffic per step at config 2. */
 int nef_lead_mean_mix_shared(const float* z1, const float* z2r, const float* q, float* latent, float* D2, int B, int V,
                              int T, int c1, int c2, const int32_t* choice_dev, nef_stream_t stream);
+/* The same two outputs straight from the segment tensor z2b [B][128V][7][32] of nef_roi_unpool_fwd's input: the un-pooled tensor
+ * z2r is never written.  latent and D2 are bit-identical to nef_roi_unpool_fwd followed by nef_lead_mean_mix_shared, `status` is
+ * raised as nef_roi_unpool_fwd raises it.  The z1 half runs nef_lead_mean_mix_shared's kernels on the rows c < 128; the z2 half holds
+ * the V leads' segment samples of a (sample, channel) row on chip, evaluates the resampling taps once per output position and forms
+ * mean and pick there.  1 <= V <= NEF_UNPOOL_MIX_MAX_V. */
+#define NEF_UNPOOL_MIX_MAX_V 12
+int nef_lead_mean_mix_unpool(const float* z1, const float* z2b, const int64_t* rois, const float* q, float* latent, float* D2,
+                             int32_t* status, int B, int V, int T, int c1, int c2, const int32_t* choice_dev, nef_stream_t stream);
+/* Its adjoint: nef_mix_bwd(shared = 1, up = 0) followed by nef_roi_unpool_bwd without the gradient gz2r between them.
+ * gD [2B][256][T], latent [B][256][T]; gz1 [B][128V][T], gz2b [B][128V][7][32] and gq [B][256] are bit-identical to the two calls
+ * (the z2 half deals a row's positions to the lanes as the nef_mix_bwd kernel of the same shape does, so gq adds in the same order).  Of the V gradient rows of a (sample, channel) only two
+ * differ -- the picked lead's and everyone else's -- so the gather transpose runs twice per row, not V times; the picked lead's
+ * un-pooled value that gq needs is rebuilt from z2b.  2 <= T <= NEF_UNPOOL_MIX_MAX_T (two gradient rows per wave in LDS). */
+#define NEF_UNPOOL_MIX_MAX_T 1936
+int nef_mix_bwd_unpool(const float* gD, const float* latent, const float* z1, const float* z2b, const int64_t* rois, const float* q,
+                       float* gz1, float* gz2b, float* gq, int B, int V, int T, int c1, int c2, const int32_t* choice_dev, int relu_z1,
+                       nef_stream_t stream);
 int nef_pass_combine_fwd(const float* P2, const float* bias, float* c1, int B, int C, int L, nef_stream_t stream);
 /* nef_pass_combine_fwd that also leaves the train-mode BatchNorm statistics of its output (3 passes of B samples; same
  * outputs as nef_bn_train_stats(c1, ..., P = 3, Bp = B, ...), running statistics updated pass by pass): saves the separate
