@@ -73,6 +73,12 @@ class EmaArgs(C.Structure):
     _fields_ = [("ema", p), ("n_averaged", p), ("decay", C.c_double), ("warmup", i32), ("reserved0", i32)]
 
 
+class TrustArgs(C.Structure):
+    """Mirror of `nef_trust_args` (include/nefnet_hip.h)."""
+    _fields_ = [("seg_end", p), ("seg_wd_mul", p), ("seg_adapt", p), ("ratio", p), ("stats", p), ("taint", p), ("ws", p),
+                ("ws_bytes", sz), ("trust_coef", f32), ("trust_eps", f32), ("n_segs", i32), ("reserved0", i32)]
+
+
 class PackDesc(C.Structure):
     """Mirror of `nef_pack_desc` (include/nefnet_hip.h)."""
     _fields_ = [("w", p), ("wp", p), ("G", i32), ("Cog", i32), ("Cig", i32), ("K", i32), ("transpose_flip", i32),
@@ -157,6 +163,9 @@ SIGNATURES = {
     "nef_update_args_bytes": (sz, []),
     "nef_update_ema": (i32, [C.POINTER(UpdateArgs), C.POINTER(EmaArgs), p]),
     "nef_ema_args_bytes": (sz, []),
+    "nef_update_trust": (i32, [C.POINTER(UpdateArgs), C.POINTER(TrustArgs), C.POINTER(EmaArgs), p]),
+    "nef_update_trust_ws_bytes": (sz, [i64, i32]),
+    "nef_trust_args_bytes": (sz, []),
     "nef_grad_clip_ws_bytes": (sz, []),
     "nef_grad_clip": (i32, [p, i64, f32, f32, p, p, p, sz, p]),
     "nef_h2_taint": (i32, [p, p, p, p]),
@@ -206,7 +215,8 @@ def load():
                                ("nef_bww_args", lib.nef_bww_args_bytes(), BwwArgs),
                                ("nef_bn_bwd_args", lib.nef_bn_bwd_args_bytes(), BnBwdArgs),
                                ("nef_update_args", lib.nef_update_args_bytes(), UpdateArgs),
-                               ("nef_ema_args", lib.nef_ema_args_bytes(), EmaArgs)):
+                               ("nef_ema_args", lib.nef_ema_args_bytes(), EmaArgs),
+                               ("nef_trust_args", lib.nef_trust_args_bytes(), TrustArgs)):
         if size != C.sizeof(mirror):
             raise NefLibraryError(f"{LIB_PATH}: {name} is {size} bytes, the binding mirrors {C.sizeof(mirror)}; rebuild with "
                                   "`python -m electrocardio_panorama_amd.csrc.build`")

@@ -70,6 +70,14 @@ _DEFAULTS = {
         "ema_warmup": False,
         # with ema_decay > 0: the per-epoch test phase (psnr_gen, best_valid) and Solver.val run on the averaged weights
         "ema_eval": True,
+        # optim 'lars' / 'lamb': layer-wise trust ratios inside the update (nef_update_trust; one norm pair per parameter tensor).
+        # 'lars' multiplies every tensor's decayed gradient by trust_coef * ||p|| / (||g|| + weight_decay * ||p|| + trust_eps) in front of
+        # the momentum; 'lamb' scales Adam's direction u by ||p|| / ||u|| and uses neither number
+        "trust_coef": 1e-3,
+        "trust_eps": 1e-8,
+        # fnmatch patterns on the state_dict keys of the parameters whose trust ratio stays 1 (they step at the plain learning rate),
+        # e.g. ['*.bias', '*.double_conv.[14].*'] for the biases and the BatchNorm affine parameters
+        "trust_exempt": [],
     },
 }
 

@@ -1559,6 +1559,293 @@ __global__ __launch_bounds__(256) void clip_scale(float* __restrict__ g, int64_t
 }
 
 // ------------------------------------------------------------------------------------------------
+// nef_update_trust: LARS / LAMB, a layer-wise trust ratio per SEGMENT of the flat buffers       (no counterpart in the reference)
+// ------------------------------------------------------------------------------------------------
+// Three launches.  (1) trust_norms: block b owns the fixed chunk [b*TRUST_CHUNK - mis, (b+1)*TRUST_CHUNK - mis) of the flat index
+// space (mis: the elements p lies behind a 16-byte boundary, so every chunk but the first starts on one) and leaves, for every
+// segment s that meets its chunk, the fp64 pair (sum p^2, sum g'^2 or sum u^2) in slot b + s of the workspace.  The pairs (b, s)
+// that meet are strictly increasing in b + s, so no two share a slot, a segment's partials are contiguous and in block order, and
+// the workspace is 2 (blocks + n_segs) doubles.  Every sum has a fixed order (lane, wave, block: nef_block_sum_d): no atomics.
+// (2) trust_finish: one block, lane s sums the partials of segment s in ascending order and forms q_s; a non-finite sum taints the
+// step.  (3) trust_update: update_kernel's structure with (end, wd_s, q_s) per segment staged in LDS.
+// The word behind the partials (`flag`) is what (2) tells (3) and the one-lane launch: > 0 = leave everything as it is.
+constexpr int TRUST_CHUNK = 4096;      // elements per block: 4 dwordx4 loads per lane and stream; 7.18 M parameters: 1753 blocks, ~7 per CU
+constexpr int TRUST_VPL = TRUST_CHUNK / (256 * 4);
+
+static inline int trust_blocks(int64_t n) { return (int)nef_cdiv(n + 3, TRUST_CHUNK); }      // n alone: mis <= 3 is covered (the last block may be empty)
+
+struct trust_lamb_consts {
+    float gscale, w1, b2, w2, inv_bc1, inv_bc2s, eps;
+};
+
+__device__ __forceinline__ trust_lamb_consts trust_lamb_setup(const float* __restrict__ step, double b1, double b2, float eps, float gscale) {
+    // the bias corrections in fp64, as in adam_kernel
+    const double t = (double)step[0] + 1.0;
+    const double bc1 = 1.0 - pow(b1, t), bc2 = 1.0 - pow(b2, t);
+    trust_lamb_consts c;
+    c.gscale = gscale, c.eps = eps;
+    c.inv_bc1 = (float)(1.0 / bc1);
+    c.inv_bc2s = 1.f / (float)sqrt(bc2);
+    c.w1 = (float)(1.0 - b1), c.w2 = (float)(1.0 - b2), c.b2 = (float)b2;
+    return c;
+}
+
+// LAMB's moments and the undecayed direction r = (m / bc1) / (sqrt(v / bc2) + eps) of one element: the norm pass and the update call
+// this one function on the same old state, so the u = r + wd_s * p that is applied is the u that was measured
+__device__ __forceinline__ float trust_lamb_r(const trust_lamb_consts& c, float g, float& m, float& v) {
+    const float gv = g * c.gscale;
+    m = m + c.w1 * (gv - m);
+    v = v * c.b2 + c.w2 * gv * gv;
+    return (m * c.inv_bc1) / (sqrtf(v) * c.inv_bc2s + c.eps);
+}
+__device__ __forceinline__ float trust_lamb_u(float r, float wd, float p) { return wd != 0.f ? r + wd * p : r; }
+
+// RULE 0: LARS (a = p, b = g * gscale).  RULE 1: LAMB (a = p, b = r; u = r + wd_s * a is formed per segment).  VEC: p, g (m, v) lie
+// equally far behind a 16-byte boundary -- whole in-range vectors are loaded as dwordx4, the rest (and everything without VEC) by
+// guarded scalar loads of the same elements, so both forms add the same values in the same order.
+template <int RULE, bool VEC>
+__global__ __launch_bounds__(256) void trust_norms(const float* __restrict__ p, const float* __restrict__ g, const float* __restrict__ m,
+                                                   const float* __restrict__ v, int64_t n, int mis, float gscale, float wd, double b1,
+                                                   double b2, float eps, const float* __restrict__ step, const float* __restrict__ skip,
+                                                   const float* __restrict__ taint, const int64_t* __restrict__ seg_end,
+                                                   const float* __restrict__ seg_wd_mul, int n_segs, double* __restrict__ part) {
+    __shared__ int64_t s_end[NEF_TRUST_MAX_SEGS];
+    __shared__ double sm[4];
+    if ((skip && skip[0] > 0.f) || (taint && taint[0] > 0.f)) return;      // the step is skipped anyway: the finish reads nothing
+    const int64_t base = (int64_t)blockIdx.x * TRUST_CHUNK - mis;
+    const int64_t lo = base < 0 ? 0 : base, hi = base + TRUST_CHUNK < n ? base + TRUST_CHUNK : n;
+    if (lo >= hi) return;
+    for (int s = threadIdx.x; s < n_segs; s += 256) s_end[s] = seg_end[s];
+    __syncthreads();
+    trust_lamb_consts c = {};
+    if (RULE == 1) c = trust_lamb_setup(step, b1, b2, eps, gscale);
+    float a[TRUST_VPL][4], b[TRUST_VPL][4];
+#pragma unroll
+    for (int k = 0; k < TRUST_VPL; ++k) {
+        const int64_t i0 = base + (int64_t)(k * 256 + threadIdx.x) * 4;
+        nef_f32x4 pv = {0.f, 0.f, 0.f, 0.f}, gv = pv, mv = pv, vv = pv;
+        if (VEC && i0 >= 0 && i0 + 4 <= n) {
+            pv = *(const nef_f32x4*)(p + i0), gv = *(const nef_f32x4*)(g + i0);
+            if (RULE == 1) mv = *(const nef_f32x4*)(m + i0), vv = *(const nef_f32x4*)(v + i0);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int64_t i = i0 + e;
+                if (i >= 0 && i < n) {
+                    pv[e] = p[i], gv[e] = g[i];
+                    if (RULE == 1) mv[e] = m[i], vv[e] = v[i];
+                }
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            a[k][e] = pv[e];
+            if (RULE == 0) {
+                b[k][e] = gv[e] * gscale;
+            } else {      // the new m and v stay in registers: this pass stores nothing but partial sums
+                float me = mv[e], ve = vv[e];
+                b[k][e] = trust_lamb_r(c, gv[e], me, ve);
+            }
+        }
+    }
+    // every segment that meets [lo, hi): elements outside [0, n) lie in no segment
+    int s = upd_find_run(s_end, n_segs, 0, lo);
+    int64_t beg = s == 0 ? 0 : s_end[s - 1];
+    for (; s < n_segs && beg < hi; ++s) {
+        const int64_t end = s_end[s];
+        const float wd_s = RULE == 1 ? wd * seg_wd_mul[s] : 0.f;
+        double sa = 0.0, sb = 0.0;
+#pragma unroll
+        for (int k = 0; k < TRUST_VPL; ++k) {
+            const int64_t i0 = base + (int64_t)(k * 256 + threadIdx.x) * 4;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (i0 + e >= beg && i0 + e < end) {
+                    const float be = RULE == 1 ? trust_lamb_u(b[k][e], wd_s, a[k][e]) : b[k][e];
+                    sa += (double)a[k][e] * (double)a[k][e];
+                    sb += (double)be * (double)be;
+                }
+            }
+        }
+        sa = nef_block_sum_d(sa, sm);
+        sb = nef_block_sum_d(sb, sm);
+        if (threadIdx.x == 0) part[2 * ((int64_t)blockIdx.x + s)] = sa, part[2 * ((int64_t)blockIdx.x + s) + 1] = sb;
+        beg = end;
+    }
+}
+
+// One block; lane s owns segment s.  stats: [0] / [1] the smallest / largest q_s over the adapted segments of this call (1 when none
+// adapts), [2] += 1 per call that updates, [3] += 1 per call whose norms were not finite.
+template <int RULE>
+__global__ __launch_bounds__(256) void trust_finish(const double* __restrict__ part, int nblk, int64_t n, int mis, float wd, float coef,
+                                                    float teps, const int64_t* __restrict__ seg_end, const float* __restrict__ seg_wd_mul,
+                                                    const float* __restrict__ seg_adapt, int n_segs, const float* __restrict__ skip,
+                                                    float* __restrict__ taint, float* __restrict__ ratio, float* __restrict__ stats,
+                                                    float* __restrict__ flag) {
+    __shared__ float s_q[NEF_TRUST_MAX_SEGS];
+    __shared__ int s_adapt[NEF_TRUST_MAX_SEGS];
+    if ((skip && skip[0] > 0.f) || (taint && taint[0] > 0.f)) {      // skipped on entry: ratio and stats stay as they are
+        if (threadIdx.x == 0) flag[0] = 1.f;
+        return;
+    }
+    const int s = threadIdx.x;
+    bool bad = false;
+    float q = 1.f;
+    int adapt = 0;
+    if (s < n_segs) {
+        const int64_t beg = s == 0 ? 0 : seg_end[s - 1], end = seg_end[s];
+        double sa = 0.0, sb = 0.0;
+        if (end > beg) {
+            const int64_t b0 = (beg + mis) / TRUST_CHUNK, b1 = (end - 1 + mis) / TRUST_CHUNK;
+            const double* __restrict__ ps = part + 2 * (b0 + s);
+            for (int64_t k = 0; k <= b1 - b0; ++k) sa += ps[2 * k], sb += ps[2 * k + 1];
+        }
+        bad = !(isfinite(sa) && isfinite(sb));
+        adapt = seg_adapt[s] != 0.f;
+        const double wn = sqrt(sa), xn = sqrt(sb);
+        if (adapt && !bad && wn > 0.0 && xn > 0.0) {      // q_s in fp64, rounded to fp32 once
+            if (RULE == 0) q = (float)((double)coef * wn / (xn + (double)wd * (double)seg_wd_mul[s] * wn + (double)teps));
+            else q = (float)(wn / xn);
+        }
+    }
+    const int any_bad = __syncthreads_or(bad ? 1 : 0);
+    if (any_bad) {      // a non-finite norm: the step is skipped, the ratio table stays as it was
+        if (threadIdx.x == 0) {
+            stats[3] += 1.f;
+            if (taint) taint[0] += 1.f;
+            flag[0] = 1.f;
+        }
+        return;
+    }
+    if (s < n_segs) ratio[s] = q, s_q[s] = q, s_adapt[s] = adapt;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    float qmin = 0.f, qmax = 0.f;
+    bool have = false;
+    for (int i = 0; i < n_segs; ++i) {
+        if (!s_adapt[i]) continue;
+        qmin = have ? fminf(qmin, s_q[i]) : s_q[i];
+        qmax = have ? fmaxf(qmax, s_q[i]) : s_q[i];
+        have = true;
+    }
+    stats[0] = have ? qmin : 1.f;
+    stats[1] = have ? qmax : 1.f;
+    stats[2] += 1.f;
+    flag[0] = 0.f;
+}
+
+struct trust_upd_consts {
+    float lr, gscale, mu;
+    int nesterov;
+    trust_lamb_consts l;
+};
+
+// RULE 0, LARS: d = (g' + wd_s p) q_s in SGD's operation order (upd_elem), so q_s = 1 gives nef_update's bits.  RULE 1, LAMB.
+template <int RULE>
+__device__ __forceinline__ void trust_elem(const trust_upd_consts& c, float wd, float q, float& p, float g, float& s0, float& s1) {
+    if (RULE == 0) {
+        float gv = g * c.gscale;
+        if (wd != 0.f) gv = gv + wd * p;
+        const float d = gv * q;
+        const float bv = fmaf(c.mu, s0, d);
+        s0 = bv;
+        const float dd = c.nesterov ? d + c.mu * bv : bv;
+        p = p - c.lr * dd;
+    } else {
+        const float u = trust_lamb_u(trust_lamb_r(c.l, g, s0, s1), wd, p);
+        p = p - (c.lr * q) * u;
+    }
+}
+
+template <int RULE, bool VEC, bool EMA>
+__global__ __launch_bounds__(256) void trust_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s0,
+                                                    float* __restrict__ s1, int64_t n, float lr, float mu, int nesterov, double b1,
+                                                    double b2, float eps, float wd, float gscale, const float* __restrict__ step,
+                                                    const float* __restrict__ skip, const float* __restrict__ flag, int32_t* skipped,
+                                                    const float* __restrict__ lr_dev, const int64_t* __restrict__ seg_end,
+                                                    const float* __restrict__ seg_wd_mul, const float* __restrict__ ratio, int n_segs,
+                                                    float* __restrict__ ema, const float* __restrict__ ema_n, double ema_decay,
+                                                    int ema_warmup) {
+    __shared__ int64_t s_end[NEF_TRUST_MAX_SEGS];
+    __shared__ float s_wd[NEF_TRUST_MAX_SEGS], s_q[NEF_TRUST_MAX_SEGS];
+    if (lr_dev) lr = lr_dev[0];
+    if ((skip && skip[0] > 0.f) || flag[0] > 0.f) {      // a tainted step, or norms that were not finite: nothing moves
+        if (skipped && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(skipped, 1);
+        return;
+    }
+    for (int r = threadIdx.x; r < n_segs; r += blockDim.x) s_end[r] = seg_end[r], s_wd[r] = wd * seg_wd_mul[r], s_q[r] = ratio[r];
+    __syncthreads();
+    trust_upd_consts c;
+    c.lr = lr, c.gscale = gscale, c.mu = mu, c.nesterov = nesterov, c.l = trust_lamb_consts{};
+    if (RULE == 1) c.l = trust_lamb_setup(step, b1, b2, eps, gscale);
+    float ew = 0.f;
+    if (EMA) {      // as in update_kernel
+        double d = ema_decay;
+        if (ema_warmup) {
+            const double t = (double)ema_n[0];
+            d = fmin(d, (1.0 + t) / (10.0 + t));
+        }
+        ew = (float)(1.0 - d);
+    }
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t n4 = VEC ? (n >> 2) : 0;
+    int run = 0;
+    if (VEC) {      // 16-byte body: one dwordx4 load / store per stream and lane, one table lookup per vector
+        for (int64_t i = gid; i < n4; i += stride) {
+            nef_f32x4 pv = ((const nef_f32x4*)p)[i], av = ((const nef_f32x4*)s0)[i], bv = {0.f, 0.f, 0.f, 0.f};
+            if (RULE != 0) bv = ((const nef_f32x4*)s1)[i];
+            const nef_f32x4 gv = ((const nef_f32x4*)g)[i];
+            nef_f32x4 ev = {0.f, 0.f, 0.f, 0.f};
+            if (EMA) ev = ((const nef_f32x4*)ema)[i];
+            float wds[4], qs[4];
+            run = upd_find_run(s_end, n_segs, run, 4 * i);
+            int r = run;
+            wds[0] = s_wd[r], qs[0] = s_q[r];
+            if (s_end[r] >= 4 * i + 4) {
+                wds[1] = wds[2] = wds[3] = wds[0];
+                qs[1] = qs[2] = qs[3] = qs[0];
+            } else {
+#pragma unroll
+                for (int e = 1; e < 4; ++e) {
+                    while (r < n_segs - 1 && s_end[r] <= 4 * i + e) ++r;
+                    wds[e] = s_wd[r], qs[e] = s_q[r];
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float pe = pv[e], ae = av[e], be = bv[e];
+                trust_elem<RULE>(c, wds[e], qs[e], pe, gv[e], ae, be);
+                pv[e] = pe, av[e] = ae, bv[e] = be;
+                if (EMA) ev[e] = fmaf(ew, pe - ev[e], ev[e]);
+            }
+            ((nef_f32x4*)p)[i] = pv;
+            ((nef_f32x4*)s0)[i] = av;
+            if (RULE != 0) ((nef_f32x4*)s1)[i] = bv;
+            if (EMA) ((nef_f32x4*)ema)[i] = ev;
+        }
+    }
+    run = 0;
+    for (int64_t i = 4 * n4 + gid; i < n; i += stride) {       // the n % 4 tail (VEC), or everything
+        run = upd_find_run(s_end, n_segs, run, i);
+        float pe = p[i], ae = s0[i], be = RULE != 0 ? s1[i] : 0.f;
+        trust_elem<RULE>(c, s_wd[run], s_q[run], pe, g[i], ae, be);
+        p[i] = pe, s0[i] = ae;
+        if (RULE != 0) s1[i] = be;
+        if (EMA) {
+            const float ee = ema[i];
+            ema[i] = fmaf(ew, pe - ee, ee);
+        }
+    }
+}
+
+// The one-lane launch behind trust_update: *step (LAMB) and the count of EMA updates advance unless the step was skipped
+__global__ void trust_step_kernel(float* step, float* n_averaged, const float* __restrict__ skip, const float* __restrict__ flag) {
+    if ((skip && skip[0] > 0.f) || flag[0] > 0.f) return;
+    if (step) step[0] += 1.f;
+    if (n_averaged) n_averaged[0] += 1.f;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Round 6: the last torch elementwise kernels of the train step, as one launch each.
 // amax_roll: ops.amax_roll's follow-up rule on the split-fp16 site table (was ~10 ATen launches: compares, ors, where, fill).
 __global__ __launch_bounds__(256) void amax_roll_kernel(float* __restrict__ cur, float* __restrict__ nxt, int n, float up, float down,
@@ -1880,6 +2167,44 @@ static void update_dispatch(const nef_update_args& a, const nef_ema_args* e, hip
         if (table) update_launch<2, true, EMA>(a, a.m, a.v, e, st);
         else update_launch<2, false, EMA>(a, a.m, a.v, e, st);
     }
+}
+
+template <int RULE, bool EMA>
+static void trust_launch(const nef_update_args& a, const nef_trust_args& t, const nef_ema_args* e, hipStream_t stream) {
+    float* s0 = RULE == 0 ? a.buf : a.m;
+    float* s1 = RULE == 0 ? nullptr : a.v;
+    float* ema = EMA ? e->ema : nullptr;
+    const int nblk = trust_blocks(a.n);
+    double* part = (double*)t.ws;
+    float* flag = (float*)(part + 2 * ((size_t)nblk + (size_t)t.n_segs));
+    // the norm pass: dwordx4 loads when its streams lie equally far behind a 16-byte boundary
+    const int mis = (int)(((uintptr_t)a.p >> 2) & 3);
+    bool same = (((uintptr_t)a.g >> 2) & 3) == (unsigned)mis && ((uintptr_t)a.p & 3) == 0 && ((uintptr_t)a.g & 3) == 0;
+    if (RULE == 1) same = same && (((uintptr_t)a.m >> 2) & 3) == (unsigned)mis && (((uintptr_t)a.v >> 2) & 3) == (unsigned)mis;
+#define NEF_TRUST_NORM_ARGS                                                                                                        \
+    a.p, a.g, a.m, a.v, a.n, mis, a.gscale, a.weight_decay, a.beta1, a.beta2, a.eps, a.step, a.skip_if_positive, (const float*)t.taint, \
+        t.seg_end, t.seg_wd_mul, t.n_segs, part
+    if (same) hipLaunchKernelGGL((trust_norms<RULE, true>), dim3(nblk), dim3(256), 0, NEF_ST, NEF_TRUST_NORM_ARGS);
+    else hipLaunchKernelGGL((trust_norms<RULE, false>), dim3(nblk), dim3(256), 0, NEF_ST, NEF_TRUST_NORM_ARGS);
+#undef NEF_TRUST_NORM_ARGS
+    hipLaunchKernelGGL(trust_finish<RULE>, dim3(1), dim3(256), 0, NEF_ST, (const double*)part, nblk, a.n, mis, a.weight_decay,
+                       t.trust_coef, t.trust_eps, t.seg_end, t.seg_wd_mul, t.seg_adapt, t.n_segs, a.skip_if_positive, t.taint, t.ratio,
+                       t.stats, flag);
+    // (s1, ema NULL: aligned)
+    const bool vec = (((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)s0 | (uintptr_t)s1 | (uintptr_t)ema) & 15) == 0 && a.n >= 4;
+#define NEF_TRUST_UPD_ARGS                                                                                                       \
+    a.p, a.g, s0, s1, a.n, a.lr, a.mu, a.nesterov, a.beta1, a.beta2, a.eps, a.weight_decay, a.gscale, a.step, a.skip_if_positive, \
+        (const float*)flag, a.skipped, a.lr_dev, t.seg_end, t.seg_wd_mul, (const float*)t.ratio, t.n_segs, ema,                 \
+        EMA ? (const float*)e->n_averaged : nullptr, EMA ? e->decay : 0.0, EMA ? (int)(e->warmup != 0) : 0
+    if (vec)
+        hipLaunchKernelGGL((trust_update<RULE, true, EMA>), dim3(nef_stream_grid(a.n >> 2, 256)), dim3(256), 0, NEF_ST, NEF_TRUST_UPD_ARGS);
+    else
+        hipLaunchKernelGGL((trust_update<RULE, false, EMA>), dim3(nef_stream_grid(a.n, 256)), dim3(256), 0, NEF_ST, NEF_TRUST_UPD_ARGS);
+#undef NEF_TRUST_UPD_ARGS
+    // stream order: every block of the update has read the step word and the EMA count before this ONE launch advances them
+    if (RULE == 1 || EMA)
+        hipLaunchKernelGGL(trust_step_kernel, dim3(1), dim3(1), 0, NEF_ST, RULE == 1 ? a.step : nullptr, EMA ? e->n_averaged : nullptr,
+                           a.skip_if_positive, (const float*)flag);
 }
 
 extern "C" {
@@ -2624,6 +2949,41 @@ int nef_grad_clip(float* g, int64_t n, float max_norm, float gscale, float* tain
     hipLaunchKernelGGL(clip_partial, dim3(nblk), dim3(256), 0, NEF_ST, g, n, head, (double*)ws);
     hipLaunchKernelGGL(clip_final, dim3(1), dim3(256), 0, NEF_ST, (const double*)ws, nblk, max_norm, gscale, taint, stats);
     hipLaunchKernelGGL(clip_scale, dim3(nblk), dim3(256), 0, NEF_ST, g, n, head, (const float*)stats);
+    return nef_launch_status();
+}
+
+size_t nef_trust_args_bytes(void) { return sizeof(nef_trust_args); }
+
+// the fp64 partial pairs, then the 16-byte line whose first word tells the update to skip
+size_t nef_update_trust_ws_bytes(int64_t n, int32_t n_segs) {
+    if (n <= 0 || n_segs <= 0) return 0;
+    return (size_t)2 * ((size_t)trust_blocks(n) + (size_t)n_segs) * sizeof(double) + 16;
+}
+
+int nef_update_trust(const nef_update_args* args, const nef_trust_args* t, const nef_ema_args* e, nef_stream_t stream) {
+    NEF_ENTER();
+    NEF_REQUIRE(args && t, NEF_E_NULL);
+    const nef_update_args& a = *args;
+    NEF_REQUIRE(a.p && a.g, NEF_E_NULL);
+    NEF_REQUIRE(a.rule == 0 || a.rule == 1, NEF_E_UNSUPPORTED);
+    NEF_REQUIRE(a.rule == 0 ? a.buf != nullptr : (a.m && a.v && a.step), NEF_E_NULL);
+    NEF_REQUIRE(t->seg_end && t->seg_wd_mul && t->seg_adapt && t->ratio && t->stats && t->ws, NEF_E_NULL);
+    NEF_REQUIRE(a.n > 0 && a.n_runs == 0, NEF_E_SHAPE);      // the decay multipliers travel per segment
+    NEF_REQUIRE(t->n_segs >= 1 && t->n_segs <= NEF_TRUST_MAX_SEGS, NEF_E_SHAPE);
+    NEF_REQUIRE(a.weight_decay >= 0.f && t->trust_coef >= 0.f && t->trust_eps >= 0.f, NEF_E_SHAPE);      // (a NaN fails the comparison too)
+    NEF_REQUIRE(((uintptr_t)t->ws & 7) == 0, NEF_E_SHAPE);
+    NEF_REQUIRE(t->ws_bytes >= nef_update_trust_ws_bytes(a.n, t->n_segs), NEF_E_WORKSPACE);
+    if (e) {
+        NEF_REQUIRE(e->ema && e->n_averaged, NEF_E_NULL);
+        NEF_REQUIRE(e->decay >= 0.0 && e->decay < 1.0, NEF_E_SHAPE);
+    }
+    if (a.rule == 0) {
+        if (e) trust_launch<0, true>(a, *t, e, NEF_ST);
+        else trust_launch<0, false>(a, *t, nullptr, NEF_ST);
+    } else {
+        if (e) trust_launch<1, true>(a, *t, e, NEF_ST);
+        else trust_launch<1, false>(a, *t, nullptr, NEF_ST);
+    }
     return nef_launch_status();
 }
 

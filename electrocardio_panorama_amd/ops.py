@@ -1811,6 +1811,68 @@ def update_adam(p, g, m, v, step, lr, beta1, beta2, eps, weight_decay, gscale, d
             weight_decay, runs, skip, lr_dev, ema=ema, m=_p(m), v=_p(v), step=_p(step), beta1=beta1, beta2=beta2, eps=eps)
 
 
+def _update_trust(tag, hbm, rule, p, g, lr, gscale, weight_decay, segs, ratio, stats, trust_coef, trust_eps, skip, lr_dev, taint, ema,
+                  **fields):
+    """One nef_update_trust call (include/nefnet_hip.h).  `segs`: the segment table (seg_end int64 [S], seg_wd_mul fp32 [S], seg_adapt
+    fp32 [S]) on p's device -- one segment per parameter tensor, exclusive ends in flat order, ascending, the last one = p.numel(); the
+    library cannot check it.  `ratio` fp32 [S] and `stats` fp32 [4] are the caller's: the call writes them.  `ema`: as for _update (the
+    tag gets "_ema", the bytes two streams more)."""
+    L = _lib.load()
+    _chk(p), _chk(ratio), _chk(stats)
+    seg_end, seg_wd_mul, seg_adapt = segs
+    _chk(seg_end, torch.int64), _chk(seg_wd_mul), _chk(seg_adapt)
+    S = seg_end.numel()
+    assert 0 < S == seg_wd_mul.numel() == seg_adapt.numel() == ratio.numel() and stats.numel() == 4
+    assert g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.numel() == p.numel()
+    if taint is not None:
+        _chk(taint)
+    E = None
+    if ema is not None:
+        e_buf, e_n, decay, warmup = ema
+        _chk(e_buf), _chk(e_n)
+        assert e_buf.numel() == p.numel() and e_n.numel() == 1
+        if not 0.0 <= float(decay) < 1.0:
+            raise ValueError(f"Invalid ema decay: {decay}")
+        E = _lib.EmaArgs(ema=_p(e_buf), n_averaged=_p(e_n), decay=float(decay), warmup=int(bool(warmup)))
+        tag, hbm = tag + "_ema", tuple(hbm) + (e_buf, e_buf)
+    nws = L.nef_update_trust_ws_bytes(p.numel(), S)
+    ws = workspace(nws, p.device)
+    ev = _hbm(tag, *hbm)
+    sk = _p(_amax_state(p.device)["skipped"]) if skip is not None else None
+    A = _lib.UpdateArgs(p=_p(p), g=_p(g), n=p.numel(), lr=lr, gscale=gscale, weight_decay=weight_decay, rule=rule,
+                        skip_if_positive=_p(skip), skipped=sk, lr_dev=_p(lr_dev), n_runs=0, **fields)
+    T = _lib.TrustArgs(seg_end=_p(seg_end), seg_wd_mul=_p(seg_wd_mul), seg_adapt=_p(seg_adapt), ratio=_p(ratio), stats=_p(stats),
+                       taint=_p(taint), ws=_p(ws), ws_bytes=nws, trust_coef=float(trust_coef), trust_eps=float(trust_eps), n_segs=S)
+    _lib.check(L.nef_update_trust(C.byref(A), C.byref(T), None if E is None else C.byref(E), _stream()), "nef_update_trust")
+    _done(ev)
+
+
+def update_lars(p, g, buf, lr, mu, gscale, segs, ratio, stats, trust_coef=1e-3, trust_eps=1e-8, weight_decay=0.0, nesterov=False,
+                skip=None, lr_dev=None, taint=None, ema=None):
+    """LARS over flat fp32 buffers, in place on p / buf (`buf` starts at zero): momentum SGD (dampening 0, optional Nesterov) whose
+    decayed gradient of segment s is multiplied by q_s = trust_coef * ||p_s|| / (||g'_s|| + wd_s * ||p_s|| + trust_eps), g' = g * gscale,
+    wd_s = weight_decay * seg_wd_mul[s]; q_s = 1 where seg_adapt[s] is 0 or a norm is 0.  `segs`: (seg_end int64, seg_wd_mul, seg_adapt)
+    device tensors, one entry per parameter tensor.  `ratio` [S] receives the q_s of this call; `stats` (4 words): [0] / [1] the smallest
+    / largest q_s over the adapted segments, [2] += 1 when the call updated, [3] += 1 when a norm was not finite -- such a call changes
+    nothing else but `taint` (+= 1 when given) and counts in h2_skipped().  `skip`, `lr_dev`, `ema`: as for update_sgd.  The norms are
+    deterministic fp64 sums: the same buffers give the same bits eagerly, under graph replay and on every rank.  Capturable."""
+    _chk(buf)
+    assert buf.numel() == p.numel()
+    _update_trust("update_lars", (p, g, p, p, g, buf, buf), 0, p, g, lr, gscale, weight_decay, segs, ratio, stats, trust_coef, trust_eps,
+                  skip, lr_dev, taint, ema, buf=_p(buf), mu=mu, nesterov=int(bool(nesterov)))
+
+
+def update_lamb(p, g, m, v, step, lr, beta1, beta2, eps, weight_decay, gscale, segs, ratio, stats, skip=None, lr_dev=None, taint=None,
+                ema=None):
+    """LAMB over flat fp32 buffers, in place on p / m / v: Adam's moments and bias corrections (`step` as for adam), the direction
+    u = (m / bc1) / (sqrt(v / bc2) + eps) + wd_s * p, and p -= lr * q_s * u with q_s = ||p_s|| / ||u_s|| per segment (1 where seg_adapt[s]
+    is 0 or a norm is 0).  `segs`, `ratio`, `stats`, `taint`, `skip`, `lr_dev`, `ema`: as for update_lars."""
+    _chk(m), _chk(v), _chk(step)
+    assert p.numel() == m.numel() == v.numel() and step.numel() == 1
+    _update_trust("update_lamb", (p, g, m, v, p, p, g, m, m, v, v), 1, p, g, lr, gscale, weight_decay, segs, ratio, stats, 0.0, 0.0,
+                  skip, lr_dev, taint, ema, m=_p(m), v=_p(v), step=_p(step), beta1=beta1, beta2=beta2, eps=eps)
+
+
 def grad_clip(g, max_norm, gscale, stats, taint=None):
     """torch.nn.utils.clip_grad_norm_(max_norm, norm_type=2) on the averaged flat gradient gscale * g, in place on `g` (which stays the
     un-averaged sum: the update behind it applies gscale).  `stats`: 4 fp32 device words -- [0] the norm and [1] the coefficient of this

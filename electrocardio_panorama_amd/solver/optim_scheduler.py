@@ -8,6 +8,9 @@ gradient buffer per step (data-parallel training, one process per GPU; SURVEY.md
 decoupled), SOLVER.nesterov the first, and SOLVER.no_decay exempts tensors by name inside the one flat launch (decay_runs).
 SOLVER.ema_decay keeps an exponential moving average of the flat parameters inside that same launch (nef_update_ema): ema_state_dict,
 load_ema_state_dict and the ema_weights() context are its surface.
+'lars' / 'lamb' return FusedLARS / FusedLAMB: the layer-wise trust ratios of large-batch training on the same machinery (nef_update_trust:
+one norm pair per parameter tensor by a deterministic segmented reduction, then the update), with SOLVER.trust_coef, SOLVER.trust_eps and
+SOLVER.trust_exempt (tensors whose ratio stays 1).
 DataParallelAdam (torch Adam behind a separate all-reduce) is kept as the unfused comparison."""
 import contextlib
 import fnmatch
@@ -47,6 +50,26 @@ def decay_runs(names, sizes, patterns):
     if all(m == 1.0 for m in muls):
         return [], []
     return ends, muls
+
+
+MAX_SEGS = 256      # NEF_TRUST_MAX_SEGS (include/nefnet_hip.h): segments of one nef_update_trust call
+
+
+def trust_segments(names, sizes, no_decay, trust_exempt):
+    """The segment table of nef_update_trust for tensors laid out one behind the other: one segment per non-empty tensor, nothing
+    merged (a trust ratio belongs to ONE tensor).  `names[i]` (None: unnamed, never exempt from anything) holds `sizes[i]` elements; its
+    decay multiplier is 0 when it matches one of the fnmatch patterns `no_decay`, else 1, and it adapts (1) unless it matches one of
+    `trust_exempt` (0: its ratio is 1).  Returns (ends, wd_muls, adapts): the exclusive end of every segment in flat order and its two
+    numbers."""
+    ends, wd_muls, adapts, off = [], [], [], 0
+    for name, k in zip(names, sizes):
+        if k <= 0:
+            continue
+        off += int(k)
+        ends.append(off)
+        wd_muls.append(0.0 if name is not None and any(fnmatch.fnmatchcase(name, pat) for pat in no_decay) else 1.0)
+        adapts.append(0.0 if name is not None and any(fnmatch.fnmatchcase(name, pat) for pat in trust_exempt) else 1.0)
+    return ends, wd_muls, adapts
 
 
 class _FusedFlat(torch.optim.Optimizer):
@@ -501,6 +524,120 @@ class FusedAdamW(FusedAdam):
             raise NotImplementedError("FusedAdamW implements amsgrad=False, maximize=False, decoupled weight_decay")
 
 
+class _TrustMixin:
+    """What FusedLARS and FusedLAMB share: the segment table (one segment per live tensor), the ratio table and the stats words of
+    ops.update_lars / ops.update_lamb, built with the flat buffers -- before any capture, because a tensor made inside a capture belongs
+    to the graph.  `trust_exempt`: fnmatch patterns on a parameter's `_nef_name`, an attribute like no_decay."""
+
+    def _trust_init(self, trust_exempt):
+        if isinstance(trust_exempt, str):
+            trust_exempt = (trust_exempt,)
+        self.trust_exempt = tuple(str(pat) for pat in trust_exempt)
+        self._trust_names = {}      # group index -> the segments' names (kept out of _flat: the graphed step clones every tensor in there)
+
+    @staticmethod
+    def _check_trust(trust_coef, trust_eps):
+        if not 0.0 <= trust_coef:      # (NaN fails the comparison too)
+            raise ValueError(f"Invalid trust_coef value: {trust_coef}")
+        if not 0.0 <= trust_eps:
+            raise ValueError(f"Invalid trust_eps value: {trust_eps}")
+
+    def _build(self, gi, live):
+        ends, wd_muls, adapts = trust_segments([getattr(p, "_nef_name", None) for p in live], [p.numel() for p in live], self.no_decay,
+                                               self.trust_exempt)
+        if len(ends) > MAX_SEGS:
+            raise ValueError(f"{len(ends)} live parameter tensors; one trust-ratio update takes {MAX_SEGS} segments")
+        super()._build(gi, live)
+        fl, dev = self._flat[gi], live[0].device
+        fl.pop("run_end", None), fl.pop("run_mul", None)      # the decay multipliers travel per segment
+        fl["seg_end"] = torch.tensor(ends, device=dev, dtype=torch.int64)
+        fl["seg_wd_mul"] = torch.tensor(wd_muls, device=dev, dtype=torch.float32)
+        fl["seg_adapt"] = torch.tensor(adapts, device=dev, dtype=torch.float32)
+        fl["ratio"] = torch.ones(len(ends), device=dev, dtype=torch.float32)
+        # [smallest, largest ratio over the adapted tensors, steps updated, steps skipped for non-finite norms]
+        fl["trust_stats"] = torch.tensor([1.0, 1.0, 0.0, 0.0], device=dev, dtype=torch.float32)
+        self._trust_names[gi] = [getattr(p, "_nef_name", None) or f"param {i}" for i, p in enumerate(live) if p.numel() > 0]
+
+    @staticmethod
+    def _segs(fl):
+        return fl["seg_end"], fl["seg_wd_mul"], fl["seg_adapt"]
+
+    @property
+    def trust_stats(self):
+        """The 4 device words of the first built group; None before the first step."""
+        for _, fl in sorted(self._flat.items()):
+            return fl["trust_stats"]
+        return None
+
+    def trust_ratios(self):
+        """name -> the trust ratio the last updating step applied to that tensor (1.0: exempt, or a zero norm); empty before the first
+        step.  One synchronisation, on demand."""
+        out = OrderedDict()
+        for gi, fl in sorted(self._flat.items()):
+            out.update(zip(self._trust_names[gi], (float(q) for q in fl["ratio"].tolist())))
+        return out
+
+
+class FusedLARS(_TrustMixin, FusedSGD):
+    """LARS on FusedSGD's machinery (You, Gitman, Ginsburg 2017): momentum SGD whose decayed gradient of every parameter tensor is
+    multiplied by q = trust_coef * ||p|| / (||g|| + wd * ||p|| + trust_eps) -- norms per tensor, on the averaged (and clipped) gradient;
+    q = 1 for the tensors matching `trust_exempt` and where a norm is zero.  One nef_update_trust call per parameter group.  The state is
+    torch.optim.SGD's (momentum_buffer); `trust_coef` and `trust_eps` are group keys."""
+
+    def __init__(self, params, lr, momentum=0.9, dampening=0, weight_decay=0, nesterov=False, trust_coef=1e-3, trust_eps=1e-8, *,
+                 no_decay=(), trust_exempt=(), max_grad_norm=0.0, ema_decay=0.0, ema_warmup=False):
+        self._check_trust(trust_coef, trust_eps)
+        self._trust_init(trust_exempt)
+        super().__init__(params, lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
+                         no_decay=no_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup)
+        for group in self.param_groups:
+            group.setdefault("trust_coef", float(trust_coef))
+            group.setdefault("trust_eps", float(trust_eps))
+        self.defaults.update(trust_coef=float(trust_coef), trust_eps=float(trust_eps))
+
+    def _captured_scalars(self, group):
+        return super()._captured_scalars(group) + (float(group.get("trust_coef", self.defaults["trust_coef"])),
+                                                   float(group.get("trust_eps", self.defaults["trust_eps"])))
+
+    def _device_update(self, fl, group, gscale, skip=None, lr_dev=None):
+        self._check_group(group)
+        sc = self._captured_scalars(group)
+        mu, wd, nesterov = sc[:3]
+        coef, teps = sc[-2:]
+        self._check_trust(coef, teps)
+        ops.update_lars(fl["p"], fl["g"], fl["buf"], float(group["lr"]), mu, gscale, self._segs(fl), fl["ratio"], fl["trust_stats"],
+                        trust_coef=coef, trust_eps=teps, weight_decay=wd, nesterov=nesterov, skip=skip, lr_dev=lr_dev, taint=skip,
+                        ema=self._ema(fl))
+
+
+class FusedLAMB(_TrustMixin, FusedAdam):
+    """LAMB on FusedAdam's machinery (You et al. 2020): Adam's direction u = m_hat / (sqrt(v_hat) + eps) + wd * p, scaled per parameter
+    tensor by q = ||p|| / ||u|| (1 for the tensors matching `trust_exempt` and where a norm is zero): p -= lr * q * u.  One
+    nef_update_trust call per parameter group.  The state is torch.optim.Adam's (step, exp_avg, exp_avg_sq); `trust_coef` and `trust_eps`
+    are group keys as in FusedLARS (LAMB's ratio uses neither)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0, amsgrad=False, trust_coef=1e-3, trust_eps=1e-8, *,
+                 maximize=False, no_decay=(), trust_exempt=(), max_grad_norm=0.0, ema_decay=0.0, ema_warmup=False):
+        self._check_trust(trust_coef, trust_eps)
+        self._trust_init(trust_exempt)
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
+                         no_decay=no_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup)
+        for group in self.param_groups:
+            group.setdefault("trust_coef", float(trust_coef))
+            group.setdefault("trust_eps", float(trust_eps))
+        self.defaults.update(trust_coef=float(trust_coef), trust_eps=float(trust_eps))
+
+    def _captured_scalars(self, group):
+        return super()._captured_scalars(group) + (float(group.get("trust_coef", self.defaults["trust_coef"])),
+                                                   float(group.get("trust_eps", self.defaults["trust_eps"])))
+
+    def _device_update(self, fl, group, gscale, skip=None, lr_dev=None):
+        self._check_group(group)
+        b1, b2, eps, wd = self._captured_scalars(group)[:4]
+        ops.update_lamb(fl["p"], fl["g"], fl["m"], fl["v"], fl["step"], float(group["lr"]), b1, b2, eps, wd, gscale, self._segs(fl),
+                        fl["ratio"], fl["trust_stats"], skip=skip, lr_dev=lr_dev, taint=skip, ema=self._ema(fl))
+
+
 class DataParallelAdam(Adam):
     """torch Adam (the reference's other optimiser choice, optim_scheduler.py:8) whose step first averages the
     gradients over the data-parallel ranks with the same single flat all-reduce FusedSGD uses -- without it the
@@ -538,6 +675,13 @@ def get_optimizer(cfg, model_params):
     elif optim_name == 'sgd':
         return FusedSGD(model_params, lr=cfg.SOLVER.lr, momentum=0.9, weight_decay=wd, nesterov=bool(cfg.SOLVER.get('nesterov', False)),
                         no_decay=no_decay, max_grad_norm=clip, **ema)
+    elif optim_name in ('lars', 'lamb'):
+        trust = dict(trust_coef=float(cfg.SOLVER.get('trust_coef', 1e-3)), trust_eps=float(cfg.SOLVER.get('trust_eps', 1e-8)),
+                     trust_exempt=tuple(cfg.SOLVER.get('trust_exempt', None) or ()))
+        if optim_name == 'lars':
+            return FusedLARS(model_params, lr=cfg.SOLVER.lr, momentum=0.9, weight_decay=wd, nesterov=bool(cfg.SOLVER.get('nesterov', False)),
+                             no_decay=no_decay, max_grad_norm=clip, **trust, **ema)
+        return FusedLAMB(model_params, lr=cfg.SOLVER.lr, weight_decay=wd, no_decay=no_decay, max_grad_norm=clip, **trust, **ema)
 
 
 def get_lr_scheduler(cfg, optim=None):

@@ -183,6 +183,9 @@ class Solver:
                 names.append('train_grad_norm')
                 msg += '\ngrad_norm: {} (max_norm {}): {} of {} steps clipped, {} skipped for a non-finite norm'.format(
                     scalars[-1], optimizer.max_grad_norm, self.last_clip_counts[0], len(self.last_grad_norms), self.last_clip_counts[1])
+            if getattr(self, 'last_trust_stats', None) is not None:      # SOLVER.optim is lars or lamb
+                msg += '\ntrust ratio: min {:.3e}, max {:.3e} over the adapted tensors; {} steps skipped for non-finite norms'.format(
+                    *self.last_trust_stats)
             if self.summary_writer is not None:
                 self.write_tensorboardx(scalars, names, epoch)
             print(msg)
@@ -311,6 +314,9 @@ class Solver:
         clip_s = _HostSink() if phase == 'train' and getattr(optim, 'max_grad_norm', 0.0) > 0 else None
         # the optimiser's counters (steps clipped, steps with a non-finite norm) before this epoch: nothing is in flight here
         clip_0 = optim.clip_stats[2:].tolist() if clip_s is not None and optim.clip_stats is not None else [0.0, 0.0]
+        # SOLVER.optim lars / lamb: the count of steps skipped for non-finite norms before this epoch
+        trust = phase == 'train' and hasattr(optim, 'trust_ratios')
+        trust_0 = float(optim.trust_stats[3].item()) if trust and optim.trust_stats is not None else 0.0
         for meta in dl:
             source_data, rois, input_theta, target_view, target_theta, noise = self._to_device(meta)
             rest_theta = torch.as_tensor(meta['rest_theta']).to(self.device) if 'rest_theta' in meta else None
@@ -360,6 +366,13 @@ class Solver:
                 self.last_grad_norms = [a.tolist() for a in clip_s.arrays()]
                 clip_1 = optim.clip_stats[2:].tolist()
                 self.last_clip_counts = (int(clip_1[0] - clip_0[0]), int(clip_1[1] - clip_0[1]))
+            # trust ratios (SOLVER.optim lars / lamb) of the last updating step: name -> q, (min, max) over the adapted tensors and this
+            # epoch's steps skipped for non-finite norms -- read once, here, where the device has been waited for anyway
+            self.last_trust_ratios, self.last_trust_stats = {}, None
+            if trust and optim.trust_stats is not None:
+                st = optim.trust_stats.tolist()
+                self.last_trust_ratios = optim.trust_ratios()
+                self.last_trust_stats = (st[0], st[1], int(st[3] - trust_0))
             return losses, gt_s.rows(), pred_s.rows(), in_s.rows(), [], rois_s.rows()
         mertics_all, mertics_gen_singlelead = [], []
         for ps, ss in zip(psnr_s.arrays(), ssim_s.arrays()):

@@ -621,6 +621,58 @@ typedef struct nef_ema_args {
 int nef_update_ema(const nef_update_args* a, const nef_ema_args* e, nef_stream_t stream);
 /* sizeof(nef_ema_args) as the library was built. */
 size_t nef_ema_args_bytes(void);
+/* Layer-wise trust ratios: LARS (a->rule 0, the SGD family) and LAMB (a->rule 1, the Adam family) over the flat buffers of
+ * nef_update_args, with one norm pair per SEGMENT (parameter tensor) -- no counterpart in the reference or in torch.optim, so the
+ * semantics are written out here.  Segment s is [beg_s, end_s) in flat order (beg_0 = 0, beg_s = seg_end[s - 1]) and carries
+ * seg_wd_mul[s] >= 0 and seg_adapt[s] (0 = exempt from the ratio, anything else = adapted).  g' = g * gscale (behind the clipping when
+ * nef_grad_clip ran in front), wd_s = weight_decay * seg_wd_mul[s]; norms are 2-norms over the segment, fp64 sums of the squares of
+ * the fp32 values, in a fixed order (no atomics): the same buffers give the same bits eagerly, under hipGraph replay and on every rank.
+ *   rule 0, LARS (momentum SGD, dampening 0, optional Nesterov): wn = ||p_s||, gn = ||g'_s||;
+ *           q_s = trust_coef * wn / (gn + wd_s * wn + trust_eps) when seg_adapt[s], wn > 0 and gn > 0, else 1 -- formed in fp64, rounded
+ *           to fp32 once; d = (g' + wd_s * p) * q_s; buf = mu * buf + d; p -= lr * (nesterov ? d + mu * buf : buf).  With every q_s = 1
+ *           these are rule 0's bits of nef_update under a run table with the same multipliers.
+ *   rule 1, LAMB: m = lerp(m, g', 1 - beta1); v = beta2 * v + (1 - beta2) * g'^2; t = *step + 1, bc1 = 1 - beta1^t, bc2 = 1 - beta2^t
+ *           in fp64 as in nef_adam; u = (m / bc1) / (sqrt(v / bc2) + eps) + wd_s * p; wn = ||p_s||, un = ||u_s||; q_s = wn / un when
+ *           seg_adapt[s], wn > 0 and un > 0, else 1; p -= lr * q_s * u; *step advances.
+ * Three stream-ordered launches and a one-lane one (rule 1, or with the average): a read-only norm pass (rule 1: it forms the new m,
+ * v and u in registers and stores none of them; the update recomputes them from the old state in the same operation order, so the
+ * u applied is the u measured), a one-block finish (ratio, stats, taint) and the update.
+ *   ratio[s] = q_s of this call;  stats[0] / stats[1] = the smallest / largest q_s over the adapted segments (1 when none adapts);
+ *   stats[2] += 1 per call that updated;  stats[3] += 1 per call whose norms were not finite.
+ * Norms that are not finite (in any segment) skip the step: stats[3] and, if given, taint[0] advance by 1, ratio[] and stats[0..2]
+ * stay as they were, and p, every state buffer, *step, the average and its count keep their bits; `skipped` counts the step once.
+ * A positive skip word -- or a positive taint[0] -- on entry does the same without touching ratio, stats or taint.  lr_dev replaces lr.
+ * e: NULL, or the moving average of nef_update_ema, kept inside the update launch; p and the state get the same bits with and without.
+ * a->run_end / run_mul are not read: a->n_runs must be 0 (NEF_E_SHAPE), the multipliers travel per segment.  a->rule > 1:
+ * NEF_E_UNSUPPORTED.  t, seg_end, seg_wd_mul, seg_adapt, ratio, stats or ws NULL: NEF_E_NULL; n_segs outside 1 .. NEF_TRUST_MAX_SEGS,
+ * a negative (or NaN) trust_coef / trust_eps / weight_decay: NEF_E_SHAPE; ws_bytes below nef_update_trust_ws_bytes: NEF_E_WORKSPACE.
+ * Every check sits in front of the first launch.
+ * THE SEGMENT TABLE IS THE CALLER'S DUTY, as the run table of nef_update is: this entry cannot read device memory, so nothing checks
+ * that seg_end is ascending, that its last element equals n or that seg_wd_mul is non-negative.  (Elements behind the last end belong
+ * to no norm and are updated with the last segment's factors; the lookups never leave the n_segs entries.)
+ * Capturable: nothing is read by the host, nothing is allocated. */
+#define NEF_TRUST_MAX_SEGS 256 /* segments of one call (the table is staged in LDS; the finish gives every segment one lane) */
+typedef struct nef_trust_args {
+    const int64_t* seg_end;        /* [n_segs] device int64: the exclusive end of each segment in flat order, ascending, the last one = n */
+    const float* seg_wd_mul;       /* [n_segs] device floats >= 0: the decay multiplier of the segment */
+    const float* seg_adapt;        /* [n_segs] device floats: 0 = q_s is 1 (exempt), else the segment takes its trust ratio */
+    float* ratio;                  /* [n_segs] caller-owned device table, out: the q_s of this call */
+    float* stats;                  /* 4 caller-owned device words, see above */
+    float* taint;                  /* NULL, or the device word in front of the flat gradients (the skip word of the update) */
+    void* ws;                      /* device workspace, 8-byte aligned */
+    size_t ws_bytes;
+    float trust_coef;              /* rule 0: LARS's coefficient (>= 0).  Rule 1: unused */
+    float trust_eps;               /* rule 0: added to LARS's denominator (>= 0).  Rule 1: unused */
+    int32_t n_segs;                /* 1 .. NEF_TRUST_MAX_SEGS */
+    int32_t reserved0;             /* 0 */
+} nef_trust_args;
+
+int nef_update_trust(const nef_update_args* a, const nef_trust_args* t, const nef_ema_args* e /* NULL: no average */,
+                     nef_stream_t stream);
+/* The workspace of one call over n elements in n_segs segments: the fp64 partial pairs of a grid that depends on n alone. */
+size_t nef_update_trust_ws_bytes(int64_t n, int32_t n_segs);
+/* sizeof(nef_trust_args) as the library was built. */
+size_t nef_trust_args_bytes(void);
 /* Global gradient-norm clipping over a flat buffer: torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2) on the averaged
  * gradient gscale * g (no counterpart in the reference).  total = gscale * sqrt(sum g[i]^2), coef = min(1, max_norm / (total + 1e-6)),
  * g[i] *= coef; g stays the un-averaged sum, so the update launch behind this call still applies gscale.  The sum is deterministic:

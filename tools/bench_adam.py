@@ -4,6 +4,7 @@
     python tools/bench_adam.py --clip MAX_NORM [--parent-tree DIR] [--out profiles/clip_bench_line.json]
     python tools/bench_adam.py --weight-decay X [--no-decay PATTERN...] [--parent-tree DIR] [--out profiles/wd_bench_line.json]
     python tools/bench_adam.py --ema D [--parent-tree DIR] [--out profiles/ema_bench_line.json]
+    python tools/bench_adam.py --trust lars|lamb [--parent-tree DIR] [--out profiles/r11_trust_bench_line.json]
 
 Each measurement runs in a child process of its own under `timeout` (nothing more is started once one fails), `--reps` rounds of
 the three children; every figure is reported as [min, median, max] over the rounds:
@@ -31,7 +32,13 @@ the entry it stands beside (nef_sgd_momentum, nef_adam) in the same process: sam
 (B=32, L=512): per round and shape the graphed FusedSGD step with the average off (sgd-graph) and with ema_decay = D (sgd-graph-ema), and
 -- with --parent-tree DIR -- DIR's own sgd-graph step at that shape (DIR/tools/bench_adam.py's `child` function, called in a fresh
 process).  The config-2 EMA child also times the update launch alone on the flat buffers, cold as above: nef_update_ema beside nef_update
-in one process (rule 0, no table: five fp32 streams per parameter against seven)."""
+in one process (rule 0, no table: five fp32 streams per parameter against seven).
+
+--trust lars|lamb measures the layer-wise trust ratios (nef_update_trust), at the same two shapes: per round and shape the graphed step with
+FusedSGD / FusedAdam (sgd-graph for lars, adam-graph for lamb), the graphed step with FusedLARS / FusedLAMB (lars-graph / lamb-graph: one
+segment per live tensor, nothing exempt), and -- with --parent-tree DIR -- DIR's own sgd-graph / adam-graph step.  The config-2 trust child
+also times the entry's launches alone on the flat buffers with the model's real segment table, cold as above, beside nef_update (same rule,
+no table) in one process.  Writes profiles/r11_trust_bench_line.json unless --out says otherwise."""
 import argparse
 import json
 import os
@@ -46,6 +53,7 @@ MODES = {"sgd-graph": 900, "adam-graph": 900, "adam-eager": 1200}      # child -
 CLIP_MODES = {"sgd-graph": 900, "sgd-graph-clip": 900}
 WD_MODES = {"sgd-graph": 900, "sgd-graph-wd": 900, "adam-graph": 900, "adamw-graph": 900}
 EMA_MODES = {"sgd-graph": 900, "sgd-graph-ema": 900}
+TRUST_BASE = {"lars": "sgd-graph", "lamb": "adam-graph"}
 EMA_SHAPES = {"config2": (256, 5000), "reference": (32, 512)}      # (B, L) at 3 leads
 
 
@@ -97,6 +105,10 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
         optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9, ema_decay=ema)
     elif mode == "adam-graph":
         optim = FusedAdam(model.parameters(), lr=1e-3)
+    elif mode == "lars-graph":
+        optim = optim_scheduler.FusedLARS(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9)
+    elif mode == "lamb-graph":
+        optim = optim_scheduler.FusedLAMB(model.parameters(), lr=1e-3)
     elif mode == "adamw-graph":
         optim = optim_scheduler.FusedAdamW(model.parameters(), lr=1e-3, weight_decay=wd, no_decay=no_decay)
     else:
@@ -137,6 +149,25 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
         res.update(ema_decay=ema, ema_updates=float(fl["ema_n"].item()), update_params=n, nef_update_cold_ms=round(old_ms, 4),
                    nef_update_ema_cold_ms=round(new_ms, 4), nef_update_cold_GBps=round(5 * 4 * n / (old_ms * 1e-3) / 1e9, 1),
                    nef_update_ema_cold_GBps=round(7 * 4 * n / (new_ms * 1e-3) / 1e9, 1))
+    if mode in ("lars-graph", "lamb-graph") and (B, L) == EMA_SHAPES["config2"]:
+        fl = optim._flat[0]
+        n, segs = fl["p"].numel(), optim._segs(fl)
+        ratio, stats = fl["ratio"].clone(), fl["trust_stats"].clone()
+        if mode == "lars-graph":
+            p, g, buf = (fl[k].clone() for k in ("p", "g", "buf"))
+            old_ms, new_ms = cold_ms([lambda: ops.update_sgd(p, g, buf, 0.1, 0.9, 1.0),
+                                      lambda: ops.update_lars(p, g, buf, 0.1, 0.9, 1.0, segs, ratio, stats)], dev)
+            old_streams, new_streams = 5, 7
+        else:
+            p, g, m, v, s = (fl[k].clone() for k in ("p", "g", "m", "v", "step"))
+            old_ms, new_ms = cold_ms([lambda: ops.update_adam(p, g, m, v, s, 1e-3, 0.9, 0.999, 1e-6, 0.0, 1.0),
+                                      lambda: ops.update_lamb(p, g, m, v, s, 1e-3, 0.9, 0.999, 1e-6, 0.0, 1.0, segs, ratio, stats)], dev)
+            old_streams, new_streams = 7, 11
+        q = [x for x in fl["ratio"].tolist()]
+        res.update(segments=int(segs[0].numel()), update_params=n, ratio_min=min(q), ratio_max=max(q),
+                   steps_skipped_non_finite=int(fl["trust_stats"][3].item()), nef_update_cold_ms=round(old_ms, 4),
+                   nef_update_trust_cold_ms=round(new_ms, 4), nef_update_cold_GBps=round(old_streams * 4 * n / (old_ms * 1e-3) / 1e9, 1),
+                   nef_update_trust_cold_GBps=round(new_streams * 4 * n / (new_ms * 1e-3) / 1e9, 1))
     if mode == "adam-graph":
         fl = optim._flat[0]
         p, g, m, v, s = (fl[k].clone() for k in ("p", "g", "m", "v", "step"))
@@ -271,6 +302,60 @@ def ema_rounds(args):
             f.write(line + "\n")
 
 
+def trust_rounds(args):
+    """--trust lars|lamb: `--reps` alternating rounds of fresh children per shape (see the module docstring); prints and writes one JSON
+    line."""
+    base, new = TRUST_BASE[args.trust], args.trust + "-graph"
+    modes = dict({base: 900, new: 900}, **({"parent": 900} if args.parent_tree else {}))
+    results = {(shape, mode): [] for shape in EMA_SHAPES for mode in modes}
+    for rnd in range(args.reps):
+        order = list(modes) if rnd % 2 == 0 else list(reversed(modes))
+        for shape, (B, L) in EMA_SHAPES.items():
+            for mode in order:
+                if mode == "parent":
+                    # the parent's tool may lack --shape: its `child` function is called directly, in a fresh process of its own tree
+                    tree = os.path.abspath(args.parent_tree)
+                    code = ("import importlib.util as u; s = u.spec_from_file_location('parent_bench', %r); m = u.module_from_spec(s); "
+                            "s.loader.exec_module(m); m.child(%r, %d, %d, B=%d, L=%d)"
+                            % (os.path.join(tree, "tools", "bench_adam.py"), base, args.steps, args.warmup, B, L))
+                    cmd = ["timeout", "-k", "10", str(modes[mode]), sys.executable, "-c", code]
+                else:
+                    tree = ROOT
+                    cmd = ["timeout", "-k", "10", str(modes[mode]), sys.executable, os.path.join(ROOT, "tools", "bench_adam.py"), "--child", mode,
+                           "--steps", str(args.steps), "--warmup", str(args.warmup), "--shape", str(B), str(L)]
+                results[(shape, mode)].append(run_child(cmd, tree, mode))
+                sys.stderr.write(f"round {rnd + 1}/{args.reps} {shape} {mode}: {results[(shape, mode)][-1]['ms_per_step']} ms/step\n")
+                sys.stderr.flush()
+
+    def spread(shape, mode, key):
+        v = sorted(x[key] for x in results[(shape, mode)])
+        return [v[0], v[len(v) // 2], v[-1]]
+
+    t2 = results[("config2", new)][0]
+    out = {"metric": "ms per train step, graphed: %s beside %s ([min, median, max] over rounds)" % (new, base), "rounds": args.reps,
+           "trust": args.trust, "shapes": {k: "B=%d, 3 leads, L=%d, one GPU, dropout on" % v for k, v in EMA_SHAPES.items()}}
+    for shape in EMA_SHAPES:
+        out[shape + "_" + base.replace("-", "_") + "_ms"] = spread(shape, base, "ms_per_step")
+        out[shape + "_" + new.replace("-", "_") + "_ms"] = spread(shape, new, "ms_per_step")
+        if args.parent_tree:
+            out[shape + "_parent_" + base.replace("-", "_") + "_ms"] = par = spread(shape, "parent", "ms_per_step")
+            # the bar: the trust median <= the parent's median of the plain optimiser + 0.3 ms
+            out[shape + "_trust_median_minus_parent_median_ms"] = round(out[shape + "_" + new.replace("-", "_") + "_ms"][1] - par[1], 3)
+    out.update(update_params=t2["update_params"], segments=t2["segments"], ratio_min=t2["ratio_min"], ratio_max=t2["ratio_max"],
+               nef_update_cold_ms=spread("config2", new, "nef_update_cold_ms"),
+               nef_update_trust_cold_ms=spread("config2", new, "nef_update_trust_cold_ms"),
+               nef_update_cold_GBps=spread("config2", new, "nef_update_cold_GBps"),
+               nef_update_trust_cold_GBps=spread("config2", new, "nef_update_trust_cold_GBps"),
+               update_note="the entry's launches alone on the flat buffers with the model's segment table, nef_update_trust alternating with "
+                           "nef_update (same rule, no table) in one process; cold = a 512 MiB buffer written before each call; bytes counted: "
+                           "lars 2 + 5 fp32 streams per parameter against 5, lamb 4 + 7 against 7",
+               steps=args.steps, warmup=args.warmup)
+    line = json.dumps(out)
+    print(line)
+    with open(args.out or os.path.join(ROOT, "profiles", "r11_trust_bench_line.json"), "w") as f:
+        f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
@@ -281,10 +366,11 @@ def main():
     ap.add_argument("--weight-decay", type=float, default=None, metavar="X", help="measure weight decay in the update launch (see above)")
     ap.add_argument("--no-decay", nargs="*", default=[], metavar="PATTERN", help="with --weight-decay: fnmatch patterns of exempt tensors")
     ap.add_argument("--ema", type=float, default=None, metavar="D", help="measure the EMA of the weights in the update launch (see above)")
+    ap.add_argument("--trust", choices=sorted(TRUST_BASE), default=None, help="measure the layer-wise trust ratios (see above)")
     ap.add_argument("--shape", type=int, nargs=2, default=(256, 5000), metavar=("B", "L"), help="with --child: batch size and length")
     ap.add_argument("--parent-tree", default=None,
                     help="with --clip / --weight-decay / --ema: a built checkout whose own sgd-graph child runs in every round")
-    ap.add_argument("--child", choices=sorted({**MODES, **CLIP_MODES, **WD_MODES, **EMA_MODES}), default=None)
+    ap.add_argument("--child", choices=sorted({**MODES, **CLIP_MODES, **WD_MODES, **EMA_MODES, "lars-graph": 900, "lamb-graph": 900}), default=None)
     args = ap.parse_args()
     if args.child == "sgd-graph-ema" and not (args.ema is not None and 0.0 < args.ema < 1.0):
         ap.error("--child sgd-graph-ema needs --ema D in (0, 1)")
@@ -296,14 +382,18 @@ def main():
         ap.error(f"--child {args.child} needs --weight-decay X")
     if args.clip is not None and args.weight_decay is not None:
         ap.error("--clip and --weight-decay are two measurements")
-    if args.parent_tree and args.clip is None and args.weight_decay is None and args.ema is None:
-        ap.error("--parent-tree goes with --clip, --weight-decay or --ema")
+    if args.trust is not None and (args.clip is not None or args.weight_decay is not None or args.ema is not None):
+        ap.error("--trust is a measurement of its own")
+    if args.parent_tree and args.clip is None and args.weight_decay is None and args.ema is None and args.trust is None:
+        ap.error("--parent-tree goes with --clip, --weight-decay, --ema or --trust")
     if args.child:
         return child(args.child, args.steps if args.child != "adam-eager" else max(3, args.steps // 2), args.warmup,
                      B=args.shape[0], L=args.shape[1], clip=args.clip or 0.0, wd=args.weight_decay or 0.0,
                      no_decay=tuple(args.no_decay), ema=args.ema or 0.0)
     if args.ema is not None:
         return ema_rounds(args)
+    if args.trust is not None:
+        return trust_rounds(args)
     modes = dict(MODES)
     if args.clip is not None:
         modes = dict(CLIP_MODES, **({"parent": 900} if args.parent_tree else {}))
