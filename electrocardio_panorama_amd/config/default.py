@@ -78,6 +78,12 @@ _DEFAULTS = {
         # fnmatch patterns on the state_dict keys of the parameters whose trust ratio stays 1 (they step at the plain learning rate),
         # e.g. ['*.bias', '*.double_conv.[14].*'] for the biases and the BatchNorm affine parameters
         "trust_exempt": [],
+        # gradient accumulation on the device: an update every accum_steps train batches (micro-batches).  Every micro-batch runs forward,
+        # loss and backward as a step does -- its own BatchNorm statistics, Standin draws, dropout seed and loss row -- and its gradients
+        # are summed in fp32 into the one flat gradient buffer (nef_flatten_acc); taint word, all-reduce, clipping and the update run once
+        # per window on the mean over its micro-batches (and ranks), in the eager and the graphed step.  A window never crosses an epoch:
+        # the last, incomplete one is flushed on the micro-batches it has.  1 = off: the launches and graphs are what they were
+        "accum_steps": 1,
     },
 }
 

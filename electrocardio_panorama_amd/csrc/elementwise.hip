@@ -1879,6 +1879,34 @@ __global__ __launch_bounds__(256) void flatten_kernel(FlatTable t, float* __rest
     }
 }
 
+// flatten_acc: flatten_kernel's shape with an accumulate form -- out[off_k + i] = src_k[i] or out[off_k + i] += src_k[i] (gradient
+// accumulation: the micro-batches of a window summed in fp32 into the one flat gradient buffer).  `acc_dev` (or NULL) is a device word
+// that replaces `acc` at run time, so one captured launch serves the first and the later micro-batches of a window.  The choice is
+// uniform over the launch, and the assign form never reads `out`.  One writer per element, plain loads and stores, no atomics.
+__global__ __launch_bounds__(256) void flatten_acc_kernel(FlatTable t, float* __restrict__ out, int acc, const int32_t* __restrict__ acc_dev) {
+    const FlatDesc& d = t.d[blockIdx.y];
+    const float* __restrict__ src = d.src;
+    float* __restrict__ dst = out + d.off;
+    const int64_t n = d.n;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool add = (acc_dev ? acc_dev[0] : acc) != 0;
+    const bool vec = (((uintptr_t)src | (uintptr_t)dst) & 15) == 0;
+    const int64_t n4 = vec ? n >> 2 : 0;
+    if (add) {
+        for (int64_t i = i0; i < n4; i += stride) {
+            const float4 s = reinterpret_cast<const float4*>(src)[i];
+            float4 o = reinterpret_cast<float4*>(dst)[i];
+            o.x += s.x, o.y += s.y, o.z += s.z, o.w += s.w;
+            reinterpret_cast<float4*>(dst)[i] = o;
+        }
+        for (int64_t i = (n4 << 2) + i0; i < n; i += stride) dst[i] += src[i];
+    } else {
+        for (int64_t i = i0; i < n4; i += stride) reinterpret_cast<float4*>(dst)[i] = reinterpret_cast<const float4*>(src)[i];
+        for (int64_t i = (n4 << 2) + i0; i < n; i += stride) dst[i] = src[i];
+    }
+}
+
 // regroup_halves: w [Co][2 Cih][K] <-> grouped [2 Co][Cih][K] (group = input-channel half; engine._regroup_halves / _ungroup_halves)
 __global__ __launch_bounds__(256) void regroup_halves_kernel(const float* __restrict__ src, float* __restrict__ dst, int Co, int Cih,
                                                             int K, int inverse) {
@@ -3084,6 +3112,35 @@ int nef_flatten(const float* const* srcs, const int64_t* sizes, int n, float* ou
         if (gx > 128) gx = 128;
         if (gx < 1) gx = 1;
         hipLaunchKernelGGL(flatten_kernel, dim3((unsigned)gx, (unsigned)m), dim3(256), 0, NEF_ST, t, out);
+    }
+    return nef_launch_status();
+}
+
+int nef_flatten_acc(const float* const* srcs, const int64_t* sizes, int n, float* out, int accumulate, const int32_t* accumulate_dev,
+                    nef_stream_t stream) {
+    NEF_ENTER();
+    NEF_REQUIRE((srcs && sizes && out) || n <= 0, NEF_E_NULL);
+    NEF_REQUIRE(n >= 0 && (accumulate == 0 || accumulate == 1), NEF_E_SHAPE);
+    // every check before the first launch: a bad entry behind the 64th tensor must not leave a half-written buffer
+    for (int i = 0; i < n; ++i) {
+        NEF_REQUIRE(sizes[i] >= 0, NEF_E_SHAPE);
+        NEF_REQUIRE(srcs[i] || sizes[i] == 0, NEF_E_NULL);
+    }
+    if (n == 0) return NEF_OK;
+    int64_t off = 0;
+    for (int i0 = 0; i0 < n; i0 += FLAT_MAX) {
+        FlatTable t;
+        const int m = n - i0 < FLAT_MAX ? n - i0 : FLAT_MAX;
+        int64_t biggest = 1;
+        for (int i = 0; i < m; ++i) {
+            t.d[i] = FlatDesc{srcs[i0 + i], sizes[i0 + i], off};
+            off += sizes[i0 + i];
+            if (sizes[i0 + i] > biggest) biggest = sizes[i0 + i];
+        }
+        int gx = (int)nef_cdiv(biggest, 256 * 4 * 4);      // as nef_flatten: a grid that depends on the sizes alone
+        if (gx > 128) gx = 128;
+        if (gx < 1) gx = 1;
+        hipLaunchKernelGGL(flatten_acc_kernel, dim3((unsigned)gx, (unsigned)m), dim3(256), 0, NEF_ST, t, out, accumulate, accumulate_dev);
     }
     return nef_launch_status();
 }

@@ -18,6 +18,13 @@ for checkpoints.
 Data parallel (world > 1): the step is captured as TWO graphs cut at the early-bucket point of the backward pass; the all-reduce
 of the bucket that is final there runs between the replays, under the second graph (`_capture_split`; NEF_GRAPH_SPLIT=0 keeps one
 graph and one exposed all-reduce).
+
+Gradient accumulation (the optimiser's accum_steps = K > 1): the per-shape graphs hold forward, backward and the accumulating flatten
+(ops.flatten_into(accumulate_dev=): a device word says "assign" on the first micro-batch of a window and "add" on the later ones, so every
+micro-batch replays the same graph and shapes share the window); the taint word, the all-reduces, the clip and the update are issued
+eagerly behind the window's last replay -- a handful of launches the host queues while the device is still inside the replay, with
+the window's own gscale, which a captured update would have frozen.  The window position is the optimiser's (`_acc_n`), so eager and
+replayed micro-batches mix.  K == 1: nothing of this runs.
 """
 import random
 
@@ -57,6 +64,8 @@ class GraphedTrainStep:
         self.live = None
         self.choice_dev = None
         self.lr_dev = None
+        self.acc_dev = None      # accum_steps > 1: the int32 device word the captured flatten reads (0: assign, 1: add)
+        self._acc_word = None    # ... and what it holds
         self.calls = 0
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         # dp: the step sums its gradients through torch.distributed.  True for more than one rank -- and for a ONE-rank group under the
@@ -130,7 +139,21 @@ class GraphedTrainStep:
         """The optimiser's scalars that the captured launches freeze: those of its update and -- single process, where the clip launches
         sit inside the graph -- its max_grad_norm (data parallel they are issued behind the all-reduces, outside the graphs)."""
         opt = self.optimizer
-        return opt._captured_scalars(opt.param_groups[0]) + (() if self.dp else (float(opt.max_grad_norm),))
+        return opt._captured_scalars(opt.param_groups[0]) + (() if self.dp else (float(opt.max_grad_norm),)) + (
+            (int(opt.accum_steps),) if opt.accum_steps > 1 else ())      # (what the graphs hold differs between K == 1 and K > 1)
+
+    @property
+    def accum(self):
+        """Micro-batches per update: the optimiser's accum_steps (the stepper with private buffers does not accumulate)."""
+        return getattr(self.optimizer, "accum_steps", 1)
+
+    def _into_flat(self, tensors, out):
+        """This backward pass's gradients into (a slice of) the flat gradient buffer: assigned, or -- accumulating -- assigned or added as
+        the window word says when the launch runs."""
+        if self.accum > 1:
+            ops.flatten_into(tensors, out, accumulate_dev=self.acc_dev)
+        else:
+            ops.flatten_into(tensors, out)
 
     def _clip(self):
         """The optimiser's global gradient-norm clipping (its own clip_stats), between the summed gradients and the update; the stepper
@@ -150,7 +173,9 @@ class GraphedTrainStep:
 
     def _body(self):
         grads = self._fwd_bwd()
-        ops.flatten_into([grads[k] for k in self.live], self.flat_g)
+        self._into_flat([grads[k] for k in self.live], self.flat_g)
+        if self.accum > 1:
+            return                             # taint word, clip and update: once per window, behind its last replay (_accum_replay)
         ops.h2_taint(self.flat_g_all[:1])      # this step's clamped split-fp16 launches: the update is skipped (on every rank)
         if not self.dp:
             self._clip()
@@ -174,7 +199,7 @@ class GraphedTrainStep:
                 raise RuntimeError("early gradient bucket is not a suffix of the live parameters")
             named = dict(self.model.named_parameters())
             info["k0"], info["split"] = k0, sum(named[k].numel() for k in self.live[:k0])
-            ops.flatten_into([grads[k] for k in early], self.flat_g[info["split"]:])
+            self._into_flat([grads[k] for k in early], self.flat_g[info["split"]:])
             gA.capture_end()
             gB.capture_begin(pool=gA.pool())
 
@@ -193,8 +218,9 @@ class GraphedTrainStep:
             if "split" not in info:
                 raise RuntimeError("engine.backward never reached its early-bucket point")
             if info["k0"]:
-                ops.flatten_into([grads[k] for k in self.live[:info["k0"]]], self.flat_g[:info["split"]])
-            ops.h2_taint(self.flat_g_all[:1])
+                self._into_flat([grads[k] for k in self.live[:info["k0"]]], self.flat_g[:info["split"]])
+            if self.accum == 1:                # (accumulating: the taint word is taken once per window, behind its last replay)
+                ops.h2_taint(self.flat_g_all[:1])
             gB.capture_end()
         torch.cuda.current_stream().wait_stream(cap)
         self._comm = getattr(self, "_comm", None) or torch.cuda.Stream()
@@ -228,6 +254,8 @@ class GraphedTrainStep:
             self.status = torch.zeros(1, device=dev, dtype=torch.int32)
             self.losses = torch.zeros(4, device=dev, dtype=torch.float32)
             self.lr_dev = torch.full((1,), self.lr, device=dev, dtype=torch.float32)
+        if self.accum > 1 and self.acc_dev is None:
+            self.acc_dev, self._acc_word = torch.zeros(1, device=dev, dtype=torch.int32), 0
         # the probe runs THIS step's inputs, Standin choices and dropout seed (drawn by __call__ before it builds): the split-fp16
         # convs measure their operands in it, and what they measure must be what the eager path measures on the same step
         self._stage(data, in_theta, q_theta, rois, target, noise, draw=False)
@@ -310,6 +338,60 @@ class GraphedTrainStep:
             if getattr(self, "lr_dev", None) is not None:
                 self.lr_dev.fill_(self.lr)
 
+    def flush(self):
+        """Close an incomplete accumulation window (the optimiser's flush(): taint word, all-reduce, clip and update on the micro-batches
+        summed so far); nothing to do on an empty window, with accum_steps == 1 or without an optimiser."""
+        if self.optimizer is not None:
+            self.optimizer.flush()
+
+    def _accum_replay(self, slot):
+        """One micro-batch of an accumulation window: the window word, the replay (data parallel: both graphs, with NO collective), and
+        behind the window's last micro-batch the taint word, the all-reduces (the suffix bucket under graph B, the encoder bucket with the
+        header behind it), the clip and the update -- issued eagerly, with gscale = 1 / (world * micro-batches)."""
+        opt = self.optimizer
+        word = 1 if opt._acc_n else 0
+        if word != self._acc_word:
+            self.acc_dev.fill_(word)
+            self._acc_word = word
+        last = opt._acc_n + 1 >= opt.accum_steps
+        split = isinstance(slot["graph"], tuple)
+        if not self.dp:
+            slot["graph"].replay()
+        elif not last:
+            for g in (slot["graph"][:2] if split else (slot["graph"],)):
+                g.replay()
+        else:
+            from . import parallel
+            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if parallel.TIMING is not None else None
+            if split:
+                gA, gB, cut = slot["graph"]
+                gA.replay()
+                cur = torch.cuda.current_stream()
+                self._comm.wait_stream(cur)
+                with torch.cuda.stream(self._comm):        # the window's suffix bucket travels while graph B runs
+                    work = self._all_reduce(self.flat_g[cut:], async_op=True)
+                gB.replay()
+                ops.h2_taint(self.flat_g_all[:1])          # the clamps of every micro-batch of the window
+                if ev is not None:
+                    ev[0].record()
+                self._all_reduce(self.flat_g_all[:self.flat_g_all.numel() - self.flat_g.numel() + cut])
+                work.wait()
+                cur.wait_stream(self._comm)
+            else:
+                slot["graph"].replay()
+                ops.h2_taint(self.flat_g_all[:1])
+                if ev is not None:
+                    ev[0].record()
+                self._all_reduce(self.flat_g_all)
+            if ev is not None:
+                ev[1].record()
+                parallel.TIMING.append(ev)
+        opt._acc_groups = (0,)
+        opt._acc_n += 1
+        if last:
+            opt._close_window(taint=not self.dp, reduce=False)
+        return self.losses
+
     def state_dict(self):
         """The optimiser state of the graphed path: the flat momentum buffer and the parameter order it refers to."""
         return {"lr": self.lr, "momentum": self.mu, "live": list(self.live or []), "calls": int(self.calls),
@@ -366,6 +448,8 @@ class GraphedTrainStep:
             self._restore_momentum()
         self._use(slot)
         self._stage(data, in_theta, q_theta, rois, target, noise, draw=False)
+        if self.accum > 1:
+            return self._accum_replay(slot)
         if not self.dp:
             slot["graph"].replay()
             return self.losses

@@ -1670,18 +1670,35 @@ def loss_bwd(pred, pred_p, pred_l, target, gscale, factors, reg_l2, use_mask, no
     return g_pred, g_p, g_l
 
 
-def flatten_into(tensors, out):
-    """out[:] = concatenation of `tensors` (contiguous fp32, flattened), ONE launch per 64 tensors (nef_flatten; was torch.cat)."""
+def flatten_into(tensors, out, accumulate=False, accumulate_dev=None):
+    """out[:] = concatenation of `tensors` (contiguous fp32, flattened), ONE launch per 64 tensors (nef_flatten; was torch.cat).
+    `accumulate`: out[:] += the concatenation instead (gradient accumulation: one fp32 add per element, no atomics).  `accumulate_dev`: a
+    one-element int32 device tensor that replaces `accumulate` when the launch runs (non-zero: add) -- a captured launch then serves the
+    first and the later micro-batches of a window.  Either one sends the call to nef_flatten_acc (tag "flatten_acc"); the default call
+    is nef_flatten as before."""
     n = len(tensors)
     if n == 0:
         return out
     tensors = [t.detach() if t.is_contiguous() else t.detach().contiguous() for t in tensors]
     if not out.is_cuda or any((not t.is_cuda) or t.dtype != torch.float32 for t in tensors) or out.dtype != torch.float32:
+        if accumulate_dev is not None:
+            accumulate = bool(int(accumulate_dev.reshape(-1)[0]))
+        if accumulate:
+            return out.add_(torch.cat([t.reshape(-1) for t in tensors]))
         return torch.cat([t.reshape(-1) for t in tensors], out=out)          # (CPU plumbing tests; never on the device path)
     assert out.is_contiguous() and out.numel() == sum(t.numel() for t in tensors), (out.numel(), sum(t.numel() for t in tensors))
     srcs = (C.c_void_p * n)(*[t.data_ptr() for t in tensors])
     sizes = (C.c_int64 * n)(*[t.numel() for t in tensors])
-    _lib.check(_lib.load().nef_flatten(srcs, sizes, n, _p(out), _stream()), "nef_flatten")
+    if not accumulate and accumulate_dev is None:
+        _lib.check(_lib.load().nef_flatten(srcs, sizes, n, _p(out), _stream()), "nef_flatten")
+        return out
+    if accumulate_dev is not None:
+        _chk(accumulate_dev, torch.int32)
+        assert accumulate_dev.numel() == 1
+    ev = _hbm("flatten_acc", out, *tensors)
+    _lib.check(_lib.load().nef_flatten_acc(srcs, sizes, n, _p(out), int(bool(accumulate)), _p(accumulate_dev), _stream()),
+               "nef_flatten_acc")
+    _done(ev)
     return out
 
 

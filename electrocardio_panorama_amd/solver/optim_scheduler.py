@@ -11,6 +11,8 @@ load_ema_state_dict and the ema_weights() context are its surface.
 'lars' / 'lamb' return FusedLARS / FusedLAMB: the layer-wise trust ratios of large-batch training on the same machinery (nef_update_trust:
 one norm pair per parameter tensor by a deterministic segmented reduction, then the update), with SOLVER.trust_coef, SOLVER.trust_eps and
 SOLVER.trust_exempt (tensors whose ratio stays 1).
+SOLVER.accum_steps = K > 1 makes every fused optimiser accumulate: step() sums p.grad into the flat gradient buffer (nef_flatten_acc) and its
+K-th call -- or flush() on an incomplete window -- takes the taint word, all-reduces, clips and updates once, on the mean over the window.
 DataParallelAdam (torch Adam behind a separate all-reduce) is kept as the unfused comparison."""
 import contextlib
 import fnmatch
@@ -82,8 +84,17 @@ class _FusedFlat(torch.optim.Optimizer):
     BatchNorm running statistics its forward pass already updated are NOT rolled back (DESIGN.md 3.0 "Range")."""
     _SLOTS = ()
 
-    def __init__(self, params, defaults, max_grad_norm=0.0, no_decay=(), ema_decay=0.0, ema_warmup=False):
+    def __init__(self, params, defaults, max_grad_norm=0.0, no_decay=(), ema_decay=0.0, ema_warmup=False, accum_steps=1):
         super().__init__(params, defaults)
+        # gradient accumulation: step() folds p.grad into the flat gradient buffer (the first micro-batch of a window assigns, the later
+        # ones add: ops.flatten_into(accumulate=)) and only its accum_steps-th call takes the taint word, all-reduces, clips and updates,
+        # with gscale = 1 / (world * accum_steps); flush() closes an incomplete window.  1 = off: step() is what it was.  An attribute like
+        # max_grad_norm, NOT a param_groups key.  The window position lives here, so eager and replayed micro-batches share a window
+        if isinstance(accum_steps, bool) or not isinstance(accum_steps, int) or accum_steps < 1:
+            raise ValueError(f"Invalid accum_steps value: {accum_steps!r}")
+        self.accum_steps = accum_steps
+        self._acc_n = 0          # micro-batches summed into the open window (0: no window is open)
+        self._acc_groups = ()    # the parameter groups that window covers
         # an exponential moving average of the parameters, kept by the update launch itself (ops.update_*(ema=)): e += (1 - d_t) * (p - e)
         # after every update that is not skipped, d_t = ema_decay or (ema_warmup) min(ema_decay, (1 + t) / (10 + t)) over the t completed
         # EMA updates.  0 = off: no buffer, no other launch.  Attributes like max_grad_norm, NOT param_groups keys
@@ -104,7 +115,8 @@ class _FusedFlat(torch.optim.Optimizer):
             raise ValueError(f"Invalid max_grad_norm value: {max_grad_norm}")
         self.max_grad_norm = float(max_grad_norm)
         self._clip_stats = None      # 4 device words [norm, coefficient, steps clipped, steps with a non-finite norm]: made at first use
-        parallel.enable_early_reduce()      # this optimiser consumes engine.backward's early gradient bucket (see _reduce)
+        if accum_steps == 1:                    # (accumulating: one all-reduce per window, no early bucket)
+            parallel.enable_early_reduce()      # this optimiser consumes engine.backward's early gradient bucket (see _reduce)
 
     def _build(self, gi, live):
         n = sum(p.numel() for p in live)
@@ -260,6 +272,9 @@ class _FusedFlat(torch.optim.Optimizer):
         if fl is None or fl["ids"] != [id(p) for p in live] or ("ema" in fl) != (self.ema_decay > 0) or any(
                 p.data.data_ptr() < fl["p"].data_ptr() or
                 p.data.data_ptr() >= fl["p"].data_ptr() + fl["p"].numel() * 4 for p in live):
+            if self._acc_n:      # a rebuild would drop the partial sum of the open window
+                raise RuntimeError(f"the live parameters of group {gi} changed or were re-pointed after {self._acc_n} of {self.accum_steps} "
+                                   "accumulated micro-batches; flush() the window first")
             self._build(gi, live)
             fl = self._flat[gi]
         return fl
@@ -281,6 +296,8 @@ class _FusedFlat(torch.optim.Optimizer):
 
     def load_state_dict(self, state_dict):
         """The loaded state replaces the flat buffers: drop the flat views so the next step() re-imports them."""
+        if self._acc_n:
+            raise RuntimeError(f"load_state_dict inside an accumulation window ({self._acc_n} of {self.accum_steps} micro-batches); flush() first")
         super().load_state_dict(state_dict)
         self._flat = {}
 
@@ -341,8 +358,75 @@ class _FusedFlat(torch.optim.Optimizer):
             parallel.TIMING.append(ev)
         flat[split:].copy_(early["flat"])
 
+    @property
+    def window_open(self):
+        """Whether micro-batches are summed in the flat gradient buffer that no update has consumed yet (accum_steps > 1 only)."""
+        return self._acc_n > 0
+
+    def _accumulate(self):
+        """step() with accum_steps > 1: this micro-batch's p.grad into the flat gradient buffers -- assigned by the first micro-batch of a
+        window, added by the later ones, in call order -- and the window closed behind the accum_steps-th."""
+        if self.max_grad_norm > 0 and sum(any(p.grad is not None for p in g["params"]) for g in self.param_groups) > 1:
+            raise NotImplementedError("max_grad_norm clips the global norm of ONE parameter group")
+        groups = []
+        for gi, group in enumerate(self.param_groups):
+            live = [p for p in group["params"] if p.grad is not None]
+            if not live:
+                continue
+            fl = self._current(gi, live)      # (raises inside a window where it would have to rebuild)
+            ops.flatten_into([p.grad for p in live], fl["g"], accumulate=self._acc_n > 0)
+            groups.append(gi)
+        if not groups:
+            return
+        if self._acc_n and tuple(groups) != self._acc_groups:
+            raise RuntimeError(f"parameter groups {groups} have gradients, the open accumulation window covers {list(self._acc_groups)}")
+        early = parallel.take_early() if dist.is_available() and dist.is_initialized() else None
+        if early is not None:
+            early["work"].wait()      # somebody else opted in: a bucket of ONE backward pass, retired like one that does not line up
+        self._acc_groups = tuple(groups)
+        self._acc_n += 1
+        if self._acc_n >= self.accum_steps:
+            self._close_window()
+
+    @torch.no_grad()
+    def flush(self):
+        """Close an incomplete window: the update on the m < accum_steps micro-batches summed so far, gscale = 1 / (world * m).  Nothing
+        happens on an empty window (and with accum_steps == 1, where no window is ever open)."""
+        if self._acc_n:
+            self._close_window()
+
+    def _close_window(self, taint=True, reduce=True):
+        """What step() does behind its flatten, once per window of `_acc_n` micro-batches: the taint word (h2_taint advances its mark only
+        when it runs, so this one launch covers every micro-batch), ONE all-reduce of g_all (header included), the clip and the update,
+        with gscale = 1 / (world * _acc_n).  GraphedTrainStep passes taint / reduce False where it has issued them itself."""
+        world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+        gscale = 1.0 / (world * self._acc_n)
+        word = None
+        for gi in self._acc_groups:
+            fl, group = self._flat[gi], self.param_groups[gi]
+            if taint:
+                if word is None:
+                    ops.h2_taint(fl["g_all"][:1])
+                else:
+                    fl["g_all"][:1].zero_()
+            if reduce and world > 1:
+                dist.all_reduce(fl["g_all"])
+            if taint:
+                if word is None:
+                    word = fl["g_all"][:1]
+                else:
+                    fl["g_all"][:1].copy_(word)       # (already summed over the ranks)
+            if self.max_grad_norm > 0:
+                self._clip(fl, gscale)
+            self._device_update(fl, group, gscale, skip=fl["g_all"][:1])
+        ops._PREPACKED.clear()
+        self._ema_pending = None
+        self._acc_n, self._acc_groups = 0, ()
+
     @torch.no_grad()
     def step(self, closure=None):
+        if self.accum_steps > 1:
+            return self._accumulate()
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         taint = None           # ONE taint word per step: h2_taint advances its mark, so later groups reuse the first group's (summed) word
         clip = self.max_grad_norm > 0
@@ -379,7 +463,7 @@ class FusedSGD(_FusedFlat):
     _SLOTS = (("buf", "momentum_buffer"),)
 
     def __init__(self, params, lr, momentum=0.9, dampening=0, weight_decay=0, nesterov=False, *, no_decay=(), max_grad_norm=0.0,
-                 ema_decay=0.0, ema_warmup=False):
+                 ema_decay=0.0, ema_warmup=False, accum_steps=1):
         if not 0.0 <= lr:
             raise ValueError(f"Invalid learning rate: {lr}")
         if not 0.0 <= momentum:
@@ -392,7 +476,7 @@ class FusedSGD(_FusedFlat):
             raise NotImplementedError("FusedSGD implements dampening=0")
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=bool(nesterov),
                                       maximize=False, foreach=None, differentiable=False, fused=None),
-                         max_grad_norm=max_grad_norm, no_decay=no_decay, ema_decay=ema_decay, ema_warmup=ema_warmup)
+                         max_grad_norm=max_grad_norm, no_decay=no_decay, ema_decay=ema_decay, ema_warmup=ema_warmup, accum_steps=accum_steps)
 
     @staticmethod
     def _check_group(group):
@@ -432,7 +516,7 @@ class FusedAdam(_FusedFlat):
     _DECOUPLED = False
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, maximize=False,
-                 no_decay=(), max_grad_norm=0.0, ema_decay=0.0, ema_warmup=False):
+                 no_decay=(), max_grad_norm=0.0, ema_decay=0.0, ema_warmup=False, accum_steps=1):
         if amsgrad or maximize:
             raise NotImplementedError(f"{type(self).__name__} implements amsgrad=False, maximize=False")
         if not 0.0 <= lr:
@@ -444,7 +528,7 @@ class FusedAdam(_FusedFlat):
         if not 0.0 <= weight_decay:
             raise ValueError(f"Invalid weight_decay value: {weight_decay}")
         super().__init__(params, self._defaults(lr, (float(betas[0]), float(betas[1])), eps, weight_decay),
-                         max_grad_norm=max_grad_norm, no_decay=no_decay, ema_decay=ema_decay, ema_warmup=ema_warmup)
+                         max_grad_norm=max_grad_norm, no_decay=no_decay, ema_decay=ema_decay, ema_warmup=ema_warmup, accum_steps=accum_steps)
 
     @staticmethod
     def _defaults(lr, betas, eps, weight_decay):
@@ -509,9 +593,9 @@ class FusedAdamW(FusedAdam):
     _DECOUPLED = True
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False,
-                 no_decay=(), max_grad_norm=0.0, ema_decay=0.0, ema_warmup=False):
+                 no_decay=(), max_grad_norm=0.0, ema_decay=0.0, ema_warmup=False, accum_steps=1):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
-                         no_decay=no_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup)
+                         no_decay=no_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup, accum_steps=accum_steps)
 
     @staticmethod
     def _defaults(lr, betas, eps, weight_decay):
@@ -585,11 +669,11 @@ class FusedLARS(_TrustMixin, FusedSGD):
     torch.optim.SGD's (momentum_buffer); `trust_coef` and `trust_eps` are group keys."""
 
     def __init__(self, params, lr, momentum=0.9, dampening=0, weight_decay=0, nesterov=False, trust_coef=1e-3, trust_eps=1e-8, *,
-                 no_decay=(), trust_exempt=(), max_grad_norm=0.0, ema_decay=0.0, ema_warmup=False):
+                 no_decay=(), trust_exempt=(), max_grad_norm=0.0, ema_decay=0.0, ema_warmup=False, accum_steps=1):
         self._check_trust(trust_coef, trust_eps)
         self._trust_init(trust_exempt)
         super().__init__(params, lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
-                         no_decay=no_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup)
+                         no_decay=no_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup, accum_steps=accum_steps)
         for group in self.param_groups:
             group.setdefault("trust_coef", float(trust_coef))
             group.setdefault("trust_eps", float(trust_eps))
@@ -617,11 +701,11 @@ class FusedLAMB(_TrustMixin, FusedAdam):
     are group keys as in FusedLARS (LAMB's ratio uses neither)."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0, amsgrad=False, trust_coef=1e-3, trust_eps=1e-8, *,
-                 maximize=False, no_decay=(), trust_exempt=(), max_grad_norm=0.0, ema_decay=0.0, ema_warmup=False):
+                 maximize=False, no_decay=(), trust_exempt=(), max_grad_norm=0.0, ema_decay=0.0, ema_warmup=False, accum_steps=1):
         self._check_trust(trust_coef, trust_eps)
         self._trust_init(trust_exempt)
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
-                         no_decay=no_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup)
+                         no_decay=no_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup, accum_steps=accum_steps)
         for group in self.param_groups:
             group.setdefault("trust_coef", float(trust_coef))
             group.setdefault("trust_eps", float(trust_eps))
@@ -667,7 +751,9 @@ def get_optimizer(cfg, model_params):
     clip = float(cfg.SOLVER.get('clip_grad_norm', 0.0))      # (.get: configs written before the key existed)
     wd = float(cfg.SOLVER.get('weight_decay', 0.0))          # sgd, adam: L2 (added to the gradient); adamw: decoupled
     no_decay = tuple(cfg.SOLVER.get('no_decay', None) or ())
-    ema = dict(ema_decay=float(cfg.SOLVER.get('ema_decay', 0.0)), ema_warmup=bool(cfg.SOLVER.get('ema_warmup', False)))
+    # (what every fused optimiser takes: the weight average and SOLVER.accum_steps, the micro-batches per update)
+    ema = dict(ema_decay=float(cfg.SOLVER.get('ema_decay', 0.0)), ema_warmup=bool(cfg.SOLVER.get('ema_warmup', False)),
+               accum_steps=cfg.SOLVER.get('accum_steps', 1))
     if optim_name == 'adam':
         return FusedAdam(model_params, lr=cfg.SOLVER.lr, weight_decay=wd, no_decay=no_decay, max_grad_norm=clip, **ema)
     elif optim_name == 'adamw':

@@ -183,6 +183,8 @@ class Solver:
                 names.append('train_grad_norm')
                 msg += '\ngrad_norm: {} (max_norm {}): {} of {} steps clipped, {} skipped for a non-finite norm'.format(
                     scalars[-1], optimizer.max_grad_norm, self.last_clip_counts[0], len(self.last_grad_norms), self.last_clip_counts[1])
+            if getattr(optimizer, 'accum_steps', 1) > 1:
+                msg += '\naccum_steps {}: {} updates from {} batches'.format(optimizer.accum_steps, *self.last_updates)
             if getattr(self, 'last_trust_stats', None) is not None:      # SOLVER.optim is lars or lamb
                 msg += '\ntrust ratio: min {:.3e}, max {:.3e} over the adapted tensors; {} steps skipped for non-finite norms'.format(
                     *self.last_trust_stats)
@@ -317,6 +319,9 @@ class Solver:
         # SOLVER.optim lars / lamb: the count of steps skipped for non-finite norms before this epoch
         trust = phase == 'train' and hasattr(optim, 'trust_ratios')
         trust_0 = float(optim.trust_stats[3].item()) if trust and optim.trust_stats is not None else 0.0
+        # SOLVER.accum_steps: an update closes every window of K train batches; clip_stats are recorded per UPDATE, not per batch
+        accum = phase == 'train' and getattr(optim, 'accum_steps', 1) > 1
+        n_batches = n_updates = 0
         for meta in dl:
             source_data, rois, input_theta, target_view, target_theta, noise = self._to_device(meta)
             rest_theta = torch.as_tensor(meta['rest_theta']).to(self.device) if 'rest_theta' in meta else None
@@ -351,17 +356,28 @@ class Solver:
                 if keep:
                     pred_s.add(rest_out)                           # solver.py:182
                     rest_s.add(rest_view)
-            if clip_s is not None and optim.clip_stats is not None:
+            updated = phase == 'train' and not (accum and optim.window_open)
+            n_batches += 1
+            n_updates += int(updated)
+            if updated and clip_s is not None and optim.clip_stats is not None:
                 clip_s.add(optim.clip_stats[:2])
             if keep:
                 gt_s.add(target_view.squeeze(1))
                 in_s.add(source_data)
                 rois_s.add(rois)
+        if accum and optim.window_open:
+            # a window never crosses an epoch: the incomplete last one is flushed on the micro-batches it has (issued eagerly, also behind
+            # replayed micro-batches: the stepper and the optimiser share the window)
+            optim.flush()
+            n_updates += 1
+            if clip_s is not None and optim.clip_stats is not None:
+                clip_s.add(optim.clip_stats[:2])
         losses = [a.tolist() for a in losses_s.arrays()]
         self._check_h2_range(phase, optim)       # same cadence as the loss read-back above: the device has been waited for anyway
         if phase == 'train':
             # [norm, coefficient] of every step and this epoch's (steps clipped, steps skipped for a non-finite norm); clipping off: empty
             self.last_grad_norms, self.last_clip_counts = [], (0, 0)
+            self.last_updates = (n_updates, n_batches)      # (equal unless SOLVER.accum_steps > 1)
             if clip_s is not None and optim.clip_stats is not None:
                 self.last_grad_norms = [a.tolist() for a in clip_s.arrays()]
                 clip_1 = optim.clip_stats[2:].tolist()

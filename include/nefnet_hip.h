@@ -709,6 +709,17 @@ int nef_amax_roll(float* cur, float* nxt, int n, float follow_up, float follow_d
  * arrays.  Builds the flat gradient buffer FusedSGD / the data-parallel all-reduce work on (replaces the torch.cat of
  * codes/solver's per-parameter .grad tensors; optim_scheduler.py:10 steps them one by one). */
 int nef_flatten(const float* const* srcs, const int64_t* sizes, int n, float* out, nef_stream_t stream);
+/* nef_flatten with an accumulate form (gradient accumulation, SOLVER.accum_steps: the micro-batches of a window are summed in fp32 into
+ * the one flat gradient buffer; the reference accumulates by leaving out zero_grad()).  With off_k the sum of sizes[0..k):
+ *   out[off_k + i]  = srcs[k][i]   when not accumulating -- `out` is never read, it may hold anything;
+ *   out[off_k + i] += srcs[k][i]   when accumulating (one fp32 add per element, one writer per element, no atomics).
+ * `accumulate` is 0 or 1.  A non-NULL `accumulate_dev` is a DEVICE word (int32) that replaces `accumulate` when the launch runs (non-zero:
+ * accumulate), so one captured launch serves the first and the later micro-batches of a window.  `srcs` / `sizes` are HOST arrays; one
+ * launch per 64 tensors, the grid a function of the sizes alone.  A source of 0 elements may be NULL.  Every argument is checked before
+ * the first launch: NULL srcs / sizes / out with n > 0 (or a NULL source of sizes[k] > 0) is NEF_E_NULL; n < 0, a negative size or
+ * `accumulate` outside {0, 1} is NEF_E_SHAPE; n == 0 is NEF_OK and launches nothing. */
+int nef_flatten_acc(const float* const* srcs, const int64_t* sizes, int n, float* out, int accumulate, const int32_t* accumulate_dev,
+                    nef_stream_t stream);
 /* w [Co][2 Cih][K] -> grouped [2 Co][Cih][K] (group = input-channel half: the first decoder conv runs once per distinct half,
  * DESIGN.md section 2; weight of codes/network/model_nefnet.py:18), inverse != 0: the other way (its gradient). */
 int nef_regroup_halves(const float* src, float* dst, int Co, int Cih, int K, int inverse, nef_stream_t stream);

@@ -5,6 +5,7 @@
     python tools/bench_adam.py --weight-decay X [--no-decay PATTERN...] [--parent-tree DIR] [--out profiles/wd_bench_line.json]
     python tools/bench_adam.py --ema D [--parent-tree DIR] [--out profiles/ema_bench_line.json]
     python tools/bench_adam.py --trust lars|lamb [--parent-tree DIR] [--out profiles/r11_trust_bench_line.json]
+    python tools/bench_adam.py --accum K [--parent-tree DIR] [--out profiles/r12_accum_bench_line.json]
 
 Each measurement runs in a child process of its own under `timeout` (nothing more is started once one fails), `--reps` rounds of
 the three children; every figure is reported as [min, median, max] over the rounds:
@@ -38,7 +39,13 @@ in one process (rule 0, no table: five fp32 streams per parameter against seven)
 FusedSGD / FusedAdam (sgd-graph for lars, adam-graph for lamb), the graphed step with FusedLARS / FusedLAMB (lars-graph / lamb-graph: one
 segment per live tensor, nothing exempt), and -- with --parent-tree DIR -- DIR's own sgd-graph / adam-graph step.  The config-2 trust child
 also times the entry's launches alone on the flat buffers with the model's real segment table, cold as above, beside nef_update (same rule,
-no table) in one process.  Writes profiles/r11_trust_bench_line.json unless --out says otherwise."""
+no table) in one process.  Writes profiles/r11_trust_bench_line.json unless --out says otherwise.
+
+--accum K measures gradient accumulation (SOLVER.accum_steps), at the same two shapes: per round and shape the graphed FusedSGD step with
+accum_steps = 1 (sgd-graph: the parent's code path) and with accum_steps = K (sgd-graph-accum: ms per MICRO-batch, an update every K-th),
+and -- with --parent-tree DIR -- DIR's own sgd-graph step.  The config-2 accumulating child also times the flatten launch alone on the
+model's real gradient tensors, cold as above: nef_flatten_acc (accumulate form) beside nef_flatten in one process (3 fp32 streams per
+parameter against 2).  Writes profiles/r12_accum_bench_line.json unless --out says otherwise."""
 import argparse
 import json
 import os
@@ -78,7 +85,7 @@ def cold_ms(launches, dev, reps=30):
     return [float(np.median([a.elapsed_time(b) for a, b in ev])) for ev in evs]
 
 
-def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=(), ema=0.0):
+def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=(), ema=0.0, accum=1):
     import numpy as np
     import torch
     from electrocardio_panorama_amd import ops, synth
@@ -103,6 +110,8 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
         optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9, weight_decay=wd, no_decay=no_decay)
     elif mode == "sgd-graph-ema":
         optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9, ema_decay=ema)
+    elif mode == "sgd-graph-accum":
+        optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9, accum_steps=accum)
     elif mode == "adam-graph":
         optim = FusedAdam(model.parameters(), lr=1e-3)
     elif mode == "lars-graph":
@@ -140,6 +149,17 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
         step()
     torch.cuda.synchronize(dev)
     res = {"mode": mode, "ms_per_step": round((time.perf_counter() - t0) * 1e3 / steps, 3), "steps": steps, "warmup": warmup, "B": B, "L": L}
+    if mode == "sgd-graph-accum":
+        graphed.flush()      # (a window the timed micro-batches left open)
+        res.update(accum_steps=accum, ms_per_step_note="per micro-batch; an update behind every accum_steps-th")
+    if mode == "sgd-graph-accum" and (B, L) == EMA_SHAPES["config2"]:
+        fl = optim._flat[0]
+        srcs = [torch.randn_like(p_) for p_ in fl["params"]]      # the model's gradient tensors: their sizes and count
+        out_, n = torch.zeros_like(fl["g"]), fl["g"].numel()
+        old_ms, new_ms = cold_ms([lambda: ops.flatten_into(srcs, out_), lambda: ops.flatten_into(srcs, out_, accumulate=True)], dev)
+        res.update(flatten_tensors=len(srcs), flatten_params=n, nef_flatten_cold_ms=round(old_ms, 4), nef_flatten_acc_cold_ms=round(new_ms, 4),
+                   nef_flatten_cold_GBps=round(2 * 4 * n / (old_ms * 1e-3) / 1e9, 1),
+                   nef_flatten_acc_cold_GBps=round(3 * 4 * n / (new_ms * 1e-3) / 1e9, 1))
     if mode == "sgd-graph-ema":
         fl = optim._flat[0]
         p, g, buf, e, e_n = (fl[k].clone() for k in ("p", "g", "buf", "ema", "ema_n"))
@@ -302,6 +322,60 @@ def ema_rounds(args):
             f.write(line + "\n")
 
 
+def accum_rounds(args):
+    """--accum K: `--reps` alternating rounds of fresh children per shape (see the module docstring); prints and writes one JSON line."""
+    modes = dict({"sgd-graph": 900, "sgd-graph-accum": 900}, **({"parent": 900} if args.parent_tree else {}))
+    results = {(shape, mode): [] for shape in EMA_SHAPES for mode in modes}
+    for rnd in range(args.reps):
+        order = list(modes) if rnd % 2 == 0 else list(reversed(modes))
+        for shape, (B, L) in EMA_SHAPES.items():
+            for mode in order:
+                if mode == "parent":
+                    # the parent's tool may lack --shape: its `child` function is called directly, in a fresh process of its own tree
+                    tree = os.path.abspath(args.parent_tree)
+                    code = ("import importlib.util as u; s = u.spec_from_file_location('parent_bench', %r); m = u.module_from_spec(s); "
+                            "s.loader.exec_module(m); m.child('sgd-graph', %d, %d, B=%d, L=%d)"
+                            % (os.path.join(tree, "tools", "bench_adam.py"), args.steps, args.warmup, B, L))
+                    cmd = ["timeout", "-k", "10", str(modes[mode]), sys.executable, "-c", code]
+                else:
+                    tree = ROOT
+                    cmd = ["timeout", "-k", "10", str(modes[mode]), sys.executable, os.path.join(ROOT, "tools", "bench_adam.py"), "--child", mode,
+                           "--steps", str(args.steps), "--warmup", str(args.warmup), "--shape", str(B), str(L)]
+                    if mode == "sgd-graph-accum":
+                        cmd += ["--accum", str(args.accum)]
+                results[(shape, mode)].append(run_child(cmd, tree, mode))
+                sys.stderr.write(f"round {rnd + 1}/{args.reps} {shape} {mode}: {results[(shape, mode)][-1]['ms_per_step']} ms/step\n")
+                sys.stderr.flush()
+
+    def spread(shape, mode, key):
+        v = sorted(x[key] for x in results[(shape, mode)])
+        return [v[0], v[len(v) // 2], v[-1]]
+
+    a2 = results[("config2", "sgd-graph-accum")][0]
+    out = {"metric": "ms per train batch, graphed FusedSGD with accum_steps 1 and %d (per micro-batch) ([min, median, max] over rounds)" % args.accum,
+           "rounds": args.reps, "accum_steps": args.accum,
+           "shapes": {k: "B=%d, 3 leads, L=%d, one GPU, dropout on" % v for k, v in EMA_SHAPES.items()}}
+    for shape in EMA_SHAPES:
+        out[shape + "_accum_1_ms"] = spread(shape, "sgd-graph", "ms_per_step")
+        out[shape + "_accum_%d_ms_per_micro_batch" % args.accum] = spread(shape, "sgd-graph-accum", "ms_per_step")
+        if args.parent_tree:
+            out[shape + "_parent_ms"] = par = spread(shape, "parent", "ms_per_step")
+            # the condition: accum_steps 1 is the parent's code path -- its median inside the parent's own min-max spread
+            out[shape + "_accum_1_median_inside_parent_spread"] = par[0] <= out[shape + "_accum_1_ms"][1] <= par[2]
+    out.update(flatten_tensors=a2["flatten_tensors"], flatten_params=a2["flatten_params"],
+               nef_flatten_cold_ms=spread("config2", "sgd-graph-accum", "nef_flatten_cold_ms"),
+               nef_flatten_acc_cold_ms=spread("config2", "sgd-graph-accum", "nef_flatten_acc_cold_ms"),
+               nef_flatten_cold_GBps=spread("config2", "sgd-graph-accum", "nef_flatten_cold_GBps"),
+               nef_flatten_acc_cold_GBps=spread("config2", "sgd-graph-accum", "nef_flatten_acc_cold_GBps"),
+               flatten_note="the flatten launch alone on tensors of the model's gradient sizes, nef_flatten_acc (accumulate form) alternating "
+                            "with nef_flatten in one process; cold = a 512 MiB buffer written before each launch; 3 and 2 fp32 streams per parameter",
+               steps=args.steps, warmup=args.warmup)
+    line = json.dumps(out)
+    print(line)
+    with open(args.out or os.path.join(ROOT, "profiles", "r12_accum_bench_line.json"), "w") as f:
+        f.write(line + "\n")
+
+
 def trust_rounds(args):
     """--trust lars|lamb: `--reps` alternating rounds of fresh children per shape (see the module docstring); prints and writes one JSON
     line."""
@@ -367,10 +441,12 @@ def main():
     ap.add_argument("--no-decay", nargs="*", default=[], metavar="PATTERN", help="with --weight-decay: fnmatch patterns of exempt tensors")
     ap.add_argument("--ema", type=float, default=None, metavar="D", help="measure the EMA of the weights in the update launch (see above)")
     ap.add_argument("--trust", choices=sorted(TRUST_BASE), default=None, help="measure the layer-wise trust ratios (see above)")
+    ap.add_argument("--accum", type=int, default=None, metavar="K", help="measure gradient accumulation, accum_steps = K (see above)")
     ap.add_argument("--shape", type=int, nargs=2, default=(256, 5000), metavar=("B", "L"), help="with --child: batch size and length")
     ap.add_argument("--parent-tree", default=None,
                     help="with --clip / --weight-decay / --ema: a built checkout whose own sgd-graph child runs in every round")
-    ap.add_argument("--child", choices=sorted({**MODES, **CLIP_MODES, **WD_MODES, **EMA_MODES, "lars-graph": 900, "lamb-graph": 900}), default=None)
+    ap.add_argument("--child", choices=sorted({**MODES, **CLIP_MODES, **WD_MODES, **EMA_MODES, "lars-graph": 900, "lamb-graph": 900, "sgd-graph-accum": 900}),
+                    default=None)
     args = ap.parse_args()
     if args.child == "sgd-graph-ema" and not (args.ema is not None and 0.0 < args.ema < 1.0):
         ap.error("--child sgd-graph-ema needs --ema D in (0, 1)")
@@ -384,16 +460,23 @@ def main():
         ap.error("--clip and --weight-decay are two measurements")
     if args.trust is not None and (args.clip is not None or args.weight_decay is not None or args.ema is not None):
         ap.error("--trust is a measurement of its own")
-    if args.parent_tree and args.clip is None and args.weight_decay is None and args.ema is None and args.trust is None:
-        ap.error("--parent-tree goes with --clip, --weight-decay, --ema or --trust")
+    if args.accum is not None and (args.accum < 2 or args.clip is not None or args.weight_decay is not None or args.ema is not None
+                                   or args.trust is not None):
+        ap.error("--accum K >= 2 is a measurement of its own")
+    if args.child == "sgd-graph-accum" and args.accum is None:
+        ap.error("--child sgd-graph-accum needs --accum K")
+    if args.parent_tree and args.clip is None and args.weight_decay is None and args.ema is None and args.trust is None and args.accum is None:
+        ap.error("--parent-tree goes with --clip, --weight-decay, --ema, --trust or --accum")
     if args.child:
         return child(args.child, args.steps if args.child != "adam-eager" else max(3, args.steps // 2), args.warmup,
                      B=args.shape[0], L=args.shape[1], clip=args.clip or 0.0, wd=args.weight_decay or 0.0,
-                     no_decay=tuple(args.no_decay), ema=args.ema or 0.0)
+                     no_decay=tuple(args.no_decay), ema=args.ema or 0.0, accum=args.accum or 1)
     if args.ema is not None:
         return ema_rounds(args)
     if args.trust is not None:
         return trust_rounds(args)
+    if args.accum is not None:
+        return accum_rounds(args)
     modes = dict(MODES)
     if args.clip is not None:
         modes = dict(CLIP_MODES, **({"parent": 900} if args.parent_tree else {}))
