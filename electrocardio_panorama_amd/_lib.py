@@ -132,6 +132,8 @@ SIGNATURES = {
     "nef_lead_mean_mix_shared": (i32, [p, p, p, p, p, i32, i32, i32, i32, i32, p, p]),
     "nef_lead_mean_mix_unpool": (i32, [p, p, p, p, p, p, p, i32, i32, i32, i32, i32, p, p]),
     "nef_mix_bwd_unpool": (i32, [p, p, p, p, p, p, p, p, p, i32, i32, i32, i32, i32, p, i32, p]),
+    "nef_mix_bwd_unpool_rs": (i32, [p, p, p, p, p, p, p, p, p, p, p, sz, p, i32, i32, i32, i32, i32, p, i32, p]),
+    "nef_mix_bwd_unpool_rs_ws_bytes": (sz, [i32, i32]),
     "nef_pass_combine_fwd": (i32, [p, p, p, i32, i32, i32, p]),
     "nef_pass_combine_bwd": (i32, [p, p, i32, i32, i32, p]),
     "nef_pass_combine_stats_ws_bytes": (sz, [i32, i32]),
@@ -148,6 +150,8 @@ SIGNATURES = {
     "nef_bn_bwd_ws_bytes": (sz, [C.POINTER(BnBwdArgs)]),
     "nef_bn_relu_bwd": (i32, [C.POINTER(BnBwdArgs), p]),
     "nef_bn_bwd_args_bytes": (sz, []),
+    "nef_bn_relu_bwd_outconv_w": (i32, [C.POINTER(BnBwdArgs), p, p, p, sz, p]),
+    "nef_bn_relu_bwd_outconv_w_ws_bytes": (sz, [C.POINTER(BnBwdArgs)]),
     "nef_outconv_fwd": (i32, [p, p, p, i32, p, p, p, i32, i32, i32, p]),
     "nef_outconv_bwd_weight": (i32, [p, p, p, p, p, i32, p, p, p, sz, i32, i32, i32, p]),
     "nef_outconv_bwd_data": (i32, [p, p, p, p, i32, i32, i32, p]),

@@ -413,12 +413,17 @@ __global__ void mix_bwd_kernel(const float* __restrict__ gD, const float* __rest
 // (c even, c + 1), one aligned span of T / 2 four-float vectors in every tensor involved (see lead_mean_mix_shared_pair_kernel); the
 // vector that straddles the rows carries both rows' scale and feeds both rows' gq sum.  gz1 / gz2r: the same expressions per element
 // (bit-identical); gq: the same terms in another lane order, as between the two paths of mix_bwd_kernel.
+// NV > 0 (V <= NV, rows c < 128 only): rowsum[(b*V + v)*128 + c] = the sum of the gz1 row as stored (after the relu_z1 mask), in fp64
+// from the first element -- the bias gradient of the residual conv that reads gz1 (block_bwd), without reading gz1 back.
+constexpr int MIX_RS_MAX_V = 4;
+
+template <int NV>
 __global__ __launch_bounds__(256) void mix_bwd_shared_pair_kernel(const float* __restrict__ gD, const float* __restrict__ latent,
                                                                   const float* __restrict__ z1, const float* __restrict__ z2r,
                                                                   const float* __restrict__ q, float* __restrict__ gz1,
                                                                   float* __restrict__ gz2r, float* __restrict__ gq, int B, int V, int T,
                                                                   int c1, int c2, const int32_t* __restrict__ choice_dev, int relu_z1,
-                                                                  int cshift) {
+                                                                  int cshift, double* __restrict__ rowsum) {
     typedef float vec __attribute__((ext_vector_type(4)));
     if (choice_dev) { c1 = choice_dev[0]; c2 = choice_dev[1]; }
     const int64_t pairs = (int64_t)B * 128;
@@ -443,6 +448,9 @@ __global__ __launch_bounds__(256) void mix_bwd_shared_pair_kernel(const float* _
         const vec* g1r = g0 + gpass;
         const bool mask = relu_z1 && first;
         float acc0 = 0.f, acc1 = 0.f;
+        double rs0[NV > 0 ? NV : 1], rs1[NV > 0 ? NV : 1];
+#pragma unroll
+        for (int v = 0; v < NV; ++v) rs0[v] = rs1[v] = 0.0;
         for (int t = lane; t < TW; t += 64) {
             const vec ga = g0[t], gb = g1r[t], l4 = lat[t], pk = zsrc[(int64_t)pick_v * lead + t];
             const vec fq = t < mid ? vec{f0, f0, f0, f0} : (t > mid ? vec{f1, f1, f1, f1} : vec{f0, f0, f1, f1});
@@ -451,7 +459,7 @@ __global__ __launch_bounds__(256) void mix_bwd_shared_pair_kernel(const float* _
                 const float term = ga[e] * l4[e] + gb[e] * pk[e];
                 if (t < mid || (t == mid && e < 2)) acc0 += term; else acc1 += term;
             }
-            for (int v = 0; v < V; ++v) {
+            auto one_lead = [&](int v) -> vec {
                 vec o;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) o[e] = fq[e] * ga[e] / fv + (v == pick_v ? fq[e] * gb[e] : 0.f);
@@ -462,11 +470,34 @@ __global__ __launch_bounds__(256) void mix_bwd_shared_pair_kernel(const float* _
                         if (!(z[e] > 0.f)) o[e] = 0.f;
                 }
                 gdst[(int64_t)v * lead + t] = o;
+                return o;
+            };
+            if constexpr (NV > 0) {
+#pragma unroll
+                for (int v = 0; v < NV; ++v)
+                    if (v < V) {
+                        const vec o = one_lead(v);
+                        const double lo = (double)o[0] + (double)o[1], hi = (double)o[2] + (double)o[3];
+                        if (t < mid) rs0[v] += lo + hi;
+                        else if (t > mid) rs1[v] += lo + hi;
+                        else { rs0[v] += lo; rs1[v] += hi; }
+                    }
+            } else {
+                for (int v = 0; v < V; ++v) one_lead(v);
             }
         }
         acc0 = nef_wave_sum(acc0);
         acc1 = nef_wave_sum(acc1);
         if (lane == 0) { gq[row] = acc0; gq[row + 1] = acc1; }
+        if constexpr (NV > 0) {
+            double* const rdst = rowsum + (int64_t)b * V * 128 + (c & 127);
+#pragma unroll
+            for (int v = 0; v < NV; ++v)
+                if (v < V) {
+                    const double a0 = nef_wave_sum_d(rs0[v]), a1 = nef_wave_sum_d(rs1[v]);
+                    if (lane == 0) { rdst[v * 128] = a0; rdst[v * 128 + 1] = a1; }
+                }
+        }
     }
 }
 
@@ -686,7 +717,9 @@ __global__ void outconv_go_kernel(const float* __restrict__ gout, const float* _
 // Four consecutive values of g[c][t] = w[c][0]*go[t+1] + w[c][1]*go[t] + w[c][2]*go[t-1] (the input gradient of the last
 // conv, same expression as outconv_bwd_data_kernel) from one go row, so that BatchNorm-backward can read the small go
 // instead of a materialised [N][64][L] gradient.
-__device__ __forceinline__ nef_f32x4 oc_grad4(const float* __restrict__ gor, int t4, int L, float w0, float w1, float w2) {
+// `go6`: the six values read, go[4*t4 - 1 .. 4*t4 + 4] (zero outside the row)
+__device__ __forceinline__ nef_f32x4 oc_grad4_go(const float* __restrict__ gor, int t4, int L, float w0, float w1, float w2,
+                                                 float (&go6)[6]) {
     const nef_f32x4 m = *(const nef_f32x4*)(gor + 4 * t4);
     const float lo = t4 > 0 ? gor[4 * t4 - 1] : 0.f;
     const float hi = 4 * t4 + 4 < L ? gor[4 * t4 + 4] : 0.f;
@@ -695,7 +728,13 @@ __device__ __forceinline__ nef_f32x4 oc_grad4(const float* __restrict__ gor, int
     g[1] = w0 * m[2] + w1 * m[1] + w2 * m[0];
     g[2] = w0 * m[3] + w1 * m[2] + w2 * m[1];
     g[3] = w0 * hi + w1 * m[3] + w2 * m[2];
+    go6[0] = lo; go6[1] = m[0]; go6[2] = m[1]; go6[3] = m[2]; go6[4] = m[3]; go6[5] = hi;
     return g;
+}
+
+__device__ __forceinline__ nef_f32x4 oc_grad4(const float* __restrict__ gor, int t4, int L, float w0, float w1, float w2) {
+    float go6[6];
+    return oc_grad4_go(gor, t4, L, w0, w1, w2, go6);
 }
 
 // four consecutive values of the x2-upsampling adjoint (positions 4*t4 .. 4*t4+3 of an L-long row) from the 2L-long
@@ -716,12 +755,17 @@ __device__ __forceinline__ nef_f32x4 up2_adjoint4(const float* __restrict__ gr, 
 
 // MODE 1: `gy` is the go tensor [P*Bp][L] of the last conv and `ocw` its weight [C][3]; MODE 2: `gy` is the gradient wrt
 // the x2-UPSAMPLED activation [rows][2L]; in both cases g is rebuilt on the fly (L % 4 == 0)
-template <int MODE>
+// OCW (MODE 1 only, L % 4 == 0): the pass also forms the last conv's weight and bias gradient (model_nefnet.py:106,168), which are sums
+// over the same (go, x) stream -- gw[c][k] = sum go[t - k + 1] * max(x*a + b, 0), gb = sum go -- from the values already at hand: fp32
+// inside a lane's share of one sample row, fp64 from there on.  part2[((p*C + c)*BN_SPLIT + sp)*4 + {0,1,2}] = gw[c][0..2] partial, + 3 =
+// the gb partial (written by the c == 0 workgroups, zero elsewhere).  s1 / s2 are accumulated by the same code as without it.
+template <int MODE, bool OCW = false>
 __global__ __launch_bounds__(256) void bn_bwd_partial(const float* __restrict__ gy, const float* __restrict__ x,
                                                       const float* __restrict__ mean, const float* __restrict__ invstd,
                                                       const float* __restrict__ a, const float* __restrict__ b,
                                                       double* __restrict__ part, int P, int Bp, int C, int L,
-                                                      const float* __restrict__ ocw) {
+                                                      const float* __restrict__ ocw, double* __restrict__ part2 = nullptr) {
+    static_assert(!OCW || MODE == 1, "the weight-gradient sums ride on the last conv's form");
     __shared__ double sm[4];
     int bid = blockIdx.x;
     const int sp = bid % BN_SPLIT;
@@ -732,6 +776,7 @@ __global__ __launch_bounds__(256) void bn_bwd_partial(const float* __restrict__ 
     constexpr bool OC = MODE == 1, UPG = MODE == 2;
     const float w0 = OC ? ocw[c * 3] : 0.f, w1 = OC ? ocw[c * 3 + 1] : 0.f, w2 = OC ? ocw[c * 3 + 2] : 0.f;
     double s1 = 0.0, s2 = 0.0;
+    double d0 = 0.0, d1 = 0.0, d2 = 0.0, db = 0.0;      // OCW
     // accumulate in double from the first element: sum(g) cancels heavily and k1 = sum(g)/n shifts every gx
     if ((L & 3) == 0) {
         const int L4 = L >> 2;
@@ -741,17 +786,30 @@ __global__ __launch_bounds__(256) void bn_bwd_partial(const float* __restrict__ 
             const nef_f32x4* gr = (const nef_f32x4*)(gy + off);
             const float* gor = gy + ((int64_t)p * Bp + bb) * L;
             const float* gur = gy + 2 * off;
+            float r0 = 0.f, r1 = 0.f, r2 = 0.f, rb = 0.f;      // OCW: this lane's share of the row
 #pragma unroll 2
             for (int t = threadIdx.x; t < L4; t += 256) {
+                float go6[6];
                 const nef_f32x4 xv = xr[t],
-                                gv = OC ? oc_grad4(gor, t, L, w0, w1, w2) : (UPG ? up2_adjoint4(gur, t, L) : gr[t]);
+                                gv = OCW ? oc_grad4_go(gor, t, L, w0, w1, w2, go6)
+                                         : (OC ? oc_grad4(gor, t, L, w0, w1, w2) : (UPG ? up2_adjoint4(gur, t, L) : gr[t]));
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float g = fmaf(xv[e], af, bf) > 0.f ? gv[e] : 0.f;
+                    const float y = fmaf(xv[e], af, bf);
+                    const float g = y > 0.f ? gv[e] : 0.f;
                     s1 += (double)g;
                     s2 += (double)g * (double)((xv[e] - mf) * is);
+                    if constexpr (OCW) {
+                        const float v = fmaxf(y, 0.f);
+                        r0 = fmaf(go6[e + 2], v, r0);
+                        r1 = fmaf(go6[e + 1], v, r1);
+                        r2 = fmaf(go6[e], v, r2);
+                    }
                 }
+                if constexpr (OCW)
+                    if (c == 0) rb += (go6[1] + go6[2]) + (go6[3] + go6[4]);
             }
+            if constexpr (OCW) { d0 += (double)r0; d1 += (double)r1; d2 += (double)r2; db += (double)rb; }
         }
     } else {
         for (int bb = sp; bb < Bp; bb += BN_SPLIT) {
@@ -770,6 +828,28 @@ __global__ __launch_bounds__(256) void bn_bwd_partial(const float* __restrict__ 
         part[((int64_t)(p * C + c) * BN_SPLIT + sp) * 2] = s1;
         part[((int64_t)(p * C + c) * BN_SPLIT + sp) * 2 + 1] = s2;
     }
+    if constexpr (OCW) {
+        d0 = nef_block_sum_d(d0, sm);
+        d1 = nef_block_sum_d(d1, sm);
+        d2 = nef_block_sum_d(d2, sm);
+        db = nef_block_sum_d(db, sm);
+        if (threadIdx.x == 0) {
+            double* o = part2 + ((int64_t)(p * C + c) * BN_SPLIT + sp) * 4;
+            o[0] = d0; o[1] = d1; o[2] = d2; o[3] = db;
+        }
+    }
+}
+
+// gw[c][k] (thread c*3 + k) and gb (thread 3C) of the last conv from bn_bwd_partial<1, true>'s part2: passes, then splits, ascending
+__global__ void bn_bwd_outconv_w_final(const double* __restrict__ part2, float* __restrict__ gw, float* __restrict__ gb, int P, int C) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > 3 * C) return;
+    const int c = i < 3 * C ? i / 3 : 0, k = i < 3 * C ? i % 3 : 3;
+    double s = 0.0;
+    for (int p = 0; p < P; ++p)
+        for (int sp = 0; sp < BN_SPLIT; ++sp) s += part2[((int64_t)(p * C + c) * BN_SPLIT + sp) * 4 + k];
+    if (i < 3 * C) gw[i] = (float)s;
+    else gb[0] = (float)s;
 }
 
 // coef[(p*C+c)*2] = s1/n, s2/n ; ggamma[c] = sum_p s2 ; gbeta[c] = sum_p s1
@@ -2607,8 +2687,8 @@ int nef_mix_bwd(const float* gD, const float* latent, const float* z1, const flo
     hipLaunchKernelGGL((mix_bwd_kernel<UP, SHARED>), dim3(nef_stream_grid((int64_t)B * 256, 4)), dim3(256), 0, NEF_ST, gD, latent, \
                        z1, z2r, q, gz1, gz2r, gq, B, V, T, c1, c2, choice_dev, relu_z1, 8)
     if (shared && !up && T % 4 == 2 && T >= 8 && al16)
-        hipLaunchKernelGGL(mix_bwd_shared_pair_kernel, dim3(nef_stream_grid((int64_t)B * 128, 4)), dim3(256), 0, NEF_ST, gD, latent, z1,
-                           z2r, q, gz1, gz2r, gq, B, V, T, c1, c2, choice_dev, relu_z1, 8);
+        hipLaunchKernelGGL(mix_bwd_shared_pair_kernel<0>, dim3(nef_stream_grid((int64_t)B * 128, 4)), dim3(256), 0, NEF_ST, gD, latent, z1,
+                           z2r, q, gz1, gz2r, gq, B, V, T, c1, c2, choice_dev, relu_z1, 8, (double*)nullptr);
     else if (shared && up) NEF_MIX_BWD(true, true);
     else if (shared) NEF_MIX_BWD(false, true);
     else if (up) NEF_MIX_BWD(true, false);
@@ -2617,24 +2697,60 @@ int nef_mix_bwd(const float* gD, const float* latent, const float* z1, const flo
     return nef_launch_status();
 }
 
-int nef_mix_bwd_unpool(const float* gD, const float* latent, const float* z1, const float* z2b, const int64_t* rois, const float* q,
-                       float* gz1, float* gz2b, float* gq, int B, int V, int T, int c1, int c2, const int32_t* choice_dev, int relu_z1,
-                       nef_stream_t stream) {
-    NEF_ENTER();
+// gz1_chan_sum / ws: both NULL (nef_mix_bwd_unpool), or the per-channel sum of gz1 is wanted too
+static int mix_bwd_unpool_launch(const float* gD, const float* latent, const float* z1, const float* z2b, const int64_t* rois, const float* q,
+                                 float* gz1, float* gz2b, float* gq, int B, int V, int T, int c1, int c2, const int32_t* choice_dev,
+                                 int relu_z1, float* gz1_chan_sum, void* ws, size_t ws_bytes, int* in_kernel, nef_stream_t stream) {
     NEF_REQUIRE(gD && latent && z1 && z2b && rois && q && gz1 && gz2b && gq, NEF_E_NULL);
     NEF_REQUIRE(B > 0 && V > 0 && T > 1 && T <= NEF_UNPOOL_MIX_MAX_T && c1 >= 0 && c1 < V && c2 >= 0 && c2 < V, NEF_E_SHAPE);
     // z1 half: nef_mix_bwd's shared, not-upsampled launch on the rows c < 128 (z2r / gz2r are not touched)
     const bool al16 = (((uintptr_t)gD | (uintptr_t)latent | (uintptr_t)z1 | (uintptr_t)gz1) & 15) == 0;
     const bool pair = T % 4 == 2 && T >= 8 && al16;
-    if (pair)
-        hipLaunchKernelGGL(mix_bwd_shared_pair_kernel, dim3(nef_stream_grid((int64_t)B * 64, 4)), dim3(256), 0, NEF_ST, gD, latent, z1,
-                           (const float*)nullptr, q, gz1, (float*)nullptr, gq, B, V, T, c1, c2, choice_dev, relu_z1, 7);
+    // the pair kernel forms the row sums while it stores gz1: two fp64 sums per lead in registers, so up to MIX_RS_MAX_V leads
+    const bool rs = gz1_chan_sum && pair && V <= MIX_RS_MAX_V;
+    if (in_kernel) *in_kernel = rs;
+#define NEF_MIX_PAIR(NV, ROWSUM)                                                                                                        \
+    hipLaunchKernelGGL(mix_bwd_shared_pair_kernel<NV>, dim3(nef_stream_grid((int64_t)B * 64, 4)), dim3(256), 0, NEF_ST, gD, latent, z1, \
+                       (const float*)nullptr, q, gz1, (float*)nullptr, gq, B, V, T, c1, c2, choice_dev, relu_z1, 7, ROWSUM)
+    if (rs) {
+        NEF_MIX_PAIR(MIX_RS_MAX_V, (double*)ws);
+        hipLaunchKernelGGL(rowsum_to_channel, dim3(128 * V), dim3(256), 0, NEF_ST, (const double*)ws, gz1_chan_sum, B, 128 * V);
+    } else if (pair)
+        NEF_MIX_PAIR(0, (double*)nullptr);
     else
         hipLaunchKernelGGL((mix_bwd_kernel<false, true>), dim3(nef_stream_grid((int64_t)B * 128, 4)), dim3(256), 0, NEF_ST, gD, latent, z1,
                            (const float*)nullptr, q, gz1, (float*)nullptr, gq, B, V, T, c1, c2, choice_dev, relu_z1, 7);
+#undef NEF_MIX_PAIR
     // the z2 half deals positions to lanes as the kernel above does (pair kernel / its vector path / its scalar path): same gq bits
     nef_unpool_mix_bwd_z2(gD, latent, z2b, rois, q, gz2b, gq, B, V, T, c2, choice_dev, pair ? 4 : ((T & 1) == 0 && T >= 8 ? 2 : 1), NEF_ST);
+    if (gz1_chan_sum && !rs)      // the other kernels of the z1 half: the sum is taken over the stored gz1
+        return nef_chan_sum(gz1, gz1_chan_sum, ws, ws_bytes, B, 128 * V, T, stream);
     return nef_launch_status();
+}
+
+int nef_mix_bwd_unpool(const float* gD, const float* latent, const float* z1, const float* z2b, const int64_t* rois, const float* q,
+                       float* gz1, float* gz2b, float* gq, int B, int V, int T, int c1, int c2, const int32_t* choice_dev, int relu_z1,
+                       nef_stream_t stream) {
+    NEF_ENTER();
+    return mix_bwd_unpool_launch(gD, latent, z1, z2b, rois, q, gz1, gz2b, gq, B, V, T, c1, c2, choice_dev, relu_z1, nullptr, nullptr, 0,
+                                 nullptr, stream);
+}
+
+size_t nef_mix_bwd_unpool_rs_ws_bytes(int B, int V) {
+    if (B <= 0 || V <= 0) return 0;
+    const size_t rows = (size_t)B * 128 * V * sizeof(double), cs = nef_chan_sum_ws_bytes(128 * V);
+    return rows > cs ? rows : cs;
+}
+
+int nef_mix_bwd_unpool_rs(const float* gD, const float* latent, const float* z1, const float* z2b, const int64_t* rois, const float* q,
+                          float* gz1, float* gz2b, float* gq, float* gz1_chan_sum, void* ws, size_t ws_bytes, int* in_kernel, int B, int V,
+                          int T, int c1, int c2, const int32_t* choice_dev, int relu_z1, nef_stream_t stream) {
+    NEF_ENTER();
+    NEF_REQUIRE(gz1_chan_sum && ws, NEF_E_NULL);
+    NEF_REQUIRE(B > 0 && V > 0, NEF_E_SHAPE);
+    NEF_REQUIRE(ws_bytes >= nef_mix_bwd_unpool_rs_ws_bytes(B, V), NEF_E_WORKSPACE);
+    return mix_bwd_unpool_launch(gD, latent, z1, z2b, rois, q, gz1, gz2b, gq, B, V, T, c1, c2, choice_dev, relu_z1, gz1_chan_sum, ws,
+                                 ws_bytes, in_kernel, stream);
 }
 
 int nef_upsample2_fwd(const float* x, float* y, int64_t N, int Tin, nef_stream_t stream) {
@@ -2746,9 +2862,8 @@ size_t nef_bn_bwd_ws_bytes(const nef_bn_bwd_args* a) {
     return nef_bn_ws_bytes(a->P, a->C) + (size_t)a->P * a->Bp * a->C * sizeof(double) + go;
 }
 
-int nef_bn_relu_bwd(const nef_bn_bwd_args* args, nef_stream_t stream) {
-    NEF_ENTER();
-    NEF_REQUIRE(args, NEF_E_NULL);
+// gwout / gbout / ws2: all NULL (nef_bn_relu_bwd), or form 1 with the last conv's weight and bias gradient out of the sums pass
+static int bn_relu_bwd_launch(const nef_bn_bwd_args* args, float* gwout, float* gbout, double* ws2, nef_stream_t stream) {
     const nef_bn_bwd_args& a = *args;
     const int P = a.P, Bp = a.Bp, C = a.C, L = a.L, form = a.form, deint = a.phase_major;
     NEF_REQUIRE(a.x && a.mean && a.invstd && a.a && a.b && a.gx && a.ggamma && a.gbeta && a.ws, NEF_E_NULL);
@@ -2787,15 +2902,19 @@ int nef_bn_relu_bwd(const nef_bn_bwd_args* args, nef_stream_t stream) {
                            L, Bp * a.nslot);
     } else {
         const dim3 grid(P * C * BN_SPLIT);
-        if (form == 1)
+        if (form == 1 && ws2) {
+            hipLaunchKernelGGL((bn_bwd_partial<1, true>), grid, dim3(256), 0, NEF_ST, g, a.x, a.mean, a.invstd, a.a, a.b, part, P, Bp, C, L,
+                               a.wout, ws2);
+            hipLaunchKernelGGL(bn_bwd_outconv_w_final, dim3((3 * C + 64) / 64), dim3(64), 0, NEF_ST, (const double*)ws2, gwout, gbout, P, C);
+        } else if (form == 1)
             hipLaunchKernelGGL(bn_bwd_partial<1>, grid, dim3(256), 0, NEF_ST, g, a.x, a.mean, a.invstd, a.a, a.b, part, P, Bp, C, L,
-                               a.wout);
+                               a.wout, (double*)nullptr);
         else if (form == 2)
             hipLaunchKernelGGL(bn_bwd_partial<2>, grid, dim3(256), 0, NEF_ST, g, a.x, a.mean, a.invstd, a.a, a.b, part, P, Bp, C, L,
-                               (const float*)nullptr);
+                               (const float*)nullptr, (double*)nullptr);
         else
             hipLaunchKernelGGL(bn_bwd_partial<0>, grid, dim3(256), 0, NEF_ST, g, a.x, a.mean, a.invstd, a.a, a.b, part, P, Bp, C, L,
-                               (const float*)nullptr);
+                               (const float*)nullptr, (double*)nullptr);
         hipLaunchKernelGGL(bn_bwd_final, dim3((C + 63) / 64), dim3(64), 0, NEF_ST, (const double*)part, coef, a.ggamma, a.gbeta, P, Bp, C,
                            L, BN_SPLIT);
     }
@@ -2818,6 +2937,26 @@ int nef_bn_relu_bwd(const nef_bn_bwd_args* args, nef_stream_t stream) {
     if (a.gx_chan_sum)
         hipLaunchKernelGGL(rowsum_to_channel, dim3(C), dim3(256), 0, NEF_ST, (const double*)rowsum, a.gx_chan_sum, P * Bp, C);
     return nef_launch_status();
+}
+
+int nef_bn_relu_bwd(const nef_bn_bwd_args* args, nef_stream_t stream) {
+    NEF_ENTER();
+    NEF_REQUIRE(args, NEF_E_NULL);
+    return bn_relu_bwd_launch(args, nullptr, nullptr, nullptr, stream);
+}
+
+size_t nef_bn_relu_bwd_outconv_w_ws_bytes(const nef_bn_bwd_args* a) {
+    if (!a || a->form != 1 || a->P <= 0 || a->C <= 0) return 0;
+    return (size_t)a->P * a->C * BN_SPLIT * 4 * sizeof(double);
+}
+
+int nef_bn_relu_bwd_outconv_w(const nef_bn_bwd_args* args, float* gwout, float* gbout, void* ws2, size_t ws2_bytes, nef_stream_t stream) {
+    NEF_ENTER();
+    NEF_REQUIRE(args && gwout && gbout && ws2, NEF_E_NULL);
+    NEF_REQUIRE(args->form == 1, NEF_E_UNSUPPORTED);
+    NEF_REQUIRE(args->P > 0 && args->C > 0, NEF_E_SHAPE);
+    NEF_REQUIRE(ws2_bytes >= nef_bn_relu_bwd_outconv_w_ws_bytes(args), NEF_E_WORKSPACE);
+    return bn_relu_bwd_launch(args, gwout, gbout, (double*)ws2, stream);
 }
 
 int nef_outconv_fwd(const float* x, const float* a, const float* b, int Bp, const float* w, const float* bias,

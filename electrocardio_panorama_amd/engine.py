@@ -165,12 +165,13 @@ def _side(device, work=None):
     return ops.SideStream.get(device)
 
 
-def block_bwd(saved, gy, P, grads, out=None, side=None, pre_gated=False, gate_input=False, scale_bwd=False):
+def block_bwd(saved, gy, P, grads, out=None, side=None, pre_gated=False, gate_input=False, scale_bwd=False, g2_chan_sum=None):
     """Accumulates the block's parameter gradients into `grads`; returns the gradient wrt the block input
     (written into the GV `out` when given, e.g. one half of the z1/z2 split).  Weight / bias gradients are issued on
     the side stream: they are off the dependency chain and overlap with the chain's HBM-bound kernels.
     `gate_input`: the block input is itself a ReLU output whose producer would mask this gradient first thing in its own
-    backward -- apply that mask in the epilogue of the last conv here; the producer is then called with `pre_gated`."""
+    backward -- apply that mask in the epilogue of the last conv here; the producer is then called with `pre_gated`.
+    `g2_chan_sum`: chan_sum of the gated gy where its producer already formed it -- it is the residual conv's bias gradient."""
     xv, h, y, prefix, K, Cog, res_conv, dscale = saved[:8]
     in_scale = saved[8] if len(saved) > 8 else None      # the block input is xv * in_scale: the returned gradient is wrt THAT product
     side = side or ops._Inline()
@@ -185,7 +186,7 @@ def block_bwd(saved, gy, P, grads, out=None, side=None, pre_gated=False, gate_in
     grads[prefix + ".conv1.weight"] = side.run(lambda: ops.conv_bwd_weight(xv, gc1v, K, in_scale=in_scale, site=P[prefix + ".conv1.weight"].data_ptr()), xv.t, gc1)
     if res_conv:
         grads[prefix + ".residual_conv.weight"] = side.run(lambda: ops.conv_bwd_weight(xv, g2v, 1, site=P[prefix + ".residual_conv.weight"].data_ptr()), xv.t, g2)
-        grads[prefix + ".residual_conv.bias"] = side.run(lambda: ops.chan_sum(g2), g2)
+        grads[prefix + ".residual_conv.bias"] = g2_chan_sum if g2_chan_sum is not None else side.run(lambda: ops.chan_sum(g2), g2)
         gres = ops.conv(g2v, ops.pack_weight(P[prefix + ".residual_conv.weight"], G, flip=True, T=xv.T), Cig, 1,
                         role="conv_bwd_data")
         resv = GV.dense(gres, G)
@@ -345,10 +346,12 @@ def decoder_bwd(dsaved, g_out, P, grads, side=None):
     side = side or ops._Inline()
     if len(dsaved) > 5:                # the fused decoder: its backward-data operands in one launch
         ops.pack_many(_decoder_pack_requests(P, c4.shape[2] // 4, True))
-    grads["decoder.4.weight"], grads["decoder.4.bias"] = side.run(
-        lambda: ops.outconv_bwd_weight(g_out, out, c4, pro=pro4), g_out, out, c4)
-    # the last BatchNorm's backward rebuilds the last conv's input gradient from go on the fly (never materialised)
+    # the last BatchNorm's backward rebuilds the last conv's input gradient from go on the fly (never materialised), and its sums pass
+    # leaves that conv's weight and bias gradient: c4 is streamed twice, not three times
     fuse_last = c4.shape[2] % 4 == 0
+    if not fuse_last:
+        grads["decoder.4.weight"], grads["decoder.4.bias"] = side.run(
+            lambda: ops.outconv_bwd_weight(g_out, out, c4, pro=pro4), g_out, out, c4)
     g_is_up = False
     g = None if fuse_last else ops.outconv_bwd_data(g_out, out, P["decoder.4.weight"], c4.shape[1])
     g_slots = None            # BatchNorm-backward sums the conv that produced g left in its epilogue
@@ -367,7 +370,8 @@ def decoder_bwd(dsaved, g_out, P, grads, side=None):
         wname, bname, pre = f"{blk}.double_conv.{cv}.weight", f"{blk}.double_conv.{cv}.bias", f"{blk}.double_conv.{bn}"
         pm0_done = False
         if li == 3 and fuse_last:
-            gc, gg, gbeta, gbias = ops.bn_relu_bwd_outconv(g_out, out, P["decoder.4.weight"], c, mean, invstd, a, b, passes)
+            gc, gg, gbeta, gbias, grads["decoder.4.weight"], grads["decoder.4.bias"] = ops.bn_relu_bwd_outconv(
+                g_out, out, P["decoder.4.weight"], c, mean, invstd, a, b, passes, outconv_w=True)
         elif li == 0 and shared_B is not None and not g_is_up:
             # gc is the per-half gradient [2B, 2*128, 2T] straight away (pass_combine_bwd fused into the apply pass)
             gc, gg, gbeta, gbias = ops.bn_relu_bwd_combine3(g, c, mean, invstd, a, b, slots=g_slots, phase_major=pm)
@@ -702,11 +706,13 @@ def _head_bwd(P, sv, g_outs, grads, side, relu_z1=False):
     gz2r = gz2b = None
     z2r, T = sv["z2r"], sv["latent"].shape[2]
     fused = z2r is None and gD.shape[2] == T and T <= ops.UNPOOL_MIX_MAX_T
+    gz1_sum = None             # chan_sum(gz1) where the kernel that stores gz1 forms it (relu_z1: what z1_conv's block would sum)
     if z2r is None and not fused:      # the gradient arrives upsampled, or its rows are too long for the strips: the two-pass form
         z2r = ops.roi_unpool_fwd(sv["z2b"], sv["rois"], T)
     if fused:                          # forward mixed straight from the segments: (gz1, gz2b), no gz2r, no un-pooling backward
-        gz1, gz2b, gq = ops.mix_bwd_shared_unpool(gD, sv["latent"], sv["z1"], sv["z2b"], sv["rois"], sv["q"], V, sv["choice"],
-                                                  relu_z1=relu_z1)
+        gz1, gz2b, gq, *rest = ops.mix_bwd_shared_unpool(gD, sv["latent"], sv["z1"], sv["z2b"], sv["rois"], sv["q"], V, sv["choice"],
+                                                         relu_z1=relu_z1, chan_sum=relu_z1)
+        gz1_sum = rest[0] if rest else None
     elif shared:
         gz1, gz2r, gq = ops.mix_bwd_shared_up(gD, sv["latent"], sv["z1"], z2r, sv["q"], V, sv["choice"],
                                               relu_z1=relu_z1)
@@ -715,15 +721,15 @@ def _head_bwd(P, sv, g_outs, grads, side, relu_z1=False):
                                     relu_z1=relu_z1)
     gW2, gb2 = side.run(lambda: ops.theta_mlp_bwd(sv["q_theta"], gq, 256), gq)
     grads["mlp2.weight"], grads["mlp2.bias"] = gW2, gb2
-    return gz1, gz2r, gz2b
+    return gz1, gz2r, gz2b, gz1_sum
 
 
 EARLY_HOOK = None      # callable(P, grads, side) invoked instead of parallel.early_reduce at the early-bucket point of backward()
 
 
-def _latents_bwd(P, sv, gz1, gz2r, grads, side, z1_pre_gated=False, early=False, gz2b=None):
+def _latents_bwd(P, sv, gz1, gz2r, grads, side, z1_pre_gated=False, early=False, gz2b=None, gz1_sum=None):
     """Back through `_latents` (+ the segment un-pooling that follows it, unless the caller already holds `gz2b`, the gradient
-    wrt the segment tensor): encoder-side parameter gradients."""
+    wrt the segment tensor): encoder-side parameter gradients.  `gz1_sum`: chan_sum(gz1) of a pre-gated gz1, where _head_bwd has it."""
     B, V, T = sv["B"], sv["V"], sv["T"]
     ops.pack_many(_latent_pack_requests(P, V, T, sv["z2_win"], True))
     if gz2b is None:
@@ -737,7 +743,8 @@ def _latents_bwd(P, sv, gz1, gz2r, grads, side, z1_pre_gated=False, early=False,
     gh0 = block_bwd(sv["blk_c20"], gh1, P, grads, side=side)
     genc = torch.empty(B, 128 * V, T, device=gz1.device, dtype=torch.float32)
     # z1_conv / z2_conv1 read the ReLU output of w_conv: they mask their input gradient with it, w_conv skips its gate
-    block_bwd(sv["blk_z1"], gz1, P, grads, out=GV.half(genc, V, 0), side=side, pre_gated=z1_pre_gated, gate_input=True)
+    block_bwd(sv["blk_z1"], gz1, P, grads, out=GV.half(genc, V, 0), side=side, pre_gated=z1_pre_gated, gate_input=True,
+              g2_chan_sum=gz1_sum if z1_pre_gated else None)
     win = sv["z2_win"]
     if win is not None:
         gz2c = ops.roi_align_bwd(gh0.view(B, 128 * V, N_SEG, ROI_BINS), sv["rois"], T, win[1], win[0])
@@ -768,8 +775,8 @@ def backward(P, sv, g_outs):
     """g_outs: gradients wrt (out, shuffle_p, shuffle_l), each [B,1,L] or None.  Returns {param name: grad}."""
     grads = {}
     side = _side(sv["z1"].device, sv["z1"].numel())
-    gz1, gz2r, gz2b = _head_bwd(P, sv, g_outs, grads, side, relu_z1=True)
-    _latents_bwd(P, sv, gz1, gz2r, grads, side, z1_pre_gated=True, early=True, gz2b=gz2b)
+    gz1, gz2r, gz2b, gz1_sum = _head_bwd(P, sv, g_outs, grads, side, relu_z1=True)
+    _latents_bwd(P, sv, gz1, gz2r, grads, side, z1_pre_gated=True, early=True, gz2b=gz2b, gz1_sum=gz1_sum)
     side.join()
     return grads
 
@@ -779,7 +786,7 @@ def backward2(P, sv, g_outs):
     gradients summed over the leads in lead order), then the folded-batch encoder."""
     grads = {}
     side = _side(sv["z1"].device, sv["z1"].numel())
-    gZ1, gZ2, _ = _head_bwd(P, sv, g_outs, grads, side)                           # [B, 128V, T]
+    gZ1, gZ2, _, _ = _head_bwd(P, sv, g_outs, grads, side)                           # [B, 128V, T]
     B, V = sv["fold"]
     T = gZ1.shape[2]
     gz1f = torch.empty(V * B, 128, T, device=gZ1.device, dtype=torch.float32)

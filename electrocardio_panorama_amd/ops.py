@@ -1385,9 +1385,10 @@ def lead_mean_mix_unpool(z1, z2b, rois, q, V, choice, T, status=None):
     return latent, D2
 
 
-def mix_bwd_shared_unpool(gD, latent, z1, z2b, rois, q, V, choice, relu_z1=False):
+def mix_bwd_shared_unpool(gD, latent, z1, z2b, rois, q, V, choice, relu_z1=False, chan_sum=False):
     """mix_bwd_shared_up (on the gradient wrt D2 itself, [2B,256,T]) + roi_unpool_bwd without gz2r between them:
-    (gz1 [B,128V,T], gz2b [B,128V,7,32], gq [B,256]), bit-identical to the two calls.  T <= UNPOOL_MIX_MAX_T."""
+    (gz1 [B,128V,T], gz2b [B,128V,7,32], gq [B,256]), bit-identical to the two calls.  T <= UNPOOL_MIX_MAX_T.
+    `chan_sum`: chan_sum(gz1) [128V] follows, formed by the kernel that stores gz1 where the shape allows."""
     L = _lib.load()
     c1, c2, cdev = _choice(choice)
     _chk(gD), _chk(latent), _chk(z1), _chk(z2b), _chk(q), _chk(rois, torch.int64)
@@ -1396,6 +1397,14 @@ def mix_bwd_shared_unpool(gD, latent, z1, z2b, rois, q, V, choice, relu_z1=False
     gz1, gz2b = torch.empty_like(z1), torch.empty_like(z2b)
     gq = torch.empty(B, 256, device=latent.device, dtype=torch.float32)
     ev = _hbm("mix_bwd_shared_unpool", gD, latent, z1, z2b, gz1, gz2b)
+    if chan_sum:
+        cs = torch.empty(128 * V, device=latent.device, dtype=torch.float32)
+        n = L.nef_mix_bwd_unpool_rs_ws_bytes(B, V)
+        ws = workspace(n, latent.device)
+        _lib.check(L.nef_mix_bwd_unpool_rs(_p(gD), _p(latent), _p(z1), _p(z2b), _p(rois), _p(q), _p(gz1), _p(gz2b), _p(gq), _p(cs), _p(ws),
+                                           n, None, B, V, T, c1, c2, cdev, int(relu_z1), _stream()), "nef_mix_bwd_unpool_rs")
+        _done(ev)
+        return gz1, gz2b, gq, cs
     _lib.check(L.nef_mix_bwd_unpool(_p(gD), _p(latent), _p(z1), _p(z2b), _p(rois), _p(q), _p(gz1), _p(gz2b), _p(gq), B, V, T, c1, c2,
                                     cdev, int(relu_z1), _stream()), "nef_mix_bwd_unpool")
     _done(ev)
@@ -1539,9 +1548,10 @@ def affine_relu_fwd(x, a, b, P):
     return y
 
 
-def _bn_bwd(form, tag, hbm, x, mean, invstd, a, b, P, gx, chan_sum=True, slots=None, phase_major=False, **grad):
+def _bn_bwd(form, tag, hbm, x, mean, invstd, a, b, P, gx, chan_sum=True, slots=None, phase_major=False, outconv_w=False, **grad):
     """One nef_bn_relu_bwd call of kernel family `form` (nef_bn_bwd_args) writing into `gx`.  `grad`: g=..., or gout= / out= / wout=
-    for form 1; `hbm`: the tensors the `tag` launch is priced by.  Returns (gx, ggamma, gbeta, sum_{b,t} gx per channel or None)."""
+    for form 1; `hbm`: the tensors the `tag` launch is priced by.  Returns (gx, ggamma, gbeta, sum_{b,t} gx per channel or None);
+    `outconv_w` (form 1): nef_bn_relu_bwd_outconv_w, and the last conv's (gw [1,C,3], gb [1]) follow."""
     L = _lib.load()
     N, Ct, Ln = x.shape
     gg = torch.empty(Ct, device=x.device, dtype=torch.float32)
@@ -1551,6 +1561,17 @@ def _bn_bwd(form, tag, hbm, x, mean, invstd, a, b, P, gx, chan_sum=True, slots=N
                        gx_chan_sum=_p(gs), slots=_p(slots[0]) if slots else None, nslot=slots[1] if slots else 0, P=P, Bp=N // P,
                        C=Ct, L=Ln, form=form, phase_major=int(phase_major), **{k: _p(t) for k, t in grad.items()})
     A.ws_bytes = L.nef_bn_bwd_ws_bytes(C.byref(A))
+    if outconv_w:
+        gw = torch.empty(1, Ct, 3, device=x.device, dtype=torch.float32)
+        gbo = torch.empty(1, device=x.device, dtype=torch.float32)
+        n2, off = L.nef_bn_relu_bwd_outconv_w_ws_bytes(C.byref(A)), (A.ws_bytes + 255) // 256 * 256
+        ws = workspace(off + n2, x.device)      # one buffer per stream: the second workspace sits behind the first
+        A.ws = _p(ws)
+        ev = _hbm(tag, *hbm)
+        _lib.check(L.nef_bn_relu_bwd_outconv_w(C.byref(A), _p(gw), _p(gbo), ws.data_ptr() + off, n2, _stream()),
+                   "nef_bn_relu_bwd_outconv_w")
+        _done(ev)
+        return gx, gg, gb, gs, gw, gbo
     A.ws = _p(workspace(A.ws_bytes, x.device))
     ev = _hbm(tag, *hbm)
     _lib.check(L.nef_bn_relu_bwd(C.byref(A), _stream()), f"nef_bn_relu_bwd form {form}")
@@ -1591,15 +1612,16 @@ def bn_relu_bwd_up(gu, x, mean, invstd, a, b, P, slots=None):
     return _bn_bwd(2, "bn_relu_bwd_up", (gu, x, gx), x, mean, invstd, a, b, P, gx, slots=slots, g=gu)
 
 
-def bn_relu_bwd_outconv(gout, out, wout, x, mean, invstd, a, b, P):
+def bn_relu_bwd_outconv(gout, out, wout, x, mean, invstd, a, b, P, outconv_w=False):
     """bn_relu_bwd(outconv_bwd_data(gout, out, wout), x, ...) without materialising the [N,C,L] gradient in between.
-    Returns (gx, ggamma, gbeta, sum_{b,t} gx per channel)."""
+    Returns (gx, ggamma, gbeta, sum_{b,t} gx per channel); with `outconv_w` the reduction pass also forms what
+    outconv_bwd_weight(gout, out, x, pro=(a, b, N // P)) returns, and (gw, gb) follow."""
     _chk(gout), _chk(out), _chk(x)
     gx = torch.empty_like(x)
     # a two-pass pair by construction (the reduction pass reads x, the apply pass reads it again and writes gx): priced by
     # what the pair has to move -- 2 reads + 1 write of the [N, C, L] tensor (+ the small gout / out rows twice)
-    return _bn_bwd(1, "bn_relu_bwd_outconv", (gout, out, x, gout, out, x, gx), x, mean, invstd, a, b, P, gx, gout=gout, out=out,
-                   wout=wout)
+    return _bn_bwd(1, "bn_relu_bwd_outconv", (gout, out, x, gout, out, x, gx), x, mean, invstd, a, b, P, gx, outconv_w=outconv_w,
+                   gout=gout, out=out, wout=wout)
 
 
 def outconv_fwd(x, w, bias, pro=None):

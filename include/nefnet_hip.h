@@ -412,6 +412,15 @@ int nef_lead_mean_mix_unpool(const float* z1, const float* z2b, const int64_t* r
 int nef_mix_bwd_unpool(const float* gD, const float* latent, const float* z1, const float* z2b, const int64_t* rois, const float* q,
                        float* gz1, float* gz2b, float* gq, int B, int V, int T, int c1, int c2, const int32_t* choice_dev, int relu_z1,
                        nef_stream_t stream);
+/* nef_mix_bwd_unpool that also leaves gz1_chan_sum [128V] = sum_{b,t} gz1[b][c][t] of the gz1 it stores (after the relu_z1 mask): the bias
+ * gradient of the residual 1x1 conv that reads gz1, without reading gz1 back.  gz1, gz2b and gq are bit-identical to nef_mix_bwd_unpool.
+ * Where the 16-byte pair kernel runs (T % 4 == 2, T >= 8, 16-byte aligned tensors) and V <= 4 it adds what it stores, in fp64 from the first
+ * element, per (sample, lead, channel) row, and the rows are summed over the samples in a fixed order; *in_kernel (may be NULL) is then
+ * 1.  Otherwise the sum is taken by nef_chan_sum over the stored gz1 and *in_kernel is 0.  ws: nef_mix_bwd_unpool_rs_ws_bytes(B, V). */
+int nef_mix_bwd_unpool_rs(const float* gD, const float* latent, const float* z1, const float* z2b, const int64_t* rois, const float* q,
+                          float* gz1, float* gz2b, float* gq, float* gz1_chan_sum, void* ws, size_t ws_bytes, int* in_kernel, int B, int V,
+                          int T, int c1, int c2, const int32_t* choice_dev, int relu_z1, nef_stream_t stream);
+size_t nef_mix_bwd_unpool_rs_ws_bytes(int B, int V);
 int nef_pass_combine_fwd(const float* P2, const float* bias, float* c1, int B, int C, int L, nef_stream_t stream);
 /* nef_pass_combine_fwd that also leaves the train-mode BatchNorm statistics of its output (3 passes of B samples; same
  * outputs as nef_bn_train_stats(c1, ..., P = 3, Bp = B, ...), running statistics updated pass by pass): saves the separate
@@ -504,6 +513,14 @@ int nef_bn_relu_bwd(const nef_bn_bwd_args* a, nef_stream_t stream);
 size_t nef_bn_bwd_ws_bytes(const nef_bn_bwd_args* a);
 /* sizeof(nef_bn_bwd_args) as the library was built: a binding checks its mirror of the struct against it. */
 size_t nef_bn_bwd_args_bytes(void);
+/* nef_bn_relu_bwd form 1 whose sums pass also leaves the gradients of the last Conv1d(C->1, k3, p1, bias) (model_nefnet.py:106,168):
+ * gwout [1][C][3] and gbout [1], the outputs of nef_outconv_bwd_weight with x' = max(0, x*a + b), formed from the go values and the
+ * x*a + b the pass already holds, so the [P*Bp][C][L] tensor is not streamed a third time.  gx, ggamma, gbeta and gx_chan_sum are
+ * bit-identical to nef_bn_relu_bwd; gwout / gbout add in fp32 inside a lane's share of one sample row and in fp64, in a fixed order,
+ * from there on.  Any form but 1 is NEF_E_UNSUPPORTED.  ws2: nef_bn_relu_bwd_outconv_w_ws_bytes (0 for a form other than 1), apart from
+ * a->ws. */
+int nef_bn_relu_bwd_outconv_w(const nef_bn_bwd_args* a, float* gwout, float* gbout, void* ws2, size_t ws2_bytes, nef_stream_t stream);
+size_t nef_bn_relu_bwd_outconv_w_ws_bytes(const nef_bn_bwd_args* a);
 
 /* Final Conv1d(64->1,k3,p1,bias) + sigmoid(x/3).  model_nefnet.py:106,168.
  *   x [N][C][L], w [1][C][3], bias [1], out [N][L].
