@@ -79,6 +79,13 @@ class TrustArgs(C.Structure):
                 ("ws_bytes", sz), ("trust_coef", f32), ("trust_eps", f32), ("n_segs", i32), ("reserved0", i32)]
 
 
+class LrSchedArgs(C.Structure):
+    """Mirror of `nef_lr_sched_args` (include/nefnet_hip.h)."""
+    _fields_ = [("t", p), ("base_dev", p), ("lr_out", p), ("skip_if_positive", p), ("flag", p), ("warmup_updates", i64),
+                ("total_updates", i64), ("base", C.c_double), ("warmup_start", C.c_double), ("lr_floor", C.c_double),
+                ("poly_power", C.c_double), ("shape", i32), ("advance", i32)]
+
+
 class PackDesc(C.Structure):
     """Mirror of `nef_pack_desc` (include/nefnet_hip.h)."""
     _fields_ = [("w", p), ("wp", p), ("G", i32), ("Cog", i32), ("Cig", i32), ("K", i32), ("transpose_flip", i32),
@@ -170,6 +177,8 @@ SIGNATURES = {
     "nef_update_trust": (i32, [C.POINTER(UpdateArgs), C.POINTER(TrustArgs), C.POINTER(EmaArgs), p]),
     "nef_update_trust_ws_bytes": (sz, [i64, i32]),
     "nef_trust_args_bytes": (sz, []),
+    "nef_lr_sched": (i32, [C.POINTER(LrSchedArgs), p]),
+    "nef_lr_sched_args_bytes": (sz, []),
     "nef_grad_clip_ws_bytes": (sz, []),
     "nef_grad_clip": (i32, [p, i64, f32, f32, p, p, p, sz, p]),
     "nef_h2_taint": (i32, [p, p, p, p]),
@@ -212,7 +221,11 @@ def load():
             "Build it with `python -m electrocardio_panorama_amd.csrc.build`.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)        # AttributeError if the symbol is not exported
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:         # a stale .so whose ABI number did not move (additions keep it): the missing symbol tells
+            raise NefLibraryError(f"{LIB_PATH} does not export {name}: it is older than this binding; rebuild with "
+                                  "`python -m electrocardio_panorama_amd.csrc.build`") from None
         fn.restype = res
         fn.argtypes = args
     # a stale .so next to a newer binding (or the reverse)
@@ -221,7 +234,8 @@ def load():
                                ("nef_bn_bwd_args", lib.nef_bn_bwd_args_bytes(), BnBwdArgs),
                                ("nef_update_args", lib.nef_update_args_bytes(), UpdateArgs),
                                ("nef_ema_args", lib.nef_ema_args_bytes(), EmaArgs),
-                               ("nef_trust_args", lib.nef_trust_args_bytes(), TrustArgs)):
+                               ("nef_trust_args", lib.nef_trust_args_bytes(), TrustArgs),
+                               ("nef_lr_sched_args", lib.nef_lr_sched_args_bytes(), LrSchedArgs)):
         if size != C.sizeof(mirror):
             raise NefLibraryError(f"{LIB_PATH}: {name} is {size} bytes, the binding mirrors {C.sizeof(mirror)}; rebuild with "
                                   "`python -m electrocardio_panorama_amd.csrc.build`")

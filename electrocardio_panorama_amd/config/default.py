@@ -84,6 +84,22 @@ _DEFAULTS = {
         # per window on the mean over its micro-batches (and ranks), in the eager and the graphed step.  A window never crosses an epoch:
         # the last, incomplete one is flushed on the micro-batches it has.  1 = off: the launches and graphs are what they were
         "accum_steps": 1,
+        # a per-update learning-rate schedule on the device, behind every fused optimiser's update (nef_lr_sched: one single-wave launch,
+        # in the eager and the graphed step): the update's rate is group lr -- what the per-epoch `scheduler` sets -- times m(t), t the
+        # number of updates APPLIED so far (a skipped step does not count; with accum_steps, updates, not micro-batches).
+        # t < warmup_updates: m = warmup_start + (1 - warmup_start) * t / warmup_updates (torch's LinearLR).  Behind it, with
+        # x = clamp((t - warmup_updates) / max(1, total_updates - warmup_updates), 0, 1), lr_shape 'const': m = 1; 'cosine':
+        # m = lr_floor + (1 - lr_floor) * (1 + cos(pi * x)) / 2 (CosineAnnealingLR); 'poly': m = lr_floor + (1 - lr_floor) * (1 - x)^poly_power
+        # (PolynomialLR at lr_floor 0); 'none' with a warm-up behaves as 'const'.  warmup_updates 0 and lr_shape 'none' = off: no device
+        # word, no launch, the scheduler object and the bits are what they were before the keys existed
+        "warmup_updates": 0,
+        "warmup_start": 0.01,       # in [0, 1]
+        "lr_shape": "none",         # 'none', 'const', 'cosine' or 'poly'
+        # the update at which the shape reaches its end value (kept from there on); 0 = Solver.train derives it before the first step as
+        # epochs * ceil(len(dl_train) / accum_steps)
+        "total_updates": 0,
+        "lr_floor": 0.0,            # in [0, 1]: the end value as a fraction of group lr
+        "poly_power": 1.0,          # > 0
     },
 }
 

@@ -1926,6 +1926,41 @@ __global__ void trust_step_kernel(float* step, float* n_averaged, const float* _
 }
 
 // ------------------------------------------------------------------------------------------------
+// nef_lr_sched: the per-update learning-rate schedule (warm-up, then const / cosine / poly), one single-wave launch behind the update
+// ------------------------------------------------------------------------------------------------
+// m(t) over the count t of APPLIED updates, in fp64, in the operation order of the closed forms the header writes out (the host
+// restatement in solver/optim_scheduler.py uses the same order).  N <= W: the span is 1, so x is 0 at t == W and 1 behind it; W == 0:
+// the warm-up branch is never taken (t >= 0), nothing divides by W.
+__device__ __forceinline__ double lr_sched_factor(int64_t t, int64_t W, int64_t N, double s, double f, double p, int shape) {
+    if (t < 0) t = 0;
+    if (t < W) return s + (1.0 - s) * (double)t / (double)W;
+    if (shape == 0) return 1.0;
+    const int64_t span = N - W > 1 ? N - W : 1;
+    double x = (double)(t - W) / (double)span;
+    x = x < 0.0 ? 0.0 : (x > 1.0 ? 1.0 : x);
+    if (shape == 1) return f + (1.0 - f) * (1.0 + cos(3.14159265358979323846 * x)) / 2.0;
+    return f + (1.0 - f) * pow(1.0 - x, p);
+}
+
+// Lane 0 of one wave.  advance: the rule of adam_step_kernel / trust_step_kernel on the same words -- a positive skip word or trust
+// flag means the update in front was not applied: t and the rate word keep their bits; otherwise t += 1 and the rate of the NEXT
+// update is written.  Without advance only the rate is re-evaluated (at build time, or after the host changed the base rate).
+__global__ __launch_bounds__(64) void lr_sched_kernel(int64_t* __restrict__ t_word, const double* __restrict__ base_dev, double base,
+                                                      float* __restrict__ lr_out, const float* __restrict__ skip,
+                                                      const float* __restrict__ flag, int advance, int64_t W, int64_t N, double s, double f,
+                                                      double p, int shape) {
+    if (threadIdx.x != 0) return;
+    int64_t t = t_word[0];
+    if (advance) {
+        if ((skip && skip[0] > 0.f) || (flag && flag[0] > 0.f)) return;
+        t += 1;
+        t_word[0] = t;
+    }
+    if (base_dev) base = base_dev[0];
+    lr_out[0] = (float)(base * lr_sched_factor(t, W, N, s, f, p, shape));      // fp64 product, rounded once
+}
+
+// ------------------------------------------------------------------------------------------------
 // Round 6: the last torch elementwise kernels of the train step, as one launch each.
 // amax_roll: ops.amax_roll's follow-up rule on the split-fp16 site table (was ~10 ATen launches: compares, ors, where, fill).
 __global__ __launch_bounds__(256) void amax_roll_kernel(float* __restrict__ cur, float* __restrict__ nxt, int n, float up, float down,
@@ -3151,6 +3186,25 @@ int nef_update_trust(const nef_update_args* args, const nef_trust_args* t, const
         if (e) trust_launch<1, true>(a, *t, e, NEF_ST);
         else trust_launch<1, false>(a, *t, nullptr, NEF_ST);
     }
+    return nef_launch_status();
+}
+
+size_t nef_lr_sched_args_bytes(void) { return sizeof(nef_lr_sched_args); }
+
+int nef_lr_sched(const nef_lr_sched_args* args, nef_stream_t stream) {
+    NEF_ENTER();
+    NEF_REQUIRE(args, NEF_E_NULL);
+    const nef_lr_sched_args& a = *args;
+    NEF_REQUIRE(a.t && a.lr_out, NEF_E_NULL);
+    NEF_REQUIRE(a.shape >= 0 && a.shape <= 2, NEF_E_UNSUPPORTED);
+    NEF_REQUIRE(a.advance == 0 || a.advance == 1, NEF_E_SHAPE);
+    NEF_REQUIRE(a.warmup_updates >= 0 && a.total_updates >= 0, NEF_E_SHAPE);
+    // (a NaN fails every comparison)
+    NEF_REQUIRE(a.warmup_start >= 0.0 && a.warmup_start <= 1.0 && a.lr_floor >= 0.0 && a.lr_floor <= 1.0, NEF_E_SHAPE);
+    NEF_REQUIRE(a.poly_power > 0.0 && a.poly_power <= 1.7e308, NEF_E_SHAPE);
+    NEF_REQUIRE(a.base_dev || (a.base >= 0.0 && a.base <= 1.7e308), NEF_E_SHAPE);
+    hipLaunchKernelGGL(lr_sched_kernel, dim3(1), dim3(64), 0, NEF_ST, a.t, a.base_dev, a.base, a.lr_out, a.skip_if_positive, a.flag,
+                       a.advance, a.warmup_updates, a.total_updates, a.warmup_start, a.lr_floor, a.poly_power, a.shape);
     return nef_launch_status();
 }
 

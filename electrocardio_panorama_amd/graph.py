@@ -25,6 +25,11 @@ micro-batch replays the same graph and shapes share the window); the taint word,
 eagerly behind the window's last replay -- a handful of launches the host queues while the device is still inside the replay, with
 the window's own gscale, which a captured update would have frozen.  The window position is the optimiser's (`_acc_n`), so eager and
 replayed micro-batches mix.  K == 1: nothing of this runs.
+
+The per-update learning-rate schedule (the optimiser's lr_schedule): `_device_update` reads the optimiser's own rate word and issues the
+single-wave nef_lr_sched launch behind the update -- inside the graph where the update is (single process), behind the all-reduces where
+it is issued eagerly (data parallel, accumulation).  The rate changes from replay to replay with no host write between them; the
+schedule's numbers are among the frozen scalars.  The stepper with private buffers (optimizer=None) has no schedule.
 """
 import random
 
@@ -430,6 +435,9 @@ class GraphedTrainStep:
                 self.mu = float(g.get("momentum", self.mu))
                 self.slots.clear()
             self.set_lr(g["lr"])                               # a scheduler stepped: the device word follows, nothing is re-captured
+            # the per-update schedule (optimizer.lr_schedule): the captured update reads the optimiser's rate word and the captured
+            # nef_lr_sched launch behind it writes the next rate -- nothing to do here unless the host changed the base rate
+            self.optimizer._sched_sync()
             fl = self.optimizer._flat.get(0)
             if self.flat_p is not None and (fl is None or fl["p"] is not self.flat_p):   # e.g. optimizer.load_state_dict
                 self.slots.clear()

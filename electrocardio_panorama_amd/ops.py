@@ -1884,6 +1884,9 @@ def _update_trust(tag, hbm, rule, p, g, lr, gscale, weight_decay, segs, ratio, s
                        taint=_p(taint), ws=_p(ws), ws_bytes=nws, trust_coef=float(trust_coef), trust_eps=float(trust_eps), n_segs=S)
     _lib.check(L.nef_update_trust(C.byref(A), C.byref(T), None if E is None else C.byref(E), _stream()), "nef_update_trust")
     _done(ev)
+    # the call's trust flag (> 0: norms not finite or a positive skip word -- nothing was applied): the fp32 word at the start of the
+    # workspace's last 16 bytes, valid in stream order until the next call that takes the workspace (lr_sched(flag=) reads it)
+    return ws[nws - 16:nws - 12].view(torch.float32)
 
 
 def update_lars(p, g, buf, lr, mu, gscale, segs, ratio, stats, trust_coef=1e-3, trust_eps=1e-8, weight_decay=0.0, nesterov=False,
@@ -1894,10 +1897,11 @@ def update_lars(p, g, buf, lr, mu, gscale, segs, ratio, stats, trust_coef=1e-3, 
     device tensors, one entry per parameter tensor.  `ratio` [S] receives the q_s of this call; `stats` (4 words): [0] / [1] the smallest
     / largest q_s over the adapted segments, [2] += 1 when the call updated, [3] += 1 when a norm was not finite -- such a call changes
     nothing else but `taint` (+= 1 when given) and counts in h2_skipped().  `skip`, `lr_dev`, `ema`: as for update_sgd.  The norms are
-    deterministic fp64 sums: the same buffers give the same bits eagerly, under graph replay and on every rank.  Capturable."""
+    deterministic fp64 sums: the same buffers give the same bits eagerly, under graph replay and on every rank.  Capturable.  Returns the
+    call's trust flag, a one-element fp32 device view (> 0: nothing was applied) for lr_sched(flag=)."""
     _chk(buf)
     assert buf.numel() == p.numel()
-    _update_trust("update_lars", (p, g, p, p, g, buf, buf), 0, p, g, lr, gscale, weight_decay, segs, ratio, stats, trust_coef, trust_eps,
+    return _update_trust("update_lars", (p, g, p, p, g, buf, buf), 0, p, g, lr, gscale, weight_decay, segs, ratio, stats, trust_coef, trust_eps,
                   skip, lr_dev, taint, ema, buf=_p(buf), mu=mu, nesterov=int(bool(nesterov)))
 
 
@@ -1908,8 +1912,40 @@ def update_lamb(p, g, m, v, step, lr, beta1, beta2, eps, weight_decay, gscale, s
     is 0 or a norm is 0).  `segs`, `ratio`, `stats`, `taint`, `skip`, `lr_dev`, `ema`: as for update_lars."""
     _chk(m), _chk(v), _chk(step)
     assert p.numel() == m.numel() == v.numel() and step.numel() == 1
-    _update_trust("update_lamb", (p, g, m, v, p, p, g, m, m, v, v), 1, p, g, lr, gscale, weight_decay, segs, ratio, stats, 0.0, 0.0,
+    return _update_trust("update_lamb", (p, g, m, v, p, p, g, m, m, v, v), 1, p, g, lr, gscale, weight_decay, segs, ratio, stats, 0.0, 0.0,
                   skip, lr_dev, taint, ema, m=_p(m), v=_p(v), step=_p(step), beta1=beta1, beta2=beta2, eps=eps)
+
+
+LR_SHAPES = {"const": 0, "cosine": 1, "poly": 2}
+
+
+def lr_sched(t, lr_out, base, shape, warmup_updates=0, warmup_start=0.01, total_updates=0, lr_floor=0.0, poly_power=1.0, advance=True,
+             skip=None, flag=None):
+    """The per-update learning-rate schedule, one single-wave launch (nef_lr_sched, include/nefnet_hip.h).  `t`: a one-element int64
+    device tensor, the updates applied so far; `lr_out`: a one-element fp32 device tensor, the rate the next update reads as `lr_dev`;
+    `base`: a one-element fp64 device tensor or a Python float; `shape`: 'const', 'cosine' or 'poly'.  advance: behind an update --
+    t += 1 and lr_out = (float)(base * m(t)) unless `skip` (the update's skip word) or `flag` (update_lars' / update_lamb's return) is
+    positive, which leaves both words alone.  advance False: lr_out = (float)(base * m(t)) and nothing else.  Capturable."""
+    L = _lib.load()
+    _chk(t, torch.int64), _chk(lr_out)
+    assert t.numel() == 1 and lr_out.numel() == 1
+    base_dev = None
+    if torch.is_tensor(base):
+        base_dev, base = _chk(base, torch.float64), 0.0
+        assert base_dev.numel() == 1
+    if skip is not None:
+        _chk(skip)
+    if flag is not None:
+        _chk(flag)
+    if shape not in LR_SHAPES:
+        raise ValueError(f"Invalid lr shape: {shape!r}")
+    ev = _timed(("lr_sched", "advance" if advance else "evaluate"))
+    A = _lib.LrSchedArgs(t=_p(t), base_dev=_p(base_dev), lr_out=_p(lr_out), skip_if_positive=_p(skip), flag=_p(flag),
+                         warmup_updates=int(warmup_updates), total_updates=int(total_updates), base=float(base),
+                         warmup_start=float(warmup_start), lr_floor=float(lr_floor), poly_power=float(poly_power),
+                         shape=LR_SHAPES[shape], advance=int(bool(advance)))
+    _lib.check(L.nef_lr_sched(C.byref(A), _stream()), "nef_lr_sched")
+    _done(ev)
 
 
 def grad_clip(g, max_norm, gscale, stats, taint=None):

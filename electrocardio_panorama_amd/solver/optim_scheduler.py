@@ -13,9 +13,14 @@ one norm pair per parameter tensor by a deterministic segmented reduction, then 
 SOLVER.trust_exempt (tensors whose ratio stays 1).
 SOLVER.accum_steps = K > 1 makes every fused optimiser accumulate: step() sums p.grad into the flat gradient buffer (nef_flatten_acc) and its
 K-th call -- or flush() on an incomplete window -- takes the taint word, all-reduces, clips and updates once, on the mean over the window.
+SOLVER.warmup_updates / SOLVER.lr_shape put a per-update learning-rate schedule behind every fused optimiser (LrSchedule, lr_factor): the
+update reads its rate from a device word, and one single-wave launch behind it (nef_lr_sched) advances the device-side count of APPLIED
+updates and writes base * m(t) for the next one -- no host work per update, a skipped step moves neither.  get_lr_scheduler then wraps
+the per-epoch scheduler in ScheduledLR, whose state dict carries the count.
 DataParallelAdam (torch Adam behind a separate all-reduce) is kept as the unfused comparison."""
 import contextlib
 import fnmatch
+import math
 from collections import OrderedDict
 
 import torch
@@ -74,6 +79,76 @@ def trust_segments(names, sizes, no_decay, trust_exempt):
     return ends, wd_muls, adapts
 
 
+LR_SHAPES = ('none', 'const', 'cosine', 'poly')
+
+
+def lr_factor(t, warmup_updates=0, warmup_start=0.01, lr_shape='const', total_updates=0, lr_floor=0.0, poly_power=1.0):
+    """m(t) of the per-update schedule in Python floats (fp64), in the operation order of the device's lr_sched_factor
+    (csrc/elementwise.hip): the host restatement the tests pin to torch's LinearLR / CosineAnnealingLR / PolynomialLR and compare the
+    kernel against.  `t`: updates applied so far (the first update uses m(0)).  t < W: s + (1 - s) * t / W.  Behind the warm-up, with
+    x = clamp((t - W) / max(1, N - W), 0, 1): 'const' (and 'none') 1; 'cosine' f + (1 - f) * (1 + cos(pi * x)) / 2; 'poly'
+    f + (1 - f) * (1 - x)^p -- the end value is kept for t >= N."""
+    t, W, N = max(int(t), 0), int(warmup_updates), int(total_updates)
+    s, f, p = float(warmup_start), float(lr_floor), float(poly_power)
+    if t < W:
+        return s + (1.0 - s) * float(t) / float(W)
+    if lr_shape in ('none', 'const'):
+        return 1.0
+    x = min(max(float(t - W) / float(max(1, N - W)), 0.0), 1.0)
+    if lr_shape == 'cosine':
+        return f + (1.0 - f) * (1.0 + math.cos(math.pi * x)) / 2.0
+    if lr_shape == 'poly':
+        return f + (1.0 - f) * (1.0 - x) ** p
+    raise ValueError(f"Invalid lr_shape value: {lr_shape!r}")
+
+
+class LrSchedule:
+    """The validated numbers of the per-update schedule (SOLVER.warmup_updates, warmup_start, lr_shape, total_updates, lr_floor,
+    poly_power).  `on`: warmup_updates > 0 or lr_shape != 'none'; 'none' with a warm-up behaves as 'const'.  total_updates may be
+    assigned later (Solver.train derives it before the first step); the optimiser re-evaluates its rate word when a number changed."""
+
+    def __init__(self, warmup_updates=0, warmup_start=0.01, lr_shape='none', total_updates=0, lr_floor=0.0, poly_power=1.0):
+        for key, v in (("warmup_updates", warmup_updates), ("total_updates", total_updates)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise ValueError(f"Invalid {key} value: {v!r}")
+        if lr_shape not in LR_SHAPES:
+            raise ValueError(f"Invalid lr_shape value: {lr_shape!r} (one of {', '.join(LR_SHAPES)})")
+        for key, v in (("warmup_start", warmup_start), ("lr_floor", lr_floor)):
+            if isinstance(v, (bool, str)) or not 0.0 <= float(v) <= 1.0:      # (NaN fails the comparison too)
+                raise ValueError(f"Invalid {key} value: {v!r}")
+        if isinstance(poly_power, (bool, str)) or not 0.0 < float(poly_power) < math.inf:
+            raise ValueError(f"Invalid poly_power value: {poly_power!r}")
+        self.warmup_updates, self.total_updates = warmup_updates, total_updates
+        self.warmup_start, self.lr_floor, self.poly_power = float(warmup_start), float(lr_floor), float(poly_power)
+        self.lr_shape = lr_shape
+
+    @classmethod
+    def from_cfg(cls, cfg):
+        S = cfg.SOLVER      # (.get: configs written before the keys existed)
+        return cls(S.get('warmup_updates', 0), S.get('warmup_start', 0.01), S.get('lr_shape', 'none'), S.get('total_updates', 0),
+                       S.get('lr_floor', 0.0), S.get('poly_power', 1.0))
+
+    @property
+    def on(self):
+        return self.warmup_updates > 0 or self.lr_shape != 'none'
+
+    def kwargs(self):
+        """The keyword arguments of ops.lr_sched / lr_factor's keywords under ops' names."""
+        return dict(shape='const' if self.lr_shape == 'none' else self.lr_shape, warmup_updates=self.warmup_updates,
+                    warmup_start=self.warmup_start, total_updates=self.total_updates, lr_floor=self.lr_floor, poly_power=self.poly_power)
+
+    def scalars(self):
+        k = self.kwargs()
+        return (k["shape"], k["warmup_updates"], k["warmup_start"], k["total_updates"], k["lr_floor"], k["poly_power"])
+
+    def state_dict(self):
+        return dict(warmup_updates=self.warmup_updates, warmup_start=self.warmup_start, lr_shape=self.lr_shape,
+                    total_updates=self.total_updates, lr_floor=self.lr_floor, poly_power=self.poly_power)
+
+    def factor(self, t):
+        return lr_factor(t, **self.state_dict())
+
+
 class _FusedFlat(torch.optim.Optimizer):
     """Flat-buffer machinery of the fused optimisers: the live parameters of a group become views of one flat fp32 buffer, the
     per-element state (`_SLOTS`: flat key -> torch state key) views of flat buffers of the same layout, and a step is ONE
@@ -84,8 +159,17 @@ class _FusedFlat(torch.optim.Optimizer):
     BatchNorm running statistics its forward pass already updated are NOT rolled back (DESIGN.md 3.0 "Range")."""
     _SLOTS = ()
 
-    def __init__(self, params, defaults, max_grad_norm=0.0, no_decay=(), ema_decay=0.0, ema_warmup=False, accum_steps=1):
+    def __init__(self, params, defaults, max_grad_norm=0.0, no_decay=(), ema_decay=0.0, ema_warmup=False, accum_steps=1, lr_schedule=None):
         super().__init__(params, defaults)
+        # the per-update learning-rate schedule (LrSchedule; None or one that is not `on`: off -- no word, no launch, lr travels as it
+        # did).  On: every _device_update reads its rate from the group's device word (eagerly as well) and the nef_lr_sched launch
+        # behind it advances the count of applied updates and writes the next rate.  An attribute like max_grad_norm, NOT a param_groups
+        # key.  The words live outside `_flat`: they survive a rebuild and load_state_dict, and captured launches keep their addresses
+        if lr_schedule is not None and not isinstance(lr_schedule, LrSchedule):
+            raise ValueError(f"Invalid lr_schedule value: {lr_schedule!r}")
+        self.lr_schedule = lr_schedule
+        self._sched = {}             # group index -> dict(t int64 word, base fp64 word, lr fp32 word, host: what the lr word was evaluated for)
+        self._sched_pending = None   # set_lr_updates() before the words exist: the count they start from
         # gradient accumulation: step() folds p.grad into the flat gradient buffer (the first micro-batch of a window assigns, the later
         # ones add: ops.flatten_into(accumulate=)) and only its accum_steps-th call takes the taint word, all-reduces, clips and updates,
         # with gscale = 1 / (world * accum_steps); flush() closes an incomplete window.  1 = off: step() is what it was.  An attribute like
@@ -194,8 +278,8 @@ class _FusedFlat(torch.optim.Optimizer):
 
     def _ema_scalars(self):
         """The part of `_captured_scalars` every fused optimiser shares: a captured update freezes the decay and the warm-up flag (the
-        count of EMA updates lives on the device: a replay needs nothing)."""
-        return (float(self.ema_decay), bool(self.ema_warmup))
+        count of EMA updates lives on the device: a replay needs nothing), and the learning-rate schedule's numbers when it is on."""
+        return (float(self.ema_decay), bool(self.ema_warmup)) + self._sched_scalars()
 
     def ema_state_dict(self, model):
         """The averaged model for a checkpoint: {"decay", "warmup", "n_averaged", "model"}; "model" has exactly the keys of
@@ -277,7 +361,86 @@ class _FusedFlat(torch.optim.Optimizer):
                                    "accumulated micro-batches; flush() the window first")
             self._build(gi, live)
             fl = self._flat[gi]
+        if self._sched_on:
+            self._sched_words(gi, fl["p"].device)      # made (and brought up to date) before anything can be captured
         return fl
+
+    # ---------------------------------------------------------------- the per-update learning-rate schedule
+    @property
+    def _sched_on(self):
+        return self.lr_schedule is not None and self.lr_schedule.on
+
+    def _sched_scalars(self):
+        """The part of `_captured_scalars` the schedule adds: a captured nef_lr_sched launch freezes its shape numbers (off: nothing)."""
+        return self.lr_schedule.scalars() if self._sched_on else ()
+
+    def _sched_gi(self, group):
+        return next(i for i, g in enumerate(self.param_groups) if g is group)
+
+    def _sched_words(self, gi, device=None):
+        """The schedule's device words of group `gi`, made at first use (the count starts at what set_lr_updates left, else 0) and
+        brought up to date: when group["lr"] (the per-epoch scheduler), a shape number or the count was changed by the host, the base
+        word is refreshed and the rate re-evaluated WITHOUT advancing.  Never inside a capture: _current and GraphedTrainStep.__call__
+        come here first."""
+        sc, group = self.lr_schedule, self.param_groups[gi]
+        w = self._sched.get(gi)
+        if w is None:
+            # one count for every group: a group built later starts where the others are (a device copy, nothing is read)
+            t = next(iter(self._sched.values()))["t"].clone() if self._sched else torch.full(
+                (1,), int(self._sched_pending or 0), device=device, dtype=torch.int64)
+            w = self._sched[gi] = dict(t=t, base=torch.zeros(1, device=device, dtype=torch.float64),
+                                       lr=torch.zeros(1, device=device, dtype=torch.float32), host=None)
+            self._sched_pending = None
+        key = (float(group["lr"]),) + sc.scalars()
+        if w["host"] != key:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the learning-rate schedule's base rate changed inside a graph capture")
+            w["base"].fill_(float(group["lr"]))
+            ops.lr_sched(w["t"], w["lr"], w["base"], advance=False, **sc.kwargs())
+            w["host"] = key
+        return w
+
+    def _sched_sync(self):
+        """Every existing rate word follows a host change of group["lr"] or of the schedule's numbers (no launch when nothing changed)."""
+        if self._sched_on:
+            for gi in self._sched:
+                self._sched_words(gi)
+
+    def _sched_lr(self, fl, group, lr_dev):
+        """The rate word `_device_update` hands to its launch: the schedule's when it is on, else the caller's (None: the scalar)."""
+        if not self._sched_on:
+            return lr_dev
+        return self._sched_words(self._sched_gi(group), fl["p"].device)["lr"]
+
+    def _sched_advance(self, group, skip, flag=None):
+        """Behind the update launch: the count advances and the next rate is written, unless the update was not applied (the skip word;
+        lars / lamb: the trust flag) -- the words adam_step_kernel / trust_step_kernel decide on."""
+        if self._sched_on:
+            w = self._sched[self._sched_gi(group)]
+            ops.lr_sched(w["t"], w["lr"], w["base"], advance=True, skip=skip, flag=flag, **self.lr_schedule.kwargs())
+
+    def set_lr_updates(self, t):
+        """The count of applied updates (a checkpoint's): into the device words where they exist -- the rate is re-evaluated at the next
+        use -- else kept until they are made, as `_ema_pending` waits for the flat buffers."""
+        t = int(t)
+        if t < 0:
+            raise ValueError(f"Invalid count of applied updates: {t}")
+        self._sched_pending = t
+        for w in self._sched.values():
+            w["t"].fill_(t)
+            w["host"] = None
+
+    def lr_state(self):
+        """(t, effective lr) of the first parameter group: the updates applied so far and the rate the next one uses.  One synchronising
+        read (none before the first step, where both come from the host's numbers).  Schedule off: (None, group["lr"])."""
+        if not self._sched_on:
+            return None, float(self.param_groups[0]["lr"])
+        if 0 not in self._sched:
+            t = int(self._sched_pending or 0)
+            return t, float(torch.tensor(float(self.param_groups[0]["lr"]) * self.lr_schedule.factor(t), dtype=torch.float64).float())
+        w = self._sched_words(0)
+        t, lr = torch.cat([w["t"].double(), w["lr"].double()]).tolist()
+        return int(t), lr
 
     @property
     def clip_stats(self):
@@ -463,7 +626,7 @@ class FusedSGD(_FusedFlat):
     _SLOTS = (("buf", "momentum_buffer"),)
 
     def __init__(self, params, lr, momentum=0.9, dampening=0, weight_decay=0, nesterov=False, *, no_decay=(), max_grad_norm=0.0,
-                 ema_decay=0.0, ema_warmup=False, accum_steps=1):
+                 ema_decay=0.0, ema_warmup=False, accum_steps=1, lr_schedule=None):
         if not 0.0 <= lr:
             raise ValueError(f"Invalid learning rate: {lr}")
         if not 0.0 <= momentum:
@@ -476,7 +639,8 @@ class FusedSGD(_FusedFlat):
             raise NotImplementedError("FusedSGD implements dampening=0")
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=bool(nesterov),
                                       maximize=False, foreach=None, differentiable=False, fused=None),
-                         max_grad_norm=max_grad_norm, no_decay=no_decay, ema_decay=ema_decay, ema_warmup=ema_warmup, accum_steps=accum_steps)
+                         max_grad_norm=max_grad_norm, no_decay=no_decay, ema_decay=ema_decay, ema_warmup=ema_warmup, accum_steps=accum_steps,
+                         lr_schedule=lr_schedule)
 
     @staticmethod
     def _check_group(group):
@@ -496,11 +660,13 @@ class FusedSGD(_FusedFlat):
         self._check_group(group)
         mu, wd, nesterov = self._captured_scalars(group)[:3]
         runs, ema = self._runs(fl), self._ema(fl)
+        lr_dev = self._sched_lr(fl, group, lr_dev)
         if wd == 0.0 and not nesterov and runs is None and ema is None:
             ops.sgd_momentum(fl["p"], fl["g"], fl["buf"], float(group["lr"]), mu, gscale, False, skip=skip, lr_dev=lr_dev)
         else:
             ops.update_sgd(fl["p"], fl["g"], fl["buf"], float(group["lr"]), mu, gscale, wd, nesterov, runs=runs, skip=skip,
                            lr_dev=lr_dev, ema=ema)
+        self._sched_advance(group, skip)
 
 
 class FusedAdam(_FusedFlat):
@@ -516,7 +682,7 @@ class FusedAdam(_FusedFlat):
     _DECOUPLED = False
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, maximize=False,
-                 no_decay=(), max_grad_norm=0.0, ema_decay=0.0, ema_warmup=False, accum_steps=1):
+                 no_decay=(), max_grad_norm=0.0, ema_decay=0.0, ema_warmup=False, accum_steps=1, lr_schedule=None):
         if amsgrad or maximize:
             raise NotImplementedError(f"{type(self).__name__} implements amsgrad=False, maximize=False")
         if not 0.0 <= lr:
@@ -528,7 +694,8 @@ class FusedAdam(_FusedFlat):
         if not 0.0 <= weight_decay:
             raise ValueError(f"Invalid weight_decay value: {weight_decay}")
         super().__init__(params, self._defaults(lr, (float(betas[0]), float(betas[1])), eps, weight_decay),
-                         max_grad_norm=max_grad_norm, no_decay=no_decay, ema_decay=ema_decay, ema_warmup=ema_warmup, accum_steps=accum_steps)
+                         max_grad_norm=max_grad_norm, no_decay=no_decay, ema_decay=ema_decay, ema_warmup=ema_warmup, accum_steps=accum_steps,
+                         lr_schedule=lr_schedule)
 
     @staticmethod
     def _defaults(lr, betas, eps, weight_decay):
@@ -579,11 +746,13 @@ class FusedAdam(_FusedFlat):
         self._check_group(group)
         b1, b2, eps, wd = self._captured_scalars(group)[:4]
         runs, ema = self._runs(fl), self._ema(fl)
+        lr_dev = self._sched_lr(fl, group, lr_dev)
         if not self._DECOUPLED and runs is None and ema is None:
             ops.adam(fl["p"], fl["g"], fl["m"], fl["v"], fl["step"], float(group["lr"]), b1, b2, eps, wd, gscale, skip=skip, lr_dev=lr_dev)
         else:
             ops.update_adam(fl["p"], fl["g"], fl["m"], fl["v"], fl["step"], float(group["lr"]), b1, b2, eps, wd, gscale,
                             decoupled=self._DECOUPLED, runs=runs, skip=skip, lr_dev=lr_dev, ema=ema)
+        self._sched_advance(group, skip)
 
 
 class FusedAdamW(FusedAdam):
@@ -593,9 +762,10 @@ class FusedAdamW(FusedAdam):
     _DECOUPLED = True
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False,
-                 no_decay=(), max_grad_norm=0.0, ema_decay=0.0, ema_warmup=False, accum_steps=1):
+                 no_decay=(), max_grad_norm=0.0, ema_decay=0.0, ema_warmup=False, accum_steps=1, lr_schedule=None):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
-                         no_decay=no_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup, accum_steps=accum_steps)
+                         no_decay=no_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup, accum_steps=accum_steps,
+                         lr_schedule=lr_schedule)
 
     @staticmethod
     def _defaults(lr, betas, eps, weight_decay):
@@ -669,11 +839,12 @@ class FusedLARS(_TrustMixin, FusedSGD):
     torch.optim.SGD's (momentum_buffer); `trust_coef` and `trust_eps` are group keys."""
 
     def __init__(self, params, lr, momentum=0.9, dampening=0, weight_decay=0, nesterov=False, trust_coef=1e-3, trust_eps=1e-8, *,
-                 no_decay=(), trust_exempt=(), max_grad_norm=0.0, ema_decay=0.0, ema_warmup=False, accum_steps=1):
+                 no_decay=(), trust_exempt=(), max_grad_norm=0.0, ema_decay=0.0, ema_warmup=False, accum_steps=1, lr_schedule=None):
         self._check_trust(trust_coef, trust_eps)
         self._trust_init(trust_exempt)
         super().__init__(params, lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
-                         no_decay=no_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup, accum_steps=accum_steps)
+                         no_decay=no_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup, accum_steps=accum_steps,
+                         lr_schedule=lr_schedule)
         for group in self.param_groups:
             group.setdefault("trust_coef", float(trust_coef))
             group.setdefault("trust_eps", float(trust_eps))
@@ -689,9 +860,11 @@ class FusedLARS(_TrustMixin, FusedSGD):
         mu, wd, nesterov = sc[:3]
         coef, teps = sc[-2:]
         self._check_trust(coef, teps)
-        ops.update_lars(fl["p"], fl["g"], fl["buf"], float(group["lr"]), mu, gscale, self._segs(fl), fl["ratio"], fl["trust_stats"],
-                        trust_coef=coef, trust_eps=teps, weight_decay=wd, nesterov=nesterov, skip=skip, lr_dev=lr_dev, taint=skip,
-                        ema=self._ema(fl))
+        lr_dev = self._sched_lr(fl, group, lr_dev)
+        flag = ops.update_lars(fl["p"], fl["g"], fl["buf"], float(group["lr"]), mu, gscale, self._segs(fl), fl["ratio"], fl["trust_stats"],
+                               trust_coef=coef, trust_eps=teps, weight_decay=wd, nesterov=nesterov, skip=skip, lr_dev=lr_dev, taint=skip,
+                               ema=self._ema(fl))
+        self._sched_advance(group, skip, flag)
 
 
 class FusedLAMB(_TrustMixin, FusedAdam):
@@ -701,11 +874,12 @@ class FusedLAMB(_TrustMixin, FusedAdam):
     are group keys as in FusedLARS (LAMB's ratio uses neither)."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0, amsgrad=False, trust_coef=1e-3, trust_eps=1e-8, *,
-                 maximize=False, no_decay=(), trust_exempt=(), max_grad_norm=0.0, ema_decay=0.0, ema_warmup=False, accum_steps=1):
+                 maximize=False, no_decay=(), trust_exempt=(), max_grad_norm=0.0, ema_decay=0.0, ema_warmup=False, accum_steps=1, lr_schedule=None):
         self._check_trust(trust_coef, trust_eps)
         self._trust_init(trust_exempt)
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
-                         no_decay=no_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup, accum_steps=accum_steps)
+                         no_decay=no_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup, accum_steps=accum_steps,
+                         lr_schedule=lr_schedule)
         for group in self.param_groups:
             group.setdefault("trust_coef", float(trust_coef))
             group.setdefault("trust_eps", float(trust_eps))
@@ -718,8 +892,10 @@ class FusedLAMB(_TrustMixin, FusedAdam):
     def _device_update(self, fl, group, gscale, skip=None, lr_dev=None):
         self._check_group(group)
         b1, b2, eps, wd = self._captured_scalars(group)[:4]
-        ops.update_lamb(fl["p"], fl["g"], fl["m"], fl["v"], fl["step"], float(group["lr"]), b1, b2, eps, wd, gscale, self._segs(fl),
-                        fl["ratio"], fl["trust_stats"], skip=skip, lr_dev=lr_dev, taint=skip, ema=self._ema(fl))
+        lr_dev = self._sched_lr(fl, group, lr_dev)
+        flag = ops.update_lamb(fl["p"], fl["g"], fl["m"], fl["v"], fl["step"], float(group["lr"]), b1, b2, eps, wd, gscale, self._segs(fl),
+                               fl["ratio"], fl["trust_stats"], skip=skip, lr_dev=lr_dev, taint=skip, ema=self._ema(fl))
+        self._sched_advance(group, skip, flag)
 
 
 class DataParallelAdam(Adam):
@@ -754,6 +930,9 @@ def get_optimizer(cfg, model_params):
     # (what every fused optimiser takes: the weight average and SOLVER.accum_steps, the micro-batches per update)
     ema = dict(ema_decay=float(cfg.SOLVER.get('ema_decay', 0.0)), ema_warmup=bool(cfg.SOLVER.get('ema_warmup', False)),
                accum_steps=cfg.SOLVER.get('accum_steps', 1))
+    sched = LrSchedule.from_cfg(cfg)      # (validated whether on or off)
+    if sched.on:
+        ema["lr_schedule"] = sched        # SOLVER.warmup_updates / lr_shape: the per-update schedule behind the update launch
     if optim_name == 'adam':
         return FusedAdam(model_params, lr=cfg.SOLVER.lr, weight_decay=wd, no_decay=no_decay, max_grad_norm=clip, **ema)
     elif optim_name == 'adamw':
@@ -770,9 +949,69 @@ def get_optimizer(cfg, model_params):
         return FusedLAMB(model_params, lr=cfg.SOLVER.lr, weight_decay=wd, no_decay=no_decay, max_grad_norm=clip, **trust, **ema)
 
 
+class ScheduledLR:
+    """What get_lr_scheduler returns with the per-update schedule on: the per-epoch scheduler `inner` (it still sets group["lr"], the
+    BASE rate) beside the optimiser's device-side schedule.  step() is the per-epoch scheduler's; get_last_lr() gives the effective
+    rate base * m(t) per group.  state_dict() is the inner scheduler's own dict plus one key, "per_update" = {"t", the schedule's
+    numbers}: a scheduler of the other kind reads it too (torch's load_state_dict keeps unknown keys as attributes), and a dict without
+    the key -- written with the schedule off -- loads here with t = 0."""
+
+    def __init__(self, optimizer, inner):
+        if not getattr(optimizer, "_sched_on", False):
+            raise ValueError("ScheduledLR needs a fused optimiser whose lr_schedule is on")
+        self.optimizer, self.inner = optimizer, inner
+
+    def step(self, *args, **kwargs):
+        return self.inner.step(*args, **kwargs)
+
+    def get_last_lr(self):
+        opt = self.optimizer
+        t, lr = opt.lr_state()
+        if len(opt.param_groups) == 1:
+            return [lr]
+        # (more groups: one count, each group's own base rate -- the host's restatement of the words)
+        return [float(torch.tensor(float(g["lr"]) * opt.lr_schedule.factor(t), dtype=torch.float64).float()) for g in opt.param_groups]
+
+    def state_dict(self):
+        sd = dict(self.inner.state_dict()) if self.inner is not None else {}
+        sd["per_update"] = dict(self.optimizer.lr_schedule.state_dict(), t=int(self.optimizer.lr_state()[0]))
+        return sd
+
+    def load_state_dict(self, sd):
+        sd = dict(sd)
+        per = sd.pop("per_update", None)
+        if self.inner is not None:
+            self.inner.load_state_dict(sd)
+        if per is None:
+            print("the checkpoint's scheduler entry carries no count of applied updates (written with the per-update schedule off): "
+                  "the schedule starts at t = 0")
+            self.optimizer.set_lr_updates(0)
+            return
+        mine = self.optimizer.lr_schedule.state_dict()
+        diff = {k: (per[k], v) for k, v in mine.items() if k in per and per[k] != v and not (k == "total_updates" and 0 in (per[k], v))}
+        if diff:
+            print("the checkpoint's per-update schedule differs from this run's, which is kept: " +
+                  ", ".join(f"{k} {a!r} -> {b!r}" for k, (a, b) in sorted(diff.items())))
+        self.optimizer.set_lr_updates(per.get("t", 0))
+
+    def __getattr__(self, name):         # last_epoch, milestones, ...: the per-epoch scheduler's
+        if name in ("inner", "optimizer"):
+            raise AttributeError(name)
+        return getattr(self.inner, name)
+
+
 def get_lr_scheduler(cfg, optim=None):
     sche_name = cfg.SOLVER.scheduler
+    inner = None
     if sche_name == 'steplr':
-        return StepLR(optim, 50, gamma=0.1)
+        inner = StepLR(optim, 50, gamma=0.1)
     elif sche_name == 'MultiStep':
-        return MultiStepLR(optim, cfg.SOLVER.lr_step, gamma=0.1)
+        inner = MultiStepLR(optim, cfg.SOLVER.lr_step, gamma=0.1)
+    sched = LrSchedule.from_cfg(cfg)
+    if not sched.on:          # exactly what it returned before the keys existed
+        return inner
+    if not hasattr(optim, "_sched"):
+        raise ValueError("SOLVER.warmup_updates / SOLVER.lr_shape need a fused optimiser (SOLVER.optim sgd, adam, adamw, lars or lamb)")
+    if not optim._sched_on:
+        optim.lr_schedule = sched
+    return ScheduledLR(optim, inner)

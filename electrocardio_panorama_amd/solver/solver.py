@@ -141,6 +141,10 @@ class Solver:
         self.model.dropout_epoch = start_epoch          # a resumed run must not replay epoch 0's dropout masks
         print('the latest best_test_psnr_gen is {:06f}'.format(best_test_psnr_gen))
         save_arguments = {}
+        sched = getattr(optimizer, 'lr_schedule', None)
+        if sched is not None and sched.on and sched.total_updates == 0:
+            # SOLVER.total_updates 0: the run's updates, known here -- before the first step, so nothing is re-captured for it
+            sched.total_updates = max_epochs * -(-len(dl_train) // getattr(optimizer, 'accum_steps', 1))
         for epoch in range(start_epoch, max_epochs):
             print('---------------------------------{}---{}-------------------------------------'.format(self.cfg.desc, epoch))
             if hasattr(getattr(dl_train, 'sampler', None), 'set_epoch'):
@@ -185,6 +189,11 @@ class Solver:
                     scalars[-1], optimizer.max_grad_norm, self.last_clip_counts[0], len(self.last_grad_norms), self.last_clip_counts[1])
             if getattr(optimizer, 'accum_steps', 1) > 1:
                 msg += '\naccum_steps {}: {} updates from {} batches'.format(optimizer.accum_steps, *self.last_updates)
+            if getattr(self, 'last_lr', None) is not None:                # SOLVER.warmup_updates / lr_shape
+                scalars.append(self.last_lr[1])
+                names.append('train_lr')
+                msg += '\nlr: {:.6e} at the first update, {:.6e} behind the last ({} updates applied so far)'.format(
+                    *self.last_lr, self.last_lr_updates)
             if getattr(self, 'last_trust_stats', None) is not None:      # SOLVER.optim is lars or lamb
                 msg += '\ntrust ratio: min {:.3e}, max {:.3e} over the adapted tensors; {} steps skipped for non-finite norms'.format(
                     *self.last_trust_stats)
@@ -321,6 +330,12 @@ class Solver:
         trust_0 = float(optim.trust_stats[3].item()) if trust and optim.trust_stats is not None else 0.0
         # SOLVER.accum_steps: an update closes every window of K train batches; clip_stats are recorded per UPDATE, not per batch
         accum = phase == 'train' and getattr(optim, 'accum_steps', 1) > 1
+        # the per-update learning-rate schedule: the count the epoch starts from is the host's (the previous epoch's read; before the first
+        # step: the loaded or zero count, no device word exists yet) and so is the rate of its first update
+        lr_on = phase == 'train' and getattr(optim, '_sched_on', False)
+        if lr_on and (getattr(self, '_lr_seen', None) is None or self._lr_seen[0] is not optim):
+            self._lr_seen = (optim, optim.lr_state()[0])
+        lr_first = float(np.float32(float(optim.param_groups[0]['lr']) * optim.lr_schedule.factor(self._lr_seen[1]))) if lr_on else None
         n_batches = n_updates = 0
         for meta in dl:
             source_data, rois, input_theta, target_view, target_theta, noise = self._to_device(meta)
@@ -382,6 +397,11 @@ class Solver:
                 self.last_grad_norms = [a.tolist() for a in clip_s.arrays()]
                 clip_1 = optim.clip_stats[2:].tolist()
                 self.last_clip_counts = (int(clip_1[0] - clip_0[0]), int(clip_1[1] - clip_0[1]))
+            # the schedule's (first, last) effective rate of this epoch and the count behind it: ONE read, here
+            self.last_lr = self.last_lr_updates = None
+            if lr_on:
+                t_now, lr_now = optim.lr_state()
+                self.last_lr, self.last_lr_updates, self._lr_seen = (lr_first, lr_now), t_now, (optim, t_now)
             # trust ratios (SOLVER.optim lars / lamb) of the last updating step: name -> q, (min, max) over the adapted tensors and this
             # epoch's steps skipped for non-finite norms -- read once, here, where the device has been waited for anyway
             self.last_trust_ratios, self.last_trust_stats = {}, None

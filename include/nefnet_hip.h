@@ -34,7 +34,7 @@ extern "C" {
 typedef void* nef_stream_t;
 
 /* ABI version of this header; bumped on any signature change. */
-int nef_abi_version(void);   /* 22 (weight packing is ONE entry, nef_pack_weights(nef_pack_desc*, n), + nef_pack_bytes(nef_pack_desc*) for the size of any operand.  ABI <= 21 had nef_pack_weight, nef_pack_weight_wino, nef_pack_weight_wino4, nef_pack_weight_h2 and nef_pack_weight_h2_bytes: each is one descriptor with wino = 0 / 1 / 2 / 3); 21 (BatchNorm backward is ONE entry on a nef_bn_bwd_args struct, + nef_bn_bwd_args_bytes; nef_mix_bwd takes `up` / `shared` flags; nef_outconv_fwd / nef_outconv_bwd_weight take the prologue arguments.  ABI <= 20 had nef_bn_relu_bwd_phase_major, nef_bn_relu_bwd_up, nef_bn_relu_bwd_combine3, nef_bn_relu_bwd_combine3_phase_major, nef_bn_relu_bwd_outconv, nef_bn_bwd_outconv_ws_bytes, nef_mix_bwd_up, nef_mix_bwd_shared, nef_mix_bwd_shared_up, nef_outconv_fwd_pro and nef_outconv_bwd_weight_pro); 20 (the weight gradient is ONE entry, nef_conv_bwd_weight(nef_bww_args*), + nef_bww_args_bytes; its _pro, _wino4, _h2 and _h2_ws_bytes variants are gone); 19 (+ nef_adam, nef_h2_tail_census, nef_bwd_weight_clamp_ends: additions only; the kernel-form option entry points of 16 and nef_upsample2_aff_fwd are gone; + nef_debug_spin_us); 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + kernel-form option entry points); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + the split-fp16 weight gradient, now form 3); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, the transposed F(3,4) / F(4,4) entry, now form 4, covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
+int nef_abi_version(void);   /* 22 (+ nef_flatten_acc, nef_lr_sched / nef_lr_sched_args_bytes: additions only, the number stays; a binding finds a library without them by the missing symbol.  Weight packing is ONE entry, nef_pack_weights(nef_pack_desc*, n), + nef_pack_bytes(nef_pack_desc*) for the size of any operand.  ABI <= 21 had nef_pack_weight, nef_pack_weight_wino, nef_pack_weight_wino4, nef_pack_weight_h2 and nef_pack_weight_h2_bytes: each is one descriptor with wino = 0 / 1 / 2 / 3); 21 (BatchNorm backward is ONE entry on a nef_bn_bwd_args struct, + nef_bn_bwd_args_bytes; nef_mix_bwd takes `up` / `shared` flags; nef_outconv_fwd / nef_outconv_bwd_weight take the prologue arguments.  ABI <= 20 had nef_bn_relu_bwd_phase_major, nef_bn_relu_bwd_up, nef_bn_relu_bwd_combine3, nef_bn_relu_bwd_combine3_phase_major, nef_bn_relu_bwd_outconv, nef_bn_bwd_outconv_ws_bytes, nef_mix_bwd_up, nef_mix_bwd_shared, nef_mix_bwd_shared_up, nef_outconv_fwd_pro and nef_outconv_bwd_weight_pro); 20 (the weight gradient is ONE entry, nef_conv_bwd_weight(nef_bww_args*), + nef_bww_args_bytes; its _pro, _wino4, _h2 and _h2_ws_bytes variants are gone); 19 (+ nef_adam, nef_h2_tail_census, nef_bwd_weight_clamp_ends: additions only; the kernel-form option entry points of 16 and nef_upsample2_aff_fwd are gone; + nef_debug_spin_us); 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + kernel-form option entry points); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + the split-fp16 weight gradient, now form 3); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, the transposed F(3,4) / F(4,4) entry, now form 4, covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
 
 /* Diagnostics: `wgs` workgroups busy for `us` microseconds on `stream` (a stand-in for a collective's time on the chip:
  * parallel.DryCollective, bench.py --dry-collective).  0 <= us <= 50000, 1 <= wgs <= 64. */
@@ -690,6 +690,44 @@ int nef_update_trust(const nef_update_args* a, const nef_trust_args* t, const ne
 size_t nef_update_trust_ws_bytes(int64_t n, int32_t n_segs);
 /* sizeof(nef_trust_args) as the library was built. */
 size_t nef_trust_args_bytes(void);
+/* The per-update learning-rate schedule (no counterpart in the reference, whose two schedulers step per epoch): the effective rate of
+ * an update is base * m(t), t = *t the number of updates APPLIED so far (the first update uses m(0)), with W = warmup_updates,
+ * N = total_updates, s = warmup_start, f = lr_floor, p = poly_power:
+ *   t < W:   m = s + (1 - s) * t / W                                            (torch's LinearLR, closed form)
+ *   t >= W:  x = clamp((t - W) / max(1, N - W), 0, 1);
+ *            shape 0 (const):  m = 1
+ *            shape 1 (cosine): m = f + (1 - f) * (1 + cos(pi * x)) / 2         (CosineAnnealingLR, T_max = N - W, eta_min = f * base)
+ *            shape 2 (poly):   m = f + (1 - f) * (1 - x)^p                     (PolynomialLR when f = 0)
+ *   and m keeps its end value for t >= N.  N <= W: the span counts as 1 (x = 0 at t = W, 1 behind it); W = 0: no warm-up, no division.
+ * m and the product are formed in fp64 and rounded ONCE into the fp32 word *lr_out -- the word the update entries take as lr_dev.
+ * base = *base_dev (a device fp64 word) when base_dev is given, else the scalar.  *t is an int64 word: a float count stops at 2^24.
+ *   advance = 1: behind an update.  The update counted as applied unless *skip_if_positive > 0 or *flag > 0 (either may be NULL) --
+ *                the rule and the words of the one-lane launches behind nef_adam / nef_update_trust (flag: the 4-byte word at
+ *                ws + nef_update_trust_ws_bytes(n, n_segs) - 16 of the nef_update_trust call in front).  Applied: *t += 1, then
+ *                *lr_out = (float)(base * m(*t)).  Not applied: *t and *lr_out keep their bits.
+ *   advance = 0: only *lr_out = (float)(base * m(*t)); *t is not written, the two words are not read.
+ * One single-wave launch, lane 0 working.  args, t or lr_out NULL: NEF_E_NULL; shape outside 0..2: NEF_E_UNSUPPORTED; advance not 0 / 1,
+ * a negative W or N, s or f outside [0, 1], p <= 0, a negative scalar base, or a NaN / infinity in any of them: NEF_E_SHAPE.  Every check
+ * sits in front of the launch.  Capturable: nothing is read by the host, nothing is allocated. */
+typedef struct nef_lr_sched_args {
+    int64_t* t;                    /* device int64 word: applied updates */
+    const double* base_dev;        /* NULL, or a device fp64 word that replaces `base` at run time */
+    float* lr_out;                 /* device fp32 word, out: the rate of the next update */
+    const float* skip_if_positive; /* NULL, or the skip word of the update in front */
+    const float* flag;             /* NULL, or the trust flag of the nef_update_trust call in front */
+    int64_t warmup_updates;        /* W >= 0 */
+    int64_t total_updates;         /* N >= 0 */
+    double base;                   /* the base rate when base_dev is NULL (>= 0) */
+    double warmup_start;           /* s in [0, 1] */
+    double lr_floor;               /* f in [0, 1] */
+    double poly_power;             /* p > 0 */
+    int32_t shape;                 /* 0 const, 1 cosine, 2 poly */
+    int32_t advance;               /* 0 / 1 */
+} nef_lr_sched_args;
+
+int nef_lr_sched(const nef_lr_sched_args* a, nef_stream_t stream);
+/* sizeof(nef_lr_sched_args) as the library was built. */
+size_t nef_lr_sched_args_bytes(void);
 /* Global gradient-norm clipping over a flat buffer: torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2) on the averaged
  * gradient gscale * g (no counterpart in the reference).  total = gscale * sqrt(sum g[i]^2), coef = min(1, max_norm / (total + 1e-6)),
  * g[i] *= coef; g stays the un-averaged sum, so the update launch behind this call still applies gscale.  The sum is deterministic:

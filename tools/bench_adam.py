@@ -6,6 +6,7 @@
     python tools/bench_adam.py --ema D [--parent-tree DIR] [--out profiles/ema_bench_line.json]
     python tools/bench_adam.py --trust lars|lamb [--parent-tree DIR] [--out profiles/r11_trust_bench_line.json]
     python tools/bench_adam.py --accum K [--parent-tree DIR] [--out profiles/r12_accum_bench_line.json]
+    python tools/bench_adam.py --sched const|cosine|poly --warmup W [--parent-tree DIR] [--out profiles/r14_sched_bench_line.json]
 
 Each measurement runs in a child process of its own under `timeout` (nothing more is started once one fails), `--reps` rounds of
 the three children; every figure is reported as [min, median, max] over the rounds:
@@ -45,7 +46,14 @@ no table) in one process.  Writes profiles/r11_trust_bench_line.json unless --ou
 accum_steps = 1 (sgd-graph: the parent's code path) and with accum_steps = K (sgd-graph-accum: ms per MICRO-batch, an update every K-th),
 and -- with --parent-tree DIR -- DIR's own sgd-graph step.  The config-2 accumulating child also times the flatten launch alone on the
 model's real gradient tensors, cold as above: nef_flatten_acc (accumulate form) beside nef_flatten in one process (3 fp32 streams per
-parameter against 2).  Writes profiles/r12_accum_bench_line.json unless --out says otherwise."""
+parameter against 2).  Writes profiles/r12_accum_bench_line.json unless --out says otherwise.
+
+--sched SHAPE --warmup W measures the per-update learning-rate schedule (SOLVER.warmup_updates / lr_shape), at the same two shapes: per
+round and shape the graphed FusedSGD step with the keys off (sgd-graph: the parent's code path) and with the schedule on (sgd-graph-sched:
+warmup_updates = W, lr_shape = SHAPE, total_updates = W + 1000, so the timed steps sit on the ramp or the shape), and -- with --parent-tree
+DIR -- DIR's own sgd-graph step.  Beside --sched, --warmup is the SCHEDULE's W; every child then runs 3 untimed steps in front of the
+timed ones (the default of the other measurements).  The config-2 schedule child also times the nef_lr_sched launch alone: cold as above
+and warm (back-to-back launches).  Writes profiles/r14_sched_bench_line.json unless --out says otherwise."""
 import argparse
 import json
 import os
@@ -85,7 +93,7 @@ def cold_ms(launches, dev, reps=30):
     return [float(np.median([a.elapsed_time(b) for a, b in ev])) for ev in evs]
 
 
-def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=(), ema=0.0, accum=1):
+def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=(), ema=0.0, accum=1, sched=None):
     import numpy as np
     import torch
     from electrocardio_panorama_amd import ops, synth
@@ -112,6 +120,10 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
         optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9, ema_decay=ema)
     elif mode == "sgd-graph-accum":
         optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9, accum_steps=accum)
+    elif mode == "sgd-graph-sched":
+        shape, W = sched
+        optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9,
+                         lr_schedule=optim_scheduler.LrSchedule(warmup_updates=W, lr_shape=shape, total_updates=W + 1000))
     elif mode == "adam-graph":
         optim = FusedAdam(model.parameters(), lr=1e-3)
     elif mode == "lars-graph":
@@ -160,6 +172,23 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
         res.update(flatten_tensors=len(srcs), flatten_params=n, nef_flatten_cold_ms=round(old_ms, 4), nef_flatten_acc_cold_ms=round(new_ms, 4),
                    nef_flatten_cold_GBps=round(2 * 4 * n / (old_ms * 1e-3) / 1e9, 1),
                    nef_flatten_acc_cold_GBps=round(3 * 4 * n / (new_ms * 1e-3) / 1e9, 1))
+    if mode == "sgd-graph-sched":
+        t, lr = optim.lr_state()
+        res.update(lr_shape=sched[0], warmup_updates=sched[1], updates_applied=t, effective_lr=lr)
+    if mode == "sgd-graph-sched" and (B, L) == EMA_SHAPES["config2"]:
+        sc = optim.lr_schedule
+        t_w, lr_w = torch.zeros(1, device=dev, dtype=torch.int64), torch.zeros(1, device=dev)
+        skip = torch.zeros(1, device=dev)
+        launch = lambda: ops.lr_sched(t_w, lr_w, float(cfg.SOLVER.lr), skip=skip, **sc.kwargs())      # noqa: E731
+        cold = cold_ms([launch], dev)[0]
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        reps = 200
+        e0.record()
+        for _ in range(reps):
+            launch()
+        e1.record()
+        e1.synchronize()
+        res.update(nef_lr_sched_cold_ms=round(cold, 4), nef_lr_sched_warm_ms=round(e0.elapsed_time(e1) / reps, 4))
     if mode == "sgd-graph-ema":
         fl = optim._flat[0]
         p, g, buf, e, e_n = (fl[k].clone() for k in ("p", "g", "buf", "ema", "ema_n"))
@@ -376,6 +405,59 @@ def accum_rounds(args):
         f.write(line + "\n")
 
 
+def sched_rounds(args):
+    """--sched SHAPE --warmup W: `--reps` alternating rounds of fresh children per shape (see the module docstring); prints and writes one
+    JSON line."""
+    W, untimed = args.warmup, 3
+    modes = dict({"sgd-graph": 900, "sgd-graph-sched": 900}, **({"parent": 900} if args.parent_tree else {}))
+    results = {(shape, mode): [] for shape in EMA_SHAPES for mode in modes}
+    for rnd in range(args.reps):
+        order = list(modes) if rnd % 2 == 0 else list(reversed(modes))
+        for shape, (B, L) in EMA_SHAPES.items():
+            for mode in order:
+                if mode == "parent":
+                    # the parent's tool may lack --shape: its `child` function is called directly, in a fresh process of its own tree
+                    tree = os.path.abspath(args.parent_tree)
+                    code = ("import importlib.util as u; s = u.spec_from_file_location('parent_bench', %r); m = u.module_from_spec(s); "
+                            "s.loader.exec_module(m); m.child('sgd-graph', %d, %d, B=%d, L=%d)"
+                            % (os.path.join(tree, "tools", "bench_adam.py"), args.steps, untimed, B, L))
+                    cmd = ["timeout", "-k", "10", str(modes[mode]), sys.executable, "-c", code]
+                else:
+                    tree = ROOT
+                    cmd = ["timeout", "-k", "10", str(modes[mode]), sys.executable, os.path.join(ROOT, "tools", "bench_adam.py"), "--child", mode,
+                           "--steps", str(args.steps), "--warmup", str(untimed), "--shape", str(B), str(L)]
+                    if mode == "sgd-graph-sched":
+                        cmd += ["--sched", args.sched, "--sched-warmup", str(W)]
+                results[(shape, mode)].append(run_child(cmd, tree, mode))
+                sys.stderr.write(f"round {rnd + 1}/{args.reps} {shape} {mode}: {results[(shape, mode)][-1]['ms_per_step']} ms/step\n")
+                sys.stderr.flush()
+
+    def spread(shape, mode, key):
+        v = sorted(x[key] for x in results[(shape, mode)])
+        return [v[0], v[len(v) // 2], v[-1]]
+
+    out = {"metric": "ms per train step, graphed FusedSGD with the per-update learning-rate schedule off and on ([min, median, max] over rounds)",
+           "rounds": args.reps, "lr_shape": args.sched, "warmup_updates": W,
+           "shapes": {k: "B=%d, 3 leads, L=%d, one GPU, dropout on" % v for k, v in EMA_SHAPES.items()}}
+    for shape in EMA_SHAPES:
+        out[shape + "_sched_off_ms"] = spread(shape, "sgd-graph", "ms_per_step")
+        out[shape + "_sched_on_ms"] = spread(shape, "sgd-graph-sched", "ms_per_step")
+        if args.parent_tree:
+            out[shape + "_parent_ms"] = par = spread(shape, "parent", "ms_per_step")
+            # to be read against each other: the keys-off median and the parent's own min-max spread
+            out[shape + "_sched_off_median_inside_parent_spread"] = par[0] <= out[shape + "_sched_off_ms"][1] <= par[2]
+            out[shape + "_sched_on_median_minus_parent_median_ms"] = round(out[shape + "_sched_on_ms"][1] - par[1], 3)
+    out.update(nef_lr_sched_cold_ms=spread("config2", "sgd-graph-sched", "nef_lr_sched_cold_ms"),
+               nef_lr_sched_warm_ms=spread("config2", "sgd-graph-sched", "nef_lr_sched_warm_ms"),
+               launch_note="the single-wave nef_lr_sched launch (advance form) alone; cold = a 512 MiB buffer written before each launch, warm = "
+                           "200 back-to-back launches issued from Python (host-issue bound)",
+               steps=args.steps, untimed_steps=untimed)
+    line = json.dumps(out)
+    print(line)
+    with open(args.out or os.path.join(ROOT, "profiles", "r14_sched_bench_line.json"), "w") as f:
+        f.write(line + "\n")
+
+
 def trust_rounds(args):
     """--trust lars|lamb: `--reps` alternating rounds of fresh children per shape (see the module docstring); prints and writes one JSON
     line."""
@@ -442,10 +524,14 @@ def main():
     ap.add_argument("--ema", type=float, default=None, metavar="D", help="measure the EMA of the weights in the update launch (see above)")
     ap.add_argument("--trust", choices=sorted(TRUST_BASE), default=None, help="measure the layer-wise trust ratios (see above)")
     ap.add_argument("--accum", type=int, default=None, metavar="K", help="measure gradient accumulation, accum_steps = K (see above)")
+    ap.add_argument("--sched", choices=("const", "cosine", "poly"), default=None,
+                    help="measure the per-update learning-rate schedule of this shape; --warmup is then the schedule's W (see above)")
+    ap.add_argument("--sched-warmup", type=int, default=None, metavar="W", help="with --child sgd-graph-sched: the schedule's W")
     ap.add_argument("--shape", type=int, nargs=2, default=(256, 5000), metavar=("B", "L"), help="with --child: batch size and length")
     ap.add_argument("--parent-tree", default=None,
                     help="with --clip / --weight-decay / --ema: a built checkout whose own sgd-graph child runs in every round")
-    ap.add_argument("--child", choices=sorted({**MODES, **CLIP_MODES, **WD_MODES, **EMA_MODES, "lars-graph": 900, "lamb-graph": 900, "sgd-graph-accum": 900}),
+    ap.add_argument("--child", choices=sorted({**MODES, **CLIP_MODES, **WD_MODES, **EMA_MODES, "lars-graph": 900, "lamb-graph": 900, "sgd-graph-accum": 900,
+                                             "sgd-graph-sched": 900}),
                     default=None)
     args = ap.parse_args()
     if args.child == "sgd-graph-ema" and not (args.ema is not None and 0.0 < args.ema < 1.0):
@@ -465,12 +551,21 @@ def main():
         ap.error("--accum K >= 2 is a measurement of its own")
     if args.child == "sgd-graph-accum" and args.accum is None:
         ap.error("--child sgd-graph-accum needs --accum K")
-    if args.parent_tree and args.clip is None and args.weight_decay is None and args.ema is None and args.trust is None and args.accum is None:
-        ap.error("--parent-tree goes with --clip, --weight-decay, --ema, --trust or --accum")
+    if args.sched is not None and not args.child and (args.clip is not None or args.weight_decay is not None or args.ema is not None
+                                                      or args.trust is not None or args.accum is not None or args.warmup < 0):
+        ap.error("--sched SHAPE --warmup W >= 0 is a measurement of its own")
+    if args.child == "sgd-graph-sched" and (args.sched is None or args.sched_warmup is None):
+        ap.error("--child sgd-graph-sched needs --sched SHAPE and --sched-warmup W")
+    if (args.parent_tree and args.clip is None and args.weight_decay is None and args.ema is None and args.trust is None
+            and args.accum is None and args.sched is None):
+        ap.error("--parent-tree goes with --clip, --weight-decay, --ema, --trust, --accum or --sched")
     if args.child:
         return child(args.child, args.steps if args.child != "adam-eager" else max(3, args.steps // 2), args.warmup,
                      B=args.shape[0], L=args.shape[1], clip=args.clip or 0.0, wd=args.weight_decay or 0.0,
-                     no_decay=tuple(args.no_decay), ema=args.ema or 0.0, accum=args.accum or 1)
+                     no_decay=tuple(args.no_decay), ema=args.ema or 0.0, accum=args.accum or 1,
+                     sched=(args.sched, args.sched_warmup) if args.child == "sgd-graph-sched" else None)
+    if args.sched is not None:
+        return sched_rounds(args)
     if args.ema is not None:
         return ema_rounds(args)
     if args.trust is not None:
