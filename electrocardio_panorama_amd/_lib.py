@@ -86,6 +86,12 @@ class LrSchedArgs(C.Structure):
                 ("poly_power", C.c_double), ("shape", i32), ("advance", i32)]
 
 
+class LossSsimArgs(C.Structure):
+    """Mirror of `nef_loss_ssim_args` (include/nefnet_hip.h)."""
+    _fields_ = [("pred", p), ("target", p), ("noise", p), ("rois", p), ("losses", p), ("ws", p), ("ws_bytes", sz), ("gscale", p),
+                ("g_pred", p), ("B", i32), ("L", i32), ("factor", f32), ("reserved0", i32)]
+
+
 class PackDesc(C.Structure):
     """Mirror of `nef_pack_desc` (include/nefnet_hip.h)."""
     _fields_ = [("w", p), ("wp", p), ("G", i32), ("Cog", i32), ("Cig", i32), ("K", i32), ("transpose_flip", i32),
@@ -168,6 +174,10 @@ SIGNATURES = {
     "nef_loss_bwd": (i32, [p, p, p, p, p, p, p, p, i64, f32, f32, f32, i32, i32, p]),
     "nef_loss_noise_fwd": (i32, [p, p, p, p, p, p, p, sz, i64, f32, f32, f32, i32, i32, p]),
     "nef_loss_noise_bwd": (i32, [p, p, p, p, p, p, p, p, p, i64, f32, f32, f32, i32, i32, p]),
+    "nef_loss_ssim_fwd": (i32, [C.POINTER(LossSsimArgs), p]),
+    "nef_loss_ssim_bwd": (i32, [C.POINTER(LossSsimArgs), p]),
+    "nef_loss_ssim_ws_bytes": (sz, [i32, i32]),
+    "nef_loss_ssim_args_bytes": (sz, []),
     "nef_sgd_momentum": (i32, [p, p, p, i64, f32, f32, f32, i32, p, p, p, p]),
     "nef_adam": (i32, [p, p, p, p, i64, f32, C.c_double, C.c_double, f32, f32, f32, p, p, p, p, p]),
     "nef_update": (i32, [C.POINTER(UpdateArgs), p]),
@@ -235,7 +245,8 @@ def load():
                                ("nef_update_args", lib.nef_update_args_bytes(), UpdateArgs),
                                ("nef_ema_args", lib.nef_ema_args_bytes(), EmaArgs),
                                ("nef_trust_args", lib.nef_trust_args_bytes(), TrustArgs),
-                               ("nef_lr_sched_args", lib.nef_lr_sched_args_bytes(), LrSchedArgs)):
+                               ("nef_lr_sched_args", lib.nef_lr_sched_args_bytes(), LrSchedArgs),
+                               ("nef_loss_ssim_args", lib.nef_loss_ssim_args_bytes(), LossSsimArgs)):
         if size != C.sizeof(mirror):
             raise NefLibraryError(f"{LIB_PATH}: {name} is {size} bytes, the binding mirrors {C.sizeof(mirror)}; rebuild with "
                                   "`python -m electrocardio_panorama_amd.csrc.build`")

@@ -100,6 +100,14 @@ _DEFAULTS = {
         "total_updates": 0,
         "lr_floor": 0.0,            # in [0, 1]: the end value as a fraction of group lr
         "poly_power": 1.0,          # > 0
+        # a structural-similarity term in the training loss, on the device (nef_loss_ssim_fwd / nef_loss_ssim_bwd behind the loss launches,
+        # in the eager and the graphed step): loss += ssim_factor * (1 - mean SSIM(prediction (+ DATA.noise), target)) with the SSIM the test
+        # phase reports as ssim_gen (7-tap window, utils/metric.py:ssim_1d); the loss tuple and the graphed step's loss row gain the term as
+        # their LAST element, logged as train_loss_ssim / test_loss_ssim.  0 = off: the 4-element rows, launches, graphs and bits are what
+        # they were before the key existed; a negative value is rejected where the loss is built
+        "ssim_factor": 0.0,
+        # True: every row ends at rois[i, -1, 0] as in the test phase's metrics (a row shorter than the window is left out); False: whole rows
+        "ssim_crop": True,
     },
 }
 

@@ -7,6 +7,7 @@ it: inputs are copied into static buffers, and the only per-step host decisions 
 (reference model_nefnet.py:154,156, drawn from Python's `random` in the reference's order) and the dropout seed --
 travel through device words that the kernels read at run time.  Same arithmetic as the eager path.  `cfg.DATA.noise`: the
 per-sample noise row is one more static input, added to the prediction inside the loss kernels (ops.loss_fwd / loss_bwd, noise=).
+`cfg.SOLVER.ssim_factor`: the SSIM term's three launches (ops.loss_ssim_fwd / loss_ssim_bwd) sit behind them in the same graph.
 
 One graph (with its own static input buffers) is kept per input shape, so a final partial batch or alternating shapes
 replay instead of re-capturing; the flat parameter / gradient / momentum buffers are shared by all of them and survive
@@ -51,6 +52,11 @@ class GraphedTrainStep:
         # and added inside the loss kernels; off: no buffer, no copy
         self.use_noise = bool(cfg.DATA.noise)
         self.noise = None
+        # cfg.SOLVER.ssim_factor: the SSIM term's launches behind the loss launches, on the static rois and noise; the loss row has 5
+        # elements then.  0: no launch, the 4-element row
+        from .network.loss.losses import ssim_settings
+        self.ssim_factor = ssim_settings(cfg, need_rois=False)[0]
+        self.ssim_crop = self.ssim_factor > 0 and bool(cfg.SOLVER.get('ssim_crop', True))
         self.optimizer = optimizer
         if optimizer is not None:
             if len(optimizer.param_groups) != 1 or not hasattr(optimizer, "_device_update"):
@@ -138,6 +144,10 @@ class GraphedTrainStep:
             o, p_, l_ = (t.contiguous() for t in outs)
             ops.loss_fwd(o, p_, l_, self.target, self.factors, self.reg_l2, self.use_mask, out=self.losses, noise=self.noise)
             g3 = ops.loss_bwd(o, p_, l_, self.target, None, self.factors, self.reg_l2, self.use_mask, noise=self.noise)
+            if self.ssim_factor > 0:
+                rois = self.rois if self.ssim_crop else None
+                ops.loss_ssim_fwd(o, self.target, self.losses, self.ssim_factor, rois=rois, noise=self.noise)
+                ops.loss_ssim_bwd(o, self.target, g3[0], self.ssim_factor, rois=rois, noise=self.noise)
             return engine.backward(P, sv, g3)
 
     def _frozen(self):
@@ -257,7 +267,7 @@ class GraphedTrainStep:
             self.choice_dev = torch.zeros(2, device=dev, dtype=torch.int32)
             self.seed_dev = torch.zeros(1, device=dev, dtype=torch.int64)
             self.status = torch.zeros(1, device=dev, dtype=torch.int32)
-            self.losses = torch.zeros(4, device=dev, dtype=torch.float32)
+            self.losses = torch.zeros(5 if self.ssim_factor > 0 else 4, device=dev, dtype=torch.float32)
             self.lr_dev = torch.full((1,), self.lr, device=dev, dtype=torch.float32)
         if self.accum > 1 and self.acc_dev is None:
             self.acc_dev, self._acc_word = torch.zeros(1, device=dev, dtype=torch.int32), 0
@@ -421,7 +431,8 @@ class GraphedTrainStep:
         self._pending_momentum = None
 
     def __call__(self, data, in_theta, q_theta, rois, target, noise=None):
-        """One train step; returns the device tensor [loss, f0*l1, f1*l2, f2*l3] (valid in stream order).  `noise`: the batch's
+        """One train step; returns the device tensor [loss, f0*l1, f1*l2, f2*l3] (valid in stream order; with cfg.SOLVER.ssim_factor > 0 a
+        fifth element, the SSIM term, which `loss` then includes).  `noise`: the batch's
         [B, L] or [B, 1, L] noise rows, required when cfg.DATA.noise is set and ignored when it is not (as the reference ignores
         meta['noise'] then)."""
         self.model._check_inputs(data, rois)       # what Model_nefnet.forward rejects (float rois, L % 4, CPU tensors) is rejected here too

@@ -24,4 +24,7 @@ def build_loss(cfg):
         make = _LOSSES[cfg.MODEL.loss]
     except KeyError:
         raise ValueError('build loss: loss name error') from None
+    if cfg.MODEL.loss == "v1":
+        from .loss.losses import ssim_settings
+        ssim_settings(cfg, need_rois=False)          # a negative SOLVER.ssim_factor is rejected here, not at the first batch
     return make()

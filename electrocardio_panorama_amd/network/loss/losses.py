@@ -6,27 +6,56 @@ from ... import ops
 
 class _LossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pred, pred_p, pred_l, target, factors, reg_l2, use_mask, noise=None):
+    def forward(ctx, pred, pred_p, pred_l, target, factors, reg_l2, use_mask, noise=None, ssim_factor=0.0, rois=None):
         pred, pred_p, pred_l, target = (t.contiguous() for t in (pred, pred_p, pred_l, target))
-        ctx.save_for_backward(pred, pred_p, pred_l, target, noise)
-        ctx.cfg = (factors, reg_l2, use_mask)
-        return ops.loss_fwd(pred, pred_p, pred_l, target, factors, reg_l2, use_mask, noise=noise)
+        ctx.save_for_backward(pred, pred_p, pred_l, target, noise, rois)
+        ctx.cfg = (factors, reg_l2, use_mask, ssim_factor)
+        if not ssim_factor > 0:
+            return ops.loss_fwd(pred, pred_p, pred_l, target, factors, reg_l2, use_mask, noise=noise)
+        # SOLVER.ssim_factor: a 5-element row -- the SSIM term behind the four, added into the total by its own finish launch
+        row = torch.empty(5, device=pred.device, dtype=torch.float32)
+        ops.loss_fwd(pred, pred_p, pred_l, target, factors, reg_l2, use_mask, out=row, noise=noise)
+        return ops.loss_ssim_fwd(pred, target, row, ssim_factor, rois=rois, noise=noise)
 
     @staticmethod
     def backward(ctx, g):
-        pred, pred_p, pred_l, target, noise = ctx.saved_tensors
-        factors, reg_l2, use_mask = ctx.cfg
-        g_pred, g_p, g_l = ops.loss_bwd(pred, pred_p, pred_l, target, g.contiguous(), factors, reg_l2, use_mask, noise=noise)
-        return g_pred, g_p, g_l, None, None, None, None, None
+        pred, pred_p, pred_l, target, noise, rois = ctx.saved_tensors
+        factors, reg_l2, use_mask, ssim_factor = ctx.cfg
+        g = g.contiguous()
+        g_pred, g_p, g_l = ops.loss_bwd(pred, pred_p, pred_l, target, g, factors, reg_l2, use_mask, noise=noise)
+        if ssim_factor > 0:         # accumulated onto the reconstruction term's gradient, in the same stream behind it
+            ops.loss_ssim_bwd(pred, target, g_pred, ssim_factor, rois=rois, noise=noise, gscale=g)
+        return g_pred, g_p, g_l, None, None, None, None, None, None, None
+
+
+def ssim_settings(cfg, rois=None, need_rois=True):
+    """(SOLVER.ssim_factor, the rois the SSIM term crops its rows with or None for whole rows).  A negative (or NaN) factor and
+    ssim_crop without rois raise ValueError; factor 0: (0.0, None), whatever else is set."""
+    factor = float(cfg.SOLVER.get('ssim_factor', 0.0))         # (.get: configs written before the key existed)
+    if not factor >= 0.0:
+        raise ValueError(f"Invalid SOLVER.ssim_factor: {factor} (it must be >= 0)")
+    if factor == 0.0:
+        return 0.0, None
+    if not cfg.SOLVER.get('ssim_crop', True):
+        return factor, None
+    if rois is None and need_rois:
+        raise ValueError("SOLVER.ssim_crop is set: the SSIM term needs this batch's rois (losswrapper(..., rois=)); "
+                         "set SOLVER.ssim_crop False to take whole rows")
+    return factor, rois
 
 
 def losswrapper(predict, predict_shuffle_p, predict_shuffle_l, target, cfg, rest_out=None, rest_view=None,
-                loss1_gt=None, loss2_gt=None, noise=None):
-    """Returns (loss, f0*loss1, f1*loss2, f2*loss3[, loss_unsperv]) as 0-dim tensors; `loss` supports .backward().
+                loss1_gt=None, loss2_gt=None, noise=None, rois=None):
+    """Returns (loss, f0*loss1, f1*loss2, f2*loss3[, loss_unsperv][, loss_ssim]) as 0-dim tensors; `loss` supports .backward().
     The Standin terms compare against the detached prediction (OurLoss1, losses.py:5-18).
     `noise` (behind the reference's signature): cfg.DATA.noise's per-sample row, [B, 1, L] or anything that expands to the prediction's
     shape.  The three terms are taken at predict + noise inside the loss kernels -- the reference's `out = out + noise` between model
-    and loss (solver.py:185-186), bit for bit, without a kernel of its own; the rest_out / rest_view term never sees it."""
+    and loss (solver.py:185-186), bit for bit, without a kernel of its own; the rest_out / rest_view term never sees it.
+    `rois` (behind `noise`; no counterpart in the reference): the batch's int64 [B, 7, 2] rois.  With cfg.SOLVER.ssim_factor > 0 the tuple
+    gains the SSIM term ssim_factor * (1 - mean SSIM(predict (+ noise), target)) as its LAST element and `loss` includes it; with
+    cfg.SOLVER.ssim_crop the rows end at rois[i, -1, 0] as the test phase's ssim_gen does (rois is required then).  Factor 0: `rois` is
+    not looked at and the tuple, the launches and the bits are what they were."""
+    ssim_factor, ssim_rois = ssim_settings(cfg, rois)
     if cfg.SOLVER.reg_loss == 'l2_loss':
         reg_l2 = True
     elif cfg.SOLVER.reg_loss == 'l1_loss':
@@ -41,14 +70,17 @@ def losswrapper(predict, predict_shuffle_p, predict_shuffle_l, target, cfg, rest
     target = target.to(torch.float32).expand_as(predict)
     if noise is not None:
         noise = noise.detach().to(torch.float32).expand_as(predict).contiguous()
-    L4 = _LossFn.apply(predict, predict_shuffle_p, predict_shuffle_l, target, factors, reg_l2, use_mask, noise)
+    if ssim_rois is not None:
+        ssim_rois = ssim_rois.detach().to(torch.int64).contiguous()
+    L4 = _LossFn.apply(predict, predict_shuffle_p, predict_shuffle_l, target, factors, reg_l2, use_mask, noise, ssim_factor, ssim_rois)
     result = (L4[0], L4[1].detach(), L4[2].detach(), L4[3].detach())
+    tail = (L4[4].detach(),) if ssim_factor > 0 else ()
     if rest_out is not None and rest_view is not None:
         ro = rest_out.detach().to(torch.float32).contiguous()
         rv = rest_view.detach().to(torch.float32).contiguous()
         unsup = ops.loss_fwd(ro, ro, ro, rv, (0.0, 0.0, 1.0), reg_l2, 4)[3]
-        return result + (unsup,)
-    return result
+        return result + (unsup,) + tail
+    return result + tail
 
 
 class MSELead(torch.nn.Module):
@@ -59,4 +91,4 @@ class MSELead(torch.nn.Module):
         target = target.to(torch.float32).expand_as(input)
         # element [0] (the total) is the one _LossFn back-propagates through; with factors (0, 0, 1) and only the
         # reconstruction term enabled it IS the MSE (element [3] carries the same number but no gradient)
-        return _LossFn.apply(input, input, input, target, (0.0, 0.0, 1.0), True, 4, None)[0]
+        return _LossFn.apply(input, input, input, target, (0.0, 0.0, 1.0), True, 4, None, 0.0, None)[0]

@@ -1692,6 +1692,63 @@ def loss_bwd(pred, pred_p, pred_l, target, gscale, factors, reg_l2, use_mask, no
     return g_pred, g_p, g_l
 
 
+LOSS_SSIM_TILE = 512      # NEF_LOSS_SSIM_TILE (include/nefnet_hip.h): window starts / positions per block of the two SSIM kernels
+
+
+def _ssim_args(pred, target, factor, rois, noise):
+    """The checks and the shape the two SSIM entries share: pred / target [B, 1, L] (or [B, L]), rois None or int64 [B, 7, 2], noise None
+    or pred's elements."""
+    _chk(pred), _chk(target)
+    if pred.dim() < 2 or target.numel() != pred.numel():
+        raise ValueError(f"prediction {tuple(pred.shape)} and target {tuple(target.shape)} must hold the same [B, 1, L] rows")
+    Ln = pred.shape[-1]
+    B = pred.numel() // Ln
+    if noise is not None and _chk(noise).numel() != pred.numel():
+        raise ValueError(f"noise {tuple(noise.shape)} does not have the prediction's {tuple(pred.shape)} elements")
+    if rois is not None and (_chk(rois, torch.int64).dim() != 3 or tuple(rois.shape) != (B, N_SEG, 2)):
+        raise ValueError(f"rois {tuple(rois.shape)} is not [{B}, {N_SEG}, 2]")
+    if not float(factor) >= 0.0:
+        raise ValueError(f"Invalid ssim factor: {factor}")
+    return B, Ln
+
+
+def loss_ssim_fwd(pred, target, losses, factor, rois=None, noise=None):
+    """The SSIM term of the training loss behind loss_fwd (nef_loss_ssim_fwd, include/nefnet_hip.h): losses[4] = factor * (1 - mean SSIM
+    of pred (+ noise) against target over the rows with a 7-tap window on [0, rois[i, -1, 0]), whole rows with rois None) and
+    losses[0] += losses[4].  `losses`: the FIVE-element row whose first four elements loss_fwd(out=) has written.  Two launches,
+    capturable."""
+    L = _lib.load()
+    B, Ln = _ssim_args(pred, target, factor, rois, noise)
+    _chk(losses)
+    assert losses.numel() == 5, losses.shape
+    n = L.nef_loss_ssim_ws_bytes(B, Ln)
+    ws = workspace(n, pred.device)
+    ev = _hbm("loss_ssim_fwd", pred, target, noise)
+    A = _lib.LossSsimArgs(pred=_p(pred), target=_p(target), noise=_p(noise), rois=_p(rois), losses=_p(losses), ws=_p(ws), ws_bytes=n,
+                          gscale=None, g_pred=None, B=B, L=Ln, factor=float(factor))
+    _lib.check(L.nef_loss_ssim_fwd(C.byref(A), _stream()), "nef_loss_ssim_fwd")
+    _done(ev)
+    return losses
+
+
+def loss_ssim_bwd(pred, target, g_pred, factor, rois=None, noise=None, gscale=None):
+    """g_pred += gscale * d(SSIM term) / d pred behind loss_bwd (nef_loss_ssim_bwd): `g_pred` is loss_bwd's first gradient, the first
+    third of its [3B, 1, L] buffer.  Positions at or behind a row's end and rows without a window keep their bits.  `gscale`: None (1) or
+    loss_bwd's device word.  One launch, capturable, no state: the row count is re-derived from `rois` on the device."""
+    L = _lib.load()
+    B, Ln = _ssim_args(pred, target, factor, rois, noise)
+    if _chk(g_pred).numel() != pred.numel():
+        raise ValueError(f"g_pred {tuple(g_pred.shape)} does not have the prediction's {tuple(pred.shape)} elements")
+    if gscale is not None:
+        _chk(gscale)
+    ev = _hbm("loss_ssim_bwd", pred, target, noise, g_pred, g_pred)
+    A = _lib.LossSsimArgs(pred=_p(pred), target=_p(target), noise=_p(noise), rois=_p(rois), losses=None, ws=None, ws_bytes=0,
+                          gscale=_p(gscale), g_pred=_p(g_pred), B=B, L=Ln, factor=float(factor))
+    _lib.check(L.nef_loss_ssim_bwd(C.byref(A), _stream()), "nef_loss_ssim_bwd")
+    _done(ev)
+    return g_pred
+
+
 def flatten_into(tensors, out, accumulate=False, accumulate_dev=None):
     """out[:] = concatenation of `tensors` (contiguous fp32, flattened), ONE launch per 64 tensors (nef_flatten; was torch.cat).
     `accumulate`: out[:] += the concatenation instead (gradient accumulation: one fp32 add per element, no atomics).  `accumulate_dev`: a

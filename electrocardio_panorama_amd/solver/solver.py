@@ -181,6 +181,14 @@ class Solver:
                         scalars += [float(np.mean(single[:, i, 0])), float(np.mean(single[:, i, 1]))]
                 msg += ', test_loss: {}'.format(float(te[0]))
                 msg += '\npsnr_gen: {}, psnr_reg: {}, ssim_gen:{}, ssim_reg:{}'.format(psnr_gen, psnr_reg, ssim_gen, ssim_reg)
+            if tl.shape[0] > 4:                   # SOLVER.ssim_factor is on: the term is the last element of every loss row
+                scalars.append(float(tl[-1]))
+                names.append('train_loss_ssim')
+                msg += '\nloss_ssim (factor {}): train {}'.format(self.cfg.SOLVER.get('ssim_factor', 0.0), float(tl[-1]))
+                if dl_test is not None:
+                    scalars.append(float(te[-1]))
+                    names.append('test_loss_ssim')
+                    msg += ', test {}'.format(float(te[-1]))
             if self.last_grad_norms:              # SOLVER.clip_grad_norm is on
                 norms = [t for t, _ in self.last_grad_norms if np.isfinite(t)]
                 scalars.append(float(np.mean(norms)) if norms else float('nan'))
@@ -255,6 +263,12 @@ class Solver:
                 raise ValueError(f"DATA.super_mode {super_mode!r}: the last character must be the number of generated views")
             gen_num = int(super_mode[-1])
         return gen_num, whole
+
+    def _loss_rois(self, rois):
+        """`rois=` for the loss when SOLVER.ssim_factor is on and the loss takes it (losswrapper); nothing otherwise."""
+        if self.cfg.MODEL.loss == 'v1' and float(self.cfg.SOLVER.get('ssim_factor', 0.0)) > 0:
+            return {'rois': rois}
+        return {}
 
     def _graphed_step(self, optim, data, keep):
         """The hipGraph stepper for this batch, or None when the step runs eagerly: `cfg.SOLVER.graph` False, the per-view host lists are wanted (the graph returns losses only), the
@@ -353,7 +367,8 @@ class Solver:
                 if keep:
                     pred_s.add(out.squeeze(1))                     # solver.py:179 (before the optional noise)
                 # DATA.noise (solver.py:185-186): the loss kernels add the row to the prediction, no launch of its own
-                losses = self.loss(out, shuf_p, shuf_l, target_view, self.cfg, noise=noise if self.cfg.DATA.noise else None)
+                losses = self.loss(out, shuf_p, shuf_l, target_view, self.cfg, noise=noise if self.cfg.DATA.noise else None,
+                                   **self._loss_rois(rois))
                 losses_s.add(torch.stack([l_.detach() for l_ in losses]))
                 losses[0].backward()
                 optim.step()
@@ -363,7 +378,7 @@ class Solver:
                 out, shuf_p, shuf_l, rest_out = self.model(source_data, input_theta, target_theta, rois,
                                                            rest_theta=rest_theta, phase='test')
                 losses = self.loss(out, shuf_p, shuf_l, target_view, self.cfg, rest_out[:, -4:, :].contiguous(),
-                                   rest_view[:, -4:, :].contiguous())
+                                   rest_view[:, -4:, :].contiguous(), **self._loss_rois(rois))
                 losses_s.add(torch.stack([l_.detach() for l_ in losses]))
                 ps, ss = ops.view_metrics(rest_out.contiguous(), rest_view, None if whole else rois.contiguous())
                 psnr_s.add(ps)

@@ -34,7 +34,7 @@ extern "C" {
 typedef void* nef_stream_t;
 
 /* ABI version of this header; bumped on any signature change. */
-int nef_abi_version(void);   /* 22 (+ nef_flatten_acc, nef_lr_sched / nef_lr_sched_args_bytes: additions only, the number stays; a binding finds a library without them by the missing symbol.  Weight packing is ONE entry, nef_pack_weights(nef_pack_desc*, n), + nef_pack_bytes(nef_pack_desc*) for the size of any operand.  ABI <= 21 had nef_pack_weight, nef_pack_weight_wino, nef_pack_weight_wino4, nef_pack_weight_h2 and nef_pack_weight_h2_bytes: each is one descriptor with wino = 0 / 1 / 2 / 3); 21 (BatchNorm backward is ONE entry on a nef_bn_bwd_args struct, + nef_bn_bwd_args_bytes; nef_mix_bwd takes `up` / `shared` flags; nef_outconv_fwd / nef_outconv_bwd_weight take the prologue arguments.  ABI <= 20 had nef_bn_relu_bwd_phase_major, nef_bn_relu_bwd_up, nef_bn_relu_bwd_combine3, nef_bn_relu_bwd_combine3_phase_major, nef_bn_relu_bwd_outconv, nef_bn_bwd_outconv_ws_bytes, nef_mix_bwd_up, nef_mix_bwd_shared, nef_mix_bwd_shared_up, nef_outconv_fwd_pro and nef_outconv_bwd_weight_pro); 20 (the weight gradient is ONE entry, nef_conv_bwd_weight(nef_bww_args*), + nef_bww_args_bytes; its _pro, _wino4, _h2 and _h2_ws_bytes variants are gone); 19 (+ nef_adam, nef_h2_tail_census, nef_bwd_weight_clamp_ends: additions only; the kernel-form option entry points of 16 and nef_upsample2_aff_fwd are gone; + nef_debug_spin_us); 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + kernel-form option entry points); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + the split-fp16 weight gradient, now form 3); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, the transposed F(3,4) / F(4,4) entry, now form 4, covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
+int nef_abi_version(void);   /* 22 (+ nef_flatten_acc, nef_lr_sched / nef_lr_sched_args_bytes, nef_loss_ssim_fwd / nef_loss_ssim_bwd / nef_loss_ssim_ws_bytes / nef_loss_ssim_args_bytes: additions only, the number stays; a binding finds a library without them by the missing symbol.  Weight packing is ONE entry, nef_pack_weights(nef_pack_desc*, n), + nef_pack_bytes(nef_pack_desc*) for the size of any operand.  ABI <= 21 had nef_pack_weight, nef_pack_weight_wino, nef_pack_weight_wino4, nef_pack_weight_h2 and nef_pack_weight_h2_bytes: each is one descriptor with wino = 0 / 1 / 2 / 3); 21 (BatchNorm backward is ONE entry on a nef_bn_bwd_args struct, + nef_bn_bwd_args_bytes; nef_mix_bwd takes `up` / `shared` flags; nef_outconv_fwd / nef_outconv_bwd_weight take the prologue arguments.  ABI <= 20 had nef_bn_relu_bwd_phase_major, nef_bn_relu_bwd_up, nef_bn_relu_bwd_combine3, nef_bn_relu_bwd_combine3_phase_major, nef_bn_relu_bwd_outconv, nef_bn_bwd_outconv_ws_bytes, nef_mix_bwd_up, nef_mix_bwd_shared, nef_mix_bwd_shared_up, nef_outconv_fwd_pro and nef_outconv_bwd_weight_pro); 20 (the weight gradient is ONE entry, nef_conv_bwd_weight(nef_bww_args*), + nef_bww_args_bytes; its _pro, _wino4, _h2 and _h2_ws_bytes variants are gone); 19 (+ nef_adam, nef_h2_tail_census, nef_bwd_weight_clamp_ends: additions only; the kernel-form option entry points of 16 and nef_upsample2_aff_fwd are gone; + nef_debug_spin_us); 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + kernel-form option entry points); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + the split-fp16 weight gradient, now form 3); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, the transposed F(3,4) / F(4,4) entry, now form 4, covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
 
 /* Diagnostics: `wgs` workgroups busy for `us` microseconds on `stream` (a stand-in for a collective's time on the chip:
  * parallel.DryCollective, bench.py --dry-collective).  0 <= us <= 50000, 1 <= wgs <= 64. */
@@ -554,6 +554,46 @@ int nef_loss_noise_fwd(const float* pred, const float* pred_p, const float* pred
 int nef_loss_noise_bwd(const float* pred, const float* pred_p, const float* pred_l, const float* target,
                        const float* noise, const float* gscale /* device scalar */, float* g_pred, float* g_p, float* g_l,
                        int64_t n, float f0, float f1, float f2, int reg_l2, int use_mask, nef_stream_t stream);
+
+/* The structural-similarity term of the training loss (cfg.SOLVER.ssim_factor; no counterpart in the reference): factor * (1 - mean SSIM)
+ * beside the three terms above, with the SSIM of nef_view_metrics (utils/metric.py:ssim_1d) so that 1 - term / factor is the number the
+ * test phase reports on the same rows.  Row i of x = pred (+ noise: the same fp32 add as above) against target on [0, end_i), end_i =
+ * clamp(rois[i, -1, 0], 0, L), or L with rois NULL.  7-tap uniform window, n = 7/6, c1 = 1e-4, c2 = 9e-4:
+ *   S_p = (2 ux uy + c1)(2 vxy + c2) / ((ux^2 + uy^2 + c1)(vx + vy + c2)),  S_i = mean of S_p over the end_i - 6 full windows;
+ *   a row with end_i < 7 has no window and is left out (zero gradient);  R = rows with a window;
+ *   term = factor * (1 - (1/R) sum_i S_i),  0 with R = 0.
+ * fwd (two launches behind nef_loss_*_fwd on the same stream): fp64 window arithmetic, one fp64 partial sum per (row, tile of
+ *   NEF_LOSS_SSIM_TILE window starts) in ws, a one-block finish that adds them in a fixed order (no atomics: the same bits eagerly,
+ *   under hipGraph replay and on every rank) and writes losses[4] = (float)term, then losses[0] = losses[0] + losses[4] (one fp32 add).
+ *   `losses` has FIVE elements here.  g_pred and gscale are not read.
+ * bwd (one launch behind nef_loss_*_bwd on the same stream): g_pred[i, t] += (float)g_t for t < end_i,
+ *   g_t = -factor * gscale / (R (end_i - 6)) * sum over the windows p that hold t of dS_p/dx_t, in fp64 (per window a_p + b_p x_t + c_p y_t);
+ *   positions t >= end_i and rows without a window are not touched.  R is derived from rois inside the launch: the entry keeps no
+ *   state.  gscale: NULL (1) or the device word of nef_loss_bwd.  losses, ws and ws_bytes are not read.
+ * args, pred, target, losses (fwd) / g_pred (bwd) NULL: NEF_E_NULL; B or L <= 0, B > 65535, a negative or NaN factor: NEF_E_SHAPE; fwd: ws_bytes below
+ * nef_loss_ssim_ws_bytes(B, L): NEF_E_WORKSPACE, then ws NULL: NEF_E_NULL.  Every check sits in front of the launches.  Capturable: nothing
+ * is read by the host, nothing is allocated. */
+#define NEF_LOSS_SSIM_TILE 512
+typedef struct nef_loss_ssim_args {
+    const float* pred;      /* [B, L] */
+    const float* target;    /* [B, L] */
+    const float* noise;     /* NULL, or [B, L] */
+    const int64_t* rois;    /* NULL (whole rows), or [B, 7, 2] */
+    float* losses;          /* fwd: the 5-element loss row */
+    void* ws;               /* fwd */
+    size_t ws_bytes;        /* fwd */
+    const float* gscale;    /* bwd: NULL, or a device scalar */
+    float* g_pred;          /* bwd: [B, L], accumulated into */
+    int32_t B;              /* rows, 1 .. 65535 */
+    int32_t L;              /* row length */
+    float factor;           /* >= 0 */
+    int32_t reserved0;      /* 0 */
+} nef_loss_ssim_args;
+int nef_loss_ssim_fwd(const nef_loss_ssim_args* a, nef_stream_t stream);
+int nef_loss_ssim_bwd(const nef_loss_ssim_args* a, nef_stream_t stream);
+size_t nef_loss_ssim_ws_bytes(int B, int L);
+/* sizeof(nef_loss_ssim_args) as the library was built. */
+size_t nef_loss_ssim_args_bytes(void);
 
 /* ---------------------------------------------------------------------------------------------
  * SGD with momentum over a flat buffer.  codes/solver/optim_scheduler.py:10 (torch.optim.SGD semantics:

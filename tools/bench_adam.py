@@ -7,6 +7,7 @@
     python tools/bench_adam.py --trust lars|lamb [--parent-tree DIR] [--out profiles/r11_trust_bench_line.json]
     python tools/bench_adam.py --accum K [--parent-tree DIR] [--out profiles/r12_accum_bench_line.json]
     python tools/bench_adam.py --sched const|cosine|poly --warmup W [--parent-tree DIR] [--out profiles/r14_sched_bench_line.json]
+    python tools/bench_adam.py --ssim F [--parent-tree DIR] [--out profiles/r15_ssim_bench_line.json]
 
 Each measurement runs in a child process of its own under `timeout` (nothing more is started once one fails), `--reps` rounds of
 the three children; every figure is reported as [min, median, max] over the rounds:
@@ -53,7 +54,12 @@ round and shape the graphed FusedSGD step with the keys off (sgd-graph: the pare
 warmup_updates = W, lr_shape = SHAPE, total_updates = W + 1000, so the timed steps sit on the ramp or the shape), and -- with --parent-tree
 DIR -- DIR's own sgd-graph step.  Beside --sched, --warmup is the SCHEDULE's W; every child then runs 3 untimed steps in front of the
 timed ones (the default of the other measurements).  The config-2 schedule child also times the nef_lr_sched launch alone: cold as above
-and warm (back-to-back launches).  Writes profiles/r14_sched_bench_line.json unless --out says otherwise."""
+and warm (back-to-back launches).  Writes profiles/r14_sched_bench_line.json unless --out says otherwise.
+
+--ssim F measures the SSIM term of the training loss (SOLVER.ssim_factor = F, ssim_crop true), at the same two shapes: per round and
+shape the graphed FusedSGD step with the key off (sgd-graph: the parent's code path) and on (sgd-graph-ssim), and -- with --parent-tree
+DIR -- DIR's own sgd-graph step.  The config-2 child with the term on also times the term's launches alone, cold: nef_loss_ssim_fwd
+(two launches) and nef_loss_ssim_bwd.  Writes profiles/r15_ssim_bench_line.json unless --out says otherwise."""
 import argparse
 import json
 import os
@@ -93,7 +99,7 @@ def cold_ms(launches, dev, reps=30):
     return [float(np.median([a.elapsed_time(b) for a, b in ev])) for ev in evs]
 
 
-def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=(), ema=0.0, accum=1, sched=None):
+def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=(), ema=0.0, accum=1, sched=None, ssim=0.0):
     import numpy as np
     import torch
     from electrocardio_panorama_amd import ops, synth
@@ -105,12 +111,14 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
     cfg = get_defaults()
     cfg.merge_from_file(resolve_config_path("config/nef_net.yml"))
     cfg.DATA.lead_num = V
+    if mode == "sgd-graph-ssim":
+        cfg.SOLVER.ssim_factor, cfg.SOLVER.ssim_crop = float(ssim), True
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     seed_torch(cfg.seed)
     model = build_model(cfg).float().to(dev).train()
     lossf = build_loss(cfg)
-    if mode == "sgd-graph":
+    if mode in ("sgd-graph", "sgd-graph-ssim"):
         optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9)
     elif mode == "sgd-graph-clip":
         optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9, max_grad_norm=clip)
@@ -189,6 +197,15 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
         e1.record()
         e1.synchronize()
         res.update(nef_lr_sched_cold_ms=round(cold, 4), nef_lr_sched_warm_ms=round(e0.elapsed_time(e1) / reps, 4))
+    if mode == "sgd-graph-ssim":
+        res.update(ssim_factor=ssim, loss_row=[round(float(v), 6) for v in graphed.losses.tolist()])
+    if mode == "sgd-graph-ssim" and (B, L) == EMA_SHAPES["config2"]:
+        pred, g_pred, row = torch.rand(B, 1, L, device=dev) / 3, torch.zeros(B, 1, L, device=dev), torch.zeros(5, device=dev)
+        fwd_ms, bwd_ms = cold_ms([lambda: ops.loss_ssim_fwd(pred, tgt_view, row, ssim, rois=rois),
+                                  lambda: ops.loss_ssim_bwd(pred, tgt_view, g_pred, ssim, rois=rois)], dev)
+        n = pred.numel()
+        res.update(nef_loss_ssim_fwd_cold_ms=round(fwd_ms, 4), nef_loss_ssim_bwd_cold_ms=round(bwd_ms, 4),
+                   nef_loss_ssim_bwd_cold_GBps=round(4 * 4 * n / (bwd_ms * 1e-3) / 1e9, 1))
     if mode == "sgd-graph-ema":
         fl = optim._flat[0]
         p, g, buf, e, e_n = (fl[k].clone() for k in ("p", "g", "buf", "ema", "ema_n"))
@@ -458,6 +475,57 @@ def sched_rounds(args):
         f.write(line + "\n")
 
 
+def ssim_rounds(args):
+    """--ssim F: `--reps` alternating rounds of fresh children per shape (see the module docstring); prints and writes one JSON line."""
+    modes = dict({"sgd-graph": 900, "sgd-graph-ssim": 900}, **({"parent": 900} if args.parent_tree else {}))
+    results = {(shape, mode): [] for shape in EMA_SHAPES for mode in modes}
+    for rnd in range(args.reps):
+        order = list(modes) if rnd % 2 == 0 else list(reversed(modes))
+        for shape, (B, L) in EMA_SHAPES.items():
+            for mode in order:
+                if mode == "parent":
+                    # the parent's tool may lack --shape: its `child` function is called directly, in a fresh process of its own tree
+                    tree = os.path.abspath(args.parent_tree)
+                    code = ("import importlib.util as u; s = u.spec_from_file_location('parent_bench', %r); m = u.module_from_spec(s); "
+                            "s.loader.exec_module(m); m.child('sgd-graph', %d, %d, B=%d, L=%d)"
+                            % (os.path.join(tree, "tools", "bench_adam.py"), args.steps, args.warmup, B, L))
+                    cmd = ["timeout", "-k", "10", str(modes[mode]), sys.executable, "-c", code]
+                else:
+                    tree = ROOT
+                    cmd = ["timeout", "-k", "10", str(modes[mode]), sys.executable, os.path.join(ROOT, "tools", "bench_adam.py"), "--child", mode,
+                           "--steps", str(args.steps), "--warmup", str(args.warmup), "--shape", str(B), str(L)]
+                    if mode == "sgd-graph-ssim":
+                        cmd += ["--ssim", str(args.ssim)]
+                results[(shape, mode)].append(run_child(cmd, tree, mode))
+                sys.stderr.write(f"round {rnd + 1}/{args.reps} {shape} {mode}: {results[(shape, mode)][-1]['ms_per_step']} ms/step\n")
+                sys.stderr.flush()
+
+    def spread(shape, mode, key):
+        v = sorted(x[key] for x in results[(shape, mode)])
+        return [v[0], v[len(v) // 2], v[-1]]
+
+    out = {"metric": "ms per train step, graphed FusedSGD with the SSIM term of the loss off and on ([min, median, max] over rounds)",
+           "rounds": args.reps, "ssim_factor": args.ssim,
+           "shapes": {k: "B=%d, 3 leads, L=%d, one GPU, dropout on" % v for k, v in EMA_SHAPES.items()}}
+    for shape in EMA_SHAPES:
+        out[shape + "_ssim_off_ms"] = spread(shape, "sgd-graph", "ms_per_step")
+        out[shape + "_ssim_on_ms"] = spread(shape, "sgd-graph-ssim", "ms_per_step")
+        if args.parent_tree:
+            out[shape + "_parent_ms"] = par = spread(shape, "parent", "ms_per_step")
+            # to be read against each other: the key-off median and the parent's own min-max spread; the bar with the key on: + 0.3 ms
+            out[shape + "_ssim_off_median_inside_parent_spread"] = par[0] <= out[shape + "_ssim_off_ms"][1] <= par[2]
+            out[shape + "_ssim_on_median_minus_parent_median_ms"] = round(out[shape + "_ssim_on_ms"][1] - par[1], 3)
+    out.update(nef_loss_ssim_fwd_cold_ms=spread("config2", "sgd-graph-ssim", "nef_loss_ssim_fwd_cold_ms"),
+               nef_loss_ssim_bwd_cold_ms=spread("config2", "sgd-graph-ssim", "nef_loss_ssim_bwd_cold_ms"),
+               launch_note="the term's launches alone at config 2 on the batch's rois (forward: partial sums + finish; backward: one launch); "
+                           "cold = a 512 MiB buffer written before each call",
+               steps=args.steps, warmup=args.warmup)
+    line = json.dumps(out)
+    print(line)
+    with open(args.out or os.path.join(ROOT, "profiles", "r15_ssim_bench_line.json"), "w") as f:
+        f.write(line + "\n")
+
+
 def trust_rounds(args):
     """--trust lars|lamb: `--reps` alternating rounds of fresh children per shape (see the module docstring); prints and writes one JSON
     line."""
@@ -527,11 +595,12 @@ def main():
     ap.add_argument("--sched", choices=("const", "cosine", "poly"), default=None,
                     help="measure the per-update learning-rate schedule of this shape; --warmup is then the schedule's W (see above)")
     ap.add_argument("--sched-warmup", type=int, default=None, metavar="W", help="with --child sgd-graph-sched: the schedule's W")
+    ap.add_argument("--ssim", type=float, default=None, metavar="F", help="measure the SSIM term of the loss, ssim_factor = F (see above)")
     ap.add_argument("--shape", type=int, nargs=2, default=(256, 5000), metavar=("B", "L"), help="with --child: batch size and length")
     ap.add_argument("--parent-tree", default=None,
                     help="with --clip / --weight-decay / --ema: a built checkout whose own sgd-graph child runs in every round")
     ap.add_argument("--child", choices=sorted({**MODES, **CLIP_MODES, **WD_MODES, **EMA_MODES, "lars-graph": 900, "lamb-graph": 900, "sgd-graph-accum": 900,
-                                             "sgd-graph-sched": 900}),
+                                             "sgd-graph-sched": 900, "sgd-graph-ssim": 900}),
                     default=None)
     args = ap.parse_args()
     if args.child == "sgd-graph-ema" and not (args.ema is not None and 0.0 < args.ema < 1.0):
@@ -556,14 +625,22 @@ def main():
         ap.error("--sched SHAPE --warmup W >= 0 is a measurement of its own")
     if args.child == "sgd-graph-sched" and (args.sched is None or args.sched_warmup is None):
         ap.error("--child sgd-graph-sched needs --sched SHAPE and --sched-warmup W")
+    if args.ssim is not None and (not args.ssim > 0 or (not args.child and (
+            args.clip is not None or args.weight_decay is not None or args.ema is not None or args.trust is not None
+            or args.accum is not None or args.sched is not None))):
+        ap.error("--ssim F > 0 is a measurement of its own")
+    if args.child == "sgd-graph-ssim" and args.ssim is None:
+        ap.error("--child sgd-graph-ssim needs --ssim F")
     if (args.parent_tree and args.clip is None and args.weight_decay is None and args.ema is None and args.trust is None
-            and args.accum is None and args.sched is None):
-        ap.error("--parent-tree goes with --clip, --weight-decay, --ema, --trust, --accum or --sched")
+            and args.accum is None and args.sched is None and args.ssim is None):
+        ap.error("--parent-tree goes with --clip, --weight-decay, --ema, --trust, --accum, --sched or --ssim")
     if args.child:
         return child(args.child, args.steps if args.child != "adam-eager" else max(3, args.steps // 2), args.warmup,
                      B=args.shape[0], L=args.shape[1], clip=args.clip or 0.0, wd=args.weight_decay or 0.0,
                      no_decay=tuple(args.no_decay), ema=args.ema or 0.0, accum=args.accum or 1,
-                     sched=(args.sched, args.sched_warmup) if args.child == "sgd-graph-sched" else None)
+                     sched=(args.sched, args.sched_warmup) if args.child == "sgd-graph-sched" else None, ssim=args.ssim or 0.0)
+    if args.ssim is not None:
+        return ssim_rounds(args)
     if args.sched is not None:
         return sched_rounds(args)
     if args.ema is not None:
