@@ -196,6 +196,7 @@ SIGNATURES = {
     "nef_step_words": (i32, [p, p, i32, i32, i64, p]),
     "nef_flatten": (i32, [C.POINTER(p), C.POINTER(i64), i32, p, p]),
     "nef_flatten_acc": (i32, [C.POINTER(p), C.POINTER(i64), i32, p, i32, p, p]),
+    "nef_copy_many": (i32, [C.POINTER(p), C.POINTER(p), C.POINTER(i64), i32, i32, p]),
     "nef_regroup_halves": (i32, [p, p, i32, i32, i32, i32, p]),
     "nef_slots_to_rows": (i32, [p, i32, p, i32, i32, p]),
     "nef_poly_weights": (i32, [p, p, i32, i32, i32, p]),

@@ -108,6 +108,14 @@ _DEFAULTS = {
         "ssim_factor": 0.0,
         # True: every row ends at rois[i, -1, 0] as in the test phase's metrics (a row shorter than the window is left out); False: whole rows
         "ssim_crop": True,
+        # target views supervised per train step.  The batch carries every lead that is not an input (rest_view / rest_theta, supervised
+        # ones first); with train_views = Q >= 2 a step draws Q of the S supervised ones -- one draw per step from (seed, epoch, batch
+        # index), shared by the batch and the ranks; Q == S takes all in order -- runs the encoder ONCE and the head (mlp2, Standin mixes,
+        # three decoder passes) once per view, each with its own BatchNorm batch statistics, and minimises the mean of the Q per-view
+        # losses: the gradient is the mean of Q single-view steps at one dropout seed and Standin draw.  target_view / target_theta are not
+        # used then; the loss row keeps its elements (each the mean over views).  Q > S and DATA.noise with Q >= 2 are rejected.
+        # 1 = off: the launches, graphs, loader fields and bits are what they were before the key existed
+        "train_views": 1,
     },
 }
 

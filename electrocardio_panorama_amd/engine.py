@@ -524,11 +524,43 @@ def _head_fwd(P, Bf, z1, z2r, q_theta, V, rest_theta, phase, training, lead_choi
     raise KeyError("please type correct phase")
 
 
+def _views_fwd(P, Bf, z1, z2r, q_theta, V, training, lead_choice, sv, unpool):
+    """The head once per query angle of q_theta [Q, B, 2] on ONE encoder pass (SOLVER.train_views; the reference's forward takes one
+    query_theta in train mode, model_nefnet.py:109): every view runs _head_fwd as a single-view step would -- its own BatchNorm batch
+    statistics, the running statistics updated in view order -- with the step's one dropout seed and Standin draw, and keeps its own
+    saved state.  Returns three contiguous [Q, B, 1, L] tensors, consecutive views of one [3, Q, B, 1, L] buffer: what
+    ops.loss_bwd's stacked gradient and ops.stacked3 expect, filled by one ops.copy_many launch."""
+    Q, B, L = q_theta.shape[0], z1.shape[0], 4 * z1.shape[2]
+    buf = torch.empty(3, Q, B, 1, L, device=z1.device, dtype=torch.float32)
+    heads, srcs, dsts = [], [], []
+    for k in range(Q):
+        hsv = None
+        if sv is not None:
+            hsv = dict(rois=sv["rois"])
+        # the step-level pack serves every view: the operands stay in the table until the last head has taken them
+        with ops.pack_keep(k < Q - 1):
+            outs, hsv = _head_fwd(P, Bf, z1, z2r, q_theta[k], V, None, "train", training, lead_choice, hsv, 8, False, unpool=unpool)
+        heads.append(hsv)
+        srcs += list(outs)
+        dsts += [buf[j, k] for j in range(3)]
+    ops.copy_many(srcs, dsts)
+    if sv is not None:
+        sv.update(z1=z1, views=heads)
+    return (buf[0], buf[1], buf[2]), sv
+
+
 def forward(P, Bf, x, in_theta, q_theta, rois, rest_theta=None, phase="train", training=True, drop=None,
             lead_choice=(0, 0), save=False, rest_chunk=8, status=None, half_sweep=False):
     """Returns (outputs tuple, saved-state or None).  `lead_choice` are the two Standin lead indices
-    (model_nefnet.py:154,156), drawn by the caller: a tuple of ints, or a device int32[2] tensor (graph replay)."""
+    (model_nefnet.py:154,156), drawn by the caller: a tuple of ints, or a device int32[2] tensor (graph replay).
+    A 3-D `q_theta` [Q, B, 2] (view-major; phase "train" only) is the multi-view form: one encoder pass, Q heads (_views_fwd), and
+    three [Q, B, 1, L] outputs."""
     drop = drop or DropCfg(False)
+    multi = q_theta.dim() == 3
+    if multi and phase != "train":
+        raise ValueError(f"a 3-D query_theta [Q, B, 2] is the multi-view TRAIN step; phase {phase!r} takes [B, 2]")
+    if multi and (q_theta.shape[0] < 1 or q_theta.shape[1] != x.shape[0] or q_theta.shape[2] != 2):
+        raise ValueError(f"query_theta {tuple(q_theta.shape)} is not [Q, {x.shape[0]}, 2]")
     B, V, L = x.shape
     T = L // 4
     ops.BATCH_HINT = B     # small batches stay on the fp32 kernels (ops._h2_fills)
@@ -544,9 +576,13 @@ def forward(P, Bf, x, in_theta, q_theta, rois, rest_theta=None, phase="train", t
         return (z1, z2b), None
     if _head_shared(T) and V <= ops.UNPOOL_MIX_MAX_V:
         # z2r [B, 128V, T] is never written: the mix reads the segments (and the backward hands their gradient straight back)
+        if multi:
+            return _views_fwd(P, Bf, z1, None, q_theta, V, training, lead_choice, sv, (z2b, rois, status))
         return _head_fwd(P, Bf, z1, None, q_theta, V, rest_theta, phase, training, lead_choice, sv, rest_chunk, half_sweep,
                          unpool=(z2b, rois, status))
     z2r = ops.roi_unpool_fwd(z2b, rois, T, status)
+    if multi:
+        return _views_fwd(P, Bf, z1, z2r, q_theta, V, training, lead_choice, sv, None)
     return _head_fwd(P, Bf, z1, z2r, q_theta, V, rest_theta, phase, training, lead_choice, sv, rest_chunk, half_sweep)
 
 
@@ -564,6 +600,9 @@ def forward2(P, Bf, x, in_theta, q_theta, rois, rest_theta=None, phase="train", 
     :140,:149) write their outputs lead by lead into lead-blocked [B, 128V, T] tensors, from where the lead mean, the
     Standin mixes and the decoder are exactly Model_nefnet's."""
     drop = drop or DropCfg(False)
+    if q_theta.dim() != 2:
+        raise ValueError(f"Model_nefnet2 takes one query_theta [B, 2] per step, got {tuple(q_theta.shape)} (the multi-view train step, "
+                         "SOLVER.train_views, is Model_nefnet's)")
     B, V, L = x.shape
     T, N = L // 4, V * B
     ops.BATCH_HINT = N
@@ -724,6 +763,38 @@ def _head_bwd(P, sv, g_outs, grads, side, relu_z1=False):
     return gz1, gz2r, gz2b, gz1_sum
 
 
+def _views_bwd(P, sv, g_outs, grads, side):
+    """Backward of _views_fwd: g_outs are the gradients wrt its three [Q, B, 1, L] outputs (or None).  One ops.copy_many launch hands
+    every view its stacked [3B, 1, L] gradient; the views then run _head_bwd in view order, and views 1 .. Q-1 are summed into view
+    0's results -- the latent gradients on this stream, the head's parameter gradients (decoder.*, mlp2.*) on the stream their
+    weight gradients were formed on -- one launch each per view, fixed order, so the sum has the same bits eagerly and under replay.
+    What comes back is what _head_bwd returns for one view: _latents_bwd runs once on it."""
+    heads = sv["views"]
+    Q, B = len(heads), sv["B"]
+    like = heads[0]["dec"][2]                                         # a view's stacked decoder output [3B, 1, L]
+    g = ops.stacked3(g_outs) if all(t is not None for t in g_outs) else None          # [3Q, B, 1, L]: ops.loss_bwd's buffer, no copy
+    if g is None:
+        parts = [t.contiguous() if t is not None else torch.zeros((Q, B) + tuple(like.shape[1:]), device=like.device) for t in g_outs]
+        g = torch.cat([p_.view((Q, B) + tuple(like.shape[1:])) for p_ in parts], dim=0)
+    gvs = [torch.empty_like(like) for _ in range(Q)]
+    ops.copy_many([g[j * Q + k] for k in range(Q) for j in range(3)], [gvs[k][j * B:(j + 1) * B] for k in range(Q) for j in range(3)])
+    out0 = None
+    for k in range(Q):
+        gk = grads if k == 0 else {}
+        with ops.pack_keep(k < Q - 1):
+            out = _head_bwd(P, heads[k], (gvs[k][0:B], gvs[k][B:2 * B], gvs[k][2 * B:]), gk, side, relu_z1=True)
+        heads[k] = None                                               # (the view's saved activations are free from here on)
+        if k == 0:
+            out0 = out
+            continue
+        lat = [(s, d) for s, d in zip(out, out0) if s is not None]
+        ops.copy_many([s for s, _ in lat], [d for _, d in lat], accumulate=True)
+        names = [n for n in gk if gk[n] is not None]
+        srcs = [gk[n] if gk[n].is_contiguous() else gk[n].contiguous() for n in names]
+        side.run(lambda: ops.copy_many(srcs, [grads[n] for n in names], accumulate=True), *srcs)
+    return out0
+
+
 EARLY_HOOK = None      # callable(P, grads, side) invoked instead of parallel.early_reduce at the early-bucket point of backward()
 
 
@@ -775,7 +846,10 @@ def backward(P, sv, g_outs):
     """g_outs: gradients wrt (out, shuffle_p, shuffle_l), each [B,1,L] or None.  Returns {param name: grad}."""
     grads = {}
     side = _side(sv["z1"].device, sv["z1"].numel())
-    gz1, gz2r, gz2b, gz1_sum = _head_bwd(P, sv, g_outs, grads, side, relu_z1=True)
+    if "views" in sv:
+        gz1, gz2r, gz2b, gz1_sum = _views_bwd(P, sv, g_outs, grads, side)
+    else:
+        gz1, gz2r, gz2b, gz1_sum = _head_bwd(P, sv, g_outs, grads, side, relu_z1=True)
     _latents_bwd(P, sv, gz1, gz2r, grads, side, z1_pre_gated=True, early=True, gz2b=gz2b, gz1_sum=gz1_sum)
     side.join()
     return grads

@@ -31,6 +31,11 @@ The per-update learning-rate schedule (the optimiser's lr_schedule): `_device_up
 single-wave nef_lr_sched launch behind the update -- inside the graph where the update is (single process), behind the all-reduces where
 it is issued eagerly (data parallel, accumulation).  The rate changes from replay to replay with no host write between them; the
 schedule's numbers are among the frozen scalars.  The stepper with private buffers (optimizer=None) has no schedule.
+
+Several target views per step (cfg.SOLVER.train_views; the call signature does not change, the shapes decide): a `q_theta` of
+[Q, B, 2] with a target of [Q, B, 1, L] selects engine.forward's multi-view form -- one graph per (shape, Q), its slot holding static
+[Q, B, 2] angles, [Q, B, 1, L] targets and, for the cropped SSIM term, the rois tiled once per view, all staged outside the graph with
+the other inputs.  The sums over views are ops.copy_many launches inside the graph; both capture forms are otherwise as above.
 """
 import random
 
@@ -52,6 +57,7 @@ class GraphedTrainStep:
         # and added inside the loss kernels; off: no buffer, no copy
         self.use_noise = bool(cfg.DATA.noise)
         self.noise = None
+        self.rois_q = None       # multi-view steps with the cropped SSIM term: the slot's rois tiled Q times
         # cfg.SOLVER.ssim_factor: the SSIM term's launches behind the loss launches, on the static rois and noise; the loss row has 5
         # elements then.  0: no launch, the 4-element row
         from .network.loss.losses import ssim_settings
@@ -145,7 +151,8 @@ class GraphedTrainStep:
             ops.loss_fwd(o, p_, l_, self.target, self.factors, self.reg_l2, self.use_mask, out=self.losses, noise=self.noise)
             g3 = ops.loss_bwd(o, p_, l_, self.target, None, self.factors, self.reg_l2, self.use_mask, noise=self.noise)
             if self.ssim_factor > 0:
-                rois = self.rois if self.ssim_crop else None
+                # (multi-view: the rows are the Q * B (view, sample) pairs, the rois tiled once per view)
+                rois = (self.rois if self.rois_q is None else self.rois_q) if self.ssim_crop else None
                 ops.loss_ssim_fwd(o, self.target, self.losses, self.ssim_factor, rois=rois, noise=self.noise)
                 ops.loss_ssim_bwd(o, self.target, g3[0], self.ssim_factor, rois=rois, noise=self.noise)
             return engine.backward(P, sv, g3)
@@ -251,6 +258,7 @@ class GraphedTrainStep:
         self.data, self.in_theta, self.q_theta, self.rois, self.target = (slot[k] for k in
                                                                           ("data", "in_theta", "q_theta", "rois", "target"))
         self.noise = slot.get("noise")
+        self.rois_q = slot.get("rois_q")
 
     def _build(self, data, in_theta, q_theta, rois, target, noise=None):
         dev = data.device
@@ -260,6 +268,18 @@ class GraphedTrainStep:
                     q_theta=torch.empty(q_theta.shape, device=dev, dtype=torch.float32),
                     rois=torch.empty(rois.shape, device=dev, dtype=torch.int64),
                     target=torch.empty(data.shape[0], 1, data.shape[2], device=dev, dtype=torch.float32))
+        if q_theta.dim() == 3:
+            # SOLVER.train_views: q_theta [Q, B, 2] selects the multi-view step (engine.forward) -- the targets are [Q, B, 1, L], and the
+            # SSIM term's rows are the Q * B (view, sample) pairs, cropped by the rois tiled once per view
+            Q = q_theta.shape[0]
+            if self.use_noise:
+                raise ValueError("DATA.noise with SOLVER.train_views >= 2: the batch carries noise for the target lead only")
+            slot["target"] = torch.empty(Q, data.shape[0], 1, data.shape[2], device=dev, dtype=torch.float32)
+            if self.ssim_factor > 0:
+                from .network.loss.losses import check_view_rows
+                check_view_rows(Q, data.shape[0])
+            if self.ssim_crop:
+                slot["rois_q"] = torch.empty(Q * rois.shape[0], rois.shape[1], rois.shape[2], device=dev, dtype=torch.int64)
         if self.use_noise:
             slot["noise"] = torch.empty(data.shape[0], 1, data.shape[2], device=dev, dtype=torch.float32)
         self._use(slot)
@@ -328,6 +348,8 @@ class GraphedTrainStep:
         self.in_theta.copy_(in_theta, non_blocking=True)
         self.q_theta.copy_(q_theta, non_blocking=True)
         self.rois.copy_(rois, non_blocking=True)
+        if self.rois_q is not None:
+            self.rois_q.view((-1,) + tuple(self.rois.shape)).copy_(self.rois.unsqueeze(0).expand(self.rois_q.shape[0] // self.rois.shape[0], -1, -1, -1))
         self.target.copy_(target.reshape(self.target.shape), non_blocking=True)
         if self.noise is not None:
             self.noise.copy_(noise.reshape(self.noise.shape), non_blocking=True)
@@ -460,7 +482,7 @@ class GraphedTrainStep:
             self._scope = self.model._nef_scope                            # start over (ops.amax_scope), and the captures hold the old slots
             self.slots.clear()
         self._draw()
-        shape = (tuple(data.shape), tuple(in_theta.shape))
+        shape = (tuple(data.shape), tuple(in_theta.shape)) + ((q_theta.shape[0],) if q_theta.dim() == 3 else ())      # one graph per (shape, Q)
         slot = self.slots.get(shape)
         if slot is None:
             slot = self.slots[shape] = self._build(data, in_theta, q_theta, rois, target, noise)

@@ -44,6 +44,16 @@ def ssim_settings(cfg, rois=None, need_rois=True):
     return factor, rois
 
 
+SSIM_MAX_ROWS = 65535      # nef_loss_ssim_fwd / _bwd: the rows are a grid's y extent
+
+
+def check_view_rows(Q, B):
+    """The SSIM term of a multi-view step takes its Q * B (view, sample) pairs as rows."""
+    if Q * B > SSIM_MAX_ROWS:
+        raise ValueError(f"SOLVER.train_views ({Q}) x the batch ({B}) = {Q * B} rows is more than the {SSIM_MAX_ROWS} the SSIM term "
+                         "(SOLVER.ssim_factor) takes: lower SOLVER.train_views or the batch size, or set SOLVER.ssim_factor 0")
+
+
 def losswrapper(predict, predict_shuffle_p, predict_shuffle_l, target, cfg, rest_out=None, rest_view=None,
                 loss1_gt=None, loss2_gt=None, noise=None, rois=None):
     """Returns (loss, f0*loss1, f1*loss2, f2*loss3[, loss_unsperv][, loss_ssim]) as 0-dim tensors; `loss` supports .backward().
@@ -54,8 +64,15 @@ def losswrapper(predict, predict_shuffle_p, predict_shuffle_l, target, cfg, rest
     `rois` (behind `noise`; no counterpart in the reference): the batch's int64 [B, 7, 2] rois.  With cfg.SOLVER.ssim_factor > 0 the tuple
     gains the SSIM term ssim_factor * (1 - mean SSIM(predict (+ noise), target)) as its LAST element and `loss` includes it; with
     cfg.SOLVER.ssim_crop the rows end at rois[i, -1, 0] as the test phase's ssim_gen does (rois is required then).  Factor 0: `rois` is
-    not looked at and the tuple, the launches and the bits are what they were."""
+    not looked at and the tuple, the launches and the bits are what they were.
+    Multi-view steps (SOLVER.train_views; Model_nefnet.forward with query_theta [Q, B, 2]): predictions and target are [Q, B, 1, L] and
+    every term is the mean over all Q * B * L elements -- the mean over views, which have equal size.  The SSIM term's rows are the
+    Q * B (view, sample) pairs; `rois` [B, 7, 2] is tiled once per view here ([Q * B, 7, 2] is taken as it is)."""
     ssim_factor, ssim_rois = ssim_settings(cfg, rois)
+    if ssim_factor > 0 and predict.dim() == 4:
+        check_view_rows(predict.shape[0], predict.shape[1])
+        if ssim_rois is not None and ssim_rois.shape[0] == predict.shape[1]:
+            ssim_rois = ssim_rois.repeat(predict.shape[0], 1, 1)
     if cfg.SOLVER.reg_loss == 'l2_loss':
         reg_l2 = True
     elif cfg.SOLVER.reg_loss == 'l1_loss':

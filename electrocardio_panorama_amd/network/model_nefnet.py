@@ -6,6 +6,9 @@ signatures, phases and return tuples, same `state_dict()` keys (so reference che
 ways).  The torch.nn layers below are parameter containers only -- they give the reference's names,
 shapes and default initialisation; their own forward() is never called.  All compute goes through
 `engine` -> `ops` -> libnefnet_hip.so, and raises if that library is missing.
+
+Beyond the reference: `forward(..., query_theta [Q, B, 2], phase='train')` (view-major angles) supervises Q views on one encoder pass
+and returns three [Q, B, 1, L] tensors (SOLVER.train_views; engine._views_fwd); a 2-D `query_theta` is the reference's call.
 """
 import math
 import random
@@ -194,6 +197,10 @@ class Model_nefnet(nn.Module):
     # ------------------------------------------------------------------ reference API
     def forward(self, x, input_thetas, query_theta, rois, rest_theta=None, phase='train'):
         self._check_inputs(x, rois)
+        if query_theta.dim() == 3 and (phase != 'train' or self._ENGINE[0] is not engine.forward):
+            # [Q, B, 2], view-major: the multi-view train step (SOLVER.train_views), three [Q, B, 1, L] outputs from one encoder pass
+            raise ValueError("a 3-D query_theta [Q, B, 2] is Model_nefnet's multi-view train step: phase {!r} of {} takes [B, 2]".format(
+                phase, type(self).__name__))
         if self._status is None or self._status.device != x.device:
             self._status = torch.zeros(1, dtype=torch.int32, device=x.device)
         V = self.lead_num

@@ -592,6 +592,22 @@ def wino_ok(K, Cin_g, Cout_g, T_out, pro=0):
 _PREPACKED = {}     # (weight data_ptr, G, flip, wino, src) -> operand packed by pack_many(), consumed by the next pack_weight()
 
 
+_PACK_KEEP = False
+
+
+@contextlib.contextmanager
+def pack_keep(on=True):
+    """Inside (with `on`): pack_weight() hands a pre-packed operand out WITHOUT taking it from the table, so the next pass through the
+    same weights finds it again -- the multi-view train step runs its head once per view on one step-level pack_many.  The operand is
+    a function of the weight alone, so who packed it never shows in a result."""
+    global _PACK_KEEP
+    prev, _PACK_KEEP = _PACK_KEEP, bool(on)
+    try:
+        yield
+    finally:
+        _PACK_KEEP = prev
+
+
 def _logical_shape(w, src):
     """Shape of the weight tensor that is packed: w's own, or -- src = ("poly", Cr) -- the PHASE weights of conv1d(upsample2(x), w)
     (twice the rows, formed inside the pack kernel: nef_pack_desc.src_mode 1)."""
@@ -686,7 +702,8 @@ def pack_weight(w, G, flip=False, T=None, f4=False, site=None, shared=False, pla
     `src` = ("poly", Cr): pack the phase weights of conv1d(upsample2(x), w) instead of w itself (split-fp16 operands only)."""
     _chk(w)
     Cog, Cig, K, wino = _pack_shape(w, G, flip, T, f4, plain, src)
-    hit = _PREPACKED.pop((w.data_ptr(), G, bool(flip), wino, src), None)
+    key = (w.data_ptr(), G, bool(flip), wino, src)
+    hit = _PREPACKED.get(key) if _PACK_KEEP else _PREPACKED.pop(key, None)
     if hit is not None and hit[1] is w and hit[2] == w._version:
         return hit[0]
     wp, = _pack([(w, G, Cog, Cig, K, bool(flip), wino, src, site)], "pack_weight")
@@ -1779,6 +1796,27 @@ def flatten_into(tensors, out, accumulate=False, accumulate_dev=None):
                "nef_flatten_acc")
     _done(ev)
     return out
+
+
+def copy_many(srcs, dsts, accumulate=False):
+    """dsts[k][:] = srcs[k] -- or, `accumulate`, dsts[k][:] += srcs[k] -- for every pair of contiguous fp32 device tensors of equal
+    element counts, ONE launch per 64 pairs (nef_copy_many; the multi-view train step's glue: no torch kernel in the replayed step).
+    The tensors may be slices (4-byte aligned); no destination may overlap another destination or a source.  One writer per element,
+    no atomics: the same bits eagerly and under replay."""
+    n = len(srcs)
+    if len(dsts) != n:
+        raise ValueError(f"copy_many: {n} sources for {len(dsts)} destinations")
+    if n == 0:
+        return
+    for s, d in zip(srcs, dsts):
+        if _chk(s).numel() != _chk(d).numel():
+            raise ValueError(f"copy_many: source {tuple(s.shape)} and destination {tuple(d.shape)} differ in size")
+    sp = (C.c_void_p * n)(*[s.data_ptr() for s in srcs])
+    dp = (C.c_void_p * n)(*[d.data_ptr() for d in dsts])
+    sizes = (C.c_int64 * n)(*[s.numel() for s in srcs])
+    ev = _hbm("copy_many", *srcs, *dsts, *(dsts if accumulate else ()))
+    _lib.check(_lib.load().nef_copy_many(sp, dp, sizes, n, int(bool(accumulate)), _stream()), "nef_copy_many")
+    _done(ev)
 
 
 def stacked3(parts):

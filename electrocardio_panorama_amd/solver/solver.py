@@ -12,7 +12,11 @@ device by `nef_view_metrics`, one launch per batch.
 
 Data parallelism replaces `nn.DataParallel` (solver.py:32-34) with one process per GPU (`parallel.py`): the loaders
 hand every rank its shard, FusedSGD all-reduces the flat gradient, rank 0 owns the BatchNorm running statistics,
-the scalar log and the checkpoints."""
+the scalar log and the checkpoints.
+
+`SOLVER.train_views = Q >= 2` (no counterpart in the reference): a train step supervises Q of the batch's supervised rest views on one
+encoder pass -- the targets are drawn per step by `views.draw_views(seed, epoch, batch index, Q, S)` and handed to the model as
+`query_theta` [Q, B, 2] with `[Q, B, 1, L]` targets, eagerly or through the graphed step; `target_view` / `target_theta` are not used."""
 import contextlib
 import json
 import os
@@ -22,7 +26,7 @@ import torch
 from .. import _env
 import torch.distributed as dist
 
-from .. import engine, ops, parallel
+from .. import engine, ops, parallel, views
 from ..network import build_model, build_loss
 from ..utils import CheckPointer
 from .optim_scheduler import get_optimizer, get_lr_scheduler
@@ -112,6 +116,9 @@ class Solver:
         self.output_dir = os.path.join(cfg.output_dir, cfg.desc)
         self.desc = cfg.desc
         self.collect_views = collect_views       # False: skip the per-view host lists (benchmarks)
+        # SOLVER.train_views = Q >= 2: a train step supervises Q of the batch's supervised rest views on one encoder pass (views.py);
+        # 1: the reference's step on target_view / target_theta.  Invalid values and DATA.noise with Q >= 2 are rejected here
+        self.train_views = views.train_views(cfg)
         self.model = build_model(cfg).float()
         self.loss = build_loss(cfg)
         self._init_model_device()
@@ -351,9 +358,22 @@ class Solver:
             self._lr_seen = (optim, optim.lr_state()[0])
         lr_first = float(np.float32(float(optim.param_groups[0]['lr']) * optim.lr_schedule.factor(self._lr_seen[1]))) if lr_on else None
         n_batches = n_updates = 0
+        n_views = self.train_views if phase == 'train' else 1
+        if n_views >= 2 and type(self.model).__name__ != 'Model_nefnet':
+            raise ValueError("SOLVER.train_views >= 2 is Model_nefnet's multi-view train step; {} takes one view".format(type(self.model).__name__))
         for meta in dl:
             source_data, rois, input_theta, target_view, target_theta, noise = self._to_device(meta)
             rest_theta = torch.as_tensor(meta['rest_theta']).to(self.device) if 'rest_theta' in meta else None
+            if n_views >= 2:
+                # this step's targets: Q of the S supervised rest views -- one draw from (seed, epoch, batch index), the same on every
+                # rank and in a resumed run; target_view / target_theta are not used.  [Q, B, 1, L] and [Q, B, 2], view-major
+                if rest_theta is None or 'rest_view' not in meta:
+                    raise KeyError("SOLVER.train_views >= 2 needs the batch's rest_view / rest_theta (train_net.build_loaders ships them)")
+                rest_view = torch.as_tensor(meta['rest_view']).to(self.device, non_blocking=True)
+                n_sup = views.supervised_views(self.cfg, rest_theta.shape[1])
+                views.check_views(n_views, min(n_sup, rest_view.shape[1]))
+                picked = views.draw_views(self.cfg.get('seed', 0), int(getattr(self.model, 'dropout_epoch', 0)), n_batches, n_views, n_sup)
+                target_view, target_theta = views.select_views(rest_view, rest_theta, picked)
             stepper = self._graphed_step(optim, source_data, keep) if phase == 'train' else None
             if stepper is not None:
                 # forward + losswrapper + backward + SGD as ONE replayed hipGraph (one graph per batch shape: the final partial
@@ -364,8 +384,8 @@ class Solver:
             elif phase == 'train':
                 out, shuf_p, shuf_l = self.model(source_data, input_theta, target_theta, rois, rest_theta=rest_theta,
                                                  phase='train')
-                if keep:
-                    pred_s.add(out.squeeze(1))                     # solver.py:179 (before the optional noise)
+                if keep:       # solver.py:179 (before the optional noise); multi-view: one [Q, B, L] entry per batch
+                    pred_s.add(out.squeeze(1) if n_views < 2 else out.squeeze(2).unsqueeze(0))
                 # DATA.noise (solver.py:185-186): the loss kernels add the row to the prediction, no launch of its own
                 losses = self.loss(out, shuf_p, shuf_l, target_view, self.cfg, noise=noise if self.cfg.DATA.noise else None,
                                    **self._loss_rois(rois))
@@ -392,7 +412,7 @@ class Solver:
             if updated and clip_s is not None and optim.clip_stats is not None:
                 clip_s.add(optim.clip_stats[:2])
             if keep:
-                gt_s.add(target_view.squeeze(1))
+                gt_s.add(target_view.squeeze(1) if n_views < 2 else target_view.squeeze(2).unsqueeze(0))
                 in_s.add(source_data)
                 rois_s.add(rois)
         if accum and optim.window_open:

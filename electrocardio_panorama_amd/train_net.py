@@ -15,14 +15,15 @@ import os
 import numpy as np
 import torch
 
-from . import parallel, synth
+from . import parallel, synth, views
 from .prefetch import DevicePrefetcher
 from .solver import Solver
 from .utils import seed_torch
 
 
 class SyntheticLoader:
-    """Iterable of `meta` dicts (reference codes/dataset/tianchi.py:212-224 schema), `n_batches` per epoch."""
+    """Iterable of `meta` dicts (reference codes/dataset/tianchi.py:212-224 schema), `n_batches` per epoch.  Every batch carries its
+    `Q` rest views as float32 `rest_view` / `rest_theta`, all of them supervised: what a SOLVER.train_views step draws its targets from."""
 
     def __init__(self, cfg, batch_size=32, n_batches=8, length=512, seed=0, Q=None):
         self.V, self.B, self.n, self.L, self.seed = cfg.DATA.lead_num, batch_size, n_batches, length, seed
@@ -55,6 +56,13 @@ def build_loaders(cfg, batch_size=32, phases=('train', 'test')):
     from torch.utils.data import DataLoader
     from torch.utils.data.distributed import DistributedSampler
     from .dataset import build_dataset
+    # SOLVER.train_views >= 2: the train batches also carry the S supervised rest views (nothing more is shipped with the key off)
+    collate_train = _collate_train
+    if views.train_views(cfg) >= 2:
+        import functools
+        n_sup = views.planned_views(cfg)[1]
+        views.check_views(views.train_views(cfg), n_sup)
+        collate_train = functools.partial(_collate_train, rest_views=n_sup)
     for ph in phases:
         ds = build_dataset(cfg, phase=ph)
         if ph == 'train':
@@ -73,10 +81,10 @@ def build_loaders(cfg, batch_size=32, phases=('train', 'test')):
             elif world > 1:
                 sampler = DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=True, seed=cfg.seed, drop_last=True)
                 dl = DataLoader(ds, batch_size=batch_size // world, sampler=sampler, num_workers=16, drop_last=True,
-                                collate_fn=_collate_train, pin_memory=True, persistent_workers=True, prefetch_factor=4)
+                                collate_fn=collate_train, pin_memory=True, persistent_workers=True, prefetch_factor=4)
             else:
                 dl = DataLoader(ds, batch_size=batch_size, shuffle=True, num_workers=16, drop_last=True,
-                                collate_fn=_collate_train, pin_memory=True, persistent_workers=True, prefetch_factor=4)
+                                collate_fn=collate_train, pin_memory=True, persistent_workers=True, prefetch_factor=4)
         else:
             dl = DataLoader(ds, batch_size=batch_size, num_workers=8, drop_last=True, collate_fn=_collate, pin_memory=True)
         out.append(dl)
@@ -89,8 +97,13 @@ def build_loaders(cfg, batch_size=32, phases=('train', 'test')):
 _TRAIN_FIELDS = ('data', 'rois', 'input_theta', 'target_view', 'target_theta', 'noise', 'rest_theta')
 
 
-def _collate_train(items):
-    return _collate([{k: it[k] for k in _TRAIN_FIELDS if k in it} for it in items])
+def _collate_train(items, rest_views=0):
+    """`rest_views` = S > 0 (SOLVER.train_views >= 2: the step draws its targets from the rest views) also ships `rest_view`, cut to the
+    S supervised leads -- they come first -- and cast to float32 here, in the worker: a fraction of the 12-lead float64 field."""
+    out = _collate([{k: it[k] for k in _TRAIN_FIELDS if k in it} for it in items])
+    if rest_views > 0:
+        out['rest_view'] = torch.from_numpy(np.stack([np.asarray(it['rest_view'][:rest_views], dtype=np.float32) for it in items]))
+    return out
 
 
 def _collate(items):

@@ -815,6 +815,19 @@ int nef_flatten(const float* const* srcs, const int64_t* sizes, int n, float* ou
  * `accumulate` outside {0, 1} is NEF_E_SHAPE; n == 0 is NEF_OK and launches nothing. */
 int nef_flatten_acc(const float* const* srcs, const int64_t* sizes, int n, float* out, int accumulate, const int32_t* accumulate_dev,
                     nef_stream_t stream);
+/* n independent segment copies or sums in one launch per 64 segments (csrc/views.hip; the glue of the multi-view train step,
+ * SOLVER.train_views, which the reference has no counterpart of: its forward takes one query angle per step):
+ *   dsts[k][i]  = srcs[k][i]   for i < sizes[k], when `accumulate` is 0 -- dsts[k] is never read;
+ *   dsts[k][i] += srcs[k][i]   when `accumulate` is 1 (one fp32 add per element).
+ * One writer per element, no atomics; the grid is a function of n and the sizes alone, so the bits are the same eagerly, under graph
+ * replay and on every rank.  `srcs` / `dsts` / `sizes` are HOST arrays of DEVICE pointers / float counts.  The pointers need only
+ * 4-byte alignment (they are slices): a segment whose source and destination share their offset inside a 16-byte line moves its body
+ * in 16-byte accesses between a scalar head and tail, any other segment is scalar.  OVERLAPPING SEGMENTS ARE NOT SUPPORTED: no
+ * destination may overlap another destination or any source of the call (a source may appear in several segments).  A segment of 0
+ * elements may have NULL pointers.  Every argument is checked before the first launch: NULL srcs / dsts / sizes with n > 0 (or a NULL
+ * source or destination of sizes[k] > 0) is NEF_E_NULL; n < 0, a negative size or `accumulate` outside {0, 1} is NEF_E_SHAPE; n == 0 is
+ * NEF_OK and launches nothing. */
+int nef_copy_many(const float* const* srcs, float* const* dsts, const int64_t* sizes, int n, int accumulate, nef_stream_t stream);
 /* w [Co][2 Cih][K] -> grouped [2 Co][Cih][K] (group = input-channel half: the first decoder conv runs once per distinct half,
  * DESIGN.md section 2; weight of codes/network/model_nefnet.py:18), inverse != 0: the other way (its gradient). */
 int nef_regroup_halves(const float* src, float* dst, int Co, int Cih, int K, int inverse, nef_stream_t stream);

@@ -8,6 +8,7 @@
     python tools/bench_adam.py --accum K [--parent-tree DIR] [--out profiles/r12_accum_bench_line.json]
     python tools/bench_adam.py --sched const|cosine|poly --warmup W [--parent-tree DIR] [--out profiles/r14_sched_bench_line.json]
     python tools/bench_adam.py --ssim F [--parent-tree DIR] [--out profiles/r15_ssim_bench_line.json]
+    python tools/bench_adam.py --views Q [Q ...] [--parent-tree DIR] [--out profiles/r16_views_bench_line.json]
 
 Each measurement runs in a child process of its own under `timeout` (nothing more is started once one fails), `--reps` rounds of
 the three children; every figure is reported as [min, median, max] over the rounds:
@@ -59,7 +60,14 @@ and warm (back-to-back launches).  Writes profiles/r14_sched_bench_line.json unl
 --ssim F measures the SSIM term of the training loss (SOLVER.ssim_factor = F, ssim_crop true), at the same two shapes: per round and
 shape the graphed FusedSGD step with the key off (sgd-graph: the parent's code path) and on (sgd-graph-ssim), and -- with --parent-tree
 DIR -- DIR's own sgd-graph step.  The config-2 child with the term on also times the term's launches alone, cold: nef_loss_ssim_fwd
-(two launches) and nef_loss_ssim_bwd.  Writes profiles/r15_ssim_bench_line.json unless --out says otherwise."""
+(two launches) and nef_loss_ssim_bwd.  Writes profiles/r15_ssim_bench_line.json unless --out says otherwise.
+
+--views Q [Q ...] measures several target views per train step (SOLVER.train_views), at the same two shapes: per round and shape the graphed
+FusedSGD step with the key off (sgd-graph: the parent's code path) and one child per Q (sgd-graph-views: query_theta [Q, B, 2], targets
+[Q, B, 1, L]; ms per step, and per supervised view = step / Q, beside the FLOP model 1 + 0.31 (Q - 1) steps), and -- with --parent-tree DIR
+-- DIR's own sgd-graph step.  Every child reports torch.cuda.max_memory_allocated; the config-2 views children also time the step's four
+nef_copy_many launches alone, cold: the outputs into the loss's layout, the loss gradient back out, one view's latent gradients and one view's
+head parameter gradients summed into the first view's.  Writes profiles/r16_views_bench_line.json unless --out says otherwise."""
 import argparse
 import json
 import os
@@ -99,7 +107,7 @@ def cold_ms(launches, dev, reps=30):
     return [float(np.median([a.elapsed_time(b) for a, b in ev])) for ev in evs]
 
 
-def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=(), ema=0.0, accum=1, sched=None, ssim=0.0):
+def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=(), ema=0.0, accum=1, sched=None, ssim=0.0, views=1):
     import numpy as np
     import torch
     from electrocardio_panorama_amd import ops, synth
@@ -118,7 +126,7 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
     seed_torch(cfg.seed)
     model = build_model(cfg).float().to(dev).train()
     lossf = build_loss(cfg)
-    if mode in ("sgd-graph", "sgd-graph-ssim"):
+    if mode in ("sgd-graph", "sgd-graph-ssim", "sgd-graph-views"):
         optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9)
     elif mode == "sgd-graph-clip":
         optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9, max_grad_norm=clip)
@@ -146,6 +154,13 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
     data, rois, in_theta, tgt_view, tgt_theta = (torch.from_numpy(np.ascontiguousarray(meta[k])).to(dev) for k in
                                                  ("data", "rois", "input_theta", "target_view", "target_theta"))
     tgt_view = tgt_view.unsqueeze(1)
+    if mode == "sgd-graph-views":
+        # SOLVER.train_views = Q: the step's targets are Q rest views of the batch -- [Q, B, 1, L] and [Q, B, 2], view-major
+        from electrocardio_panorama_amd.views import select_views
+        meta = synth.make_batch(B, V, L, seed=123, Q=views)
+        data, rois, in_theta, rest_view, rest_theta = (torch.from_numpy(np.ascontiguousarray(meta[k])).to(dev) for k in
+                                                       ("data", "rois", "input_theta", "rest_view", "rest_theta"))
+        tgt_view, tgt_theta = select_views(rest_view, rest_theta, list(range(views)))
     graphed = None
     if "-graph" in mode:
         from electrocardio_panorama_amd.graph import GraphedTrainStep
@@ -168,7 +183,29 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
     for _ in range(steps):
         step()
     torch.cuda.synchronize(dev)
-    res = {"mode": mode, "ms_per_step": round((time.perf_counter() - t0) * 1e3 / steps, 3), "steps": steps, "warmup": warmup, "B": B, "L": L}
+    res = {"mode": mode, "ms_per_step": round((time.perf_counter() - t0) * 1e3 / steps, 3), "steps": steps, "warmup": warmup, "B": B, "L": L,
+           "max_memory_allocated_GiB": round(torch.cuda.max_memory_allocated(dev) / 2.0 ** 30, 3)}
+    if mode == "sgd-graph-views":
+        res.update(train_views=views, ms_per_view=round(res["ms_per_step"] / views, 3),
+                   loss_row=[round(float(v), 6) for v in graphed.losses.tolist()])
+    if mode == "sgd-graph-views" and (B, L) == EMA_SHAPES["config2"]:
+        # the step's nef_copy_many launches alone, cold, on tensors of the step's own sizes
+        Q, T = views, L // 4
+        out3 = [torch.randn(3 * B, 1, L, device=dev) for _ in range(Q)]
+        buf = torch.empty(3, Q, B, 1, L, device=dev)
+        scat = ([o[j * B:(j + 1) * B] for o in out3 for j in range(3)], [buf[j, k] for k in range(Q) for j in range(3)])
+        lat = [torch.randn(B, 128 * V, T, device=dev), torch.randn(B, 128 * V, 7, 32, device=dev), torch.randn(128 * V, device=dev)]
+        lat0 = [torch.zeros_like(t) for t in lat]
+        head = [p_ for n_, p_ in model.named_parameters() if n_.startswith(("decoder.", "mlp2."))]
+        hg, hg0 = [torch.randn_like(p_) for p_ in head], [torch.zeros_like(p_) for p_ in head]
+        ms = cold_ms([lambda: ops.copy_many(scat[0], scat[1]), lambda: ops.copy_many(scat[1], scat[0]),
+                      lambda: ops.copy_many(lat, lat0, accumulate=True), lambda: ops.copy_many(hg, hg0, accumulate=True)], dev)
+        nb = [2 * 4 * buf.numel(), 2 * 4 * buf.numel(), 3 * 4 * sum(t.numel() for t in lat), 3 * 4 * sum(t.numel() for t in hg)]
+        res.update(copy_many_cold_ms=dict(zip(("outputs_to_loss_layout", "loss_gradient_to_views", "latent_gradient_sum", "head_parameter_gradient_sum"),
+                                              [round(m_, 4) for m_ in ms])),
+                   copy_many_cold_GBps=dict(zip(("outputs_to_loss_layout", "loss_gradient_to_views", "latent_gradient_sum", "head_parameter_gradient_sum"),
+                                                [round(b_ / (m_ * 1e-3) / 1e9, 1) for b_, m_ in zip(nb, ms)])),
+                   copy_many_head_tensors=len(hg))
     if mode == "sgd-graph-accum":
         graphed.flush()      # (a window the timed micro-batches left open)
         res.update(accum_steps=accum, ms_per_step_note="per micro-batch; an update behind every accum_steps-th")
@@ -526,6 +563,75 @@ def ssim_rounds(args):
         f.write(line + "\n")
 
 
+def views_rounds(args):
+    """--views Q [Q ...]: `--reps` alternating rounds of fresh children per shape (see the module docstring); prints and writes one JSON
+    line."""
+    qs = list(args.views)
+    modes = dict({"sgd-graph": 900}, **{f"views{q}": 900 for q in qs}, **({"parent": 900} if args.parent_tree else {}))
+    shapes = {k: v for k, v in EMA_SHAPES.items() if args.only_shape in (None, k)}
+    results = {(shape, mode): [] for shape in shapes for mode in modes}
+    for rnd in range(args.reps):
+        order = list(modes) if rnd % 2 == 0 else list(reversed(modes))
+        for shape, (B, L) in shapes.items():
+            for mode in order:
+                if mode == "parent":
+                    # the parent's tool may lack --shape: its `child` function is called directly, in a fresh process of its own tree
+                    tree = os.path.abspath(args.parent_tree)
+                    code = ("import importlib.util as u; s = u.spec_from_file_location('parent_bench', %r); m = u.module_from_spec(s); "
+                            "s.loader.exec_module(m); m.child('sgd-graph', %d, %d, B=%d, L=%d)"
+                            % (os.path.join(tree, "tools", "bench_adam.py"), args.steps, args.warmup, B, L))
+                    cmd = ["timeout", "-k", "10", str(modes[mode]), sys.executable, "-c", code]
+                else:
+                    tree = ROOT
+                    cmd = ["timeout", "-k", "10", str(modes[mode]), sys.executable, os.path.join(ROOT, "tools", "bench_adam.py"), "--child",
+                           "sgd-graph" if mode == "sgd-graph" else "sgd-graph-views", "--steps", str(args.steps), "--warmup", str(args.warmup),
+                           "--shape", str(B), str(L)]
+                    if mode != "sgd-graph":
+                        cmd += ["--views", mode[len("views"):]]
+                results[(shape, mode)].append(run_child(cmd, tree, mode))
+                sys.stderr.write(f"round {rnd + 1}/{args.reps} {shape} {mode}: {results[(shape, mode)][-1]['ms_per_step']} ms/step\n")
+                sys.stderr.flush()
+
+    def spread(shape, mode, key):
+        v = sorted(x[key] for x in results[(shape, mode)])
+        return [v[0], v[len(v) // 2], v[-1]]
+
+    out = {"metric": "ms per train step, graphed FusedSGD, one target view per step (key off) and SOLVER.train_views = Q ([min, median, max] over "
+                     "rounds of fresh processes)",
+           "rounds": args.reps, "train_views": qs, "flop_model": "a Q-view step costs 1 + 0.31 (Q - 1) single-view steps (SURVEY.md 8(d))",
+           "shapes": {k: "B=%d, 3 leads, L=%d, one GPU, dropout on" % v for k, v in shapes.items()}}
+    for shape in shapes:
+        out[shape + "_views_off_ms"] = off = spread(shape, "sgd-graph", "ms_per_step")
+        out[shape + "_views_off_max_memory_GiB"] = spread(shape, "sgd-graph", "max_memory_allocated_GiB")[1]
+        base = off
+        if args.parent_tree:
+            out[shape + "_parent_ms"] = par = spread(shape, "parent", "ms_per_step")
+            out[shape + "_views_off_median_inside_parent_spread"] = par[0] <= off[1] <= par[2]
+            out[shape + "_views_off_median_minus_parent_max_ms"] = round(off[1] - par[2], 3)
+            base = par
+        for q in qs:
+            out[f"{shape}_views{q}_ms"] = st = spread(shape, f"views{q}", "ms_per_step")
+            out[f"{shape}_views{q}_ms_per_view"] = spread(shape, f"views{q}", "ms_per_view")
+            out[f"{shape}_views{q}_steps_measured_vs_model"] = [round(st[1] / base[1], 3), round(1 + 0.31 * (q - 1), 2)]
+            out[f"{shape}_views{q}_max_memory_GiB"] = spread(shape, f"views{q}", "max_memory_allocated_GiB")[1]
+        # the one speed condition: ms per supervised view at the largest Q below the single-view step of the same session
+        q = max(qs)
+        out[f"{shape}_ms_per_view_at_{q}_below_single_view_step"] = out[f"{shape}_views{q}_ms_per_view"][1] < base[1]
+    if "config2" in shapes:
+        q = max(qs)
+        out.update(copy_many_cold_ms={f"views{q_}": results[("config2", f"views{q_}")][0]["copy_many_cold_ms"] for q_ in qs},
+                   copy_many_cold_GBps={f"views{q_}": results[("config2", f"views{q_}")][0]["copy_many_cold_GBps"] for q_ in qs},
+                   copy_many_note="the step's four nef_copy_many launches alone at config 2 (first round's child): 3Q output segments into the "
+                                  "[3, Q, B, 1, L] layout, the same back, one view's (gz1, gz2b, chan_sum) and one view's %d head parameter "
+                                  "gradients summed into the first view's (the last two run Q - 1 times per step); cold = a 512 MiB buffer "
+                                  "written before each call" % results[("config2", f"views{q}")][0]["copy_many_head_tensors"])
+    out.update(steps=args.steps, warmup=args.warmup)
+    line = json.dumps(out)
+    print(line)
+    with open(args.out or os.path.join(ROOT, "profiles", "r16_views_bench_line.json"), "w") as f:
+        f.write(line + "\n")
+
+
 def trust_rounds(args):
     """--trust lars|lamb: `--reps` alternating rounds of fresh children per shape (see the module docstring); prints and writes one JSON
     line."""
@@ -596,11 +702,14 @@ def main():
                     help="measure the per-update learning-rate schedule of this shape; --warmup is then the schedule's W (see above)")
     ap.add_argument("--sched-warmup", type=int, default=None, metavar="W", help="with --child sgd-graph-sched: the schedule's W")
     ap.add_argument("--ssim", type=float, default=None, metavar="F", help="measure the SSIM term of the loss, ssim_factor = F (see above)")
+    ap.add_argument("--views", type=int, nargs="+", default=None, metavar="Q",
+                    help="measure SOLVER.train_views = Q for every Q given (see above); with --child sgd-graph-views: the one Q")
+    ap.add_argument("--only-shape", choices=sorted(EMA_SHAPES), default=None, help="with --views: measure this shape only")
     ap.add_argument("--shape", type=int, nargs=2, default=(256, 5000), metavar=("B", "L"), help="with --child: batch size and length")
     ap.add_argument("--parent-tree", default=None,
                     help="with --clip / --weight-decay / --ema: a built checkout whose own sgd-graph child runs in every round")
     ap.add_argument("--child", choices=sorted({**MODES, **CLIP_MODES, **WD_MODES, **EMA_MODES, "lars-graph": 900, "lamb-graph": 900, "sgd-graph-accum": 900,
-                                             "sgd-graph-sched": 900, "sgd-graph-ssim": 900}),
+                                             "sgd-graph-sched": 900, "sgd-graph-ssim": 900, "sgd-graph-views": 900}),
                     default=None)
     args = ap.parse_args()
     if args.child == "sgd-graph-ema" and not (args.ema is not None and 0.0 < args.ema < 1.0):
@@ -631,14 +740,23 @@ def main():
         ap.error("--ssim F > 0 is a measurement of its own")
     if args.child == "sgd-graph-ssim" and args.ssim is None:
         ap.error("--child sgd-graph-ssim needs --ssim F")
-    if (args.parent_tree and args.clip is None and args.weight_decay is None and args.ema is None and args.trust is None
+    if args.views is not None and (min(args.views) < 2 or (args.child == "sgd-graph-views" and len(args.views) != 1) or (not args.child and (
+            args.clip is not None or args.weight_decay is not None or args.ema is not None or args.trust is not None
+            or args.accum is not None or args.sched is not None or args.ssim is not None))):
+        ap.error("--views Q >= 2 is a measurement of its own (one Q with --child sgd-graph-views)")
+    if args.child == "sgd-graph-views" and args.views is None:
+        ap.error("--child sgd-graph-views needs --views Q")
+    if (args.parent_tree and args.views is None and args.clip is None and args.weight_decay is None and args.ema is None and args.trust is None
             and args.accum is None and args.sched is None and args.ssim is None):
-        ap.error("--parent-tree goes with --clip, --weight-decay, --ema, --trust, --accum, --sched or --ssim")
+        ap.error("--parent-tree goes with --clip, --weight-decay, --ema, --trust, --accum, --sched, --ssim or --views")
     if args.child:
         return child(args.child, args.steps if args.child != "adam-eager" else max(3, args.steps // 2), args.warmup,
                      B=args.shape[0], L=args.shape[1], clip=args.clip or 0.0, wd=args.weight_decay or 0.0,
                      no_decay=tuple(args.no_decay), ema=args.ema or 0.0, accum=args.accum or 1,
-                     sched=(args.sched, args.sched_warmup) if args.child == "sgd-graph-sched" else None, ssim=args.ssim or 0.0)
+                     sched=(args.sched, args.sched_warmup) if args.child == "sgd-graph-sched" else None, ssim=args.ssim or 0.0,
+                     views=args.views[0] if args.views else 1)
+    if args.views is not None:
+        return views_rounds(args)
     if args.ssim is not None:
         return ssim_rounds(args)
     if args.sched is not None:
