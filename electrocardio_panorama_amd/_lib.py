@@ -92,6 +92,14 @@ class LossSsimArgs(C.Structure):
                 ("g_pred", p), ("B", i32), ("L", i32), ("factor", f32), ("reserved0", i32)]
 
 
+class AugmentArgs(C.Structure):
+    """Mirror of `nef_augment_args` (include/nefnet_hip.h)."""
+    _fields_ = [("x", p), ("rois", p), ("y", p), ("seed_dev", p), ("seed", C.c_uint64),
+                ("wander_amp", C.c_double), ("wander_lo", C.c_double), ("wander_hi", C.c_double), ("hum_amp", C.c_double),
+                ("hum_hz", C.c_double), ("sample_rate", C.c_double), ("noise_std", f32), ("lead_drop", f32),
+                ("B", i32), ("V", i32), ("L", i32), ("R", i32), ("crop", i32), ("reserved0", i32)]
+
+
 class PackDesc(C.Structure):
     """Mirror of `nef_pack_desc` (include/nefnet_hip.h)."""
     _fields_ = [("w", p), ("wp", p), ("G", i32), ("Cog", i32), ("Cig", i32), ("K", i32), ("transpose_flip", i32),
@@ -178,6 +186,8 @@ SIGNATURES = {
     "nef_loss_ssim_bwd": (i32, [C.POINTER(LossSsimArgs), p]),
     "nef_loss_ssim_ws_bytes": (sz, [i32, i32]),
     "nef_loss_ssim_args_bytes": (sz, []),
+    "nef_augment": (i32, [C.POINTER(AugmentArgs), p]),
+    "nef_augment_args_bytes": (sz, []),
     "nef_sgd_momentum": (i32, [p, p, p, i64, f32, f32, f32, i32, p, p, p, p]),
     "nef_adam": (i32, [p, p, p, p, i64, f32, C.c_double, C.c_double, f32, f32, f32, p, p, p, p, p]),
     "nef_update": (i32, [C.POINTER(UpdateArgs), p]),
@@ -247,7 +257,8 @@ def load():
                                ("nef_ema_args", lib.nef_ema_args_bytes(), EmaArgs),
                                ("nef_trust_args", lib.nef_trust_args_bytes(), TrustArgs),
                                ("nef_lr_sched_args", lib.nef_lr_sched_args_bytes(), LrSchedArgs),
-                               ("nef_loss_ssim_args", lib.nef_loss_ssim_args_bytes(), LossSsimArgs)):
+                               ("nef_loss_ssim_args", lib.nef_loss_ssim_args_bytes(), LossSsimArgs),
+                               ("nef_augment_args", lib.nef_augment_args_bytes(), AugmentArgs)):
         if size != C.sizeof(mirror):
             raise NefLibraryError(f"{LIB_PATH}: {name} is {size} bytes, the binding mirrors {C.sizeof(mirror)}; rebuild with "
                                   "`python -m electrocardio_panorama_amd.csrc.build`")

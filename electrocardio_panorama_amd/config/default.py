@@ -23,6 +23,22 @@ _DEFAULTS = {
         "super_mode": "normal",
         "weighted_sample": False,
         "synthetic": False,            # (not in the reference) train / validate on seeded synthetic `meta` batches
+        # (not in the reference) corruption of the INPUT leads of every train step, on the device (nef_augment: one launch in front of
+        # the stem, in the eager and the graphed step; targets and rest views stay clean; augment.py).  Every draw comes from the step's
+        # counter-RNG seed, so a resumed run and a replayed step see the same corruption, and shards differ.  The four amplitude /
+        # probability keys at 0 = off: no launch, no buffer, the graphs and bits are what they were before the keys existed
+        "aug_noise_std": 0.0,          # sigma of white Gaussian noise on every input lead, in signal units (the loaders' rows are in [0, 1])
+        "aug_wander_amp": 0.0,         # largest amplitude of ONE baseline-wander sinusoid per (sample, lead): amplitude, frequency, phase drawn
+        "aug_wander_hz": [0.05, 0.7],  # its frequency range [lo, hi], Hz
+        "aug_hum_amp": 0.0,            # largest amplitude of ONE mains-hum sinusoid per (sample, lead): amplitude and phase drawn
+        "aug_hum_hz": 50.0,            # its frequency, Hz
+        "aug_lead_drop": 0.0,          # probability that an input lead of a sample is zeroed (in [0, 1)); every sample keeps at least one lead
+        "sample_rate": 500.0,          # Hz: turns the two frequencies into turns per sample
+        "aug_crop": True,              # corrupt positions t < rois[i, -1, 0] only (the row's valid extent, as SOLVER.ssim_crop); padding stays
+        # with any corruption on: Solver.train / Solver.val run the test phase a second time on corrupted inputs -- one fixed corrupted
+        # test set per (seed, batch index, rank) -- and log psnr_gen_aug / psnr_reg_aug / ssim_gen_aug / ssim_reg_aug; best_valid stays on
+        # the clean psnr_gen
+        "aug_eval": False,
     },
     "MODEL": {
         "model": "modelv2",            # 'model_nefnet' selects Nef-Net

@@ -36,6 +36,11 @@ Several target views per step (cfg.SOLVER.train_views; the call signature does n
 [Q, B, 2] with a target of [Q, B, 1, L] selects engine.forward's multi-view form -- one graph per (shape, Q), its slot holding static
 [Q, B, 2] angles, [Q, B, 1, L] targets and, for the cropped SSIM term, the rois tiled once per view, all staged outside the graph with
 the other inputs.  The sums over views are ops.copy_many launches inside the graph; both capture forms are otherwise as above.
+
+Input-lead augmentation (cfg.DATA.aug_*; augment.py): every shape slot owns one more static [B, V, L] buffer, and ops.augment from the
+staged inputs into it is the FIRST launch of the captured forward -- it reads the step's seed through the `seed_dev` word the dropout
+epilogues read, so every replay (every micro-batch of an accumulation window; once per multi-view step) draws its own corruption with no
+host write of its own.  Off: no buffer, no launch.
 """
 import random
 
@@ -63,6 +68,10 @@ class GraphedTrainStep:
         from .network.loss.losses import ssim_settings
         self.ssim_factor = ssim_settings(cfg, need_rois=False)[0]
         self.ssim_crop = self.ssim_factor > 0 and bool(cfg.SOLVER.get('ssim_crop', True))
+        # cfg.DATA.aug_*: every shape slot owns a static [B, V, L] buffer the captured ops.augment writes and the forward reads; None: neither
+        from . import augment as _augment
+        self.augment = _augment.from_cfg(cfg)
+        self.data_aug = None
         self.optimizer = optimizer
         if optimizer is not None:
             if len(optimizer.param_groups) != 1 or not hasattr(optimizer, "_device_update"):
@@ -143,8 +152,13 @@ class GraphedTrainStep:
         m = self.model
         P = {k: v.detach() for k, v in m.named_parameters()}
         drop = engine.DropCfg(True, m.dropout_p, m.dropout_masks, seed=0, seed_dev=self.seed_dev)
+        data = self.data
+        if self.augment is not None:
+            # the step's first launch: the corrupted leads into the slot's buffer, at host word + seed_dev = the eager step's seed word
+            from . import augment as _augment
+            data = ops.augment(self.data, self.rois, self.augment, seed=_augment.site_word(), seed_dev=self.seed_dev, out=self.data_aug)
         with ops.amax_scope((m._nef_scope, True)):        # the train-mode call sites of the model (Model_nefnet._engine_fwd)
-            outs, sv = engine.forward(P, dict(m.named_buffers()), self.data, self.in_theta, self.q_theta, self.rois,
+            outs, sv = engine.forward(P, dict(m.named_buffers()), data, self.in_theta, self.q_theta, self.rois,
                                       phase="train", training=True, drop=drop, lead_choice=self.choice_dev, save=True,
                                       status=self.status)
             o, p_, l_ = (t.contiguous() for t in outs)
@@ -259,6 +273,7 @@ class GraphedTrainStep:
                                                                           ("data", "in_theta", "q_theta", "rois", "target"))
         self.noise = slot.get("noise")
         self.rois_q = slot.get("rois_q")
+        self.data_aug = slot.get("data_aug")
 
     def _build(self, data, in_theta, q_theta, rois, target, noise=None):
         dev = data.device
@@ -282,6 +297,8 @@ class GraphedTrainStep:
                 slot["rois_q"] = torch.empty(Q * rois.shape[0], rois.shape[1], rois.shape[2], device=dev, dtype=torch.int64)
         if self.use_noise:
             slot["noise"] = torch.empty(data.shape[0], 1, data.shape[2], device=dev, dtype=torch.float32)
+        if self.augment is not None:
+            slot["data_aug"] = torch.empty(data.shape, device=dev, dtype=torch.float32)
         self._use(slot)
         if self.choice_dev is None:
             self.choice_dev = torch.zeros(2, device=dev, dtype=torch.int32)

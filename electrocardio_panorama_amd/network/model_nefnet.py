@@ -9,6 +9,7 @@ shapes and default initialisation; their own forward() is never called.  All com
 
 Beyond the reference: `forward(..., query_theta [Q, B, 2], phase='train')` (view-major angles) supervises Q views on one encoder pass
 and returns three [Q, B, 1, L] tensors (SOLVER.train_views; engine._views_fwd); a 2-D `query_theta` is the reference's call.
+`model.augment` (DATA.aug_*; augment.py): a train-phase forward in train() mode reads its input leads through ops.augment.
 """
 import math
 import random
@@ -16,6 +17,7 @@ import random
 import torch
 import torch.nn as nn
 
+from .. import augment as _augment
 from .. import engine, ops
 
 
@@ -144,6 +146,9 @@ class Model_nefnet(nn.Module):
         # 'fp32' (reference arithmetic) or 'fp16': eval-mode view sweeps (phase 'val'/'test' rest_out, gen_ecg) on the
         # fp16 matrix cores with fp32 accumulation -- opt-in, gated at 2e-3 rel-L2 against the fp32 path
         self.panorama_dtype = 'fp32'
+        # DATA.aug_* (augment.from_cfg's Augment; Solver.__init__ sets it from the config): a train-phase forward of a model in train()
+        # mode corrupts its input leads in front of the stem, keyed on the forward's dropout seed; None: the input is read as it is
+        self.augment = None
         self._drop_calls = 0
         self.dropout_epoch = 0         # set by Solver.train: a resumed run must not replay the masks of epoch 0
         self._status = None
@@ -207,6 +212,10 @@ class Model_nefnet(nn.Module):
         x, input_thetas, query_theta = self._f32(x), self._f32(input_thetas), self._f32(query_theta)
         rois = rois.detach().to(torch.int64).contiguous()
         drop = self._drop_cfg()
+        if phase == 'train' and self.training and self.augment is not None:
+            # DATA.aug_*: forward and the stem's weight gradient (the saved x) both see the corrupted leads; the caller's tensor is not
+            # written.  No other phase corrupts its input, and neither does a train-phase call on a model in eval()
+            x = ops.augment(x, rois, self.augment, seed=_augment.train_seed(drop.seed))
         if phase == 'gen':
             with torch.no_grad():
                 (z1, z2), _ = self._engine_fwd(self._params_by_name(), self._buffers_by_name(), x, input_thetas,

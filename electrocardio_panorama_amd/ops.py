@@ -1766,6 +1766,55 @@ def loss_ssim_bwd(pred, target, g_pred, factor, rois=None, noise=None, gscale=No
     return g_pred
 
 
+AUGMENT_TILE = 1024      # NEF_AUGMENT_TILE (include/nefnet_hip.h): positions of a row per workgroup of nef_augment
+
+
+def augment(x, rois, aug, seed=0, seed_dev=None, out=None):
+    """The input leads `x` [B, V, L] corrupted as cfg.DATA.aug_* say (`aug`: augment.from_cfg's Augment; nef_augment, include/nefnet_hip.h,
+    defines every draw): a new tensor, or `out`; `x` is never written.  `aug` None: `x` itself, no launch.  `rois`: the batch's integer
+    [B, R, 2] rows on x's device (read with aug.crop only).  `seed`: the launch's 64-bit seed word (augment.train_seed / eval_seed);
+    `seed_dev`: None, or a one-element int64 device tensor added to it when the launch runs (the replayed step's seed word, with
+    seed = augment.site_word()).  One launch, capturable.  Every argument check sits in front of the library."""
+    if aug is None:
+        return x
+    if not torch.is_tensor(x) or x.dtype != torch.float32:
+        raise TypeError(f"x must be a float32 tensor, got {getattr(x, 'dtype', type(x))}")
+    if x.dim() != 3 or not x.is_contiguous():
+        raise ValueError(f"x must be a contiguous [B, V, L] tensor, got {tuple(x.shape)} with strides {tuple(x.stride())}")
+    B, V, Ln = x.shape
+    if min(B, V, Ln) < 1 or Ln % 4 != 0:
+        raise ValueError(f"x {tuple(x.shape)}: B, V, L >= 1 and L a multiple of 4")
+    if not torch.is_tensor(rois) or rois.dtype not in (torch.int64, torch.int32):
+        raise TypeError(f"rois must be an integer tensor [B, R, 2], got {getattr(rois, 'dtype', type(rois))}")
+    if rois.dim() != 3 or rois.shape[0] != B or rois.shape[1] < 1 or rois.shape[2] != 2:
+        raise ValueError(f"rois {tuple(rois.shape)} is not [{B}, R, 2]")
+    if rois.device != x.device:
+        raise ValueError(f"rois is on {rois.device}, x on {x.device}")
+    if out is not None:
+        if not torch.is_tensor(out) or out.dtype != torch.float32 or out.shape != x.shape or not out.is_contiguous() or out.device != x.device:
+            raise ValueError("out must be a contiguous float32 tensor of x's shape on x's device")
+        if out.data_ptr() == x.data_ptr():
+            raise ValueError("out is x: the corruption is out of place, the loader's tensor is never modified")
+    if seed_dev is not None and (not torch.is_tensor(seed_dev) or seed_dev.dtype != torch.int64 or seed_dev.numel() != 1
+                                 or seed_dev.device != x.device):
+        raise ValueError("seed_dev must be a one-element int64 tensor on x's device")
+    if not x.is_cuda:
+        raise RuntimeError("ops.augment runs on a HIP device only (no CPU path)")
+    if x.data_ptr() % 16 != 0:
+        raise ValueError("x is not 16-byte aligned")
+    L = _lib.load()
+    rois = rois.to(torch.int64).contiguous()
+    y = torch.empty_like(x) if out is None else out
+    ev = _hbm("augment", x, y)
+    A = _lib.AugmentArgs(x=_p(x), rois=_p(rois), y=_p(y), seed_dev=_p(seed_dev), seed=int(seed) & 0xFFFFFFFFFFFFFFFF,
+                         wander_amp=aug.wander_amp, wander_lo=aug.wander_lo, wander_hi=aug.wander_hi, hum_amp=aug.hum_amp,
+                         hum_hz=aug.hum_hz, sample_rate=aug.sample_rate, noise_std=aug.noise_std, lead_drop=aug.lead_drop,
+                         B=B, V=V, L=Ln, R=rois.shape[1], crop=int(bool(aug.crop)))
+    _lib.check(L.nef_augment(C.byref(A), _stream()), "nef_augment")
+    _done(ev)
+    return y
+
+
 def flatten_into(tensors, out, accumulate=False, accumulate_dev=None):
     """out[:] = concatenation of `tensors` (contiguous fp32, flattened), ONE launch per 64 tensors (nef_flatten; was torch.cat).
     `accumulate`: out[:] += the concatenation instead (gradient accumulation: one fp32 add per element, no atomics).  `accumulate_dev`: a

@@ -16,17 +16,24 @@ the scalar log and the checkpoints.
 
 `SOLVER.train_views = Q >= 2` (no counterpart in the reference): a train step supervises Q of the batch's supervised rest views on one
 encoder pass -- the targets are drawn per step by `views.draw_views(seed, epoch, batch index, Q, S)` and handed to the model as
-`query_theta` [Q, B, 2] with `[Q, B, 1, L]` targets, eagerly or through the graphed step; `target_view` / `target_theta` are not used."""
+`query_theta` [Q, B, 2] with `[Q, B, 1, L]` targets, eagerly or through the graphed step; `target_view` / `target_theta` are not used.
+
+`DATA.aug_*` (no counterpart in the reference; augment.py): the train step corrupts its INPUT leads on the device -- inside the model's
+train-phase forward or as the first launch of the graphed step -- against the clean targets; with a corruption on, the step counters
+restart with every train epoch, so the step's seed is a function of (seed, epoch, batch index, rank) and a resumed epoch draws what the
+uninterrupted one drew.  `DATA.aug_eval`: `train` and `val` run the test phase a second time on one fixed corrupted test set and report
+psnr_gen_aug / psnr_reg_aug / ssim_gen_aug / ssim_reg_aug beside the clean numbers, which decide best_valid as before."""
 import contextlib
 import json
 import os
+import random
 
 import numpy as np
 import torch
 from .. import _env
 import torch.distributed as dist
 
-from .. import engine, ops, parallel, views
+from .. import augment, engine, ops, parallel, views
 from ..network import build_model, build_loss
 from ..utils import CheckPointer
 from .optim_scheduler import get_optimizer, get_lr_scheduler
@@ -120,6 +127,8 @@ class Solver:
         # 1: the reference's step on target_view / target_theta.  Invalid values and DATA.noise with Q >= 2 are rejected here
         self.train_views = views.train_views(cfg)
         self.model = build_model(cfg).float()
+        # DATA.aug_*: the train step corrupts its input leads on the device (augment.py); invalid keys are rejected here.  None = off
+        self.augment = self.model.augment = augment.from_cfg(cfg)
         self.loss = build_loss(cfg)
         self._init_model_device()
         if self.desc != 'debug' and use_tensorboardx and _is_main():       # solver.py:23-26
@@ -152,6 +161,8 @@ class Solver:
         if sched is not None and sched.on and sched.total_updates == 0:
             # SOLVER.total_updates 0: the run's updates, known here -- before the first step, so nothing is re-captured for it
             sched.total_updates = max_epochs * -(-len(dl_train) // getattr(optimizer, 'accum_steps', 1))
+        if self.augment is not None:
+            print(self.augment.describe())                # once: the DATA.aug_* keys that are on
         for epoch in range(start_epoch, max_epochs):
             print('---------------------------------{}---{}-------------------------------------'.format(self.cfg.desc, epoch))
             if hasattr(getattr(dl_train, 'sampler', None), 'set_epoch'):
@@ -188,6 +199,13 @@ class Solver:
                         scalars += [float(np.mean(single[:, i, 0])), float(np.mean(single[:, i, 1]))]
                 msg += ', test_loss: {}'.format(float(te[0]))
                 msg += '\npsnr_gen: {}, psnr_reg: {}, ssim_gen:{}, ssim_reg:{}'.format(psnr_gen, psnr_reg, ssim_gen, ssim_reg)
+                if self.augment is not None and self.augment.eval:
+                    # DATA.aug_eval: the same weights on the fixed corrupted test set; best_valid stays on the clean psnr_gen
+                    with optimizer.ema_weights() if self._ema_eval(optimizer) else contextlib.nullcontext():
+                        aug_metrics = self._aug_eval(dl_test)
+                    scalars += list(aug_metrics)
+                    names += ['psnr_gen_aug', 'psnr_reg_aug', 'ssim_gen_aug', 'ssim_reg_aug']
+                    msg += '\npsnr_gen_aug: {}, psnr_reg_aug: {}, ssim_gen_aug:{}, ssim_reg_aug:{}'.format(*aug_metrics)
             if tl.shape[0] > 4:                   # SOLVER.ssim_factor is on: the term is the last element of every loss row
                 scalars.append(float(tl[-1]))
                 names.append('train_loss_ssim')
@@ -232,9 +250,26 @@ class Solver:
         on = float(self.cfg.SOLVER.get('ema_decay', 0.0)) > 0 and bool(self.cfg.SOLVER.get('ema_eval', True))
         return on and (optimizer is None or getattr(optimizer, 'ema_decay', 0.0) > 0)
 
+    def _aug_eval(self, dl_test):
+        """DATA.aug_eval: (psnr_gen, psnr_reg, ssim_gen, ssim_reg) of the test phase on corrupted inputs -- batch i under
+        augment.eval_seed(cfg.seed, i, rank), so every epoch and every resumed run judges the same corrupted test set and no seed is a
+        train step's.  The run goes on as if this pass had not happened: Python's `random` stream (the Standin draws), the model's
+        forward counter and the eval-mode operand magnitudes of the split-fp16 call sites are put back."""
+        state, calls, amax0 = random.getstate(), getattr(self.model, '_drop_calls', 0), ops.amax_snapshot(self.device)
+        try:
+            with torch.no_grad():
+                metrics = self.run_one_epoch(dl_test, phase='test', collect_views=False, aug_eval=True)[4]
+        finally:
+            random.setstate(state)
+            self.model._drop_calls = calls
+            ops.amax_restore(self.device, amax0)
+        self.last_aug_metrics = tuple(float(v) for v in np.mean(metrics, axis=0))
+        return self.last_aug_metrics
+
     def val(self, dl_test, epoch=-1):
         """solver.py:118-137: load `best_valid.pkl` (epoch == -1) or `epoch_<n>.pkl`, run the test phase, print and
-        return (psnr_gen, psnr_reg, ssim_gen, ssim_reg)."""
+        return (psnr_gen, psnr_reg, ssim_gen, ssim_reg).  DATA.aug_eval with a corruption on: the corrupted test set's four numbers are
+        printed behind them and kept in `last_aug_metrics`; the return value is the clean one."""
         self.model.eval()
         optimizer = get_optimizer(self.cfg, self.model.parameters())
         scheduler = get_lr_scheduler(self.cfg, optimizer)
@@ -249,6 +284,8 @@ class Solver:
             mertics_all = self.run_one_epoch(dl_test, phase='test', collect_views=False)[4]
         psnr_gen, psnr_reg, ssim_gen, ssim_reg = (float(v) for v in np.mean(mertics_all, axis=0))
         print('psnr_gen:{}, psnr_reg:{}, ssim_gen:{}, ssim_reg:{}'.format(psnr_gen, psnr_reg, ssim_gen, ssim_reg))
+        if self.augment is not None and self.augment.eval:
+            print('psnr_gen_aug:{}, psnr_reg_aug:{}, ssim_gen_aug:{}, ssim_reg_aug:{}'.format(*self._aug_eval(dl_test)))
         return psnr_gen, psnr_reg, ssim_gen, ssim_reg
 
     def _to_device(self, meta):
@@ -329,10 +366,20 @@ class Solver:
             return
         raise RuntimeError(msg + '; their results are wrong.  Set NEF_H2=0 (fp32 kernels), or NEF_H2_ALLOW_CLAMP=1 to continue')
 
-    def run_one_epoch(self, dl, phase, optim=None, collect_views=None):
+    def run_one_epoch(self, dl, phase, optim=None, collect_views=None, aug_eval=False):
         """solver.py:139-246.  `collect_views` (default: the Solver's setting) = also return the per-view host lists the
         reference returns (inputs, ground truth, predictions, rois); train() / val() only consume losses and metrics and
-        pass False, so an epoch stages nothing but a few scalars per step."""
+        pass False, so an epoch stages nothing but a few scalars per step.  With DATA.aug_* on, the inputs in those lists are the CLEAN
+        ones the loader delivered: the corrupted copy lives inside the step.  `aug_eval` (test phase, DATA.aug_* on): the model reads
+        batch i corrupted under augment.eval_seed(cfg.seed, i, rank) -- the robustness read-out of `_aug_eval`."""
+        if aug_eval and (phase != 'test' or self.augment is None):
+            raise ValueError('aug_eval is the test phase with a DATA.aug_* corruption on')
+        if phase == 'train' and self.augment is not None:
+            # the step's seed counts from the start of the epoch: a function of (seed, epoch, batch index, rank) on the eager and the
+            # replayed path alike, whatever ran in between (test phases, a resume)
+            self.model._drop_calls = 0
+            if getattr(self, '_graph_stepper', None) is not None:
+                self._graph_stepper.calls = 0
         if phase == 'train':
             self.model.train()
         elif phase == 'test':
@@ -395,6 +442,10 @@ class Solver:
                 optim.zero_grad()
             else:
                 rest_view = torch.as_tensor(meta['rest_view']).to(self.device, torch.float32).contiguous()
+                if aug_eval:
+                    rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+                    source_data = ops.augment(source_data.to(torch.float32).contiguous(), rois, self.augment,
+                                              seed=augment.eval_seed(self.cfg.get('seed', 0), n_batches, rank))
                 out, shuf_p, shuf_l, rest_out = self.model(source_data, input_theta, target_theta, rois,
                                                            rest_theta=rest_theta, phase='test')
                 losses = self.loss(out, shuf_p, shuf_l, target_view, self.cfg, rest_out[:, -4:, :].contiguous(),

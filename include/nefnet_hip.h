@@ -595,6 +595,49 @@ size_t nef_loss_ssim_ws_bytes(int B, int L);
 /* sizeof(nef_loss_ssim_args) as the library was built. */
 size_t nef_loss_ssim_args_bytes(void);
 
+/* Input-lead augmentation of the train step (cfg.DATA.aug_*; no counterpart in the reference, whose only augmentation is the host-side
+ * angle jitter): y = a corrupted copy of the input leads x [B, V, L]; x is never written.  Every draw comes from the counter RNG of the
+ * dropout epilogues (z = mix(seed + seed_dev[0], counter); k0 = z >> 40 and k1 = (z >> 16) & 0xFFFFFF are its two 24-bit fields):
+ *   per element, counter = (dense element index of x) >> 1, so elements 2k and 2k + 1 share a word (L % 4 == 0: never across rows):
+ *     r = sqrt(-2 ln((k0 + 1) / 2^24)),  n_even = r cos(2 pi k1 / 2^24),  n_odd = r sin(2 pi k1 / 2^24);
+ *   per row (b, v), counter = 2^62 + 4 (b V + v) + j:
+ *     j = 0: A_w = wander_amp k0 / 2^24,  f_w = wander_lo + (wander_hi - wander_lo) k1 / 2^24;
+ *     j = 1: phi_w = k0 / 2^24 turns,  A_h = hum_amp k1 / 2^24;
+ *     j = 2: phi_h = k0 / 2^24 turns,  u_d = k1 / 2^24;
+ *     j = 3, of row (b, 0) only: the fallback lead floor(V k0 / 2^24).
+ * Row (b, v) is dropped when u_d < lead_drop -- unless that drops all V rows of sample b, then the fallback lead is kept.  A dropped
+ * row is 0 over its whole length.  A kept row, with end_b = clamp(rois[b, R - 1, 0], 0, L) (L when crop is 0):
+ *   y = x + noise_std n_t + A_w sin(2 pi (f_w t / sample_rate + phi_w)) + A_h sin(2 pi (hum_hz t / sample_rate + phi_h))   for t < end_b,
+ *   y = x (the bits)                                                                                                         for t >= end_b.
+ * A term whose amplitude is 0 is not evaluated: with lead_drop alone, kept rows are bit copies.  The row parameters and the phase (in
+ * turns, reduced to [0, 1)) are fp64; the transcendental functions and the three adds (left to right as written) are fp32.
+ * One workgroup per (row, tile of NEF_AUGMENT_TILE positions), one 16-byte load and store per thread, one writer per element, no
+ * atomics: the same bits eagerly, under hipGraph replay (seed_dev: the replayed step's seed word) and on every rank at one seed.
+ * args, x, y NULL, or crop set with rois NULL: NEF_E_NULL; B, V, L <= 0, L % 4 != 0, R <= 0 with rois, more than 2^31 - 1 workgroups,
+ * a negative or NaN amplitude, lead_drop outside [0, 1), sample_rate <= 0, wander_lo > wander_hi, wander_hi or hum_hz at or above
+ * sample_rate / 2 while its amplitude is on: NEF_E_SHAPE; x or y not 16-byte aligned, or the two overlapping: NEF_E_UNSUPPORTED.
+ * Every check sits in front of the launch.  Capturable: nothing is read by the host, nothing is allocated. */
+#define NEF_AUGMENT_TILE 1024
+typedef struct nef_augment_args {
+    const float* x;             /* [B, V, L] */
+    const int64_t* rois;        /* NULL, or [B, R, 2] */
+    float* y;                   /* [B, V, L], not x */
+    const uint64_t* seed_dev;   /* NULL, or a device word added to seed when the launch runs */
+    uint64_t seed;
+    double wander_amp, wander_lo, wander_hi;   /* signal units, Hz, Hz */
+    double hum_amp, hum_hz;
+    double sample_rate;         /* Hz, > 0 */
+    float noise_std;            /* >= 0 */
+    float lead_drop;            /* in [0, 1) */
+    int32_t B, V, L;
+    int32_t R;                  /* rois per sample (7) */
+    int32_t crop;               /* 1: corrupt t < rois[b, R - 1, 0] only */
+    int32_t reserved0;          /* 0 */
+} nef_augment_args;
+int nef_augment(const nef_augment_args* a, nef_stream_t stream);
+/* sizeof(nef_augment_args) as the library was built. */
+size_t nef_augment_args_bytes(void);
+
 /* ---------------------------------------------------------------------------------------------
  * SGD with momentum over a flat buffer.  codes/solver/optim_scheduler.py:10 (torch.optim.SGD semantics:
  * first step buf = g, afterwards buf = mu*buf + g; p -= lr*buf).  g is multiplied by gscale first
