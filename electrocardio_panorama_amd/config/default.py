@@ -132,6 +132,16 @@ _DEFAULTS = {
         # used then; the loss row keeps its elements (each the mean over views).  Q > S and DATA.noise with Q >= 2 are rejected.
         # 1 = off: the launches, graphs, loader fields and bits are what they were before the key existed
         "train_views": 1,
+        # weights of the reconstruction term by wave segment, on the device (nef_loss_seg_fwd / nef_loss_seg_bwd behind the loss launches, in
+        # the eager and the graphed step): [P, PR, QRS, ST, T, TP, pad] -- seven finite numbers >= 0, not all zero.  Term 3 becomes
+        # f2 * (1/n) * sum w[segment of (i, t)] * e(i, t) over ALL n elements (no renormalisation: 3 counts a position three times, all ones
+        # is the flat mean, pad = 0 takes the zero padding out).  The segment of a position comes from the batch's rois: t >= rois[i, 6, 0]
+        # is pad, otherwise the number of k in 1..5 with rois[i, k, 0] <= t.  Needs 3 in loss_using.  [] = off: the launches, graphs, loss
+        # rows and bits are what they were before the key existed
+        "seg_weights": [],
+        # True: the test phase also reports the PSNR of each wave segment (nef_view_seg_metrics beside nef_view_metrics), logged as
+        # psnr_gen_seg_{P,PR,QRS,ST,T,TP} / psnr_reg_seg_* with the view split of psnr_gen / psnr_reg.  False: no launch, no buffer
+        "seg_eval": False,
     },
 }
 

@@ -8,6 +8,8 @@ it: inputs are copied into static buffers, and the only per-step host decisions 
 travel through device words that the kernels read at run time.  Same arithmetic as the eager path.  `cfg.DATA.noise`: the
 per-sample noise row is one more static input, added to the prediction inside the loss kernels (ops.loss_fwd / loss_bwd, noise=).
 `cfg.SOLVER.ssim_factor`: the SSIM term's three launches (ops.loss_ssim_fwd / loss_ssim_bwd) sit behind them in the same graph.
+`cfg.SOLVER.seg_weights`: the segment weights' three launches (ops.loss_seg_fwd / loss_seg_bwd) sit between the two, each behind the loss
+launch it rewrites; the weights are config constants, frozen into the capture as scalars.
 
 One graph (with its own static input buffers) is kept per input shape, so a final partial batch or alternating shapes
 replay instead of re-capturing; the flat parameter / gradient / momentum buffers are shared by all of them and survive
@@ -62,12 +64,15 @@ class GraphedTrainStep:
         # and added inside the loss kernels; off: no buffer, no copy
         self.use_noise = bool(cfg.DATA.noise)
         self.noise = None
-        self.rois_q = None       # multi-view steps with the cropped SSIM term: the slot's rois tiled Q times
+        self.rois_q = None       # multi-view steps with the cropped SSIM term or segment weights: the slot's rois tiled Q times
         # cfg.SOLVER.ssim_factor: the SSIM term's launches behind the loss launches, on the static rois and noise; the loss row has 5
         # elements then.  0: no launch, the 4-element row
         from .network.loss.losses import ssim_settings
         self.ssim_factor = ssim_settings(cfg, need_rois=False)[0]
         self.ssim_crop = self.ssim_factor > 0 and bool(cfg.SOLVER.get('ssim_crop', True))
+        # cfg.SOLVER.seg_weights: None (no launch), or the seven weights of the reconstruction term's positions
+        from .network.loss.losses import seg_settings
+        self.seg_weights = seg_settings(cfg)
         # cfg.DATA.aug_*: every shape slot owns a static [B, V, L] buffer the captured ops.augment writes and the forward reads; None: neither
         from . import augment as _augment
         self.augment = _augment.from_cfg(cfg)
@@ -164,6 +169,10 @@ class GraphedTrainStep:
             o, p_, l_ = (t.contiguous() for t in outs)
             ops.loss_fwd(o, p_, l_, self.target, self.factors, self.reg_l2, self.use_mask, out=self.losses, noise=self.noise)
             g3 = ops.loss_bwd(o, p_, l_, self.target, None, self.factors, self.reg_l2, self.use_mask, noise=self.noise)
+            if self.seg_weights is not None:
+                rois = self.rois if self.rois_q is None else self.rois_q
+                ops.loss_seg_fwd(o, self.target, self.losses, self.seg_weights, self.factors[2], self.reg_l2, rois, noise=self.noise)
+                ops.loss_seg_bwd(g3[0], self.seg_weights, rois)
             if self.ssim_factor > 0:
                 # (multi-view: the rows are the Q * B (view, sample) pairs, the rois tiled once per view)
                 rois = (self.rois if self.rois_q is None else self.rois_q) if self.ssim_crop else None
@@ -293,7 +302,10 @@ class GraphedTrainStep:
             if self.ssim_factor > 0:
                 from .network.loss.losses import check_view_rows
                 check_view_rows(Q, data.shape[0])
-            if self.ssim_crop:
+            if self.seg_weights is not None:
+                from .network.loss.losses import check_seg_rows
+                check_seg_rows(Q * data.shape[0])
+            if self.ssim_crop or self.seg_weights is not None:
                 slot["rois_q"] = torch.empty(Q * rois.shape[0], rois.shape[1], rois.shape[2], device=dev, dtype=torch.int64)
         if self.use_noise:
             slot["noise"] = torch.empty(data.shape[0], 1, data.shape[2], device=dev, dtype=torch.float32)

@@ -25,6 +25,7 @@ def build_loss(cfg):
     except KeyError:
         raise ValueError('build loss: loss name error') from None
     if cfg.MODEL.loss == "v1":
-        from .loss.losses import ssim_settings
+        from .loss.losses import seg_settings, ssim_settings
         ssim_settings(cfg, need_rois=False)          # a negative SOLVER.ssim_factor is rejected here, not at the first batch
+        seg_settings(cfg)                            # ... and a malformed SOLVER.seg_weights
     return make()

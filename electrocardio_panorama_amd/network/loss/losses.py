@@ -6,26 +6,33 @@ from ... import ops
 
 class _LossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pred, pred_p, pred_l, target, factors, reg_l2, use_mask, noise=None, ssim_factor=0.0, rois=None):
+    def forward(ctx, pred, pred_p, pred_l, target, factors, reg_l2, use_mask, noise=None, ssim_factor=0.0, rois=None, seg_weights=None,
+                seg_rois=None):
         pred, pred_p, pred_l, target = (t.contiguous() for t in (pred, pred_p, pred_l, target))
-        ctx.save_for_backward(pred, pred_p, pred_l, target, noise, rois)
-        ctx.cfg = (factors, reg_l2, use_mask, ssim_factor)
-        if not ssim_factor > 0:
+        ctx.save_for_backward(pred, pred_p, pred_l, target, noise, rois, seg_rois)
+        ctx.cfg = (factors, reg_l2, use_mask, ssim_factor, seg_weights)
+        if not ssim_factor > 0 and seg_weights is None:
             return ops.loss_fwd(pred, pred_p, pred_l, target, factors, reg_l2, use_mask, noise=noise)
         # SOLVER.ssim_factor: a 5-element row -- the SSIM term behind the four, added into the total by its own finish launch
-        row = torch.empty(5, device=pred.device, dtype=torch.float32)
+        row = torch.empty(5 if ssim_factor > 0 else 4, device=pred.device, dtype=torch.float32)
         ops.loss_fwd(pred, pred_p, pred_l, target, factors, reg_l2, use_mask, out=row, noise=noise)
-        return ops.loss_ssim_fwd(pred, target, row, ssim_factor, rois=rois, noise=noise)
+        if seg_weights is not None:     # SOLVER.seg_weights: the reconstruction term and the total rewritten, in front of the SSIM term
+            ops.loss_seg_fwd(pred, target, row, seg_weights, factors[2], reg_l2, seg_rois, noise=noise)
+        if ssim_factor > 0:
+            ops.loss_ssim_fwd(pred, target, row, ssim_factor, rois=rois, noise=noise)
+        return row
 
     @staticmethod
     def backward(ctx, g):
-        pred, pred_p, pred_l, target, noise, rois = ctx.saved_tensors
-        factors, reg_l2, use_mask, ssim_factor = ctx.cfg
+        pred, pred_p, pred_l, target, noise, rois, seg_rois = ctx.saved_tensors
+        factors, reg_l2, use_mask, ssim_factor, seg_weights = ctx.cfg
         g = g.contiguous()
         g_pred, g_p, g_l = ops.loss_bwd(pred, pred_p, pred_l, target, g, factors, reg_l2, use_mask, noise=noise)
+        if seg_weights is not None:     # the reconstruction term's gradient times its position's weight, in place
+            ops.loss_seg_bwd(g_pred, seg_weights, seg_rois)
         if ssim_factor > 0:         # accumulated onto the reconstruction term's gradient, in the same stream behind it
             ops.loss_ssim_bwd(pred, target, g_pred, ssim_factor, rois=rois, noise=noise, gscale=g)
-        return g_pred, g_p, g_l, None, None, None, None, None, None, None
+        return g_pred, g_p, g_l, None, None, None, None, None, None, None, None, None
 
 
 def ssim_settings(cfg, rois=None, need_rois=True):
@@ -44,6 +51,31 @@ def ssim_settings(cfg, rois=None, need_rois=True):
     return factor, rois
 
 
+SEG_NAMES = ('P', 'PR', 'QRS', 'ST', 'T', 'TP', 'pad')
+
+
+def seg_settings(cfg):
+    """SOLVER.seg_weights as a 7-tuple of floats [P, PR, QRS, ST, T, TP, pad], or None when the key is empty (off).  ValueError for a
+    wrong length, a negative or non-finite entry, all zeros, or the key on while the reconstruction term (3) is not in SOLVER.loss_using."""
+    raw = cfg.SOLVER.get('seg_weights', None)               # (.get: configs written before the key existed)
+    if raw is None or len(raw) == 0:
+        return None
+    if len(raw) != len(SEG_NAMES):
+        raise ValueError(f"Invalid SOLVER.seg_weights: {list(raw)} ({len(SEG_NAMES)} numbers are needed: {list(SEG_NAMES)}, or [] for off)")
+    try:
+        w = tuple(float(x) for x in raw)
+    except (TypeError, ValueError):
+        raise ValueError(f"Invalid SOLVER.seg_weights: {list(raw)} (numbers are needed)") from None
+    if not all(0.0 <= x < float('inf') for x in w):         # (NaN fails <=)
+        raise ValueError(f"Invalid SOLVER.seg_weights: {list(w)} (every weight must be finite and >= 0)")
+    if not any(x > 0.0 for x in w):
+        raise ValueError(f"Invalid SOLVER.seg_weights: {list(w)} (not all weights may be zero; [] switches the key off)")
+    if 3 not in cfg.SOLVER.loss_using:
+        raise ValueError("SOLVER.seg_weights weighs the reconstruction term, which SOLVER.loss_using leaves out: add 3 to "
+                         "SOLVER.loss_using or set SOLVER.seg_weights []")
+    return w
+
+
 SSIM_MAX_ROWS = 65535      # nef_loss_ssim_fwd / _bwd: the rows are a grid's y extent
 
 
@@ -52,6 +84,21 @@ def check_view_rows(Q, B):
     if Q * B > SSIM_MAX_ROWS:
         raise ValueError(f"SOLVER.train_views ({Q}) x the batch ({B}) = {Q * B} rows is more than the {SSIM_MAX_ROWS} the SSIM term "
                          "(SOLVER.ssim_factor) takes: lower SOLVER.train_views or the batch size, or set SOLVER.ssim_factor 0")
+
+
+def check_seg_rows(rows):
+    """The segment-weight launches take every (view, sample) row as one y index of their grid."""
+    if rows > SSIM_MAX_ROWS:
+        raise ValueError(f"{rows} rows (SOLVER.train_views x the batch) is more than the {SSIM_MAX_ROWS} the segment weights "
+                         "(SOLVER.seg_weights) take: lower SOLVER.train_views or the batch size, or set SOLVER.seg_weights []")
+
+
+def _rows_rois(rois, predict):
+    """int64 contiguous rois for the rows of `predict`: [B, 7, 2] tiled once per view for a multi-view prediction [Q, B, 1, L];
+    [Q * B, 7, 2] is taken as it is."""
+    if predict.dim() == 4 and rois.shape[0] == predict.shape[1]:
+        rois = rois.repeat(predict.shape[0], 1, 1)
+    return rois.detach().to(torch.int64).contiguous()
 
 
 def losswrapper(predict, predict_shuffle_p, predict_shuffle_l, target, cfg, rest_out=None, rest_view=None,
@@ -67,8 +114,20 @@ def losswrapper(predict, predict_shuffle_p, predict_shuffle_l, target, cfg, rest
     not looked at and the tuple, the launches and the bits are what they were.
     Multi-view steps (SOLVER.train_views; Model_nefnet.forward with query_theta [Q, B, 2]): predictions and target are [Q, B, 1, L] and
     every term is the mean over all Q * B * L elements -- the mean over views, which have equal size.  The SSIM term's rows are the
-    Q * B (view, sample) pairs; `rois` [B, 7, 2] is tiled once per view here ([Q * B, 7, 2] is taken as it is)."""
+    Q * B (view, sample) pairs; `rois` [B, 7, 2] is tiled once per view here ([Q * B, 7, 2] is taken as it is).
+    cfg.SOLVER.seg_weights [P, PR, QRS, ST, T, TP, pad]: the reconstruction term becomes f2 * (1/n) * sum w[seg(i, t)] * e(i, t) over all
+    n elements, seg(i, t) from `rois` (required then; tiled per view in the same way) by the definition of nef_loss_seg_args
+    (include/nefnet_hip.h).  No renormalisation: all ones is the flat mean.  The tuple keeps its length; the Standin terms, the rest_out /
+    rest_view term and the SSIM term are untouched.  []: `rois` is not looked at for it."""
     ssim_factor, ssim_rois = ssim_settings(cfg, rois)
+    seg_weights = seg_settings(cfg)
+    seg_rois = None
+    if seg_weights is not None:
+        if rois is None:
+            raise ValueError("SOLVER.seg_weights is set: the loss needs this batch's rois (losswrapper(..., rois=)); "
+                             "set SOLVER.seg_weights [] to switch the weights off")
+        check_seg_rows(predict.numel() // predict.shape[-1])
+        seg_rois = _rows_rois(rois, predict)
     if ssim_factor > 0 and predict.dim() == 4:
         check_view_rows(predict.shape[0], predict.shape[1])
         if ssim_rois is not None and ssim_rois.shape[0] == predict.shape[1]:
@@ -89,7 +148,8 @@ def losswrapper(predict, predict_shuffle_p, predict_shuffle_l, target, cfg, rest
         noise = noise.detach().to(torch.float32).expand_as(predict).contiguous()
     if ssim_rois is not None:
         ssim_rois = ssim_rois.detach().to(torch.int64).contiguous()
-    L4 = _LossFn.apply(predict, predict_shuffle_p, predict_shuffle_l, target, factors, reg_l2, use_mask, noise, ssim_factor, ssim_rois)
+    L4 = _LossFn.apply(predict, predict_shuffle_p, predict_shuffle_l, target, factors, reg_l2, use_mask, noise, ssim_factor, ssim_rois,
+                       seg_weights, seg_rois)
     result = (L4[0], L4[1].detach(), L4[2].detach(), L4[3].detach())
     tail = (L4[4].detach(),) if ssim_factor > 0 else ()
     if rest_out is not None and rest_view is not None:
@@ -108,4 +168,4 @@ class MSELead(torch.nn.Module):
         target = target.to(torch.float32).expand_as(input)
         # element [0] (the total) is the one _LossFn back-propagates through; with factors (0, 0, 1) and only the
         # reconstruction term enabled it IS the MSE (element [3] carries the same number but no gradient)
-        return _LossFn.apply(input, input, input, target, (0.0, 0.0, 1.0), True, 4, None, 0.0, None)[0]
+        return _LossFn.apply(input, input, input, target, (0.0, 0.0, 1.0), True, 4, None, 0.0, None, None, None)[0]

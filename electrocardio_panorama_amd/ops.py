@@ -1815,6 +1815,73 @@ def augment(x, rois, aug, seed=0, seed_dev=None, out=None):
     return y
 
 
+LOSS_SEG_TILE = 1024      # NEF_LOSS_SEG_TILE (include/nefnet_hip.h): positions per block of the two segment-weight kernels
+LOSS_SEG_MAX_ROWS = 65535  # the rows are a grid's y extent
+
+
+def _seg_weights(weights):
+    """SOLVER.seg_weights as the seven floats of nef_loss_seg_args.w: [P, PR, QRS, ST, T, TP, pad], finite and >= 0."""
+    w = tuple(float(x) for x in weights)
+    if len(w) != N_SEG:
+        raise ValueError(f"segment weights {w}: {N_SEG} numbers are needed [P, PR, QRS, ST, T, TP, pad]")
+    if not all(0.0 <= x < float("inf") for x in w):
+        raise ValueError(f"Invalid segment weights: {w} (finite numbers >= 0)")
+    return (C.c_float * N_SEG)(*w)
+
+
+def _seg_rows(t, rois, what):
+    """(B, L) of a [B, 1, L] / [Q, B, 1, L] / [B, L] tensor whose rows `rois` int64 [B, 7, 2] describes."""
+    _chk(t)
+    if t.dim() < 2:
+        raise ValueError(f"{what} {tuple(t.shape)} must hold [B, 1, L] rows")
+    Ln = t.shape[-1]
+    B = t.numel() // Ln
+    if _chk(rois, torch.int64).dim() != 3 or tuple(rois.shape) != (B, N_SEG, 2):
+        raise ValueError(f"rois {tuple(rois.shape)} is not [{B}, {N_SEG}, 2]")
+    if Ln % 4:
+        raise ValueError(f"{what} {tuple(t.shape)}: the row length must be a multiple of 4")
+    if B > LOSS_SEG_MAX_ROWS:
+        raise ValueError(f"{what} {tuple(t.shape)}: {B} rows is more than the {LOSS_SEG_MAX_ROWS} the segment kernels take")
+    return B, Ln
+
+
+def loss_seg_fwd(pred, target, losses, weights, f2, reg_l2, rois, noise=None):
+    """The wave-segment weighted reconstruction term behind loss_fwd (nef_loss_seg_fwd, include/nefnet_hip.h): losses[3] =
+    f2 * (1/n) * sum w[seg(i, t)] * e(i, t) over all n = B * L elements, e as loss_fwd forms it at pred (+ noise), and losses[0] =
+    (losses[1] + losses[2]) + losses[3].  `losses`: the row loss_fwd(out=) has written (4 elements, or 5 with the SSIM term, whose
+    launches come behind this one).  `weights`: [P, PR, QRS, ST, T, TP, pad].  Two launches, capturable."""
+    L = _lib.load()
+    B, Ln = _seg_rows(pred, rois, "prediction")
+    if _chk(target).numel() != pred.numel():
+        raise ValueError(f"prediction {tuple(pred.shape)} and target {tuple(target.shape)} must hold the same rows")
+    if noise is not None and _chk(noise).numel() != pred.numel():
+        raise ValueError(f"noise {tuple(noise.shape)} does not have the prediction's {tuple(pred.shape)} elements")
+    _chk(losses)
+    assert losses.numel() in (4, 5), losses.shape
+    n = L.nef_loss_seg_ws_bytes(B, Ln)
+    ws = workspace(n, pred.device)
+    ev = _hbm("loss_seg_fwd", pred, target, noise)
+    A = _lib.LossSegArgs(pred=_p(pred), target=_p(target), noise=_p(noise), rois=_p(rois), losses=_p(losses), g_pred=None, ws=_p(ws),
+                         ws_bytes=n, B=B, L=Ln, reg_l2=int(bool(reg_l2)), f2=float(f2), w=_seg_weights(weights))
+    _lib.check(L.nef_loss_seg_fwd(C.byref(A), _stream()), "nef_loss_seg_fwd")
+    _done(ev)
+    return losses
+
+
+def loss_seg_bwd(g_pred, weights, rois):
+    """g_pred[i, t] = w[seg(i, t)] * g_pred[i, t] in place behind loss_bwd and in front of loss_ssim_bwd (nef_loss_seg_bwd): `g_pred` is
+    loss_bwd's first gradient, the first third of its [3B, 1, L] buffer.  One fp32 multiply per element; one launch, capturable, no
+    state."""
+    L = _lib.load()
+    B, Ln = _seg_rows(g_pred, rois, "g_pred")
+    ev = _hbm("loss_seg_bwd", g_pred, g_pred)
+    A = _lib.LossSegArgs(pred=None, target=None, noise=None, rois=_p(rois), losses=None, g_pred=_p(g_pred), ws=None, ws_bytes=0,
+                         B=B, L=Ln, reg_l2=0, f2=0.0, w=_seg_weights(weights))
+    _lib.check(L.nef_loss_seg_bwd(C.byref(A), _stream()), "nef_loss_seg_bwd")
+    _done(ev)
+    return g_pred
+
+
 def flatten_into(tensors, out, accumulate=False, accumulate_dev=None):
     """out[:] = concatenation of `tensors` (contiguous fp32, flattened), ONE launch per 64 tensors (nef_flatten; was torch.cat).
     `accumulate`: out[:] += the concatenation instead (gradient accumulation: one fp32 add per element, no atomics).  `accumulate_dev`: a
@@ -1909,6 +1976,25 @@ def view_metrics(pred, gt, rois=None):
     ssim = torch.empty(B, Q, device=pred.device, dtype=torch.float64)
     _lib.check(L.nef_view_metrics(_p(pred), _p(gt), _p(rois), _p(psnr), _p(ssim), B, Q, Ln, _stream()), "nef_view_metrics")
     return psnr, ssim
+
+
+def view_seg_metrics(pred, gt, rois):
+    """Per-row, per-wave-segment squared error of pred vs gt [B, Q, L] (nef_view_seg_metrics): (se fp64 [B, Q, 7], cnt int32 [B, Q, 7]) --
+    the sum of squared differences over the positions of segment k of sample b (P, PR, QRS, ST, T, TP, pad; the definition of
+    nef_loss_seg_args) and their number.  rois: int64 [B, 7, 2]."""
+    L = _lib.load()
+    _chk(pred), _chk(gt)
+    if pred.dim() != 3 or gt.shape != pred.shape:
+        raise ValueError(f"prediction {tuple(pred.shape)} and ground truth {tuple(gt.shape)} must both be [B, Q, L]")
+    B, Q, Ln = pred.shape
+    if _chk(rois, torch.int64).dim() != 3 or tuple(rois.shape) != (B, N_SEG, 2):
+        raise ValueError(f"rois {tuple(rois.shape)} is not [{B}, {N_SEG}, 2]")
+    if Ln % 4:
+        raise ValueError(f"prediction {tuple(pred.shape)}: the row length must be a multiple of 4")
+    se = torch.empty(B, Q, N_SEG, device=pred.device, dtype=torch.float64)
+    cnt = torch.empty(B, Q, N_SEG, device=pred.device, dtype=torch.int32)
+    _lib.check(L.nef_view_seg_metrics(_p(pred), _p(gt), _p(rois), _p(se), _p(cnt), B, Q, Ln, _stream()), "nef_view_seg_metrics")
+    return se, cnt
 
 
 def sgd_momentum(p, g, buf, lr, mu, gscale, first_step, skip=None, lr_dev=None):

@@ -22,7 +22,11 @@ encoder pass -- the targets are drawn per step by `views.draw_views(seed, epoch,
 train-phase forward or as the first launch of the graphed step -- against the clean targets; with a corruption on, the step counters
 restart with every train epoch, so the step's seed is a function of (seed, epoch, batch index, rank) and a resumed epoch draws what the
 uninterrupted one drew.  `DATA.aug_eval`: `train` and `val` run the test phase a second time on one fixed corrupted test set and report
-psnr_gen_aug / psnr_reg_aug / ssim_gen_aug / ssim_reg_aug beside the clean numbers, which decide best_valid as before."""
+psnr_gen_aug / psnr_reg_aug / ssim_gen_aug / ssim_reg_aug beside the clean numbers, which decide best_valid as before.
+
+`SOLVER.seg_weights` / `SOLVER.seg_eval` (no counterpart in the reference): the loss takes the batch's rois and weighs the reconstruction
+term by wave segment; the test phase reports the PSNR of each of the six wave segments (`nef_view_seg_metrics`, one more launch per
+batch) as psnr_gen_seg_* / psnr_reg_seg_*, in `Solver.last_seg_psnr`."""
 import contextlib
 import json
 import os
@@ -113,6 +117,23 @@ class _HostSink:
         return [x for a in self.arrays() for x in a]
 
 
+def seg_psnr(se, cnt):
+    """PSNR per wave segment from nef_view_seg_metrics' tables of one batch: se, cnt [B, Q', 7] -> the mean over the (row, view) pairs
+    that own positions of the segment of 100 (se == 0) or 20 log10(1 / sqrt(se / cnt)), for the six segments in front of the padding.  NaN
+    where no pair has a position."""
+    out = []
+    for k in range(6):
+        s, c = se[..., k].reshape(-1), cnt[..., k].reshape(-1)
+        has = c > 0
+        s, c = s[has], c[has].astype(np.float64)
+        if s.size == 0:
+            out.append(float('nan'))
+            continue
+        rmse = np.sqrt(s / c)
+        out.append(float(np.mean(np.where(rmse == 0.0, 100.0, 20.0 * np.log10(1.0 / np.where(rmse == 0.0, 1.0, rmse))))))
+    return out
+
+
 def _is_main():
     return not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
 
@@ -130,6 +151,9 @@ class Solver:
         # DATA.aug_*: the train step corrupts its input leads on the device (augment.py); invalid keys are rejected here.  None = off
         self.augment = self.model.augment = augment.from_cfg(cfg)
         self.loss = build_loss(cfg)
+        # SOLVER.seg_eval: the test phase also fills last_seg_psnr = {'gen': [6 numbers], 'reg': [6 numbers]} (P, PR, QRS, ST, T, TP)
+        self.seg_eval = bool(cfg.SOLVER.get('seg_eval', False))
+        self.last_seg_psnr = None
         self._init_model_device()
         if self.desc != 'debug' and use_tensorboardx and _is_main():       # solver.py:23-26
             self.summary_writer = make_summary_writer(os.path.join(cfg.output_dir, 'tf_logs'))
@@ -163,6 +187,10 @@ class Solver:
             sched.total_updates = max_epochs * -(-len(dl_train) // getattr(optimizer, 'accum_steps', 1))
         if self.augment is not None:
             print(self.augment.describe())                # once: the DATA.aug_* keys that are on
+        seg_w = self._seg_weights()
+        if seg_w is not None:                             # once: SOLVER.seg_weights
+            from ..network.loss.losses import SEG_NAMES
+            print('seg_weights: ' + ', '.join('{} {:g}'.format(n, w) for n, w in zip(SEG_NAMES, seg_w)))
         for epoch in range(start_epoch, max_epochs):
             print('---------------------------------{}---{}-------------------------------------'.format(self.cfg.desc, epoch))
             if hasattr(getattr(dl_train, 'sampler', None), 'set_epoch'):
@@ -199,6 +227,11 @@ class Solver:
                         scalars += [float(np.mean(single[:, i, 0])), float(np.mean(single[:, i, 1]))]
                 msg += ', test_loss: {}'.format(float(te[0]))
                 msg += '\npsnr_gen: {}, psnr_reg: {}, ssim_gen:{}, ssim_reg:{}'.format(psnr_gen, psnr_reg, ssim_gen, ssim_reg)
+                if self.seg_eval:                 # SOLVER.seg_eval: the clean test phase's PSNR per wave segment
+                    seg_names, seg_vals = self._seg_scalars()
+                    scalars += seg_vals
+                    names += seg_names
+                    msg += '\n' + self._seg_message()
                 if self.augment is not None and self.augment.eval:
                     # DATA.aug_eval: the same weights on the fixed corrupted test set; best_valid stays on the clean psnr_gen
                     with optimizer.ema_weights() if self._ema_eval(optimizer) else contextlib.nullcontext():
@@ -250,6 +283,24 @@ class Solver:
         on = float(self.cfg.SOLVER.get('ema_decay', 0.0)) > 0 and bool(self.cfg.SOLVER.get('ema_eval', True))
         return on and (optimizer is None or getattr(optimizer, 'ema_decay', 0.0) > 0)
 
+    def _seg_weights(self):
+        """SOLVER.seg_weights as the loss reads it (a 7-tuple, or None for off) when the loss is losswrapper."""
+        if self.cfg.MODEL.loss != 'v1':
+            return None
+        from ..network.loss.losses import seg_settings
+        return seg_settings(self.cfg)
+
+    def _seg_scalars(self):
+        """(names, values) of last_seg_psnr: psnr_gen_seg_P .. psnr_gen_seg_TP, psnr_reg_seg_P .. psnr_reg_seg_TP."""
+        from ..network.loss.losses import SEG_NAMES
+        names = ['psnr_{}_seg_{}'.format(split, n) for split in ('gen', 'reg') for n in SEG_NAMES[:6]]
+        return names, list(self.last_seg_psnr['gen']) + list(self.last_seg_psnr['reg'])
+
+    def _seg_message(self):
+        from ..network.loss.losses import SEG_NAMES
+        return '\n'.join('psnr_{}_seg: '.format(split) + ', '.join('{} {}'.format(n, v) for n, v in zip(SEG_NAMES, self.last_seg_psnr[split]))
+                         for split in ('gen', 'reg'))
+
     def _aug_eval(self, dl_test):
         """DATA.aug_eval: (psnr_gen, psnr_reg, ssim_gen, ssim_reg) of the test phase on corrupted inputs -- batch i under
         augment.eval_seed(cfg.seed, i, rank), so every epoch and every resumed run judges the same corrupted test set and no seed is a
@@ -284,6 +335,8 @@ class Solver:
             mertics_all = self.run_one_epoch(dl_test, phase='test', collect_views=False)[4]
         psnr_gen, psnr_reg, ssim_gen, ssim_reg = (float(v) for v in np.mean(mertics_all, axis=0))
         print('psnr_gen:{}, psnr_reg:{}, ssim_gen:{}, ssim_reg:{}'.format(psnr_gen, psnr_reg, ssim_gen, ssim_reg))
+        if self.seg_eval:
+            print(self._seg_message())
         if self.augment is not None and self.augment.eval:
             print('psnr_gen_aug:{}, psnr_reg_aug:{}, ssim_gen_aug:{}, ssim_reg_aug:{}'.format(*self._aug_eval(dl_test)))
         return psnr_gen, psnr_reg, ssim_gen, ssim_reg
@@ -309,8 +362,10 @@ class Solver:
         return gen_num, whole
 
     def _loss_rois(self, rois):
-        """`rois=` for the loss when SOLVER.ssim_factor is on and the loss takes it (losswrapper); nothing otherwise."""
-        if self.cfg.MODEL.loss == 'v1' and float(self.cfg.SOLVER.get('ssim_factor', 0.0)) > 0:
+        """`rois=` for the loss when SOLVER.ssim_factor or SOLVER.seg_weights is on and the loss takes it (losswrapper); nothing
+        otherwise."""
+        if self.cfg.MODEL.loss == 'v1' and (float(self.cfg.SOLVER.get('ssim_factor', 0.0)) > 0 or
+                                            len(self.cfg.SOLVER.get('seg_weights', None) or ()) > 0):
             return {'rois': rois}
         return {}
 
@@ -388,6 +443,7 @@ class Solver:
             raise ValueError('phase param not found.')
         keep = self.collect_views if collect_views is None else bool(collect_views)
         losses_s, pred_s, gt_s, in_s, rest_s, rois_s, psnr_s, ssim_s = (_HostSink() for _ in range(8))
+        seg_s = (_HostSink(), _HostSink()) if phase == 'test' and self.seg_eval and not aug_eval else None      # (se, cnt) per clean batch
         gen_num, whole = self._gen_num() if phase == 'test' else (0, True)
         # gradient-norm clipping (SOLVER.clip_grad_norm): [norm, coefficient] of every train step travel like the losses
         clip_s = _HostSink() if phase == 'train' and getattr(optim, 'max_grad_norm', 0.0) > 0 else None
@@ -454,6 +510,10 @@ class Solver:
                 ps, ss = ops.view_metrics(rest_out.contiguous(), rest_view, None if whole else rois.contiguous())
                 psnr_s.add(ps)
                 ssim_s.add(ss)
+                if seg_s is not None:
+                    se, cnt = ops.view_seg_metrics(rest_out.contiguous(), rest_view, rois.to(torch.int64).contiguous())
+                    seg_s[0].add(se)
+                    seg_s[1].add(cnt)
                 if keep:
                     pred_s.add(rest_out)                           # solver.py:182
                     rest_s.add(rest_view)
@@ -510,4 +570,16 @@ class Solver:
                 mertics_gen_singlelead.append([[float(ps[:, Q - gen_num + i].mean()), float(ss[:, Q - gen_num + i].mean())]
                                                for i in range(gen_num)])
             mertics_all.append([pg, pr, sg, sr])
+        if seg_s is not None:
+            # per batch the mean over the split's (row, view) pairs that own positions of the segment, then the mean over batches as
+            # psnr_gen / psnr_reg are formed (a batch without any such pair is left out)
+            per_batch = {'gen': [], 'reg': []}
+            for se, cnt in zip(seg_s[0].arrays(), seg_s[1].arrays()):
+                per_batch['gen'].append(seg_psnr(se, cnt) if whole else seg_psnr(se[:, -gen_num:], cnt[:, -gen_num:]))
+                per_batch['reg'].append(seg_psnr(se, cnt) if whole else seg_psnr(se[:, :-gen_num], cnt[:, :-gen_num]))
+            self.last_seg_psnr = {}
+            for split, rows in per_batch.items():
+                a = np.asarray(rows, dtype=np.float64).reshape(-1, 6)
+                ok = ~np.isnan(a)
+                self.last_seg_psnr[split] = [float(a[ok[:, k], k].mean()) if ok[:, k].any() else float('nan') for k in range(6)]
         return losses, rest_s.rows(), pred_s.rows(), in_s.rows(), mertics_all, rois_s.rows(), mertics_gen_singlelead

@@ -34,7 +34,7 @@ extern "C" {
 typedef void* nef_stream_t;
 
 /* ABI version of this header; bumped on any signature change. */
-int nef_abi_version(void);   /* 22 (+ nef_flatten_acc, nef_lr_sched / nef_lr_sched_args_bytes, nef_loss_ssim_fwd / nef_loss_ssim_bwd / nef_loss_ssim_ws_bytes / nef_loss_ssim_args_bytes: additions only, the number stays; a binding finds a library without them by the missing symbol.  Weight packing is ONE entry, nef_pack_weights(nef_pack_desc*, n), + nef_pack_bytes(nef_pack_desc*) for the size of any operand.  ABI <= 21 had nef_pack_weight, nef_pack_weight_wino, nef_pack_weight_wino4, nef_pack_weight_h2 and nef_pack_weight_h2_bytes: each is one descriptor with wino = 0 / 1 / 2 / 3); 21 (BatchNorm backward is ONE entry on a nef_bn_bwd_args struct, + nef_bn_bwd_args_bytes; nef_mix_bwd takes `up` / `shared` flags; nef_outconv_fwd / nef_outconv_bwd_weight take the prologue arguments.  ABI <= 20 had nef_bn_relu_bwd_phase_major, nef_bn_relu_bwd_up, nef_bn_relu_bwd_combine3, nef_bn_relu_bwd_combine3_phase_major, nef_bn_relu_bwd_outconv, nef_bn_bwd_outconv_ws_bytes, nef_mix_bwd_up, nef_mix_bwd_shared, nef_mix_bwd_shared_up, nef_outconv_fwd_pro and nef_outconv_bwd_weight_pro); 20 (the weight gradient is ONE entry, nef_conv_bwd_weight(nef_bww_args*), + nef_bww_args_bytes; its _pro, _wino4, _h2 and _h2_ws_bytes variants are gone); 19 (+ nef_adam, nef_h2_tail_census, nef_bwd_weight_clamp_ends: additions only; the kernel-form option entry points of 16 and nef_upsample2_aff_fwd are gone; + nef_debug_spin_us); 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + kernel-form option entry points); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + the split-fp16 weight gradient, now form 3); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, the transposed F(3,4) / F(4,4) entry, now form 4, covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
+int nef_abi_version(void);   /* 22 (+ nef_flatten_acc, nef_lr_sched / nef_lr_sched_args_bytes, nef_loss_ssim_fwd / nef_loss_ssim_bwd / nef_loss_ssim_ws_bytes / nef_loss_ssim_args_bytes, nef_loss_seg_fwd / nef_loss_seg_bwd / nef_loss_seg_ws_bytes / nef_loss_seg_args_bytes / nef_view_seg_metrics: additions only, the number stays; a binding finds a library without them by the missing symbol.  Weight packing is ONE entry, nef_pack_weights(nef_pack_desc*, n), + nef_pack_bytes(nef_pack_desc*) for the size of any operand.  ABI <= 21 had nef_pack_weight, nef_pack_weight_wino, nef_pack_weight_wino4, nef_pack_weight_h2 and nef_pack_weight_h2_bytes: each is one descriptor with wino = 0 / 1 / 2 / 3); 21 (BatchNorm backward is ONE entry on a nef_bn_bwd_args struct, + nef_bn_bwd_args_bytes; nef_mix_bwd takes `up` / `shared` flags; nef_outconv_fwd / nef_outconv_bwd_weight take the prologue arguments.  ABI <= 20 had nef_bn_relu_bwd_phase_major, nef_bn_relu_bwd_up, nef_bn_relu_bwd_combine3, nef_bn_relu_bwd_combine3_phase_major, nef_bn_relu_bwd_outconv, nef_bn_bwd_outconv_ws_bytes, nef_mix_bwd_up, nef_mix_bwd_shared, nef_mix_bwd_shared_up, nef_outconv_fwd_pro and nef_outconv_bwd_weight_pro); 20 (the weight gradient is ONE entry, nef_conv_bwd_weight(nef_bww_args*), + nef_bww_args_bytes; its _pro, _wino4, _h2 and _h2_ws_bytes variants are gone); 19 (+ nef_adam, nef_h2_tail_census, nef_bwd_weight_clamp_ends: additions only; the kernel-form option entry points of 16 and nef_upsample2_aff_fwd are gone; + nef_debug_spin_us); 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + kernel-form option entry points); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + the split-fp16 weight gradient, now form 3); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, the transposed F(3,4) / F(4,4) entry, now form 4, covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
 
 /* Diagnostics: `wgs` workgroups busy for `us` microseconds on `stream` (a stand-in for a collective's time on the chip:
  * parallel.DryCollective, bench.py --dry-collective).  0 <= us <= 50000, 1 <= wgs <= 64. */
@@ -594,6 +594,53 @@ int nef_loss_ssim_bwd(const nef_loss_ssim_args* a, nef_stream_t stream);
 size_t nef_loss_ssim_ws_bytes(int B, int L);
 /* sizeof(nef_loss_ssim_args) as the library was built. */
 size_t nef_loss_ssim_args_bytes(void);
+
+/* Wave-segment weights on the reconstruction term (cfg.SOLVER.seg_weights; no counterpart in the reference) and the per-segment squared
+ * error of the test phase (cfg.SOLVER.seg_eval).  The segment of position t of row i -- ONE definition for the three entries below:
+ *   end_i = clamp(rois[i, 6, 0], 0, L)                        (the row end of nef_loss_ssim_* and nef_view_metrics);
+ *   t >= end_i: segment 6 (pad);  otherwise: #{k in 1..5 : rois[i, k, 0] <= t}, a value in 0..5 (P, PR, QRS, ST, T, TP).
+ * Only the six start points rois[i, 1..6, 0] are read: the rule is total for any int64 content (negative, beyond L, non-monotonic, empty
+ * segments) and equals "the k with rois[i, k, 0] <= t < rois[i, k, 1]" for contiguous rois.
+ * fwd (two launches behind nef_loss_*_fwd on the same stream): with e(i, t) the element of the reconstruction term as nef_loss_fwd forms
+ *   it in fp32 -- |d| (reg_l2 0) or d * d, d = (pred (+ noise)) - target --, S = sum_{i, t} (double)w[seg(i, t)] * (double)e(i, t): one
+ *   fp64 partial per (row, tile of NEF_LOSS_SEG_TILE positions) in ws, a one-block finish that adds them in a fixed order (no atomics:
+ *   the same bits eagerly, under hipGraph replay and on every rank), then losses[3] = (float)(S / (B L)) * f2 and
+ *   losses[0] = (losses[1] + losses[2]) + losses[3], the association of nef_loss_fwd.  No renormalisation: all weights 1 is the flat
+ *   mean.  losses[1], losses[2] and any element behind [3] keep their bits.  g_pred is not read.
+ * bwd (one launch behind nef_loss_*_bwd, in front of nef_loss_ssim_bwd): g_pred[i, t] = w[seg(i, t)] * g_pred[i, t] in place, one fp32
+ *   multiply and one writer per element.  Reads rois and g_pred only; keeps no state.
+ * args, rois, pred / target / losses (fwd), g_pred (bwd) NULL: NEF_E_NULL; B or L <= 0, B > 65535 (the rows are a grid's y extent),
+ * L % 4 != 0, a negative, infinite or NaN weight: NEF_E_SHAPE; fwd: ws_bytes below nef_loss_seg_ws_bytes(B, L): NEF_E_WORKSPACE, then ws
+ * NULL: NEF_E_NULL; a tensor not 16-byte aligned: NEF_E_UNSUPPORTED.  Every check sits in front of the launches.  Capturable: nothing is
+ * read by the host, nothing is allocated. */
+#define NEF_LOSS_SEG_TILE 1024
+typedef struct nef_loss_seg_args {
+    const float* pred;      /* fwd: [B, L] */
+    const float* target;    /* fwd: [B, L] */
+    const float* noise;     /* fwd: NULL, or [B, L] */
+    const int64_t* rois;    /* [B, 7, 2] */
+    float* losses;          /* fwd: the loss row, elements [1], [2] written by nef_loss_*_fwd */
+    float* g_pred;          /* bwd: [B, L], scaled in place */
+    void* ws;               /* fwd */
+    size_t ws_bytes;        /* fwd */
+    int32_t B;              /* rows, 1 .. 65535 */
+    int32_t L;              /* row length, a multiple of 4 */
+    int32_t reg_l2;         /* fwd: 0 |d|, otherwise d * d */
+    float f2;               /* fwd: the reconstruction term's factor */
+    float w[7];             /* P, PR, QRS, ST, T, TP, pad: finite, >= 0 */
+    int32_t reserved0;      /* 0 */
+} nef_loss_seg_args;
+int nef_loss_seg_fwd(const nef_loss_seg_args* a, nef_stream_t stream);
+int nef_loss_seg_bwd(const nef_loss_seg_args* a, nef_stream_t stream);
+size_t nef_loss_seg_ws_bytes(int B, int L);
+/* sizeof(nef_loss_seg_args) as the library was built. */
+size_t nef_loss_seg_args_bytes(void);
+/* Per-segment squared error of the test phase, one block per (sample, view) row as nef_view_metrics: pred, gt fp32 [B][Q][L], rois
+ * [B, 7, 2] (required); se fp64 [B][Q][7]: the sum of ((double)x - (double)y)^2 over the positions of segment k of sample b (the
+ * definition above); cnt int32 [B][Q][7]: their number.  All seven bins are fixed-order block sums, no atomics.  A pointer NULL:
+ * NEF_E_NULL; B, Q or L <= 0, B > 65535, L % 4 != 0: NEF_E_SHAPE; pred or gt not 16-byte aligned: NEF_E_UNSUPPORTED. */
+int nef_view_seg_metrics(const float* pred, const float* gt, const int64_t* rois, double* se, int32_t* cnt, int B, int Q, int L,
+                         nef_stream_t stream);
 
 /* Input-lead augmentation of the train step (cfg.DATA.aug_*; no counterpart in the reference, whose only augmentation is the host-side
  * angle jitter): y = a corrupted copy of the input leads x [B, V, L]; x is never written.  Every draw comes from the counter RNG of the
