@@ -98,6 +98,12 @@ class LossSegArgs(C.Structure):
                 ("B", i32), ("L", i32), ("reg_l2", i32), ("f2", f32), ("w", f32 * 7), ("reserved0", i32)]
 
 
+class LossSlopeArgs(C.Structure):
+    """Mirror of `nef_loss_slope_args` (include/nefnet_hip.h)."""
+    _fields_ = [("pred", p), ("target", p), ("noise", p), ("rois", p), ("losses", p), ("ws", p), ("ws_bytes", sz), ("gscale", p),
+                ("g_pred", p), ("B", i32), ("L", i32), ("factor", f32), ("l2", i32), ("slot", i32), ("reserved0", i32)]
+
+
 class AugmentArgs(C.Structure):
     """Mirror of `nef_augment_args` (include/nefnet_hip.h)."""
     _fields_ = [("x", p), ("rois", p), ("y", p), ("seed_dev", p), ("seed", C.c_uint64),
@@ -196,6 +202,10 @@ SIGNATURES = {
     "nef_loss_seg_bwd": (i32, [C.POINTER(LossSegArgs), p]),
     "nef_loss_seg_ws_bytes": (sz, [i32, i32]),
     "nef_loss_seg_args_bytes": (sz, []),
+    "nef_loss_slope_fwd": (i32, [C.POINTER(LossSlopeArgs), p]),
+    "nef_loss_slope_bwd": (i32, [C.POINTER(LossSlopeArgs), p]),
+    "nef_loss_slope_ws_bytes": (sz, [i32, i32]),
+    "nef_loss_slope_args_bytes": (sz, []),
     "nef_augment": (i32, [C.POINTER(AugmentArgs), p]),
     "nef_augment_args_bytes": (sz, []),
     "nef_sgd_momentum": (i32, [p, p, p, i64, f32, f32, f32, i32, p, p, p, p]),
@@ -226,6 +236,7 @@ SIGNATURES = {
     "nef_poly_bwd_edge": (i32, [p, p, p, i32, i32, i32, i32, i32, p, p, p, p, p, i32, p, i32, i32, p]),
     "nef_view_metrics": (i32, [p, p, p, p, p, i32, i32, i32, p]),
     "nef_view_seg_metrics": (i32, [p, p, p, p, p, i32, i32, i32, p]),
+    "nef_view_slope_metrics": (i32, [p, p, p, p, p, i32, i32, i32, p]),
     "nef_pano_h_from_f32": (i32, [p, p, i32, i32, i32, p]),
     "nef_pano_h_pack_weight": (i32, [p, p, i32, i32, p]),
     "nef_pano_h_conv": (i32, [p, p, p, p, p, i32, i32, i32, i32, i32, i32, i32, i64, i64, p]),
@@ -270,6 +281,7 @@ def load():
                                ("nef_lr_sched_args", lib.nef_lr_sched_args_bytes(), LrSchedArgs),
                                ("nef_loss_ssim_args", lib.nef_loss_ssim_args_bytes(), LossSsimArgs),
                                ("nef_loss_seg_args", lib.nef_loss_seg_args_bytes(), LossSegArgs),
+                               ("nef_loss_slope_args", lib.nef_loss_slope_args_bytes(), LossSlopeArgs),
                                ("nef_augment_args", lib.nef_augment_args_bytes(), AugmentArgs)):
         if size != C.sizeof(mirror):
             raise NefLibraryError(f"{LIB_PATH}: {name} is {size} bytes, the binding mirrors {C.sizeof(mirror)}; rebuild with "

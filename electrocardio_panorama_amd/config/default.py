@@ -142,6 +142,20 @@ _DEFAULTS = {
         # True: the test phase also reports the PSNR of each wave segment (nef_view_seg_metrics beside nef_view_metrics), logged as
         # psnr_gen_seg_{P,PR,QRS,ST,T,TP} / psnr_reg_seg_* with the view split of psnr_gen / psnr_reg.  False: no launch, no buffer
         "seg_eval": False,
+        # a slope (first-difference) term in the training loss, on the device (nef_loss_slope_fwd / nef_loss_slope_bwd behind the loss, segment
+        # and SSIM launches, in the eager and the graphed step): loss += slope_factor * mean over rows of the row's mean |d| (or d^2),
+        # d = (x[t + 1] - x[t]) - (y[t + 1] - y[t]) at x = prediction (+ DATA.noise), y = target; the loss tuple and the graphed step's loss
+        # row gain the term as their LAST element (behind the SSIM term when both are on), logged as train_loss_slope / test_loss_slope.
+        # Independent of seg_weights, loss_using and loss_factor.  0 = off: the rows, launches, graphs and bits are what they were before the
+        # key existed; a negative value is rejected where the loss is built
+        "slope_factor": 0.0,
+        # 'l1_loss': |d|, 'l2_loss': d^2; anything else is rejected where the loss is built
+        "slope_loss": "l1_loss",
+        # True: every row ends at rois[i, -1, 0] as in the test phase's metrics (a row with fewer than 2 samples is left out); False: whole rows
+        "slope_crop": True,
+        # True: the test phase also reports the PSNR of the first differences (nef_view_slope_metrics beside nef_view_metrics), logged as
+        # psnr_slope_gen / psnr_slope_reg with the view split of psnr_gen / psnr_reg; best_valid stays on psnr_gen.  False: no launch, no buffer
+        "slope_eval": False,
     },
 }
 

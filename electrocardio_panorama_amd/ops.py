@@ -1882,6 +1882,69 @@ def loss_seg_bwd(g_pred, weights, rois):
     return g_pred
 
 
+LOSS_SLOPE_TILE = 1024     # NEF_LOSS_SLOPE_TILE (include/nefnet_hip.h): difference starts / positions per block of the slope kernels
+LOSS_SLOPE_MAX_ROWS = 65535  # the rows are a grid's y extent
+
+
+def _slope_args(pred, target, factor, rois, noise):
+    """The checks and the shape the two slope entries share: pred / target [B, 1, L] (or [Q, B, 1, L], [B, L]; any L >= 1), rois None or
+    int64 [B, 7, 2], noise None or pred's elements."""
+    _chk(pred), _chk(target)
+    if pred.dim() < 2 or target.numel() != pred.numel() or pred.numel() == 0:
+        raise ValueError(f"prediction {tuple(pred.shape)} and target {tuple(target.shape)} must hold the same [B, 1, L] rows")
+    Ln = pred.shape[-1]
+    B = pred.numel() // Ln
+    if B > LOSS_SLOPE_MAX_ROWS:
+        raise ValueError(f"prediction {tuple(pred.shape)}: {B} rows is more than the {LOSS_SLOPE_MAX_ROWS} the slope kernels take")
+    if noise is not None and _chk(noise).numel() != pred.numel():
+        raise ValueError(f"noise {tuple(noise.shape)} does not have the prediction's {tuple(pred.shape)} elements")
+    if rois is not None and (_chk(rois, torch.int64).dim() != 3 or tuple(rois.shape) != (B, N_SEG, 2)):
+        raise ValueError(f"rois {tuple(rois.shape)} is not [{B}, {N_SEG}, 2]")
+    if not float(factor) >= 0.0:
+        raise ValueError(f"Invalid slope factor: {factor}")
+    return B, Ln
+
+
+def loss_slope_fwd(pred, target, losses, factor, l2, rois=None, noise=None):
+    """The slope term of the training loss behind loss_fwd, loss_seg_fwd and loss_ssim_fwd (nef_loss_slope_fwd, include/nefnet_hip.h):
+    losses[-1] = factor * mean over the rows with a difference of the row's mean |d| (`l2` False) or d^2, d(i, t) = (x[t + 1] - x[t]) -
+    (y[t + 1] - y[t]) at x = pred (+ noise), y = target, t in [0, rois[i, -1, 0] - 1) (whole rows with rois None), and losses[0] +=
+    losses[-1].  `losses`: the row whose front loss_fwd(out=) has written -- 5 elements (the term is losses[4]), or 6 with the SSIM term in
+    losses[4] (the term is losses[5]).  Two launches, capturable."""
+    L = _lib.load()
+    B, Ln = _slope_args(pred, target, factor, rois, noise)
+    _chk(losses)
+    if losses.numel() not in (5, 6):
+        raise ValueError(f"losses {tuple(losses.shape)}: the slope term takes a 5-element row, or a 6-element one behind the SSIM term")
+    n = L.nef_loss_slope_ws_bytes(B, Ln)
+    ws = workspace(n, pred.device)
+    ev = _hbm("loss_slope_fwd", pred, target, noise)
+    A = _lib.LossSlopeArgs(pred=_p(pred), target=_p(target), noise=_p(noise), rois=_p(rois), losses=_p(losses), ws=_p(ws), ws_bytes=n,
+                           gscale=None, g_pred=None, B=B, L=Ln, factor=float(factor), l2=int(bool(l2)), slot=losses.numel() - 1)
+    _lib.check(L.nef_loss_slope_fwd(C.byref(A), _stream()), "nef_loss_slope_fwd")
+    _done(ev)
+    return losses
+
+
+def loss_slope_bwd(pred, target, g_pred, factor, l2, rois=None, noise=None, gscale=None):
+    """g_pred += gscale * d(slope term) / d pred behind loss_bwd, loss_seg_bwd and loss_ssim_bwd (nef_loss_slope_bwd): `g_pred` is
+    loss_bwd's first gradient, the first third of its [3B, 1, L] buffer.  Positions at or behind a row's end and rows without a difference
+    keep their bits.  `gscale`: None (1) or loss_bwd's device word.  One launch, capturable, no state: the row count is re-derived from
+    `rois` on the device."""
+    L = _lib.load()
+    B, Ln = _slope_args(pred, target, factor, rois, noise)
+    if _chk(g_pred).numel() != pred.numel():
+        raise ValueError(f"g_pred {tuple(g_pred.shape)} does not have the prediction's {tuple(pred.shape)} elements")
+    if gscale is not None:
+        _chk(gscale)
+    ev = _hbm("loss_slope_bwd", pred, target, noise, g_pred, g_pred)
+    A = _lib.LossSlopeArgs(pred=_p(pred), target=_p(target), noise=_p(noise), rois=_p(rois), losses=None, ws=None, ws_bytes=0,
+                           gscale=_p(gscale), g_pred=_p(g_pred), B=B, L=Ln, factor=float(factor), l2=int(bool(l2)), slot=4)
+    _lib.check(L.nef_loss_slope_bwd(C.byref(A), _stream()), "nef_loss_slope_bwd")
+    _done(ev)
+    return g_pred
+
+
 def flatten_into(tensors, out, accumulate=False, accumulate_dev=None):
     """out[:] = concatenation of `tensors` (contiguous fp32, flattened), ONE launch per 64 tensors (nef_flatten; was torch.cat).
     `accumulate`: out[:] += the concatenation instead (gradient accumulation: one fp32 add per element, no atomics).  `accumulate_dev`: a
@@ -1994,6 +2057,23 @@ def view_seg_metrics(pred, gt, rois):
     se = torch.empty(B, Q, N_SEG, device=pred.device, dtype=torch.float64)
     cnt = torch.empty(B, Q, N_SEG, device=pred.device, dtype=torch.int32)
     _lib.check(L.nef_view_seg_metrics(_p(pred), _p(gt), _p(rois), _p(se), _p(cnt), B, Q, Ln, _stream()), "nef_view_seg_metrics")
+    return se, cnt
+
+
+def view_slope_metrics(pred, gt, rois=None):
+    """Per-row squared slope error of pred vs gt [B, Q, L] (nef_view_slope_metrics): (se fp64 [B, Q], cnt int32 [B, Q]) -- the sum of
+    ((x[t + 1] - x[t]) - (y[t + 1] - y[t]))^2 over t in [0, rois[b, -1, 0] - 1) (whole rows with rois None) and the number of those
+    differences.  rois: None or int64 [B, 7, 2].  Any L >= 1."""
+    L = _lib.load()
+    _chk(pred), _chk(gt)
+    if pred.dim() != 3 or gt.shape != pred.shape or pred.numel() == 0:
+        raise ValueError(f"prediction {tuple(pred.shape)} and ground truth {tuple(gt.shape)} must both be [B, Q, L]")
+    B, Q, Ln = pred.shape
+    if rois is not None and (_chk(rois, torch.int64).dim() != 3 or tuple(rois.shape) != (B, N_SEG, 2)):
+        raise ValueError(f"rois {tuple(rois.shape)} is not [{B}, {N_SEG}, 2]")
+    se = torch.empty(B, Q, device=pred.device, dtype=torch.float64)
+    cnt = torch.empty(B, Q, device=pred.device, dtype=torch.int32)
+    _lib.check(L.nef_view_slope_metrics(_p(pred), _p(gt), _p(rois), _p(se), _p(cnt), B, Q, Ln, _stream()), "nef_view_slope_metrics")
     return se, cnt
 
 

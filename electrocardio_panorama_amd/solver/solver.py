@@ -26,7 +26,10 @@ psnr_gen_aug / psnr_reg_aug / ssim_gen_aug / ssim_reg_aug beside the clean numbe
 
 `SOLVER.seg_weights` / `SOLVER.seg_eval` (no counterpart in the reference): the loss takes the batch's rois and weighs the reconstruction
 term by wave segment; the test phase reports the PSNR of each of the six wave segments (`nef_view_seg_metrics`, one more launch per
-batch) as psnr_gen_seg_* / psnr_reg_seg_*, in `Solver.last_seg_psnr`."""
+batch) as psnr_gen_seg_* / psnr_reg_seg_*, in `Solver.last_seg_psnr`.
+`SOLVER.slope_factor` / `SOLVER.slope_eval` (no counterpart in the reference): the loss gains the first-difference term, logged as
+train_loss_slope / test_loss_slope; the test phase reports the PSNR of the first differences (`nef_view_slope_metrics`, one more launch per
+batch) as psnr_slope_gen / psnr_slope_reg, in `Solver.last_slope_psnr`."""
 import contextlib
 import json
 import os
@@ -134,6 +137,18 @@ def seg_psnr(se, cnt):
     return out
 
 
+def slope_psnr(se, cnt):
+    """PSNR of the first differences from nef_view_slope_metrics' tables of one batch: se, cnt [B, Q'] -> the mean over the (row, view)
+    pairs that have a difference of 100 (se == 0) or 20 log10(1 / sqrt(se / cnt)).  NaN where no pair has one."""
+    s, c = np.asarray(se, dtype=np.float64).reshape(-1), np.asarray(cnt).reshape(-1)
+    has = c > 0
+    s, c = s[has], c[has].astype(np.float64)
+    if s.size == 0:
+        return float('nan')
+    rmse = np.sqrt(s / c)
+    return float(np.mean(np.where(rmse == 0.0, 100.0, 20.0 * np.log10(1.0 / np.where(rmse == 0.0, 1.0, rmse)))))
+
+
 def _is_main():
     return not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
 
@@ -154,6 +169,9 @@ class Solver:
         # SOLVER.seg_eval: the test phase also fills last_seg_psnr = {'gen': [6 numbers], 'reg': [6 numbers]} (P, PR, QRS, ST, T, TP)
         self.seg_eval = bool(cfg.SOLVER.get('seg_eval', False))
         self.last_seg_psnr = None
+        # SOLVER.slope_eval: the test phase also fills last_slope_psnr = {'gen': number, 'reg': number}
+        self.slope_eval = bool(cfg.SOLVER.get('slope_eval', False))
+        self.last_slope_psnr = None
         self._init_model_device()
         if self.desc != 'debug' and use_tensorboardx and _is_main():       # solver.py:23-26
             self.summary_writer = make_summary_writer(os.path.join(cfg.output_dir, 'tf_logs'))
@@ -232,6 +250,10 @@ class Solver:
                     scalars += seg_vals
                     names += seg_names
                     msg += '\n' + self._seg_message()
+                if self.slope_eval:               # SOLVER.slope_eval: the clean test phase's PSNR of the first differences
+                    scalars += [self.last_slope_psnr['gen'], self.last_slope_psnr['reg']]
+                    names += ['psnr_slope_gen', 'psnr_slope_reg']
+                    msg += '\n' + self._slope_message()
                 if self.augment is not None and self.augment.eval:
                     # DATA.aug_eval: the same weights on the fixed corrupted test set; best_valid stays on the clean psnr_gen
                     with optimizer.ema_weights() if self._ema_eval(optimizer) else contextlib.nullcontext():
@@ -239,14 +261,16 @@ class Solver:
                     scalars += list(aug_metrics)
                     names += ['psnr_gen_aug', 'psnr_reg_aug', 'ssim_gen_aug', 'ssim_reg_aug']
                     msg += '\npsnr_gen_aug: {}, psnr_reg_aug: {}, ssim_gen_aug:{}, ssim_reg_aug:{}'.format(*aug_metrics)
-            if tl.shape[0] > 4:                   # SOLVER.ssim_factor is on: the term is the last element of every loss row
-                scalars.append(float(tl[-1]))
-                names.append('train_loss_ssim')
-                msg += '\nloss_ssim (factor {}): train {}'.format(self.cfg.SOLVER.get('ssim_factor', 0.0), float(tl[-1]))
+            # SOLVER.ssim_factor / SOLVER.slope_factor: the terms that are on sit behind the four (train) / five (test: the rest_out term)
+            # elements of every loss row, in this order
+            for k, key in enumerate(self._tail_terms()):
+                scalars.append(float(tl[4 + k]))
+                names.append('train_loss_' + key)
+                msg += '\nloss_{} (factor {}): train {}'.format(key, self.cfg.SOLVER.get(key + '_factor', 0.0), float(tl[4 + k]))
                 if dl_test is not None:
-                    scalars.append(float(te[-1]))
-                    names.append('test_loss_ssim')
-                    msg += ', test {}'.format(float(te[-1]))
+                    scalars.append(float(te[5 + k]))
+                    names.append('test_loss_' + key)
+                    msg += ', test {}'.format(float(te[5 + k]))
             if self.last_grad_norms:              # SOLVER.clip_grad_norm is on
                 norms = [t for t, _ in self.last_grad_norms if np.isfinite(t)]
                 scalars.append(float(np.mean(norms)) if norms else float('nan'))
@@ -289,6 +313,16 @@ class Solver:
             return None
         from ..network.loss.losses import seg_settings
         return seg_settings(self.cfg)
+
+    def _tail_terms(self):
+        """The loss terms behind the reference's elements of a loss row, in the row's order: 'ssim' (SOLVER.ssim_factor > 0), then 'slope'
+        (SOLVER.slope_factor > 0), when the loss is losswrapper."""
+        if self.cfg.MODEL.loss != 'v1':
+            return []
+        return [key for key in ('ssim', 'slope') if float(self.cfg.SOLVER.get(key + '_factor', 0.0)) > 0]
+
+    def _slope_message(self):
+        return 'psnr_slope_gen: {}, psnr_slope_reg: {}'.format(self.last_slope_psnr['gen'], self.last_slope_psnr['reg'])
 
     def _seg_scalars(self):
         """(names, values) of last_seg_psnr: psnr_gen_seg_P .. psnr_gen_seg_TP, psnr_reg_seg_P .. psnr_reg_seg_TP."""
@@ -337,6 +371,8 @@ class Solver:
         print('psnr_gen:{}, psnr_reg:{}, ssim_gen:{}, ssim_reg:{}'.format(psnr_gen, psnr_reg, ssim_gen, ssim_reg))
         if self.seg_eval:
             print(self._seg_message())
+        if self.slope_eval:
+            print(self._slope_message())
         if self.augment is not None and self.augment.eval:
             print('psnr_gen_aug:{}, psnr_reg_aug:{}, ssim_gen_aug:{}, ssim_reg_aug:{}'.format(*self._aug_eval(dl_test)))
         return psnr_gen, psnr_reg, ssim_gen, ssim_reg
@@ -362,9 +398,10 @@ class Solver:
         return gen_num, whole
 
     def _loss_rois(self, rois):
-        """`rois=` for the loss when SOLVER.ssim_factor or SOLVER.seg_weights is on and the loss takes it (losswrapper); nothing
-        otherwise."""
+        """`rois=` for the loss when SOLVER.ssim_factor, SOLVER.slope_factor or SOLVER.seg_weights is on and the loss takes it
+        (losswrapper); nothing otherwise."""
         if self.cfg.MODEL.loss == 'v1' and (float(self.cfg.SOLVER.get('ssim_factor', 0.0)) > 0 or
+                                            float(self.cfg.SOLVER.get('slope_factor', 0.0)) > 0 or
                                             len(self.cfg.SOLVER.get('seg_weights', None) or ()) > 0):
             return {'rois': rois}
         return {}
@@ -444,6 +481,7 @@ class Solver:
         keep = self.collect_views if collect_views is None else bool(collect_views)
         losses_s, pred_s, gt_s, in_s, rest_s, rois_s, psnr_s, ssim_s = (_HostSink() for _ in range(8))
         seg_s = (_HostSink(), _HostSink()) if phase == 'test' and self.seg_eval and not aug_eval else None      # (se, cnt) per clean batch
+        slope_s = (_HostSink(), _HostSink()) if phase == 'test' and self.slope_eval and not aug_eval else None  # (se, cnt) per clean batch
         gen_num, whole = self._gen_num() if phase == 'test' else (0, True)
         # gradient-norm clipping (SOLVER.clip_grad_norm): [norm, coefficient] of every train step travel like the losses
         clip_s = _HostSink() if phase == 'train' and getattr(optim, 'max_grad_norm', 0.0) > 0 else None
@@ -514,6 +552,11 @@ class Solver:
                     se, cnt = ops.view_seg_metrics(rest_out.contiguous(), rest_view, rois.to(torch.int64).contiguous())
                     seg_s[0].add(se)
                     seg_s[1].add(cnt)
+                if slope_s is not None:           # the rows of view_metrics: cropped at rois[i, -1, 0] unless the split is off
+                    se, cnt = ops.view_slope_metrics(rest_out.contiguous(), rest_view,
+                                                     None if whole else rois.to(torch.int64).contiguous())
+                    slope_s[0].add(se)
+                    slope_s[1].add(cnt)
                 if keep:
                     pred_s.add(rest_out)                           # solver.py:182
                     rest_s.add(rest_view)
@@ -582,4 +625,16 @@ class Solver:
                 a = np.asarray(rows, dtype=np.float64).reshape(-1, 6)
                 ok = ~np.isnan(a)
                 self.last_seg_psnr[split] = [float(a[ok[:, k], k].mean()) if ok[:, k].any() else float('nan') for k in range(6)]
+        if slope_s is not None:
+            # per batch the mean over the split's (row, view) pairs that have a difference, then the mean over batches, as psnr_gen /
+            # psnr_reg are formed (a batch without any such pair is left out)
+            per_batch = {'gen': [], 'reg': []}
+            for se, cnt in zip(slope_s[0].arrays(), slope_s[1].arrays()):
+                per_batch['gen'].append(slope_psnr(se, cnt) if whole else slope_psnr(se[:, -gen_num:], cnt[:, -gen_num:]))
+                per_batch['reg'].append(slope_psnr(se, cnt) if whole else slope_psnr(se[:, :-gen_num], cnt[:, :-gen_num]))
+            self.last_slope_psnr = {}
+            for split, vals in per_batch.items():
+                a = np.asarray(vals, dtype=np.float64)
+                ok = ~np.isnan(a)
+                self.last_slope_psnr[split] = float(a[ok].mean()) if ok.any() else float('nan')
         return losses, rest_s.rows(), pred_s.rows(), in_s.rows(), mertics_all, rois_s.rows(), mertics_gen_singlelead

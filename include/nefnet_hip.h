@@ -34,7 +34,7 @@ extern "C" {
 typedef void* nef_stream_t;
 
 /* ABI version of this header; bumped on any signature change. */
-int nef_abi_version(void);   /* 22 (+ nef_flatten_acc, nef_lr_sched / nef_lr_sched_args_bytes, nef_loss_ssim_fwd / nef_loss_ssim_bwd / nef_loss_ssim_ws_bytes / nef_loss_ssim_args_bytes, nef_loss_seg_fwd / nef_loss_seg_bwd / nef_loss_seg_ws_bytes / nef_loss_seg_args_bytes / nef_view_seg_metrics: additions only, the number stays; a binding finds a library without them by the missing symbol.  Weight packing is ONE entry, nef_pack_weights(nef_pack_desc*, n), + nef_pack_bytes(nef_pack_desc*) for the size of any operand.  ABI <= 21 had nef_pack_weight, nef_pack_weight_wino, nef_pack_weight_wino4, nef_pack_weight_h2 and nef_pack_weight_h2_bytes: each is one descriptor with wino = 0 / 1 / 2 / 3); 21 (BatchNorm backward is ONE entry on a nef_bn_bwd_args struct, + nef_bn_bwd_args_bytes; nef_mix_bwd takes `up` / `shared` flags; nef_outconv_fwd / nef_outconv_bwd_weight take the prologue arguments.  ABI <= 20 had nef_bn_relu_bwd_phase_major, nef_bn_relu_bwd_up, nef_bn_relu_bwd_combine3, nef_bn_relu_bwd_combine3_phase_major, nef_bn_relu_bwd_outconv, nef_bn_bwd_outconv_ws_bytes, nef_mix_bwd_up, nef_mix_bwd_shared, nef_mix_bwd_shared_up, nef_outconv_fwd_pro and nef_outconv_bwd_weight_pro); 20 (the weight gradient is ONE entry, nef_conv_bwd_weight(nef_bww_args*), + nef_bww_args_bytes; its _pro, _wino4, _h2 and _h2_ws_bytes variants are gone); 19 (+ nef_adam, nef_h2_tail_census, nef_bwd_weight_clamp_ends: additions only; the kernel-form option entry points of 16 and nef_upsample2_aff_fwd are gone; + nef_debug_spin_us); 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + kernel-form option entry points); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + the split-fp16 weight gradient, now form 3); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, the transposed F(3,4) / F(4,4) entry, now form 4, covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
+int nef_abi_version(void);   /* 22 (+ nef_flatten_acc, nef_lr_sched / nef_lr_sched_args_bytes, nef_loss_ssim_fwd / nef_loss_ssim_bwd / nef_loss_ssim_ws_bytes / nef_loss_ssim_args_bytes, nef_loss_seg_fwd / nef_loss_seg_bwd / nef_loss_seg_ws_bytes / nef_loss_seg_args_bytes / nef_view_seg_metrics, nef_loss_slope_fwd / nef_loss_slope_bwd / nef_loss_slope_ws_bytes / nef_loss_slope_args_bytes / nef_view_slope_metrics: additions only, the number stays; a binding finds a library without them by the missing symbol.  Weight packing is ONE entry, nef_pack_weights(nef_pack_desc*, n), + nef_pack_bytes(nef_pack_desc*) for the size of any operand.  ABI <= 21 had nef_pack_weight, nef_pack_weight_wino, nef_pack_weight_wino4, nef_pack_weight_h2 and nef_pack_weight_h2_bytes: each is one descriptor with wino = 0 / 1 / 2 / 3); 21 (BatchNorm backward is ONE entry on a nef_bn_bwd_args struct, + nef_bn_bwd_args_bytes; nef_mix_bwd takes `up` / `shared` flags; nef_outconv_fwd / nef_outconv_bwd_weight take the prologue arguments.  ABI <= 20 had nef_bn_relu_bwd_phase_major, nef_bn_relu_bwd_up, nef_bn_relu_bwd_combine3, nef_bn_relu_bwd_combine3_phase_major, nef_bn_relu_bwd_outconv, nef_bn_bwd_outconv_ws_bytes, nef_mix_bwd_up, nef_mix_bwd_shared, nef_mix_bwd_shared_up, nef_outconv_fwd_pro and nef_outconv_bwd_weight_pro); 20 (the weight gradient is ONE entry, nef_conv_bwd_weight(nef_bww_args*), + nef_bww_args_bytes; its _pro, _wino4, _h2 and _h2_ws_bytes variants are gone); 19 (+ nef_adam, nef_h2_tail_census, nef_bwd_weight_clamp_ends: additions only; the kernel-form option entry points of 16 and nef_upsample2_aff_fwd are gone; + nef_debug_spin_us); 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + kernel-form option entry points); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + the split-fp16 weight gradient, now form 3); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, the transposed F(3,4) / F(4,4) entry, now form 4, covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
 
 /* Diagnostics: `wgs` workgroups busy for `us` microseconds on `stream` (a stand-in for a collective's time on the chip:
  * parallel.DryCollective, bench.py --dry-collective).  0 <= us <= 50000, 1 <= wgs <= 64. */
@@ -641,6 +641,59 @@ size_t nef_loss_seg_args_bytes(void);
  * NEF_E_NULL; B, Q or L <= 0, B > 65535, L % 4 != 0: NEF_E_SHAPE; pred or gt not 16-byte aligned: NEF_E_UNSUPPORTED. */
 int nef_view_seg_metrics(const float* pred, const float* gt, const int64_t* rois, double* se, int32_t* cnt, int B, int Q, int L,
                          nef_stream_t stream);
+
+/* The slope (first-difference) term of the training loss (cfg.SOLVER.slope_factor; no counterpart in the reference): beside the terms
+ * above it compares how prediction and target CHANGE from one sample to the next.  Row i of x = pred (+ noise: the same fp32 add as above)
+ * against y = target on [0, end_i), end_i = clamp(rois[i, -1, 0], 0, L) (the row end of nef_loss_ssim_* and nef_view_metrics), or L with
+ * rois NULL.  For t in [0, end_i - 1), in fp64 from the fp32 values and in this order:
+ *   d(i, t) = ((double)x[t + 1] - (double)x[t]) - ((double)y[t + 1] - (double)y[t]);   e = |d| (l2 0) or d * d;
+ *   S_i = mean of e over the end_i - 1 differences;  a row with end_i < 2 has no difference and is left out (zero gradient);
+ *   R = rows with a difference;  term = factor * (1/R) sum_i S_i,  0 with R = 0.
+ * Independent of the reconstruction term's factor, norm and segment weights.
+ * fwd (two launches behind nef_loss_*_fwd -- and nef_loss_seg_fwd, nef_loss_ssim_fwd when they run -- on the same stream): one fp64
+ *   partial sum per (row, tile of NEF_LOSS_SLOPE_TILE difference starts, staged with a one-element halo to the right) in ws, a one-block
+ *   finish that adds them in a fixed order (no atomics: the same bits eagerly, under hipGraph replay and on every rank) and writes
+ *   losses[slot] = (float)term, then losses[0] = losses[0] + losses[slot] (one fp32 add).  slot: 4 (a 5-element row), or 5 behind the SSIM
+ *   term (a 6-element row); elements [1 .. slot - 1] keep their bits.  g_pred and gscale are not read.
+ * bwd (one launch behind nef_loss_*_bwd, nef_loss_seg_bwd and nef_loss_ssim_bwd on the same stream): g_pred[i, t] += (float)g_t for
+ *   t < end_i, g_t = factor * gscale / (R (end_i - 1)) * (s(t - 1) - s(t)) in fp64, s(t) = sign(d(i, t)) (sign(0) = 0; l2 0) or 2 d(i, t),
+ *   s = 0 outside [0, end_i - 1); one fp32 add and one writer per element.  Positions t >= end_i and rows without a difference are not
+ *   touched.  R is derived from rois inside the launch: the entry keeps no state.  gscale: NULL (1) or the device word of nef_loss_bwd.
+ *   losses, ws, ws_bytes and slot are not read.
+ * No alignment beyond 4 bytes is asked for and any L >= 1 is taken: rows whose pointers are 16-byte aligned are staged with 16-byte
+ * loads, others element by element.
+ * args, pred, target, losses (fwd) / g_pred (bwd) NULL: NEF_E_NULL; B or L <= 0, B > 65535 (the rows are a grid's y extent), a negative
+ * or NaN factor, fwd: slot not 4 or 5: NEF_E_SHAPE; fwd: ws_bytes below nef_loss_slope_ws_bytes(B, L): NEF_E_WORKSPACE, then ws NULL:
+ * NEF_E_NULL.  Every check sits in front of the launches.  Capturable: nothing is read by the host, nothing is allocated. */
+#define NEF_LOSS_SLOPE_TILE 1024
+typedef struct nef_loss_slope_args {
+    const float* pred;      /* [B, L] */
+    const float* target;    /* [B, L] */
+    const float* noise;     /* NULL, or [B, L] */
+    const int64_t* rois;    /* NULL (whole rows), or [B, 7, 2] */
+    float* losses;          /* fwd: the loss row, slot + 1 elements */
+    void* ws;               /* fwd */
+    size_t ws_bytes;        /* fwd */
+    const float* gscale;    /* bwd: NULL, or a device scalar */
+    float* g_pred;          /* bwd: [B, L], accumulated into */
+    int32_t B;              /* rows, 1 .. 65535 */
+    int32_t L;              /* row length, >= 1 */
+    float factor;           /* >= 0 */
+    int32_t l2;             /* 0: |d|, otherwise d * d */
+    int32_t slot;           /* fwd: 4, or 5 behind the SSIM term */
+    int32_t reserved0;      /* 0 */
+} nef_loss_slope_args;
+int nef_loss_slope_fwd(const nef_loss_slope_args* a, nef_stream_t stream);
+int nef_loss_slope_bwd(const nef_loss_slope_args* a, nef_stream_t stream);
+size_t nef_loss_slope_ws_bytes(int B, int L);
+/* sizeof(nef_loss_slope_args) as the library was built. */
+size_t nef_loss_slope_args_bytes(void);
+/* Squared slope error of the test phase (cfg.SOLVER.slope_eval), one block per (sample, view) row as nef_view_metrics: pred, gt fp32
+ * [B][Q][L], rois NULL (whole rows) or [B, 7, 2]; se fp64 [B][Q]: the sum of d * d over the row's differences (the definition above
+ * without noise); cnt int32 [B][Q]: their number, max(end_i - 1, 0).  Fixed-order block sums, no atomics.  pred, gt, se or cnt NULL:
+ * NEF_E_NULL; B, Q or L <= 0, B * Q > 2^31 - 1: NEF_E_SHAPE. */
+int nef_view_slope_metrics(const float* pred, const float* gt, const int64_t* rois, double* se, int32_t* cnt, int B, int Q, int L,
+                           nef_stream_t stream);
 
 /* Input-lead augmentation of the train step (cfg.DATA.aug_*; no counterpart in the reference, whose only augmentation is the host-side
  * angle jitter): y = a corrupted copy of the input leads x [B, V, L]; x is never written.  Every draw comes from the counter RNG of the

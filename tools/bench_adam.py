@@ -11,6 +11,7 @@
     python tools/bench_adam.py --views Q [Q ...] [--parent-tree DIR] [--out profiles/r16_views_bench_line.json]
     python tools/bench_adam.py --augment [--parent-tree DIR] [--out profiles/r17_augment_bench_line.json]
     python tools/bench_adam.py --seg W0 W1 W2 W3 W4 W5 W6 [--parent-tree DIR] [--out profiles/r18_seg_bench_line.json]
+    python tools/bench_adam.py --slope F [--parent-tree DIR] [--out profiles/r19_slope_bench_line.json]
 
 Each measurement runs in a child process of its own under `timeout` (nothing more is started once one fails), `--reps` rounds of
 the three children; every figure is reported as [min, median, max] over the rounds:
@@ -81,7 +82,13 @@ profiles/r17_augment_bench_line.json unless --out says otherwise.
 same two shapes: per round and shape the graphed FusedSGD step with the key off (sgd-graph: the parent's code path) and on (sgd-graph-seg),
 and -- with --parent-tree DIR -- DIR's own sgd-graph step.  The config-2 child with the key on also times the three new entries alone,
 cold: nef_loss_seg_fwd and nef_loss_seg_bwd on the batch's prediction-sized tensors and rois, nef_view_seg_metrics on [B, 9, L] rows.
-Writes profiles/r18_seg_bench_line.json unless --out says otherwise."""
+Writes profiles/r18_seg_bench_line.json unless --out says otherwise.
+
+--slope F measures the slope term of the training loss (SOLVER.slope_factor = F, slope_loss l1_loss, slope_crop true), at the same two
+shapes: per round and shape the graphed FusedSGD step with the key off (sgd-graph: the parent's code path) and on (sgd-graph-slope), and
+-- with --parent-tree DIR -- DIR's own sgd-graph step.  The config-2 child with the term on also times the three entries alone, cold:
+nef_loss_slope_fwd (two launches) and nef_loss_slope_bwd on the batch's prediction-sized tensors and rois, nef_view_slope_metrics on
+[B, 9, L] rows.  Writes profiles/r19_slope_bench_line.json unless --out says otherwise."""
 import argparse
 import json
 import os
@@ -124,7 +131,7 @@ def cold_ms(launches, dev, reps=30):
 
 
 def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=(), ema=0.0, accum=1, sched=None, ssim=0.0, views=1,
-          seg=None):
+          seg=None, slope=0.0):
     import numpy as np
     import torch
     from electrocardio_panorama_amd import ops, synth
@@ -143,12 +150,14 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
             cfg.DATA[k] = v
     if mode == "sgd-graph-seg":
         cfg.SOLVER.seg_weights = [float(w) for w in seg]
+    if mode == "sgd-graph-slope":
+        cfg.SOLVER.slope_factor, cfg.SOLVER.slope_loss, cfg.SOLVER.slope_crop = float(slope), "l1_loss", True
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     seed_torch(cfg.seed)
     model = build_model(cfg).float().to(dev).train()
     lossf = build_loss(cfg)
-    if mode in ("sgd-graph", "sgd-graph-ssim", "sgd-graph-views", "sgd-graph-augment", "sgd-graph-seg"):
+    if mode in ("sgd-graph", "sgd-graph-ssim", "sgd-graph-views", "sgd-graph-augment", "sgd-graph-seg", "sgd-graph-slope"):
         optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9)
     elif mode == "sgd-graph-clip":
         optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9, max_grad_norm=clip)
@@ -288,6 +297,21 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
                    nef_loss_seg_fwd_cold_GBps=round(2 * 4 * n / (fwd_ms * 1e-3) / 1e9, 1),
                    nef_loss_seg_bwd_cold_GBps=round(2 * 4 * n / (bwd_ms * 1e-3) / 1e9, 1),
                    nef_view_seg_metrics_cold_GBps=round(2 * 4 * xs.numel() / (met_ms * 1e-3) / 1e9, 1))
+    if mode == "sgd-graph-slope":
+        res.update(slope_factor=slope, loss_row=[round(float(v), 6) for v in graphed.losses.tolist()])
+    if mode == "sgd-graph-slope" and (B, L) == EMA_SHAPES["config2"]:
+        Qm = 9
+        pred, g_pred, row = torch.rand(B, 1, L, device=dev) / 3, torch.zeros(B, 1, L, device=dev), torch.zeros(5, device=dev)
+        xs, ys = torch.rand(B, Qm, L, device=dev) / 3, torch.rand(B, Qm, L, device=dev) / 3
+        fwd_ms, bwd_ms, met_ms = cold_ms([lambda: ops.loss_slope_fwd(pred, tgt_view, row, slope, False, rois=rois),
+                                          lambda: ops.loss_slope_bwd(pred, tgt_view, g_pred, slope, False, rois=rois),
+                                          lambda: ops.view_slope_metrics(xs, ys, rois)], dev)
+        n = pred.numel()
+        res.update(nef_loss_slope_fwd_cold_ms=round(fwd_ms, 4), nef_loss_slope_bwd_cold_ms=round(bwd_ms, 4),
+                   nef_view_slope_metrics_cold_ms=round(met_ms, 4),
+                   nef_loss_slope_fwd_cold_GBps=round(2 * 4 * n / (fwd_ms * 1e-3) / 1e9, 1),
+                   nef_loss_slope_bwd_cold_GBps=round(4 * 4 * n / (bwd_ms * 1e-3) / 1e9, 1),
+                   nef_view_slope_metrics_cold_GBps=round(2 * 4 * xs.numel() / (met_ms * 1e-3) / 1e9, 1))
     if mode == "sgd-graph-ema":
         fl = optim._flat[0]
         p, g, buf, e, e_n = (fl[k].clone() for k in ("p", "g", "buf", "ema", "ema_n"))
@@ -712,6 +736,64 @@ def seg_rounds(args):
         f.write(line + "\n")
 
 
+def slope_rounds(args):
+    """--slope F: `--reps` alternating rounds of fresh children per shape (see the module docstring); prints and writes one JSON line."""
+    modes = dict({"sgd-graph": 900, "sgd-graph-slope": 900}, **({"parent": 900} if args.parent_tree else {}))
+    shapes = {k: v for k, v in EMA_SHAPES.items() if args.only_shape in (None, k)}
+    results = {(shape, mode): [] for shape in shapes for mode in modes}
+    for rnd in range(args.reps):
+        order = list(modes) if rnd % 2 == 0 else list(reversed(modes))
+        for shape, (B, L) in shapes.items():
+            for mode in order:
+                if mode == "parent":
+                    # the parent's tool has no --slope: its `child` function is called directly, in a fresh process of its own tree
+                    tree = os.path.abspath(args.parent_tree)
+                    code = ("import importlib.util as u; s = u.spec_from_file_location('parent_bench', %r); m = u.module_from_spec(s); "
+                            "s.loader.exec_module(m); m.child('sgd-graph', %d, %d, B=%d, L=%d)"
+                            % (os.path.join(tree, "tools", "bench_adam.py"), args.steps, args.warmup, B, L))
+                    cmd = ["timeout", "-k", "10", str(modes[mode]), sys.executable, "-c", code]
+                else:
+                    tree = ROOT
+                    cmd = ["timeout", "-k", "10", str(modes[mode]), sys.executable, os.path.join(ROOT, "tools", "bench_adam.py"), "--child", mode,
+                           "--steps", str(args.steps), "--warmup", str(args.warmup), "--shape", str(B), str(L)]
+                    if mode == "sgd-graph-slope":
+                        cmd += ["--slope", repr(float(args.slope))]
+                results[(shape, mode)].append(run_child(cmd, tree, mode))
+                sys.stderr.write(f"round {rnd + 1}/{args.reps} {shape} {mode}: {results[(shape, mode)][-1]['ms_per_step']} ms/step\n")
+                sys.stderr.flush()
+
+    def spread(shape, mode, key):
+        v = sorted(x[key] for x in results[(shape, mode)])
+        return [v[0], v[len(v) // 2], v[-1]]
+
+    out = {"metric": "ms per train step, graphed FusedSGD with the slope term of the loss off and on ([min, median, max] over rounds of "
+                     "fresh processes)", "rounds": args.reps, "slope_factor": args.slope, "slope_loss": "l1_loss", "slope_crop": True,
+           "shapes": {k: "B=%d, 3 leads, L=%d, one GPU, dropout on" % v for k, v in shapes.items()}}
+    for shape in shapes:
+        out[shape + "_slope_off_ms"] = spread(shape, "sgd-graph", "ms_per_step")
+        out[shape + "_slope_on_ms"] = spread(shape, "sgd-graph-slope", "ms_per_step")
+        out[shape + "_slope_on_loss_row"] = results[(shape, "sgd-graph-slope")][0]["loss_row"]
+        if args.parent_tree:
+            out[shape + "_parent_ms"] = par = spread(shape, "parent", "ms_per_step")
+            # the bar: key on, the median at most 0.3 ms above the parent's.  Key off (the parent's launches): where the median lies
+            # against the parent's own spread is reported, not judged
+            out[shape + "_slope_on_median_minus_parent_median_ms"] = round(out[shape + "_slope_on_ms"][1] - par[1], 3)
+            out[shape + "_slope_off_median_inside_parent_spread"] = par[0] <= out[shape + "_slope_off_ms"][1] <= par[2]
+            out[shape + "_slope_off_median_minus_parent_median_ms"] = round(out[shape + "_slope_off_ms"][1] - par[1], 3)
+    if "config2" in shapes:
+        for k in ("nef_loss_slope_fwd", "nef_loss_slope_bwd", "nef_view_slope_metrics"):
+            out[k + "_cold_ms"] = spread("config2", "sgd-graph-slope", k + "_cold_ms")
+            out[k + "_cold_GBps"] = spread("config2", "sgd-graph-slope", k + "_cold_GBps")
+        out.update(launch_note="the three entries alone at config 2 (B=256, L=5000; the metrics on 9 views per sample); cold = a 512 MiB "
+                               "buffer written before each call; bytes counted: prediction and target read (fwd), prediction and target "
+                               "read, the gradient read and written (bwd), prediction and ground truth read (metrics)")
+    out.update(steps=args.steps, warmup=args.warmup)
+    line = json.dumps(out)
+    print(line)
+    with open(args.out or os.path.join(ROOT, "profiles", "r19_slope_bench_line.json"), "w") as f:
+        f.write(line + "\n")
+
+
 def views_rounds(args):
     """--views Q [Q ...]: `--reps` alternating rounds of fresh children per shape (see the module docstring); prints and writes one JSON
     line."""
@@ -856,13 +938,14 @@ def main():
     ap.add_argument("--augment", action="store_true", help="measure the input-lead augmentation of the train step, DATA.aug_* (see above)")
     ap.add_argument("--seg", type=float, nargs=7, default=None, metavar="W",
                     help="measure the wave-segment weights of the reconstruction term, SOLVER.seg_weights = W0 .. W6 (see above)")
-    ap.add_argument("--only-shape", choices=sorted(EMA_SHAPES), default=None, help="with --views: measure this shape only")
+    ap.add_argument("--slope", type=float, default=None, metavar="F", help="measure the slope term of the loss, slope_factor = F (see above)")
+    ap.add_argument("--only-shape", choices=sorted(EMA_SHAPES), default=None, help="with --views or --slope: measure this shape only")
     ap.add_argument("--shape", type=int, nargs=2, default=(256, 5000), metavar=("B", "L"), help="with --child: batch size and length")
     ap.add_argument("--parent-tree", default=None,
                     help="with --clip / --weight-decay / --ema: a built checkout whose own sgd-graph child runs in every round")
     ap.add_argument("--child", choices=sorted({**MODES, **CLIP_MODES, **WD_MODES, **EMA_MODES, "lars-graph": 900, "lamb-graph": 900, "sgd-graph-accum": 900,
                                              "sgd-graph-sched": 900, "sgd-graph-ssim": 900, "sgd-graph-views": 900, "sgd-graph-augment": 900,
-                                             "sgd-graph-seg": 900}),
+                                             "sgd-graph-seg": 900, "sgd-graph-slope": 900}),
                     default=None)
     args = ap.parse_args()
     if args.child == "sgd-graph-ema" and not (args.ema is not None and 0.0 < args.ema < 1.0):
@@ -909,15 +992,24 @@ def main():
         ap.error("--seg is a measurement of its own")
     if args.child == "sgd-graph-seg" and args.seg is None:
         ap.error("--child sgd-graph-seg needs --seg W0 .. W6")
-    if (args.parent_tree and args.seg is None and not args.augment and args.views is None and args.clip is None and args.weight_decay is None and args.ema is None and args.trust is None
+    if args.slope is not None and (not args.slope > 0 or (not args.child and (
+            args.seg is not None or args.augment or args.views is not None or args.clip is not None or args.weight_decay is not None
+            or args.ema is not None or args.trust is not None or args.accum is not None or args.sched is not None
+            or args.ssim is not None))):
+        ap.error("--slope F > 0 is a measurement of its own")
+    if args.child == "sgd-graph-slope" and args.slope is None:
+        ap.error("--child sgd-graph-slope needs --slope F")
+    if (args.parent_tree and args.slope is None and args.seg is None and not args.augment and args.views is None and args.clip is None and args.weight_decay is None and args.ema is None and args.trust is None
             and args.accum is None and args.sched is None and args.ssim is None):
-        ap.error("--parent-tree goes with --clip, --weight-decay, --ema, --trust, --accum, --sched, --ssim, --views, --augment or --seg")
+        ap.error("--parent-tree goes with --clip, --weight-decay, --ema, --trust, --accum, --sched, --ssim, --views, --augment, --seg or --slope")
     if args.child:
         return child(args.child, args.steps if args.child != "adam-eager" else max(3, args.steps // 2), args.warmup,
                      B=args.shape[0], L=args.shape[1], clip=args.clip or 0.0, wd=args.weight_decay or 0.0,
                      no_decay=tuple(args.no_decay), ema=args.ema or 0.0, accum=args.accum or 1,
                      sched=(args.sched, args.sched_warmup) if args.child == "sgd-graph-sched" else None, ssim=args.ssim or 0.0,
-                     views=args.views[0] if args.views else 1, seg=args.seg)
+                     views=args.views[0] if args.views else 1, seg=args.seg, slope=args.slope or 0.0)
+    if args.slope is not None:
+        return slope_rounds(args)
     if args.seg is not None:
         return seg_rounds(args)
     if args.augment:
