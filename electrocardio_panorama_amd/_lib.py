@@ -104,6 +104,12 @@ class LossSlopeArgs(C.Structure):
                 ("g_pred", p), ("B", i32), ("L", i32), ("factor", f32), ("l2", i32), ("slot", i32), ("reserved0", i32)]
 
 
+class LossCorrArgs(C.Structure):
+    """Mirror of `nef_loss_corr_args` (include/nefnet_hip.h)."""
+    _fields_ = [("pred", p), ("target", p), ("noise", p), ("rois", p), ("losses", p), ("ws", p), ("ws_bytes", sz), ("gscale", p),
+                ("g_pred", p), ("eps", C.c_double), ("B", i32), ("L", i32), ("factor", f32), ("slot", i32)]
+
+
 class AugmentArgs(C.Structure):
     """Mirror of `nef_augment_args` (include/nefnet_hip.h)."""
     _fields_ = [("x", p), ("rois", p), ("y", p), ("seed_dev", p), ("seed", C.c_uint64),
@@ -206,6 +212,10 @@ SIGNATURES = {
     "nef_loss_slope_bwd": (i32, [C.POINTER(LossSlopeArgs), p]),
     "nef_loss_slope_ws_bytes": (sz, [i32, i32]),
     "nef_loss_slope_args_bytes": (sz, []),
+    "nef_loss_corr_fwd": (i32, [C.POINTER(LossCorrArgs), p]),
+    "nef_loss_corr_bwd": (i32, [C.POINTER(LossCorrArgs), p]),
+    "nef_loss_corr_ws_bytes": (sz, [i32, i32]),
+    "nef_loss_corr_args_bytes": (sz, []),
     "nef_augment": (i32, [C.POINTER(AugmentArgs), p]),
     "nef_augment_args_bytes": (sz, []),
     "nef_sgd_momentum": (i32, [p, p, p, i64, f32, f32, f32, i32, p, p, p, p]),
@@ -237,6 +247,7 @@ SIGNATURES = {
     "nef_view_metrics": (i32, [p, p, p, p, p, i32, i32, i32, p]),
     "nef_view_seg_metrics": (i32, [p, p, p, p, p, i32, i32, i32, p]),
     "nef_view_slope_metrics": (i32, [p, p, p, p, p, i32, i32, i32, p]),
+    "nef_view_corr_metrics": (i32, [p, p, p, p, p, i32, i32, i32, p]),
     "nef_pano_h_from_f32": (i32, [p, p, i32, i32, i32, p]),
     "nef_pano_h_pack_weight": (i32, [p, p, i32, i32, p]),
     "nef_pano_h_conv": (i32, [p, p, p, p, p, i32, i32, i32, i32, i32, i32, i32, i64, i64, p]),
@@ -282,6 +293,7 @@ def load():
                                ("nef_loss_ssim_args", lib.nef_loss_ssim_args_bytes(), LossSsimArgs),
                                ("nef_loss_seg_args", lib.nef_loss_seg_args_bytes(), LossSegArgs),
                                ("nef_loss_slope_args", lib.nef_loss_slope_args_bytes(), LossSlopeArgs),
+                               ("nef_loss_corr_args", lib.nef_loss_corr_args_bytes(), LossCorrArgs),
                                ("nef_augment_args", lib.nef_augment_args_bytes(), AugmentArgs)):
         if size != C.sizeof(mirror):
             raise NefLibraryError(f"{LIB_PATH}: {name} is {size} bytes, the binding mirrors {C.sizeof(mirror)}; rebuild with "

@@ -156,6 +156,20 @@ _DEFAULTS = {
         # True: the test phase also reports the PSNR of the first differences (nef_view_slope_metrics beside nef_view_metrics), logged as
         # psnr_slope_gen / psnr_slope_reg with the view split of psnr_gen / psnr_reg; best_valid stays on psnr_gen.  False: no launch, no buffer
         "slope_eval": False,
+        # a correlation term in the training loss, on the device (nef_loss_corr_fwd / nef_loss_corr_bwd behind the loss, segment, SSIM and slope
+        # launches, in the eager and the graphed step): loss += corr_factor * mean over rows of 1 - r_i, r_i the Pearson correlation coefficient
+        # of the row's prediction (+ DATA.noise) and target -- no gain and no baseline offset of the prediction changes it; the loss tuple and
+        # the graphed step's loss row gain the term as their LAST element (behind the SSIM and slope terms), logged as train_loss_corr /
+        # test_loss_corr.  Independent of seg_weights, loss_using and loss_factor.  0 = off: the rows, launches, graphs and bits are what they
+        # were before the key existed; a negative value is rejected where the loss is built
+        "corr_factor": 0.0,
+        # True: every row ends at rois[i, -1, 0] as in the test phase's metrics (a row with fewer than 2 samples is left out); False: whole rows
+        "corr_crop": True,
+        # r_i = (c + eps) / sqrt((vx + eps) (vy + eps)): keeps a constant row finite (two constant rows give exactly 1); > 0 and finite
+        "corr_eps": 1e-8,
+        # True: the test phase also reports the mean correlation coefficient (nef_view_corr_metrics beside nef_view_metrics), logged as
+        # corr_gen / corr_reg with the view split of psnr_gen / psnr_reg; best_valid stays on psnr_gen.  False: no launch, no buffer
+        "corr_eval": False,
     },
 }
 

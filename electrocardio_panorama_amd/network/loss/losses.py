@@ -7,29 +7,32 @@ from ... import ops
 class _LossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, pred_p, pred_l, target, factors, reg_l2, use_mask, noise=None, ssim_factor=0.0, rois=None, seg_weights=None,
-                seg_rois=None, slope_factor=0.0, slope_l2=False, slope_rois=None):
+                seg_rois=None, slope_factor=0.0, slope_l2=False, slope_rois=None, corr_factor=0.0, corr_eps=1e-8, corr_rois=None):
         pred, pred_p, pred_l, target = (t.contiguous() for t in (pred, pred_p, pred_l, target))
-        ctx.save_for_backward(pred, pred_p, pred_l, target, noise, rois, seg_rois, slope_rois)
-        ctx.cfg = (factors, reg_l2, use_mask, ssim_factor, seg_weights, slope_factor, slope_l2)
-        if not ssim_factor > 0 and seg_weights is None and not slope_factor > 0:
+        ctx.save_for_backward(pred, pred_p, pred_l, target, noise, rois, seg_rois, slope_rois, corr_rois)
+        ctx.cfg = (factors, reg_l2, use_mask, ssim_factor, seg_weights, slope_factor, slope_l2, corr_factor, corr_eps)
+        if not ssim_factor > 0 and seg_weights is None and not slope_factor > 0 and not corr_factor > 0:
             return ops.loss_fwd(pred, pred_p, pred_l, target, factors, reg_l2, use_mask, noise=noise)
-        # SOLVER.ssim_factor / SOLVER.slope_factor: one more element each -- the SSIM term behind the four, the slope term last, each added
-        # into the total by its own finish launch
+        # SOLVER.ssim_factor / SOLVER.slope_factor / SOLVER.corr_factor: one more element each -- the SSIM term behind the four, then the
+        # slope term, the correlation term last, each added into the total by its own finish launch
         n_front = 5 if ssim_factor > 0 else 4
-        row = torch.empty(n_front + (1 if slope_factor > 0 else 0), device=pred.device, dtype=torch.float32)
+        n_slope = n_front + (1 if slope_factor > 0 else 0)
+        row = torch.empty(n_slope + (1 if corr_factor > 0 else 0), device=pred.device, dtype=torch.float32)
         ops.loss_fwd(pred, pred_p, pred_l, target, factors, reg_l2, use_mask, out=row, noise=noise)
         if seg_weights is not None:     # SOLVER.seg_weights: the reconstruction term and the total rewritten, in front of the SSIM term
             ops.loss_seg_fwd(pred, target, row[:n_front], seg_weights, factors[2], reg_l2, seg_rois, noise=noise)
         if ssim_factor > 0:
             ops.loss_ssim_fwd(pred, target, row[:5], ssim_factor, rois=rois, noise=noise)
         if slope_factor > 0:
-            ops.loss_slope_fwd(pred, target, row, slope_factor, slope_l2, rois=slope_rois, noise=noise)
+            ops.loss_slope_fwd(pred, target, row[:n_slope], slope_factor, slope_l2, rois=slope_rois, noise=noise)
+        if corr_factor > 0:
+            ops.loss_corr_fwd(pred, target, row, corr_factor, corr_eps, rois=corr_rois, noise=noise)
         return row
 
     @staticmethod
     def backward(ctx, g):
-        pred, pred_p, pred_l, target, noise, rois, seg_rois, slope_rois = ctx.saved_tensors
-        factors, reg_l2, use_mask, ssim_factor, seg_weights, slope_factor, slope_l2 = ctx.cfg
+        pred, pred_p, pred_l, target, noise, rois, seg_rois, slope_rois, corr_rois = ctx.saved_tensors
+        factors, reg_l2, use_mask, ssim_factor, seg_weights, slope_factor, slope_l2, corr_factor, corr_eps = ctx.cfg
         g = g.contiguous()
         g_pred, g_p, g_l = ops.loss_bwd(pred, pred_p, pred_l, target, g, factors, reg_l2, use_mask, noise=noise)
         if seg_weights is not None:     # the reconstruction term's gradient times its position's weight, in place
@@ -38,7 +41,9 @@ class _LossFn(torch.autograd.Function):
             ops.loss_ssim_bwd(pred, target, g_pred, ssim_factor, rois=rois, noise=noise, gscale=g)
         if slope_factor > 0:        # ... and the slope term's behind both
             ops.loss_slope_bwd(pred, target, g_pred, slope_factor, slope_l2, rois=slope_rois, noise=noise, gscale=g)
-        return g_pred, g_p, g_l, None, None, None, None, None, None, None, None, None, None, None, None
+        if corr_factor > 0:         # ... and the correlation term's last
+            ops.loss_corr_bwd(pred, target, g_pred, corr_factor, corr_eps, rois=corr_rois, noise=noise, gscale=g)
+        return g_pred, g_p, g_l, None, None, None, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 def ssim_settings(cfg, rois=None, need_rois=True):
@@ -76,6 +81,32 @@ def slope_settings(cfg, rois=None, need_rois=True):
         raise ValueError("SOLVER.slope_crop is set: the slope term needs this batch's rois (losswrapper(..., rois=)); "
                          "set SOLVER.slope_crop False to take whole rows")
     return factor, l2, rois
+
+
+CORR_EPS = 1e-8            # SOLVER.corr_eps' default
+
+
+def corr_settings(cfg, rois=None, need_rois=True):
+    """(SOLVER.corr_factor, SOLVER.corr_eps, the rois the correlation term crops its rows with or None for whole rows).  A negative (or
+    NaN) factor, a corr_eps that is not positive and finite, and corr_crop without rois raise ValueError; factor 0: (0.0, corr_eps' default,
+    None), whatever else is set."""
+    factor = float(cfg.SOLVER.get('corr_factor', 0.0))         # (.get: configs written before the key existed)
+    if not factor >= 0.0:
+        raise ValueError(f"Invalid SOLVER.corr_factor: {factor} (it must be >= 0)")
+    if factor == 0.0:
+        return 0.0, CORR_EPS, None
+    try:
+        eps = float(cfg.SOLVER.get('corr_eps', CORR_EPS))
+    except (TypeError, ValueError):
+        raise ValueError(f"Invalid SOLVER.corr_eps: {cfg.SOLVER.get('corr_eps')!r} (a number is needed)") from None
+    if not 0.0 < eps < float('inf'):                           # (NaN fails <)
+        raise ValueError(f"Invalid SOLVER.corr_eps: {eps} (it must be positive and finite)")
+    if not cfg.SOLVER.get('corr_crop', True):
+        return factor, eps, None
+    if rois is None and need_rois:
+        raise ValueError("SOLVER.corr_crop is set: the correlation term needs this batch's rois (losswrapper(..., rois=)); "
+                         "set SOLVER.corr_crop False to take whole rows")
+    return factor, eps, rois
 
 
 SEG_NAMES = ('P', 'PR', 'QRS', 'ST', 'T', 'TP', 'pad')
@@ -120,6 +151,13 @@ def check_slope_rows(rows):
                          "(SOLVER.slope_factor) takes: lower SOLVER.train_views or the batch size, or set SOLVER.slope_factor 0")
 
 
+def check_corr_rows(rows):
+    """The correlation term's launches take every (view, sample) row as one y index of their grid."""
+    if rows > SSIM_MAX_ROWS:
+        raise ValueError(f"{rows} rows (SOLVER.train_views x the batch) is more than the {SSIM_MAX_ROWS} the correlation term "
+                         "(SOLVER.corr_factor) takes: lower SOLVER.train_views or the batch size, or set SOLVER.corr_factor 0")
+
+
 def check_seg_rows(rows):
     """The segment-weight launches take every (view, sample) row as one y index of their grid."""
     if rows > SSIM_MAX_ROWS:
@@ -137,7 +175,7 @@ def _rows_rois(rois, predict):
 
 def losswrapper(predict, predict_shuffle_p, predict_shuffle_l, target, cfg, rest_out=None, rest_view=None,
                 loss1_gt=None, loss2_gt=None, noise=None, rois=None):
-    """Returns (loss, f0*loss1, f1*loss2, f2*loss3[, loss_unsperv][, loss_ssim][, loss_slope]) as 0-dim tensors; `loss` supports .backward().
+    """Returns (loss, f0*loss1, f1*loss2, f2*loss3[, loss_unsperv][, loss_ssim][, loss_slope][, loss_corr]) as 0-dim tensors; `loss` supports .backward().
     The Standin terms compare against the detached prediction (OurLoss1, losses.py:5-18).
     `noise` (behind the reference's signature): cfg.DATA.noise's per-sample row, [B, 1, L] or anything that expands to the prediction's
     shape.  The three terms are taken at predict + noise inside the loss kernels -- the reference's `out = out + noise` between model
@@ -157,13 +195,22 @@ def losswrapper(predict, predict_shuffle_p, predict_shuffle_l, target, cfg, rest
     difference of the first differences of predict (+ noise) and target; nef_loss_slope_args, include/nefnet_hip.h) as its LAST element,
     behind the SSIM term when both are on, and `loss` includes it.  With cfg.SOLVER.slope_crop the rows end at rois[i, -1, 0] (rois is
     required then; tiled per view in the same way).  The term does not depend on SOLVER.seg_weights, loss_using or loss_factor.  Factor 0:
-    nothing changes."""
+    nothing changes.
+    cfg.SOLVER.corr_factor > 0: the tuple gains the correlation term corr_factor * (mean over rows of 1 - r_i, r_i the Pearson correlation
+    coefficient of predict (+ noise) and target with cfg.SOLVER.corr_eps; nef_loss_corr_args, include/nefnet_hip.h) as its LAST element,
+    behind the SSIM and slope terms, and `loss` includes it.  With cfg.SOLVER.corr_crop the rows end at rois[i, -1, 0] (rois is required
+    then; tiled per view in the same way).  Independent of SOLVER.seg_weights, loss_using and loss_factor.  Factor 0: nothing changes."""
     ssim_factor, ssim_rois = ssim_settings(cfg, rois)
     slope_factor, slope_l2, slope_rois = slope_settings(cfg, rois)
     if slope_factor > 0:
         check_slope_rows(predict.numel() // predict.shape[-1])
         if slope_rois is not None:
             slope_rois = _rows_rois(slope_rois, predict)
+    corr_factor, corr_eps, corr_rois = corr_settings(cfg, rois)
+    if corr_factor > 0:
+        check_corr_rows(predict.numel() // predict.shape[-1])
+        if corr_rois is not None:
+            corr_rois = _rows_rois(corr_rois, predict)
     seg_weights = seg_settings(cfg)
     seg_rois = None
     if seg_weights is not None:
@@ -193,10 +240,12 @@ def losswrapper(predict, predict_shuffle_p, predict_shuffle_l, target, cfg, rest
     if ssim_rois is not None:
         ssim_rois = ssim_rois.detach().to(torch.int64).contiguous()
     L4 = _LossFn.apply(predict, predict_shuffle_p, predict_shuffle_l, target, factors, reg_l2, use_mask, noise, ssim_factor, ssim_rois,
-                       seg_weights, seg_rois, slope_factor, slope_l2, slope_rois)
+                       seg_weights, seg_rois, slope_factor, slope_l2, slope_rois, corr_factor, corr_eps, corr_rois)
     result = (L4[0], L4[1].detach(), L4[2].detach(), L4[3].detach())
     tail = (L4[4].detach(),) if ssim_factor > 0 else ()
     if slope_factor > 0:
+        tail += (L4[4 + len(tail)].detach(),)
+    if corr_factor > 0:
         tail += (L4[-1].detach(),)
     if rest_out is not None and rest_view is not None:
         ro = rest_out.detach().to(torch.float32).contiguous()
@@ -214,4 +263,5 @@ class MSELead(torch.nn.Module):
         target = target.to(torch.float32).expand_as(input)
         # element [0] (the total) is the one _LossFn back-propagates through; with factors (0, 0, 1) and only the
         # reconstruction term enabled it IS the MSE (element [3] carries the same number but no gradient)
-        return _LossFn.apply(input, input, input, target, (0.0, 0.0, 1.0), True, 4, None, 0.0, None, None, None, 0.0, False, None)[0]
+        return _LossFn.apply(input, input, input, target, (0.0, 0.0, 1.0), True, 4, None, 0.0, None, None, None, 0.0, False, None, 0.0, CORR_EPS,
+                             None)[0]

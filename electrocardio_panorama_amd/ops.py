@@ -1945,6 +1945,74 @@ def loss_slope_bwd(pred, target, g_pred, factor, l2, rois=None, noise=None, gsca
     return g_pred
 
 
+LOSS_CORR_TILE = 1024      # NEF_LOSS_CORR_TILE (include/nefnet_hip.h): positions per block of the correlation term's kernels
+LOSS_CORR_MAX_ROWS = 65535  # the rows are a grid's y extent
+
+
+def _corr_args(pred, target, factor, eps, rois, noise):
+    """The checks and the shape the two correlation entries share: pred / target [B, 1, L] (or [Q, B, 1, L], [B, L]; any L >= 1), rois
+    None or int64 [B, 7, 2], noise None or pred's elements."""
+    _chk(pred), _chk(target)
+    if pred.dim() < 2 or target.numel() != pred.numel() or pred.numel() == 0:
+        raise ValueError(f"prediction {tuple(pred.shape)} and target {tuple(target.shape)} must hold the same [B, 1, L] rows")
+    Ln = pred.shape[-1]
+    B = pred.numel() // Ln
+    if B > LOSS_CORR_MAX_ROWS:
+        raise ValueError(f"prediction {tuple(pred.shape)}: {B} rows is more than the {LOSS_CORR_MAX_ROWS} the correlation kernels take")
+    if noise is not None and _chk(noise).numel() != pred.numel():
+        raise ValueError(f"noise {tuple(noise.shape)} does not have the prediction's {tuple(pred.shape)} elements")
+    if rois is not None and (_chk(rois, torch.int64).dim() != 3 or tuple(rois.shape) != (B, N_SEG, 2)):
+        raise ValueError(f"rois {tuple(rois.shape)} is not [{B}, {N_SEG}, 2]")
+    if not float(factor) >= 0.0:
+        raise ValueError(f"Invalid correlation factor: {factor}")
+    if not float(eps) >= 0.0:
+        raise ValueError(f"Invalid correlation eps: {eps}")
+    return B, Ln
+
+
+def loss_corr_fwd(pred, target, losses, factor, eps, rois=None, noise=None):
+    """The correlation term of the training loss behind loss_fwd, loss_seg_fwd, loss_ssim_fwd and loss_slope_fwd (nef_loss_corr_fwd,
+    include/nefnet_hip.h): losses[-1] = factor * mean over the rows with at least two samples of 1 - r_i, r_i the Pearson correlation
+    coefficient (with `eps` in numerator and both variances) of x = pred (+ noise) and y = target over [0, rois[i, -1, 0]) (whole rows with
+    rois None), and losses[0] += losses[-1].  `losses`: the row whose front loss_fwd(out=) has written -- 5 elements (the term is
+    losses[4]), 6 or 7 with the SSIM and / or slope terms in front of it.  Two launches, capturable."""
+    L = _lib.load()
+    B, Ln = _corr_args(pred, target, factor, eps, rois, noise)
+    _chk(losses)
+    if losses.numel() not in (5, 6, 7):
+        raise ValueError(f"losses {tuple(losses.shape)}: the correlation term takes a 5-element row, or a 6- / 7-element one behind the "
+                         "SSIM and slope terms")
+    n = L.nef_loss_corr_ws_bytes(B, Ln)
+    ws = workspace(n, pred.device)
+    ev = _hbm("loss_corr_fwd", pred, target, noise)
+    A = _lib.LossCorrArgs(pred=_p(pred), target=_p(target), noise=_p(noise), rois=_p(rois), losses=_p(losses), ws=_p(ws), ws_bytes=n,
+                          gscale=None, g_pred=None, eps=float(eps), B=B, L=Ln, factor=float(factor), slot=losses.numel() - 1)
+    _lib.check(L.nef_loss_corr_fwd(C.byref(A), _stream()), "nef_loss_corr_fwd")
+    _done(ev)
+    return losses
+
+
+def loss_corr_bwd(pred, target, g_pred, factor, eps, rois=None, noise=None, gscale=None):
+    """g_pred += gscale * d(correlation term) / d pred behind loss_bwd, loss_seg_bwd, loss_ssim_bwd and loss_slope_bwd
+    (nef_loss_corr_bwd): `g_pred` is loss_bwd's first gradient, the first third of its [3B, 1, L] buffer.  Positions at or behind a row's
+    end and rows with fewer than two samples keep their bits.  `gscale`: None (1) or loss_bwd's device word.  Three launches (the row
+    moments are reduced again, then applied), capturable, no state from the forward."""
+    L = _lib.load()
+    B, Ln = _corr_args(pred, target, factor, eps, rois, noise)
+    if _chk(g_pred).numel() != pred.numel():
+        raise ValueError(f"g_pred {tuple(g_pred.shape)} does not have the prediction's {tuple(pred.shape)} elements")
+    if gscale is not None:
+        _chk(gscale)
+    n = L.nef_loss_corr_ws_bytes(B, Ln)
+    ws = workspace(n, pred.device)
+    ev = _hbm("loss_corr_bwd", pred, target, noise, pred, target, noise, g_pred, g_pred)
+    A = _lib.LossCorrArgs(pred=_p(pred), target=_p(target), noise=_p(noise), rois=_p(rois), losses=None, ws=_p(ws), ws_bytes=n,
+                          gscale=_p(gscale), g_pred=_p(g_pred), eps=float(eps), B=B, L=Ln, factor=float(factor), slot=4)
+    _lib.check(L.nef_loss_corr_bwd(C.byref(A), _stream()), "nef_loss_corr_bwd")
+    _done(ev)
+    return g_pred
+
+
 def flatten_into(tensors, out, accumulate=False, accumulate_dev=None):
     """out[:] = concatenation of `tensors` (contiguous fp32, flattened), ONE launch per 64 tensors (nef_flatten; was torch.cat).
     `accumulate`: out[:] += the concatenation instead (gradient accumulation: one fp32 add per element, no atomics).  `accumulate_dev`: a
@@ -2075,6 +2143,24 @@ def view_slope_metrics(pred, gt, rois=None):
     cnt = torch.empty(B, Q, device=pred.device, dtype=torch.int32)
     _lib.check(L.nef_view_slope_metrics(_p(pred), _p(gt), _p(rois), _p(se), _p(cnt), B, Q, Ln, _stream()), "nef_view_slope_metrics")
     return se, cnt
+
+
+def view_corr_metrics(pred, gt, rois=None):
+    """Per-row moments of pred vs gt [B, Q, L] for the correlation coefficient (nef_view_corr_metrics): (mom fp64 [B, Q, 3], cnt int32
+    [B, Q]) -- (vx, vy, c), the variances and the covariance over t in [0, rois[b, -1, 0]) (whole rows with rois None), and the number of
+    those samples.  r = (c + eps) / sqrt((vx + eps) (vy + eps)) is formed by the caller for the rows with cnt >= 2.  rois: None or int64
+    [B, 7, 2].  Any L >= 1."""
+    L = _lib.load()
+    _chk(pred), _chk(gt)
+    if pred.dim() != 3 or gt.shape != pred.shape or pred.numel() == 0:
+        raise ValueError(f"prediction {tuple(pred.shape)} and ground truth {tuple(gt.shape)} must both be [B, Q, L]")
+    B, Q, Ln = pred.shape
+    if rois is not None and (_chk(rois, torch.int64).dim() != 3 or tuple(rois.shape) != (B, N_SEG, 2)):
+        raise ValueError(f"rois {tuple(rois.shape)} is not [{B}, {N_SEG}, 2]")
+    mom = torch.empty(B, Q, 3, device=pred.device, dtype=torch.float64)
+    cnt = torch.empty(B, Q, device=pred.device, dtype=torch.int32)
+    _lib.check(L.nef_view_corr_metrics(_p(pred), _p(gt), _p(rois), _p(mom), _p(cnt), B, Q, Ln, _stream()), "nef_view_corr_metrics")
+    return mom, cnt
 
 
 def sgd_momentum(p, g, buf, lr, mu, gscale, first_step, skip=None, lr_dev=None):

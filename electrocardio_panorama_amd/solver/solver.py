@@ -29,7 +29,10 @@ term by wave segment; the test phase reports the PSNR of each of the six wave se
 batch) as psnr_gen_seg_* / psnr_reg_seg_*, in `Solver.last_seg_psnr`.
 `SOLVER.slope_factor` / `SOLVER.slope_eval` (no counterpart in the reference): the loss gains the first-difference term, logged as
 train_loss_slope / test_loss_slope; the test phase reports the PSNR of the first differences (`nef_view_slope_metrics`, one more launch per
-batch) as psnr_slope_gen / psnr_slope_reg, in `Solver.last_slope_psnr`."""
+batch) as psnr_slope_gen / psnr_slope_reg, in `Solver.last_slope_psnr`.
+`SOLVER.corr_factor` / `SOLVER.corr_eval` (no counterpart in the reference): the loss gains 1 - the Pearson correlation coefficient, logged
+as train_loss_corr / test_loss_corr; the test phase reports the mean coefficient (`nef_view_corr_metrics`, one more launch per batch) as
+corr_gen / corr_reg, in `Solver.last_corr`."""
 import contextlib
 import json
 import os
@@ -149,6 +152,14 @@ def slope_psnr(se, cnt):
     return float(np.mean(np.where(rmse == 0.0, 100.0, 20.0 * np.log10(1.0 / np.where(rmse == 0.0, 1.0, rmse)))))
 
 
+def corr_pairs(mom, cnt, eps):
+    """The correlation coefficients from nef_view_corr_metrics' tables of one batch: mom [B, Q', 3] = (vx, vy, c), cnt [B, Q'] -> the 1-D
+    array of r = (c + eps) / sqrt((vx + eps) (vy + eps)) of the (row, view) pairs with at least two samples."""
+    m, n = np.asarray(mom, dtype=np.float64).reshape(-1, 3), np.asarray(cnt).reshape(-1)
+    m = m[n >= 2]
+    return (m[:, 2] + eps) / np.sqrt((m[:, 0] + eps) * (m[:, 1] + eps))
+
+
 def _is_main():
     return not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
 
@@ -172,6 +183,9 @@ class Solver:
         # SOLVER.slope_eval: the test phase also fills last_slope_psnr = {'gen': number, 'reg': number}
         self.slope_eval = bool(cfg.SOLVER.get('slope_eval', False))
         self.last_slope_psnr = None
+        # SOLVER.corr_eval: the test phase also fills last_corr = {'gen': number, 'reg': number}
+        self.corr_eval = bool(cfg.SOLVER.get('corr_eval', False))
+        self.last_corr = None
         self._init_model_device()
         if self.desc != 'debug' and use_tensorboardx and _is_main():       # solver.py:23-26
             self.summary_writer = make_summary_writer(os.path.join(cfg.output_dir, 'tf_logs'))
@@ -254,6 +268,10 @@ class Solver:
                     scalars += [self.last_slope_psnr['gen'], self.last_slope_psnr['reg']]
                     names += ['psnr_slope_gen', 'psnr_slope_reg']
                     msg += '\n' + self._slope_message()
+                if self.corr_eval:                # SOLVER.corr_eval: the clean test phase's mean correlation coefficient
+                    scalars += [self.last_corr['gen'], self.last_corr['reg']]
+                    names += ['corr_gen', 'corr_reg']
+                    msg += '\n' + self._corr_message()
                 if self.augment is not None and self.augment.eval:
                     # DATA.aug_eval: the same weights on the fixed corrupted test set; best_valid stays on the clean psnr_gen
                     with optimizer.ema_weights() if self._ema_eval(optimizer) else contextlib.nullcontext():
@@ -261,7 +279,7 @@ class Solver:
                     scalars += list(aug_metrics)
                     names += ['psnr_gen_aug', 'psnr_reg_aug', 'ssim_gen_aug', 'ssim_reg_aug']
                     msg += '\npsnr_gen_aug: {}, psnr_reg_aug: {}, ssim_gen_aug:{}, ssim_reg_aug:{}'.format(*aug_metrics)
-            # SOLVER.ssim_factor / SOLVER.slope_factor: the terms that are on sit behind the four (train) / five (test: the rest_out term)
+            # SOLVER.ssim_factor / SOLVER.slope_factor / SOLVER.corr_factor: the terms that are on sit behind the four (train) / five (test: the rest_out term)
             # elements of every loss row, in this order
             for k, key in enumerate(self._tail_terms()):
                 scalars.append(float(tl[4 + k]))
@@ -316,13 +334,16 @@ class Solver:
 
     def _tail_terms(self):
         """The loss terms behind the reference's elements of a loss row, in the row's order: 'ssim' (SOLVER.ssim_factor > 0), then 'slope'
-        (SOLVER.slope_factor > 0), when the loss is losswrapper."""
+        (SOLVER.slope_factor > 0), then 'corr' (SOLVER.corr_factor > 0), when the loss is losswrapper."""
         if self.cfg.MODEL.loss != 'v1':
             return []
-        return [key for key in ('ssim', 'slope') if float(self.cfg.SOLVER.get(key + '_factor', 0.0)) > 0]
+        return [key for key in ('ssim', 'slope', 'corr') if float(self.cfg.SOLVER.get(key + '_factor', 0.0)) > 0]
 
     def _slope_message(self):
         return 'psnr_slope_gen: {}, psnr_slope_reg: {}'.format(self.last_slope_psnr['gen'], self.last_slope_psnr['reg'])
+
+    def _corr_message(self):
+        return 'corr_gen: {}, corr_reg: {}'.format(self.last_corr['gen'], self.last_corr['reg'])
 
     def _seg_scalars(self):
         """(names, values) of last_seg_psnr: psnr_gen_seg_P .. psnr_gen_seg_TP, psnr_reg_seg_P .. psnr_reg_seg_TP."""
@@ -373,6 +394,8 @@ class Solver:
             print(self._seg_message())
         if self.slope_eval:
             print(self._slope_message())
+        if self.corr_eval:
+            print(self._corr_message())
         if self.augment is not None and self.augment.eval:
             print('psnr_gen_aug:{}, psnr_reg_aug:{}, ssim_gen_aug:{}, ssim_reg_aug:{}'.format(*self._aug_eval(dl_test)))
         return psnr_gen, psnr_reg, ssim_gen, ssim_reg
@@ -398,10 +421,11 @@ class Solver:
         return gen_num, whole
 
     def _loss_rois(self, rois):
-        """`rois=` for the loss when SOLVER.ssim_factor, SOLVER.slope_factor or SOLVER.seg_weights is on and the loss takes it
+        """`rois=` for the loss when SOLVER.ssim_factor, SOLVER.slope_factor, SOLVER.corr_factor or SOLVER.seg_weights is on and the loss takes it
         (losswrapper); nothing otherwise."""
         if self.cfg.MODEL.loss == 'v1' and (float(self.cfg.SOLVER.get('ssim_factor', 0.0)) > 0 or
                                             float(self.cfg.SOLVER.get('slope_factor', 0.0)) > 0 or
+                                            float(self.cfg.SOLVER.get('corr_factor', 0.0)) > 0 or
                                             len(self.cfg.SOLVER.get('seg_weights', None) or ()) > 0):
             return {'rois': rois}
         return {}
@@ -482,6 +506,7 @@ class Solver:
         losses_s, pred_s, gt_s, in_s, rest_s, rois_s, psnr_s, ssim_s = (_HostSink() for _ in range(8))
         seg_s = (_HostSink(), _HostSink()) if phase == 'test' and self.seg_eval and not aug_eval else None      # (se, cnt) per clean batch
         slope_s = (_HostSink(), _HostSink()) if phase == 'test' and self.slope_eval and not aug_eval else None  # (se, cnt) per clean batch
+        corr_s = (_HostSink(), _HostSink()) if phase == 'test' and self.corr_eval and not aug_eval else None    # (mom, cnt) per clean batch
         gen_num, whole = self._gen_num() if phase == 'test' else (0, True)
         # gradient-norm clipping (SOLVER.clip_grad_norm): [norm, coefficient] of every train step travel like the losses
         clip_s = _HostSink() if phase == 'train' and getattr(optim, 'max_grad_norm', 0.0) > 0 else None
@@ -557,6 +582,11 @@ class Solver:
                                                      None if whole else rois.to(torch.int64).contiguous())
                     slope_s[0].add(se)
                     slope_s[1].add(cnt)
+                if corr_s is not None:            # the same rows
+                    mom, cnt = ops.view_corr_metrics(rest_out.contiguous(), rest_view,
+                                                     None if whole else rois.to(torch.int64).contiguous())
+                    corr_s[0].add(mom)
+                    corr_s[1].add(cnt)
                 if keep:
                     pred_s.add(rest_out)                           # solver.py:182
                     rest_s.add(rest_view)
@@ -637,4 +667,16 @@ class Solver:
                 a = np.asarray(vals, dtype=np.float64)
                 ok = ~np.isnan(a)
                 self.last_slope_psnr[split] = float(a[ok].mean()) if ok.any() else float('nan')
+        if corr_s is not None:
+            # the mean coefficient over the split's (row, view) pairs of the whole phase that have at least two samples; NaN without one
+            from ..network.loss.losses import CORR_EPS
+            eps = float(self.cfg.SOLVER.get('corr_eps', CORR_EPS))
+            pairs = {'gen': [], 'reg': []}
+            for mom, cnt in zip(corr_s[0].arrays(), corr_s[1].arrays()):
+                pairs['gen'].append(corr_pairs(mom, cnt, eps) if whole else corr_pairs(mom[:, -gen_num:], cnt[:, -gen_num:], eps))
+                pairs['reg'].append(corr_pairs(mom, cnt, eps) if whole else corr_pairs(mom[:, :-gen_num], cnt[:, :-gen_num], eps))
+            self.last_corr = {}
+            for split, vals in pairs.items():
+                a = np.concatenate(vals) if vals else np.zeros(0)
+                self.last_corr[split] = float(a.mean()) if a.size else float('nan')
         return losses, rest_s.rows(), pred_s.rows(), in_s.rows(), mertics_all, rois_s.rows(), mertics_gen_singlelead

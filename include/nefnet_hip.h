@@ -34,7 +34,7 @@ extern "C" {
 typedef void* nef_stream_t;
 
 /* ABI version of this header; bumped on any signature change. */
-int nef_abi_version(void);   /* 22 (+ nef_flatten_acc, nef_lr_sched / nef_lr_sched_args_bytes, nef_loss_ssim_fwd / nef_loss_ssim_bwd / nef_loss_ssim_ws_bytes / nef_loss_ssim_args_bytes, nef_loss_seg_fwd / nef_loss_seg_bwd / nef_loss_seg_ws_bytes / nef_loss_seg_args_bytes / nef_view_seg_metrics, nef_loss_slope_fwd / nef_loss_slope_bwd / nef_loss_slope_ws_bytes / nef_loss_slope_args_bytes / nef_view_slope_metrics: additions only, the number stays; a binding finds a library without them by the missing symbol.  Weight packing is ONE entry, nef_pack_weights(nef_pack_desc*, n), + nef_pack_bytes(nef_pack_desc*) for the size of any operand.  ABI <= 21 had nef_pack_weight, nef_pack_weight_wino, nef_pack_weight_wino4, nef_pack_weight_h2 and nef_pack_weight_h2_bytes: each is one descriptor with wino = 0 / 1 / 2 / 3); 21 (BatchNorm backward is ONE entry on a nef_bn_bwd_args struct, + nef_bn_bwd_args_bytes; nef_mix_bwd takes `up` / `shared` flags; nef_outconv_fwd / nef_outconv_bwd_weight take the prologue arguments.  ABI <= 20 had nef_bn_relu_bwd_phase_major, nef_bn_relu_bwd_up, nef_bn_relu_bwd_combine3, nef_bn_relu_bwd_combine3_phase_major, nef_bn_relu_bwd_outconv, nef_bn_bwd_outconv_ws_bytes, nef_mix_bwd_up, nef_mix_bwd_shared, nef_mix_bwd_shared_up, nef_outconv_fwd_pro and nef_outconv_bwd_weight_pro); 20 (the weight gradient is ONE entry, nef_conv_bwd_weight(nef_bww_args*), + nef_bww_args_bytes; its _pro, _wino4, _h2 and _h2_ws_bytes variants are gone); 19 (+ nef_adam, nef_h2_tail_census, nef_bwd_weight_clamp_ends: additions only; the kernel-form option entry points of 16 and nef_upsample2_aff_fwd are gone; + nef_debug_spin_us); 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + kernel-form option entry points); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + the split-fp16 weight gradient, now form 3); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, the transposed F(3,4) / F(4,4) entry, now form 4, covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
+int nef_abi_version(void);   /* 22 (+ nef_flatten_acc, nef_lr_sched / nef_lr_sched_args_bytes, nef_loss_ssim_fwd / nef_loss_ssim_bwd / nef_loss_ssim_ws_bytes / nef_loss_ssim_args_bytes, nef_loss_seg_fwd / nef_loss_seg_bwd / nef_loss_seg_ws_bytes / nef_loss_seg_args_bytes / nef_view_seg_metrics, nef_loss_slope_fwd / nef_loss_slope_bwd / nef_loss_slope_ws_bytes / nef_loss_slope_args_bytes / nef_view_slope_metrics, nef_loss_corr_fwd / nef_loss_corr_bwd / nef_loss_corr_ws_bytes / nef_loss_corr_args_bytes / nef_view_corr_metrics: additions only, the number stays; a binding finds a library without them by the missing symbol.  Weight packing is ONE entry, nef_pack_weights(nef_pack_desc*, n), + nef_pack_bytes(nef_pack_desc*) for the size of any operand.  ABI <= 21 had nef_pack_weight, nef_pack_weight_wino, nef_pack_weight_wino4, nef_pack_weight_h2 and nef_pack_weight_h2_bytes: each is one descriptor with wino = 0 / 1 / 2 / 3); 21 (BatchNorm backward is ONE entry on a nef_bn_bwd_args struct, + nef_bn_bwd_args_bytes; nef_mix_bwd takes `up` / `shared` flags; nef_outconv_fwd / nef_outconv_bwd_weight take the prologue arguments.  ABI <= 20 had nef_bn_relu_bwd_phase_major, nef_bn_relu_bwd_up, nef_bn_relu_bwd_combine3, nef_bn_relu_bwd_combine3_phase_major, nef_bn_relu_bwd_outconv, nef_bn_bwd_outconv_ws_bytes, nef_mix_bwd_up, nef_mix_bwd_shared, nef_mix_bwd_shared_up, nef_outconv_fwd_pro and nef_outconv_bwd_weight_pro); 20 (the weight gradient is ONE entry, nef_conv_bwd_weight(nef_bww_args*), + nef_bww_args_bytes; its _pro, _wino4, _h2 and _h2_ws_bytes variants are gone); 19 (+ nef_adam, nef_h2_tail_census, nef_bwd_weight_clamp_ends: additions only; the kernel-form option entry points of 16 and nef_upsample2_aff_fwd are gone; + nef_debug_spin_us); 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + kernel-form option entry points); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + the split-fp16 weight gradient, now form 3); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, the transposed F(3,4) / F(4,4) entry, now form 4, covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
 
 /* Diagnostics: `wgs` workgroups busy for `us` microseconds on `stream` (a stand-in for a collective's time on the chip:
  * parallel.DryCollective, bench.py --dry-collective).  0 <= us <= 50000, 1 <= wgs <= 64. */
@@ -694,6 +694,59 @@ size_t nef_loss_slope_args_bytes(void);
  * NEF_E_NULL; B, Q or L <= 0, B * Q > 2^31 - 1: NEF_E_SHAPE. */
 int nef_view_slope_metrics(const float* pred, const float* gt, const int64_t* rois, double* se, int32_t* cnt, int B, int Q, int L,
                            nef_stream_t stream);
+
+/* The correlation term of the training loss (cfg.SOLVER.corr_factor; no counterpart in the reference): 1 - the Pearson correlation
+ * coefficient of prediction and target, which no gain and no baseline offset of the prediction changes.  Row i of x = pred (+ noise: the
+ * same fp32 add as above) against y = target on [0, n_i), n_i = clamp(rois[i, -1, 0], 0, L) (the row end of nef_loss_ssim_*,
+ * nef_loss_slope_* and nef_view_metrics), or L with rois NULL.  In fp64 from the fp32 values, on values shifted by the row's first sample
+ * (exact in fp64; a constant row then has moments that are exact zeros), u_t = x_t - x_0, w_t = y_t - y_0:
+ *   mu = (1/n) sum u;  mw = (1/n) sum w;  vx = (1/n) sum u^2 - mu^2;  vy = (1/n) sum w^2 - mw^2;  c = (1/n) sum u w - mu mw;
+ *   D = sqrt((vx + eps) (vy + eps));  r_i = (c + eps) / D   -- in (-1, 1]; exactly 1.0 for x == y and for two constant rows;
+ *   a row with n_i < 2 is left out (zero gradient);  R = rows that count;  term = factor * (1/R) sum_i (1 - r_i),  0 with R = 0.
+ * Independent of the reconstruction term's factor, norm and segment weights.
+ * fwd (two launches behind nef_loss_*_fwd -- and nef_loss_seg_fwd, nef_loss_ssim_fwd, nef_loss_slope_fwd when they run -- on the same
+ *   stream): the five sums of each (row, tile of NEF_LOSS_CORR_TILE positions) in ws, a one-block finish that walks rows and tiles in a
+ *   fixed order (no atomics: the same bits eagerly, under hipGraph replay and on every rank) and writes losses[slot] = (float)term, then
+ *   losses[0] = losses[0] + losses[slot] (one fp32 add).  slot: 4, 5 or 6 -- the term is the last element of its row, behind the SSIM and
+ *   slope elements; elements [1 .. slot - 1] keep their bits.  g_pred and gscale are not read.
+ * bwd (three launches behind nef_loss_*_bwd, nef_loss_seg_bwd, nef_loss_ssim_bwd and nef_loss_slope_bwd on the same stream; no state from
+ *   the forward): the same partial sums into ws, a one-block finish that writes mu, mw, a_i = -factor / (R n_i D) and
+ *   k_i = r_i D / (vx + eps) per row behind them, and an apply launch: g_pred[i, t] += (float)(gscale * a_i * ((w_t - mw) - k_i (u_t -
+ *   mu))) for t < n_i; one fp32 add and one writer per element.  Positions t >= n_i and rows that do not count are not touched.  R is
+ *   derived from rois inside the launch.  gscale: NULL (1) or the device word of nef_loss_bwd.  losses and slot are not read.
+ * No alignment beyond 4 bytes is asked for and any L >= 1 is taken: tiles whose pointers are 16-byte aligned use 16-byte accesses, others
+ * go element by element.
+ * args, pred, target, losses (fwd) / g_pred (bwd) NULL: NEF_E_NULL; B or L <= 0, B > 65535 (the rows are a grid's y extent), a negative
+ * or NaN factor or eps, fwd: slot outside 4 .. 6: NEF_E_SHAPE; ws_bytes below nef_loss_corr_ws_bytes(B, L): NEF_E_WORKSPACE, then ws
+ * NULL: NEF_E_NULL.  Every check sits in front of the launches.  Capturable: nothing is read by the host, nothing is allocated. */
+#define NEF_LOSS_CORR_TILE 1024
+typedef struct nef_loss_corr_args {
+    const float* pred;      /* [B, L] */
+    const float* target;    /* [B, L] */
+    const float* noise;     /* NULL, or [B, L] */
+    const int64_t* rois;    /* NULL (whole rows), or [B, 7, 2] */
+    float* losses;          /* fwd: the loss row, slot + 1 elements */
+    void* ws;               /* 8-byte aligned; fwd and bwd may share one (stream order) */
+    size_t ws_bytes;        /* at least nef_loss_corr_ws_bytes(B, L) */
+    const float* gscale;    /* bwd: NULL, or a device scalar */
+    float* g_pred;          /* bwd: [B, L], accumulated into */
+    double eps;             /* >= 0 */
+    int32_t B;              /* rows, 1 .. 65535 */
+    int32_t L;              /* row length, >= 1 */
+    float factor;           /* >= 0 */
+    int32_t slot;           /* fwd: 4, 5 or 6 */
+} nef_loss_corr_args;
+int nef_loss_corr_fwd(const nef_loss_corr_args* a, nef_stream_t stream);
+int nef_loss_corr_bwd(const nef_loss_corr_args* a, nef_stream_t stream);
+size_t nef_loss_corr_ws_bytes(int B, int L);
+/* sizeof(nef_loss_corr_args) as the library was built. */
+size_t nef_loss_corr_args_bytes(void);
+/* Moments of the test phase's correlation coefficient (cfg.SOLVER.corr_eval), one block per (sample, view) row as nef_view_metrics: pred,
+ * gt fp32 [B][Q][L], rois NULL (whole rows) or [B, 7, 2]; mom fp64 [B][Q][3] = (vx, vy, c) by the definition above without noise (zeros
+ * for an empty row); cnt int32 [B][Q] = n_i.  The host forms r = (c + eps) / sqrt((vx + eps) (vy + eps)) for the rows with cnt >= 2.
+ * Fixed-order block sums, no atomics.  pred, gt, mom or cnt NULL: NEF_E_NULL; B, Q or L <= 0, B * Q > 2^31 - 1: NEF_E_SHAPE. */
+int nef_view_corr_metrics(const float* pred, const float* gt, const int64_t* rois, double* mom, int32_t* cnt, int B, int Q, int L,
+                          nef_stream_t stream);
 
 /* Input-lead augmentation of the train step (cfg.DATA.aug_*; no counterpart in the reference, whose only augmentation is the host-side
  * angle jitter): y = a corrupted copy of the input leads x [B, V, L]; x is never written.  Every draw comes from the counter RNG of the

@@ -12,6 +12,7 @@
     python tools/bench_adam.py --augment [--parent-tree DIR] [--out profiles/r17_augment_bench_line.json]
     python tools/bench_adam.py --seg W0 W1 W2 W3 W4 W5 W6 [--parent-tree DIR] [--out profiles/r18_seg_bench_line.json]
     python tools/bench_adam.py --slope F [--parent-tree DIR] [--out profiles/r19_slope_bench_line.json]
+    python tools/bench_adam.py --corr F [--parent-tree DIR] [--out profiles/r20_corr_bench_line.json]
 
 Each measurement runs in a child process of its own under `timeout` (nothing more is started once one fails), `--reps` rounds of
 the three children; every figure is reported as [min, median, max] over the rounds:
@@ -88,7 +89,13 @@ Writes profiles/r18_seg_bench_line.json unless --out says otherwise.
 shapes: per round and shape the graphed FusedSGD step with the key off (sgd-graph: the parent's code path) and on (sgd-graph-slope), and
 -- with --parent-tree DIR -- DIR's own sgd-graph step.  The config-2 child with the term on also times the three entries alone, cold:
 nef_loss_slope_fwd (two launches) and nef_loss_slope_bwd on the batch's prediction-sized tensors and rois, nef_view_slope_metrics on
-[B, 9, L] rows.  Writes profiles/r19_slope_bench_line.json unless --out says otherwise."""
+[B, 9, L] rows.  Writes profiles/r19_slope_bench_line.json unless --out says otherwise.
+
+--corr F measures the correlation term of the training loss (SOLVER.corr_factor = F, corr_crop true, corr_eps at its default), at the same
+two shapes: per round and shape the graphed FusedSGD step with the key off (sgd-graph: the parent's code path) and on (sgd-graph-corr), and
+-- with --parent-tree DIR -- DIR's own sgd-graph step.  The config-2 child with the term on also times the three entries alone, cold:
+nef_loss_corr_fwd (two launches) and nef_loss_corr_bwd (three) on the batch's prediction-sized tensors and rois, nef_view_corr_metrics on
+[B, 9, L] rows.  Writes profiles/r20_corr_bench_line.json unless --out says otherwise."""
 import argparse
 import json
 import os
@@ -131,7 +138,7 @@ def cold_ms(launches, dev, reps=30):
 
 
 def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=(), ema=0.0, accum=1, sched=None, ssim=0.0, views=1,
-          seg=None, slope=0.0):
+          seg=None, slope=0.0, corr=0.0):
     import numpy as np
     import torch
     from electrocardio_panorama_amd import ops, synth
@@ -152,12 +159,14 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
         cfg.SOLVER.seg_weights = [float(w) for w in seg]
     if mode == "sgd-graph-slope":
         cfg.SOLVER.slope_factor, cfg.SOLVER.slope_loss, cfg.SOLVER.slope_crop = float(slope), "l1_loss", True
+    if mode == "sgd-graph-corr":
+        cfg.SOLVER.corr_factor, cfg.SOLVER.corr_crop = float(corr), True
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     seed_torch(cfg.seed)
     model = build_model(cfg).float().to(dev).train()
     lossf = build_loss(cfg)
-    if mode in ("sgd-graph", "sgd-graph-ssim", "sgd-graph-views", "sgd-graph-augment", "sgd-graph-seg", "sgd-graph-slope"):
+    if mode in ("sgd-graph", "sgd-graph-ssim", "sgd-graph-views", "sgd-graph-augment", "sgd-graph-seg", "sgd-graph-slope", "sgd-graph-corr"):
         optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9)
     elif mode == "sgd-graph-clip":
         optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9, max_grad_norm=clip)
@@ -312,6 +321,22 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
                    nef_loss_slope_fwd_cold_GBps=round(2 * 4 * n / (fwd_ms * 1e-3) / 1e9, 1),
                    nef_loss_slope_bwd_cold_GBps=round(4 * 4 * n / (bwd_ms * 1e-3) / 1e9, 1),
                    nef_view_slope_metrics_cold_GBps=round(2 * 4 * xs.numel() / (met_ms * 1e-3) / 1e9, 1))
+    if mode == "sgd-graph-corr":
+        res.update(corr_factor=corr, loss_row=[round(float(v), 6) for v in graphed.losses.tolist()])
+    if mode == "sgd-graph-corr" and (B, L) == EMA_SHAPES["config2"]:
+        Qm = 9
+        eps = float(cfg.SOLVER.corr_eps)
+        pred, g_pred, row = torch.rand(B, 1, L, device=dev) / 3, torch.zeros(B, 1, L, device=dev), torch.zeros(5, device=dev)
+        xs, ys = torch.rand(B, Qm, L, device=dev) / 3, torch.rand(B, Qm, L, device=dev) / 3
+        fwd_ms, bwd_ms, met_ms = cold_ms([lambda: ops.loss_corr_fwd(pred, tgt_view, row, corr, eps, rois=rois),
+                                          lambda: ops.loss_corr_bwd(pred, tgt_view, g_pred, corr, eps, rois=rois),
+                                          lambda: ops.view_corr_metrics(xs, ys, rois)], dev)
+        n = pred.numel()
+        res.update(nef_loss_corr_fwd_cold_ms=round(fwd_ms, 4), nef_loss_corr_bwd_cold_ms=round(bwd_ms, 4),
+                   nef_view_corr_metrics_cold_ms=round(met_ms, 4),
+                   nef_loss_corr_fwd_cold_GBps=round(2 * 4 * n / (fwd_ms * 1e-3) / 1e9, 1),
+                   nef_loss_corr_bwd_cold_GBps=round(6 * 4 * n / (bwd_ms * 1e-3) / 1e9, 1),
+                   nef_view_corr_metrics_cold_GBps=round(2 * 4 * xs.numel() / (met_ms * 1e-3) / 1e9, 1))
     if mode == "sgd-graph-ema":
         fl = optim._flat[0]
         p, g, buf, e, e_n = (fl[k].clone() for k in ("p", "g", "buf", "ema", "ema_n"))
@@ -794,6 +819,64 @@ def slope_rounds(args):
         f.write(line + "\n")
 
 
+def corr_rounds(args):
+    """--corr F: `--reps` alternating rounds of fresh children per shape (see the module docstring); prints and writes one JSON line."""
+    modes = dict({"sgd-graph": 900, "sgd-graph-corr": 900}, **({"parent": 900} if args.parent_tree else {}))
+    shapes = {k: v for k, v in EMA_SHAPES.items() if args.only_shape in (None, k)}
+    results = {(shape, mode): [] for shape in shapes for mode in modes}
+    for rnd in range(args.reps):
+        order = list(modes) if rnd % 2 == 0 else list(reversed(modes))
+        for shape, (B, L) in shapes.items():
+            for mode in order:
+                if mode == "parent":
+                    # the parent's tool has no --corr: its `child` function is called directly, in a fresh process of its own tree
+                    tree = os.path.abspath(args.parent_tree)
+                    code = ("import importlib.util as u; s = u.spec_from_file_location('parent_bench', %r); m = u.module_from_spec(s); "
+                            "s.loader.exec_module(m); m.child('sgd-graph', %d, %d, B=%d, L=%d)"
+                            % (os.path.join(tree, "tools", "bench_adam.py"), args.steps, args.warmup, B, L))
+                    cmd = ["timeout", "-k", "10", str(modes[mode]), sys.executable, "-c", code]
+                else:
+                    tree = ROOT
+                    cmd = ["timeout", "-k", "10", str(modes[mode]), sys.executable, os.path.join(ROOT, "tools", "bench_adam.py"), "--child", mode,
+                           "--steps", str(args.steps), "--warmup", str(args.warmup), "--shape", str(B), str(L)]
+                    if mode == "sgd-graph-corr":
+                        cmd += ["--corr", repr(float(args.corr))]
+                results[(shape, mode)].append(run_child(cmd, tree, mode))
+                sys.stderr.write(f"round {rnd + 1}/{args.reps} {shape} {mode}: {results[(shape, mode)][-1]['ms_per_step']} ms/step\n")
+                sys.stderr.flush()
+
+    def spread(shape, mode, key):
+        v = sorted(x[key] for x in results[(shape, mode)])
+        return [v[0], v[len(v) // 2], v[-1]]
+
+    out = {"metric": "ms per train step, graphed FusedSGD with the correlation term of the loss off and on ([min, median, max] over rounds "
+                     "of fresh processes)", "rounds": args.reps, "corr_factor": args.corr, "corr_crop": True,
+           "shapes": {k: "B=%d, 3 leads, L=%d, one GPU, dropout on" % v for k, v in shapes.items()}}
+    for shape in shapes:
+        out[shape + "_corr_off_ms"] = spread(shape, "sgd-graph", "ms_per_step")
+        out[shape + "_corr_on_ms"] = spread(shape, "sgd-graph-corr", "ms_per_step")
+        out[shape + "_corr_on_loss_row"] = results[(shape, "sgd-graph-corr")][0]["loss_row"]
+        if args.parent_tree:
+            out[shape + "_parent_ms"] = par = spread(shape, "parent", "ms_per_step")
+            # the bar: key on, the median at most 0.3 ms above the parent's.  Key off (the parent's launches): where the median lies
+            # against the parent's own spread is reported, not judged
+            out[shape + "_corr_on_median_minus_parent_median_ms"] = round(out[shape + "_corr_on_ms"][1] - par[1], 3)
+            out[shape + "_corr_off_median_inside_parent_spread"] = par[0] <= out[shape + "_corr_off_ms"][1] <= par[2]
+            out[shape + "_corr_off_median_minus_parent_median_ms"] = round(out[shape + "_corr_off_ms"][1] - par[1], 3)
+    if "config2" in shapes:
+        for k in ("nef_loss_corr_fwd", "nef_loss_corr_bwd", "nef_view_corr_metrics"):
+            out[k + "_cold_ms"] = spread("config2", "sgd-graph-corr", k + "_cold_ms")
+            out[k + "_cold_GBps"] = spread("config2", "sgd-graph-corr", k + "_cold_GBps")
+        out.update(launch_note="the three entries alone at config 2 (B=256, L=5000; the metrics on 9 views per sample); cold = a 512 MiB "
+                               "buffer written before each call; bytes counted: prediction and target read (fwd), prediction and target "
+                               "read twice, the gradient read and written (bwd), prediction and ground truth read (metrics)")
+    out.update(steps=args.steps, warmup=args.warmup)
+    line = json.dumps(out)
+    print(line)
+    with open(args.out or os.path.join(ROOT, "profiles", "r20_corr_bench_line.json"), "w") as f:
+        f.write(line + "\n")
+
+
 def views_rounds(args):
     """--views Q [Q ...]: `--reps` alternating rounds of fresh children per shape (see the module docstring); prints and writes one JSON
     line."""
@@ -939,13 +1022,14 @@ def main():
     ap.add_argument("--seg", type=float, nargs=7, default=None, metavar="W",
                     help="measure the wave-segment weights of the reconstruction term, SOLVER.seg_weights = W0 .. W6 (see above)")
     ap.add_argument("--slope", type=float, default=None, metavar="F", help="measure the slope term of the loss, slope_factor = F (see above)")
-    ap.add_argument("--only-shape", choices=sorted(EMA_SHAPES), default=None, help="with --views or --slope: measure this shape only")
+    ap.add_argument("--corr", type=float, default=None, metavar="F", help="measure the correlation term of the loss, corr_factor = F (see above)")
+    ap.add_argument("--only-shape", choices=sorted(EMA_SHAPES), default=None, help="with --views, --slope or --corr: measure this shape only")
     ap.add_argument("--shape", type=int, nargs=2, default=(256, 5000), metavar=("B", "L"), help="with --child: batch size and length")
     ap.add_argument("--parent-tree", default=None,
                     help="with --clip / --weight-decay / --ema: a built checkout whose own sgd-graph child runs in every round")
     ap.add_argument("--child", choices=sorted({**MODES, **CLIP_MODES, **WD_MODES, **EMA_MODES, "lars-graph": 900, "lamb-graph": 900, "sgd-graph-accum": 900,
                                              "sgd-graph-sched": 900, "sgd-graph-ssim": 900, "sgd-graph-views": 900, "sgd-graph-augment": 900,
-                                             "sgd-graph-seg": 900, "sgd-graph-slope": 900}),
+                                             "sgd-graph-seg": 900, "sgd-graph-slope": 900, "sgd-graph-corr": 900}),
                     default=None)
     args = ap.parse_args()
     if args.child == "sgd-graph-ema" and not (args.ema is not None and 0.0 < args.ema < 1.0):
@@ -999,15 +1083,24 @@ def main():
         ap.error("--slope F > 0 is a measurement of its own")
     if args.child == "sgd-graph-slope" and args.slope is None:
         ap.error("--child sgd-graph-slope needs --slope F")
-    if (args.parent_tree and args.slope is None and args.seg is None and not args.augment and args.views is None and args.clip is None and args.weight_decay is None and args.ema is None and args.trust is None
+    if args.corr is not None and (not args.corr > 0 or (not args.child and (
+            args.slope is not None or args.seg is not None or args.augment or args.views is not None or args.clip is not None
+            or args.weight_decay is not None or args.ema is not None or args.trust is not None or args.accum is not None
+            or args.sched is not None or args.ssim is not None))):
+        ap.error("--corr F > 0 is a measurement of its own")
+    if args.child == "sgd-graph-corr" and args.corr is None:
+        ap.error("--child sgd-graph-corr needs --corr F")
+    if (args.parent_tree and args.corr is None and args.slope is None and args.seg is None and not args.augment and args.views is None and args.clip is None and args.weight_decay is None and args.ema is None and args.trust is None
             and args.accum is None and args.sched is None and args.ssim is None):
-        ap.error("--parent-tree goes with --clip, --weight-decay, --ema, --trust, --accum, --sched, --ssim, --views, --augment, --seg or --slope")
+        ap.error("--parent-tree goes with --clip, --weight-decay, --ema, --trust, --accum, --sched, --ssim, --views, --augment, --seg, --slope or --corr")
     if args.child:
         return child(args.child, args.steps if args.child != "adam-eager" else max(3, args.steps // 2), args.warmup,
                      B=args.shape[0], L=args.shape[1], clip=args.clip or 0.0, wd=args.weight_decay or 0.0,
                      no_decay=tuple(args.no_decay), ema=args.ema or 0.0, accum=args.accum or 1,
                      sched=(args.sched, args.sched_warmup) if args.child == "sgd-graph-sched" else None, ssim=args.ssim or 0.0,
-                     views=args.views[0] if args.views else 1, seg=args.seg, slope=args.slope or 0.0)
+                     views=args.views[0] if args.views else 1, seg=args.seg, slope=args.slope or 0.0, corr=args.corr or 0.0)
+    if args.corr is not None:
+        return corr_rounds(args)
     if args.slope is not None:
         return slope_rounds(args)
     if args.seg is not None:
