@@ -17,12 +17,6 @@ static_assert(TILE % 4 == 0, "a tile is whole float4 groups");
 constexpr int NSUM = 5;                       // sum u, sum w, sum u^2, sum w^2, sum u w
 constexpr int NSTAT = 4;                      // mu, mw, a, k per row
 
-__device__ __forceinline__ int row_end(const int64_t* __restrict__ rois, int i, int L) {
-    if (!rois) return L;
-    const int64_t e = rois[(int64_t)i * 14 + 12];       // rois[i, -1, 0]
-    return e < 0 ? 0 : (e > L ? L : (int)e);
-}
-
 __device__ __forceinline__ void add_sample(double (&s)[NSUM], float xf, float yf, double x0, double y0) {
     const double u = (double)xf - x0, w = (double)yf - y0;
     s[0] += u;
@@ -83,7 +77,7 @@ __global__ __launch_bounds__(256) void corr_partial(const float* __restrict__ pr
                                                     double* __restrict__ part, int L) {
     __shared__ double sm[NSUM][4];
     const int row = blockIdx.y;
-    const int end = row_end(rois, row, L);
+    const int end = nef_row_end(rois, row, L);
     const int t0 = blockIdx.x * TILE;
     const int n = min(TILE, end - t0);                   // positions of this tile: [t0, t0 + n)
     double s[NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0};
@@ -130,7 +124,7 @@ __global__ __launch_bounds__(256) void corr_final(const double* __restrict__ par
     __shared__ double sm[4];
     double s = 0.0, r = 0.0;
     for (int i = threadIdx.x; i < B; i += 256) {
-        const int end = row_end(rois, i, L);
+        const int end = nef_row_end(rois, i, L);
         if (end < 2) continue;
         const RowMoments m = row_moments(part, i, tiles, end);
         const double D = sqrt((m.vx + eps) * (m.vy + eps));
@@ -151,10 +145,10 @@ __global__ __launch_bounds__(256) void corr_bwd_final(const double* __restrict__
                                                       double* __restrict__ stat, int B, int L, int tiles, float factor, double eps) {
     __shared__ double sm[4];
     double R = 0.0;
-    for (int i = threadIdx.x; i < B; i += 256) R += row_end(rois, i, L) >= 2 ? 1.0 : 0.0;
+    for (int i = threadIdx.x; i < B; i += 256) R += nef_row_end(rois, i, L) >= 2 ? 1.0 : 0.0;
     R = nef_block_sum_d(R, sm);
     for (int i = threadIdx.x; i < B; i += 256) {
-        const int end = row_end(rois, i, L);
+        const int end = nef_row_end(rois, i, L);
         double* o = stat + (int64_t)i * NSTAT;
         if (end < 2) {
             o[0] = 0.0, o[1] = 0.0, o[2] = 0.0, o[3] = 0.0;
@@ -181,7 +175,7 @@ __global__ __launch_bounds__(256) void corr_apply(const float* __restrict__ pred
                                                   const float* __restrict__ gscale, const double* __restrict__ stat,
                                                   float* __restrict__ g_pred, int L) {
     const int row = blockIdx.y;
-    const int end = row_end(rois, row, L);
+    const int end = nef_row_end(rois, row, L);
     const int t0 = blockIdx.x * TILE;
     if (end < 2 || t0 >= end) return;                    // block-uniform: a row that does not count, a tile behind the row's end
     const int64_t r0 = (int64_t)row * L;
@@ -222,7 +216,7 @@ __global__ __launch_bounds__(256) void view_corr_metrics_kernel(const float* __r
                                                                 int32_t* __restrict__ cnt, int Q, int L) {
     __shared__ double sm[NSUM][4];
     const int row = blockIdx.x;
-    const int end = row_end(rois, row / Q, L);
+    const int end = nef_row_end(rois, row / Q, L);
     const int64_t r0 = (int64_t)row * L;
     double s[NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0};
     if (end > 0) {                                       // block-uniform

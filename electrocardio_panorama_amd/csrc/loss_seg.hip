@@ -1,6 +1,6 @@
 // Wave-segment weights on the reconstruction term of the training loss (cfg.SOLVER.seg_weights) and the per-segment squared error of
 // the test phase (cfg.SOLVER.seg_eval).  One definition of "the segment of a position", used by all three kernels (include/nefnet_hip.h,
-// nef_loss_seg_args): end_i = clamp(rois[i, 6, 0], 0, L) -- row_end of loss_ssim.hip --; t >= end_i is segment 6 (pad); otherwise the
+// nef_loss_seg_args): end_i = clamp(rois[i, 6, 0], 0, L) -- nef_row_end of nef_common.h --; t >= end_i is segment 6 (pad); otherwise the
 // segment is the number of k in 1..5 with rois[i, k, 0] <= t.  Only the six start points are read, so the rule is total for any int64
 // content.  The starts are clamped to [0, L] once per block: for 0 <= t < L that keeps every comparison (s < 0 -> 0 <= t holds;
 // s > L -> L <= t fails), and the per-element work is five 32-bit compares.  The weight of a position is picked by a select chain over

@@ -13,12 +13,6 @@ static_assert(TILE % 4 == 0, "the body of a tile is whole float4 groups");
 constexpr int BODY = 4;                       // backward: the body sits at index 4 of the LDS rows, the left halo at 3
 constexpr int NS = TILE + 8;
 
-__device__ __forceinline__ int row_end(const int64_t* __restrict__ rois, int i, int L) {
-    if (!rois) return L;
-    const int64_t e = rois[(int64_t)i * 14 + 12];       // rois[i, -1, 0]
-    return e < 0 ? 0 : (e > L ? L : (int)e);
-}
-
 // xs / ys[k] = x (+ z) / y[lo + k] for k in [0, count): the caller guarantees lo + count <= L and 16-byte aligned xs, ys
 __device__ __forceinline__ void stage(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, int lo,
                                       int count, float* __restrict__ xs, float* __restrict__ ys) {
@@ -53,7 +47,7 @@ __global__ __launch_bounds__(256) void slope_partial(const float* __restrict__ p
     __shared__ double sm[4];
     __shared__ __attribute__((aligned(16))) float xs[NS], ys[NS];
     const int row = blockIdx.y;
-    const int end = row_end(rois, row, L);
+    const int end = nef_row_end(rois, row, L);
     const int t0 = blockIdx.x * TILE;
     const int n = min(TILE, end - 1 - t0);               // difference starts of this tile: [t0, t0 + n)
     double acc = 0.0;
@@ -76,7 +70,7 @@ __global__ __launch_bounds__(256) void slope_final(const double* __restrict__ pa
     __shared__ double sm[4];
     double s = 0.0, r = 0.0;
     for (int i = threadIdx.x; i < B; i += 256) {
-        const int end = row_end(rois, i, L);
+        const int end = nef_row_end(rois, i, L);
         if (end < 2) continue;
         double si = 0.0;
         for (int t = 0; t < tiles; ++t) si += part[(int64_t)i * tiles + t];
@@ -102,11 +96,11 @@ __global__ __launch_bounds__(256) void slope_bwd_kernel(const float* __restrict_
     __shared__ double sm[4];
     __shared__ __attribute__((aligned(16))) float xs[NS], ys[NS];
     const int row = blockIdx.y;
-    const int end = row_end(rois, row, L);
+    const int end = nef_row_end(rois, row, L);
     const int t0 = blockIdx.x * TILE;
     if (end < 2 || t0 >= end) return;                    // block-uniform: a row without a difference, a tile behind the row's end
     double r = 0.0;
-    for (int i = threadIdx.x; i < B; i += 256) r += row_end(rois, i, L) >= 2 ? 1.0 : 0.0;
+    for (int i = threadIdx.x; i < B; i += 256) r += nef_row_end(rois, i, L) >= 2 ? 1.0 : 0.0;
     r = nef_block_sum_d(r, sm);                          // >= 1: this row counts
     const int64_t r0 = (int64_t)row * L;
     const float* x = pred + r0;
@@ -144,7 +138,7 @@ __global__ __launch_bounds__(256) void view_slope_metrics_kernel(const float* __
     __shared__ double sm[4];
     __shared__ __attribute__((aligned(16))) float xs[NS], ys[NS];
     const int row = blockIdx.x;
-    const int end = row_end(rois, row / Q, L);
+    const int end = nef_row_end(rois, row / Q, L);
     const int64_t r0 = (int64_t)row * L;
     double acc = 0.0;
     for (int t0 = 0; t0 < end - 1; t0 += TILE) {         // block-uniform

@@ -12,12 +12,6 @@ constexpr int TILE = NEF_LOSS_SSIM_TILE;      // window starts (forward) / posit
 constexpr int HALO = WIN - 1;
 constexpr double C1 = 0.01 * 0.01, C2 = 0.03 * 0.03, COV_NORM = (double)WIN / (WIN - 1.0);
 
-__device__ __forceinline__ int row_end(const int64_t* __restrict__ rois, int i, int L) {
-    if (!rois) return L;
-    const int64_t e = rois[(int64_t)i * 14 + 12];       // rois[i, -1, 0]
-    return e < 0 ? 0 : (e > L ? L : (int)e);
-}
-
 // the five window moments -> means and (co)variances
 struct ssim_win {
     double ux, uy, vx, vy, vxy;
@@ -37,7 +31,7 @@ __global__ __launch_bounds__(256) void ssim_partial(const float* __restrict__ pr
                                                     double* __restrict__ part, int L) {
     __shared__ double sm[4];
     const int row = blockIdx.y;
-    const int end = row_end(rois, row, L);
+    const int end = nef_row_end(rois, row, L);
     const int p0 = blockIdx.x * TILE;
     const int p1 = min(p0 + TILE, end - HALO);           // window starts of this tile: [p0, p1)
     const float* x = pred + (int64_t)row * L;
@@ -64,7 +58,7 @@ __global__ __launch_bounds__(256) void ssim_final(const double* __restrict__ par
     __shared__ double sm[4];
     double s = 0.0, r = 0.0;
     for (int i = threadIdx.x; i < B; i += 256) {
-        const int end = row_end(rois, i, L);
+        const int end = nef_row_end(rois, i, L);
         if (end < WIN) continue;
         double si = 0.0;
         for (int t = 0; t < tiles; ++t) si += part[(int64_t)i * tiles + t];
@@ -93,11 +87,11 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(const float* __restrict__
     __shared__ float xs[NX], ys[NX];
     __shared__ double ca[NW], cb[NW], cc[NW];
     const int row = blockIdx.y;
-    const int end = row_end(rois, row, L);
+    const int end = nef_row_end(rois, row, L);
     const int t0 = blockIdx.x * TILE;
     if (end < WIN || t0 >= end) return;                  // block-uniform: a row without a window, a tile behind the row's end
     double r = 0.0;
-    for (int i = threadIdx.x; i < B; i += 256) r += row_end(rois, i, L) >= WIN ? 1.0 : 0.0;
+    for (int i = threadIdx.x; i < B; i += 256) r += nef_row_end(rois, i, L) >= WIN ? 1.0 : 0.0;
     r = nef_block_sum_d(r, sm);                          // >= 1: this row counts
     const float* x = pred + (int64_t)row * L;
     const float* y = tgt + (int64_t)row * L;

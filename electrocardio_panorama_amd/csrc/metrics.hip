@@ -20,12 +20,7 @@ __global__ __launch_bounds__(256) void view_metrics_kernel(const float* __restri
                                                            double* __restrict__ ssim, int Q, int L) {
     __shared__ double sm[4];
     const int row = blockIdx.x;
-    const int i = row / Q;
-    int end = L;
-    if (rois) {
-        const int64_t e = rois[(int64_t)i * 14 + 12];       // rois[i, -1, 0]
-        end = e < 0 ? 0 : (e > L ? L : (int)e);
-    }
+    const int end = nef_row_end(rois, row / Q, L);
     const float* x = pred + (int64_t)row * L;
     const float* y = gt + (int64_t)row * L;
     double se = 0.0;

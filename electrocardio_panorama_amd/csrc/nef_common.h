@@ -80,6 +80,13 @@ __device__ __forceinline__ double nef_block_sum_d(double v, double* sm) {
     return sm[0] + sm[1] + sm[2] + sm[3];
 }
 
+// Where row i of L samples ends for the loss terms and metrics that crop at the un-padded region: all of it without rois.
+__device__ __forceinline__ int nef_row_end(const int64_t* __restrict__ rois, int i, int L) {
+    if (!rois) return L;
+    const int64_t e = rois[(int64_t)i * 14 + 12];       // rois[i, -1, 0]
+    return e < 0 ? 0 : (e > L ? L : (int)e);
+}
+
 // Counter-based keep decision for in-kernel dropout: uniform in [0,1) from (seed, dense element index).  One 64-bit mix
 // (two 64-bit multiplies: ~90 % of the decision's cost) serves TWO neighbouring elements -- elements 2k and 2k+1 take the
 // bit fields [40,64) and [16,40) of the same word -- so the Winograd epilogues, which own aligned output pairs, hash once

@@ -7,13 +7,9 @@ it: inputs are copied into static buffers, and the only per-step host decisions 
 (reference model_nefnet.py:154,156, drawn from Python's `random` in the reference's order) and the dropout seed --
 travel through device words that the kernels read at run time.  Same arithmetic as the eager path.  `cfg.DATA.noise`: the
 per-sample noise row is one more static input, added to the prediction inside the loss kernels (ops.loss_fwd / loss_bwd, noise=).
-`cfg.SOLVER.ssim_factor`: the SSIM term's three launches (ops.loss_ssim_fwd / loss_ssim_bwd) sit behind them in the same graph.
-`cfg.SOLVER.seg_weights`: the segment weights' three launches (ops.loss_seg_fwd / loss_seg_bwd) sit between the two, each behind the loss
-launch it rewrites; the weights are config constants, frozen into the capture as scalars.
-`cfg.SOLVER.slope_factor`: the slope term's three launches (ops.loss_slope_fwd / loss_slope_bwd) sit behind the SSIM ones; its factor and
-norm are frozen into the capture, and the loss row has 4 + (SSIM on) + (slope on) + (correlation on) elements.
-`cfg.SOLVER.corr_factor`: the correlation term's five launches (ops.loss_corr_fwd / loss_corr_bwd) sit behind the slope ones, on the same
-static rois and noise buffer; its factor and eps are frozen into the capture.
+`cfg.SOLVER.seg_weights`, `ssim_factor`, `slope_factor`, `corr_factor`: the launches of the terms that are on sit behind them in the same
+graph, in the order and on the loss row that network.loss.losses.LossPlan lays out (per term its forward, then its backward), on the same
+static rois and noise buffer; their weights, factors and other scalars are config constants, frozen into the capture.
 
 One graph (with its own static input buffers) is kept per input shape, so a final partial batch or alternating shapes
 replay instead of re-capturing; the flat parameter / gradient / momentum buffers are shared by all of them and survive
@@ -68,23 +64,11 @@ class GraphedTrainStep:
         # and added inside the loss kernels; off: no buffer, no copy
         self.use_noise = bool(cfg.DATA.noise)
         self.noise = None
-        self.rois_q = None       # multi-view steps with the cropped SSIM / slope / correlation term or segment weights: the rois tiled Q times
-        # cfg.SOLVER.ssim_factor: the SSIM term's launches behind the loss launches, on the static rois and noise; the loss row has 5
-        # elements then.  0: no launch, the 4-element row
-        from .network.loss.losses import ssim_settings
-        self.ssim_factor = ssim_settings(cfg, need_rois=False)[0]
-        self.ssim_crop = self.ssim_factor > 0 and bool(cfg.SOLVER.get('ssim_crop', True))
-        # cfg.SOLVER.slope_factor: the slope term's launches behind the SSIM ones; one more element at the end of the loss row.  0: no launch
-        from .network.loss.losses import slope_settings
-        self.slope_factor, self.slope_l2 = slope_settings(cfg, need_rois=False)[:2]
-        self.slope_crop = self.slope_factor > 0 and bool(cfg.SOLVER.get('slope_crop', True))
-        # cfg.SOLVER.corr_factor: the correlation term's launches behind the slope ones; the last element of the loss row.  0: no launch
-        from .network.loss.losses import corr_settings
-        self.corr_factor, self.corr_eps = corr_settings(cfg, need_rois=False)[:2]
-        self.corr_crop = self.corr_factor > 0 and bool(cfg.SOLVER.get('corr_crop', True))
-        # cfg.SOLVER.seg_weights: None (no launch), or the seven weights of the reconstruction term's positions
-        from .network.loss.losses import seg_settings
-        self.seg_weights = seg_settings(cfg)
+        self.rois_q = None       # multi-view steps whose plan needs rois (a cropped term, segment weights): the rois tiled Q times
+        # the terms behind the four of ops.loss_fwd: their launches behind the loss launches, one more element of the loss row per tail term
+        from .network.loss.losses import LossPlan
+        self.plan = LossPlan.from_cfg(cfg)
+        self.seg_weights = self.plan.seg_weights      # None, or the seven weights of the reconstruction term's positions
         # cfg.DATA.aug_*: every shape slot owns a static [B, V, L] buffer the captured ops.augment writes and the forward reads; None: neither
         from . import augment as _augment
         self.augment = _augment.from_cfg(cfg)
@@ -181,25 +165,10 @@ class GraphedTrainStep:
             o, p_, l_ = (t.contiguous() for t in outs)
             ops.loss_fwd(o, p_, l_, self.target, self.factors, self.reg_l2, self.use_mask, out=self.losses, noise=self.noise)
             g3 = ops.loss_bwd(o, p_, l_, self.target, None, self.factors, self.reg_l2, self.use_mask, noise=self.noise)
-            if self.seg_weights is not None:
-                rois = self.rois if self.rois_q is None else self.rois_q
-                ops.loss_seg_fwd(o, self.target, self.losses[:5 if self.ssim_factor > 0 else 4], self.seg_weights, self.factors[2],
-                                 self.reg_l2, rois, noise=self.noise)
-                ops.loss_seg_bwd(g3[0], self.seg_weights, rois)
-            if self.ssim_factor > 0:
-                # (multi-view: the rows are the Q * B (view, sample) pairs, the rois tiled once per view)
-                rois = (self.rois if self.rois_q is None else self.rois_q) if self.ssim_crop else None
-                ops.loss_ssim_fwd(o, self.target, self.losses[:5], self.ssim_factor, rois=rois, noise=self.noise)
-                ops.loss_ssim_bwd(o, self.target, g3[0], self.ssim_factor, rois=rois, noise=self.noise)
-            if self.slope_factor > 0:
-                rois = (self.rois if self.rois_q is None else self.rois_q) if self.slope_crop else None
-                ops.loss_slope_fwd(o, self.target, self.losses[:5 + int(self.ssim_factor > 0)], self.slope_factor, self.slope_l2, rois=rois,
-                                   noise=self.noise)
-                ops.loss_slope_bwd(o, self.target, g3[0], self.slope_factor, self.slope_l2, rois=rois, noise=self.noise)
-            if self.corr_factor > 0:
-                rois = (self.rois if self.rois_q is None else self.rois_q) if self.corr_crop else None
-                ops.loss_corr_fwd(o, self.target, self.losses, self.corr_factor, self.corr_eps, rois=rois, noise=self.noise)
-                ops.loss_corr_bwd(o, self.target, g3[0], self.corr_factor, self.corr_eps, rois=rois, noise=self.noise)
+            rois = self.rois if self.rois_q is None else self.rois_q      # (multi-view: the rows are the Q * B (view, sample) pairs)
+            for step in self.plan:
+                step.fwd(o, self.target, self.losses, rois, self.noise)
+                step.bwd(o, self.target, g3[0], rois, self.noise)
             return engine.backward(P, sv, g3)
 
     def _frozen(self):
@@ -321,19 +290,8 @@ class GraphedTrainStep:
             if self.use_noise:
                 raise ValueError("DATA.noise with SOLVER.train_views >= 2: the batch carries noise for the target lead only")
             slot["target"] = torch.empty(Q, data.shape[0], 1, data.shape[2], device=dev, dtype=torch.float32)
-            if self.ssim_factor > 0:
-                from .network.loss.losses import check_view_rows
-                check_view_rows(Q, data.shape[0])
-            if self.seg_weights is not None:
-                from .network.loss.losses import check_seg_rows
-                check_seg_rows(Q * data.shape[0])
-            if self.slope_factor > 0:
-                from .network.loss.losses import check_slope_rows
-                check_slope_rows(Q * data.shape[0])
-            if self.corr_factor > 0:
-                from .network.loss.losses import check_corr_rows
-                check_corr_rows(Q * data.shape[0])
-            if self.ssim_crop or self.slope_crop or self.corr_crop or self.seg_weights is not None:
+            self.plan.check_rows(Q * data.shape[0], views=Q)
+            if self.plan.needs_rois:
                 slot["rois_q"] = torch.empty(Q * rois.shape[0], rois.shape[1], rois.shape[2], device=dev, dtype=torch.int64)
         if self.use_noise:
             slot["noise"] = torch.empty(data.shape[0], 1, data.shape[2], device=dev, dtype=torch.float32)
@@ -344,8 +302,7 @@ class GraphedTrainStep:
             self.choice_dev = torch.zeros(2, device=dev, dtype=torch.int32)
             self.seed_dev = torch.zeros(1, device=dev, dtype=torch.int64)
             self.status = torch.zeros(1, device=dev, dtype=torch.int32)
-            self.losses = torch.zeros(4 + int(self.ssim_factor > 0) + int(self.slope_factor > 0) + int(self.corr_factor > 0), device=dev,
-                                      dtype=torch.float32)
+            self.losses = torch.zeros(self.plan.row_len, device=dev, dtype=torch.float32)
             self.lr_dev = torch.full((1,), self.lr, device=dev, dtype=torch.float32)
         if self.accum > 1 and self.acc_dev is None:
             self.acc_dev, self._acc_word = torch.zeros(1, device=dev, dtype=torch.int32), 0
@@ -511,12 +468,9 @@ class GraphedTrainStep:
         self._pending_momentum = None
 
     def __call__(self, data, in_theta, q_theta, rois, target, noise=None):
-        """One train step; returns the device tensor [loss, f0*l1, f1*l2, f2*l3] (valid in stream order; with cfg.SOLVER.ssim_factor > 0 a
-        fifth element, the SSIM term, and with cfg.SOLVER.slope_factor > 0 one more behind it, the slope term, and with
-        cfg.SOLVER.corr_factor > 0 one more behind that, the correlation term; `loss` includes them all).
-        `noise`: the batch's
-        [B, L] or [B, 1, L] noise rows, required when cfg.DATA.noise is set and ignored when it is not (as the reference ignores
-        meta['noise'] then)."""
+        """One train step; returns the device tensor [loss, f0*l1, f1*l2, f2*l3] + one element per tail term of `self.plan` that is on
+        (valid in stream order; `loss` includes them all).  `noise`: the batch's [B, L] or [B, 1, L] noise rows, required when
+        cfg.DATA.noise is set and ignored when it is not (as the reference ignores meta['noise'] then)."""
         self.model._check_inputs(data, rois)       # what Model_nefnet.forward rejects (float rois, L % 4, CPU tensors) is rejected here too
         if self.use_noise and noise is None:
             raise ValueError("cfg.DATA.noise is set: the step needs this batch's noise")

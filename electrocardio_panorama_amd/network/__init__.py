@@ -25,9 +25,6 @@ def build_loss(cfg):
     except KeyError:
         raise ValueError('build loss: loss name error') from None
     if cfg.MODEL.loss == "v1":
-        from .loss.losses import corr_settings, seg_settings, slope_settings, ssim_settings
-        ssim_settings(cfg, need_rois=False)          # a negative SOLVER.ssim_factor is rejected here, not at the first batch
-        seg_settings(cfg)                            # ... and a malformed SOLVER.seg_weights
-        slope_settings(cfg, need_rois=False)         # ... and a negative SOLVER.slope_factor or an unknown SOLVER.slope_loss
-        corr_settings(cfg, need_rois=False)          # ... and a negative SOLVER.corr_factor or a SOLVER.corr_eps that is not positive
+        from .loss.losses import LossPlan
+        LossPlan.from_cfg(cfg)          # a bad SOLVER.ssim_* / slope_* / corr_* / seg_weights key is rejected here, not at the first batch
     return make()

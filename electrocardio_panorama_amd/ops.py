@@ -1709,24 +1709,40 @@ def loss_bwd(pred, pred_p, pred_l, target, gscale, factors, reg_l2, use_mask, no
     return g_pred, g_p, g_l
 
 
-LOSS_SSIM_TILE = 512      # NEF_LOSS_SSIM_TILE (include/nefnet_hip.h): window starts / positions per block of the two SSIM kernels
-
-
-def _ssim_args(pred, target, factor, rois, noise):
-    """The checks and the shape the two SSIM entries share: pred / target [B, 1, L] (or [B, L]), rois None or int64 [B, 7, 2], noise None
-    or pred's elements."""
+def _row_term_args(what, pred, target, factor, rois, noise, max_rows=None, eps=None, g_pred=None, gscale=None):
+    """The checks and the shape (B, L) the entries of a row term ('ssim', 'slope', 'correlation') share: pred / target [B, 1, L] (or
+    [Q, B, 1, L], [B, L]), rois None or int64 [B, 7, 2], noise None or pred's elements.  `max_rows`: the row cap of the slope and correlation
+    kernels, which also reject an empty prediction; `eps`: the correlation term's; `g_pred`, `gscale`: a backward entry's."""
     _chk(pred), _chk(target)
-    if pred.dim() < 2 or target.numel() != pred.numel():
+    if pred.dim() < 2 or target.numel() != pred.numel() or (max_rows is not None and pred.numel() == 0):
         raise ValueError(f"prediction {tuple(pred.shape)} and target {tuple(target.shape)} must hold the same [B, 1, L] rows")
     Ln = pred.shape[-1]
     B = pred.numel() // Ln
+    if max_rows is not None and B > max_rows:
+        raise ValueError(f"prediction {tuple(pred.shape)}: {B} rows is more than the {max_rows} the {what} kernels take")
     if noise is not None and _chk(noise).numel() != pred.numel():
         raise ValueError(f"noise {tuple(noise.shape)} does not have the prediction's {tuple(pred.shape)} elements")
     if rois is not None and (_chk(rois, torch.int64).dim() != 3 or tuple(rois.shape) != (B, N_SEG, 2)):
         raise ValueError(f"rois {tuple(rois.shape)} is not [{B}, {N_SEG}, 2]")
     if not float(factor) >= 0.0:
-        raise ValueError(f"Invalid ssim factor: {factor}")
+        raise ValueError(f"Invalid {what} factor: {factor}")
+    if eps is not None and not float(eps) >= 0.0:
+        raise ValueError(f"Invalid {what} eps: {eps}")
+    if g_pred is not None and _chk(g_pred).numel() != pred.numel():
+        raise ValueError(f"g_pred {tuple(g_pred.shape)} does not have the prediction's {tuple(pred.shape)} elements")
+    if gscale is not None:
+        _chk(gscale)
     return B, Ln
+
+
+def _row_term_call(tag, A, *hbm):
+    """The entry nef_<tag> on the filled struct `A`, priced for bench.py by the tensors `hbm`."""
+    ev = _hbm(tag, *hbm)
+    _lib.check(getattr(_lib.load(), "nef_" + tag)(C.byref(A), _stream()), "nef_" + tag)
+    _done(ev)
+
+
+LOSS_SSIM_TILE = 512      # NEF_LOSS_SSIM_TILE (include/nefnet_hip.h): window starts / positions per block of the two SSIM kernels
 
 
 def loss_ssim_fwd(pred, target, losses, factor, rois=None, noise=None):
@@ -1734,17 +1750,14 @@ def loss_ssim_fwd(pred, target, losses, factor, rois=None, noise=None):
     of pred (+ noise) against target over the rows with a 7-tap window on [0, rois[i, -1, 0]), whole rows with rois None) and
     losses[0] += losses[4].  `losses`: the FIVE-element row whose first four elements loss_fwd(out=) has written.  Two launches,
     capturable."""
-    L = _lib.load()
-    B, Ln = _ssim_args(pred, target, factor, rois, noise)
+    B, Ln = _row_term_args("ssim", pred, target, factor, rois, noise)
     _chk(losses)
     assert losses.numel() == 5, losses.shape
-    n = L.nef_loss_ssim_ws_bytes(B, Ln)
+    n = _lib.load().nef_loss_ssim_ws_bytes(B, Ln)
     ws = workspace(n, pred.device)
-    ev = _hbm("loss_ssim_fwd", pred, target, noise)
     A = _lib.LossSsimArgs(pred=_p(pred), target=_p(target), noise=_p(noise), rois=_p(rois), losses=_p(losses), ws=_p(ws), ws_bytes=n,
                           gscale=None, g_pred=None, B=B, L=Ln, factor=float(factor))
-    _lib.check(L.nef_loss_ssim_fwd(C.byref(A), _stream()), "nef_loss_ssim_fwd")
-    _done(ev)
+    _row_term_call("loss_ssim_fwd", A, pred, target, noise)
     return losses
 
 
@@ -1752,17 +1765,10 @@ def loss_ssim_bwd(pred, target, g_pred, factor, rois=None, noise=None, gscale=No
     """g_pred += gscale * d(SSIM term) / d pred behind loss_bwd (nef_loss_ssim_bwd): `g_pred` is loss_bwd's first gradient, the first
     third of its [3B, 1, L] buffer.  Positions at or behind a row's end and rows without a window keep their bits.  `gscale`: None (1) or
     loss_bwd's device word.  One launch, capturable, no state: the row count is re-derived from `rois` on the device."""
-    L = _lib.load()
-    B, Ln = _ssim_args(pred, target, factor, rois, noise)
-    if _chk(g_pred).numel() != pred.numel():
-        raise ValueError(f"g_pred {tuple(g_pred.shape)} does not have the prediction's {tuple(pred.shape)} elements")
-    if gscale is not None:
-        _chk(gscale)
-    ev = _hbm("loss_ssim_bwd", pred, target, noise, g_pred, g_pred)
+    B, Ln = _row_term_args("ssim", pred, target, factor, rois, noise, g_pred=g_pred, gscale=gscale)
     A = _lib.LossSsimArgs(pred=_p(pred), target=_p(target), noise=_p(noise), rois=_p(rois), losses=None, ws=None, ws_bytes=0,
                           gscale=_p(gscale), g_pred=_p(g_pred), B=B, L=Ln, factor=float(factor))
-    _lib.check(L.nef_loss_ssim_bwd(C.byref(A), _stream()), "nef_loss_ssim_bwd")
-    _done(ev)
+    _row_term_call("loss_ssim_bwd", A, pred, target, noise, g_pred, g_pred)
     return g_pred
 
 
@@ -1886,43 +1892,21 @@ LOSS_SLOPE_TILE = 1024     # NEF_LOSS_SLOPE_TILE (include/nefnet_hip.h): differe
 LOSS_SLOPE_MAX_ROWS = 65535  # the rows are a grid's y extent
 
 
-def _slope_args(pred, target, factor, rois, noise):
-    """The checks and the shape the two slope entries share: pred / target [B, 1, L] (or [Q, B, 1, L], [B, L]; any L >= 1), rois None or
-    int64 [B, 7, 2], noise None or pred's elements."""
-    _chk(pred), _chk(target)
-    if pred.dim() < 2 or target.numel() != pred.numel() or pred.numel() == 0:
-        raise ValueError(f"prediction {tuple(pred.shape)} and target {tuple(target.shape)} must hold the same [B, 1, L] rows")
-    Ln = pred.shape[-1]
-    B = pred.numel() // Ln
-    if B > LOSS_SLOPE_MAX_ROWS:
-        raise ValueError(f"prediction {tuple(pred.shape)}: {B} rows is more than the {LOSS_SLOPE_MAX_ROWS} the slope kernels take")
-    if noise is not None and _chk(noise).numel() != pred.numel():
-        raise ValueError(f"noise {tuple(noise.shape)} does not have the prediction's {tuple(pred.shape)} elements")
-    if rois is not None and (_chk(rois, torch.int64).dim() != 3 or tuple(rois.shape) != (B, N_SEG, 2)):
-        raise ValueError(f"rois {tuple(rois.shape)} is not [{B}, {N_SEG}, 2]")
-    if not float(factor) >= 0.0:
-        raise ValueError(f"Invalid slope factor: {factor}")
-    return B, Ln
-
-
 def loss_slope_fwd(pred, target, losses, factor, l2, rois=None, noise=None):
     """The slope term of the training loss behind loss_fwd, loss_seg_fwd and loss_ssim_fwd (nef_loss_slope_fwd, include/nefnet_hip.h):
     losses[-1] = factor * mean over the rows with a difference of the row's mean |d| (`l2` False) or d^2, d(i, t) = (x[t + 1] - x[t]) -
     (y[t + 1] - y[t]) at x = pred (+ noise), y = target, t in [0, rois[i, -1, 0] - 1) (whole rows with rois None), and losses[0] +=
     losses[-1].  `losses`: the row whose front loss_fwd(out=) has written -- 5 elements (the term is losses[4]), or 6 with the SSIM term in
     losses[4] (the term is losses[5]).  Two launches, capturable."""
-    L = _lib.load()
-    B, Ln = _slope_args(pred, target, factor, rois, noise)
+    B, Ln = _row_term_args("slope", pred, target, factor, rois, noise, LOSS_SLOPE_MAX_ROWS)
     _chk(losses)
     if losses.numel() not in (5, 6):
         raise ValueError(f"losses {tuple(losses.shape)}: the slope term takes a 5-element row, or a 6-element one behind the SSIM term")
-    n = L.nef_loss_slope_ws_bytes(B, Ln)
+    n = _lib.load().nef_loss_slope_ws_bytes(B, Ln)
     ws = workspace(n, pred.device)
-    ev = _hbm("loss_slope_fwd", pred, target, noise)
     A = _lib.LossSlopeArgs(pred=_p(pred), target=_p(target), noise=_p(noise), rois=_p(rois), losses=_p(losses), ws=_p(ws), ws_bytes=n,
                            gscale=None, g_pred=None, B=B, L=Ln, factor=float(factor), l2=int(bool(l2)), slot=losses.numel() - 1)
-    _lib.check(L.nef_loss_slope_fwd(C.byref(A), _stream()), "nef_loss_slope_fwd")
-    _done(ev)
+    _row_term_call("loss_slope_fwd", A, pred, target, noise)
     return losses
 
 
@@ -1931,43 +1915,15 @@ def loss_slope_bwd(pred, target, g_pred, factor, l2, rois=None, noise=None, gsca
     loss_bwd's first gradient, the first third of its [3B, 1, L] buffer.  Positions at or behind a row's end and rows without a difference
     keep their bits.  `gscale`: None (1) or loss_bwd's device word.  One launch, capturable, no state: the row count is re-derived from
     `rois` on the device."""
-    L = _lib.load()
-    B, Ln = _slope_args(pred, target, factor, rois, noise)
-    if _chk(g_pred).numel() != pred.numel():
-        raise ValueError(f"g_pred {tuple(g_pred.shape)} does not have the prediction's {tuple(pred.shape)} elements")
-    if gscale is not None:
-        _chk(gscale)
-    ev = _hbm("loss_slope_bwd", pred, target, noise, g_pred, g_pred)
+    B, Ln = _row_term_args("slope", pred, target, factor, rois, noise, LOSS_SLOPE_MAX_ROWS, g_pred=g_pred, gscale=gscale)
     A = _lib.LossSlopeArgs(pred=_p(pred), target=_p(target), noise=_p(noise), rois=_p(rois), losses=None, ws=None, ws_bytes=0,
                            gscale=_p(gscale), g_pred=_p(g_pred), B=B, L=Ln, factor=float(factor), l2=int(bool(l2)), slot=4)
-    _lib.check(L.nef_loss_slope_bwd(C.byref(A), _stream()), "nef_loss_slope_bwd")
-    _done(ev)
+    _row_term_call("loss_slope_bwd", A, pred, target, noise, g_pred, g_pred)
     return g_pred
 
 
 LOSS_CORR_TILE = 1024      # NEF_LOSS_CORR_TILE (include/nefnet_hip.h): positions per block of the correlation term's kernels
 LOSS_CORR_MAX_ROWS = 65535  # the rows are a grid's y extent
-
-
-def _corr_args(pred, target, factor, eps, rois, noise):
-    """The checks and the shape the two correlation entries share: pred / target [B, 1, L] (or [Q, B, 1, L], [B, L]; any L >= 1), rois
-    None or int64 [B, 7, 2], noise None or pred's elements."""
-    _chk(pred), _chk(target)
-    if pred.dim() < 2 or target.numel() != pred.numel() or pred.numel() == 0:
-        raise ValueError(f"prediction {tuple(pred.shape)} and target {tuple(target.shape)} must hold the same [B, 1, L] rows")
-    Ln = pred.shape[-1]
-    B = pred.numel() // Ln
-    if B > LOSS_CORR_MAX_ROWS:
-        raise ValueError(f"prediction {tuple(pred.shape)}: {B} rows is more than the {LOSS_CORR_MAX_ROWS} the correlation kernels take")
-    if noise is not None and _chk(noise).numel() != pred.numel():
-        raise ValueError(f"noise {tuple(noise.shape)} does not have the prediction's {tuple(pred.shape)} elements")
-    if rois is not None and (_chk(rois, torch.int64).dim() != 3 or tuple(rois.shape) != (B, N_SEG, 2)):
-        raise ValueError(f"rois {tuple(rois.shape)} is not [{B}, {N_SEG}, 2]")
-    if not float(factor) >= 0.0:
-        raise ValueError(f"Invalid correlation factor: {factor}")
-    if not float(eps) >= 0.0:
-        raise ValueError(f"Invalid correlation eps: {eps}")
-    return B, Ln
 
 
 def loss_corr_fwd(pred, target, losses, factor, eps, rois=None, noise=None):
@@ -1976,19 +1932,16 @@ def loss_corr_fwd(pred, target, losses, factor, eps, rois=None, noise=None):
     coefficient (with `eps` in numerator and both variances) of x = pred (+ noise) and y = target over [0, rois[i, -1, 0]) (whole rows with
     rois None), and losses[0] += losses[-1].  `losses`: the row whose front loss_fwd(out=) has written -- 5 elements (the term is
     losses[4]), 6 or 7 with the SSIM and / or slope terms in front of it.  Two launches, capturable."""
-    L = _lib.load()
-    B, Ln = _corr_args(pred, target, factor, eps, rois, noise)
+    B, Ln = _row_term_args("correlation", pred, target, factor, rois, noise, LOSS_CORR_MAX_ROWS, eps)
     _chk(losses)
     if losses.numel() not in (5, 6, 7):
         raise ValueError(f"losses {tuple(losses.shape)}: the correlation term takes a 5-element row, or a 6- / 7-element one behind the "
                          "SSIM and slope terms")
-    n = L.nef_loss_corr_ws_bytes(B, Ln)
+    n = _lib.load().nef_loss_corr_ws_bytes(B, Ln)
     ws = workspace(n, pred.device)
-    ev = _hbm("loss_corr_fwd", pred, target, noise)
     A = _lib.LossCorrArgs(pred=_p(pred), target=_p(target), noise=_p(noise), rois=_p(rois), losses=_p(losses), ws=_p(ws), ws_bytes=n,
                           gscale=None, g_pred=None, eps=float(eps), B=B, L=Ln, factor=float(factor), slot=losses.numel() - 1)
-    _lib.check(L.nef_loss_corr_fwd(C.byref(A), _stream()), "nef_loss_corr_fwd")
-    _done(ev)
+    _row_term_call("loss_corr_fwd", A, pred, target, noise)
     return losses
 
 
@@ -1997,19 +1950,12 @@ def loss_corr_bwd(pred, target, g_pred, factor, eps, rois=None, noise=None, gsca
     (nef_loss_corr_bwd): `g_pred` is loss_bwd's first gradient, the first third of its [3B, 1, L] buffer.  Positions at or behind a row's
     end and rows with fewer than two samples keep their bits.  `gscale`: None (1) or loss_bwd's device word.  Three launches (the row
     moments are reduced again, then applied), capturable, no state from the forward."""
-    L = _lib.load()
-    B, Ln = _corr_args(pred, target, factor, eps, rois, noise)
-    if _chk(g_pred).numel() != pred.numel():
-        raise ValueError(f"g_pred {tuple(g_pred.shape)} does not have the prediction's {tuple(pred.shape)} elements")
-    if gscale is not None:
-        _chk(gscale)
-    n = L.nef_loss_corr_ws_bytes(B, Ln)
+    B, Ln = _row_term_args("correlation", pred, target, factor, rois, noise, LOSS_CORR_MAX_ROWS, eps, g_pred=g_pred, gscale=gscale)
+    n = _lib.load().nef_loss_corr_ws_bytes(B, Ln)
     ws = workspace(n, pred.device)
-    ev = _hbm("loss_corr_bwd", pred, target, noise, pred, target, noise, g_pred, g_pred)
     A = _lib.LossCorrArgs(pred=_p(pred), target=_p(target), noise=_p(noise), rois=_p(rois), losses=None, ws=_p(ws), ws_bytes=n,
                           gscale=_p(gscale), g_pred=_p(g_pred), eps=float(eps), B=B, L=Ln, factor=float(factor), slot=4)
-    _lib.check(L.nef_loss_corr_bwd(C.byref(A), _stream()), "nef_loss_corr_bwd")
-    _done(ev)
+    _row_term_call("loss_corr_bwd", A, pred, target, noise, pred, target, noise, g_pred, g_pred)
     return g_pred
 
 

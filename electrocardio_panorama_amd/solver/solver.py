@@ -279,12 +279,12 @@ class Solver:
                     scalars += list(aug_metrics)
                     names += ['psnr_gen_aug', 'psnr_reg_aug', 'ssim_gen_aug', 'ssim_reg_aug']
                     msg += '\npsnr_gen_aug: {}, psnr_reg_aug: {}, ssim_gen_aug:{}, ssim_reg_aug:{}'.format(*aug_metrics)
-            # SOLVER.ssim_factor / SOLVER.slope_factor / SOLVER.corr_factor: the terms that are on sit behind the four (train) / five (test: the rest_out term)
-            # elements of every loss row, in this order
-            for k, key in enumerate(self._tail_terms()):
+            # the plan's tail terms that are on sit behind the four (train) / five (test: the rest_out term) elements of every loss row
+            for k, term in enumerate(self._plan().tail):
+                key = term.name
                 scalars.append(float(tl[4 + k]))
                 names.append('train_loss_' + key)
-                msg += '\nloss_{} (factor {}): train {}'.format(key, self.cfg.SOLVER.get(key + '_factor', 0.0), float(tl[4 + k]))
+                msg += '\nloss_{} (factor {}): train {}'.format(key, term.factor, float(tl[4 + k]))
                 if dl_test is not None:
                     scalars.append(float(te[5 + k]))
                     names.append('test_loss_' + key)
@@ -325,19 +325,18 @@ class Solver:
         on = float(self.cfg.SOLVER.get('ema_decay', 0.0)) > 0 and bool(self.cfg.SOLVER.get('ema_eval', True))
         return on and (optimizer is None or getattr(optimizer, 'ema_decay', 0.0) > 0)
 
+    def _plan(self):
+        """The loss's LossPlan as `self.cfg` says now; everything off unless the loss is losswrapper."""
+        from ..network.loss.losses import LossPlan
+        return LossPlan.from_cfg(self.cfg) if self.cfg.MODEL.loss == 'v1' else LossPlan()
+
     def _seg_weights(self):
-        """SOLVER.seg_weights as the loss reads it (a 7-tuple, or None for off) when the loss is losswrapper."""
-        if self.cfg.MODEL.loss != 'v1':
-            return None
-        from ..network.loss.losses import seg_settings
-        return seg_settings(self.cfg)
+        """SOLVER.seg_weights as the loss reads it (a 7-tuple, or None for off)."""
+        return self._plan().seg_weights
 
     def _tail_terms(self):
-        """The loss terms behind the reference's elements of a loss row, in the row's order: 'ssim' (SOLVER.ssim_factor > 0), then 'slope'
-        (SOLVER.slope_factor > 0), then 'corr' (SOLVER.corr_factor > 0), when the loss is losswrapper."""
-        if self.cfg.MODEL.loss != 'v1':
-            return []
-        return [key for key in ('ssim', 'slope', 'corr') if float(self.cfg.SOLVER.get(key + '_factor', 0.0)) > 0]
+        """The names of the loss terms behind the reference's elements of a loss row, in the row's order."""
+        return self._plan().names
 
     def _slope_message(self):
         return 'psnr_slope_gen: {}, psnr_slope_reg: {}'.format(self.last_slope_psnr['gen'], self.last_slope_psnr['reg'])
@@ -421,14 +420,8 @@ class Solver:
         return gen_num, whole
 
     def _loss_rois(self, rois):
-        """`rois=` for the loss when SOLVER.ssim_factor, SOLVER.slope_factor, SOLVER.corr_factor or SOLVER.seg_weights is on and the loss takes it
-        (losswrapper); nothing otherwise."""
-        if self.cfg.MODEL.loss == 'v1' and (float(self.cfg.SOLVER.get('ssim_factor', 0.0)) > 0 or
-                                            float(self.cfg.SOLVER.get('slope_factor', 0.0)) > 0 or
-                                            float(self.cfg.SOLVER.get('corr_factor', 0.0)) > 0 or
-                                            len(self.cfg.SOLVER.get('seg_weights', None) or ()) > 0):
-            return {'rois': rois}
-        return {}
+        """`rois=` for the loss when a term of its plan is on (losswrapper takes it then); nothing otherwise."""
+        return {'rois': rois} if self._plan().any_on else {}
 
     def _graphed_step(self, optim, data, keep):
         """The hipGraph stepper for this batch, or None when the step runs eagerly: `cfg.SOLVER.graph` False, the per-view host lists are wanted (the graph returns losses only), the
