@@ -110,6 +110,25 @@ class LossCorrArgs(C.Structure):
                 ("g_pred", p), ("eps", C.c_double), ("B", i32), ("L", i32), ("factor", f32), ("slot", i32)]
 
 
+class LocateScoreArgs(C.Structure):
+    """Mirror of `nef_locate_score_args` (include/nefnet_hip.h)."""
+    _fields_ = [("pred", p), ("obs", p), ("rois", p), ("scores", p), ("pred_bs", i64), ("pred_as", i64), ("obs_bs", i64), ("obs_rs", i64),
+                ("sc_bs", i64), ("sc_rs", i64), ("col_off", i64), ("eps", C.c_double),
+                ("B", i32), ("A", i32), ("R", i32), ("L", i32), ("mode", i32), ("group", i32)]
+
+
+class LocateBestArgs(C.Structure):
+    """Mirror of `nef_locate_best_args` (include/nefnet_hip.h)."""
+    _fields_ = [("scores", p), ("cands", p), ("best_score", p), ("best_theta", p), ("best_index", p), ("sc_bs", i64), ("sc_rs", i64),
+                ("index_base", i64), ("B", i32), ("R", i32), ("A", i32), ("per_pair", i32), ("init", i32), ("keep_index", i32)]
+
+
+class LocateCandsArgs(C.Structure):
+    """Mirror of `nef_locate_cands_args` (include/nefnet_hip.h)."""
+    _fields_ = [("best_theta", p), ("best_index", p), ("cands", p), ("s1", f32), ("s2", f32), ("ph1", f32), ("ph2", f32),
+                ("B", i32), ("R", i32), ("radius", i32), ("reserved0", i32)]
+
+
 class AugmentArgs(C.Structure):
     """Mirror of `nef_augment_args` (include/nefnet_hip.h)."""
     _fields_ = [("x", p), ("rois", p), ("y", p), ("seed_dev", p), ("seed", C.c_uint64),
@@ -216,6 +235,12 @@ SIGNATURES = {
     "nef_loss_corr_bwd": (i32, [C.POINTER(LossCorrArgs), p]),
     "nef_loss_corr_ws_bytes": (sz, [i32, i32]),
     "nef_loss_corr_args_bytes": (sz, []),
+    "nef_locate_score": (i32, [C.POINTER(LocateScoreArgs), p]),
+    "nef_locate_score_args_bytes": (sz, []),
+    "nef_locate_best": (i32, [C.POINTER(LocateBestArgs), p]),
+    "nef_locate_best_args_bytes": (sz, []),
+    "nef_locate_cands": (i32, [C.POINTER(LocateCandsArgs), p]),
+    "nef_locate_cands_args_bytes": (sz, []),
     "nef_augment": (i32, [C.POINTER(AugmentArgs), p]),
     "nef_augment_args_bytes": (sz, []),
     "nef_sgd_momentum": (i32, [p, p, p, i64, f32, f32, f32, i32, p, p, p, p]),
@@ -294,6 +319,9 @@ def load():
                                ("nef_loss_seg_args", lib.nef_loss_seg_args_bytes(), LossSegArgs),
                                ("nef_loss_slope_args", lib.nef_loss_slope_args_bytes(), LossSlopeArgs),
                                ("nef_loss_corr_args", lib.nef_loss_corr_args_bytes(), LossCorrArgs),
+                               ("nef_locate_score_args", lib.nef_locate_score_args_bytes(), LocateScoreArgs),
+                               ("nef_locate_best_args", lib.nef_locate_best_args_bytes(), LocateBestArgs),
+                               ("nef_locate_cands_args", lib.nef_locate_cands_args_bytes(), LocateCandsArgs),
                                ("nef_augment_args", lib.nef_augment_args_bytes(), AugmentArgs)):
         if size != C.sizeof(mirror):
             raise NefLibraryError(f"{LIB_PATH}: {name} is {size} bytes, the binding mirrors {C.sizeof(mirror)}; rebuild with "

@@ -170,6 +170,21 @@ _DEFAULTS = {
         # True: the test phase also reports the mean correlation coefficient (nef_view_corr_metrics beside nef_view_metrics), logged as
         # corr_gen / corr_reg with the view split of psnr_gen / psnr_reg; best_valid stays on psnr_gen.  False: no launch, no buffer
         "corr_eval": False,
+        # True: Solver.val also locates every rest view of every test batch from the batch's input leads (Solver.locate: one encoder pass and
+        # one level-0 panorama per batch, scored against all rest views on the device, then coarse-to-fine refinement) and prints the mean and
+        # median angular error in degrees and the share of views found within one level-0 step on both axes -- locate_err1_gen /
+        # locate_err2_gen / locate_hit_gen and the _reg forms, with the view split of psnr_gen / psnr_reg; best_valid and every other number
+        # keep their bits.  One rank only.  False: no launch, no buffer, the keys below are not looked at
+        "locate_eval": False,
+        # level 0: locate_grid[0] x locate_grid[1] angles over locate_range_deg (degrees; the default is the span of the nominal lead table,
+        # in steps of 15 and 10 degrees); an axis with one point is pinned at the range's start
+        "locate_grid": [9, 19],
+        "locate_range_deg": [[60, 180], [-90, 90]],
+        # 'corr': 1 - the correlation coefficient (eps: corr_eps) -- no gain or offset of the located lead changes it; 'mse'
+        "locate_score": "corr",
+        # refinement levels behind level 0, each (2 locate_radius + 1)^2 candidates around the running best at half the previous step
+        "locate_levels": 3,
+        "locate_radius": 2,
     },
 }
 

@@ -731,6 +731,61 @@ def gen_ecg(P, Bf, z1, z2b, query_thetas, rois, chunk=8, half=False):
     return sweep(P, Bf, latent, query_thetas, False, chunk)
 
 
+LOCATE_VIEW_BYTES = 1 << 30      # level-0 views alive at a time when `chunk` is left to locate()
+
+
+def locate_latent(z1, z2b, rois):
+    """The decoder's latent [B, 256, T] from phase 'gen's pair: Model_nefnet returns z1 [B, 128V, T] and the pooled z2 [B, 128V, 7, 32]
+    (un-pooled and averaged over the leads here, as gen_ecg does); Model_nefnet2 returns the two lead means [B, 128, T] themselves."""
+    if z2b.dim() == 3:
+        return torch.cat([z1, z2b], dim=1).contiguous()
+    z2r = ops.roi_unpool_fwd(z2b.contiguous(), rois, z1.shape[2])
+    return ops.lead_mean(z1, z2r, z1.shape[1] // 128)
+
+
+def locate(P, Bf, z1, z2b, observed, rois, grid, score="corr", levels=3, radius=2, crop=True, eps=1e-8, chunk=None, half=False,
+           return_scores=False, return_trace=False):
+    """The viewing angle of each observed row [B, R, L] by a scored panorama search (locate.py; include/nefnet_hip.h,
+    nef_locate_score_args): the latent is formed once, as gen_ecg does; level 0 sweeps the grid's angles in chunks of at most `chunk`
+    (views of one chunk exist at a time) and scores each chunk into its columns of scores [B, R, A], one nef_locate_best picks the winners;
+    every further level is nef_locate_cands, one sweep of the R * (2 radius + 1)^2 per-sample angles, a grouped score and a merge.
+    Everything is stream-ordered: nothing is read by the host.  Returns (theta, score, index, theta0, score0, scores or None, trace or
+    None) with the R dimension kept."""
+    from . import locate as _loc
+    ops.BATCH_HINT = z1.shape[0]
+    ops.amax_roll()
+    latent = locate_latent(z1, z2b, rois)
+    B, R, Ln = observed.shape
+    dev = latent.device
+    row_rois = rois if crop else None
+    th_host = grid.thetas()
+    placeholder = (float(th_host[0, 0]), float(th_host[0, 1]))                    # the grid's first angle: finite, for pairs without a score
+    thetas = torch.from_numpy(th_host).to(dev)                                    # [A, 2]
+    A = thetas.shape[0]
+    if chunk is None:
+        chunk = max(1, min(A, LOCATE_VIEW_BYTES // (4 * B * Ln)))
+    scores = torch.empty(B, R, A, device=dev, dtype=torch.float64)
+    for a0 in range(0, A, chunk):
+        n = min(chunk, A - a0)
+        th = thetas[a0:a0 + n].unsqueeze(0).expand(B, n, 2).contiguous()
+        views = sweep(P, Bf, latent, th, False, min(n, 8), half)                  # [B, n, L]
+        ops.locate_score(views, observed, row_rois, score, eps, out=scores, col=a0)
+        del views
+    best = ops.locate_best(scores, thetas)
+    theta0, score0 = best[1].clone(), best[0].clone()
+    trace = [] if return_trace else None
+    G = (2 * radius + 1) ** 2
+    for s1, s2 in _loc.level_steps(grid, levels):
+        cands = ops.locate_cands(best[1], best[2], s1, s2, radius, placeholder)
+        views = sweep(P, Bf, latent, cands, False, 8, half)                       # [B, R * G, L]
+        sc = ops.locate_score(views, observed, row_rois, score, eps, group=G)     # [B, R, G]
+        del views
+        ops.locate_best(sc, cands, best, keep_index=True)
+        if trace is not None:
+            trace.append(dict(cands=cands, scores=sc, theta=best[1].clone(), score=best[0].clone(), steps=(float(s1), float(s2))))
+    return best[1], best[0], best[2], theta0, score0, (scores if return_scores else None), trace
+
+
 def _head_bwd(P, sv, g_outs, grads, side, relu_z1=False):
     """Back through decoder passes, Standin mixes and mlp2: returns the gradients wrt the lead-blocked z1 and z2r -- or, where the
     forward mixed straight from the segment tensor z2b, wrt z1 and z2b: (gz1, gz2r, None) or (gz1, None, gz2b)."""

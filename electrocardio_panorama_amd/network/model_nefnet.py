@@ -250,6 +250,45 @@ class Model_nefnet(nn.Module):
                                   self._f32(query_theta), rois.detach().to(torch.int64).contiguous(),
                                   half=self._half_sweep())
 
+    def locate(self, x, input_thetas, rois, observed, *, grid=None, score='corr', levels=3, radius=2, crop=True, eps=None, chunk=None,
+               return_scores=False, return_trace=False):
+        """At which angle was `observed` recorded?  (No counterpart in the reference.)  x [B, V, L], input_thetas [B, V, 2], rois
+        [B, 7, 2] as for forward; observed fp32 [B, L] or [B, R, L] in the loaders' normalisation.  One encoder pass (phase 'gen'), a
+        level-0 panorama over `grid` (locate.Grid; None: 9 x 19 over LEAD_THETA's span) scored against every observed row ('corr': 1 - r,
+        which no gain or offset of the observed lead changes; 'mse'), the deterministic arg-best, and `levels` rounds of (2 radius + 1)^2
+        candidates around it at halving steps -- all on the device and stream-ordered (engine.locate).  crop: rows end at rois[b, -1, 0].
+        eps: 'corr's eps (None: 1e-8, SOLVER.corr_eps' default).  chunk: level-0 angles decoded at a time.  Honours panorama_dtype;
+        the model is put back in the mode it was in.  Returns a locate.LocateResult."""
+        from .. import locate as _loc
+        st = _loc.check_settings(grid, score, levels, radius, eps)
+        if crop and rois is None:
+            raise ValueError("locate: crop=True needs rois (the rows end at rois[b, -1, 0]); pass crop=False for whole rows")
+        if rois is None:
+            raise ValueError("locate: rois [B, 7, 2] is needed by the encoder pass, with or without crop")
+        if observed.dim() not in (2, 3) or observed.shape[0] != x.shape[0] or observed.shape[-1] != x.shape[-1] or observed.numel() == 0:
+            raise ValueError(f"locate: observed {tuple(observed.shape)} is neither [B, L] nor [B, R, L] for x {tuple(x.shape)}")
+        if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1):
+            raise ValueError(f"locate: chunk must be an integer >= 1, got {chunk!r}")
+        half = self._half_sweep()
+        squeeze = observed.dim() == 2
+        obs = self._f32(observed.unsqueeze(1) if squeeze else observed)
+        was_training = self.training
+        self.eval()
+        try:
+            z1, z2 = self.forward(x, input_thetas, self._f32(input_thetas)[:, 0], rois, phase='gen')
+            with torch.no_grad(), ops.amax_scope((self._nef_scope, False)):
+                out = engine.locate(self._params_by_name(), self._buffers_by_name(), self._f32(z1), self._f32(z2), obs,
+                                    rois.detach().to(torch.int64).contiguous(), st.grid, score=st.score, levels=st.levels,
+                                    radius=st.radius, crop=bool(crop), eps=1e-8 if eps is None else float(eps), chunk=chunk, half=half,
+                                    return_scores=return_scores, return_trace=return_trace)
+        finally:
+            self.train(was_training)
+        theta, sc, index, theta0, score0, scores, trace = out
+        if squeeze:
+            theta, sc, index, theta0, score0 = theta[:, 0], sc[:, 0], index[:, 0], theta0[:, 0], score0[:, 0]
+            scores = None if scores is None else scores[:, 0]
+        return _loc.LocateResult(theta, sc, index, theta0, score0, scores, trace)
+
 
 class Model_nefnet2(Model_nefnet):
     """Nef-Net2 (reference codes/network/model_nefnet2.py:63-228): one single-lead encoder shared by every input lead,

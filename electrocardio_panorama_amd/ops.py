@@ -2109,6 +2109,98 @@ def view_corr_metrics(pred, gt, rois=None):
     return mom, cnt
 
 
+LOCATE_MODES = {"mse": 0, "corr": 1}     # nef_locate_score_args.mode
+
+
+def _rows3(t, dtype, what):
+    """A [B, N, L] device tensor whose rows are dense (a slice of a larger tensor is fine): (batch stride, row stride) in elements."""
+    if not (t.is_cuda and t.dtype == dtype and t.dim() == 3 and t.numel() > 0 and (t.shape[2] == 1 or t.stride(2) == 1)):
+        raise ValueError(f"{what} must be a non-empty {dtype} device tensor [B, N, L] with dense rows, got {tuple(t.shape)} {t.dtype} "
+                         f"strides {t.stride()}")
+    return t.stride(0), t.stride(1)
+
+
+def locate_score(pred, obs, rois=None, mode="corr", eps=1e-8, group=0, out=None, col=0):
+    """Score every candidate view against the observed rows (nef_locate_score; lower is better): pred fp32 [B, A, L] and obs fp32
+    [B, R, L] (rows dense, batch and row strides free: chunks of larger tensors are taken as they are), rois None (whole rows) or int64
+    [B, 7, 2].  mode 'mse': the mean squared difference over t in [0, n_b); 'corr': 1 - r with r of view_corr_metrics' moments and `eps`;
+    +inf for a row that does not count (n_b < 1 / n_b < 2) and for a NaN.  group 0: every candidate against every observed row ->
+    [B, R, A]; group G > 0: A == R * G and candidate a is scored against row a // G -> [B, R, G].  `out`: an fp64 [B, R, N] tensor (or a
+    slice of one) whose columns [col, col + A or G) are written; None: a new tensor of exactly that width.  Returns `out`."""
+    L = _lib.load()
+    if mode not in LOCATE_MODES:
+        raise ValueError(f"score must be one of {sorted(LOCATE_MODES)}, got {mode!r}")
+    p_bs, p_as = _rows3(pred, torch.float32, "pred")
+    o_bs, o_rs = _rows3(obs, torch.float32, "obs")
+    B, A, Ln = pred.shape
+    R = obs.shape[1]
+    if obs.shape[0] != B or obs.shape[2] != Ln:
+        raise ValueError(f"obs {tuple(obs.shape)} does not match pred {tuple(pred.shape)}: [B, R, L] with the same B and L")
+    if rois is not None and (_chk(rois, torch.int64).dim() != 3 or tuple(rois.shape) != (B, N_SEG, 2)):
+        raise ValueError(f"rois {tuple(rois.shape)} is not [{B}, {N_SEG}, 2]")
+    group = int(group)
+    if group < 0 or (group and R * group != A):
+        raise ValueError(f"group {group}: pred has {A} candidates per sample, not {R} x {group}")
+    width = group if group else A
+    if out is None:
+        out, col = torch.empty(B, R, width, device=pred.device, dtype=torch.float64), 0
+    s_bs, s_rs = _rows3(out, torch.float64, "out")
+    if out.shape[0] != B or out.shape[1] != R or col < 0 or col + width > out.shape[2]:
+        raise ValueError(f"out {tuple(out.shape)} does not hold columns [{col}, {col + width}) of [{B}, {R}, .]")
+    a = _lib.LocateScoreArgs(pred=_p(pred), obs=_p(obs), rois=_p(rois), scores=_p(out), pred_bs=p_bs, pred_as=p_as, obs_bs=o_bs, obs_rs=o_rs,
+                             sc_bs=s_bs, sc_rs=s_rs, col_off=int(col), eps=float(eps), B=B, A=A, R=R, L=Ln, mode=LOCATE_MODES[mode],
+                             group=group)
+    _lib.check(L.nef_locate_score(C.byref(a), _stream()), "nef_locate_score")
+    return out
+
+
+def locate_best(scores, cands, best=None, index_base=0, keep_index=False):
+    """The deterministic arg-best of scores fp64 [B, R, A] (rows dense; a column slice is fine) over the matching candidates
+    (nef_locate_best): cands fp32 [A, 2], shared, or [B, R * A, 2], the pair's own.  A strictly lower score replaces the running best,
+    ties go to the earliest candidate, NaN counts as +inf.  `best` None: returns a new (score fp64 [B, R], theta fp32 [B, R, 2], index
+    int64 [B, R]) -- index -1, theta NaN, score +inf where no score is finite; otherwise the three are merged into in place and
+    returned.  A winner's index is index_base + its column; keep_index (levels >= 1): the index is left alone and a pair at -1 stays."""
+    L = _lib.load()
+    s_bs, s_rs = _rows3(scores, torch.float64, "scores")
+    B, R, A = scores.shape
+    _chk(cands)
+    per_pair = cands.dim() == 3
+    if tuple(cands.shape) != ((B, R * A, 2) if per_pair else (A, 2)):
+        raise ValueError(f"cands {tuple(cands.shape)} is neither [{A}, 2] nor [{B}, {R * A}, 2]")
+    init = best is None
+    if init:
+        if keep_index:
+            raise ValueError("keep_index needs a running best")
+        best = (torch.empty(B, R, device=scores.device, dtype=torch.float64), torch.empty(B, R, 2, device=scores.device, dtype=torch.float32),
+                torch.empty(B, R, device=scores.device, dtype=torch.int64))
+    bs, bt, bi = best
+    _chk(bs, torch.float64), _chk(bt), _chk(bi, torch.int64)
+    if tuple(bs.shape) != (B, R) or tuple(bt.shape) != (B, R, 2) or tuple(bi.shape) != (B, R):
+        raise ValueError(f"best {tuple(bs.shape)}, {tuple(bt.shape)}, {tuple(bi.shape)} is not [{B}, {R}], [{B}, {R}, 2], [{B}, {R}]")
+    a = _lib.LocateBestArgs(scores=_p(scores), cands=_p(cands), best_score=_p(bs), best_theta=_p(bt), best_index=_p(bi), sc_bs=s_bs,
+                            sc_rs=s_rs, index_base=int(index_base), B=B, R=R, A=A, per_pair=int(per_pair), init=int(init),
+                            keep_index=int(bool(keep_index)))
+    _lib.check(L.nef_locate_best(C.byref(a), _stream()), "nef_locate_best")
+    return bs, bt, bi
+
+
+def locate_cands(best_theta, best_index, s1, s2, radius, placeholder):
+    """The next level's candidates around the running best (nef_locate_cands): fp32 [B, R * (2 radius + 1)^2, 2], candidate
+    r * G + i * (2 radius + 1) + k = best_theta[b, r] + (float(i - radius) * s1, float(k - radius) * s2) in fp32 (one rounded multiply, one
+    rounded add); a pair whose best_index is -1 is centred on `placeholder` (two finite floats) instead."""
+    L = _lib.load()
+    _chk(best_theta), _chk(best_index, torch.int64)
+    if best_theta.dim() != 3 or best_theta.shape[2] != 2 or tuple(best_index.shape) != tuple(best_theta.shape[:2]) or best_index.numel() == 0:
+        raise ValueError(f"best_theta {tuple(best_theta.shape)} / best_index {tuple(best_index.shape)} are not [B, R, 2] / [B, R]")
+    B, R = best_index.shape
+    W = 2 * int(radius) + 1
+    out = torch.empty(B, R * W * W, 2, device=best_theta.device, dtype=torch.float32)
+    a = _lib.LocateCandsArgs(best_theta=_p(best_theta), best_index=_p(best_index), cands=_p(out), s1=float(s1), s2=float(s2),
+                             ph1=float(placeholder[0]), ph2=float(placeholder[1]), B=B, R=R, radius=int(radius), reserved0=0)
+    _lib.check(L.nef_locate_cands(C.byref(a), _stream()), "nef_locate_cands")
+    return out
+
+
 def sgd_momentum(p, g, buf, lr, mu, gscale, first_step, skip=None, lr_dev=None):
     """`skip`: a one-element fp32 device view (h2_taint's output, summed over the ranks): > 0 leaves p and buf untouched and counts
     the step in h2_skipped().  `lr_dev`: a one-element fp32 device tensor that replaces `lr` at run time (captured steps)."""

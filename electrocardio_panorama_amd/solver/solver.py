@@ -32,7 +32,10 @@ train_loss_slope / test_loss_slope; the test phase reports the PSNR of the first
 batch) as psnr_slope_gen / psnr_slope_reg, in `Solver.last_slope_psnr`.
 `SOLVER.corr_factor` / `SOLVER.corr_eval` (no counterpart in the reference): the loss gains 1 - the Pearson correlation coefficient, logged
 as train_loss_corr / test_loss_corr; the test phase reports the mean coefficient (`nef_view_corr_metrics`, one more launch per batch) as
-corr_gen / corr_reg, in `Solver.last_corr`."""
+corr_gen / corr_reg, in `Solver.last_corr`.
+`SOLVER.locate_eval` (no counterpart in the reference; locate.py): `Solver.val` also locates every rest view of every test batch from the
+batch's input leads (`Solver.locate`: Model_nefnet.locate with observed = rest_view, truth = rest_theta) and prints the angular error
+as locate_err1_* / locate_err2_* / locate_hit_* with the gen / reg view split, in `Solver.last_locate`."""
 import contextlib
 import json
 import os
@@ -44,6 +47,7 @@ from .. import _env
 import torch.distributed as dist
 
 from .. import augment, engine, ops, parallel, views
+from .. import locate as _locate
 from ..network import build_model, build_loss
 from ..utils import CheckPointer
 from .optim_scheduler import get_optimizer, get_lr_scheduler
@@ -186,6 +190,9 @@ class Solver:
         # SOLVER.corr_eval: the test phase also fills last_corr = {'gen': number, 'reg': number}
         self.corr_eval = bool(cfg.SOLVER.get('corr_eval', False))
         self.last_corr = None
+        # SOLVER.locate_eval: val() also fills last_locate = {'locate_err1_gen': ..., ...} (Solver.locate); invalid keys are rejected here
+        self.locate_eval = _locate.from_cfg(cfg) is not None
+        self.last_locate = None
         self._init_model_device()
         if self.desc != 'debug' and use_tensorboardx and _is_main():       # solver.py:23-26
             self.summary_writer = make_summary_writer(os.path.join(cfg.output_dir, 'tf_logs'))
@@ -397,7 +404,61 @@ class Solver:
             print(self._corr_message())
         if self.augment is not None and self.augment.eval:
             print('psnr_gen_aug:{}, psnr_reg_aug:{}, ssim_gen_aug:{}, ssim_reg_aug:{}'.format(*self._aug_eval(dl_test)))
+        if self.locate_eval:
+            self.locate(dl_test)
+            print(self._locate_message())
         return psnr_gen, psnr_reg, ssim_gen, ssim_reg
+
+    def _locate_message(self):
+        return '\n'.join(', '.join('{}:{}'.format(k, v) for k, v in self.last_locate.items() if k.endswith(split)) for split in ('_gen', '_reg'))
+
+    def locate(self, dl_test):
+        """SOLVER.locate_*: locate every rest view of every test batch from the batch's input leads -- observed = rest_view, the truth is
+        rest_theta; one encoder pass and one level-0 panorama per batch, for all rest views together (Model_nefnet.locate), rows cropped as
+        the test phase's metrics crop them.  Fills and returns last_locate: the mean (locate_err1_*, locate_err2_*) and median
+        (locate_err1_med_*, locate_err2_med_*) of |theta - truth| on both axes in degrees, and locate_hit_*, the share of views found
+        within one level-0 step on both axes, for the view split of psnr_gen / psnr_reg (`*` = gen, reg); a view without a finite score
+        counts as a miss and is left out of the errors.  The settings are the config's whether or not locate_eval is on.  The run goes on
+        as if this pass had not happened: Python's `random` stream, the model's forward counter, its mode and the eval-mode operand
+        magnitudes of the split-fp16 call sites are put back.  One rank only."""
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("SOLVER.locate_eval under data parallelism: the located views are not gathered over the ranks")
+        kw = _locate.from_cfg(self.cfg, force=True)
+        gen_num, whole = self._gen_num()
+        found_s, truth_s = _HostSink(), _HostSink()
+        state, calls, amax0 = random.getstate(), getattr(self.model, '_drop_calls', 0), ops.amax_snapshot(self.device)
+        was_training = self.model.training
+        try:
+            with torch.no_grad():
+                for meta in dl_test:
+                    source_data, rois, input_theta = self._to_device(meta)[:3]
+                    rest_view = torch.as_tensor(meta['rest_view']).to(self.device, torch.float32).contiguous()
+                    res = self.model.locate(source_data, input_theta, rois, rest_view, crop=not whole, **kw)
+                    found_s.add(res.theta)
+                    truth_s.add(torch.as_tensor(meta['rest_theta']).to(self.device, torch.float32).contiguous())
+        finally:
+            random.setstate(state)
+            self.model._drop_calls = calls
+            ops.amax_restore(self.device, amax0)
+            self.model.train(was_training)
+        found = [a.astype(np.float64) for a in found_s.arrays()]
+        truth = [a.astype(np.float64) for a in truth_s.arrays()]
+        d1, d2 = (np.degrees(d) for d in kw['grid'].steps)
+        self.last_locate = {}
+        for split in ('gen', 'reg'):
+            sl = slice(None) if whole else (slice(-gen_num, None) if split == 'gen' else slice(None, -gen_num))
+            err = [np.degrees(np.abs(f[:, sl] - t[:, sl])).reshape(-1, 2) for f, t in zip(found, truth)]
+            err = np.concatenate(err) if err else np.zeros((0, 2))
+            ok = ~np.isnan(err).any(axis=1)
+            good = err[ok]
+            nan = float('nan')
+            self.last_locate['locate_err1_' + split] = float(good[:, 0].mean()) if good.size else nan
+            self.last_locate['locate_err1_med_' + split] = float(np.median(good[:, 0])) if good.size else nan
+            self.last_locate['locate_err2_' + split] = float(good[:, 1].mean()) if good.size else nan
+            self.last_locate['locate_err2_med_' + split] = float(np.median(good[:, 1])) if good.size else nan
+            hit = ok & (np.nan_to_num(err[:, 0], nan=np.inf) <= d1) & (np.nan_to_num(err[:, 1], nan=np.inf) <= d2)
+            self.last_locate['locate_hit_' + split] = float(hit.mean()) if err.shape[0] else nan
+        return self.last_locate
 
     def _to_device(self, meta):
         dev = self.device

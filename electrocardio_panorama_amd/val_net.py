@@ -1,5 +1,6 @@
 """`python -m electrocardio_panorama_amd.val_net --config-file config/nef_net.yml [--epoch N]` -- reference
-codes/val_net.py:9-48: build the test loader, load `best_valid.pkl` (or `epoch_N.pkl`) and print PSNR / SSIM."""
+codes/val_net.py:9-48: build the test loader, load `best_valid.pkl` (or `epoch_N.pkl`) and print PSNR / SSIM.  `--locate` (no counterpart in
+the reference) switches SOLVER.locate_eval on: the angular error with which the model finds its own held-out leads is printed too."""
 import argparse
 import os
 
@@ -28,12 +29,15 @@ def run(argv=None):
     parser.add_argument('--config-file', default="", metavar="FILE", help="path to config file", type=str)
     parser.add_argument('--epoch', default=-1, type=int)
     parser.add_argument('--ds', default='tianchi', type=str)
+    parser.add_argument('--locate', action='store_true', help="SOLVER.locate_eval: also locate every rest view and print the angular error")
     parser.add_argument('opts', nargs=argparse.REMAINDER, help="KEY VALUE overrides")
     args = parser.parse_args(argv)
     if args.config_file != '':
         cfg.merge_from_file(resolve_config_path(args.config_file))
     if args.opts:
         cfg.merge_from_list(args.opts)
+    if args.locate:
+        cfg.SOLVER.locate_eval = True
     cfg.desc = args.config_file.split('/')[-1].replace('.yml', '') or cfg.desc
     cfg.output_dir = os.path.join(cfg.output_dir, cfg.desc)
     return main(cfg, epoch=args.epoch)

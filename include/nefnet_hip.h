@@ -34,7 +34,7 @@ extern "C" {
 typedef void* nef_stream_t;
 
 /* ABI version of this header; bumped on any signature change. */
-int nef_abi_version(void);   /* 22 (+ nef_flatten_acc, nef_lr_sched / nef_lr_sched_args_bytes, nef_loss_ssim_fwd / nef_loss_ssim_bwd / nef_loss_ssim_ws_bytes / nef_loss_ssim_args_bytes, nef_loss_seg_fwd / nef_loss_seg_bwd / nef_loss_seg_ws_bytes / nef_loss_seg_args_bytes / nef_view_seg_metrics, nef_loss_slope_fwd / nef_loss_slope_bwd / nef_loss_slope_ws_bytes / nef_loss_slope_args_bytes / nef_view_slope_metrics, nef_loss_corr_fwd / nef_loss_corr_bwd / nef_loss_corr_ws_bytes / nef_loss_corr_args_bytes / nef_view_corr_metrics: additions only, the number stays; a binding finds a library without them by the missing symbol.  Weight packing is ONE entry, nef_pack_weights(nef_pack_desc*, n), + nef_pack_bytes(nef_pack_desc*) for the size of any operand.  ABI <= 21 had nef_pack_weight, nef_pack_weight_wino, nef_pack_weight_wino4, nef_pack_weight_h2 and nef_pack_weight_h2_bytes: each is one descriptor with wino = 0 / 1 / 2 / 3); 21 (BatchNorm backward is ONE entry on a nef_bn_bwd_args struct, + nef_bn_bwd_args_bytes; nef_mix_bwd takes `up` / `shared` flags; nef_outconv_fwd / nef_outconv_bwd_weight take the prologue arguments.  ABI <= 20 had nef_bn_relu_bwd_phase_major, nef_bn_relu_bwd_up, nef_bn_relu_bwd_combine3, nef_bn_relu_bwd_combine3_phase_major, nef_bn_relu_bwd_outconv, nef_bn_bwd_outconv_ws_bytes, nef_mix_bwd_up, nef_mix_bwd_shared, nef_mix_bwd_shared_up, nef_outconv_fwd_pro and nef_outconv_bwd_weight_pro); 20 (the weight gradient is ONE entry, nef_conv_bwd_weight(nef_bww_args*), + nef_bww_args_bytes; its _pro, _wino4, _h2 and _h2_ws_bytes variants are gone); 19 (+ nef_adam, nef_h2_tail_census, nef_bwd_weight_clamp_ends: additions only; the kernel-form option entry points of 16 and nef_upsample2_aff_fwd are gone; + nef_debug_spin_us); 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + kernel-form option entry points); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + the split-fp16 weight gradient, now form 3); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, the transposed F(3,4) / F(4,4) entry, now form 4, covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
+int nef_abi_version(void);   /* 22 (+ nef_flatten_acc, nef_lr_sched / nef_lr_sched_args_bytes, nef_loss_ssim_fwd / nef_loss_ssim_bwd / nef_loss_ssim_ws_bytes / nef_loss_ssim_args_bytes, nef_loss_seg_fwd / nef_loss_seg_bwd / nef_loss_seg_ws_bytes / nef_loss_seg_args_bytes / nef_view_seg_metrics, nef_loss_slope_fwd / nef_loss_slope_bwd / nef_loss_slope_ws_bytes / nef_loss_slope_args_bytes / nef_view_slope_metrics, nef_loss_corr_fwd / nef_loss_corr_bwd / nef_loss_corr_ws_bytes / nef_loss_corr_args_bytes / nef_view_corr_metrics, nef_locate_score / nef_locate_best / nef_locate_cands and their _args_bytes: additions only, the number stays; a binding finds a library without them by the missing symbol.  Weight packing is ONE entry, nef_pack_weights(nef_pack_desc*, n), + nef_pack_bytes(nef_pack_desc*) for the size of any operand.  ABI <= 21 had nef_pack_weight, nef_pack_weight_wino, nef_pack_weight_wino4, nef_pack_weight_h2 and nef_pack_weight_h2_bytes: each is one descriptor with wino = 0 / 1 / 2 / 3); 21 (BatchNorm backward is ONE entry on a nef_bn_bwd_args struct, + nef_bn_bwd_args_bytes; nef_mix_bwd takes `up` / `shared` flags; nef_outconv_fwd / nef_outconv_bwd_weight take the prologue arguments.  ABI <= 20 had nef_bn_relu_bwd_phase_major, nef_bn_relu_bwd_up, nef_bn_relu_bwd_combine3, nef_bn_relu_bwd_combine3_phase_major, nef_bn_relu_bwd_outconv, nef_bn_bwd_outconv_ws_bytes, nef_mix_bwd_up, nef_mix_bwd_shared, nef_mix_bwd_shared_up, nef_outconv_fwd_pro and nef_outconv_bwd_weight_pro); 20 (the weight gradient is ONE entry, nef_conv_bwd_weight(nef_bww_args*), + nef_bww_args_bytes; its _pro, _wino4, _h2 and _h2_ws_bytes variants are gone); 19 (+ nef_adam, nef_h2_tail_census, nef_bwd_weight_clamp_ends: additions only; the kernel-form option entry points of 16 and nef_upsample2_aff_fwd are gone; + nef_debug_spin_us); 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + kernel-form option entry points); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + the split-fp16 weight gradient, now form 3); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, the transposed F(3,4) / F(4,4) entry, now form 4, covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
 
 /* Diagnostics: `wgs` workgroups busy for `us` microseconds on `stream` (a stand-in for a collective's time on the chip:
  * parallel.DryCollective, bench.py --dry-collective).  0 <= us <= 50000, 1 <= wgs <= 64. */
@@ -747,6 +747,102 @@ size_t nef_loss_corr_args_bytes(void);
  * Fixed-order block sums, no atomics.  pred, gt, mom or cnt NULL: NEF_E_NULL; B, Q or L <= 0, B * Q > 2^31 - 1: NEF_E_SHAPE. */
 int nef_view_corr_metrics(const float* pred, const float* gt, const int64_t* rois, double* mom, int32_t* cnt, int B, int Q, int L,
                           nef_stream_t stream);
+
+/* Locating a lead's viewing angle by a scored panorama search (Model_nefnet.locate, engine.locate; no counterpart in the reference):
+ * every (sample, candidate angle) view of a sweep is scored against the sample's observed rows, the best candidate is kept under a
+ * deterministic rule, and the next level's candidates are laid around it.  Three entries, additions to ABI 22; all of them check their
+ * arguments in front of any device work, read nothing on the host and allocate nothing (stream-ordered, capturable).
+ *
+ * Row length: n_i = clamp(rois[i, -1, 0], 0, L) (nef_row_end), or L with rois NULL.
+ * Score of the fp32 view p against the fp32 observed row y on [0, n_i), formed in fp64 from the fp32 values; lower is better:
+ *   mode 0 ('mse'):  (1/n) sum (p_t - y_t)^2;  +inf with n_i < 1.
+ *   mode 1 ('corr'): 1 - r, r as nef_loss_corr_args defines it (sums on values shifted by each row's first sample, u = p - p_0,
+ *     w = y - y_0; r = (c + eps) / sqrt((vx + eps) (vy + eps)));  +inf with n_i < 2.  No gain or offset of y changes it.
+ *   A NaN score is stored as +inf.  p == y gives exactly 0 in both modes.
+ * Best rule: candidates in order, a strictly lower score replaces the running best (ties go to the earliest candidate); with no finite
+ *   score: index -1, theta NaN, score +inf.
+ *
+ * nef_locate_score: one wave per (sample, candidate) row, four rows of one sample per 256-thread block.  A row of up to
+ *   NEF_LOCATE_SEG positions stays in the wave's registers while the wave walks the R observed rows (small: they hit L2), so every view is
+ *   read from HBM once; a longer row is walked segment by segment per observed row.  Lane l owns the float4 groups q with q % 64 == l, in
+ *   rising order, and the last partial group's elements one by one: 16-byte loads where a row's pointer is 16-byte aligned, scalar loads
+ *   otherwise, the SAME order of additions on both, then a fixed butterfly over the 64 lanes -- a row's score depends on that row alone, not
+ *   on A, the chunking or the alignment.  No atomics, no LDS, no scratch.
+ *   group == 0: every candidate against every observed row, scores[b, r, col_off + a]; group == G > 0: A == R * G, candidate a belongs
+ *   to observed row a / G, scores[b, a / G, col_off + a % G].
+ *   args, pred, obs or scores NULL: NEF_E_NULL; B, A, R or L < 1, L > 2^30, B * ceil(A / 4) > 2^31 - 1, group < 0, A != R * group under grouping, a
+ *   negative stride or column offset, a mode other than 0 / 1, eps not finite or <= 0: NEF_E_SHAPE.
+ * nef_locate_best: one wave per (sample, observed row) applies the best rule to scores[b, r, 0 .. A) (a slice: sc_bs / sc_rs strides) and
+ *   the matching candidates -- a shared table cands [A, 2] (per_pair 0) or the pair's own cands [B, R * A, 2] rows [r * A, (r + 1) * A)
+ *   (per_pair 1) -- and merges into best_score [B, R] fp64, best_theta [B, R, 2] fp32, best_index [B, R] int64, in place.  init 1: the
+ *   three are written from scratch (nothing is read); init 0: the running best is kept unless a candidate is strictly lower.
+ *   keep_index 0: a winner's index is index_base + its column (level 0, chunk by chunk); keep_index 1 (later levels): best_index is not
+ *   written, and a pair whose best_index is -1 is left as it is.
+ *   NULL pointers: NEF_E_NULL; B, R or A < 1, B * R > 2^31 - 1, a negative stride or index_base: NEF_E_SHAPE.
+ * nef_locate_cands: cands[b, r * G + i * (2 radius + 1) + k] = centre + ((float)(i - radius) * s1, (float)(k - radius) * s2),
+ *   G = (2 radius + 1)^2, i-major, each coordinate one rounded fp32 multiply and one rounded fp32 add (no contraction), so the middle
+ *   candidate is the centre itself.  centre = best_theta[b, r], or (ph1, ph2) -- a finite placeholder -- where best_index[b, r] < 0.
+ *   Angles are neither wrapped nor clamped.  NULL pointers: NEF_E_NULL; B or R < 1, radius < 0 or > 16, B * R * G > 2^31 - 1, a step or
+ *   placeholder that is not finite: NEF_E_SHAPE. */
+#define NEF_LOCATE_SEG 1024
+typedef struct nef_locate_score_args {
+    const float* pred;      /* views [B, A, L]: element (b, a, t) at pred[b * pred_bs + a * pred_as + t] */
+    const float* obs;       /* observed rows [B, R, L]: (b, r, t) at obs[b * obs_bs + r * obs_rs + t] */
+    const int64_t* rois;    /* NULL (whole rows), or [B, 7, 2] */
+    double* scores;         /* (b, r, j) at scores[b * sc_bs + r * sc_rs + col_off + j] */
+    int64_t pred_bs;        /* element strides, >= 0 */
+    int64_t pred_as;
+    int64_t obs_bs;
+    int64_t obs_rs;
+    int64_t sc_bs;
+    int64_t sc_rs;
+    int64_t col_off;        /* first column written, >= 0 */
+    double eps;             /* mode 1: > 0 and finite (checked in both modes) */
+    int32_t B;              /* samples, >= 1 */
+    int32_t A;              /* candidates per sample, >= 1 */
+    int32_t R;              /* observed rows per sample, >= 1 */
+    int32_t L;              /* row length, >= 1 */
+    int32_t mode;           /* 0 'mse', 1 'corr' */
+    int32_t group;          /* 0: all pairs; G > 0: A == R * G, candidate a against row a / G */
+} nef_locate_score_args;
+int nef_locate_score(const nef_locate_score_args* a, nef_stream_t stream);
+/* sizeof(nef_locate_score_args) as the library was built. */
+size_t nef_locate_score_args_bytes(void);
+typedef struct nef_locate_best_args {
+    const double* scores;   /* (b, r, j) at scores[b * sc_bs + r * sc_rs + j], j < A */
+    const float* cands;     /* per_pair 0: [A, 2]; per_pair 1: [B, R * A, 2] */
+    double* best_score;     /* [B, R] */
+    float* best_theta;      /* [B, R, 2] */
+    int64_t* best_index;    /* [B, R] */
+    int64_t sc_bs;          /* element strides, >= 0 */
+    int64_t sc_rs;
+    int64_t index_base;     /* keep_index 0: a winner's index is index_base + j; >= 0 */
+    int32_t B;              /* samples, >= 1 */
+    int32_t R;              /* observed rows per sample, >= 1 */
+    int32_t A;              /* candidates per (sample, observed row), >= 1 */
+    int32_t per_pair;       /* 0 shared candidates, 1 per-pair candidates */
+    int32_t init;           /* 1: initialise, 0: merge into the running best */
+    int32_t keep_index;     /* 1: best_index is read only (levels >= 1) */
+} nef_locate_best_args;
+int nef_locate_best(const nef_locate_best_args* a, nef_stream_t stream);
+/* sizeof(nef_locate_best_args) as the library was built. */
+size_t nef_locate_best_args_bytes(void);
+typedef struct nef_locate_cands_args {
+    const float* best_theta;    /* [B, R, 2] */
+    const int64_t* best_index;  /* [B, R] */
+    float* cands;               /* [B, R * (2 radius + 1)^2, 2] */
+    float s1;                   /* this level's steps, finite */
+    float s2;
+    float ph1;                  /* the placeholder centre of a pair without a finite score, finite */
+    float ph2;
+    int32_t B;                  /* samples, >= 1 */
+    int32_t R;                  /* observed rows per sample, >= 1 */
+    int32_t radius;             /* 0 .. 16 */
+    int32_t reserved0;          /* 0 */
+} nef_locate_cands_args;
+int nef_locate_cands(const nef_locate_cands_args* a, nef_stream_t stream);
+/* sizeof(nef_locate_cands_args) as the library was built. */
+size_t nef_locate_cands_args_bytes(void);
 
 /* Input-lead augmentation of the train step (cfg.DATA.aug_*; no counterpart in the reference, whose only augmentation is the host-side
  * angle jitter): y = a corrupted copy of the input leads x [B, V, L]; x is never written.  Every draw comes from the counter RNG of the
