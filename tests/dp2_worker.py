@@ -12,9 +12,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import dp_common as dpc                                                      # noqa: E402
 from electrocardio_panorama_amd import parallel, synth                       # noqa: E402
 from electrocardio_panorama_amd.network import build_loss, build_model       # noqa: E402
 from electrocardio_panorama_amd.solver import Solver                         # noqa: E402
@@ -22,10 +21,8 @@ from electrocardio_panorama_amd.solver.optim_scheduler import get_optimizer  # n
 from oracle import hashweights as hw                                         # noqa: E402
 from test_model_gpu import make_cfg, oracle_replaying                        # noqa: E402
 
-out_dir = sys.argv[1]
-rank, world, local = parallel.init_from_env()
-assert world == 2 and dist.is_initialized() and local == (0 if os.environ.get("NEF_SHARE_GPU") == "1" else rank)
-dev = torch.device("cuda", local)
+rank, world, local, dev, out_dir = dpc.start()
+assert local == (0 if os.environ.get("NEF_SHARE_GPU") == "1" else rank)
 
 
 def flat_params(model):
@@ -49,7 +46,7 @@ idx = parallel.shard_indices(B, rank, world)
 masks = hw.hashed_masks(V, B, L // 4)
 shard_masks = {k: v[idx[0]:idx[-1] + 1].contiguous() for k, v in masks.items()}
 model.dropout_masks = {k: v.to(dev) for k, v in shard_masks.items()}
-b = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in shard.items()}
+b = dpc.shard_to_device(full, rank, world, dev)
 optim = get_optimizer(cfg, model.parameters())
 random.seed(seed)
 outs = model(b["data"], b["input_theta"], b["target_theta"], b["rois"], phase="train")
@@ -138,10 +135,9 @@ more = [synth.make_batch(B, V, L, seed=seed + 1 + s, Q=2) for s in range(2)]
 sol.model.keep_saved = False
 sol.model.last_saved = None
 res2 = sol.run_one_epoch(parallel.ShardedLoader(more), "train", optim)
-np.savez(os.path.join(out_dir, f"solver_rank{rank}.npz"), params_1=params_1, params_3=flat_params(sol.model),
-         losses=np.array(res[0] + res2[0]), oracle_losses=np.array([float(v) for v in rl]), avg_grad=avg_grad,
-         oracle_grad=oracle_grad, live=np.array(live), flips=np.array(dec.total_flips()))
-dist.barrier()
+dpc.save("solver", params_1=params_1, params_3=flat_params(sol.model), losses=np.array(res[0] + res2[0]),
+         oracle_losses=np.array([float(v) for v in rl]), avg_grad=avg_grad, oracle_grad=oracle_grad, live=np.array(live),
+         flips=np.array(dec.total_flips()))
 
 # ---------------------------------------------------------------- part 3: the same three iterations through the GRAPHED Solver
 # (cfg.SOLVER.graph: forward + loss + backward captured once per shape, the flat gradient as ONE all-reduce behind the replay,
@@ -156,9 +152,7 @@ random.seed(seed)
 res_g = sol_g.run_one_epoch(parallel.ShardedLoader([full]), "train", optim_g, collect_views=False)
 res_g2 = sol_g.run_one_epoch(parallel.ShardedLoader(more), "train", optim_g, collect_views=False)
 assert sol_g._graph_stepper is not None and sol_g._graph_stepper.calls == 3
-np.savez(os.path.join(out_dir, f"graph_rank{rank}.npz"), params_3=flat_params(sol_g.model),
-         losses=np.array(res_g[0] + res_g2[0]))
-dist.barrier()
+dpc.save("graph", params_3=flat_params(sol_g.model), losses=np.array(res_g[0] + res_g2[0]))
 
 # ---------------------------------------------------------------- part 4: a split-fp16 launch clamps on ONE rank
 # (simulated: rank 1 bumps its device clamp counter -- exactly what conv_h2_kernel's x_clamped does).  The taint word travels in
@@ -184,7 +178,5 @@ for label, solver, opt in (("eager", sol, optim), ("graph", sol_g, optim_g)):
     solver.run_one_epoch(parallel.ShardedLoader([full]), "train", opt, collect_views=False)
     taint[label + "_resumed"] = bool(not np.array_equal(before, flat_params(solver.model)))
     taint[label + "_params"] = flat_params(solver.model)
-np.savez(os.path.join(out_dir, f"taint_rank{rank}.npz"), **{k: np.array(v) for k, v in taint.items()})
-dist.barrier()
-dist.destroy_process_group()
-print("DP2_OK", rank)
+dpc.save("taint", **{k: np.array(v) for k, v in taint.items()})
+dpc.finish("DP2")

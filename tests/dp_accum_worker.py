@@ -9,23 +9,14 @@ import random
 import sys
 
 import numpy as np
-import torch
 import torch.distributed as dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import dp_common as dpc                                                      # noqa: E402
 from electrocardio_panorama_amd import parallel, synth                       # noqa: E402
 from electrocardio_panorama_amd.network import build_loss                    # noqa: E402
-from electrocardio_panorama_amd.solver import Solver                         # noqa: E402
-from electrocardio_panorama_amd.solver.optim_scheduler import FusedSGD, get_optimizer  # noqa: E402
-from oracle import hashweights as hw                                         # noqa: E402
-from test_model_gpu import make_cfg                                          # noqa: E402
 
-out_dir = sys.argv[1]
-rank, world, local = parallel.init_from_env()
-assert world == 2 and dist.is_initialized()
-dev = torch.device("cuda", local)
+rank, world, local, dev, out_dir = dpc.start()
 # The learning rate is this test's to choose, and the displacement check against fp64 decides it: fp32 parameters of rms 5.8e-2 carry a
 # rounding of 2^-24 * |p| whatever the update computes, and the gradients of these batches have rms 2.7e-4, so the correctly rounded
 # result alone sits at 4.5e-6 / lr of the displacement lr * mean(g).  lr = 1 puts that floor at half the 1e-5 bar (lr = 0.1 would put it
@@ -35,22 +26,8 @@ fulls = [synth.make_batch(B, V, L, seed=seed + s, Q=2) for s in range(steps)]
 
 
 def solver(graph):
-    cfg = make_cfg(V, lr=LR)
-    cfg.SOLVER["accum_steps"] = K
-    cfg.SOLVER["graph"] = graph
-    sol = Solver(cfg, use_tensorboardx=False)
-    sol.model.load_state_dict({**hw.hashed_params(V), **hw.hashed_buffers()})
-    sol.model.dropout_p = 0.0
-    opt = get_optimizer(cfg, sol.model.parameters())
-    assert isinstance(opt, FusedSGD) and opt.accum_steps == K
-    return cfg, sol, opt
+    return dpc.make_solver(V, graph, lr=LR, solver=dict(accum_steps=K), check=lambda opt: opt.accum_steps == K)
 
-
-def flat(opt, key):
-    return opt._flat[0][key].detach().cpu().numpy().copy()
-
-
-real_all_reduce = dist.all_reduce
 
 # ---------------------------------------------------------------- part 1: eager
 cfg, sol, opt = solver(False)
@@ -59,19 +36,13 @@ lossf = build_loss(cfg)
 grads, reduced, p_first = [], [], None
 random.seed(seed)
 for s in range(steps):
-    b = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in parallel.shard_batch(fulls[s], rank, world).items()}
+    b = dpc.shard_to_device(fulls[s], rank, world, dev)
     o = sol.model(b["data"], b["input_theta"], b["target_theta"], b["rois"], phase="train")
     lossf(o[0], o[1], o[2], b["target_view"].unsqueeze(1), cfg)[0].backward()
-    live = [n for n, p in sol.model.named_parameters() if p.grad is not None]
-    grads.append(torch.cat([p.grad.detach().reshape(-1) for p in sol.model.parameters() if p.grad is not None]).cpu().numpy())
+    live, grad = dpc.live_grad(sol.model)
+    grads.append(grad)
     assert parallel._EARLY["pending"] is None          # an accumulating optimiser does not opt in to the early bucket
-    sizes = []
-
-    def counting(t, *a, **k):
-        sizes.append(t.numel())
-        return real_all_reduce(t, *a, **k)
-    dist.all_reduce = counting
-    try:
+    with dpc.all_reduce_sizes() as sizes:
         opt.step()
         if s == steps - 1:
             assert opt.window_open
@@ -79,22 +50,18 @@ for s in range(steps):
             opt.flush()                                    # the epoch ends inside a window: one micro-batch, gscale 1 / (world * 1)
             flush_sizes = sizes[n_before:]
             del sizes[n_before:]
-    finally:
-        dist.all_reduce = real_all_reduce
     opt.zero_grad()
     reduced.append(max(sizes) if sizes else 0)
     if s == K - 1:
         assert not opt.window_open
-        p_first = flat(opt, "p")
-np.savez(os.path.join(out_dir, f"eager_rank{rank}.npz"), grads=np.stack(grads), live=np.array(live), p=flat(opt, "p"),
-         buf=flat(opt, "buf"), p_first=p_first, reduced=np.array(reduced), flush_reduced=np.array(flush_sizes),
-         n=np.array(opt._flat[0]["p"].numel()), lr=np.array(LR),
-         p0=torch.cat([hw.hashed_params(V)[n].reshape(-1) for n in live]).numpy())
-dist.barrier()
+        p_first = dpc.flat(opt, "p")
+dpc.save("eager", grads=np.stack(grads), live=np.array(live), p=dpc.flat(opt, "p"), buf=dpc.flat(opt, "buf"), p_first=p_first,
+         reduced=np.array(reduced), flush_reduced=np.array(flush_sizes), n=np.array(opt._flat[0]["p"].numel()), lr=np.array(LR),
+         p0=dpc.live_p0(live, V))
 
 # ---------------------------------------------------------------- part 2: the same batches as one epoch of the graphed Solver
 cfg, sol_g, opt_g = solver(True)
-calls = []
+calls, real_all_reduce = [], dist.all_reduce
 
 
 def counting_g(t, *a, **k):
@@ -112,7 +79,5 @@ st = sol_g._graph_stepper
 assert st is not None and st.calls == steps and len(st.slots) == 1 and not opt_g.window_open
 assert isinstance(next(iter(st.slots.values()))["graph"], tuple)      # two graphs per micro-batch
 assert sol_g.last_updates == (2, 3)
-np.savez(os.path.join(out_dir, f"graph_rank{rank}.npz"), p=flat(opt_g, "p"), buf=flat(opt_g, "buf"), calls=np.array(calls))
-dist.barrier()
-dist.destroy_process_group()
-print("DPACCUM_OK", rank)
+dpc.save("graph", p=dpc.flat(opt_g, "p"), buf=dpc.flat(opt_g, "buf"), calls=np.array(calls))
+dpc.finish("DPACCUM")

@@ -4,25 +4,16 @@ ops.H2_TAIL_FRAC below 0, so every weight-gradient site of rank 0 routes to the 
 the middle of the backward pass) and none of rank 1 does.  Two train steps of the Solver, eager and graphed; saved per rank: the
 parameters, the sites routed during the run and the weight-gradient sites of the model."""
 import os
-import random
 import sys
 
 import numpy as np
 import torch
-import torch.distributed as dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-from electrocardio_panorama_amd import ops, parallel, synth                  # noqa: E402
-from electrocardio_panorama_amd.solver import Solver                         # noqa: E402
-from electrocardio_panorama_amd.solver.optim_scheduler import get_optimizer  # noqa: E402
-from oracle import hashweights as hw                                         # noqa: E402
-from test_model_gpu import make_cfg                                          # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import dp_common as dpc                                                      # noqa: E402
+from electrocardio_panorama_amd import ops, synth                            # noqa: E402
 
-out_dir = sys.argv[1]
-rank, world, local = parallel.init_from_env()
-assert world == 2 and dist.is_initialized()
+rank, world, local, dev, out_dir = dpc.start()
 V, B, L, seed, steps = 3, 4, 512, 5, 2
 fulls = [synth.make_batch(B, V, L, seed=seed + s, Q=2) for s in range(steps)]
 ops._H2_MIN_WGS = 0
@@ -37,22 +28,11 @@ def routed_total():
 
 
 for graph in (False, True):
-    cfg = make_cfg(V, lr=0.05)
-    cfg.SOLVER["graph"] = graph
-    sol = Solver(cfg, use_tensorboardx=False)
-    sol.model.load_state_dict({**hw.hashed_params(V), **hw.hashed_buffers()})
-    sol.model.dropout_p = 0.0
-    opt = get_optimizer(cfg, sol.model.parameters())
+    cfg, sol, opt = dpc.make_solver(V, graph, lr=0.05)
     n0 = routed_total()
-    for s in range(steps):
-        random.seed(seed + s)
-        sol.run_one_epoch(parallel.ShardedLoader([fulls[s]]), "train", opt, collect_views=False)
-    assert (getattr(sol, "_graph_stepper", None) is not None) == graph
+    dpc.one_batch_epochs(sol, opt, fulls, seed, graph)
     blob = sol.model.h2_state()
-    np.savez(os.path.join(out_dir, f"{'graph' if graph else 'eager'}_rank{rank}.npz"),
-             p=torch.cat([p.detach().reshape(-1) for p in sol.model.parameters()]).cpu().numpy(),
+    dpc.save("graph" if graph else "eager", p=torch.cat([p.detach().reshape(-1) for p in sol.model.parameters()]).cpu().numpy(),
              moved=np.array(routed_total() - n0), n_bww=np.array(sum(1 for k in blob["keys"] if k[2] == "conv_bwd_weight")),
              routed=np.array(sum(blob.get("fp32", []))))
-    dist.barrier()
-dist.destroy_process_group()
-print("DPH2TAIL_OK", rank)
+dpc.finish("DPH2TAIL")

@@ -4,24 +4,15 @@ Two train steps with cfg.DATA.noise on this rank's shard of the global batch -- 
 (parallel.ShardedLoader) -- through the Solver, once eagerly and once through the graphed step; the parent compares the two paths, the
 ranks, and each rank's first-step losses with the oracle on that rank's shard."""
 import os
-import random
 import sys
 
 import numpy as np
-import torch.distributed as dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import dp_common as dpc                                                      # noqa: E402
 from electrocardio_panorama_amd import parallel, synth                       # noqa: E402
-from electrocardio_panorama_amd.solver import Solver                         # noqa: E402
-from electrocardio_panorama_amd.solver.optim_scheduler import FusedSGD, get_optimizer  # noqa: E402
-from oracle import hashweights as hw                                         # noqa: E402
-from test_model_gpu import make_cfg                                          # noqa: E402
 
-out_dir = sys.argv[1]
-rank, world, local = parallel.init_from_env()
-assert world == 2 and dist.is_initialized()
+rank, world, local, dev, out_dir = dpc.start()
 V, B, L, seed, steps = 3, 4, 512, 5, 2
 fulls = []
 for s in range(steps):
@@ -30,27 +21,13 @@ for s in range(steps):
     fulls.append(b)
 
 for graph in (False, True):
-    cfg = make_cfg(V, lr=0.1, noise=True)
-    cfg.SOLVER["graph"] = graph
-    sol = Solver(cfg, use_tensorboardx=False)
-    sol.model.load_state_dict({**hw.hashed_params(V), **hw.hashed_buffers()})
-    sol.model.dropout_p = 0.0
-    opt = get_optimizer(cfg, sol.model.parameters())
-    assert isinstance(opt, FusedSGD)
+    cfg, sol, opt = dpc.make_solver(V, graph, lr=0.1, data=dict(noise=True))
     losses = []
-    for s in range(steps):
-        random.seed(seed + s)
-        losses += sol.run_one_epoch(parallel.ShardedLoader([fulls[s]]), "train", opt, collect_views=False)[0]
-    st = getattr(sol, "_graph_stepper", None)
-    assert (st is not None) == graph
+    st = dpc.one_batch_epochs(sol, opt, fulls, seed, graph, each=lambda res: losses.extend(res[0]))
     if graph:
-        assert st.calls == steps and len(st.slots) == 1
+        assert len(st.slots) == 1
         slot = next(iter(st.slots.values()))
         mine = parallel.shard_batch(fulls[-1], rank, world)["noise"]
         assert np.array_equal(slot["noise"].cpu().numpy().reshape(mine.shape), mine)       # this rank's rows, not the other's
-    fl = opt._flat[0]
-    np.savez(os.path.join(out_dir, f"{'graph' if graph else 'eager'}_rank{rank}.npz"), p=fl["p"].detach().cpu().numpy(),
-             buf=fl["buf"].detach().cpu().numpy(), losses=np.array(losses))
-    dist.barrier()
-dist.destroy_process_group()
-print("DPNOISE_OK", rank)
+    dpc.save("graph" if graph else "eager", **dpc.flats(opt, "p", "buf"), losses=np.array(losses))
+dpc.finish("DPNOISE")

@@ -10,25 +10,20 @@ import sys
 
 import numpy as np
 import torch
-import torch.distributed as dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import dp_common as dpc                                                      # noqa: E402
 from electrocardio_panorama_amd import ops, parallel, synth                  # noqa: E402
 from electrocardio_panorama_amd.solver import Solver                         # noqa: E402
 from electrocardio_panorama_amd.solver.optim_scheduler import FusedSGD, get_optimizer  # noqa: E402
 from test_model_gpu import make_cfg                                          # noqa: E402
 
-out_dir = sys.argv[1]
-rank, world, local = parallel.init_from_env()
-assert world == 2 and dist.is_initialized()
-dev = torch.device("cuda", local)
+rank, world, local, dev, out_dir = dpc.start()
 V, B, L, seed, LR = 3, 4, 512, 5, 0.1
 fulls = [synth.make_batch(B, V, L, seed=seed + s, Q=2) for s in range(6)]
 
 
-def solver(graph):
+def solver(graph):          # (the default weights, not the hashed ones: not dpc.make_solver)
     cfg = make_cfg(V, lr=LR)
     cfg.SOLVER.update(graph=graph, warmup_updates=2, lr_shape="cosine", total_updates=6, lr_floor=0.1)
     torch.manual_seed(1234)                     # the same default weights on both ranks
@@ -41,9 +36,8 @@ def solver(graph):
 
 def record(opt, into, tag):
     t, lr = opt.lr_state()
-    fl = opt._flat[0]
-    into.update({f"p_{tag}": fl["p"].detach().cpu().numpy().copy(), f"buf_{tag}": fl["buf"].detach().cpu().numpy().copy(),
-                 f"t_{tag}": np.array(t), f"lr_{tag}": np.array(lr, dtype=np.float32)})
+    into.update({f"p_{tag}": dpc.flat(opt, "p"), f"buf_{tag}": dpc.flat(opt, "buf"), f"t_{tag}": np.array(t),
+                 f"lr_{tag}": np.array(lr, dtype=np.float32)})
 
 
 for graph in (False, True):
@@ -62,7 +56,5 @@ for graph in (False, True):
     random.seed(seed + 2)
     sol.run_one_epoch(parallel.ShardedLoader(fulls[5:]), "train", opt, collect_views=False)
     record(opt, z, "clean")
-    np.savez(os.path.join(out_dir, f"{'graph' if graph else 'eager'}_rank{rank}.npz"), base=np.array(LR), **z)
-    dist.barrier()
-dist.destroy_process_group()
-print("DPSCHED_OK", rank)
+    dpc.save("graph" if graph else "eager", base=np.array(LR), **z)
+dpc.finish("DPSCHED")

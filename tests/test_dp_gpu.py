@@ -14,26 +14,16 @@ import numpy as np
 import pytest
 import torch
 
-from util import free_port, rel
+from dp_launch import ROOT, TESTS, run_ranks, world2_env
+from util import rel
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _env(port):
-    return dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), WORLD_SIZE="2", NEF_DIST_BACKEND="gloo",
-                NEF_SHARE_GPU="1", NEF_TEST_HOOKS="1", PYTHONPATH=ROOT, HSA_ENABLE_IPC_MODE_LEGACY="0")
 
 
 @pytest.fixture(scope="module")
 def dp_run(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("dp2"))
-    script = os.path.join(ROOT, "tests", "dp2_worker.py")
-    env = _env(free_port())
-    procs = [subprocess.Popen([sys.executable, script, out], env=dict(env, RANK=str(r), LOCAL_RANK=str(r)),
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for r in range(2)]
-    logs = [p.communicate(timeout=900)[0] for p in procs]
-    assert all(p.returncode == 0 for p in procs), "\n".join(lg[-3000:] for lg in logs)
+    run_ranks(os.path.join(TESTS, "dp2_worker.py"), out, timeout=900)
     return out
 
 
@@ -131,14 +121,7 @@ def test_world2_rccl_on_two_devices(tmp_path):
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two HIP devices (RCCL between two ranks)")
     out = str(tmp_path)
-    env = _env(free_port())
-    env.pop("NEF_DIST_BACKEND")
-    env.pop("NEF_SHARE_GPU")
-    script = os.path.join(ROOT, "tests", "dp2_worker.py")
-    procs = [subprocess.Popen([sys.executable, script, out], env=dict(env, RANK=str(r), LOCAL_RANK=str(r)),
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for r in range(2)]
-    logs = [p.communicate(timeout=900)[0] for p in procs]
-    assert all(p.returncode == 0 for p in procs), "\n".join(lg[-3000:] for lg in logs)
+    run_ranks(os.path.join(TESTS, "dp2_worker.py"), out, timeout=900, env=world2_env(share_gpu=False))
     a, b = (np.load(os.path.join(out, f"step_rank{r}.npz")) for r in range(2))
     assert np.array_equal(a["params"], b["params"]) and np.array_equal(a["avg_grad"], b["avg_grad"])
     want = 0.5 * (a["oracle_grad"].astype(np.float64) + b["oracle_grad"].astype(np.float64))
@@ -189,11 +172,10 @@ def test_world2_clamp_on_one_rank_skips_the_step_on_both(dp_run):
 
 def test_bench_two_ranks_prints_one_json_line():
     """bench.py's torchrun branch (barrier, max-over-ranks timing, whole-job value) with world_size 2."""
-    port = free_port()
+    env = world2_env()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
+           "127.0.0.1", "--master-port", env["MASTER_PORT"], os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
            "--warmup", "1", "--batch", "8", "--len", "1000", "--leads", "8"]
-    env = _env(port)
     env.pop("WORLD_SIZE")
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
@@ -209,7 +191,7 @@ def test_bench_two_ranks_prints_one_json_line():
 def test_bench_self_launches_two_ranks():
     """Plain `python bench.py --gpus 2` (no torchrun environment -- how the round driver calls it): bench.py re-executes
     itself under torch.distributed.run and rank 0 still prints exactly one JSON line for the whole job."""
-    env = _env(0)
+    env = world2_env()
     for k in ("WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8",
@@ -228,7 +210,7 @@ def test_bench_self_launches_eight_ranks():
     NEF_SHARE_GPU / NEF_DIST_BACKEND test hooks) -- the launcher, the rendezvous, the 8-way shard arithmetic, the two-graph split
     capture with the early bucket between the replays, max-over-ranks timing and the single JSON line are the production path;
     only the transport differs from RCCL over xGMI.  Tiny shape (batch 2 per rank, L = 512)."""
-    env = _env(0)
+    env = world2_env()
     for k in ("WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--batch", "2",

@@ -3,37 +3,22 @@ sharded with the batch, the graphed step (two graphs with the early bucket's all
 bit, and every rank's first-step losses are the oracle's on that rank's shard with that shard's noise."""
 import os
 import random
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-from util import free_port
+from dp_launch import TESTS, load_ranks, run_ranks
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def dp_noise(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("dp_noise"))
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()), WORLD_SIZE="2", NEF_DIST_BACKEND="gloo",
-               NEF_SHARE_GPU="1", NEF_TEST_HOOKS="1", PYTHONPATH=ROOT, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    script = os.path.join(ROOT, "tests", "dp_noise_worker.py")
-    procs = [subprocess.Popen([sys.executable, script, out], env=dict(env, RANK=str(r), LOCAL_RANK=str(r)),
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for r in range(2)]
-    try:
-        logs = [p.communicate(timeout=600)[0] for p in procs]
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-                p.wait()
-    assert all(p.returncode == 0 for p in procs), "\n".join(lg[-3000:] for lg in logs)
-    return [dict(np.load(os.path.join(out, f"eager_rank{r}.npz"))) for r in range(2)], \
-        [dict(np.load(os.path.join(out, f"graph_rank{r}.npz"))) for r in range(2)]
+    run_ranks(os.path.join(TESTS, "dp_noise_worker.py"), out)
+    z = load_ranks(out)
+    return z["eager"], z["graph"]
 
 
 def test_world2_noise_graphed_equals_eager_and_ranks_agree(dp_noise):

@@ -3,16 +3,13 @@ tests/test_dp_accum_gpu.py): four updates, eagerly and through the two-graph dat
 and parameters, the graphed run equals the eager one, and a taint raised on rank 1 only skips the update on both ranks and advances the
 schedule on neither."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from util import free_port
+from dp_launch import TESTS, load_ranks, run_ranks
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 POINTS = ("four", "tainted", "clean")
 KEYS = ("p", "buf", "t", "lr")
 
@@ -20,20 +17,8 @@ KEYS = ("p", "buf", "t", "lr")
 @pytest.fixture(scope="module")
 def dp_sched(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("dp_sched"))
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()), WORLD_SIZE="2", NEF_DIST_BACKEND="gloo",
-               NEF_SHARE_GPU="1", NEF_TEST_HOOKS="1", PYTHONPATH=ROOT, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    script = os.path.join(ROOT, "tests", "dp_sched_worker.py")
-    procs = [subprocess.Popen([sys.executable, script, out], env=dict(env, RANK=str(r), LOCAL_RANK=str(r)),
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for r in range(2)]
-    try:
-        logs = [p.communicate(timeout=600)[0] for p in procs]      # every child has its own time limit
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-                p.wait()
-    assert all(p.returncode == 0 for p in procs), "\n".join(lg[-3000:] for lg in logs)
-    return {mode: [dict(np.load(os.path.join(out, f"{mode}_rank{r}.npz"))) for r in range(2)] for mode in ("eager", "graph")}
+    run_ranks(os.path.join(TESTS, "dp_sched_worker.py"), out)
+    return load_ranks(out)
 
 
 @pytest.mark.parametrize("mode", ["eager", "graph"])

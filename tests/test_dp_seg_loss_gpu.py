@@ -2,67 +2,35 @@
 one FusedSGD step with the segment weights on.  Both ranks end bit for bit alike, the graphed step equals the eager one, the update is
 p0 - lr * mean of the two ranks' recorded gradients in fp64, and each rank's term 3 is the weighted mean of its own shard."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+import dp_checks
 import seg_ref
-from util import free_port, rel
+from dp_launch import TESTS, load_ranks, run_ranks
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def dp_seg(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("dp_seg"))
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()), WORLD_SIZE="2", NEF_DIST_BACKEND="gloo",
-               NEF_SHARE_GPU="1", NEF_TEST_HOOKS="1", PYTHONPATH=ROOT, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    script = os.path.join(ROOT, "tests", "dp_seg_loss_worker.py")
-    procs = [subprocess.Popen([sys.executable, script, out], env=dict(env, RANK=str(r), LOCAL_RANK=str(r)),
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for r in range(2)]
-    try:
-        logs = [p.communicate(timeout=600)[0] for p in procs]      # every child has its own time limit
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-                p.wait()
-    assert all(p.returncode == 0 for p in procs), "\n".join(lg[-3000:] for lg in logs)
-    return [dict(np.load(os.path.join(out, f"eager_rank{r}.npz"))) for r in range(2)], \
-        [dict(np.load(os.path.join(out, f"graph_rank{r}.npz"))) for r in range(2)]
+    run_ranks(os.path.join(TESTS, "dp_loss_term_worker.py"), out, extra_args=("seg",))
+    z = load_ranks(out)
+    return z["eager"], z["graph"]
 
 
 def test_world2_seg_ranks_agree_and_graphed_equals_eager(dp_seg):
-    eager, graph = dp_seg
-    for k in ("p", "buf", "p0"):
-        assert np.array_equal(eager[0][k], eager[1][k]), k
-    for k in ("p", "buf"):
-        assert np.array_equal(graph[0][k], graph[1][k]), k
-    assert not np.array_equal(eager[0]["grad"], eager[1]["grad"])       # the ranks saw different shards
-    for e, g in zip(eager, graph):
-        for k in ("p", "buf"):
-            assert np.array_equal(e[k], g[k]), k
-        assert g["losses"].shape == (1, 4) and np.array_equal(g["losses"][0], e["losses"])
+    dp_checks.ranks_agree_and_graphed_equals_eager(*dp_seg, row_len=4)
 
 
 def test_world2_seg_update_is_the_mean_of_the_two_gradients(dp_seg):
     """The single-process step on the mean of the two shards' gradients, in fp64: displacement rel-L2 against p0 - lr * mean(g).  Bar
     4.5e-6: what tests/dp_accum_worker.py derives for this comparison at lr = 1 (the fp32 rounding of the stored parameters, 2^-24 * |p|
     at parameter rms 5.8e-2 against a displacement of rms 2.7e-4 there)."""
-    a, b = dp_seg[0]
-    p0 = a["p0"].astype(np.float64)
-    want = p0 - float(a["lr"]) * np.stack([a["grad"], b["grad"]]).astype(np.float64).mean(0)
-    got = a["p"].astype(np.float64)
-    e = rel(got - p0, want - p0)
-    floor = rel(want.astype(np.float32).astype(np.float64) - p0, want - p0)
-    print(f"world 2, seg_weights: displacement of the update vs fp64 {e:.3e} (bar 4.5e-6); the fp64 result rounded to fp32 sits at "
-          f"{floor:.3e}; displacement rms {np.sqrt(np.mean((want - p0) ** 2)):.3e}")
-    assert rel(got - p0, 2.0 * (want - p0)) > 0.1              # a sum instead of the mean is far outside
-    assert e <= 4.5e-6
+    dp_checks.update_is_mean_of_gradients(dp_seg[0], "seg_weights", 4.5e-6)
 
 
 def test_world2_seg_term_is_the_per_shard_weighted_mean(dp_seg):

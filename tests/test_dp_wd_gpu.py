@@ -3,37 +3,24 @@ tests/test_dp_adam_gpu.py): the early gradient bucket is consumed, both ranks ho
 torch.optim.AdamW -- the exempt tensors in a group without decay -- on the mean of the ranks' gradients, and the graphed step equals
 the eager one bit for bit."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-from util import free_port, rel
+import dp_checks
+from dp_launch import TESTS, load_ranks, run_ranks
+from util import rel
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def dp_wd(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("dp_wd"))
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()), WORLD_SIZE="2", NEF_DIST_BACKEND="gloo",
-               NEF_SHARE_GPU="1", NEF_TEST_HOOKS="1", PYTHONPATH=ROOT, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    script = os.path.join(ROOT, "tests", "dp_wd_worker.py")
-    procs = [subprocess.Popen([sys.executable, script, out], env=dict(env, RANK=str(r), LOCAL_RANK=str(r)),
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for r in range(2)]
-    try:
-        logs = [p.communicate(timeout=600)[0] for p in procs]
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-                p.wait()
-    assert all(p.returncode == 0 for p in procs), "\n".join(lg[-3000:] for lg in logs)
-    return [dict(np.load(os.path.join(out, f"eager_rank{r}.npz"))) for r in range(2)], \
-        [dict(np.load(os.path.join(out, f"graph_rank{r}.npz"))) for r in range(2)]
+    run_ranks(os.path.join(TESTS, "dp_wd_worker.py"), out)
+    z = load_ranks(out)
+    return z["eager"], z["graph"]
 
 
 def test_world2_wd_ranks_agree_and_match_torch_adamw_on_mean_gradient(dp_wd):
@@ -70,10 +57,7 @@ def test_world2_wd_ranks_agree_and_match_torch_adamw_on_mean_gradient(dp_wd):
 
 
 def test_world2_wd_consumes_the_early_bucket(dp_wd):
-    eager, _ = dp_wd
-    for z in eager:
-        assert (z["early"] > 0).all()                      # engine.backward started the bucket every step ...
-        assert (z["reduced"] > 0).all() and (z["reduced"] < int(z["n"])).all()     # ... and the step reduced only the rest
+    dp_checks.consumes_the_early_bucket(dp_wd[0])
 
 
 def test_world2_wd_graphed_equals_eager(dp_wd):
