@@ -137,6 +137,12 @@ class AugmentArgs(C.Structure):
                 ("B", i32), ("V", i32), ("L", i32), ("R", i32), ("crop", i32), ("reserved0", i32)]
 
 
+class BeatBatchArgs(C.Structure):
+    """Mirror of `nef_beat_batch_args` (include/nefnet_hip.h)."""
+    _fields_ = [("signal", p), ("plan", p), ("data", p), ("target_view", p), ("rest_view", p), ("signal_elems", i64),
+                ("B", i32), ("V", i32), ("R", i32), ("dtype", i32)]
+
+
 class PackDesc(C.Structure):
     """Mirror of `nef_pack_desc` (include/nefnet_hip.h)."""
     _fields_ = [("w", p), ("wp", p), ("G", i32), ("Cog", i32), ("Cig", i32), ("K", i32), ("transpose_flip", i32),
@@ -243,6 +249,8 @@ SIGNATURES = {
     "nef_locate_cands_args_bytes": (sz, []),
     "nef_augment": (i32, [C.POINTER(AugmentArgs), p]),
     "nef_augment_args_bytes": (sz, []),
+    "nef_beat_batch": (i32, [C.POINTER(BeatBatchArgs), p]),
+    "nef_beat_batch_args_bytes": (sz, []),
     "nef_sgd_momentum": (i32, [p, p, p, i64, f32, f32, f32, i32, p, p, p, p]),
     "nef_adam": (i32, [p, p, p, p, i64, f32, C.c_double, C.c_double, f32, f32, f32, p, p, p, p, p]),
     "nef_update": (i32, [C.POINTER(UpdateArgs), p]),
@@ -322,7 +330,8 @@ def load():
                                ("nef_locate_score_args", lib.nef_locate_score_args_bytes(), LocateScoreArgs),
                                ("nef_locate_best_args", lib.nef_locate_best_args_bytes(), LocateBestArgs),
                                ("nef_locate_cands_args", lib.nef_locate_cands_args_bytes(), LocateCandsArgs),
-                               ("nef_augment_args", lib.nef_augment_args_bytes(), AugmentArgs)):
+                               ("nef_augment_args", lib.nef_augment_args_bytes(), AugmentArgs),
+                               ("nef_beat_batch_args", lib.nef_beat_batch_args_bytes(), BeatBatchArgs)):
         if size != C.sizeof(mirror):
             raise NefLibraryError(f"{LIB_PATH}: {name} is {size} bytes, the binding mirrors {C.sizeof(mirror)}; rebuild with "
                                   "`python -m electrocardio_panorama_amd.csrc.build`")

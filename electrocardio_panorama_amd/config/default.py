@@ -39,6 +39,13 @@ _DEFAULTS = {
         # test set per (seed, batch index, rank) -- and log psnr_gen_aug / psnr_reg_aug / ssim_gen_aug / ssim_reg_aug; best_valid stays on
         # the clean psnr_gen
         "aug_eval": False,
+        # (not in the reference) keep the phase's Tianchi recordings in device memory and build every batch there: the host draws a small
+        # integer plan per batch, one launch of nef_beat_batch crops, derives, normalises and pads (dataset/resident.py; the bits of the
+        # host loader's items).  train_net.build_loaders and val_net hand out ResidentLoaders instead of DataLoaders: no worker processes.
+        # Deliberately not on this path, ValueError with the key on: DATA.noise (it needs the quiet segment's sigma and a device draw, a
+        # different random stream from the host's), every dataset but tianchi (PTB), DATA.weighted_sample, DATA.synthetic.
+        # False: the DataLoaders, launches and bits are what they were before the key existed
+        "device_resident": False,
     },
     "MODEL": {
         "model": "modelv2",            # 'model_nefnet' selects Nef-Net

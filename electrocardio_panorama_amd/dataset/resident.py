@@ -1,0 +1,252 @@
+"""Tianchi batches built on the device from recordings kept in device memory (cfg.DATA.device_resident).
+
+The host path (dataset/tianchi.py behind a 16-worker DataLoader) builds every beat in numpy.  Here the phase's recordings are read once
+and packed into one device tensor (`ResidentTianchi`); per batch the host only makes the draws of `EcgTianChiInterval.__getitem__` -- the
+beat, the input leads, the target lead -- into a small integer table (`draw_plan`), and one launch of nef_beat_batch (ops.beat_batch) crops,
+derives the four limb leads, normalises and pads.  The bits are the host path's: the kernel works in fp64 from a lossless copy of the
+stored values.  `ResidentLoader` is the iterable of `meta` dicts the Solver consumes in place of the DataLoader.
+
+Left out on this path, and rejected where the key is read: DATA.noise (it needs the quiet segment's sigma and a device draw, a different
+random stream from the host's), DATA.weighted_sample, DATA.synthetic and every dataset but tianchi (PTB)."""
+import random
+from concurrent.futures import ThreadPoolExecutor
+from typing import NamedTuple
+
+import numpy as np
+import torch
+
+from ..synth import LEAD_THETA
+from .tianchi import BEAT_LEN, EcgTianChiInterval, _lead_plan
+
+LABEL_KEYS = ('P on', 'P off', 'R on', 'R off', 'T on', 'T off')
+READERS = 16          # files read at a time; a constant, never the host's core count (a job's CPU allotment is smaller than the machine)
+
+
+def check_cfg(cfg):
+    """DATA.device_resident goes with the tianchi dataset and without DATA.noise / weighted_sample / synthetic: ValueError otherwise."""
+    if cfg.DATA.get('dataset', 'tianchi') != 'tianchi':
+        raise ValueError(f"DATA.device_resident keeps Tianchi recordings on the device; DATA.dataset {cfg.DATA.dataset!r} is not built there")
+    if cfg.DATA.get('noise', False):
+        raise ValueError("DATA.device_resident with DATA.noise: the noise row needs the quiet segment's sigma and a host draw; "
+                         "it is not built on the device")
+    if cfg.DATA.get('weighted_sample', False):
+        raise ValueError("DATA.device_resident with DATA.weighted_sample: the weighted draw is not planned on this path")
+    if cfg.DATA.get('synthetic', False):
+        raise ValueError("DATA.device_resident with DATA.synthetic: synthetic batches have no recordings to keep on the device")
+
+
+def _pack(name, sig):
+    """One recording's [8, len] float64 signal as int16 when that is lossless, else as float32 when that is, else ValueError."""
+    sig = np.asarray(sig)
+    if sig.ndim != 2 or sig.shape[0] != 8 or sig.shape[1] < 1:
+        raise ValueError(f"recording {name}: signal {sig.shape} is not [8, len]")
+    with np.errstate(invalid='ignore'):
+        as16 = sig.astype(np.int16)
+    if np.array_equal(as16.astype(np.float64), sig):
+        return as16
+    with np.errstate(over='ignore'):
+        as32 = sig.astype(np.float32)
+    if np.array_equal(as32.astype(np.float64), sig):
+        return as32
+    raise ValueError(f"recording {name}: its values survive neither int16 nor float32 storage exactly; the device path "
+                     "cannot promise the host path's bits from a lossy copy")
+
+
+class ResidentTianchi:
+    """Every recording of the phase's label list, read once through `EcgTianChiInterval._load` (.npy + .json, or .npz bundles).
+
+    signal        flat int16 tensor on `device` -- float32 when some value of some recording is not an int16 -- recording i at
+                  [offsets[i], offsets[i + 1]) as [8, lengths[i]], lead-major
+    offsets       int64 numpy [N + 1], in elements; lengths int64 numpy [N]
+    labels[k]     the six 'P on' .. 'T off' index lists, each concatenated over the recordings (host numpy int64, never on the device),
+                  recording i at [label_offsets[k][i], label_offsets[k][i + 1])
+    names         the label list's lines (the `id` of a sample)
+    `device` None or 'cpu' keeps `signal` on the host (packing only: ops.beat_batch has no CPU path)."""
+
+    def __init__(self, cfg, phase, device=None):
+        ds = EcgTianChiInterval(cfg, phase)
+        self.cfg, self.phase, self.names = cfg, phase, list(ds.dataset)
+        if not self.names:
+            raise ValueError(f"DATA.device_resident: the {phase} label list is empty")
+
+        def read(name):
+            sig, label = ds._load(name)
+            lab = [np.asarray(label[k], dtype=np.int64).reshape(-1) for k in LABEL_KEYS]
+            self._check_labels(name, lab, sig.shape[-1])
+            return _pack(name, sig), lab
+
+        with ThreadPoolExecutor(max_workers=min(READERS, len(self.names))) as pool:
+            items = list(pool.map(read, self.names))          # results (and the first error) in list order
+        sigs = [s for s, _ in items]
+        if any(s.dtype != np.int16 for s in sigs):
+            sigs = [s.astype(np.float32) for s in sigs]        # int16 -> float32 is exact
+        self.lengths = np.array([s.shape[1] for s in sigs], dtype=np.int64)
+        self.offsets = np.concatenate([[0], np.cumsum(8 * self.lengths)]).astype(np.int64)
+        flat = torch.from_numpy(np.concatenate([s.reshape(-1) for s in sigs]))
+        dev = torch.device('cpu' if device is None else device)
+        self.signal = flat if dev.type == 'cpu' else flat.to(dev)
+        self.labels = [np.concatenate([lab[k] for _, lab in items]) for k in range(6)]
+        self.label_offsets = [np.concatenate([[0], np.cumsum([lab[k].size for _, lab in items])]).astype(np.int64) for k in range(6)]
+        self.n_p_on = np.diff(self.label_offsets[0])
+
+    @staticmethod
+    def _check_labels(name, lab, length):
+        """Every beat a draw can pick is usable: at least two P onsets, each with its five other marks, 0 <= p_on < the next p_on <= len."""
+        p_on = lab[0]
+        if p_on.size < 2:
+            raise ValueError(f"recording {name}: {p_on.size} 'P on' entries, no drawable beat (two are needed)")
+        if any(v.size < p_on.size - 1 for v in lab[1:]):
+            raise ValueError(f"recording {name}: a label list is shorter than its {p_on.size - 1} drawable beats")
+        if p_on[0] < 0 or np.any(np.diff(p_on) < 1) or p_on[-1] > length:
+            raise ValueError(f"recording {name}: 'P on' must rise strictly within [0, {length}]")
+
+    def __len__(self):
+        return len(self.names)
+
+    @property
+    def device_bytes(self):
+        return self.signal.numel() * self.signal.element_size()
+
+
+class Plan(NamedTuple):
+    """What draw_plan returns: `table` goes to the kernel, the rest is the batch's small host part."""
+    table: np.ndarray           # int64 [B, 3 + V + 1 + R]: offset of lead 0 at p_on, lead stride, n, V input leads, target lead, R rest leads
+    rois: np.ndarray            # int64 [B, 7, 2]
+    input_theta: np.ndarray     # float32 [B, V, 2]
+    target_theta: np.ndarray    # float32 [B, 2]
+    rest_theta: np.ndarray      # float32 [B, R, 2]
+    id: list
+    unsupervision_lead_name: list
+    V: int
+    R: int
+    beats: np.ndarray           # int64 [B]: the beat drawn of every sample's recording
+
+
+def draw_plan(store, indices, cfg, phase, rng, jitter_rng=None):
+    """The draws of `EcgTianChiInterval.__getitem__` for the recordings `indices`, item after item and in its order -- the beat, the input-lead
+    scheme's draws, the target lead -- from `rng` (a `random.Random`, or the `random` module).  MODEL.jitter_factor > 0 in the train phase
+    draws the angles' jitter from `jitter_rng`, a numpy Generator (required then); numpy's global state is never used."""
+    jitter = float(cfg.MODEL.jitter_factor) if phase == 'train' else 0.0
+    if jitter > 0 and jitter_rng is None:
+        raise ValueError("MODEL.jitter_factor > 0: draw_plan needs a numpy Generator for the jitter (jitter_rng)")
+    lead_num, super_mode, data_mode = cfg.DATA.lead_num, cfg.DATA.super_mode, cfg.DATA.train_data_mode
+    idx = np.asarray(list(indices), dtype=np.int64)
+    B = idx.size
+    n_p_on = store.n_p_on[idx].tolist()
+    beats, rows, unsups, thetas = [], [], [], []
+    for j in range(B):
+        beats.append(rng.sample(range(n_p_on[j] - 1), 1)[0])
+        if jitter > 0:
+            thetas.append(LEAD_THETA + jitter_rng.normal(scale=jitter / 180 * np.pi, size=LEAD_THETA.shape))
+        sel, sup, unsup, keep = _lead_plan(lead_num, super_mode, data_mode, rng=rng)
+        rest = list(sup) if keep else [x for x in sup if x not in sel]
+        target = rng.sample(rest, 1)[0]
+        rows.append(list(sel) + [target] + rest + list(unsup))           # unsupervised leads last
+        unsups.append(list(unsup))
+    V = len(sel)
+    leads = np.array(rows, dtype=np.int64)
+    R = leads.shape[1] - V - 1
+    beats = np.array(beats, dtype=np.int64)
+    marks = [store.labels[k][store.label_offsets[k][idx] + beats] for k in range(6)]
+    p_on, p_off, r_on, r_off, t_on, t_off = marks
+    end = store.labels[0][store.label_offsets[0][idx] + beats + 1]      # always the next P onset: the beat comes from range(n_P_on - 1)
+    edges = np.stack([p_on, p_off, r_on, r_off, t_on, t_off, end, BEAT_LEN + p_on], axis=1) - p_on[:, None]
+    rois = np.stack([edges[:, :-1], edges[:, 1:]], axis=2)
+    table = np.concatenate([np.stack([store.offsets[idx] + p_on, store.lengths[idx], end - p_on], axis=1), leads], axis=1)
+    theta = np.stack(thetas) if jitter > 0 else np.broadcast_to(LEAD_THETA, (B,) + LEAD_THETA.shape)
+    take = np.arange(B)[:, None]
+    return Plan(table=np.ascontiguousarray(table, dtype=np.int64), rois=np.ascontiguousarray(rois, dtype=np.int64),
+                input_theta=theta[take, leads[:, :V]].astype(np.float32), target_theta=theta[np.arange(B), leads[:, V]].astype(np.float32),
+                rest_theta=theta[take, leads[:, V + 1:]].astype(np.float32), id=[store.names[i] for i in idx.tolist()],
+                unsupervision_lead_name=unsups, V=V, R=R, beats=beats)
+
+
+class _EpochSampler:
+    """The `.sampler` the Solver pokes once per epoch."""
+
+    def __init__(self):
+        self.epoch = 0
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+
+def _align16(n):
+    return (n + 15) // 16 * 16
+
+
+class ResidentLoader:
+    """Iterable of `meta` dicts on `store`'s device: data, rois, input_theta, target_view, target_theta, rest_theta in the dtypes of the
+    collated host batch, rest_view float32 (always carried), noise zeros [B, 512], id and unsupervision_lead_name as host lists.
+
+    Train phase: the epoch's order is a permutation of the list drawn from (seed, epoch); of its first (N // world) * world entries rank r
+    takes every world-th from r (the shards are disjoint).  Test phase: the list in order, whole, on every rank.  `batch_size` is this
+    rank's; a short last batch is dropped, as the DataLoaders do.  Batch i's draws come from a private random.Random seeded by
+    (seed, epoch, rank, i) -- and a numpy Generator of the same four for MODEL.jitter_factor -- so neither Python's nor numpy's global state
+    is touched and an epoch entered after a resume repeats the uninterrupted one.  Every batch gets fresh tensors; the one launch and the
+    one copy of the plan go on the current stream."""
+
+    def __init__(self, store, cfg, phase, batch_size, seed=0, rank=0, world=1):
+        if batch_size < 1 or world < 1 or not 0 <= rank < world:
+            raise ValueError(f"batch_size {batch_size}, rank {rank}, world {world}")
+        self.store, self.cfg, self.phase, self.batch_size = store, cfg, phase, int(batch_size)
+        self.seed, self.rank, self.world = int(seed), int(rank), int(world)
+        self.sampler = _EpochSampler()
+
+    def __len__(self):
+        return (len(self.store) // self.world) // self.batch_size
+
+    def order(self, epoch=None):
+        """This rank's recording indices of the epoch, before they are cut into batches."""
+        epoch = self.sampler.epoch if epoch is None else int(epoch)
+        idx = list(range(len(self.store)))
+        if self.phase == 'train':
+            random.Random(f"nef-resident-order:{self.seed}:{epoch}").shuffle(idx)
+        return idx[:(len(idx) // self.world) * self.world][self.rank::self.world]
+
+    def plans(self, epoch=None):
+        """(batch index, recording indices, Plan) of every batch of the epoch: the host half of the loader, no device needed."""
+        epoch = self.sampler.epoch if epoch is None else int(epoch)
+        idx, B = self.order(epoch), self.batch_size
+        jitter = self.phase == 'train' and float(self.cfg.MODEL.jitter_factor) > 0
+        for i in range(len(idx) // B):
+            rng = random.Random(f"nef-resident-batch:{self.seed}:{epoch}:{self.rank}:{i}")
+            jrng = np.random.default_rng([abs(self.seed), epoch, self.rank, i]) if jitter else None
+            batch = idx[i * B:(i + 1) * B]
+            yield i, batch, draw_plan(self.store, batch, self.cfg, self.phase, rng, jrng)
+
+    def __iter__(self):
+        from .. import ops
+        dev = self.store.signal.device
+        for _, _, plan in self.plans():
+            yield self._build(ops, dev, plan)
+
+    def _build(self, ops, dev, plan):
+        B, V, R = plan.table.shape[0], plan.V, plan.R
+        # one pinned staging buffer and one copy for the plan and the batch's small host arrays; every part starts 16-byte aligned
+        parts = (plan.table, plan.rois, plan.input_theta, plan.target_theta, plan.rest_theta)
+        starts, total = [], 0
+        for a in parts:
+            starts.append(total)
+            total = _align16(total + a.nbytes)
+        stage = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+        host = stage.numpy()
+        for a, s in zip(parts, starts):
+            host[s:s + a.nbytes] = a.reshape(-1).view(np.uint8)
+        buf = stage.to(dev, non_blocking=True)
+        table, rois, in_th, tg_th, rs_th = (buf[s:s + a.nbytes].view(torch.int64 if a.dtype == np.int64 else torch.float32).view(a.shape)
+                                            for a, s in zip(parts, starts))
+        data, target, rest = ops.beat_batch(self.store.signal, table, V, R)
+        return {'data': data, 'rois': rois, 'input_theta': in_th, 'target_view': target, 'target_theta': tg_th, 'rest_view': rest,
+                'rest_theta': rs_th, 'noise': torch.zeros((B, BEAT_LEN), dtype=torch.float32, device=dev), 'id': plan.id,
+                'unsupervision_lead_name': plan.unsupervision_lead_name}
+
+
+def build_loader(cfg, phase, batch_size, device, rank=0, world=1):
+    """The ResidentLoader of `phase` as train_net.build_loaders hands it out: `batch_size` is this rank's share; only the train phase is
+    sharded and shuffled."""
+    check_cfg(cfg)
+    store = ResidentTianchi(cfg, phase, device)
+    if phase == 'train':
+        return ResidentLoader(store, cfg, phase, batch_size, seed=cfg.seed, rank=rank, world=world)
+    return ResidentLoader(store, cfg, phase, batch_size, seed=cfg.seed)

@@ -25,18 +25,19 @@ def _others(*taken):
     return [i for i in range(12) if i not in used]
 
 
-def _lead_plan(lead_num, super_mode, data_mode):
-    """(select, supervised, unsupervised, keep_supervised_as_rest) for the configured input-lead scheme (:127-191)."""
+def _lead_plan(lead_num, super_mode, data_mode, rng=random):
+    """(select, supervised, unsupervised, keep_supervised_as_rest) for the configured input-lead scheme (:127-191).  `rng`: where the
+    draws come from, Python's global `random` or a `random.Random` of the caller's (dataset/resident.py)."""
     sup, unsup = _LIMB + _CHEST, _others(_LIMB + _CHEST)
     sel = None
     if lead_num == 3:
-        n_limb = random.randint(1, 2)                 # drawn in every mode, as the reference does (:128)
+        n_limb = rng.randint(1, 2)                    # drawn in every mode, as the reference does (:128)
         if data_mode == 'input_fix':
             if super_mode == 'IIv2v5_v4I_372':
                 sel, unsup = [1, 3, 6], [5, 0]
                 sup = _others(sel, unsup)
         else:
-            sel = random.sample(_LIMB, n_limb) + random.sample(_CHEST, 3 - n_limb)
+            sel = rng.sample(_LIMB, n_limb) + rng.sample(_CHEST, 3 - n_limb)
     elif lead_num == 12 and super_mode == '_12120':
         sel, sup, unsup = list(range(12)), list(range(12)), []
     elif lead_num == 9:

@@ -1821,6 +1821,57 @@ def augment(x, rois, aug, seed=0, seed_dev=None, out=None):
     return y
 
 
+BEAT_LEN = 512           # NEF_BEAT_LEN (include/nefnet_hip.h): samples of a row of nef_beat_batch
+BEAT_MAX_REST = 64       # the largest R nef_beat_batch takes
+
+
+def beat_batch(signal, plan, V, R):
+    """One batch of Tianchi beats built from device-resident recordings (nef_beat_batch, include/nefnet_hip.h; the batches of
+    cfg.DATA.device_resident): `signal` is the store's flat int16 or float32 device tensor, `plan` the int64 [B, 3 + V + 1 + R] table of
+    dataset/resident.py's draw_plan -- per sample [offset of lead 0 at p_on, lead stride, n, V input leads, target lead, R rest leads].  A plan
+    on the host is checked against `signal` here, row by row, and copied; one that is on the device already is taken as it is (the kernel
+    gives a row that leaves `signal` NaNs, and reads nothing).  Returns fresh float32 (data [B, V, 512], target_view [B, 512],
+    rest_view [B, R, 512]); one launch on the current stream, capturable with a device plan.  Every argument check sits in front of the library."""
+    if not torch.is_tensor(signal) or signal.dtype not in (torch.int16, torch.float32):
+        raise TypeError(f"signal must be an int16 or float32 tensor, got {getattr(signal, 'dtype', type(signal))}")
+    if signal.dim() != 1 or signal.numel() < 1 or not signal.is_contiguous():
+        raise ValueError(f"signal must be a non-empty contiguous 1-D tensor, got {tuple(signal.shape)}")
+    V, R = int(V), int(R)
+    if not 1 <= V <= 12 or not 0 <= R <= BEAT_MAX_REST:
+        raise ValueError(f"V = {V}, R = {R}: 1 <= V <= 12 input leads and 0 <= R <= {BEAT_MAX_REST} rest leads")
+    if not torch.is_tensor(plan) or plan.dtype != torch.int64:
+        raise TypeError(f"plan must be an int64 tensor, got {getattr(plan, 'dtype', type(plan))}")
+    W = 3 + V + 1 + R
+    if plan.dim() != 2 or plan.shape[0] < 1 or plan.shape[1] != W or not plan.is_contiguous():
+        raise ValueError(f"plan {tuple(plan.shape)} is not a contiguous [B >= 1, {W}] table (3 + V + 1 + R words per sample)")
+    if not plan.is_cuda:
+        off, stride, n = plan[:, 0], plan[:, 1], plan[:, 2]
+        bad = (off < 0) | (stride < 1) | (n < 1) | (n > stride) | (off + 7 * stride + n > signal.numel()) | \
+              ((plan[:, 3:] < 0) | (plan[:, 3:] > 11)).any(dim=1)
+        if bool(bad.any()):
+            i = int(bad.nonzero()[0, 0])
+            raise ValueError(f"plan row {i} {plan[i].tolist()} leaves the signal of {signal.numel()} elements or names a lead outside 0..11")
+    elif plan.device != signal.device:
+        raise ValueError(f"plan is on {plan.device}, signal on {signal.device}")
+    if not signal.is_cuda:
+        raise RuntimeError("ops.beat_batch runs on a HIP device only (no CPU path)")
+    if signal.data_ptr() % 16 != 0:
+        raise ValueError("signal is not 16-byte aligned")
+    L = _lib.load()
+    if not plan.is_cuda:
+        plan = plan.to(signal.device, non_blocking=True)
+    B = plan.shape[0]
+    data = torch.empty((B, V, BEAT_LEN), dtype=torch.float32, device=signal.device)
+    target = torch.empty((B, BEAT_LEN), dtype=torch.float32, device=signal.device)
+    rest = torch.empty((B, R, BEAT_LEN), dtype=torch.float32, device=signal.device)
+    ev = _hbm("beat_batch", plan, data, target, rest)
+    A = _lib.BeatBatchArgs(signal=_p(signal), plan=_p(plan), data=_p(data), target_view=_p(target), rest_view=_p(rest) if R else None,
+                           signal_elems=signal.numel(), B=B, V=V, R=R, dtype=0 if signal.dtype == torch.int16 else 1)
+    _lib.check(L.nef_beat_batch(C.byref(A), _stream()), "nef_beat_batch")
+    _done(ev)
+    return data, target, rest
+
+
 LOSS_SEG_TILE = 1024      # NEF_LOSS_SEG_TILE (include/nefnet_hip.h): positions per block of the two segment-weight kernels
 LOSS_SEG_MAX_ROWS = 65535  # the rows are a grid's y extent
 

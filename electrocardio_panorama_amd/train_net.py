@@ -3,7 +3,8 @@
 Data.  The configured label lists (`cfg.DATA.train_label_path` / `test_label_path`, reference on-disk format) feed the
 packaged Tianchi per-beat dataset (`dataset/tianchi.py`) through torch DataLoaders exactly as the reference does; a
 missing list is an error, as it is in the reference.  `cfg.DATA.synthetic = True` (a key the reference does not have)
-selects seeded synthetic `meta` batches with the same schema instead.
+selects seeded synthetic `meta` batches with the same schema instead.  `cfg.DATA.device_resident = True` (not in the reference either)
+keeps the recordings on the device and builds the same batches there, one launch each (`dataset/resident.py`).
 
 Data parallelism (torchrun, one process per GPU).  `batch_size` is the GLOBAL batch, as under the reference's
 nn.DataParallel (solver.py:32-34): every rank draws its 1/world share -- a DistributedSampler over the real dataset,
@@ -43,6 +44,10 @@ def build_loaders(cfg, batch_size=32, phases=('train', 'test')):
     if batch_size % world:
         raise ValueError(f"global batch {batch_size} is not divisible by world size {world}")
     out = []
+    resident = bool(cfg.DATA.get('device_resident', False))
+    if resident:
+        from .dataset import resident as res
+        res.check_cfg(cfg)                                # tianchi only; not with DATA.noise / weighted_sample / synthetic
     if cfg.DATA.get('synthetic', False):
         for ph in phases:
             if ph == 'train':
@@ -53,6 +58,12 @@ def build_loaders(cfg, batch_size=32, phases=('train', 'test')):
     for path in ([cfg.DATA.train_label_path] if 'train' in phases else []) + [cfg.DATA.test_label_path]:
         if not os.path.exists(path):
             raise FileNotFoundError(f"{path} (set DATA.synthetic True to train on synthetic meta batches)")
+    if resident:
+        # DATA.device_resident: the recordings live on this rank's device and every batch is one launch there (dataset/resident.py); no
+        # worker processes.  The train phase is sharded like the DistributedSampler's, the test set is whole on every rank
+        import torch.distributed as dist
+        dev = torch.device('cuda', parallel.local_rank() if dist.is_available() and dist.is_initialized() else 0)    # the Solver's device
+        return [res.build_loader(cfg, ph, batch_size // world if ph == 'train' else batch_size, dev, rank, world) for ph in phases]
     from torch.utils.data import DataLoader
     from torch.utils.data.distributed import DistributedSampler
     from .dataset import build_dataset

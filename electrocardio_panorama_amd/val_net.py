@@ -1,6 +1,7 @@
 """`python -m electrocardio_panorama_amd.val_net --config-file config/nef_net.yml [--epoch N]` -- reference
 codes/val_net.py:9-48: build the test loader, load `best_valid.pkl` (or `epoch_N.pkl`) and print PSNR / SSIM.  `--locate` (no counterpart in
-the reference) switches SOLVER.locate_eval on: the angular error with which the model finds its own held-out leads is printed too."""
+the reference) switches SOLVER.locate_eval on: the angular error with which the model finds its own held-out leads is printed too.
+DATA.device_resident is honoured here as in training: build_loaders hands out the ResidentLoader of the test list (dataset/resident.py)."""
 import argparse
 import os
 

@@ -34,7 +34,7 @@ extern "C" {
 typedef void* nef_stream_t;
 
 /* ABI version of this header; bumped on any signature change. */
-int nef_abi_version(void);   /* 22 (+ nef_flatten_acc, nef_lr_sched / nef_lr_sched_args_bytes, nef_loss_ssim_fwd / nef_loss_ssim_bwd / nef_loss_ssim_ws_bytes / nef_loss_ssim_args_bytes, nef_loss_seg_fwd / nef_loss_seg_bwd / nef_loss_seg_ws_bytes / nef_loss_seg_args_bytes / nef_view_seg_metrics, nef_loss_slope_fwd / nef_loss_slope_bwd / nef_loss_slope_ws_bytes / nef_loss_slope_args_bytes / nef_view_slope_metrics, nef_loss_corr_fwd / nef_loss_corr_bwd / nef_loss_corr_ws_bytes / nef_loss_corr_args_bytes / nef_view_corr_metrics, nef_locate_score / nef_locate_best / nef_locate_cands and their _args_bytes: additions only, the number stays; a binding finds a library without them by the missing symbol.  Weight packing is ONE entry, nef_pack_weights(nef_pack_desc*, n), + nef_pack_bytes(nef_pack_desc*) for the size of any operand.  ABI <= 21 had nef_pack_weight, nef_pack_weight_wino, nef_pack_weight_wino4, nef_pack_weight_h2 and nef_pack_weight_h2_bytes: each is one descriptor with wino = 0 / 1 / 2 / 3); 21 (BatchNorm backward is ONE entry on a nef_bn_bwd_args struct, + nef_bn_bwd_args_bytes; nef_mix_bwd takes `up` / `shared` flags; nef_outconv_fwd / nef_outconv_bwd_weight take the prologue arguments.  ABI <= 20 had nef_bn_relu_bwd_phase_major, nef_bn_relu_bwd_up, nef_bn_relu_bwd_combine3, nef_bn_relu_bwd_combine3_phase_major, nef_bn_relu_bwd_outconv, nef_bn_bwd_outconv_ws_bytes, nef_mix_bwd_up, nef_mix_bwd_shared, nef_mix_bwd_shared_up, nef_outconv_fwd_pro and nef_outconv_bwd_weight_pro); 20 (the weight gradient is ONE entry, nef_conv_bwd_weight(nef_bww_args*), + nef_bww_args_bytes; its _pro, _wino4, _h2 and _h2_ws_bytes variants are gone); 19 (+ nef_adam, nef_h2_tail_census, nef_bwd_weight_clamp_ends: additions only; the kernel-form option entry points of 16 and nef_upsample2_aff_fwd are gone; + nef_debug_spin_us); 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + kernel-form option entry points); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + the split-fp16 weight gradient, now form 3); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, the transposed F(3,4) / F(4,4) entry, now form 4, covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
+int nef_abi_version(void);   /* 22 (+ nef_flatten_acc, nef_lr_sched / nef_lr_sched_args_bytes, nef_loss_ssim_fwd / nef_loss_ssim_bwd / nef_loss_ssim_ws_bytes / nef_loss_ssim_args_bytes, nef_loss_seg_fwd / nef_loss_seg_bwd / nef_loss_seg_ws_bytes / nef_loss_seg_args_bytes / nef_view_seg_metrics, nef_loss_slope_fwd / nef_loss_slope_bwd / nef_loss_slope_ws_bytes / nef_loss_slope_args_bytes / nef_view_slope_metrics, nef_loss_corr_fwd / nef_loss_corr_bwd / nef_loss_corr_ws_bytes / nef_loss_corr_args_bytes / nef_view_corr_metrics, nef_locate_score / nef_locate_best / nef_locate_cands and their _args_bytes, nef_beat_batch / nef_beat_batch_args_bytes: additions only, the number stays; a binding finds a library without them by the missing symbol.  Weight packing is ONE entry, nef_pack_weights(nef_pack_desc*, n), + nef_pack_bytes(nef_pack_desc*) for the size of any operand.  ABI <= 21 had nef_pack_weight, nef_pack_weight_wino, nef_pack_weight_wino4, nef_pack_weight_h2 and nef_pack_weight_h2_bytes: each is one descriptor with wino = 0 / 1 / 2 / 3); 21 (BatchNorm backward is ONE entry on a nef_bn_bwd_args struct, + nef_bn_bwd_args_bytes; nef_mix_bwd takes `up` / `shared` flags; nef_outconv_fwd / nef_outconv_bwd_weight take the prologue arguments.  ABI <= 20 had nef_bn_relu_bwd_phase_major, nef_bn_relu_bwd_up, nef_bn_relu_bwd_combine3, nef_bn_relu_bwd_combine3_phase_major, nef_bn_relu_bwd_outconv, nef_bn_bwd_outconv_ws_bytes, nef_mix_bwd_up, nef_mix_bwd_shared, nef_mix_bwd_shared_up, nef_outconv_fwd_pro and nef_outconv_bwd_weight_pro); 20 (the weight gradient is ONE entry, nef_conv_bwd_weight(nef_bww_args*), + nef_bww_args_bytes; its _pro, _wino4, _h2 and _h2_ws_bytes variants are gone); 19 (+ nef_adam, nef_h2_tail_census, nef_bwd_weight_clamp_ends: additions only; the kernel-form option entry points of 16 and nef_upsample2_aff_fwd are gone; + nef_debug_spin_us); 18 (round 6: nef_pack_desc + src_mode / src_Cr (polyphase weights synthesized inside the pack), + nef_amax_roll, nef_flatten, nef_regroup_halves, nef_step_words, nef_pano_h_conv_tail, + num_batches_tracked in the three BatchNorm statistics entry points, nef_pano_h_conv_pair for any length); 17 (round 5: + pro_mode 4 / 8 / 9, nef_poly_weights, nef_poly_fwd_edge, nef_poly_bwd_edge, nef_mix_bwd_shared: polyphase forward / backward-data through the x2 upsampling); 16 (round 5: + kernel-form option entry points); 15 (round 4: + x_clamped / clamped counters); 14 (round 4: + the split-fp16 weight gradient, now form 3); 13 (round 4: + nef_pack_weight_h2 / conv args wino = 3 and x_scale: direct convolutions on exact fp16 splits of the fp32 operands); 12 (round 4: nef_conv_bwd_weight_wino -- the transposed F(3,2) weight gradient -- is gone, the transposed F(3,4) / F(4,4) entry, now form 4, covers every shape it took; 11, round 3: the K = 7 F(4,.) operand has 13 planes, Winograd operands are laid out as 16-byte vectors; 10: + nef_pano_h_conv_pair) */
 
 /* Diagnostics: `wgs` workgroups busy for `us` microseconds on `stream` (a stand-in for a collective's time on the chip:
  * parallel.DryCollective, bench.py --dry-collective).  0 <= us <= 50000, 1 <= wgs <= 64. */
@@ -886,6 +886,40 @@ typedef struct nef_augment_args {
 int nef_augment(const nef_augment_args* a, nef_stream_t stream);
 /* sizeof(nef_augment_args) as the library was built. */
 size_t nef_augment_args_bytes(void);
+
+/* Tianchi train / test batches built on the device from recordings kept in device memory (cfg.DATA.device_resident; the host path is
+ * dataset/tianchi.py, EcgTianChiInterval.__getitem__, whose bits this entry promises).  `signal` holds every recording's eight stored
+ * leads, lead-major per recording ([8, len_i], recordings concatenated), as int16 (dtype 0) or fp32 (dtype 1) elements.  `plan` is the
+ * host's draw for the batch, one row of W = 3 + V + 1 + R int64 words per sample:
+ *   [0] element index of lead 0 at the beat's P onset   [1] the recording's lead stride (its length)   [2] n = end - p_on
+ *   [3 .. 3 + V) the input leads   [3 + V] the target lead   [4 + V .. W) the rest leads          (lead indices 0..11; 8..11 are derived)
+ * With I, II the stored leads 0 and 1, the derived leads are 8: II - I, 9: -0.5 * (I + II), 10: I - 0.5 * II, 11: II - 0.5 * I, formed in
+ * fp64 without contraction.  Per sample: lo / hi = min / max over all 12 leads and all n positions (NaN propagates, as numpy.min does); output
+ * row r (r-th lead of the plan row) holds (float)((s - lo) / (hi - lo)) at t < n, in fp64 with IEEE division and one rounding, and 0.0f at
+ * n <= t < 512.  hi == lo gives what IEEE gives (NaN).  n may exceed 512: lo / hi see the whole beat, the rows its first 512 positions.
+ * One workgroup per sample, no atomics, one writer per element, 16-byte stores; a row is read with 16- / 8- / 4-byte loads where its first
+ * element's address allows and element by element otherwise, the values are the same either way.
+ * A plan row that points outside `signal` (offset < 0, n < 1, n > stride, offset + 7 * stride + n > signal_elems) or names a lead outside
+ * 0..11 reads nothing: all of that sample's output rows are NaN.
+ * B < 1, V outside 1..12, R outside 0..64, dtype outside {0, 1}, signal_elems < 1: NEF_E_SHAPE; a NULL pointer (rest_view may be NULL
+ * only with R == 0): NEF_E_NULL; signal, data, target_view or rest_view not 16-byte aligned: NEF_E_UNSUPPORTED.  Every check sits in front
+ * of the launch.  Capturable: nothing is read by the host, nothing is allocated. */
+#define NEF_BEAT_LEN 512
+typedef struct nef_beat_batch_args {
+    const void* signal;         /* int16 or fp32 elements */
+    const int64_t* plan;        /* [B, 3 + V + 1 + R] */
+    float* data;                /* [B, V, 512] */
+    float* target_view;         /* [B, 512] */
+    float* rest_view;           /* [B, R, 512]; NULL with R == 0 */
+    int64_t signal_elems;       /* elements in `signal` */
+    int32_t B;
+    int32_t V;
+    int32_t R;
+    int32_t dtype;              /* 0: int16, 1: fp32 */
+} nef_beat_batch_args;
+int nef_beat_batch(const nef_beat_batch_args* a, nef_stream_t stream);
+/* sizeof(nef_beat_batch_args) as the library was built. */
+size_t nef_beat_batch_args_bytes(void);
 
 /* ---------------------------------------------------------------------------------------------
  * SGD with momentum over a flat buffer.  codes/solver/optim_scheduler.py:10 (torch.optim.SGD semantics:

@@ -6,11 +6,19 @@ reference codes/README.md:13), then drives it exactly as the packaged trainer do
 a HIP device is present -- and prints samples/s next to the rate one GPU consumes at that shape.
 
     python tools/bench_loader.py [--n 2048] [--epochs 3] [--workers 16] [--batch 32]
+
+`--resident` compares that loader with DATA.device_resident (dataset/resident.py) on the same tree: `--rounds` alternating rounds of fresh
+processes, each leg at batch 32 and batch 256 -- the worker loader through DevicePrefetcher as above; the resident loader alone with one
+host thread; nef_beat_batch alone on cold recordings; the resident loader feeding a graphed FusedSGD step at batch 32 beside the same step
+on preloaded synthetic batches.  Prints one JSON line of [min, median, max] per figure (`--out FILE` also writes it).
+
+    python tools/bench_loader.py --resident [--rounds 3] [--n 2048] [--out profiles/r23_resident_bench_line.json]
 """
 import argparse
 import json
 import os
 import shutil
+import subprocess
 import sys
 import tempfile
 import time
@@ -19,6 +27,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np   # noqa: E402
 import torch         # noqa: E402
+
+BATCHES = (32, 256)
 
 
 def make_tree(root, n, seed=0):
@@ -46,6 +56,161 @@ def make_tree(root, n, seed=0):
     return os.path.join(root, "list.txt")
 
 
+def tree_cfg(root, leads):
+    from electrocardio_panorama_amd.config import get_defaults, resolve_config_path
+    cfg = get_defaults()
+    cfg.merge_from_file(resolve_config_path("config/nef_net.yml"))
+    cfg.DATA.lead_num = leads
+    cfg.DATA.dataset = "tianchi"
+    cfg.DATA.train_label_path = cfg.DATA.test_label_path = os.path.join(root, "list.txt")
+    cfg.DATA.train_data_root = os.path.join(root, "npy")
+    cfg.DATA.train_label_root = os.path.join(root, "json")
+    return cfg
+
+
+def worker_loader_rates(cfg, batch, workers, epochs, modes):
+    """samples/s of the packaged worker loader: 'host' = batches arriving in the trainer, 'device' = behind DevicePrefetcher."""
+    from electrocardio_panorama_amd import train_net
+    from electrocardio_panorama_amd.prefetch import DevicePrefetcher
+    import torch.utils.data as tud
+    orig = tud.DataLoader
+
+    def patched(*args, **kw):           # the packaged loader, with the worker count under test
+        if kw.get("num_workers", 0) == 16:
+            kw["num_workers"] = workers
+        return orig(*args, **kw)
+    tud.DataLoader = patched
+    try:
+        dl = train_net.build_loaders(cfg, batch_size=batch, phases=("train",))[0]
+    finally:
+        tud.DataLoader = orig
+    dev = torch.device("cuda", 0)
+    res = {}
+    for mode in modes:
+        it_src = dl if mode == "host" else DevicePrefetcher(dl, dev)
+        n, t0 = 0, None
+        for ep in range(epochs + 1):            # epoch 0: worker start-up, untimed
+            if ep == 1:
+                t0, n = time.perf_counter(), 0
+            for meta in it_src:
+                n += int(meta["data"].shape[0])
+        if mode == "device":
+            torch.cuda.synchronize()
+        res[mode] = n / (time.perf_counter() - t0)
+    del dl
+    return res
+
+
+def leg_workers(a):
+    cfg = tree_cfg(a.tree, a.leads)
+    cfg.MODEL.jitter_factor = 0.0       # both legs of --resident without the angle jitter
+    out = {"leg": "workers", "workers": a.workers}
+    for b in BATCHES:
+        out[f"workers_on_device_b{b}"] = round(worker_loader_rates(cfg, b, a.workers, a.epochs, ["device"])["device"], 1)
+    return out
+
+
+def leg_resident(a):
+    """The resident loader alone (one host thread), the kernel alone on cold recordings, and the loader feeding a graphed step."""
+    import random
+    from electrocardio_panorama_amd import ops, synth
+    from electrocardio_panorama_amd.dataset import resident
+    from electrocardio_panorama_amd.solver import Solver
+    from electrocardio_panorama_amd.solver.optim_scheduler import get_optimizer
+    torch.set_num_threads(1)
+    dev = torch.device("cuda", 0)
+    cfg = tree_cfg(a.tree, a.leads)
+    cfg.DATA.device_resident = True
+    cfg.MODEL.jitter_factor = 0.0
+    torch.zeros(1, device=dev)
+    t0 = time.perf_counter()
+    store = resident.ResidentTianchi(cfg, "train", dev)
+    torch.cuda.synchronize()
+    out = {"leg": "resident", "store_build_s": round(time.perf_counter() - t0, 3), "store_device_bytes": store.device_bytes,
+           "store_dtype": str(store.signal.dtype).replace("torch.", "")}
+    flush = torch.empty(512 << 20, dtype=torch.uint8, device=dev)        # larger than L2 and the Infinity Cache together
+    for b in BATCHES:
+        ld = resident.ResidentLoader(store, cfg, "train", b, seed=cfg.seed)
+        n, t0 = 0, None
+        for ep in range(a.resident_epochs + 1):                          # epoch 0: first launches, untimed
+            if ep == 1:
+                torch.cuda.synchronize()
+                t0, n = time.perf_counter(), 0
+            ld.sampler.set_epoch(ep)
+            for meta in ld:
+                n += int(meta["data"].shape[0])
+        torch.cuda.synchronize()
+        out[f"resident_on_device_b{b}"] = round(n / (time.perf_counter() - t0), 1)
+        # the kernel alone: every launch behind a 512 MiB fill, so its recordings come from HBM
+        us, nbytes = [], 0
+        for _, _, plan in list(ld.plans(0))[:12]:
+            table = torch.from_numpy(plan.table).to(dev)
+            flush.zero_()
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            ops.beat_batch(store.signal, table, plan.V, plan.R)
+            e.record()
+            e.synchronize()
+            us.append(s.elapsed_time(e) * 1e3)
+            # algorithmic bytes: the beat's eight stored leads once, the plan, the rows written
+            nbytes = int(plan.table[:, 2].sum()) * 8 * store.signal.element_size() + plan.table.nbytes + b * (plan.V + 1 + plan.R) * 512 * 4
+        out[f"beat_batch_cold_us_b{b}"] = round(float(np.median(us[2:] or us)), 2)      # the first two: code load, allocator
+        out[f"beat_batch_bytes_b{b}"] = nbytes
+    del flush
+    # the graphed FusedSGD step at batch 32: fed by the resident loader, and on preloaded synthetic batches of the same shape
+    cfg.SOLVER.graph = True
+    ld = resident.ResidentLoader(store, cfg, "train", 32, seed=cfg.seed)
+    pre = [{k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in synth.make_batch(32, a.leads, 512, seed=i, Q=9).items()}
+           for i in range(len(ld))]
+    for name, feed in (("resident", ld), ("preloaded_synthetic", pre)):
+        torch.manual_seed(1234)
+        sol = Solver(cfg, use_tensorboardx=False)
+        opt = get_optimizer(cfg, sol.model.parameters())
+        random.seed(1)
+        sol.run_one_epoch(feed, "train", opt, collect_views=False)       # capture and warm-up
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.step_epochs):
+            sol.run_one_epoch(feed, "train", opt, collect_views=False)
+        torch.cuda.synchronize()
+        out[f"graphed_step_ms_b32_{name}"] = round((time.perf_counter() - t0) * 1e3 / (a.step_epochs * len(feed)), 4)
+        assert getattr(sol, "_graph_stepper", None) is not None
+    return out
+
+
+def drive_resident(a):
+    """`--rounds` alternating rounds of fresh processes on one tree; [min, median, max] of every figure."""
+    root = tempfile.mkdtemp(prefix="nef_loader_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
+    runs = []
+    try:
+        make_tree(root, a.n)
+        for _ in range(a.rounds):
+            for leg in ("workers", "resident"):
+                cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg, "--tree", root, "--epochs", str(a.epochs), "--workers",
+                       str(a.workers), "--leads", str(a.leads), "--resident-epochs", str(a.resident_epochs), "--step-epochs", str(a.step_epochs)]
+                res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=a.leg_timeout)
+                if res.returncode != 0:
+                    raise RuntimeError(f"leg {leg} ended with exit code {res.returncode}")
+                runs.append(json.loads(res.stdout.strip().splitlines()[-1]))
+                print(json.dumps(runs[-1]), flush=True)
+    finally:
+        shutil.rmtree(root, ignore_errors=True)
+    line = {"recordings": a.n, "rounds": a.rounds, "leads": a.leads, "workers": a.workers, "host_cores": os.cpu_count()}
+    for key in sorted({k for r in runs for k in r}):
+        vals = [r[key] for r in runs if key in r]
+        if isinstance(vals[0], (int, float)) and key != "workers":
+            line[key] = [min(vals), float(np.median(vals)), max(vals)] if len(set(vals)) > 1 else vals[0]
+        elif key not in ("leg", "workers"):
+            line[key] = vals[0]
+    w, r = line.get("workers_on_device_b32"), line.get("resident_on_device_b32")
+    med = lambda v: v[1] if isinstance(v, list) else v      # noqa: E731
+    line["resident_one_thread_matches_workers_b32"] = bool(med(r) >= med(w))
+    print(json.dumps(line))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(line) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=2048)
@@ -53,46 +218,28 @@ def main():
     ap.add_argument("--workers", type=int, default=16)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--leads", type=int, default=3)
+    ap.add_argument("--resident", action="store_true", help="compare the worker loader with DATA.device_resident (needs a HIP device)")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--resident-epochs", type=int, default=10)
+    ap.add_argument("--step-epochs", type=int, default=3)
+    ap.add_argument("--leg-timeout", type=float, default=400.0)
+    ap.add_argument("--out", default="")
+    ap.add_argument("--leg", choices=("workers", "resident"), help="(internal) one leg of --resident in this process")
+    ap.add_argument("--tree", default="", help="(internal) the tree --leg reads")
     a = ap.parse_args()
-    from electrocardio_panorama_amd import train_net
-    from electrocardio_panorama_amd.config import get_defaults, resolve_config_path
-    from electrocardio_panorama_amd.prefetch import DevicePrefetcher
+    if a.leg:
+        if not torch.cuda.is_available():
+            raise SystemExit("--resident needs a HIP device")
+        print(json.dumps(leg_workers(a) if a.leg == "workers" else leg_resident(a)))
+        return
+    if a.resident:
+        return drive_resident(a)
     root = tempfile.mkdtemp(prefix="nef_loader_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
     try:
-        lst = make_tree(root, a.n)
-        cfg = get_defaults()
-        cfg.merge_from_file(resolve_config_path("config/nef_net.yml"))
-        cfg.DATA.lead_num = a.leads
-        cfg.DATA.dataset = "tianchi"
-        cfg.DATA.train_label_path = cfg.DATA.test_label_path = lst
-        cfg.DATA.train_data_root = os.path.join(root, "npy")
-        cfg.DATA.train_label_root = os.path.join(root, "json")
-        # the packaged loader, with the worker count under test
-        import torch.utils.data as tud
-        orig = tud.DataLoader
-
-        def patched(*args, **kw):
-            if kw.get("num_workers", 0) == 16:
-                kw["num_workers"] = a.workers
-            return orig(*args, **kw)
-        tud.DataLoader = patched
-        try:
-            dl = train_net.build_loaders(cfg, batch_size=a.batch, phases=("train",))[0]
-        finally:
-            tud.DataLoader = orig
+        make_tree(root, a.n)
+        cfg = tree_cfg(root, a.leads)
         dev = torch.device("cuda", 0) if torch.cuda.is_available() else None
-        res = {}
-        for mode in (["host"] + (["device"] if dev is not None else [])):
-            it_src = dl if mode == "host" else DevicePrefetcher(dl, dev)
-            n, t0 = 0, None
-            for ep in range(a.epochs + 1):            # epoch 0: worker start-up, untimed
-                if ep == 1:
-                    t0, n = time.perf_counter(), 0
-                for meta in it_src:
-                    n += int(meta["data"].shape[0])
-            if dev is not None:
-                torch.cuda.synchronize()
-            res[mode] = n / (time.perf_counter() - t0)
+        res = worker_loader_rates(cfg, a.batch, a.workers, a.epochs, ["host"] + (["device"] if dev is not None else []))
         out = {"recordings": a.n, "batch": a.batch, "workers": a.workers, "host_cores": os.cpu_count(), "leads": a.leads,
                "samples_per_s_host_batches": round(res["host"], 1),
                "samples_per_s_on_device": round(res.get("device", float("nan")), 1)}
