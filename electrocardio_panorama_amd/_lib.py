@@ -143,6 +143,24 @@ class BeatBatchArgs(C.Structure):
                 ("B", i32), ("V", i32), ("R", i32), ("dtype", i32)]
 
 
+class BeatRangeArgs(C.Structure):
+    """Mirror of `nef_beat_range_args` (include/nefnet_hip.h)."""
+    _fields_ = [("signal", p), ("plan", p), ("range", p), ("signal_elems", i64), ("B", i32), ("V", i32), ("R", i32), ("dtype", i32)]
+
+
+class BeatStitchArgs(C.Structure):
+    """Mirror of `nef_beat_stitch_args` (include/nefnet_hip.h)."""
+    _fields_ = [("views", p), ("range", p), ("table", p), ("out", p), ("view_bs", i64), ("view_as", i64), ("out_elems", i64),
+                ("Bt", i32), ("A", i32), ("fill", i32), ("reserved0", i32)]
+
+
+class RecordingStatsArgs(C.Structure):
+    """Mirror of `nef_recording_stats_args` (include/nefnet_hip.h)."""
+    _fields_ = [("out", p), ("signal", p), ("beat_table", p), ("rec_table", p), ("out_offsets", p), ("score_leads", p), ("stats", p),
+                ("out_elems", i64), ("signal_elems", i64), ("Bt", i32), ("N", i32), ("A", i32), ("fill", i32), ("dtype", i32),
+                ("reserved0", i32)]
+
+
 class PackDesc(C.Structure):
     """Mirror of `nef_pack_desc` (include/nefnet_hip.h)."""
     _fields_ = [("w", p), ("wp", p), ("G", i32), ("Cog", i32), ("Cig", i32), ("K", i32), ("transpose_flip", i32),
@@ -251,6 +269,12 @@ SIGNATURES = {
     "nef_augment_args_bytes": (sz, []),
     "nef_beat_batch": (i32, [C.POINTER(BeatBatchArgs), p]),
     "nef_beat_batch_args_bytes": (sz, []),
+    "nef_beat_range": (i32, [C.POINTER(BeatRangeArgs), p]),
+    "nef_beat_range_args_bytes": (sz, []),
+    "nef_beat_stitch": (i32, [C.POINTER(BeatStitchArgs), p]),
+    "nef_beat_stitch_args_bytes": (sz, []),
+    "nef_recording_stats": (i32, [C.POINTER(RecordingStatsArgs), p]),
+    "nef_recording_stats_args_bytes": (sz, []),
     "nef_sgd_momentum": (i32, [p, p, p, i64, f32, f32, f32, i32, p, p, p, p]),
     "nef_adam": (i32, [p, p, p, p, i64, f32, C.c_double, C.c_double, f32, f32, f32, p, p, p, p, p]),
     "nef_update": (i32, [C.POINTER(UpdateArgs), p]),
@@ -331,7 +355,10 @@ def load():
                                ("nef_locate_best_args", lib.nef_locate_best_args_bytes(), LocateBestArgs),
                                ("nef_locate_cands_args", lib.nef_locate_cands_args_bytes(), LocateCandsArgs),
                                ("nef_augment_args", lib.nef_augment_args_bytes(), AugmentArgs),
-                               ("nef_beat_batch_args", lib.nef_beat_batch_args_bytes(), BeatBatchArgs)):
+                               ("nef_beat_batch_args", lib.nef_beat_batch_args_bytes(), BeatBatchArgs),
+                               ("nef_beat_range_args", lib.nef_beat_range_args_bytes(), BeatRangeArgs),
+                               ("nef_beat_stitch_args", lib.nef_beat_stitch_args_bytes(), BeatStitchArgs),
+                               ("nef_recording_stats_args", lib.nef_recording_stats_args_bytes(), RecordingStatsArgs)):
         if size != C.sizeof(mirror):
             raise NefLibraryError(f"{LIB_PATH}: {name} is {size} bytes, the binding mirrors {C.sizeof(mirror)}; rebuild with "
                                   "`python -m electrocardio_panorama_amd.csrc.build`")

@@ -161,6 +161,64 @@ def draw_plan(store, indices, cfg, phase, rng, jitter_rng=None):
                 unsupervision_lead_name=unsups, V=V, R=R, beats=beats)
 
 
+class RecordingPlan(NamedTuple):
+    """What recording_plan returns: `plan` is a Plan of every beat, the tables place its rows in [A, len_i] signals."""
+    plan: Plan
+    rec: np.ndarray             # int64 [Bt]: the position in `indices` of each row's recording
+    stitch: np.ndarray          # int64 [Bt, 4]: index in the output of angle 0 at p_on, the recording's length, n, 1 where row b + 1 continues
+    recordings: np.ndarray      # int64 [N, 4]: first row, rows, store.offsets[i], len_i
+    out_offsets: np.ndarray     # int64 [N + 1]: recording j owns [out_offsets[j], out_offsets[j + 1]) of the flat output as [A, len]
+    A: int
+
+
+def check_leads(input_leads):
+    """1 to 12 distinct integers in 0..11, as a list: ValueError otherwise."""
+    leads = list(input_leads)
+    if not 1 <= len(leads) <= 12 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 11 for v in leads) \
+            or len(set(int(v) for v in leads)) != len(leads):
+        raise ValueError(f"input_leads {leads}: 1 to 12 distinct integers in 0..11")
+    return [int(v) for v in leads]
+
+
+def recording_plan(store, indices, input_leads, angles=12):
+    """Every beat of the recordings `indices`, in their order and in beat order: no draw, no RNG state touched.  The Plan's rows carry
+    `input_leads` as the V input leads, input_leads[0] as the (unused) target, R = 0, LEAD_THETA without jitter and the rois of
+    `EcgTianChiInterval.__getitem__` for that beat; the tables lay the beats out in one flat output of [angles, len_i] signals per
+    recording (recording.synthesize; ops.beat_stitch, ops.recording_stats)."""
+    leads = check_leads(input_leads)
+    if isinstance(angles, bool) or not isinstance(angles, (int, np.integer)) or angles < 1:
+        raise ValueError(f"angles must be an integer >= 1, got {angles!r}")
+    idx = np.asarray(list(indices), dtype=np.int64).reshape(-1)
+    if idx.size < 1 or np.any(idx < 0) or np.any(idx >= len(store)):
+        raise ValueError(f"indices {idx.tolist()[:8]}...: at least one recording, each in 0..{len(store) - 1}")
+    A, V = int(angles), len(leads)
+    counts = store.n_p_on[idx] - 1
+    first = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    rec = np.repeat(np.arange(idx.size, dtype=np.int64), counts)
+    beats = np.arange(first[-1], dtype=np.int64) - first[rec]
+    of = idx[rec]
+    marks = [store.labels[k][store.label_offsets[k][of] + beats] for k in range(6)]
+    p_on = marks[0]
+    end = store.labels[0][store.label_offsets[0][of] + beats + 1]
+    edges = np.stack(marks + [end, BEAT_LEN + p_on], axis=1) - p_on[:, None]
+    rois = np.stack([edges[:, :-1], edges[:, 1:]], axis=2)
+    Bt = rec.size
+    row = np.array(leads + [leads[0]], dtype=np.int64)
+    table = np.concatenate([np.stack([store.offsets[of] + p_on, store.lengths[of], end - p_on], axis=1), np.broadcast_to(row, (Bt, V + 1))], axis=1)
+    out_offsets = np.concatenate([[0], np.cumsum(A * store.lengths[idx])]).astype(np.int64)
+    link = np.zeros(Bt, dtype=np.int64)
+    link[:-1] = rec[1:] == rec[:-1]
+    stitch = np.stack([out_offsets[rec] + p_on, store.lengths[of], end - p_on, link], axis=1)
+    recordings = np.stack([first[:-1], counts, store.offsets[idx], store.lengths[idx]], axis=1)
+    plan = Plan(table=np.ascontiguousarray(table, dtype=np.int64), rois=np.ascontiguousarray(rois, dtype=np.int64),
+                input_theta=np.ascontiguousarray(np.broadcast_to(LEAD_THETA[leads], (Bt, V, 2)), dtype=np.float32),
+                target_theta=np.ascontiguousarray(np.broadcast_to(LEAD_THETA[leads[0]], (Bt, 2)), dtype=np.float32),
+                rest_theta=np.zeros((Bt, 0, 2), dtype=np.float32), id=[store.names[i] for i in of.tolist()],
+                unsupervision_lead_name=[[] for _ in range(Bt)], V=V, R=0, beats=beats)
+    return RecordingPlan(plan=plan, rec=rec, stitch=np.ascontiguousarray(stitch, dtype=np.int64),
+                         recordings=np.ascontiguousarray(recordings, dtype=np.int64), out_offsets=out_offsets, A=A)
+
+
 class _EpochSampler:
     """The `.sampler` the Solver pokes once per epoch."""
 
@@ -173,6 +231,22 @@ class _EpochSampler:
 
 def _align16(n):
     return (n + 15) // 16 * 16
+
+
+def stage_to_device(parts, dev):
+    """int64 / float32 / float64 numpy arrays -> device tensors of their shapes through one pinned staging buffer and one copy on the current
+    stream; every part starts 16-byte aligned."""
+    kinds = {np.dtype(np.int64): torch.int64, np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}
+    starts, total = [], 0
+    for a in parts:
+        starts.append(total)
+        total = _align16(total + a.nbytes)
+    stage = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+    host = stage.numpy()
+    for a, s in zip(parts, starts):
+        host[s:s + a.nbytes] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+    buf = stage.to(dev, non_blocking=True)
+    return [buf[s:s + a.nbytes].view(kinds[a.dtype]).view(a.shape) for a, s in zip(parts, starts)]
 
 
 class ResidentLoader:
@@ -223,19 +297,7 @@ class ResidentLoader:
 
     def _build(self, ops, dev, plan):
         B, V, R = plan.table.shape[0], plan.V, plan.R
-        # one pinned staging buffer and one copy for the plan and the batch's small host arrays; every part starts 16-byte aligned
-        parts = (plan.table, plan.rois, plan.input_theta, plan.target_theta, plan.rest_theta)
-        starts, total = [], 0
-        for a in parts:
-            starts.append(total)
-            total = _align16(total + a.nbytes)
-        stage = torch.empty(total, dtype=torch.uint8, pin_memory=True)
-        host = stage.numpy()
-        for a, s in zip(parts, starts):
-            host[s:s + a.nbytes] = a.reshape(-1).view(np.uint8)
-        buf = stage.to(dev, non_blocking=True)
-        table, rois, in_th, tg_th, rs_th = (buf[s:s + a.nbytes].view(torch.int64 if a.dtype == np.int64 else torch.float32).view(a.shape)
-                                            for a, s in zip(parts, starts))
+        table, rois, in_th, tg_th, rs_th = stage_to_device((plan.table, plan.rois, plan.input_theta, plan.target_theta, plan.rest_theta), dev)
         data, target, rest = ops.beat_batch(self.store.signal, table, V, R)
         return {'data': data, 'rois': rois, 'input_theta': in_th, 'target_view': target, 'target_theta': tg_th, 'rest_view': rest,
                 'rest_theta': rs_th, 'noise': torch.zeros((B, BEAT_LEN), dtype=torch.float32, device=dev), 'id': plan.id,

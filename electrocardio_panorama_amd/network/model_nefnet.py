@@ -250,6 +250,29 @@ class Model_nefnet(nn.Module):
                                   self._f32(query_theta), rois.detach().to(torch.int64).contiguous(),
                                   half=self._half_sweep())
 
+    def panorama(self, x, input_thetas, rois, query_thetas):
+        """The views of every sample at its A query angles, [B, A, L], from one encoder pass (phase 'gen') and one eval-mode sweep.  (No
+        counterpart in the reference, which decodes the angles of gen_ecg from a latent pair the caller carries.)  x [B, V, L],
+        input_thetas [B, V, 2], rois [B, 7, 2] as for forward; query_thetas [B, A, 2], or [A, 2] shared by the batch.  Honours
+        panorama_dtype; the model is put back in the mode it was in."""
+        q = self._f32(query_thetas)
+        if q.dim() == 2:
+            q = q.unsqueeze(0).expand(x.shape[0], -1, -1).contiguous()
+        if q.dim() != 3 or q.shape[0] != x.shape[0] or q.shape[1] < 1 or q.shape[2] != 2:
+            raise ValueError(f"panorama: query_thetas {tuple(query_thetas.shape)} is neither [A, 2] nor [B, A, 2] for x {tuple(x.shape)}")
+        half = self._half_sweep()
+        was_training = self.training
+        self.eval()
+        try:
+            z1, z2 = self.forward(x, input_thetas, self._f32(input_thetas)[:, 0], rois, phase='gen')
+            with torch.no_grad(), ops.amax_scope((self._nef_scope, False)):
+                ops.BATCH_HINT = z1.shape[0]
+                ops.amax_roll()
+                latent = engine.locate_latent(self._f32(z1), self._f32(z2), rois.detach().to(torch.int64).contiguous())
+                return engine.sweep(self._params_by_name(), self._buffers_by_name(), latent, q, training=False, half=half)
+        finally:
+            self.train(was_training)
+
     def locate(self, x, input_thetas, rois, observed, *, grid=None, score='corr', levels=3, radius=2, crop=True, eps=None, chunk=None,
                return_scores=False, return_trace=False):
         """At which angle was `observed` recorded?  (No counterpart in the reference.)  x [B, V, L], input_thetas [B, V, 2], rois

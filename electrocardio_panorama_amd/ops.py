@@ -1825,13 +1825,8 @@ BEAT_LEN = 512           # NEF_BEAT_LEN (include/nefnet_hip.h): samples of a row
 BEAT_MAX_REST = 64       # the largest R nef_beat_batch takes
 
 
-def beat_batch(signal, plan, V, R):
-    """One batch of Tianchi beats built from device-resident recordings (nef_beat_batch, include/nefnet_hip.h; the batches of
-    cfg.DATA.device_resident): `signal` is the store's flat int16 or float32 device tensor, `plan` the int64 [B, 3 + V + 1 + R] table of
-    dataset/resident.py's draw_plan -- per sample [offset of lead 0 at p_on, lead stride, n, V input leads, target lead, R rest leads].  A plan
-    on the host is checked against `signal` here, row by row, and copied; one that is on the device already is taken as it is (the kernel
-    gives a row that leaves `signal` NaNs, and reads nothing).  Returns fresh float32 (data [B, V, 512], target_view [B, 512],
-    rest_view [B, R, 512]); one launch on the current stream, capturable with a device plan.  Every argument check sits in front of the library."""
+def _check_beat_plan(signal, plan, V, R, who):
+    """The argument checks ops.beat_batch and ops.beat_range share; returns (V, R) as ints."""
     if not torch.is_tensor(signal) or signal.dtype not in (torch.int16, torch.float32):
         raise TypeError(f"signal must be an int16 or float32 tensor, got {getattr(signal, 'dtype', type(signal))}")
     if signal.dim() != 1 or signal.numel() < 1 or not signal.is_contiguous():
@@ -1854,9 +1849,20 @@ def beat_batch(signal, plan, V, R):
     elif plan.device != signal.device:
         raise ValueError(f"plan is on {plan.device}, signal on {signal.device}")
     if not signal.is_cuda:
-        raise RuntimeError("ops.beat_batch runs on a HIP device only (no CPU path)")
+        raise RuntimeError(f"ops.{who} runs on a HIP device only (no CPU path)")
     if signal.data_ptr() % 16 != 0:
         raise ValueError("signal is not 16-byte aligned")
+    return V, R
+
+
+def beat_batch(signal, plan, V, R):
+    """One batch of Tianchi beats built from device-resident recordings (nef_beat_batch, include/nefnet_hip.h; the batches of
+    cfg.DATA.device_resident): `signal` is the store's flat int16 or float32 device tensor, `plan` the int64 [B, 3 + V + 1 + R] table of
+    dataset/resident.py's draw_plan -- per sample [offset of lead 0 at p_on, lead stride, n, V input leads, target lead, R rest leads].  A plan
+    on the host is checked against `signal` here, row by row, and copied; one that is on the device already is taken as it is (the kernel
+    gives a row that leaves `signal` NaNs, and reads nothing).  Returns fresh float32 (data [B, V, 512], target_view [B, 512],
+    rest_view [B, R, 512]); one launch on the current stream, capturable with a device plan.  Every argument check sits in front of the library."""
+    V, R = _check_beat_plan(signal, plan, V, R, "beat_batch")
     L = _lib.load()
     if not plan.is_cuda:
         plan = plan.to(signal.device, non_blocking=True)
@@ -1870,6 +1876,164 @@ def beat_batch(signal, plan, V, R):
     _lib.check(L.nef_beat_batch(C.byref(A), _stream()), "nef_beat_batch")
     _done(ev)
     return data, target, rest
+
+
+def _check_signal(signal, who):
+    if not torch.is_tensor(signal) or signal.dtype not in (torch.int16, torch.float32):
+        raise TypeError(f"signal must be an int16 or float32 tensor, got {getattr(signal, 'dtype', type(signal))}")
+    if signal.dim() != 1 or signal.numel() < 1 or not signal.is_contiguous():
+        raise ValueError(f"signal must be a non-empty contiguous 1-D tensor, got {tuple(signal.shape)}")
+    if not signal.is_cuda:
+        raise RuntimeError(f"ops.{who} runs on a HIP device only (no CPU path)")
+    if signal.data_ptr() % 16 != 0:
+        raise ValueError("signal is not 16-byte aligned")
+
+
+def _device_table(t, name, cols, dtype, dev, rows=None):
+    """An integer / fp64 table [rows >= 1, cols] (cols None: 1-D) as a contiguous tensor on `dev`; one on the host is copied."""
+    if not torch.is_tensor(t) or t.dtype != dtype:
+        raise TypeError(f"{name} must be a {dtype} tensor, got {getattr(t, 'dtype', type(t))}")
+    shape_ok = (t.dim() == 1) if cols is None else (t.dim() == 2 and t.shape[1] == cols)
+    if not shape_ok or t.shape[0] < 1 or (rows is not None and t.shape[0] != rows) or not t.is_contiguous():
+        want = f"[{rows if rows is not None else 'rows >= 1'}{'' if cols is None else ', ' + str(cols)}]"
+        raise ValueError(f"{name} {tuple(t.shape)} is not a contiguous {want} table")
+    if t.is_cuda and t.device != dev:
+        raise ValueError(f"{name} is on {t.device}, not on {dev}")
+    return t if t.is_cuda else t.to(dev, non_blocking=True)
+
+
+def beat_range(signal, plan, V, R):
+    """(lo, hi) of every row of a beat plan, fp64 [B, 2], exactly as nef_beat_batch forms them for its normalisation (nef_beat_range,
+    include/nefnet_hip.h): what de-normalises a row of ops.beat_batch, or a view predicted in its place.  `signal` and `plan` as for
+    ops.beat_batch, a host plan checked against `signal` here in the same way; a row of a device plan that leaves the signal gives
+    (NaN, NaN).  One launch on the current stream, capturable with a device plan."""
+    V, R = _check_beat_plan(signal, plan, V, R, "beat_range")
+    L = _lib.load()
+    if not plan.is_cuda:
+        plan = plan.to(signal.device, non_blocking=True)
+    B = plan.shape[0]
+    rng = torch.empty((B, 2), dtype=torch.float64, device=signal.device)
+    ev = _hbm("beat_range", plan, rng)
+    A = _lib.BeatRangeArgs(signal=_p(signal), plan=_p(plan), range=_p(rng), signal_elems=signal.numel(), B=B, V=V, R=R,
+                           dtype=0 if signal.dtype == torch.int16 else 1)
+    _lib.check(L.nef_beat_range(C.byref(A), _stream()), "nef_beat_range")
+    _done(ev)
+    return rng
+
+
+STITCH_FILLS = ("nan", "bridge")      # nef_beat_stitch_args.fill 0 / 1
+STITCH_MAX_BEATS = 65535              # the beats are a grid's y extent
+STITCH_MAX_ANGLES = 65536
+
+
+def _fill_code(fill):
+    if fill in (0, 1) and not isinstance(fill, bool):
+        return int(fill)
+    if fill not in STITCH_FILLS:
+        raise ValueError(f"fill must be one of {STITCH_FILLS} (or 0 / 1), got {fill!r}")
+    return STITCH_FILLS.index(fill)
+
+
+def beat_stitch(views, rng, table, out, fill):
+    """De-normalise per-beat views and write them at the beats' P onsets of whole-recording signals (nef_beat_stitch, include/nefnet_hip.h).
+    views: fp32 [Bt, A, 512] on the device, last dimension contiguous, any beat / angle strides (a slice of a larger tensor is taken as it
+    is); rng: fp64 [Bt, 2] of ops.beat_range; table: int64 [Bt, 4] = [index in `out` of angle 0 at p_on, angle stride = the recording's
+    length, n, 1 where the next row continues the recording]; out: a flat contiguous fp32 device buffer, written in place at the beats'
+    positions only and returned.  fill: 'nan' or 'bridge' for the positions of a beat behind its 512-sample row.  A host table is checked
+    against `out` here and copied; a row of a device table that would leave `out` writes nothing.  One launch, capturable."""
+    code = _fill_code(fill)
+    if not torch.is_tensor(views) or views.dtype != torch.float32 or views.dim() != 3 or views.shape[2] != BEAT_LEN:
+        raise TypeError(f"views must be a float32 [Bt, A, {BEAT_LEN}] tensor, got {getattr(views, 'dtype', type(views))} "
+                        f"{tuple(getattr(views, 'shape', ()))}")
+    if not views.is_cuda:
+        raise RuntimeError("ops.beat_stitch runs on a HIP device only (no CPU path)")
+    Bt, A = views.shape[0], views.shape[1]
+    if not 1 <= Bt <= STITCH_MAX_BEATS or not 1 <= A <= STITCH_MAX_ANGLES:
+        raise ValueError(f"views {tuple(views.shape)}: 1 <= Bt <= {STITCH_MAX_BEATS} beats and 1 <= A <= {STITCH_MAX_ANGLES} angles a launch")
+    as_ = views.stride(1) if A > 1 else BEAT_LEN        # the stride of a dimension of one entry means nothing
+    bs = views.stride(0) if Bt > 1 else A * as_
+    if views.stride(2) != 1 or as_ < BEAT_LEN or bs < A * as_:
+        raise ValueError(f"views strides {views.stride()}: rows must be contiguous, angle rows {BEAT_LEN} apart or more and beats behind them")
+    if not torch.is_tensor(out) or out.dtype != torch.float32 or out.dim() != 1 or out.numel() < 1 or not out.is_contiguous():
+        raise TypeError("out must be a non-empty contiguous 1-D float32 tensor")
+    if out.device != views.device:
+        raise ValueError(f"out is on {out.device}, views on {views.device}")
+    if out.numel() >= 1 << 40:
+        raise ValueError(f"out holds {out.numel()} elements; a launch addresses fewer than 2^40")
+    if torch.is_tensor(table) and table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 4 and not table.is_cuda:
+        base, stride, n = table[:, 0], table[:, 1], table[:, 2]
+        bad = (base < 0) | (stride < 1) | (n < 1) | (n > stride) | (base + (A - 1) * stride + n > out.numel())
+        if bool(bad.any()):
+            i = int(bad.nonzero()[0, 0])
+            raise ValueError(f"table row {i} {table[i].tolist()} leaves the output of {out.numel()} elements at {A} angles")
+    table = _device_table(table, "table", 4, torch.int64, views.device, rows=Bt)
+    rng = _device_table(rng, "rng", 2, torch.float64, views.device, rows=Bt)
+    L = _lib.load()
+    ev = _hbm("beat_stitch", views, rng, table)
+    S = _lib.BeatStitchArgs(views=_p(views), range=_p(rng), table=_p(table), out=_p(out), view_bs=bs, view_as=as_, out_elems=out.numel(),
+                            Bt=Bt, A=A, fill=code, reserved0=0)
+    _lib.check(L.nef_beat_stitch(C.byref(S), _stream()), "nef_beat_stitch")
+    _done(ev)
+    return out
+
+
+def recording_stats(out, signal, beat_table, rec_table, score_leads, fill, out_offsets):
+    """Per (recording, angle) the count and the six fp64 sums of the stitched signals against stored or derived leads: fp64 [N, A, 7] =
+    [count, sum d^2, sum u, sum w, sum u^2, sum w^2, sum u w] (nef_recording_stats, include/nefnet_hip.h; recording.metrics turns them into
+    RMSE and correlation).  out: the flat fp32 buffer ops.beat_stitch wrote; signal: the store's flat tensor; beat_table: the int64
+    [Bt, 4] table of ops.beat_stitch over all recordings; rec_table: int64 [N, 4] = [first row, rows, offset in `signal`, length];
+    score_leads: A leads in -1..11 (a list, or an int32 tensor; -1: the angle is not scored and gets zeros); out_offsets: int64 [N], where
+    recording i's [A, len_i] signals start in `out`.  fill as for ops.beat_stitch: 'bridge' counts the positions behind a beat's 512-sample
+    row too.  A row of a launch depends on that recording's own tables alone.  One launch, capturable with device tables."""
+    code = _fill_code(fill)
+    if not torch.is_tensor(out) or out.dtype != torch.float32 or out.dim() != 1 or out.numel() < 1 or not out.is_contiguous():
+        raise TypeError("out must be a non-empty contiguous 1-D float32 tensor")
+    if out.numel() >= 1 << 40:
+        raise ValueError(f"out holds {out.numel()} elements; a launch addresses fewer than 2^40")
+    if not torch.is_tensor(score_leads):
+        score_leads = torch.tensor([int(v) for v in score_leads], dtype=torch.int32)
+    if score_leads.dtype != torch.int32 or score_leads.dim() != 1 or not 1 <= score_leads.numel() <= STITCH_MAX_ANGLES:
+        raise ValueError(f"score_leads must be 1 to {STITCH_MAX_ANGLES} int32 leads, got {score_leads.dtype} {tuple(score_leads.shape)}")
+    if not score_leads.is_cuda and bool(((score_leads < -1) | (score_leads > 11)).any()):
+        raise ValueError(f"score_leads {score_leads.tolist()}: each is a lead 0..11, or -1 for an angle that is not scored")
+    _check_signal(signal, "recording_stats")
+    dev = signal.device
+    if out.device != dev:
+        raise ValueError(f"out is on {out.device}, signal on {dev}")
+    A = score_leads.numel()
+    host = [t for t in (beat_table, rec_table, out_offsets) if torch.is_tensor(t) and not t.is_cuda]
+    beat_table = _device_table(beat_table, "beat_table", 4, torch.int64, dev)
+    rec_table = _device_table(rec_table, "rec_table", 4, torch.int64, dev)
+    N, Bt = rec_table.shape[0], beat_table.shape[0]
+    out_offsets = _device_table(out_offsets, "out_offsets", None, torch.int64, dev, rows=N)
+    if len(host) == 3:          # all on the host: checked here as the kernel checks device tables
+        bt, rt, oo = host
+        first, rows, soff, ln = rt[:, 0], rt[:, 1], rt[:, 2], rt[:, 3]
+        bad = (first < 0) | (rows < 0) | (first + rows > Bt) | (soff < 0) | (ln < 1) | (soff + 8 * ln > signal.numel()) | (oo < 0) | \
+              (oo + A * ln > out.numel())
+        if bool(bad.any()):
+            i = int(bad.nonzero()[0, 0])
+            raise ValueError(f"rec_table row {i} {rt[i].tolist()} (output offset {int(oo[i])}) leaves the signal, the output or the beat table")
+        for i in range(N):
+            b = bt[int(first[i]):int(first[i] + rows[i])]
+            p = b[:, 0] - oo[i]
+            if bool(((p < 0) | (b[:, 1] != ln[i]) | (b[:, 2] < 1) | (p + b[:, 2] > ln[i])).any()):
+                raise ValueError(f"a beat of recording {i} lies outside its {int(ln[i])} positions")
+    if N * A > 0x7FFFFFFF:
+        raise ValueError(f"{N} recordings x {A} angles: a launch takes fewer than 2^31 pairs")
+    if score_leads.is_cuda and score_leads.device != dev:
+        raise ValueError(f"score_leads is on {score_leads.device}, signal on {dev}")
+    score_leads = score_leads.contiguous() if score_leads.is_cuda else score_leads.contiguous().to(dev, non_blocking=True)
+    L = _lib.load()
+    stats = torch.empty((N, A, 7), dtype=torch.float64, device=dev)
+    ev = _hbm("recording_stats", out, signal, beat_table, rec_table, stats)
+    S = _lib.RecordingStatsArgs(out=_p(out), signal=_p(signal), beat_table=_p(beat_table), rec_table=_p(rec_table),
+                                out_offsets=_p(out_offsets), score_leads=_p(score_leads), stats=_p(stats), out_elems=out.numel(),
+                                signal_elems=signal.numel(), Bt=Bt, N=N, A=A, fill=code, dtype=0 if signal.dtype == torch.int16 else 1,
+                                reserved0=0)
+    _lib.check(L.nef_recording_stats(C.byref(S), _stream()), "nef_recording_stats")
+    _done(ev)
+    return stats
 
 
 LOSS_SEG_TILE = 1024      # NEF_LOSS_SEG_TILE (include/nefnet_hip.h): positions per block of the two segment-weight kernels

@@ -921,6 +921,93 @@ int nef_beat_batch(const nef_beat_batch_args* a, nef_stream_t stream);
 /* sizeof(nef_beat_batch_args) as the library was built. */
 size_t nef_beat_batch_args_bytes(void);
 
+/* Whole recordings from per-beat views (recording.py): the three entries that take nef_beat_batch's direction back.  All are
+ * capturable and stateless, use no atomics and no scratch, and give every output element one writer.  `views` and `out` may sit at any
+ * 4-byte address: a row whose first element is 16-byte aligned moves in 16-byte accesses, another one element by element, the values
+ * being the same either way.
+ *
+ * nef_beat_range: range[b] = (lo, hi) of plan row b, formed exactly as nef_beat_batch forms them (all 12 leads, all n positions, fp64, a
+ * NaN wins) from the same `signal` and the same plan of W = 3 + V + 1 + R words per row.  One workgroup per row.  A row that leaves `signal`
+ * or names a lead outside 0..11 -- the rows nef_beat_batch answers with NaNs -- reads nothing and gives (NaN, NaN).
+ * B < 1, V outside 1..12, R outside 0..64, dtype outside {0, 1}, signal_elems < 1: NEF_E_SHAPE; a NULL pointer: NEF_E_NULL; signal not
+ * 16-byte aligned, plan or range not 8-byte aligned: NEF_E_UNSUPPORTED. */
+typedef struct nef_beat_range_args {
+    const void* signal;         /* int16 or fp32 elements */
+    const int64_t* plan;        /* [B, 3 + V + 1 + R] */
+    double* range;              /* [B, 2]: lo, hi */
+    int64_t signal_elems;
+    int32_t B;
+    int32_t V;
+    int32_t R;
+    int32_t dtype;              /* 0: int16, 1: fp32 */
+} nef_beat_range_args;
+int nef_beat_range(const nef_beat_range_args* a, nef_stream_t stream);
+size_t nef_beat_range_args_bytes(void);
+
+/* nef_beat_stitch: views[b, a, 0..512) (fp32; beat b's angle row a starts at views + b * view_bs + a * view_as, strides in elements, the
+ * row itself contiguous) is beat b of a recording seen from angle a in the beat's own normalisation.  With (lo, hi) = range[b],
+ * span = hi - lo, and table row b =
+ *   [0] element index in `out` of angle 0 at the beat's P onset   [1] the recording's length = the angle stride of its [A, len] signals
+ *   [2] n = end - p_on                                             [3] 1: row b + 1 is the following beat of the same recording, else 0
+ * it writes, for every a < A,
+ *   t < min(n, 512):  out[[0] + a * [1] + t] = (float)(lo + (double)views[b, a, t] * span)      one fp64 multiply, one fp64 add, one rounding
+ *   512 <= t < n:     fill 0: NaN.  fill 1 ("bridge"): (float)(a0 + (a1 - a0) * ((double)(t - 511) / (double)(n - 511))), a0 this beat's
+ *                     fp64 value at t = 511 and a1 the next row's fp64 value at t = 0 where [3] == 1 (and b + 1 < Bt), else a0 (hold).
+ * hi == lo gives the constant lo.  A range whose span is not finite makes every value formed with it NaN.  Positions outside every beat
+ * are never written.  A table row that would leave `out` (offset < 0, n < 1, n > stride, [0] + (A - 1) * [1] + n > out_elems) writes
+ * nothing; the check is inside the launch, per block.  Grid (groups of 4 angles, beat): a wave per angle row, 8 positions per lane, the
+ * tail beyond 512 strided over the wave.
+ * Bt outside 1..65535, A outside 1..65536, fill outside {0, 1}, out_elems outside [1, 2^40), view_as < 512, view_bs < A * view_as:
+ * NEF_E_SHAPE; a NULL pointer: NEF_E_NULL; views or out not 4-byte aligned, range or table not 8-byte aligned: NEF_E_UNSUPPORTED. */
+typedef struct nef_beat_stitch_args {
+    const float* views;         /* [Bt, A, 512] through view_bs / view_as */
+    const double* range;        /* [Bt, 2] */
+    const int64_t* table;       /* [Bt, 4] */
+    float* out;                 /* out_elems floats */
+    int64_t view_bs;            /* elements between beats */
+    int64_t view_as;            /* elements between the angle rows of a beat */
+    int64_t out_elems;
+    int32_t Bt;
+    int32_t A;
+    int32_t fill;               /* 0: NaN, 1: bridge */
+    int32_t reserved0;          /* 0 */
+} nef_beat_stitch_args;
+int nef_beat_stitch(const nef_beat_stitch_args* a, nef_stream_t stream);
+size_t nef_beat_stitch_args_bytes(void);
+
+/* nef_recording_stats: stats[i, a, 0..7) of the stitched signal x = out[out_offsets[i] + a * len_i + .] against the truth y = lead
+ * score_leads[a] (0..11; 8..11 derived as nef_beat_batch derives them; -1: none, seven zeros) of recording i, whose eight stored leads sit
+ * at signal[[2] .. [2] + 8 * [3]) of rec_table row i = [first row of beat_table, number of rows, offset in `signal`, len_i].  beat_table is
+ * nef_beat_stitch's table.  Covered positions: the first min(n, 512) of each of the recording's beats, all n with fill 1.  In fp64 from
+ * the fp32 / stored values, with u = x - x_first and w = y - y_first shifted by the recording's first covered sample and d = x - y:
+ *   [0] count   [1] sum d^2   [2] sum u   [3] sum w   [4] sum u^2   [5] sum w^2   [6] sum u w
+ * A NaN in x propagates into the sums.  One workgroup per (recording, angle); wave w takes the recording's beats w, w + 4, ..., lane l the
+ * groups of 8 positions l, l + 64, ... of a beat; lanes are summed by a shuffle tree and the four waves in order, so a result depends on
+ * the recording's own rows alone -- not on N, A or the rest of the launch.  A recording that would leave `signal` or `out`, a beat outside
+ * its recording or a lead outside -1..11 reads nothing and gives seven NaNs.
+ * Bt, N or A < 1, A > 65536, N * A >= 2^31, fill or dtype outside {0, 1}, out_elems outside [1, 2^40), signal_elems < 1: NEF_E_SHAPE; a
+ * NULL pointer: NEF_E_NULL; signal not 16-byte aligned, out or score_leads not 4-byte, a table or stats not 8-byte aligned:
+ * NEF_E_UNSUPPORTED. */
+typedef struct nef_recording_stats_args {
+    const float* out;           /* the stitched signals */
+    const void* signal;         /* int16 or fp32 elements */
+    const int64_t* beat_table;  /* [Bt, 4] */
+    const int64_t* rec_table;   /* [N, 4] */
+    const int64_t* out_offsets; /* [N]: element index in `out` of recording i's [A, len_i] signals */
+    const int32_t* score_leads; /* [A] */
+    double* stats;              /* [N, A, 7] */
+    int64_t out_elems;
+    int64_t signal_elems;
+    int32_t Bt;
+    int32_t N;
+    int32_t A;
+    int32_t fill;               /* 0: the first 512 positions of a beat are covered, 1: all n */
+    int32_t dtype;              /* 0: int16, 1: fp32 */
+    int32_t reserved0;          /* 0 */
+} nef_recording_stats_args;
+int nef_recording_stats(const nef_recording_stats_args* a, nef_stream_t stream);
+size_t nef_recording_stats_args_bytes(void);
+
 /* ---------------------------------------------------------------------------------------------
  * SGD with momentum over a flat buffer.  codes/solver/optim_scheduler.py:10 (torch.optim.SGD semantics:
  * first step buf = g, afterwards buf = mu*buf + g; p -= lr*buf).  g is multiplied by gscale first
