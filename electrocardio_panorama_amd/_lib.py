@@ -137,6 +137,13 @@ class AugmentArgs(C.Structure):
                 ("B", i32), ("V", i32), ("L", i32), ("R", i32), ("crop", i32), ("reserved0", i32)]
 
 
+class WarpArgs(C.Structure):
+    """Mirror of `nef_warp_args` (include/nefnet_hip.h)."""
+    _fields_ = [("data", p), ("target", p), ("rest", p), ("rois", p), ("data_out", p), ("target_out", p), ("rest_out", p),
+                ("rois_out", p), ("seed", C.c_uint64), ("index0", i64), ("amp", C.c_double * 6),
+                ("jitter", i32), ("B", i32), ("V", i32), ("R", i32), ("L", i32), ("reserved0", i32)]
+
+
 class BeatBatchArgs(C.Structure):
     """Mirror of `nef_beat_batch_args` (include/nefnet_hip.h)."""
     _fields_ = [("signal", p), ("plan", p), ("data", p), ("target_view", p), ("rest_view", p), ("signal_elems", i64),
@@ -267,6 +274,8 @@ SIGNATURES = {
     "nef_locate_cands_args_bytes": (sz, []),
     "nef_augment": (i32, [C.POINTER(AugmentArgs), p]),
     "nef_augment_args_bytes": (sz, []),
+    "nef_warp": (i32, [C.POINTER(WarpArgs), p]),
+    "nef_warp_args_bytes": (sz, []),
     "nef_beat_batch": (i32, [C.POINTER(BeatBatchArgs), p]),
     "nef_beat_batch_args_bytes": (sz, []),
     "nef_beat_range": (i32, [C.POINTER(BeatRangeArgs), p]),
@@ -355,6 +364,7 @@ def load():
                                ("nef_locate_best_args", lib.nef_locate_best_args_bytes(), LocateBestArgs),
                                ("nef_locate_cands_args", lib.nef_locate_cands_args_bytes(), LocateCandsArgs),
                                ("nef_augment_args", lib.nef_augment_args_bytes(), AugmentArgs),
+                               ("nef_warp_args", lib.nef_warp_args_bytes(), WarpArgs),
                                ("nef_beat_batch_args", lib.nef_beat_batch_args_bytes(), BeatBatchArgs),
                                ("nef_beat_range_args", lib.nef_beat_range_args_bytes(), BeatRangeArgs),
                                ("nef_beat_stitch_args", lib.nef_beat_stitch_args_bytes(), BeatStitchArgs),

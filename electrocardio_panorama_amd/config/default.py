@@ -39,6 +39,17 @@ _DEFAULTS = {
         # test set per (seed, batch index, rank) -- and log psnr_gen_aug / psnr_reg_aug / ssim_gen_aug / ssim_reg_aug; best_valid stays on
         # the clean psnr_gen
         "aug_eval": False,
+        # (not in the reference) time warp of the whole train batch on the device, in front of everything else in the step (warp.py;
+        # nef_warp): inputs, target, rest views and rois change together, DATA.aug_* then corrupts the warped inputs.  Every draw is a
+        # function of (seed, epoch, batch index, rank, sample).  Not with DATA.noise (its row is padded to the unwarped beat)
+        "aug_warp": [],                # off when empty; else six amplitudes [P, PR, QRS, ST, T, TP], each in [0, 0.9]: segment k of every
+                                       # train beat is resampled to 1 + a_k (2 u - 1) times its length, u uniform per (sample, segment)
+        "aug_roi_jitter": 0,           # J in 0..64: each of the five interior marks of the warped beat moves by an integer drawn
+                                       # uniformly from [-J, J]; the signal does not move
+        # with a warp or a jitter on: Solver.train / Solver.val run the test phase once more on one fixed warped and jittered test set
+        # per (seed, batch index, rank) and log psnr_gen_warp / psnr_reg_warp / ssim_gen_warp / ssim_reg_warp; best_valid stays on the
+        # unwarped psnr_gen
+        "aug_warp_eval": False,
         # (not in the reference) keep the phase's Tianchi recordings in device memory and build every batch there: the host draws a small
         # integer plan per batch, one launch of nef_beat_batch crops, derives, normalises and pads (dataset/resident.py; the bits of the
         # host loader's items).  train_net.build_loaders and val_net hand out ResidentLoaders instead of DataLoaders: no worker processes.

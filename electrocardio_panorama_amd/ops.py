@@ -1821,6 +1821,64 @@ def augment(x, rois, aug, seed=0, seed_dev=None, out=None):
     return y
 
 
+def warp(data, target, rest, rois, warp, seed, index0=0):
+    """The batch warped in time as cfg.DATA.aug_warp / aug_roi_jitter say (`warp`: warp.from_cfg's Warp; nef_warp, include/nefnet_hip.h,
+    defines every step) -> (data, target, rest, rois), all new tensors; no input is written.  `data` [B, V, L], `target` [B, L] or
+    [B, 1, L] (returned in the shape given), `rest` [B, R, L] or None (None back), `rois` [B, 7, 2] integer (int64 back): float32,
+    contiguous, on one HIP device.  `warp` None: the four inputs themselves, no launch.  `seed`: the launch's 64-bit seed word
+    (warp.train_seed / eval_seed); sample i draws as sample `index0` + i.  One launch, capturable.  Every argument check sits in front of
+    the library."""
+    if warp is None:
+        return data, target, rest, rois
+    for name, t in (("data", data), ("target", target)) + ((("rest", rest),) if rest is not None else ()):
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise TypeError(f"{name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous, got {tuple(t.shape)} with strides {tuple(t.stride())}")
+    if data.dim() != 3:
+        raise ValueError(f"data must be [B, V, L], got {tuple(data.shape)}")
+    B, V, Ln = data.shape
+    if B < 1 or not 1 <= V <= 12 or not 4 <= Ln <= 1 << 24 or Ln % 4 != 0:
+        raise ValueError(f"data {tuple(data.shape)}: B >= 1, V in 1..12, L a multiple of 4 in 4..2^24")
+    if tuple(target.shape) not in ((B, Ln), (B, 1, Ln)):
+        raise ValueError(f"target {tuple(target.shape)} is neither [{B}, {Ln}] nor [{B}, 1, {Ln}]")
+    R = 0
+    if rest is not None:
+        if rest.dim() != 3 or rest.shape[0] != B or rest.shape[2] != Ln or not 1 <= rest.shape[1] <= BEAT_MAX_REST:
+            raise ValueError(f"rest {tuple(rest.shape)} is not [{B}, R, {Ln}] with R in 1..{BEAT_MAX_REST}")
+        R = rest.shape[1]
+    if not torch.is_tensor(rois) or rois.dtype not in (torch.int64, torch.int32):
+        raise TypeError(f"rois must be an integer tensor [B, 7, 2], got {getattr(rois, 'dtype', type(rois))}")
+    if tuple(rois.shape) != (B, 7, 2):
+        raise ValueError(f"rois {tuple(rois.shape)} is not [{B}, 7, 2]")
+    for name, t in (("target", target), ("rest", rest), ("rois", rois)):
+        if t is not None and t.device != data.device:
+            raise ValueError(f"{name} is on {t.device}, data on {data.device}")
+    amp = tuple(float(a) for a in warp.amp)
+    if len(amp) != 6 or not all(0.0 <= a <= 0.9 for a in amp):
+        raise ValueError(f"warp.amp {warp.amp!r}: six amplitudes in [0, 0.9]")
+    if isinstance(warp.jitter, bool) or not isinstance(warp.jitter, int) or not 0 <= warp.jitter <= 64:
+        raise ValueError(f"warp.jitter {warp.jitter!r}: an integer in 0..64")
+    if not -(1 << 60) <= int(index0) < 1 << 60:
+        raise ValueError(f"index0 {index0!r} is outside +-2^60")
+    if not data.is_cuda:
+        raise RuntimeError("ops.warp runs on a HIP device only (no CPU path)")
+    rois = rois.to(torch.int64).contiguous()
+    for name, t in (("data", data), ("target", target), ("rest", rest), ("rois", rois)):
+        if t is not None and t.data_ptr() % 16 != 0:
+            raise ValueError(f"{name} is not 16-byte aligned")
+    L = _lib.load()
+    data_o, target_o, rois_o = torch.empty_like(data), torch.empty_like(target), torch.empty_like(rois)
+    rest_o = torch.empty_like(rest) if rest is not None else None
+    ev = _hbm("warp", data, target, rest, rois, data_o, target_o, rest_o, rois_o)
+    A = _lib.WarpArgs(data=_p(data), target=_p(target), rest=_p(rest), rois=_p(rois), data_out=_p(data_o), target_out=_p(target_o),
+                      rest_out=_p(rest_o), rois_out=_p(rois_o), seed=int(seed) & 0xFFFFFFFFFFFFFFFF, index0=int(index0),
+                      amp=(C.c_double * 6)(*amp), jitter=warp.jitter, B=B, V=V, R=R, L=Ln)
+    _lib.check(L.nef_warp(C.byref(A), _stream()), "nef_warp")
+    _done(ev)
+    return data_o, target_o, rest_o, rois_o
+
+
 BEAT_LEN = 512           # NEF_BEAT_LEN (include/nefnet_hip.h): samples of a row of nef_beat_batch
 BEAT_MAX_REST = 64       # the largest R nef_beat_batch takes
 

@@ -24,6 +24,12 @@ restart with every train epoch, so the step's seed is a function of (seed, epoch
 uninterrupted one drew.  `DATA.aug_eval`: `train` and `val` run the test phase a second time on one fixed corrupted test set and report
 psnr_gen_aug / psnr_reg_aug / ssim_gen_aug / ssim_reg_aug beside the clean numbers, which decide best_valid as before.
 
+`DATA.aug_warp` / `DATA.aug_roi_jitter` (no counterpart in the reference; warp.py): the train phase warps every batch in time on the device
+right behind its arrival there -- inputs, target, rest views and rois in one launch (ops.warp) under warp.train_seed(seed, epoch, batch
+index, rank) -- so the eager step, the replayed step and everything inside them receive a batch that is already consistent.
+`DATA.aug_warp_eval`: `train` and `val` run the test phase once more on one fixed warped and jittered test set and report psnr_gen_warp /
+psnr_reg_warp / ssim_gen_warp / ssim_reg_warp beside the unwarped numbers, which decide best_valid as before.
+
 `SOLVER.seg_weights` / `SOLVER.seg_eval` (no counterpart in the reference): the loss takes the batch's rois and weighs the reconstruction
 term by wave segment; the test phase reports the PSNR of each of the six wave segments (`nef_view_seg_metrics`, one more launch per
 batch) as psnr_gen_seg_* / psnr_reg_seg_*, in `Solver.last_seg_psnr`.
@@ -47,6 +53,7 @@ from .. import _env
 import torch.distributed as dist
 
 from .. import augment, engine, ops, parallel, views
+from .. import warp as _warp
 from .. import locate as _locate
 from ..network import build_model, build_loss
 from ..utils import CheckPointer
@@ -180,6 +187,9 @@ class Solver:
         self.model = build_model(cfg).float()
         # DATA.aug_*: the train step corrupts its input leads on the device (augment.py); invalid keys are rejected here.  None = off
         self.augment = self.model.augment = augment.from_cfg(cfg)
+        # DATA.aug_warp / aug_roi_jitter: the train phase warps every batch in time on the device (warp.py); invalid keys are rejected
+        # here.  None = off
+        self.warp = _warp.from_cfg(cfg)
         self.loss = build_loss(cfg)
         # SOLVER.seg_eval: the test phase also fills last_seg_psnr = {'gen': [6 numbers], 'reg': [6 numbers]} (P, PR, QRS, ST, T, TP)
         self.seg_eval = bool(cfg.SOLVER.get('seg_eval', False))
@@ -226,6 +236,8 @@ class Solver:
             sched.total_updates = max_epochs * -(-len(dl_train) // getattr(optimizer, 'accum_steps', 1))
         if self.augment is not None:
             print(self.augment.describe())                # once: the DATA.aug_* keys that are on
+        if self.warp is not None:
+            print(self.warp.describe())                   # once: DATA.aug_warp / aug_roi_jitter / aug_warp_eval
         seg_w = self._seg_weights()
         if seg_w is not None:                             # once: SOLVER.seg_weights
             from ..network.loss.losses import SEG_NAMES
@@ -286,6 +298,13 @@ class Solver:
                     scalars += list(aug_metrics)
                     names += ['psnr_gen_aug', 'psnr_reg_aug', 'ssim_gen_aug', 'ssim_reg_aug']
                     msg += '\npsnr_gen_aug: {}, psnr_reg_aug: {}, ssim_gen_aug:{}, ssim_reg_aug:{}'.format(*aug_metrics)
+                if self.warp is not None and self.warp.eval:
+                    # DATA.aug_warp_eval: the same weights on the fixed warped test set; best_valid stays on the unwarped psnr_gen
+                    with optimizer.ema_weights() if self._ema_eval(optimizer) else contextlib.nullcontext():
+                        warp_metrics = self._warp_eval(dl_test)
+                    scalars += list(warp_metrics)
+                    names += ['psnr_gen_warp', 'psnr_reg_warp', 'ssim_gen_warp', 'ssim_reg_warp']
+                    msg += '\npsnr_gen_warp: {}, psnr_reg_warp: {}, ssim_gen_warp:{}, ssim_reg_warp:{}'.format(*warp_metrics)
             # the plan's tail terms that are on sit behind the four (train) / five (test: the rest_out term) elements of every loss row
             for k, term in enumerate(self._plan().tail):
                 key = term.name
@@ -378,6 +397,22 @@ class Solver:
         self.last_aug_metrics = tuple(float(v) for v in np.mean(metrics, axis=0))
         return self.last_aug_metrics
 
+    def _warp_eval(self, dl_test):
+        """DATA.aug_warp_eval: (psnr_gen, psnr_reg, ssim_gen, ssim_reg) of the test phase on warped and jittered batches -- batch i under
+        warp.eval_seed(cfg.seed, i, rank), so every epoch and every resumed run judges the same warped test set and no seed is a train
+        batch's.  The run goes on as if this pass had not happened, as after `_aug_eval`; the read-outs of the unwarped pass
+        (last_seg_psnr, last_slope_psnr, last_corr) stay."""
+        state, calls, amax0 = random.getstate(), getattr(self.model, '_drop_calls', 0), ops.amax_snapshot(self.device)
+        try:
+            with torch.no_grad():
+                metrics = self.run_one_epoch(dl_test, phase='test', collect_views=False, warp_eval=True)[4]
+        finally:
+            random.setstate(state)
+            self.model._drop_calls = calls
+            ops.amax_restore(self.device, amax0)
+        self.last_warp_metrics = tuple(float(v) for v in np.mean(metrics, axis=0))
+        return self.last_warp_metrics
+
     def val(self, dl_test, epoch=-1):
         """solver.py:118-137: load `best_valid.pkl` (epoch == -1) or `epoch_<n>.pkl`, run the test phase, print and
         return (psnr_gen, psnr_reg, ssim_gen, ssim_reg).  DATA.aug_eval with a corruption on: the corrupted test set's four numbers are
@@ -404,6 +439,8 @@ class Solver:
             print(self._corr_message())
         if self.augment is not None and self.augment.eval:
             print('psnr_gen_aug:{}, psnr_reg_aug:{}, ssim_gen_aug:{}, ssim_reg_aug:{}'.format(*self._aug_eval(dl_test)))
+        if self.warp is not None and self.warp.eval:
+            print('psnr_gen_warp:{}, psnr_reg_warp:{}, ssim_gen_warp:{}, ssim_reg_warp:{}'.format(*self._warp_eval(dl_test)))
         if self.locate_eval:
             self.locate(dl_test)
             print(self._locate_message())
@@ -465,6 +502,12 @@ class Solver:
         t = lambda v: torch.as_tensor(v).to(dev, non_blocking=True)   # noqa: E731
         return (t(meta['data']), t(meta['rois']), t(meta['input_theta']), t(meta['target_view']).unsqueeze(1),
                 t(meta['target_theta']), t(meta['noise']).unsqueeze(1))
+
+    def _warp_batch(self, source_data, target_view, rest_view, rois, seed):
+        """The batch warped under `seed` (ops.warp: one launch on the current stream into fresh tensors); float32 rows, as the model
+        takes them."""
+        f = lambda v: None if v is None else v.to(torch.float32).contiguous()   # noqa: E731
+        return ops.warp(f(source_data), f(target_view), f(rest_view), rois.contiguous(), self.warp, seed)
 
     def _gen_num(self):
         """How many trailing rest views are 'generated' (never supervised), and whether the split applies at all
@@ -536,12 +579,16 @@ class Solver:
             return
         raise RuntimeError(msg + '; their results are wrong.  Set NEF_H2=0 (fp32 kernels), or NEF_H2_ALLOW_CLAMP=1 to continue')
 
-    def run_one_epoch(self, dl, phase, optim=None, collect_views=None, aug_eval=False):
+    def run_one_epoch(self, dl, phase, optim=None, collect_views=None, aug_eval=False, warp_eval=False):
         """solver.py:139-246.  `collect_views` (default: the Solver's setting) = also return the per-view host lists the
         reference returns (inputs, ground truth, predictions, rois); train() / val() only consume losses and metrics and
         pass False, so an epoch stages nothing but a few scalars per step.  With DATA.aug_* on, the inputs in those lists are the CLEAN
         ones the loader delivered: the corrupted copy lives inside the step.  `aug_eval` (test phase, DATA.aug_* on): the model reads
-        batch i corrupted under augment.eval_seed(cfg.seed, i, rank) -- the robustness read-out of `_aug_eval`."""
+        batch i corrupted under augment.eval_seed(cfg.seed, i, rank) -- the robustness read-out of `_aug_eval`.  With DATA.aug_warp /
+        aug_roi_jitter on, the train phase's lists hold the WARPED batch: what the step saw.  `warp_eval` (test phase, a warp on): batch i
+        is warped under warp.eval_seed(cfg.seed, i, rank) -- inputs, target, rest views and rois -- the read-out of `_warp_eval`."""
+        if warp_eval and (phase != 'test' or self.warp is None):
+            raise ValueError('warp_eval is the test phase with DATA.aug_warp / DATA.aug_roi_jitter on')
         if aug_eval and (phase != 'test' or self.augment is None):
             raise ValueError('aug_eval is the test phase with a DATA.aug_* corruption on')
         if phase == 'train' and self.augment is not None:
@@ -558,9 +605,10 @@ class Solver:
             raise ValueError('phase param not found.')
         keep = self.collect_views if collect_views is None else bool(collect_views)
         losses_s, pred_s, gt_s, in_s, rest_s, rois_s, psnr_s, ssim_s = (_HostSink() for _ in range(8))
-        seg_s = (_HostSink(), _HostSink()) if phase == 'test' and self.seg_eval and not aug_eval else None      # (se, cnt) per clean batch
-        slope_s = (_HostSink(), _HostSink()) if phase == 'test' and self.slope_eval and not aug_eval else None  # (se, cnt) per clean batch
-        corr_s = (_HostSink(), _HostSink()) if phase == 'test' and self.corr_eval and not aug_eval else None    # (mom, cnt) per clean batch
+        clean = phase == 'test' and not (aug_eval or warp_eval)         # the read-out passes fill none of the three below
+        seg_s = (_HostSink(), _HostSink()) if clean and self.seg_eval else None          # (se, cnt) per clean batch
+        slope_s = (_HostSink(), _HostSink()) if clean and self.slope_eval else None      # (se, cnt) per clean batch
+        corr_s = (_HostSink(), _HostSink()) if clean and self.corr_eval else None        # (mom, cnt) per clean batch
         gen_num, whole = self._gen_num() if phase == 'test' else (0, True)
         # gradient-norm clipping (SOLVER.clip_grad_norm): [norm, coefficient] of every train step travel like the losses
         clip_s = _HostSink() if phase == 'train' and getattr(optim, 'max_grad_norm', 0.0) > 0 else None
@@ -579,6 +627,7 @@ class Solver:
         lr_first = float(np.float32(float(optim.param_groups[0]['lr']) * optim.lr_schedule.factor(self._lr_seen[1]))) if lr_on else None
         n_batches = n_updates = 0
         n_views = self.train_views if phase == 'train' else 1
+        warp_rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
         if n_views >= 2 and type(self.model).__name__ != 'Model_nefnet':
             raise ValueError("SOLVER.train_views >= 2 is Model_nefnet's multi-view train step; {} takes one view".format(type(self.model).__name__))
         for meta in dl:
@@ -590,10 +639,18 @@ class Solver:
                 if rest_theta is None or 'rest_view' not in meta:
                     raise KeyError("SOLVER.train_views >= 2 needs the batch's rest_view / rest_theta (train_net.build_loaders ships them)")
                 rest_view = torch.as_tensor(meta['rest_view']).to(self.device, non_blocking=True)
+                if self.warp is not None:         # the views are drawn from the warped rest views
+                    source_data, target_view, rest_view, rois = self._warp_batch(
+                        source_data, target_view, rest_view, rois,
+                        _warp.train_seed(self.cfg.get('seed', 0), int(getattr(self.model, 'dropout_epoch', 0)), n_batches, warp_rank))
                 n_sup = views.supervised_views(self.cfg, rest_theta.shape[1])
                 views.check_views(n_views, min(n_sup, rest_view.shape[1]))
                 picked = views.draw_views(self.cfg.get('seed', 0), int(getattr(self.model, 'dropout_epoch', 0)), n_batches, n_views, n_sup)
                 target_view, target_theta = views.select_views(rest_view, rest_theta, picked)
+            elif phase == 'train' and self.warp is not None:
+                source_data, target_view, _, rois = self._warp_batch(
+                    source_data, target_view, None, rois,
+                    _warp.train_seed(self.cfg.get('seed', 0), int(getattr(self.model, 'dropout_epoch', 0)), n_batches, warp_rank))
             stepper = self._graphed_step(optim, source_data, keep) if phase == 'train' else None
             if stepper is not None:
                 # forward + losswrapper + backward + SGD as ONE replayed hipGraph (one graph per batch shape: the final partial
@@ -615,6 +672,9 @@ class Solver:
                 optim.zero_grad()
             else:
                 rest_view = torch.as_tensor(meta['rest_view']).to(self.device, torch.float32).contiguous()
+                if warp_eval:
+                    source_data, target_view, rest_view, rois = self._warp_batch(
+                        source_data, target_view, rest_view, rois, _warp.eval_seed(self.cfg.get('seed', 0), n_batches, warp_rank))
                 if aug_eval:
                     rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
                     source_data = ops.augment(source_data.to(torch.float32).contiguous(), rois, self.augment,

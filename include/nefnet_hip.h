@@ -887,6 +887,56 @@ int nef_augment(const nef_augment_args* a, nef_stream_t stream);
 /* sizeof(nef_augment_args) as the library was built. */
 size_t nef_augment_args_bytes(void);
 
+/* Time warp of a whole train batch with jittered marks (cfg.DATA.aug_warp / aug_roi_jitter; no counterpart in the reference): every
+ * segment of every beat is resampled to a drawn multiple of its length -- inputs, target and rest views alike -- and the marks follow,
+ * each interior one then moved by a drawn integer.  Out of place; no input is written.  Per sample i, with L the row length and
+ * clamp(v, lo, hi) = min(max(v, lo), hi):
+ *   1. edges    c_0 = clamp(rois[i,0,0], 0, L),  c_k = clamp(max(rois[i,k,0], c_{k-1}), 0, L) for k = 1..6,  n_k = c_{k+1} - c_k for k = 0..5.
+ *               Only the clamped values enter any arithmetic or any address: `rois` may hold anything.
+ *   2. draws    z_k = mix(seed, 2^62 + 8 (index0 + i) + k), k = 0..5 (uint64 wrap-around; mix is the counter RNG of the dropout epilogues);
+ *               u_k = (z_k >> 40) 2^-24;  s_k = 1.0 + amp[k] * (2.0 * u_k - 1.0) in fp64.
+ *   3. lengths  m_k = 0 when n_k == 0, else max(1, (int64)floor((double)n_k * s_k + 0.5)).  A cropped beat (c_6 == L: the signal goes on
+ *               behind the row) is not warped, m_k = n_k: shrinking it would label live signal as padding.
+ *   4. new edges d_0 = c_0, d_{k+1} = min(d_k + m_k, L): a stretched beat is cut at L.  The mapping below uses the uncut m_k.
+ *   5. values, for every row x -> y of the sample (V inputs, the target, R rest views):
+ *               t < d_0: y[t] = x[t] (the bits);  t >= d_6: y[t] = +0.0;  t in [d_k, d_{k+1}), j = t - d_k:
+ *               r = (double)n_k / (double)m_k,  p = clamp((j + 0.5) * r - 0.5, 0, n_k - 1),  i0 = floor(p),  f = p - i0,
+ *               i1 = min(i0 + 1, n_k - 1),  x0 = x[c_k + i0],  x1 = x[c_k + i1] as fp64,
+ *               y[t] = (float)x0 when f == 0, else (float)(x0 + f * (x1 - x0)): fp64 without contraction, one rounding to fp32.
+ *               (The half-pixel convention of the ROI resampling; a segment reads nothing from its neighbours.)
+ *   6. marks    e_0 = d_0, e_6 = d_6; for k = 1..5 in order: j_k = (int)(((2 J + 1) * ((z_k >> 16) & 0xFFFFFF)) >> 24) - J with
+ *               J = jitter, e_k = clamp(d_k + j_k, e_{k-1}, d_6).  rois_out[i,k] = [e_k, e_{k+1}] for k = 0..5 and
+ *               rois_out[i,6] = [e_6, rois[i,6,1]].  The signal does not move with the jitter.
+ * Zero amplitudes and jitter 0 return a beat whose rois are contiguous and in range and whose padding is zero bit for bit.  A sample's
+ * result is a function of seed, index0 + i and its own rows.
+ * One 256-thread workgroup per sample; a wave owns one row at a time, a lane four neighbouring outputs = one 16-byte store; wave 0 writes
+ * rois_out.  One writer per element, no atomics, no scratch.
+ * args, data, target, rois or an output NULL, rest or rest_out NULL with R > 0: NEF_E_NULL; B < 1, V outside 1..12, R outside 0..64,
+ * L outside 4 .. 2^24 or L % 4 != 0, an amplitude outside [0, 0.9] (or NaN), jitter outside 0..64: NEF_E_SHAPE; a pointer not 16-byte
+ * aligned, or an output that overlaps an input: NEF_E_UNSUPPORTED.  Every check sits in front of the launch.  Capturable: nothing is read
+ * by the host, nothing is allocated. */
+#define NEF_WARP_MAX_AMP 0.9
+#define NEF_WARP_MAX_JITTER 64
+typedef struct nef_warp_args {
+    const float* data;          /* [B, V, L] */
+    const float* target;        /* [B, L] */
+    const float* rest;          /* [B, R, L]; NULL with R == 0 */
+    const int64_t* rois;        /* [B, 7, 2], any content */
+    float* data_out;            /* [B, V, L] */
+    float* target_out;          /* [B, L] */
+    float* rest_out;            /* [B, R, L]; NULL with R == 0 */
+    int64_t* rois_out;          /* [B, 7, 2] */
+    uint64_t seed;
+    int64_t index0;             /* sample i draws as sample index0 + i */
+    double amp[6];              /* P, PR, QRS, ST, T, TP: each in [0, 0.9] */
+    int32_t jitter;             /* J in 0 .. 64 */
+    int32_t B, V, R, L;
+    int32_t reserved0;          /* 0 */
+} nef_warp_args;
+int nef_warp(const nef_warp_args* a, nef_stream_t stream);
+/* sizeof(nef_warp_args) as the library was built. */
+size_t nef_warp_args_bytes(void);
+
 /* Tianchi train / test batches built on the device from recordings kept in device memory (cfg.DATA.device_resident; the host path is
  * dataset/tianchi.py, EcgTianChiInterval.__getitem__, whose bits this entry promises).  `signal` holds every recording's eight stored
  * leads, lead-major per recording ([8, len_i], recordings concatenated), as int16 (dtype 0) or fp32 (dtype 1) elements.  `plan` is the

@@ -13,6 +13,7 @@
     python tools/bench_adam.py --seg W0 W1 W2 W3 W4 W5 W6 [--parent-tree DIR] [--out profiles/r18_seg_bench_line.json]
     python tools/bench_adam.py --slope F [--parent-tree DIR] [--out profiles/r19_slope_bench_line.json]
     python tools/bench_adam.py --corr F [--parent-tree DIR] [--out profiles/r20_corr_bench_line.json]
+    python tools/bench_adam.py --warp A0 A1 A2 A3 A4 A5 [--roi-jitter J] [--parent-tree DIR] [--out profiles/r25_warp_bench_line.json]
 
 Each measurement runs in a child process of its own under `timeout` (nothing more is started once one fails), `--reps` rounds of
 the three children; every figure is reported as [min, median, max] over the rounds:
@@ -95,7 +96,13 @@ nef_loss_slope_fwd (two launches) and nef_loss_slope_bwd on the batch's predicti
 two shapes: per round and shape the graphed FusedSGD step with the key off (sgd-graph: the parent's code path) and on (sgd-graph-corr), and
 -- with --parent-tree DIR -- DIR's own sgd-graph step.  The config-2 child with the term on also times the three entries alone, cold:
 nef_loss_corr_fwd (two launches) and nef_loss_corr_bwd (three) on the batch's prediction-sized tensors and rois, nef_view_corr_metrics on
-[B, 9, L] rows.  Writes profiles/r20_corr_bench_line.json unless --out says otherwise."""
+[B, 9, L] rows.  Writes profiles/r20_corr_bench_line.json unless --out says otherwise.
+
+--warp A0 .. A5 [--roi-jitter J] measures the time warp of the train batch (DATA.aug_warp = [P, PR, QRS, ST, T, TP], DATA.aug_roi_jitter =
+J), at the same two shapes: per round and shape the graphed FusedSGD step with the keys off (sgd-graph: the parent's code path) and on
+(sgd-graph-warp: one nef_warp launch on the stream in front of every replay, into fresh tensors, as Solver.run_one_epoch places it), and --
+with --parent-tree DIR -- DIR's own sgd-graph step.  The config-2 child with the keys on also times the nef_warp launch alone on the batch's
+inputs, target and rois, cold.  Writes profiles/r25_warp_bench_line.json unless --out says otherwise."""
 import argparse
 import json
 import os
@@ -138,7 +145,7 @@ def cold_ms(launches, dev, reps=30):
 
 
 def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=(), ema=0.0, accum=1, sched=None, ssim=0.0, views=1,
-          seg=None, slope=0.0, corr=0.0):
+          seg=None, slope=0.0, corr=0.0, warp=None, roi_jitter=0):
     import numpy as np
     import torch
     from electrocardio_panorama_amd import ops, synth
@@ -157,6 +164,8 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
             cfg.DATA[k] = v
     if mode == "sgd-graph-seg":
         cfg.SOLVER.seg_weights = [float(w) for w in seg]
+    if mode == "sgd-graph-warp":
+        cfg.DATA.aug_warp, cfg.DATA.aug_roi_jitter = [float(a) for a in warp], int(roi_jitter)
     if mode == "sgd-graph-slope":
         cfg.SOLVER.slope_factor, cfg.SOLVER.slope_loss, cfg.SOLVER.slope_crop = float(slope), "l1_loss", True
     if mode == "sgd-graph-corr":
@@ -166,7 +175,8 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
     seed_torch(cfg.seed)
     model = build_model(cfg).float().to(dev).train()
     lossf = build_loss(cfg)
-    if mode in ("sgd-graph", "sgd-graph-ssim", "sgd-graph-views", "sgd-graph-augment", "sgd-graph-seg", "sgd-graph-slope", "sgd-graph-corr"):
+    if mode in ("sgd-graph", "sgd-graph-ssim", "sgd-graph-views", "sgd-graph-augment", "sgd-graph-seg", "sgd-graph-slope", "sgd-graph-corr",
+                "sgd-graph-warp"):
         optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9)
     elif mode == "sgd-graph-clip":
         optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9, max_grad_norm=clip)
@@ -206,7 +216,19 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
         from electrocardio_panorama_amd.graph import GraphedTrainStep
         graphed = GraphedTrainStep(model, cfg, optimizer=optim)
 
+    warp_cfg, warped = None, []
+    if mode == "sgd-graph-warp":
+        # DATA.aug_warp / aug_roi_jitter as Solver.run_one_epoch places it: one launch on the stream into fresh tensors in front of the
+        # replayed step, batch i under warp.train_seed(seed, 0, i, 0)
+        from electrocardio_panorama_amd import warp as _warp
+        warp_cfg = _warp.from_cfg(cfg)
+        assert warp_cfg is not None
+
     def step():
+        if warp_cfg is not None:
+            d, t, _, r = ops.warp(data, tgt_view, None, rois, warp_cfg, _warp.train_seed(cfg.seed, 0, len(warped), 0))
+            warped.append((d, r) if not warped else None)      # (the first step's, for the result line)
+            return graphed(d, in_theta, tgt_theta, r, t)
         if graphed is not None:
             return graphed(data, in_theta, tgt_theta, rois, tgt_view)
         out, sp, sl = model(data, in_theta, tgt_theta, rois, phase="train")
@@ -291,6 +313,15 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
         y = torch.empty_like(data)
         ms = cold_ms([lambda: ops.augment(data, rois, graphed.augment, seed=_augment.train_seed(1), out=y)], dev)[0]
         res.update(nef_augment_cold_ms=round(ms, 4), nef_augment_cold_GBps=round(2 * 4 * data.numel() / (ms * 1e-3) / 1e9, 1))
+    if mode == "sgd-graph-warp":
+        d0, r0 = warped[0]
+        res.update(aug_warp=[float(a) for a in warp], aug_roi_jitter=int(roi_jitter), loss_row=[round(float(v), 6) for v in graphed.losses.tolist()],
+                   input_elements_changed=round(float((d0 != data).float().mean().item()), 4),
+                   marks_moved=round(float((r0 != rois).float().mean().item()), 4))
+    if mode == "sgd-graph-warp" and (B, L) == EMA_SHAPES["config2"]:
+        ms = cold_ms([lambda: ops.warp(data, tgt_view, None, rois, warp_cfg, 1)], dev)[0]
+        nbytes = 2 * 4 * (data.numel() + tgt_view.numel()) + 2 * 8 * rois.numel()
+        res.update(nef_warp_cold_ms=round(ms, 4), nef_warp_bytes=nbytes, nef_warp_cold_GBps=round(nbytes / (ms * 1e-3) / 1e9, 1))
     if mode == "sgd-graph-seg":
         res.update(seg_weights=[float(w) for w in seg], loss_row=[round(float(v), 6) for v in graphed.losses.tolist()])
     if mode == "sgd-graph-seg" and (B, L) == EMA_SHAPES["config2"]:
@@ -707,6 +738,60 @@ def augment_rounds(args):
         f.write(line + "\n")
 
 
+def warp_rounds(args):
+    """--warp A0 .. A5 [--roi-jitter J]: `--reps` alternating rounds of fresh children per shape (see the module docstring); prints and
+    writes one JSON line."""
+    modes = dict({"sgd-graph": 900, "sgd-graph-warp": 900}, **({"parent": 900} if args.parent_tree else {}))
+    results = {(shape, mode): [] for shape in EMA_SHAPES for mode in modes}
+    for rnd in range(args.reps):
+        order = list(modes) if rnd % 2 == 0 else list(reversed(modes))
+        for shape, (B, L) in EMA_SHAPES.items():
+            for mode in order:
+                if mode == "parent":
+                    # the parent's tool lacks --warp: its `child` function is called directly, in a fresh process of its own tree
+                    tree = os.path.abspath(args.parent_tree)
+                    code = ("import importlib.util as u; s = u.spec_from_file_location('parent_bench', %r); m = u.module_from_spec(s); "
+                            "s.loader.exec_module(m); m.child('sgd-graph', %d, %d, B=%d, L=%d)"
+                            % (os.path.join(tree, "tools", "bench_adam.py"), args.steps, args.warmup, B, L))
+                    cmd = ["timeout", "-k", "10", str(modes[mode]), sys.executable, "-c", code]
+                else:
+                    tree = ROOT
+                    cmd = ["timeout", "-k", "10", str(modes[mode]), sys.executable, os.path.join(ROOT, "tools", "bench_adam.py"), "--child", mode,
+                           "--steps", str(args.steps), "--warmup", str(args.warmup), "--shape", str(B), str(L),
+                           "--warp"] + [repr(float(a)) for a in args.warp] + ["--roi-jitter", str(args.roi_jitter)]
+                results[(shape, mode)].append(run_child(cmd, tree, mode))
+                sys.stderr.write(f"round {rnd + 1}/{args.reps} {shape} {mode}: {results[(shape, mode)][-1]['ms_per_step']} ms/step\n")
+                sys.stderr.flush()
+
+    def spread(shape, mode, key):
+        v = sorted(x[key] for x in results[(shape, mode)])
+        return [v[0], v[len(v) // 2], v[-1]]
+
+    out = {"metric": "ms per train step, graphed FusedSGD with the time warp off and on -- on: one nef_warp launch per step in front of the "
+                     "replay ([min, median, max] over rounds of fresh processes)", "rounds": args.reps,
+           "aug_warp": [float(a) for a in args.warp], "aug_roi_jitter": args.roi_jitter,
+           "shapes": {k: "B=%d, 3 leads, L=%d, one GPU, dropout on" % v for k, v in EMA_SHAPES.items()}}
+    for shape in EMA_SHAPES:
+        out[shape + "_warp_off_ms"] = spread(shape, "sgd-graph", "ms_per_step")
+        out[shape + "_warp_on_ms"] = spread(shape, "sgd-graph-warp", "ms_per_step")
+        out[shape + "_input_elements_changed"] = spread(shape, "sgd-graph-warp", "input_elements_changed")[1]
+        if args.parent_tree:
+            out[shape + "_parent_ms"] = par = spread(shape, "parent", "ms_per_step")
+            # to be read against each other: the keys-off median and the parent's own min-max spread; the bar with the keys on: + 0.3 ms
+            out[shape + "_warp_off_median_inside_parent_spread"] = par[0] <= out[shape + "_warp_off_ms"][1] <= par[2]
+            out[shape + "_warp_on_median_minus_parent_median_ms"] = round(out[shape + "_warp_on_ms"][1] - par[1], 3)
+    out.update(nef_warp_cold_ms=spread("config2", "sgd-graph-warp", "nef_warp_cold_ms"),
+               nef_warp_cold_GBps=spread("config2", "sgd-graph-warp", "nef_warp_cold_GBps"),
+               nef_warp_bytes=results[("config2", "sgd-graph-warp")][0]["nef_warp_bytes"],
+               launch_note="the nef_warp launch alone at config 2 on the batch's inputs, target and rois (no rest views); cold = a 512 MiB "
+                           "buffer written before each call; bytes counted: every input read once, every output written",
+               steps=args.steps, warmup=args.warmup)
+    line = json.dumps(out)
+    print(line)
+    with open(args.out or os.path.join(ROOT, "profiles", "r25_warp_bench_line.json"), "w") as f:
+        f.write(line + "\n")
+
+
 def seg_rounds(args):
     """--seg W0 .. W6: `--reps` alternating rounds of fresh children per shape (see the module docstring); prints and writes one JSON line."""
     modes = dict({"sgd-graph": 900, "sgd-graph-seg": 900}, **({"parent": 900} if args.parent_tree else {}))
@@ -1023,13 +1108,16 @@ def main():
                     help="measure the wave-segment weights of the reconstruction term, SOLVER.seg_weights = W0 .. W6 (see above)")
     ap.add_argument("--slope", type=float, default=None, metavar="F", help="measure the slope term of the loss, slope_factor = F (see above)")
     ap.add_argument("--corr", type=float, default=None, metavar="F", help="measure the correlation term of the loss, corr_factor = F (see above)")
+    ap.add_argument("--warp", type=float, nargs=6, default=None, metavar="A",
+                    help="measure the time warp of the train batch, DATA.aug_warp = A0 .. A5 (see above)")
+    ap.add_argument("--roi-jitter", type=int, default=0, metavar="J", help="with --warp: DATA.aug_roi_jitter = J")
     ap.add_argument("--only-shape", choices=sorted(EMA_SHAPES), default=None, help="with --views, --slope or --corr: measure this shape only")
     ap.add_argument("--shape", type=int, nargs=2, default=(256, 5000), metavar=("B", "L"), help="with --child: batch size and length")
     ap.add_argument("--parent-tree", default=None,
                     help="with --clip / --weight-decay / --ema: a built checkout whose own sgd-graph child runs in every round")
     ap.add_argument("--child", choices=sorted({**MODES, **CLIP_MODES, **WD_MODES, **EMA_MODES, "lars-graph": 900, "lamb-graph": 900, "sgd-graph-accum": 900,
                                              "sgd-graph-sched": 900, "sgd-graph-ssim": 900, "sgd-graph-views": 900, "sgd-graph-augment": 900,
-                                             "sgd-graph-seg": 900, "sgd-graph-slope": 900, "sgd-graph-corr": 900}),
+                                             "sgd-graph-seg": 900, "sgd-graph-slope": 900, "sgd-graph-corr": 900, "sgd-graph-warp": 900}),
                     default=None)
     args = ap.parse_args()
     if args.child == "sgd-graph-ema" and not (args.ema is not None and 0.0 < args.ema < 1.0):
@@ -1090,15 +1178,24 @@ def main():
         ap.error("--corr F > 0 is a measurement of its own")
     if args.child == "sgd-graph-corr" and args.corr is None:
         ap.error("--child sgd-graph-corr needs --corr F")
-    if (args.parent_tree and args.corr is None and args.slope is None and args.seg is None and not args.augment and args.views is None and args.clip is None and args.weight_decay is None and args.ema is None and args.trust is None
+    if args.warp is not None and not args.child and (
+            args.corr is not None or args.slope is not None or args.seg is not None or args.augment or args.views is not None
+            or args.clip is not None or args.weight_decay is not None or args.ema is not None or args.trust is not None
+            or args.accum is not None or args.sched is not None or args.ssim is not None):
+        ap.error("--warp is a measurement of its own")
+    if args.child == "sgd-graph-warp" and args.warp is None:
+        ap.error("--child sgd-graph-warp needs --warp A0 .. A5")
+    if (args.parent_tree and args.warp is None and args.corr is None and args.slope is None and args.seg is None and not args.augment and args.views is None and args.clip is None and args.weight_decay is None and args.ema is None and args.trust is None
             and args.accum is None and args.sched is None and args.ssim is None):
-        ap.error("--parent-tree goes with --clip, --weight-decay, --ema, --trust, --accum, --sched, --ssim, --views, --augment, --seg, --slope or --corr")
+        ap.error("--parent-tree goes with --clip, --weight-decay, --ema, --trust, --accum, --sched, --ssim, --views, --augment, --seg, --slope, --corr or --warp")
     if args.child:
         return child(args.child, args.steps if args.child != "adam-eager" else max(3, args.steps // 2), args.warmup,
                      B=args.shape[0], L=args.shape[1], clip=args.clip or 0.0, wd=args.weight_decay or 0.0,
                      no_decay=tuple(args.no_decay), ema=args.ema or 0.0, accum=args.accum or 1,
                      sched=(args.sched, args.sched_warmup) if args.child == "sgd-graph-sched" else None, ssim=args.ssim or 0.0,
-                     views=args.views[0] if args.views else 1, seg=args.seg, slope=args.slope or 0.0, corr=args.corr or 0.0)
+                     views=args.views[0] if args.views else 1, seg=args.seg, slope=args.slope or 0.0, corr=args.corr or 0.0, warp=args.warp, roi_jitter=args.roi_jitter)
+    if args.warp is not None:
+        return warp_rounds(args)
     if args.corr is not None:
         return corr_rounds(args)
     if args.slope is not None:
