@@ -2716,7 +2716,8 @@ int nef_mix_bwd(const float* gD, const float* latent, const float* z1, const flo
                 int shared, nef_stream_t stream) {
     NEF_ENTER();
     NEF_REQUIRE(gD && latent && z1 && z2r && q && gz1 && gz2r && gq, NEF_E_NULL);
-    NEF_REQUIRE(B > 0 && V > 0 && T > (up || shared ? 1 : 0) && c1 >= 0 && c1 < V && c2 >= 0 && c2 < V, NEF_E_SHAPE);
+    // (up with T = 1, a 4-sample signal's latent row: both upsampled positions are edges, up2_bwd_edge gives each the weight 1)
+    NEF_REQUIRE(B > 0 && V > 0 && T > (shared ? 1 : 0) && c1 >= 0 && c1 < V && c2 >= 0 && c2 < V, NEF_E_SHAPE);
     const bool al16 = (((uintptr_t)gD | (uintptr_t)latent | (uintptr_t)z1 | (uintptr_t)z2r | (uintptr_t)gz1 | (uintptr_t)gz2r) & 15) == 0;
 #define NEF_MIX_BWD(UP, SHARED)                                                                                                \
     hipLaunchKernelGGL((mix_bwd_kernel<UP, SHARED>), dim3(nef_stream_grid((int64_t)B * 256, 4)), dim3(256), 0, NEF_ST, gD, latent, \

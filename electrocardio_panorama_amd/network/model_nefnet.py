@@ -20,6 +20,8 @@ import torch.nn as nn
 from .. import augment as _augment
 from .. import engine, ops
 
+MIN_SIGNAL_LENGTH = 4      # one latent position (T = L / 4 = 1); every multiple of 4 from here up runs (README.md)
+
 
 class _Block(nn.Module):
     """Parameter container of BasicBlock (model_nefnet.py:36-47 / encoder/resnet_1d.py:27-37)."""
@@ -172,8 +174,8 @@ class Model_nefnet(nn.Module):
             raise RuntimeError("Model_nefnet runs on a HIP device only (no CPU path); move model and inputs to cuda")
         if rois.dtype.is_floating_point:
             raise TypeError("rois must be an integer tensor [B,7,2] (the reference mutates float rois in place)")
-        if x.shape[-1] % 4 != 0:
-            raise ValueError("signal length must be a multiple of 4")
+        if x.shape[-1] < MIN_SIGNAL_LENGTH or x.shape[-1] % 4 != 0:
+            raise ValueError(f"signal length must be a multiple of 4, at least {MIN_SIGNAL_LENGTH} (got {x.shape[-1]})")
 
     @staticmethod
     def _f32(t):

@@ -376,7 +376,7 @@ int nef_mix_bwd(const float* gD, const float* latent, const float* z1, const flo
                 int shared, nef_stream_t stream);
 /* relu_z1 != 0: z1 is a ReLU output; gz1 is additionally masked with z1 > 0.
  * up != 0: gD is the gradient wrt the x2-UPSAMPLED decoder input, [..][256][2T] (what the first decoder conv's backward-data
- *   writes); the upsampling adjoint (nef_upsample2_bwd) is taken while reading it.  T > 1.
+ *   writes); the upsampling adjoint (nef_upsample2_bwd) is taken while reading it.  Any T >= 1, as nef_upsample2_bwd.
  * shared != 0: gD is the two-pass gradient wrt D2 of nef_mix_fwd_shared (below), [2B][256][T] or, with `up`, [2B][256][2T],
  *   instead of the three-pass [3B][256][..].  T > 1. */
 

@@ -74,10 +74,12 @@ def _choices(V):
     return [c for c in ((0, 0), (V - 1, 0), (1, 2)) if max(c) < V]
 
 
-@pytest.mark.parametrize("T", [64, 70, 1250])
+@pytest.mark.parametrize("T", [64, 70, 1250, 65, 125, 7, 5, 4, 2])
 @pytest.mark.parametrize("V", [1, 3, 12])
 def test_unpool_mixes_equal_the_op_pairs(V, T):
-    """T = 64: T % 4 == 0 (8-byte kernels); 70: T % 4 == 2 (the pair kernels); 1250: more than one 64-lane trip per segment."""
+    """T = 64: T % 4 == 0 (8-byte kernels); 70: T % 4 == 2 (the pair kernels); 1250: more than one 64-lane trip per segment;
+    65, 125: odd (the scalar kernels, one position per lane; 125 is the latent row of a 500-sample beat); 7, 5, 4, 2: rows shorter
+    than 8 deal their positions to the lanes one by one whatever their parity, and some of the seven segments are empty."""
     from electrocardio_panorama_amd import synth
     B = 3
     rois = torch.from_numpy(synth.make_rois(np.random.default_rng(5), B, 4 * T))
@@ -120,24 +122,63 @@ def test_unpool_mixes_on_a_malformed_roi_table():
     assert torch.equal(gq_f, gq)
 
 
-def test_unpool_mixes_against_the_oracle():
-    """One case against the CPU oracle's roi_unpool / lead_mean and autograd, at the bars test_mix and
-    test_roi_backward_and_status hold the two-pass ops to (1e-6 forward, 1e-5 gradients)."""
+def _off8(t):
+    """The same values 8 bytes off a 16-byte boundary (test_shared_first_conv_pieces)."""
+    buf = torch.empty(t.numel() + 2, device=DEV)
+    v = buf[2:].view(t.shape)
+    v.copy_(t)
+    assert v.data_ptr() % 16 == 8
+    return v
+
+
+@pytest.mark.parametrize("T", [66, 1250])
+def test_unpool_mixes_off_a_16_byte_boundary(T):
+    """T % 4 == 2 on operands that are only 8-byte aligned: the un-pooling mixes fall back from the row-pair kernels to the 8-byte forms
+    (and deal the z2 half's positions in pairs, not fours).  Same latent / D2 / gz1 / gz2b bits as the aligned run; gq, whose lane order
+    follows the form, has the bits of the two-pass pair on the same misaligned operands.  (The outputs are the ops' own allocations:
+    gz1 is 16-byte aligned in both runs, one misaligned operand is enough to leave the pair kernels.)"""
+    from electrocardio_panorama_amd import synth
+    o = ops()
+    B, V, choice = 3, 3, (1, 2)
+    rois = g(torch.from_numpy(synth.make_rois(np.random.default_rng(8), B, 4 * T)))
+    z1, z2b, q, gD = _inputs(B, V, T, 400)
+    z1o, gDo = _off8(z1), _off8(gD)
+    lat, D2 = o.lead_mean_mix_unpool(z1, z2b, rois, q, V, choice, T)
+    lat_o, D2_o = o.lead_mean_mix_unpool(z1o, z2b, rois, q, V, choice, T)
+    assert torch.equal(lat_o, lat) and torch.equal(D2_o, D2)
+    z2r = o.roi_unpool_fwd(z2b, rois, T)
+    for relu in (False, True):
+        gz1, gz2b, gq = o.mix_bwd_shared_unpool(gD, lat, z1, z2b, rois, q, V, choice, relu_z1=relu)
+        gz1_o, gz2b_o, gq_o = o.mix_bwd_shared_unpool(gDo, _off8(lat), z1o, z2b, rois, q, V, choice, relu_z1=relu)
+        assert torch.equal(gz1_o, gz1) and torch.equal(gz2b_o, gz2b), relu
+        pair = o.mix_bwd_shared_up(gDo, _off8(lat), z1o, _off8(z2r), q, V, choice, relu_z1=relu)
+        assert torch.equal(pair[0], gz1) and torch.equal(o.roi_unpool_bwd(pair[1], rois), gz2b), relu
+        assert torch.equal(gq_o, pair[2]), relu
+        assert rel(gq_o, gq) < 1e-6, relu
+
+
+@pytest.mark.parametrize("L", [512, 500, 260, 28, 20, 8])
+def test_unpool_mixes_against_the_oracle(L):
+    """Against the CPU oracle's roi_unpool / lead_mean and autograd in fp64, at the bars test_mix and test_roi_backward_and_status
+    hold the two-pass ops to (1e-6 forward, 1e-5 gradients).  T = 128; 125 and 65 (odd); 7, 5 and 2 (shorter than 8)."""
     o = ops()
     from oracle import nefnet_oracle as orc
     from electrocardio_panorama_amd import synth
-    B, V, L, c1, c2 = 3, 3, 512, 2, 1
+    B, V, c1, c2 = 3, 3, 2, 1
     T = L // 4
     rois = torch.from_numpy(synth.make_rois(np.random.default_rng(6), B, L))
-    z1, zs, q = (rnd(B, 128 * V, T, seed=50).requires_grad_(True), rnd(B, 128 * V, 7, 32, seed=51).requires_grad_(True),
-                 rnd(B, 256, seed=52).requires_grad_(True))
+    z1f, zsf, qf = rnd(B, 128 * V, T, seed=50), rnd(B, 128 * V, 7, 32, seed=51), rnd(B, 256, seed=52)
+    z1, zs, q = (t.double().requires_grad_(True) for t in (z1f, zsf, qf))
     z2r = orc.roi_unpool(zs, rois)
+    assert z2r.dtype == torch.float64 and z2r.shape == (B, 128 * V, T)
     latent = torch.cat([orc.lead_mean(z1, V), orc.lead_mean(z2r, V)], 1)
     D2 = torch.cat([q[:, :, None] * latent,
                     q[:, :, None] * torch.cat([z1[:, 128 * c1:128 * (c1 + 1)], z2r[:, 128 * c2:128 * (c2 + 1)]], 1)], 0)
-    lat_d, D2_d = o.lead_mean_mix_unpool(g(z1.detach()), g(zs.detach()), g(rois), g(q.detach()), V, (c1, c2), T)
+    st = torch.zeros(1, dtype=torch.int32, device=DEV)
+    lat_d, D2_d = o.lead_mean_mix_unpool(g(z1f), g(zsf), g(rois), g(qf), V, (c1, c2), T, st)
+    assert int(st.item()) == 0
     assert rel(lat_d, latent) < 1e-6 and rel(D2_d, D2) < 1e-6
     gD = rnd(*D2.shape, seed=53)
-    D2.backward(gD)
-    gz1, gz2b, gq = o.mix_bwd_shared_unpool(g(gD), lat_d, g(z1.detach()), g(zs.detach()), g(rois), g(q.detach()), V, (c1, c2))
+    D2.backward(gD.double())
+    gz1, gz2b, gq = o.mix_bwd_shared_unpool(g(gD), lat_d, g(z1f), g(zsf), g(rois), g(qf), V, (c1, c2))
     assert rel(gz1, z1.grad) < 1e-5 and rel(gz2b, zs.grad) < 1e-5 and rel(gq, q.grad) < 1e-5

@@ -107,7 +107,7 @@ def test_rejects_bad_calls_without_touching_the_gpu():
     assert L.nef_bn_bwd_ws_bytes(bnb(form=9)) == 0
     assert L.nef_bn_bwd_ws_bytes(bnb(form=1)) == L.nef_bn_bwd_ws_bytes(bnb(form=0)) + 3 * 2 * 16 * 4 > 3 * 2 * 16 * 4
     assert L.nef_mix_bwd(None, None, None, None, None, None, None, None, 1, 1, 8, 0, 0, None, 0, 0, 0, None) == -2
-    assert L.nef_mix_bwd(8, 8, 8, 8, 8, 8, 8, 8, 1, 1, 1, 0, 0, None, 0, 1, 0, None) == -1        # up: T > 1
+    assert L.nef_mix_bwd(8, 8, 8, 8, 8, 8, 8, 8, 1, 1, 0, 0, 0, None, 0, 1, 0, None) == -1        # up: T >= 1 (a 4-sample signal's row)
     assert L.nef_mix_bwd(8, 8, 8, 8, 8, 8, 8, 8, 1, 1, 1, 0, 0, None, 0, 0, 1, None) == -1        # shared: T > 1
 
 

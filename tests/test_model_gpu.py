@@ -167,7 +167,7 @@ def test_side_stream_modes_are_bit_identical(monkeypatch):
 
 
 def oracle_replaying(m, outs, b, V, seed, masks=None, dt=torch.float32, reg="l1_loss", model2=False, fold=None,
-                     lead_choice=None):
+                     lead_choice=None, zero_floor=None):
     """Run the CPU oracle on the same inputs while it REPLAYS the discrete decisions (ReLU on/off, L1 signs) the HIP
     path took in `m`'s last forward (tests/decisions.py); assert every decision the oracle would have taken differently
     is a tie; assert the gradients agree at the tie-free bars (flat <= 1e-4, per tensor <= 1e-3).  Returns
@@ -187,7 +187,8 @@ def oracle_replaying(m, outs, b, V, seed, masks=None, dt=torch.float32, reg="l1_
     rl[0].backward()
     assert_flips_are_ties(dec)
     named = {k: p.grad for k, p in m.named_parameters()}
-    flat, worst = assert_grad_parity(named, P, dead=orc.DEAD_PARAMS, n_terms=3.0 * b["data"].shape[0] * b["data"].shape[2])
+    flat, worst = assert_grad_parity(named, P, dead=orc.DEAD_PARAMS, n_terms=3.0 * b["data"].shape[0] * b["data"].shape[2],
+                                     zero_floor=zero_floor)
     dec.oracle_buffers, dec.oracle_params = Bf, P
     return ref, rl, dec, flat
 
