@@ -13,6 +13,8 @@ PRODUCT = {
     "NEF_H2_TAIL": "warn (default): split-fp16 call sites whose operand is heavy-tailed (ops.H2_TAIL_FRAC) are counted and reported; "
                    "fp32: such WEIGHT-GRADIENT sites run on the fp32 kernels for their lifetime (per site, per rank)",
     "NEF_H2_ALLOW_CLAMP": "1: Solver warns instead of raising when a split-fp16 launch clamped outside a protected train step",
+    "NEF_LIVE": "1 (default): the encoder-side convs skip the tiles in a beat's all-zero tail (ops.LIVE / ops.LIVE_WGRAD); fwd: forward and "
+                "backward-data convs only, the weight gradients multiply every item; 0: off",
     "NEF_WINOGRAD": "fp32 path: 4 (default) F(4,.) forms where allowed, 2 / 1: F(2,.) only, 0: direct kernels only",
     "NEF_SIDE_STREAM": "auto (default) / 1 / 0: weight gradients on a second HIP stream",
     "NEF_SOLVER_GRAPH": "0: Solver never replays the captured step",

@@ -183,10 +183,13 @@ SIGNATURES = {
     "nef_stem_bwd_weight": (i32, [p, p, p, p, p, sz, i32, i32, i32, p]),
     "nef_pack_weights": (i32, [C.POINTER(PackDesc), i32, p]),
     "nef_pack_bytes": (sz, [C.POINTER(PackDesc)]),
+    "nef_live_extent": (i32, [p, p, i32, i32, i32, p]),
     "nef_conv_fwd": (i32, [C.POINTER(ConvArgs), p]),
+    "nef_conv_fwd_live": (i32, [C.POINTER(ConvArgs), p, i32, p]),
     "nef_conv_args_bytes": (sz, []),
     "nef_conv_bwd_weight_ws_bytes": (sz, [C.POINTER(BwwArgs)]),
     "nef_conv_bwd_weight": (i32, [C.POINTER(BwwArgs), p]),
+    "nef_conv_bwd_weight_live": (i32, [C.POINTER(BwwArgs), p, i32, p]),
     "nef_bww_args_bytes": (sz, []),
     "nef_h2_tail_census_ws_bytes": (sz, [i32, i32, i32]),
     "nef_h2_tail_census": (i32, [p, i64, i64, i32, i32, i32, i32, p, i64, i64, p, p, i32, i32, p, f32, f32, p, sz, p, p, p, p]),

@@ -173,11 +173,19 @@ __global__ __launch_bounds__(256) void pack_h2_kernel(H2PackTable tab) {
 // workgroups per CU the 64-channel tile is compiled for (168 VGPRs); the x2-upsampling prologue needs 2 (at three it spills 8
 // registers and is 2 % slower)
 constexpr int H2_OCC1 = 3;
+// LIVE EXTENT (nef_conv_fwd_live; the plain forms PRO = 0, !PACK only): `live_` [B][G] + `live_add_` promise that the operand, after
+// in_scale, is exactly zero at every t >= live_[b * G + g] + live_add_.  A tile whose whole staged window t0 - PAD .. lies behind that
+// bound is DEAD: its buffer descriptors get a zero extent (the stage-0 loads return 0.0 without a memory access), the stage loop runs
+// zero times (nst = 0: the loop's own trip count, no branch around it), its magnitude counts as 0 (Al[] is not published), so no
+// rescue pass; the epilogue then runs unchanged on +0 accumulators and writes every output.  Bit for bit what the full
+// loop gives with finite weights: products of zeros accumulate to +0.  (A non-finite weight would have made NaNs of those zeros;
+// such a step is already broken, and the launch's live tiles still report it.)
 // PACK (short rows, 8 <= T <= 64, T % 4 == 0): a tile is `tps` SAMPLES laid end to end at a pitch of T + 4 positions -- the four
 // positions between two samples are staged as zeros (the zero padding of both neighbours) and their outputs are dropped; a lane's
 // four adjacent outputs lie inside one sample or inside one gap.  No prologue, channel scale or statistics in this mode.
 template <int K, int PRO, int TM, bool PACK = false>
-__global__ __launch_bounds__(256, (TM == 1 && (PRO & 2) == 0) ? H2_OCC1 : 2) void conv_h2_kernel(nef_conv_args a_, int tps_, int n_tiles_, int m_tiles_) {
+__global__ __launch_bounds__(256, (TM == 1 && (PRO & 2) == 0) ? H2_OCC1 : 2) void conv_h2_kernel(nef_conv_args a_, int tps_, int n_tiles_, int m_tiles_,
+                                                                                                const int32_t* live_, int live_add_) {
     constexpr int MT = 64 * TM;                    // output channels per workgroup: 2 (co) x 2 (t) waves of TM x 4 tiles
     constexpr bool UP = (PRO & 2) != 0, AFF = (PRO & 1) != 0;
     // PH (pro_mode 4, polyphase backward-data through a x2 upsampling): the input is a FULL-resolution tensor [Cin_g / 2][2 T] read as
@@ -224,7 +232,7 @@ __global__ __launch_bounds__(256, (TM == 1 && (PRO & 2) == 0) ? H2_OCC1 : 2) voi
     // the first copy for the sake of the second and cost the K = 3 launches 2 .. 15 % (tools/h2_rescue_ab.sh).
     typedef const nef_conv_args __attribute__((address_space(4))) kargs_t;
     auto tile_pass = [&](kargs_t* const ap, const int bid, const int tid, const int tps, const int n_tiles, const int m_tiles,
-                         const float xs_force, const bool last) __attribute__((always_inline)) -> float {
+                         const float xs_force, const bool last, const int32_t* const lv, const int lv_add) __attribute__((always_inline)) -> float {
 #define a (*ap)
     const int tile = bid % n_tiles;
     const int gm = bid / n_tiles;
@@ -247,6 +255,11 @@ __global__ __launch_bounds__(256, (TM == 1 && (PRO & 2) == 0) ? H2_OCC1 : 2) voi
     }
     const int m0 = mt * MT;
     const int T = a.T, Cig = a.Cin_g, Cog = a.Cout_g;
+    bool dead = false;      // workgroup-uniform: every staged position of this tile lies in the operand's all-zero tail
+    if constexpr (PRO == 0 && !PACK) {
+        if (lv) dead = t0 - PAD >= lv[b0 * a.G + g] + lv_add;
+    }
+    const unsigned op_bytes = dead ? 0u : 0x7FFFFFFCu;
     const int lane = tid & 63, wave = tid >> 6;
     const int lo = lane & 31, hi = lane >> 5;
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
@@ -254,11 +267,11 @@ __global__ __launch_bounds__(256, (TM == 1 && (PRO & 2) == 0) ? H2_OCC1 : 2) voi
     const int Tin = UP ? (T >> 1) : (PH ? 2 * T : T);      // row pitch of the input tensor
 
     const float* const xbase = a.x + (int64_t)b0 * a.x_bs + (int64_t)g * a.x_gs;
-    const __amdgpu_buffer_rsrc_t xrs = nef_rsrc(xbase);
+    const __amdgpu_buffer_rsrc_t xrs = nef_rsrc_n(xbase, op_bytes);
     const _Float16* const wph = reinterpret_cast<const _Float16*>(a.wp);
     const int ncot = Cog / 32, nc16 = Cig / 16;
     // this wave's 2 TM A fragments of (chunk c, tap kk): contiguous at ((g*nc16 + c)*K + kk)*ncot*2 KB + (m0/32 + TM wm)*2 KB
-    const __amdgpu_buffer_rsrc_t wrs = nef_rsrc(wph + ((int64_t)g * nc16 * K * ncot * 2 + (int64_t)(m0 / 32 + TM * wm) * 2) * 512);
+    const __amdgpu_buffer_rsrc_t wrs = nef_rsrc_n(wph + ((int64_t)g * nc16 * K * ncot * 2 + (int64_t)(m0 / 32 + TM * wm) * 2) * 512, op_bytes);
     const unsigned a_tap = (unsigned)(ncot * 2 * 1024);      // bytes between taps of one chunk
 
     const int64_t soff = (int64_t)b0 * a.sc_bs + (int64_t)g * a.sc_gs;
@@ -492,7 +505,7 @@ __global__ __launch_bounds__(256, (TM == 1 && (PRO & 2) == 0) ? H2_OCC1 : 2) voi
     NEF_H2X_STORE(0, Xl)
     __syncthreads();
 
-    const int nst = Cig / KC;
+    const int nst = dead ? 0 : Cig / KC;
     // this lane's fragment address inside a plane: position wn * 32 + lo (+ the s-dependent constant), channels 8 hi ..
     const unsigned fb_lane = (unsigned)(hi * HALF + (wn * 32 + lo) * 16);
     for (int st = 0; st < nst; ++st) {
@@ -564,7 +577,8 @@ __global__ __launch_bounds__(256, (TM == 1 && (PRO & 2) == 0) ? H2_OCC1 : 2) voi
         __syncthreads();
     }
     {
-        const float wg_ = fmaxf(fmaxf(Al[0], Al[1]), fmaxf(Al[2], Al[3]));      // workgroup-uniform
+        // workgroup-uniform (a dead tile never reached the loop's last stage, which publishes the magnitudes: its operand's is 0)
+        const float wg_ = dead ? 0.f : fmaxf(fmaxf(Al[0], Al[1]), fmaxf(Al[2], Al[3]));
         if (!last && !(wg_ * xs_ < 65000.f) && wg_ < 3e38f) {
             __syncthreads();      // (Al is rewritten by the second pass)
             return wg_;
@@ -869,19 +883,19 @@ __global__ __launch_bounds__(256, (TM == 1 && (PRO & 2) == 0) ? H2_OCC1 : 2) voi
     };      // tile_pass
     kargs_t* ap_ = (kargs_t*)__builtin_amdgcn_kernarg_segment_ptr();      // (a_ is the segment's first member)
     (void)a_;
-    const float over_ = tile_pass(ap_, (int)blockIdx.x, (int)threadIdx.x, tps_, n_tiles_, m_tiles_, 0.f, false);
+    const float over_ = tile_pass(ap_, (int)blockIdx.x, (int)threadIdx.x, tps_, n_tiles_, m_tiles_, 0.f, false, live_, live_add_);
     if (over_ > 0.f) {
         int e_;
         (void)frexpf(over_, &e_);
         int bid_ = (int)blockIdx.x, tid_ = (int)threadIdx.x, tps2_ = tps_, nt2_ = n_tiles_, mt2_ = m_tiles_;
         asm volatile("" : "+s"(ap_), "+s"(bid_), "+s"(tps2_), "+s"(nt2_), "+s"(mt2_));
         asm volatile("" : "+v"(tid_));
-        (void)tile_pass(ap_, bid_, tid_, tps2_, nt2_, mt2_, ldexpf(1.f, 9 - e_ < 100 ? 9 - e_ : 100), true);
+        (void)tile_pass(ap_, bid_, tid_, tps2_, nt2_, mt2_, ldexpf(1.f, 9 - e_ < 100 ? 9 - e_ : 100), true, nullptr, 0);      // (a dead tile asks for no rescue)
     }
 }
 
 template <int K, int PRO, int TM, bool PACK = false>
-int launch_h2(const nef_conv_args& a, hipStream_t st) {
+int launch_h2(const nef_conv_args& a, hipStream_t st, const int32_t* live = nullptr, int live_add = 0) {
     constexpr int MT = 64 * TM;
     constexpr int XROW = NTO + K - 1;
     constexpr int P4 = (XROW + 3) / 4 + 1;
@@ -895,7 +909,7 @@ int launch_h2(const nef_conv_args& a, hipStream_t st) {
     const int m_tiles = a.Cout_g / MT;
     const int64_t blocks = (int64_t)a.G * m_tiles * n_tiles;
     if (blocks <= 0 || blocks > 0x7fffffff) return NEF_E_SHAPE;
-    hipLaunchKernelGGL((conv_h2_kernel<K, PRO, TM, PACK>), dim3((unsigned)blocks), dim3(256), lds, st, a, tps, n_tiles, m_tiles);
+    hipLaunchKernelGGL((conv_h2_kernel<K, PRO, TM, PACK>), dim3((unsigned)blocks), dim3(256), lds, st, a, tps, n_tiles, m_tiles, live, live_add);
     return nef_launch_status();
 }
 
@@ -924,7 +938,8 @@ __attribute__((visibility("hidden"))) bool nef_h2_ok(const nef_conv_args* a) {
            (!(a->pro_mode & 1) || a->Cin_g <= PRO_MAX_CIN);
 }
 
-__attribute__((visibility("hidden"))) int nef_h2_launch(const nef_conv_args* a, hipStream_t st) {
+// `live` / `live_add`: nef_conv_fwd_live's promise (NULL: none); only the plain forms <K, 0, TM> take it, every other form ignores it
+__attribute__((visibility("hidden"))) int nef_h2_launch(const nef_conv_args* a, hipStream_t st, const int32_t* live, int live_add) {
     if (!nef_h2_ok(a)) return NEF_E_SHAPE;
     if ((a->pro_mode & 1) && !(a->pro_a && a->pro_b && a->pro_Bp > 0)) return NEF_E_NULL;
     const bool wide = a->Cout_g % 128 == 0;
@@ -933,10 +948,10 @@ __attribute__((visibility("hidden"))) int nef_h2_launch(const nef_conv_args* a, 
     // always take the 64-channel tile (the 128-channel instantiations <3, 2, 2> / <3, 3, 2> are no longer built)
     if (a->T < NTO / 2)      // short rows: the 64-channel tile (the 128-channel form spills 185 registers with the per-lane sample offsets)
         return a->K == 1 ? launch_h2<1, 0, 1, true>(*a, st) : launch_h2<3, 0, 1, true>(*a, st);
-    if (a->K == 7) return wide ? launch_h2<7, 0, 2>(*a, st) : launch_h2<7, 0, 1>(*a, st);
-    if (a->K == 1) return wide ? launch_h2<1, 0, 2>(*a, st) : launch_h2<1, 0, 1>(*a, st);
+    if (a->K == 7) return wide ? launch_h2<7, 0, 2>(*a, st, live, live_add) : launch_h2<7, 0, 1>(*a, st, live, live_add);
+    if (a->K == 1) return wide ? launch_h2<1, 0, 2>(*a, st, live, live_add) : launch_h2<1, 0, 1>(*a, st, live, live_add);
     switch (a->pro_mode) {
-        case 0: return wide ? launch_h2<3, 0, 2>(*a, st) : launch_h2<3, 0, 1>(*a, st);
+        case 0: return wide ? launch_h2<3, 0, 2>(*a, st, live, live_add) : launch_h2<3, 0, 1>(*a, st, live, live_add);
         case 1: return wide ? launch_h2<3, 1, 2>(*a, st) : launch_h2<3, 1, 1>(*a, st);
         case 2: return launch_h2<3, 2, 1>(*a, st);
         case 4: return wide ? launch_h2<3, 4, 2>(*a, st) : launch_h2<3, 4, 1>(*a, st);

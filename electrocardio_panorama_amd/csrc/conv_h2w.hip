@@ -67,7 +67,55 @@ struct H2WArgs {
     int B, T, G, Cig, Cog, pro_Bp, S, tps, n_tiles, m_tiles, c_tiles, teams;
     float x_scale, gy_scale;
     int xclamp;      // pro_mode bit 2 (polyphase weight gradient): the window's columns -1 and T hold x[0] and x[T-1] instead of zeros
+    // live extents (nef_conv_bwd_weight_live; conv_h2w2_kernel with PRO = 0 only, else NULL): per group, rank[N] = live items in front
+    // of item N of the full (sample, tile) space ([n_tiles + 1] words) and items[j] = the j-th live item ([n_tiles] words)
+    const int32_t* live_rank;
+    const int32_t* live_items;
 };
+
+// The two tables of a launch from the promise "every product of item (b, tile) with tile * TT >= live[b * G + g] + add is zero": the
+// live tiles of a sample are its first cnt = ceil(bound / TT) ones.  One workgroup per group; the prefix over the samples is a
+// block scan, 256 samples at a time with a carry.
+__global__ __launch_bounds__(256) void h2w_live_tables_kernel(const int32_t* __restrict__ live, int add, int B, int G, int tps,
+                                                              int32_t* __restrict__ rank, int32_t* __restrict__ items) {
+    extern __shared__ int pre_[];      // [B + 1]: pre_[b] = live items of the samples in front of b
+    __shared__ int sc_[256];
+    const int g = blockIdx.x;
+    const int n_tiles = B * tps;
+    const int tid = (int)threadIdx.x;
+    int carry = 0;
+    for (int base = 0; base < B; base += 256) {
+        const int b = base + tid;
+        int c = 0;
+        if (b < B) {
+            const int bound = live[b * G + g] + add;
+            c = bound > 0 ? (bound + TT - 1) / TT : 0;
+            c = c < tps ? c : tps;
+        }
+        sc_[tid] = c;
+        __syncthreads();
+        for (int o = 1; o < 256; o <<= 1) {      // inclusive scan
+            const int v = tid >= o ? sc_[tid - o] : 0;
+            __syncthreads();
+            sc_[tid] += v;
+            __syncthreads();
+        }
+        if (b < B) pre_[b + 1] = carry + sc_[tid];
+        carry += sc_[255];
+        __syncthreads();
+    }
+    if (tid == 0) pre_[0] = 0;
+    __syncthreads();
+    int32_t* const rk = rank + (int64_t)g * (n_tiles + 1);
+    int32_t* const it = items + (int64_t)g * n_tiles;
+    for (int N = threadIdx.x; N < n_tiles; N += 256) {
+        const int b = N / tps, tile = N - b * tps;
+        const int p0 = pre_[b], c = pre_[b + 1] - p0;
+        rk[N] = p0 + (tile < c ? tile : c);
+        if (tile < c) it[p0 + tile] = N;
+    }
+    if (threadIdx.x == 0) rk[n_tiles] = pre_[B];
+}
 
 
 // (x0, x1) * s -> fp16 pair h, residual pair l.  No clamp: a tile whose data does not fit is redone with its own scale (range
@@ -530,6 +578,26 @@ __global__ __launch_bounds__(64 * (WM / WR * WN + NP), 1) void conv_h2w2_kernel(
     const int n_lo = (int)(per * sp);
     int n_hi = (int)(per * (sp + 1));
     if (n_hi > a.n_tiles) n_hi = a.n_tiles;
+    // Live extents: the share keeps its boundaries in the full item space; inside it the dead items are left out, in order -- every
+    // partial sum keeps its bits (a dead item adds products of zeros: + 0).  The loops below run over n_lo .. n_lo + (live items of
+    // the share) and item(N) maps such a position to the (sample, tile) item it stands for: one scalar load from the launch's table.
+    const int32_t* items_ = nullptr;      // the group's list of live items, and what turns a loop position into an index of it
+    int ioff_ = 0;
+    if constexpr (PRO == 0) {
+        if (a.live_rank && n_lo < n_hi) {
+            const int32_t* const rk = a.live_rank + (int64_t)g * (a.n_tiles + 1);
+            const int j_lo = rk[n_lo], j_hi = rk[n_hi];
+            items_ = a.live_items + (int64_t)g * a.n_tiles;
+            ioff_ = j_lo - n_lo;
+            n_hi = n_lo + (j_hi - j_lo);
+        }
+    }
+    auto item = [&](int N) __attribute__((always_inline)) -> int {
+        if constexpr (PRO == 0) {
+            if (items_) return N < n_hi ? items_[N + ioff_] : 0;
+        }
+        return N;
+    };
 
     // Range rescue (round 5, as conv_h2w_kernel): the whole share again with scales from its own operands if an element left fp16's
     // range; the pass -- both roles -- is a lambda inlined twice.  The producers know the magnitudes; they publish them through the
@@ -572,11 +640,12 @@ __global__ __launch_bounds__(64 * (WM / WR * WN + NP), 1) void conv_h2w2_kernel(
     Stage st0, st1;
 
     // a tile away from the row ends: the whole window (and, UP, every source column) exists
-    auto is_edge = [&](int N) { const int t0_ = (N % a.tps) * TTv; return !(t0_ > 0 && t0_ + TTv + 6 <= T); };
+    auto is_edge = [&](int N) { const int t0_ = (item(N) % a.tps) * TTv; return !(t0_ > 0 && t0_ + TTv + 6 <= T); };
 
     auto issue = [&](Stage& z, int N, auto edge_c, int part) __attribute__((always_inline)) {
         constexpr bool EDGE = decltype(edge_c)::value;
-        const int b_ = N / a.tps, t0_ = (N % a.tps) * TTv;
+        const int Ni_ = item(N);
+        const int b_ = Ni_ / a.tps, t0_ = (Ni_ % a.tps) * TTv;
         const bool on_ = N < n_hi;
         // gy: descriptor origin = column t0 of the tile's first row
         const int64_t goff = (int64_t)b_ * a.gy_bs + (int64_t)g * a.gy_gs + (int64_t)(mt * RG) * T + (EDGE ? 0 : t0_);
@@ -637,7 +706,7 @@ __global__ __launch_bounds__(64 * (WM / WR * WN + NP), 1) void conv_h2w2_kernel(
 
     auto store = [&](Stage& z, int N, unsigned char* bufp, auto edge_c, int part) __attribute__((always_inline)) {
         constexpr bool EDGE = decltype(edge_c)::value;
-        const int t0_ = (N % a.tps) * TTv;
+        const int t0_ = (item(N) % a.tps) * TTv;
 #pragma unroll
         for (int q = 0; q < ((part & 1) ? NGQ : 0); ++q) {
             const f32x4 v = z.gq[q];
@@ -857,8 +926,16 @@ __attribute__((visibility("hidden"))) int nef_h2w_splits(int B, int T, int G, in
     return S;
 }
 
+// bytes of the two live-extent tables behind the partial sums in the workspace (nef_conv_bwd_weight_ws_bytes counts them in)
+__attribute__((visibility("hidden"))) size_t nef_h2w_live_bytes(int B, int T, int G) {
+    const int64_t n_tiles = (int64_t)B * ((T + TT - 1) / TT);
+    return (size_t)G * (2 * n_tiles + 1) * sizeof(int32_t);
+}
+
 // `b`: the call as nef_conv_bwd_weight validated it (x_scale / gy_scale of 0 mean 1: scale_from); S from nef_h2w_splits
-__attribute__((visibility("hidden"))) int nef_h2w_launch(const nef_bww_args& b, int S, hipStream_t st) {
+// `live` / `live_add` (NULL: none) + `tables`, nef_h2w_live_bytes of scratch: nef_conv_bwd_weight_live's promise
+__attribute__((visibility("hidden"))) int nef_h2w_launch(const nef_bww_args& b, int S, hipStream_t st, const int32_t* live, int live_add,
+                                                          void* tables) {
     const int B = b.B, T = b.T, G = b.G, Cig = b.Cin_g, Cog = b.Cout_g, K = b.K;
     int pro_mode = b.pro_mode;
     if (!nef_h2w_ok(B, T, Cig, Cog, K, pro_mode)) return NEF_E_SHAPE;
@@ -875,6 +952,15 @@ __attribute__((visibility("hidden"))) int nef_h2w_launch(const nef_bww_args& b, 
     a.teams = G * S;
     a.x_scale = b.x_scale, a.gy_scale = b.gy_scale;
     a.xclamp = (pro_mode >> 2) & 1;
+    a.live_rank = a.live_items = nullptr;
+    // only the producer / consumer form without a prologue skips dead items (every other form multiplies them: exact either way)
+    if (live && tables && pro_mode == 0 && h2w2_form(Cog, 0) && (size_t)(B + 1) * sizeof(int) <= 48 * 1024) {
+        int32_t* const rank = static_cast<int32_t*>(tables);
+        int32_t* const items = rank + (int64_t)G * ((int64_t)a.n_tiles + 1);
+        hipLaunchKernelGGL(h2w_live_tables_kernel, dim3((unsigned)G), dim3(256), (size_t)(B + 1) * sizeof(int), st, live, live_add, B, G,
+                           a.tps, rank, items);
+        a.live_rank = rank, a.live_items = items;
+    }
     pro_mode &= 3;
     const int Tin = (pro_mode & 2) ? T / 2 : T;
     a.x_end = ((int64_t)(B - 1) * b.x_bs + (int64_t)(G - 1) * b.x_gs + (int64_t)Cig * Tin) * 4;

@@ -2192,7 +2192,7 @@ constexpr int CHAN_SUM_SPLIT = 16;
 
 // conv_h2.hip: direct convolutions on exact fp16 splits of the fp32 operands (conv args wino = 3)
 __attribute__((visibility("hidden"))) bool nef_h2_ok(const nef_conv_args* a);
-__attribute__((visibility("hidden"))) int nef_h2_launch(const nef_conv_args* a, hipStream_t st);
+__attribute__((visibility("hidden"))) int nef_h2_launch(const nef_conv_args* a, hipStream_t st, const int32_t* live, int live_add);
 __attribute__((visibility("hidden"))) int nef_h2_pack(const nef_pack_desc* descs, int n, hipStream_t st);
 __attribute__((visibility("hidden"))) int nef_h2_pack_status(const nef_pack_desc* d);
 
@@ -2269,8 +2269,7 @@ int nef_pack_weights(const nef_pack_desc* descs, int n, nef_stream_t stream) {
 size_t nef_conv_args_bytes(void) { return sizeof(nef_conv_args); }
 
 
-int nef_conv_fwd(const nef_conv_args* a, nef_stream_t stream) {
-    NEF_ENTER();
+static int conv_fwd_entry(const nef_conv_args* a, const int32_t* live, int32_t live_add, nef_stream_t stream) {
     NEF_REQUIRE(a && a->x && a->wp && a->y, NEF_E_NULL);
     NEF_REQUIRE(a->B > 0 && a->T > 0 && a->G > 0, NEF_E_SHAPE);
     const int K = a->K;
@@ -2285,7 +2284,7 @@ int nef_conv_fwd(const nef_conv_args* a, nef_stream_t stream) {
     NEF_REQUIRE((!a->res_scale && !a->gate_rowscale && a->stats_mode == 0) || a->wino == 3, NEF_E_UNSUPPORTED);
     if (a->wino == 3) {      // split-fp16 operand (nef_pack_desc.wino 3): direct conv on exact fp16 splits (conv_h2.hip)
         NEF_REQUIRE(nef_h2_ok(a), NEF_E_SHAPE);
-        return nef_h2_launch(a, st);
+        return nef_h2_launch(a, st, live, live_add);
     }
     bool big = (a->Cout_g % 128 == 0);
     if (big) {
@@ -2322,6 +2321,20 @@ int nef_conv_fwd(const nef_conv_args* a, nef_stream_t stream) {
     }
 }
 
+int nef_conv_fwd(const nef_conv_args* a, nef_stream_t stream) {
+    NEF_ENTER();
+    return conv_fwd_entry(a, nullptr, 0, stream);
+}
+
+// nef_conv_fwd with the live-extent promise (include/nefnet_hip.h).  The plain split-fp16 forms (wino 3, pro_mode 0, T >= 128) skip the
+// main loop of column tiles that lie in the operand's zero tail -- same bits, the outputs are all written; every other form runs as
+// nef_conv_fwd does and never looks at the table.
+int nef_conv_fwd_live(const nef_conv_args* a, const int32_t* live, int32_t live_add, nef_stream_t stream) {
+    NEF_ENTER();
+    NEF_REQUIRE(live, NEF_E_NULL);
+    return conv_fwd_entry(a, live, live_add, stream);
+}
+
 int nef_conv_stats_slots(int T, int Cout_g) {
     if (T <= 0 || T % 2 != 0 || Cout_g <= 0 || Cout_g % 64 != 0) return 0;
     const bool wide = (Cout_g % 128 == 0);
@@ -2349,7 +2362,8 @@ size_t nef_conv_bwd_weight_ws_bytes(const nef_bww_args* a) {
             if (p_ > partials) partials = p_;
         }
     }
-    return (size_t)partials * G * K * Cout_g * Cin_g * sizeof(float);
+    // form 3: + the two item tables of nef_conv_bwd_weight_live behind the partial sums
+    return (size_t)partials * G * K * Cout_g * Cin_g * sizeof(float) + (a->form == 3 && partials ? nef_h2w_live_bytes(B, T, G) : 0);
 }
 
 // form 0: the direct kernel, with or without the input prologue.  *S_used = partial sums left in a.ws
@@ -2389,16 +2403,16 @@ static int bww_direct(const nef_bww_args& a, hipStream_t st, int* S_used) {
 }
 
 // form 3: exact fp16 splits of both operands (conv_h2w.hip)
-static int bww_h2(const nef_bww_args& a, hipStream_t st, int* S_used) {
+static int bww_h2(const nef_bww_args& a, hipStream_t st, int* S_used, const int32_t* live, int live_add) {
     NEF_REQUIRE(a.G > 0 && nef_h2w_ok(a.B, a.T, a.Cin_g, a.Cout_g, a.K, a.pro_mode), NEF_E_SHAPE);
     NEF_REQUIRE(!(a.pro_mode && a.in_scale), NEF_E_UNSUPPORTED);
     const int S = nef_h2w_splits(a.B, a.T, a.G, a.Cin_g, a.Cout_g, a.K, a.pro_mode, S_used);
-    NEF_REQUIRE(a.ws_bytes >= (size_t)*S_used * a.G * a.K * a.Cout_g * a.Cin_g * sizeof(float), NEF_E_WORKSPACE);
-    return nef_h2w_launch(a, S, st);
+    const size_t partial_bytes = (size_t)*S_used * a.G * a.K * a.Cout_g * a.Cin_g * sizeof(float);
+    NEF_REQUIRE(a.ws_bytes >= partial_bytes + (live ? nef_h2w_live_bytes(a.B, a.T, a.G) : 0), NEF_E_WORKSPACE);
+    return nef_h2w_launch(a, S, st, live, live_add, live ? static_cast<char*>(a.ws) + partial_bytes : nullptr);
 }
 
-int nef_conv_bwd_weight(const nef_bww_args* args, nef_stream_t stream) {
-    NEF_ENTER();
+static int conv_bwd_weight_entry(const nef_bww_args* args, const int32_t* live, int32_t live_add, nef_stream_t stream) {
     NEF_REQUIRE(args && args->x && args->gy && args->gw && args->ws, NEF_E_NULL);
     nef_bww_args a = *args;
     if (!(a.pro_mode & 1) && a.pro_Bp <= 0) a.pro_Bp = 1;
@@ -2408,7 +2422,7 @@ int nef_conv_bwd_weight(const nef_bww_args* args, nef_stream_t stream) {
     switch (a.form) {
         case 0: rc = bww_direct(a, st, &S); break;
         case 4: rc = nef_mfma_bww_wino4(a, st, &S); break;
-        case 3: rc = bww_h2(a, st, &S); break;
+        case 3: rc = bww_h2(a, st, &S, live, live_add); break;
         default: return NEF_E_UNSUPPORTED;
     }
     if (rc != NEF_OK) return rc;
@@ -2416,6 +2430,20 @@ int nef_conv_bwd_weight(const nef_bww_args* args, nef_stream_t stream) {
     hipLaunchKernelGGL(conv_bwd_weight_reduce, dim3(nef_stream_grid(n, 256)), dim3(256), 0, st, (const float*)a.ws, a.gw, a.G,
                        a.Cout_g, a.Cin_g, a.K, S);
     return nef_launch_status();
+}
+
+int nef_conv_bwd_weight(const nef_bww_args* args, nef_stream_t stream) {
+    NEF_ENTER();
+    return conv_bwd_weight_entry(args, nullptr, 0, stream);
+}
+
+// nef_conv_bwd_weight with the live-extent promise (include/nefnet_hip.h): form 3 only.  The producer / consumer kernel without a
+// prologue leaves the dead items out inside each share; every other kernel of the form multiplies them as before (exact either way).
+int nef_conv_bwd_weight_live(const nef_bww_args* args, const int32_t* live, int32_t live_add, nef_stream_t stream) {
+    NEF_ENTER();
+    NEF_REQUIRE(args && live, NEF_E_NULL);
+    NEF_REQUIRE(args->form == 3, NEF_E_UNSUPPORTED);
+    return conv_bwd_weight_entry(args, live, live_add, stream);
 }
 
 size_t nef_chan_sum_ws_bytes(int C) { return (size_t)CHAN_SUM_SPLIT * C * sizeof(double); }

@@ -150,7 +150,8 @@ extern "C" {
 // conv_h2w.hip (form 3): shape rule, split count S (and partial sums per element), launch with that S
 NEF_HIDDEN bool nef_h2w_ok(int B, int T, int Cig, int Cog, int K, int pro_mode);
 NEF_HIDDEN int nef_h2w_splits(int B, int T, int G, int Cig, int Cog, int K, int pro_mode, int* partials);
-NEF_HIDDEN int nef_h2w_launch(const nef_bww_args& a, int S, hipStream_t st);
+NEF_HIDDEN int nef_h2w_launch(const nef_bww_args& a, int S, hipStream_t st, const int32_t* live, int live_add, void* tables);
+NEF_HIDDEN size_t nef_h2w_live_bytes(int B, int T, int G);
 // conv_bww_glds.hip (form 4 by LDS-DMA): `half` 0 for K = 3, 4 / 5 for the two launches of K = 7; S_max: the split count the
 // workspace was sized for; fixed_S > 0: use exactly this many (second launch of K = 7)
 NEF_HIDDEN bool nef_bww_glds_ok(const nef_bww_args& a);

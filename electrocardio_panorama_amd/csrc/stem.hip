@@ -334,9 +334,58 @@ __global__ __launch_bounds__(256) void stem_bwd_weight_reduce(const float* __res
     if (wave == 0 && i < n) gw[i] = (sm[0][lane] + sm[1][lane]) + (sm[2][lane] + sm[3][lane]);
 }
 
+// Live extent of the stem's output, one workgroup per (sample, lead) row.  e = 1 + index of the row's last element with x != 0.f
+// (-0.f is zero, NaN is not; an all-zero row: 0).  Conv output j reads x[2j - 7 .. 2j + 7], so it can be non-zero up to
+// j = (e + 6) / 2; pooled output tp covers j = 2tp - 1 .. 2tp + 1, so it can be non-zero up to tp = cj / 2 (cj = the conv's extent).
+// Everything behind is ReLU(0) = max(0, ..) = exactly 0: the stem has no bias.
+__global__ __launch_bounds__(256) void live_extent_kernel(const float* __restrict__ x, int32_t* __restrict__ live, int L, int vec) {
+    __shared__ int sm[4];
+    const float* const row = x + (int64_t)blockIdx.x * L;
+    int e = 0;      // (the index grows with the trip count: the last hit of a thread is its largest)
+    if (vec) {
+        const float4* const row4 = reinterpret_cast<const float4*>(row);
+        for (int i = threadIdx.x; i < L / 4; i += 256) {
+            const float4 v = row4[i];
+            const int m = v.w != 0.f ? 4 : (v.z != 0.f ? 3 : (v.y != 0.f ? 2 : (v.x != 0.f ? 1 : 0)));
+            if (m) e = 4 * i + m;
+        }
+    } else {
+        for (int i = threadIdx.x; i < L; i += 256)
+            if (row[i] != 0.f) e = i + 1;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int t = __shfl_xor(e, o, 64);
+        e = t > e ? t : e;
+    }
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = e;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int a = sm[0] > sm[1] ? sm[0] : sm[1], b = sm[2] > sm[3] ? sm[2] : sm[3];
+        e = a > b ? a : b;
+        int cj = 0, lv = 0;
+        if (e) {
+            cj = (e + 6) / 2 + 1;
+            cj = cj < L / 2 ? cj : L / 2;
+            lv = cj / 2 + 1;
+            lv = lv < L / 4 ? lv : L / 4;
+        }
+        live[blockIdx.x] = lv;
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int nef_live_extent(const float* x, int32_t* live, int B, int V, int L, nef_stream_t stream) {
+    NEF_ENTER();
+    NEF_REQUIRE(x && live, NEF_E_NULL);
+    NEF_REQUIRE(B > 0 && V > 0 && L >= 4 && L % 4 == 0 && (int64_t)B * V <= 0x7fffffff, NEF_E_SHAPE);
+    const int vec = (reinterpret_cast<uintptr_t>(x) & 15) == 0;      // (L % 4 == 0: every row is then 16-byte aligned)
+    hipLaunchKernelGGL(live_extent_kernel, dim3((unsigned)(B * V)), dim3(256), 0, (hipStream_t)stream, x, live, L, vec);
+    return nef_launch_status();
+}
 
 int nef_stem_fwd(const float* x, const float* w, float* y, int B, int V, int L, nef_stream_t stream) {
     NEF_ENTER();

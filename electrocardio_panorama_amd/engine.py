@@ -60,23 +60,38 @@ class DropCfg:
 # ----------------------------------------------------------------------------------------------
 # BasicBlock (resnet_1d.py:42-53 with k=7; model_nefnet.py:48-60 with k=3)
 # ----------------------------------------------------------------------------------------------
-def block_fwd(xv, P, prefix, K, Cog, drop, in_scale=None):
+def _live_add(live, n):
+    """The promise `live` = (table, addend) behind a bias-free conv that widens the extent by n positions."""
+    return None if live is None else (live[0], live[1] + n)
+
+
+def block_live_out(saved):
+    """The live-extent promise that holds for a block's OUTPUT: its input's, widened by both convs -- with the identity residual only
+    (the residual conv has a bias: its output has no zero tail)."""
+    live = saved[9] if len(saved) > 9 else None
+    return None if saved[6] else _live_add(live, 2 * ((saved[4] - 1) // 2))
+
+
+def block_fwd(xv, P, prefix, K, Cog, drop, in_scale=None, live=None):
     """`in_scale` (tensor [B, G, Cin], batch stride, group stride): the block's input is xv * in_scale per (sample, channel) -- applied
     by the first conv while it stages and by the last one to its residual, so the scaled tensor is never written (split-fp16
-    launches, identity residual only: the caller checks block_scale_ok)."""
+    launches, identity residual only: the caller checks block_scale_ok).
+    `live` = (table, addend): xv is exactly zero at t >= table[b, g] + addend (ops.live_extent through bias-free convs).
+    The block's convs have no bias and ReLU / dropout keep zeros, so conv1's output h carries the promise widened by (K-1)/2."""
     G = xv.G
-    h = ops.conv(xv, ops.pack_weight(P[prefix + ".conv1.weight"], G, T=xv.T), Cog, K, relu=True, in_scale=in_scale, **drop.args(prefix))
+    h = ops.conv(xv, ops.pack_weight(P[prefix + ".conv1.weight"], G, T=xv.T), Cog, K, relu=True, in_scale=in_scale, live=live,
+                 **drop.args(prefix))
     res_conv = (K == 3 and Cog != xv.Cg)                     # model_nefnet.py:54
     assert in_scale is None or not res_conv
     if res_conv:
         r = ops.conv(xv, ops.pack_weight(P[prefix + ".residual_conv.weight"], G, T=xv.T), Cog, 1,
-                     bias=P[prefix + ".residual_conv.bias"])
+                     bias=P[prefix + ".residual_conv.bias"], live=live)
         resv = GV.dense(r, G)
     else:
         resv = xv
     y = ops.conv(GV.dense(h, G), ops.pack_weight(P[prefix + ".conv2.weight"], G, T=xv.T), Cog, K, res=resv, relu=True,
-                 res_scale=in_scale)
-    return y, (xv, h, y, prefix, K, Cog, res_conv, drop.scale, in_scale)
+                 res_scale=in_scale, live=_live_add(live, (K - 1) // 2))
+    return y, (xv, h, y, prefix, K, Cog, res_conv, drop.scale, in_scale, live)
 
 
 def block_scale_ok(P, prefix, G, T):
@@ -174,16 +189,24 @@ def block_bwd(saved, gy, P, grads, out=None, side=None, pre_gated=False, gate_in
     `g2_chan_sum`: chan_sum of the gated gy where its producer already formed it -- it is the residual conv's bias gradient."""
     xv, h, y, prefix, K, Cog, res_conv, dscale = saved[:8]
     in_scale = saved[8] if len(saved) > 8 else None      # the block input is xv * in_scale: the returned gradient is wrt THAT product
+    # live extents of the two gradient operands: g2 is gated by y and gc1 by h (dropout included), so each is exactly zero wherever
+    # that forward activation was -- y only has a zero tail behind the identity residual
+    live_x = saved[9] if len(saved) > 9 else None
+    live_h = _live_add(live_x, (K - 1) // 2)
+    live_y = block_live_out(saved)
+    # A weight gradient takes the promise only where BOTH its operands carry the tail: its magnitude words (the next step's scales)
+    # are taken over the live items.  conv1: gc1's bound = the input's + PAD.  conv2: g2's bound = h's + PAD, behind the identity
+    # residual only -- z1_conv's g2 is gated by an output without a zero tail, so its conv2 and residual-conv gradients run in full.
     side = side or ops._Inline()
     G, Cig = xv.G, xv.Cg
     g2 = gy if pre_gated else ops.gate(gy, y)                # through the final ReLU
     g2v, hv = GV.dense(g2, G), GV.dense(h, G)
-    grads[prefix + ".conv2.weight"] = side.run(lambda: ops.conv_bwd_weight(hv, g2v, K, site=P[prefix + ".conv2.weight"].data_ptr()), h, g2)
+    grads[prefix + ".conv2.weight"] = side.run(lambda: ops.conv_bwd_weight(hv, g2v, K, site=P[prefix + ".conv2.weight"].data_ptr(), live=live_y), h, g2)
     # through conv2, then dropout and the inner ReLU: h > 0 <=> ReLU active and kept
     gc1 = ops.conv(g2v, ops.pack_weight(P[prefix + ".conv2.weight"], G, flip=True, T=xv.T, f4=_bwd_f4(K)), Cog, K, gate=hv,
-                   gate_scale=dscale, role="conv_bwd_data")
+                   gate_scale=dscale, role="conv_bwd_data", live=live_y)
     gc1v = GV.dense(gc1, G)
-    grads[prefix + ".conv1.weight"] = side.run(lambda: ops.conv_bwd_weight(xv, gc1v, K, in_scale=in_scale, site=P[prefix + ".conv1.weight"].data_ptr()), xv.t, gc1)
+    grads[prefix + ".conv1.weight"] = side.run(lambda: ops.conv_bwd_weight(xv, gc1v, K, in_scale=in_scale, site=P[prefix + ".conv1.weight"].data_ptr(), live=live_h), xv.t, gc1)
     if res_conv:
         grads[prefix + ".residual_conv.weight"] = side.run(lambda: ops.conv_bwd_weight(xv, g2v, 1, site=P[prefix + ".residual_conv.weight"].data_ptr()), xv.t, g2)
         grads[prefix + ".residual_conv.bias"] = g2_chan_sum if g2_chan_sum is not None else side.run(lambda: ops.chan_sum(g2), g2)
@@ -199,10 +222,10 @@ def block_bwd(saved, gy, P, grads, out=None, side=None, pre_gated=False, gate_in
         slots = ops.conv_stats_buffer(wp1f, xv.B, G, Cig, xv.T, xv.t.device)
         if slots is not None:
             gx = ops.conv(gc1v, wp1f, Cig, K, res=resv, gate=xv, gate_scale=1.0, gate_rowscale=in_scale, stats=slots, stats_mode=1,
-                          role="conv_bwd_data")
+                          role="conv_bwd_data", live=live_h)
             return gx, ops.slots_to_rows(slots, xv.B)
     return ops.conv(gc1v, wp1f, Cig, K, res=resv,
-                    out=out, gate=xv if gate_input else None, gate_scale=1.0, role="conv_bwd_data")
+                    out=out, gate=xv if gate_input else None, gate_scale=1.0, role="conv_bwd_data", live=live_h)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -453,21 +476,26 @@ def _latents(P, x, in_theta, rois, drop, save, pack_side=None):
     r0 = (T - 1) // 2
     win = (r0 - 2, 6) if (T % 2 == 0 and r0 - 2 >= 0 and r0 + 4 <= T) else None
     ops.pack_many(_latent_pack_requests(P, V, T, win, False))       # every conv operand of this function in one launch
+    # the beat's all-zero tail, measured on the tensor the stem reads: the stem's output is exactly zero behind live[b, v], and every
+    # bias-free conv below widens that by (K-1)/2 -- the promise is carried down the chain, never taken from rois or configuration
+    live = (ops.live_extent(x), 0) if ops.LIVE else None
     a = ops.stem_fwd(x, P["W_encoder.conv1.weight"])
     if pack_side is not None:
         pack_side.join()
     sv["blk_enc"] = []
     for i in range(3):
-        a, s = block_fwd(GV.dense(a, V), P, f"W_encoder.layer1.{i}", 7, 128, drop)
+        a, s = block_fwd(GV.dense(a, V), P, f"W_encoder.layer1.{i}", 7, 128, drop, live=live)
         sv["blk_enc"].append(s)
+        live = block_live_out(s)
     e = ops.theta_mlp_fwd(in_theta, P["mlp1.weight"], P["mlp1.bias"])           # [B, V, 128]
     if block_scale_ok(P, "w_conv.0", V, T):
         # a * e is never written: w_conv's first conv scales while it stages, its last conv scales the residual (round 5)
-        enc, sv["blk_w_conv"] = block_fwd(GV.dense(a, V), P, "w_conv.0", 3, 128, drop, in_scale=(e, V * 128, 128))
+        enc, sv["blk_w_conv"] = block_fwd(GV.dense(a, V), P, "w_conv.0", 3, 128, drop, in_scale=(e, V * 128, 128), live=live)
     else:
         ew = ops.chscale_fwd(a, e)
-        enc, sv["blk_w_conv"] = block_fwd(GV.dense(ew, V), P, "w_conv.0", 3, 128, drop)
-    z1, sv["blk_z1"] = block_fwd(GV.half(enc, V, 0), P, "z1_conv.0", 3, 128, drop)
+        enc, sv["blk_w_conv"] = block_fwd(GV.dense(ew, V), P, "w_conv.0", 3, 128, drop, live=live)
+    live = block_live_out(sv["blk_w_conv"])
+    z1, sv["blk_z1"] = block_fwd(GV.half(enc, V, 0), P, "z1_conv.0", 3, 128, drop, live=live)
     # z2_conv1 feeds only roi_algin, which reads exactly two time rows: run the block on the window of
     # six samples whose centre two are exact (k=3 twice -> 2 samples of context per side) instead of all T.
     if win is not None:

@@ -187,6 +187,51 @@ def stem_fwd(x, w):
     return y
 
 
+# Live extents: the convs behind the bias-free stem skip the column tiles that lie in a beat's all-zero tail.  Off: every
+# launch goes through the plain entry points, as if no table had been handed over (same bits either way).
+_LV = _env.get("NEF_LIVE", "1")
+if _LV not in ("0", "1", "fwd"):
+    raise ValueError(f"NEF_LIVE={_LV!r}: expected 0, 1 or fwd")
+LIVE = _LV != "0"
+LIVE_WGRAD = _LV == "1"       # ... the weight gradients too (needs LIVE)
+_LIVE_HOST = [None, None]     # (table, its host copy): one read-back per profiled step, for bench.py's executed-work figures
+_LIVE_ACC = {}                # tag -> [sum of live-tile fractions, launches] over the launches of ONE profile (PROFILE list)
+_LIVE_ACC_OF = [None]         # the PROFILE list _LIVE_ACC belongs to
+
+
+def live_extent(x):
+    """int32 [B, V]: from which position on ops.stem_fwd(x, .)'s output row (b, v) is exactly zero (nef_live_extent).  No host read."""
+    L = _lib.load()
+    _chk(x)
+    B, V, Ln = x.shape
+    live = torch.empty(B, V, device=x.device, dtype=torch.int32)
+    ev = _hbm("live_extent", x)
+    _lib.check(L.nef_live_extent(_p(x), _p(live), B, V, Ln, _stream()), "nef_live_extent")
+    _done(ev)
+    return live
+
+
+def _live_note(tag, frac):
+    """Executed-work figure of a profiled launch: EXEC_FP16[tag] = 3 x the mean live fraction of the tag's launches in this profile."""
+    if _LIVE_ACC_OF[0] is not PROFILE:
+        _LIVE_ACC.clear()
+        _LIVE_ACC_OF[0] = PROFILE
+    acc = _LIVE_ACC.setdefault(tag, [0.0, 0])
+    acc[0] += frac
+    acc[1] += 1
+    EXEC_FP16[tag] = 3.0 * acc[0] / acc[1]
+
+
+def _live_frac(live, pad, T, tile=256):
+    """Mean fraction of `tile`-column tiles a split-fp16 launch with this promise multiplies: tile t0 is live iff t0 < table + addend
+    + pad (profiled launches only: the one place a table is read back, once per table, BEFORE the launch's start event)."""
+    if _LIVE_HOST[0] is not live[0]:
+        _LIVE_HOST[0], _LIVE_HOST[1] = live[0], live[0].to("cpu", torch.int64)
+    tps = (T + tile - 1) // tile
+    bound = _LIVE_HOST[1] + int(live[1]) + pad
+    return float(((bound + tile - 1) // tile).clamp(0, tps).double().mean()) / tps
+
+
 def stem_bwd_weight(x, w, gy):
     L = _lib.load()
     _chk(x), _chk(w), _chk(gy)
@@ -753,15 +798,25 @@ def _operand(a, xv, in_scale, pro):
 
 def conv(xv, wp, Cog, K, out=None, bias=None, in_scale=None, res=None, gate=None, gate_scale=1.0, relu=False,
          mask=None, drop_p=0.0, drop_scale=1.0, seed=0, role="conv_fwd", pro=None, seed_dev=None, stats=None, bnb=None,
-         x_scale=0.0, tag_extra="", res_scale=None, gate_rowscale=None, stats_mode=0):
+         x_scale=0.0, tag_extra="", res_scale=None, gate_rowscale=None, stats_mode=0, live=None):
     """out = epilogue(conv1d(prologue(x) * in_scale, w) + bias + res * res_scale).  `xv`, `res`, `gate`, `out` are GV views;
     `in_scale` / `res_scale` are (tensor, batch_stride, group_stride).  `pro` = (mode, a, b, Bp): input prologue applied while
     staging -- bit0 BatchNorm affine + ReLU with a/b [P, C_in], bit1 x2 linear upsampling of a half-resolution input
     (the output is then 2*xv.T long).  `stats`: a conv_stats_buffer() the epilogue fills with the per-slot sum and sum
     of squares of the outputs; `bnb` = (x, mean, invstd, a, b, Bp, conv_stats_buffer()[, up]): the epilogue leaves the
-    BatchNorm-backward sums sum(g*m), sum(g*m*xhat) of the layer this backward-data launch propagates into.  Returns the
-    output tensor."""
+    BatchNorm-backward sums sum(g*m), sum(g*m*xhat) of the layer this backward-data launch propagates into.
+    `live` = (int32 table [B, G], addend): the caller's promise that the operand, after in_scale, is exactly zero at every
+    t >= table[b, g] + addend (ops.live_extent + the bias-free convs in between, never configuration): nef_conv_fwd_live, same bits.
+    Returns the output tensor."""
     L = _lib.load()
+    if live is not None and not LIVE:
+        live = None
+
+    def launch():
+        if live is not None:
+            _lib.check(L.nef_conv_fwd_live(C.byref(a), _p(live[0]), int(live[1]), _stream()), "nef_conv_fwd_live")
+        else:
+            _lib.check(L.nef_conv_fwd(C.byref(a), _stream()), "nef_conv_fwd")
     T_out = xv.T * 2 if (pro is not None and pro[0] & 2) else xv.T
     if out is None:
         y = torch.empty(xv.B, xv.G * Cog, T_out, device=xv.t.device, dtype=torch.float32)
@@ -812,7 +867,7 @@ def conv(xv, wp, Cog, K, out=None, bias=None, in_scale=None, res=None, gate=None
                 raise RuntimeError("split-fp16 conv: a call site's first launch (it measures its operand) cannot be captured; "
                                    "run the step once eagerly first (GraphedTrainStep does)")
             st["nxt"][i] = 0.0
-            _lib.check(L.nef_conv_fwd(C.byref(a), _stream()), "nef_conv_fwd")
+            launch()
             st["cur"][i] = st["nxt"][i]
             if site is not None:
                 _note_tail(st, i, [(xv, in_scale, pro)])
@@ -825,11 +880,16 @@ def conv(xv, wp, Cog, K, out=None, bias=None, in_scale=None, res=None, gate=None
     # BatchNorm input of the layer below (full / half resolution) for the backward sums
     extra = ("up" if (pro is not None and pro[0] & 2) else "") + ("ph" if (pro is not None and pro[0] == 4) else "") + ("pf" if (pro is not None and pro[0] & 8) else "") + tag_extra + ("bnb" + ("up" if len(bnb) > 7 and bnb[7] else "") if bnb is not None else "")
     tag = (role, K, xv.G, xv.Cg, Cog, xv.B, T_out) + ((extra,) if extra else ())
+    frac = 1.0      # executed work: the plain forms skip the dead tiles of a launch that carries a promise (the table's read-back
+    if PROFILE is not None and live is not None and a.wino == 3 and not a.pro_mode and T_out >= 128:      # stays outside the events)
+        frac = _live_frac(live, (K - 1) // 2, T_out)
     ev = _timed(tag)
     if ev is not None:
         EXEC_FRAC[tag] = 0.0 if a.wino == 3 else _exec_frac(K, a.wino)
         EXEC_FP16[tag] = 3.0 if a.wino == 3 else 0.0
-    _lib.check(L.nef_conv_fwd(C.byref(a), _stream()), "nef_conv_fwd")
+        if a.wino == 3 and LIVE:
+            _live_note(tag, frac)
+    launch()
     if ev is not None:
         ev.record()
     return out.t
@@ -952,14 +1012,17 @@ def h2w_ok(K, Cig, Cog, T, pro_mode=0, in_scale=False):
             (K == 3 or not pro_mode) and not (pro_mode and in_scale))
 
 
-def conv_bwd_weight(xv, gyv, K, in_scale=None, pro=None, wino=None, site=None, h2=None, x_scale=0.0, gy_scale=0.0, xedge=None):
+def conv_bwd_weight(xv, gyv, K, in_scale=None, pro=None, wino=None, site=None, h2=None, x_scale=0.0, gy_scale=0.0, xedge=None, live=None):
     """gw [G*Cog, Cig, K] for y = conv(prologue(x) * in_scale, w); `pro` as in conv().  Default path: the split-fp16 kernel
     (csrc/conv_h2w.hip) wherever its shape rules hold (h2w_ok; `h2=False` forbids it, giving `wino` forbids it too); `site`: the
     identity of the call site for its operand-magnitude slots (the engine passes the weight's address; None = measure at every
     call), `x_scale` / `gy_scale`: explicit powers of two instead.  `wino`: force (True / 4) or forbid
     (False) the transposed-Winograd form -- F(3,4) for K == 3, the 4 + 3 split through F(4,4) + F(3,4) for K == 7; default:
     wherever it applies (see WINOGRAD, WINO_BW4, WINO_BW7).  `xedge` [B, G*Cig, 2]: the prologue's output at both row ends, which
-    pro_mode bit 2 needs on the fp32 kernels (conv_bwd_weight_poly passes it)."""
+    pro_mode bit 2 needs on the fp32 kernels (conv_bwd_weight_poly passes it).  `live` = (int32 table [B, G], addend): the caller's
+    promise that every product of a (sample, 64-column tile) item with t0 >= table[b, g] + addend is zero -- the gradient's bound, or
+    the input's bound + (K-1)/2 (split-fp16 kernel only: nef_conv_bwd_weight_live, same gw bits; the fp32 forms ignore it).  The launch's
+    magnitude words are taken over the live items: they are unchanged only where BOTH operands are zero in the dead ones."""
     L = _lib.load()
     B, T, G, Cig, Cog = xv.B, gyv.T, xv.G, xv.Cg, gyv.Cg
     dev = xv.t.device
@@ -991,7 +1054,7 @@ def conv_bwd_weight(xv, gyv, K, in_scale=None, pro=None, wino=None, site=None, h
                 if torch.cuda.is_current_stream_capturing():
                     raise RuntimeError("split-fp16 weight gradient: a call site's first launch cannot be captured")
                 st["nxt"][i:i + 2] = 0.0
-                _bww(L, a)      # (x_amax, gy_amax and clamped still NULL: it measures)
+                _bww(L, a, live)      # (x_amax, gy_amax and clamped still NULL: it measures)
                 st["cur"][i:i + 2] = st["nxt"][i:i + 2]
                 if key is not None:
                     flag = _note_tail(st, i, [(xv, in_scale, pro), (gyv, None, None)])
@@ -1006,11 +1069,16 @@ def conv_bwd_weight(xv, gyv, K, in_scale=None, pro=None, wino=None, site=None, h
                 a.x_amax, a.gy_amax, a.clamped = cur, cur + 4, st["clamped"].data_ptr()
         if not routed:
             tag = ("conv_bwd_weight", K, G, Cig, Cog, B, T) + (("up",) if pm0 & 2 else (("pw",) if pm0 & 4 else ()))
+            frac = 1.0      # executed work: the producer / consumer kernel without a prologue leaves the dead 64-column items out
+            if PROFILE is not None and live is not None and LIVE and LIVE_WGRAD and not pm0 and Cog % 128 == 0:
+                frac = _live_frac(live, 0, T, 64)
             ev = _timed(tag)
             if ev is not None:
                 EXEC_FRAC[tag] = 0.0
                 EXEC_FP16[tag] = 3.0
-            _bww(L, a)
+                if LIVE:
+                    _live_note(tag, frac)
+            _bww(L, a, live)
             _done(ev)
             return gw
     # fp32 kernels.  A routed split-fp16 site (H2_TAIL_MODE) takes the DIRECT form: the transposed-Winograd transforms add and
@@ -1057,8 +1125,13 @@ def _bww_form(L, a, form, device, unsupported):
     a.ws = _p(workspace(a.ws_bytes, device))
 
 
-def _bww(L, a):
-    _lib.check(L.nef_conv_bwd_weight(C.byref(a), _stream()), "nef_conv_bwd_weight")
+def _bww(L, a, live=None):
+    """`live` = (int32 table [B, G], addend): every product of a (sample, 64-column tile) item with t0 >= table[b, g] + addend is zero
+    (form 3 only: nef_conv_bwd_weight_live, same bits); ops.LIVE or ops.LIVE_WGRAD off: the plain entry."""
+    if live is not None and LIVE and LIVE_WGRAD and a.form == 3:
+        _lib.check(L.nef_conv_bwd_weight_live(C.byref(a), _p(live[0]), int(live[1]), _stream()), "nef_conv_bwd_weight_live")
+    else:
+        _lib.check(L.nef_conv_bwd_weight(C.byref(a), _stream()), "nef_conv_bwd_weight")
 
 
 def _tail_mode():

@@ -47,6 +47,14 @@ int nef_debug_spin_us(float us, int wgs, nef_stream_t stream);
  * bwd_weight recomputes the conv, routes gy through the pool arg-max and the ReLU.
  *   ws: nef_stem_bwd_ws_bytes(V) bytes of scratch. */
 int nef_stem_fwd(const float* x, const float* w, float* y, int B, int V, int L, nef_stream_t stream);
+/* Live extent of the stem's output, measured on the tensor the stem reads: live[b*V + v] (int32) = the first pooled position from
+ * which row (b, v) of nef_stem_fwd's output is exactly zero, in all 128 channels.  With e = 1 + index of the row's last element
+ * x != 0.f (-0.f counts as zero, NaN as non-zero; an all-zero row: e = 0):
+ *   cj = e ? min(L/2, (e+6)/2 + 1) : 0,   live = cj ? min(L/4, cj/2 + 1) : 0
+ * (conv output j reads x[2j-7 .. 2j+7], pooled output t covers j = 2t-1 .. 2t+1; no bias, so ReLU(0) = 0 behind them).
+ * A bias-free conv of kernel size K widens the extent by (K-1)/2 and no more: nef_conv_fwd_live takes the table + that addend.
+ * One small launch, no host read; L % 4 == 0. */
+int nef_live_extent(const float* x, int32_t* live, int B, int V, int L, nef_stream_t stream);
 size_t nef_stem_bwd_ws_bytes(int V);
 int nef_stem_bwd_weight(const float* x, const float* w, const float* gy, float* gw, void* ws, size_t ws_bytes,
                         int B, int V, int L, nef_stream_t stream);
@@ -194,6 +202,16 @@ typedef struct nef_conv_args {
 /* y = epilogue(conv(x * in_scale, wp) + bias + res).  Also the bwd-data pass (pack with transpose_flip=1,
  * swap Cin_g/Cout_g). */
 int nef_conv_fwd(const nef_conv_args* a, nef_stream_t stream);
+/* The same launch with one promise added: the operand x, after in_scale, is EXACTLY zero at every t >= live[b*G + g] + live_add
+ * (live: device int32 [B][G], e.g. nef_live_extent's table; live_add: what the convs between the stem and this operand widened it
+ * by).  The plain split-fp16 forms (wino 3, pro_mode 0, T >= 128; K = 1, 3, 7) then skip the main loop of every 256-column tile
+ * whose staged window t0 - (K-1)/2 .. lies behind that bound: no operand loads, no matrix instructions, no rescue pass.  The
+ * epilogue runs unchanged on zero accumulators -- bias, residual, ReLU, dropout, gate, statistics, x_amax_next and every output
+ * store -- so the result is what nef_conv_fwd gives, bit for bit, with finite weights (products of zeros accumulate to +0).
+ * A non-finite weight would have turned those zeros into NaN; such a step is already broken and the live tiles still report it.
+ * Every other form (other wino, prologues, short rows) ignores the table and runs as nef_conv_fwd.  A promise that does not hold
+ * gives wrong results silently: derive it from a measured table and a chain of bias-free convs only. */
+int nef_conv_fwd_live(const nef_conv_args* a, const int32_t* live, int32_t live_add, nef_stream_t stream);
 /* sizeof(nef_conv_args) as the library was built: a binding checks its mirror of the struct against it. */
 size_t nef_conv_args_bytes(void);
 
@@ -255,6 +273,19 @@ typedef struct nef_bww_args {
 } nef_bww_args;
 
 int nef_conv_bwd_weight(const nef_bww_args* a, nef_stream_t stream);
+/* Form 3 with one promise added: every product of a (sample b, 64-column tile t0) item with t0 >= live[b*G + g] + live_add is zero
+ * (live: device int32 [B][G], nef_live_extent's table).  The caller picks live_add for whichever operand is zero-tailed: the
+ * gradient's bound (gy exactly zero at t >= bound), or the input's bound + (K-1)/2 (the item's window starts at t0 - (K-1)/2).
+ * The shares of the (sample, tile) sequence keep their boundaries in the FULL item space; inside each share the dead items are left
+ * out, in order -- a dead item only adds products of zeros (+0), so every partial sum and gw keep nef_conv_bwd_weight's bits (finite
+ * operands; a NaN or Inf opposite a promised zero would have made a NaN: such a step is already broken).  x_amax_next / gy_amax_next
+ * are taken over the live items: the words (and with them the next launch's scales and the
+ * share's rescue decision) are nef_conv_bwd_weight's only when BOTH operands are zero in the dead items; with a lone promised
+ * operand the other one's word covers its live part only.  A caller that needs the words unchanged -- the train step does: they
+ * set the next step's scales -- hands the promise over only where both operands carry the tail (engine.block_bwd).  A small launch in
+ * front builds the item tables in the workspace, behind the partial sums: nef_conv_bwd_weight_ws_bytes counts them in.  The
+ * producer / consumer kernel without a prologue (Cout_g % 128 == 0, pro_mode 0) skips; the other kernels of the form run as before. */
+int nef_conv_bwd_weight_live(const nef_bww_args* a, const int32_t* live, int32_t live_add, nef_stream_t stream);
 /* Reads form, B, T, G, Cin_g, Cout_g, K only; 0: unsupported shape or form.  Forms 0 and 4: the split bound of the prologue-free
  * direct plan (no plan with a prologue or a Winograd form has more splits); form 3: sized for whichever tile form the launch's
  * prologue mode takes (the largest over the modes). */
