@@ -181,11 +181,13 @@ SIGNATURES = {
     "nef_stem_fwd": (i32, [p, p, p, i32, i32, i32, p]),
     "nef_stem_bwd_ws_bytes": (sz, [i32]),
     "nef_stem_bwd_weight": (i32, [p, p, p, p, p, sz, i32, i32, i32, p]),
+    "nef_stem_bwd_weight_live": (i32, [p, p, p, p, p, sz, i32, i32, i32, p, p]),
     "nef_pack_weights": (i32, [C.POINTER(PackDesc), i32, p]),
     "nef_pack_bytes": (sz, [C.POINTER(PackDesc)]),
     "nef_live_extent": (i32, [p, p, i32, i32, i32, p]),
     "nef_conv_fwd": (i32, [C.POINTER(ConvArgs), p]),
     "nef_conv_fwd_live": (i32, [C.POINTER(ConvArgs), p, i32, p]),
+    "nef_conv_fwd_live_res": (i32, [C.POINTER(ConvArgs), p, i32, i32, p]),
     "nef_conv_args_bytes": (sz, []),
     "nef_conv_bwd_weight_ws_bytes": (sz, [C.POINTER(BwwArgs)]),
     "nef_conv_bwd_weight": (i32, [C.POINTER(BwwArgs), p]),

@@ -180,12 +180,14 @@ constexpr int H2_OCC1 = 3;
 // rescue pass; the epilogue then runs unchanged on +0 accumulators and writes every output.  Bit for bit what the full
 // loop gives with finite weights: products of zeros accumulate to +0.  (A non-finite weight would have made NaNs of those zeros;
 // such a step is already broken, and the launch's live tiles still report it.)
+// Where the launch also says that this epilogue can only write zeros (zf_, see the ZERO-FILL EXIT in front of the first tile_pass), a dead
+// workgroup stores them there and never gets here.
 // PACK (short rows, 8 <= T <= 64, T % 4 == 0): a tile is `tps` SAMPLES laid end to end at a pitch of T + 4 positions -- the four
 // positions between two samples are staged as zeros (the zero padding of both neighbours) and their outputs are dropped; a lane's
 // four adjacent outputs lie inside one sample or inside one gap.  No prologue, channel scale or statistics in this mode.
 template <int K, int PRO, int TM, bool PACK = false>
 __global__ __launch_bounds__(256, (TM == 1 && (PRO & 2) == 0) ? H2_OCC1 : 2) void conv_h2_kernel(nef_conv_args a_, int tps_, int n_tiles_, int m_tiles_,
-                                                                                                const int32_t* live_, int live_add_) {
+                                                                                                const int32_t* live_, int live_add_, int zf_, int res_add_) {
     constexpr int MT = 64 * TM;                    // output channels per workgroup: 2 (co) x 2 (t) waves of TM x 4 tiles
     constexpr bool UP = (PRO & 2) != 0, AFF = (PRO & 1) != 0;
     // PH (pro_mode 4, polyphase backward-data through a x2 upsampling): the input is a FULL-resolution tensor [Cin_g / 2][2 T] read as
@@ -883,6 +885,43 @@ __global__ __launch_bounds__(256, (TM == 1 && (PRO & 2) == 0) ? H2_OCC1 : 2) voi
     };      // tile_pass
     kargs_t* ap_ = (kargs_t*)__builtin_amdgcn_kernarg_segment_ptr();      // (a_ is the segment's first member)
     (void)a_;
+    // ZERO-FILL EXIT (zf_ != 0: launch_h2 found no bias, no statistics and no BatchNorm-backward sums; zf_ == 2: a residual whose
+    // caller promises zeros at t >= live + res_add_).  A dead tile of such a launch is known to come out of the epilogue as zeros:
+    // +0 accumulators, a zero residual, and ReLU / dropout / gate keep zeros.  The workgroup stores them and leaves -- no LDS, no
+    // barrier, no table, no other operand.  (A negative gate scale would have written -0.0; this path writes +0.0.)  Workgroup-uniform,
+    // in front of the first tile_pass and not inside it: see the note on branches above.
+    if constexpr (PRO == 0 && !PACK) {
+        if (zf_) {
+            const int tile = (int)blockIdx.x % n_tiles_, gm = (int)blockIdx.x / n_tiles_;
+            const int mt = gm % m_tiles_, g = gm / m_tiles_;
+            const int full = (n_tiles_ / (8 * tps_)) * (8 * tps_);      // (tile_pass's mapping)
+            int b0, t0;
+            if (tile < full) {
+                const int grp = tile / (8 * tps_), r = tile % (8 * tps_);
+                b0 = grp * 8 + (r & 7);
+                t0 = (r >> 3) * NTO;
+            } else {
+                b0 = tile / tps_;
+                t0 = (tile - b0 * tps_) * NTO;
+            }
+            const int e = live_[b0 * ap_->G + g];
+            const bool dead = t0 - PAD >= e + live_add_;      // (tile_pass's rule)
+            if (dead && (zf_ == 1 || t0 >= e + res_add_)) {
+                const int T = ap_->T;
+                const int t = t0 + 4 * ((int)threadIdx.x & 63);      // a wave stores one row's 256 columns per instruction
+                float* const yp = ap_->y + (int64_t)b0 * ap_->y_bs + (int64_t)g * ap_->y_gs + (int64_t)(mt * MT) * T + t;
+                // rows are 8-byte aligned (T even), every other one 16-byte aligned when T % 4 == 2: 16-byte stores at 4-byte alignment
+                if (t + 3 < T) {
+#pragma unroll 8
+                    for (int r = (int)threadIdx.x >> 6; r < MT; r += 4) *reinterpret_cast<f32x4_a4*>(yp + (int64_t)r * T) = f32x4_a4{0.f, 0.f, 0.f, 0.f};
+                } else if (t < T) {      // the half-live quad at the end of a row with T % 4 == 2
+#pragma unroll 8
+                    for (int r = (int)threadIdx.x >> 6; r < MT; r += 4) *reinterpret_cast<f32x2*>(yp + (int64_t)r * T) = f32x2{0.f, 0.f};
+                }
+                return;
+            }
+        }
+    }
     const float over_ = tile_pass(ap_, (int)blockIdx.x, (int)threadIdx.x, tps_, n_tiles_, m_tiles_, 0.f, false, live_, live_add_);
     if (over_ > 0.f) {
         int e_;
@@ -895,7 +934,7 @@ __global__ __launch_bounds__(256, (TM == 1 && (PRO & 2) == 0) ? H2_OCC1 : 2) voi
 }
 
 template <int K, int PRO, int TM, bool PACK = false>
-int launch_h2(const nef_conv_args& a, hipStream_t st, const int32_t* live = nullptr, int live_add = 0) {
+int launch_h2(const nef_conv_args& a, hipStream_t st, const int32_t* live = nullptr, int live_add = 0, const int* res_add = nullptr) {
     constexpr int MT = 64 * TM;
     constexpr int XROW = NTO + K - 1;
     constexpr int P4 = (XROW + 3) / 4 + 1;
@@ -909,7 +948,13 @@ int launch_h2(const nef_conv_args& a, hipStream_t st, const int32_t* live = null
     const int m_tiles = a.Cout_g / MT;
     const int64_t blocks = (int64_t)a.G * m_tiles * n_tiles;
     if (blocks <= 0 || blocks > 0x7fffffff) return NEF_E_SHAPE;
-    hipLaunchKernelGGL((conv_h2_kernel<K, PRO, TM, PACK>), dim3((unsigned)blocks), dim3(256), lds, st, a, tps, n_tiles, m_tiles, live, live_add);
+    // the zero-fill exit of dead tiles (see the kernel): only where the epilogue maps a zero accumulator to zero at every output of such a
+    // tile and leaves nothing else behind -- no bias, no statistics of either kind (the stats_mode 1 launch, w_conv's channel-scale
+    // gradient, stays on the full epilogue: its slots are not worth a second writer), a residual only with its caller's promise
+    int zf = 0;
+    if (PRO == 0 && !PACK && live && !a.bias && !a.stats && !a.bnb_slots) zf = !a.res ? 1 : (res_add ? 2 : 0);
+    hipLaunchKernelGGL((conv_h2_kernel<K, PRO, TM, PACK>), dim3((unsigned)blocks), dim3(256), lds, st, a, tps, n_tiles, m_tiles, live, live_add, zf,
+                       res_add ? *res_add : 0);
     return nef_launch_status();
 }
 
@@ -938,8 +983,9 @@ __attribute__((visibility("hidden"))) bool nef_h2_ok(const nef_conv_args* a) {
            (!(a->pro_mode & 1) || a->Cin_g <= PRO_MAX_CIN);
 }
 
-// `live` / `live_add`: nef_conv_fwd_live's promise (NULL: none); only the plain forms <K, 0, TM> take it, every other form ignores it
-__attribute__((visibility("hidden"))) int nef_h2_launch(const nef_conv_args* a, hipStream_t st, const int32_t* live, int live_add) {
+// `live` / `live_add`: nef_conv_fwd_live's promise (NULL: none); `res_add`: nef_conv_fwd_live_res's promise for the residual (NULL: none);
+// only the plain forms <K, 0, TM> take them, every other form ignores them
+__attribute__((visibility("hidden"))) int nef_h2_launch(const nef_conv_args* a, hipStream_t st, const int32_t* live, int live_add, const int* res_add) {
     if (!nef_h2_ok(a)) return NEF_E_SHAPE;
     if ((a->pro_mode & 1) && !(a->pro_a && a->pro_b && a->pro_Bp > 0)) return NEF_E_NULL;
     const bool wide = a->Cout_g % 128 == 0;
@@ -948,10 +994,10 @@ __attribute__((visibility("hidden"))) int nef_h2_launch(const nef_conv_args* a, 
     // always take the 64-channel tile (the 128-channel instantiations <3, 2, 2> / <3, 3, 2> are no longer built)
     if (a->T < NTO / 2)      // short rows: the 64-channel tile (the 128-channel form spills 185 registers with the per-lane sample offsets)
         return a->K == 1 ? launch_h2<1, 0, 1, true>(*a, st) : launch_h2<3, 0, 1, true>(*a, st);
-    if (a->K == 7) return wide ? launch_h2<7, 0, 2>(*a, st, live, live_add) : launch_h2<7, 0, 1>(*a, st, live, live_add);
-    if (a->K == 1) return wide ? launch_h2<1, 0, 2>(*a, st, live, live_add) : launch_h2<1, 0, 1>(*a, st, live, live_add);
+    if (a->K == 7) return wide ? launch_h2<7, 0, 2>(*a, st, live, live_add, res_add) : launch_h2<7, 0, 1>(*a, st, live, live_add, res_add);
+    if (a->K == 1) return wide ? launch_h2<1, 0, 2>(*a, st, live, live_add, res_add) : launch_h2<1, 0, 1>(*a, st, live, live_add, res_add);
     switch (a->pro_mode) {
-        case 0: return wide ? launch_h2<3, 0, 2>(*a, st, live, live_add) : launch_h2<3, 0, 1>(*a, st, live, live_add);
+        case 0: return wide ? launch_h2<3, 0, 2>(*a, st, live, live_add, res_add) : launch_h2<3, 0, 1>(*a, st, live, live_add, res_add);
         case 1: return wide ? launch_h2<3, 1, 2>(*a, st) : launch_h2<3, 1, 1>(*a, st);
         case 2: return launch_h2<3, 2, 1>(*a, st);
         case 4: return wide ? launch_h2<3, 4, 2>(*a, st) : launch_h2<3, 4, 1>(*a, st);

@@ -2192,7 +2192,7 @@ constexpr int CHAN_SUM_SPLIT = 16;
 
 // conv_h2.hip: direct convolutions on exact fp16 splits of the fp32 operands (conv args wino = 3)
 __attribute__((visibility("hidden"))) bool nef_h2_ok(const nef_conv_args* a);
-__attribute__((visibility("hidden"))) int nef_h2_launch(const nef_conv_args* a, hipStream_t st, const int32_t* live, int live_add);
+__attribute__((visibility("hidden"))) int nef_h2_launch(const nef_conv_args* a, hipStream_t st, const int32_t* live, int live_add, const int* res_add);
 __attribute__((visibility("hidden"))) int nef_h2_pack(const nef_pack_desc* descs, int n, hipStream_t st);
 __attribute__((visibility("hidden"))) int nef_h2_pack_status(const nef_pack_desc* d);
 
@@ -2269,7 +2269,7 @@ int nef_pack_weights(const nef_pack_desc* descs, int n, nef_stream_t stream) {
 size_t nef_conv_args_bytes(void) { return sizeof(nef_conv_args); }
 
 
-static int conv_fwd_entry(const nef_conv_args* a, const int32_t* live, int32_t live_add, nef_stream_t stream) {
+static int conv_fwd_entry(const nef_conv_args* a, const int32_t* live, int32_t live_add, const int32_t* res_add, nef_stream_t stream) {
     NEF_REQUIRE(a && a->x && a->wp && a->y, NEF_E_NULL);
     NEF_REQUIRE(a->B > 0 && a->T > 0 && a->G > 0, NEF_E_SHAPE);
     const int K = a->K;
@@ -2284,7 +2284,7 @@ static int conv_fwd_entry(const nef_conv_args* a, const int32_t* live, int32_t l
     NEF_REQUIRE((!a->res_scale && !a->gate_rowscale && a->stats_mode == 0) || a->wino == 3, NEF_E_UNSUPPORTED);
     if (a->wino == 3) {      // split-fp16 operand (nef_pack_desc.wino 3): direct conv on exact fp16 splits (conv_h2.hip)
         NEF_REQUIRE(nef_h2_ok(a), NEF_E_SHAPE);
-        return nef_h2_launch(a, st, live, live_add);
+        return nef_h2_launch(a, st, live, live_add, res_add);
     }
     bool big = (a->Cout_g % 128 == 0);
     if (big) {
@@ -2323,16 +2323,23 @@ static int conv_fwd_entry(const nef_conv_args* a, const int32_t* live, int32_t l
 
 int nef_conv_fwd(const nef_conv_args* a, nef_stream_t stream) {
     NEF_ENTER();
-    return conv_fwd_entry(a, nullptr, 0, stream);
+    return conv_fwd_entry(a, nullptr, 0, nullptr, stream);
 }
 
 // nef_conv_fwd with the live-extent promise (include/nefnet_hip.h).  The plain split-fp16 forms (wino 3, pro_mode 0, T >= 128) skip the
-// main loop of column tiles that lie in the operand's zero tail -- same bits, the outputs are all written; every other form runs as
-// nef_conv_fwd does and never looks at the table.
+// main loop of column tiles that lie in the operand's zero tail, and the whole tile but its stores where the epilogue is known to
+// leave zeros -- same bits, the outputs are all written; every other form runs as nef_conv_fwd does and never looks at the table.
 int nef_conv_fwd_live(const nef_conv_args* a, const int32_t* live, int32_t live_add, nef_stream_t stream) {
     NEF_ENTER();
     NEF_REQUIRE(live, NEF_E_NULL);
-    return conv_fwd_entry(a, live, live_add, stream);
+    return conv_fwd_entry(a, live, live_add, nullptr, stream);
+}
+
+// ... and with the residual's own promise: a->res (after res_scale) is exactly zero at every t >= live[b*G + g] + res_add
+int nef_conv_fwd_live_res(const nef_conv_args* a, const int32_t* live, int32_t live_add, int32_t res_add, nef_stream_t stream) {
+    NEF_ENTER();
+    NEF_REQUIRE(live && a && a->res, NEF_E_NULL);
+    return conv_fwd_entry(a, live, live_add, &res_add, stream);
 }
 
 int nef_conv_stats_slots(int T, int Cout_g) {

@@ -199,6 +199,9 @@ __global__ __launch_bounds__(256) void stem_bwd_weight_kernel(const float* __res
 // A workgroup owns one (sample, lead) row: the 5000 input samples sit in LDS (zero-filled halo), every A fragment is a
 // conflict-free ds_read_b32 shared by the wave's two 16-channel tiles; 24 matrix instructions per (16 outputs x 16
 // channels).  One partial [128][15] per row slot, reduced by stem_bwd_weight_reduce.
+// `live` (nef_live_extent's [B][V] table, NULL: none): behind live[b][v] every pooled output of the row is exactly zero in all
+// channels, so every `pre` there is 0 and `ge` is 0 whatever gy holds: those tiles' GEMM 2 adds x * 0 = 0 to a sum that started
+// at +0.  The tile loop stops at the extent rounded up to a whole tile, and only the part of the row it reads is staged.
 constexpr int MB_SPLIT = 256;              // partial slots: rows b = slot, slot + 256, ...
 constexpr int MB_HALO = 16;                // LDS index of x[0]
 constexpr int MB_TAIL = 96;                // the last 16-output tile reads up to x[L + 66]
@@ -206,13 +209,13 @@ typedef float f32x4s __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(256) void stem_bwd_weight_mfma_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                                    const float* __restrict__ gy, float* __restrict__ part,
-                                                                   int B, int V, int L, int T) {
+                                                                   int B, int V, int L, int T, const int32_t* __restrict__ live) {
     extern __shared__ float xs[];          // [MB_HALO + L + MB_TAIL]: xs[MB_HALO + p] = x[p], zeros outside [0, L)
     const int v = blockIdx.x % V, slot = blockIdx.x / V;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int n16 = lane & 15, kk = lane >> 4;
     const int Lc = L / 2;
-    const int xlen = MB_HALO + L + MB_TAIL;
+    const int xlen_full = MB_HALO + L + MB_TAIL;
     // B operand of GEMM 1: w^T[tap = 4s + kk][co], two 16-channel tiles per wave (channels 32 * wave + 16 * ct + n16)
     float wb[2][4];
 #pragma unroll
@@ -227,6 +230,13 @@ __global__ __launch_bounds__(256) void stem_bwd_weight_mfma_kernel(const float* 
     for (int ct = 0; ct < 2; ++ct) acc[ct] = f32x4s{0.f, 0.f, 0.f, 0.f};
     for (int b = slot; b < B; b += MB_SPLIT) {
         __syncthreads();                   // the previous row's readers are done
+        // the row's tiles: tp0 = 0, 16, .. < Tb.  The last one reads up to xs[MB_HALO + 4 (tp0 + 12) - 9 + 15 + 16] = [.. + 4 tp0 + 70]
+        int Tb = T, xlen = xlen_full;
+        if (live) {
+            const int e = live[b * V + v];
+            const int e16 = (e + 15) & ~15;
+            if (e16 < T) Tb = e16 > 0 ? e16 : 0, xlen = MB_HALO + 4 * Tb + 8;      // (4 (Tb - 16) + 70 < 4 Tb + 8 <= L)
+        }
         const float* xrow = x + ((int64_t)b * V + v) * L;
         for (int i = threadIdx.x; i < xlen; i += 256) {
             const int p = i - MB_HALO;
@@ -248,9 +258,9 @@ __global__ __launch_bounds__(256) void stem_bwd_weight_mfma_kernel(const float* 
     }
         f32x4s gnext[2];
         NEF_STEM_GLOAD(0, gnext)
-        for (int tp0 = 0; tp0 < T; tp0 += 16) {
+        for (int tp0 = 0; tp0 < Tb; tp0 += 16) {
             f32x4s gcur[2] = {gnext[0], gnext[1]};
-            if (tp0 + 16 < T) NEF_STEM_GLOAD(tp0 + 16, gnext)
+            if (tp0 + 16 < Tb) NEF_STEM_GLOAD(tp0 + 16, gnext)
             // A fragments: GEMM 1 lane (m = tp = n16, k = kk) reads x[4(tp0 + n16) - 9 + o + kk], o = 2i + 4s in {0, 2, .., 16};
             // GEMM 2 lane (m = tap = n16, k = kk) reads x[4(tp0 + 4kk + r) - 9 + o' + n16], o' = 2i in {0, 2, 4}
             const float* p1 = xs + MB_HALO + 4 * (tp0 + n16) - 9 + kk;
@@ -400,9 +410,8 @@ int nef_stem_fwd(const float* x, const float* w, float* y, int B, int V, int L, 
 
 size_t nef_stem_bwd_ws_bytes(int V) { return (size_t)(MB_SPLIT > BW_SPLIT ? MB_SPLIT : BW_SPLIT) * V * CPL * KW * sizeof(float); }
 
-int nef_stem_bwd_weight(const float* x, const float* w, const float* gy, float* gw, void* ws, size_t ws_bytes, int B,
-                        int V, int L, nef_stream_t stream) {
-    NEF_ENTER();
+static int stem_bwd_weight_entry(const float* x, const float* w, const float* gy, float* gw, void* ws, size_t ws_bytes, int B,
+                                 int V, int L, const int32_t* live, nef_stream_t stream) {
     NEF_REQUIRE(x && w && gy && gw && ws, NEF_E_NULL);
     NEF_REQUIRE(B > 0 && V > 0 && L >= 4 && L % 4 == 0, NEF_E_SHAPE);
     NEF_REQUIRE(ws_bytes >= nef_stem_bwd_ws_bytes(V), NEF_E_WORKSPACE);
@@ -413,7 +422,7 @@ int nef_stem_bwd_weight(const float* x, const float* w, const float* gy, float* 
     if (T % 2 == 0 && lds <= 64 * 1024) {       // a whole input row in LDS; gy rows 8-byte aligned
         const int slots = B < MB_SPLIT ? B : MB_SPLIT;
         hipLaunchKernelGGL(stem_bwd_weight_mfma_kernel, dim3((unsigned)(slots * V)), dim3(256), lds, st, x, w, gy, (float*)ws, B,
-                           V, L, T);
+                           V, L, T, live);
         hipLaunchKernelGGL(stem_bwd_weight_reduce, dim3((n + 63) / 64), dim3(256), 0, st, (const float*)ws, gw, n, slots);
         return nef_launch_status();
     }
@@ -422,6 +431,21 @@ int nef_stem_bwd_weight(const float* x, const float* w, const float* gy, float* 
                        gy, (float*)ws, B, V, L, T, tiles);
     hipLaunchKernelGGL(stem_bwd_weight_reduce, dim3((n + 63) / 64), dim3(256), 0, st, (const float*)ws, gw, n, BW_SPLIT);
     return nef_launch_status();
+}
+
+int nef_stem_bwd_weight(const float* x, const float* w, const float* gy, float* gw, void* ws, size_t ws_bytes, int B,
+                        int V, int L, nef_stream_t stream) {
+    NEF_ENTER();
+    return stem_bwd_weight_entry(x, w, gy, gw, ws, ws_bytes, B, V, L, nullptr, stream);
+}
+
+// ... with nef_live_extent's table of the same x: the matrix-core kernel stops every row at its extent (same bits); the VALU kernel
+// (odd T, rows beyond 64 KiB of LDS) does not look at it
+int nef_stem_bwd_weight_live(const float* x, const float* w, const float* gy, float* gw, void* ws, size_t ws_bytes, int B,
+                             int V, int L, const int32_t* live, nef_stream_t stream) {
+    NEF_ENTER();
+    NEF_REQUIRE(live, NEF_E_NULL);
+    return stem_bwd_weight_entry(x, w, gy, gw, ws, ws_bytes, B, V, L, live, stream);
 }
 
 }  // extern "C"

@@ -77,7 +77,10 @@ def block_fwd(xv, P, prefix, K, Cog, drop, in_scale=None, live=None):
     by the first conv while it stages and by the last one to its residual, so the scaled tensor is never written (split-fp16
     launches, identity residual only: the caller checks block_scale_ok).
     `live` = (table, addend): xv is exactly zero at t >= table[b, g] + addend (ops.live_extent through bias-free convs).
-    The block's convs have no bias and ReLU / dropout keep zeros, so conv1's output h carries the promise widened by (K-1)/2."""
+    The block's convs have no bias and ReLU / dropout keep zeros, so conv1's output h carries the promise widened by (K-1)/2.
+    conv2 adds the residual: the identity one is xv itself (times a finite in_scale), zero behind xv's own bound -- which lies in front
+    of every tile that is dead for h (t0 - PAD >= bound + PAD), so conv2 hands xv's addend over as the residual's promise and its dead
+    tiles only store zeros.  The residual conv has a bias: its output carries no promise, and conv2 then runs its epilogue in full."""
     G = xv.G
     h = ops.conv(xv, ops.pack_weight(P[prefix + ".conv1.weight"], G, T=xv.T), Cog, K, relu=True, in_scale=in_scale, live=live,
                  **drop.args(prefix))
@@ -90,7 +93,7 @@ def block_fwd(xv, P, prefix, K, Cog, drop, in_scale=None, live=None):
     else:
         resv = xv
     y = ops.conv(GV.dense(h, G), ops.pack_weight(P[prefix + ".conv2.weight"], G, T=xv.T), Cog, K, res=resv, relu=True,
-                 res_scale=in_scale, live=_live_add(live, (K - 1) // 2))
+                 res_scale=in_scale, live=_live_add(live, (K - 1) // 2), res_live=None if (res_conv or live is None) else live[1])
     return y, (xv, h, y, prefix, K, Cog, res_conv, drop.scale, in_scale, live)
 
 
@@ -197,6 +200,15 @@ def block_bwd(saved, gy, P, grads, out=None, side=None, pre_gated=False, gate_in
     # A weight gradient takes the promise only where BOTH its operands carry the tail: its magnitude words (the next step's scales)
     # are taken over the live items.  conv1: gc1's bound = the input's + PAD.  conv2: g2's bound = h's + PAD, behind the identity
     # residual only -- z1_conv's g2 is gated by an output without a zero tail, so its conv2 and residual-conv gradients run in full.
+    # The backward-data convs and what their dead tiles may skip (zero-fill: no bias anywhere here, a gate needs no condition):
+    #   gc1 = conv(g2) gated by h: operand bound live_y, nothing added -- no promise needed.
+    #   gx = conv(gc1) + res, gated by the block input or not at all: operand bound live_h.  Behind the identity residual res is g2
+    #     itself, zero wherever y was: bound live_y = live_h + PAD.  A tile is dead for gc1 when t0 - PAD >= live_h, that is
+    #     t0 >= live_h + PAD = live_y: every dead tile lies behind the residual's bound as well, so live_y's addend is handed over.
+    #     Behind a residual conv res is gres = conv1x1(g2) and g2 has no zero tail (live_y is None): no promise, full epilogue.
+    #   The stats_mode 1 launch (w_conv, scale_bwd) carries the same promise; the kernel keeps its dead tiles on the full epilogue
+    #     for the slot sums.
+    res_live = None if (res_conv or live_y is None) else live_y[1]
     side = side or ops._Inline()
     G, Cig = xv.G, xv.Cg
     g2 = gy if pre_gated else ops.gate(gy, y)                # through the final ReLU
@@ -222,10 +234,10 @@ def block_bwd(saved, gy, P, grads, out=None, side=None, pre_gated=False, gate_in
         slots = ops.conv_stats_buffer(wp1f, xv.B, G, Cig, xv.T, xv.t.device)
         if slots is not None:
             gx = ops.conv(gc1v, wp1f, Cig, K, res=resv, gate=xv, gate_scale=1.0, gate_rowscale=in_scale, stats=slots, stats_mode=1,
-                          role="conv_bwd_data", live=live_h)
+                          role="conv_bwd_data", live=live_h, res_live=res_live)
             return gx, ops.slots_to_rows(slots, xv.B)
     return ops.conv(gc1v, wp1f, Cig, K, res=resv,
-                    out=out, gate=xv if gate_input else None, gate_scale=1.0, role="conv_bwd_data", live=live_h)
+                    out=out, gate=xv if gate_input else None, gate_scale=1.0, role="conv_bwd_data", live=live_h, res_live=res_live)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -479,6 +491,7 @@ def _latents(P, x, in_theta, rois, drop, save, pack_side=None):
     # the beat's all-zero tail, measured on the tensor the stem reads: the stem's output is exactly zero behind live[b, v], and every
     # bias-free conv below widens that by (K-1)/2 -- the promise is carried down the chain, never taken from rois or configuration
     live = (ops.live_extent(x), 0) if ops.LIVE else None
+    sv["stem_live"] = live[0] if live is not None else None      # the stem's weight gradient stops every row at it
     a = ops.stem_fwd(x, P["W_encoder.conv1.weight"])
     if pack_side is not None:
         pack_side.join()
@@ -922,7 +935,7 @@ def _latents_bwd(P, sv, gz1, gz2r, grads, side, z1_pre_gated=False, early=False,
             parallel.early_reduce(P, grads, getattr(side, "stream", None))
     for i in (2, 1, 0):
         g = block_bwd(sv["blk_enc"][i], g, P, grads, side=side, pre_gated=True, gate_input=(i > 0))
-    grads["W_encoder.conv1.weight"] = ops.stem_bwd_weight(sv["x"], P["W_encoder.conv1.weight"], g)
+    grads["W_encoder.conv1.weight"] = ops.stem_bwd_weight(sv["x"], P["W_encoder.conv1.weight"], g, live=sv.get("stem_live"))
 
 
 def backward(P, sv, g_outs):

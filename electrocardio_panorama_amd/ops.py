@@ -232,7 +232,9 @@ def _live_frac(live, pad, T, tile=256):
     return float(((bound + tile - 1) // tile).clamp(0, tps).double().mean()) / tps
 
 
-def stem_bwd_weight(x, w, gy):
+def stem_bwd_weight(x, w, gy, live=None):
+    """`live`: ops.live_extent(x) -- the matrix-core kernel then stops every row at its extent (same bits; part of ops.LIVE, and like the
+    other weight gradients of ops.LIVE_WGRAD)."""
     L = _lib.load()
     _chk(x), _chk(w), _chk(gy)
     B, V, Ln = x.shape
@@ -240,7 +242,11 @@ def stem_bwd_weight(x, w, gy):
     n = L.nef_stem_bwd_ws_bytes(V)
     ws = workspace(n, x.device)
     ev = _hbm("stem_bwd_weight", x, gy)
-    _lib.check(L.nef_stem_bwd_weight(_p(x), _p(w), _p(gy), _p(gw), _p(ws), n, B, V, Ln, _stream()), "nef_stem_bwd_weight")
+    if live is not None and LIVE and LIVE_WGRAD:
+        assert live.shape == (B, V) and live.dtype == torch.int32
+        _lib.check(L.nef_stem_bwd_weight_live(_p(x), _p(w), _p(gy), _p(gw), _p(ws), n, B, V, Ln, _p(live), _stream()), "nef_stem_bwd_weight_live")
+    else:
+        _lib.check(L.nef_stem_bwd_weight(_p(x), _p(w), _p(gy), _p(gw), _p(ws), n, B, V, Ln, _stream()), "nef_stem_bwd_weight")
     _done(ev)
     return gw
 
@@ -798,7 +804,7 @@ def _operand(a, xv, in_scale, pro):
 
 def conv(xv, wp, Cog, K, out=None, bias=None, in_scale=None, res=None, gate=None, gate_scale=1.0, relu=False,
          mask=None, drop_p=0.0, drop_scale=1.0, seed=0, role="conv_fwd", pro=None, seed_dev=None, stats=None, bnb=None,
-         x_scale=0.0, tag_extra="", res_scale=None, gate_rowscale=None, stats_mode=0, live=None):
+         x_scale=0.0, tag_extra="", res_scale=None, gate_rowscale=None, stats_mode=0, live=None, res_live=None):
     """out = epilogue(conv1d(prologue(x) * in_scale, w) + bias + res * res_scale).  `xv`, `res`, `gate`, `out` are GV views;
     `in_scale` / `res_scale` are (tensor, batch_stride, group_stride).  `pro` = (mode, a, b, Bp): input prologue applied while
     staging -- bit0 BatchNorm affine + ReLU with a/b [P, C_in], bit1 x2 linear upsampling of a half-resolution input
@@ -807,13 +813,17 @@ def conv(xv, wp, Cog, K, out=None, bias=None, in_scale=None, res=None, gate=None
     BatchNorm-backward sums sum(g*m), sum(g*m*xhat) of the layer this backward-data launch propagates into.
     `live` = (int32 table [B, G], addend): the caller's promise that the operand, after in_scale, is exactly zero at every
     t >= table[b, g] + addend (ops.live_extent + the bias-free convs in between, never configuration): nef_conv_fwd_live, same bits.
+    `res_live` = the addend of the same promise for `res` (after res_scale), over the same table: a dead tile behind it as well only
+    stores its zeros (nef_conv_fwd_live_res).  None: no promise, such a tile runs the whole epilogue.
     Returns the output tensor."""
     L = _lib.load()
     if live is not None and not LIVE:
         live = None
 
     def launch():
-        if live is not None:
+        if live is not None and res is not None and res_live is not None:
+            _lib.check(L.nef_conv_fwd_live_res(C.byref(a), _p(live[0]), int(live[1]), int(res_live), _stream()), "nef_conv_fwd_live_res")
+        elif live is not None:
             _lib.check(L.nef_conv_fwd_live(C.byref(a), _p(live[0]), int(live[1]), _stream()), "nef_conv_fwd_live")
         else:
             _lib.check(L.nef_conv_fwd(C.byref(a), _stream()), "nef_conv_fwd")

@@ -58,6 +58,11 @@ int nef_live_extent(const float* x, int32_t* live, int B, int V, int L, nef_stre
 size_t nef_stem_bwd_ws_bytes(int V);
 int nef_stem_bwd_weight(const float* x, const float* w, const float* gy, float* gw, void* ws, size_t ws_bytes,
                         int B, int V, int L, nef_stream_t stream);
+/* The same with nef_live_extent's table of the same x (live [B][V], required): behind a row's extent the conv's pre-activations are
+ * exactly zero, so the ReLU gate kills gy there whatever it holds; the matrix-core kernel (L % 8 == 0, row within 64 KiB of LDS) walks
+ * and stages every row only up to its extent rounded up to 16 outputs.  Same bits; the other kernel ignores the table. */
+int nef_stem_bwd_weight_live(const float* x, const float* w, const float* gy, float* gw, void* ws, size_t ws_bytes,
+                             int B, int V, int L, const int32_t* live, nef_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Grouped Conv1d (stride 1, odd K in {1,3,7}, pad (K-1)/2) as an implicit GEMM on fp32 MFMA.
@@ -212,6 +217,16 @@ int nef_conv_fwd(const nef_conv_args* a, nef_stream_t stream);
  * Every other form (other wino, prologues, short rows) ignores the table and runs as nef_conv_fwd.  A promise that does not hold
  * gives wrong results silently: derive it from a measured table and a chain of bias-free convs only. */
 int nef_conv_fwd_live(const nef_conv_args* a, const int32_t* live, int32_t live_add, nef_stream_t stream);
+/* Zero-fill exit.  A dead tile of such a launch (its window behind the bound as above) stores +0.0 to
+ * its outputs and leaves -- no operand, table, LDS or barrier -- when the launch says that the epilogue maps a zero accumulator to
+ * zero at every output of the tile: no bias, no statistics (stats / bnb_slots NULL; a stats_mode 1 launch therefore keeps the full
+ * epilogue), and no residual -- or, through nef_conv_fwd_live_res, a residual with a promise of its own: a->res (after res_scale) is
+ * exactly zero at every t >= live[b*G + g] + res_add, and the tile qualifies only if t0 >= live + res_add.  ReLU, dropout and the
+ * gate keep zeros and need no condition; where a negative gate scale would have written -0.0 this path writes +0.0 (equal as
+ * numbers, and a later conv's sums do not tell them apart).  x_amax_next and x_clamped need nothing: a dead tile's magnitude is 0.
+ * A dead tile that does not qualify runs the path above.  nef_conv_fwd_live_res requires a->res; everything else as
+ * nef_conv_fwd_live.  An addition: the ABI number stays, a binding finds a library without it by the missing symbol. */
+int nef_conv_fwd_live_res(const nef_conv_args* a, const int32_t* live, int32_t live_add, int32_t res_add, nef_stream_t stream);
 /* sizeof(nef_conv_args) as the library was built: a binding checks its mirror of the struct against it. */
 size_t nef_conv_args_bytes(void);
 
