@@ -137,6 +137,23 @@ class AugmentArgs(C.Structure):
                 ("B", i32), ("V", i32), ("L", i32), ("R", i32), ("crop", i32), ("reserved0", i32)]
 
 
+class LeadMaskMixFwdArgs(C.Structure):
+    """Mirror of `nef_lead_mask_mix_fwd_args` (include/nefnet_hip.h)."""
+    _fields_ = [("z1", p), ("z2r", p), ("mask", p), ("q", p), ("choice_dev", p), ("latent", p), ("D", p), ("picks", p),
+                ("B", i32), ("V", i32), ("T", i32), ("c1", i32), ("c2", i32), ("reserved0", i32)]
+
+
+class LeadMaskMixBwdArgs(C.Structure):
+    """Mirror of `nef_lead_mask_mix_bwd_args` (include/nefnet_hip.h)."""
+    _fields_ = [("gD", p), ("latent", p), ("z1", p), ("z2r", p), ("q", p), ("mask", p), ("choice_dev", p), ("gz1", p), ("gz2r", p),
+                ("gq", p), ("B", i32), ("V", i32), ("T", i32), ("c1", i32), ("c2", i32), ("relu_z1", i32), ("up", i32), ("reserved0", i32)]
+
+
+class AugmentMaskArgs(C.Structure):
+    """Mirror of `nef_augment_mask_args` (include/nefnet_hip.h)."""
+    _fields_ = [("mask", p), ("seed_dev", p), ("seed", C.c_uint64), ("lead_drop", f32), ("B", i32), ("V", i32), ("reserved0", i32)]
+
+
 class WarpArgs(C.Structure):
     """Mirror of `nef_warp_args` (include/nefnet_hip.h)."""
     _fields_ = [("data", p), ("target", p), ("rest", p), ("rois", p), ("data_out", p), ("target_out", p), ("rest_out", p),
@@ -279,6 +296,12 @@ SIGNATURES = {
     "nef_locate_cands_args_bytes": (sz, []),
     "nef_augment": (i32, [C.POINTER(AugmentArgs), p]),
     "nef_augment_args_bytes": (sz, []),
+    "nef_lead_mask_mix_fwd": (i32, [C.POINTER(LeadMaskMixFwdArgs), p]),
+    "nef_lead_mask_mix_fwd_args_bytes": (sz, []),
+    "nef_lead_mask_mix_bwd": (i32, [C.POINTER(LeadMaskMixBwdArgs), p]),
+    "nef_lead_mask_mix_bwd_args_bytes": (sz, []),
+    "nef_augment_mask": (i32, [C.POINTER(AugmentMaskArgs), p]),
+    "nef_augment_mask_args_bytes": (sz, []),
     "nef_warp": (i32, [C.POINTER(WarpArgs), p]),
     "nef_warp_args_bytes": (sz, []),
     "nef_beat_batch": (i32, [C.POINTER(BeatBatchArgs), p]),
@@ -369,6 +392,9 @@ def load():
                                ("nef_locate_best_args", lib.nef_locate_best_args_bytes(), LocateBestArgs),
                                ("nef_locate_cands_args", lib.nef_locate_cands_args_bytes(), LocateCandsArgs),
                                ("nef_augment_args", lib.nef_augment_args_bytes(), AugmentArgs),
+                               ("nef_lead_mask_mix_fwd_args", lib.nef_lead_mask_mix_fwd_args_bytes(), LeadMaskMixFwdArgs),
+                               ("nef_lead_mask_mix_bwd_args", lib.nef_lead_mask_mix_bwd_args_bytes(), LeadMaskMixBwdArgs),
+                               ("nef_augment_mask_args", lib.nef_augment_mask_args_bytes(), AugmentMaskArgs),
                                ("nef_warp_args", lib.nef_warp_args_bytes(), WarpArgs),
                                ("nef_beat_batch_args", lib.nef_beat_batch_args_bytes(), BeatBatchArgs),
                                ("nef_beat_range_args", lib.nef_beat_range_args_bytes(), BeatRangeArgs),

@@ -57,10 +57,21 @@ def _number(cfg, key, default):
     return float(v)
 
 
+def lead_mask_on(cfg):
+    """MODEL.lead_mask: the train step (and the aug_eval read-out) tell the head which leads DATA.aug_lead_drop zeroed, so the lead mean
+    and the Standin picks run over the present leads only (include/nefnet_hip.h, nef_lead_mask_mix_fwd_args).  Configs written before
+    the key existed have none: off."""
+    model = cfg.get("MODEL") or {}
+    v = model.get("lead_mask", False)
+    if not isinstance(v, bool):
+        raise ValueError(f"Invalid MODEL.lead_mask: {v!r} (True or False)")
+    return v
+
+
 def from_cfg(cfg) -> Optional[Augment]:
     """The run's Augment, or None when aug_noise_std, aug_wander_amp, aug_hum_amp and aug_lead_drop are all 0 (configs written before the
     keys existed have none).  Raises ValueError, naming the key: a negative value, aug_lead_drop >= 1, aug_wander_hz with lo > hi,
-    sample_rate <= 0, a wander or hum frequency at or above sample_rate / 2."""
+    sample_rate <= 0, a wander or hum frequency at or above sample_rate / 2, MODEL.lead_mask on with aug_lead_drop 0 (nothing to mask)."""
     noise, wander, hum, drop = (_number(cfg, k, 0.0) for k in ("aug_noise_std", "aug_wander_amp", "aug_hum_amp", "aug_lead_drop"))
     hz = cfg.DATA.get("aug_wander_hz", [0.05, 0.7])
     if not isinstance(hz, (list, tuple)) or len(hz) != 2 or any(isinstance(f, bool) or not isinstance(f, (int, float)) or f != f for f in hz):
@@ -81,6 +92,8 @@ def from_cfg(cfg) -> Optional[Augment]:
         raise ValueError(f"Invalid DATA.aug_wander_hz: {hz!r} reaches sample_rate / 2 = {fs / 2:g} Hz")
     if hum_hz >= fs / 2:
         raise ValueError(f"Invalid DATA.aug_hum_hz: {hum_hz!r} reaches sample_rate / 2 = {fs / 2:g} Hz")
+    if lead_mask_on(cfg) and drop == 0:
+        raise ValueError("MODEL.lead_mask is on with DATA.aug_lead_drop 0: no lead is ever dropped, there is nothing to mask")
     if noise == 0 and wander == 0 and hum == 0 and drop == 0:
         return None
     return Augment(noise, wander, lo, hi, hum, hum_hz, drop, fs, bool(cfg.DATA.get("aug_crop", True)), bool(cfg.DATA.get("aug_eval", False)))

@@ -64,6 +64,12 @@ _DEFAULTS = {
         "loss": "v1",                  # 'v1' = losswrapper (L1/L2 + Standin terms)
         "jitter_factor": 0.0,          # view-angle jitter in degrees (dataset side)
         "theta_L": 1,
+        # True (needs DATA.aug_lead_drop > 0): the train step -- and the DATA.aug_eval read-out -- hand the head a per-sample lead mask of the
+        # leads aug_lead_drop zeroed, so the lead mean and the Standin picks run over the present leads only and a dropped lead's encoder
+        # output is never averaged in (include/nefnet_hip.h, nef_lead_mask_mix_fwd_args).  The masked head runs the
+        # un-fused three-pass route.  The clean test phase passes no mask.  Inference: the `lead_mask=` keyword of Model_nefnet.forward /
+        # gen_ecg / panorama / locate.  False: the launches, graphs and bits are what they were before the key existed
+        "lead_mask": False,
     },
     "SOLVER": {
         # 'sgd' (FusedSGD: torch.optim.SGD, momentum 0.9), 'adam' (FusedAdam: torch.optim.Adam) or 'adamw' (FusedAdamW: torch.optim.AdamW)

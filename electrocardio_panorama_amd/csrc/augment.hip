@@ -8,17 +8,15 @@
 // formed and reduced to [0, 1) turns in fp64 (a 50 Hz hum's 4000 turns at t = 40000 would be good to 2^-12 turns in fp32), the sine
 // itself is fp32.
 #include "nef_common.h"
+#include "aug_drop.h"
 
 namespace {
+
+using namespace nef_aug;      // field0 / field1 / INV24F / ROW_BASE / lead_dropped: shared with nef_augment_mask
 
 constexpr int TILE = NEF_AUGMENT_TILE;
 static_assert(TILE == 256 * 4, "one float4 per thread of a 256-thread block");
 constexpr double INV24 = 1.0 / 16777216.0;
-constexpr float INV24F = 1.0f / 16777216.0f;
-constexpr uint64_t ROW_BASE = 1ull << 62;       // row counters live far above every element counter
-
-__device__ __forceinline__ uint32_t field0(uint64_t z) { return (uint32_t)(z >> 40); }
-__device__ __forceinline__ uint32_t field1(uint64_t z) { return (uint32_t)((z >> 16) & 0xFFFFFFull); }
 
 // sin(2 pi (w t + phi)) with the phase in turns: fp64 up to the reduced phase, fp32 from there
 __device__ __forceinline__ float turn_sin(double w, double phi, int t) {
@@ -37,16 +35,9 @@ __global__ __launch_bounds__(256) void augment_kernel(const nef_augment_args a, 
     float4* __restrict__ out = reinterpret_cast<float4*>(a.y + e0);
     const uint64_t rc = ROW_BASE + 4ull * (uint64_t)row;
 
-    if (a.lead_drop > 0.f && field1(nef_rng_mix(seed, rc + 2)) * INV24F < a.lead_drop) {      // block-uniform
-        // this row drew "dropped": it is kept all the same when every lead of the sample did and it is the fallback lead
-        bool all = true;
-        for (int v2 = 0; v2 < a.V; ++v2)
-            all = all && field1(nef_rng_mix(seed, ROW_BASE + 4ull * (uint64_t)(b * a.V + v2) + 2)) * INV24F < a.lead_drop;
-        const int fallback = (int)(((uint64_t)a.V * field0(nef_rng_mix(seed, ROW_BASE + 4ull * (uint64_t)(b * a.V) + 3))) >> 24);
-        if (!(all && fallback == v)) {
-            *out = make_float4(0.f, 0.f, 0.f, 0.f);
-            return;
-        }
+    if (lead_dropped(seed, b, v, a.V, a.lead_drop)) {                // block-uniform (aug_drop.h)
+        *out = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
     }
 
     const float4 xv = *reinterpret_cast<const float4*>(a.x + e0);

@@ -535,14 +535,21 @@ def _head_shared(T):
     return 2 * T >= 128
 
 
-def _head_fwd(P, Bf, z1, z2r, q_theta, V, rest_theta, phase, training, lead_choice, sv, rest_chunk, half_sweep, unpool=None):
+def _head_fwd(P, Bf, z1, z2r, q_theta, V, rest_theta, phase, training, lead_choice, sv, rest_chunk, half_sweep, unpool=None,
+              lead_mask=None):
     """model_nefnet.py:146-190: lead means, Standin mixes, query scaling, the three decoder passes (+ the sweep).
-    `unpool` = (z2b, rois, status) instead of z2r (None): the shared path un-pools the segments while it mixes."""
+    `unpool` = (z2b, rois, status) instead of z2r (None): the shared path un-pools the segments while it mixes.
+    `lead_mask` uint8 [B, V]: mean and picks over each sample's present leads (ops.lead_mask_mix_fwd) and the three-pass decoder, at
+    every T."""
     B = z1.shape[0]
     save = sv is not None
     q = ops.theta_mlp_fwd(q_theta, P["mlp2.weight"], P["mlp2.bias"])             # [B, 256]
     z2b = None
-    if unpool is not None:
+    if lead_mask is not None:
+        assert unpool is None
+        latent, D = ops.lead_mask_mix_fwd(z1, z2r, lead_mask, q, lead_choice)     # [B, 256, T], [3B, 256, T]
+        out3, dsv = decoder_fwd(D, P, Bf, 3, training, save)
+    elif unpool is not None:
         assert _head_shared(z1.shape[2])
         z2b, rois, status = unpool
         latent, D2 = ops.lead_mean_mix_unpool(z1, z2b, rois, q, V, lead_choice, z1.shape[2], status)
@@ -556,7 +563,7 @@ def _head_fwd(P, Bf, z1, z2r, q_theta, V, rest_theta, phase, training, lead_choi
         out3, dsv = decoder_fwd(D, P, Bf, 3, training, save)
     outs = (out3[0:B], out3[B:2 * B], out3[2 * B:3 * B])
     if save:
-        sv.update(z1=z1, z2r=z2r, z2b=z2b, latent=latent, q=q, q_theta=q_theta, choice=lead_choice, dec=dsv, hB=B, hV=V)
+        sv.update(z1=z1, z2r=z2r, z2b=z2b, latent=latent, q=q, q_theta=q_theta, choice=lead_choice, dec=dsv, hB=B, hV=V, mask=lead_mask)
     if phase == "train":
         return outs, sv
     if phase in ("val", "test"):
@@ -565,7 +572,7 @@ def _head_fwd(P, Bf, z1, z2r, q_theta, V, rest_theta, phase, training, lead_choi
     raise KeyError("please type correct phase")
 
 
-def _views_fwd(P, Bf, z1, z2r, q_theta, V, training, lead_choice, sv, unpool):
+def _views_fwd(P, Bf, z1, z2r, q_theta, V, training, lead_choice, sv, unpool, lead_mask=None):
     """The head once per query angle of q_theta [Q, B, 2] on ONE encoder pass (SOLVER.train_views; the reference's forward takes one
     query_theta in train mode, model_nefnet.py:109): every view runs _head_fwd as a single-view step would -- its own BatchNorm batch
     statistics, the running statistics updated in view order -- with the step's one dropout seed and Standin draw, and keeps its own
@@ -580,7 +587,8 @@ def _views_fwd(P, Bf, z1, z2r, q_theta, V, training, lead_choice, sv, unpool):
             hsv = dict(rois=sv["rois"])
         # the step-level pack serves every view: the operands stay in the table until the last head has taken them
         with ops.pack_keep(k < Q - 1):
-            outs, hsv = _head_fwd(P, Bf, z1, z2r, q_theta[k], V, None, "train", training, lead_choice, hsv, 8, False, unpool=unpool)
+            outs, hsv = _head_fwd(P, Bf, z1, z2r, q_theta[k], V, None, "train", training, lead_choice, hsv, 8, False, unpool=unpool,
+                                  lead_mask=lead_mask)
         heads.append(hsv)
         srcs += list(outs)
         dsts += [buf[j, k] for j in range(3)]
@@ -591,11 +599,13 @@ def _views_fwd(P, Bf, z1, z2r, q_theta, V, training, lead_choice, sv, unpool):
 
 
 def forward(P, Bf, x, in_theta, q_theta, rois, rest_theta=None, phase="train", training=True, drop=None,
-            lead_choice=(0, 0), save=False, rest_chunk=8, status=None, half_sweep=False):
+            lead_choice=(0, 0), save=False, rest_chunk=8, status=None, half_sweep=False, lead_mask=None):
     """Returns (outputs tuple, saved-state or None).  `lead_choice` are the two Standin lead indices
     (model_nefnet.py:154,156), drawn by the caller: a tuple of ints, or a device int32[2] tensor (graph replay).
     A 3-D `q_theta` [Q, B, 2] (view-major; phase "train" only) is the multi-view form: one encoder pass, Q heads (_views_fwd), and
-    three [Q, B, 1, L] outputs."""
+    three [Q, B, 1, L] outputs.
+    `lead_mask`: None, or uint8 [B, V] (ops.lead_mask_arg): the head averages and picks among each sample's present leads and runs the
+    un-fused three-pass route (_head_fwd); phase "gen" returns the per-lead pair and ignores it."""
     drop = drop or DropCfg(False)
     multi = q_theta.dim() == 3
     if multi and phase != "train":
@@ -615,6 +625,12 @@ def forward(P, Bf, x, in_theta, q_theta, rois, rest_theta=None, phase="train", t
     z1, z2b, sv = _latents(P, x, in_theta, rois, drop, save, pack_side)
     if phase == "gen":
         return (z1, z2b), None
+    if lead_mask is not None:
+        z2r = ops.roi_unpool_fwd(z2b, rois, T, status)
+        if multi:
+            return _views_fwd(P, Bf, z1, z2r, q_theta, V, training, lead_choice, sv, None, lead_mask=lead_mask)
+        return _head_fwd(P, Bf, z1, z2r, q_theta, V, rest_theta, phase, training, lead_choice, sv, rest_chunk, half_sweep,
+                         lead_mask=lead_mask)
     if _head_shared(T) and V <= ops.UNPOOL_MIX_MAX_V:
         # z2r [B, 128V, T] is never written: the mix reads the segments (and the backward hands their gradient straight back)
         if multi:
@@ -634,12 +650,13 @@ def _lead_view(t, i, V):
 
 
 def forward2(P, Bf, x, in_theta, q_theta, rois, rest_theta=None, phase="train", training=True, drop=None,
-             lead_choice=(0, 0), save=False, rest_chunk=8, status=None, half_sweep=False):
+             lead_choice=(0, 0), save=False, rest_chunk=8, status=None, half_sweep=False, lead_mask=None):
     """Model_nefnet2.forward (reference codes/network/model_nefnet2.py:118-194): ONE single-lead encoder shared by all
     leads.  The reference loops over the leads; here the leads are folded into the batch (lead-major, n = v*B + b), so
     the shared-weight encoder runs once on V*B single-lead samples, and the two extra convs (`single_conv_z1/_z2`,
     :140,:149) write their outputs lead by lead into lead-blocked [B, 128V, T] tensors, from where the lead mean, the
-    Standin mixes and the decoder are exactly Model_nefnet's."""
+    Standin mixes and the decoder are exactly Model_nefnet's.  `lead_mask`: as in forward(); phase "gen" returns the two means over
+    the present leads."""
     drop = drop or DropCfg(False)
     if q_theta.dim() != 2:
         raise ValueError(f"Model_nefnet2 takes one query_theta [B, 2] per step, got {tuple(q_theta.shape)} (the multi-view train step, "
@@ -663,11 +680,11 @@ def forward2(P, Bf, x, in_theta, q_theta, rois, rest_theta=None, phase="train", 
         ops.conv(GV.dense(z2rf[i * B:(i + 1) * B], 1), wp2, 128, 3, bias=P["single_conv_z2.0.bias"],
                  out=_lead_view(Z2, i, V))
     if phase == "gen":                                                             # :158-159: the two lead means
-        latent = ops.lead_mean(Z1, Z2, V)
+        latent = ops.lead_mean(Z1, Z2, V) if lead_mask is None else ops.lead_mask_mix_fwd(Z1, Z2, lead_mask, None)[0]
         return (latent[:, :128].contiguous(), latent[:, 128:].contiguous()), None
     if save:
         sv.update(z1f=z1f, z2rf=z2rf, fold=(B, V))
-    return _head_fwd(P, Bf, Z1, Z2, q_theta, V, rest_theta, phase, training, lead_choice, sv, rest_chunk, half_sweep)
+    return _head_fwd(P, Bf, Z1, Z2, q_theta, V, rest_theta, phase, training, lead_choice, sv, rest_chunk, half_sweep, lead_mask=lead_mask)
 
 
 def sweep(P, Bf, latent, query_thetas, training=False, chunk=8, half=False):
@@ -760,13 +777,13 @@ def sweep_eval_h(P, Bf, latent, query_thetas, pair_budget=16384):
     return rest
 
 
-def gen_ecg(P, Bf, z1, z2b, query_thetas, rois, chunk=8, half=False):
-    """model_nefnet.py:196-218 (always eval-mode BatchNorm)."""
+def gen_ecg(P, Bf, z1, z2b, query_thetas, rois, chunk=8, half=False, lead_mask=None):
+    """model_nefnet.py:196-218 (always eval-mode BatchNorm).  `lead_mask` uint8 [B, V]: the latent is the mean over the present leads."""
     V = z1.shape[1] // 128
     ops.BATCH_HINT = z1.shape[0]      # as forward(): the kernel choice follows THIS call's batch, not whichever pass ran last
     ops.amax_roll()                   # ... and the split-fp16 convs of the sweep start from the scales their last sweep left
     z2r = ops.roi_unpool_fwd(z2b.contiguous(), rois, z1.shape[2])
-    latent = ops.lead_mean(z1, z2r, V)
+    latent = ops.lead_mean(z1, z2r, V) if lead_mask is None else ops.lead_mask_mix_fwd(z1, z2r, lead_mask, None)[0]
     if half:
         return sweep_eval_h(P, Bf, latent, query_thetas)
     return sweep(P, Bf, latent, query_thetas, False, chunk)
@@ -775,17 +792,20 @@ def gen_ecg(P, Bf, z1, z2b, query_thetas, rois, chunk=8, half=False):
 LOCATE_VIEW_BYTES = 1 << 30      # level-0 views alive at a time when `chunk` is left to locate()
 
 
-def locate_latent(z1, z2b, rois):
+def locate_latent(z1, z2b, rois, lead_mask=None):
     """The decoder's latent [B, 256, T] from phase 'gen's pair: Model_nefnet returns z1 [B, 128V, T] and the pooled z2 [B, 128V, 7, 32]
-    (un-pooled and averaged over the leads here, as gen_ecg does); Model_nefnet2 returns the two lead means [B, 128, T] themselves."""
+    (un-pooled and averaged over the leads -- the present ones, with `lead_mask` uint8 [B, V] -- here, as gen_ecg does); Model_nefnet2
+    returns the two lead means [B, 128, T] themselves (its phase 'gen' has applied the mask)."""
     if z2b.dim() == 3:
         return torch.cat([z1, z2b], dim=1).contiguous()
     z2r = ops.roi_unpool_fwd(z2b.contiguous(), rois, z1.shape[2])
+    if lead_mask is not None:
+        return ops.lead_mask_mix_fwd(z1, z2r, lead_mask, None)[0]
     return ops.lead_mean(z1, z2r, z1.shape[1] // 128)
 
 
 def locate(P, Bf, z1, z2b, observed, rois, grid, score="corr", levels=3, radius=2, crop=True, eps=1e-8, chunk=None, half=False,
-           return_scores=False, return_trace=False):
+           return_scores=False, return_trace=False, lead_mask=None):
     """The viewing angle of each observed row [B, R, L] by a scored panorama search (locate.py; include/nefnet_hip.h,
     nef_locate_score_args): the latent is formed once, as gen_ecg does; level 0 sweeps the grid's angles in chunks of at most `chunk`
     (views of one chunk exist at a time) and scores each chunk into its columns of scores [B, R, A], one nef_locate_best picks the winners;
@@ -795,7 +815,7 @@ def locate(P, Bf, z1, z2b, observed, rois, grid, score="corr", levels=3, radius=
     from . import locate as _loc
     ops.BATCH_HINT = z1.shape[0]
     ops.amax_roll()
-    latent = locate_latent(z1, z2b, rois)
+    latent = locate_latent(z1, z2b, rois, lead_mask)
     B, R, Ln = observed.shape
     dev = latent.device
     row_rois = rois if crop else None
@@ -842,6 +862,12 @@ def _head_bwd(P, sv, g_outs, grads, side, relu_z1=False):
     z2r, T = sv["z2r"], sv["latent"].shape[2]
     fused = z2r is None and gD.shape[2] == T and T <= ops.UNPOOL_MIX_MAX_T
     gz1_sum = None             # chan_sum(gz1) where the kernel that stores gz1 forms it (relu_z1: what z1_conv's block would sum)
+    if sv.get("mask") is not None:      # the masked head: three passes, rows of absent leads come back as zeros
+        assert not shared and z2r is not None
+        gz1, gz2r, gq = ops.lead_mask_mix_bwd(gD, sv["latent"], sv["z1"], z2r, sv["q"], sv["mask"], sv["choice"], up=up, relu_z1=relu_z1)
+        gW2, gb2 = side.run(lambda: ops.theta_mlp_bwd(sv["q_theta"], gq, 256), gq)
+        grads["mlp2.weight"], grads["mlp2.bias"] = gW2, gb2
+        return gz1, gz2r, None, None
     if z2r is None and not fused:      # the gradient arrives upsampled, or its rows are too long for the strips: the two-pass form
         z2r = ops.roi_unpool_fwd(sv["z2b"], sv["rois"], T)
     if fused:                          # forward mixed straight from the segments: (gz1, gz2b), no gz2r, no un-pooling backward
@@ -938,8 +964,24 @@ def _latents_bwd(P, sv, gz1, gz2r, grads, side, z1_pre_gated=False, early=False,
     grads["W_encoder.conv1.weight"] = ops.stem_bwd_weight(sv["x"], P["W_encoder.conv1.weight"], g, live=sv.get("stem_live"))
 
 
-def backward(P, sv, g_outs):
-    """g_outs: gradients wrt (out, shuffle_p, shuffle_l), each [B,1,L] or None.  Returns {param name: grad}."""
+def _check_saved_mask(sv, lead_mask):
+    """backward(lead_mask=...): the mask is part of the saved forward state; one passed again has to be the forward's tensor -- bool or
+    uint8, a view of it counts.  Identity is checked, not content: nothing is read by the host."""
+    if lead_mask is None:
+        return
+    saved = [h.get("mask") for h in sv["views"]] if "views" in sv else [sv.get("mask")]
+    wrong = ValueError("backward: lead_mask is not the mask the forward ran with (the saved state carries it; pass None or the same tensor)")
+    if any(m is None for m in saved):
+        raise wrong
+    given = ops.lead_mask_arg(lead_mask, saved[0].shape[0], saved[0].shape[1], saved[0].device)
+    if any(m.data_ptr() != given.data_ptr() for m in saved):
+        raise wrong
+
+
+def backward(P, sv, g_outs, lead_mask=None):
+    """g_outs: gradients wrt (out, shuffle_p, shuffle_l), each [B,1,L] or None.  Returns {param name: grad}.  `lead_mask`: None (the
+    forward's mask travels in `sv`), or that same tensor."""
+    _check_saved_mask(sv, lead_mask)
     grads = {}
     side = _side(sv["z1"].device, sv["z1"].numel())
     if "views" in sv:
@@ -951,9 +993,10 @@ def backward(P, sv, g_outs):
     return grads
 
 
-def backward2(P, sv, g_outs):
+def backward2(P, sv, g_outs, lead_mask=None):
     """Backward of forward2: the head as in Model_nefnet, then the two shared single convs lead by lead (their weight
-    gradients summed over the leads in lead order), then the folded-batch encoder."""
+    gradients summed over the leads in lead order), then the folded-batch encoder.  `lead_mask`: as in backward()."""
+    _check_saved_mask(sv, lead_mask)
     grads = {}
     side = _side(sv["z1"].device, sv["z1"].numel())
     gZ1, gZ2, _, _ = _head_bwd(P, sv, g_outs, grads, side)                           # [B, 128V, T]

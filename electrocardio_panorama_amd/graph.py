@@ -43,6 +43,11 @@ Input-lead augmentation (cfg.DATA.aug_*; augment.py): every shape slot owns one 
 staged inputs into it is the FIRST launch of the captured forward -- it reads the step's seed through the `seed_dev` word the dropout
 epilogues read, so every replay (every micro-batch of an accumulation window; once per multi-view step) draws its own corruption with no
 host write of its own.  Off: no buffer, no launch.
+
+Lead masks (cfg.MODEL.lead_mask, with DATA.aug_lead_drop): every shape slot owns a static uint8 [B, V] buffer, filled by
+ops.augment_mask directly behind the captured ops.augment from the same host word and `seed_dev`, and handed to engine.forward, whose
+head then averages and picks among the leads the corruption left (the backward finds the mask in the saved state).  Two library
+launches in the graph, no torch kernel, no host write between replays.  Off: no buffer, no launch, today's graph.
 """
 import random
 
@@ -73,6 +78,9 @@ class GraphedTrainStep:
         from . import augment as _augment
         self.augment = _augment.from_cfg(cfg)
         self.data_aug = None
+        # cfg.MODEL.lead_mask: every shape slot owns a static uint8 [B, V] mask the captured ops.augment_mask writes and the head reads
+        self.lead_mask_on = self.augment is not None and _augment.lead_mask_on(cfg)
+        self.lead_mask = None
         self.optimizer = optimizer
         if optimizer is not None:
             if len(optimizer.param_groups) != 1 or not hasattr(optimizer, "_device_update"):
@@ -158,10 +166,16 @@ class GraphedTrainStep:
             # the step's first launch: the corrupted leads into the slot's buffer, at host word + seed_dev = the eager step's seed word
             from . import augment as _augment
             data = ops.augment(self.data, self.rois, self.augment, seed=_augment.site_word(), seed_dev=self.seed_dev, out=self.data_aug)
+        mask_kw = {}
+        if self.lead_mask_on:
+            # ... and directly behind it the mask of the leads it zeroed, from the same two seed words
+            ops.augment_mask(self.data.shape[0], self.data.shape[1], self.augment.lead_drop, seed=_augment.site_word(),
+                             seed_dev=self.seed_dev, out=self.lead_mask)
+            mask_kw = dict(lead_mask=self.lead_mask)
         with ops.amax_scope((m._nef_scope, True)):        # the train-mode call sites of the model (Model_nefnet._engine_fwd)
             outs, sv = engine.forward(P, dict(m.named_buffers()), data, self.in_theta, self.q_theta, self.rois,
                                       phase="train", training=True, drop=drop, lead_choice=self.choice_dev, save=True,
-                                      status=self.status)
+                                      status=self.status, **mask_kw)
             o, p_, l_ = (t.contiguous() for t in outs)
             ops.loss_fwd(o, p_, l_, self.target, self.factors, self.reg_l2, self.use_mask, out=self.losses, noise=self.noise)
             g3 = ops.loss_bwd(o, p_, l_, self.target, None, self.factors, self.reg_l2, self.use_mask, noise=self.noise)
@@ -274,6 +288,7 @@ class GraphedTrainStep:
         self.noise = slot.get("noise")
         self.rois_q = slot.get("rois_q")
         self.data_aug = slot.get("data_aug")
+        self.lead_mask = slot.get("lead_mask")
 
     def _build(self, data, in_theta, q_theta, rois, target, noise=None):
         dev = data.device
@@ -297,6 +312,8 @@ class GraphedTrainStep:
             slot["noise"] = torch.empty(data.shape[0], 1, data.shape[2], device=dev, dtype=torch.float32)
         if self.augment is not None:
             slot["data_aug"] = torch.empty(data.shape, device=dev, dtype=torch.float32)
+        if self.lead_mask_on:
+            slot["lead_mask"] = torch.empty(data.shape[0], data.shape[1], device=dev, dtype=torch.uint8)
         self._use(slot)
         if self.choice_dev is None:
             self.choice_dev = torch.zeros(2, device=dev, dtype=torch.int32)

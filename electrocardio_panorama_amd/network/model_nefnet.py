@@ -10,6 +10,10 @@ shapes and default initialisation; their own forward() is never called.  All com
 Beyond the reference: `forward(..., query_theta [Q, B, 2], phase='train')` (view-major angles) supervises Q views on one encoder pass
 and returns three [Q, B, 1, L] tensors (SOLVER.train_views; engine._views_fwd); a 2-D `query_theta` is the reference's call.
 `model.augment` (DATA.aug_*; augment.py): a train-phase forward in train() mode reads its input leads through ops.augment.
+`lead_mask=` (keyword only; bool / uint8 [B, V] on the input's device) on forward, gen_ecg, panorama and locate: the lead mean and the
+Standin picks run over each sample's present leads (include/nefnet_hip.h, nef_lead_mask_mix_fwd_args); absent leads are never read
+behind the encoder.  `model.lead_mask_from_aug` (MODEL.lead_mask): the train step derives the mask from the leads DATA.aug_lead_drop
+zeroed.
 """
 import math
 import random
@@ -59,11 +63,11 @@ class _NefNetFn(torch.autograd.Function):
     """One autograd node for the whole train-phase forward; backward is engine.backward."""
 
     @staticmethod
-    def forward(ctx, model, x, in_theta, q_theta, rois, choice, drop, names, *params):
+    def forward(ctx, model, x, in_theta, q_theta, rois, choice, drop, mask, names, *params):
         P = dict(zip(names, params))
         outs, sv = model._engine_fwd(P, model._buffers_by_name(), x, in_theta, q_theta, rois, phase="train",
                                      training=model.training, drop=drop, lead_choice=choice, save=True,
-                                     status=model._status)
+                                     status=model._status, **model._mask_kw(mask))      # (the mask reaches the backward in sv)
         ctx.sv, ctx.names, ctx.P, ctx.bwd = sv, names, P, model._engine_bwd
         if model.keep_saved:
             model.last_saved = sv
@@ -73,7 +77,7 @@ class _NefNetFn(torch.autograd.Function):
     def backward(ctx, g_out, g_p, g_l):
         grads = ctx.bwd(ctx.P, ctx.sv, (g_out, g_p, g_l))
         ctx.sv = None
-        return (None,) * 8 + tuple(grads.get(n) for n in ctx.names)
+        return (None,) * 9 + tuple(grads.get(n) for n in ctx.names)
 
 
 class Model_nefnet(nn.Module):
@@ -151,6 +155,9 @@ class Model_nefnet(nn.Module):
         # DATA.aug_* (augment.from_cfg's Augment; Solver.__init__ sets it from the config): a train-phase forward of a model in train()
         # mode corrupts its input leads in front of the stem, keyed on the forward's dropout seed; None: the input is read as it is
         self.augment = None
+        # MODEL.lead_mask (Solver.__init__ sets it): with `augment.lead_drop > 0`, the forward that corrupts its input also derives the
+        # lead mask of the leads ops.augment zeroed (ops.augment_mask, same seed) and hands it to the head
+        self.lead_mask_from_aug = False
         self._drop_calls = 0
         self.dropout_epoch = 0         # set by Solver.train: a resumed run must not replay the masks of epoch 0
         self._status = None
@@ -181,6 +188,18 @@ class Model_nefnet(nn.Module):
     def _f32(t):
         return t.detach().to(torch.float32).contiguous()
 
+    @staticmethod
+    def _mask_kw(mask):
+        """The engine's keyword for a mask; nothing without one, so that an unmasked call is today's call."""
+        return {} if mask is None else {"lead_mask": mask}
+
+    @staticmethod
+    def _check_mask(lead_mask, B, V, device):
+        """None, or the mask as the uint8 [B, V] tensor the engine reads.  Shape, dtype and device only: no host read."""
+        if lead_mask is None:
+            return None
+        return ops.lead_mask_arg(lead_mask.detach() if torch.is_tensor(lead_mask) else lead_mask, B, V, device)
+
     def _drop_cfg(self):
         """Counter-RNG seed of this forward: global seed + epoch + call counter, offset per data-parallel rank so that
         shards draw independent masks (parameters and Standin lead choices stay identical across ranks)."""
@@ -202,8 +221,9 @@ class Model_nefnet(nn.Module):
         return 0 if self._status is None else int(self._status.item())
 
     # ------------------------------------------------------------------ reference API
-    def forward(self, x, input_thetas, query_theta, rois, rest_theta=None, phase='train'):
+    def forward(self, x, input_thetas, query_theta, rois, rest_theta=None, phase='train', *, lead_mask=None):
         self._check_inputs(x, rois)
+        mask = self._check_mask(lead_mask, x.shape[0], self.lead_num, x.device)
         if query_theta.dim() == 3 and (phase != 'train' or self._ENGINE[0] is not engine.forward):
             # [Q, B, 2], view-major: the multi-view train step (SOLVER.train_views), three [Q, B, 1, L] outputs from one encoder pass
             raise ValueError("a 3-D query_theta [Q, B, 2] is Model_nefnet's multi-view train step: phase {!r} of {} takes [B, 2]".format(
@@ -217,11 +237,17 @@ class Model_nefnet(nn.Module):
         if phase == 'train' and self.training and self.augment is not None:
             # DATA.aug_*: forward and the stem's weight gradient (the saved x) both see the corrupted leads; the caller's tensor is not
             # written.  No other phase corrupts its input, and neither does a train-phase call on a model in eval()
+            if self.lead_mask_from_aug and self.augment.lead_drop > 0:
+                if mask is not None:
+                    raise ValueError("lead_mask_from_aug derives the train step's mask from the dropped leads; an explicit lead_mask "
+                                     "cannot be passed as well")
+                mask = ops.augment_mask(x.shape[0], V, self.augment.lead_drop, seed=_augment.train_seed(drop.seed), device=x.device)
             x = ops.augment(x, rois, self.augment, seed=_augment.train_seed(drop.seed))
+        mkw = self._mask_kw(mask)
         if phase == 'gen':
             with torch.no_grad():
                 (z1, z2), _ = self._engine_fwd(self._params_by_name(), self._buffers_by_name(), x, input_thetas,
-                                             query_theta, rois, phase='gen', training=self.training, drop=drop)
+                                             query_theta, rois, phase='gen', training=self.training, drop=drop, **mkw)
             return z1, z2
         # Python `random` is consumed exactly twice, z1 choice first (model_nefnet.py:154,156)
         choice = (random.randint(0, V - 1), random.randint(0, V - 1))
@@ -229,34 +255,40 @@ class Model_nefnet(nn.Module):
             named = [(n, p) for n, p in self.named_parameters()]
             names = tuple(n for n, _ in named)
             if torch.is_grad_enabled() and any(p.requires_grad for _, p in named):
-                return _NefNetFn.apply(self, x, input_thetas, query_theta, rois, choice, drop, names,
+                return _NefNetFn.apply(self, x, input_thetas, query_theta, rois, choice, drop, mask, names,
                                        *[p for _, p in named])
             with torch.no_grad():
                 outs, _ = self._engine_fwd(dict(named), self._buffers_by_name(), x, input_thetas, query_theta, rois,
                                          phase='train', training=self.training, drop=drop, lead_choice=choice,
-                                         status=self._status)
+                                         status=self._status, **mkw)
             return outs
         if phase in ('val', 'test'):
             with torch.no_grad():
                 outs, _ = self._engine_fwd(self._params_by_name(), self._buffers_by_name(), x, input_thetas, query_theta,
                                          rois, rest_theta=self._f32(rest_theta), phase=phase, training=self.training,
                                          drop=drop, lead_choice=choice, status=self._status,
-                                         half_sweep=self._half_sweep())
+                                         half_sweep=self._half_sweep(), **mkw)
             return outs
         raise KeyError("please type correct phase")
 
-    def gen_ecg(self, z1, z2, query_theta, rois):
+    def gen_ecg(self, z1, z2, query_theta, rois, *, lead_mask=None):
+        """model_nefnet.py:196-218 on phase 'gen's pair.  lead_mask: bool / uint8 [B, V] for Model_nefnet's per-lead pair (z1 [B, 128V, T]):
+        the latent is the mean over each sample's present leads.  Model_nefnet2's phase 'gen' returns the two lead MEANS, with the mask
+        given to that call already applied: its gen_ecg takes no mask (a [B, V] mask does not fit the one-lead pair: ValueError)."""
+        mask = self._check_mask(lead_mask, z1.shape[0], z1.shape[1] // 128, z1.device)
         self.eval()
         with torch.no_grad(), ops.amax_scope((self._nef_scope, False)):      # the sweep's split-fp16 convs keep their call sites (no measuring launch per call)
             return engine.gen_ecg(self._params_by_name(), self._buffers_by_name(), self._f32(z1), self._f32(z2),
                                   self._f32(query_theta), rois.detach().to(torch.int64).contiguous(),
-                                  half=self._half_sweep())
+                                  half=self._half_sweep(), **self._mask_kw(mask))
 
-    def panorama(self, x, input_thetas, rois, query_thetas):
+    def panorama(self, x, input_thetas, rois, query_thetas, *, lead_mask=None):
         """The views of every sample at its A query angles, [B, A, L], from one encoder pass (phase 'gen') and one eval-mode sweep.  (No
         counterpart in the reference, which decodes the angles of gen_ecg from a latent pair the caller carries.)  x [B, V, L],
         input_thetas [B, V, 2], rois [B, 7, 2] as for forward; query_thetas [B, A, 2], or [A, 2] shared by the batch.  Honours
-        panorama_dtype; the model is put back in the mode it was in."""
+        panorama_dtype; the model is put back in the mode it was in.  lead_mask: bool / uint8 [B, V], the leads of each sample that are
+        there; the latent is the mean over them."""
+        mask = self._check_mask(lead_mask, x.shape[0], self.lead_num, x.device)
         q = self._f32(query_thetas)
         if q.dim() == 2:
             q = q.unsqueeze(0).expand(x.shape[0], -1, -1).contiguous()
@@ -266,24 +298,26 @@ class Model_nefnet(nn.Module):
         was_training = self.training
         self.eval()
         try:
-            z1, z2 = self.forward(x, input_thetas, self._f32(input_thetas)[:, 0], rois, phase='gen')
+            z1, z2 = self.forward(x, input_thetas, self._f32(input_thetas)[:, 0], rois, phase='gen', lead_mask=mask)
             with torch.no_grad(), ops.amax_scope((self._nef_scope, False)):
                 ops.BATCH_HINT = z1.shape[0]
                 ops.amax_roll()
-                latent = engine.locate_latent(self._f32(z1), self._f32(z2), rois.detach().to(torch.int64).contiguous())
+                latent = engine.locate_latent(self._f32(z1), self._f32(z2), rois.detach().to(torch.int64).contiguous(), mask)
                 return engine.sweep(self._params_by_name(), self._buffers_by_name(), latent, q, training=False, half=half)
         finally:
             self.train(was_training)
 
     def locate(self, x, input_thetas, rois, observed, *, grid=None, score='corr', levels=3, radius=2, crop=True, eps=None, chunk=None,
-               return_scores=False, return_trace=False):
+               return_scores=False, return_trace=False, lead_mask=None):
         """At which angle was `observed` recorded?  (No counterpart in the reference.)  x [B, V, L], input_thetas [B, V, 2], rois
         [B, 7, 2] as for forward; observed fp32 [B, L] or [B, R, L] in the loaders' normalisation.  One encoder pass (phase 'gen'), a
         level-0 panorama over `grid` (locate.Grid; None: 9 x 19 over LEAD_THETA's span) scored against every observed row ('corr': 1 - r,
         which no gain or offset of the observed lead changes; 'mse'), the deterministic arg-best, and `levels` rounds of (2 radius + 1)^2
         candidates around it at halving steps -- all on the device and stream-ordered (engine.locate).  crop: rows end at rois[b, -1, 0].
         eps: 'corr's eps (None: 1e-8, SOLVER.corr_eps' default).  chunk: level-0 angles decoded at a time.  Honours panorama_dtype;
-        the model is put back in the mode it was in.  Returns a locate.LocateResult."""
+        the model is put back in the mode it was in.  lead_mask: bool / uint8 [B, V], the leads of each sample that are there.  Returns a
+        locate.LocateResult."""
+        mask = self._check_mask(lead_mask, x.shape[0], self.lead_num, x.device)
         from .. import locate as _loc
         st = _loc.check_settings(grid, score, levels, radius, eps)
         if crop and rois is None:
@@ -300,12 +334,12 @@ class Model_nefnet(nn.Module):
         was_training = self.training
         self.eval()
         try:
-            z1, z2 = self.forward(x, input_thetas, self._f32(input_thetas)[:, 0], rois, phase='gen')
+            z1, z2 = self.forward(x, input_thetas, self._f32(input_thetas)[:, 0], rois, phase='gen', lead_mask=mask)
             with torch.no_grad(), ops.amax_scope((self._nef_scope, False)):
                 out = engine.locate(self._params_by_name(), self._buffers_by_name(), self._f32(z1), self._f32(z2), obs,
                                     rois.detach().to(torch.int64).contiguous(), st.grid, score=st.score, levels=st.levels,
                                     radius=st.radius, crop=bool(crop), eps=1e-8 if eps is None else float(eps), chunk=chunk, half=half,
-                                    return_scores=return_scores, return_trace=return_trace)
+                                    return_scores=return_scores, return_trace=return_trace, **self._mask_kw(mask))
         finally:
             self.train(was_training)
         theta, sc, index, theta0, score0, scores, trace = out

@@ -1904,6 +1904,147 @@ def augment(x, rois, aug, seed=0, seed_dev=None, out=None):
     return y
 
 
+LEAD_MASK_MAX_V = 12      # NEF_LEAD_MASK_MAX_V (include/nefnet_hip.h)
+
+
+def lead_mask_arg(mask, B, V, device, what="lead_mask"):
+    """`mask` as the uint8 [B, V] tensor the lead-mask entries read (torch.bool through a view).  Shape, dtype and device are checked;
+    the content is not -- nothing is read by the host."""
+    if not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"{what} must be a bool or uint8 tensor [B, V], got {getattr(mask, 'dtype', type(mask))}")
+    if tuple(mask.shape) != (B, V):
+        raise ValueError(f"{what} {tuple(mask.shape)} is not [{B}, {V}]")
+    if mask.device != device:
+        raise ValueError(f"{what} is on {mask.device}, the leads on {device}")
+    mask = mask if mask.is_contiguous() else mask.contiguous()
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
+def _lead_mask_leads(z1, z2r):
+    for name, t in (("z1", z1), ("z2r", z2r)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise TypeError(f"{name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+        if t.dim() != 3 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous [B, 128 V, T] tensor, got {tuple(t.shape)} with strides {tuple(t.stride())}")
+    B, Ct, T = z1.shape
+    if B < 1 or T < 1 or Ct % 128 != 0 or not 1 <= Ct // 128 <= LEAD_MASK_MAX_V:
+        raise ValueError(f"z1 {tuple(z1.shape)}: [B, 128 V, T] with B, T >= 1 and V in 1..{LEAD_MASK_MAX_V}")
+    if z2r.shape != z1.shape or z2r.device != z1.device:
+        raise ValueError(f"z2r {tuple(z2r.shape)} on {z2r.device} does not match z1 {tuple(z1.shape)} on {z1.device}")
+    return B, Ct // 128, T
+
+
+def _lead_mask_choice(choice, device):
+    """The Standin draws: two ints >= 0, or a device int32[2] tensor (graph replay) -> (c1, c2, device pointer)."""
+    if torch.is_tensor(choice):
+        if choice.dtype != torch.int32 or choice.numel() != 2 or not choice.is_contiguous() or choice.device != device:
+            raise ValueError("choice must be two ints or a contiguous int32 tensor of two elements on the leads' device")
+        return 0, 0, choice.data_ptr()
+    try:
+        c1, c2 = choice
+        if isinstance(c1, bool) or isinstance(c2, bool):
+            raise TypeError
+        c1, c2 = int(c1), int(c2)
+    except (TypeError, ValueError):
+        raise TypeError(f"choice must be two ints or a device int32[2] tensor, got {choice!r}") from None
+    if c1 < 0 or c2 < 0 or c1 > 0x7FFFFFFF or c2 > 0x7FFFFFFF:
+        raise ValueError(f"choice {choice!r}: both draws must be in 0 .. 2^31 - 1")
+    return c1, c2, None
+
+
+def _lead_mask_f32(name, t, shape, device):
+    if not torch.is_tensor(t) or t.dtype != torch.float32:
+        raise TypeError(f"{name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {list(shape)} tensor, got {tuple(t.shape)} with strides {tuple(t.stride())}")
+    if t.device != device:
+        raise ValueError(f"{name} is on {t.device}, the leads on {device}")
+
+
+def lead_mask_mix_fwd(z1, z2r, mask, q, choice=(0, 0), picks=False):
+    """The lead mean and the Standin mixes over each sample's present leads (nef_lead_mask_mix_fwd, include/nefnet_hip.h, defines every
+    element): z1, z2r [B, 128 V, T], mask bool / uint8 [B, V], q [B, 256] -> (latent [B, 256, T], D [3B, 256, T]); `q` None: (latent,
+    None), the inference form.  `choice`: the two Standin draws, ints or a device int32[2] tensor; sample b picks its
+    (draw mod n_b)-th present lead.  picks=True: a third result, int32 [B, 2], the picked leads (-1 without a present lead).  One launch,
+    capturable.  Every argument check sits in front of the library."""
+    B, V, T = _lead_mask_leads(z1, z2r)
+    mask = lead_mask_arg(mask, B, V, z1.device, "mask")
+    if q is not None:
+        _lead_mask_f32("q", q, (B, 256), z1.device)
+    c1, c2, cdev = _lead_mask_choice(choice, z1.device)
+    if not z1.is_cuda:
+        raise RuntimeError("ops.lead_mask_mix_fwd runs on a HIP device only (no CPU path)")
+    L = _lib.load()
+    latent = torch.empty(B, 256, T, device=z1.device, dtype=torch.float32)
+    D = torch.empty(3 * B, 256, T, device=z1.device, dtype=torch.float32) if q is not None else None
+    pk = torch.empty(B, 2, device=z1.device, dtype=torch.int32) if picks else None
+    ev = _hbm("lead_mask_mix_fwd", z1, z2r, latent, D)
+    A = _lib.LeadMaskMixFwdArgs(z1=_p(z1), z2r=_p(z2r), mask=_p(mask), q=_p(q), choice_dev=cdev, latent=_p(latent), D=_p(D), picks=_p(pk),
+                                B=B, V=V, T=T, c1=c1, c2=c2)
+    _lib.check(L.nef_lead_mask_mix_fwd(C.byref(A), _stream()), "nef_lead_mask_mix_fwd")
+    _done(ev)
+    return (latent, D, pk) if picks else (latent, D)
+
+
+def lead_mask_mix_bwd(gD, latent, z1, z2r, q, mask, choice=(0, 0), up=False, relu_z1=False):
+    """The adjoint of lead_mask_mix_fwd (nef_lead_mask_mix_bwd): gD [3B, 256, T] -- [3B, 256, 2T] with `up`, the gradient wrt the
+    x2-upsampled D, whose adjoint is taken while reading -- and the forward's latent, leads, q, mask and draws -> (gz1, gz2r
+    [B, 128 V, T], gq [B, 256]).  Rows of absent leads are zeros.  relu_z1: gz1 also carries the mask z1 > 0.  One launch, capturable,
+    no atomics.  Every argument check sits in front of the library."""
+    B, V, T = _lead_mask_leads(z1, z2r)
+    mask = lead_mask_arg(mask, B, V, z1.device, "mask")
+    _lead_mask_f32("gD", gD, (3 * B, 256, 2 * T if up else T), z1.device)
+    _lead_mask_f32("latent", latent, (B, 256, T), z1.device)
+    _lead_mask_f32("q", q, (B, 256), z1.device)
+    c1, c2, cdev = _lead_mask_choice(choice, z1.device)
+    if not z1.is_cuda:
+        raise RuntimeError("ops.lead_mask_mix_bwd runs on a HIP device only (no CPU path)")
+    L = _lib.load()
+    gz1, gz2r = torch.empty_like(z1), torch.empty_like(z2r)
+    gq = torch.empty(B, 256, device=z1.device, dtype=torch.float32)
+    ev = _hbm("lead_mask_mix_bwd", gD, latent, z1, z2r, gz1, gz2r)
+    A = _lib.LeadMaskMixBwdArgs(gD=_p(gD), latent=_p(latent), z1=_p(z1), z2r=_p(z2r), q=_p(q), mask=_p(mask), choice_dev=cdev,
+                                gz1=_p(gz1), gz2r=_p(gz2r), gq=_p(gq), B=B, V=V, T=T, c1=c1, c2=c2, relu_z1=int(bool(relu_z1)),
+                                up=int(bool(up)))
+    _lib.check(L.nef_lead_mask_mix_bwd(C.byref(A), _stream()), "nef_lead_mask_mix_bwd")
+    _done(ev)
+    return gz1, gz2r, gq
+
+
+def augment_mask(B, V, lead_drop, seed=0, seed_dev=None, device=None, out=None):
+    """uint8 [B, V]: 0 where ops.augment with the same seed, seed_dev and lead_drop zeroes the lead, 1 elsewhere (nef_augment_mask: the
+    decision is one device function shared with nef_augment).  `device`: where the mask lives (taken from `out` or `seed_dev` when None).
+    `out`: a contiguous uint8 [B, V] tensor to fill (the replayed step's static buffer).  One launch, capturable.  Every argument check
+    sits in front of the library."""
+    for name, n in (("B", B), ("V", V)):
+        if isinstance(n, bool) or not isinstance(n, int):
+            raise TypeError(f"{name} must be an int, got {n!r}")
+    if B < 1 or not 1 <= V <= LEAD_MASK_MAX_V or B * V > 0x7FFFFFFF:
+        raise ValueError(f"B = {B}, V = {V}: B >= 1, V in 1..{LEAD_MASK_MAX_V}")
+    if not 0.0 <= float(lead_drop) < 1.0:
+        raise ValueError(f"lead_drop must be in [0, 1), got {lead_drop!r}")
+    if device is None:
+        device = out.device if torch.is_tensor(out) else (seed_dev.device if torch.is_tensor(seed_dev) else None)
+    if device is None:
+        raise ValueError("augment_mask needs a device (or `out` / `seed_dev` to take it from)")
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None and torch.cuda.is_available():
+        device = torch.device("cuda", torch.cuda.current_device())
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != (B, V) or not out.is_contiguous()
+                            or out.device != device):
+        raise ValueError(f"out must be a contiguous uint8 [{B}, {V}] tensor on {device}")
+    if seed_dev is not None and (not torch.is_tensor(seed_dev) or seed_dev.dtype != torch.int64 or seed_dev.numel() != 1
+                                 or seed_dev.device != device):
+        raise ValueError(f"seed_dev must be a one-element int64 tensor on {device}")
+    if device.type != "cuda":
+        raise RuntimeError("ops.augment_mask runs on a HIP device only (no CPU path)")
+    L = _lib.load()
+    mask = torch.empty(B, V, device=device, dtype=torch.uint8) if out is None else out
+    A = _lib.AugmentMaskArgs(mask=_p(mask), seed_dev=_p(seed_dev), seed=int(seed) & 0xFFFFFFFFFFFFFFFF, lead_drop=float(lead_drop), B=B, V=V)
+    _lib.check(L.nef_augment_mask(C.byref(A), _stream()), "nef_augment_mask")
+    return mask
+
+
 def warp(data, target, rest, rois, warp, seed, index0=0):
     """The batch warped in time as cfg.DATA.aug_warp / aug_roi_jitter say (`warp`: warp.from_cfg's Warp; nef_warp, include/nefnet_hip.h,
     defines every step) -> (data, target, rest, rois), all new tensors; no input is written.  `data` [B, V, L], `target` [B, L] or

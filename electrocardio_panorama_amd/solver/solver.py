@@ -187,6 +187,8 @@ class Solver:
         self.model = build_model(cfg).float()
         # DATA.aug_*: the train step corrupts its input leads on the device (augment.py); invalid keys are rejected here.  None = off
         self.augment = self.model.augment = augment.from_cfg(cfg)
+        # MODEL.lead_mask (from_cfg has rejected it without DATA.aug_lead_drop): the train step's head reads the mask of the dropped leads
+        self.lead_mask = self.model.lead_mask_from_aug = augment.lead_mask_on(cfg)
         # DATA.aug_warp / aug_roi_jitter: the train phase warps every batch in time on the device (warp.py); invalid keys are rejected
         # here.  None = off
         self.warp = _warp.from_cfg(cfg)
@@ -672,6 +674,7 @@ class Solver:
                 optim.zero_grad()
             else:
                 rest_view = torch.as_tensor(meta['rest_view']).to(self.device, torch.float32).contiguous()
+                mask_kw = {}                # the clean test phase passes no mask
                 if warp_eval:
                     source_data, target_view, rest_view, rois = self._warp_batch(
                         source_data, target_view, rest_view, rois, _warp.eval_seed(self.cfg.get('seed', 0), n_batches, warp_rank))
@@ -679,8 +682,12 @@ class Solver:
                     rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
                     source_data = ops.augment(source_data.to(torch.float32).contiguous(), rois, self.augment,
                                               seed=augment.eval_seed(self.cfg.get('seed', 0), n_batches, rank))
+                    if self.lead_mask:      # MODEL.lead_mask: the read-out's head is told which leads its own fixed seed dropped
+                        mask_kw = dict(lead_mask=ops.augment_mask(source_data.shape[0], source_data.shape[1], self.augment.lead_drop,
+                                                                  seed=augment.eval_seed(self.cfg.get('seed', 0), n_batches, rank),
+                                                                  device=source_data.device))
                 out, shuf_p, shuf_l, rest_out = self.model(source_data, input_theta, target_theta, rois,
-                                                           rest_theta=rest_theta, phase='test')
+                                                           rest_theta=rest_theta, phase='test', **mask_kw)
                 losses = self.loss(out, shuf_p, shuf_l, target_view, self.cfg, rest_out[:, -4:, :].contiguous(),
                                    rest_view[:, -4:, :].contiguous(), **self._loss_rois(rois))
                 losses_s.add(torch.stack([l_.detach() for l_ in losses]))

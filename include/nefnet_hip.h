@@ -933,6 +933,84 @@ int nef_augment(const nef_augment_args* a, nef_stream_t stream);
 /* sizeof(nef_augment_args) as the library was built. */
 size_t nef_augment_args_bytes(void);
 
+/* Lead masks (cfg.MODEL.lead_mask; no counterpart in the reference): the lead mean and the Standin picks over each sample's PRESENT
+ * leads.  `mask` is uint8 [B][V] on the device, read as zero / non-zero.  For sample b: P_b = the ascending list of v with
+ * mask[b][v] != 0, n_b = |P_b|.
+ *   mean    per channel row and position: s = lead P_b[0]; s += lead P_b[k] for k = 1 .. n_b - 1, in that order, fp32;
+ *           mean = s / (float)n_b  (nef_lead_mean's expression with n_b for V: an all-ones mask gives its bits).
+ *   picks   with the step's two Standin draws (c1, c2) (the two ints, or choice_dev[0..1]): p1_b = P_b[c1 mod n_b],
+ *           p2_b = P_b[c2 mod n_b] (the draws are read as unsigned).  All ones: c1, c2.
+ *   D       [3B][256][T] as nef_mix_fwd builds it, one rounded multiply per element: pass 0 = q * latent,
+ *           pass 1 = q * cat(z1[p1_b] | z2 mean), pass 2 = q * cat(z1 mean | z2r[p2_b]).
+ *   absent leads are never read (a select, not a multiply by 0): a NaN in their rows reaches no output.
+ *   n_b = 0: latent and the three D rows of the sample are +0.0, its picks are -1, its backward rows (gz1, gz2r, gq) are +0.0; no
+ *           flag, nothing read by the host.
+ *   backward  the adjoint of the above with nef_mix_bwd(shared = 0)'s expressions in their order and n_b for V:
+ *           g_mean = gD0 + gD2 (z1 half) or gD0 + gD1 (z2 half), g_pick = gD1 or gD2;  gz[v] = q * g_mean / (float)n_b
+ *           + (v == pick ? q * g_pick : 0) for present v -- masked with z1 > 0 on the z1 half when relu_z1 -- and +0.0 for absent v
+ *           (every row of gz1 / gz2r is written);  gq[b][c] = sum_t (g_mean * latent + g_pick * z[pick]) in fp32, one wave per row.
+ *           up != 0: gD is [3B][256][2T], read through the x2-upsampling adjoint exactly as nef_mix_bwd reads it.
+ * One wave per (sample, channel) row; the mask row is decoded once per row into a wave-uniform bit set of present leads, which the
+ * lead loop walks with scalar instructions: no per-element branch on v.  With every pointer 16-byte aligned a row is cut into an
+ * unaligned head of up to three elements, 16-byte accesses and a tail (every tensor's row has the same offset modulo 16 bytes);
+ * otherwise 4-byte accesses.  The same expressions per element on every path.  One writer per element, no atomics, no scratch, no
+ * state: the same bits from run to run, eagerly and under hipGraph replay.
+ * nef_lead_mask_mix_fwd: q == NULL and D == NULL together: the latent only (inference).  picks: NULL, or int32 [B][2].
+ * args or a required pointer NULL, q NULL without D NULL (or the reverse): NEF_E_NULL; B < 1, V outside 1..12, T outside 1..2^24,
+ * B * 256 * 3 * 2 * T >= 2^62, c1 or c2 negative: NEF_E_SHAPE; a float or int32 pointer not 4-byte aligned: NEF_E_UNSUPPORTED.  Every check
+ * sits in front of the launch.  Capturable. */
+#define NEF_LEAD_MASK_MAX_V 12
+typedef struct nef_lead_mask_mix_fwd_args {
+    const float* z1;            /* [B][128V][T] */
+    const float* z2r;           /* [B][128V][T] */
+    const uint8_t* mask;        /* [B][V] */
+    const float* q;             /* [B][256], or NULL with D NULL */
+    const int32_t* choice_dev;  /* NULL, or device {c1, c2} that overrides the two ints */
+    float* latent;              /* [B][256][T] */
+    float* D;                   /* [3B][256][T], or NULL with q NULL */
+    int32_t* picks;             /* NULL, or [B][2] = {p1_b, p2_b} */
+    int32_t B, V, T;
+    int32_t c1, c2;             /* >= 0 */
+    int32_t reserved0;          /* 0 */
+} nef_lead_mask_mix_fwd_args;
+int nef_lead_mask_mix_fwd(const nef_lead_mask_mix_fwd_args* a, nef_stream_t stream);
+size_t nef_lead_mask_mix_fwd_args_bytes(void);
+
+typedef struct nef_lead_mask_mix_bwd_args {
+    const float* gD;            /* [3B][256][T], or [3B][256][2T] with up */
+    const float* latent;        /* [B][256][T], the forward's */
+    const float* z1;            /* [B][128V][T] */
+    const float* z2r;           /* [B][128V][T] */
+    const float* q;             /* [B][256] */
+    const uint8_t* mask;        /* [B][V] */
+    const int32_t* choice_dev;  /* as in the forward */
+    float* gz1;                 /* [B][128V][T] */
+    float* gz2r;                /* [B][128V][T] */
+    float* gq;                  /* [B][256] */
+    int32_t B, V, T;
+    int32_t c1, c2;
+    int32_t relu_z1;            /* != 0: gz1 also carries the mask z1 > 0 */
+    int32_t up;                 /* != 0: gD is wrt the x2-upsampled D */
+    int32_t reserved0;          /* 0 */
+} nef_lead_mask_mix_bwd_args;
+int nef_lead_mask_mix_bwd(const nef_lead_mask_mix_bwd_args* a, nef_stream_t stream);
+size_t nef_lead_mask_mix_bwd_args_bytes(void);
+
+/* mask[b][v] = 0 where nef_augment with the same (seed, seed_dev, lead_drop, B, V) zeroes row (b, v), 1 elsewhere: the row draw, the
+ * "all dropped" test and the fallback lead are ONE device function shared with nef_augment (csrc/aug_drop.h).  lead_drop == 0: all
+ * ones.  One thread per (b, v).  args or mask NULL: NEF_E_NULL; B < 1, V outside 1..12, B * V >= 2^31, lead_drop outside [0, 1) or
+ * NaN: NEF_E_SHAPE.  Capturable. */
+typedef struct nef_augment_mask_args {
+    uint8_t* mask;              /* [B][V] */
+    const uint64_t* seed_dev;   /* NULL, or a device word added to seed when the launch runs */
+    uint64_t seed;
+    float lead_drop;            /* in [0, 1) */
+    int32_t B, V;
+    int32_t reserved0;          /* 0 */
+} nef_augment_mask_args;
+int nef_augment_mask(const nef_augment_mask_args* a, nef_stream_t stream);
+size_t nef_augment_mask_args_bytes(void);
+
 /* Time warp of a whole train batch with jittered marks (cfg.DATA.aug_warp / aug_roi_jitter; no counterpart in the reference): every
  * segment of every beat is resampled to a drawn multiple of its length -- inputs, target and rest views alike -- and the marks follow,
  * each interior one then moved by a drawn integer.  Out of place; no input is written.  Per sample i, with L the row length and

@@ -10,6 +10,7 @@
     python tools/bench_adam.py --ssim F [--parent-tree DIR] [--out profiles/r15_ssim_bench_line.json]
     python tools/bench_adam.py --views Q [Q ...] [--parent-tree DIR] [--out profiles/r16_views_bench_line.json]
     python tools/bench_adam.py --augment [--parent-tree DIR] [--out profiles/r17_augment_bench_line.json]
+    python tools/bench_adam.py --augment --lead-mask [--parent-tree DIR] [--out profiles/r28_lead_mask_bench_line.json]
     python tools/bench_adam.py --seg W0 W1 W2 W3 W4 W5 W6 [--parent-tree DIR] [--out profiles/r18_seg_bench_line.json]
     python tools/bench_adam.py --slope F [--parent-tree DIR] [--out profiles/r19_slope_bench_line.json]
     python tools/bench_adam.py --corr F [--parent-tree DIR] [--out profiles/r20_corr_bench_line.json]
@@ -79,6 +80,12 @@ FusedSGD step with the keys off (sgd-graph: the parent's code path) and with all
 aug_wander_amp 0.2, aug_hum_amp 0.1, aug_lead_drop 0.1, aug_crop true), and -- with --parent-tree DIR -- DIR's own sgd-graph step.  The
 config-2 child with the keys on also times the nef_augment launch alone on the batch's inputs and rois, cold.  Writes
 profiles/r17_augment_bench_line.json unless --out says otherwise.
+
+--augment --lead-mask adds the masked head (MODEL.lead_mask, which needs --augment's aug_lead_drop) as a third child per round and shape
+(sgd-graph-lead-mask: the same four corruptions, the head over the present leads on the un-fused three-pass route).  The config-2 child
+with the key on also times the two mix entries alone, cold, beside the launches they stand in for: nef_lead_mask_mix_fwd against
+nef_lead_mean + nef_mix_fwd, nef_lead_mask_mix_bwd against nef_mix_bwd (three passes, gradient at the latent's resolution).  Writes
+profiles/r28_lead_mask_bench_line.json unless --out says otherwise.
 
 --seg W0 .. W6 measures the wave-segment weights of the reconstruction term (SOLVER.seg_weights = [P, PR, QRS, ST, T, TP, pad]), at the
 same two shapes: per round and shape the graphed FusedSGD step with the key off (sgd-graph: the parent's code path) and on (sgd-graph-seg),
@@ -159,9 +166,11 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
     cfg.DATA.lead_num = V
     if mode == "sgd-graph-ssim":
         cfg.SOLVER.ssim_factor, cfg.SOLVER.ssim_crop = float(ssim), True
-    if mode == "sgd-graph-augment":
+    if mode in ("sgd-graph-augment", "sgd-graph-lead-mask"):
         for k, v in AUGMENT_KEYS.items():
             cfg.DATA[k] = v
+    if mode == "sgd-graph-lead-mask":
+        cfg.MODEL.lead_mask = True
     if mode == "sgd-graph-seg":
         cfg.SOLVER.seg_weights = [float(w) for w in seg]
     if mode == "sgd-graph-warp":
@@ -176,7 +185,7 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
     model = build_model(cfg).float().to(dev).train()
     lossf = build_loss(cfg)
     if mode in ("sgd-graph", "sgd-graph-ssim", "sgd-graph-views", "sgd-graph-augment", "sgd-graph-seg", "sgd-graph-slope", "sgd-graph-corr",
-                "sgd-graph-warp"):
+                "sgd-graph-warp", "sgd-graph-lead-mask"):
         optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9)
     elif mode == "sgd-graph-clip":
         optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9, max_grad_norm=clip)
@@ -313,6 +322,20 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
         y = torch.empty_like(data)
         ms = cold_ms([lambda: ops.augment(data, rois, graphed.augment, seed=_augment.train_seed(1), out=y)], dev)[0]
         res.update(nef_augment_cold_ms=round(ms, 4), nef_augment_cold_GBps=round(2 * 4 * data.numel() / (ms * 1e-3) / 1e9, 1))
+    if mode == "sgd-graph-lead-mask":
+        res.update(augment=dict(AUGMENT_KEYS), loss_row=[round(float(v), 6) for v in graphed.losses.tolist()],
+                   leads_masked=round(float((graphed.lead_mask == 0).float().mean().item()), 4))
+    if mode == "sgd-graph-lead-mask" and (B, L) == EMA_SHAPES["config2"]:
+        T = L // 4
+        z1, z2r = torch.randn(B, 128 * V, T, device=dev), torch.randn(B, 128 * V, T, device=dev)
+        q, gD = torch.randn(B, 256, device=dev), torch.randn(3 * B, 256, T, device=dev)
+        mask, c = graphed.lead_mask, (1, 2)
+        latent = ops.lead_mean(z1, z2r, V)
+        ms = cold_ms([lambda: ops.lead_mask_mix_fwd(z1, z2r, mask, q, c),
+                      lambda: ops.mix_fwd(ops.lead_mean(z1, z2r, V), z1, z2r, q, V, c),
+                      lambda: ops.lead_mask_mix_bwd(gD, latent, z1, z2r, q, mask, c, relu_z1=True),
+                      lambda: ops.mix_bwd(gD, latent, z1, z2r, q, V, c, relu_z1=True)], dev)
+        res.update(mix_cold_ms=dict(zip(("lead_mask_mix_fwd", "lead_mean_plus_mix_fwd", "lead_mask_mix_bwd", "mix_bwd"), [round(m_, 4) for m_ in ms])))
     if mode == "sgd-graph-warp":
         d0, r0 = warped[0]
         res.update(aug_warp=[float(a) for a in warp], aug_roi_jitter=int(roi_jitter), loss_row=[round(float(v), 6) for v in graphed.losses.tolist()],
@@ -690,7 +713,8 @@ def ssim_rounds(args):
 
 def augment_rounds(args):
     """--augment: `--reps` alternating rounds of fresh children per shape (see the module docstring); prints and writes one JSON line."""
-    modes = dict({"sgd-graph": 900, "sgd-graph-augment": 900}, **({"parent": 900} if args.parent_tree else {}))
+    modes = dict({"sgd-graph": 900, "sgd-graph-augment": 900}, **({"sgd-graph-lead-mask": 900} if args.lead_mask else {}),
+                 **({"parent": 900} if args.parent_tree else {}))
     results = {(shape, mode): [] for shape in EMA_SHAPES for mode in modes}
     for rnd in range(args.reps):
         order = list(modes) if rnd % 2 == 0 else list(reversed(modes))
@@ -727,6 +751,16 @@ def augment_rounds(args):
             # to be read against each other: the keys-off median and the parent's own min-max spread; the bar with the keys on: + 0.3 ms
             out[shape + "_augment_off_median_inside_parent_spread"] = par[0] <= out[shape + "_augment_off_ms"][1] <= par[2]
             out[shape + "_augment_on_median_minus_parent_median_ms"] = round(out[shape + "_augment_on_ms"][1] - par[1], 3)
+            out[shape + "_augment_off_median_minus_parent_median_ms"] = round(out[shape + "_augment_off_ms"][1] - par[1], 3)
+        if args.lead_mask:
+            out[shape + "_lead_mask_on_ms"] = on = spread(shape, "sgd-graph-lead-mask", "ms_per_step")
+            out[shape + "_leads_masked"] = spread(shape, "sgd-graph-lead-mask", "leads_masked")[1]
+            out[shape + "_lead_mask_over_augment_median"] = round(on[1] / out[shape + "_augment_on_ms"][1], 4)
+    if args.lead_mask:
+        cold = [x["mix_cold_ms"] for x in results[("config2", "sgd-graph-lead-mask")]]
+        out.update(lead_mask=True, mix_cold_ms={k: sorted(c[k] for c in cold)[len(cold) // 2] for k in cold[0]},
+                   mix_note="medians over the rounds; the two mix entries alone at config 2 (a mask with aug_lead_drop's share of leads "
+                            "absent) beside nef_lead_mean + nef_mix_fwd and nef_mix_bwd(shared = 0, up = 0), cold")
     out.update(nef_augment_cold_ms=spread("config2", "sgd-graph-augment", "nef_augment_cold_ms"),
                nef_augment_cold_GBps=spread("config2", "sgd-graph-augment", "nef_augment_cold_GBps"),
                launch_note="the nef_augment launch alone at config 2 on the batch's inputs and rois, all four corruptions on; cold = a 512 MiB "
@@ -734,7 +768,8 @@ def augment_rounds(args):
                steps=args.steps, warmup=args.warmup)
     line = json.dumps(out)
     print(line)
-    with open(args.out or os.path.join(ROOT, "profiles", "r17_augment_bench_line.json"), "w") as f:
+    default = "r28_lead_mask_bench_line.json" if args.lead_mask else "r17_augment_bench_line.json"
+    with open(args.out or os.path.join(ROOT, "profiles", default), "w") as f:
         f.write(line + "\n")
 
 
@@ -1104,6 +1139,7 @@ def main():
     ap.add_argument("--views", type=int, nargs="+", default=None, metavar="Q",
                     help="measure SOLVER.train_views = Q for every Q given (see above); with --child sgd-graph-views: the one Q")
     ap.add_argument("--augment", action="store_true", help="measure the input-lead augmentation of the train step, DATA.aug_* (see above)")
+    ap.add_argument("--lead-mask", action="store_true", help="with --augment: also measure the masked head, MODEL.lead_mask (see above)")
     ap.add_argument("--seg", type=float, nargs=7, default=None, metavar="W",
                     help="measure the wave-segment weights of the reconstruction term, SOLVER.seg_weights = W0 .. W6 (see above)")
     ap.add_argument("--slope", type=float, default=None, metavar="F", help="measure the slope term of the loss, slope_factor = F (see above)")
@@ -1116,7 +1152,7 @@ def main():
     ap.add_argument("--parent-tree", default=None,
                     help="with --clip / --weight-decay / --ema: a built checkout whose own sgd-graph child runs in every round")
     ap.add_argument("--child", choices=sorted({**MODES, **CLIP_MODES, **WD_MODES, **EMA_MODES, "lars-graph": 900, "lamb-graph": 900, "sgd-graph-accum": 900,
-                                             "sgd-graph-sched": 900, "sgd-graph-ssim": 900, "sgd-graph-views": 900, "sgd-graph-augment": 900,
+                                             "sgd-graph-sched": 900, "sgd-graph-ssim": 900, "sgd-graph-views": 900, "sgd-graph-augment": 900, "sgd-graph-lead-mask": 900,
                                              "sgd-graph-seg": 900, "sgd-graph-slope": 900, "sgd-graph-corr": 900, "sgd-graph-warp": 900}),
                     default=None)
     args = ap.parse_args()
@@ -1158,6 +1194,8 @@ def main():
                                             or args.ema is not None or args.trust is not None or args.accum is not None
                                             or args.sched is not None or args.ssim is not None):
         ap.error("--augment is a measurement of its own")
+    if args.lead_mask and not args.child and not args.augment:
+        ap.error("--lead-mask goes with --augment: MODEL.lead_mask needs its aug_lead_drop")
     if args.seg is not None and not args.child and (args.augment or args.views is not None or args.clip is not None
                                                     or args.weight_decay is not None or args.ema is not None or args.trust is not None
                                                     or args.accum is not None or args.sched is not None or args.ssim is not None):
