@@ -185,6 +185,18 @@ class RecordingStatsArgs(C.Structure):
                 ("reserved0", i32)]
 
 
+class MarkEnvelopeArgs(C.Structure):
+    """Mirror of `nef_mark_envelope_args` (include/nefnet_hip.h)."""
+    _fields_ = [("signal", p), ("table", p), ("env", p), ("signal_elems", i64), ("env_elems", i64), ("max_len", i64), ("N", i32), ("D", i32),
+                ("H", i32), ("lead_bits", i32), ("dtype", i32), ("reserved0", i32)]
+
+
+class MarkPeaksArgs(C.Structure):
+    """Mirror of `nef_mark_peaks_args` (include/nefnet_hip.h)."""
+    _fields_ = [("env", p), ("table", p), ("peaks", p), ("count", p), ("level", p), ("env_elems", i64), ("max_len", i64),
+                ("frac", C.c_double), ("N", i32), ("seg", i32), ("r", i32), ("max_peaks", i32)]
+
+
 class PackDesc(C.Structure):
     """Mirror of `nef_pack_desc` (include/nefnet_hip.h)."""
     _fields_ = [("w", p), ("wp", p), ("G", i32), ("Cog", i32), ("Cig", i32), ("K", i32), ("transpose_flip", i32),
@@ -312,6 +324,10 @@ SIGNATURES = {
     "nef_beat_stitch_args_bytes": (sz, []),
     "nef_recording_stats": (i32, [C.POINTER(RecordingStatsArgs), p]),
     "nef_recording_stats_args_bytes": (sz, []),
+    "nef_mark_envelope": (i32, [C.POINTER(MarkEnvelopeArgs), p]),
+    "nef_mark_envelope_args_bytes": (sz, []),
+    "nef_mark_peaks": (i32, [C.POINTER(MarkPeaksArgs), p]),
+    "nef_mark_peaks_args_bytes": (sz, []),
     "nef_sgd_momentum": (i32, [p, p, p, i64, f32, f32, f32, i32, p, p, p, p]),
     "nef_adam": (i32, [p, p, p, p, i64, f32, C.c_double, C.c_double, f32, f32, f32, p, p, p, p, p]),
     "nef_update": (i32, [C.POINTER(UpdateArgs), p]),
@@ -399,7 +415,9 @@ def load():
                                ("nef_beat_batch_args", lib.nef_beat_batch_args_bytes(), BeatBatchArgs),
                                ("nef_beat_range_args", lib.nef_beat_range_args_bytes(), BeatRangeArgs),
                                ("nef_beat_stitch_args", lib.nef_beat_stitch_args_bytes(), BeatStitchArgs),
-                               ("nef_recording_stats_args", lib.nef_recording_stats_args_bytes(), RecordingStatsArgs)):
+                               ("nef_recording_stats_args", lib.nef_recording_stats_args_bytes(), RecordingStatsArgs),
+                               ("nef_mark_envelope_args", lib.nef_mark_envelope_args_bytes(), MarkEnvelopeArgs),
+                               ("nef_mark_peaks_args", lib.nef_mark_peaks_args_bytes(), MarkPeaksArgs)):
         if size != C.sizeof(mirror):
             raise NefLibraryError(f"{LIB_PATH}: {name} is {size} bytes, the binding mirrors {C.sizeof(mirror)}; rebuild with "
                                   "`python -m electrocardio_panorama_amd.csrc.build`")

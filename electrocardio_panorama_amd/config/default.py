@@ -57,6 +57,16 @@ _DEFAULTS = {
         # different random stream from the host's), every dataset but tianchi (PTB), DATA.weighted_sample, DATA.synthetic.
         # False: the DataLoaders, launches and bits are what they were before the key existed
         "device_resident": False,
+        # (not in the reference) with device_resident: the store reads the SIGNALS of the label list's recordings only -- no <id>.json is
+        # opened -- and makes the six 'P on' .. 'T off' lists itself: a QRS detector on the device (nef_mark_envelope, nef_mark_peaks) and
+        # the timing table of mark_table, which `python -m electrocardio_panorama_amd.mark_net --fit` fits on an annotated list
+        # (dataset/marks.py).  Rejected without device_resident -- `mark_net --write` writes label files for the host
+        # loader -- and DATA.weighted_sample stays rejected.  False: no launch, no buffer, the loaders, graphs and bits are what they were
+        # before the key existed
+        "auto_marks": False,
+        "mark_table": "",              # the JSON table file; required with auto_marks
+        # a recording that gets no labels (fewer than two beats left) is an error; True: it is dropped from the store, one warning counts them
+        "auto_marks_skip": False,
     },
     "MODEL": {
         "model": "modelv2",            # 'model_nefnet' selects Nef-Net

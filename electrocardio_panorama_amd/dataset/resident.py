@@ -8,7 +8,9 @@ stored values.  `ResidentLoader` is the iterable of `meta` dicts the Solver cons
 
 Left out on this path, and rejected where the key is read: DATA.noise (it needs the quiet segment's sigma and a device draw, a different
 random stream from the host's), DATA.weighted_sample, DATA.synthetic and every dataset but tianchi (PTB)."""
+import os
 import random
+import warnings
 from concurrent.futures import ThreadPoolExecutor
 from typing import NamedTuple
 
@@ -16,6 +18,7 @@ import numpy as np
 import torch
 
 from ..synth import LEAD_THETA
+from . import marks
 from .tianchi import BEAT_LEN, EcgTianChiInterval, _lead_plan
 
 LABEL_KEYS = ('P on', 'P off', 'R on', 'R off', 'T on', 'T off')
@@ -33,6 +36,7 @@ def check_cfg(cfg):
         raise ValueError("DATA.device_resident with DATA.weighted_sample: the weighted draw is not planned on this path")
     if cfg.DATA.get('synthetic', False):
         raise ValueError("DATA.device_resident with DATA.synthetic: synthetic batches have no recordings to keep on the device")
+    marks.check_cfg(cfg)                                   # DATA.auto_marks needs DATA.mark_table
 
 
 def _pack(name, sig):
@@ -61,15 +65,29 @@ class ResidentTianchi:
     labels[k]     the six 'P on' .. 'T off' index lists, each concatenated over the recordings (host numpy int64, never on the device),
                   recording i at [label_offsets[k][i], label_offsets[k][i + 1])
     names         the label list's lines (the `id` of a sample)
-    `device` None or 'cpu' keeps `signal` on the host (packing only: ops.beat_batch has no CPU path)."""
+    `device` None or 'cpu' keeps `signal` on the host (packing only: ops.beat_batch has no CPU path).
 
-    def __init__(self, cfg, phase, device=None):
+    `marks` (or cfg.DATA.auto_marks, which reads cfg.DATA.mark_table): the signals alone are read -- no label file is opened -- and the
+    six lists are made on the device from a timing table (dataset/marks.py: detect, labels_from_peaks).  `marks` is a [6, 2] table, a
+    (table, MarkParams) pair or the path of a table file; it needs a HIP `device`.  A recording that gets no labels raises a ValueError
+    naming it; with cfg.DATA.auto_marks_skip it is dropped from `names` and counted in one warning.  `auto_report` holds the counts
+    (None on an annotated store)."""
+
+    def __init__(self, cfg, phase, device=None, marks=None):
         ds = EcgTianChiInterval(cfg, phase)
         self.cfg, self.phase, self.names = cfg, phase, list(ds.dataset)
+        self.auto_report = None
         if not self.names:
             raise ValueError(f"DATA.device_resident: the {phase} label list is empty")
+        spec = marks
+        if spec is None and cfg.DATA.get('auto_marks', False):
+            spec = cfg.DATA.get('mark_table', '')
+            if not spec:
+                raise ValueError("DATA.auto_marks needs DATA.mark_table: the JSON timing table `mark_net --fit` writes")
 
         def read(name):
+            if spec is not None:
+                return _pack(name, ds._load_signal(name)), None
             sig, label = ds._load(name)
             lab = [np.asarray(label[k], dtype=np.int64).reshape(-1) for k in LABEL_KEYS]
             self._check_labels(name, lab, sig.shape[-1])
@@ -85,9 +103,49 @@ class ResidentTianchi:
         flat = torch.from_numpy(np.concatenate([s.reshape(-1) for s in sigs]))
         dev = torch.device('cpu' if device is None else device)
         self.signal = flat if dev.type == 'cpu' else flat.to(dev)
+        if spec is not None:
+            self._auto_mark(spec, bool(cfg.DATA.get('auto_marks_skip', False)))
+            return
         self.labels = [np.concatenate([lab[k] for _, lab in items]) for k in range(6)]
         self.label_offsets = [np.concatenate([[0], np.cumsum([lab[k].size for _, lab in items])]).astype(np.int64) for k in range(6)]
         self.n_p_on = np.diff(self.label_offsets[0])
+
+    def _auto_mark(self, spec, skip):
+        """Fill labels, label_offsets and n_p_on from the signals (dataset/marks.py); recordings without labels raise, or leave with `skip`."""
+        if isinstance(spec, (str, os.PathLike)):
+            table, _, params = marks.load_table(spec)
+        elif isinstance(spec, tuple) and len(spec) == 2 and isinstance(spec[1], marks.MarkParams):
+            table, params = spec
+        else:
+            table, params = spec, marks.MarkParams()
+        table = marks._check_table(table)
+        found = marks.detect(self, params=params)
+        lab = marks.labels_from_peaks(found.peaks, found.count, self.lengths, table)
+        beats = np.diff(lab.label_offsets[0])
+        bare = np.flatnonzero(beats < 2)
+        report = {'recordings': len(self.names), 'marked': len(self.names) - bare.size, 'skipped': [self.names[i] for i in bare.tolist()],
+                  'peaks': int(np.maximum(found.count, 0).sum()), 'dropped': int(lab.dropped.sum()), 'adjusted': int(lab.adjusted.sum())}
+        labels, offsets = lab.labels, lab.label_offsets
+        if bare.size:
+            if not skip:
+                i = int(bare[0])
+                raise ValueError(f"recording {self.names[i]}: no labels from its {int(found.count[i])} detected peaks ({bare.size} of "
+                                 f"{len(self.names)} recordings have none; DATA.auto_marks_skip drops them)")
+            keep = np.flatnonzero(beats >= 2)
+            if not keep.size:
+                raise ValueError(f"DATA.auto_marks: none of the {len(self.names)} recordings of the {self.phase} list got labels")
+            warnings.warn(f"DATA.auto_marks_skip: {bare.size} of {len(self.names)} recordings of the {self.phase} list got no labels and "
+                          f"were dropped (first: {self.names[int(bare[0])]})")
+            self.signal = torch.cat([self.signal[self.offsets[i]:self.offsets[i + 1]] for i in keep.tolist()])
+            self.names = [self.names[i] for i in keep.tolist()]
+            self.lengths = self.lengths[keep]
+            self.offsets = np.concatenate([[0], np.cumsum(8 * self.lengths)]).astype(np.int64)
+            offsets = [np.concatenate([[0], np.cumsum(beats[keep])]).astype(np.int64) for _ in range(6)]      # bare recordings hold no marks
+        self.labels, self.label_offsets = labels, offsets
+        self.n_p_on = np.diff(self.label_offsets[0])
+        for i, name in enumerate(self.names):
+            self._check_labels(name, [self.labels[k][offsets[k][i]:offsets[k][i + 1]] for k in range(6)], int(self.lengths[i]))
+        self.auto_report = report
 
     @staticmethod
     def _check_labels(name, lab, length):
@@ -306,7 +364,7 @@ class ResidentLoader:
 
 def build_loader(cfg, phase, batch_size, device, rank=0, world=1):
     """The ResidentLoader of `phase` as train_net.build_loaders hands it out: `batch_size` is this rank's share; only the train phase is
-    sharded and shuffled."""
+    sharded and shuffled.  DATA.auto_marks: the store marks its recordings itself (ResidentTianchi)."""
     check_cfg(cfg)
     store = ResidentTianchi(cfg, phase, device)
     if phase == 'train':

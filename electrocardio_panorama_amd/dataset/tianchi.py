@@ -109,6 +109,14 @@ class EcgTianChiInterval:
         with open(os.path.join(self.label_dir, name)) as f:
             return sig, json.load(f)
 
+    def _load_signal(self, name):
+        """The recording alone: `.npz` with `signal`, or `.npy`.  No label file is opened (dataset/marks.py makes the labels)."""
+        stem = name.replace('.json', '')
+        npz = os.path.join(self.data_root, stem + '.npz')
+        if os.path.exists(npz):
+            return np.load(npz)['signal'].astype(np.float64)
+        return np.load(os.path.join(self.data_root, stem + '.npy')).astype(np.float64)
+
     def __getitem__(self, index):
         sig, label = self._load(self.dataset[index])
         lead_i, lead_ii = sig[0:1], sig[1:2]

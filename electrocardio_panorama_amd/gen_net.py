@@ -1,10 +1,11 @@
 """`python -m electrocardio_panorama_amd.gen_net --config-file config/nef_net.yml [--epoch N] [--leads I ...] [--fill bridge] [--out DIR]
-[--phase test]` -- no counterpart in the reference: synthesise every recording of the phase's label list as a whole 12-lead strip on its
-own time axis and in its own units (recording.synthesize) from the leads the model takes as inputs, and print RMSE and correlation per
+[--phase test] [--auto-marks TABLE.json]` -- no counterpart in the reference: synthesise every recording of the phase's label list as a
+whole 12-lead strip on its own time axis and in its own units (recording.synthesize) from the leads the model takes as inputs, and print RMSE and correlation per
 recording and lead, averaged: rec_rmse_reg / rec_corr_reg over the input leads, rec_rmse_gen / rec_corr_gen over the others.  The
 checkpoint is `best_valid.pkl` (or `epoch_N.pkl`), with the averaged weights under SOLVER.ema_eval as Solver.val takes them.  `--out`
 writes `<id>.npy` ([12, len] float32) per recording and one `metrics.json`.  Without `--leads` the input leads are those of the
-configured lead scheme; the random 3-lead mode has no fixed ones and asks for `--leads`."""
+configured lead scheme; the random 3-lead mode has no fixed ones and asks for `--leads`.  `--auto-marks TABLE.json` builds the store from
+the signals alone: the beats are marked on the device with that timing table (dataset/marks.py), no label file is read."""
 import argparse
 import json
 import os
@@ -35,7 +36,7 @@ def _mean(a):
     return float(np.mean(a)) if a.size else float('nan')
 
 
-def main(cfg, epoch=-1, leads=None, fill='nan', out_dir=None, phase='test', beats_per_pass=256):
+def main(cfg, epoch=-1, leads=None, fill='nan', out_dir=None, phase='test', beats_per_pass=256, auto_marks=None):
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 or (torch.distributed.is_available() and torch.distributed.is_initialized()
                                                       and torch.distributed.get_world_size() > 1):
         raise NotImplementedError("gen_net runs on one rank: the recordings are not sharded")
@@ -51,7 +52,10 @@ def main(cfg, epoch=-1, leads=None, fill='nan', out_dir=None, phase='test', beat
     extra = ckpt.load(best_valid=True, ema=ema) if epoch == -1 else \
         ckpt.load(os.path.join(solver.output_dir, 'epoch_{}.pkl'.format(epoch)), ema=ema)
     print('the latest best_test_psnr_gen is {:06f} of epoch {}'.format(extra.get('best_test_psnr_gen', 0.), extra.get('epoch', 0)))
-    store = ResidentTianchi(cfg, phase, solver.device)
+    store = ResidentTianchi(cfg, phase, solver.device, marks=auto_marks)       # None: annotated, or marked as DATA.auto_marks says
+    if store.auto_report is not None:
+        print('auto marks: {marked} of {recordings} recordings marked, {dropped} of {peaks} peaks dropped, {adjusted} marks adjusted'.format(
+            **store.auto_report))
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
     rmse, corr = [], []
@@ -84,6 +88,7 @@ def run(argv=None):
     parser.add_argument('--fill', default='nan', choices=('nan', 'bridge'), help="positions of a beat behind its 512-sample row")
     parser.add_argument('--out', default=None, metavar="DIR", help="write <id>.npy per recording and metrics.json here")
     parser.add_argument('--phase', default='test', choices=('train', 'test'))
+    parser.add_argument('--auto-marks', default=None, metavar="TABLE.json", help="mark the recordings on the device with this timing table")
     parser.add_argument('opts', nargs=argparse.REMAINDER, help="KEY VALUE overrides")
     args = parser.parse_args(argv)
     if args.config_file != '':
@@ -92,7 +97,7 @@ def run(argv=None):
         cfg.merge_from_list(args.opts)
     cfg.desc = args.config_file.split('/')[-1].replace('.yml', '') or cfg.desc
     cfg.output_dir = os.path.join(cfg.output_dir, cfg.desc)
-    return main(cfg, epoch=args.epoch, leads=args.leads, fill=args.fill, out_dir=args.out, phase=args.phase)
+    return main(cfg, epoch=args.epoch, leads=args.leads, fill=args.fill, out_dir=args.out, phase=args.phase, auto_marks=args.auto_marks)
 
 
 if __name__ == '__main__':

@@ -2318,6 +2318,105 @@ def recording_stats(out, signal, beat_table, rec_table, score_leads, fill, out_o
     return stats
 
 
+MARK_TILE = 1024          # NEF_MARK_TILE (include/nefnet_hip.h): positions per workgroup of nef_mark_envelope
+MARK_MAX_D, MARK_MAX_H, MARK_MAX_R, MARK_MAX_SEGMENTS = 4096, 256, 512, 4096
+MARK_MAX_ROWS = 65535     # the rows are a grid's y extent
+MARK_MAX_LEN = 0x7FFF0000
+MARK_MAX_PEAKS = 1 << 20
+
+
+def _mark_int(name, v, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+        raise ValueError(f"{name} = {v!r}: an integer in {lo}..{hi}")
+    return v
+
+
+def _mark_table(table, dev, max_len, env_elems, signal_elems=None, max_rows=None):
+    """The (offset, len, env_offset) table of the two mark entries on `dev`, and the launch's max_len.  A host table is checked row by row
+    against the buffers here, and gives max_len; a device table is taken as it is (the kernels answer a bad row themselves) and needs
+    max_len from the caller."""
+    if not torch.is_tensor(table) or table.dtype != torch.int64:
+        raise TypeError(f"table must be an int64 tensor, got {getattr(table, 'dtype', type(table))}")
+    if table.dim() != 2 or table.shape[1] != 3 or table.shape[0] < 1 or not table.is_contiguous():
+        raise ValueError(f"table {tuple(table.shape)} is not a contiguous [rows >= 1, 3] table of (offset, len, env_offset)")
+    if max_rows is not None and table.shape[0] > max_rows:
+        raise ValueError(f"table has {table.shape[0]} rows; a launch takes at most {max_rows}")
+    if table.is_cuda:
+        if table.device != dev:
+            raise ValueError(f"table is on {table.device}, not on {dev}")
+        if max_len is None:
+            raise ValueError("a device table needs max_len: the launch is sized on the host")
+        return table, _mark_int("max_len", max_len, 1, MARK_MAX_LEN)
+    off, ln, eoff = table[:, 0], table[:, 1], table[:, 2]
+    bad = (ln < 1) | (ln > MARK_MAX_LEN) | (eoff < 0) | (eoff + ln > env_elems)
+    if signal_elems is not None:
+        bad = bad | (off < 0) | (off + 8 * ln > signal_elems)
+    if max_len is not None:
+        bad = bad | (ln > _mark_int("max_len", max_len, 1, MARK_MAX_LEN))
+    if bool(bad.any()):
+        i = int(bad.nonzero()[0, 0])
+        raise ValueError(f"table row {i} {table[i].tolist()} leaves the signal ({signal_elems} elements), the envelope ({env_elems}) or max_len {max_len}")
+    return table.to(dev, non_blocking=True), int(ln.max()) if max_len is None else max_len
+
+
+def _check_env(env, dev):
+    if not torch.is_tensor(env) or env.dtype != torch.float64 or env.dim() != 1 or env.numel() < 1 or not env.is_contiguous():
+        raise TypeError("env must be a non-empty contiguous 1-D float64 tensor")
+    if not env.is_cuda:
+        raise RuntimeError("the mark entries run on a HIP device only (no CPU path)")
+    if dev is not None and env.device != dev:
+        raise ValueError(f"env is on {env.device}, not on {dev}")
+
+
+def mark_envelope(signal, table, env, D=2, H=20, lead_bits=255, max_len=None):
+    """The detector's envelope of recordings of a resident store (nef_mark_envelope, include/nefnet_hip.h): for every row (offset, len,
+    env_offset) of the int64 [N, 3] `table`, env[env_offset + t] = the sum over the window [t - H, t + H] (cut at the recording's ends) of
+    the squared differences x[t + D] - x[t - D] (indices clamped) of the leads in `lead_bits`, in fp64 from the stored int16 / float32 values.
+    `env` is a flat float64 device buffer, written in place at the rows' positions only and returned.  A host table is checked against
+    `signal` and `env` here and copied; a device table needs `max_len`, and a row of it that would leave a buffer writes nothing.  One
+    launch on the current stream, capturable with a device table."""
+    _check_signal(signal, "mark_envelope")
+    _check_env(env, signal.device)
+    D, H = _mark_int("D", D, 0, MARK_MAX_D), _mark_int("H", H, 0, MARK_MAX_H)
+    lead_bits = _mark_int("lead_bits", lead_bits, 1, 255)
+    table, max_len = _mark_table(table, signal.device, max_len, env.numel(), signal.numel(), max_rows=MARK_MAX_ROWS)
+    L = _lib.load()
+    ev = _hbm("mark_envelope", signal, table, env)
+    A = _lib.MarkEnvelopeArgs(signal=_p(signal), table=_p(table), env=_p(env), signal_elems=signal.numel(), env_elems=env.numel(),
+                              max_len=max_len, N=table.shape[0], D=D, H=H, lead_bits=lead_bits,
+                              dtype=0 if signal.dtype == torch.int16 else 1, reserved0=0)
+    _lib.check(L.nef_mark_envelope(C.byref(A), _stream()), "nef_mark_envelope")
+    _done(ev)
+    return env
+
+
+def mark_peaks(env, table, r=100, seg=1000, frac=0.125, max_peaks=256, max_len=None):
+    """The peaks of every row's envelope (nef_mark_peaks, include/nefnet_hip.h): level = the lower median of the maxima of the len // seg
+    segments; t is a peak iff env[t] > 0, env[t] >= level * frac, nothing in the r positions before it is as high and nothing in the r
+    behind it higher.  `env` and `table` as for ops.mark_envelope (a row's signal offset is not read).  Returns fresh (peaks int32
+    [N, max_peaks] ascending with -1 behind them, count int32 [N] -- the true number, also above max_peaks -- and level float64 [N]); a row
+    with a non-finite envelope gets count -1, a NaN level and -1s.  One launch on the current stream, capturable with a device table."""
+    _check_env(env, None)
+    r, seg = _mark_int("r", r, 0, MARK_MAX_R), _mark_int("seg", seg, 1, MARK_MAX_LEN)
+    max_peaks = _mark_int("max_peaks", max_peaks, 1, MARK_MAX_PEAKS)
+    if isinstance(frac, bool) or not isinstance(frac, (int, float)) or not 0.0 <= float(frac) < float('inf'):
+        raise ValueError(f"frac = {frac!r}: a finite number >= 0")
+    table, max_len = _mark_table(table, env.device, max_len, env.numel())
+    if max_len // seg > MARK_MAX_SEGMENTS:
+        raise ValueError(f"max_len {max_len} with seg {seg}: more than {MARK_MAX_SEGMENTS} segments a recording")
+    N = table.shape[0]
+    peaks = torch.empty((N, max_peaks), dtype=torch.int32, device=env.device)
+    count = torch.empty((N,), dtype=torch.int32, device=env.device)
+    level = torch.empty((N,), dtype=torch.float64, device=env.device)
+    L = _lib.load()
+    ev = _hbm("mark_peaks", table, peaks, count, level)
+    A = _lib.MarkPeaksArgs(env=_p(env), table=_p(table), peaks=_p(peaks), count=_p(count), level=_p(level), env_elems=env.numel(),
+                           max_len=max_len, frac=float(frac), N=N, seg=seg, r=r, max_peaks=max_peaks)
+    _lib.check(L.nef_mark_peaks(C.byref(A), _stream()), "nef_mark_peaks")
+    _done(ev)
+    return peaks, count, level
+
+
 LOSS_SEG_TILE = 1024      # NEF_LOSS_SEG_TILE (include/nefnet_hip.h): positions per block of the two segment-weight kernels
 LOSS_SEG_MAX_ROWS = 65535  # the rows are a grid's y extent
 

@@ -48,6 +48,9 @@ def build_loaders(cfg, batch_size=32, phases=('train', 'test')):
     if resident:
         from .dataset import resident as res
         res.check_cfg(cfg)                                # tianchi only; not with DATA.noise / weighted_sample / synthetic
+    elif cfg.DATA.get('auto_marks', False):
+        from .dataset import marks
+        marks.check_cfg(cfg)                              # DATA.auto_marks marks the resident store only: ValueError
     if cfg.DATA.get('synthetic', False):
         for ph in phases:
             if ph == 'train':

@@ -1182,6 +1182,71 @@ typedef struct nef_recording_stats_args {
 int nef_recording_stats(const nef_recording_stats_args* a, nef_stream_t stream);
 size_t nef_recording_stats_args_bytes(void);
 
+/* Marks for unannotated recordings (dataset/marks.py): the QRS detector over a device-resident store.  Both entries are
+ * capturable and stateless, use no atomics and no scratch, and give every output element one writer.  They share one device table of int64
+ * rows [0] offset of the recording in `signal` (its eight stored leads as [8, len], lead-major)  [1] len  [2] offset of its envelope in `env`.
+ *
+ * nef_mark_envelope: with x_c the stored lead c as fp64 and the leads c of lead_bits (bit c set) in ascending order,
+ *   d_c(t) = x_c[min(t + D, len - 1)] - x_c[max(t - D, 0)]        e(t) = sum_c d_c(t) * d_c(t)
+ *   env[[2] + t] = sum of e(u), u from max(t - H, 0) to min(t + H, len - 1) in ascending order,
+ * the multiply and each add rounded separately (fp64, no contraction).  On an int16 store every intermediate is an integer below 2^41 and the
+ * order does not matter; on an fp32 store the order above is the definition.  One workgroup per (recording, tile of NEF_MARK_TILE
+ * positions), the tile of e and its H halo staged in LDS once; any offset alignment and any len >= 1 give the same values.  A row that would
+ * leave `signal` or `env`, or whose len is below 1 or above max_len (the grid covers max_len positions), writes nothing; the check is inside
+ * the launch, per block.
+ * N outside 1..65535, max_len outside 1..2^31 - 65536, D outside 0..NEF_MARK_MAX_D, H outside 0..NEF_MARK_MAX_H, lead_bits outside 1..255,
+ * dtype outside {0, 1}, signal_elems or env_elems < 1: NEF_E_SHAPE; a NULL pointer: NEF_E_NULL; signal not 16-byte aligned, table or env not
+ * 8-byte aligned: NEF_E_UNSUPPORTED. */
+#define NEF_MARK_TILE 1024
+#define NEF_MARK_MAX_D 4096
+#define NEF_MARK_MAX_H 256
+#define NEF_MARK_MAX_R 512
+#define NEF_MARK_MAX_SEGMENTS 4096
+typedef struct nef_mark_envelope_args {
+    const void* signal;         /* int16 or fp32 elements */
+    const int64_t* table;       /* [N, 3] */
+    double* env;                /* env_elems doubles */
+    int64_t signal_elems;
+    int64_t env_elems;
+    int64_t max_len;            /* no row is longer */
+    int32_t N;
+    int32_t D;
+    int32_t H;
+    int32_t lead_bits;
+    int32_t dtype;              /* 0: int16, 1: fp32 */
+    int32_t reserved0;          /* 0 */
+} nef_mark_envelope_args;
+int nef_mark_envelope(const nef_mark_envelope_args* a, nef_stream_t stream);
+size_t nef_mark_envelope_args_bytes(void);
+
+/* nef_mark_peaks: the peaks of every row's envelope env[[2] .. [2] + len), one workgroup per row ([0] is not read).
+ *   level   nseg = max(len / seg, 1) segments [i seg, (i + 1) seg), the last one extended to len; level = the lower median of their maxima,
+ *           the element of rank (nseg - 1) / 2 in ascending order.
+ *   peak    t is one iff env[t] > 0, env[t] >= level * frac (one fp64 multiply), env[u] < env[t] for every u in [max(t - r, 0), t) and
+ *           env[u] <= env[t] for every u in (t, min(t + r, len - 1)]: non-maximum suppression, a plateau going to its earliest position.
+ * peaks[i, 0 .. max_peaks) holds row i's peaks in ascending order, -1 behind them; count[i] is their true number, also above max_peaks;
+ * level[i] the level.  A row whose envelope holds a non-finite value, that would leave `env`, or whose len is below 1 or above max_len gets
+ * count -1, a NaN level and a row of -1.  No sequential state: a row's result is a function of its envelope alone.
+ * N < 1, max_len outside 1..2^31 - 65536, seg < 1, max_len / seg > NEF_MARK_MAX_SEGMENTS, r outside 0..NEF_MARK_MAX_R, max_peaks outside
+ * 1..2^20, frac negative, infinite or NaN, env_elems < 1: NEF_E_SHAPE; a NULL pointer: NEF_E_NULL; env, table or level not 8-byte aligned,
+ * peaks or count not 4-byte aligned: NEF_E_UNSUPPORTED. */
+typedef struct nef_mark_peaks_args {
+    const double* env;          /* env_elems doubles */
+    const int64_t* table;       /* [N, 3] */
+    int32_t* peaks;             /* [N, max_peaks] */
+    int32_t* count;             /* [N] */
+    double* level;              /* [N] */
+    int64_t env_elems;
+    int64_t max_len;            /* no row is longer */
+    double frac;
+    int32_t N;
+    int32_t seg;
+    int32_t r;
+    int32_t max_peaks;
+} nef_mark_peaks_args;
+int nef_mark_peaks(const nef_mark_peaks_args* a, nef_stream_t stream);
+size_t nef_mark_peaks_args_bytes(void);
+
 /* ---------------------------------------------------------------------------------------------
  * SGD with momentum over a flat buffer.  codes/solver/optim_scheduler.py:10 (torch.optim.SGD semantics:
  * first step buf = g, afterwards buf = mu*buf + g; p -= lr*buf).  g is multiplied by gscale first

@@ -13,6 +13,12 @@ host thread; nef_beat_batch alone on cold recordings; the resident loader feedin
 on preloaded synthetic batches.  Prints one JSON line of [min, median, max] per figure (`--out FILE` also writes it).
 
     python tools/bench_loader.py --resident [--rounds 3] [--n 2048] [--out profiles/r23_resident_bench_line.json]
+
+`--resident --auto-marks` times DATA.auto_marks (dataset/marks.py) instead: the timing table is fitted on the tree once, then `--rounds`
+alternating rounds of fresh processes build the annotated store and the auto-marked one (signals only, no label file read), and the second
+also times marks.detect alone and the two kernels on cold data with their algorithmic bytes.  The line says how many recordings got labels.
+
+    python tools/bench_loader.py --resident --auto-marks [--rounds 3] [--n 2048] [--out profiles/r29_marks_bench_line.json]
 """
 import argparse
 import json
@@ -178,6 +184,118 @@ def leg_resident(a):
     return out
 
 
+def _timed_store(cfg, dev, **kw):
+    from electrocardio_panorama_amd.dataset import resident
+    torch.zeros(1, device=dev)
+    t0 = time.perf_counter()
+    store = resident.ResidentTianchi(cfg, "train", dev, **kw)
+    torch.cuda.synchronize()
+    return store, round(time.perf_counter() - t0, 3)
+
+
+def leg_fit(a):
+    """Fit the ratio table on the tree's own annotations and leave it in the tree."""
+    from electrocardio_panorama_amd.dataset import marks, resident
+    cfg = tree_cfg(a.tree, a.leads)
+    store = resident.ResidentTianchi(cfg, "train", torch.device("cuda", 0))
+    params = marks.MarkParams.from_rate(cfg.DATA.sample_rate)
+    fit = marks.fit_table(store, marks.detect(store, params=params))
+    marks.save_table(os.path.join(a.tree, "table.json"), fit.table, params=params)
+    return {"leg": "fit", "fit_matched_beats": fit.matched, "fit_left_out_beats": fit.left_out, "fit_table_b": np.round(fit.table[:, 1], 4).tolist()}
+
+
+def leg_store(a):
+    """The annotated store build alone: what the auto-marked build is held against."""
+    cfg = tree_cfg(a.tree, a.leads)
+    cfg.DATA.device_resident = True
+    torch.set_num_threads(1)
+    _, sec = _timed_store(cfg, torch.device("cuda", 0))
+    return {"leg": "store", "annotated_store_build_s": sec}
+
+
+def leg_auto(a):
+    """The auto-marked store build (signals only), marks.detect alone on the built store, and the two kernels behind a cache flush."""
+    from electrocardio_panorama_amd import ops
+    from electrocardio_panorama_amd.dataset import marks
+    torch.set_num_threads(1)
+    dev = torch.device("cuda", 0)
+    cfg = tree_cfg(a.tree, a.leads)
+    cfg.DATA.train_label_root = os.path.join(a.tree, "no_labels")        # nothing there: the build opens no label file
+    cfg.DATA.device_resident, cfg.DATA.auto_marks, cfg.DATA.auto_marks_skip = True, True, True
+    cfg.DATA.mark_table = os.path.join(a.tree, "table.json")
+    store, sec = _timed_store(cfg, dev)
+    rep = store.auto_report
+    out = {"leg": "auto", "auto_store_build_s": sec, "auto_recordings_marked": rep["marked"], "auto_recordings": rep["recordings"],
+           "auto_peaks": rep["peaks"], "auto_peaks_dropped": rep["dropped"], "auto_marks_adjusted": rep["adjusted"],
+           "store_dtype": str(store.signal.dtype).replace("torch.", "")}
+    _, _, params = marks.load_table(cfg.DATA.mark_table)
+    ms = []
+    for _ in range(4):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        marks.detect(store, params=params)
+        ms.append((time.perf_counter() - t0) * 1e3)
+    out["detect_ms"] = round(float(np.median(ms[1:])), 3)
+    # the kernels alone, every launch behind a 512 MiB fill: one chunk of at most 2^25 samples, as detect cuts them
+    flush = torch.empty(512 << 20, dtype=torch.uint8, device=dev)
+    a0, b0 = marks._chunks(store.lengths.tolist(), 1 << 25)[0]
+    ln = store.lengths[a0:b0]
+    eoff = np.concatenate([[0], np.cumsum(ln)[:-1]])
+    table = torch.from_numpy(np.ascontiguousarray(np.stack([store.offsets[a0:b0], ln, eoff], axis=1), dtype=np.int64)).to(dev)
+    env = torch.empty(int(ln.sum()), dtype=torch.float64, device=dev)
+    us = {"mark_envelope": [], "mark_peaks": []}
+    for _ in range(5):
+        for name, call in (("mark_envelope", lambda: ops.mark_envelope(store.signal, table, env, D=params.D, H=params.H,
+                                                                       lead_bits=params.lead_bits, max_len=int(ln.max()))),
+                           ("mark_peaks", lambda: ops.mark_peaks(env, table, r=params.r, seg=params.seg, frac=params.frac,
+                                                                 max_peaks=params.max_peaks, max_len=int(ln.max())))):
+            flush.zero_()
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            call()
+            e.record()
+            e.synchronize()
+            us[name].append(s.elapsed_time(e) * 1e3)
+    samples, rows = int(ln.sum()), int(ln.size)
+    nbytes = {"mark_envelope": samples * 8 * store.signal.element_size() + samples * 8 + rows * 24,
+              "mark_peaks": samples * 8 + rows * (24 + 4 * params.max_peaks + 12)}
+    for name in us:
+        t = float(np.median(us[name][1:]))                              # the first: code load, allocator
+        out[f"{name}_cold_us"], out[f"{name}_bytes"], out[f"{name}_tb_s"] = round(t, 2), nbytes[name], round(nbytes[name] / t * 1e-6, 4)
+    return out
+
+
+def drive_auto(a):
+    """The table once, then `--rounds` alternating rounds of fresh processes: the annotated build, the auto-marked build."""
+    root = tempfile.mkdtemp(prefix="nef_marks_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
+    runs = []
+    try:
+        make_tree(root, a.n)
+        for leg in ["fit"] + ["store", "auto"] * a.rounds:
+            cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg, "--tree", root, "--leads", str(a.leads)]
+            res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=a.leg_timeout)
+            if res.returncode != 0:
+                raise RuntimeError(f"leg {leg} ended with exit code {res.returncode}")
+            runs.append(json.loads(res.stdout.strip().splitlines()[-1]))
+            print(json.dumps(runs[-1]), flush=True)
+    finally:
+        shutil.rmtree(root, ignore_errors=True)
+    line = {"recordings": a.n, "rounds": a.rounds}
+    for key in sorted({k for r in runs for k in r}):
+        vals = [r[key] for r in runs if key in r]
+        if isinstance(vals[0], (int, float)) and len(set(vals)) > 1:
+            line[key] = [min(vals), float(np.median(vals)), max(vals)]
+        elif key != "leg":
+            line[key] = vals[0]
+    med = lambda v: v[1] if isinstance(v, list) else v      # noqa: E731
+    line["auto_build_over_annotated"] = round(med(line["auto_store_build_s"]) / med(line["annotated_store_build_s"]), 4)
+    line["auto_build_within_10_percent"] = bool(line["auto_build_over_annotated"] <= 1.10)
+    print(json.dumps(line))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(line) + "\n")
+
+
 def drive_resident(a):
     """`--rounds` alternating rounds of fresh processes on one tree; [min, median, max] of every figure."""
     root = tempfile.mkdtemp(prefix="nef_loader_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
@@ -224,16 +342,20 @@ def main():
     ap.add_argument("--step-epochs", type=int, default=3)
     ap.add_argument("--leg-timeout", type=float, default=400.0)
     ap.add_argument("--out", default="")
-    ap.add_argument("--leg", choices=("workers", "resident"), help="(internal) one leg of --resident in this process")
+    ap.add_argument("--auto-marks", action="store_true", help="with --resident: time DATA.auto_marks against the annotated store build")
+    ap.add_argument("--leg", choices=("workers", "resident", "fit", "store", "auto"), help="(internal) one leg of --resident in this process")
     ap.add_argument("--tree", default="", help="(internal) the tree --leg reads")
     a = ap.parse_args()
     if a.leg:
         if not torch.cuda.is_available():
             raise SystemExit("--resident needs a HIP device")
-        print(json.dumps(leg_workers(a) if a.leg == "workers" else leg_resident(a)))
+        legs = {"workers": leg_workers, "resident": leg_resident, "fit": leg_fit, "store": leg_store, "auto": leg_auto}
+        print(json.dumps(legs[a.leg](a)))
         return
+    if a.auto_marks and not a.resident:
+        raise SystemExit("--auto-marks goes with --resident: the marks are made on the device-resident store")
     if a.resident:
-        return drive_resident(a)
+        return drive_auto(a) if a.auto_marks else drive_resident(a)
     root = tempfile.mkdtemp(prefix="nef_loader_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
     try:
         make_tree(root, a.n)
