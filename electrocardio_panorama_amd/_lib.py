@@ -154,6 +154,11 @@ class AugmentMaskArgs(C.Structure):
     _fields_ = [("mask", p), ("seed_dev", p), ("seed", C.c_uint64), ("lead_drop", f32), ("B", i32), ("V", i32), ("reserved0", i32)]
 
 
+class NoiseRowArgs(C.Structure):
+    """Mirror of `nef_noise_row_args` (include/nefnet_hip.h)."""
+    _fields_ = [("target", p), ("rois", p), ("out", p), ("sigma", p), ("seed_dev", p), ("seed", C.c_uint64), ("Rw", i32), ("L", i32)]
+
+
 class WarpArgs(C.Structure):
     """Mirror of `nef_warp_args` (include/nefnet_hip.h)."""
     _fields_ = [("data", p), ("target", p), ("rest", p), ("rois", p), ("data_out", p), ("target_out", p), ("rest_out", p),
@@ -314,6 +319,8 @@ SIGNATURES = {
     "nef_lead_mask_mix_bwd_args_bytes": (sz, []),
     "nef_augment_mask": (i32, [C.POINTER(AugmentMaskArgs), p]),
     "nef_augment_mask_args_bytes": (sz, []),
+    "nef_noise_row": (i32, [C.POINTER(NoiseRowArgs), p]),
+    "nef_noise_row_args_bytes": (sz, []),
     "nef_warp": (i32, [C.POINTER(WarpArgs), p]),
     "nef_warp_args_bytes": (sz, []),
     "nef_beat_batch": (i32, [C.POINTER(BeatBatchArgs), p]),
@@ -411,6 +418,7 @@ def load():
                                ("nef_lead_mask_mix_fwd_args", lib.nef_lead_mask_mix_fwd_args_bytes(), LeadMaskMixFwdArgs),
                                ("nef_lead_mask_mix_bwd_args", lib.nef_lead_mask_mix_bwd_args_bytes(), LeadMaskMixBwdArgs),
                                ("nef_augment_mask_args", lib.nef_augment_mask_args_bytes(), AugmentMaskArgs),
+                               ("nef_noise_row_args", lib.nef_noise_row_args_bytes(), NoiseRowArgs),
                                ("nef_warp_args", lib.nef_warp_args_bytes(), WarpArgs),
                                ("nef_beat_batch_args", lib.nef_beat_batch_args_bytes(), BeatBatchArgs),
                                ("nef_beat_range_args", lib.nef_beat_range_args_bytes(), BeatRangeArgs),

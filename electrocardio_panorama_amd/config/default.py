@@ -67,6 +67,15 @@ _DEFAULTS = {
         "mark_table": "",              # the JSON table file; required with auto_marks
         # a recording that gets no labels (fewer than two beats left) is an error; True: it is dropped from the store, one warning counts them
         "auto_marks_skip": False,
+        # (not in the reference) DATA.noise's addend drawn by the TRAIN step itself on the device (device_noise.py; nef_noise_row): per
+        # target row a Gaussian draw whose sigma is the standard deviation of the quiet second half of the row's T-P segment, taken from
+        # the step's final target rows and rois -- behind the warp and the view selection -- and handed to the loss where DATA.noise's row
+        # goes, in the eager and the graphed step; meta['noise'] is not read, the test phase adds no noise.  Goes with everything
+        # DATA.noise is rejected with (device_resident, auto_marks, aug_warp / aug_roi_jitter, SOLVER.train_views >= 2) and with synthetic
+        # batches; ValueError together with DATA.noise.  A segment without a sample inside the row gives sigma 0 and a row of zeros (the
+        # host row is NaN there).  Every draw comes from the step's counter-RNG seed: a resumed run and a replayed step see the same row,
+        # steps and shards differ.  False: no launch, no buffer, the graphs and bits are what they were before the key existed
+        "device_noise": False,
     },
     "MODEL": {
         "model": "modelv2",            # 'model_nefnet' selects Nef-Net

@@ -7,7 +7,8 @@ derives the four limb leads, normalises and pads.  The bits are the host path's:
 stored values.  `ResidentLoader` is the iterable of `meta` dicts the Solver consumes in place of the DataLoader.
 
 Left out on this path, and rejected where the key is read: DATA.noise (it needs the quiet segment's sigma and a device draw, a different
-random stream from the host's), DATA.weighted_sample, DATA.synthetic and every dataset but tianchi (PTB)."""
+random stream from the host's), DATA.weighted_sample, DATA.synthetic and every dataset but tianchi (PTB).  DATA.device_noise is that device
+draw, made by the train step from the batch this path builds (device_noise.py): it goes with the key."""
 import os
 import random
 import warnings
@@ -31,7 +32,7 @@ def check_cfg(cfg):
         raise ValueError(f"DATA.device_resident keeps Tianchi recordings on the device; DATA.dataset {cfg.DATA.dataset!r} is not built there")
     if cfg.DATA.get('noise', False):
         raise ValueError("DATA.device_resident with DATA.noise: the noise row needs the quiet segment's sigma and a host draw; "
-                         "it is not built on the device")
+                         "it is not built on the device (DATA.device_noise: the train step draws the row itself)")
     if cfg.DATA.get('weighted_sample', False):
         raise ValueError("DATA.device_resident with DATA.weighted_sample: the weighted draw is not planned on this path")
     if cfg.DATA.get('synthetic', False):

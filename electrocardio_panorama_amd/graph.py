@@ -48,6 +48,11 @@ Lead masks (cfg.MODEL.lead_mask, with DATA.aug_lead_drop): every shape slot owns
 ops.augment_mask directly behind the captured ops.augment from the same host word and `seed_dev`, and handed to engine.forward, whose
 head then averages and picks among the leads the corruption left (the backward finds the mask in the saved state).  Two library
 launches in the graph, no torch kernel, no host write between replays.  Off: no buffer, no launch, today's graph.
+
+The step's own noise row (cfg.DATA.device_noise; device_noise.py): the slot's static noise buffer is [Rw, 1, L] -- one row per (view,
+sample), also for Q >= 2, whose rois are then tiled per view whatever the plan needs -- and ops.noise_row from the static target and rois
+fills it directly in front of ops.loss_fwd, at device_noise.site_word() + `seed_dev`: every replay draws its own row, the eager step's at
+the same step seed, with no staged copy and no `noise=` from the caller.  Off: no buffer, no launch.
 """
 import random
 
@@ -67,7 +72,11 @@ class GraphedTrainStep:
         self.model, self.cfg = model, cfg
         # cfg.DATA.noise (reference solver.py:185-186): every shape slot owns a static [B, 1, L] noise buffer, staged with the other inputs
         # and added inside the loss kernels; off: no buffer, no copy
-        self.use_noise = bool(cfg.DATA.noise)
+        # cfg.DATA.device_noise (device_noise.py): the buffer is [Rw, 1, L], one row per (view, sample), and a captured ops.noise_row on the
+        # static target and rois fills it in front of the loss launches -- nothing is staged, the caller hands no noise.  Both keys: ValueError
+        from . import device_noise as _device_noise
+        self.device_noise = _device_noise.on(cfg)
+        self.use_noise = bool(cfg.DATA.noise) or self.device_noise
         self.noise = None
         self.rois_q = None       # multi-view steps whose plan needs rois (a cropped term, segment weights): the rois tiled Q times
         # the terms behind the four of ops.loss_fwd: their launches behind the loss launches, one more element of the loss row per tail term
@@ -177,6 +186,11 @@ class GraphedTrainStep:
                                       phase="train", training=True, drop=drop, lead_choice=self.choice_dev, save=True,
                                       status=self.status, **mask_kw)
             o, p_, l_ = (t.contiguous() for t in outs)
+            if self.device_noise:
+                # this step's noise row from its own target rows, at host word + seed_dev = the eager step's seed word
+                from . import device_noise as _device_noise
+                ops.noise_row(self.target, self.rois if self.rois_q is None else self.rois_q, seed=_device_noise.site_word(),
+                              seed_dev=self.seed_dev, out=self.noise)
             ops.loss_fwd(o, p_, l_, self.target, self.factors, self.reg_l2, self.use_mask, out=self.losses, noise=self.noise)
             g3 = ops.loss_bwd(o, p_, l_, self.target, None, self.factors, self.reg_l2, self.use_mask, noise=self.noise)
             rois = self.rois if self.rois_q is None else self.rois_q      # (multi-view: the rows are the Q * B (view, sample) pairs)
@@ -302,13 +316,15 @@ class GraphedTrainStep:
             # SOLVER.train_views: q_theta [Q, B, 2] selects the multi-view step (engine.forward) -- the targets are [Q, B, 1, L], and the
             # SSIM term's rows are the Q * B (view, sample) pairs, cropped by the rois tiled once per view
             Q = q_theta.shape[0]
-            if self.use_noise:
+            if self.use_noise and not self.device_noise:
                 raise ValueError("DATA.noise with SOLVER.train_views >= 2: the batch carries noise for the target lead only")
             slot["target"] = torch.empty(Q, data.shape[0], 1, data.shape[2], device=dev, dtype=torch.float32)
             self.plan.check_rows(Q * data.shape[0], views=Q)
-            if self.plan.needs_rois:
+            if self.plan.needs_rois or self.device_noise:      # (the noise row's quiet segment is read per (view, sample) row too)
                 slot["rois_q"] = torch.empty(Q * rois.shape[0], rois.shape[1], rois.shape[2], device=dev, dtype=torch.int64)
-        if self.use_noise:
+        if self.device_noise:
+            slot["noise"] = torch.empty(slot["target"].numel() // data.shape[2], 1, data.shape[2], device=dev, dtype=torch.float32)
+        elif self.use_noise:
             slot["noise"] = torch.empty(data.shape[0], 1, data.shape[2], device=dev, dtype=torch.float32)
         if self.augment is not None:
             slot["data_aug"] = torch.empty(data.shape, device=dev, dtype=torch.float32)
@@ -383,7 +399,7 @@ class GraphedTrainStep:
         if self.rois_q is not None:
             self.rois_q.view((-1,) + tuple(self.rois.shape)).copy_(self.rois.unsqueeze(0).expand(self.rois_q.shape[0] // self.rois.shape[0], -1, -1, -1))
         self.target.copy_(target.reshape(self.target.shape), non_blocking=True)
-        if self.noise is not None:
+        if self.noise is not None and not self.device_noise:
             self.noise.copy_(noise.reshape(self.noise.shape), non_blocking=True)
         if draw:
             self._draw()
@@ -487,9 +503,10 @@ class GraphedTrainStep:
     def __call__(self, data, in_theta, q_theta, rois, target, noise=None):
         """One train step; returns the device tensor [loss, f0*l1, f1*l2, f2*l3] + one element per tail term of `self.plan` that is on
         (valid in stream order; `loss` includes them all).  `noise`: the batch's [B, L] or [B, 1, L] noise rows, required when
-        cfg.DATA.noise is set and ignored when it is not (as the reference ignores meta['noise'] then)."""
+        cfg.DATA.noise is set and ignored when it is not (as the reference ignores meta['noise'] then; cfg.DATA.device_noise: the step
+        makes its own)."""
         self.model._check_inputs(data, rois)       # what Model_nefnet.forward rejects (float rois, L % 4, CPU tensors) is rejected here too
-        if self.use_noise and noise is None:
+        if self.use_noise and not self.device_noise and noise is None:
             raise ValueError("cfg.DATA.noise is set: the step needs this batch's noise")
         if self.optimizer is not None:
             g = self.optimizer.param_groups[0]

@@ -206,9 +206,10 @@ class Model_nefnet(nn.Module):
         self._drop_calls += 1
         rank = torch.distributed.get_rank() if (torch.distributed.is_available() and
                                                 torch.distributed.is_initialized()) else 0
-        return engine.DropCfg(self.training, self.dropout_p, self.dropout_masks,
-                              seed=(torch.initial_seed() + self._drop_calls + int(self.dropout_epoch) * 0x1000003
-                                    + rank * 0x9E3779B1) & 0x7FFFFFFFFFFF)
+        # (kept: the step's seed is also what DATA.device_noise's row is drawn under, behind the forward -- Solver.run_one_epoch)
+        self.last_step_seed = (torch.initial_seed() + self._drop_calls + int(self.dropout_epoch) * 0x1000003
+                               + rank * 0x9E3779B1) & 0x7FFFFFFFFFFF
+        return engine.DropCfg(self.training, self.dropout_p, self.dropout_masks, seed=self.last_step_seed)
 
     def _half_sweep(self):
         if self.panorama_dtype not in ('fp32', 'fp16'):

@@ -1904,6 +1904,54 @@ def augment(x, rois, aug, seed=0, seed_dev=None, out=None):
     return y
 
 
+def noise_row(target, rois, seed, seed_dev=None, out=None, sigma_out=None):
+    """cfg.DATA.device_noise's addend of the loss (nef_noise_row, include/nefnet_hip.h, defines it): per target row a Gaussian draw whose
+    sigma is the standard deviation of the quiet second half of the row's T-P segment, +0.0 at and behind the row's end.  `target`: the
+    step's final float32 target rows, [B, 1, L], [Q, B, 1, L] or [Rw, L], contiguous; `rois`: int64 [Rw, 7, 2] on target's device, one per
+    row (a multi-view step's are tiled per view by the caller).  Returns a new tensor of target's shape, or `out`; `target` is never
+    written.  `seed`: the launch's 64-bit seed word (device_noise.train_seed); `seed_dev`: None, or a one-element int64 device tensor added
+    to it when the launch runs (the replayed step's seed word, with seed = device_noise.site_word()).  `sigma_out`: None, or a float64
+    [Rw] tensor that receives every row's sigma.  One launch, capturable.  Every argument check sits in front of the library."""
+    if not torch.is_tensor(target) or target.dtype != torch.float32:
+        raise TypeError(f"target must be a float32 tensor, got {getattr(target, 'dtype', type(target))}")
+    if target.dim() < 2 or not target.is_contiguous() or target.numel() == 0:
+        raise ValueError(f"target must be a contiguous tensor of [.., L] rows, got {tuple(target.shape)} with strides {tuple(target.stride())}")
+    Ln = target.shape[-1]
+    Rw = target.numel() // Ln
+    if Ln % 4 != 0:
+        raise ValueError(f"target {tuple(target.shape)}: L a multiple of 4")
+    if not torch.is_tensor(rois) or rois.dtype != torch.int64:
+        raise TypeError(f"rois must be an int64 tensor [{Rw}, {N_SEG}, 2], got {getattr(rois, 'dtype', type(rois))}")
+    if tuple(rois.shape) != (Rw, N_SEG, 2) or not rois.is_contiguous():
+        raise ValueError(f"rois {tuple(rois.shape)} is not a contiguous [{Rw}, {N_SEG}, 2]")
+    if rois.device != target.device:
+        raise ValueError(f"rois is on {rois.device}, target on {target.device}")
+    if out is not None:
+        if (not torch.is_tensor(out) or out.dtype != torch.float32 or out.numel() != target.numel() or not out.is_contiguous()
+                or out.device != target.device):
+            raise ValueError("out must be a contiguous float32 tensor of target's elements on target's device")
+        if out.data_ptr() == target.data_ptr():
+            raise ValueError("out is target: the row is made out of place, the target is never modified")
+    if sigma_out is not None and (not torch.is_tensor(sigma_out) or sigma_out.dtype != torch.float64 or tuple(sigma_out.shape) != (Rw,)
+                                  or not sigma_out.is_contiguous() or sigma_out.device != target.device):
+        raise ValueError(f"sigma_out must be a contiguous float64 tensor [{Rw}] on target's device")
+    if seed_dev is not None and (not torch.is_tensor(seed_dev) or seed_dev.dtype != torch.int64 or seed_dev.numel() != 1
+                                 or seed_dev.device != target.device):
+        raise ValueError("seed_dev must be a one-element int64 tensor on target's device")
+    if not target.is_cuda:
+        raise RuntimeError("ops.noise_row runs on a HIP device only (no CPU path)")
+    if target.data_ptr() % 16 != 0 or (out is not None and out.data_ptr() % 16 != 0):
+        raise ValueError("target / out is not 16-byte aligned")
+    L = _lib.load()
+    y = torch.empty_like(target) if out is None else out
+    ev = _hbm("noise_row", y)
+    A = _lib.NoiseRowArgs(target=_p(target), rois=_p(rois), out=_p(y), sigma=_p(sigma_out), seed_dev=_p(seed_dev),
+                          seed=int(seed) & 0xFFFFFFFFFFFFFFFF, Rw=Rw, L=Ln)
+    _lib.check(L.nef_noise_row(C.byref(A), _stream()), "nef_noise_row")
+    _done(ev)
+    return y
+
+
 LEAD_MASK_MAX_V = 12      # NEF_LEAD_MASK_MAX_V (include/nefnet_hip.h)
 
 

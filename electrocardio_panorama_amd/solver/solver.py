@@ -30,6 +30,11 @@ index, rank) -- so the eager step, the replayed step and everything inside them 
 `DATA.aug_warp_eval`: `train` and `val` run the test phase once more on one fixed warped and jittered test set and report psnr_gen_warp /
 psnr_reg_warp / ssim_gen_warp / ssim_reg_warp beside the unwarped numbers, which decide best_valid as before.
 
+`DATA.device_noise` (no counterpart in the reference; device_noise.py): the train step draws DATA.noise's addend itself on the device --
+ops.noise_row on the step's final target rows and rois, behind the warp and the view selection, eagerly right behind the model call or as
+a captured launch of the graphed step -- and hands it to the loss as `noise=`; meta['noise'] is not read and the test phase adds no
+noise.  The step counters restart with every train epoch then, as with DATA.aug_*.
+
 `SOLVER.seg_weights` / `SOLVER.seg_eval` (no counterpart in the reference): the loss takes the batch's rois and weighs the reconstruction
 term by wave segment; the test phase reports the PSNR of each of the six wave segments (`nef_view_seg_metrics`, one more launch per
 batch) as psnr_gen_seg_* / psnr_reg_seg_*, in `Solver.last_seg_psnr`.
@@ -55,6 +60,7 @@ import torch.distributed as dist
 from .. import augment, engine, ops, parallel, views
 from .. import warp as _warp
 from .. import locate as _locate
+from .. import device_noise as _device_noise
 from ..network import build_model, build_loss
 from ..utils import CheckPointer
 from .optim_scheduler import get_optimizer, get_lr_scheduler
@@ -184,6 +190,8 @@ class Solver:
         # SOLVER.train_views = Q >= 2: a train step supervises Q of the batch's supervised rest views on one encoder pass (views.py);
         # 1: the reference's step on target_view / target_theta.  Invalid values and DATA.noise with Q >= 2 are rejected here
         self.train_views = views.train_views(cfg)
+        # DATA.device_noise: the train step draws its own noise row on the device (device_noise.py); with DATA.noise it is rejected here
+        self.device_noise = _device_noise.on(cfg)
         self.model = build_model(cfg).float()
         # DATA.aug_*: the train step corrupts its input leads on the device (augment.py); invalid keys are rejected here.  None = off
         self.augment = self.model.augment = augment.from_cfg(cfg)
@@ -240,6 +248,8 @@ class Solver:
             print(self.augment.describe())                # once: the DATA.aug_* keys that are on
         if self.warp is not None:
             print(self.warp.describe())                   # once: DATA.aug_warp / aug_roi_jitter / aug_warp_eval
+        if self.device_noise:                             # once: DATA.device_noise
+            print("noise row on the device: per target row, sigma of the quiet second half of its T-P segment (device_noise)")
         seg_w = self._seg_weights()
         if seg_w is not None:                             # once: SOLVER.seg_weights
             from ..network.loss.losses import SEG_NAMES
@@ -593,7 +603,7 @@ class Solver:
             raise ValueError('warp_eval is the test phase with DATA.aug_warp / DATA.aug_roi_jitter on')
         if aug_eval and (phase != 'test' or self.augment is None):
             raise ValueError('aug_eval is the test phase with a DATA.aug_* corruption on')
-        if phase == 'train' and self.augment is not None:
+        if phase == 'train' and (self.augment is not None or self.device_noise):
             # the step's seed counts from the start of the epoch: a function of (seed, epoch, batch index, rank) on the eager and the
             # replayed path alike, whatever ran in between (test phases, a resume)
             self.model._drop_calls = 0
@@ -666,8 +676,13 @@ class Solver:
                 if keep:       # solver.py:179 (before the optional noise); multi-view: one [Q, B, L] entry per batch
                     pred_s.add(out.squeeze(1) if n_views < 2 else out.squeeze(2).unsqueeze(0))
                 # DATA.noise (solver.py:185-186): the loss kernels add the row to the prediction, no launch of its own
-                losses = self.loss(out, shuf_p, shuf_l, target_view, self.cfg, noise=noise if self.cfg.DATA.noise else None,
-                                   **self._loss_rois(rois))
+                step_noise = noise if self.cfg.DATA.noise else None
+                if self.device_noise:
+                    # DATA.device_noise: the row from this step's final target rows and rois (behind the warp and the view selection),
+                    # under the seed of the forward that has just run -- the captured launch of the graphed step at the same step seed
+                    step_noise = ops.noise_row(*_device_noise.rows(target_view, rois),
+                                               seed=_device_noise.train_seed(self.model.last_step_seed))
+                losses = self.loss(out, shuf_p, shuf_l, target_view, self.cfg, noise=step_noise, **self._loss_rois(rois))
                 losses_s.add(torch.stack([l_.detach() for l_ in losses]))
                 losses[0].backward()
                 optim.step()

@@ -16,7 +16,7 @@ def train_views(cfg):
     Q = int(Q)
     if Q >= 2 and cfg.DATA.get('noise', False):
         raise ValueError("DATA.noise with SOLVER.train_views >= 2: the batch carries noise for the target lead only (meta['noise']); "
-                         "switch one of them off")
+                         "switch one of them off (DATA.device_noise draws a row per view)")
     return Q
 
 

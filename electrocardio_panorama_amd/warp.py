@@ -4,7 +4,8 @@ seeds, the log line; no counterpart in the reference, whose only augmentation is
 DATA.aug_* (augment.py) corrupts the input leads additively and never changes a beat's timing; this stretches or shrinks each of the six
 wave segments of every beat by a drawn factor -- inputs, target, rest views and the marks in `rois` together -- and then moves each
 interior mark by a drawn integer, the signal staying where it is: the first gives a run timing diversity, the second prepares it for marks
-that are a few samples off.  `from_cfg` turns the keys into a `Warp` (None when nothing is on); ops.warp applies it (nef_warp,
+that are a few samples off.  (DATA.noise's host row belongs to the unwarped beat and is rejected; DATA.device_noise draws the row from the
+warped target and its jittered marks, device_noise.py.)  `from_cfg` turns the keys into a `Warp` (None when nothing is on); ops.warp applies it (nef_warp,
 include/nefnet_hip.h, where every step is defined), in Solver.run_one_epoch right behind the batch's arrival on the device: one launch
 into fresh tensors, outside the replayed graph, so every later stage of the step receives a batch that is already consistent.
 
@@ -52,7 +53,8 @@ def from_cfg(cfg) -> Optional[Warp]:
     if not any(amp) and J == 0:
         return None
     if cfg.DATA.get("noise", False):
-        raise ValueError("DATA.noise with DATA.aug_warp / DATA.aug_roi_jitter on: the noise row is padded to the unwarped beat")
+        raise ValueError("DATA.noise with DATA.aug_warp / DATA.aug_roi_jitter on: the noise row is padded to the unwarped beat "
+                         "(DATA.device_noise draws the row from the warped target)")
     return Warp(amp, int(J), bool(cfg.DATA.get("aug_warp_eval", False)))
 
 

@@ -1011,6 +1011,39 @@ typedef struct nef_augment_mask_args {
 int nef_augment_mask(const nef_augment_mask_args* a, nef_stream_t stream);
 size_t nef_augment_mask_args_bytes(void);
 
+/* The train step's label-noise row, made on the device (cfg.DATA.device_noise; the reference's DATA.noise row, solver.py:185-186, is a
+ * host draw of its loader): out [Rw][L] is the addend the loss entries take as `noise`, a Gaussian draw per position whose sigma is the
+ * standard deviation of the quiet second half of the row's T-P segment, measured on the TARGET row itself.  Rows are the step's final
+ * fp32 target rows (Rw = B, or Q * B view-major) with their rois [Rw][7][2].  Per row i:
+ *   end   = clamp(rois[i][6][0], 0, L)                      (the row end of the SSIM, slope and correlation terms)
+ *   q0    = floor((rois[i][5][0] + rois[i][5][1]) / 2)      (the exact integer sum, true floor for a negative one)
+ *   q1    = rois[i][5][1]
+ *   [q0, q1) is cut to [0, end): q0' = clamp(q0, 0, end), q1' = clamp(q1, 0, end), m = max(q1' - q0', 0).  Only clamped values reach an
+ *   address: `rois` may hold anything.
+ *   sigma = sqrt(sum_t (v_t - mean)^2 / m),  mean = sum_t v_t / m  over t in [q0', q1'), in fp64 from the fp32 values (two passes, a
+ *           fixed order that depends on the segment alone): the population standard deviation.  m == 0: sigma = 0 (the host row would
+ *           be NaN).  A NaN in the segment: sigma is NaN.
+ *   out[i][t] = (float)sigma * n_t  for t < end,  +0.0 for t >= end -- and +0.0 for every t when (float)sigma == 0.  n_t is the
+ *           per-element stream of nef_augment_args under seed + seed_dev[0]: counter = (i L + t) >> 1, r = sqrt(-2 ln((k0 + 1) / 2^24)),
+ *           n_even = r cos(2 pi k1 / 2^24), n_odd = r sin(2 pi k1 / 2^24), the same fp32 expressions; a row end that splits a pair
+ *           leaves the element behind it +0.0.
+ *   sigma[i] (when given) = sigma, fp64.
+ * One 256-thread workgroup per row; the reduction is a function of the row's own data, not of Rw or the launch.  One writer per
+ * element, no atomics, no scratch, no state: the same bits eagerly and under hipGraph replay (seed_dev: the replayed step's seed word).
+ * args, target, rois or out NULL: NEF_E_NULL; Rw < 1, L <= 0, L % 4 != 0: NEF_E_SHAPE; target or out not 16-byte aligned, rois, sigma or
+ * seed_dev not 8-byte aligned, target and out overlapping: NEF_E_UNSUPPORTED.  Every check sits in front of the launch.  Capturable. */
+typedef struct nef_noise_row_args {
+    const float* target;        /* [Rw][L] */
+    const int64_t* rois;        /* [Rw][7][2] */
+    float* out;                 /* [Rw][L], not target */
+    double* sigma;              /* NULL, or [Rw] */
+    const uint64_t* seed_dev;   /* NULL, or a device word added to seed when the launch runs */
+    uint64_t seed;
+    int32_t Rw, L;
+} nef_noise_row_args;
+int nef_noise_row(const nef_noise_row_args* a, nef_stream_t stream);
+size_t nef_noise_row_args_bytes(void);
+
 /* Time warp of a whole train batch with jittered marks (cfg.DATA.aug_warp / aug_roi_jitter; no counterpart in the reference): every
  * segment of every beat is resampled to a drawn multiple of its length -- inputs, target and rest views alike -- and the marks follow,
  * each interior one then moved by a drawn integer.  Out of place; no input is written.  Per sample i, with L the row length and

@@ -15,6 +15,7 @@
     python tools/bench_adam.py --slope F [--parent-tree DIR] [--out profiles/r19_slope_bench_line.json]
     python tools/bench_adam.py --corr F [--parent-tree DIR] [--out profiles/r20_corr_bench_line.json]
     python tools/bench_adam.py --warp A0 A1 A2 A3 A4 A5 [--roi-jitter J] [--parent-tree DIR] [--out profiles/r25_warp_bench_line.json]
+    python tools/bench_adam.py --device-noise [--parent-tree DIR] [--out profiles/r30_device_noise_bench_line.json]
 
 Each measurement runs in a child process of its own under `timeout` (nothing more is started once one fails), `--reps` rounds of
 the three children; every figure is reported as [min, median, max] over the rounds:
@@ -109,7 +110,15 @@ nef_loss_corr_fwd (two launches) and nef_loss_corr_bwd (three) on the batch's pr
 J), at the same two shapes: per round and shape the graphed FusedSGD step with the keys off (sgd-graph: the parent's code path) and on
 (sgd-graph-warp: one nef_warp launch on the stream in front of every replay, into fresh tensors, as Solver.run_one_epoch places it), and --
 with --parent-tree DIR -- DIR's own sgd-graph step.  The config-2 child with the keys on also times the nef_warp launch alone on the batch's
-inputs, target and rois, cold.  Writes profiles/r25_warp_bench_line.json unless --out says otherwise."""
+inputs, target and rois, cold.  Writes profiles/r25_warp_bench_line.json unless --out says otherwise.
+
+--device-noise measures the train step's own noise row (DATA.device_noise), at the same two shapes: per round and shape the graphed FusedSGD
+step with the keys off (sgd-graph: the parent's code path) and with the key on (sgd-graph-device-noise: one captured nef_noise_row launch in
+front of the loss launches, the loss kernels with the addend), and -- with --parent-tree DIR -- DIR's own sgd-graph step and DIR's graphed
+step with DATA.noise on and a host row staged per step (sgd-graph-noise, this tool's child importing DIR's package: the like-for-like step the
+key-on step is compared with).  The config-2 child with the key on also times the nef_noise_row launch alone on the batch's target and
+rois, cold, beside its bytes (the quiet segments read, the row written).  Writes profiles/r30_device_noise_bench_line.json unless --out
+says otherwise."""
 import argparse
 import json
 import os
@@ -175,6 +184,10 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
         cfg.SOLVER.seg_weights = [float(w) for w in seg]
     if mode == "sgd-graph-warp":
         cfg.DATA.aug_warp, cfg.DATA.aug_roi_jitter = [float(a) for a in warp], int(roi_jitter)
+    if mode == "sgd-graph-noise":
+        cfg.DATA.noise = True
+    if mode == "sgd-graph-device-noise":
+        cfg.DATA.device_noise = True
     if mode == "sgd-graph-slope":
         cfg.SOLVER.slope_factor, cfg.SOLVER.slope_loss, cfg.SOLVER.slope_crop = float(slope), "l1_loss", True
     if mode == "sgd-graph-corr":
@@ -185,7 +198,7 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
     model = build_model(cfg).float().to(dev).train()
     lossf = build_loss(cfg)
     if mode in ("sgd-graph", "sgd-graph-ssim", "sgd-graph-views", "sgd-graph-augment", "sgd-graph-seg", "sgd-graph-slope", "sgd-graph-corr",
-                "sgd-graph-warp", "sgd-graph-lead-mask"):
+                "sgd-graph-warp", "sgd-graph-lead-mask", "sgd-graph-noise", "sgd-graph-device-noise"):
         optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9)
     elif mode == "sgd-graph-clip":
         optim = FusedSGD(model.parameters(), lr=cfg.SOLVER.lr, momentum=0.9, max_grad_norm=clip)
@@ -233,11 +246,19 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
         warp_cfg = _warp.from_cfg(cfg)
         assert warp_cfg is not None
 
+    # DATA.noise: a host row per sample as the loaders make it (sigma 0.01 in front of the row end, zeros behind it)
+    host_noise = None
+    if mode == "sgd-graph-noise":
+        live = torch.arange(L, device=dev)[None, :] < rois[:, 6, 0].clamp(0, L)[:, None]
+        host_noise = (0.01 * torch.randn(B, L, device=dev) * live).unsqueeze(1).contiguous()
+
     def step():
         if warp_cfg is not None:
             d, t, _, r = ops.warp(data, tgt_view, None, rois, warp_cfg, _warp.train_seed(cfg.seed, 0, len(warped), 0))
             warped.append((d, r) if not warped else None)      # (the first step's, for the result line)
             return graphed(d, in_theta, tgt_theta, r, t)
+        if host_noise is not None:       # DATA.noise: the loader's row, staged with the other inputs
+            return graphed(data, in_theta, tgt_theta, rois, tgt_view, noise=host_noise)
         if graphed is not None:
             return graphed(data, in_theta, tgt_theta, rois, tgt_view)
         out, sp, sl = model(data, in_theta, tgt_theta, rois, phase="train")
@@ -345,6 +366,23 @@ def child(mode, steps, warmup, V=3, B=256, L=5000, clip=0.0, wd=0.0, no_decay=()
         ms = cold_ms([lambda: ops.warp(data, tgt_view, None, rois, warp_cfg, 1)], dev)[0]
         nbytes = 2 * 4 * (data.numel() + tgt_view.numel()) + 2 * 8 * rois.numel()
         res.update(nef_warp_cold_ms=round(ms, 4), nef_warp_bytes=nbytes, nef_warp_cold_GBps=round(nbytes / (ms * 1e-3) / 1e9, 1))
+    if mode == "sgd-graph-noise":
+        res.update(loss_row=[round(float(v), 6) for v in graphed.losses.tolist()])
+    if mode == "sgd-graph-device-noise":
+        res.update(loss_row=[round(float(v), 6) for v in graphed.losses.tolist()],
+                   noise_elements_nonzero=round(float((graphed.noise != 0).float().mean().item()), 4),
+                   noise_abs_mean=float(graphed.noise.abs().mean().item()))
+    if mode == "sgd-graph-device-noise" and (B, L) == EMA_SHAPES["config2"]:
+        from electrocardio_panorama_amd import device_noise as _dn
+        t_rows, r_rows = _dn.rows(tgt_view, rois)
+        y = torch.empty_like(t_rows)
+        ms = cold_ms([lambda: ops.noise_row(t_rows, r_rows, _dn.train_seed(1), out=y)], dev)[0]
+        end = r_rows[:, 6, 0].clamp(0, L)
+        q0 = torch.div(r_rows[:, 5, 0] + r_rows[:, 5, 1], 2, rounding_mode="floor").clamp(min=0)
+        seg = (torch.minimum(r_rows[:, 5, 1].clamp(min=0), end) - torch.minimum(q0, end)).clamp(min=0)
+        nbytes = 4 * y.numel() + 2 * 4 * int(seg.sum().item()) + 8 * r_rows.numel()      # the row written, the segments read twice, the rois
+        res.update(nef_noise_row_cold_ms=round(ms, 4), nef_noise_row_bytes=nbytes, nef_noise_row_cold_GBps=round(nbytes / (ms * 1e-3) / 1e9, 1),
+                   nef_noise_row_segment_elements=int(seg.sum().item()))
     if mode == "sgd-graph-seg":
         res.update(seg_weights=[float(w) for w in seg], loss_row=[round(float(v), 6) for v in graphed.losses.tolist()])
     if mode == "sgd-graph-seg" and (B, L) == EMA_SHAPES["config2"]:
@@ -827,6 +865,64 @@ def warp_rounds(args):
         f.write(line + "\n")
 
 
+def device_noise_rounds(args):
+    """--device-noise: `--reps` alternating rounds of fresh children per shape (see the module docstring); prints and writes one JSON line."""
+    modes = dict({"sgd-graph": 900, "sgd-graph-device-noise": 900}, **({"parent": 900, "parent-noise": 900} if args.parent_tree else {}))
+    results = {(shape, mode): [] for shape in EMA_SHAPES for mode in modes}
+    for rnd in range(args.reps):
+        order = list(modes) if rnd % 2 == 0 else list(reversed(modes))
+        for shape, (B, L) in EMA_SHAPES.items():
+            for mode in order:
+                tree = os.path.abspath(args.parent_tree) if mode.startswith("parent") else ROOT
+                if mode == "parent":
+                    # the parent's tool lacks --device-noise: its `child` function is called directly, in a fresh process of its own tree
+                    code = ("import importlib.util as u; s = u.spec_from_file_location('parent_bench', %r); m = u.module_from_spec(s); "
+                            "s.loader.exec_module(m); m.child('sgd-graph', %d, %d, B=%d, L=%d)"
+                            % (os.path.join(tree, "tools", "bench_adam.py"), args.steps, args.warmup, B, L))
+                    cmd = ["timeout", "-k", "10", str(modes[mode]), sys.executable, "-c", code]
+                else:
+                    # parent-noise: this tool's DATA.noise child on the parent's package (--parent-tree puts DIR in front of the path)
+                    cmd = ["timeout", "-k", "10", str(modes[mode]), sys.executable, os.path.join(ROOT, "tools", "bench_adam.py"), "--child",
+                           "sgd-graph-noise" if mode == "parent-noise" else mode,
+                           "--steps", str(args.steps), "--warmup", str(args.warmup), "--shape", str(B), str(L)]
+                    if mode == "parent-noise":
+                        cmd += ["--parent-tree", tree]
+                results[(shape, mode)].append(run_child(cmd, tree, mode))
+                sys.stderr.write(f"round {rnd + 1}/{args.reps} {shape} {mode}: {results[(shape, mode)][-1]['ms_per_step']} ms/step\n")
+                sys.stderr.flush()
+
+    def spread(shape, mode, key):
+        v = sorted(x[key] for x in results[(shape, mode)])
+        return [v[0], v[len(v) // 2], v[-1]]
+
+    out = {"metric": "ms per train step, graphed FusedSGD with DATA.device_noise off and on -- on: one captured nef_noise_row launch in front "
+                     "of the loss launches ([min, median, max] over rounds of fresh processes)", "rounds": args.reps,
+           "shapes": {k: "B=%d, 3 leads, L=%d, one GPU, dropout on, synthetic batches" % v for k, v in EMA_SHAPES.items()}}
+    for shape in EMA_SHAPES:
+        out[shape + "_device_noise_off_ms"] = spread(shape, "sgd-graph", "ms_per_step")
+        out[shape + "_device_noise_on_ms"] = spread(shape, "sgd-graph-device-noise", "ms_per_step")
+        out[shape + "_noise_elements_nonzero"] = spread(shape, "sgd-graph-device-noise", "noise_elements_nonzero")[1]
+        if args.parent_tree:
+            out[shape + "_parent_ms"] = par = spread(shape, "parent", "ms_per_step")
+            out[shape + "_parent_data_noise_ms"] = pn = spread(shape, "parent-noise", "ms_per_step")
+            # to be read against each other: the keys-off median and the parent's own min-max spread; the key-on median and the parent's
+            # like-for-like step with a host row (DATA.noise), the bar: + 0.3 ms
+            out[shape + "_device_noise_off_median_inside_parent_spread"] = par[0] <= out[shape + "_device_noise_off_ms"][1] <= par[2]
+            out[shape + "_device_noise_off_median_minus_parent_median_ms"] = round(out[shape + "_device_noise_off_ms"][1] - par[1], 3)
+            out[shape + "_device_noise_on_median_minus_parent_data_noise_median_ms"] = round(out[shape + "_device_noise_on_ms"][1] - pn[1], 3)
+    out.update(nef_noise_row_cold_ms=spread("config2", "sgd-graph-device-noise", "nef_noise_row_cold_ms"),
+               nef_noise_row_cold_GBps=spread("config2", "sgd-graph-device-noise", "nef_noise_row_cold_GBps"),
+               nef_noise_row_bytes=results[("config2", "sgd-graph-device-noise")][0]["nef_noise_row_bytes"],
+               nef_noise_row_segment_elements=results[("config2", "sgd-graph-device-noise")][0]["nef_noise_row_segment_elements"],
+               launch_note="the nef_noise_row launch alone at config 2 on the batch's target and rois; cold = a 512 MiB buffer written before "
+                           "each call; bytes counted: the row written, the quiet segments read twice, the rois",
+               steps=args.steps, warmup=args.warmup)
+    line = json.dumps(out)
+    print(line)
+    with open(args.out or os.path.join(ROOT, "profiles", "r30_device_noise_bench_line.json"), "w") as f:
+        f.write(line + "\n")
+
+
 def seg_rounds(args):
     """--seg W0 .. W6: `--reps` alternating rounds of fresh children per shape (see the module docstring); prints and writes one JSON line."""
     modes = dict({"sgd-graph": 900, "sgd-graph-seg": 900}, **({"parent": 900} if args.parent_tree else {}))
@@ -1147,13 +1243,15 @@ def main():
     ap.add_argument("--warp", type=float, nargs=6, default=None, metavar="A",
                     help="measure the time warp of the train batch, DATA.aug_warp = A0 .. A5 (see above)")
     ap.add_argument("--roi-jitter", type=int, default=0, metavar="J", help="with --warp: DATA.aug_roi_jitter = J")
+    ap.add_argument("--device-noise", action="store_true", help="measure the train step's own noise row, DATA.device_noise (see above)")
     ap.add_argument("--only-shape", choices=sorted(EMA_SHAPES), default=None, help="with --views, --slope or --corr: measure this shape only")
     ap.add_argument("--shape", type=int, nargs=2, default=(256, 5000), metavar=("B", "L"), help="with --child: batch size and length")
     ap.add_argument("--parent-tree", default=None,
                     help="with --clip / --weight-decay / --ema: a built checkout whose own sgd-graph child runs in every round")
     ap.add_argument("--child", choices=sorted({**MODES, **CLIP_MODES, **WD_MODES, **EMA_MODES, "lars-graph": 900, "lamb-graph": 900, "sgd-graph-accum": 900,
                                              "sgd-graph-sched": 900, "sgd-graph-ssim": 900, "sgd-graph-views": 900, "sgd-graph-augment": 900, "sgd-graph-lead-mask": 900,
-                                             "sgd-graph-seg": 900, "sgd-graph-slope": 900, "sgd-graph-corr": 900, "sgd-graph-warp": 900}),
+                                             "sgd-graph-seg": 900, "sgd-graph-slope": 900, "sgd-graph-corr": 900, "sgd-graph-warp": 900,
+                                             "sgd-graph-noise": 900, "sgd-graph-device-noise": 900}),
                     default=None)
     args = ap.parse_args()
     if args.child == "sgd-graph-ema" and not (args.ema is not None and 0.0 < args.ema < 1.0):
@@ -1223,15 +1321,24 @@ def main():
         ap.error("--warp is a measurement of its own")
     if args.child == "sgd-graph-warp" and args.warp is None:
         ap.error("--child sgd-graph-warp needs --warp A0 .. A5")
-    if (args.parent_tree and args.warp is None and args.corr is None and args.slope is None and args.seg is None and not args.augment and args.views is None and args.clip is None and args.weight_decay is None and args.ema is None and args.trust is None
+    if args.device_noise and not args.child and (
+            args.warp is not None or args.corr is not None or args.slope is not None or args.seg is not None or args.augment
+            or args.views is not None or args.clip is not None or args.weight_decay is not None or args.ema is not None
+            or args.trust is not None or args.accum is not None or args.sched is not None or args.ssim is not None):
+        ap.error("--device-noise is a measurement of its own")
+    if (args.parent_tree and not args.device_noise and not args.child and args.warp is None and args.corr is None and args.slope is None and args.seg is None and not args.augment and args.views is None and args.clip is None and args.weight_decay is None and args.ema is None and args.trust is None
             and args.accum is None and args.sched is None and args.ssim is None):
-        ap.error("--parent-tree goes with --clip, --weight-decay, --ema, --trust, --accum, --sched, --ssim, --views, --augment, --seg, --slope, --corr or --warp")
+        ap.error("--parent-tree goes with --clip, --weight-decay, --ema, --trust, --accum, --sched, --ssim, --views, --augment, --seg, --slope, --corr, --warp or --device-noise")
     if args.child:
+        if args.parent_tree:       # the child imports DIR's package (and loads DIR's library) instead of this tree's
+            sys.path.insert(0, os.path.abspath(args.parent_tree))
         return child(args.child, args.steps if args.child != "adam-eager" else max(3, args.steps // 2), args.warmup,
                      B=args.shape[0], L=args.shape[1], clip=args.clip or 0.0, wd=args.weight_decay or 0.0,
                      no_decay=tuple(args.no_decay), ema=args.ema or 0.0, accum=args.accum or 1,
                      sched=(args.sched, args.sched_warmup) if args.child == "sgd-graph-sched" else None, ssim=args.ssim or 0.0,
                      views=args.views[0] if args.views else 1, seg=args.seg, slope=args.slope or 0.0, corr=args.corr or 0.0, warp=args.warp, roi_jitter=args.roi_jitter)
+    if args.device_noise:
+        return device_noise_rounds(args)
     if args.warp is not None:
         return warp_rounds(args)
     if args.corr is not None:
