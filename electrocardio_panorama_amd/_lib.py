@@ -202,6 +202,12 @@ class MarkPeaksArgs(C.Structure):
                 ("frac", C.c_double), ("N", i32), ("seg", i32), ("r", i32), ("max_peaks", i32)]
 
 
+class ResampleArgs(C.Structure):
+    """Mirror of `nef_resample_args` (include/nefnet_hip.h)."""
+    _fields_ = [("src", p), ("table", p), ("dst", p), ("taps", p), ("first", p), ("src_elems", i64), ("dst_elems", i64),
+                ("max_out_len", i64), ("N", i32), ("max_rows", i32), ("up", i32), ("down", i32), ("K", i32), ("dtype", i32)]
+
+
 class PackDesc(C.Structure):
     """Mirror of `nef_pack_desc` (include/nefnet_hip.h)."""
     _fields_ = [("w", p), ("wp", p), ("G", i32), ("Cog", i32), ("Cig", i32), ("K", i32), ("transpose_flip", i32),
@@ -335,6 +341,8 @@ SIGNATURES = {
     "nef_mark_envelope_args_bytes": (sz, []),
     "nef_mark_peaks": (i32, [C.POINTER(MarkPeaksArgs), p]),
     "nef_mark_peaks_args_bytes": (sz, []),
+    "nef_resample": (i32, [C.POINTER(ResampleArgs), p]),
+    "nef_resample_args_bytes": (sz, []),
     "nef_sgd_momentum": (i32, [p, p, p, i64, f32, f32, f32, i32, p, p, p, p]),
     "nef_adam": (i32, [p, p, p, p, i64, f32, C.c_double, C.c_double, f32, f32, f32, p, p, p, p, p]),
     "nef_update": (i32, [C.POINTER(UpdateArgs), p]),
@@ -425,7 +433,8 @@ def load():
                                ("nef_beat_stitch_args", lib.nef_beat_stitch_args_bytes(), BeatStitchArgs),
                                ("nef_recording_stats_args", lib.nef_recording_stats_args_bytes(), RecordingStatsArgs),
                                ("nef_mark_envelope_args", lib.nef_mark_envelope_args_bytes(), MarkEnvelopeArgs),
-                               ("nef_mark_peaks_args", lib.nef_mark_peaks_args_bytes(), MarkPeaksArgs)):
+                               ("nef_mark_peaks_args", lib.nef_mark_peaks_args_bytes(), MarkPeaksArgs),
+                               ("nef_resample_args", lib.nef_resample_args_bytes(), ResampleArgs)):
         if size != C.sizeof(mirror):
             raise NefLibraryError(f"{LIB_PATH}: {name} is {size} bytes, the binding mirrors {C.sizeof(mirror)}; rebuild with "
                                   "`python -m electrocardio_panorama_amd.csrc.build`")

@@ -76,6 +76,17 @@ _DEFAULTS = {
         # host row is NaN there).  Every draw comes from the step's counter-RNG seed: a resumed run and a replayed step see the same row,
         # steps and shards differ.  False: no launch, no buffer, the graphs and bits are what they were before the key existed
         "device_noise": False,
+        # (not in the reference) with device_resident: the files hold recordings at source_rate Hz, not at sample_rate.  The store uploads
+        # them as they are and resamples them on the device to sample_rate -- a rational polyphase FIR, Kaiser-windowed sinc, per-phase
+        # normalised (resample.py; nef_resample) -- into a float32 store; annotated label lists are rescaled on the host,
+        # auto_marks detects on the resampled signal, and everything that counts samples (the 512-sample beat, the detector, the timing
+        # table, aug_wander_hz / aug_hum_hz, the SSIM window) keeps counting them at sample_rate.  Whole positive rates only, sample_rate
+        # too with the key on; up <= 1024, down <= 8 up, at most 512 taps a phase: ValueError otherwise, and without device_resident
+        # (`mark_net --resample DIR` writes resampled files for the host loader).  0, or sample_rate itself: no launch, no buffer, the store
+        # stays int16 / float32 and the loaders, graphs and bits are what they were before the key existed
+        "source_rate": 0,
+        "resample_zeros": 16,          # zero crossings of the sinc on each side of its centre, at the lower of the two rates
+        "resample_beta": 8.6,          # the Kaiser window's beta
     },
     "MODEL": {
         "model": "modelv2",            # 'model_nefnet' selects Nef-Net

@@ -15,6 +15,8 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
+from ..resample import increasing
+
 LABEL_KEYS = ('P on', 'P off', 'R on', 'R off', 'T on', 'T off')
 FORMS = ('ratio', 'affine')
 MAX_ROWS = 65535          # recordings a launch (ops.MARK_MAX_ROWS)
@@ -119,9 +121,6 @@ def _beat_rr(p, first, last):
     return prv, nxt
 
 
-_BIG = 1 << 40
-
-
 def labels_from_peaks(peaks, count, lengths, table):
     """The six label lists of every recording from its peaks, vectorised over all beats.  For the peaks p_0 .. p_{P-1} of a recording,
     mark[j, k] = p[j] + floor(a_k + b_k * RR + 0.5), RR the interval to the previous peak for 'P on' / 'P off' and to the next one for the
@@ -156,11 +155,9 @@ def labels_from_peaks(peaks, count, lengths, table):
         np.minimum.at(hi, rec, np.where(m[:, 5] > lengths[rec] - 1, j, max_peaks))
         keep = (j >= lo[rec]) & (j < hi[rec])
         m, rec = m[keep], rec[keep]
-        # strictly increasing within a recording: m_i - i is made non-decreasing (a running maximum; _BIG per recording keeps them apart)
-        flat, frec = m.reshape(-1), np.repeat(rec, 6)
-        i = np.arange(flat.size, dtype=np.int64)
-        fixed = np.maximum.accumulate(flat - i + frec * _BIG) - frec * _BIG + i
-        changed = (fixed != flat).reshape(-1, 6)
+        # strictly increasing within a recording (resample.increasing: the fix-up rescaled label lists get too)
+        fixed, changed = increasing(m.reshape(-1), np.repeat(rec, 6))
+        changed = changed.reshape(-1, 6)
         m = fixed.reshape(-1, 6)
         keep = m[:, 5] <= lengths[rec] - 1                      # increasing: what does not fit is a recording's tail
         m, rec, changed = m[keep], rec[keep], changed[keep]

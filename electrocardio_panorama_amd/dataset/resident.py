@@ -18,6 +18,7 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
+from .. import resample
 from ..synth import LEAD_THETA
 from . import marks
 from .tianchi import BEAT_LEN, EcgTianChiInterval, _lead_plan
@@ -38,6 +39,46 @@ def check_cfg(cfg):
     if cfg.DATA.get('synthetic', False):
         raise ValueError("DATA.device_resident with DATA.synthetic: synthetic batches have no recordings to keep on the device")
     marks.check_cfg(cfg)                                   # DATA.auto_marks needs DATA.mark_table
+    source_plan(cfg)                                       # DATA.source_rate: whole rates, a ratio nef_resample takes
+
+
+class SourcePlan(NamedTuple):
+    """DATA.source_rate read: the two rates, their ratio and the filter's two parameters."""
+    source_rate: int
+    sample_rate: int
+    up: int
+    down: int
+    zeros: int
+    beta: float
+
+
+def source_plan(cfg, need_resident=True):
+    """None with DATA.source_rate off (0, or DATA.sample_rate itself), else the SourcePlan.  ValueError: the key without
+    DATA.device_resident (the loaders; the store itself does not ask), a rate that is not a whole positive number of Hz, a ratio or a
+    filter outside nef_resample's limits."""
+    src = cfg.DATA.get('source_rate', 0)
+    if isinstance(src, bool) or not isinstance(src, (int, float)) or src != src or src != int(src) or src < 0:
+        raise ValueError(f"DATA.source_rate = {src!r}: a whole number of Hz, or 0 for off; non-integer and negative rates are not resampled")
+    src = int(src)
+    if src == 0:
+        return None
+    if need_resident and not cfg.DATA.get('device_resident', False):
+        raise ValueError("DATA.source_rate resamples the recordings of the device-resident store: set DATA.device_resident (the host "
+                         "loader stays file based; `python -m electrocardio_panorama_amd.mark_net --resample DIR` writes files for it)")
+    try:
+        dst = resample.check_rate("DATA.sample_rate", cfg.DATA.get('sample_rate', 500.0))
+    except ValueError as e:
+        raise ValueError(f"{e}; DATA.source_rate = {src} needs an integer DATA.sample_rate") from None
+    if src == dst:
+        return None
+    zeros, beta = cfg.DATA.get('resample_zeros', 16), cfg.DATA.get('resample_beta', 8.6)
+    if isinstance(zeros, bool) or not isinstance(zeros, int) or zeros < 1:
+        raise ValueError(f"DATA.resample_zeros = {zeros!r}: an integer >= 1")
+    if isinstance(beta, bool) or not isinstance(beta, (int, float)) or not 0.0 <= float(beta) < float('inf'):
+        raise ValueError(f"DATA.resample_beta = {beta!r}: a finite number >= 0")
+    up, down = resample.ratio(src, dst)
+    resample.check_ratio(up, down, zeros, f"DATA.source_rate {src}", f"DATA.sample_rate {dst}")
+    return SourcePlan(src, dst, up, down, zeros, float(beta))
 
 
 def _pack(name, sig):
@@ -72,12 +113,20 @@ class ResidentTianchi:
     six lists are made on the device from a timing table (dataset/marks.py: detect, labels_from_peaks).  `marks` is a [6, 2] table, a
     (table, MarkParams) pair or the path of a table file; it needs a HIP `device`.  A recording that gets no labels raises a ValueError
     naming it; with cfg.DATA.auto_marks_skip it is dropped from `names` and counted in one warning.  `auto_report` holds the counts
-    (None on an annotated store)."""
+    (None on an annotated store).
+
+    cfg.DATA.source_rate (not 0, not DATA.sample_rate): the files hold recordings at that rate.  They are packed and uploaded as above,
+    resampled on the device to DATA.sample_rate (resample.design; ops.resample, one launch per chunk) into a float32 `signal` with new
+    `lengths` and `offsets`, and the raw buffer is released; annotated label lists are rescaled on the host (resample.rescale_all) and
+    checked again, auto marks are detected on the resampled signal.  It needs a HIP `device`.  `source_rate` (0: the files were at the
+    model's rate), `raw_lengths` (the files' lengths), `source` (the SourcePlan, or None) and `resample_report` (None when off) stay."""
 
     def __init__(self, cfg, phase, device=None, marks=None):
         ds = EcgTianChiInterval(cfg, phase)
         self.cfg, self.phase, self.names = cfg, phase, list(ds.dataset)
         self.auto_report = None
+        self.source = source_plan(cfg, need_resident=False)
+        self.source_rate, self.resample_report = 0 if self.source is None else self.source.source_rate, None
         if not self.names:
             raise ValueError(f"DATA.device_resident: the {phase} label list is empty")
         spec = marks
@@ -104,12 +153,47 @@ class ResidentTianchi:
         flat = torch.from_numpy(np.concatenate([s.reshape(-1) for s in sigs]))
         dev = torch.device('cpu' if device is None else device)
         self.signal = flat if dev.type == 'cpu' else flat.to(dev)
+        self.raw_lengths = self.lengths
+        if self.source is not None:
+            self._resample()
         if spec is not None:
             self._auto_mark(spec, bool(cfg.DATA.get('auto_marks_skip', False)))
             return
-        self.labels = [np.concatenate([lab[k] for _, lab in items]) for k in range(6)]
-        self.label_offsets = [np.concatenate([[0], np.cumsum([lab[k].size for _, lab in items])]).astype(np.int64) for k in range(6)]
+        if self.source is not None:
+            self._rescale_labels([lab for _, lab in items])
+        else:
+            self.labels = [np.concatenate([lab[k] for _, lab in items]) for k in range(6)]
+            self.label_offsets = [np.concatenate([[0], np.cumsum([lab[k].size for _, lab in items])]).astype(np.int64) for k in range(6)]
         self.n_p_on = np.diff(self.label_offsets[0])
+
+    def _resample(self, budget=1 << 25):
+        """`signal` from source.source_rate to source.sample_rate on the device: chunks of whole recordings of at most `budget` output
+        samples, one ops.resample launch each, all into one float32 buffer that replaces the raw one."""
+        from .. import ops
+        src = self.source
+        if not self.signal.is_cuda:
+            raise RuntimeError("DATA.source_rate resamples on a HIP device only: build the store on one (no CPU path)")
+        taps, first = resample.design(src.up, src.down, src.zeros, src.beta)
+        lengths = resample.out_len(self.raw_lengths, src.up, src.down)
+        offsets = np.concatenate([[0], np.cumsum(8 * lengths)]).astype(np.int64)
+        out = torch.empty(int(offsets[-1]), dtype=torch.float32, device=self.signal.device)
+        taps_d, first_d = torch.from_numpy(taps).to(out.device), torch.from_numpy(first).to(out.device)
+        chunks = marks._chunks((8 * lengths).tolist(), int(budget))
+        for a, b in chunks:
+            table = np.stack([self.offsets[a:b], self.raw_lengths[a:b], offsets[a:b], np.full(b - a, 8, dtype=np.int64)], axis=1)
+            ops.resample(self.signal, torch.from_numpy(np.ascontiguousarray(table, dtype=np.int64)), out, taps_d, first_d, src.up, src.down)
+        self.signal, self.lengths, self.offsets = out, lengths, offsets
+        self.resample_report = {'recordings': len(self.names), 'source_rate': src.source_rate, 'sample_rate': src.sample_rate, 'up': src.up,
+                                'down': src.down, 'taps': int(taps.shape[1]), 'launches': len(chunks), 'adjusted': 0}
+
+    def _rescale_labels(self, labs):
+        """`labels` / `label_offsets` from the annotated lists on the resampled time axis (resample.rescale_all: every recording in one
+        pass), checked against the new lengths."""
+        self.labels, self.label_offsets, moved = resample.rescale_all(labs, self.source.up, self.source.down)
+        self.resample_report['adjusted'] = moved
+        for i, name in enumerate(self.names):
+            self._check_labels(name, [self.labels[k][self.label_offsets[k][i]:self.label_offsets[k][i + 1]] for k in range(6)],
+                               int(self.lengths[i]))
 
     def _auto_mark(self, spec, skip):
         """Fill labels, label_offsets and n_p_on from the signals (dataset/marks.py); recordings without labels raise, or leave with `skip`."""
@@ -139,7 +223,7 @@ class ResidentTianchi:
                           f"were dropped (first: {self.names[int(bare[0])]})")
             self.signal = torch.cat([self.signal[self.offsets[i]:self.offsets[i + 1]] for i in keep.tolist()])
             self.names = [self.names[i] for i in keep.tolist()]
-            self.lengths = self.lengths[keep]
+            self.lengths, self.raw_lengths = self.lengths[keep], self.raw_lengths[keep]
             self.offsets = np.concatenate([[0], np.cumsum(8 * self.lengths)]).astype(np.int64)
             offsets = [np.concatenate([[0], np.cumsum(beats[keep])]).astype(np.int64) for _ in range(6)]      # bare recordings hold no marks
         self.labels, self.label_offsets = labels, offsets

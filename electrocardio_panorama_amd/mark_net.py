@@ -1,5 +1,5 @@
 """`python -m electrocardio_panorama_amd.mark_net --config-file F (--fit TABLE.json [--form ratio|affine] | --compare TABLE.json |
---write DIR TABLE.json [--phase test])` -- no counterpart in the reference, whose label lists come from an annotation tool: make the six
+--write DIR TABLE.json | --resample DIR [--phase test])` -- no counterpart in the reference, whose label lists come from an annotation tool: make the six
 'P on' .. 'T off' lists of recordings from their signals (dataset/marks.py).
 
 --fit      detect the QRS complexes of the annotated train list on the device (the detector's windows follow DATA.sample_rate) and fit the
@@ -8,6 +8,10 @@
            annotator in samples, and the share of annotated beats that were matched.
 --write    mark the phase's recordings from their signals alone and write `<id>.json` in the reference's six-key format into DIR, so the
            host loader -- and the reference itself -- can train on them (DATA.train_label_root = DIR).
+--resample with DATA.source_rate: resample the phase's recordings to DATA.sample_rate on the device (resample.py) and write
+           each as `<id>.npy`, float32 [8, len'], into DIR; for an annotated list also `<id>.json` with the rescaled marks in the
+           six-key format, so the host loader -- and the reference itself -- train on what the device path sees (DATA.train_data_root =
+           DATA.train_label_root = DIR, DATA.source_rate 0).  With DATA.auto_marks the marks written are the detector's.
 
 One rank only."""
 import argparse
@@ -70,6 +74,25 @@ def write(cfg, out_dir, table_path, phase='test', device='cuda:0'):
     return store.auto_report
 
 
+def resample_to(cfg, out_dir, phase='test', device='cuda:0'):
+    """Write the phase's recordings at DATA.sample_rate, and their marks, into out_dir; returns the store's resample_report."""
+    _one_rank(cfg)
+    store = ResidentTianchi(cfg, phase, torch.device(device))
+    if store.source is None:
+        raise ValueError("mark_net --resample: DATA.source_rate is off (0, or DATA.sample_rate itself); there is nothing to resample")
+    os.makedirs(out_dir, exist_ok=True)
+    signal = store.signal.cpu().numpy()
+    for i, name in enumerate(store.names):
+        stem = name[:-len('.json')] if name.endswith('.json') else name
+        np.save(os.path.join(out_dir, stem + '.npy'), signal[store.offsets[i]:store.offsets[i + 1]].reshape(8, -1))
+        doc = {key: store.labels[k][store.label_offsets[k][i]:store.label_offsets[k][i + 1]].tolist() for k, key in enumerate(marks.LABEL_KEYS)}
+        with open(os.path.join(out_dir, stem + '.json'), 'w') as f:
+            json.dump(doc, f)
+    print('resampled {recordings} recordings from {source_rate} Hz to {sample_rate} Hz ({up}/{down}, {taps} taps a phase), {adjusted} marks '
+          'adjusted'.format(**store.resample_report))
+    return store.resample_report
+
+
 def run(argv=None):
     parser = argparse.ArgumentParser(description='marks for unannotated ecg recordings')
     parser.add_argument('--config-file', default="", metavar="FILE", help="path to config file", type=str)
@@ -77,6 +100,7 @@ def run(argv=None):
     what.add_argument('--fit', metavar="TABLE.json", help="fit the timing table on the annotated train list")
     what.add_argument('--compare', metavar="TABLE.json", help="compare the table's marks with the annotated test list")
     what.add_argument('--write', nargs=2, metavar=("DIR", "TABLE.json"), help="write <id>.json label files for the phase's recordings")
+    what.add_argument('--resample', metavar="DIR", help="with DATA.source_rate: write the recordings at DATA.sample_rate, and their marks")
     parser.add_argument('--form', default='ratio', choices=marks.FORMS)
     parser.add_argument('--phase', default='test', choices=('train', 'test'))
     parser.add_argument('opts', nargs=argparse.REMAINDER, help="KEY VALUE overrides")
@@ -89,6 +113,8 @@ def run(argv=None):
         return fit(cfg, args.fit, form=args.form)
     if args.compare:
         return compare(cfg, args.compare)
+    if args.resample:
+        return resample_to(cfg, args.resample, phase=args.phase)
     return write(cfg, args.write[0], args.write[1], phase=args.phase)
 
 

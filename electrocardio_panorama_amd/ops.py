@@ -10,6 +10,7 @@ import itertools
 import os
 from typing import NamedTuple, Optional
 
+import numpy as np
 import torch
 from . import _env
 
@@ -2463,6 +2464,81 @@ def mark_peaks(env, table, r=100, seg=1000, frac=0.125, max_peaks=256, max_len=N
     _lib.check(L.nef_mark_peaks(C.byref(A), _stream()), "nef_mark_peaks")
     _done(ev)
     return peaks, count, level
+
+
+RESAMPLE_TILE = 1024      # NEF_RESAMPLE_TILE (include/nefnet_hip.h): outputs per workgroup of nef_resample
+RESAMPLE_MAX_UP, RESAMPLE_MAX_K, RESAMPLE_MAX_RATIO = 1024, 512, 8
+RESAMPLE_MAX_ROWS = 65535  # table rows, and signals a table row: a grid's z and y extents
+
+
+def resample(src, table, dst, taps, first, up, down, max_out_len=None, max_rows=None):
+    """Resample lead-major rows of `src` in time by up / down into `dst` (nef_resample, include/nefnet_hip.h).  Every row (in_offset, len,
+    out_offset, rows) of the int64 [N, 4] `table` names `rows` signals [rows, len] of the flat int16 / float32 device buffer `src`; they
+    come out as [rows, out_len] float32 at out_offset of the flat float32 device buffer `dst`, out_len = (len * up + down - 1) // down:
+    y[m] = float32(sum_k taps[p, k] * x[clamp(i0 + first[p] + k, 0, len - 1)]), i0 = m * down // up, p = m * down % up, in fp64 and
+    ascending k.  `taps` (float64 [up, K]) and `first` (int32 [up]) are resample.design's table, numpy or torch, host or device.  `dst` is
+    written in place at the rows' positions only and returned.  A host table is checked against both buffers here and copied; a device
+    table needs `max_out_len` and `max_rows` (the launch is sized on the host), and a row of it that would leave a buffer writes nothing.
+    One launch on the current stream, capturable with device tables."""
+    _check_signal(src, "resample")
+    if not torch.is_tensor(dst) or dst.dtype != torch.float32 or dst.dim() != 1 or dst.numel() < 1 or not dst.is_contiguous():
+        raise TypeError("dst must be a non-empty contiguous 1-D float32 tensor")
+    if not dst.is_cuda or dst.device != src.device:
+        raise ValueError(f"dst is on {dst.device}, src on {src.device}")
+    up, down = _mark_int("up", up, 1, RESAMPLE_MAX_UP), _mark_int("down", down, 1, 1 << 30)
+    if down > RESAMPLE_MAX_RATIO * up:
+        raise ValueError(f"down = {down} is above {RESAMPLE_MAX_RATIO} x up = {up}")
+    dev = src.device
+    taps = torch.from_numpy(np.ascontiguousarray(taps)) if isinstance(taps, np.ndarray) else taps
+    first = torch.from_numpy(np.ascontiguousarray(first)) if isinstance(first, np.ndarray) else first
+    if not torch.is_tensor(taps) or taps.dtype != torch.float64 or taps.dim() != 2 or taps.shape[0] != up or \
+            not 1 <= taps.shape[1] <= RESAMPLE_MAX_K:
+        raise ValueError(f"taps must be float64 [up = {up}, K in 1..{RESAMPLE_MAX_K}], got "
+                         f"{getattr(taps, 'dtype', type(taps))} {tuple(getattr(taps, 'shape', ()))}")
+    if not torch.is_tensor(first) or first.dtype != torch.int32 or tuple(first.shape) != (up,):
+        raise ValueError(f"first must be int32 [up = {up}], got {getattr(first, 'dtype', type(first))} {tuple(getattr(first, 'shape', ()))}")
+    for name, t in (("taps", taps), ("first", first)):
+        if t.is_cuda and t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, src on {dev}")
+    K = int(taps.shape[1])
+    taps, first = taps.contiguous().to(dev, non_blocking=True), first.contiguous().to(dev, non_blocking=True)
+    if not torch.is_tensor(table) or table.dtype != torch.int64:
+        raise TypeError(f"table must be an int64 tensor, got {getattr(table, 'dtype', type(table))}")
+    if table.dim() != 2 or table.shape[1] != 4 or table.shape[0] < 1 or not table.is_contiguous():
+        raise ValueError(f"table {tuple(table.shape)} is not a contiguous [rows >= 1, 4] table of (in_offset, len, out_offset, rows)")
+    if table.shape[0] > RESAMPLE_MAX_ROWS:
+        raise ValueError(f"table has {table.shape[0]} rows; a launch takes at most {RESAMPLE_MAX_ROWS}")
+    if table.is_cuda:
+        if table.device != dev:
+            raise ValueError(f"table is on {table.device}, not on {dev}")
+        if max_out_len is None or max_rows is None:
+            raise ValueError("a device table needs max_out_len and max_rows: the launch is sized on the host")
+        max_out_len, max_rows = _mark_int("max_out_len", max_out_len, 1, MARK_MAX_LEN), _mark_int("max_rows", max_rows, 1, RESAMPLE_MAX_ROWS)
+    else:
+        off, ln, ooff, rows = table[:, 0], table[:, 1], table[:, 2], table[:, 3]
+        bad = (ln < 1) | (ln > MARK_MAX_LEN) | (rows < 1) | (rows > RESAMPLE_MAX_ROWS) | (off < 0) | (ooff < 0)
+        oln = (ln.clamp(1, MARK_MAX_LEN) * up + down - 1) // down
+        r = rows.clamp(1, RESAMPLE_MAX_ROWS)
+        bad = bad | (oln > MARK_MAX_LEN) | (off + r * ln.clamp(1, MARK_MAX_LEN) > src.numel()) | (ooff + r * oln > dst.numel())
+        if max_out_len is not None:
+            bad = bad | (oln > _mark_int("max_out_len", max_out_len, 1, MARK_MAX_LEN))
+        if max_rows is not None:
+            bad = bad | (rows > _mark_int("max_rows", max_rows, 1, RESAMPLE_MAX_ROWS))
+        if bool(bad.any()):
+            i = int(bad.nonzero()[0, 0])
+            raise ValueError(f"table row {i} {table[i].tolist()} leaves src ({src.numel()} elements), dst ({dst.numel()}), "
+                             f"max_out_len {max_out_len} or max_rows {max_rows}")
+        max_out_len = int(oln.max()) if max_out_len is None else max_out_len
+        max_rows = int(rows.max()) if max_rows is None else max_rows
+        table = table.to(dev, non_blocking=True)
+    L = _lib.load()
+    ev = _hbm("resample", src, table, dst)
+    A = _lib.ResampleArgs(src=_p(src), table=_p(table), dst=_p(dst), taps=_p(taps), first=_p(first), src_elems=src.numel(),
+                          dst_elems=dst.numel(), max_out_len=max_out_len, N=table.shape[0], max_rows=max_rows, up=up, down=down, K=K,
+                          dtype=0 if src.dtype == torch.int16 else 1)
+    _lib.check(L.nef_resample(C.byref(A), _stream()), "nef_resample")
+    _done(ev)
+    return dst
 
 
 LOSS_SEG_TILE = 1024      # NEF_LOSS_SEG_TILE (include/nefnet_hip.h): positions per block of the two segment-weight kernels

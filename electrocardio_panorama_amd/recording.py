@@ -14,7 +14,8 @@ from typing import NamedTuple, Optional
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, resample
+from .dataset import marks
 from .dataset.resident import RecordingPlan, check_leads, recording_plan, stage_to_device
 from .synth import LEAD_THETA
 
@@ -43,6 +44,16 @@ class Synthesis(NamedTuple):
     plan: RecordingPlan
     score_leads: tuple
     views: Optional[torch.Tensor]       # fp32 [Bt, A, 512] with return_views, else None
+    native: Optional[torch.Tensor] = None       # native_rate on a resampled store: the flat fp32 buffer of the [A, raw_len_j] strips
+    native_offsets: Optional[np.ndarray] = None # int64 [N + 1]: recording j at [native_offsets[j], native_offsets[j + 1]) of `native`
+
+    @property
+    def native_signals(self):
+        """Per recording the [A, raw_len] strip at the store's source rate; `signals` when nothing was resampled."""
+        if self.native is None:
+            return self.signals
+        o, A = self.native_offsets, self.plan.A
+        return [self.native[int(o[j]):int(o[j + 1])].view(A, -1) for j in range(len(o) - 1)]
 
     @property
     def signals(self):
@@ -71,12 +82,51 @@ def chunks(plan, beats_per_pass):
     return out
 
 
-def synthesize(model, store, indices, input_leads, query_thetas=None, score_leads=None, fill="nan", beats_per_pass=256, return_views=False):
+def to_native_rate(store, out, out_offsets, lengths, raw_lengths, A, budget=1 << 25):
+    """The [A, len'] strips of `out` (recording j at out_offsets[j]) back at the store's source rate: resampled with the swapped ratio
+    (resample.design(down, up); one ops.resample per chunk of whole recordings, rows = A, fp32 in) and cut to raw_len columns -- the way
+    back gives ceil(len' down / up) >= raw_len of them, so nothing has to be held at the edge; a recording for which that is raw_len
+    itself is written in place, the others pass through a scratch buffer.  NaNs spread as the formula says: by at most
+    K samples.  Returns (flat fp32 buffer, int64 offsets [N + 1])."""
+    src = store.source
+    resample.check_ratio(src.down, src.up, src.zeros, f"DATA.sample_rate {src.sample_rate}", f"DATA.source_rate {src.source_rate}")
+    taps, first = resample.design(src.down, src.up, src.zeros, src.beta)
+    dev = out.device
+    taps_d, first_d = torch.from_numpy(taps).to(dev), torch.from_numpy(first).to(dev)
+    back = resample.out_len(lengths, src.down, src.up)
+    noff = np.concatenate([[0], np.cumsum(A * raw_lengths)]).astype(np.int64)
+    native = torch.empty(int(noff[-1]), dtype=torch.float32, device=dev)
+    exact = back == raw_lengths                          # these land in `native` as they are; the others go through `tmp` and are cut
+    tmp = None
+    for a, b in marks._chunks((A * back).tolist(), int(budget)):
+        toff = np.concatenate([[0], np.cumsum(np.where(exact[a:b], 0, A * back[a:b]))]).astype(np.int64)
+        for direct in (True, False):
+            rows = np.flatnonzero(exact[a:b] == direct)
+            if not rows.size:
+                continue
+            if not direct and (tmp is None or tmp.numel() < int(toff[-1])):
+                tmp = torch.empty(int(toff[-1]), dtype=torch.float32, device=dev)
+            table = np.stack([out_offsets[a:b][rows], lengths[a:b][rows], (noff[a:b] if direct else toff[:-1])[rows],
+                              np.full(rows.size, A, dtype=np.int64)], axis=1)
+            ops.resample(out, torch.from_numpy(np.ascontiguousarray(table, dtype=np.int64)), native if direct else tmp, taps_d, first_d,
+                         src.down, src.up)
+            if not direct:
+                for r in rows.tolist():
+                    n, raw, j = int(back[a + r]), int(raw_lengths[a + r]), a + r
+                    native[int(noff[j]):int(noff[j + 1])].view(A, raw).copy_(tmp[int(toff[r]):int(toff[r + 1])].view(A, n)[:, :raw])
+    return native, noff
+
+
+def synthesize(model, store, indices, input_leads, query_thetas=None, score_leads=None, fill="nan", beats_per_pass=256, return_views=False,
+               native_rate=False):
     """The recordings `indices` of `store` (a ResidentTianchi on the model's device) at the angles query_thetas ([A, 2]; None: the 12 rows
     of LEAD_THETA), predicted from their `input_leads`.  score_leads: per angle the lead 0..11 that is its truth, or -1 (None: 0..11 with
     the default angles, else none).  fill: 'nan' or 'bridge' for the positions of a beat behind its 512-sample row (ops.beat_stitch).
     A beat whose range is not finite or is flat (hi == lo) has no normalised form: its input rows go to the model as zeros -- its NaNs
-    would spoil the chunk's shared activation scales -- and its output is what the stitch makes of that range (NaN, or the constant lo)."""
+    would spoil the chunk's shared activation scales -- and its output is what the stitch makes of that range (NaN, or the constant lo).
+    native_rate: on a store that was resampled (DATA.source_rate) the strips are also handed back at the source rate, [A, raw_len] each
+    (Synthesis.native, .native_signals: to_native_rate); the statistics are still taken at the model's rate.  On any other store it
+    changes nothing."""
     if fill not in ops.STITCH_FILLS:
         raise ValueError(f"fill must be one of {ops.STITCH_FILLS}, got {fill!r}")
     leads = check_leads(input_leads)
@@ -119,4 +169,8 @@ def synthesize(model, store, indices, input_leads, query_thetas=None, score_lead
             views_all[r0:r1] = views
     beat_table, rec_table, offs = stage_to_device((plan.stitch, plan.recordings, plan.out_offsets[:-1]), dev)
     stats = ops.recording_stats(out, store.signal, beat_table, rec_table, score, fill, offs)
-    return Synthesis(out=out, range=rng, stats=stats, plan=plan, score_leads=tuple(score), views=views_all)
+    native, noff = None, None
+    if native_rate and getattr(store, 'source', None) is not None:
+        idx = np.asarray(list(indices), dtype=np.int64).reshape(-1)
+        native, noff = to_native_rate(store, out, plan.out_offsets[:-1], store.lengths[idx], store.raw_lengths[idx], A)
+    return Synthesis(out=out, range=rng, stats=stats, plan=plan, score_leads=tuple(score), views=views_all, native=native, native_offsets=noff)

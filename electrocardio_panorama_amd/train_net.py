@@ -51,6 +51,9 @@ def build_loaders(cfg, batch_size=32, phases=('train', 'test')):
     elif cfg.DATA.get('auto_marks', False):
         from .dataset import marks
         marks.check_cfg(cfg)                              # DATA.auto_marks marks the resident store only: ValueError
+    elif cfg.DATA.get('source_rate', 0):
+        from .dataset import resident as res
+        res.source_plan(cfg)                              # DATA.source_rate resamples the resident store only: ValueError
     if cfg.DATA.get('synthetic', False):
         for ph in phases:
             if ph == 'train':

@@ -1280,6 +1280,55 @@ typedef struct nef_mark_peaks_args {
 int nef_mark_peaks(const nef_mark_peaks_args* a, nef_stream_t stream);
 size_t nef_mark_peaks_args_bytes(void);
 
+/* Resampling in time by a rational factor (resample.py; dataset/resident.py: DATA.source_rate): a polyphase FIR that
+ * takes recordings stored at another rate to the model's, and synthesised strips back.  Capturable and stateless, no atomics, no scratch,
+ * one writer per element; a row's output is a function of that row alone.
+ *
+ * Rates are positive integers in Hz: g = gcd(src, dst), up = dst / g, down = src / g; a row of len samples gives
+ * out_len = (len * up + down - 1) / down.  The filter is designed on the host in fp64 (resample.design(up, down, zeros, beta)):
+ *   m = max(up, down), c = zeros * m, N = 2 c + 1, h[n] = sinc((n - c) / m) * kaiser(N, beta)[n]
+ *   for phase p in [0, up): first[p] = ceil((p - c) / up), cnt[p] = floor((p + c) / up) - first[p] + 1, K = max cnt
+ *   raw[p, k] = h[p + c - (first[p] + k) * up] for k < cnt[p], else 0.0;  taps[p, k] = raw[p, k] / (the sum of raw[p, :] in ascending k)
+ * -- normalised per phase, so that a constant row comes out as that constant.  The device receives `taps` (fp64 [up, K]) and `first`
+ * (int32 [up]) and forms, for output m of a row x with i0 = (m * down) / up and p = (m * down) % up,
+ *   y[m] = (float) sum_{k = 0 .. K-1} taps[p, k] * (double) x[clamp(i0 + first[p] + k, 0, len - 1)]
+ * in ascending k from +0.0, every multiply and every add rounded on its own (fp64, no contraction).  The ends are edge replication; a
+ * zero-padded tap still multiplies its clamped sample, so a NaN spreads exactly as the formula says.  The result is defined bit for bit
+ * by the table the caller hands in.
+ *
+ * `table` holds N int64 rows [0] offset in `src` of `rows` lead-major signals [rows, len]  [1] len  [2] offset in `dst` of their
+ * [rows, out_len] fp32 results  [3] rows.  One 256-thread workgroup per (table row, signal, tile of NEF_RESAMPLE_TILE outputs): the input
+ * stretch of the tile is staged in LDS once, clamped, at any offset alignment and any len >= 1; the taps come from LDS when
+ * up * K <= NEF_RESAMPLE_LDS_TAPS and from global memory otherwise, in the same order.  A row that would leave `src` or `dst`, whose len is
+ * below 1, whose rows are outside 1..max_rows or whose out_len is above max_out_len (the grid covers max_rows x max_out_len) writes
+ * nothing; the check is inside the launch, per block.  `first` is not trusted either: any content gives the formula's sum.
+ * N or max_rows outside 1..65535, max_out_len outside 1..2^31 - 65536, up outside 1..NEF_RESAMPLE_MAX_UP, K outside 1..NEF_RESAMPLE_MAX_K,
+ * down outside 1..NEF_RESAMPLE_MAX_RATIO * up, dtype outside {0, 1}, src_elems or dst_elems < 1: NEF_E_SHAPE; a NULL pointer: NEF_E_NULL;
+ * src not 16-byte aligned, table or taps not 8-byte, dst or first not 4-byte aligned: NEF_E_UNSUPPORTED. */
+#define NEF_RESAMPLE_TILE 1024
+#define NEF_RESAMPLE_MAX_UP 1024
+#define NEF_RESAMPLE_MAX_K 512
+#define NEF_RESAMPLE_MAX_RATIO 8
+#define NEF_RESAMPLE_LDS_TAPS 4096
+typedef struct nef_resample_args {
+    const void* src;            /* int16 or fp32 elements */
+    const int64_t* table;       /* [N, 4] */
+    float* dst;                 /* dst_elems floats */
+    const double* taps;         /* [up, K] */
+    const int32_t* first;       /* [up] */
+    int64_t src_elems;
+    int64_t dst_elems;
+    int64_t max_out_len;        /* no row's out_len is larger */
+    int32_t N;
+    int32_t max_rows;           /* no table row holds more signals */
+    int32_t up;
+    int32_t down;
+    int32_t K;
+    int32_t dtype;              /* 0: int16, 1: fp32 */
+} nef_resample_args;
+int nef_resample(const nef_resample_args* a, nef_stream_t stream);
+size_t nef_resample_args_bytes(void);
+
 /* ---------------------------------------------------------------------------------------------
  * SGD with momentum over a flat buffer.  codes/solver/optim_scheduler.py:10 (torch.optim.SGD semantics:
  * first step buf = g, afterwards buf = mu*buf + g; p -= lr*buf).  g is multiplied by gscale first

@@ -19,6 +19,13 @@ alternating rounds of fresh processes build the annotated store and the auto-mar
 also times marks.detect alone and the two kernels on cold data with their algorithmic bytes.  The line says how many recordings got labels.
 
     python tools/bench_loader.py --resident --auto-marks [--rounds 3] [--n 2048] [--out profiles/r29_marks_bench_line.json]
+
+`--resident --source-rate R [R ...]` times DATA.source_rate (resample.py; nef_resample): per rate the tree is written at R Hz -- the same
+beats, 5000 R / 500 samples a recording -- and `--rounds` alternating rounds of fresh processes build the store of those files with the key
+off and with DATA.source_rate = R; the second also times nef_resample alone on cold data, with its algorithmic bytes, at the store's own
+ratio (taps in LDS) and at 500 / 257 on the same buffer (taps in global memory).  The line says whether the key-on build stays within 10 %.
+
+    python tools/bench_loader.py --resident --source-rate 1000 360 [--rounds 3] [--n 2048] [--out profiles/r31_resample_bench_line.json]
 """
 import argparse
 import json
@@ -37,19 +44,23 @@ import torch         # noqa: E402
 BATCHES = (32, 256)
 
 
-def make_tree(root, n, seed=0):
-    """n recordings: smooth 8-lead signals with a beat every 600..900 samples and plausible wave boundaries."""
+def make_tree(root, n, seed=0, rate=500):
+    """n recordings: smooth 8-lead signals with a beat every 600..900 samples and plausible wave boundaries -- at 500 Hz; `rate` writes the
+    same ten seconds at another rate (every count of samples times rate / 500)."""
     rng = np.random.default_rng(seed)
     os.makedirs(os.path.join(root, "npy"), exist_ok=True)
     os.makedirs(os.path.join(root, "json"), exist_ok=True)
     names = []
-    t = np.arange(5000)
+    k = rate / 500.0
+    q = lambda v: np.round(np.asarray(v) * k).astype(np.int64)      # noqa: E731
+    length = int(q(5000))
+    t = np.arange(length)
     for i in range(n):
-        period = int(rng.integers(600, 900))
-        p_on = np.arange(int(rng.integers(20, 100)), 5000 - period, period)
-        lab = {"P on": p_on, "P off": p_on + 60, "R on": p_on + 110, "R off": p_on + 170, "T on": p_on + 260, "T off": p_on + 400}
-        sig = np.zeros((8, 5000))
-        for c, w in ((85, 18), (140, 9), (330, 40)):
+        period = int(q(rng.integers(600, 900)))
+        p_on = np.arange(int(q(rng.integers(20, 100))), length - period, period)
+        lab = {"P on": p_on, "P off": p_on + q(60), "R on": p_on + q(110), "R off": p_on + q(170), "T on": p_on + q(260), "T off": p_on + q(400)}
+        sig = np.zeros((8, length))
+        for c, w in ((85 * k, 18 * k), (140 * k, 9 * k), (330 * k, 40 * k)):
             for p in p_on:
                 sig += rng.normal(1.0, 0.3, size=(8, 1)) * np.exp(-0.5 * ((t - p - c) / w) ** 2)
         sig += rng.normal(0, 0.01, size=sig.shape)
@@ -265,6 +276,85 @@ def leg_auto(a):
     return out
 
 
+def leg_rate(a):
+    """The store build with DATA.source_rate on, and nef_resample alone behind a cache flush: at the store's ratio (taps in LDS) and at
+    500 / 257 on the same raw buffer (taps in global memory)."""
+    from electrocardio_panorama_amd import ops, resample
+    from electrocardio_panorama_amd.dataset import marks, resident
+    torch.set_num_threads(1)
+    dev = torch.device("cuda", 0)
+    cfg = tree_cfg(a.tree, a.leads)
+    cfg.DATA.device_resident, cfg.DATA.source_rate = True, a.rate
+    store, sec = _timed_store(cfg, dev)
+    rep = store.resample_report
+    out = {"leg": "rate", "resampled_store_build_s": sec, "store_dtype": str(store.signal.dtype).replace("torch.", ""), "up": rep["up"],
+           "down": rep["down"], "taps_per_phase": rep["taps"], "launches": rep["launches"], "marks_adjusted": rep["adjusted"],
+           "store_device_bytes": store.device_bytes}
+    cfg.DATA.source_rate = 0
+    raw = resident.ResidentTianchi(cfg, "train", dev)
+    flush = torch.empty(512 << 20, dtype=torch.uint8, device=dev)
+    for tag, (up, down) in (("lds_taps", (rep["up"], rep["down"])), ("global_taps", (500, 257))):
+        taps, first = resample.design(up, down)
+        assert (taps.size <= 4096) == (tag == "lds_taps")
+        new = resample.out_len(raw.lengths, up, down)
+        a0, b0 = marks._chunks((8 * new).tolist(), 1 << 25)[0]
+        ooff = np.concatenate([[0], np.cumsum(8 * new[a0:b0])])
+        table = torch.from_numpy(np.ascontiguousarray(np.stack([raw.offsets[a0:b0], raw.lengths[a0:b0], ooff[:-1], np.full(b0 - a0, 8)], axis=1),
+                                                      dtype=np.int64)).to(dev)
+        dst = torch.empty(int(ooff[-1]), dtype=torch.float32, device=dev)
+        taps_d, first_d = torch.from_numpy(taps).to(dev), torch.from_numpy(first).to(dev)
+        us = []
+        for _ in range(6):
+            flush.zero_()
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            ops.resample(raw.signal, table, dst, taps_d, first_d, up, down, max_out_len=int(new[a0:b0].max()), max_rows=8)
+            e.record()
+            e.synchronize()
+            us.append(s.elapsed_time(e) * 1e3)
+        # algorithmic bytes: the rows read once, the results written once, the two tables
+        nbytes = int(8 * raw.lengths[a0:b0].sum()) * raw.signal.element_size() + int(ooff[-1]) * 4 + table.numel() * 8 + taps.nbytes + first.nbytes
+        t = float(np.median(us[1:]))                                    # the first: code load, allocator
+        out[f"resample_{tag}_cold_us"], out[f"resample_{tag}_bytes"] = round(t, 2), nbytes
+        out[f"resample_{tag}_tb_s"], out[f"resample_{tag}_ratio"] = round(nbytes / t * 1e-6, 4), f"{up}/{down}"
+    return out
+
+
+def drive_rate(a):
+    """Per rate: the tree at that rate, then `--rounds` alternating rounds of fresh processes -- the key-off build, the key-on build."""
+    line = {"recordings": a.n, "rounds": a.rounds, "rates": {}}
+    med = lambda v: v[1] if isinstance(v, list) else v      # noqa: E731
+    for rate in a.source_rate:
+        root = tempfile.mkdtemp(prefix="nef_rate_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
+        runs = []
+        try:
+            make_tree(root, a.n, rate=rate)
+            for leg in ["store", "rate"] * a.rounds:
+                cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg, "--tree", root, "--leads", str(a.leads), "--rate", str(rate)]
+                res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=a.leg_timeout)
+                if res.returncode != 0:
+                    raise RuntimeError(f"leg {leg} ended with exit code {res.returncode}")
+                runs.append(json.loads(res.stdout.strip().splitlines()[-1]))
+                print(json.dumps(runs[-1]), flush=True)
+        finally:
+            shutil.rmtree(root, ignore_errors=True)
+        one = {}
+        for key in sorted({k for r in runs for k in r}):
+            vals = [r[key] for r in runs if key in r]
+            if isinstance(vals[0], (int, float)) and len(set(vals)) > 1:
+                one[key] = [min(vals), float(np.median(vals)), max(vals)]
+            elif key != "leg":
+                one[key] = vals[0]
+        one["key_off_store_build_s"] = one.pop("annotated_store_build_s")
+        one["resampled_build_over_key_off"] = round(med(one["resampled_store_build_s"]) / med(one["key_off_store_build_s"]), 4)
+        one["resampled_build_within_10_percent"] = bool(one["resampled_build_over_key_off"] <= 1.10)
+        line["rates"][str(rate)] = one
+    print(json.dumps(line))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(line) + "\n")
+
+
 def drive_auto(a):
     """The table once, then `--rounds` alternating rounds of fresh processes: the annotated build, the auto-marked build."""
     root = tempfile.mkdtemp(prefix="nef_marks_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
@@ -343,17 +433,24 @@ def main():
     ap.add_argument("--leg-timeout", type=float, default=400.0)
     ap.add_argument("--out", default="")
     ap.add_argument("--auto-marks", action="store_true", help="with --resident: time DATA.auto_marks against the annotated store build")
-    ap.add_argument("--leg", choices=("workers", "resident", "fit", "store", "auto"), help="(internal) one leg of --resident in this process")
+    ap.add_argument("--source-rate", type=int, nargs="+", default=[], metavar="R",
+                    help="with --resident: time DATA.source_rate = R against the key-off build of the same files, per rate")
+    ap.add_argument("--leg", choices=("workers", "resident", "fit", "store", "auto", "rate"), help="(internal) one leg of --resident in this process")
+    ap.add_argument("--rate", type=int, default=500, help="(internal) the rate the tree of --leg rate was written at")
     ap.add_argument("--tree", default="", help="(internal) the tree --leg reads")
     a = ap.parse_args()
     if a.leg:
         if not torch.cuda.is_available():
             raise SystemExit("--resident needs a HIP device")
-        legs = {"workers": leg_workers, "resident": leg_resident, "fit": leg_fit, "store": leg_store, "auto": leg_auto}
+        legs = {"workers": leg_workers, "resident": leg_resident, "fit": leg_fit, "store": leg_store, "auto": leg_auto, "rate": leg_rate}
         print(json.dumps(legs[a.leg](a)))
         return
     if a.auto_marks and not a.resident:
         raise SystemExit("--auto-marks goes with --resident: the marks are made on the device-resident store")
+    if a.source_rate and (not a.resident or a.auto_marks):
+        raise SystemExit("--source-rate goes with --resident alone: the recordings are resampled on the device-resident store")
+    if a.resident and a.source_rate:
+        return drive_rate(a)
     if a.resident:
         return drive_auto(a) if a.auto_marks else drive_resident(a)
     root = tempfile.mkdtemp(prefix="nef_loader_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)

@@ -8,6 +8,11 @@ condition it judges is `synthesize`'s median time at most 10 % above the median 
 
     python tools/bench_recording.py [--rounds 3] [--n 2048] [--out profiles/r24_recording_bench_line.json]
 
+`--source-rate R` writes the tree at R Hz and builds the store with DATA.source_rate = R (resampled to 500 Hz on the device): every figure
+is then taken on the resampled store, and `synthesize(native_rate=True)` -- the strips handed back at R Hz -- is timed beside the plain one.
+
+    python tools/bench_recording.py --source-rate 1000 [--rounds 3] [--n 2048] [--out FILE]
+
 Not measured: real Tianchi at full size, more than one GPU, gen_net's file writing."""
 import argparse
 import json
@@ -37,6 +42,7 @@ def leg(a):
     torch.set_num_threads(1)
     dev = torch.device("cuda", 0)
     cfg = tree_cfg(a.tree, len(LEADS))
+    cfg.DATA.source_rate = a.source_rate
     torch.manual_seed(1234)
     model = build_model(cfg).float().to(dev).eval()
     model.panorama_dtype = a.leg
@@ -71,6 +77,11 @@ def leg(a):
             out[f"synthesize_s_p{bpp}"], out[f"batch_and_panorama_s_p{bpp}"] = round(s, 4), round(al, 4)
             out[f"recordings_per_s_p{bpp}"], out[f"beats_per_s_p{bpp}"] = round(len(store) / s, 1), round(plan.rec.size / s, 1)
             out[f"synthesize_over_alone_p{bpp}"] = round(s / al, 4)
+            if store.source is not None:                 # the strips also handed back at the source rate
+                native = lambda: recording.synthesize(model, store, idx, LEADS, beats_per_pass=bpp, native_rate=True)      # noqa: E731
+                timed(native)
+                tn = float(np.median([timed(native) for _ in range(a.repeats)]))
+                out[f"synthesize_native_rate_s_p{bpp}"], out[f"native_rate_over_plain_p{bpp}"] = round(tn, 4), round(tn / s, 4)
         # the three new launches alone on the first 1024 beats' worth of whole recordings, each behind a fill larger than every cache
         r0, r1 = recording.chunks(plan, 1024)[0]
         nrec = int(plan.rec[r1 - 1]) + 1
@@ -106,10 +117,11 @@ def drive(a):
     root = tempfile.mkdtemp(prefix="nef_recording_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
     runs = []
     try:
-        make_tree(root, a.n)
+        make_tree(root, a.n, rate=a.source_rate or 500)
         for _ in range(a.rounds):
             for dtype in ("fp32", "fp16"):
-                cmd = [sys.executable, os.path.abspath(__file__), "--leg", dtype, "--tree", root, "--repeats", str(a.repeats)]
+                cmd = [sys.executable, os.path.abspath(__file__), "--leg", dtype, "--tree", root, "--repeats", str(a.repeats),
+                       "--source-rate", str(a.source_rate)]
                 res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=a.leg_timeout)
                 if res.returncode != 0:
                     raise RuntimeError(f"leg {dtype} ended with exit code {res.returncode}")
@@ -118,6 +130,8 @@ def drive(a):
     finally:
         shutil.rmtree(root, ignore_errors=True)
     line = {"recordings": a.n, "rounds": a.rounds, "input_leads": LEADS, "angles": 12}
+    if a.source_rate:
+        line["source_rate"] = a.source_rate
     for dtype in ("fp32", "fp16"):
         mine = [r for r in runs if r["leg"] == dtype]
         for key in sorted(mine[0]):
@@ -141,6 +155,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3, help="timed (alone, synthesize) pairs per beats_per_pass in a process")
     ap.add_argument("--leg-timeout", type=float, default=400.0)
     ap.add_argument("--out", default="")
+    ap.add_argument("--source-rate", type=int, default=0, metavar="R", help="write the tree at R Hz and resample it on the device")
     ap.add_argument("--leg", choices=("fp32", "fp16"), help="(internal) one panorama dtype in this process")
     ap.add_argument("--tree", default="", help="(internal) the tree --leg reads")
     a = ap.parse_args()
