@@ -208,6 +208,12 @@ class ResampleArgs(C.Structure):
                 ("max_out_len", i64), ("N", i32), ("max_rows", i32), ("up", i32), ("down", i32), ("K", i32), ("dtype", i32)]
 
 
+class SlidingMedianArgs(C.Structure):
+    """Mirror of `nef_sliding_median_args` (include/nefnet_hip.h)."""
+    _fields_ = [("src", p), ("table", p), ("dst", p), ("minuend", p), ("src_elems", i64), ("dst_elems", i64), ("minuend_elems", i64),
+                ("max_len", i64), ("N", i32), ("max_rows", i32), ("h", i32), ("dtype", i32), ("minuend_dtype", i32), ("reserved0", i32)]
+
+
 class PackDesc(C.Structure):
     """Mirror of `nef_pack_desc` (include/nefnet_hip.h)."""
     _fields_ = [("w", p), ("wp", p), ("G", i32), ("Cog", i32), ("Cig", i32), ("K", i32), ("transpose_flip", i32),
@@ -343,6 +349,8 @@ SIGNATURES = {
     "nef_mark_peaks_args_bytes": (sz, []),
     "nef_resample": (i32, [C.POINTER(ResampleArgs), p]),
     "nef_resample_args_bytes": (sz, []),
+    "nef_sliding_median": (i32, [C.POINTER(SlidingMedianArgs), p]),
+    "nef_sliding_median_args_bytes": (sz, []),
     "nef_sgd_momentum": (i32, [p, p, p, i64, f32, f32, f32, i32, p, p, p, p]),
     "nef_adam": (i32, [p, p, p, p, i64, f32, C.c_double, C.c_double, f32, f32, f32, p, p, p, p, p]),
     "nef_update": (i32, [C.POINTER(UpdateArgs), p]),
@@ -434,7 +442,8 @@ def load():
                                ("nef_recording_stats_args", lib.nef_recording_stats_args_bytes(), RecordingStatsArgs),
                                ("nef_mark_envelope_args", lib.nef_mark_envelope_args_bytes(), MarkEnvelopeArgs),
                                ("nef_mark_peaks_args", lib.nef_mark_peaks_args_bytes(), MarkPeaksArgs),
-                               ("nef_resample_args", lib.nef_resample_args_bytes(), ResampleArgs)):
+                               ("nef_resample_args", lib.nef_resample_args_bytes(), ResampleArgs),
+                               ("nef_sliding_median_args", lib.nef_sliding_median_args_bytes(), SlidingMedianArgs)):
         if size != C.sizeof(mirror):
             raise NefLibraryError(f"{LIB_PATH}: {name} is {size} bytes, the binding mirrors {C.sizeof(mirror)}; rebuild with "
                                   "`python -m electrocardio_panorama_amd.csrc.build`")

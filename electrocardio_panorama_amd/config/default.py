@@ -87,6 +87,20 @@ _DEFAULTS = {
         "source_rate": 0,
         "resample_zeros": 16,          # zero crossings of the sinc on each side of its centre, at the lower of the two rates
         "resample_beta": 8.6,          # the Kaiser window's beta
+        # (not in the reference) with device_resident: clean the recordings on the device behind the resampling and in front of the
+        # detector (clean.py).  baseline_ms = [w1, w2] removes the baseline wander: the signal minus the w2-ms sliding
+        # median of its w1-ms sliding median (nef_sliding_median; [200, 600] is the usual pair, 101 and 301 samples at 500 Hz; windows
+        # in milliseconds at sample_rate, half widths 1..512 samples).  mains_hz = 50 or 60 removes the mains hum: a linear-phase
+        # band-stop mains_width_hz wide, a Kaiser-windowed FIR of mains_taps taps with unit gain at 0 Hz, run first through nef_resample
+        # at 1/1.  Either key makes the store float32, in the cleaned signal's units; lengths, offsets and annotated labels stay,
+        # auto_marks detects on the cleaned signal.  ValueError without device_resident (`mark_net --clean DIR` writes cleaned files for
+        # the host loader).  [] and 0: no launch, no buffer, the store stays int16 / float32 and the loaders, graphs and bits are what
+        # they were before the keys existed
+        "baseline_ms": [],
+        "mains_hz": 0.0,
+        "mains_width_hz": 6.0,         # the stop band's width: mains_hz -+ half of it
+        "mains_taps": 511,             # odd, 3..511
+        "mains_beta": 8.6,             # the Kaiser window's beta
     },
     "MODEL": {
         "model": "modelv2",            # 'model_nefnet' selects Nef-Net

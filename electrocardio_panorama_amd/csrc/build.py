@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 # conv_mfma.hip is compiled as four objects (-DNEF_MFMA_PART=1..4: see the top of that file), in parallel with the other sources
 MFMA_PARTS = 4
-SOURCES = ["conv_mfma.hip", "conv_h2.hip", "conv_h2w.hip", "conv_bww_glds.hip", "stem.hip", "elementwise.hip", "roi.hip", "convt_theta.hip", "pano_h.hip", "metrics.hip", "h2_tail.hip", "loss_ssim.hip", "loss_seg.hip", "loss_slope.hip", "loss_corr.hip", "locate.hip", "views.hip", "augment.hip", "noise_row.hip", "warp.hip", "beats.hip", "recording.hip", "lead_mask.hip", "marks.hip", "resample.hip"]
+SOURCES = ["conv_mfma.hip", "conv_h2.hip", "conv_h2w.hip", "conv_bww_glds.hip", "stem.hip", "elementwise.hip", "roi.hip", "convt_theta.hip", "pano_h.hip", "metrics.hip", "h2_tail.hip", "loss_ssim.hip", "loss_seg.hip", "loss_slope.hip", "loss_corr.hip", "locate.hip", "views.hip", "augment.hip", "noise_row.hip", "warp.hip", "beats.hip", "recording.hip", "lead_mask.hip", "marks.hip", "resample.hip", "median.hip"]
 LIB = os.path.join(HERE, "libnefnet_hip.so")
 # per-source extra flags.  Every source that issues matrix instructions is built WITHOUT SLP vectorisation: the packed-fp32
 # instructions it creates (v_pk_fma_f32 with op_sel on registers a ds_read_b128 has just returned, in conv_h2.hip's epilogue)

@@ -18,7 +18,7 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from .. import resample
+from .. import clean, resample
 from ..synth import LEAD_THETA
 from . import marks
 from .tianchi import BEAT_LEN, EcgTianChiInterval, _lead_plan
@@ -40,6 +40,7 @@ def check_cfg(cfg):
         raise ValueError("DATA.device_resident with DATA.synthetic: synthetic batches have no recordings to keep on the device")
     marks.check_cfg(cfg)                                   # DATA.auto_marks needs DATA.mark_table
     source_plan(cfg)                                       # DATA.source_rate: whole rates, a ratio nef_resample takes
+    clean.clean_plan(cfg)                                  # DATA.baseline_ms / DATA.mains_hz: windows and a band the kernels take
 
 
 class SourcePlan(NamedTuple):
@@ -119,7 +120,13 @@ class ResidentTianchi:
     resampled on the device to DATA.sample_rate (resample.design; ops.resample, one launch per chunk) into a float32 `signal` with new
     `lengths` and `offsets`, and the raw buffer is released; annotated label lists are rescaled on the host (resample.rescale_all) and
     checked again, auto marks are detected on the resampled signal.  It needs a HIP `device`.  `source_rate` (0: the files were at the
-    model's rate), `raw_lengths` (the files' lengths), `source` (the SourcePlan, or None) and `resample_report` (None when off) stay."""
+    model's rate), `raw_lengths` (the files' lengths), `source` (the SourcePlan, or None) and `resample_report` (None when off) stay.
+
+    cfg.DATA.baseline_ms / cfg.DATA.mains_hz (clean.py): behind the resampling and in front of the marks the recordings are cleaned on the
+    device, per chunk of whole recordings -- the mains band-stop first (ops.resample at 1/1 with clean.notch_taps' row), then the signal
+    minus the h2 sliding median of its h1 sliding median (ops.sliding_median, twice) -- into a float32 `signal`; `lengths`, `offsets`
+    and annotated labels stay, auto marks are detected on the cleaned signal.  It needs a HIP `device`.  `clean` holds the CleanPlan (None
+    with both keys off) and `clean_report` the recordings, h1, h2, the taps and the launch count (None when off)."""
 
     def __init__(self, cfg, phase, device=None, marks=None):
         ds = EcgTianChiInterval(cfg, phase)
@@ -127,6 +134,7 @@ class ResidentTianchi:
         self.auto_report = None
         self.source = source_plan(cfg, need_resident=False)
         self.source_rate, self.resample_report = 0 if self.source is None else self.source.source_rate, None
+        self.clean, self.clean_report = clean.clean_plan(cfg, need_resident=False), None
         if not self.names:
             raise ValueError(f"DATA.device_resident: the {phase} label list is empty")
         spec = marks
@@ -156,6 +164,8 @@ class ResidentTianchi:
         self.raw_lengths = self.lengths
         if self.source is not None:
             self._resample()
+        if self.clean is not None:
+            self._clean()
         if spec is not None:
             self._auto_mark(spec, bool(cfg.DATA.get('auto_marks_skip', False)))
             return
@@ -185,6 +195,40 @@ class ResidentTianchi:
         self.signal, self.lengths, self.offsets = out, lengths, offsets
         self.resample_report = {'recordings': len(self.names), 'source_rate': src.source_rate, 'sample_rate': src.sample_rate, 'up': src.up,
                                 'down': src.down, 'taps': int(taps.shape[1]), 'launches': len(chunks), 'adjusted': 0}
+
+    def _clean(self, budget=1 << 25):
+        """`signal` cleaned on the device (clean.py), in chunks of whole recordings of at most `budget` samples: the band-stop at
+        clean.mains_hz by one ops.resample at 1/1 per chunk into a fresh float32 buffer that replaces the one before; then per chunk
+        tmp = median_h1(signal) and out = signal - median_h2(tmp) by two ops.sliding_median launches, one `tmp` of at most a chunk,
+        `out` a fresh float32 store."""
+        from .. import ops
+        plan = self.clean
+        if not self.signal.is_cuda:
+            raise RuntimeError("DATA.baseline_ms / DATA.mains_hz clean on a HIP device only: build the store on one (no CPU path)")
+        dev = self.signal.device
+        chunks = marks._chunks((8 * self.lengths).tolist(), int(budget))
+        eight = np.full(len(self.names), 8, dtype=np.int64)
+        launches, K = 0, 0
+        if plan.mains_hz > 0:
+            taps, first = clean.notch_taps(plan.rate, plan.mains_hz, plan.width, plan.taps, plan.beta)
+            taps_d, first_d = torch.from_numpy(taps).to(dev), torch.from_numpy(first).to(dev)
+            out = torch.empty(int(self.offsets[-1]), dtype=torch.float32, device=dev)
+            for a, b in chunks:
+                table = np.stack([self.offsets[a:b], self.lengths[a:b], self.offsets[a:b], eight[a:b]], axis=1)
+                ops.resample(self.signal, torch.from_numpy(np.ascontiguousarray(table, dtype=np.int64)), out, taps_d, first_d, 1, 1)
+            self.signal, launches, K = out, launches + len(chunks), int(taps.shape[1])
+        if plan.h1 > 0:
+            out = torch.empty(int(self.offsets[-1]), dtype=torch.float32, device=dev)
+            tmp = torch.empty(int(max(self.offsets[b] - self.offsets[a] for a, b in chunks)), dtype=torch.float32, device=dev)
+            for a, b in chunks:
+                lo, hi = int(self.offsets[a]), int(self.offsets[b])
+                table = np.stack([self.offsets[a:b] - lo, self.lengths[a:b], eight[a:b]], axis=1)
+                table = torch.from_numpy(np.ascontiguousarray(table, dtype=np.int64))
+                part = self.signal[lo:hi]                                   # a chunk starts at a multiple of 8 elements: 16-byte aligned
+                ops.sliding_median(part, table, tmp[:hi - lo], plan.h1)
+                ops.sliding_median(tmp[:hi - lo], table, out[lo:hi], plan.h2, minuend=part)
+            self.signal, launches = out, launches + 2 * len(chunks)
+        self.clean_report = {'recordings': len(self.names), 'h1': plan.h1, 'h2': plan.h2, 'taps': K, 'launches': launches}
 
     def _rescale_labels(self, labs):
         """`labels` / `label_offsets` from the annotated lists on the resampled time axis (resample.rescale_all: every recording in one

@@ -1,5 +1,5 @@
 """`python -m electrocardio_panorama_amd.mark_net --config-file F (--fit TABLE.json [--form ratio|affine] | --compare TABLE.json |
---write DIR TABLE.json | --resample DIR [--phase test])` -- no counterpart in the reference, whose label lists come from an annotation tool: make the six
+--write DIR TABLE.json | --resample DIR | --clean DIR [--phase test])` -- no counterpart in the reference, whose label lists come from an annotation tool: make the six
 'P on' .. 'T off' lists of recordings from their signals (dataset/marks.py).
 
 --fit      detect the QRS complexes of the annotated train list on the device (the detector's windows follow DATA.sample_rate) and fit the
@@ -12,6 +12,9 @@
            each as `<id>.npy`, float32 [8, len'], into DIR; for an annotated list also `<id>.json` with the rescaled marks in the
            six-key format, so the host loader -- and the reference itself -- train on what the device path sees (DATA.train_data_root =
            DATA.train_label_root = DIR, DATA.source_rate 0).  With DATA.auto_marks the marks written are the detector's.
+--clean    with DATA.baseline_ms / DATA.mains_hz: clean the phase's recordings on the device (clean.py) -- behind the
+           resampling when DATA.source_rate is on -- and write them and their marks in the format of --resample, for the host loader and
+           the reference (DATA.baseline_ms [], DATA.mains_hz 0 and DATA.source_rate 0 there).  An error with both cleaning keys off.
 
 One rank only."""
 import argparse
@@ -21,6 +24,7 @@ import os
 import numpy as np
 import torch
 
+from .clean import clean_plan
 from .config import cfg, resolve_config_path
 from .dataset import marks
 from .dataset.resident import ResidentTianchi
@@ -74,12 +78,8 @@ def write(cfg, out_dir, table_path, phase='test', device='cuda:0'):
     return store.auto_report
 
 
-def resample_to(cfg, out_dir, phase='test', device='cuda:0'):
-    """Write the phase's recordings at DATA.sample_rate, and their marks, into out_dir; returns the store's resample_report."""
-    _one_rank(cfg)
-    store = ResidentTianchi(cfg, phase, torch.device(device))
-    if store.source is None:
-        raise ValueError("mark_net --resample: DATA.source_rate is off (0, or DATA.sample_rate itself); there is nothing to resample")
+def _write_store(store, out_dir):
+    """Every recording of the store as `<id>.npy`, float32 [8, len], and `<id>.json` with its six lists."""
     os.makedirs(out_dir, exist_ok=True)
     signal = store.signal.cpu().numpy()
     for i, name in enumerate(store.names):
@@ -88,9 +88,30 @@ def resample_to(cfg, out_dir, phase='test', device='cuda:0'):
         doc = {key: store.labels[k][store.label_offsets[k][i]:store.label_offsets[k][i + 1]].tolist() for k, key in enumerate(marks.LABEL_KEYS)}
         with open(os.path.join(out_dir, stem + '.json'), 'w') as f:
             json.dump(doc, f)
+
+
+def resample_to(cfg, out_dir, phase='test', device='cuda:0'):
+    """Write the phase's recordings at DATA.sample_rate, and their marks, into out_dir; returns the store's resample_report."""
+    _one_rank(cfg)
+    store = ResidentTianchi(cfg, phase, torch.device(device))
+    if store.source is None:
+        raise ValueError("mark_net --resample: DATA.source_rate is off (0, or DATA.sample_rate itself); there is nothing to resample")
+    _write_store(store, out_dir)
     print('resampled {recordings} recordings from {source_rate} Hz to {sample_rate} Hz ({up}/{down}, {taps} taps a phase), {adjusted} marks '
           'adjusted'.format(**store.resample_report))
     return store.resample_report
+
+
+def clean_to(cfg, out_dir, phase='test', device='cuda:0'):
+    """Write the phase's cleaned recordings (resampled first with DATA.source_rate), and their marks, into out_dir; returns the store's
+    clean_report."""
+    _one_rank(cfg)
+    if clean_plan(cfg, need_resident=False) is None:
+        raise ValueError("mark_net --clean: DATA.baseline_ms is [] and DATA.mains_hz is 0; there is nothing to clean")
+    store = ResidentTianchi(cfg, phase, torch.device(device))
+    _write_store(store, out_dir)
+    print('cleaned {recordings} recordings: median half widths {h1} and {h2}, {taps} notch taps, {launches} launches'.format(**store.clean_report))
+    return store.clean_report
 
 
 def run(argv=None):
@@ -101,6 +122,7 @@ def run(argv=None):
     what.add_argument('--compare', metavar="TABLE.json", help="compare the table's marks with the annotated test list")
     what.add_argument('--write', nargs=2, metavar=("DIR", "TABLE.json"), help="write <id>.json label files for the phase's recordings")
     what.add_argument('--resample', metavar="DIR", help="with DATA.source_rate: write the recordings at DATA.sample_rate, and their marks")
+    what.add_argument('--clean', metavar="DIR", help="with DATA.baseline_ms / DATA.mains_hz: write the cleaned recordings, and their marks")
     parser.add_argument('--form', default='ratio', choices=marks.FORMS)
     parser.add_argument('--phase', default='test', choices=('train', 'test'))
     parser.add_argument('opts', nargs=argparse.REMAINDER, help="KEY VALUE overrides")
@@ -115,6 +137,8 @@ def run(argv=None):
         return compare(cfg, args.compare)
     if args.resample:
         return resample_to(cfg, args.resample, phase=args.phase)
+    if args.clean:
+        return clean_to(cfg, args.clean, phase=args.phase)
     return write(cfg, args.write[0], args.write[1], phase=args.phase)
 
 

@@ -2541,6 +2541,84 @@ def resample(src, table, dst, taps, first, up, down, max_out_len=None, max_rows=
     return dst
 
 
+MEDIAN_TILE = 1024        # NEF_MEDIAN_TILE (include/nefnet_hip.h): outputs per workgroup of nef_sliding_median
+MEDIAN_MAX_H = 512        # NEF_MEDIAN_MAX_H
+MEDIAN_MAX_ROWS = 65535   # table rows, and signals a table row: a grid's z and y extents
+
+
+def _overlap(a, b):
+    """Two tensors whose bytes share an address."""
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def sliding_median(src, table, dst, h, minuend=None, max_len=None, max_rows=None):
+    """The sliding median of lead-major rows of `src` into `dst` (nef_sliding_median, include/nefnet_hip.h).  Every row (offset, len,
+    rows) of the int64 [N, 3] `table` names `rows` signals [rows, len] at the same offset of the flat int16 / float32 device buffer `src`,
+    of the flat float32 device buffer `dst` and of `minuend`: dst[t] = m(t), the (h + 1)-th smallest of the 2 h + 1 values
+    x[clamp(t + j, 0, len - 1)], j = -h .. h, as float32 -- NaN when the window holds one -- or, with `minuend` (flat int16 / float32, same
+    layout), float32(float64(minuend[t]) - float64(m(t))).  `dst` may be a float32 `minuend` itself; it may not overlap `src`.  `dst` is
+    written in place at the rows' positions only and returned.  A host table is checked against every buffer here and copied; a device
+    table needs `max_len` and `max_rows` (the launch is sized on the host), and a row of it that would leave a buffer writes nothing.
+    One launch on the current stream, capturable with a device table."""
+    _check_signal(src, "sliding_median")
+    if not torch.is_tensor(dst) or dst.dtype != torch.float32 or dst.dim() != 1 or dst.numel() < 1 or not dst.is_contiguous():
+        raise TypeError("dst must be a non-empty contiguous 1-D float32 tensor")
+    if not dst.is_cuda or dst.device != src.device:
+        raise ValueError(f"dst is on {dst.device}, src on {src.device}")
+    if _overlap(dst, src):
+        raise ValueError("dst overlaps src: a window reads positions that other threads write")
+    h = _mark_int("h", h, 0, MEDIAN_MAX_H)
+    dev = src.device
+    elems = min(src.numel(), dst.numel())
+    if minuend is not None:
+        if not torch.is_tensor(minuend) or minuend.dtype not in (torch.int16, torch.float32):
+            raise TypeError(f"minuend must be an int16 or float32 tensor, got {getattr(minuend, 'dtype', type(minuend))}")
+        if minuend.dim() != 1 or minuend.numel() < 1 or not minuend.is_contiguous():
+            raise ValueError(f"minuend must be a non-empty contiguous 1-D tensor, got {tuple(minuend.shape)}")
+        if not minuend.is_cuda or minuend.device != dev:
+            raise ValueError(f"minuend is on {minuend.device}, src on {dev}")
+        if minuend.data_ptr() != dst.data_ptr() and _overlap(minuend, dst):
+            raise ValueError("dst overlaps minuend without being it: an element would be written by another thread than reads it")
+        elems = min(elems, minuend.numel())
+    if not torch.is_tensor(table) or table.dtype != torch.int64:
+        raise TypeError(f"table must be an int64 tensor, got {getattr(table, 'dtype', type(table))}")
+    if table.dim() != 2 or table.shape[1] != 3 or table.shape[0] < 1 or not table.is_contiguous():
+        raise ValueError(f"table {tuple(table.shape)} is not a contiguous [rows >= 1, 3] table of (offset, len, rows)")
+    if table.shape[0] > MEDIAN_MAX_ROWS:
+        raise ValueError(f"table has {table.shape[0]} rows; a launch takes at most {MEDIAN_MAX_ROWS}")
+    if table.is_cuda:
+        if table.device != dev:
+            raise ValueError(f"table is on {table.device}, not on {dev}")
+        if max_len is None or max_rows is None:
+            raise ValueError("a device table needs max_len and max_rows: the launch is sized on the host")
+        max_len, max_rows = _mark_int("max_len", max_len, 1, MARK_MAX_LEN), _mark_int("max_rows", max_rows, 1, MEDIAN_MAX_ROWS)
+    else:
+        off, ln, rows = table[:, 0], table[:, 1], table[:, 2]
+        bad = (ln < 1) | (ln > MARK_MAX_LEN) | (rows < 1) | (rows > MEDIAN_MAX_ROWS) | (off < 0)
+        bad = bad | (off + rows.clamp(1, MEDIAN_MAX_ROWS) * ln.clamp(1, MARK_MAX_LEN) > elems)
+        if max_len is not None:
+            bad = bad | (ln > _mark_int("max_len", max_len, 1, MARK_MAX_LEN))
+        if max_rows is not None:
+            bad = bad | (rows > _mark_int("max_rows", max_rows, 1, MEDIAN_MAX_ROWS))
+        if bool(bad.any()):
+            i = int(bad.nonzero()[0, 0])
+            raise ValueError(f"table row {i} {table[i].tolist()} leaves src ({src.numel()} elements), dst ({dst.numel()}), minuend "
+                             f"({None if minuend is None else minuend.numel()}), max_len {max_len} or max_rows {max_rows}")
+        max_len = int(ln.max()) if max_len is None else max_len
+        max_rows = int(rows.max()) if max_rows is None else max_rows
+        table = table.to(dev, non_blocking=True)
+    L = _lib.load()
+    ev = _hbm("sliding_median", src, table, dst, minuend)
+    A = _lib.SlidingMedianArgs(src=_p(src), table=_p(table), dst=_p(dst), minuend=_p(minuend), src_elems=src.numel(), dst_elems=dst.numel(),
+                               minuend_elems=0 if minuend is None else minuend.numel(), max_len=max_len, N=table.shape[0],
+                               max_rows=max_rows, h=h, dtype=0 if src.dtype == torch.int16 else 1,
+                               minuend_dtype=1 if minuend is None or minuend.dtype == torch.float32 else 0, reserved0=0)
+    _lib.check(L.nef_sliding_median(C.byref(A), _stream()), "nef_sliding_median")
+    _done(ev)
+    return dst
+
+
 LOSS_SEG_TILE = 1024      # NEF_LOSS_SEG_TILE (include/nefnet_hip.h): positions per block of the two segment-weight kernels
 LOSS_SEG_MAX_ROWS = 65535  # the rows are a grid's y extent
 

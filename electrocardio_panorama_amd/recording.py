@@ -126,7 +126,8 @@ def synthesize(model, store, indices, input_leads, query_thetas=None, score_lead
     would spoil the chunk's shared activation scales -- and its output is what the stitch makes of that range (NaN, or the constant lo).
     native_rate: on a store that was resampled (DATA.source_rate) the strips are also handed back at the source rate, [A, raw_len] each
     (Synthesis.native, .native_signals: to_native_rate); the statistics are still taken at the model's rate.  On any other store it
-    changes nothing."""
+    changes nothing.  On a store that was cleaned (DATA.baseline_ms / DATA.mains_hz) the strips and the scores are in the cleaned signal's
+    units: the baseline and the hum the store removed are not put back."""
     if fill not in ops.STITCH_FILLS:
         raise ValueError(f"fill must be one of {ops.STITCH_FILLS}, got {fill!r}")
     leads = check_leads(input_leads)

@@ -54,6 +54,9 @@ def build_loaders(cfg, batch_size=32, phases=('train', 'test')):
     elif cfg.DATA.get('source_rate', 0):
         from .dataset import resident as res
         res.source_plan(cfg)                              # DATA.source_rate resamples the resident store only: ValueError
+    if not resident:
+        from . import clean
+        clean.clean_plan(cfg)                             # DATA.baseline_ms / DATA.mains_hz clean the resident store only: ValueError
     if cfg.DATA.get('synthetic', False):
         for ph in phases:
             if ph == 'train':

@@ -1329,6 +1329,49 @@ typedef struct nef_resample_args {
 int nef_resample(const nef_resample_args* a, nef_stream_t stream);
 size_t nef_resample_args_bytes(void);
 
+/* Sliding median over rows of a resident store (clean.py; dataset/resident.py: DATA.baseline_ms): the baseline estimate
+ * of a recording, or the recording minus it.  Capturable and stateless, no atomics, no scratch, one writer per element; a signal's result
+ * is a function of that signal alone.
+ *
+ * `table` holds N int64 rows [0] offset  [1] len  [2] rows: `rows` lead-major signals [rows, len] at the same offset in `src`, `dst` and
+ * `minuend`.  For every signal x and every t in [0, len) the window is the 2 h + 1 values x[clamp(t + j, 0, len - 1)], j = -h .. h (edge
+ * replication), taken as fp32.  m(t) is the (h + 1)-th smallest of them, ordered by value: -0.0 and +0.0 compare equal and either may come
+ * out, infinities order as usual, and m(t) is NaN if any value of the window is NaN (numpy.median's rule; the window is odd, so m(t) is one
+ * of its elements and nothing is averaged).
+ *   minuend NULL:   dst[t] = m(t)
+ *   else:           dst[t] = (float) ((double) minuend[t] - (double) m(t))          -- one rounding
+ * `dst` may be an fp32 `minuend` itself: each element is read and written by the one thread that owns it.  `dst` must not overlap `src`.
+ * h = 0 copies (or subtracts a value from itself).  Positions outside every row are never written.
+ *
+ * One 256-thread workgroup per (table row, signal, tile of NEF_MEDIAN_TILE outputs): the tile and h positions of halo on each side are
+ * staged in LDS once as order-preserving 32-bit keys (u ^ (sign ? ~0 : 0x80000000), -0.0 folded onto +0.0, a NaN counted) with their
+ * positions, sorted by key, and every output walks the sorted positions counting those inside its window up to h + 1; any offset alignment
+ * and any len >= 1.  A row that would leave `src`, `dst` or `minuend`, whose len is outside 1..max_len or whose rows are outside
+ * 1..max_rows (the grid covers max_rows x max_len) writes nothing; the check is inside the launch, per block.
+ * N or max_rows outside 1..65535, max_len outside 1..2^31 - 65536, h outside 0..NEF_MEDIAN_MAX_H, dtype or minuend_dtype outside {0, 1},
+ * an element count < 1: NEF_E_SHAPE; src, table or dst NULL: NEF_E_NULL; src not 16-byte aligned, table not 8-byte, dst not 4-byte,
+ * minuend not aligned to its element: NEF_E_UNSUPPORTED. */
+#define NEF_MEDIAN_TILE 1024
+#define NEF_MEDIAN_MAX_H 512
+typedef struct nef_sliding_median_args {
+    const void* src;            /* int16 or fp32 elements */
+    const int64_t* table;       /* [N, 3] */
+    float* dst;                 /* dst_elems floats */
+    const void* minuend;        /* NULL, or int16 / fp32 elements */
+    int64_t src_elems;
+    int64_t dst_elems;
+    int64_t minuend_elems;      /* read with a minuend only */
+    int64_t max_len;            /* no row is longer */
+    int32_t N;
+    int32_t max_rows;           /* no table row holds more signals */
+    int32_t h;
+    int32_t dtype;              /* of src: 0 int16, 1 fp32 */
+    int32_t minuend_dtype;      /* 0 int16, 1 fp32 */
+    int32_t reserved0;          /* 0 */
+} nef_sliding_median_args;
+int nef_sliding_median(const nef_sliding_median_args* a, nef_stream_t stream);
+size_t nef_sliding_median_args_bytes(void);
+
 /* ---------------------------------------------------------------------------------------------
  * SGD with momentum over a flat buffer.  codes/solver/optim_scheduler.py:10 (torch.optim.SGD semantics:
  * first step buf = g, afterwards buf = mu*buf + g; p -= lr*buf).  g is multiplied by gscale first

@@ -26,6 +26,13 @@ off and with DATA.source_rate = R; the second also times nef_resample alone on c
 ratio (taps in LDS) and at 500 / 257 on the same buffer (taps in global memory).  The line says whether the key-on build stays within 10 %.
 
     python tools/bench_loader.py --resident --source-rate 1000 360 [--rounds 3] [--n 2048] [--out profiles/r31_resample_bench_line.json]
+
+`--resident --clean` times DATA.baseline_ms / DATA.mains_hz (clean.py; nef_sliding_median): the tree is written with a 0.3 Hz wander and a
+50 Hz hum added to every lead, and `--rounds` alternating rounds of fresh processes build the store of those files with the keys off and
+with [200, 600] ms + 50 Hz on; the second also times, on one chunk of at most 2^25 samples behind a cache flush and with their algorithmic
+bytes, nef_sliding_median at h = 50 and h = 150 and the 1/1 511-tap nef_resample.  The line says whether the key-on build stays within 10 %.
+
+    python tools/bench_loader.py --resident --clean [--rounds 3] [--n 2048] [--out profiles/r32_clean_bench_line.json]
 """
 import argparse
 import json
@@ -44,9 +51,10 @@ import torch         # noqa: E402
 BATCHES = (32, 256)
 
 
-def make_tree(root, n, seed=0, rate=500):
+def make_tree(root, n, seed=0, rate=500, dirty=False):
     """n recordings: smooth 8-lead signals with a beat every 600..900 samples and plausible wave boundaries -- at 500 Hz; `rate` writes the
-    same ten seconds at another rate (every count of samples times rate / 500)."""
+    same ten seconds at another rate (every count of samples times rate / 500); `dirty` adds a 0.3 Hz wander of half a beat's height and a
+    50 Hz hum of a tenth to every lead."""
     rng = np.random.default_rng(seed)
     os.makedirs(os.path.join(root, "npy"), exist_ok=True)
     os.makedirs(os.path.join(root, "json"), exist_ok=True)
@@ -64,6 +72,8 @@ def make_tree(root, n, seed=0, rate=500):
             for p in p_on:
                 sig += rng.normal(1.0, 0.3, size=(8, 1)) * np.exp(-0.5 * ((t - p - c) / w) ** 2)
         sig += rng.normal(0, 0.01, size=sig.shape)
+        if dirty:
+            sig += 0.5 * np.sin(2 * np.pi * 0.3 * t / rate + 0.7) + 0.1 * np.sin(2 * np.pi * 50.0 * t / rate + 0.3)
         np.save(os.path.join(root, "npy", f"{i}.npy"), sig.astype(np.float32))
         with open(os.path.join(root, "json", f"{i}.json"), "w") as f:
             json.dump({k: v.tolist() for k, v in lab.items()}, f)
@@ -320,6 +330,88 @@ def leg_rate(a):
     return out
 
 
+def leg_clean(a):
+    """The store build with DATA.baseline_ms and DATA.mains_hz on, and the three launches alone behind a cache flush on one chunk."""
+    from electrocardio_panorama_amd import clean, ops
+    from electrocardio_panorama_amd.dataset import marks, resident
+    torch.set_num_threads(1)
+    dev = torch.device("cuda", 0)
+    cfg = tree_cfg(a.tree, a.leads)
+    cfg.DATA.device_resident, cfg.DATA.baseline_ms, cfg.DATA.mains_hz = True, [200, 600], 50.0
+    store, sec = _timed_store(cfg, dev)
+    rep = store.clean_report
+    out = {"leg": "clean", "cleaned_store_build_s": sec, "store_dtype": str(store.signal.dtype).replace("torch.", ""), "h1": rep["h1"],
+           "h2": rep["h2"], "notch_taps": rep["taps"], "launches": rep["launches"], "store_device_bytes": store.device_bytes}
+    cfg.DATA.baseline_ms, cfg.DATA.mains_hz = [], 0.0
+    raw = resident.ResidentTianchi(cfg, "train", dev)
+    a0, b0 = marks._chunks((8 * raw.lengths).tolist(), 1 << 25)[0]
+    lo, hi = int(raw.offsets[a0]), int(raw.offsets[b0])
+    src = raw.signal[lo:hi]
+    table = torch.from_numpy(np.ascontiguousarray(np.stack([raw.offsets[a0:b0] - lo, raw.lengths[a0:b0], np.full(b0 - a0, 8)], axis=1),
+                                                  dtype=np.int64)).to(dev)
+    table4 = torch.from_numpy(np.ascontiguousarray(np.stack([raw.offsets[a0:b0] - lo, raw.lengths[a0:b0], raw.offsets[a0:b0] - lo,
+                                                             np.full(b0 - a0, 8)], axis=1), dtype=np.int64)).to(dev)
+    dst, tmp = torch.empty(hi - lo, dtype=torch.float32, device=dev), torch.empty(hi - lo, dtype=torch.float32, device=dev)
+    taps, first = clean.notch_taps(500.0, 50.0)
+    taps_d, first_d = torch.from_numpy(taps).to(dev), torch.from_numpy(first).to(dev)
+    max_len = int(raw.lengths[a0:b0].max())
+    ops.sliding_median(src, table, tmp, 50, max_len=max_len, max_rows=8)
+    calls = (("median_h50", lambda: ops.sliding_median(src, table, dst, 50, max_len=max_len, max_rows=8), src.element_size() + 4),
+             ("median_h150_minus", lambda: ops.sliding_median(tmp, table, dst, 150, minuend=src, max_len=max_len, max_rows=8), 4 + src.element_size() + 4),
+             ("notch_511", lambda: ops.resample(src, table4, dst, taps_d, first_d, 1, 1, max_out_len=max_len, max_rows=8), src.element_size() + 4))
+    flush = torch.empty(512 << 20, dtype=torch.uint8, device=dev)        # larger than L2 and the Infinity Cache together
+    out["chunk_samples"] = hi - lo
+    for name, call, per_sample in calls:
+        us = []
+        for _ in range(5):
+            flush.zero_()
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            call()
+            e.record()
+            e.synchronize()
+            us.append(s.elapsed_time(e) * 1e3)
+        # algorithmic bytes: every input read once, the result written once, the table
+        nbytes = (hi - lo) * per_sample + table.numel() * 8 + (taps.nbytes + first.nbytes if name == "notch_511" else 0)
+        t = float(np.median(us[1:]))                                    # the first: code load, allocator
+        out[f"{name}_cold_us"], out[f"{name}_bytes"], out[f"{name}_tb_s"] = round(t, 2), nbytes, round(nbytes / t * 1e-6, 4)
+    return out
+
+
+def drive_clean(a):
+    """The dirty tree once, then `--rounds` alternating rounds of fresh processes: the key-off build, the key-on build."""
+    root = tempfile.mkdtemp(prefix="nef_clean_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
+    runs = []
+    try:
+        make_tree(root, a.n, dirty=True)
+        for leg in ["store", "clean"] * a.rounds:
+            cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg, "--tree", root, "--leads", str(a.leads)]
+            res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=a.leg_timeout)
+            if res.returncode != 0:
+                raise RuntimeError(f"leg {leg} ended with exit code {res.returncode}")
+            runs.append(json.loads(res.stdout.strip().splitlines()[-1]))
+            print(json.dumps(runs[-1]), flush=True)
+    finally:
+        shutil.rmtree(root, ignore_errors=True)
+    line = {"recordings": a.n, "rounds": a.rounds}
+    for key in sorted({k for r in runs for k in r}):
+        vals = [r[key] for r in runs if key in r]
+        if isinstance(vals[0], (int, float)) and len(set(vals)) > 1:
+            line[key] = [min(vals), float(np.median(vals)), max(vals)]
+        elif key != "leg":
+            line[key] = vals[0]
+    med = lambda v: v[1] if isinstance(v, list) else v      # noqa: E731
+    line["key_off_store_build_s"] = line.pop("annotated_store_build_s")
+    line["cleaned_build_over_key_off"] = round(med(line["cleaned_store_build_s"]) / med(line["key_off_store_build_s"]), 4)
+    line["cleaned_build_within_10_percent"] = bool(line["cleaned_build_over_key_off"] <= 1.10)
+    launches_ms = (med(line["median_h50_cold_us"]) + med(line["median_h150_minus_cold_us"]) + med(line["notch_511_cold_us"])) * 1e-3
+    line["launches_ms_one_chunk"] = round(launches_ms, 3)
+    print(json.dumps(line))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(line) + "\n")
+
+
 def drive_rate(a):
     """Per rate: the tree at that rate, then `--rounds` alternating rounds of fresh processes -- the key-off build, the key-on build."""
     line = {"recordings": a.n, "rounds": a.rounds, "rates": {}}
@@ -435,20 +527,26 @@ def main():
     ap.add_argument("--auto-marks", action="store_true", help="with --resident: time DATA.auto_marks against the annotated store build")
     ap.add_argument("--source-rate", type=int, nargs="+", default=[], metavar="R",
                     help="with --resident: time DATA.source_rate = R against the key-off build of the same files, per rate")
-    ap.add_argument("--leg", choices=("workers", "resident", "fit", "store", "auto", "rate"), help="(internal) one leg of --resident in this process")
+    ap.add_argument("--clean", action="store_true", help="with --resident: time DATA.baseline_ms / DATA.mains_hz against the key-off build")
+    ap.add_argument("--leg", choices=("workers", "resident", "fit", "store", "auto", "rate", "clean"), help="(internal) one leg of --resident in this process")
     ap.add_argument("--rate", type=int, default=500, help="(internal) the rate the tree of --leg rate was written at")
     ap.add_argument("--tree", default="", help="(internal) the tree --leg reads")
     a = ap.parse_args()
     if a.leg:
         if not torch.cuda.is_available():
             raise SystemExit("--resident needs a HIP device")
-        legs = {"workers": leg_workers, "resident": leg_resident, "fit": leg_fit, "store": leg_store, "auto": leg_auto, "rate": leg_rate}
+        legs = {"workers": leg_workers, "resident": leg_resident, "fit": leg_fit, "store": leg_store, "auto": leg_auto, "rate": leg_rate,
+                "clean": leg_clean}
         print(json.dumps(legs[a.leg](a)))
         return
     if a.auto_marks and not a.resident:
         raise SystemExit("--auto-marks goes with --resident: the marks are made on the device-resident store")
     if a.source_rate and (not a.resident or a.auto_marks):
         raise SystemExit("--source-rate goes with --resident alone: the recordings are resampled on the device-resident store")
+    if a.clean and (not a.resident or a.auto_marks or a.source_rate):
+        raise SystemExit("--clean goes with --resident alone: the recordings are cleaned on the device-resident store")
+    if a.resident and a.clean:
+        return drive_clean(a)
     if a.resident and a.source_rate:
         return drive_rate(a)
     if a.resident:
